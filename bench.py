@@ -12,9 +12,13 @@ rank takes its part by the deterministic longest-processing-time rule of rust-br
 -- the code the 2-rank gloo test covers -- generates the streams of its part locally (they are a function of the
 stream index: payload never crosses xGMI), decodes them on its GPU, and the per-stream status words are gathered.
 
-Prints ONE JSON line on rank 0 (contract in the task description), with these extra objects:
+Prints ONE JSON line on rank 0: metric, value (MB/s), unit, higher_is_better, dtype, ms_per_step (host clock of one timed
+step), config, command rates and
   roofline       -- HBM roofline of the decode kernel: algorithmic bytes (compressed read + decompressed written)
                     per launch / mean kernel time from HIP events on the launch stream, against 8 TB/s
+A plain run does only what that line needs: workload, first decode (status words checked), warm-up, the timed steps.
+--full adds every check and leg beside it: each output hashed (SHA-256) against the regenerated raw data before and
+after the timed steps, and on one GPU these objects:
   cpu_baseline   -- the CPU oracle ("port": the reference itself is Rust and cannot be built here) on a bounded
                     sample of the same workload: all host threads, one thread, and -- when libbrotlidec.so.1 can
                     be loaded -- Google's C decoder on one thread as a proxy for the reference (a port of it)
@@ -22,6 +26,13 @@ Prints ONE JSON line on rank 0 (contract in the task description), with these ex
                     roofline, command rates and CPU legs: C2 1024 x alice29, C4 256 x 4 MiB high-entropy literals, C3 as ONE
                     many-metablock stream (64 MiB, and 1 GiB as BASELINE writes it), the metric's streams twice (512 x 4 MiB),
                     the same data at -q9, as 1024 x 1 MiB, and at the make-up of SURVEY 8(a1)'s prototype
+  host_buffers   -- the same batch from pageable host memory and back (BrotliAmdBatchDecodeHost)
+
+--dump-outputs DIR writes what the last timed step returned to its caller (N > 1: rank 0's streams), as float64 / float32:
+  status.npy         per stream [result, error_code, decoded_size, consumed] (BrotliAmdBatchWait behind the last step)
+  output_sample.npy  decoded bytes at fixed, seeded positions: up to 8 Mi of them, spread evenly over the streams
+  output_sha256.npy  per stream the SHA-256 of its decoded bytes as eight big-endian 32-bit words (every byte compared)
+The inputs are a function of the arguments, so two builds compare output for output.
 """
 import argparse
 import ctypes
@@ -128,8 +139,9 @@ class DeviceJob:
         self.comp_total = sum(self.sizes)
         self.raw_total = sum(self.caps)
 
-    def decode_and_check(self):
-        """First decode + bit-exact check against the regenerated raw data (SHA-256 per stream) -> status rows"""
+    def decode_and_check(self, hash_outputs=True):
+        """First decode, every stream's status checked, + (hash_outputs) bit-exact check against the regenerated raw data
+        (SHA-256 per stream) -> status rows"""
         if not self.indices:
             self.second_pass = 0
             self.probe_ms = 0.0
@@ -150,11 +162,8 @@ class DeviceJob:
         bad = [j for j, r in enumerate(res) if r.result != 1 or r.decoded_size != self.caps[j]]
         if bad:
             raise SystemExit("decode failed: stream %d result %d error %d" % (self.indices[bad[0]], res[bad[0]].result, res[bad[0]].error_code))
-        host = self.d_out.cpu().numpy()
-        for j, i in enumerate(self.indices):
-            _, sz, sha = self.unique[i % len(self.unique)]
-            if hashlib.sha256(host[j * self.out_stride: j * self.out_stride + sz].tobytes()).hexdigest() != sha:
-                raise SystemExit("stream %d is not bit-exact" % i)
+        if hash_outputs:
+            self.verify("")
         return [[r.result, r.error_code, r.decoded_size, r.consumed] for r in res]
 
     def poison(self):
@@ -162,12 +171,31 @@ class DeviceJob:
         self.d_out.fill_(0xA5)
         self.torch.cuda.synchronize()
 
-    def verify(self):
+    def verify(self, when=" after the timed steps"):
         host = self.d_out.cpu().numpy()
         for j, i in enumerate(self.indices):
             _, sz, sha = self.unique[i % len(self.unique)]
             if hashlib.sha256(host[j * self.out_stride: j * self.out_stride + sz].tobytes()).hexdigest() != sha:
-                raise SystemExit("stream %d is not bit-exact after the timed steps" % i)
+                raise SystemExit("stream %d is not bit-exact%s" % (i, when))
+
+    def dump_outputs(self, out_dir, sample_total=8 << 20):
+        """What the last step returned to its caller -> out_dir/*.npy (module docstring); at most 8 Mi float32 + 12 float64 a stream"""
+        import numpy as np
+        os.makedirs(out_dir, exist_ok=True)
+        res = self.batch.wait() if self.indices else []
+        status = np.array([[r.result, r.error_code, r.decoded_size, r.consumed] for r in res], dtype=np.float64).reshape(-1, 4)
+        host = self.d_out.cpu().numpy()
+        rng = np.random.Generator(np.random.PCG64(20240601))
+        per_stream = max(1, sample_total // max(1, len(self.indices)))
+        sample, digests = [], []
+        for j, cap in enumerate(self.caps):
+            out = host[j * self.out_stride: j * self.out_stride + cap]
+            pos = np.arange(cap) if cap <= per_stream else np.sort(rng.integers(0, cap, size=per_stream))
+            sample.append(out[pos].astype(np.float32))
+            digests.append(np.frombuffer(hashlib.sha256(out.tobytes()).digest(), dtype=">u4").astype(np.float64))
+        np.save(os.path.join(out_dir, "status.npy"), status)
+        np.save(os.path.join(out_dir, "output_sample.npy"), np.concatenate(sample) if sample else np.zeros(0, np.float32))
+        np.save(os.path.join(out_dir, "output_sha256.npy"), np.array(digests, dtype=np.float64).reshape(-1, 8))
 
     def step(self):
         if not self.indices:
@@ -342,8 +370,11 @@ def main():
     ap.add_argument("--workload", default=os.environ.get("BROTLI_BENCH_WORKLOAD", "longbackref_256x4MiB"),
                     help="longbackref_256x4MiB (default, the metric's configuration), highentropy_256x4MiB, alice29x1024, "
                          "fixture:<name>x<n>, or <longbackref|highentropy>_<streams>x<size><KiB|MiB> for occupancy sweeps")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra_configs legs (C2, C4, C3 as one stream)")
+    ap.add_argument("--full", action="store_true",
+                    help="every check and leg beside the headline: outputs hashed before and after the timed steps, cpu_baseline, host_buffers, extra_configs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU legs and host_buffers")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra_configs legs (C2, C4, C3 as one stream)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy (module docstring)")
     args = ap.parse_args()
 
     import numpy as np
@@ -376,7 +407,7 @@ def main():
     mine = sharding.lpt_partition(table[:, 2], world)[rank]
 
     job = DeviceJob(pkg, torch, dev, unique, mine)
-    status_rows = job.decode_and_check()
+    status_rows = job.decode_and_check(hash_outputs=args.full)
 
     for _ in range(args.warmup):
         job.step()
@@ -392,7 +423,10 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    job.verify()
+    if args.full:
+        job.verify()
+    if args.dump_outputs and rank == 0:
+        job.dump_outputs(args.dump_outputs)
 
     # per-stream status words back to every rank (the gather of sharding.py), the step time as the maximum over ranks
     status = sharding.gather_status(np.array(status_rows, dtype=np.int64).reshape(-1, sharding.STATUS_COLS), mine, n_total, dev if world > 1 else "cpu")
@@ -423,9 +457,9 @@ def main():
         out["roofline"]["traffic_source"] = traffic_source
         if world == 1:
             out.update(command_rates(job, elapsed_max / args.steps))
-        out["config"]["outputs_poisoned_before_and_hashed_after_the_timed_steps"] = True
+        out["config"]["outputs_poisoned_before_and_hashed_after_the_timed_steps"] = args.full
     job.close()
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         if not args.no_cpu_baseline:  # (a host-side baseline: rank 0 at N = 1 only)
             out["cpu_baseline"] = cpu_baseline(unique)
             try:  # the same batch from pageable host memory and back (BrotliAmdBatchDecodeHost): PCIe-inclusive, never the `value`

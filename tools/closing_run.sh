@@ -11,7 +11,7 @@ timeout 900 tools/collect_profiles.sh ${TAG}_highentropy highentropy_256x4MiB > 
 timeout 900 tools/collect_profiles.sh ${TAG}_alice29x1024 alice29x1024 > $O/collect_c2.log 2>&1
 cd "$REPO"
 for WL in longbackref_256x4MiB highentropy_256x4MiB alice29x1024; do
-  timeout 300 python bench.py --workload $WL --steps 10 --warmup 2 --no-extra > $O/bench_$WL.txt 2>&1
+  timeout 300 python bench.py --workload $WL --steps 10 --warmup 2 --full --no-extra > $O/bench_$WL.txt 2>&1
 done
 if [ -f tools/scratch/lib_scanprof.so ]; then
   for WL in longbackref_256x4MiB highentropy_256x4MiB; do
@@ -21,6 +21,6 @@ fi
 if [ -f tools/scratch/lib_waveprof.so ]; then
   BROTLI_AMD_LIB=tools/scratch/lib_waveprof.so timeout 300 python bench.py --workload longbackref_256x4MiB --steps 2 --warmup 1 --no-cpu-baseline --no-extra > $O/waves_longbackref_256x4MiB.txt 2>&1
 fi
-( time timeout 900 python bench.py ) > $O/bench_default.json 2> $O/bench_default.err
+( time timeout 900 python bench.py --full ) > $O/bench_default.json 2> $O/bench_default.err
 tail -1 $O/bench_default.json | cut -c1-600
 tail -4 $O/bench_default.err
