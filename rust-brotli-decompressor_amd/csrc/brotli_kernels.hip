@@ -474,11 +474,6 @@ struct Stream {
 #endif
 };
 
-#ifdef BROTLI_AMD_NO_COLD_UNIFORM
-#define COLD_UNIFORMIZE(x)
-#else
-#define COLD_UNIFORMIZE(x) x
-#endif
 #ifdef BROTLI_AMD_TRACE
 #define TRACE_STOP(br, e) do { if (lane_id() == 0) printf("stop line %d e=%d pos=%llu total=%llu\n", __LINE__, (int)(e), (unsigned long long)(br).pos(), (unsigned long long)(br).total_bits()); } while (0)
 #else
@@ -765,7 +760,7 @@ __device__ __noinline__ int read_huffman_code(Stream& s, uint32_t alphabet_size,
 #endif
   struct Scope {  // register copies of the reader and the arena, stored back on every exit
     Stream& s; BitReader br; Arena ar;
-    __device__ __forceinline__ Scope(Stream& s_) : s(s_), br(s_.br), ar(s_.ar) { COLD_UNIFORMIZE(br.uniformize(); ar.uniformize();) }
+    __device__ __forceinline__ Scope(Stream& s_) : s(s_), br(s_.br), ar(s_.ar) { br.uniformize(); ar.uniformize(); }
     __device__ __forceinline__ ~Scope() { s.br = br; s.ar = ar; }
   } sc(s);
   BitReader& br = sc.br;
@@ -852,16 +847,14 @@ __device__ __noinline__ int read_huffman_code(Stream& s, uint32_t alphabet_size,
     // symbol code lengths (decode.rs:661-797, 558-658)
     uint32_t symbol = 0, prev_code_len = 8, repeat = 0, repeat_code_len = 0;
     space = 32768;
-#ifndef BROTLI_AMD_SERIAL_LENGTHS
     if (num_codes != 1) {
       LengthsOut lo_;
       const int e_ = rfl(read_symbol_lengths_wide(&br, cl_table, max_symbol, &lo_));
-      COLD_UNIFORMIZE(br.uniformize();)
+      br.uniformize();
       if (e_ == E_NEEDS_MORE_INPUT) { NEED_INPUT(br); return E_NEEDS_MORE_INPUT; }
       if (e_ != E_SUCCESS) FAIL(br, e_);
       symbol = max_symbol; space = rfl(lo_.space);   // (the loop below has nothing left to do)
     }
-#endif
     while (symbol < max_symbol && space > 0) {
       uint32_t p = rdlane(cl_table, br.peek32() & 31u);
       uint32_t code_len = p >> 4;
@@ -909,12 +902,12 @@ __device__ __noinline__ int read_huffman_code(Stream& s, uint32_t alphabet_size,
 // go through the Stream object in memory.
 struct ColdScope {
   Stream& s; BitReader br;
-  __device__ __forceinline__ ColdScope(Stream& s_) : s(s_), br(s_.br) { COLD_UNIFORMIZE(br.uniformize();) }
+  __device__ __forceinline__ ColdScope(Stream& s_) : s(s_), br(s_.br) { br.uniformize(); }
   __device__ __forceinline__ ~ColdScope() { s.br = br; }
   __device__ __forceinline__ int huffman(uint32_t alphabet, uint32_t max_symbol, uint32_t* tree, bool cold = false) {
     s.br = br;
     int e = rfl(read_huffman_code(s, alphabet, max_symbol, tree, cold));
-    br = s.br; COLD_UNIFORMIZE(br.uniformize(); *tree = rfl(*tree);)
+    br = s.br; br.uniformize(); *tree = rfl(*tree);
     return e;
   }
 };
@@ -1171,11 +1164,11 @@ __device__ __forceinline__ uint32_t dictionary_word_bytes(gcu8* dict, uint32_t o
 //   helper's answer, round moved.
 enum { HC_SEQ = 0, HC_KIND = 1, HC_DW0 = 2, HC_SHIFT = 3, HC_TREE = 4, HC_BASE = 5, HC_NW = 6, HC_OUT_LO = 7, HC_OUT_HI = 8, HC_CAPPED = 9, HC_FAILED = 10,
        HC_SCAN_BASE = 11 /* LDS base of the command engine (brotli_scan_engine.h); 0 = this block has none */, HC_NW_ALL = 12 /* waves in the block */,
-       HC_EXT_BASE = 13 /* LDS base of the command-record ring of the parse / copy split (SPX_BYTES, in the free tail of the table arena); 0 = this metablock has none */,
+       HC_EXT_BASE = 13 /* LDS base of the command-record ring (SPX_BYTES, in the free tail of the table arena); 0 = this metablock has none */,
        // a gang of blocks on one stream (see GC_* below): this block's number in it (0: the stream's owner), the gang's blocks, its control block in memory,
        // the owner's count of the engine's invocations (a helper's: the last one it has seen), the bytes of the table arena in use
        HC_GANG_ROLE = 14, HC_GANG_M = 15, HC_GANG_LO = 16, HC_GANG_HI = 17, HC_GANG_EPOCH = 18, HC_GANG_READY = 19 /* the owner's: what the control block's READY says when the helpers of every invocation so far have left */ };
-enum { HK_ROUND = 1, HK_EXIT = 2, HK_NO_ROUNDS = 3, HK_SCAN = 4, HK_PATH = 5, HK_SPLIT = 6, HK_PATH2 = 7, HK_PATHG = 8, HK_PATHR = 9 };  // HC_KIND
+enum { HK_ROUND = 1, HK_EXIT = 2, HK_NO_ROUNDS = 3, HK_SCAN = 4, HK_PATH = 5, HK_RECORDS = 6, HK_PATHG = 8, HK_PATHR = 9 };  // HC_KIND
 enum { HW_DONE = 0, HW_N = 1, HW_EXIT = 2, HW_MVGO = 3, HW_MVSRC = 4, HW_MVDST_LO = 5, HW_MVDST_HI = 6, HW_MVN = 7, HW_MVDONE = 8,
        // a helper's own account of how the chain of the chunk before (entered where that chunk's chain ends) falls in
        // with its own: round resolved, fell in (1/0), literals of that chain before it did, the helper's literals before
@@ -1388,53 +1381,23 @@ __device__ __noinline__ void spec_chunk(uint32_t w, uint32_t dw0, uint32_t sh, u
 __device__ __noinline__ uint32_t scan_engine(const uint32_t me_);
 namespace pe16 { __device__ __noinline__ uint32_t path_engine(const uint32_t me_); }   // one engine of sixteen waves, the lean form: no words of the static dictionary
 namespace pe16g { __device__ __noinline__ uint32_t path_engine(const uint32_t me_); }  // ... the general form
-namespace pe8 { __device__ __noinline__ uint32_t path_engine(const uint32_t me_); }    // two engines of eight, regions in turns
 #ifdef BROTLI_AMD_GANG_KERNEL
 namespace pe16r { __device__ __noinline__ uint32_t path_engine(const uint32_t me_); }  // one engine of sixteen a block, the blocks of a gang taking the regions in turns
 #endif
-// which command engine blocks of sixteen waves use: 0 = the path engine where it applies (brotli_path_engine.h), 1 = the scan
-// engine only (experiments, A/B tests: BROTLI_AMD_ENGINE=scan)
-__device__ uint32_t g_engine_mode = 2;
+// what the decoding takes (A/B tests, BROTLI_AMD_ENGINE: see brotli_amd_launch_decode); 0 = everything where it applies
+__device__ uint32_t g_engine_mode = 0;
 
 
-// ===================================== parse / copy split (context-modelled metablocks) =====================================
-// A metablock whose literals depend on context cannot be parsed ahead of its output by more than the output allows: the
-// tree of a literal is a function of the two bytes before it (decode.rs:2463-2551), which after a copy come out of the
-// output.  What CAN leave the decoding wave is everything that moves bytes (decode.rs:2641-2720): in a block with helper
-// waves the decoding wave only PARSES such a metablock (lean_split_commands) and leaves one 16-byte record per command in
-// an LDS ring -- literals (bytes in a second ring), copy length, resolved distance -- and wave 1 of the block EXECUTES
-// the records in order: literal stores, LZ77 loads and stores.  The parser never waits for a store; the two context
-// bytes behind a copy are fetched from the copy's SOURCE (out[P - dist + n - 2 ..], asked for when the distance is
-// known, used a command later) once the copier says that part of the output is in memory, else the parser waits for
-// the copier to catch up.  Everything the lean loop does not take (limits, dictionary words, block switches) ends the
-// split: the parser waits until the ring is drained and goes through the checked stages as before.
-//   control words (CW_*, in the body of wave slot 3; the record ring is the body of slot 1, the literal ring of slot 2 --
-//   the literal rounds that own these slots never run inside a context-modelled metablock):
-//   records posted (parser), records / literal bytes taken out of the rings, records whose stores have completed and the
-//   output position below which everything is in memory (copier), stop request / acknowledgement, output address.
-enum { CW_HEAD = 0, CW_TAIL = 1, CW_LIT_TAIL = 2, CW_DONE_SEQ = 3, CW_DONE_P = 4, CW_STOP = 5, CW_OUT_LO = 6, CW_OUT_HI = 7, CW_WORDS = 8 };
-enum { SPR_COPY = 0, SPR_SETP = 1 };  // record kinds: literals + copy; the copier's output position (the parser came back from the checked stages)
-constexpr uint32_t SP_RECS = 64u, SP_LIT_BYTES = 1024u;
-constexpr uint32_t SP_MAX_INSERT = 256u;      // longer literal runs go through the checked stages
-constexpr uint32_t SP_MIN_MLEN = 4096u;       // smaller metablocks are not worth waking the copier for
-constexpr uint32_t SP_SPIN_CAP = 1u << 24;    // polls of the parser before it gives the stream up (never seen)
-static_assert(SP_RECS * 16u <= HL_SLOT - HL_MASK && SP_LIT_BYTES <= HL_SLOT - HL_MASK, "the rings live in the bodies of wave slots");
-__device__ __forceinline__ uint32_t sp_rec_base() { return hc_ld(HC_BASE) + HL_SLOT + HL_MASK; }
-__device__ __forceinline__ uint32_t sp_lit_base() { return hc_ld(HC_BASE) + 2u * HL_SLOT + HL_MASK; }
-__device__ __forceinline__ uint32_t sp_ctl_base() { return hc_ld(HC_BASE) + 3u * HL_SLOT + HL_MASK; }
+// ===================================== helper waves of a metablock: command records =====================================
+constexpr uint32_t SP_MIN_MLEN = 4096u;       // smaller metablocks are not worth waking the helper waves for
+constexpr uint32_t SP_SPIN_CAP = 1u << 24;    // polls of the decoding wave before it gives a helper wave up (never seen)
 __device__ __forceinline__ uint32_t sp_ld(uint32_t ctl, uint32_t k) { return rfl(*reinterpret_cast<lds_vu32*>(&g_smem[ctl + 4u * k])); }
 __device__ __forceinline__ void sp_st(uint32_t ctl, uint32_t k, uint32_t v) { if (lane_id() == 0) *reinterpret_cast<lds_vu32*>(&g_smem[ctl + 4u * k]) = v; }
 #ifdef BROTLI_AMD_PROFILE_SPLIT
 __device__ unsigned long long g_split_prof[40];
-#define SPLIT_PROF(k, t0) do { if (blockIdx.x == 0 && lane_id() == 0) g_split_prof[k] += __builtin_amdgcn_s_memtime() - (t0); } while (0)
-#define SPLIT_COUNT(k, v) do { if (blockIdx.x == 0 && lane_id() == 0) g_split_prof[k] += (v); } while (0)
-#define SPLIT_T() __builtin_amdgcn_s_memtime()
 #define SPLIT_LAP(k) do { const uint64_t t_ = __builtin_amdgcn_s_memtime(); lap_acc[k] += t_ - lap_t; lap_t = t_; } while (0)
 #else
 #define SPLIT_LAP(k) do { } while (0)
-#define SPLIT_PROF(k, t0) do { (void)(t0); } while (0)
-#define SPLIT_COUNT(k, v) do { } while (0)
-#define SPLIT_T() 0ull
 #endif
 
 
@@ -1459,93 +1422,6 @@ enum : uint32_t { XR_VALID = 1u << 23, XR_LITERALS = 1u << 24, XR_IMPLICIT = 1u 
        XR_NOT_RUN = 1u << 31 /* not a record the hand-written run takes: not valid, or a copy of more than 63 bytes (its tests are one sign test) */ };
 __device__ __noinline__ void rec_wave();
 
-// Wave 1 of the block while the decoding wave parses a context-modelled metablock.
-__device__ __noinline__ void copier_wave() {
-  const uint32_t lane = lane_id();
-  const uint32_t rec = sp_rec_base(), lit = sp_lit_base(), ctl = sp_ctl_base();
-  gu8* const out = (gu8*)(uintptr_t)((uint64_t)sp_ld(ctl, CW_OUT_LO) | ((uint64_t)sp_ld(ctl, CW_OUT_HI) << 32));
-  uint64_t P = 0;
-  uint32_t tail = 0, lit_tail = 0, idle = 0;
-  bool quiet = false;
-  for (;;) {
-    const uint32_t head = sp_ld(ctl, CW_HEAD);
-    if (head == tail) {
-      if (!quiet) {  // nothing to do: everything so far is in memory once the stores have been acknowledged
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        sp_st(ctl, CW_DONE_P, (uint32_t)P);
-        lds_release();
-        sp_st(ctl, CW_DONE_SEQ, tail);
-        quiet = true;
-      }
-      if (sp_ld(ctl, CW_STOP) != 0u) break;
-      // (a SIMD issues one scalar instruction every four clocks for ALL its waves, and the parser of another block lives on
-      // this one: a poll every 64 clocks took a third of them)
-      idle++;
-      if (idle < 16u) __builtin_amdgcn_s_sleep(4); else __builtin_amdgcn_s_sleep(16);
-      continue;
-    }
-    const uint64_t busy_t0 = SPLIT_T();
-    idle = 0; quiet = false;
-    lds_acquire();
-    while (tail != head) {
-      uint32_t w = 0;
-      if (lane < 4u) w = lds_ld32(rec + ((tail & (SP_RECS - 1u)) << 4) + 4u * lane);
-      const uint32_t w0 = rdlane(w, 0), w1 = rdlane(w, 1), w2 = rdlane(w, 2), w3 = rdlane(w, 3);
-      tail++;
-      if ((w0 & 0xFFu) == (uint32_t)SPR_SETP) {
-        P = (uint64_t)w1 | ((uint64_t)w2 << 32);
-        sp_st(ctl, CW_TAIL, tail);
-        continue;
-      }
-      const uint32_t ins = w0 >> 8;
-      for (uint32_t k = 0; k < ins; k += 64u) {
-        if (k + lane < ins) { const uint32_t b = lds_ld8(lit + ((w3 + k + lane) & (SP_LIT_BYTES - 1u))); out[P + k + lane] = (uint8_t)b; }
-      }
-      P += ins;
-      lit_tail += ins;
-      if (lane == 0) {  // the ring entries are free again (LDS operations of a wave execute in order: the reads above are done)
-        *reinterpret_cast<lds_vu32*>(&g_smem[ctl + 4u * CW_LIT_TAIL]) = lit_tail;
-        *reinterpret_cast<lds_vu32*>(&g_smem[ctl + 4u * CW_TAIL]) = tail;
-      }
-      // ---- the copy: chunks of up to 64 lanes; a chunk reads what lies `span` bytes before it, a multiple of the distance that
-      // is at least the chunk's length (a copy that overlaps itself repeats its first `dist` bytes: decode.rs:2641-2720) ----
-      uint32_t rem = w1, span = w2, done = 0;
-      const uint32_t dist = w2;
-      uint64_t dst = P;
-      bool first = true;
-      while (rem != 0u) {
-        uint32_t bytes;
-        if (span >= 64u && rem >= 16u) {
-          uint32_t n16 = rem >> 4;
-          if (n16 > 64u) n16 = 64u;
-          if (n16 > (span >> 4)) n16 = span >> 4;
-          bytes = n16 << 4;
-          u32x4 v = {0, 0, 0, 0};
-          if (lane < n16) v = *reinterpret_cast<gu32x4*>(out + dst - span + (uint64_t)lane * 16u);
-          asm volatile("s_waitcnt vmcnt(0)" : "+v"(v) :: "memory");
-          if (first) { sp_st(ctl, CW_DONE_P, (uint32_t)P); sp_st(ctl, CW_DONE_SEQ, tail - 1u); first = false; }
-          if (lane < n16) *reinterpret_cast<gu32x4*>(out + dst + (uint64_t)lane * 16u) = v;
-        } else {
-          bytes = rem < 64u ? rem : 64u;
-          if (bytes > span) bytes = span;
-          uint32_t b = 0;
-          if (lane < bytes) b = (out + dst - span)[lane];
-          asm volatile("s_waitcnt vmcnt(0)" : "+v"(b) :: "memory");
-          if (first) { sp_st(ctl, CW_DONE_P, (uint32_t)P); sp_st(ctl, CW_DONE_SEQ, tail - 1u); first = false; }
-          if (lane < bytes) (out + dst)[lane] = (uint8_t)b;
-        }
-        dst += bytes; rem -= bytes; done += bytes;
-        while (span < 64u && done + dist >= 2u * span) span <<= 1;
-      }
-      P = dst;
-      SPLIT_COUNT(12, 1);
-    }
-    SPLIT_PROF(5, busy_t0);
-  }
-  lds_release();
-  sp_st(ctl, CW_STOP, 2u);
-}
-
 __device__ __noinline__ void helper_wave(const uint32_t me /* 1 .. waves - 1 */, gu8* scratch_sym) {
   const uint32_t lane = lane_id();
   const uint32_t slot = hc_ld(HC_BASE) + me * HL_SLOT;
@@ -1566,12 +1442,11 @@ __device__ __noinline__ void helper_wave(const uint32_t me /* 1 .. waves - 1 */,
     if (kind == HK_SCAN) { scan_engine(me); continue; }  // every wave of the block runs the command engine
     if (kind == HK_PATH) { seq = rfl(pe16::path_engine(me)); continue; }   // (back with the last request it answered: see there)
     if (kind == HK_PATHG) { seq = rfl(pe16g::path_engine(me)); continue; }
-    if (kind == HK_PATH2) { seq = rfl(pe8::path_engine(me)); continue; }
 #ifdef BROTLI_AMD_GANG_KERNEL
     if (kind == HK_PATHR) { seq = rfl(pe16r::path_engine(me)); continue; }
 #endif
-    if (kind == HK_SPLIT) {  // a context-modelled metablock: wave 1 copies (if asked to), wave 2 parses command records; the others go back to sleep
-      if (rfl(me) == 1u && (g_engine_mode & 2u) == 0u) copier_wave(); else if (rfl(me) == 2u && hc_ld(HC_EXT_BASE) != 0u) rec_wave();
+    if (kind == HK_RECORDS) {  // a metablock with command records: wave 2 parses them; the others go back to sleep
+      if (rfl(me) == 2u && hc_ld(HC_EXT_BASE) != 0u) rec_wave();
       continue;
     }
     if (kind != HK_ROUND) return;
@@ -1786,7 +1661,7 @@ enum { L_BUF_LO, L_BUF_HI, L_CNT, L_NEXT_DW, L_ISSUED, L_END_DW, L_P_LO, L_P_HI,
        L_D3, L_NCMD_LO, L_NCMD_HI, L_CMD_TREE, L_LIT_TREE, L_DT0, L_DT1, L_DT2, L_DT3, L_MAX_BACKWARD, L_POSTFIX, L_NUM_DIRECT, L_OUT_LO,
        L_OUT_HI, L_INSERT, L_COPY, L_DCODE, L_DCTX, L_LITS_LEFT, L_P1, L_P2, L_CTX_REGS, L_TRIVIAL, L_CTX_LUT, L_CHUNK_BASE, L_SPEC_LO, L_SPEC_HI, L_COUNT };
 static_assert(L_COUNT * 4 <= 192, "LDS_LEAN too small");
-// (parse / copy split and command records, see copier_wave / rec_wave)
+// (command records, see rec_wave)
 enum { L_SP_HEAD = L_COUNT, L_SP_LIT = L_COUNT + 1, L_SP_ORIGIN = L_COUNT + 2 /* dword the record ring's positions count from */,
        L_SP_REC = L_COUNT + 3 /* command records (rec_wave) in use */, L_SP_WAITED = L_COUNT + 4 /* why the record loop left: 1 wave 2's records were not there yet, 2 a command with more than 63 literals or a copy of more than 63 bytes, 0 anything else */,
        L_SP_COUNT = L_COUNT + 5 };
@@ -2040,9 +1915,6 @@ __device__ __noinline__ void spec_rounds(uint32_t tree_addr) {
 
 #include "brotli_scan_engine.h"
 #define PE_CFG_NS pe16
-#define PE_CFG_WAVES 16
-#define PE_CFG_RBL 32768
-#define PE_CFG_PIPE 0
 #define PE_CFG_DICT 0
 #define PE_CFG_REMOTE 0
 #include "brotli_path_engine.h"
@@ -2060,26 +1932,8 @@ __device__ __noinline__ void spec_rounds(uint32_t tree_addr) {
 #define PE_CFG_REMOTE 1
 #include "brotli_path_engine.h"
 #undef PE_CFG_NS
-#undef PE_CFG_REMOTE
-#define PE_CFG_REMOTE 0
-#else
-#define PE_CFG_DICT 0
+#undef PE_CFG_DICT
 #endif
-#undef PE_CFG_WAVES
-#undef PE_CFG_RBL
-#undef PE_CFG_PIPE
-#undef PE_CFG_DICT
-#define PE_CFG_NS pe8
-#define PE_CFG_WAVES 8
-#define PE_CFG_RBL 16384
-#define PE_CFG_PIPE 1
-#define PE_CFG_DICT 0
-#include "brotli_path_engine.h"
-#undef PE_CFG_NS
-#undef PE_CFG_WAVES
-#undef PE_CFG_RBL
-#undef PE_CFG_PIPE
-#undef PE_CFG_DICT
 #undef PE_CFG_REMOTE
 using pe16::PE_MIN_INPUT;
 
@@ -2811,317 +2665,6 @@ __device__ __noinline__ __attribute__((aligned(256))) uint32_t lean_rec_commands
   return rfl(stage);
 }
 
-// ===================================== split lean loop: the parser =====================================
-// lean_commands<false> without the part that moves bytes (see "parse / copy split" above): the same stages, the same
-// hand-over to process_commands (L_STAGE ...), but a command that stays clear of every limit becomes a record for the
-// copier wave.  Returns with the ring drained: whatever the records produced is in memory.
-#define SP_CTX_REG "v125"
-__device__ __noinline__ __attribute__((aligned(256))) uint32_t lean_split_commands(uint32_t lut_vgpr, uint32_t ctx_tree_v) {
-  const uint32_t lane = lane_id();
-  const Arena a = {nullptr, 0xFFFFFFFFu, 0u};
-  BitReader br;
-  br.buf = (uint64_t)LEAN_LD(L_BUF_LO) | ((uint64_t)LEAN_LD(L_BUF_HI) << 32);
-  br.cnt = LEAN_LD(L_CNT); br.next_dw = LEAN_LD(L_NEXT_DW); br.issued_half = LEAN_LD(L_ISSUED); br.end_dw = LEAN_LD(L_END_DW);
-  br.chunk_base = LEAN_LD(L_CHUNK_BASE); br.cur = lds_ld32(LDS_LEANWIN + 4u * lane);
-  gu8* const out = (gu8*)(uintptr_t)((uint64_t)LEAN_LD(L_OUT_LO) | ((uint64_t)LEAN_LD(L_OUT_HI) << 32));
-  uint64_t P = (uint64_t)LEAN_LD(L_P_LO) | ((uint64_t)LEAN_LD(L_P_HI) << 32);
-  uint32_t quota = LEAN_LD(L_QUOTA);
-  int32_t mlen = (int32_t)LEAN_LD(L_MLEN);
-  uint32_t bl0 = LEAN_LD(L_BL0), bl1 = LEAN_LD(L_BL1), bl2 = LEAN_LD(L_BL2);
-  int32_t d0 = (int32_t)LEAN_LD(L_D0), d1 = (int32_t)LEAN_LD(L_D1), d2 = (int32_t)LEAN_LD(L_D2), d3 = (int32_t)LEAN_LD(L_D3);
-  uint32_t ncmd = 0;
-  const uint32_t cmd_tree = LEAN_LD(L_CMD_TREE), lit_tree = LEAN_LD(L_LIT_TREE);
-  const uint32_t dt0 = LEAN_LD(L_DT0), dt1 = LEAN_LD(L_DT1), dt2 = LEAN_LD(L_DT2), dt3 = LEAN_LD(L_DT3);
-  const int32_t max_backward = (int32_t)LEAN_LD(L_MAX_BACKWARD);
-  const uint32_t postfix_bits = LEAN_LD(L_POSTFIX), num_direct = LEAN_LD(L_NUM_DIRECT);
-  const bool dlut_ok = postfix_bits == 0u && num_direct == 16u;
-  uint32_t dlut;
-  {
-    const uint32_t dv = (lane - 16u) & 63u, nb = (dv >> 1) + 1u;
-    dlut = nb | ((((2u + (dv & 1u)) << nb) - 3u) << 5);
-  }
-  const uint32_t safe_dw = br.end_dw > 72u ? br.end_dw - 72u : 0u;
-  uint32_t lit_reg = 0, lit_n = 0;
-  uint32_t p1 = LEAN_LD(L_P1), p2 = LEAN_LD(L_P2);
-  // where the two bytes before P are: p1/p2 (ctx_regs), on their way from the last copy's source into SP_CTX_REG (ctx_pend),
-  // or in memory once the copier has caught up
-  bool ctx_regs = LEAN_LD(L_CTX_REGS) != 0u, ctx_pend = false;
-  const uint32_t trivial = LEAN_LD(L_TRIVIAL), ctx_lut = LEAN_LD(L_CTX_LUT);
-  const uint32_t lut0v = lds_ld32(ctx_lut + 4u * lane), lut1v = lds_ld32(ctx_lut + 256u + 4u * lane);
-  const uint32_t sp_rec = sp_rec_base(), sp_lit = sp_lit_base(), sp_ctl = sp_ctl_base();
-  uint32_t sp_head = LEAN_LD(L_SP_HEAD), lit_head = LEAN_LD(L_SP_LIT);
-  uint32_t sp_tail_c = sp_ld(sp_ctl, CW_TAIL), lit_tail_c = sp_ld(sp_ctl, CW_LIT_TAIL);
-  uint32_t failed = 0;
-  uint32_t stage = LS_BEGIN;
-  int32_t insert_len = 0, copy_len = 0, distance_code = 0;
-  uint32_t distance_context = 0, lits_left = 0;
-  uint32_t rec_ins = 0, rec_lit = lit_head;  // literals decoded but not posted yet, and where their bytes start in the ring
-  // command records (rec_wave): positions are stream bits from dword origin_dw; front_c: positions below have a record
-  const uint32_t xb = hc_ld(HC_EXT_BASE), xring = xb + SPX_CTL_BYTES;
-  const bool rec_on = LEAN_LD(L_SP_REC) != 0u;
-  const uint32_t origin_bits = LEAN_LD(L_SP_ORIGIN) << 5;
-  uint32_t my_epoch = 0, front_c = 0;
-  typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-  u32x2 rec_v = {0u, 0u};
-  bool rec_ok = false;
-  if (rec_on) {
-    // the prefix codes the records are parsed with: new ones (the first time, after a block switch) start a new epoch
-    my_epoch = sp_ld(xb, XW_EPOCH);
-    const bool same = my_epoch != 0u && sp_ld(xb, XW_CMD_TREE) == LDS_FIXED + cmd_tree && sp_ld(xb, XW_DT0) == LDS_FIXED + dt0 && sp_ld(xb, XW_DT0 + 1) == LDS_FIXED + dt1 &&
-                      sp_ld(xb, XW_DT0 + 2) == LDS_FIXED + dt2 && sp_ld(xb, XW_DT0 + 3) == LDS_FIXED + dt3;
-    sp_st(xb, XW_POS, br.next_dw * 32u - br.cnt - origin_bits);
-    if (!same) {
-      sp_st(xb, XW_CMD_TREE, LDS_FIXED + cmd_tree); sp_st(xb, XW_DT0, LDS_FIXED + dt0); sp_st(xb, XW_DT0 + 1, LDS_FIXED + dt1);
-      sp_st(xb, XW_DT0 + 2, LDS_FIXED + dt2); sp_st(xb, XW_DT0 + 3, LDS_FIXED + dt3);
-      sp_st(xb, XW_POSTFIX, postfix_bits); sp_st(xb, XW_NUM_DIRECT, num_direct);
-      my_epoch++;
-      lds_release();
-      sp_st(xb, XW_EPOCH, my_epoch);
-    }
-  }
-  // ask for the record of the command that starts where the reader stands (looked at when the command is begun)
-#define SP_REC_REQUEST() do { rec_ok = false; \
-    if (rec_on) { const uint32_t rel_ = br.next_dw * 32u - br.cnt - origin_bits; \
-      if ((ncmd & 3u) == 0u) sp_st(xb, XW_POS, rel_); \
-      if (rel_ < 0x40000000u) { \
-        if (rel_ >= front_c) { const uint64_t f_ = *reinterpret_cast<volatile __attribute__((address_space(3))) uint64_t*>(&g_smem[xb + 4u * XW_FRONT]); \
-          front_c = rfl((uint32_t)(f_ >> 32)) == my_epoch ? rfl((uint32_t)f_) : 0u; lds_acquire(); SPLIT_COUNT(14, 1); } \
-        if (rel_ < front_c) { rec_v = *reinterpret_cast<__attribute__((address_space(3))) const u32x2*>(&g_smem[xring + ((rel_ & sp_ld(xb, XW_RING_MASK)) << 3)]); rec_ok = true; } } } } while (0)
-
-  // one record: lane 0 writes its four words, then the head (LDS operations of a wave execute in order)
-#define SP_POST(W0_, W1_, W2_, W3_) do { \
-    if (sp_head - sp_tail_c >= SP_RECS - 1u) { const uint64_t t_ = SPLIT_T(); uint32_t spins_ = 0; \
-      do { __builtin_amdgcn_s_sleep(1); sp_tail_c = sp_ld(sp_ctl, CW_TAIL); if (++spins_ > SP_SPIN_CAP) { failed = 1; break; } } while (sp_head - sp_tail_c >= SP_RECS - 1u); \
-      SPLIT_PROF(0, t_); } \
-    const u32x4 wv_ = {(uint32_t)(W0_), (uint32_t)(W1_), (uint32_t)(W2_), (uint32_t)(W3_)}; \
-    const uint32_t ra_ = sp_rec + ((sp_head & (SP_RECS - 1u)) << 4); \
-    sp_head++; \
-    asm volatile("" ::: "memory");  /* (the literal bytes are written; no hardware wait: DS operations stay in order) */ \
-    if (lane == 0) { *reinterpret_cast<__attribute__((address_space(3))) u32x4*>(&g_smem[ra_]) = wv_; \
-                     asm volatile("" ::: "memory"); \
-                     *reinterpret_cast<lds_vu32*>(&g_smem[sp_ctl + 4u * CW_HEAD]) = sp_head; } } while (0)
-  // the copier has executed every record and its stores have completed
-#define SP_DRAIN() do { const uint64_t t_ = SPLIT_T(); uint32_t spins_ = 0; \
-    while (sp_ld(sp_ctl, CW_DONE_SEQ) != sp_head) { __builtin_amdgcn_s_sleep(1); if (++spins_ > SP_SPIN_CAP) { failed = 1; break; } } \
-    lds_acquire(); SPLIT_PROF(1, t_); } while (0)
-  // literals collected in lit_reg go to the literal ring
-#define SP_LIT_FLUSH() do { if (lit_n) { if (lane < lit_n) lds_st8(sp_lit + ((lit_head + lane) & (SP_LIT_BYTES - 1u)), lit_reg); lit_head += lit_n; lit_n = 0; } } while (0)
-
-  const uint64_t split_t0 = SPLIT_T();
-  SP_POST(SPR_SETP, (uint32_t)P, (uint32_t)(P >> 32), 0u);
-
-  br.need32();
-  uint32_t next_root = lds_ld16(LDS_FIXED + cmd_tree + (((uint32_t)br.buf & 0xFFu) << 1));
-  SP_REC_REQUEST();
-
-  // a distance symbol 1..15: one of the last four distances, +- up to 3 (TakeDistanceFromRingBuffer, decode.rs:2017-2049)
-  auto ring_distance = [&](uint32_t code) -> int32_t {
-    const uint32_t sh = code << 1;
-    const uint32_t back = 3u - ((0xaaafff1bu >> sh) & 3u);
-    int32_t v = back == 0 ? d0 : back == 1 ? d1 : back == 2 ? d2 : d3;
-    const int32_t mag = (int32_t)((0xfa5fa500u >> sh) & 3u);
-    if (code & 1u) v += mag;
-    else { v -= mag; if (v <= 0) v = 0x7fffffff; }
-    return v;
-  };
-
-#ifdef BROTLI_AMD_PROFILE_SPLIT
-  uint64_t lap_acc[6] = {0, 0, 0, 0, 0, 0}; uint64_t lap_t = __builtin_amdgcn_s_memtime();
-#endif
-  for (;;) {
-    SPLIT_LAP(5);
-    if (bl1 == 0 || br.next_dw >= safe_dw || failed) { stage = LS_BEGIN; break; }
-    // how far the copier's stores have got (asked for now, looked at when this command's distance is known)
-    const uint32_t done_v = *reinterpret_cast<lds_vu32*>(&g_smem[sp_ctl + 4u * CW_DONE_P]);
-    bool have_dist = false;
-    uint32_t rec_lo = 0, rec_hi = 0;
-    if (rec_ok) { rec_lo = rfl(rec_v.x); rec_hi = rfl(rec_v.y); }
-    // a record that is the exact parse of this position (an explicit distance needs its block count)
-    if ((rec_lo & XR_VALID) != 0u && ((rec_lo & (XR_LITERALS | XR_IMPLICIT)) != 0u || bl2 != 0u)) {
-      SPLIT_COUNT(15, 1);
-      copy_len = (int32_t)(rec_lo & 0xFFFFu);
-      distance_context = (rec_lo >> XR_DCTX_SHIFT) & 3u;
-      distance_code = (rec_lo & XR_IMPLICIT) ? 0 : -1;
-      insert_len = 0;
-      if (rec_lo & XR_LITERALS) insert_len = (int32_t)rec_hi;
-      else if (!(rec_lo & XR_IMPLICIT)) {
-        have_dist = true;
-        distance_context = 0;
-        if (rec_lo & XR_SHORT) {
-          if (rec_hi == 0u) { distance_code = d0; distance_context = 1; }
-          else distance_code = ring_distance(rec_hi);
-        } else distance_code = (int32_t)rec_hi;
-        bl2--;
-      }
-      br.advance((rec_lo >> 16) & 127u);
-    } else {
-      uint32_t cmd;
-      {
-        uint32_t e = rfl(next_root);
-        uint32_t len = e & 15u;
-        if (len > ROOT_BITS) {
-          uint32_t idx = (e >> 4) + (((uint32_t)br.buf >> ROOT_BITS) & mask_bits(len - ROOT_BITS));
-          e = rfl(lds_ld16(LDS_FIXED + cmd_tree + (idx << 1)));
-          len = ROOT_BITS + (e & 15u);
-        }
-        br.drop(len);
-        cmd = e >> 4;
-      }
-      uint32_t cell = cmd >> 6;
-      uint32_t ins_code = (((0x298500u >> (cell * 2)) & 3u) << 3) | ((cmd >> 3) & 7u);
-      uint32_t copy_code = (((0x262444u >> (cell * 2)) & 3u) << 3) | (cmd & 7u);
-      uint32_t ie = rdlane(lut_vgpr, ins_code), ce = rdlane(lut_vgpr, 32u + copy_code);
-      distance_code = cmd < 128 ? 0 : -1;
-      distance_context = copy_code > 2 ? 3u : copy_code;
-      insert_len = (int32_t)((ie & 0xFFFFu) + br.read24(ie >> 16));
-      copy_len = (int32_t)((ce & 0xFFFFu) + br.read24(ce >> 16));
-    }
-    SPLIT_LAP(0);
-    bl1--;
-    ncmd++;
-    lits_left = (uint32_t)insert_len;
-    rec_ins = 0; rec_lit = lit_head;
-    if (insert_len != 0) {
-      if ((uint32_t)insert_len > quota || (uint32_t)insert_len > bl0 || (uint32_t)insert_len > SP_MAX_INSERT) { stage = LS_AFTER_HEAD; break; }
-      mlen -= insert_len;
-      uint32_t i = (uint32_t)insert_len;
-      if (!ctx_regs) {
-        if (ctx_pend) {  // the last copy's source bytes, asked for when its distance was known
-          const uint64_t t_ = SPLIT_T();
-          asm volatile("s_waitcnt vmcnt(0)\n\tv_readlane_b32 %0, " SP_CTX_REG ", 0\n\tv_readlane_b32 %1, " SP_CTX_REG ", 1" : "=s"(p1), "=s"(p2) :: "memory");
-          SPLIT_PROF(2, t_); SPLIT_COUNT(8, 1);
-        } else {  // they were not in memory yet when the copy was posted (or the copy repeats itself): wait for the copier
-          SP_DRAIN();
-          SPLIT_COUNT(9, 1);
-          const uint64_t t_ = SPLIT_T();
-          p1 = P >= 1 ? (uint32_t)rfl(out[P - 1]) : 0u;
-          p2 = P >= 2 ? (uint32_t)rfl(out[P - 2]) : 0u;
-          SPLIT_PROF(3, t_);
-        }
-        ctx_regs = true; ctx_pend = false;
-      }
-      if (lit_head + i - lit_tail_c > SP_LIT_BYTES) {  // room in the literal ring
-        const uint64_t t_ = SPLIT_T(); uint32_t spins_ = 0;
-        do { __builtin_amdgcn_s_sleep(1); lit_tail_c = sp_ld(sp_ctl, CW_LIT_TAIL); if (++spins_ > SP_SPIN_CAP) { failed = 1; break; } } while (lit_head + i - lit_tail_c > SP_LIT_BYTES);
-        SPLIT_PROF(0, t_);
-      }
-      while (i > 0 && br.next_dw < safe_dw) {
-        uint32_t tree = lit_tree;
-        if (!trivial) {
-          const uint32_t context = ((rdlane(lut0v, p1 >> 2) >> ((p1 & 3u) << 3)) | (rdlane(lut1v, p2 >> 2) >> ((p2 & 3u) << 3))) & 0xFFu;
-          tree = rdlane(ctx_tree_v, context);
-        }
-        uint32_t lit = read_symbol<true>(br, a, tree);
-        p2 = p1; p1 = lit;
-        lit_reg = (lane == lit_n) ? lit : lit_reg;
-        lit_n++;
-        if (lit_n == 64) SP_LIT_FLUSH();
-        i--;
-      }
-      SP_LIT_FLUSH();
-      const uint32_t done = (uint32_t)insert_len - i;
-      P += done; bl0 -= done; quota -= done;
-      rec_ins = done;
-      lits_left = i;
-      if (i != 0) { stage = LS_LITERALS_REST; break; }
-      if (quota == 0) { stage = LS_LITERALS_AT_LIMIT; break; }
-    }
-    SPLIT_LAP(1);
-    // ---- distance (ReadDistanceInternal, decode.rs:2066-2131; see process_commands) ----
-    if (have_dist) {
-    } else if (distance_code >= 0) {
-      distance_context = 1;
-      distance_code = d0;
-    } else {
-      if (bl2 == 0) { stage = LS_DISTANCE; break; }
-      uint32_t dtree = distance_context == 0 ? dt0 : distance_context == 1 ? dt1 : distance_context == 2 ? dt2 : dt3;
-      uint32_t code = read_symbol<true>(br, a, dtree);
-      distance_context = 0;
-      if (code < 16) {
-        if (code == 0) {
-          distance_code = d0;
-          distance_context = 1;
-        } else distance_code = ring_distance(code);
-      } else if (dlut_ok && code < 64u) {
-        const uint32_t de = rdlane(dlut, code);
-        distance_code = (int32_t)((de >> 5) + br.read(de & 31u));
-      } else {
-        int32_t distval = (int32_t)code - (int32_t)num_direct;
-        int32_t dc = (int32_t)code;
-        if (distval >= 0) {
-          int32_t postfix = distval & (int32_t)mask_bits(postfix_bits);
-          distval >>= postfix_bits;
-          uint32_t nbits = ((uint32_t)distval >> 1) + 1;
-          uint32_t bits = br.read(nbits);
-          int64_t offset = (int64_t)(int32_t)((((uint32_t)(distval & 1) + 2u) << nbits) - 4u);
-          dc = (int32_t)(((offset + (int64_t)bits) << postfix_bits) + postfix + (int64_t)num_direct);
-        }
-        distance_code = (int32_t)((uint32_t)dc - 16u + 1u);
-      }
-      bl2--;
-      if (br.next_dw > br.end_dw) { stage = LS_NEEDS_INPUT; break; }
-    }
-    SPLIT_LAP(2);
-    br.need32();
-    next_root = lds_ld16(LDS_FIXED + cmd_tree + (((uint32_t)br.buf & 0xFFu) << 1));
-    SP_REC_REQUEST();
-    // ---- the copy becomes a record: an LZ77 reference (not the dictionary) inside the quota ----
-    {
-      const uint32_t n = (uint32_t)copy_len, dist = (uint32_t)distance_code;
-      const int32_t max_distance = (P < (uint64_t)(uint32_t)max_backward) ? (int32_t)P : max_backward;
-      if (distance_code > max_distance || distance_code <= 0 || n > quota) { stage = LS_POST_DISTANCE; break; }
-    SPLIT_LAP(3);
-      if (distance_context == 0) { d3 = d2; d2 = d1; d1 = d0; d0 = distance_code; }
-      mlen -= copy_len;
-      SP_POST((uint32_t)SPR_COPY | (rec_ins << 8), n, dist, rec_lit);
-      rec_ins = 0;
-      // the two bytes before the next command's first literal are the last two of this copy = of its source, if that is
-      // in memory already and the copy does not repeat itself (copy lengths start at 2)
-      ctx_regs = false; ctx_pend = false;
-      const uint64_t s2 = P + n - 2u - dist;  // (>= 0: dist <= P)
-      if (dist >= n && (int32_t)(rfl(done_v) - (uint32_t)(s2 + 2u)) >= 0) {
-        asm volatile("s_mov_b64 exec, 3\n\tglobal_load_ubyte " SP_CTX_REG ", %0, %1\n\ts_mov_b64 exec, -1" :: "v"(1u - lane), "s"(out + s2) : "memory", SP_CTX_REG);
-        ctx_pend = true;
-      }
-    SPLIT_LAP(4);
-      P += n;
-      quota -= n;
-      if (quota == 0) { stage = LS_COMMAND_DONE; break; }
-    }
-  }
-  // literals of a command that did not get to its copy here: a record of their own
-  if (rec_ins != 0u) SP_POST((uint32_t)SPR_COPY | (rec_ins << 8), 0u, 1u, rec_lit);
-  if (!ctx_regs && ctx_pend) {
-    asm volatile("s_waitcnt vmcnt(0)\n\tv_readlane_b32 %0, " SP_CTX_REG ", 0\n\tv_readlane_b32 %1, " SP_CTX_REG ", 1" : "=s"(p1), "=s"(p2) :: "memory");
-    ctx_regs = true;
-  }
-  SP_DRAIN();
-#ifdef BROTLI_AMD_PROFILE_SPLIT
-  if (blockIdx.x == 0 && lane == 0) for (int k = 0; k < 6; k++) g_split_prof[16 + k] += lap_acc[k];
-#endif
-  SPLIT_PROF(4, split_t0); SPLIT_COUNT(10, 1); SPLIT_COUNT(11, ncmd); SPLIT_COUNT(7, stage == LS_POST_DISTANCE ? 1 : 0);
-#undef SP_POST
-#undef SP_DRAIN
-#undef SP_LIT_FLUSH
-#undef SP_REC_REQUEST
-  if (rec_on) sp_st(xb, XW_POS, br.next_dw * 32u - br.cnt - origin_bits);
-  if (failed) hc_st(HC_FAILED, 1);
-  lds_st32(LDS_LEANWIN + 4u * lane, br.cur);
-  if (lane == 0) {
-    LEAN_ST(L_CHUNK_BASE, br.chunk_base);
-    LEAN_ST(L_P1, p1); LEAN_ST(L_P2, p2); LEAN_ST(L_CTX_REGS, ctx_regs ? 1u : 0u);
-    LEAN_ST(L_BUF_LO, (uint32_t)br.buf); LEAN_ST(L_BUF_HI, (uint32_t)(br.buf >> 32)); LEAN_ST(L_CNT, br.cnt); LEAN_ST(L_NEXT_DW, br.next_dw);
-    LEAN_ST(L_ISSUED, br.issued_half); LEAN_ST(L_P_LO, (uint32_t)P); LEAN_ST(L_P_HI, (uint32_t)(P >> 32)); LEAN_ST(L_QUOTA, quota);
-    LEAN_ST(L_MLEN, mlen); LEAN_ST(L_BL0, bl0); LEAN_ST(L_BL1, bl1); LEAN_ST(L_BL2, bl2);
-    LEAN_ST(L_D0, d0); LEAN_ST(L_D1, d1); LEAN_ST(L_D2, d2); LEAN_ST(L_D3, d3); LEAN_ST(L_NCMD_LO, ncmd);
-    LEAN_ST(L_INSERT, insert_len); LEAN_ST(L_COPY, copy_len); LEAN_ST(L_DCODE, distance_code); LEAN_ST(L_DCTX, distance_context);
-    LEAN_ST(L_LITS_LEFT, lits_left);
-    LEAN_ST(L_SP_HEAD, sp_head); LEAN_ST(L_SP_LIT, lit_head);
-  }
-  lds_sync();
-  return rfl(stage);
-}
-
 // (tree cache, context-modelled literals: does every literal block type's context map name at most `slots` trees?)
 __device__ __forceinline__ bool lit_types_fit_cache(const Arena& ar, const uint32_t nbt0, const uint32_t ctx_map, const uint32_t slots) {
   for (uint32_t bt = 0; bt < nbt0; bt++) {
@@ -3345,7 +2888,7 @@ __device__ __noinline__ int process_commands(HotArgs* args) {
   uint64_t pp_exit = 0, pp_enter = 0; (void)pp_enter; const uint64_t pp_start = __builtin_amdgcn_s_memtime(); bool pp_first = true; (void)pp_first;
 #endif
   const uint32_t engine_hints = rfl(args->general_engine);   // (bit 0: the general form; bits 8 .. 15, 16 .. 23: the gang's penalty and the invocations it still sits out, see remote_off)
-  bool prefer_one_engine = false;   // the next invocation of the path engine: its one-engine form (see `declined` below)
+  bool prefer_one_engine = false; (void)prefer_one_engine;   // the next invocation of the path engine: its one-block form (see `declined` below; gangs only)
   // ... the one-block form though the stream has a gang of blocks: for the next invocations where the gang met a literal run that wants regions
   // of its own first thing (it takes nothing then, and a region's tables of every block are lost: 8.1 against 5.8 ms on 4 MiB of high-entropy
   // literals, all runs) -- one invocation the first time, twice as many every time it happens again before the gang has taken anything, up to 64;
@@ -3358,43 +2901,37 @@ __device__ __noinline__ int process_commands(HotArgs* args) {
   bool prefer_scan = false;         // ... or the scan engine: the path engine found its regions bound by their closure (see there)
   bool prefer_general = (engine_hints & 1u) != 0u;   // ... or the path engine's general form: the lean one has stopped in front of a dictionary reference in this stream
   // ---- helper waves of a context-modelled metablock (LDS tables, a block of four or more waves): wave 2 parses command records
-  // ahead of this wave (rec_wave; the lean loop takes commands out of them); on request (BROTLI_AMD_ENGINE=split) wave 1 executes
-  // what this wave parses (copier_wave, lean_split_commands).  They stay engaged, idle while the checked stages run, until the
+  // ahead of this wave (rec_wave; the lean loop takes commands out of them).  It stays engaged, idle while the checked stages run, until the
   // metablock is done.
-  bool split_on = false, helpers_on = false;
   // (round 6) ... and of a metablock WITHOUT context too, in blocks that have helper waves and no command engine: the records and the hand-written run take
   // text -- a dozen bytes a command -- at 2.4 times what the one-wave loop does (1024 x lcet10 at -q 5: 10.4 -> 25 GB/s); a stream of long copies and long
   // literal runs leaves the run at every command, which is noticed after three calls that took next to nothing (rec_off; BROTLI_AMD_ENGINE=norecall: never)
   const bool rec_plain = CTX_NEVER && (g_engine_mode & 32u) == 0u && !scan_block;
-  if (LDS_ONLY && (!CTX_NEVER || rec_plain) && hc_ld(HC_NW_ALL) >= 4u && hc_ld(HC_KIND) != (uint32_t)HK_NO_ROUNDS && mlen >= (int32_t)SP_MIN_MLEN && (g_engine_mode & 6u) != 6u) {
-    split_on = !CTX_NEVER && (g_engine_mode & 2u) == 0u;
+  if (LDS_ONLY && (!CTX_NEVER || rec_plain) && hc_ld(HC_NW_ALL) >= 4u && hc_ld(HC_KIND) != (uint32_t)HK_NO_ROUNDS && mlen >= (int32_t)SP_MIN_MLEN && (g_engine_mode & 4u) == 0u) {
     // the records' ring: what is left of the LDS arena now that the tables of this metablock are built (no large window: a
     // record's distance has at most 24 extra bits); positions count from the dword the reader is in now
     const uint32_t free_at = tree_cache ? TREE_CACHE_BYTES + tree_cache_lit_slots(rfl(args->reserved_)) * TREE_CACHE_LIT_STRIDE : (a.top + 15u) & ~15u;   // (cached tables: behind the cache; `reserved_` is the LDS part's real size)
     const uint32_t lds_room = tree_cache ? rfl(args->reserved_) : a.lds_limit;
     const uint32_t origin_dw = (br.next_dw - ((br.cnt + 31u) >> 5)) & ~1u;
     const uint32_t ring_pos = lds_room >= free_at + SPX_BYTES ? SPX_POS : SPX_POS_MIN;   // (round 6: half a ring where the tables leave no room for a whole one -- text at -q 11 in blocks of four waves)
-    if ((g_engine_mode & 4u) == 0u && lds_room >= free_at + SPX_CTL_BYTES + ring_pos * 8u && rfl(args->large_window) == 0u && br.end_dw > origin_dw + 80u) rec_base = LDS_FIXED + free_at;
+    if (lds_room >= free_at + SPX_CTL_BYTES + ring_pos * 8u && rfl(args->large_window) == 0u && br.end_dw > origin_dw + 80u) rec_base = LDS_FIXED + free_at;
 #ifdef BROTLI_AMD_REC_DEBUG
     if (blockIdx.x == 0 && lane == 0) printf("records: room %u free_at %u need %u cache %d -> %s\n", lds_room, free_at, (uint32_t)SPX_BYTES, (int)tree_cache, rec_base != 0u ? "yes" : "no");
 #endif
-    if (split_on || rec_base != 0u) {
-      helpers_on = true;
+    if (rec_base != 0u) {
       lds_sync();
       hc_st(HC_EXT_BASE, rec_base);
-      if (rec_base != 0u && lane < (uint32_t)XW_WORDS)
+      if (lane < (uint32_t)XW_WORDS)
         lds_st32(rec_base + 4u * lane, lane == (uint32_t)XW_ORIGIN_DW ? origin_dw : lane == (uint32_t)XW_LIMIT ? ((br.end_dw - origin_dw - 8u) << 5) & ~63u :
                                        lane == (uint32_t)XW_DICT_LO ? (uint32_t)(uintptr_t)dict : lane == (uint32_t)XW_DICT_HI ? (uint32_t)((uint64_t)(uintptr_t)dict >> 32) :
                                        lane == (uint32_t)XW_RING_MASK ? ring_pos - 1u : 0u);
-      if (split_on && lane < (uint32_t)CW_WORDS)
-        lds_st32(sp_ctl_base() + 4u * lane, lane == (uint32_t)CW_OUT_LO ? (uint32_t)(uintptr_t)out : lane == (uint32_t)CW_OUT_HI ? (uint32_t)((uint64_t)(uintptr_t)out >> 32) : 0u);
-      if (lane == 0) { LEAN_ST(L_SP_HEAD, 0u); LEAN_ST(L_SP_LIT, 0u); LEAN_ST(L_SP_ORIGIN, origin_dw); LEAN_ST(L_SP_REC, rec_base != 0u ? 1u : 0u); }
-      hc_st(HC_KIND, (uint32_t)HK_SPLIT);
+      if (lane == 0) { LEAN_ST(L_SP_HEAD, 0u); LEAN_ST(L_SP_LIT, 0u); LEAN_ST(L_SP_ORIGIN, origin_dw); LEAN_ST(L_SP_REC, 1u); }
+      hc_st(HC_KIND, (uint32_t)HK_RECORDS);
       lds_release();
       hc_st(HC_SEQ, hc_ld(HC_SEQ) + 1u);
     }
   }
-  if (LDS_ONLY && !helpers_on && lane == 0) LEAN_ST(L_SP_REC, 0u);
+  if (LDS_ONLY && rec_base == 0u && lane == 0) LEAN_ST(L_SP_REC, 0u);
   uint32_t rec_poor = 0u;   // (a metablock without context) calls of the record loop in a row that took little and ended at a command too long for the run
   auto rec_off = [&]() {   // ... and the way back to the one-wave loop and its rounds: wave 2 goes back to sleep, as at the metablock's end
     sp_st(rec_base, XW_STOP, 1u);
@@ -3405,7 +2942,7 @@ __device__ __noinline__ int process_commands(HotArgs* args) {
 #ifdef BROTLI_AMD_REC_DEBUG
     if (blockIdx.x == 0 && lane == 0) printf("rec_off: stop word %u kind %u ncmd %llu mlen %d\n", sp_ld(rec_base, XW_STOP), hc_ld(HC_KIND), (unsigned long long)num_commands, mlen);
 #endif
-    rec_base = 0u; helpers_on = split_on;
+    rec_base = 0u;
     hc_st(HC_EXT_BASE, 0u);
     if (lane == 0) LEAN_ST(L_SP_REC, 0u);
     lds_sync();
@@ -3439,8 +2976,7 @@ __device__ __noinline__ int process_commands(HotArgs* args) {
         sc_ctl_st(sb, SCC_POSTFIX, postfix_bits); sc_ctl_st(sb, SCC_NUM_DIRECT, num_direct);
         sc_ctl_st(sb, SCC_OUT_LO, (uint32_t)(uintptr_t)out); sc_ctl_st(sb, SCC_OUT_HI, (uint32_t)((uint64_t)(uintptr_t)out >> 32));
         sc_ctl_st(sb, SCC_DICT_LO, (uint32_t)(uintptr_t)dict); sc_ctl_st(sb, SCC_DICT_HI, (uint32_t)((uint64_t)(uintptr_t)dict >> 32));
-        const bool use_pipe = use_path && (g_engine_mode & 8u) != 0u && !prefer_one_engine;   // (two engines of eight waves, regions in turns: BROTLI_AMD_ENGINE=path2 -- measured slower than one of sixteen, see DESIGN)
-        const bool use_general = use_path && !use_pipe && prefer_general;
+        const bool use_general = use_path && prefer_general;
         // (the stream's owner in a gang of blocks: the gang's form of the engine -- not for a literal run that wants regions of its own, nor for
         // words of the static dictionary: those are the one-block forms')
 #ifndef BROTLI_AMD_GANG_KERNEL   // (the kernel of the launches without gangs: see the end of this file)
@@ -3449,13 +2985,13 @@ __device__ __noinline__ int process_commands(HotArgs* args) {
         // (the counts looked at here, whether the helpers have all started by the engine itself the first time: a call in this place costs this
         // function three hundred bytes of frame, and the spills around it every invocation)
         bool use_remote = false;
-        if (use_path && !use_pipe && !use_general && hc_ld(HC_GANG_M) > 1u) {
+        if (use_path && !use_general && hc_ld(HC_GANG_M) > 1u) {
           const uint32_t counts = rfl(args->general_engine);
           if (((counts >> 16) & 0xFFu) != 0u) args->general_engine = counts - (1u << 16);
           else if (!prefer_one_engine) use_remote = true;
         }
 #endif
-        hc_st(HC_KIND, use_remote ? (uint32_t)HK_PATHR : use_pipe ? (uint32_t)HK_PATH2 : use_general ? (uint32_t)HK_PATHG : use_path ? (uint32_t)HK_PATH : (uint32_t)HK_SCAN);
+        hc_st(HC_KIND, use_remote ? (uint32_t)HK_PATHR : use_general ? (uint32_t)HK_PATHG : use_path ? (uint32_t)HK_PATH : (uint32_t)HK_SCAN);
         lds_release();
         hc_st(HC_SEQ, hc_ld(HC_SEQ) + 1u);  // the other waves of the block join (helper_wave)
 #ifdef BROTLI_AMD_PROFILE_SCAN
@@ -3465,9 +3001,9 @@ __device__ __noinline__ int process_commands(HotArgs* args) {
         if (blockIdx.x == 0 && lane == 0) printf("engine in: P %llu bl1 %u quota %u mlen %d commands so far %llu\n", (unsigned long long)P, bl1, quota, mlen, (unsigned long long)num_commands);
 #endif
 #ifndef BROTLI_AMD_GANG_KERNEL
-        const uint32_t took = use_pipe ? rfl(pe8::path_engine(0)) : use_general ? rfl(pe16g::path_engine(0)) : use_path ? rfl(pe16::path_engine(0)) : rfl(scan_engine(0));
+        const uint32_t took = use_general ? rfl(pe16g::path_engine(0)) : use_path ? rfl(pe16::path_engine(0)) : rfl(scan_engine(0));
 #else
-        const uint32_t took = use_remote ? rfl(pe16r::path_engine(0)) : use_pipe ? rfl(pe8::path_engine(0)) : use_general ? rfl(pe16g::path_engine(0)) : use_path ? rfl(pe16::path_engine(0)) : rfl(scan_engine(0));
+        const uint32_t took = use_remote ? rfl(pe16r::path_engine(0)) : use_general ? rfl(pe16g::path_engine(0)) : use_path ? rfl(pe16::path_engine(0)) : rfl(scan_engine(0));
 #endif
 #ifdef BROTLI_AMD_PE_DEBUG
         if (blockIdx.x == 0 && lane == 0) printf("engine out: tick %llu took %u, P %llu form %u\n", (unsigned long long)__builtin_amdgcn_s_memtime(), took, (unsigned long long)(LEAN_LD(L_P_LO) | ((uint64_t)LEAN_LD(L_P_HI) << 32)), LEAN_LD(L_SC_POS_HI));
@@ -3487,7 +3023,7 @@ __device__ __noinline__ int process_commands(HotArgs* args) {
 #ifdef BROTLI_AMD_GANG_KERNEL
         if (use_remote) gang_took(args, took, form_raw);
 #endif
-        if (((form_raw >> 9) & 1u) != 0u) prefer_scan = true;   // (the path engine's regions were bound by their closure: a stream of few literals -- the scan engine's from here on)   // (the two engines stopped in front of a literal run that wants regions of its own: the one-engine form's, at once)
+        if (((form_raw >> 9) & 1u) != 0u) prefer_scan = true;   // (the path engine's regions were bound by their closure: a stream of few literals -- the scan engine's from here on)
         const uint64_t pos = origin + LEAN_LD(L_SC_POS_LO) - BitReader::skip_bits();
         if (lane == 0) { LEAN_ST(L_SPEC_LO, (uint32_t)rfl(args->spec_scratch)); LEAN_ST(L_SPEC_HI, (uint32_t)(rfl(args->spec_scratch) >> 32)); }
         br.seek(pos);
@@ -3542,29 +3078,20 @@ __device__ __noinline__ int process_commands(HotArgs* args) {
         }
       }
       lds_sync();
-      uint32_t stage;
-      if (!CTX_NEVER && split_on) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // what this wave has stored is in memory before the copier reads it as a copy's source
-        sp_st(sp_ctl_base(), CW_DONE_P, (uint32_t)P);       // (the copier is idle: it says so again only after the next record)
-        stage = rfl(lean_split_commands(lut_vgpr, ctx_tree_v));
-        if (hc_ld(HC_FAILED) != 0u) STOP(E_UNREACHABLE);    // the copier did not answer (never seen)
-        engine_commands += LEAN_LD(L_NCMD_LO);
-      } else {
-        stage = rec_base != 0u ? rfl(lean_rec_commands(ctx_tree_v)) : rfl(lean_commands<CTX_NEVER>(lut_vgpr, ctx_tree_v));
-        if (rec_base != 0u) {
-          const uint32_t took_ = LEAN_LD(L_NCMD_LO);
-          engine_commands += took_;
-          // (a metablock without context has another road: what a call of the record loop takes, halved and added up -- a stream of long copies or long
-          // literal runs leaves the run at every command, and every way out costs what forty of its commands do)
+      uint32_t stage = rec_base != 0u ? rfl(lean_rec_commands(ctx_tree_v)) : rfl(lean_commands<CTX_NEVER>(lut_vgpr, ctx_tree_v));
+      if (rec_base != 0u) {
+        const uint32_t took_ = LEAN_LD(L_NCMD_LO);
+        engine_commands += took_;
+        // (a metablock without context has another road: what a call of the record loop takes, halved and added up -- a stream of long copies or long
+        // literal runs leaves the run at every command, and every way out costs what forty of its commands do)
 #ifdef BROTLI_AMD_REC_DEBUG
-          if (CTX_NEVER && blockIdx.x == 0 && lane == 0) printf("rec call: took %u waited %u poor %u stage %u ncmd %llu\n", took_, LEAN_LD(L_SP_WAITED), rec_poor, stage, (unsigned long long)num_commands);
+        if (CTX_NEVER && blockIdx.x == 0 && lane == 0) printf("rec call: took %u waited %u poor %u stage %u ncmd %llu\n", took_, LEAN_LD(L_SP_WAITED), rec_poor, stage, (unsigned long long)num_commands);
 #endif
-          // (a metablock without context has another road.  A stream of long copies or long literal runs leaves the run at every such command, and every way
-          // out costs what forty of the run's commands do: six calls in a row that ended at a LONG command having taken less than sixty-four, and the
-          // one-wave loop and its rounds have the rest of the metablock.  The first commands of a text -- words of the dictionary with their transforms while
-          // the window is empty -- end calls too, but not like that.)
-          if (CTX_NEVER) { if (took_ >= 64u) rec_poor = 0u; else if (LEAN_LD(L_SP_WAITED) == 2u && ++rec_poor >= 6u) rec_off(); }
-        }
+        // (a metablock without context has another road.  A stream of long copies or long literal runs leaves the run at every such command, and every way
+        // out costs what forty of the run's commands do: six calls in a row that ended at a LONG command having taken less than sixty-four, and the
+        // one-wave loop and its rounds have the rest of the metablock.  The first commands of a text -- words of the dictionary with their transforms while
+        // the window is empty -- end calls too, but not like that.)
+        if (CTX_NEVER) { if (took_ >= 64u) rec_poor = 0u; else if (LEAN_LD(L_SP_WAITED) == 2u && ++rec_poor >= 6u) rec_off(); }
       }
       br.buf = (uint64_t)LEAN_LD(L_BUF_LO) | ((uint64_t)LEAN_LD(L_BUF_HI) << 32);
       br.cnt = LEAN_LD(L_CNT); br.next_dw = LEAN_LD(L_NEXT_DW); br.issued_half = LEAN_LD(L_ISSUED);
@@ -4052,11 +3579,9 @@ done:
 #endif
   FLUSH_LITERALS();
   FLUSH_PENDING();
-  if (helpers_on) {  // the helpers go back to sleep (HC_KIND stays: a helper that looks late must find nothing to do)
-    const uint32_t ctl = sp_ctl_base();
-    if (split_on) sp_st(ctl, CW_STOP, 1u);
-    if (rec_base != 0u) sp_st(rec_base, XW_STOP, 1u);
-    for (uint32_t spins = 0; (split_on && sp_ld(ctl, CW_STOP) != 2u) || (rec_base != 0u && sp_ld(rec_base, XW_STOP) != 2u); spins++) {
+  if (rec_base != 0u) {  // the helpers go back to sleep (HC_KIND stays: a helper that looks late must find nothing to do)
+    sp_st(rec_base, XW_STOP, 1u);
+    for (uint32_t spins = 0; sp_ld(rec_base, XW_STOP) != 2u; spins++) {
       if (spins > SP_SPIN_CAP) { hc_st(HC_KIND, (uint32_t)HK_NO_ROUNDS); result = E_UNREACHABLE; break; }
       __builtin_amdgcn_s_sleep(2);
     }
@@ -4470,7 +3995,7 @@ __device__ __forceinline__ int decode_stream(Stream& s, bool have_header, uint64
 // This file compiles into two objects (Makefile): the kernel of the launches without gangs, and -- with -DBROTLI_AMD_GANG_KERNEL -- the kernel of the
 // gang launches, the only one that has the gang's form of the path engine in its call graph.  One kernel for both cost the metric 4.5 %
 // (6.39 -> 6.68 ms) while the gang's decision sat in process_commands' registers (see there); since it does not, the second kernel costs
-// launches without gangs nothing (BROTLI_AMD_GANG_KERNEL_ALWAYS=1 runs them through it) -- two objects all the same: insurance.
+// launches without gangs nothing (measured by running them through it) -- two objects all the same: insurance.
 #ifdef BROTLI_AMD_GANG_KERNEL
 #define BROTLI_AMD_KERNEL brotli_amd_decode_gang_kernel
 #define BROTLI_AMD_LAUNCH brotli_amd_launch_decode_gang
@@ -4718,17 +4243,6 @@ extern "C" __global__ __launch_bounds__(1024, 4) void BROTLI_AMD_KERNEL(const Br
            g_lean_prof[1] / g_lean_prof[4], g_lean_prof[2] / g_lean_prof[4], g_lean_prof[3] / g_lean_prof[4]);
 #endif
 #ifdef BROTLI_AMD_PROFILE_SPLIT
-  if (blockIdx.x == 0 && lane_id() == 0 && g_split_prof[10] != 0)
-    printf("split: %llu parser invocations (%llu left at a distance the lean loop does not take), %llu commands, %llu records executed; parser ticks %llu: ring full %llu, drains %llu, "
-           "context from the copy's source: %llu waits of %llu ticks; context after a drain: %llu, loads %llu ticks; copier busy ticks %llu; commands out of records %llu, looks at the records' frontier %llu; waves %u, record ring at %u (arena %u)\n",
-           g_split_prof[10], g_split_prof[7], g_split_prof[11], g_split_prof[12], g_split_prof[4], g_split_prof[0], g_split_prof[1], g_split_prof[8], g_split_prof[2],
-           g_split_prof[9], g_split_prof[3], g_split_prof[5], g_split_prof[15], g_split_prof[14], hc_ld(HC_NW_ALL), hc_ld(HC_EXT_BASE), lds_arena_bytes);
-  if (blockIdx.x == 0 && lane_id() == 0 && g_split_prof[10] != 0)
-    printf("split parser ticks per command: head %llu, literals %llu, distance %llu, next root + record request + checks %llu, post %llu, context fetch + tail %llu, loop top %llu\n",
-           g_split_prof[16] / g_split_prof[11], g_split_prof[17] / g_split_prof[11], g_split_prof[18] / g_split_prof[11], g_split_prof[19] / g_split_prof[11],
-           g_split_prof[20] / g_split_prof[11], g_split_prof[21] / g_split_prof[11], 0ull);
-#endif
-#ifdef BROTLI_AMD_PROFILE_SPLIT
   if (blockIdx.x == 0 && lane_id() == 0 && g_split_prof[37] != 0)
     printf("record loop: %llu calls, %llu commands (%llu in hand-written runs, %llu with literals, %llu without by the compiled path, %llu words), %llu ticks in the loop; ticks: top %llu, runs %llu, "
            "head + context bytes %llu, literals %llu, distance %llu, counts + literal store %llu, copy / word + next record %llu\n",
@@ -4777,7 +4291,7 @@ extern "C" __global__ __launch_bounds__(1024, 4) void BROTLI_AMD_KERNEL(const Br
     printf("\npath engine dependent copies: %llu per region, the last wave's ticks in them %llu per region\n", g_path_prof[35] / g_path_prof[20], g_path_prof[34] / g_path_prof[20]);
     printf("\npath engine literal-run regions: %llu literals in all\n", g_path_prof[19]);
     printf("\npath engine path phase: chains and entries %llu, ranks %llu (the rest: positions and literals)\n", g_path_prof[17] / g_path_prof[20], g_path_prof[18] / g_path_prof[20]);
-    printf("\npath engine, two engines (engine 0's wave 0, ticks per region): waiting for the window %llu, for the stream %llu, for the region before's output %llu\n", g_path_prof[15] / g_path_prof[20], g_path_prof[16] / g_path_prof[20], g_path_prof[14] / g_path_prof[20]);
+    printf("\npath engine, wave 0 (ticks per region): the walk's anchors %llu, the commands behind them %llu, a gang's wait for the region before's output %llu\n", g_path_prof[15] / g_path_prof[20], g_path_prof[16] / g_path_prof[20], g_path_prof[14] / g_path_prof[20]);
     printf("\nbetween two invocations of the engine in one metablock: %llu ticks in all, %llu times; inside the engine's calls %llu; from the command loop's start to the first invocation %llu; from the last one's end to the loop's end %llu; the command loops in all %llu\n", g_path_prof[36], g_path_prof[37], g_path_prof[38], g_path_prof[29], g_path_prof[39], g_path_prof[31]);
     { unsigned long long eng = 0; for (int k = 0; k <= 11; k++) eng += g_path_prof[k]; eng += g_path_prof[14] + g_path_prof[15] + g_path_prof[16]; eng += g_path_prof[17] + g_path_prof[18];
       printf("\nkernel ticks of block 0 in this launch: %llu; the path engine's regions so far (all launches): %llu\n", (unsigned long long)(__builtin_amdgcn_s_memtime() - scan_prof_t0), eng); }
@@ -4838,13 +4352,11 @@ extern "C" hipError_t BROTLI_AMD_LAUNCH(const BrotliAmdStreamDesc* descs, Brotli
   {  // BROTLI_AMD_ENGINE=scan: the round-2 command engine only (A/B tests); the symbol is per device
     static const char* const eng = getenv("BROTLI_AMD_ENGINE");
     if (eng != nullptr) {
-      // bit 0: the scan engine only; bit 1: no copier wave for context-modelled metablocks (the default: it does not pay, see DESIGN;
-      // "split" turns it on); bit 2: no command records ("norec")
-      // bit 3: the path engine as two engines of eight waves that take the stream's regions in turns ("path2"; experiment)
+      // bit 0: the scan engine only ("scan"); bit 2: no command records ("norec")
       // bit 4: tables beyond the LDS part are read where they lie instead of the trees in use being cached ("nocache": A/B)
       // bit 5: NO command records for metablocks without context ("norecall": A/B -- round 6 gave such metablocks the records and the hand-written run in blocks with helper waves)
       // (static storage: the asynchronous copy reads it after this function has returned)
-      static const uint32_t mode = strcmp(eng, "scan") == 0 ? 3u : strcmp(eng, "split") == 0 ? 0u : strcmp(eng, "norec") == 0 ? 6u : strcmp(eng, "path2") == 0 ? 10u : strcmp(eng, "nocache") == 0 ? 18u : strcmp(eng, "norecall") == 0 ? 34u : 2u;
+      static const uint32_t mode = strcmp(eng, "scan") == 0 ? 1u : strcmp(eng, "norec") == 0 ? 4u : strcmp(eng, "nocache") == 0 ? 16u : strcmp(eng, "norecall") == 0 ? 32u : 0u;
       hipError_t e2 = hipMemcpyToSymbolAsync(HIP_SYMBOL(g_engine_mode), &mode, sizeof mode, 0, hipMemcpyHostToDevice, stream);
       if (e2 != hipSuccess) return e2;
     }

@@ -32,24 +32,19 @@
 //
 // Nothing depends on a guess: a record is the exact parse of its state or a marker (END: the parse leaves the region;
 // BYHAND: a cap was hit), and the walk starts at the stream's real position.
-// (no include guard: brotli_kernels.hip includes this file once per configuration -- PE_CFG_NS the namespace, PE_CFG_WAVES the
-// waves of one engine, PE_CFG_RBL its region in stream bits, PE_CFG_PIPE whether two engines of a block take turns)
-// PE_CFG_REMOTE (round 5): the engines that take a stream's regions in turns are BLOCKS -- a gang of up to eight, a CU each,
-// on one stream (see "several CUs on one stream" below); what they tell each other goes through memory.)
-#if !defined(PE_CFG_NS) || !defined(PE_CFG_WAVES) || !defined(PE_CFG_RBL) || !defined(PE_CFG_PIPE) || !defined(PE_CFG_DICT) || !defined(PE_CFG_REMOTE)
+// (no include guard: brotli_kernels.hip includes this file once per configuration -- PE_CFG_NS the namespace, PE_CFG_DICT the
+// form (see PE_DICT below), PE_CFG_REMOTE (round 5) whether the blocks of a gang -- up to sixteen, a CU each, on one stream (see
+// "several CUs on one stream" below) -- take the stream's regions in turns; what they tell each other goes through memory.)
+#if !defined(PE_CFG_NS) || !defined(PE_CFG_DICT) || !defined(PE_CFG_REMOTE)
 #error "brotli_path_engine.h: configuration macros missing"
 #endif
-#if PE_CFG_PIPE && PE_CFG_REMOTE
-#error "brotli_path_engine.h: two engines a block or a gang of blocks, not both"
-#endif
 namespace PE_CFG_NS {
-constexpr uint32_t GW = PE_CFG_WAVES;             // waves of one engine
-constexpr bool PIPE2 = PE_CFG_PIPE != 0;          // two engines of GW waves a block, taking the stream's regions in turns
-constexpr bool REMOTE = PE_CFG_REMOTE != 0;       // ... or one engine a block, and the blocks of a gang taking them in turns
-constexpr bool PIPE = PIPE2 || REMOTE;            // (either way: a region's tables are built before the stream's entry into it is known)
-static_assert(PIPE2 ? 2u * GW == SC_WAVES : GW == SC_WAVES, "engines and waves of a block");
+constexpr uint32_t GW = 16;                       // waves of the engine: the whole block
+static_assert(GW == SC_WAVES, "one engine a block");
+constexpr bool REMOTE = PE_CFG_REMOTE != 0;       // the blocks of a gang take the stream's regions in turns (a region's tables are built
+                                                  // before the stream's entry into it is known)
 
-constexpr uint32_t PE_RBL = PE_CFG_RBL;           // stream bits per region (local bit 0 = the first bit of the region's first dword)
+constexpr uint32_t PE_RBL = 32768;                // stream bits per region (local bit 0 = the first bit of the region's first dword)
 constexpr uint32_t PE_CHUNKS = PE_RBL / 32;       // one lane per chunk of 32 bits: the whole block
 constexpr uint32_t PE_RANKS = PE_RBL / 64u * 13u;  // path positions of a region at most (the region is cut where they run out): 6656 of 32 Kbit
 constexpr uint32_t PE_WCAP = PE_RBL / 4u;         // closure states at most (records that would need more say BYHAND)
@@ -64,11 +59,8 @@ constexpr uint32_t PE_CMDS = PE_RBL / 32u;          // commands one region's wal
 constexpr uint32_t PE_DEPTH2_MIN = BROTLI_AMD_PE_DEPTH2_MIN;   // a gang of this many blocks and more may have three executes under way (see the execute's waits)
 constexpr uint32_t PE_DEP_ROUNDS = 6;             // levels of copies that build on each other which go side by side (execute); deeper ones in order
 constexpr uint32_t PE_LANE_LITS = 64;             // literal runs up to this long are stored by their command's lane, four bytes a step
-#ifndef BROTLI_AMD_PE_LANE_COPY
-#define BROTLI_AMD_PE_LANE_COPY 16
-#endif
-constexpr uint32_t PE_LANE_COPY = BROTLI_AMD_PE_LANE_COPY;  // copies up to this long from in front of the region are done by their command's lane (16-byte loads, 16 .. 64)
-static_assert(PE_LANE_COPY == 16, "lane copies: a region that is put together in LDS takes its short copies out of ONE sixteen-byte load (32 and 64 were round 3's experiment, before the stage)");
+constexpr uint32_t PE_LANE_COPY = 16;             // copies up to this long from in front of the region are done by their command's lane: a region
+                                                  // that is put together in LDS takes them out of ONE sixteen-byte load
 #ifndef BROTLI_AMD_PE_RUN_MIN
 #define BROTLI_AMD_PE_RUN_MIN 6000
 #endif
@@ -81,7 +73,6 @@ constexpr uint32_t PE_RUN_SB = BROTLI_AMD_PE_RUN_SB;   // a long literal run's r
                                                   // the likelier the lane's last word ends where it does whatever bit the lane entered at, and the fewer rounds the entries take)
 constexpr uint32_t PE_RUN_RBL = 64u * GW * PE_RUN_SB;   // ... and the bits of such a region (no tables per bit: its input lies in the input's and J1's room)
 constexpr uint32_t PE_MIN_INPUT = 4096;           // stream bits that must be left for a region to be worth its set-up
-constexpr uint32_t PE_PIPE_MARGIN = 1024;          // two engines: a region's tables start this many bits in front of where the stream is expected to enter it
 #ifndef BROTLI_AMD_PE_REMOTE_MARGIN
 #define BROTLI_AMD_PE_REMOTE_MARGIN 1024
 #endif
@@ -93,11 +84,10 @@ constexpr uint32_t PE_PIPE_MARGIN = 1024;          // two engines: a region's ta
 #endif
 constexpr uint32_t PE_SEEDS = BROTLI_AMD_PE_SEEDS;          // a gang: entry seeds of a window built ahead of the stream (PEC_SEEDLO): this many bit positions ...
 constexpr uint32_t PE_SEED_BACK = BROTLI_AMD_PE_SEED_BACK;  // ... from this far in front of where a stream that ran the region before to its end would enter
-static_assert(!PE_CFG_REMOTE || PE_SEEDS <= 64u * PE_CFG_WAVES, "a thread a seed");
-constexpr uint32_t PE_REMOTE_MARGIN = BROTLI_AMD_PE_REMOTE_MARGIN;   // a gang of blocks: the same margin between the windows of its plan
-constexpr uint32_t PE_PIPE_USEFUL = 4096;          // ... and are used if the stream enters them with at least this many bits to go
+static_assert(!PE_CFG_REMOTE || PE_SEEDS <= 64u * GW, "a thread a seed");
+constexpr uint32_t PE_REMOTE_MARGIN = BROTLI_AMD_PE_REMOTE_MARGIN;   // a gang of blocks: the margin between the windows of its plan (a region's walk ends short of its window's end)
+constexpr uint32_t PE_PIPE_USEFUL = 4096;          // ... a window's tables are used if the stream enters them with at least this many bits to go
 constexpr uint32_t PE_PIPE_HAND = 48;              // ... and the walk evaluates this many states itself before the stream is on the path (commands without literals, one after the other)
-constexpr uint32_t PE_PIPE_DECLINE = 2500;         // ... and a literal run from here on is the one-engine form's (its regions hold 6656 path positions, these half)
 static_assert(PE_CHUNKS == 64u * GW, "one chunk per lane of the block");
 
 // LDS layout, offsets from the engine's base (the scan engine's: the two never run at the same time)
@@ -158,33 +148,29 @@ static_assert(PE_RUN_QA + 64u * GW * 4u <= PE_LIST && PE_RUN_CNT % 4 == 0 && 64u
 constexpr uint32_t PE_RUN_EX = PE_PM;                              // ... u8 per lane: where its last code word ends (bits into the next lane's part)
 static_assert((PE_RUN_RBL / 32u + 8u) * 4u <= PE_PM - PE_IN && 64u * GW <= PE_CHUNKS * 4u, "a run region's input and exits");
 static_assert(PE_RUN_LIT % 16 == 0 && PE_STG % 16 == 0, "what write_out reads line by line");
-static_assert(PIPE || 64u * GW * 2u + 4096u <= PE_EX - PE_PM, "a run region's exits and its table of the literal code (one engine: two never take a run)");
+static_assert(64u * GW * 2u + 4096u <= PE_EX - PE_PM, "a run region's exits and its table of the literal code");
 constexpr uint32_t PE_SET_BYTES = PE_ANCH + 128 * 4;              // one engine's tables
-// What the engines of a block share: the invocation's parameters, the stream's state, the records' two tables.  One engine: at the
-// end of its tables (the control words are its own); two engines: in front of theirs, with a block of control words of its own.
+// The records' two tables lie at the end of the engine's tables.
 // A record is parsed where 128 bits of the region are left in front of it (pos + 128 <= L); its reads reach further: a distance
 // code of up to 15 + 62 bits (large window) in front of a head whose 64-bit read takes three dwords, i.e. bit pos + 77 + 96 at
 // most -- 45 bits beyond L, inside the six dwords (192 bits) of input that every region stages behind its last one.
 static_assert(15u + 62u + 96u <= 128u + 6u * 32u, "a record's reads stay inside the region's input slack");
 constexpr uint32_t PE_TD_ENTRIES = 1024;                          // (920 is the most a distance alphabet without large window takes; a large-window table that needs more keeps its metablock off the engine: td_ok)
-constexpr uint32_t PE_SHARED_CTL = PIPE2 ? 1024u : 0u;            // the shared control words (two engines)
-constexpr uint32_t PE_TD = PIPE2 ? PE_SHARED_CTL : PE_SET_BYTES;  // u16 per entry of the distance code's table: the same two levels, a leaf's value = bits of the whole distance code (symbol + extra)
+constexpr uint32_t PE_TD = PE_SET_BYTES;                          // u16 per entry of the distance code's table: the same two levels, a leaf's value = bits of the whole distance code (symbol + extra)
 constexpr uint32_t PE_TC = PE_TD + PE_TD_ENTRIES * 2;             // u32 per command symbol: insert base | insert extra bits << 15 | copy extra bits << 20 | implicit distance << 25
-constexpr uint32_t PE_SET0 = PIPE2 ? PE_TC + 704 * 4 : 0u;        // the first engine's tables
-constexpr uint32_t PE_BYTES = PIPE2 ? PE_SET0 + 2u * PE_SET_BYTES : PE_TC + 704 * 4;
+constexpr uint32_t PE_BYTES = PE_TC + 704 * 4;
 static_assert(PE_BYTES <= SC_BYTES, "the path engine lives in the scan engine's LDS");
 static_assert(PE_STATES * 2 <= PE_RBL + 64 && PE_WCAP * 2 <= PE_WSTB && PE_CMDS * 4 <= PE_CHUNKS * 4 && PE_STATES % 8 == 0, "overlays");
-static_assert(PE_J1F % 16 == 0 && PE_PM % 16 == 0 && PE_REC % 16 == 0 && PE_POR % 4 == 0 && PE_NEXT % 4 == 0 && PE_LIST % 4 == 0 && PE_TD % 4 == 0 && PE_TC % 4 == 0 && PE_SET0 % 16 == 0 && PE_SET_BYTES % 16 == 0, "alignment");
+static_assert(PE_J1F % 16 == 0 && PE_PM % 16 == 0 && PE_REC % 16 == 0 && PE_POR % 4 == 0 && PE_NEXT % 4 == 0 && PE_LIST % 4 == 0 && PE_TD % 4 == 0 && PE_TC % 4 == 0 && PE_SET_BYTES % 16 == 0, "alignment");
 
 enum { PEN_END = 0xFFFFu, PEN_BYHAND = 0xFFFEu, PEN_NONE = 0xFFFDu, PEN_FIRST_SPECIAL = 0xFFF0u };
 // control words of a region (from 64 on; the invocation's parameters are the scan engine's SCC_*)
 enum { PEC_LBDW = 64, PEC_LE = 65, PEC_L = 66, PEC_LP = 67, PEC_RN = 68, PEC_WN = 69, PEC_TMIN = 70, PEC_M = 71, PEC_GO = 72, PEC_KP = 73,
-       PEC_P0_LO = 74, PEC_P0_HI = 75, PEC_ANYDEP = 76, PEC_CHG = 77 /* three words */, PEC_STATE = 160 /* the stream's state between wave 0's uses of it: PeStream */, PEC_CONT = 96, PEC_NEXT_LBDW = 97, PEC_ON = 98, PEC_NA = 99, PEC_NBIG = 101, PEC_TAILN = 102, PEC_TAILNEXT = 103, PEC_READY = 104, PEC_ENT = 105, PEC_MODE = 106, PEC_DEPCHG = 107 /* the dependent copies' levels: bit r, round r changed one */, PEC_DEPLV0 = 108 /* ... levels of the copies that do not lag */, PEC_DEPLV1 = 109 /* ... and of those that do */, PEC_DEPDEEP = 110 /* ... some are deeper than the rounds go */, PEC_PREVOUT = 111 /* (a gang) the bytes of the region before's output */, PEC_DEPTH = 112 /* ... how many regions before this one its resolve took for still under way: PEC_RELAX when the stream arrived */, PEC_TAKE = 107, PEC_BKP = 108 /* + batch: 16 words */, PEC_NEXTRANK = 100, PEC_WSUM = 80 /* + wave: 16 words */, PEC_NAPUB = 125 /* anchors the walk has published */, PEC_WDONE = 126 /* the walk is over */,
-       PEC_STAGED = 127 /* the region's output is put together in LDS */, PEC_OUTTOT = 128 /* its size */, PEC_TDN = 129 /* entries of the distance code's table */, PEC_SCRATCH = 130 /* stores that are not meant land here */, PEC_GBAR = 131 /* the engine's barrier: arrivals so far */,
-       // two engines (words of the shared block): what they tell each other
-       PEC_RESOLVED = 132 /* regions whose resolve is through: the stream's state is the next one's */, PEC_EXECUTED = 133 /* regions whose output is in memory */,
-       PEC_STOP = 134 /* the invocation is over */, PEC_NFINAL = 135 /* regions whose window is final */, PEC_WINF = 136 /* + (region & 1): its first dword */,
-       PEC_DECLINE = 139 /* the next command's literal run wants regions of its own: the one-engine form's */, PEC_PLAN = 140 /* (an engine's own word) what to do with the tables it built */, PEC_MYENTRY = 141 /* ... where the stream entered its region */, PEC_MYNEXT = 142 /* ... and where it left it */,
+       PEC_P0_LO = 74, PEC_P0_HI = 75, PEC_ANYDEP = 76, PEC_CHG = 77 /* three words */, PEC_STATE = 160 /* the stream's state between wave 0's uses of it: PeStream */, PEC_CONT = 96, PEC_NEXT_LBDW = 97, PEC_ON = 98, PEC_NA = 99, PEC_NBIG = 101, PEC_TAILN = 102, PEC_TAILNEXT = 103, PEC_READY = 104, PEC_ENT = 105, PEC_MODE = 106, PEC_DEPCHG = 107 /* the dependent copies' levels: bit r, round r changed one */, PEC_DEPLV0 = 108 /* ... levels of the copies that do not lag */, PEC_DEPLV1 = 109 /* ... and of those that do */, PEC_DEPDEEP = 110 /* ... some are deeper than the rounds go */, PEC_PREVOUT = 111 /* (a gang) the bytes of the region before's output */, PEC_DEPTH = 112 /* ... how many regions before this one its resolve took for still under way: PEC_RELAX when the stream arrived */, PEC_TAKE = 107 /* (the table build) */, PEC_NEXTRANK = 100, PEC_WSUM = 80 /* + wave: 16 words */, PEC_NAPUB = 125 /* anchors the walk has published */, PEC_WDONE = 126 /* the walk is over */,
+       PEC_STAGED = 127 /* the region's output is put together in LDS */, PEC_OUTTOT = 128 /* its size */, PEC_TDN = 129 /* entries of the distance code's table */, PEC_SCRATCH = 130 /* stores that are not meant land here */,
+       // a gang: what its blocks tell each other (the engine clears EXECUTED .. DECLINE where it starts)
+       PEC_EXECUTED = 133 /* regions whose output is in memory */,
+       PEC_DECLINE = 139 /* the next command's literal run wants regions of its own: the one-block form's */, PEC_PLAN = 140 /* what to do with the tables this engine built */, PEC_MYENTRY = 141 /* ... where the stream entered its region */,
        PEC_BIGNEXT = 143 /* the execute's items that get a wave: handed out so far */, PEC_NXOK = 144 /* the number of the region whose PEC_CONT / PEC_NEXT_LBDW are there */ , PEC_KS = 145 /* the pass's first command (passes: see PE_DICT) */, PEC_DICTK = 146 /* the command whose copy is a word of the static dictionary, its literals out: its index, distance, copy length */, PEC_DICTD = 147, PEC_DICTN = 148, PEC_AGAIN = 149, PEC_PDX = 150 /* the invocation ends behind that command's distance (SCX_POST_DISTANCE) */, PEC_OVF = 151 /* regions of this invocation whose closure all but filled its room */,
        PEC_MYGEN = 157 /* (a gang) the generation of the plan this engine's window follows */, PEC_MYSHIFT = 138 /* ... and how often its regions are halved */, PEC_MEMBERS = 186 /* ... (a pool) the blocks of this invocation's gang */, PEC_NOHELP = 185 /* ... (a pool) the owner kept the invocation to itself because nobody has joined its stream */, PEC_RELAX = 159 /* ... whether this engine's executes wait twice (see there): its own observation, kept from region to region */, PEC_LAG = 137 /* ... the bytes of the region before's output: what a copy may not read before that region's engine says they are there */, PEC_BUILT = 158 /* ... whether its tables are built */,
        PEC_SEEDLO = 190 /* (a gang) the window's ENTRY SEEDS: the states 'a command starts at bit PEC_SEEDLO + i', i < PEC_SEEDN, are closure states 1 + i -- evaluated with the
@@ -192,6 +178,9 @@ enum { PEC_LBDW = 64, PEC_LE = 65, PEC_L = 66, PEC_LP = 67, PEC_RN = 68, PEC_WN 
        PEC_FIN = 156 /* a long literal run has ended in this region: its command's distance and copy are wave 0's, in place */,
        PEC_DSEEN = 155 /* (lean form) the engine's part ended in front of a dictionary reference: the general form's stream */,
        PEC_DCAND = 152 /* (PE_DICT) a command of the pass may be a word of the static dictionary */, PEC_NWORD = 153 /* ... words the pass puts out */, PEC_WNEXT = 154 /* ... handed out so far */ };
+// Words that share an index on purpose: their lifetimes do not overlap.  PEC_TAKE lives inside the table build, PEC_DEPCHG inside the
+// execute's dependent copies.
+static_assert(PEC_DEPCHG == PEC_TAKE, "a deliberate share (see above)");
 // Words of the static dictionary (decode.rs:2593-2640; one command in 33 to 87 of text at -q 4 .. 9, tools/eligibility_survey.py).
 // Round 4's engine stopped in front of each: an invocation and a region's tables for some fifty commands, 3200 clocks a command.
 // Now (one engine): the resolve lets the first such command of what is listed through with its literals alone, wave 0 puts the
@@ -203,7 +192,7 @@ enum { PEC_LBDW = 64, PEC_LE = 65, PEC_L = 66, PEC_LP = 67, PEC_RN = 68, PEC_WN 
 // did, and tells the caller, who takes the general form (PE_CFG_DICT 1) for the rest of the stream.  A stream without such words -- the
 // metric's -- never runs the general form: what that form carries had cost it 4 % through the allocation of one very large function's
 // registers (128 a wave, and the function spills).
-#if PE_CFG_DICT && !PE_CFG_PIPE && !PE_CFG_REMOTE && !defined(BROTLI_AMD_PE_NO_DICT)
+#if PE_CFG_DICT && !PE_CFG_REMOTE
 #define PE_DICT 1
 #else
 #define PE_DICT 0
@@ -412,7 +401,6 @@ __device__ __forceinline__ void pe_eval_n(const PeCtx& c, const uint32_t (&pos)[
     // there, and a lane without a state, or whose run starts beyond them, has nothing to hop)
     uint32_t m[NS]; bool part[NS];
     _Pragma("unroll") for (uint32_t t = 0; t < NS; t++) { part[t] = (bool)((uint32_t)ok[t] & (uint32_t)(y[t] < c.Lp)); m[t] = part[t] ? n[t] : 0u; }
-#ifndef BROTLI_AMD_PE_NO_HOP_ASM
     if constexpr (NS <= 2u) {
       // The same loop by hand.  A state that has stopped hopping -- no literals left, or on the path -- stays stopped, so the
       // lanes still hopping are an execution mask that only ever narrows: v_cmpx drops the lanes, the step itself is an
@@ -449,7 +437,6 @@ __device__ __forceinline__ void pe_eval_n(const PeCtx& c, const uint32_t (&pos)[
 #undef PE_HOP1
 #undef PE_HOP2
     } else
-#endif
     for (uint32_t h = 0; h < PE_HOPCAP; h++) {
       uint32_t f[NS]; bool any = false;
       _Pragma("unroll") for (uint32_t t = 0; t < NS; t++) f[t] = lds_ld8(pb + PE_J1F + (m[t] != 0u ? y[t] : 0u));
@@ -586,20 +573,7 @@ __device__ __forceinline__ void pe_eval_rec(const PeCtx& c, const uint32_t (&d)[
     uint64_t e0, e1, ea, sv;
     // (a state that has stopped hopping -- no literals left, or on the path -- stays stopped: the lanes still hopping are an
     // execution mask that only ever narrows; v_cmpx drops the lanes, the step itself is an add and a decrement)
-#ifndef BROTLI_AMD_PE_REC_HOPS
-#define BROTLI_AMD_PE_REC_HOPS 8
-#endif
-#if BROTLI_AMD_PE_REC_HOPS == 8
 #define PE_HOPS_REC(H) H H H H H H H H
-#elif BROTLI_AMD_PE_REC_HOPS == 6
-#define PE_HOPS_REC(H) H H H H H H
-#elif BROTLI_AMD_PE_REC_HOPS == 5
-#define PE_HOPS_REC(H) H H H H H
-#elif BROTLI_AMD_PE_REC_HOPS == 4
-#define PE_HOPS_REC(H) H H H H
-#elif BROTLI_AMD_PE_REC_HOPS == 12
-#define PE_HOPS_REC(H) H H H H H H H H H H H H
-#endif
 #define PE_HOP1 \
       "s_mov_b64 exec, %[e0]\n\tds_read_u8 %[f0], %[y0]\n\ts_waitcnt lgkmcnt(0)\n\tv_cmpx_gt_u32 vcc, %[c80], %[f0]\n\tv_add_u32 %[y0], %[y0], %[f0]\n\t" \
       "v_subrev_u32 %[m0], 1, %[m0]\n\tv_cmpx_ne_u32 vcc, 0, %[m0]\n\ts_mov_b64 %[e0], exec\n\ts_cmp_eq_u64 %[e0], 0\n\ts_cbranch_scc1 .Lpe_hopr_done_%=\n\t"
@@ -669,10 +643,6 @@ __device__ __forceinline__ PeParse pe_eval(const PeCtx& c, uint32_t pos, uint32_
 // literal, every path position is one of its literals, no records (ReadCommandInternal here, the literals in the run's
 // regions, the distance and the copy in the checked loop: decode.rs:2134-2189, 2393-2462).  `hp` is the local bit of the
 // command's head; on success the stream stands at the run's first literal.
-#ifdef BROTLI_AMD_NO_TRYRUN
-#define PE_TRY_RUN(st_, hp_) do { } while (0)
-#define PE_TRY_RUN_FROM(st_, hp_, min_) do { } while (0)
-#else
 #define PE_TRY_RUN(st_, hp_) PE_TRY_RUN_FROM(st_, hp_, PE_RUN_MIN)
 #define PE_TRY_RUN_FROM(st_, hp_, min_) do { \
     uint32_t lo_, hi_; \
@@ -683,21 +653,8 @@ __device__ __forceinline__ PeParse pe_eval(const PeCtx& c, uint32_t pos, uint32_
       (st_).run_on = 1u; (st_).run_rem = hins_; (st_).run_copy = rfl(h_.copy); (st_).run_implicit = rfl(h_.implicit); (st_).run_dctx = rfl(h_.dctx); \
       (st_).bl1 -= 1u; (st_).ncmd += 1u; (st_).b += hbits_; \
     } } while (0)
-#endif
 
-// The barrier of one engine's waves.  One engine a block: the hardware's.  Two: a counter in the engine's control words that
-// only ever grows -- a wave adds one and waits until all GW have (s_barrier knows the block's waves only, and the other engine is
-// somewhere else in its region).  A wave that waits unreasonably long stops the kernel rather than the machine.
-#if PE_CFG_PIPE
-__device__ __forceinline__ void pe_spin_check(uint32_t& spins) { if (++spins > (1u << 24)) __builtin_trap(); }
-#define PE_SPIN_CHECK(s_) pe_spin_check(s_)
-__device__ __forceinline__ void pe_gbar(const uint32_t pb, uint32_t& target) {
-  target += GW;
-  const uint32_t old = pe_atomic_add_uniform(pb + PE_CTL + 4u * PEC_GBAR, 1u);   // (waits for this wave's LDS traffic: lgkmcnt(0))
-  if (old + 1u != target) { uint32_t spins = 0; while ((int32_t)(pe_ctl_ld(pb, PEC_GBAR) - target) < 0) { __builtin_amdgcn_s_sleep(1); pe_spin_check(spins); } }
-}
-#define PE_BAR() pe_gbar(pb, gb_target)
-#else
+// The barrier of the engine's waves: the hardware's.
 #ifdef BROTLI_AMD_PROFILE_WAVES
 // (profile: what every wave of block 0 spends between two barriers -- its ticks from the release of one to its arrival at the next,
 // by the barrier's place in the source; the slowest wave of a step is the one the block waits for)
@@ -720,7 +677,6 @@ __device__ __forceinline__ void pe_spin_check(uint32_t& spins) { if (++spins > (
 #else
 #define PE_SPIN_CHECK(s_) do { } while (0)
 #endif
-#endif
 
 // One invocation: every wave of the block calls it (wave 0 from process_commands, the others from helper_wave).
 // Returns (wave 0) the number of commands it took; exit form and state in LDS_LEAN as the scan engine leaves them.
@@ -728,9 +684,9 @@ __device__ __forceinline__ void pe_spin_check(uint32_t& spins) { if (++spins > (
 // (PE_DICT) Wave 0, behind a pass that ended with the literals of a command whose copy is a word of the static dictionary: the
 // word goes out behind them (decode.rs:2593-2640, as lean_rec_commands takes them) and the stream's state moves on; PEC_AGAIN
 // says whether the commands behind it get a pass.  A function of its own: it is rare, and the engine's loops stay as they were.
-__device__ __noinline__ void pe_dict_word(const uint32_t pbs, const uint32_t pb, gu8* const out, gcu8* const dict, const uint32_t m) {
+__device__ __noinline__ void pe_dict_word(const uint32_t pb, gu8* const out, gcu8* const dict, const uint32_t m) {
   const uint32_t lane = lane_id();
-  PeStream sw = pe_st_load(pbs);
+  PeStream sw = pe_st_load(pb);
   const uint32_t dd = pe_ctl_ld(pb, PEC_DICTD), wn_ = pe_ctl_ld(pb, PEC_DICTN), kd = pe_ctl_ld(pb, PEC_DICTK);
   const uint32_t maxd = sw.P < (uint64_t)(uint32_t)sw.max_backward ? (uint32_t)sw.P : (uint32_t)sw.max_backward;
   bool word = false; WordShape w = {}; uint32_t word_offset = 0;
@@ -749,7 +705,7 @@ __device__ __noinline__ void pe_dict_word(const uint32_t pbs, const uint32_t pb,
     const uint32_t ob = dictionary_word_bytes(dict, word_offset, w);
     if (lane < w.total) out[sw.P + lane] = (uint8_t)ob;
     sw.P += w.total; sw.quota -= w.total; sw.mlen -= (int32_t)w.total;
-    pe_st_store(pbs, sw);
+    pe_st_store(pb, sw);
     again = (kd + 1u < m && sw.quota >= SC_MIN_QUOTA && sw.bl1 != 0u) ? 1u : 0u;
     if (again != 0u) { pe_ctl_st(pb, PEC_KS, kd + 1u); pe_ctl_st(pb, PEC_P0_LO, (uint32_t)sw.P); pe_ctl_st(pb, PEC_P0_HI, (uint32_t)(sw.P >> 32)); }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -766,22 +722,17 @@ __device__ __noinline__ void pe_dict_word(const uint32_t pbs, const uint32_t pb,
 // the shape of the stores, was the WRITE_SIZE of 1.41 (long back-references) and 2.71 (high-entropy literals) times the
 // output: 1.15 and 1.29 with the waves staying (tools/ubench/write_calib.hip: the counter is exact for every store pattern of
 // this kernel).  The loop around the function's body costs the metric 1 % (the compiler's register allocation of the whole
-// kernel shifts; -DBROTLI_AMD_PE_NO_STAY for the A/B).  Such a wave returns the number of the last request it has answered.
+// kernel shifts).  Such a wave returns the number of the last request it has answered.
 __device__ __noinline__ uint32_t path_engine(const uint32_t me_) {
 pe_again:
   const uint32_t lane = lane_id();
-  const uint32_t eng = PIPE2 ? rfl(me_) / GW : 0u;                // the engine this wave belongs to
-  const uint32_t me = PIPE2 ? rfl(me_) % GW : rfl(me_);           // ... and its number in it
-  const uint32_t T = PIPE2 ? threadIdx.x % (64u * GW) : threadIdx.x;
-  const uint32_t pbs = hc_ld(HC_SCAN_BASE);                       // what the block's engines share
-  const uint32_t pb = pbs + PE_SET0 + eng * PE_SET_BYTES;         // this engine's tables
+  const uint32_t me = rfl(me_);
+  const uint32_t T = threadIdx.x;
+  const uint32_t pb = hc_ld(HC_SCAN_BASE);                        // the engine's tables
   if (T == 0u) { lds_st32(pb + PE_CTL + 4u * PEC_NXOK, 0u); lds_st32(pb + PE_CTL + 4u * PEC_PDX, 0u); lds_st32(pb + PE_CTL + 4u * PEC_OVF, 0u); lds_st32(pb + PE_CTL + 4u * PEC_DSEEN, 0u); }
-  if (PIPE) {   // what the two engines tell each other starts from nothing
-    if (threadIdx.x < 8u) lds_st32(pbs + PE_CTL + 4u * (PEC_RESOLVED + threadIdx.x), 0u);
-    if (T == 0u) lds_st32(pb + PE_CTL + 4u * PEC_GBAR, 0u);
-  }
+  if (REMOTE && T < 7u) lds_st32(pb + PE_CTL + 4u * (PEC_EXECUTED + T), 0u);   // what the blocks of a gang tell each other starts from nothing (EXECUTED .. DECLINE)
   // ---- several CUs on one stream (PE_CFG_REMOTE; the control block's words: GC_* in brotli_kernels.hip) ----
-  // The blocks of a gang take the stream's regions in turns as the two engines of a block do -- region k is block k mod gang's --, each with
+  // The blocks of a gang take the stream's regions in turns -- region k is block k mod gang's --, each with
   // the whole of its CU: the tables of a region (70 K clocks of the 130 K a region costs one CU) are built ahead by as many CUs as it takes,
   // and the stream itself only waits for the walk, the details and the resolve of the region before (and the execute for the output of the
   // region before).  The OWNER is the block that decodes the stream; it comes here from process_commands as ever and is member 0.  The HELPERS
@@ -799,9 +750,9 @@ pe_again:
       epoch = hc_ld(HC_GANG_EPOCH) + 1u;   // (the word is this invocation's once it is everybody's: see below)
       if (pool && gang_m > 1u) {   // this invocation's gang: the helpers that have joined so far, seven at most; nobody: the one-block form's
         // (ONE look for the whole block: helpers join while it is taken)
-        if (threadIdx.x == 0u) { const uint32_t joined = gang_ld32(gc, GC_JOINED); lds_st32(pbs + PE_CTL + 4u * PEC_MEMBERS, 1u + (joined < 7u ? joined : 7u)); }
+        if (threadIdx.x == 0u) { const uint32_t joined = gang_ld32(gc, GC_JOINED); lds_st32(pb + PE_CTL + 4u * PEC_MEMBERS, 1u + (joined < 7u ? joined : 7u)); }
         __syncthreads();
-        gang_m = pe_ctl_ld(pbs, PEC_MEMBERS);
+        gang_m = pe_ctl_ld(pb, PEC_MEMBERS);
       }
       if (epoch >= (1u << 20) - 2u) {   // (the granules' tags hold twenty bits of it: a stream of a million invocations goes on without its gang)
         if (threadIdx.x == 0u) { gang_st32(gc, GC_EPOCH, GC_QUIT); *reinterpret_cast<lds_vu32*>(&g_smem[LDS_HCTL + 4u * HC_GANG_M]) = 1u; }
@@ -832,10 +783,10 @@ pe_again:
         GANG_STAT(gc, 0, 1); GANG_STAT(gc, 5, __builtin_amdgcn_s_memtime() - t0_);
       }
       __syncthreads();
-      const uint32_t ab = (pbs - LDS_FIXED + 15u) & ~15u;   // (the table arena lies between the fixed part and the engine's)
+      const uint32_t ab = (pb - LDS_FIXED + 15u) & ~15u;   // (the table arena lies between the fixed part and the engine's)
       for (uint32_t i = threadIdx.x << 4; i < ab; i += 64u * SC_WAVES * 16u)
         *reinterpret_cast<gu32x4*>(gc + GC_ARENA + i) = *reinterpret_cast<__attribute__((address_space(3))) const u32x4*>(&g_smem[LDS_FIXED + i]);
-      if (threadIdx.x < 32u) *reinterpret_cast<gu32*>(gc + GC_PARAMS + 4u * threadIdx.x) = lds_ld32(pbs + PE_CTL + 4u * threadIdx.x);
+      if (threadIdx.x < 32u) *reinterpret_cast<gu32*>(gc + GC_PARAMS + 4u * threadIdx.x) = lds_ld32(pb + PE_CTL + 4u * threadIdx.x);
       else if (threadIdx.x < 40u) *reinterpret_cast<gu32*>(gc + GC_BR + 4u * (threadIdx.x - 32u)) = lds_ld32(LDS_BR + 4u * (threadIdx.x - 32u));
       else if (threadIdx.x == 40u) *reinterpret_cast<gu32*>(gc + GC_ARENA_BYTES) = ab;
       else if (threadIdx.x == 41u) gang_st64(gc, GC_MEMBERS, ((uint64_t)epoch << 32) | (uint64_t)gang_m);   // (with the invocation it is for: a pool's late comer must not take the next one's for this one's)
@@ -868,7 +819,7 @@ pe_again:
       const uint32_t ab = *reinterpret_cast<gu32*>(gc + GC_ARENA_BYTES);
       for (uint32_t i = threadIdx.x << 4; i < ab && i < GC_ARENA_CAP; i += 64u * SC_WAVES * 16u)
         *reinterpret_cast<__attribute__((address_space(3))) u32x4*>(&g_smem[LDS_FIXED + i]) = *reinterpret_cast<gu32x4*>(gc + GC_ARENA + i);
-      if (threadIdx.x < 32u) lds_st32(pbs + PE_CTL + 4u * threadIdx.x, *reinterpret_cast<gu32*>(gc + GC_PARAMS + 4u * threadIdx.x));
+      if (threadIdx.x < 32u) lds_st32(pb + PE_CTL + 4u * threadIdx.x, *reinterpret_cast<gu32*>(gc + GC_PARAMS + 4u * threadIdx.x));
       else if (threadIdx.x < 40u) lds_st32(LDS_BR + 4u * (threadIdx.x - 32u), *reinterpret_cast<gu32*>(gc + GC_BR + 4u * (threadIdx.x - 32u)));
     }
   }
@@ -877,12 +828,12 @@ pe_again:
   uint64_t pp_acc[32] = {}; uint64_t pp_t = __builtin_amdgcn_s_memtime();
 #endif
   PeCtx c;
-  c.pb = pb; c.td = pbs + PE_TD; c.tc = pbs + PE_TC;
-  c.lit_tree = pe_ctl_ld(pbs, SCC_LIT_TREE); c.cmd_tree = pe_ctl_ld(pbs, SCC_CMD_TREE); c.dtree = pe_ctl_ld(pbs, SCC_DT0);
-  c.postfix_bits = pe_ctl_ld(pbs, SCC_POSTFIX); c.num_direct = pe_ctl_ld(pbs, SCC_NUM_DIRECT);
-  const uint32_t base_dw = pe_ctl_ld(pbs, SCC_BASE_DW), in_limit = pe_ctl_ld(pbs, SCC_IN_LIMIT);
-  gu8* const out = (gu8*)(uintptr_t)((uint64_t)pe_ctl_ld(pbs, SCC_OUT_LO) | ((uint64_t)pe_ctl_ld(pbs, SCC_OUT_HI) << 32));
-  gcu8* const dict = (gcu8*)(uintptr_t)((uint64_t)pe_ctl_ld(pbs, SCC_DICT_LO) | ((uint64_t)pe_ctl_ld(pbs, SCC_DICT_HI) << 32)); (void)dict;
+  c.pb = pb; c.td = pb + PE_TD; c.tc = pb + PE_TC;
+  c.lit_tree = pe_ctl_ld(pb, SCC_LIT_TREE); c.cmd_tree = pe_ctl_ld(pb, SCC_CMD_TREE); c.dtree = pe_ctl_ld(pb, SCC_DT0);
+  c.postfix_bits = pe_ctl_ld(pb, SCC_POSTFIX); c.num_direct = pe_ctl_ld(pb, SCC_NUM_DIRECT);
+  const uint32_t base_dw = pe_ctl_ld(pb, SCC_BASE_DW), in_limit = pe_ctl_ld(pb, SCC_IN_LIMIT);
+  gu8* const out = (gu8*)(uintptr_t)((uint64_t)pe_ctl_ld(pb, SCC_OUT_LO) | ((uint64_t)pe_ctl_ld(pb, SCC_OUT_HI) << 32));
+  gcu8* const dict = (gcu8*)(uintptr_t)((uint64_t)pe_ctl_ld(pb, SCC_DICT_LO) | ((uint64_t)pe_ctl_ld(pb, SCC_DICT_HI) << 32)); (void)dict;
   gcu32* const in_dw = BitReader::base() + base_dw;
   const uint32_t limit_dw = (in_limit + 31u) >> 5;
   c.lut_vgpr = 0;
@@ -892,7 +843,7 @@ pe_again:
   // ---- wave 0: the stream's state (uniform), into its LDS words ----
   if (me == 0 && (!REMOTE || role == 0u)) {
     PeStream st;
-    st.b = pe_ctl_ld(pbs, SCC_ENTRY);  // next command (bits from the engine's origin)
+    st.b = pe_ctl_ld(pb, SCC_ENTRY);  // next command (bits from the engine's origin)
     st.P = (uint64_t)LEAN_LD(L_P_LO) | ((uint64_t)LEAN_LD(L_P_HI) << 32);
     st.quota = LEAN_LD(L_QUOTA); st.mlen = (int32_t)LEAN_LD(L_MLEN);
     st.bl0 = LEAN_LD(L_BL0); st.bl1 = LEAN_LD(L_BL1); st.bl2 = LEAN_LD(L_BL2);
@@ -904,7 +855,7 @@ pe_again:
     st.rbl = PE_RBL;  // bits the next region takes: halved where the closure ran out of room, doubled back where it is small
     st.first = 1u;
     st.s_bits = 0u; st.s_cmds = 0u; st.s_lits = 0u; st.s_dsts = 0u;
-    pe_st_store(pbs, st);
+    pe_st_store(pb, st);
     bool long_first = false;
     if (REMOTE && st.b + 64u <= in_limit) {
       // (a gang) a first command whose literal run wants regions of its own is the one-block form's: seen here, in the stream's own bits,
@@ -917,12 +868,12 @@ pe_again:
     if (REMOTE && gang_m <= 1u) long_first = true;   // (the gang is dissolved, or a pool has sent nobody yet: the same way out)
     if (REMOTE) pe_ctl_st(pb, PEC_NOHELP, gang_m <= 1u && (hc_ld(HC_GANG_M) >> 8) != 0u ? 1u : 0u);
     if (REMOTE) pe_ctl_st(pb, PEC_PLAN, long_first ? 6u : 0u);
-    if (REMOTE && long_first) pe_ctl_st(pbs, PEC_DECLINE, 1u);
+    if (REMOTE && long_first) pe_ctl_st(pb, PEC_DECLINE, 1u);
     if (REMOTE && !long_first) {   // the invocation is everybody's: the stream's state in front of region 0, the plan (from region 0 on, at the entry), then its number
       hc_st(HC_GANG_EPOCH, epoch);
       hc_st(HC_GANG_READY, hc_ld(HC_GANG_READY) + gang_m - 1u);   // (what READY says when this invocation's helpers have all left it)
       lds_sync();
-      const uint32_t v = lane < 25u ? *reinterpret_cast<lds_vu32*>(&g_smem[pbs + PE_CTL + 4u * (PEC_STATE + (lane < 25u ? lane : 0u))]) : lane == 25u ? 1u : 0u;
+      const uint32_t v = lane < 25u ? *reinterpret_cast<lds_vu32*>(&g_smem[pb + PE_CTL + 4u * (PEC_STATE + (lane < 25u ? lane : 0u))]) : lane == 25u ? 1u : 0u;
       if (lane < GC_STATE_WORDS) gang_st64(gc, GC_STATE + 8u * lane, (uint64_t)v | ((uint64_t)(epoch << 12) << 32));
       if (lane == 0u) { gang_st64(gc, GC_PLAN, (uint64_t)st.b); gang_st64(gc, GC_ENTRY, (uint64_t)st.b | ((uint64_t)(epoch << 12) << 32)); }
       gang_drain();
@@ -936,14 +887,14 @@ pe_again:
     const uint32_t copy_code = (((0x262444u >> (cell * 2)) & 3u) << 3) | (i & 7u);
     lds_st32(c.tc + (i << 2), (uint32_t)kInsBase[ins_code] | ((uint32_t)kInsExtra[ins_code] << 15) | ((uint32_t)kCopyExtra[copy_code] << 20) | (i < 128u ? 1u << 25 : 0u));
   }
-  if (threadIdx.x == 0u) lds_st32(pbs + PE_CTL + 4u * PEC_TDN, 256u);
+  if (threadIdx.x == 0u) lds_st32(pb + PE_CTL + 4u * PEC_TDN, 256u);
   __syncthreads();
   if (threadIdx.x < 256u) {
     const uint32_t e = lds_ld16(c.dtree + (threadIdx.x << 1)), Ld = e & 15u;
-    if (Ld > ROOT_BITS) __hip_atomic_fetch_max(reinterpret_cast<pe_lds_u32*>(&g_smem[pbs + PE_CTL + 4u * PEC_TDN]), (e >> 4) + (1u << (Ld - ROOT_BITS)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (Ld > ROOT_BITS) __hip_atomic_fetch_max(reinterpret_cast<pe_lds_u32*>(&g_smem[pb + PE_CTL + 4u * PEC_TDN]), (e >> 4) + (1u << (Ld - ROOT_BITS)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   }
   __syncthreads();
-  const uint32_t td_n = pe_ctl_ld(pbs, PEC_TDN);
+  const uint32_t td_n = pe_ctl_ld(pb, PEC_TDN);
   for (uint32_t i = threadIdx.x; i < td_n && i < PE_TD_ENTRIES; i += 64u * SC_WAVES) {
     uint32_t e = lds_ld16(c.dtree + (i << 1));
     const uint32_t l4 = e & 15u;
@@ -961,9 +912,8 @@ pe_again:
 #ifdef BROTLI_AMD_PROFILE_WAVES
   uint64_t wp_t = __builtin_amdgcn_s_memtime(); (void)wp_t;
 #endif
-  uint32_t gb_target = 0; (void)gb_target;               // (two engines: this engine's barriers so far, times GW)
   uint32_t rseq = 0;                                     // regions of this invocation so far (the one at hand included)
-  uint32_t kseq = 0; (void)kseq;                         // (two engines: the number of the region this engine is at)
+  uint32_t kseq = 0; (void)kseq;                         // (a gang: the number of the region this engine is at)
   uint64_t gs_arr = 0; (void)gs_arr;                     // (gang statistics: when the stream arrived at this engine's region)
 #ifdef BROTLI_AMD_GANG_TRACE   // (a gang: a line a region of invocation BROTLI_AMD_GANG_TRACE with wave 0's clock at every hand-over -- which chain binds?)
   uint64_t gt_ts[15] = {};
@@ -1149,7 +1099,7 @@ pe_again:
     const uint32_t Rn = pe_ctl_ld(pb, PEC_RN);
     PE_COUNT(22, Rn);
     if (me == 0) {
-      const PeStream st = pe_st_load(pbs);
+      const PeStream st = pe_st_load(pb);
       uint32_t take = st.run_rem;
       const uint32_t cap1 = Rn != 0u ? Rn - 1u : 0u, cap2 = st.quota > 1u ? st.quota - 1u : 0u;
       take = take < cap1 ? take : cap1; take = take < st.bl0 ? take : st.bl0; take = take < cap2 ? take : cap2;
@@ -1169,18 +1119,17 @@ pe_again:
     PE_PROF(4);
     write_out(rl, out + P0, take);
     if (me == 0) {
-      PeStream st = pe_st_load(pbs);
+      PeStream st = pe_st_load(pb);
       st.P += take; st.quota -= take; st.bl0 -= take; st.mlen -= (int32_t)take; st.run_rem -= take;
       const uint32_t npb = take != 0u ? pe_ctl_ld(pb, PEC_NEXTRANK) : ent;
       st.b = (lbdw << 5) + npb;
       pe_ctl_st(pb, PEC_CONT, (take != 0u && st.run_rem != 0u) ? 1u : 0u); pe_ctl_st(pb, PEC_NEXT_LBDW, st.b >> 5);
       pe_ctl_st(pb, PEC_FIN, (st.run_rem == 0u && npb + 96u <= c.L + 128u) ? 1u : 0u);
       PE_COUNT(19, take);
-      pe_st_store(pbs, st);
+      pe_st_store(pb, st);
     }
     PE_BAR();
     PE_PROF(5);
-#ifndef BROTLI_AMD_PE_NO_RUN_FINISH
     if (pe_ctl_ld(pb, PEC_FIN) != 0u) {
       // The run is over: what is left of its command is a distance and a copy (decode.rs:2066-2131, 2583-2720).  Round 4 handed every
       // such command to the checked loop -- the invocation ended, the loop finished the command, and the engine came back for the next one
@@ -1189,7 +1138,7 @@ pe_again:
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the run's literals are in memory before the copy reads them)
       PE_BAR();
       if (me == 0) {
-        PeStream st = pe_st_load(pbs);
+        PeStream st = pe_st_load(pb);
         const uint32_t yb = st.b - (lbdw << 5);
         uint32_t dbits = 0, push = 0; int32_t dist = st.d0; bool ok_ = true;
         if (st.run_implicit == 0u) {
@@ -1233,13 +1182,12 @@ pe_again:
           st.run_on = 0u; st.run_rem = 0u; st.run_copy = 0u; st.run_implicit = 0u; st.run_dctx = 0u;
           st.first = 1u;   // (the next region looks at its first command as an invocation's first region does: another long run, as a rule)
           st.s_cmds = 0u;
-          pe_st_store(pbs, st);
+          pe_st_store(pb, st);
           pe_ctl_st(pb, PEC_CONT, 1u); pe_ctl_st(pb, PEC_NEXT_LBDW, st.b >> 5);
         }
       }
       PE_BAR();
     }
-#endif
     if (pe_ctl_ld(pb, PEC_CONT) == 0u) return 2u;
     {
       const uint32_t nl = pe_ctl_ld(pb, PEC_NEXT_LBDW);
@@ -1261,10 +1209,10 @@ pe_again:
     pre_ok = false;
     PE_BAR();
     PE_PROF(0);
-    if (!PIPE && me == 0 && pe_ctl_ld(pbs, PEC_STATE + 20) != 0u) {
+    if (!REMOTE && me == 0 && pe_ctl_ld(pb, PEC_STATE + 20) != 0u) {
       // the invocation's first region: is its first command one with a long literal run?  (later regions know from the resolve
       // of the region before)
-      PeStream st = pe_st_load(pbs);
+      PeStream st = pe_st_load(pb);
       st.first = 0u;
       if (c.L >= 256u) {
         PE_TRY_RUN(st, le);
@@ -1275,16 +1223,13 @@ pe_again:
           pe_ctl_st(pb, PEC_MODE, 1u); pe_ctl_st(pb, PEC_ENT, st.b - (lbdw << 5)); pe_ctl_st(pb, PEC_L, avail_ < PE_RUN_RBL ? avail_ : PE_RUN_RBL);
         }
       }
-      pe_st_store(pbs, st);
+      pe_st_store(pb, st);
     }
-#if !PE_CFG_PIPE && !PE_CFG_REMOTE && !defined(BROTLI_AMD_PE_OLD_RUN_REGIONS)
+#if !PE_CFG_REMOTE
     PE_BAR();   // (the first region's mode is wave 0's word)
     if (pe_ctl_ld(pb, PEC_MODE) != 0u) { c.L = pe_ctl_ld(pb, PEC_L); return run_region(); }
 #endif
     // ---- J1: the length of the literal code word at every bit, eight bits per lane and pass ----
-#if defined(BROTLI_AMD_PE_REPEAT) && BROTLI_AMD_PE_REPEAT == 1
-    for (int rep_ = 0; rep_ < 2; rep_++)
-#endif
     for (uint32_t g = T; g < PE_RBL / 8u; g += 64u * GW) {
       const uint32_t pos0 = g << 3;
       const uint32_t v = pe_bits32(pb, pos0);
@@ -1447,7 +1392,7 @@ pe_again:
       // the region hold (one short of each limit: what happens AT a limit is the checked loop's), go out; the next region
       // starts behind them ----
       if (me == 0) {
-        const PeStream st = pe_st_load(pbs);
+        const PeStream st = pe_st_load(pb);
         uint32_t take = st.run_rem;
         const uint32_t cap1 = c.Rn != 0u ? c.Rn - 1u : 0u, cap2 = st.quota > 1u ? st.quota - 1u : 0u;
         take = take < cap1 ? take : cap1; take = take < st.bl0 ? take : st.bl0; take = take < cap2 ? take : cap2;
@@ -1464,13 +1409,13 @@ pe_again:
         }
       }
       if (me == 0) {
-        PeStream st = pe_st_load(pbs);
+        PeStream st = pe_st_load(pb);
         st.P += take; st.quota -= take; st.bl0 -= take; st.mlen -= (int32_t)take; st.run_rem -= take;
         const uint32_t np = take != 0u ? rfl(lds_ld16(pb + PE_POR + (take << 1))) : ent;
         st.b = (lbdw << 5) + np;
         pe_ctl_st(pb, PEC_CONT, (take != 0u && st.run_rem != 0u) ? 1u : 0u); pe_ctl_st(pb, PEC_NEXT_LBDW, st.b >> 5);
         PE_COUNT(19, take);
-        pe_st_store(pbs, st);
+        pe_st_store(pb, st);
       }
       PE_BAR();
       if (pe_ctl_ld(pb, PEC_CONT) == 0u) return 2u;
@@ -1593,7 +1538,7 @@ pe_again:
     PE_COUNT(24, pe_ctl_ld(pb, PEC_WN) < PE_WCAP ? pe_ctl_ld(pb, PEC_WN) : PE_WCAP);
     wn = pe_ctl_ld(pb, PEC_WN) < PE_WCAP ? pe_ctl_ld(pb, PEC_WN) : PE_WCAP;
     if (me == 0) {
-      const uint32_t raw = pe_ctl_ld(pb, PEC_WN); uint32_t rbl = pe_ctl_ld(pbs, PEC_STATE + 8);
+      const uint32_t raw = pe_ctl_ld(pb, PEC_WN); uint32_t rbl = pe_ctl_ld(pb, PEC_STATE + 8);
       if (raw > PE_WCAP - PE_WCAP / 8u) {
         rbl = rbl > 8192u ? rbl >> 1 : rbl;
         // (a stream of few literals -- an executable: short copies one after the other -- has few path positions and long chains of
@@ -1601,13 +1546,10 @@ pe_again:
         // stream, a parse at every bit and no chains.  256 x libc.so.6 at -q 5: 0.39 against 0.77 G commands/s)
         pe_ctl_st(pb, PEC_OVF, pe_ctl_ld(pb, PEC_OVF) + 1u);
       } else if (raw < PE_GROW_BELOW && rbl < PE_RBL) rbl <<= 1;
-      pe_ctl_st(pbs, PEC_STATE + 8, rbl);
+      pe_ctl_st(pb, PEC_STATE + 8, rbl);
     }
     PE_PROF(4);
     // ---- NEXT8: the state eight commands on (PEN_NONE where the way there is not all records) ----
-#if defined(BROTLI_AMD_PE_REPEAT) && BROTLI_AMD_PE_REPEAT == 4
-    for (int rep_ = 0; rep_ < 2; rep_++)
-#endif
     // (twelve states a lane side by side -- a region's states in one go, as a rule --: the phase is eight dependent LDS round
     // trips whatever the number of states a lane carries through them)
     for (uint32_t j0 = T; j0 < c.Rn + wn; j0 += 12u * 64u * GW) {
@@ -1673,9 +1615,9 @@ pe_again:
     GANG_STAT(gc, 39, __builtin_amdgcn_s_memtime() - t0_);
     uint32_t ok_ = 0u;
     if (arrived && (rdlane((uint32_t)v, 25) & 1u) != 0u) {   // (the region before's resolve said that the stream goes on)
-      if (lane < 25u) lds_st32(pbs + PE_CTL + 4u * (PEC_STATE + lane), (uint32_t)v);   // the state into this engine's own words
+      if (lane < 25u) lds_st32(pb + PE_CTL + 4u * (PEC_STATE + lane), (uint32_t)v);   // the state into this engine's own words
       lds_sync();
-      const PeStream st = pe_st_load(pbs);
+      const PeStream st = pe_st_load(pb);
       ok_ = (walked && st.b == pe_ctl_ld(pb, PEC_MYENTRY) && st.quota >= SC_MIN_QUOTA && st.bl1 != 0u) ? 1u : 0u;
       pe_ctl_st(pb, PEC_P0_LO, (uint32_t)st.P); pe_ctl_st(pb, PEC_P0_HI, (uint32_t)(st.P >> 32));
       { const uint32_t rl = pe_ctl_ld(pb, PEC_RELAX), g26 = rdlane((uint32_t)v, 26), g27 = rdlane((uint32_t)v, 27);   // (the sizes of the two regions before this one)
@@ -1683,7 +1625,7 @@ pe_again:
         pe_ctl_st(pb, PEC_LAG, rl == 2u ? g26 + g27 : rl == 1u ? g26 : 0u); }
     }
     if (ok_ == 0u) {
-      if (!arrived) GANG_STAT(gc, 32, 1); else if ((rdlane((uint32_t)v, 25) & 1u) == 0u) GANG_STAT(gc, 33, 1); else { const PeStream st = pe_st_load(pbs); if (st.b != pe_ctl_ld(pb, PEC_MYENTRY)) GANG_STAT(gc, 34, 1); else GANG_STAT(gc, 36, 1); }
+      if (!arrived) GANG_STAT(gc, 32, 1); else if ((rdlane((uint32_t)v, 25) & 1u) == 0u) GANG_STAT(gc, 33, 1); else { const PeStream st = pe_st_load(pb); if (st.b != pe_ctl_ld(pb, PEC_MYENTRY)) GANG_STAT(gc, 34, 1); else GANG_STAT(gc, 36, 1); }
       if (arrived && lane == 0u) gang_st64(gc, GC_STOP, ((uint64_t)epoch << 32) | (uint64_t)kseq);   // (the same word, if the resolve before has written it)
       pe_ctl_st(pb, PEC_CONT, 0u);
     }
@@ -1706,8 +1648,8 @@ pe_again:
       if (REMOTE) GANG_STAT(gc, 28, __builtin_amdgcn_s_memtime() - gs_arr);   // arrival .. the walk's start
       __builtin_amdgcn_s_setprio(3);  // (the walk is the one chain everybody waits for: first in line on its SIMD)
       uint32_t id = PE_RANKS, na = 0;
-      uint32_t id_hand = PEN_NONE;   // (two engines) the first of the states the walk added itself: NEXT8 does not know them
-      if (PIPE) {
+      uint32_t id_hand = PEN_NONE;   // (a gang) the first of the states the walk added itself: NEXT8 does not know them
+      if (REMOTE) {
         // The tables were built before the stream's entry into the region was known: the state it enters in -- a command starts
         // at bit `le` -- is evaluated here, and the states it leads to, until one of them is a path state (as a rule the first
         // or the second).  They join the closure behind the ones the records put there.
@@ -1744,7 +1686,6 @@ pe_again:
         }
         lds_sync();
       }
-#if !PE_CFG_PIPE && !defined(BROTLI_AMD_PE_NO_WALK_ASM)
       bool walk_on = true;
       if (REMOTE) {
         // (a gang: the anchors up to the first one that stands on a state NEXT8 knows -- as a rule the first -- by the records, eight hops each)
@@ -1784,28 +1725,13 @@ pe_again:
           : [id] "+s"(id), [na] "+s"(na), [aa] "+s"(aa), [vr] "=&v"(vr), [va] "=&v"(va), [vt] "=&v"(vt), [sv] "=&s"(sv), [n8s] "=&s"(n8s), [ts] "=&s"(ts)
           : [n8base] "s"(n8base), [pub] "s"(pubaddr), [cap] "s"(cap) : "scc", "memory");
       }
-#else
-      for (;;) {
-        uint32_t n8;
-        if (PIPE && id >= id_hand && id < PEN_FIRST_SPECIAL) {   // eight records on from a state NEXT8 has not seen (the walk's own): by the records
-          n8 = id;
-          for (uint32_t h = 0; h < PE_JUMP; h++) n8 = n8 < PEN_FIRST_SPECIAL ? rfl(lds_ld16(pb + PE_NEXT + (n8 << 1))) : (uint32_t)PEN_NONE;
-        } else n8 = id < PEN_FIRST_SPECIAL ? rfl(lds_ld16(pb + PE_N8 + (id << 1))) : (uint32_t)PEN_NONE;
-        if (n8 >= PEN_FIRST_SPECIAL || na >= (PE_CMDS - 64u) / PE_JUMP) break;
-        if (lane == 0) {
-          *reinterpret_cast<lds_vu32*>(&g_smem[pb + PE_ANCH + (na << 2)]) = id;
-          *reinterpret_cast<lds_vu32*>(&g_smem[pb + PE_CTL + 4u * PEC_NAPUB]) = na + 1u;
-        }
-        na++; id = n8;
-      }
-#endif
       // ... then the commands behind the last anchor, up to the first record that is no way on: lane j follows the records j
       // commands on (the lanes side by side: a dozen dependent reads for all of them, where one command after the other by the
       // wave as a whole cost a third of the walk), the list's entries are theirs
-      if (!PIPE) PE_PROF(15);   // (one engine: the anchors)
+      if (!REMOTE) PE_PROF(15);   // (one block: the anchors)
       if (REMOTE) GANG_STAT(gc, 38, __builtin_amdgcn_s_memtime() - gs_arr);   // .. the anchors
       uint32_t m = PE_JUMP * na, desc;
-      if (PIPE && id >= PEN_FIRST_SPECIAL) { desc = le | 0x8000u; if (lane == 0) lds_st16(pb + PE_LIST, desc); }   // (no room for the entry's state: nothing listed -- the list's closing entry says where the stream stands)
+      if (REMOTE && id >= PEN_FIRST_SPECIAL) { desc = le | 0x8000u; if (lane == 0) lds_st16(pb + PE_LIST, desc); }   // (no room for the entry's state: nothing listed -- the list's closing entry says where the stream stands)
       else for (;;) {
         uint32_t sv = id;
         for (uint32_t h = 0; h < 63u; h++) {
@@ -1822,11 +1748,11 @@ pe_again:
         if (J < 64u) { m += J; desc = rdlane(dv, J); id = rdlane(sv, J); break; }
         m += 64u; id = rdlane(nxv, 63);
       }
-      if (!PIPE) PE_PROF(16);   // (one engine: the commands behind the last anchor)
+      if (!REMOTE) PE_PROF(16);   // (one block: the commands behind the last anchor)
       // the last command needs its distance: 64 bits at the closing state
       if (m != 0u && (desc >> 15) == 0u && (desc & 0x7FFFu) + 64u > c.L) m--;
 #ifdef BROTLI_AMD_PE_DEBUG
-      if (PIPE && blockIdx.x == 0 && lane == 0 && kseq >= 33u && kseq <= 36u) {
+      if (REMOTE && blockIdx.x == 0 && lane == 0 && kseq >= 33u && kseq <= 36u) {
         printf("   walk of region %u: le %u, id_hand %u, anchors %u, listed %u, closing state %x (id %u), L %u Lp %u\n", kseq, le, id_hand, na, m, desc, id, c.L, c.Lp);
         for (uint32_t q = 0; q < 4u; q++) printf("     hand state %u: desc %x next %u\n", q, lds_ld16(pb + PE_WST + ((wn + q) << 1)), lds_ld16(pb + PE_NEXT + ((PE_RANKS + wn + q) << 1)));
         for (uint32_t q = 0; q < (m < 12u ? m + 1u : 12u); q++) printf("     list %u: %x\n", q, lds_ld16(pb + PE_LIST + (q << 1)));
@@ -1861,7 +1787,6 @@ pe_again:
           }
         }
         if (lane == 0u) gang_st64(gc, GC_ENTRY, (uint64_t)((pe_ctl_ld(pb, PEC_LBDW) << 5) + nbit) | ((uint64_t)((epoch << 12) | (kseq + 1u)) << 32));
-        pe_ctl_st(pb, PEC_MYNEXT, (pe_ctl_ld(pb, PEC_LBDW) << 5) + nbit);
       }
       pe_ctl_st(pb, PEC_M, m); pe_ctl_st(pb, PEC_NA, na);
       lds_sync();
@@ -1935,7 +1860,7 @@ pe_pass:
       // (a gang: the stream's state is the region before's resolve's to send, and what this resolve does in front of its first barrier -- the sums, the ring
       // against an unknown ring -- does not ask for it: wave 0 waits for it behind that, see full_arrival)
       PeStream st{};
-      if (!REMOTE) st = pe_st_load(pbs);
+      if (!REMOTE) st = pe_st_load(pb);
       const bool mine = bw < nb;
       const uint32_t k0 = bw << 6;
       const uint32_t K = mine ? (m - k0 < 64u ? m - k0 : 64u) : 0u;
@@ -2010,7 +1935,7 @@ pe_pass:
       if (REMOTE) {
         if (pe_ctl_ld(pb, PEC_PLAN) == 2u) return;
         P0 = (uint64_t)pe_ctl_ld(pb, PEC_P0_LO) | ((uint64_t)pe_ctl_ld(pb, PEC_P0_HI) << 32);
-        st = pe_st_load(pbs);
+        st = pe_st_load(pb);
       }
       // what lies in front of this batch
       uint32_t c_lit = 0, c_cmd = 0, c_dst = 0, c_out = 0;
@@ -2092,13 +2017,13 @@ pe_pass:
         const uint64_t pk = st.P + rel + ins;
         const int32_t maxd = pk < (uint64_t)(uint32_t)st.max_backward ? (int32_t)pk : st.max_backward;
         if (PE_DICT) dictc = (bool)((uint32_t)ok & (uint32_t)(kind == SCK_EXPLICIT) & (uint32_t)(dist > maxd) & (uint32_t)!plainw);   // (`ok` so far: an active lane, its counts and its output -- the copy's length for the word's -- inside every limit)
-        if (!PE_DICT && !PIPE2) dref = (bool)((uint32_t)ok & (uint32_t)(kind == SCK_EXPLICIT) & (uint32_t)(dist > maxd));
+        if (!PE_DICT) dref = (bool)((uint32_t)ok & (uint32_t)(kind == SCK_EXPLICIT) & (uint32_t)(dist > maxd));
         ok = ok && (kind == SCK_NONE || plainw || (dist > 0 && dist <= maxd));
       }
       const uint64_t stopmask = __ballot(active && !ok);
       uint32_t kpb = stopmask ? (uint32_t)__builtin_ctzll(stopmask) : K;
       const uint64_t dictmask = PE_DICT ? __ballot(dictc) : 0ull;
-      const uint64_t drefmask = (!PE_DICT && !PIPE2) ? __ballot(dref) : 0ull;
+      const uint64_t drefmask = (!PE_DICT) ? __ballot(dref) : 0ull;
       if (PE_DICT && stopmask != 0ull && ((dictmask >> kpb) & 1ull) != 0ull) kpb++;   // (the pass ends BEHIND such a command's literals)
       if (mine && stopmask != 0ull && lane == 0) pe_atomic_min(pb + PE_CTL + 4u * PEC_KP, k0 + kpb);
       // a copy whose source reaches into the region's own output is done afterwards (bit 31 of w0); long items get a wave
@@ -2136,7 +2061,7 @@ pe_pass:
         const bool last = kp_total <= k0 + K;
         if (last) {
           const uint32_t kp = my_exec;
-          if (!PE_DICT && !PIPE2 && kp < 64u && ((drefmask >> kp) & 1ull) != 0ull) pe_ctl_st(pb, PEC_DSEEN, 1u);   // (the command the engine's part ends in front of)
+          if (!PE_DICT && kp < 64u && ((drefmask >> kp) & 1ull) != 0ull) pe_ctl_st(pb, PEC_DSEEN, 1u);   // (the command the engine's part ends in front of)
           // (PE_DICT: the pass's last command is one whose copy is a dictionary word -- wave 0's, behind the execute: its copy length
           // is not output of this pass, its distance not one for the ring, decode.rs:2643-2644)
           const bool dlast = PE_DICT && ((dictmask >> (kp - 1u)) & 1ull) != 0ull;
@@ -2156,7 +2081,7 @@ pe_pass:
           sn.P += out_tot; sn.bl0 -= lit_tot; sn.bl1 -= cmd_tot; sn.bl2 -= dst_tot; sn.quota -= out_tot; sn.mlen -= (int32_t)out_tot; sn.ncmd += cmd_tot;
           sn.d0 = e0; sn.d1 = e1; sn.d2 = e2; sn.d3 = e3;
           sn.s_cmds = cmd_tot; sn.s_lits = lit_tot; sn.s_dsts = dst_tot;   // (s_bits: wave 0, below, once it knows where the stream goes on)
-          pe_st_store(pbs, sn);
+          pe_st_store(pb, sn);
           pe_ctl_st(pb, PEC_ANYDEP, c_dep + (uint32_t)__popcll(dm2)); pe_ctl_st(pb, PEC_NBIG, c_big + (uint32_t)__popcll(bm2)); pe_ctl_st(pb, PEC_NWORD, c_word + (uint32_t)__popcll(wm2));
           pe_ctl_st(pb, PEC_OUTTOT, out_tot); pe_ctl_st(pb, PEC_STAGED, (PE_STG_CAP != 0u && out_tot <= PE_STG_CAP) ? 1u : 0u);
         }
@@ -2169,7 +2094,7 @@ pe_pass:
       if (me == 0) {
         // where the stream goes on: the first bit of command kp_total (its head: behind the distance code, if there is one,
         // of the state it starts from)
-        PeStream sn = pe_st_load(pbs);
+        PeStream sn = pe_st_load(pb);
         const uint32_t dsc = rfl(lds_ld16(pb + PE_LIST + (kp_total << 1)));
         uint32_t pbit = dsc & 0x7FFFu;
         if ((dsc >> 15) == 0u) {
@@ -2181,27 +2106,27 @@ pe_pass:
         { const uint32_t nb_ = (pe_ctl_ld(pb, PEC_LBDW) << 5) + pbit; sn.s_bits = kp_total > ks ? nb_ - sn.b : 0u; if (kp_total <= ks) sn.s_cmds = 0u; sn.b = nb_; }
         // the region went through whole and the next one starts at a command with a long literal run: the next regions are the run's
         const bool dict_ends = PE_DICT && pe_ctl_ld(pb, PEC_DICTK) != 0xFFFFFFFFu;   // (the pass ends with a dictionary word still to come: no run region from here -- the next region finds the run itself)
-        if (!PIPE && !dict_ends && kp_total == m && m != 0u && pbit + 64u <= c.L) PE_TRY_RUN(sn, pbit);
+        if (!REMOTE && !dict_ends && kp_total == m && m != 0u && pbit + 64u <= c.L) PE_TRY_RUN(sn, pbit);
         // ... or the region listed nothing because its first command's literal run is more than its path holds (4300 literals of
         // 7.5 bits) though less than PE_RUN_MIN: regions of its own all the same -- giving the command back would keep the engine
         // away from the commands behind it too (seen on the high-entropy streams: the rest of a metablock on one wave)
-        if (!PIPE && m == 0u && pbit + 64u <= c.L) PE_TRY_RUN_FROM(sn, pbit, 1024u);
+        if (!REMOTE && m == 0u && pbit + 64u <= c.L) PE_TRY_RUN_FROM(sn, pbit, 1024u);
         pe_ctl_st(pb, PEC_NEXT_LBDW, sn.b >> 5);
         // an invocation goes on with the next region while whole regions go through; anything else is the checked loop's
-        bool cont = (kp_total == m && m != 0u) || (!PIPE && m == 0u && sn.run_on != 0u);
-        if (!PIPE && pe_ctl_ld(pb, PEC_OVF) >= 3u && sn.run_on == 0u) cont = false;   // (closure-bound: see the records)
-        if (PIPE && cont && pbit + 64u <= c.L) {
-          // (two engines: a command whose literal run wants regions of its own ends the invocation in front of it -- the one-engine
+        bool cont = (kp_total == m && m != 0u) || (!REMOTE && m == 0u && sn.run_on != 0u);
+        if (!REMOTE && pe_ctl_ld(pb, PEC_OVF) >= 3u && sn.run_on == 0u) cont = false;   // (closure-bound: see the records)
+        if (REMOTE && cont && pbit + 64u <= c.L) {
+          // (a gang: a command whose literal run wants regions of its own ends the invocation in front of it -- the one-block
           // form has those regions, and the caller is told to take it next)
           uint32_t lo_, hi_;
           pe_bits64(pb, pbit, lo_, hi_);
           const ScHead h_ = sc_head(lo_, hi_, c.cmd_tree, c.lut_vgpr);
-          if (rfl(h_.insert) >= (REMOTE ? PE_RUN_MIN : PE_PIPE_DECLINE)) { cont = false; pe_ctl_st(pbs, PEC_DECLINE, 1u); }   // (a gang's regions are whole ones: what one of them holds, it takes)
+          if (rfl(h_.insert) >= PE_RUN_MIN) { cont = false; pe_ctl_st(pb, PEC_DECLINE, 1u); }   // (a gang's regions are whole ones: what one of them holds, it takes)
         }
         if (REMOTE && wn + 64u > PE_WCAP) {
           // (a gang: the closure has filled its room -- a stretch of few literals; the one-block form halves its regions there and hands such
           // streams to the scan engine, this form has no room left for the entry's states: the rest of the metablock is the one-block form's)
-          cont = false; pe_ctl_st(pbs, PEC_DECLINE, 3u);
+          cont = false; pe_ctl_st(pb, PEC_DECLINE, 3u);
         }
         if (REMOTE && m == 0u && pbit + 64u <= c.L) {
           // (a gang: the region listed nothing -- as a rule its first command's literal run is more than what is left of the window holds: the
@@ -2210,33 +2135,24 @@ pe_pass:
           uint32_t lo_, hi_;
           pe_bits64(pb, pbit, lo_, hi_);
           const ScHead h_ = sc_head(lo_, hi_, c.cmd_tree, c.lut_vgpr);
-          if (rfl(h_.insert) >= 1024u) pe_ctl_st(pbs, PEC_DECLINE, pe_ctl_ld(pbs, PEC_DECLINE) | 1u);
+          if (rfl(h_.insert) >= 1024u) pe_ctl_st(pb, PEC_DECLINE, pe_ctl_ld(pb, PEC_DECLINE) | 1u);
         }
         if (REMOTE && !cont) GANG_STAT(gc, 37, 1);
         if (REMOTE && !cont && kp_total != m) GANG_STAT(gc, 35, 1);
 #ifdef BROTLI_AMD_PE_DEBUG
-        if (PIPE && blockIdx.x == 0 && lane == 0) printf("   region %u: %u commands listed, %u executed, goes on at %u, cont %u, P now %llu ncmd %u\n", kseq, m, kp_total, sn.b, cont ? 1u : 0u, (unsigned long long)sn.P, sn.ncmd);
+        if (REMOTE && blockIdx.x == 0 && lane == 0) printf("   region %u: %u commands listed, %u executed, goes on at %u, cont %u, P now %llu ncmd %u\n", kseq, m, kp_total, sn.b, cont ? 1u : 0u, (unsigned long long)sn.P, sn.ncmd);
 #endif
         if (REMOTE && kseq + 1u >= GC_MAX_REGIONS) cont = false;   // (the tags of the state's granules count regions in twelve bits)
         pe_ctl_st(pb, PEC_CONT, cont ? 1u : 0u);  // (a word of its own: wave 0 writes PEC_GO for the next region while the others may still be here)
-        pe_st_store(pbs, sn);
-        if (!PIPE) { lds_sync(); pe_ctl_st(pb, PEC_NXOK, rseq); }
+        pe_st_store(pb, sn);
+        if (!REMOTE) { lds_sync(); pe_ctl_st(pb, PEC_NXOK, rseq); }
         if (REMOTE) {
           // the stream's state is the next region's from here on: granule by granule, each with the tag its reader waits for; the
           // invocation's end in a word of its own behind them (whoever waits for a region that will not come looks at it)
-          pe_ctl_st(pb, PEC_MYNEXT, sn.b);
           lds_sync();
-          const uint32_t v = lane < 25u ? *reinterpret_cast<lds_vu32*>(&g_smem[pbs + PE_CTL + 4u * (PEC_STATE + (lane < 25u ? lane : 0u))]) : lane == 25u ? (cont ? 1u : 0u) | ((pe_ctl_ld(pbs, PEC_DECLINE) & 3u) << 1) | (pe_ctl_ld(pb, PEC_DSEEN) != 0u ? 8u : 0u) : lane == 27u ? pe_ctl_ld(pb, PEC_PREVOUT) : pe_ctl_ld(pb, PEC_OUTTOT);
+          const uint32_t v = lane < 25u ? *reinterpret_cast<lds_vu32*>(&g_smem[pb + PE_CTL + 4u * (PEC_STATE + (lane < 25u ? lane : 0u))]) : lane == 25u ? (cont ? 1u : 0u) | ((pe_ctl_ld(pb, PEC_DECLINE) & 3u) << 1) | (pe_ctl_ld(pb, PEC_DSEEN) != 0u ? 8u : 0u) : lane == 27u ? pe_ctl_ld(pb, PEC_PREVOUT) : pe_ctl_ld(pb, PEC_OUTTOT);
           if (lane < GC_STATE_WORDS) gang_st64(gc, GC_STATE + 8u * lane, (uint64_t)v | ((uint64_t)((epoch << 12) | (kseq + 1u)) << 32));
           if (!cont) { gang_drain(); if (lane == 0u) gang_st64(gc, GC_STOP, ((uint64_t)epoch << 32) | (uint64_t)(kseq + 1u)); }
-        }
-        if (PIPE2) {
-          pe_ctl_st(pb, PEC_MYNEXT, sn.b);
-          // the stream's state is the next region's from here on; the invocation's end is everybody's to know first
-          lds_sync();
-          if (!cont) pe_ctl_st(pbs, PEC_STOP, 1u);
-          lds_sync();
-          pe_ctl_st(pbs, PEC_RESOLVED, kseq + 1u);
         }
       }
     }
@@ -2276,13 +2192,13 @@ pe_pass:
       }
       else if (kseq != 0u) { waited1 = await_output(kseq, 8u); if (waited1 > 6000u && gang_m >= 8u) pe_ctl_st(pb, PEC_RELAX, 1u); GANG_STAT(gc, 30, 1); }
       lds_sync();
-      pe_ctl_st(pbs, PEC_EXECUTED, kseq);
+      pe_ctl_st(pb, PEC_EXECUTED, kseq);
       GT(5);
     }
-    if (PIPE) {
+    if (REMOTE) {
       // the region before's output is in memory before this one's copies read it (its engine says so)
       uint32_t spins = 0; (void)spins;
-      while (pe_ctl_ld(pbs, PEC_EXECUTED) < kseq) { __builtin_amdgcn_s_sleep(2); PE_SPIN_CHECK(spins); }
+      while (pe_ctl_ld(pb, PEC_EXECUTED) < kseq) { __builtin_amdgcn_s_sleep(2); PE_SPIN_CHECK(spins); }
       PE_PROF(14);
     }
     // ---- execute ----
@@ -2313,11 +2229,7 @@ pe_pass:
         }
       };
       const uint32_t kp_all = pe_ctl_ld(pb, PEC_KP);
-#ifdef BROTLI_AMD_PE_NO_EXEC_SPLIT
-      const bool exec_split = false;
-#else
       const bool exec_split = nb <= GW / 2u;
-#endif
       auto path_literals = [&](const uint32_t b, const uint32_t cnt) {
         const uint32_t k = (b << 6) + lane;
         const bool on = lane < cnt && k >= ks;
@@ -2404,11 +2316,11 @@ pe_pass:
       PE_PROF(8);
       RG_STAMP(2);   // (a) done
       PE_COUNT(28, kp);
-      if (!PIPE) {   // (wave 0 says where the stream goes on behind the resolve's last barrier, while the others execute: as a rule long since)
+      if (!REMOTE) {   // (wave 0 says where the stream goes on behind the resolve's last barrier, while the others execute: as a rule long since)
         while (pe_ctl_ld(pb, PEC_NXOK) != rseq) __builtin_amdgcn_s_sleep(1);
         lds_sync();
       }
-      if (!PIPE && pe_ctl_ld(pb, PEC_CONT) != 0u) {  // the next region's input is on its way while the rest of this one is executed
+      if (!REMOTE && pe_ctl_ld(pb, PEC_CONT) != 0u) {  // the next region's input is on its way while the rest of this one is executed
         const uint32_t nl = pe_ctl_ld(pb, PEC_NEXT_LBDW);
         pre_a = nl + T < limit_dw ? in_dw[nl + T] : 0u; pre_b = (T < 6u && nl + PE_CHUNKS + T < limit_dw) ? in_dw[nl + PE_CHUNKS + T] : 0u;
         pre_ok = true;
@@ -2653,7 +2565,7 @@ pe_pass:
       // lean_rec_commands takes them): wave 0 puts it behind them, and the commands behind it get a pass of their own
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       PE_BAR();   // (the pass's output is complete, nobody reads its records any more)
-      if (me == 0) { pe_dict_word(pbs, pb, out, dict, m); pe_ctl_st(pb, PEC_DCAND, 0u); }
+      if (me == 0) { pe_dict_word(pb, out, dict, m); pe_ctl_st(pb, PEC_DCAND, 0u); }
       PE_BAR();
       if (pe_ctl_ld(pb, PEC_AGAIN) != 0u) {
         ks = pe_ctl_ld(pb, PEC_KS);
@@ -2663,10 +2575,9 @@ pe_pass:
       }
     }
 #endif
-    if (PIPE) {
+    if (REMOTE) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       PE_BAR();
-      if (PIPE2 && T == 0u) { lds_sync(); pe_ctl_st(pbs, PEC_EXECUTED, kseq + 1u); }
       if (REMOTE && T == 0u) { const uint64_t t0_ = __builtin_amdgcn_s_memtime(); (void)t0_; GANG_STAT(gc, 27, t0_ - gs_arr); gang_release();
  GANG_STAT(gc, 17, __builtin_amdgcn_s_memtime() - t0_); gang_st64(gc, GC_EXEC, ((uint64_t)epoch << 32) | (uint64_t)(kseq + 1u)); }
 #ifdef BROTLI_AMD_GANG_TRACE
@@ -2678,10 +2589,10 @@ pe_pass:
 #endif
     }
   };
-#if !PE_CFG_PIPE && !PE_CFG_REMOTE
+#if !PE_CFG_REMOTE
   for (;;) {
     if (me == 0) {
-      const PeStream st = pe_st_load(pbs);
+      const PeStream st = pe_st_load(pb);
       const uint32_t lbdw_ = st.b >> 5;
       const uint32_t avail = in_limit - (lbdw_ << 5);
       const bool go = td_ok && st.b < in_limit && avail >= PE_MIN_INPUT && st.quota >= SC_MIN_QUOTA && (st.bl1 != 0u || st.run_on != 0u);
@@ -2689,9 +2600,7 @@ pe_pass:
 #ifdef BROTLI_AMD_PE_DEBUG
       if (blockIdx.x == 0 && lane == 0 && !go) printf("  engine: no go: td_ok %d b %u in_limit %u avail %u quota %u bl1 %u run_on %u\n", (int)td_ok, st.b, in_limit, avail, st.quota, st.bl1, st.run_on);
 #endif
-#ifndef BROTLI_AMD_PE_OLD_RUN_REGIONS
       uint32_t want_bits = st.run_on != 0u ? PE_RUN_RBL : st.rbl;   // (a long literal run's regions take no tables per bit: four times the bits)
-#ifndef BROTLI_AMD_PE_NO_CUT
       if (st.run_on == 0u && st.s_cmds != 0u && st.s_bits != 0u) {
         // A block count that runs out ends the engine's part (decode.rs:1469-1524: the switch is the checked loop's), and what the region
         // holds behind that command was built for nothing -- 3.6 regions' worth a stream of the metric's, 2.6 % of its time.  The region is
@@ -2703,10 +2612,6 @@ pe_pass:
         need = need * 1.125f + 1024.0f;
         if (need < (float)want_bits) { const uint32_t nb_ = ((uint32_t)need + 31u) & ~31u; want_bits = nb_ < PE_MIN_INPUT ? PE_MIN_INPUT : nb_; }
       }
-#endif
-#else
-      const uint32_t want_bits = st.rbl;
-#endif
       setup_tables(lbdw_, st.b & 31u, avail < want_bits ? avail : want_bits, st.run_on, st.b & 31u);
       setup_walk(st.P);
     }
@@ -2738,8 +2643,8 @@ pe_pass:
 #endif
     if (pe_ctl_ld(pb, PEC_CONT) == 0u) break;
   }
-#elif PE_CFG_REMOTE
-  // ---- a gang of blocks: the stream's regions in turns, as the two engines below, but as many regions ahead as the gang has blocks.  Where
+#else
+  // ---- a gang of blocks: the stream's regions in turns, as many regions ahead as the gang has blocks.  Where
   // the windows lie is a PLAN everybody follows without asking: region k's starts (k - first) strides behind the plan's first bit (a stride is a
   // region less a margin: a region's walk ends a command or two short of its window's end wherever it entered it).  The engine whose turn it
   // is finds out whether the stream did enter its window; if not (the region before was cut short: its path's ranks or the closure's room
@@ -2831,7 +2736,6 @@ pe_pass:
               const uint32_t shsc_ = pe_ctl_ld(pb, PEC_MYSHIFT), sh_ = shsc_ & 3u;
               if (!(wn + 64u > PE_WCAP && sh_ < 2u && pe_ctl_ld(pb, PEC_L) > (PE_RBL >> (sh_ + 1u)))) {
                 pe_ctl_st(pb, PEC_LE, eb - (pe_ctl_ld(pb, PEC_LBDW) << 5));
-                pe_ctl_st(pb, PEC_MYNEXT, eb);
                 setup_walk(0ull);
                 plan = 7u;
               }
@@ -2873,7 +2777,6 @@ pe_pass:
       if (me == 0) {
         const uint32_t eb = pe_ctl_ld(pb, PEC_MYENTRY);
         pe_ctl_st(pb, PEC_LE, eb - (pe_ctl_ld(pb, PEC_LBDW) << 5));
-        pe_ctl_st(pb, PEC_MYNEXT, eb);
         setup_walk(0ull);   // (where the region's output starts: with the stream's state, behind the details)
       }
       PE_BAR();
@@ -2882,79 +2785,6 @@ pe_pass:
       { const uint64_t tc_ = __builtin_amdgcn_s_memtime(); (void)tc_;
         consume();
         if (me == 0 && role == 0u) GANG_STAT(gc, 19, __builtin_amdgcn_s_memtime() - tc_); }
-      if (pe_ctl_ld(pb, PEC_CONT) == 0u) break;
-    }
-  }
-#else
-  // ---- two engines: the stream's regions in turns.  An engine builds the tables of its next region while the other one takes
-  // the stream through its own: the tables do not depend on where the stream enters the region (any chain of literal code
-  // words is a path: they re-synchronise; the records are per state), only the walk does -- it waits for the region before's
-  // resolve (PEC_RESOLVED), and the execute for the region before's output (PEC_EXECUTED).  Where a region's tables start is a
-  // guess: the engine's own last region, carried on by what the stream advanced in it, less a margin.  A guess the stream
-  // does not enter (it ended short of it, or too close to its end) costs the tables once more, built where the stream is.
-  {
-    const uint32_t entry0 = pe_ctl_ld(pbs, SCC_ENTRY);
-    for (kseq = eng;; kseq += 2u) {
-      // -- the window --
-      if (me == 0) {
-        uint32_t wbit = entry0;
-        if (kseq != 0u) {
-          // behind the region before's window, less the margin: a region's walk ends a command or two short of its window's end
-          // wherever it entered it (that window is final once its engine has seen the stream arrive: PEC_NFINAL)
-          uint32_t spins = 0;
-          while (pe_ctl_ld(pbs, PEC_NFINAL) < kseq && pe_ctl_ld(pbs, PEC_STOP) == 0u) { __builtin_amdgcn_s_sleep(2); PE_SPIN_CHECK(spins); }
-          lds_sync();
-          wbit = (pe_ctl_ld(pbs, PEC_WINF + ((kseq - 1u) & 1u)) << 5) + PE_RBL - PE_PIPE_MARGIN;
-        } else { pe_ctl_st(pbs, PEC_WINF, entry0 >> 5); lds_sync(); pe_ctl_st(pbs, PEC_NFINAL, 1u); }   // (the first region's is where the stream is)
-        const uint32_t W = wbit >> 5;
-        const uint32_t avail = (W << 5) < in_limit ? in_limit - (W << 5) : 0u;
-        const bool buildable = td_ok && avail >= PE_MIN_INPUT && pe_ctl_ld(pbs, PEC_STOP) == 0u;
-        setup_tables(W, 0u, avail < PE_RBL ? avail : PE_RBL, 0u, 0u);
-        pe_ctl_st(pb, PEC_GO, buildable ? 1u : 0u);
-      }
-      PE_BAR();
-      PE_PROF(15);   // (waiting for the window)
-      bool built = false;
-      if (pe_ctl_ld(pb, PEC_GO) != 0u) { (void)build(); built = true; }
-      // -- the stream arrives --
-      if (me == 0) {
-        uint32_t spins = 0;
-        while (pe_ctl_ld(pbs, PEC_RESOLVED) < kseq && pe_ctl_ld(pbs, PEC_STOP) == 0u) { __builtin_amdgcn_s_sleep(2); PE_SPIN_CHECK(spins); }
-        lds_sync();
-        uint32_t plan = 2u;   // 0: the tables are the ones, 1: once more where the stream is, 2: the invocation is over
-        if (pe_ctl_ld(pbs, PEC_RESOLVED) >= kseq && pe_ctl_ld(pbs, PEC_STOP) == 0u) {
-          const PeStream st = pe_st_load(pbs);
-          const uint32_t avail = st.b < in_limit ? in_limit - ((st.b >> 5) << 5) : 0u;
-          const bool go = td_ok && st.b < in_limit && avail >= PE_MIN_INPUT && st.quota >= SC_MIN_QUOTA && st.bl1 != 0u;
-          if (go) {
-            const uint32_t w0 = pe_ctl_ld(pb, PEC_LBDW) << 5, wl = pe_ctl_ld(pb, PEC_L);
-            const bool usable = built && st.b >= w0 && st.b + PE_PIPE_USEFUL <= w0 + wl;
-            plan = usable ? 0u : 1u;
-            if (!usable) setup_tables(st.b >> 5, 0u, avail < PE_RBL ? avail : PE_RBL, 0u, 0u);
-            if (kseq != 0u) { pe_ctl_st(pbs, PEC_WINF + (kseq & 1u), usable ? w0 >> 5 : st.b >> 5); lds_sync(); pe_ctl_st(pbs, PEC_NFINAL, kseq + 1u); }
-          }
-        }
-        if (plan == 2u) pe_ctl_st(pbs, PEC_STOP, 1u);
-        pe_ctl_st(pb, PEC_PLAN, plan);
-      }
-      PE_BAR();
-      PE_PROF(16);   // (waiting for the stream)
-      const uint32_t plan = pe_ctl_ld(pb, PEC_PLAN);
-      if (plan == 2u) break;
-      if (plan == 1u) (void)build();
-      if (me == 0) {
-        const PeStream st = pe_st_load(pbs);
-        pe_ctl_st(pb, PEC_LE, st.b - (pe_ctl_ld(pb, PEC_LBDW) << 5));
-        pe_ctl_st(pb, PEC_MYENTRY, st.b); pe_ctl_st(pb, PEC_MYNEXT, st.b);
-        setup_walk(st.P);
-#ifdef BROTLI_AMD_PE_DEBUG
-        if (blockIdx.x == 0 && lane == 0) printf("region %u (engine %u): window dword %u, %u bits, entry %u (bit %u of it), plan %u, P %llu, bl1 %u, Rn %u wn %u\n", kseq, eng, pe_ctl_ld(pb, PEC_LBDW), pe_ctl_ld(pb, PEC_L), st.b, st.b - (pe_ctl_ld(pb, PEC_LBDW) << 5), plan, (unsigned long long)st.P, st.bl1, pe_ctl_ld(pb, PEC_RN), wn);
-#endif
-      }
-      PE_BAR();
-      le = pe_ctl_ld(pb, PEC_LE);
-      P0 = (uint64_t)pe_ctl_ld(pb, PEC_P0_LO) | ((uint64_t)pe_ctl_ld(pb, PEC_P0_HI) << 32);
-      consume();
       if (pe_ctl_ld(pb, PEC_CONT) == 0u) break;
     }
   }
@@ -2967,19 +2797,16 @@ pe_pass:
     goto pe_again;
   }
   if (rfl(me_) != 0u) {
-#ifdef BROTLI_AMD_PE_NO_STAY   // (for A/B: every wave returns after every invocation, as in round 3)
-    return seq_;
-#endif
     for (uint32_t idle = 0;; idle++) {   // (as helper_wave idles)
       if (hc_ld(HC_SEQ) != seq_) break;
       if (idle < 256u) __builtin_amdgcn_s_sleep(4); else __builtin_amdgcn_s_sleep(127);
     }
     lds_acquire();
-    if (hc_ld(HC_SEQ) == seq_ + 1u && hc_ld(HC_KIND) == (REMOTE ? (uint32_t)HK_PATHR : PIPE2 ? (uint32_t)HK_PATH2 : PE_DICT ? (uint32_t)HK_PATHG : (uint32_t)HK_PATH)) goto pe_again;   // (this form of the engine again: the lean one and the general one are two functions)
+    if (hc_ld(HC_SEQ) == seq_ + 1u && hc_ld(HC_KIND) == (REMOTE ? (uint32_t)HK_PATHR : PE_DICT ? (uint32_t)HK_PATHG : (uint32_t)HK_PATH)) goto pe_again;   // (this form of the engine again: the lean one and the general one are two functions)
     return seq_;
   }
 #ifdef BROTLI_AMD_PROFILE_SCAN
-  if (blockIdx.x == 0 && lane == 0) { for (int k = 0; k < 32; k++) if (k != 30) g_path_prof[k] += pp_acc[k]; g_path_prof[32] += pe_ctl_ld(pbs, PEC_STATE + 6); g_path_prof[33] += 1; }
+  if (blockIdx.x == 0 && lane == 0) { for (int k = 0; k < 32; k++) if (k != 30) g_path_prof[k] += pp_acc[k]; g_path_prof[32] += pe_ctl_ld(pb, PEC_STATE + 6); g_path_prof[33] += 1; }
 #endif
   if (REMOTE && pe_ctl_ld(pb, PEC_PLAN) != 6u) {   // (6: the owner kept the invocation to itself)
     // (the owner of a gang) the invocation's end as the gang left it: the regions resolved in all, the stream's state behind the last of them
@@ -2993,8 +2820,8 @@ pe_pass:
       if (__ballot(lane < GC_STATE_WORDS && (uint32_t)(v >> 32) == want) == ((1ull << GC_STATE_WORDS) - 1ull)) break;
       __builtin_amdgcn_s_sleep(1); PE_SPIN_CHECK(spins);
     }
-    if (lane < 25u) lds_st32(pbs + PE_CTL + 4u * (PEC_STATE + lane), (uint32_t)v);
-    pe_ctl_st(pbs, PEC_DECLINE, (rdlane((uint32_t)v, 25) >> 1) & 3u);
+    if (lane < 25u) lds_st32(pb + PE_CTL + 4u * (PEC_STATE + lane), (uint32_t)v);
+    pe_ctl_st(pb, PEC_DECLINE, (rdlane((uint32_t)v, 25) >> 1) & 3u);
     pe_ctl_st(pb, PEC_DSEEN, Kr != 0u ? (rdlane((uint32_t)v, 25) >> 3) & 1u : 0u);   // (the engine's part ended in front of a dictionary reference: the general form's stream, as the lean form says it)
     if (Kr != 0u) {
       for (;;) { const uint64_t ew = gang_ld64(gc, GC_EXEC); if ((uint32_t)(ew >> 32) == epoch && (uint32_t)ew >= Kr) break; __builtin_amdgcn_s_sleep(1); PE_SPIN_CHECK(spins); }
@@ -3005,7 +2832,7 @@ pe_pass:
     lds_sync();
   }
   // ---- hand the stream back in front of the next command (LDS_LEAN, as the scan engine does) ----
-  const PeStream st_ = pe_st_load(pbs);
+  const PeStream st_ = pe_st_load(pb);
   PeStream st = st_;
   if (REMOTE) { GANG_STAT(gc, 21, st.ncmd < 64u ? 1u : 0u); GANG_STAT(gc, 22, st.ncmd); GANG_STAT(gc, 23, st.ncmd == 0u ? 1u : 0u); }
   if (st.run_on != 0u) {
@@ -3025,7 +2852,7 @@ pe_pass:
   }
   const bool pdx = PE_DICT && pe_ctl_ld(pb, PEC_PDX) != 0u;   // (behind the distance of a command whose literals are out: postReadDistance, decode.rs:2583)
   if (lane == 0) {
-    LEAN_ST(L_SC_POS_LO, st.b); LEAN_ST(L_SC_POS_HI, pdx ? (uint32_t)SCX_POST_DISTANCE : (uint32_t)SCX_BEGIN | (PIPE && (pe_ctl_ld(pbs, PEC_DECLINE) & 1u) != 0u ? 0x100u : 0u) | (REMOTE && (pe_ctl_ld(pbs, PEC_DECLINE) & 2u) != 0u ? 0x800u : 0u) | (REMOTE && pe_ctl_ld(pb, PEC_PLAN) == 6u && pe_ctl_ld(pb, PEC_NOHELP) != 0u ? 0x1000u : 0u) | (!PIPE && pe_ctl_ld(pb, PEC_OVF) >= 3u ? 0x200u : 0u) | (!PIPE2 && !PE_DICT && pe_ctl_ld(pb, PEC_DSEEN) != 0u ? 0x400u : 0u));
+    LEAN_ST(L_SC_POS_LO, st.b); LEAN_ST(L_SC_POS_HI, pdx ? (uint32_t)SCX_POST_DISTANCE : (uint32_t)SCX_BEGIN | (REMOTE && (pe_ctl_ld(pb, PEC_DECLINE) & 1u) != 0u ? 0x100u : 0u) | (REMOTE && (pe_ctl_ld(pb, PEC_DECLINE) & 2u) != 0u ? 0x800u : 0u) | (REMOTE && pe_ctl_ld(pb, PEC_PLAN) == 6u && pe_ctl_ld(pb, PEC_NOHELP) != 0u ? 0x1000u : 0u) | (!REMOTE && pe_ctl_ld(pb, PEC_OVF) >= 3u ? 0x200u : 0u) | (!PE_DICT && pe_ctl_ld(pb, PEC_DSEEN) != 0u ? 0x400u : 0u));
     LEAN_ST(L_P_LO, (uint32_t)st.P); LEAN_ST(L_P_HI, (uint32_t)(st.P >> 32)); LEAN_ST(L_QUOTA, st.quota); LEAN_ST(L_MLEN, st.mlen);
     LEAN_ST(L_BL0, st.bl0); LEAN_ST(L_BL1, st.bl1); LEAN_ST(L_BL2, st.bl2);
     LEAN_ST(L_D0, st.d0); LEAN_ST(L_D1, st.d1); LEAN_ST(L_D2, st.d2); LEAN_ST(L_D3, st.d3); LEAN_ST(L_NCMD_LO, st.ncmd);

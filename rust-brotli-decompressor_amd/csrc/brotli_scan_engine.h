@@ -98,11 +98,7 @@ __device__ unsigned long long g_scan_prof[28];  // ([24]: wave 1's ticks in REC,
 
 // Between the stages of two chains of dependent LDS reads written side by side: the machine scheduler otherwise puts each
 // chain back together (one chain's reads, waits and all, then the other's), and the round trips no longer overlap.
-#ifdef BROTLI_AMD_SCAN_NO_STAGES
-#define SC_STAGE() do { } while (0)
-#else
 #define SC_STAGE() __builtin_amdgcn_sched_barrier(0)
-#endif
 
 // inclusive prefix sum over the wave (LLVM's buildScan: row shifts inside rows of 16, then row broadcasts)
 __device__ __forceinline__ uint32_t sc_scan(uint32_t v) {

@@ -500,8 +500,7 @@ print(json.dumps([[r.result, r.error_code, r.decoded_size, r.consumed, r.num_com
 
 
 def test_the_engines_and_the_one_wave_path_agree(pkg):
-    """The same batch (whole, truncated, damaged, one byte short) four times in fresh processes: default (path engine), two
-    engines of eight waves a block taking regions in turn (BROTLI_AMD_ENGINE=path2, round 4: kept as an opt-in), the scan
+    """The same batch (whole, truncated, damaged, one byte short) four times in fresh processes: default (path engine), the scan
     engine only (BROTLI_AMD_ENGINE=scan), no engine blocks but the command records and their hand-written run wherever a block has helper waves
     (BROTLI_AMD_NO_SCAN=1; round 6: metablocks without context too), nothing but the one-wave loops (and BROTLI_AMD_ENGINE=norecall) -- same status words and bytes;
     extra to, not instead of, the comparison with the oracle above."""
@@ -509,17 +508,17 @@ def test_the_engines_and_the_one_wave_path_agree(pkg):
     import subprocess
     _metric_streams(1)  # (skips without an encoder)
     rows = {}
-    for name, env in (("path", {}), ("path2", {"BROTLI_AMD_ENGINE": "path2"}), ("scan", {"BROTLI_AMD_ENGINE": "scan"}), ("records", {"BROTLI_AMD_NO_SCAN": "1"}),
+    for name, env in (("path", {}), ("scan", {"BROTLI_AMD_ENGINE": "scan"}), ("records", {"BROTLI_AMD_NO_SCAN": "1"}),
                       ("none", {"BROTLI_AMD_NO_SCAN": "1", "BROTLI_AMD_ENGINE": "norecall"})):
         e = dict(os.environ); e.update(env)
         out = subprocess.run([sys.executable, "-c", _AB_SCRIPT, ROOT], env=e, capture_output=True, text=True, timeout=600)
         assert out.returncode == 0, out.stderr[-2000:]
         rows[name] = json.loads(out.stdout.strip().splitlines()[-1])
     strip = lambda rs: [r[:5] + r[6:] for r in rs]  # everything but engine_commands
-    assert strip(rows["path"]) == strip(rows["path2"]) == strip(rows["scan"]) == strip(rows["records"]) == strip(rows["none"])
+    assert strip(rows["path"]) == strip(rows["scan"]) == strip(rows["records"]) == strip(rows["none"])
     assert all(r[5] == 0 for r in rows["none"]), rows["none"]
-    for name in ("path", "path2", "scan"):
-        assert all(r[5] >= (0.8 if name == "path2" else 0.9) * r[4] for r in rows[name][:2]), (name, rows[name])   # (two engines: a region whose closure is full leaves its metablock to the one-wave loop)
+    for name in ("path", "scan"):
+        assert all(r[5] >= 0.9 * r[4] for r in rows[name][:2]), (name, rows[name])
 
 
 def test_large_window_streams(pkg):
@@ -583,20 +582,19 @@ print(json.dumps([[r.result, r.error_code, r.decoded_size, r.consumed, r.num_com
 @pytest.mark.parametrize("copies", [1, 160])
 def test_context_modelled_streams_with_and_without_the_helper_waves(pkg, copies):
     """Metablocks whose literals depend on context (the reference's text fixtures: whole, truncated, damaged, output buffer too
-    small), in blocks of sixteen waves (7 streams) and of four (1120 streams), three times in fresh processes: default (wave 2
-    parses command records ahead of the decoding wave: rec_wave / lean_rec_commands), BROTLI_AMD_ENGINE=split (wave 1 also
-    executes what the decoding wave parses: copier_wave / lean_split_commands), BROTLI_AMD_ENGINE=norec (the decoding wave
+    small), in blocks of sixteen waves (7 streams) and of four (1120 streams), twice in fresh processes: default (wave 2
+    parses command records ahead of the decoding wave: rec_wave / lean_rec_commands), BROTLI_AMD_ENGINE=norec (the decoding wave
     alone).  Same status words and bytes, equal to the oracle's; `engine_commands` says which path ran."""
     import json
     import subprocess
     rows = {}
-    for name, env in (("records", {}), ("split", {"BROTLI_AMD_ENGINE": "split"}), ("alone", {"BROTLI_AMD_ENGINE": "norec"})):
+    for name, env in (("records", {}), ("alone", {"BROTLI_AMD_ENGINE": "norec"})):
         e = dict(os.environ); e.update(env)
         out = subprocess.run([sys.executable, "-c", _CTX_SCRIPT, ROOT, str(copies)], env=e, capture_output=True, text=True, timeout=600)
         assert out.returncode == 0, out.stderr[-2000:]
         rows[name] = json.loads(out.stdout.strip().splitlines()[-1])
     strip = lambda rs: [r[:5] + r[6:] for r in rs]  # everything but engine_commands
-    assert strip(rows["records"]) == strip(rows["split"]) == strip(rows["alone"])
+    assert strip(rows["records"]) == strip(rows["alone"])
     gold = os.path.join(ROOT, "tests", "golden", "testdata")
     names = ["alice29.txt.compressed", "asyoulik.txt.compressed", "lcet10.txt.compressed", "plrabn12.txt.compressed"]
     for i, n in enumerate(names):
@@ -604,8 +602,7 @@ def test_context_modelled_streams_with_and_without_the_helper_waves(pkg, copies)
         for r in rows["records"][i::7]:
             assert r[:5] == [info.result, info.error_code, info.decoded_size, info.consumed, info.num_commands] and r[6] == hashlib.sha256(exp).hexdigest(), (n, r)
     assert all(r[5] == 0 for r in rows["alone"]), rows["alone"][:7]
-    for mode in ("records", "split"):
-        assert all(r[5] >= 0.9 * r[4] for i, r in enumerate(rows[mode]) if i % 7 < 4), (mode, rows[mode][:7])
+    assert all(r[5] >= 0.9 * r[4] for i, r in enumerate(rows["records"]) if i % 7 < 4), rows["records"][:7]
 
 
 def test_text_at_every_quality_in_blocks_of_four_waves(pkg):
