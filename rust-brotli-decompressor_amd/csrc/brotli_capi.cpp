@@ -651,26 +651,6 @@ extern "C" int BrotliAmdBatchWait(BrotliAmdBatch* b, BrotliAmdResult* results) {
   if (!hip_ok(hipSetDevice(b->device), "hipSetDevice")) return -1;
   if (!hip_ok(hipMemcpyAsync(b->h_status, b->d_status, sizeof(BrotliAmdStreamStatus) * b->n, hipMemcpyDeviceToHost, b->last_stream), "hipMemcpyAsync(status)")) return -1;
   if (!hip_ok(hipStreamSynchronize(b->last_stream), "hipStreamSynchronize")) return -1;
-#ifdef BROTLI_AMD_GANG_STATS
-  if (b->last_gang > 1u && b->d_gang && getenv("BROTLI_AMD_GANG_STATS")) {   // (profile build: the first stream's gang)
-    unsigned long long st[40];
-    if (hipMemcpy(st, b->d_gang + 704, sizeof st, hipMemcpyDeviceToHost) == hipSuccess)
-      fprintf(stderr, "gang of %u: invocations %llu, regions arrived at %llu, of them not usable %llu (no tables %llu, short of the window %llu, too far into it %llu), rebuilt by a new plan %llu, tables built %llu; "
-              "ticks: owner waits for helpers to leave %llu, for the stream %llu (helpers %llu), for the region before's output %llu, for the regions' before that (executes that wait twice) %llu, at the end %llu; regions resolved %llu, declined %llu; owner inside the engine %llu (set-up %llu, its tables %llu, its regions' walk .. execute %llu), the releases behind a region's output %llu; invocations that took fewer than 64 commands %llu (none: %llu), commands in all %llu; from the stream's arrival, summed over the regions: walk done %llu, details %llu, resolve %llu, output complete %llu; (the walk's start %llu, the entry's states %llu, the anchors %llu); regions whose execute waited once %llu; invocations that resolved no region %llu; regions given up behind their details: the invocation had ended %llu, the region before said so %llu, the stream went on elsewhere %llu, no quota or commands left %llu; resolves that ended an invocation %llu (a limit cut the region: %llu); ticks waiting for the state behind the details %llu\n",
-              b->last_gang, st[0], st[1], st[2], st[10], st[11], st[12], st[3], st[4], st[5], st[6], st[7], st[8], st[9], st[13], st[14], st[15], st[16], st[18], st[20], st[19], st[17], st[21], st[23], st[22], st[24], st[25], st[26], st[27], st[28], st[29], st[38], st[30], st[31], st[32], st[33], st[34], st[36], st[37], st[35], st[39]);
-  }
-#endif
-#ifdef BROTLI_AMD_GANG_TRACE
-  if (b->last_gang > 1u && b->d_gang) {   // (profile build: the first regions of one invocation of the first stream's gang, the shared 100 MHz clock at every hand-over)
-    static unsigned long long tr[64][16];
-    if (hipMemcpy(tr, b->d_gang + 1024 + (40u << 10), sizeof tr, hipMemcpyDeviceToHost) == hipSuccess)
-      for (int k = 0; k < 64 && tr[k][6]; k++) {
-        fprintf(stderr, "GT %d blk %llu m %llu ndep %llu :", k, tr[k][15] >> 32, tr[k][15] & 0xffffull, (tr[k][15] >> 16) & 0xffffull);
-        for (int q = 0; q < 15; q++) fprintf(stderr, " %llu", tr[k][q]);
-        fprintf(stderr, "\n");
-      }
-  }
-#endif
   if (retry_with_larger_arenas(b) != 0) return -1;
   if (b->exact_limit && settle_output_limits(b) != 0) return -1;
   if (results) {
@@ -1368,9 +1348,4 @@ extern "C" void BrotliDecoderFreeUsize(BrotliDecoderState* s, size_t* data, size
 // Debug aid for tests/ (not part of the public headers): device bytes a streaming instance holds at the moment.
 extern "C" __attribute__((visibility("default"))) size_t brotli_amd_debug_stream_device_bytes(const BrotliDecoderState* s) {
   return s ? s->d_in_cap + s->d_out_cap : 0;
-}
-
-// Debug/profiling aid for tools/ (not part of the public headers): raw status block of stream i after Wait.
-extern "C" __attribute__((visibility("default"))) const BrotliAmdStreamStatus* brotli_amd_debug_status(BrotliAmdBatch* b, uint32_t i) {
-  return (b && i < b->n) ? &b->h_status[i] : nullptr;
 }

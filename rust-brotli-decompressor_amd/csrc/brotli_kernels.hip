@@ -469,19 +469,11 @@ struct Stream {
   uint32_t engine_commands;
   uint32_t general_engine;  // (see HotArgs)
   uint32_t peak_trees, peak_maps, any_compressed;  // what the reference's allocators would have been asked for (see BrotliAmdStreamStatus)
-#ifdef BROTLI_AMD_PROFILE
-  uint64_t prof[6];
-#endif
 };
 
-#ifdef BROTLI_AMD_TRACE
-#define TRACE_STOP(br, e) do { if (lane_id() == 0) printf("stop line %d e=%d pos=%llu total=%llu\n", __LINE__, (int)(e), (unsigned long long)(br).pos(), (unsigned long long)(br).total_bits()); } while (0)
-#else
-#define TRACE_STOP(br, e) do { } while (0)
-#endif
 #define TRY(x) do { int _e = (x); if (_e != E_SUCCESS) return _e; } while (0)
-#define NEED_INPUT(br) do { if ((br).over()) { TRACE_STOP(br, E_NEEDS_MORE_INPUT); return E_NEEDS_MORE_INPUT; } } while (0)
-#define FAIL(br, e) do { TRACE_STOP(br, e); return (e); } while (0)
+#define NEED_INPUT(br) do { if ((br).over()) return E_NEEDS_MORE_INPUT; } while (0)
+#define FAIL(br, e) do { return (e); } while (0)
 
 // ======================================= Huffman table build =======================================
 // Lane-parallel construction of the 2-level table from LDS_LENGTHS[sym] (code length per symbol, 0 = unused).
@@ -503,19 +495,10 @@ __device__ __forceinline__ CodeOfLane lane_code(uint32_t L, const uint32_t (&fir
   return r;
 }
 
-#ifdef BROTLI_AMD_PROFILE_HDR
-__device__ unsigned long long g_hdr_prof[8];  // ticks: code-length code, symbol lengths, build_tree (3, 6, 7: its histogram, its first pass, the rest); counts: codes, symbols
-#define BT_PROF(k) do { const uint64_t t_ = __builtin_amdgcn_s_memtime(); if (blockIdx.x == 0 && lane_id() == 0) g_hdr_prof[k] += t_ - bt_t; bt_t = t_; } while (0)
-#else
-#define BT_PROF(k) do { } while (0)
-#endif
 // (a function of its own -- and the reader of the code lengths below another: inlined into the kernel's body, at the limit of its 128
 // registers a wave, their vectors spilt to scratch in the middle of the headers' loops -- 4096 tiny streams took half as long again)
 __device__ __noinline__ uint32_t build_tree(const Arena& a, uint32_t tree, uint32_t n_sym) {
   const uint32_t lane = lane_id();
-#ifdef BROTLI_AMD_PROFILE_HDR
-  uint64_t bt_t = __builtin_amdgcn_s_memtime();
-#endif
   // 1. histogram of code lengths (uniform, via ballots) and first code per length
   uint32_t cnt[16], first_code[16], run[16];
 #pragma unroll
@@ -536,7 +519,6 @@ __device__ __noinline__ uint32_t build_tree(const Arena& a, uint32_t tree, uint3
       if (cnt[l]) max_len = l;
     }
   }
-  BT_PROF(3);
   const bool two_level = max_len > ROOT_BITS;
   // The root's 256 entries by who OWNS them (round 5): in the order of the codes -- most significant bit first -- a code of L <= 8 bits
   // covers the 2^(8 - L) entries from code << (8 - L) on, and a complete code's ranges tile the root.  Every symbol notes its entry at
@@ -567,7 +549,6 @@ __device__ __noinline__ uint32_t build_tree(const Arena& a, uint32_t tree, uint3
       }
     }
   }
-  BT_PROF(6);
   uint32_t total = 256;
   if (two_level) {
     lds_sync();
@@ -629,7 +610,6 @@ __device__ __noinline__ uint32_t build_tree(const Arena& a, uint32_t tree, uint3
     a.st16_lane(tree + (rev_bits(lane * 4 + 2, 8) << 1), e2); a.st16_lane(tree + (rev_bits(lane * 4 + 3, 8) << 1), e3);
   }
   lds_sync();
-  BT_PROF(7);
   return total;
 }
 
@@ -749,15 +729,7 @@ __device__ __noinline__ int read_symbol_lengths_wide(BitReader* const brp, const
 
 // src/decode.rs:868-1013.  Reads one prefix code, builds its table at a fresh arena allocation, returns the
 // arena offset in *tree_off.  The one helper that is a real function call (7 call sites, cold).
-#ifdef BROTLI_AMD_PROFILE_HDR
-#define HDR_PROF(k) do { const uint64_t t_ = __builtin_amdgcn_s_memtime(); if (blockIdx.x == 0 && lane_id() == 0) g_hdr_prof[k] += t_ - hp_t; hp_t = t_; } while (0)
-#else
-#define HDR_PROF(k) do { } while (0)
-#endif
 __device__ __noinline__ int read_huffman_code(Stream& s, uint32_t alphabet_size, uint32_t max_symbol, uint32_t* tree_off, bool cold = false) {
-#ifdef BROTLI_AMD_PROFILE_HDR
-  uint64_t hp_t = __builtin_amdgcn_s_memtime();
-#endif
   struct Scope {  // register copies of the reader and the arena, stored back on every exit
     Stream& s; BitReader br; Arena ar;
     __device__ __forceinline__ Scope(Stream& s_) : s(s_), br(s_.br), ar(s_.ar) { br.uniformize(); ar.uniformize(); }
@@ -843,7 +815,6 @@ __device__ __noinline__ int read_huffman_code(Stream& s, uint32_t alphabet_size,
         }
       }
     }
-    HDR_PROF(0);
     // symbol code lengths (decode.rs:661-797, 558-658)
     uint32_t symbol = 0, prev_code_len = 8, repeat = 0, repeat_code_len = 0;
     space = 32768;
@@ -887,12 +858,7 @@ __device__ __noinline__ int read_huffman_code(Stream& s, uint32_t alphabet_size,
     }
     if (space != 0) FAIL(br, E_HUFFMAN_SPACE);
     lds_sync();
-    HDR_PROF(1);
-#ifdef BROTLI_AMD_PROFILE_HDR
-    if (blockIdx.x == 0 && lane == 0) { g_hdr_prof[4] += 1; g_hdr_prof[5] += symbol; }
-#endif
     size = build_tree(ar, tree, max_symbol);
-    HDR_PROF(2);
   }
   if (!cold) ar.shrink_to(tree + size * 2);
   return E_SUCCESS;
@@ -1128,22 +1094,6 @@ __device__ __forceinline__ uint32_t dictionary_word_bytes(gcu8* dict, uint32_t o
   return b;
 }
 
-#ifdef BROTLI_AMD_PROFILE
-#define PROF_T() __builtin_amdgcn_s_memtime()
-#define PROF_ADD(acc, t0) do { uint64_t _t = __builtin_amdgcn_s_memtime(); (acc) += _t - (t0); (t0) = _t; } while (0)
-#else
-#define PROF_T() 0ull
-#define PROF_ADD(acc, t0) do { } while (0)
-#endif
-// BROTLI_AMD_PROFILE_LIT: the dist / copy slots report the batched / one-by-one literal loops instead
-#ifdef BROTLI_AMD_PROFILE_LIT
-#define PROF_LIT(acc, t0) PROF_ADD(acc, t0)
-#define PROF_REST(acc, t0) PROF_ADD(prof_cmd, t0)
-#else
-#define PROF_LIT(acc, t0) do { } while (0)
-#define PROF_REST(acc, t0) PROF_ADD(acc, t0)
-#endif
-
 // ===================================== helper waves: speculative literal runs =====================================
 // A block is up to eight waves: wave 0 decodes its stream, the others wait for work in an LDS mailbox.  The work: a
 // run of literals with one prefix code (high-entropy data: tens of thousands of literals between two copies).  A round
@@ -1215,13 +1165,6 @@ __device__ __forceinline__ uint64_t gang_ld64(gu8* gc, uint32_t off) { return __
 __device__ __forceinline__ void gang_st32(gu8* gc, uint32_t off, uint32_t v) { __hip_atomic_store(reinterpret_cast<__attribute__((address_space(1))) uint32_t*>(gc + off), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void gang_st64(gu8* gc, uint32_t off, uint64_t v) { __hip_atomic_store(reinterpret_cast<__attribute__((address_space(1))) uint64_t*>(gc + off), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ uint32_t gang_add32(gu8* gc, uint32_t off, uint32_t v) { return __hip_atomic_fetch_add(reinterpret_cast<__attribute__((address_space(1))) uint32_t*>(gc + off), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// (-DBROTLI_AMD_GANG_STATS: counters of the gang's life in its control block, from GC_STATS on; the host prints them -- BrotliAmdBatchWait)
-constexpr uint32_t GC_STATS = 704;   // u64 x 40
-#ifdef BROTLI_AMD_GANG_STATS
-#define GANG_STAT(gc_, k_, v_) do { if (lane_id() == 0) __hip_atomic_fetch_add(reinterpret_cast<__attribute__((address_space(1))) unsigned long long*>((gc_) + GC_STATS + 8u * (k_)), (unsigned long long)(v_), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); } while (0)
-#else
-#define GANG_STAT(gc_, k_, v_) do { } while (0)
-#endif
 // (the stores so far have left this wave: what is stored next cannot overtake them)
 __device__ __forceinline__ void gang_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 // plain stores of this CU (every wave has waited for its own) reach the other CUs / a look at another CU's word is followed by fresh data
@@ -1393,12 +1336,6 @@ constexpr uint32_t SP_MIN_MLEN = 4096u;       // smaller metablocks are not wort
 constexpr uint32_t SP_SPIN_CAP = 1u << 24;    // polls of the decoding wave before it gives a helper wave up (never seen)
 __device__ __forceinline__ uint32_t sp_ld(uint32_t ctl, uint32_t k) { return rfl(*reinterpret_cast<lds_vu32*>(&g_smem[ctl + 4u * k])); }
 __device__ __forceinline__ void sp_st(uint32_t ctl, uint32_t k, uint32_t v) { if (lane_id() == 0) *reinterpret_cast<lds_vu32*>(&g_smem[ctl + 4u * k]) = v; }
-#ifdef BROTLI_AMD_PROFILE_SPLIT
-__device__ unsigned long long g_split_prof[40];
-#define SPLIT_LAP(k) do { const uint64_t t_ = __builtin_amdgcn_s_memtime(); lap_acc[k] += t_ - lap_t; lap_t = t_; } while (0)
-#else
-#define SPLIT_LAP(k) do { } while (0)
-#endif
 
 
 // ---- command records ahead of the parser (wave 2 of the block, rec_wave) ----
@@ -1672,20 +1609,6 @@ enum { LS_BEGIN = 0, LS_AFTER_HEAD = 1, LS_LITERALS_REST = 2, LS_DISTANCE = 3, L
 #define LEAN_ST(k, v) lds_st32(LDS_LEAN + 4u * (uint32_t)(k), (uint32_t)(v))
 
 // Rounds of a long literal run (see the helper waves above); state through LDS_LEAN like the lean function's.
-#ifdef BROTLI_AMD_PROFILE_LEAN
-__device__ unsigned long long g_lean_prof[8];
-#define LEAN_PROF(k) do { uint64_t _t = __builtin_amdgcn_s_memtime(); if (blockIdx.x == 0) lp_acc[k] += _t - lp_t; lp_t = _t; } while (0)
-#else
-#define LEAN_PROF(k) do { } while (0)
-#endif
-#ifdef BROTLI_AMD_PROFILE_SPEC
-__device__ unsigned long long g_spec_prof[8];
-#define SPEC_PROF(k) do { uint64_t _t = __builtin_amdgcn_s_memtime(); if (blockIdx.x == 0 && lane == 0) g_spec_prof[k] += _t - sp_t; sp_t = _t; } while (0)
-#define SPEC_COUNT(k, v) do { if (blockIdx.x == 0 && lane == 0) g_spec_prof[k] += (v); } while (0)
-#else
-#define SPEC_PROF(k) do { } while (0)
-#define SPEC_COUNT(k, v) do { } while (0)
-#endif
 // position of the n-th (0-based) set bit of a mask that has more than n
 __device__ __forceinline__ uint32_t nth_set_bit(uint64_t m, uint32_t n) {
   const uint32_t lane = lane_id();
@@ -1730,9 +1653,6 @@ __device__ __noinline__ void spec_rounds(uint32_t tree_addr) {
     round_max = nw * SPEC_WINDOWS * 64u / minlen + 64u;
   }
   while (i >= SPEC_ROUND_MIN && br.next_dw + spec_input_dwords(nw) < safe_dw && hc_ld(HC_KIND) != 3u) {
-#ifdef BROTLI_AMD_PROFILE_SPEC
-    uint64_t sp_t = __builtin_amdgcn_s_memtime();
-#endif
     // A round decodes up to round_max literals.  Where the run has fewer left, the round is
     // *capped*: nothing goes to the output directly (chunk 0 uses scratch slot 0 like the helpers), and the round ends
     // at the run's last literal, whose bit position the start masks give.
@@ -1749,7 +1669,6 @@ __device__ __noinline__ void spec_rounds(uint32_t tree_addr) {
     spec_chunk(0, dw0, sh, tree_addr, capped ? spec : out + P, 0);  // the first chunk: its first bit does start a literal
     lds_release();
     hw_st(hb, HW_DONE, seq);     // (helper 1 takes this chunk's exit offset from here)
-    SPEC_PROF(0);
     uint32_t acc = hw_ld(hb, HW_N);  // literals of the round so far
     uint32_t e = hw_ld(hb, HW_EXIT);
     uint32_t bits_done = SPEC_WINDOWS * 64u + e;
@@ -1768,7 +1687,6 @@ __device__ __noinline__ void spec_rounds(uint32_t tree_addr) {
       while (__ballot(helper_lane && *flag != seq) != 0ull) { if (++polls > (1u << 20)) { lost = true; break; } __builtin_amdgcn_s_sleep(1); }
     }
     lds_acquire();
-    SPEC_PROF(1);
     if (!lost) { moving = 0; mv_seq = seq; }  // (every helper has finished the move of the round before: it decoded this round's chunk after it)
     bool open = !lost && !full;  // chunks are still being taken
     if (!capped && open) {
@@ -1862,7 +1780,6 @@ __device__ __noinline__ void spec_rounds(uint32_t tree_addr) {
         if (mv_n | mv_own) moving |= 1u << w;
       }
     }
-    SPEC_PROF(2);
     if (own) {  // chunk 0 of a capped round: out of scratch slot 0
       constexpr uint32_t H = SPEC_SLOT_BYTES / 1024u;
       const uint32_t n16 = own >> 4;
@@ -1880,11 +1797,9 @@ __device__ __noinline__ void spec_rounds(uint32_t tree_addr) {
       }
       if (lane < (own & 15u)) dst[(n16 << 4) + lane] = (uint8_t)tail;
     }
-    SPEC_PROF(3);
     if (lost) hc_st(HC_KIND, 3);  // helpers unusable from now on
     P += acc; i -= acc;
     br.seek_ahead(run_pos + bits_done);
-    SPEC_PROF(4); SPEC_COUNT(5, 1); SPEC_COUNT(6, acc); SPEC_COUNT(7, bits_done);
   }
   // what the helpers are still moving into place is part of the output before anything after the run reads it
   for (uint32_t w = 1; w < nw; w++) {
@@ -2027,11 +1942,7 @@ __device__ __noinline__ __attribute__((aligned(256))) uint32_t lean_commands(uin
   br.need32();
   uint32_t next_root = lds_ld16(LDS_FIXED + cmd_tree + (((uint32_t)br.buf & 0xFFu) << 1));
 
-#ifdef BROTLI_AMD_PROFILE_LEAN
-  uint64_t lp_acc[5] = {0, 0, 0, 0, 0}; uint64_t lp_t = __builtin_amdgcn_s_memtime();
-#endif
   for (;;) {
-    LEAN_PROF(3);
     if (bl1 == 0 || br.next_dw >= safe_dw) { stage = LS_BEGIN; break; }  // block switch due, or close to the end of the input
     uint32_t cmd;
     {  // read_symbol() with the root lookup already under way (cnt >= 32 here)
@@ -2056,7 +1967,6 @@ __device__ __noinline__ __attribute__((aligned(256))) uint32_t lean_commands(uin
     bl1--;
     ncmd++;
     lits_left = (uint32_t)insert_len;
-    LEAN_PROF(0);
     if (insert_len != 0) {
       if ((uint32_t)insert_len > quota || (uint32_t)insert_len > bl0) { stage = LS_AFTER_HEAD; break; }
       mlen -= insert_len;
@@ -2122,7 +2032,6 @@ __device__ __noinline__ __attribute__((aligned(256))) uint32_t lean_commands(uin
       if (i != 0) { stage = LS_LITERALS_REST; break; }
       if (quota == 0) { stage = LS_LITERALS_AT_LIMIT; break; }
     }
-    LEAN_PROF(1);
     // ---- distance (ReadDistanceInternal, decode.rs:2066-2131; see process_commands) ----
     if (distance_code >= 0) {
       distance_context = 1;
@@ -2166,7 +2075,6 @@ __device__ __noinline__ __attribute__((aligned(256))) uint32_t lean_commands(uin
     }
     br.need32();
     next_root = lds_ld16(LDS_FIXED + cmd_tree + (((uint32_t)br.buf & 0xFFu) << 1));
-    LEAN_PROF(2);
     // ---- copy: an LZ77 reference (not the dictionary) inside the quota that does not overlap itself ----
     {
       const uint32_t n = (uint32_t)copy_len, dist = (uint32_t)distance_code;
@@ -2178,14 +2086,7 @@ __device__ __noinline__ __attribute__((aligned(256))) uint32_t lean_commands(uin
       if (!tiny && dist < n) { stage = LS_POST_DISTANCE; break; }
       if (distance_context == 0) { d3 = d2; d2 = d1; d1 = d0; d0 = distance_code; }
       mlen -= copy_len;
-#ifdef BROTLI_AMD_PROFILE_LEAN
-      { uint64_t t0_ = __builtin_amdgcn_s_memtime(); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); uint64_t t1_ = __builtin_amdgcn_s_memtime();
-        LEAN_FLUSH();
-        uint64_t t2_ = __builtin_amdgcn_s_memtime(); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); uint64_t t3_ = __builtin_amdgcn_s_memtime();
-        if (blockIdx.x == 0) { g_lean_prof[5] += t1_ - t0_; g_lean_prof[6] += t3_ - t2_; } }
-#else
       LEAN_FLUSH();
-#endif
       gu8* src = out + P - dist;
       uint32_t n16 = 0, rem = n;
       if (tiny) {
@@ -2217,9 +2118,6 @@ __device__ __noinline__ __attribute__((aligned(256))) uint32_t lean_commands(uin
   }
   if (!CTX_NEVER && !ctx_regs && ctx_pend) { p1 = pend_byte(pend_n - 1u); p2 = pend_byte(pend_n - 2u); ctx_regs = true; }
   LEAN_FLUSH();
-#ifdef BROTLI_AMD_PROFILE_LEAN
-  if (blockIdx.x == 0 && lane == 0) { for (int k = 0; k < 4; k++) g_lean_prof[k] += lp_acc[k]; g_lean_prof[4] += ncmd; }
-#endif
 #undef LEAN_FLUSH
   lds_st32(LDS_LEANWIN + 4u * lane, br.cur);
   if (lane == 0) {
@@ -2313,15 +2211,7 @@ __device__ __noinline__ void rec_wave() {
 // store: lanes below pn the copy's bytes, the literals behind them.  The record of the next command is asked for before the memory
 // pipe is waited for.  Leaves in front of the first command that is anything else, with nothing of it touched; bit 0 of `ok` then says
 // whether rx / ry hold that command's record, bit 1 whether p1 / p2 are the two bytes before P.  P < 2^32 in here; copies of at most 63 bytes.
-#ifdef BROTLI_AMD_PROFILE_RUN_WAIT   // (tools/gen_rec_asm.py --profile-wait: s_memtime around the run's waits for the memory pipe; with -DBROTLI_AMD_PROFILE_SPLIT)
-#include "brotli_rec_run_asm_wait.h"
-#define LRA_WAIT_OPERAND , [wacc] "+s"(run_wait)
-#define LRA_WAIT_CLOBBERS "s74", "s75", "s76", "s77", "s78", "s79",
-#else
 #include "brotli_rec_run_asm.h"
-#define LRA_WAIT_OPERAND
-#define LRA_WAIT_CLOBBERS
-#endif
 static_assert(XR_VALID == 0x800000u && XR_LITERALS == 0x1000000u && XR_IMPLICIT == (1u << 25) && XR_DCTX_SHIFT == 26 && XR_SHORT == (1u << 28) && XR_NOT_RUN == (1u << 31), "LEAN_REC_RUN_ASM spells these out");
 
 // The lean loop of a context-modelled metablock whose command records are there (rec_wave): nothing of a command's head is
@@ -2436,9 +2326,6 @@ __device__ __noinline__ __attribute__((aligned(256))) uint32_t lean_rec_commands
   bool long_cmd = false;     // (... because of a command longer than the run takes: that is one)
   static const bool no_run_asm = false;
   const uint32_t ctx_tree_abs = ctx_tree_v + LDS_FIXED;   // (the run's literals: a context's tree as an address)
-#ifdef BROTLI_AMD_PROFILE_RUN_WAIT
-  uint64_t run_wait = 0;
-#endif
   // what the run reads once a command at most, a lane each: the four distance contexts' tables (lanes 0 .. 3), XW_POS (lane 5), the static dictionary's address (lanes 6, 7), XW_FRONT and the codes' epoch (lanes 8, 9)
   const uint32_t run_params = lane == 0u ? LDS_FIXED + dt0 : lane == 1u ? LDS_FIXED + dt1 : lane == 2u ? LDS_FIXED + dt2 : lane == 3u ? LDS_FIXED + dt3 :
                               lane == 6u ? sp_ld(xb, XW_DICT_LO) : lane == 7u ? sp_ld(xb, XW_DICT_HI) : lane == 8u ? xb + 4u * (uint32_t)XW_FRONT : lane == 9u ? my_epoch :
@@ -2448,36 +2335,28 @@ __device__ __noinline__ __attribute__((aligned(256))) uint32_t lean_rec_commands
   // ... and of a copy that repeats itself, by its distance d: 65536 / d + 1 (lane * that >> 16 = lane / d: the copy's byte i is byte i mod d of its source)
   const uint32_t run_mtab = lane != 0u ? 65536u / lane + 1u : 0u;
 
-#ifdef BROTLI_AMD_PROFILE_SPLIT
-  uint64_t lap_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}; uint64_t lap_t = __builtin_amdgcn_s_memtime(); const uint64_t lap_t0 = lap_t; uint32_t n_run = 0, n_lit = 0, n_nolit = 0, n_word = 0;
-#endif
   for (;;) {
     if (bl1 == 0 || br.next_dw >= safe_dw) break;
     // (the only place the window moves: between two commands.  The run goes by the reader's position in window bits: the window starts
     // in front of whatever the bit buffer still holds)
     if (br.next_dw >= win_end || (br.next_dw - br.chunk_base) * 32u < br.cnt) { br.rebase_back2(); win_end = br.chunk_base + 50u; }
-    SPLIT_LAP(0);
     if (rec_ok && !no_run_asm && P + (uint64_t)quota <= 0xFFFFFFFFull && front_c <= 0x40000000u) {   // (the run keeps the output position in 32 bits and moves it by at most `quota`: ADVICE round 3)
       // ---- a run of commands without literals (see LEAN_REC_RUN_ASM) ----
       uint32_t ok = rfl(1u | (ctx_regs ? 2u : 0u)), rx = rec_v.x, ry = rec_v.y, P32 = rfl((uint32_t)P);   // (the copy in flight lies at P - pend_n)
       uint32_t p1s = rfl(p1), p2s = rfl(p2), saids = rfl(pos_said), bl0s = rfl(bl0), fronts = rfl(front_c);
       const uint32_t lim = rfl(safe_dw < win_end ? safe_dw : win_end);  // (rfl: scalar registers for the "s" operands)
-      const uint32_t ncmd0 = ncmd, bl1_0 = bl1, quota0 = quota; (void)ncmd0;
+      const uint32_t bl1_0 = bl1, quota0 = quota;
       asm volatile(LEAN_REC_RUN_ASM
           : [buf] "+s"(br.buf), [cnt] "+s"(br.cnt), [ndw] "+s"(br.next_dw), [bl0] "+s"(bl0s), [bl1] "+s"(bl1), [bl2] "+s"(bl2),
             [d0] "+s"(d0), [d1] "+s"(d1), [d2] "+s"(d2), [d3] "+s"(d3), [P] "+s"(P32), [quota] "+s"(quota), [pn] "+s"(pend_n),
-            [ok] "+s"(ok), [p1] "+s"(p1s), [p2] "+s"(p2s), [said] "+s"(saids), [front] "+s"(fronts), [rx] "+v"(rx), [ry] "+v"(ry) LRA_WAIT_OPERAND
+            [ok] "+s"(ok), [p1] "+s"(p1s), [p2] "+s"(p2s), [said] "+s"(saids), [front] "+s"(fronts), [rx] "+v"(rx), [ry] "+v"(ry)
           : [cur] "v"(br.cur), [lane] "v"(lane), [lut0] "v"(lut0v), [lut1] "v"(lut1v), [ctxtree] "v"(ctx_tree_abs), [dlut] "v"(dlut), [params] "v"(run_params), [wtab] "v"(run_wtab), [mtab] "v"(run_mtab),
             [cb] "s"(br.chunk_base), [outlo] "s"((uint32_t)(uintptr_t)out), [outhi] "s"((uint32_t)((uint64_t)(uintptr_t)out >> 32)),
             [maxb] "s"(max_backward), [lim] "s"(lim), [xring] "s"(xring), [rmask] "s"(ring_mask), [org] "s"(origin_bits),
             [littree] "s"(rfl(LDS_FIXED + lit_tree)), [trivial] "s"(rfl(trivial))
-          : "memory", "vcc", "scc", "m0", LRA_WAIT_CLOBBERS "s80", "s81", "s82", "s83", "s84", "s85", "s86", "s87", "s88", "s89", "s90", "s91", "s92", "s93", "s94", "s95", "s96", "s97", "s98", "s99",
+          : "memory", "vcc", "scc", "m0", "s80", "s81", "s82", "s83", "s84", "s85", "s86", "s87", "s88", "s89", "s90", "s91", "s92", "s93", "s94", "s95", "s96", "s97", "s98", "s99",
             "v115", "v116", "v117", "v118", "v119", "v124");
       ncmd += bl1_0 - bl1; mlen -= (int32_t)(quota0 - quota);   // (a command of the run takes one of the command block's count, and from the quota what it takes from the metablock)
-      SPLIT_LAP(1);
-#ifdef BROTLI_AMD_PROFILE_SPLIT
-      n_run += ncmd - ncmd0;
-#endif
       P = P32; pend_pos = (uint64_t)rfl(P32 - pend_n);
       p1 = p1s; p2 = p2s; pos_said = saids; bl0 = bl0s; front_c = fronts;
       rec_v.x = rx; rec_v.y = ry; rec_ok = (ok & 1u) != 0u;
@@ -2505,7 +2384,6 @@ __device__ __noinline__ __attribute__((aligned(256))) uint32_t lean_rec_commands
         else { flush(); p1 = P >= 1 ? (uint32_t)rfl(out[P - 1]) : 0u; p2 = P >= 2 ? (uint32_t)rfl(out[P - 2]) : 0u; }
         ctx_regs = true;
       }
-      SPLIT_LAP(2);
       for (uint32_t i = 0; i < ins; i++) {
         uint32_t tree = lit_tree;
         if (!trivial) {
@@ -2516,10 +2394,6 @@ __device__ __noinline__ __attribute__((aligned(256))) uint32_t lean_rec_commands
         p2 = p1; p1 = lit;
         lit_reg = (lane == i) ? lit : lit_reg;
       }
-      SPLIT_LAP(3);
-#ifdef BROTLI_AMD_PROFILE_SPLIT
-      n_lit++;
-#endif
       lit_n = ins;
       insert_len = (int32_t)ins; copy_len = (int32_t)n;
       // ---- the distance behind them (ReadDistanceInternal, decode.rs:2066-2131) ----
@@ -2561,7 +2435,6 @@ __device__ __noinline__ __attribute__((aligned(256))) uint32_t lean_rec_commands
           distance_code = dist;
         }
       }
-      SPLIT_LAP(4);
       bl1--; ncmd++;
       mlen -= (int32_t)ins;
       // the literals go out with (in front of) the copy in flight: one store each
@@ -2592,7 +2465,6 @@ __device__ __noinline__ __attribute__((aligned(256))) uint32_t lean_rec_commands
     // ---- the plain copy (a short LZ77 reference that does not repeat itself, clear of every limit), or a word of the static dictionary
     // that is (decode.rs:2593-2640); anything else goes to the checked stages -- whole, if nothing of it has been taken yet, else they
     // finish it from the distance on (the ring and the copy's counts are untouched) ----
-    SPLIT_LAP(5);
     const uint32_t max_distance = P < (uint64_t)max_backward ? (uint32_t)P : max_backward;
     const bool plain = dist > 0 && (uint32_t)dist <= max_distance && n <= 63u && (uint32_t)dist >= n && n < quota;   // (63: the hand-written run makes a copy's lanes with s_bfm_b64)
     bool word = false;
@@ -2633,19 +2505,9 @@ __device__ __noinline__ __attribute__((aligned(256))) uint32_t lean_rec_commands
       ctx_regs = false;
       P += n; quota -= n;
     }
-    SPLIT_LAP(6);
-#ifdef BROTLI_AMD_PROFILE_SPLIT
-    if (word) n_word++; else if (!committed) n_nolit++;
-#endif
     need32();
     rec_ok = request();
   }
-#ifdef BROTLI_AMD_PROFILE_SPLIT
-  if (blockIdx.x == 0 && lane == 0) { for (int k = 0; k < 7; k++) g_split_prof[24 + k] += lap_acc[k]; g_split_prof[32] += n_run; g_split_prof[33] += n_lit; g_split_prof[34] += n_nolit; g_split_prof[35] += n_word; g_split_prof[36] += ncmd; g_split_prof[37] += 1; g_split_prof[38] += __builtin_amdgcn_s_memtime() - lap_t0; }
-#ifdef BROTLI_AMD_PROFILE_RUN_WAIT
-  if (blockIdx.x == 0 && lane == 0) g_split_prof[39] += run_wait;
-#endif
-#endif
   if (!ctx_regs && pend_n >= 2u) { p1 = pend_byte(pend_n - 1u); p2 = pend_byte(pend_n - 2u); ctx_regs = true; }
   flush();
   sp_st(xb, XW_POS, br.next_dw * 32u - br.cnt - origin_bits);
@@ -2696,7 +2558,6 @@ struct HotArgs {
   uint32_t engine_commands, reserved_;  // commands a command engine (scan or path) took
   uint32_t general_engine;  // the stream has words of the static dictionary: the path engine's general form from here on (see PE_CFG_DICT)
   uint64_t resume_out;     // global address of the status' BrotliAmdResume: command boundaries close to the end of the input are noted there
-  uint64_t prof[6];
 };
 
 #ifdef BROTLI_AMD_GANG_KERNEL
@@ -2757,10 +2618,6 @@ __device__ __noinline__ int process_commands(HotArgs* args) {
   uint64_t num_commands = rfl(args->num_commands);
   uint32_t engine_commands = rfl(args->engine_commands);
   int result = E_SUCCESS;
-  uint64_t prof_cmd = 0, prof_lit = 0, prof_dist = 0, prof_copy = 0, prof_t = PROF_T();
-  (void)prof_cmd; (void)prof_lit; (void)prof_dist; (void)prof_copy; (void)prof_t;
-  uint64_t prof_fast_batches = 0, prof_fast_syms = 0; (void)prof_fast_batches; (void)prof_fast_syms;
-  uint32_t prof_stage[8] = {0, 0, 0, 0, 0, 0, 0, 0}; (void)prof_stage;
 
   // (the LDS part as a cache of the trees in use: see run_commands)
   uint32_t rec_base = 0;   // (the command records' ring, where wave 2 parses ahead: see below)
@@ -2884,9 +2741,6 @@ __device__ __noinline__ int process_commands(HotArgs* args) {
   const bool scan_block = LDS_ONLY && CTX_NEVER && hc_ld(HC_SCAN_BASE) != 0u;
   const bool large_window = rfl(args->large_window) != 0u;   // (the path engine takes such streams since round 4, the scan engine does not)
   uint32_t scan_fails = 0;
-#ifdef BROTLI_AMD_PROFILE_SCAN
-  uint64_t pp_exit = 0, pp_enter = 0; (void)pp_enter; const uint64_t pp_start = __builtin_amdgcn_s_memtime(); bool pp_first = true; (void)pp_first;
-#endif
   const uint32_t engine_hints = rfl(args->general_engine);   // (bit 0: the general form; bits 8 .. 15, 16 .. 23: the gang's penalty and the invocations it still sits out, see remote_off)
   bool prefer_one_engine = false; (void)prefer_one_engine;   // the next invocation of the path engine: its one-block form (see `declined` below; gangs only)
   // ... the one-block form though the stream has a gang of blocks: for the next invocations where the gang met a literal run that wants regions
@@ -2915,9 +2769,6 @@ __device__ __noinline__ int process_commands(HotArgs* args) {
     const uint32_t origin_dw = (br.next_dw - ((br.cnt + 31u) >> 5)) & ~1u;
     const uint32_t ring_pos = lds_room >= free_at + SPX_BYTES ? SPX_POS : SPX_POS_MIN;   // (round 6: half a ring where the tables leave no room for a whole one -- text at -q 11 in blocks of four waves)
     if (lds_room >= free_at + SPX_CTL_BYTES + ring_pos * 8u && rfl(args->large_window) == 0u && br.end_dw > origin_dw + 80u) rec_base = LDS_FIXED + free_at;
-#ifdef BROTLI_AMD_REC_DEBUG
-    if (blockIdx.x == 0 && lane == 0) printf("records: room %u free_at %u need %u cache %d -> %s\n", lds_room, free_at, (uint32_t)SPX_BYTES, (int)tree_cache, rec_base != 0u ? "yes" : "no");
-#endif
     if (rec_base != 0u) {
       lds_sync();
       hc_st(HC_EXT_BASE, rec_base);
@@ -2939,9 +2790,6 @@ __device__ __noinline__ int process_commands(HotArgs* args) {
       if (spins > SP_SPIN_CAP) { hc_st(HC_KIND, (uint32_t)HK_NO_ROUNDS); break; }
       __builtin_amdgcn_s_sleep(2);
     }
-#ifdef BROTLI_AMD_REC_DEBUG
-    if (blockIdx.x == 0 && lane == 0) printf("rec_off: stop word %u kind %u ncmd %llu mlen %d\n", sp_ld(rec_base, XW_STOP), hc_ld(HC_KIND), (unsigned long long)num_commands, mlen);
-#endif
     rec_base = 0u;
     hc_st(HC_EXT_BASE, 0u);
     if (lane == 0) LEAN_ST(L_SP_REC, 0u);
@@ -2994,22 +2842,10 @@ __device__ __noinline__ int process_commands(HotArgs* args) {
         hc_st(HC_KIND, use_remote ? (uint32_t)HK_PATHR : use_general ? (uint32_t)HK_PATHG : use_path ? (uint32_t)HK_PATH : (uint32_t)HK_SCAN);
         lds_release();
         hc_st(HC_SEQ, hc_ld(HC_SEQ) + 1u);  // the other waves of the block join (helper_wave)
-#ifdef BROTLI_AMD_PROFILE_SCAN
-        { const uint64_t t_ = __builtin_amdgcn_s_memtime(); if (blockIdx.x == 0 && lane == 0 && pp_exit != 0) { g_path_prof[36] += t_ - pp_exit; g_path_prof[37] += 1; } if (blockIdx.x == 0 && lane == 0 && pp_exit == 0) g_path_prof[29] += t_ - pp_start; pp_enter = t_; }
-#endif
-#ifdef BROTLI_AMD_PE_DEBUG
-        if (blockIdx.x == 0 && lane == 0) printf("engine in: P %llu bl1 %u quota %u mlen %d commands so far %llu\n", (unsigned long long)P, bl1, quota, mlen, (unsigned long long)num_commands);
-#endif
 #ifndef BROTLI_AMD_GANG_KERNEL
         const uint32_t took = use_general ? rfl(pe16g::path_engine(0)) : use_path ? rfl(pe16::path_engine(0)) : rfl(scan_engine(0));
 #else
         const uint32_t took = use_remote ? rfl(pe16r::path_engine(0)) : use_general ? rfl(pe16g::path_engine(0)) : use_path ? rfl(pe16::path_engine(0)) : rfl(scan_engine(0));
-#endif
-#ifdef BROTLI_AMD_PE_DEBUG
-        if (blockIdx.x == 0 && lane == 0) printf("engine out: tick %llu took %u, P %llu form %u\n", (unsigned long long)__builtin_amdgcn_s_memtime(), took, (unsigned long long)(LEAN_LD(L_P_LO) | ((uint64_t)LEAN_LD(L_P_HI) << 32)), LEAN_LD(L_SC_POS_HI));
-#endif
-#ifdef BROTLI_AMD_PROFILE_SCAN
-        pp_exit = __builtin_amdgcn_s_memtime(); if (blockIdx.x == 0 && lane == 0) g_path_prof[38] += pp_exit - pp_enter;
 #endif
         prefer_one_engine = false;
         engine_commands += took;
@@ -3027,9 +2863,6 @@ __device__ __noinline__ int process_commands(HotArgs* args) {
         const uint64_t pos = origin + LEAN_LD(L_SC_POS_LO) - BitReader::skip_bits();
         if (lane == 0) { LEAN_ST(L_SPEC_LO, (uint32_t)rfl(args->spec_scratch)); LEAN_ST(L_SPEC_HI, (uint32_t)(rfl(args->spec_scratch) >> 32)); }
         br.seek(pos);
-#ifdef BROTLI_AMD_PE_DEBUG
-        if (blockIdx.x == 0 && lane == 0) printf("  after seek: tick %llu\n", (unsigned long long)__builtin_amdgcn_s_memtime());
-#endif
         const uint64_t P_before = P;
         P = (uint64_t)LEAN_LD(L_P_LO) | ((uint64_t)LEAN_LD(L_P_HI) << 32);
         quota = LEAN_LD(L_QUOTA); mlen = (int32_t)LEAN_LD(L_MLEN);
@@ -3084,9 +2917,6 @@ __device__ __noinline__ int process_commands(HotArgs* args) {
         engine_commands += took_;
         // (a metablock without context has another road: what a call of the record loop takes, halved and added up -- a stream of long copies or long
         // literal runs leaves the run at every command, and every way out costs what forty of its commands do)
-#ifdef BROTLI_AMD_REC_DEBUG
-        if (CTX_NEVER && blockIdx.x == 0 && lane == 0) printf("rec call: took %u waited %u poor %u stage %u ncmd %llu\n", took_, LEAN_LD(L_SP_WAITED), rec_poor, stage, (unsigned long long)num_commands);
-#endif
         // (a metablock without context has another road.  A stream of long copies or long literal runs leaves the run at every such command, and every way
         // out costs what forty of the run's commands do: six calls in a row that ended at a LONG command having taken less than sixty-four, and the
         // one-wave loop and its rounds have the rest of the metablock.  The first commands of a text -- words of the dictionary with their transforms while
@@ -3105,10 +2935,6 @@ __device__ __noinline__ int process_commands(HotArgs* args) {
         if (LEAN_LD(L_CTX_REGS)) { p1 = LEAN_LD(L_P1); p2 = LEAN_LD(L_P2); ctx_src = CTX_REGS; }
         else ctx_src = CTX_MEMORY;
       }
-#ifdef BROTLI_AMD_PROFILE
-      prof_fast_batches++; prof_fast_syms += LEAN_LD(L_NCMD_LO);  // (lean entries, commands run lean)
-      prof_stage[stage & 7]++;
-#endif
       insert_len = (int32_t)LEAN_LD(L_INSERT); copy_len = (int32_t)LEAN_LD(L_COPY);
       distance_code = (int32_t)LEAN_LD(L_DCODE); distance_context = LEAN_LD(L_DCTX); lits_left = (int32_t)LEAN_LD(L_LITS_LEFT);
       if (CTX_NEVER && stage == LS_LITERAL_ROUNDS) {
@@ -3175,7 +3001,6 @@ __device__ __noinline__ int process_commands(HotArgs* args) {
     if (br.over()) STOP(E_NEEDS_MORE_INPUT);
     bl1--;
     num_commands++;
-    PROF_ADD(prof_cmd, prof_t);
     lits_left = insert_len;  // literals of this command that are still to be decoded
 after_head:
     // p1/p2 must be right whenever a literal's context can matter: not at all in a metablock whose literal block
@@ -3234,10 +3059,6 @@ general_literals_rest:
       // Every lane decodes the symbol that would start at bit offset `lane` of a 64-bit window (one gathered table
       // lookup for all 64 candidates); a short scalar walk over the code lengths then picks the offsets that really
       // are symbol boundaries, and the surviving lanes store their bytes with one coalesced instruction.
-#ifdef BROTLI_AMD_PROFILE
-      if (prof_fast_syms == 0) prof_fast_syms = 0x100000u | (LDS_ONLY ? 1u : 0u) | (trivial ? 2u : 0u) | (mlen >= 0 ? 4u : 0u) | (i >= 8 ? 8u : 0u) | (bl0 >= 8 ? 16u : 0u) | (out_cap - P >= 8 ? 32u : 0u);
-#endif
-      PROF_LIT(prof_lit, prof_t);
 rounds_again:
       // A long run that the lean loop could not take whole (it crosses a flush point of the ring buffer, the end of a
       // literal block or of the output buffer): rounds of the helper waves for the part in front of that limit, the
@@ -3327,13 +3148,9 @@ rounds_again:
           p1 = q1;
           br.advance(off);
           P += n; i -= (int32_t)n; bl0 -= n;
-#ifdef BROTLI_AMD_PROFILE
-          prof_fast_batches++; prof_fast_syms += n;
-#endif
           if (P >= next_boundary) { RING_CROSS(); if (i >= (int32_t)SPEC_ROUND_MIN) goto rounds_again; }
         }
       }
-      PROF_LIT(prof_dist, prof_t);
       while (i > 0) {
         if (lit_n == 0) lit_pos = P;
         if (bl0 == 0) {
@@ -3365,11 +3182,9 @@ rounds_again:
         i--;
         if (P >= next_boundary) { RING_CROSS(); if (i >= (int32_t)SPEC_ROUND_MIN) goto rounds_again; }
       }
-      PROF_LIT(prof_copy, prof_t);
       if (mlen <= 0) STOP(E_SUCCESS);  // METABLOCK_DONE, copy part ignored (decode.rs:2552-2556)
       if (quota_mb) RECOMPUTE_QUOTA();
     }
-    PROF_ADD(prof_lit, prof_t);
     // ---- COMMAND_POST_DECODE_LITERALS ----
 general_distance:
     if (distance_code >= 0) {
@@ -3417,7 +3232,6 @@ general_distance:
       }
       bl2--;
     }
-    PROF_REST(prof_dist, prof_t);
     // postReadDistance, decode.rs:2583-2589
 general_post_distance:
     max_distance = (P < (uint64_t)(uint32_t)max_backward) ? (int32_t)P : max_backward;
@@ -3472,7 +3286,6 @@ general_post_distance:
         ctx_src = CTX_PEND; ctx_len = n;
         P += n;
         quota -= n;
-        PROF_REST(prof_copy, prof_t);
         if (quota != 0) continue;
         goto command_done;
       }
@@ -3494,7 +3307,6 @@ general_post_distance:
         if (!CTX_NEVER) ctx_src = CTX_MEMORY;
         P += n;
         quota -= n;
-        PROF_REST(prof_copy, prof_t);
         if (quota != 0) continue;
         goto command_done;
       }
@@ -3559,7 +3371,6 @@ general_post_distance:
       P += n;
       if (clipped) STOP(E_NEEDS_MORE_OUTPUT);
     }
-    PROF_REST(prof_copy, prof_t);
 command_done:
     if (P >= next_boundary) RING_CROSS();
     if (mlen <= 0) STOP(E_SUCCESS);  // METABLOCK_DONE
@@ -3571,12 +3382,6 @@ command_done:
 #undef STOP
 #undef RING_CROSS
 done:
-#ifdef BROTLI_AMD_PE_DEBUG
-  if (blockIdx.x == 0 && lane == 0) printf("done: tick %llu P %llu mlen %d result %d\n", (unsigned long long)__builtin_amdgcn_s_memtime(), (unsigned long long)P, mlen, result);
-#endif
-#ifdef BROTLI_AMD_PROFILE_SCAN
-  if (blockIdx.x == 0 && lane == 0) { const uint64_t t_ = __builtin_amdgcn_s_memtime(); if (pp_exit != 0) g_path_prof[39] += t_ - pp_exit; else g_path_prof[39] += 0; g_path_prof[31] += t_ - pp_start; }
-#endif
   FLUSH_LITERALS();
   FLUSH_PENDING();
   if (rec_base != 0u) {  // the helpers go back to sleep (HC_KIND stays: a helper that looks late must find nothing to do)
@@ -3593,15 +3398,6 @@ done:
   args->d0 = d0; args->d1 = d1; args->d2 = d2; args->d3 = d3;
   args->num_commands = num_commands;
   args->engine_commands = engine_commands; args->general_engine = (rfl(args->general_engine) & 0xFFFF00u) | (prefer_general ? 1u : 0u);
-#ifdef BROTLI_AMD_PROFILE
-  if (lane == 0 && blockIdx.x == 0) printf("lean exits by stage: %u %u %u %u %u %u %u %u\n", prof_stage[0], prof_stage[1], prof_stage[2], prof_stage[3], prof_stage[4], prof_stage[5], prof_stage[6], prof_stage[7]);
-  args->prof[0] = prof_cmd; args->prof[1] = prof_lit; args->prof[2] = prof_dist; args->prof[3] = prof_copy;
-#ifdef BROTLI_AMD_PROFILE_HDR
-  args->prof[4] = 0; args->prof[5] = prof_fast_syms;
-#else
-  args->prof[4] = prof_fast_batches; args->prof[5] = prof_fast_syms;
-#endif
-#endif
   return result;
 }
 
@@ -3651,7 +3447,6 @@ __device__ __forceinline__ int run_commands(Stream& s, const BrotliAmdResume* mi
   h.spec_scratch = (uint64_t)(uintptr_t)(s.ar.glb + s.ar_end);
   h.num_commands = s.num_commands;
   h.engine_commands = s.engine_commands; h.reserved_ = 0u; h.general_engine = s.general_engine;
-  h.prof[0] = h.prof[1] = h.prof[2] = h.prof[3] = h.prof[4] = h.prof[5] = 0;
   // tables entirely in the LDS part of the arena (the common case) take the ds_read-only instantiation
   int e;
   // every literal block type with a constant context map (DetectTrivialLiteralBlockTypes, decode.rs:1525-1553)?
@@ -3704,9 +3499,6 @@ __device__ __forceinline__ int run_commands(Stream& s, const BrotliAmdResume* mi
   s.num_commands = rfl(h.num_commands);
   s.engine_commands = rfl(h.engine_commands);
   s.general_engine = rfl(h.general_engine);
-#ifdef BROTLI_AMD_PROFILE
-  s.prof[0] += h.prof[0]; s.prof[1] += h.prof[1]; s.prof[2] += h.prof[2]; s.prof[3] += h.prof[3]; s.prof[4] += h.prof[4]; s.prof[5] += h.prof[5];
-#endif
   return e;
 }
 
@@ -3801,9 +3593,6 @@ __device__ __forceinline__ int decode_stream(Stream& s, bool have_header, uint64
 
   for (;;) {
     // METABLOCK_BEGIN (state.rs:422-450)
-#ifdef BROTLI_AMD_PROFILE_HDR
-    const uint64_t hdr_t0 = __builtin_amdgcn_s_memtime();
-#endif
     s.bl0 = s.bl1 = s.bl2 = 1u << 24;
     s.nbt0 = s.nbt1 = s.nbt2 = 1;
     s.ar.top = 0;
@@ -3936,9 +3725,6 @@ __device__ __forceinline__ int decode_stream(Stream& s, bool have_header, uint64
             }
             for (uint32_t m = 32u; m != 0u; m >>= 1) { all += __shfl_xor(all, m); lng += __shfl_xor(lng, m); }
             if (all == 0u || (uint64_t)lng * 100u >= (uint64_t)all * PROBE_LONG_PERCENT) every_short = false;
-#ifdef BROTLI_AMD_REC_DEBUG
-            if (blockIdx.x < 2u && lane_id() == 0) printf("probe: block %u code %u of %u: all %u long %u tree %u lds_limit %u mlen %d\n", blockIdx.x, ct, s.nbt1, all, lng, tree, a2.lds_limit, s.mlen);
-#endif
             }
             if (every_short) s.engine_commands |= 8u;
           }
@@ -3955,15 +3741,6 @@ __device__ __forceinline__ int decode_stream(Stream& s, bool have_header, uint64
           const uint32_t trees = s.num_lit_trees + s.nbt1 + s.num_dist_trees, maps = s.nbt0 * 65u + s.nbt2 * 4u;
           s.peak_trees = trees > s.peak_trees ? trees : s.peak_trees; s.peak_maps = maps > s.peak_maps ? maps : s.peak_maps; s.any_compressed = 1;
         }
-#ifdef BROTLI_AMD_PROFILE_HDR
-        s.prof[4] += __builtin_amdgcn_s_memtime() - hdr_t0;
-#endif
-#ifdef BROTLI_AMD_PROFILE_HDR
-        const uint64_t run_t0 = __builtin_amdgcn_s_memtime();
-        int run_e = run_commands(s, mid, s.P, st); mid = nullptr;
-        s.prof[5] = (s.prof[5] & 0xFFFFFu) + ((__builtin_amdgcn_s_memtime() - run_t0) >> 8);
-        TRY(run_e);
-#else
         {
           const BrotliAmdResume* const m_ = mid; mid = nullptr;
           const int run_e = run_commands(s, m_, s.P, st);
@@ -3972,7 +3749,6 @@ __device__ __forceinline__ int decode_stream(Stream& s, bool have_header, uint64
           if (run_e == E_RETRY_ARENA) s.num_metablocks = counted_before;
           TRY(run_e);
         }
-#endif
       }
     }
     // METABLOCK_DONE (decode.rs:3345-3381)
@@ -4009,12 +3785,6 @@ extern "C" __global__ __launch_bounds__(1024, 4) void BROTLI_AMD_KERNEL(const Br
                                                                            uint64_t scratch_per_block, uint32_t lds_arena_bytes,
                                                                            const uint8_t* __restrict__ dict) {
   const uint32_t lane = lane_id();
-#ifdef BROTLI_AMD_PROFILE_SCAN
-  const uint64_t scan_prof_t0 = __builtin_amdgcn_s_memtime();
-#endif
-#ifdef BROTLI_AMD_PROFILE_HDR
-  const uint64_t hdr_prof_t0 = __builtin_amdgcn_s_memtime();
-#endif
   // A gang launch (queue[2] blocks a stream, sixteen waves each; see GC_*): block b is member (b mod 8 gang) / 8 of the gang of stream
   // (b / (8 gang)) 8 + b mod 8 -- the members of a gang are eight block numbers apart, which is how the hardware deals blocks to the same
   // XCD (their L2 is one: what they hand each other does not cross the fabric; a matter of speed, not of correctness).  Member 0 owns the stream.
@@ -4151,10 +3921,6 @@ extern "C" __global__ __launch_bounds__(1024, 4) void BROTLI_AMD_KERNEL(const Br
     s.num_metablocks = 0; s.num_spilled = 0; s.num_commands = 0; s.engine_commands = 0; s.general_engine = 0;
     s.peak_trees = 0; s.peak_maps = 0; s.any_compressed = 0;
     s.mlen = 0;
-#ifdef BROTLI_AMD_PROFILE
-    s.prof[0] = s.prof[1] = s.prof[2] = s.prof[3] = s.prof[4] = s.prof[5] = 0;
-    const uint64_t prof_start = __builtin_amdgcn_s_memtime();
-#endif
     s.is_last = 0; s.is_uncompressed = 0; s.is_metadata = 0;
     s.br.set_input((uint64_t)d.in, d.in_size);
     const bool resume = (d.flags & BROTLI_AMD_FLAG_RESUME) && d.resume.window_bits != 0;
@@ -4190,18 +3956,7 @@ extern "C" __global__ __launch_bounds__(1024, 4) void BROTLI_AMD_KERNEL(const Br
     }
 
     const bool mid = resume && d.resume.mid_valid != 0u;
-#ifdef BROTLI_AMD_PROFILE_HDR
-    const uint64_t hdr_prof_t1 = __builtin_amdgcn_s_memtime();
-#endif
     int e = decode_stream(s, resume, d.in_size, st, mid ? &descs[idx].resume : nullptr);
-#ifdef BROTLI_AMD_PROFILE_HDR
-    if (blockIdx.x == 0 && lane == 0)
-      printf("prefix codes (complex form): %llu, %llu symbols; ticks: code-length code %llu, symbol lengths %llu, build_tree %llu (all tables: histogram %llu, first pass %llu, second level + root %llu)\n",
-             g_hdr_prof[4], g_hdr_prof[5], g_hdr_prof[0], g_hdr_prof[1], g_hdr_prof[2], g_hdr_prof[3], g_hdr_prof[6], g_hdr_prof[7]);
-    if (blockIdx.x == 0 && lane == 0)
-      printf("block 0: %llu ticks before the stream, %llu in it: headers %llu, command loops %llu (x 256)\n", (unsigned long long)(hdr_prof_t1 - hdr_prof_t0),
-             (unsigned long long)(__builtin_amdgcn_s_memtime() - hdr_prof_t1), (unsigned long long)s.prof[4], (unsigned long long)s.prof[5]);
-#endif
 
     // result mapping of the one-shot driver (decode.rs:2829-2916, 3382-3397; lib.rs:447-468)
     const bool over = s.br.over();
@@ -4227,76 +3982,8 @@ extern "C" __global__ __launch_bounds__(1024, 4) void BROTLI_AMD_KERNEL(const Br
       st->engine_commands = s.engine_commands;
       st->spilled_metablocks = s.num_spilled;
       st->peak_trees = s.peak_trees; st->peak_map_bytes = s.peak_maps; st->ring_bytes = s.rb_size; st->any_compressed = s.any_compressed;
-#ifdef BROTLI_AMD_PROFILE
-      // debugging aid: cycle split of the command loop in the (otherwise unused) resume block of the status
-      st->resume.bit_pos = __builtin_amdgcn_s_memtime() - prof_start;
-      st->resume.out_pos = s.prof[0];
-      st->resume.dist_rb[0] = (int32_t)(s.prof[1] >> 8); st->resume.dist_rb[1] = (int32_t)(s.prof[2] >> 8); st->resume.dist_rb[2] = (int32_t)(s.prof[3] >> 8);
-      st->resume.dist_rb[3] = (int32_t)s.prof[4]; st->resume.dist_rb_idx = (int32_t)s.prof[5];
-#endif
     }
   }
-#ifdef BROTLI_AMD_PROFILE_LEAN
-  if (blockIdx.x == 0 && lane_id() == 0)
-    printf("lean cmds %llu wait before flush %llu after flush stores %llu (ticks per cmd); ticks per cmd: head %llu literals %llu distance %llu copy %llu\n", g_lean_prof[4],
-           g_lean_prof[5] / g_lean_prof[4], g_lean_prof[6] / g_lean_prof[4], g_lean_prof[0] / g_lean_prof[4],
-           g_lean_prof[1] / g_lean_prof[4], g_lean_prof[2] / g_lean_prof[4], g_lean_prof[3] / g_lean_prof[4]);
-#endif
-#ifdef BROTLI_AMD_PROFILE_SPLIT
-  if (blockIdx.x == 0 && lane_id() == 0 && g_split_prof[37] != 0)
-    printf("record loop: %llu calls, %llu commands (%llu in hand-written runs, %llu with literals, %llu without by the compiled path, %llu words), %llu ticks in the loop; ticks: top %llu, runs %llu, "
-           "head + context bytes %llu, literals %llu, distance %llu, counts + literal store %llu, copy / word + next record %llu\n",
-           g_split_prof[37], g_split_prof[36], g_split_prof[32], g_split_prof[33], g_split_prof[34], g_split_prof[35], g_split_prof[38],
-           g_split_prof[24], g_split_prof[25], g_split_prof[26], g_split_prof[27], g_split_prof[28], g_split_prof[29], g_split_prof[30]);
-  if (blockIdx.x == 0 && lane_id() == 0 && g_split_prof[39] != 0)
-    printf("record loop: %llu ticks between the s_memtime pairs around the runs' waits for the memory pipe (an empty pair costs what tools/ubench says)\n", g_split_prof[39]);
-#endif
-#ifdef BROTLI_AMD_PROFILE_SPEC
-  if (blockIdx.x == 0 && lane_id() == 0)
-    printf("spec rounds %llu lits %llu bits %llu ticks: chunk0 %llu wait %llu resolve %llu move %llu seek %llu\n", g_spec_prof[5], g_spec_prof[6], g_spec_prof[7],
-           g_spec_prof[0], g_spec_prof[1], g_spec_prof[2], g_spec_prof[3], g_spec_prof[4]);
-#endif
-#ifdef BROTLI_AMD_PROFILE_SCAN
-  if (blockIdx.x == 0 && lane_id() == 0 && g_scan_prof[17] != 0)
-    printf("scan engine: %llu invocations, %llu commands, %llu batches, %llu entries; wave 0 ticks: execute %llu S/J1 %llu J2-32 %llu own copies %llu walk %llu resolve %llu wait for REC %llu D2/D4 %llu barrier behind S/J1 %llu barriers of J2-32 %llu\n",
-           g_scan_prof[17], g_scan_prof[16], g_scan_prof[13], g_scan_prof[12], g_scan_prof[6], g_scan_prof[1], g_scan_prof[2], g_scan_prof[8], g_scan_prof[4],
-           g_scan_prof[5], g_scan_prof[3], g_scan_prof[7], g_scan_prof[9], g_scan_prof[10]);
-  if (blockIdx.x == 0 && lane_id() == 0 && g_scan_prof[17] != 0)
-    printf("kernel ticks of block 0: %llu; the engine's ticks: %llu steps, %llu that only walk, %llu last ones\n", (unsigned long long)(__builtin_amdgcn_s_memtime() - scan_prof_t0),
-           g_scan_prof[14], g_scan_prof[15], g_scan_prof[11]);
-  if (blockIdx.x == 0 && lane_id() == 0 && g_scan_prof[17] != 0) printf("wave 1's ticks in REC: %llu; the last wave's in copies that depend on the group's own output: %llu for %llu copies\n", g_scan_prof[24], g_scan_prof[25], g_scan_prof[26]);
-  if (blockIdx.x == 0 && lane_id() == 0 && g_scan_prof[17] != 0)
-    printf("scan engine exits: input ends %llu, counts/limits %llu, distance %llu, by-hand precheck %llu, long run %llu; invocations that took < 64 commands %llu\n",
-           g_scan_prof[18], g_scan_prof[19], g_scan_prof[20], g_scan_prof[21], g_scan_prof[22], g_scan_prof[23]);
-#endif
-#ifdef BROTLI_AMD_PROFILE_WAVES
-  if (blockIdx.x == 0 && lane_id() == 0)
-    for (int k = 0; k < 96; k++) if (g_wave_prof[k][16] != 0) {
-      printf("barrier %2d (%llu times): ticks of waves 0..15 in front of it:", k, g_wave_prof[k][16]);
-      for (int w = 0; w < 16; w++) printf(" %llu", g_wave_prof[k][w] / g_wave_prof[k][16]);
-      printf("\n");
-    }
-#endif
-#ifdef BROTLI_AMD_PROFILE_SCAN
-  if (blockIdx.x == 0 && lane_id() == 0 && g_path_prof[33] != 0) {
-    printf("\npath engine: %llu invocations, %llu regions, %llu commands (%llu listed, %llu executed); wave 0 ticks per region: input %llu J1 %llu path %llu records %llu closure %llu next8 %llu walk %llu details %llu resolve %llu execute %llu own copies %llu\n",
-           g_path_prof[33], g_path_prof[20], g_path_prof[32], g_path_prof[26], g_path_prof[28], g_path_prof[0] / g_path_prof[20], g_path_prof[1] / g_path_prof[20], g_path_prof[2] / g_path_prof[20],
-           g_path_prof[3] / g_path_prof[20], g_path_prof[4] / g_path_prof[20], g_path_prof[5] / g_path_prof[20], g_path_prof[6] / g_path_prof[20], g_path_prof[7] / g_path_prof[20],
-           g_path_prof[8] / g_path_prof[20], g_path_prof[9] / g_path_prof[20], g_path_prof[10] / g_path_prof[20]);
-    printf("\npath engine per region: %llu path positions, %llu closure states in %llu.%llu rounds, %llu.%llu sync rounds, %llu anchors; states by hand %llu in all (%llu records met that said so); records that hit the hop cap %llu, the closure cap %llu\n",
-           g_path_prof[22] / g_path_prof[20], g_path_prof[24] / g_path_prof[20], g_path_prof[23] / g_path_prof[20], (g_path_prof[23] * 10 / g_path_prof[20]) % 10,
-           g_path_prof[21] / g_path_prof[20], (g_path_prof[21] * 10 / g_path_prof[20]) % 10, g_path_prof[27] / g_path_prof[20], g_path_prof[25], g_path_prof[31], g_path_prof[29], g_path_prof[30]);
-    printf("\npath engine resolve alone: %llu per region (the figure called resolve above is then the lane-per-command stores behind it)\n", g_path_prof[11] / g_path_prof[20]);
-    printf("\npath engine per region: %llu items that get a wave (long copies from in front of the region, long literal runs), %llu copies that read the region's own output\n", g_path_prof[12] / g_path_prof[20], g_path_prof[13] / g_path_prof[20]);
-    printf("\npath engine dependent copies: %llu per region, the last wave's ticks in them %llu per region\n", g_path_prof[35] / g_path_prof[20], g_path_prof[34] / g_path_prof[20]);
-    printf("\npath engine literal-run regions: %llu literals in all\n", g_path_prof[19]);
-    printf("\npath engine path phase: chains and entries %llu, ranks %llu (the rest: positions and literals)\n", g_path_prof[17] / g_path_prof[20], g_path_prof[18] / g_path_prof[20]);
-    printf("\npath engine, wave 0 (ticks per region): the walk's anchors %llu, the commands behind them %llu, a gang's wait for the region before's output %llu\n", g_path_prof[15] / g_path_prof[20], g_path_prof[16] / g_path_prof[20], g_path_prof[14] / g_path_prof[20]);
-    printf("\nbetween two invocations of the engine in one metablock: %llu ticks in all, %llu times; inside the engine's calls %llu; from the command loop's start to the first invocation %llu; from the last one's end to the loop's end %llu; the command loops in all %llu\n", g_path_prof[36], g_path_prof[37], g_path_prof[38], g_path_prof[29], g_path_prof[39], g_path_prof[31]);
-    { unsigned long long eng = 0; for (int k = 0; k <= 11; k++) eng += g_path_prof[k]; eng += g_path_prof[14] + g_path_prof[15] + g_path_prof[16]; eng += g_path_prof[17] + g_path_prof[18];
-      printf("\nkernel ticks of block 0 in this launch: %llu; the path engine's regions so far (all launches): %llu\n", (unsigned long long)(__builtin_amdgcn_s_memtime() - scan_prof_t0), eng); }
-  }
-#endif
   if (gang_m > 1u && lane == 0) gang_st32(gang_ctl(), GC_EPOCH, GC_QUIT);   // the stream is done: the gang's helper blocks may go
 #ifdef BROTLI_AMD_GANG_KERNEL
   if (pool && queue[6] == 0u) {

@@ -199,21 +199,6 @@ static_assert(PEC_DEPCHG == PEC_TAKE, "a deliberate share (see above)");
 #endif
 
 
-#ifdef BROTLI_AMD_PROFILE_SCAN
-#ifndef BROTLI_AMD_PATH_PROF_DEFINED
-#define BROTLI_AMD_PATH_PROF_DEFINED
-}  // namespace
-__device__ unsigned long long g_path_prof[40];
-namespace PE_CFG_NS {
-#endif
-#define PE_PROF(k) do { if (me == 0) { uint64_t _t = __builtin_amdgcn_s_memtime(); if (blockIdx.x == 0) pp_acc[k] += _t - pp_t; pp_t = _t; } } while (0)
-#define PE_COUNT(k, v) do { if (me == 0 && blockIdx.x == 0) pp_acc[k] += (v); } while (0)
-#define PE_LANECOUNT(k, cond) do { if (blockIdx.x == 0 && (cond)) atomicAdd(&g_path_prof[k], 1ull); } while (0)
-#else
-#define PE_LANECOUNT(k, cond) do { } while (0)
-#define PE_PROF(k) do { } while (0)
-#define PE_COUNT(k, v) do { } while (0)
-#endif
 
 typedef __attribute__((address_space(3))) uint32_t pe_lds_u32;
 __device__ __forceinline__ uint32_t pe_ctl_ld(uint32_t pb, uint32_t k) { return rfl(*reinterpret_cast<lds_vu32*>(&g_smem[pb + PE_CTL + 4u * k])); }
@@ -655,20 +640,6 @@ __device__ __forceinline__ PeParse pe_eval(const PeCtx& c, uint32_t pos, uint32_
     } } while (0)
 
 // The barrier of the engine's waves: the hardware's.
-#ifdef BROTLI_AMD_PROFILE_WAVES
-// (profile: what every wave of block 0 spends between two barriers -- its ticks from the release of one to its arrival at the next,
-// by the barrier's place in the source; the slowest wave of a step is the one the block waits for)
-#ifndef BROTLI_AMD_WAVE_PROF_DEFINED
-#define BROTLI_AMD_WAVE_PROF_DEFINED
-}  // namespace
-__device__ unsigned long long g_wave_prof[96][17];
-namespace PE_CFG_NS {
-#endif
-#define PE_BAR() do { const uint64_t t_ = __builtin_amdgcn_s_memtime(); if (blockIdx.x == 0 && lane == 0) { g_wave_prof[__COUNTER__ % 96][me] += t_ - wp_t; if (me == 0) g_wave_prof[(__COUNTER__ - 1) % 96][16] += 1; } \
-                      __syncthreads(); wp_t = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define PE_BAR() __syncthreads()
-#endif
 #if PE_CFG_REMOTE
 // (a gang's waits inside an invocation are for another block's work on one region -- whose output may be hundreds of megabytes of overlapping
 // copies: a minute or more of looking, not seconds, before the kernel is stopped rather than the machine)
@@ -739,7 +710,6 @@ pe_again:
   // live in this function: they wait for the owner's next invocation (EPOCH), take its parameters and the image of its table arena, do their
   // regions, say that they have left (READY) and wait again.
   uint32_t role = 0, gang_m = 1, epoch = 0; gu8* gc = nullptr; (void)role; (void)gang_m; (void)epoch; (void)gc;
-  const uint64_t gs_t0 = __builtin_amdgcn_s_memtime(); (void)gs_t0;
   if (REMOTE) {
     // (HC_GANG_M: the gang's blocks; bit 8: a POOL launch -- nobody is dealt to a gang, a block whose own stream is done joins a stream that is
     // not, and a stream's gang is whoever has joined it when an invocation starts: see the kernel)
@@ -777,10 +747,8 @@ pe_again:
     if (role == 0u && gang_m > 1u) {
       if (threadIdx.x == 0u) {   // the helpers have all left the invocation before (they read the image below when they enter one)
         uint32_t spins = 0; (void)spins;
-        const uint64_t t0_ = __builtin_amdgcn_s_memtime(); (void)t0_;
         const uint32_t expected = *reinterpret_cast<lds_vu32*>(&g_smem[LDS_HCTL + 4u * HC_GANG_READY]);   // (the helpers of every invocation so far, summed)
         while (gang_ld32(gc, GC_READY) != expected) { __builtin_amdgcn_s_sleep(8); PE_SPIN_CHECK(spins); }
-        GANG_STAT(gc, 0, 1); GANG_STAT(gc, 5, __builtin_amdgcn_s_memtime() - t0_);
       }
       __syncthreads();
       const uint32_t ab = (pb - LDS_FIXED + 15u) & ~15u;   // (the table arena lies between the fixed part and the engine's)
@@ -792,7 +760,7 @@ pe_again:
       else if (threadIdx.x == 41u) gang_st64(gc, GC_MEMBERS, ((uint64_t)epoch << 32) | (uint64_t)gang_m);   // (with the invocation it is for: a pool's late comer must not take the next one's for this one's)
       gang_drain();
       __syncthreads();
-      if (threadIdx.x == 0u) { gang_release(); GANG_STAT(gc, 18, __builtin_amdgcn_s_memtime() - gs_t0); }   // (the state, the plan and EPOCH follow below, where wave 0 has put the state together)
+      if (threadIdx.x == 0u) { gang_release(); }   // (the state, the plan and EPOCH follow below, where wave 0 has put the state together)
     } else if (role != 0u) {
       if (threadIdx.x == 0u) {
         uint32_t last = *reinterpret_cast<lds_vu32*>(&g_smem[LDS_HCTL + 4u * HC_GANG_EPOCH]);
@@ -824,9 +792,6 @@ pe_again:
     }
   }
   __syncthreads();  // the parameters are in place
-#ifdef BROTLI_AMD_PROFILE_SCAN
-  uint64_t pp_acc[32] = {}; uint64_t pp_t = __builtin_amdgcn_s_memtime();
-#endif
   PeCtx c;
   c.pb = pb; c.td = pb + PE_TD; c.tc = pb + PE_TC;
   c.lit_tree = pe_ctl_ld(pb, SCC_LIT_TREE); c.cmd_tree = pe_ctl_ld(pb, SCC_CMD_TREE); c.dtree = pe_ctl_ld(pb, SCC_DT0);
@@ -909,26 +874,8 @@ pe_again:
   const bool td_ok = td_n <= PE_TD_ENTRIES;   // (a table that does not fit: the engine leaves the metablock to the one-wave loop)
   uint32_t pre_a = 0, pre_b = 0; bool pre_ok = false;  // the next region's input dwords of this lane, once they are known
   uint32_t lbdw = 0, le = 0, wn = 0; uint64_t P0 = 0;   // the region: its first dword, the entry's bit in it, its closure states, where its output starts
-#ifdef BROTLI_AMD_PROFILE_WAVES
-  uint64_t wp_t = __builtin_amdgcn_s_memtime(); (void)wp_t;
-#endif
   uint32_t rseq = 0;                                     // regions of this invocation so far (the one at hand included)
   uint32_t kseq = 0; (void)kseq;                         // (a gang: the number of the region this engine is at)
-  uint64_t gs_arr = 0; (void)gs_arr;                     // (gang statistics: when the stream arrived at this engine's region)
-#ifdef BROTLI_AMD_GANG_TRACE   // (a gang: a line a region of invocation BROTLI_AMD_GANG_TRACE with wave 0's clock at every hand-over -- which chain binds?)
-  uint64_t gt_ts[15] = {};
-#define GT(k) do { gt_ts[k] = __builtin_amdgcn_s_memrealtime(); } while (0)   // (the 100 MHz clock all CUs share: s_memtime is a CU's own)
-#define GTC(w, v) do { if (lane == 0) pe_atomic_add_uniform(pb + PE_CTL + 4u * (120u + (w)), (v)); } while (0)
-#else
-#define GT(k) do { } while (0)
-#define GTC(w, v) do { } while (0)
-#endif
-#ifdef BROTLI_AMD_PROFILE_REGIONS
-  uint64_t rg_ts[10] = {}; uint64_t rg_prev_end = 0; uint64_t rg_rt[4] = {}; uint32_t rg_rn[4] = {};
-#define RG_STAMP(k) do { rg_ts[k] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define RG_STAMP(k) do { } while (0)
-#endif
   // What the region's tables start from (the engine's wave 0): the window and the counters of the phases.
   auto setup_tables = [&](const uint32_t lbdw_, const uint32_t le_, const uint32_t bits, const uint32_t mode, const uint32_t ent_) {
     pe_ctl_st(pb, PEC_LBDW, lbdw_); pe_ctl_st(pb, PEC_LE, le_); pe_ctl_st(pb, PEC_L, bits);
@@ -973,7 +920,7 @@ pe_again:
       uint32_t iv[NI];
       _Pragma("unroll") for (uint32_t q = 0; q < NI; q++) { const uint32_t i = PE_CHUNKS + 6u + T + q * 64u * GW; iv[q] = (i < ndw && lbdw + i < limit_dw) ? in_dw[lbdw + i] : 0u; }
       _Pragma("unroll") for (uint32_t q = 0; q < NI; q++) { const uint32_t i = PE_CHUNKS + 6u + T + q * 64u * GW; if (i < ndw) lds_st32(pb + PE_IN + (i << 2), iv[q]); } }
-    PE_BAR();
+    __syncthreads();
     const uint32_t base = T * PE_RUN_SB;
     const bool act = T >= et && base < lim;
     uint32_t e = T == et ? ent % PE_RUN_SB : 0u, ex = 0, cnt = 0, np = 0;
@@ -983,7 +930,7 @@ pe_again:
     const uint32_t rl = pb + PE_RUN_LIT + ((uint32_t)P0 & 15u);   // (the literals in LDS as they lie in memory, modulo sixteen: see write_out)
     const uint32_t wt = pb + PE_RUN_EX + 64u * GW;   // (behind the lanes' exits, in the room of the path's chunk words)
     for (uint32_t i = T; i < 2048u; i += 64u * GW) { uint32_t sy, ln; sc_lookup(c.lit_tree, i, sy, ln); lds_st16(wt + (i << 1), ln <= 11u ? (sy << 4) | ln : 0u); }
-    PE_BAR();
+    __syncthreads();
     // The lane's stream bits live in five registers (its 128 and the 32 behind them), moved down by every code word's length
     // The lane's stream bits live in five registers (its 128 and the 32 behind them), moved down by every code word's length
     // (`part`: the 256 bits the lane decodes -- its own, T, in the passes over the whole region; any, where only the parts whose entry
@@ -1017,11 +964,7 @@ pe_again:
       }
       if (on && !emit) { cnt = k; ex = y >= PE_RUN_SB ? y - PE_RUN_SB : 0u; }
     };
-    PE_PROF(1);
-    RG_STAMP(6);
     decode(act, false, 0u, 0u, T, e);
-    RG_STAMP(7);
-    PE_PROF(17);
     // The entries settle: a part whose entry is not where the part before it ends is decoded again from there.  The first such round
     // is nearly everybody's (the guesses were guesses) and goes lane by part as the first pass did; in the rounds behind it few parts
     // are left -- a high-entropy code re-synchronises slowly, one part in seven or so passes a wrong exit on -- and those go on a list
@@ -1034,13 +977,13 @@ pe_again:
       const uint32_t qn = pb + PE_CTL + 4u * (PEC_CHG + round % 3u);      // (a counter of three in turns: this round's list length)
       const uint32_t qa = pb + PE_RUN_QA + (round & 1u) * 64u * GW * 2u;
       if (T == 0u) lds_st32(pb + PE_CTL + 4u * (PEC_CHG + (round + 1u) % 3u), 0u);
-      PE_BAR();
+      __syncthreads();
       // part T: does it start where part T - 1 ends?
       const uint32_t ne = T > et ? lds_ld8(exa + T - 1u) : lds_ld8(ena + T);
       const bool changed = (bool)((uint32_t)act & (uint32_t)(T > et) & (uint32_t)(ne != lds_ld8(ena + T)));
       // (bit 15 of a part's count: on this round's list -- a lane that goes on into the next part, below, stops in front of such a one)
       { const uint32_t cv = lds_ld16(cna + (T << 1)); lds_st16(cna + (T << 1), (cv & 0x7FFFu) | (changed ? 0x8000u : 0u)); }
-      if (round >= 24u) { if (changed) pe_atomic_min(pb + PE_CTL + 4u * PEC_TMIN, T); PE_BAR(); tmin = pe_ctl_ld(pb, PEC_TMIN); break; }   // (a code that does not re-synchronise: the region ends where it has not)
+      if (round >= 24u) { if (changed) pe_atomic_min(pb + PE_CTL + 4u * PEC_TMIN, T); __syncthreads(); tmin = pe_ctl_ld(pb, PEC_TMIN); break; }   // (a code that does not re-synchronise: the region ends where it has not)
       {
         const uint64_t cm = __ballot(changed);
         if (cm != 0ull) {
@@ -1050,11 +993,8 @@ pe_again:
           if (changed) lds_st16(qa + ((b0 + __builtin_amdgcn_mbcnt_hi((uint32_t)(cm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cm, 0u))) << 1), T | (ne << 11));
         }
       }
-      PE_BAR();
+      __syncthreads();
       const uint32_t nq = rfl(lds_ld32(qn));
-#ifdef BROTLI_AMD_PROFILE_REGIONS
-      if (round < 4u) { rg_rt[round] = __builtin_amdgcn_s_memtime() - rg_ts[7]; rg_rn[round] = nq; }
-#endif
       if (nq == 0u) break;
       if (nq >= 32u * GW) {   // most of the region: lane by part
         if (changed) lds_st8(ena + T, ne);
@@ -1078,45 +1018,36 @@ pe_again:
       }
     }
     // part T's entry and count, as they settled
-    PE_BAR();
+    __syncthreads();
     e = lds_ld8(ena + T); cnt = act ? lds_ld16(cna + (T << 1)) & 0x7FFFu : 0u;
-    PE_PROF(18);
-    RG_STAMP(8);
     if (T >= tmin) cnt = 0;
     // ranks: exclusive prefix sum of the lanes' counts over the block; the region ends in front of the lane the literals' room runs out in
     uint32_t incl = sc_scan(cnt);
     if (lane == 63u) lds_st32(pb + PE_CTL + 4u * (PEC_WSUM + me), incl);
-    PE_BAR();
+    __syncthreads();
     uint32_t wbase;
     { const uint32_t ws = lane < GW ? lds_ld32(pb + PE_CTL + 4u * (PEC_WSUM + lane)) : 0u; const uint32_t wi = sc_scan(ws); wbase = rdlane(wi - ws, me); }
     uint32_t cb = wbase + incl - cnt;
     if (cb + cnt > PE_RUN_LITCAP) pe_atomic_min(pb + PE_CTL + 4u * PEC_TMIN, T);
-    PE_BAR();
+    __syncthreads();
     tmin = pe_ctl_ld(pb, PEC_TMIN);
     if (T >= tmin) cnt = 0;
     if (T == tmin || (tmin >= 64u * GW && T == 64u * GW - 1u)) *reinterpret_cast<lds_vu32*>(&g_smem[pb + PE_CTL + 4u * PEC_RN]) = T == tmin ? cb : cb + cnt;
-    PE_BAR();
+    __syncthreads();
     const uint32_t Rn = pe_ctl_ld(pb, PEC_RN);
-    PE_COUNT(22, Rn);
     if (me == 0) {
       const PeStream st = pe_st_load(pb);
       uint32_t take = st.run_rem;
       const uint32_t cap1 = Rn != 0u ? Rn - 1u : 0u, cap2 = st.quota > 1u ? st.quota - 1u : 0u;
       take = take < cap1 ? take : cap1; take = take < st.bl0 ? take : st.bl0; take = take < cap2 ? take : cap2;
       pe_ctl_st(pb, PEC_TAKE, take);
-#ifdef BROTLI_AMD_PE_DEBUG
-      if (blockIdx.x == 0 && lane == 0) printf("run region: L %u entry %u Rn %u run_rem %u bl0 %u quota %u mlen %d -> take %u\n", c.L, ent, Rn, st.run_rem, st.bl0, st.quota, st.mlen, take);
-#endif
     }
-    PE_BAR();
+    __syncthreads();
     const uint32_t take = pe_ctl_ld(pb, PEC_TAKE);
-    PE_PROF(2);
-    RG_STAMP(9);
     // the literals to their ranks (and the bit of the first one that does not go out: where the stream goes on)
     decode(cnt != 0u && cb <= take, true, cb, take, T, e);
     if (cnt != 0u && cb <= take && take < cb + cnt) *reinterpret_cast<lds_vu32*>(&g_smem[pb + PE_CTL + 4u * PEC_NEXTRANK]) = np;
-    PE_BAR();
-    PE_PROF(4);
+    __syncthreads();
     write_out(rl, out + P0, take);
     if (me == 0) {
       PeStream st = pe_st_load(pb);
@@ -1125,18 +1056,16 @@ pe_again:
       st.b = (lbdw << 5) + npb;
       pe_ctl_st(pb, PEC_CONT, (take != 0u && st.run_rem != 0u) ? 1u : 0u); pe_ctl_st(pb, PEC_NEXT_LBDW, st.b >> 5);
       pe_ctl_st(pb, PEC_FIN, (st.run_rem == 0u && npb + 96u <= c.L + 128u) ? 1u : 0u);
-      PE_COUNT(19, take);
       pe_st_store(pb, st);
     }
-    PE_BAR();
-    PE_PROF(5);
+    __syncthreads();
     if (pe_ctl_ld(pb, PEC_FIN) != 0u) {
       // The run is over: what is left of its command is a distance and a copy (decode.rs:2066-2131, 2583-2720).  Round 4 handed every
       // such command to the checked loop -- the invocation ended, the loop finished the command, and the engine came back for the next one
       // (a stream of high-entropy literals is nothing but such commands).  Now wave 0 takes the plain case in place -- a distance inside
       // the window, a copy inside every limit -- and the next region starts at the next command; anything else is the checked loop's as before.
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the run's literals are in memory before the copy reads them)
-      PE_BAR();
+      __syncthreads();
       if (me == 0) {
         PeStream st = pe_st_load(pb);
         const uint32_t yb = st.b - (lbdw << 5);
@@ -1186,7 +1115,7 @@ pe_again:
           pe_ctl_st(pb, PEC_CONT, 1u); pe_ctl_st(pb, PEC_NEXT_LBDW, st.b >> 5);
         }
       }
-      PE_BAR();
+      __syncthreads();
     }
     if (pe_ctl_ld(pb, PEC_CONT) == 0u) return 2u;
     {
@@ -1201,14 +1130,12 @@ pe_again:
   auto build = [&]() -> uint32_t {
     lbdw = pe_ctl_ld(pb, PEC_LBDW); le = pe_ctl_ld(pb, PEC_LE);
     c.L = pe_ctl_ld(pb, PEC_L);
-    PE_COUNT(20, 1);
     // ---- input (asked for behind the resolve of the region before, where there was one) ----
     if (!pre_ok) { pre_a = lbdw + T < limit_dw ? in_dw[lbdw + T] : 0u; pre_b = (T < 6u && lbdw + PE_CHUNKS + T < limit_dw) ? in_dw[lbdw + PE_CHUNKS + T] : 0u; }
     lds_st32(pb + PE_IN + (T << 2), pre_a);
     if (T < 6u) lds_st32(pb + PE_IN + ((PE_CHUNKS + T) << 2), pre_b);
     pre_ok = false;
-    PE_BAR();
-    PE_PROF(0);
+    __syncthreads();
     if (!REMOTE && me == 0 && pe_ctl_ld(pb, PEC_STATE + 20) != 0u) {
       // the invocation's first region: is its first command one with a long literal run?  (later regions know from the resolve
       // of the region before)
@@ -1226,7 +1153,7 @@ pe_again:
       pe_st_store(pb, st);
     }
 #if !PE_CFG_REMOTE
-    PE_BAR();   // (the first region's mode is wave 0's word)
+    __syncthreads();   // (the first region's mode is wave 0's word)
     if (pe_ctl_ld(pb, PEC_MODE) != 0u) { c.L = pe_ctl_ld(pb, PEC_L); return run_region(); }
 #endif
     // ---- J1: the length of the literal code word at every bit, eight bits per lane and pass ----
@@ -1251,8 +1178,7 @@ pe_again:
       const uint32_t w0 = Lw[0] | (Lw[1] << 8) | (Lw[2] << 16) | (Lw[3] << 24), w1 = Lw[4] | (Lw[5] << 8) | (Lw[6] << 16) | (Lw[7] << 24);
       lds_st32(pb + PE_J1F + pos0, w0); lds_st32(pb + PE_J1F + pos0 + 4u, w1);
     }
-    PE_BAR();
-    PE_PROF(1);
+    __syncthreads();
     // ---- the path: chunk T's chain from its entry.  Inside a wave the entries settle through the lanes (a chunk's entry is
     // the exit of the chunk before: one cross-lane read a step, no barrier); between waves through LDS, a barrier a round.
     // A wave's entry is exact after as many rounds as waves lie in front of it, so PE_SYNC_ROUNDS rounds make the path exact
@@ -1301,14 +1227,14 @@ pe_again:
       if (lane == 63u) lds_st8(pb + PE_EX + slot * 64u + me, ex);
       const uint32_t fw = pb + PE_CTL + 4u * (PEC_CHG + rounds % 3u);
       if (T == 0u) lds_st32(pb + PE_CTL + 4u * (PEC_CHG + (rounds + 1u) % 3u), 0u);
-      PE_BAR();
+      __syncthreads();
       const uint32_t ne = me == 0u ? 0u : rfl(lds_ld8(pb + PE_EX + slot * 64u + me - 1u));
       if (ne != wave_entry && lane == 0) lds_st32(fw, 1u);
       wave_entry = ne;
       rounds++;
-      PE_BAR();
+      __syncthreads();
       if (rfl(lds_ld32(fw)) == 0u) break;
-      if (rounds >= PE_SYNC_ROUNDS) { if (T == 0u) lds_st32(pb + PE_CTL + 4u * PEC_TMIN, 0u); PE_BAR(); break; }  // (cannot happen: see above; no path, no region)
+      if (rounds >= PE_SYNC_ROUNDS) { if (T == 0u) lds_st32(pb + PE_CTL + 4u * PEC_TMIN, 0u); __syncthreads(); break; }  // (cannot happen: see above; no path, no region)
     }
     // the chunk's own path positions: the chain from its entry, out of the registers
     uint32_t pm = 0;
@@ -1321,8 +1247,6 @@ pe_again:
         y += (d >> ((y & 3u) * 8u)) & 15u;
       }
     }
-    PE_COUNT(21, rounds);
-    PE_PROF(17);
     // bits at or beyond L - 16 are not path positions (a code word there may reach beyond the input)
     {
       const uint32_t lim = c.L > 16u ? c.L - 16u : 0u;
@@ -1334,7 +1258,7 @@ pe_again:
     uint32_t cnt = (uint32_t)__builtin_popcount(pm);
     uint32_t incl = sc_scan(cnt);
     if (lane == 63u) lds_st32(pb + PE_CTL + 4u * (PEC_WSUM + me), incl);
-    PE_BAR();
+    __syncthreads();
     uint32_t wbase = 0;
     {
       const uint32_t ws = lane < GW ? lds_ld32(pb + PE_CTL + 4u * (PEC_WSUM + lane)) : 0u;
@@ -1343,12 +1267,11 @@ pe_again:
     }
     uint32_t cb = wbase + incl - cnt;
     if (cb + cnt > PE_RANKS) pe_atomic_min(pb + PE_CTL + 4u * PEC_TMIN, T);  // the ranks run out inside this chunk: the region ends in front of it
-    PE_BAR();
+    __syncthreads();
     const uint32_t tmin = pe_ctl_ld(pb, PEC_TMIN);
     if (T >= tmin) { pm = 0; cnt = 0; }
     if (T == tmin || (tmin == PE_CHUNKS && T == PE_CHUNKS - 1u)) *reinterpret_cast<lds_vu32*>(&g_smem[pb + PE_CTL + 4u * PEC_RN]) = T == tmin ? cb : cb + cnt;
     lds_st32(pb + PE_PM + (T << 2), pm); lds_st16(pb + PE_CB + (T << 1), cb);
-    PE_PROF(18);
     {
       // the chunk's path positions: bit, literal, flag -- two at a time, out of the chunk's 64 input bits
       const uint64_t w = (uint64_t)lds_ld32(pb + PE_IN + (T << 2)) | ((uint64_t)lds_ld32(pb + PE_IN + ((T + 1u) << 2)) << 32);
@@ -1383,10 +1306,8 @@ pe_again:
     // sentinels: the sixteen bytes of J1 from Lp on carry the path flag, so that the records' hop loops stop there by themselves
     // (no path position lies there: nobody else writes them)
     if (T < 16u) lds_st8(pb + PE_J1F + c.Lp + T, lds_ld8(pb + PE_J1F + c.Lp + T) | 0x80u);
-    PE_BAR();
+    __syncthreads();
     c.Rn = pe_ctl_ld(pb, PEC_RN);
-    PE_PROF(2);
-    PE_COUNT(22, c.Rn);
     if (pe_ctl_ld(pb, PEC_MODE) != 0u) {
       // ---- a region of a long literal run: the path's literals, as many as the run, the literal block, the output limits and
       // the region hold (one short of each limit: what happens AT a limit is the checked loop's), go out; the next region
@@ -1398,7 +1319,7 @@ pe_again:
         take = take < cap1 ? take : cap1; take = take < st.bl0 ? take : st.bl0; take = take < cap2 ? take : cap2;
         pe_ctl_st(pb, PEC_TAKE, take);
       }
-      PE_BAR();
+      __syncthreads();
       const uint32_t take = pe_ctl_ld(pb, PEC_TAKE);
       {
         gu8* const o = out + P0;
@@ -1414,10 +1335,9 @@ pe_again:
         const uint32_t np = take != 0u ? rfl(lds_ld16(pb + PE_POR + (take << 1))) : ent;
         st.b = (lbdw << 5) + np;
         pe_ctl_st(pb, PEC_CONT, (take != 0u && st.run_rem != 0u) ? 1u : 0u); pe_ctl_st(pb, PEC_NEXT_LBDW, st.b >> 5);
-        PE_COUNT(19, take);
         pe_st_store(pb, st);
       }
-      PE_BAR();
+      __syncthreads();
       if (pe_ctl_ld(pb, PEC_CONT) == 0u) return 2u;
       {
         const uint32_t nl = pe_ctl_ld(pb, PEC_NEXT_LBDW);
@@ -1449,7 +1369,6 @@ pe_again:
       uint32_t sid[NSL], dsc[NSL], ry[NSL], rn[NSL], rimp[NSL]; bool has[NSL], res[NSL];
       _Pragma("unroll") for (uint32_t t = 0; t < NSL; t++) { sid[t] = 0u; dsc[t] = 0u; ry[t] = 0u; rn[t] = 0u; rimp[t] = 0u; has[t] = false; res[t] = false; }
       if (source == 0u && T == 0u) { has[0] = true; sid[0] = PE_RANKS; dsc[0] = le | 0x8000u; }  // the closure's first state: a command starts at the entry
-      uint32_t iters = 0; (void)iters;
       bool dry = false;  // the source has nothing more for this wave
       for (;;) {
         {  // free slots take new states off the source: one LDS atomic per wave and pass for all of them
@@ -1497,7 +1416,6 @@ pe_again:
           _Pragma("unroll") for (uint32_t t = 0; t < NSL; t++) dd[t] = has[t] ? dsc[t] : 0u;
           pe_eval_rec<NSL>(c, dd, has, res, ry, rn, rimp, code, nxt);
         }
-        iters++;
         {
           bool app[NSL]; uint64_t am[NSL]; uint32_t slot[NSL]; uint32_t wantw = 0;
           _Pragma("unroll") for (uint32_t t = 0; t < NSL; t++) { app[t] = (bool)((uint32_t)has[t] & (uint32_t)(code[t] == 1u)); am[t] = __ballot(app[t]); wantw += (uint32_t)__popcll(am[t]); slot[t] = 0; }
@@ -1511,7 +1429,6 @@ pe_again:
           _Pragma("unroll") for (uint32_t t = 0; t < NSL; t++) {
             const bool fin = (bool)((uint32_t)has[t] & (uint32_t)(code[t] != 3u));                  // the record is there (code 3: more hops next time, from ry / rn)
             const bool goes_on = (bool)((uint32_t)app[t] & (uint32_t)(slot[t] < PE_WCAP));           // ... and leads to a state that is not a path state: this lane's next
-            PE_LANECOUNT(30, app[t] && slot[t] >= PE_WCAP);
             const uint32_t nx = goes_on ? PE_RANKS + slot[t] : code[t] == 0u ? nxt[t] : code[t] == 2u ? (uint32_t)PEN_END : (uint32_t)PEN_BYHAND;
             // (no masks: a lane with nothing to store writes the scratch word)
             lds_st16(goes_on ? pb + PE_WST + (slot[t] << 1) : pb + PE_CTL + 4u * PEC_SCRATCH, nxt[t]);
@@ -1523,19 +1440,17 @@ pe_again:
           }
         }
       }
-      PE_COUNT(23 - 12 * source, iters);
     };
 #ifndef BROTLI_AMD_PE_BULK_NS
 #define BROTLI_AMD_PE_BULK_NS 2
 #endif
     records_loop(std::integral_constant<uint32_t, BROTLI_AMD_PE_BULK_NS>{}, 0u, c.Rn + seed_n);
-    PE_BAR();
+    __syncthreads();
     {
       const uint32_t tail_n = pe_ctl_ld(pb, PEC_TAILN) < PE_TAILCAP ? pe_ctl_ld(pb, PEC_TAILN) : PE_TAILCAP;
       if (me < PE_TAIL_WAVES && tail_n != 0u) records_loop(std::integral_constant<uint32_t, 1>{}, 1u, tail_n);
     }
-    PE_BAR();
-    PE_COUNT(24, pe_ctl_ld(pb, PEC_WN) < PE_WCAP ? pe_ctl_ld(pb, PEC_WN) : PE_WCAP);
+    __syncthreads();
     wn = pe_ctl_ld(pb, PEC_WN) < PE_WCAP ? pe_ctl_ld(pb, PEC_WN) : PE_WCAP;
     if (me == 0) {
       const uint32_t raw = pe_ctl_ld(pb, PEC_WN); uint32_t rbl = pe_ctl_ld(pb, PEC_STATE + 8);
@@ -1548,7 +1463,6 @@ pe_again:
       } else if (raw < PE_GROW_BELOW && rbl < PE_RBL) rbl <<= 1;
       pe_ctl_st(pb, PEC_STATE + 8, rbl);
     }
-    PE_PROF(4);
     // ---- NEXT8: the state eight commands on (PEN_NONE where the way there is not all records) ----
     // (twelve states a lane side by side -- a region's states in one go, as a rule --: the phase is eight dependent LDS round
     // trips whatever the number of states a lane carries through them)
@@ -1571,7 +1485,7 @@ pe_again:
       _Pragma("unroll") for (uint32_t t = 0; t < NW; t++)
         if (ix[t] < PE_STATES) lds_st16(pb + PE_N8 + (ix[t] << 1), a[t] < PEN_FIRST_SPECIAL ? a[t] : (uint32_t)PEN_NONE);
     }
-    PE_BAR();
+    __syncthreads();
     if (PE_JUMP_LOG == 4) {
       // ... and from it the state sixteen commands on, in place: every thread its own states' (one in 1024), read before the
       // barrier, written behind it
@@ -1586,14 +1500,13 @@ pe_again:
         const uint32_t w2 = lds_ld16(pb + PE_N8 + ((b2[t] < PEN_FIRST_SPECIAL ? b2[t] : 0u) << 1));
         b2[t] = b2[t] < PEN_FIRST_SPECIAL ? w2 : (uint32_t)PEN_NONE;
       }
-      PE_BAR();
+      __syncthreads();
       _Pragma("unroll") for (uint32_t t = 0; t < PER; t++) {
         const uint32_t i = T + t * 64u * GW;
         if (i < c.Rn || (i >= PE_RANKS && i < PE_RANKS + wn)) lds_st16(pb + PE_N8 + (i << 1), b2[t] < PEN_FIRST_SPECIAL ? b2[t] : (uint32_t)PEN_NONE);
       }
-      PE_BAR();
+      __syncthreads();
     }
-    PE_PROF(5);
     return 0u;
   };
   // (a gang, wave 0) The stream's state as the region before's resolve left it -- or the word that it will not come: the invocation ended in front
@@ -1604,7 +1517,6 @@ pe_again:
   auto full_arrival = [&](const bool walked) {
     const uint32_t want = (epoch << 12) | kseq;
     uint64_t v; uint32_t spins = 0; bool arrived, stopped; (void)spins;
-    const uint64_t t0_ = __builtin_amdgcn_s_memtime(); (void)t0_;
     for (;;) {
       v = gang_ld64(gc, lane < GC_STATE_WORDS ? GC_STATE + 8u * lane : GC_STOP);
       arrived = __ballot(lane < GC_STATE_WORDS && (uint32_t)(v >> 32) == want) == ((1ull << GC_STATE_WORDS) - 1ull);
@@ -1612,7 +1524,6 @@ pe_again:
       if (arrived || stopped) break;
       __builtin_amdgcn_s_sleep(1); PE_SPIN_CHECK(spins);
     }
-    GANG_STAT(gc, 39, __builtin_amdgcn_s_memtime() - t0_);
     uint32_t ok_ = 0u;
     if (arrived && (rdlane((uint32_t)v, 25) & 1u) != 0u) {   // (the region before's resolve said that the stream goes on)
       if (lane < 25u) lds_st32(pb + PE_CTL + 4u * (PEC_STATE + lane), (uint32_t)v);   // the state into this engine's own words
@@ -1625,7 +1536,6 @@ pe_again:
         pe_ctl_st(pb, PEC_LAG, rl == 2u ? g26 + g27 : rl == 1u ? g26 : 0u); }
     }
     if (ok_ == 0u) {
-      if (!arrived) GANG_STAT(gc, 32, 1); else if ((rdlane((uint32_t)v, 25) & 1u) == 0u) GANG_STAT(gc, 33, 1); else { const PeStream st = pe_st_load(pb); if (st.b != pe_ctl_ld(pb, PEC_MYENTRY)) GANG_STAT(gc, 34, 1); else GANG_STAT(gc, 36, 1); }
       if (arrived && lane == 0u) gang_st64(gc, GC_STOP, ((uint64_t)epoch << 32) | (uint64_t)kseq);   // (the same word, if the resolve before has written it)
       pe_ctl_st(pb, PEC_CONT, 0u);
     }
@@ -1645,7 +1555,6 @@ pe_again:
     const uint32_t bw = (me + GW - 1u) & (GW - 1u);  // this wave's batch (wave 0, which walks, gets the last one)
     uint32_t dr0 = 0, dr1 = 0, dr2 = 0, dr3 = 0;
     if (me == 0) {
-      if (REMOTE) GANG_STAT(gc, 28, __builtin_amdgcn_s_memtime() - gs_arr);   // arrival .. the walk's start
       __builtin_amdgcn_s_setprio(3);  // (the walk is the one chain everybody waits for: first in line on its SIMD)
       uint32_t id = PE_RANKS, na = 0;
       uint32_t id_hand = PEN_NONE;   // (a gang) the first of the states the walk added itself: NEXT8 does not know them
@@ -1668,9 +1577,6 @@ pe_again:
         if (REMOTE && !long_run) {   // (a gang) the state the stream enters in is one of the window's entry seeds: its record is there, and NEXT8 knows it
           const uint32_t sn_ = pe_ctl_ld(pb, PEC_SEEDN), off_ = le - pe_ctl_ld(pb, PEC_SEEDLO);
           if (off_ < sn_) { id = PE_RANKS + 1u + off_; id_hand = PEN_NONE; seeded = true; }
-#ifdef BROTLI_AMD_SEED_DEBUG
-          if (lane == 0 && kseq < 400u) printf("seed: region %u role %u le %u lo %u n %u hit %d L %u\n", kseq, role, le, pe_ctl_ld(pb, PEC_SEEDLO), sn_, (int)seeded, c.L);
-#endif
         }
         if (seeded) { }
         else if (slot >= PE_WCAP || long_run) id = PEN_NONE;   // (no room for the entry's state: nothing listed, the checked loop's)
@@ -1702,7 +1608,6 @@ pe_again:
         if (id >= PEN_FIRST_SPECIAL) walk_on = false;
       }
       if (REMOTE) { id = rfl(id); na = rfl(na); }   // (uniform, and in scalar registers for what follows)
-      if (REMOTE) GANG_STAT(gc, 29, __builtin_amdgcn_s_memtime() - gs_arr);   // .. the entry's states and the first anchor
       if (walk_on) {
         // The anchors by hand: one dependent LDS read an anchor is all the chain asks for, and the compiled loop wrapped it in
         // thirty-five instructions (the lane's own execution mask, the counter in a vector register): 330 clocks an anchor.
@@ -1728,8 +1633,6 @@ pe_again:
       // ... then the commands behind the last anchor, up to the first record that is no way on: lane j follows the records j
       // commands on (the lanes side by side: a dozen dependent reads for all of them, where one command after the other by the
       // wave as a whole cost a third of the walk), the list's entries are theirs
-      if (!REMOTE) PE_PROF(15);   // (one block: the anchors)
-      if (REMOTE) GANG_STAT(gc, 38, __builtin_amdgcn_s_memtime() - gs_arr);   // .. the anchors
       uint32_t m = PE_JUMP * na, desc;
       if (REMOTE && id >= PEN_FIRST_SPECIAL) { desc = le | 0x8000u; if (lane == 0) lds_st16(pb + PE_LIST, desc); }   // (no room for the entry's state: nothing listed -- the list's closing entry says where the stream stands)
       else for (;;) {
@@ -1748,16 +1651,8 @@ pe_again:
         if (J < 64u) { m += J; desc = rdlane(dv, J); id = rdlane(sv, J); break; }
         m += 64u; id = rdlane(nxv, 63);
       }
-      if (!REMOTE) PE_PROF(16);   // (one block: the commands behind the last anchor)
       // the last command needs its distance: 64 bits at the closing state
       if (m != 0u && (desc >> 15) == 0u && (desc & 0x7FFFu) + 64u > c.L) m--;
-#ifdef BROTLI_AMD_PE_DEBUG
-      if (REMOTE && blockIdx.x == 0 && lane == 0 && kseq >= 33u && kseq <= 36u) {
-        printf("   walk of region %u: le %u, id_hand %u, anchors %u, listed %u, closing state %x (id %u), L %u Lp %u\n", kseq, le, id_hand, na, m, desc, id, c.L, c.Lp);
-        for (uint32_t q = 0; q < 4u; q++) printf("     hand state %u: desc %x next %u\n", q, lds_ld16(pb + PE_WST + ((wn + q) << 1)), lds_ld16(pb + PE_NEXT + ((PE_RANKS + wn + q) << 1)));
-        for (uint32_t q = 0; q < (m < 12u ? m + 1u : 12u); q++) printf("     list %u: %x\n", q, lds_ld16(pb + PE_LIST + (q << 1)));
-      }
-#endif
       if (REMOTE && m != 0u) {
         // (a gang) where the stream goes on if every command listed goes through -- the next region's engine starts its walk from there while
         // this region is resolved: the first bit of the command the list closes with (behind the distance code, if it starts with one)
@@ -1792,11 +1687,7 @@ pe_again:
       lds_sync();
       pe_ctl_st(pb, PEC_WDONE, 1u);
       __builtin_amdgcn_s_setprio(BROTLI_AMD_DECODER_PRIO);  // (back to the decoding wave's own)
-      PE_COUNT(26, m); PE_COUNT(27, na);
     }
-    PE_PROF(6);
-    if (REMOTE && me == 0) GANG_STAT(gc, 24, __builtin_amdgcn_s_memtime() - gs_arr);   // arrival .. walk done
-    if (REMOTE && me == 0) GT(1);
     {
       const uint32_t k0 = bw << 6;
       uint32_t na_k, m_k;
@@ -1840,12 +1731,8 @@ pe_again:
         }
       }
     }
-    PE_BAR();
-    RG_STAMP(0);   // walk + details done
-    if (REMOTE && me == 0) GANG_STAT(gc, 25, __builtin_amdgcn_s_memtime() - gs_arr);   // .. details done
-    if (REMOTE && me == 0) GT(2);
+    __syncthreads();
     const uint32_t m = pe_ctl_ld(pb, PEC_M);
-    PE_PROF(7);
     // ---- resolve: wave w takes batch w (64 commands), all batches side by side.  What one batch needs from the batches in front
     // of it -- the sums (literals, commands, distances, output bytes) and the distance ring (decode.rs:2017-2049) -- goes
     // through LDS: every batch resolves its ring against an UNKNOWN ring at its start (a distance is a constant, or one of
@@ -1930,8 +1817,8 @@ pe_pass:
         if (__ballot(active && kind == SCK_EXPLICIT && val > reach) != 0ull && lane == 0) *reinterpret_cast<lds_vu32*>(&g_smem[pb + PE_CTL + 4u * PEC_DCAND]) = 1u;
       }
       if (T == 0u) { lds_st32(pb + PE_CTL + 4u * PEC_KP, m); lds_st32(pb + PE_CTL + 4u * PEC_BIGNEXT, 0u); lds_st32(pb + PE_CTL + 4u * PEC_DICTK, 0xFFFFFFFFu); lds_st32(pb + PE_CTL + 4u * PEC_WNEXT, 0u); lds_st32(pb + PE_CTL + 4u * PEC_DEPCHG, 0u); lds_st32(pb + PE_CTL + 4u * PEC_DEPLV0, 0u); lds_st32(pb + PE_CTL + 4u * PEC_DEPLV1, 0u); lds_st32(pb + PE_CTL + 4u * PEC_DEPDEEP, 0u); }   // (... and the execute's items are handed out from the first)
-      if (REMOTE && me == 0) { full_arrival(true); GT(3); }
-      PE_BAR();
+      if (REMOTE && me == 0) full_arrival(true);
+      __syncthreads();
       if (REMOTE) {
         if (pe_ctl_ld(pb, PEC_PLAN) == 2u) return;
         P0 = (uint64_t)pe_ctl_ld(pb, PEC_P0_LO) | ((uint64_t)pe_ctl_ld(pb, PEC_P0_HI) << 32);
@@ -1981,7 +1868,7 @@ pe_pass:
           prev = wdelta;
           const uint32_t slot = 52u + 4u * (it & 1u);
           if (lane == 0) lds_st32(rs + slot, (rdlane(dincl, 63) << 1) | (chg ? 1u : 0u));   // (every wave: one without a batch says 0)
-          PE_BAR();
+          __syncthreads();
           const uint32_t wv = lane < GW ? lds_ld32(pb + PE_RS + (lane << 6) + slot) : 0u;
           const bool anychg = __ballot((wv & 1u) != 0u) != 0ull;
           const uint32_t sincl = sc_scan((uint32_t)((int32_t)wv >> 1));
@@ -1992,7 +1879,7 @@ pe_pass:
         // ... and the ring once more: a dictionary word's distance is not pushed
         if (__ballot(isw) != 0ull || true) {   // (uniform over the block: every wave resolves again and meets the others at the barrier)
           ring_resolve(pushes0 && !isw);
-          PE_BAR();
+          __syncthreads();
           d0 = st.d0; d1 = st.d1; d2 = st.d2; d3 = st.d3;
           for (uint32_t j = 0; j < bw && mine; j++) {
             const uint32_t rj = pb + PE_RS + (j << 6);
@@ -2035,7 +1922,7 @@ pe_pass:
       const bool bigc = (copy_x > PE_LANE_COPY && dep == 0u) || ins - uu > PE_LANE_LITS;
       const uint64_t dmk = __ballot(lane < kpb && dep != 0u), bmk = __ballot(lane < kpb && bigc), wmk = PE_DICT ? __ballot(lane < kpb && plainw) : 0ull;
       if (mine && lane == 0) { lds_st32(rs + 48u, (uint32_t)__popcll(dmk) | ((uint32_t)__popcll(bmk) << 16)); if (PE_DICT) lds_st32(rs + 12u, (uint32_t)__popcll(wmk)); }
-      PE_BAR();
+      __syncthreads();
       const uint32_t kp_total = pe_ctl_ld(pb, PEC_KP);
       my_exec = !mine || kp_total <= k0 ? 0u : (kp_total - k0 < K ? kp_total - k0 : K);
       if (mine && my_exec != 0u) {
@@ -2090,7 +1977,7 @@ pe_pass:
       // (every wave's stores of the region before are in memory before anyone reads them as copy sources: here, a whole region's
       // tables later, the wait is over before it starts -- at the region's start it cost the stores' round trip)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      PE_BAR();
+      __syncthreads();
       if (me == 0) {
         // where the stream goes on: the first bit of command kp_total (its head: behind the distance code, if there is one,
         // of the state it starts from)
@@ -2137,11 +2024,6 @@ pe_pass:
           const ScHead h_ = sc_head(lo_, hi_, c.cmd_tree, c.lut_vgpr);
           if (rfl(h_.insert) >= 1024u) pe_ctl_st(pb, PEC_DECLINE, pe_ctl_ld(pb, PEC_DECLINE) | 1u);
         }
-        if (REMOTE && !cont) GANG_STAT(gc, 37, 1);
-        if (REMOTE && !cont && kp_total != m) GANG_STAT(gc, 35, 1);
-#ifdef BROTLI_AMD_PE_DEBUG
-        if (REMOTE && blockIdx.x == 0 && lane == 0) printf("   region %u: %u commands listed, %u executed, goes on at %u, cont %u, P now %llu ncmd %u\n", kseq, m, kp_total, sn.b, cont ? 1u : 0u, (unsigned long long)sn.P, sn.ncmd);
-#endif
         if (REMOTE && kseq + 1u >= GC_MAX_REGIONS) cont = false;   // (the tags of the state's granules count regions in twelve bits)
         pe_ctl_st(pb, PEC_CONT, cont ? 1u : 0u);  // (a word of its own: wave 0 writes PEC_GO for the next region while the others may still be here)
         pe_st_store(pb, sn);
@@ -2156,9 +2038,6 @@ pe_pass:
         }
       }
     }
-    PE_PROF(11);
-    if (REMOTE && me == 0) GANG_STAT(gc, 26, __builtin_amdgcn_s_memtime() - gs_arr);   // .. resolve done (wave 0 past the publish)
-    if (REMOTE && me == 0) GT(4);
     // (a gang) Two waits for other CUs' output: here for the regions up to the one before the region before -- the literals, and the copies that
     // read nothing younger, start at once --, and behind them for the region before, whose last bytes only the copies marked `dep` in the resolve
     // read (with uniform distances a handful a region: they go with the copies that read this region's own output).  The word is another CU's:
@@ -2168,8 +2047,8 @@ pe_pass:
     // -4 .. -10 % on batches of the metric's 4 MiB streams if it were the rule) -- an engine that has waited long for the region before's
     // output waits twice from the next region on, one whose two waits were short goes back to one.  (Gangs of eight only: smaller ones wait for a
     // block that is busy, not for a chain -- measured, two waits cost them 5 .. 8 %.)
-    auto await_output = [&](const uint32_t upto, const uint32_t stat) -> uint32_t {
-      uint32_t spins = 0; (void)spins; (void)stat;
+    auto await_output = [&](const uint32_t upto) -> uint32_t {
+      uint32_t spins = 0; (void)spins;
       const uint64_t t0_ = __builtin_amdgcn_s_memtime();
       for (;;) {
         const uint64_t ew = gang_ld64(gc, GC_EXEC);
@@ -2177,7 +2056,6 @@ pe_pass:
         __builtin_amdgcn_s_sleep(1); PE_SPIN_CHECK(spins);
       }
       const uint32_t waited = (uint32_t)(__builtin_amdgcn_s_memtime() - t0_);
-      GANG_STAT(gc, stat, waited);
       gang_acquire();
       return waited;
     };
@@ -2187,22 +2065,19 @@ pe_pass:
       if (relaxed) {
         // (the resolve marked the copies that read the one or the two regions before: as many executes besides this one may be under way)
         const uint32_t depth = pe_ctl_ld(pb, PEC_DEPTH);
-        if (kseq >= depth + 1u) waited1 = await_output(kseq - depth, 9u);
+        if (kseq >= depth + 1u) waited1 = await_output(kseq - depth);
         if (depth == 1u && waited1 > 6000u && gang_m >= PE_DEPTH2_MIN) pe_ctl_st(pb, PEC_RELAX, 2u);
       }
-      else if (kseq != 0u) { waited1 = await_output(kseq, 8u); if (waited1 > 6000u && gang_m >= 8u) pe_ctl_st(pb, PEC_RELAX, 1u); GANG_STAT(gc, 30, 1); }
+      else if (kseq != 0u) { waited1 = await_output(kseq); if (waited1 > 6000u && gang_m >= 8u) pe_ctl_st(pb, PEC_RELAX, 1u); }
       lds_sync();
       pe_ctl_st(pb, PEC_EXECUTED, kseq);
-      GT(5);
     }
     if (REMOTE) {
       // the region before's output is in memory before this one's copies read it (its engine says so)
       uint32_t spins = 0; (void)spins;
       while (pe_ctl_ld(pb, PEC_EXECUTED) < kseq) { __builtin_amdgcn_s_sleep(2); PE_SPIN_CHECK(spins); }
-      PE_PROF(14);
     }
     // ---- execute ----
-    RG_STAMP(1);   // resolve done
     {
       gu8* const o = out + P0;
       // (a) lane = command: the literals in front of the path, decoded again one after the other; the literals on the path out
@@ -2313,9 +2188,6 @@ pe_pass:
       }
       // (no barrier: what (b) stores lies elsewhere, and a wave that is through with (a) -- most have no batch -- takes items at once;
       // (c) waits for both)
-      PE_PROF(8);
-      RG_STAMP(2);   // (a) done
-      PE_COUNT(28, kp);
       if (!REMOTE) {   // (wave 0 says where the stream goes on behind the resolve's last barrier, while the others execute: as a rule long since)
         while (pe_ctl_ld(pb, PEC_NXOK) != rseq) __builtin_amdgcn_s_sleep(1);
         lds_sync();
@@ -2330,7 +2202,6 @@ pe_pass:
       // side and stored when all three are there (their sources lie far back: a round trip to memory each).
       {
         const uint32_t nbig = pe_ctl_ld(pb, PEC_NBIG);
-        PE_COUNT(12, nbig);
         auto big_item = [&](const uint32_t j, uint32_t& pt, uint32_t& pd, uint32_t& pn) {
           pn = 0; pt = 0; pd = 0;
           if (j >= nbig) return;
@@ -2386,17 +2257,13 @@ pe_pass:
         }
       }
 #endif
-      PE_PROF(9);
-      RG_STAMP(3);   // (b) done (this wave's share)
-      if (REMOTE && me == 0) GT(8);
       // (a gang whose executes wait twice) The second wait -- for the region before's output -- stands in front of the word that says this region's is
       // there, and in front of the copies that read that output (`lagging` ones: their source begins in front of the region) and of those that build on them.
       auto second_wait = [&]() {
         if (REMOTE && me == 0 && kseq != 0u && relaxed) {
-          const uint32_t waited2 = await_output(kseq, 8u);
+          const uint32_t waited2 = await_output(kseq);
           if (waited1 + waited2 < 1500u) pe_ctl_st(pb, PEC_RELAX, pe_ctl_ld(pb, PEC_DEPTH) - 1u);   // (both short: one execute fewer in flight will do)
         }
-        if (REMOTE && me == 0) GT(9);
       };
       // (c) copies that read the region's own output (`dependent` ones; a gang whose executes wait twice: and the `lagging` ones, whose source begins in
       // front of the region -- in the region before's output, which may still be on its way).  Through round 5 those that build on another one went one
@@ -2407,7 +2274,6 @@ pe_pass:
       // of level < r has its own): PE_DEP_ROUNDS rounds at most, what is deeper goes in order behind the rest, as before.  Lagging spreads the same way
       // (bit 7): what neither lags nor builds on a copy that does is done in front of the second wait.
       const uint32_t ndep = pe_ctl_ld(pb, PEC_ANYDEP);
-      PE_COUNT(13, ndep);
       auto dependent_copies = [&]() {
         const bool lagging = REMOTE && relaxed && kseq != 0u;
         const uint32_t DA = pb + PE_POR, DB = DA + 2u * PE_CMDS, DL = DB + 2u * PE_CMDS;   // (the ranks' room: nobody reads a rank behind the details)
@@ -2446,9 +2312,7 @@ pe_pass:
         const uint32_t e_ra = pb + PE_REC + (e_k << 4);
         const uint32_t e_n = lds_ld32(e_ra + 8u), e_d = lds_ld32(e_ra + 12u), e_p = lds_ld32(pb + PE_OFF + (e_k << 2)) + (lds_ld32(e_ra + 4u) & 0xFFFFu);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        PE_BAR();
-        RG_STAMP(4);   // the dependent copies' ranges, everybody's (a) and (b) in memory
-        if (REMOTE && me == 0) GT(10);
+        __syncthreads();
         for (uint32_t round = 0; round < PE_DEP_ROUNDS; round++) {   // (bit r of PEC_DEPCHG: round r changed a level -- written in round r only, read behind its barrier)
           bool chg = false;
           for (uint32_t j = T; j < ndep; j += 64u * GW) {
@@ -2459,7 +2323,7 @@ pe_pass:
             if (nv != cur) { lds_st8(DL + j, nv); chg = true; }
           }
           if (__ballot(chg) != 0ull && lane == 0) pe_atomic_or(pb + PE_CTL + 4u * PEC_DEPCHG, 1u << round);
-          PE_BAR();
+          __syncthreads();
           if (((pe_ctl_ld(pb, PEC_DEPCHG) >> round) & 1u) == 0u) break;
         }
         // what this wave's copies are: level | lagging << 7; those of level PE_DEP_ROUNDS and more are the last wave's, in order (bit 29 of w0: not)
@@ -2471,12 +2335,8 @@ pe_pass:
           for (uint64_t q = sh0; q; q &= q - 1ull) { const uint32_t v = rdlane(e_l, (uint32_t)__builtin_ctzll(q)) & 0x7Fu; m0 = v + 1u > m0 ? v + 1u : m0; }
           for (uint64_t q = sh1; q; q &= q - 1ull) { const uint32_t v = rdlane(e_l, (uint32_t)__builtin_ctzll(q)) & 0x7Fu; m1 = v + 1u > m1 ? v + 1u : m1; }
           if (lane == 0) { if (m0) pe_atomic_max(pb + PE_CTL + 4u * PEC_DEPLV0, m0); if (m1) pe_atomic_max(pb + PE_CTL + 4u * PEC_DEPLV1, m1); if (deep) pe_atomic_max(pb + PE_CTL + 4u * PEC_DEPDEEP, 1u); } }
-        PE_BAR();
+        __syncthreads();
         const uint32_t nlv0 = pe_ctl_ld(pb, PEC_DEPLV0), nlv1 = pe_ctl_ld(pb, PEC_DEPLV1);   // levels (their number) without and with lagging
-#ifdef BROTLI_AMD_GANG_TRACE
-        { for (uint32_t q = 0; q < 4u; q++) { const uint32_t c_ = (uint32_t)__popcll(__ballot(shallow && e_l == (0x80u | q))); if (c_ && lane == 0) pe_atomic_add_uniform(pb + PE_CTL + 4u * (120u + q), c_); }
-          if (T == 0u) pe_ctl_st(pb, 124u, nlv0 | (nlv1 << 8) | ((pe_ctl_ld(pb, PEC_DEPDEEP) != 0u ? 1u : 0u) << 16)); }
-#endif
         const bool any_deep = pe_ctl_ld(pb, PEC_DEPDEEP) != 0u;
         auto one_copy = [&](const uint32_t dpos, const uint32_t n, const uint32_t dist) {
           if (staged) { stage_copy(dpos, n, dist); return; }
@@ -2533,40 +2393,33 @@ pe_pass:
         for (uint32_t lv = 0; lv < nlv0; lv++) {
           level(lv);
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          PE_BAR();
+          __syncthreads();
         }
-        RG_STAMP(5);   // what does not wait for the region before is done
-        if (REMOTE && me == 0) GT(11);
         second_wait();
-        if (nlv1 != 0u || any_deep) PE_BAR();
+        if (nlv1 != 0u || any_deep) __syncthreads();
         for (uint32_t lv = 0; lv < nlv1; lv++) {
           level(lv | 0x80u);
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          PE_BAR();
-          if (REMOTE && me == 0 && lv == 0u) GT(12);
+          __syncthreads();
         }
-        if (REMOTE && me == 0) GT(14);
         if (any_deep && me == GW - 1u) in_order();
       };
       if (ndep != 0u) dependent_copies(); else second_wait();
       if (staged) {
         // the region's output, out of the stage in one piece: sixteen bytes a thread and step
-        PE_BAR();
-        if (REMOTE && me == 0) GT(12);
+        __syncthreads();
         const uint32_t tot = pe_ctl_ld(pb, PEC_OUTTOT);
         write_out(sg, o, tot);
-        if (REMOTE && me == 0) GT(13);
       }
-      PE_PROF(10);
     }
 #if PE_DICT
     if (pe_ctl_ld(pb, PEC_DICTK) != 0xFFFFFFFFu) {
       // the pass ended behind the literals of a command whose copy is a word of the static dictionary (decode.rs:2593-2640, as
       // lean_rec_commands takes them): wave 0 puts it behind them, and the commands behind it get a pass of their own
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      PE_BAR();   // (the pass's output is complete, nobody reads its records any more)
+      __syncthreads();   // (the pass's output is complete, nobody reads its records any more)
       if (me == 0) { pe_dict_word(pb, out, dict, m); pe_ctl_st(pb, PEC_DCAND, 0u); }
-      PE_BAR();
+      __syncthreads();
       if (pe_ctl_ld(pb, PEC_AGAIN) != 0u) {
         ks = pe_ctl_ld(pb, PEC_KS);
         P0 = (uint64_t)pe_ctl_ld(pb, PEC_P0_LO) | ((uint64_t)pe_ctl_ld(pb, PEC_P0_HI) << 32);
@@ -2577,16 +2430,8 @@ pe_pass:
 #endif
     if (REMOTE) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      PE_BAR();
-      if (REMOTE && T == 0u) { const uint64_t t0_ = __builtin_amdgcn_s_memtime(); (void)t0_; GANG_STAT(gc, 27, t0_ - gs_arr); gang_release();
- GANG_STAT(gc, 17, __builtin_amdgcn_s_memtime() - t0_); gang_st64(gc, GC_EXEC, ((uint64_t)epoch << 32) | (uint64_t)(kseq + 1u)); }
-#ifdef BROTLI_AMD_GANG_TRACE
-      if (REMOTE && T == 0u && epoch == (uint32_t)(BROTLI_AMD_GANG_TRACE) && kseq < 64u) { GT(6);   // (the last 8 KiB of the arena's image: a block of sixteen waves has 40 KiB of arena)
-        gt_ts[13] = (gt_ts[6] & ~0xFFFFFFFFull) | pe_ctl_ld(pb, 124u);
-        pe_ctl_st(pb, 120u, 0u); pe_ctl_st(pb, 121u, 0u); pe_ctl_st(pb, 122u, 0u); pe_ctl_st(pb, 123u, 0u);
-        for (uint32_t q = 0; q < 15u; q++) gang_st64(gc, GC_ARENA + (40u << 10) + 128u * kseq + 8u * q, gt_ts[q]);
-        gang_st64(gc, GC_ARENA + (40u << 10) + 128u * kseq + 120u, (uint64_t)pe_ctl_ld(pb, PEC_KP) | ((uint64_t)blockIdx.x << 32) | ((uint64_t)pe_ctl_ld(pb, PEC_ANYDEP) << 16)); }
-#endif
+      __syncthreads();
+      if (REMOTE && T == 0u) { gang_release(); gang_st64(gc, GC_EXEC, ((uint64_t)epoch << 32) | (uint64_t)(kseq + 1u)); }
     }
   };
 #if !PE_CFG_REMOTE
@@ -2597,9 +2442,6 @@ pe_pass:
       const uint32_t avail = in_limit - (lbdw_ << 5);
       const bool go = td_ok && st.b < in_limit && avail >= PE_MIN_INPUT && st.quota >= SC_MIN_QUOTA && (st.bl1 != 0u || st.run_on != 0u);
       pe_ctl_st(pb, PEC_GO, go ? 1u : 0u);
-#ifdef BROTLI_AMD_PE_DEBUG
-      if (blockIdx.x == 0 && lane == 0 && !go) printf("  engine: no go: td_ok %d b %u in_limit %u avail %u quota %u bl1 %u run_on %u\n", (int)td_ok, st.b, in_limit, avail, st.quota, st.bl1, st.run_on);
-#endif
       uint32_t want_bits = st.run_on != 0u ? PE_RUN_RBL : st.rbl;   // (a long literal run's regions take no tables per bit: four times the bits)
       if (st.run_on == 0u && st.s_cmds != 0u && st.s_bits != 0u) {
         // A block count that runs out ends the engine's part (decode.rs:1469-1524: the switch is the checked loop's), and what the region
@@ -2615,32 +2457,13 @@ pe_pass:
       setup_tables(lbdw_, st.b & 31u, avail < want_bits ? avail : want_bits, st.run_on, st.b & 31u);
       setup_walk(st.P);
     }
-    PE_BAR();   // (the region before's stores: waited for in front of the execute, which is the first to read them -- see the resolve's last barrier)
+    __syncthreads();   // (the region before's stores: waited for in front of the execute, which is the first to read them -- see the resolve's last barrier)
     if (pe_ctl_ld(pb, PEC_GO) == 0u) break;
     P0 = (uint64_t)pe_ctl_ld(pb, PEC_P0_LO) | ((uint64_t)pe_ctl_ld(pb, PEC_P0_HI) << 32);
-#ifdef BROTLI_AMD_PROFILE_REGIONS   // (block 0: one line a region -- what it held and what it cost)
-    const uint64_t rg_t0 = __builtin_amdgcn_s_memtime();
-    if (blockIdx.x == 0 && threadIdx.x == 0 && rg_prev_end != 0) printf("   (wave 0 waited %llu ticks for the region before's last wave + set-up)\n", (unsigned long long)(rg_t0 - rg_prev_end));
-#endif
     const uint32_t how = build();
-#ifdef BROTLI_AMD_PROFILE_REGIONS
-    const uint64_t rg_t1 = __builtin_amdgcn_s_memtime();
-    if (how != 0u && blockIdx.x == 0 && threadIdx.x == 0) printf("region (literal run, how %u): %llu ticks: input+table %llu first decode %llu settle %llu ranks %llu emit+write %llu; literals %u bits %u\n", how, (unsigned long long)(rg_t1 - rg_t0),
-        (unsigned long long)(rg_ts[6] - rg_t0), (unsigned long long)(rg_ts[7] - rg_ts[6]), (unsigned long long)(rg_ts[8] - rg_ts[7]), (unsigned long long)(rg_ts[9] - rg_ts[8]), (unsigned long long)(rg_t1 - rg_ts[9]), pe_ctl_ld(pb, PEC_TAKE), c.L);
-    if (how != 0u && blockIdx.x == 0 && threadIdx.x == 0) printf("      rounds (parts @ tick behind the first pass): %u @ %llu, %u @ %llu, %u @ %llu, %u @ %llu\n", rg_rn[0], (unsigned long long)rg_rt[0], rg_rn[1], (unsigned long long)rg_rt[1], rg_rn[2], (unsigned long long)rg_rt[2], rg_rn[3], (unsigned long long)rg_rt[3]);
-#endif
     if (how == 1u) continue;
     if (how == 2u) break;
     consume();
-#ifdef BROTLI_AMD_PROFILE_REGIONS
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-      printf("region: bits %u path %u closure %u listed %u executed %u out %u big %u dep %u staged %u | build %llu consume %llu\n", c.L, c.Rn, wn, pe_ctl_ld(pb, PEC_M), pe_ctl_ld(pb, PEC_KP),
-             pe_ctl_ld(pb, PEC_OUTTOT), pe_ctl_ld(pb, PEC_NBIG), pe_ctl_ld(pb, PEC_ANYDEP), pe_ctl_ld(pb, PEC_STAGED), (unsigned long long)(rg_t1 - rg_t0), (unsigned long long)(__builtin_amdgcn_s_memtime() - rg_t1));
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-      printf("   consume: walk+details %llu resolve %llu exec(a) %llu (b) %llu classify+wait %llu ready %llu rest(wave 0) %llu\n", (unsigned long long)(rg_ts[0] - rg_t1), (unsigned long long)(rg_ts[1] - rg_ts[0]), (unsigned long long)(rg_ts[2] - rg_ts[1]),
-             (unsigned long long)(rg_ts[3] - rg_ts[2]), (unsigned long long)(rg_ts[4] > rg_ts[3] ? rg_ts[4] - rg_ts[3] : 0), (unsigned long long)(rg_ts[5] > rg_ts[4] ? rg_ts[5] - rg_ts[4] : 0), (unsigned long long)(__builtin_amdgcn_s_memtime() - (rg_ts[5] > rg_ts[3] ? rg_ts[5] : rg_ts[3])));
-    rg_prev_end = __builtin_amdgcn_s_memtime(); rg_ts[4] = rg_ts[5] = 0;
-#endif
     if (pe_ctl_ld(pb, PEC_CONT) == 0u) break;
   }
 #else
@@ -2676,17 +2499,15 @@ pe_pass:
     const bool alone = role == 0u && pe_ctl_ld(pb, PEC_PLAN) == 6u;   // (the owner has kept the invocation to itself: see `long_first`)
     if (!alone) for (kseq = role;; kseq += gang_m) {
       if (me == 0) window_by_plan(gang_ld64(gc, GC_PLAN));
-      PE_BAR();
-      PE_PROF(15);   // (the window)
+      __syncthreads();
       uint32_t plan;
       for (;;) {
         const bool built = pe_ctl_ld(pb, PEC_GO) != 0u;
-        if (built) { const uint64_t tb_ = __builtin_amdgcn_s_memtime(); (void)tb_; (void)build(); GT(7); if (me == 0) { GANG_STAT(gc, 4, 1); if (role == 0u) GANG_STAT(gc, 20, __builtin_amdgcn_s_memtime() - tb_); } }
+        if (built) (void)build();
         // -- the stream arrives (or the plan has changed, or the invocation is over) --
         if (me == 0) {
           const uint32_t mygen = pe_ctl_ld(pb, PEC_MYGEN), want = (epoch << 12) | kseq;
           uint64_t v; uint32_t spins = 0; bool arrived, stopped, replanned;
-          const uint64_t t0_ = __builtin_amdgcn_s_memtime(); (void)t0_;
           for (;;) {
             v = gang_ld64(gc, lane == 0u ? GC_ENTRY : lane == 32u ? GC_STOP : GC_PLAN);
             arrived = rdlane((uint32_t)(v >> 32), 0) == want;
@@ -2695,11 +2516,10 @@ pe_pass:
             if (arrived || stopped || replanned) break;
             __builtin_amdgcn_s_sleep(1); PE_SPIN_CHECK(spins);
           }
-          GANG_STAT(gc, role == 0u ? 6 : 7, __builtin_amdgcn_s_memtime() - t0_); gs_arr = __builtin_amdgcn_s_memtime(); GT(0);
 
           plan = 2u;   // 0: the tables are the ones, 1: once more where the stream is, 2: the invocation is over, 3: once more by the new plan, then wait again
           if (stopped) { }
-          else if (replanned) { GANG_STAT(gc, 3, 1); window_by_plan((uint64_t)rdlane((uint32_t)v, 33) | ((uint64_t)rdlane((uint32_t)(v >> 32), 33) << 32)); plan = 3u; }
+          else if (replanned) { window_by_plan((uint64_t)rdlane((uint32_t)v, 33) | ((uint64_t)rdlane((uint32_t)(v >> 32), 33) << 32)); plan = 3u; }
           else {
             // (the bit the stream enters the region at: all the walk and the details ask for; its state comes behind the details -- see consume)
             const uint32_t eb = rdlane((uint32_t)v, 0);
@@ -2709,10 +2529,7 @@ pe_pass:
               const uint32_t w0 = pe_ctl_ld(pb, PEC_LBDW) << 5, wl = pe_ctl_ld(pb, PEC_L), shsc_ = pe_ctl_ld(pb, PEC_MYSHIFT), sh_ = shsc_ & 3u, rbl_ = PE_RBL >> sh_;
               const bool usable = built && eb >= w0 && eb + (PE_PIPE_USEFUL >> sh_) <= w0 + wl;
               plan = usable ? 0u : 1u;
-              GANG_STAT(gc, 1, 1);
               if (!usable) {
-                GANG_STAT(gc, 2, 1);
-                if (!built) GANG_STAT(gc, 10, 1); else if (eb < w0) GANG_STAT(gc, 11, 1); else GANG_STAT(gc, 12, 1);
                 setup_tables(eb >> 5, 0u, avail < rbl_ ? avail : rbl_, 0u, 0u);
                 seed_entries(0u, 32u);   // (the window starts at the entry's dword)
                 // (short of the window: the regions from here on a shorter stride -- what the region before did advance, in eighths)
@@ -2743,13 +2560,12 @@ pe_pass:
           }
           pe_ctl_st(pb, PEC_PLAN, plan);
         }
-        PE_BAR();
+        __syncthreads();
         plan = pe_ctl_ld(pb, PEC_PLAN);
         if (plan != 3u) break;
       }
-      PE_PROF(16);   // (waiting for the stream)
       if (plan == 2u) break;
-      if (plan == 4u) { if (me == 0) full_arrival(false); PE_BAR(); break; }
+      if (plan == 4u) { if (me == 0) full_arrival(false); __syncthreads(); break; }
       if (plan != 7u) {
       if (plan == 1u) (void)build();
       // a region whose closure has filled its room: half the bits, for this one and the ones behind it -- a new plan; twice, if need be
@@ -2766,11 +2582,10 @@ pe_pass:
             gang_drain();
             pe_ctl_st(pb, PEC_MYGEN, g_); pe_ctl_st(pb, PEC_MYSHIFT, shsc_ + 1u);
             again = 1u;
-            GANG_STAT(gc, 12, 1);
           }
           pe_ctl_st(pb, PEC_PLAN, again != 0u ? 5u : 0u);
         }
-        PE_BAR();
+        __syncthreads();
         if (pe_ctl_ld(pb, PEC_PLAN) != 5u) break;
         (void)build();
       }
@@ -2779,12 +2594,10 @@ pe_pass:
         pe_ctl_st(pb, PEC_LE, eb - (pe_ctl_ld(pb, PEC_LBDW) << 5));
         setup_walk(0ull);   // (where the region's output starts: with the stream's state, behind the details)
       }
-      PE_BAR();
+      __syncthreads();
       }
       le = pe_ctl_ld(pb, PEC_LE);
-      { const uint64_t tc_ = __builtin_amdgcn_s_memtime(); (void)tc_;
-        consume();
-        if (me == 0 && role == 0u) GANG_STAT(gc, 19, __builtin_amdgcn_s_memtime() - tc_); }
+      consume();
       if (pe_ctl_ld(pb, PEC_CONT) == 0u) break;
     }
   }
@@ -2805,14 +2618,10 @@ pe_pass:
     if (hc_ld(HC_SEQ) == seq_ + 1u && hc_ld(HC_KIND) == (REMOTE ? (uint32_t)HK_PATHR : PE_DICT ? (uint32_t)HK_PATHG : (uint32_t)HK_PATH)) goto pe_again;   // (this form of the engine again: the lean one and the general one are two functions)
     return seq_;
   }
-#ifdef BROTLI_AMD_PROFILE_SCAN
-  if (blockIdx.x == 0 && lane == 0) { for (int k = 0; k < 32; k++) if (k != 30) g_path_prof[k] += pp_acc[k]; g_path_prof[32] += pe_ctl_ld(pb, PEC_STATE + 6); g_path_prof[33] += 1; }
-#endif
   if (REMOTE && pe_ctl_ld(pb, PEC_PLAN) != 6u) {   // (6: the owner kept the invocation to itself)
     // (the owner of a gang) the invocation's end as the gang left it: the regions resolved in all, the stream's state behind the last of them
     // -- whoever's it was --, and the last one's output in memory
     uint32_t spins = 0; uint64_t sw_, v; (void)spins;
-    const uint64_t t0_ = __builtin_amdgcn_s_memtime(); (void)t0_;
     for (;;) { sw_ = gang_ld64(gc, GC_STOP); if ((uint32_t)(sw_ >> 32) == epoch) break; __builtin_amdgcn_s_sleep(1); PE_SPIN_CHECK(spins); }
     const uint32_t Kr = (uint32_t)sw_, want = (epoch << 12) | Kr;
     for (;;) {
@@ -2827,14 +2636,11 @@ pe_pass:
       for (;;) { const uint64_t ew = gang_ld64(gc, GC_EXEC); if ((uint32_t)(ew >> 32) == epoch && (uint32_t)ew >= Kr) break; __builtin_amdgcn_s_sleep(1); PE_SPIN_CHECK(spins); }
       gang_acquire();
     }
-    GANG_STAT(gc, 31, Kr == 0u ? 1u : 0u);
-    GANG_STAT(gc, 13, __builtin_amdgcn_s_memtime() - t0_); GANG_STAT(gc, 16, __builtin_amdgcn_s_memtime() - gs_t0); GANG_STAT(gc, 14, Kr); GANG_STAT(gc, 15, rdlane((uint32_t)v, 25) >> 1 & 1u);
     lds_sync();
   }
   // ---- hand the stream back in front of the next command (LDS_LEAN, as the scan engine does) ----
   const PeStream st_ = pe_st_load(pb);
   PeStream st = st_;
-  if (REMOTE) { GANG_STAT(gc, 21, st.ncmd < 64u ? 1u : 0u); GANG_STAT(gc, 22, st.ncmd); GANG_STAT(gc, 23, st.ncmd == 0u ? 1u : 0u); }
   if (st.run_on != 0u) {
     // inside a command whose literal run had regions of its own: the checked loop finishes its literals (what the limits kept
     // back, or none), its distance and its copy; the reference takes a command's whole insert length off when it reads the
@@ -2862,15 +2668,8 @@ pe_pass:
   return st.ncmd;
 }
 }  // namespace PE_CFG_NS
-#undef PE_PROF
-#undef PE_COUNT
-#undef PE_LANECOUNT
 #undef PE_TRY_RUN
 #undef PE_TRY_RUN_FROM
-#undef PE_BAR
 #undef PE_HOPS_REC
 #undef PE_DICT
 #undef PE_SPIN_CHECK
-#undef RG_STAMP
-#undef GT
-#undef GTC

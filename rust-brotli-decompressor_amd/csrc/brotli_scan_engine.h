@@ -87,14 +87,6 @@ enum { SCK_NONE = 0, SCK_EXPLICIT = 1, SCK_SHORT = 2, SCK_IMPLICIT = 3 };
 __device__ __forceinline__ uint32_t sc_ctl_ld(uint32_t sb, uint32_t k) { return rfl(*reinterpret_cast<lds_vu32*>(&g_smem[sb + SC_CTL + 4u * k])); }
 __device__ __forceinline__ void sc_ctl_st(uint32_t sb, uint32_t k, uint32_t v) { if (lane_id() == 0) *reinterpret_cast<lds_vu32*>(&g_smem[sb + SC_CTL + 4u * k]) = v; }
 
-#ifdef BROTLI_AMD_PROFILE_SCAN
-__device__ unsigned long long g_scan_prof[28];  // ([24]: wave 1's ticks in REC, [25] / [26]: the last wave's dependent copies)
-#define SCAN_PROF(k) do { if (me == 0) { uint64_t _t = __builtin_amdgcn_s_memtime(); if (blockIdx.x == 0) sp_acc[k] += _t - sp_t; sp_t = _t; } } while (0)
-#define SCAN_COUNT(k, v) do { if (me == 0 && blockIdx.x == 0) sp_acc[k] += (v); } while (0)
-#else
-#define SCAN_PROF(k) do { } while (0)
-#define SCAN_COUNT(k, v) do { } while (0)
-#endif
 
 // Between the stages of two chains of dependent LDS reads written side by side: the machine scheduler otherwise puts each
 // chain back together (one chain's reads, waits and all, then the other's), and the round trips no longer overlap.
@@ -205,9 +197,6 @@ __device__ __noinline__ uint32_t scan_engine(const uint32_t me_) {
   const uint32_t me = rfl(me_);
   const uint32_t sb = hc_ld(HC_SCAN_BASE);
   __syncthreads();  // the parameters are in place
-#ifdef BROTLI_AMD_PROFILE_SCAN
-  uint64_t sp_acc[24] = {}; uint64_t sp_t = __builtin_amdgcn_s_memtime();
-#endif
   const uint32_t lit_tree = sc_ctl_ld(sb, SCC_LIT_TREE), cmd_tree = sc_ctl_ld(sb, SCC_CMD_TREE);
   const uint32_t dt0 = sc_ctl_ld(sb, SCC_DT0), dt1 = sc_ctl_ld(sb, SCC_DT0 + 1), dt2 = sc_ctl_ld(sb, SCC_DT0 + 2), dt3 = sc_ctl_ld(sb, SCC_DT0 + 3);
   const uint32_t postfix_bits = sc_ctl_ld(sb, SCC_POSTFIX), num_direct = sc_ctl_ld(sb, SCC_NUM_DIRECT);
@@ -233,8 +222,6 @@ __device__ __noinline__ uint32_t scan_engine(const uint32_t me_) {
   // a literal run being walked by hand (commands REC does not hold): literals still to skip, then the distance and the copy
   bool in_run = false; uint32_t run_p = 0, run_rem = 0, run_copy = 0, run_implicit = 0, run_dctx = 0;
   uint32_t exit_form = SCX_BEGIN, exit_copy = 0, exit_dctx = 0; int32_t exit_dcode = 0;
-  uint32_t exit_why = 0;  // (profiling) 0 input ends, 1 block counts / output limits, 2 distance, 3 a command to walk by hand that does not fit, 4 long literal run
-  (void)exit_why;
 
   // frontiers (bits from the origin): below them the ring holds valid entries
   uint32_t f_1 = 0, f_4 = 0, f_16 = 0, f_32 = 0, f_rec = 0, f_d = 0;
@@ -257,7 +244,6 @@ __device__ __noinline__ uint32_t scan_engine(const uint32_t me_) {
   for (;; par ^= 1u) {
     const uint32_t gx = SCC_GRP + 16u * (par ^ 1u), xl_exec = sb + SC_XL + (par ^ 1u) * (SC_GROUP * 1024u);  // the group to execute
     const uint32_t gp = SCC_GRP + 16u * par, xl_post = sb + SC_XL + par * (SC_GROUP * 1024u);                // the group to post
-    SCAN_COUNT(14, mode == M_STEP ? 1u : 0u); SCAN_COUNT(15, mode == M_SYNC ? 1u : 0u); SCAN_COUNT(11, mode == M_FINAL ? 1u : 0u);
     // ================= part 1 (all waves): the posted group =================
     {
       const uint32_t ng = sc_ctl_ld(sb, gx + SCG_NG);
@@ -319,7 +305,6 @@ __device__ __noinline__ uint32_t scan_engine(const uint32_t me_) {
 #undef SC_EXEC
       }
     }
-    SCAN_PROF(6);
     if (f_d < f_rec) {
       // D2 / D4 of the region whose REC the tick before completed: bits from every bit to the second and the fourth command
       // after the one that would start there (0 where one of them is not in REC or lies beyond the region)
@@ -348,7 +333,6 @@ __device__ __noinline__ uint32_t scan_engine(const uint32_t me_) {
       }
       f_d = f_rec;
     }
-    SCAN_PROF(7);
     uint32_t walk_limit = f_rec;  // REC, D2 and D4 are complete below this (once the barrier in front of the walk is passed)
     uint32_t pre_v = 0, pre_i = 0; bool pre_ok = false;
     if (mode == M_STEP) {
@@ -381,10 +365,8 @@ __device__ __noinline__ uint32_t scan_engine(const uint32_t me_) {
         _Pragma("unroll") for (int u = 0; u < 2; u++) { lds_st8(sb + SC_S + (p[u] & SC_M), e[u] >> 4); lds_st8(sb + SC_J1 + (p[u] & SC_M), L[u]); }
       }
       f_1 = t_1;
-      SCAN_PROF(1);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the group's stores: in memory before anyone reads them as copy sources)
       __syncthreads();
-      SCAN_PROF(9);
       // binary lifting, two levels per pass: TO2[p] = position after two FROM-hops, TO4[p] after four
 #define SC_LEVELS(FROM, TO2, TO4, f_to, t_to) \
       for (uint32_t w0 = ((f_to) >> 6) + me; w0 < ((t_to) >> 6); w0 += 2u * SC_WAVES) { \
@@ -401,9 +383,7 @@ __device__ __noinline__ uint32_t scan_engine(const uint32_t me_) {
         _Pragma("unroll") for (int u = 0; u < 2; u++) { lds_st8(sb + TO2 + (p[u] & SC_M), a2[u]); lds_st8(sb + TO4 + (p[u] & SC_M), a4[u]); } \
       } \
       f_to = (t_to); \
-      SCAN_PROF(2); \
-      __syncthreads(); \
-      SCAN_PROF(10);
+      __syncthreads();
       SC_LEVELS(SC_J1, SC_J2, SC_J4, f_4, t_4)
       SC_LEVELS(SC_J4, SC_J8, SC_J16, f_16, t_16)
 #undef SC_LEVELS
@@ -417,13 +397,8 @@ __device__ __noinline__ uint32_t scan_engine(const uint32_t me_) {
         _Pragma("unroll") for (int u = 0; u < 2; u++) lds_st16(sb + SC_J32 + ((p[u] & SC_M) << 1), a[u] + c[u]);
       }
       f_32 = t_32;
-      SCAN_PROF(2);
       __syncthreads();
-      SCAN_PROF(10);
       if (me != 0) {
-#ifdef BROTLI_AMD_PROFILE_SCAN
-        const uint64_t rec_t0 = __builtin_amdgcn_s_memtime();
-#endif
         // REC: the command that would start at every bit of [f_rec, e_rec) -- fifteen waves, two windows per wave and pass,
         // stage by stage (wave 0 is walking the step before meanwhile)
         for (uint32_t w0 = (f_rec >> 6) + (me - 1u); w0 < (e_rec >> 6); w0 += 2u * (SC_WAVES - 1u)) {
@@ -518,9 +493,6 @@ __device__ __noinline__ uint32_t scan_engine(const uint32_t me_) {
             lds_st32(ra + 4u, good ? rhi : 0u);
           }
         }
-#ifdef BROTLI_AMD_PROFILE_SCAN
-        if (me == 1u && blockIdx.x == 0 && lane == 0) g_scan_prof[24] += __builtin_amdgcn_s_memtime() - rec_t0;
-#endif
       }
       // (f_rec moves when the step's D2 / D4 are done, below)
     }
@@ -529,9 +501,6 @@ __device__ __noinline__ uint32_t scan_engine(const uint32_t me_) {
     // (in STEP ticks the barrier behind S / J1 has put everyone's stores of part 1 in memory; in SYNC and FINAL ticks this one does)
     if (mode != M_STEP) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); }
     if (me == SC_WAVES - 1u && sc_ctl_ld(sb, gx + SCG_ANYDEP) != 0u) {
-#ifdef BROTLI_AMD_PROFILE_SCAN
-      const uint64_t dep_t0 = __builtin_amdgcn_s_memtime(); uint32_t dep_n = 0;
-#endif
       // copies of the executed group that read the group's own output: one after the other (a wave's stores are visible
       // to its later loads)
       const uint32_t ng = sc_ctl_ld(sb, gx + SCG_NG);
@@ -544,9 +513,6 @@ __device__ __noinline__ uint32_t scan_engine(const uint32_t me_) {
         while (dm) {
           const uint32_t k = (uint32_t)__builtin_ctzll(dm);
           dm &= dm - 1ull;
-#ifdef BROTLI_AMD_PROFILE_SCAN
-          dep_n++;
-#endif
           const uint32_t n = rdlane(xn, k), dist = rdlane(xd, k), dpos = rdlane(xo, k) + ((rdlane(x0, k) >> 16) & 63u);
           gu8* const dst = o + dpos; gu8* const src = dst - dist;
           if (dist < n) {
@@ -565,13 +531,8 @@ __device__ __noinline__ uint32_t scan_engine(const uint32_t me_) {
           }
         }
       }
-#ifdef BROTLI_AMD_PROFILE_SCAN
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (blockIdx.x == 0 && lane == 0) { g_scan_prof[25] += __builtin_amdgcn_s_memtime() - dep_t0; g_scan_prof[26] += dep_n; }
-#endif
     }
     if (me == 0) {
-      SCAN_PROF(8);
       uint32_t ng = 0, flags = 0, any_dep = 0;
       const uint64_t p_group = P;  // copies that read at or behind this are the ones wave 0 does itself, next tick
       bool stop = mode == M_FINAL, step_done = mode == M_FINAL;
@@ -638,12 +599,11 @@ __device__ __noinline__ uint32_t scan_engine(const uint32_t me_) {
           sc_bits64(sb, b, lo, hi);
           const ScHead h = sc_head(lo, hi, cmd_tree, lut_vgpr);
           const uint32_t hins = rfl(h.insert), hcopy = rfl(h.copy), hbits = rfl(h.bits), himp = rfl(h.implicit), hctx = rfl(h.dctx);
-          if (hbits == 0u || hins >= SC_LONG_EXIT || bl1 == 0u || hins > bl0 || (uint64_t)hins + hcopy >= (uint64_t)quota || (!himp && bl2 == 0u)) { stop = true; exit_why = hins >= SC_LONG_EXIT ? 4u : 3u; break; }
+          if (hbits == 0u || hins >= SC_LONG_EXIT || bl1 == 0u || hins > bl0 || (uint64_t)hins + hcopy >= (uint64_t)quota || (!himp && bl2 == 0u)) { stop = true; break; }
           in_run = true; run_p = b + hbits; run_rem = hins; run_copy = hcopy; run_implicit = himp; run_dctx = hctx;
         }
 #undef SC_APPEND
 #undef SC_ANCHOR
-        SCAN_PROF(4);
         // ---- the lanes behind an anchor find their command: one or two hops from the anchor's position, then its REC ----
         {
           const uint64_t am = anchors & (~0ull >> (63u - lane));       // anchors at or below this lane
@@ -716,7 +676,6 @@ __device__ __noinline__ uint32_t scan_engine(const uint32_t me_) {
         uint32_t extra_cmd = 0, extra_dst = 0;
         if (kp < K) {
           stop = true;
-          exit_why = rdlane((lit_incl <= bl0 && cmd_incl <= bl1 && dst_incl <= bl2 && s2 < quota) ? 2u : 1u, kp);
           if (kp == man_lane) {
             // the copy of a command walked by hand: its literals are out, its distance is read -- the checked loop
             // goes on behind the distance (decode.rs:2583, postReadDistance)
@@ -760,8 +719,6 @@ __device__ __noinline__ uint32_t scan_engine(const uint32_t me_) {
         }
         // state after the batch
         P += out_tot; bl0 -= lit_tot; bl1 -= cmd_tot; bl2 -= dst_tot; quota -= out_tot; mlen -= (int32_t)out_tot; ncmd += cmd_tot;
-        SCAN_PROF(5);
-        SCAN_COUNT(12, kp); SCAN_COUNT(13, 1);
       }
       if (stop) flags |= SCF_LEAVE;
       else if (!step_done) flags |= SCF_BEHIND;  // the group is full: the walk goes on in a tick of its own
@@ -776,7 +733,6 @@ __device__ __noinline__ uint32_t scan_engine(const uint32_t me_) {
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();  // ---- REC of the step is complete; the group is posted ----
-    SCAN_PROF(3);
     if (mode == M_STEP) f_rec += SC_N;
     // ---- what comes next (every wave decides the same from the posted flags) ----
     if (mode == M_FINAL) break;
@@ -789,9 +745,6 @@ __device__ __noinline__ uint32_t scan_engine(const uint32_t me_) {
   }
   __syncthreads();  // every store of the engine is in memory before the decoding wave goes on alone
   if (me != 0) return 0;
-#ifdef BROTLI_AMD_PROFILE_SCAN
-  if (blockIdx.x == 0 && lane == 0) { for (int k = 0; k < 16; k++) g_scan_prof[k] += sp_acc[k]; g_scan_prof[16] += ncmd; g_scan_prof[17] += 1; g_scan_prof[18 + (exit_why < 5u ? exit_why : 0u)] += 1; if (ncmd < 64u) g_scan_prof[23] += 1; }
-#endif
   // ---- hand the stream back (LDS_LEAN, as lean_commands does) ----
   uint32_t pos = b, lits_left = 0, insert_len = 0, copy_len = exit_copy; int32_t dcode = exit_dcode; uint32_t dctx = exit_dctx;
   if (in_run) {  // inside a command walked by hand: the checked loop finishes its literals, distance and copy

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Builds the library with extra compiler flags into tools/scratch/lib_<name>.so (git-ignored; travels to the GPU box),
-# e.g.  tools/build_variant.sh scanprof -DBROTLI_AMD_PROFILE_SCAN ; then BROTLI_AMD_LIB=tools/scratch/lib_scanprof.so python bench.py ...
+# e.g.  tools/build_variant.sh jump4 -DBROTLI_AMD_PE_JUMP_LOG=4 ; then BROTLI_AMD_LIB=tools/scratch/lib_jump4.so python bench.py ...
 set -eu
 REPO=$(cd "$(dirname "$0")/.." && pwd)
 PKG=$REPO/rust-brotli-decompressor_amd

@@ -11,9 +11,4 @@ done
   echo "# every run checks every output by SHA-256 before and after its timed steps"
   cat gpurun_out/gang_$TAG/gang_ab.txt
 } > profiles/${TAG}_gang_ab.txt
-{
-  echo "# tools/gang_run.sh $TAG: a -DBROTLI_AMD_GANG_STATS build (tools/build_variant.sh gangstats -DBROTLI_AMD_GANG_STATS), BROTLI_AMD_GANG_STATS=1: the first stream's gang,"
-  echo "# counters summed over its blocks; ticks are s_memtime's (the shader clock)"
-  cut -c1-4000 gpurun_out/gang_$TAG/gang_stats.txt
-} > profiles/${TAG}_gang_stats.txt
 ls -la profiles | grep -E "gang|1x1024|1x64|32x4"

@@ -21,18 +21,6 @@ from POS on the way out, whatever happened."""
 import os
 import sys
 
-PROFILE_WAIT = "--profile-wait" in sys.argv   # s_memtime around every wait for the memory pipe, summed into %[wacc] (a 64-bit "+s" operand; -DBROTLI_AMD_PROFILE_RUN_WAIT)
-VMWAIT = """
-s_memtime s[76:77]
-s_waitcnt lgkmcnt(0)
-s_waitcnt vmcnt(0)
-s_memtime s[74:75]
-s_waitcnt lgkmcnt(0)
-s_sub_u32 s74, s74, s76
-s_subb_u32 s75, s75, s77
-s_add_u32 s78, s78, s74
-s_addc_u32 s79, s79, s75""" if PROFILE_WAIT else "s_waitcnt vmcnt(0)"
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _label = [200]
 
@@ -234,7 +222,7 @@ def request_and_copy(A, p_expr_regs):
 s_sub_u32 s96, %[P], %[pn]
 s_add_u32 s96, %[outlo], s96
 s_addc_u32 s97, %[outhi], 0
-""" + VMWAIT
+s_waitcnt vmcnt(0)"""
         if merged:
             t += """
 s_bfm_b64 vcc, %[pn], 0
@@ -340,8 +328,6 @@ s_branch {done}""")
 def build():
     A = Asm()
     # ---------------- entry ----------------
-    if PROFILE_WAIT:
-        A.m("s_mov_b64 s[78:79], %[wacc]")
     A.m("""
 s_bitcmp0_b32 %[ok], 0
 s_cbranch_scc1 99f
@@ -477,7 +463,7 @@ s_cmp_lt_u32 %[pn], 2
 s_cbranch_scc1 90f
 s_sub_u32 s96, %[pn], 1
 s_sub_u32 s97, %[pn], 2
-{VMWAIT}
+s_waitcnt vmcnt(0)
 v_readlane_b32 %[p1], v124, s96
 v_readlane_b32 %[p2], v124, s97
 {have_ctx}:
@@ -665,7 +651,7 @@ s_cselect_b32 s96, 1, 0
 s_sub_u32 %[ndw], %[ndw], s96
 s_mov_b64 %[buf], s[98:99]
 99:
-s_waitcnt lgkmcnt(0)""" + ("\ns_mov_b64 %[wacc], s[78:79]" if PROFILE_WAIT else "")
+s_waitcnt lgkmcnt(0)"""
     lines = A.main + A.ool + [(t.strip(), None) for t in tail.strip().split("\n")]
     return lines
 
@@ -679,7 +665,7 @@ def main():
         c = ("  /* " + comment + " */") if comment else ""
         out.append('  "%s%s"%s \\' % (text, sep, c))
     out[-1] = out[-1][:-2]
-    path = os.path.join(ROOT, "rust-brotli-decompressor_amd", "csrc", "brotli_rec_run_asm_wait.h" if PROFILE_WAIT else "brotli_rec_run_asm.h")
+    path = os.path.join(ROOT, "rust-brotli-decompressor_amd", "csrc", "brotli_rec_run_asm.h")
     for a in sys.argv[1:]:
         if a.startswith("--out="):   # (tests: the committed header is what this script writes)
             path = a[len("--out="):]
