@@ -31,7 +31,7 @@
 extern "C" hipError_t brotli_amd_launch_decode(const BrotliAmdStreamDesc* descs, BrotliAmdStreamStatus* status, uint32_t n_streams,
                                                uint32_t* queue, uint8_t* scratch, uint64_t scratch_per_block, uint32_t grid,
                                                uint32_t lds_arena_bytes, const uint8_t* dict, hipStream_t stream, int waves_per_block);
-// (the same kernel with the gang's form of the path engine in it: the launches that give every stream a gang of blocks -- csrc/brotli_kernels.hip, BROTLI_AMD_GANG_KERNEL)
+// (the same kernel with the gang's form of the path engine in it: the launches that give every stream a gang of blocks -- csrc/brotli_kernels.hip, brotli_amd_decode_kernel<true>)
 extern "C" hipError_t brotli_amd_launch_decode_gang(const BrotliAmdStreamDesc* descs, BrotliAmdStreamStatus* status, uint32_t n_streams,
                                                     uint32_t* queue, uint8_t* scratch, uint64_t scratch_per_block, uint32_t grid,
                                                     uint32_t lds_arena_bytes, const uint8_t* dict, hipStream_t stream, int waves_per_block);
@@ -382,7 +382,7 @@ int submit(BrotliAmdBatch* b, uint32_t n, hipStream_t stream) {  // h_descs[0..n
   if (b->cur_arena < b->max_arena)
     for (uint32_t i = 0; i < n; i++) if (!(b->h_descs[i].flags & BROTLI_AMD_BATCH_SPILL_IN_PLACE)) b->h_descs[i].flags |= BROTLI_AMD_FLAG_NO_SPILL;
   // (a gang's helper blocks have no scratch of their own -- a slot per stream --, but a launch whose kernel decides against gangs after all
-  // (fewer waves than sixteen: BROTLI_AMD_LAUNCH experiments) indexes the scratch by block: there is a slot for every block as well)
+  // (fewer waves than sixteen: experiments) indexes the scratch by block: there is a slot for every block as well)
   if (!ensure_scratch(b, std::max(n, b->grid))) return -1;
   // more streams than blocks: the blocks take them longest first (compressed size as the measure), so that no block starts
   // a long stream when the others are done

@@ -1324,9 +1324,7 @@ __device__ __noinline__ void spec_chunk(uint32_t w, uint32_t dw0, uint32_t sh, u
 __device__ __noinline__ uint32_t scan_engine(const uint32_t me_);
 namespace pe16 { __device__ __noinline__ uint32_t path_engine(const uint32_t me_); }   // one engine of sixteen waves, the lean form: no words of the static dictionary
 namespace pe16g { __device__ __noinline__ uint32_t path_engine(const uint32_t me_); }  // ... the general form
-#ifdef BROTLI_AMD_GANG_KERNEL
 namespace pe16r { __device__ __noinline__ uint32_t path_engine(const uint32_t me_); }  // one engine of sixteen a block, the blocks of a gang taking the regions in turns
-#endif
 // what the decoding takes (A/B tests, BROTLI_AMD_ENGINE: see brotli_amd_launch_decode); 0 = everything where it applies
 __device__ uint32_t g_engine_mode = 0;
 
@@ -1359,6 +1357,7 @@ enum : uint32_t { XR_VALID = 1u << 23, XR_LITERALS = 1u << 24, XR_IMPLICIT = 1u 
        XR_NOT_RUN = 1u << 31 /* not a record the hand-written run takes: not valid, or a copy of more than 63 bytes (its tests are one sign test) */ };
 __device__ __noinline__ void rec_wave();
 
+template <bool GANG>   // (true: the gang launches' kernel, see brotli_amd_decode_kernel)
 __device__ __noinline__ void helper_wave(const uint32_t me /* 1 .. waves - 1 */, gu8* scratch_sym) {
   const uint32_t lane = lane_id();
   const uint32_t slot = hc_ld(HC_BASE) + me * HL_SLOT;
@@ -1379,9 +1378,7 @@ __device__ __noinline__ void helper_wave(const uint32_t me /* 1 .. waves - 1 */,
     if (kind == HK_SCAN) { scan_engine(me); continue; }  // every wave of the block runs the command engine
     if (kind == HK_PATH) { seq = rfl(pe16::path_engine(me)); continue; }   // (back with the last request it answered: see there)
     if (kind == HK_PATHG) { seq = rfl(pe16g::path_engine(me)); continue; }
-#ifdef BROTLI_AMD_GANG_KERNEL
-    if (kind == HK_PATHR) { seq = rfl(pe16r::path_engine(me)); continue; }
-#endif
+    if constexpr (GANG) { if (kind == HK_PATHR) { seq = rfl(pe16r::path_engine(me)); continue; } }
     if (kind == HK_RECORDS) {  // a metablock with command records: wave 2 parses them; the others go back to sleep
       if (rfl(me) == 2u && hc_ld(HC_EXT_BASE) != 0u) rec_wave();
       continue;
@@ -1840,7 +1837,6 @@ __device__ __noinline__ void spec_rounds(uint32_t tree_addr) {
 #include "brotli_path_engine.h"
 #undef PE_CFG_NS
 #undef PE_CFG_DICT
-#ifdef BROTLI_AMD_GANG_KERNEL
 #undef PE_CFG_REMOTE
 #define PE_CFG_NS pe16r
 #define PE_CFG_DICT 0
@@ -1848,7 +1844,6 @@ __device__ __noinline__ void spec_rounds(uint32_t tree_addr) {
 #include "brotli_path_engine.h"
 #undef PE_CFG_NS
 #undef PE_CFG_DICT
-#endif
 #undef PE_CFG_REMOTE
 using pe16::PE_MIN_INPUT;
 
@@ -2560,7 +2555,6 @@ struct HotArgs {
   uint64_t resume_out;     // global address of the status' BrotliAmdResume: command boundaries close to the end of the input are noted there
 };
 
-#ifdef BROTLI_AMD_GANG_KERNEL
 // What the gang made of an invocation: it sits out one invocation where it took nothing because it met a literal run that wants regions of its own first
 // thing or because its regions filled their closure's room, twice as many every time that happens again before it has taken anything, up to 64
 __device__ __noinline__ void gang_took(HotArgs* args, const uint32_t took, const uint32_t form_raw) {
@@ -2574,7 +2568,6 @@ __device__ __noinline__ void gang_took(HotArgs* args, const uint32_t took, const
   }
   args->general_engine = (counts & 0xFFu) | (pen << 8) | (hold << 16);
 }
-#endif
 
 // src/decode.rs:2330-2744 with a flat output buffer.
 //  * literals are collected one per lane (v_writelane) and stored 64 at a time;
@@ -2585,7 +2578,7 @@ __device__ __noinline__ void gang_took(HotArgs* args, const uint32_t took, const
 //    only after a long copy.
 // (CACHED: the LDS part of the arena as a cache of the trees in use, see run_commands -- an instantiation of its own, so that the
 // loop for tables that fit LDS stays the code it was: with the cache as a run-time switch the metric lost 1.3 %)
-template <bool LDS_ONLY, bool CTX_NEVER, bool CACHED = false>
+template <bool LDS_ONLY, bool CTX_NEVER, bool CACHED = false, bool GANG = false>
 __device__ __noinline__ int process_commands(HotArgs* args) {
   BitReader br = args->br; br.uniformize();
   Arena a_ = args->ar; a_.uniformize();
@@ -2742,7 +2735,7 @@ __device__ __noinline__ int process_commands(HotArgs* args) {
   const bool large_window = rfl(args->large_window) != 0u;   // (the path engine takes such streams since round 4, the scan engine does not)
   uint32_t scan_fails = 0;
   const uint32_t engine_hints = rfl(args->general_engine);   // (bit 0: the general form; bits 8 .. 15, 16 .. 23: the gang's penalty and the invocations it still sits out, see remote_off)
-  bool prefer_one_engine = false; (void)prefer_one_engine;   // the next invocation of the path engine: its one-block form (see `declined` below; gangs only)
+  bool prefer_one_engine = false;   // the next invocation of the path engine: its one-block form (see `declined` below; gangs only)
   // ... the one-block form though the stream has a gang of blocks: for the next invocations where the gang met a literal run that wants regions
   // of its own first thing (it takes nothing then, and a region's tables of every block are lost: 8.1 against 5.8 ms on 4 MiB of high-entropy
   // literals, all runs) -- one invocation the first time, twice as many every time it happens again before the gang has taken anything, up to 64;
@@ -2827,26 +2820,20 @@ __device__ __noinline__ int process_commands(HotArgs* args) {
         const bool use_general = use_path && prefer_general;
         // (the stream's owner in a gang of blocks: the gang's form of the engine -- not for a literal run that wants regions of its own, nor for
         // words of the static dictionary: those are the one-block forms')
-#ifndef BROTLI_AMD_GANG_KERNEL   // (the kernel of the launches without gangs: see the end of this file)
-        const bool use_remote = false;
-#else
         // (the counts looked at here, whether the helpers have all started by the engine itself the first time: a call in this place costs this
         // function three hundred bytes of frame, and the spills around it every invocation)
         bool use_remote = false;
-        if (use_path && !use_general && hc_ld(HC_GANG_M) > 1u) {
-          const uint32_t counts = rfl(args->general_engine);
-          if (((counts >> 16) & 0xFFu) != 0u) args->general_engine = counts - (1u << 16);
-          else if (!prefer_one_engine) use_remote = true;
+        if constexpr (GANG) {
+          if (use_path && !use_general && hc_ld(HC_GANG_M) > 1u) {
+            const uint32_t counts = rfl(args->general_engine);
+            if (((counts >> 16) & 0xFFu) != 0u) args->general_engine = counts - (1u << 16);
+            else if (!prefer_one_engine) use_remote = true;
+          }
         }
-#endif
         hc_st(HC_KIND, use_remote ? (uint32_t)HK_PATHR : use_general ? (uint32_t)HK_PATHG : use_path ? (uint32_t)HK_PATH : (uint32_t)HK_SCAN);
         lds_release();
         hc_st(HC_SEQ, hc_ld(HC_SEQ) + 1u);  // the other waves of the block join (helper_wave)
-#ifndef BROTLI_AMD_GANG_KERNEL
-        const uint32_t took = use_general ? rfl(pe16g::path_engine(0)) : use_path ? rfl(pe16::path_engine(0)) : rfl(scan_engine(0));
-#else
         const uint32_t took = use_remote ? rfl(pe16r::path_engine(0)) : use_general ? rfl(pe16g::path_engine(0)) : use_path ? rfl(pe16::path_engine(0)) : rfl(scan_engine(0));
-#endif
         prefer_one_engine = false;
         engine_commands += took;
         {  // the literal rounds' mailbox words lie in the engine's rings: back to their idle state
@@ -2856,9 +2843,7 @@ __device__ __noinline__ int process_commands(HotArgs* args) {
         const uint32_t form_raw = LEAN_LD(L_SC_POS_HI), form = form_raw & 0xFFu;
         const bool declined = ((form_raw >> 8) & 1u) != 0u;
         if (((form_raw >> 10) & 1u) != 0u) prefer_general = true;   // (the lean form stopped in front of a dictionary reference)
-#ifdef BROTLI_AMD_GANG_KERNEL
         if (use_remote) gang_took(args, took, form_raw);
-#endif
         if (((form_raw >> 9) & 1u) != 0u) prefer_scan = true;   // (the path engine's regions were bound by their closure: a stream of few literals -- the scan engine's from here on)
         const uint64_t pos = origin + LEAN_LD(L_SC_POS_LO) - BitReader::skip_bits();
         if (lane == 0) { LEAN_ST(L_SPEC_LO, (uint32_t)rfl(args->spec_scratch)); LEAN_ST(L_SPEC_HI, (uint32_t)(rfl(args->spec_scratch) >> 32)); }
@@ -3403,6 +3388,7 @@ done:
 
 // Marshals the stream state into the argument block, runs the loop, takes the results back.
 constexpr uint32_t ENGINE_ONLY_MIN_MLEN = 32768;  // (BROTLI_AMD_FLAG_ENGINE_ONLY: smaller metablocks are decoded where they are)
+template <bool GANG>
 __device__ __forceinline__ int run_commands(Stream& s, const BrotliAmdResume* mid_, uint64_t mb_out_pos, BrotliAmdStreamStatus* st) {
   HotArgs h;
   h.br = s.br; h.ar = s.ar; h.out = s.out; h.dict = s.dict;
@@ -3463,7 +3449,7 @@ __device__ __forceinline__ int run_commands(Stream& s, const BrotliAmdResume* mi
     if (!ctx_never && (rfl(s.flags) & BROTLI_AMD_FLAG_ENGINE_ONLY) && rfl((uint32_t)s.mlen) >= ENGINE_ONLY_MIN_MLEN) {
       s.num_metablocks--; return E_RETRY_ARENA;  // (see the flag; nothing of this metablock has been output yet)
     }
-    e = ctx_never ? process_commands<true, true>(&h) : process_commands<true, false>(&h);
+    e = ctx_never ? process_commands<true, true, false, GANG>(&h) : process_commands<true, false>(&h);
   } else if (ctx_never && ar_.lds_limit >= TREE_CACHE_BYTES && (g_engine_mode & 16u) == 0u && rfl(s.large_window) == 0u) {
     // (not for large-window streams: a cache slot for a distance tree holds the 928 entries the 520-symbol alphabet takes at
     // most, a large-window alphabet of up to 1128 symbols builds tables of up to 1528 -- ADVICE round 4; such a metablock spills)
@@ -3477,7 +3463,7 @@ __device__ __forceinline__ int run_commands(Stream& s, const BrotliAmdResume* mi
       *reinterpret_cast<gu32x4*>(ar_.glb + off) = *reinterpret_cast<__attribute__((address_space(3))) const u32x4*>(&g_smem[LDS_FIXED + off]);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     h.ar.lds_limit = 0u;
-    e = process_commands<true, true, true>(&h);
+    e = process_commands<true, true, true, GANG>(&h);
   } else if (!ctx_never && ar_.lds_limit >= TREE_CACHE_CTX_BYTES && (g_engine_mode & 16u) == 0u && rfl(s.large_window) == 0u && lit_types_fit_cache(ar_, rfl(s.nbt0), rfl(s.ctx_map), tree_cache_lit_slots(ar_.lds_limit)) &&
              !((rfl(s.flags) & BROTLI_AMD_FLAG_ENGINE_ONLY) && rfl((uint32_t)s.mlen) >= ENGINE_ONLY_MIN_MLEN)) {   // (engine blocks hand such a metablock back, as above)
     // ... and the same where literals do depend on context, as long as no literal block type names more trees than the LDS part has
@@ -3562,6 +3548,7 @@ __device__ __forceinline__ void store_resume(const Stream& s, const BitReader& b
 }
 
 // src/decode.rs:2779-3403 restated for one whole-input call
+template <bool GANG>
 __device__ __forceinline__ int decode_stream(Stream& s, bool have_header, uint64_t in_size, BrotliAmdStreamStatus* st, const BrotliAmdResume* mid) {
   if (!have_header) {
     ColdScope c(s);
@@ -3743,7 +3730,7 @@ __device__ __forceinline__ int decode_stream(Stream& s, bool have_header, uint64
         }
         {
           const BrotliAmdResume* const m_ = mid; mid = nullptr;
-          const int run_e = run_commands(s, m_, s.P, st);
+          const int run_e = run_commands<GANG>(s, m_, s.P, st);
           // a pass that stops in front of this metablock goes on, next time, from the resume point -- which lies in front of a run of
           // metadata blocks that came before it: the next pass counts those again (num_metablocks was inflated)
           if (run_e == E_RETRY_ARENA) s.num_metablocks = counted_before;
@@ -3768,22 +3755,18 @@ __device__ __forceinline__ int decode_stream(Stream& s, bool have_header, uint64
 }  // namespace
 
 // One decoding wave (+ up to seven helper waves) per stream; persistent blocks pull stream indices from `queue`.
-// This file compiles into two objects (Makefile): the kernel of the launches without gangs, and -- with -DBROTLI_AMD_GANG_KERNEL -- the kernel of the
-// gang launches, the only one that has the gang's form of the path engine in its call graph.  One kernel for both cost the metric 4.5 %
-// (6.39 -> 6.68 ms) while the gang's decision sat in process_commands' registers (see there); since it does not, the second kernel costs
-// launches without gangs nothing (measured by running them through it) -- two objects all the same: insurance.
-#ifdef BROTLI_AMD_GANG_KERNEL
-#define BROTLI_AMD_KERNEL brotli_amd_decode_gang_kernel
-#define BROTLI_AMD_LAUNCH brotli_amd_launch_decode_gang
-#else
-#define BROTLI_AMD_KERNEL brotli_amd_decode_kernel
-#define BROTLI_AMD_LAUNCH brotli_amd_launch_decode
-#endif
-extern "C" __global__ __launch_bounds__(1024, 4) void BROTLI_AMD_KERNEL(const BrotliAmdStreamDesc* __restrict__ descs,
-                                                                           BrotliAmdStreamStatus* __restrict__ status, uint32_t n_streams,
-                                                                           uint32_t* __restrict__ queue, uint8_t* __restrict__ scratch,
-                                                                           uint64_t scratch_per_block, uint32_t lds_arena_bytes,
-                                                                           const uint8_t* __restrict__ dict) {
+// Two kernels: brotli_amd_decode_kernel<true> is the kernel of the gang and pool launches, the only one that has the gang's form of the path engine
+// (pe16r) in its call graph; what differs is this body, helper_wave and process_commands<true, true, *> -- everything else is emitted once.
+// Launches without gangs run <false>, which has nothing of the gangs in it.  One kernel for both cost the metric 4.5 % (6.39 -> 6.68 ms) while the
+// gang's decision sat in process_commands' registers (a frame of 432 bytes a lane where it is 128: see there).  Since it does not, the gangs'
+// kernel -- 152 bytes of scratch a lane more, a longer prologue -- still costs such launches a third to half a per cent where blocks are many
+// or literal runs long, and a probe launch some 5 % (measured again when the second compile of this file went).
+template <bool GANG>
+__global__ __launch_bounds__(1024, 4) void brotli_amd_decode_kernel(const BrotliAmdStreamDesc* __restrict__ descs,
+                                                                    BrotliAmdStreamStatus* __restrict__ status, uint32_t n_streams,
+                                                                    uint32_t* __restrict__ queue, uint8_t* __restrict__ scratch,
+                                                                    uint64_t scratch_per_block, uint32_t lds_arena_bytes,
+                                                                    const uint8_t* __restrict__ dict) {
   const uint32_t lane = lane_id();
   // A gang launch (queue[2] blocks a stream, sixteen waves each; see GC_*): block b is member (b mod 8 gang) / 8 of the gang of stream
   // (b / (8 gang)) 8 + b mod 8 -- the members of a gang are eight block numbers apart, which is how the hardware deals blocks to the same
@@ -3792,15 +3775,11 @@ extern "C" __global__ __launch_bounds__(1024, 4) void BROTLI_AMD_KERNEL(const Br
   // as ever; a block that finds the queue empty -- at once, where the batch has fewer streams than CUs; when its own stream is done, otherwise --
   // joins the largest stream that is still being decoded and has fewer than seven helpers, for as long as that stream lasts, and then the next.
   // A stream's gang is whoever has joined it when one of its invocations of the path engine starts (GC_JOINED, GC_MEMBERS).
-#ifdef BROTLI_AMD_GANG_KERNEL
-  uint32_t gang_m = rfl(queue[2]), gang_role = 0, gang_stream = 0; uint64_t gang_addr = 0;
-  const bool pool = (gang_m & BROTLI_AMD_GANG_POOL_FLAG) != 0u && blockDim.x == 64u * SC_WAVES && lds_arena_bytes <= GC_ARENA_CAP;
+  uint32_t gang_m = GANG ? rfl(queue[2]) : 1u, gang_role = 0, gang_stream = 0; uint64_t gang_addr = 0;
+  const bool pool = GANG && (gang_m & BROTLI_AMD_GANG_POOL_FLAG) != 0u && blockDim.x == 64u * SC_WAVES && lds_arena_bytes <= GC_ARENA_CAP;
   const uint64_t pool_base = (uint64_t)rfl(queue[4]) | ((uint64_t)rfl(queue[5]) << 32);
   if ((gang_m & BROTLI_AMD_GANG_POOL_FLAG) != 0u) gang_m = 1u;
   bool pool_open = false;   // (this block's stream has a control block that says it is being decoded)
-#else
-  uint32_t gang_m = 1u, gang_role = 0, gang_stream = 0; uint64_t gang_addr = 0;
-#endif
   if (gang_m > 1u && gang_m <= 16u && blockDim.x == 64u * SC_WAVES && lds_arena_bytes <= GC_ARENA_CAP) {
     gang_role = (blockIdx.x % (8u * gang_m)) >> 3;
     gang_stream = (blockIdx.x / (8u * gang_m)) * 8u + (blockIdx.x & 7u);
@@ -3828,15 +3807,15 @@ extern "C" __global__ __launch_bounds__(1024, 4) void BROTLI_AMD_KERNEL(const Br
   if (gang_role != 0u) {   // a helper block of a gang: the path engine's regions of its owner's stream, nothing else (see there)
     if ((uint32_t)(uintptr_t)g_dynamic_lds != 0u) return;   // (no LDS addressing: the owner finds the gang short of a block and goes on alone)
     if (queue[6] != 0u) return;   // (tests: helpers that never turn up -- BROTLI_AMD_GANG_NO_HELPERS --, as when the device has no CU for them)
-#ifdef BROTLI_AMD_GANG_KERNEL
-    if (threadIdx.x == 0u) (void)gang_add32(gang_ctl(), GC_JOINED, 1u);
-    (void)pe16r::path_engine(rfl(threadIdx.x >> 6));
-#endif
+    if constexpr (GANG) {
+      if (threadIdx.x == 0u) (void)gang_add32(gang_ctl(), GC_JOINED, 1u);
+      (void)pe16r::path_engine(rfl(threadIdx.x >> 6));
+    }
     return;
   }
   if (rfl(threadIdx.x >> 6) != 0u) {
     if ((uint32_t)(uintptr_t)g_dynamic_lds == 0u)
-      helper_wave(rfl(threadIdx.x >> 6), as_global<gu8>(scratch + (uint64_t)scratch_slot * scratch_per_block + (scratch_per_block - BROTLI_AMD_SPEC_SCRATCH)));
+      helper_wave<GANG>(rfl(threadIdx.x >> 6), as_global<gu8>(scratch + (uint64_t)scratch_slot * scratch_per_block + (scratch_per_block - BROTLI_AMD_SPEC_SCRATCH)));
     return;
   }
   // the decoding wave is a chain of dependent instructions; the waves beside it on its SIMD (helpers of this and other blocks)
@@ -3868,12 +3847,10 @@ extern "C" __global__ __launch_bounds__(1024, 4) void BROTLI_AMD_KERNEL(const Br
 
   for (uint32_t pulls = 0;; pulls++) {
     uint32_t idx = 0;
-#ifdef BROTLI_AMD_GANG_KERNEL
     if (pool && pool_open) {   // (the stream before: done, whichever way its turn of this loop ended -- its helpers may go, the pool has one stream less)
       if (lane == 0) { gang_st32(gang_ctl(), GC_EPOCH, GC_QUIT); (void)__hip_atomic_fetch_add(queue + 8, 0xFFFFFFFFu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
       pool_open = false;
     }
-#endif
     if (gang_m > 1u) {   // (a gang's owner: its stream, and no other)
       if (pulls != 0u) break;
       idx = gang_stream;
@@ -3885,7 +3862,6 @@ extern "C" __global__ __launch_bounds__(1024, 4) void BROTLI_AMD_KERNEL(const Br
     // (the host may give an order in which to take the streams -- longest first, so that the last blocks to finish do not
     // start a long stream when the others are done: queue[1] != 0, stream of the k-th pull in queue[16 + k])
     if (queue[1] != 0u) idx = rfl(queue[16u + idx]);
-#ifdef BROTLI_AMD_GANG_KERNEL
     if (pool) {   // this block owns the stream: its control block, nobody's help yet
       const uint64_t ca = pool_base + (uint64_t)idx * GC_STRIDE;
       hc_st(HC_GANG_LO, (uint32_t)ca); hc_st(HC_GANG_HI, (uint32_t)(ca >> 32)); hc_st(HC_GANG_ROLE, 0u); hc_st(HC_GANG_M, 0x108u);
@@ -3893,7 +3869,6 @@ extern "C" __global__ __launch_bounds__(1024, 4) void BROTLI_AMD_KERNEL(const Br
       lds_sync();
       pool_open = true;
     }
-#endif
     const BrotliAmdStreamDesc d = descs[idx];
     BrotliAmdStreamStatus* st = status + idx;
     if (d.flags & BROTLI_AMD_FLAG_DEFER) {   // not this launch's stream (see the flag)
@@ -3956,7 +3931,7 @@ extern "C" __global__ __launch_bounds__(1024, 4) void BROTLI_AMD_KERNEL(const Br
     }
 
     const bool mid = resume && d.resume.mid_valid != 0u;
-    int e = decode_stream(s, resume, d.in_size, st, mid ? &descs[idx].resume : nullptr);
+    int e = decode_stream<GANG>(s, resume, d.in_size, st, mid ? &descs[idx].resume : nullptr);
 
     // result mapping of the one-shot driver (decode.rs:2829-2916, 3382-3397; lib.rs:447-468)
     const bool over = s.br.over();
@@ -3985,7 +3960,6 @@ extern "C" __global__ __launch_bounds__(1024, 4) void BROTLI_AMD_KERNEL(const Br
     }
   }
   if (gang_m > 1u && lane == 0) gang_st32(gang_ctl(), GC_EPOCH, GC_QUIT);   // the stream is done: the gang's helper blocks may go
-#ifdef BROTLI_AMD_GANG_KERNEL
   if (pool && queue[6] == 0u) {
     // no stream of its own (any more): this block helps -- the largest stream that is being decoded, is large enough to have something to divide
     // and has fewer than seven helpers; when that one is done, the next; until the pool has no stream left
@@ -4020,17 +3994,23 @@ extern "C" __global__ __launch_bounds__(1024, 4) void BROTLI_AMD_KERNEL(const Br
       (void)pe16r::path_engine(0);          // ... and stay until the stream is done
     }
   }
-#endif
   // no more streams: the helper waves may go
   hc_st(HC_KIND, 2);
   lds_release();
   hc_st(HC_SEQ, hc_ld(HC_SEQ) + 1u);
 }
+// (instantiated here, <false> first: the compiler lays functions out in the order in which they are first needed, so the functions of the launches
+// without gangs lie where they lay when this file had that kernel alone -- where a hot loop falls in the fetch windows is worth half a per cent)
+template __global__ void brotli_amd_decode_kernel<false>(const BrotliAmdStreamDesc*, BrotliAmdStreamStatus*, uint32_t, uint32_t*, uint8_t*, uint64_t, uint32_t, const uint8_t*);
+template __global__ void brotli_amd_decode_kernel<true>(const BrotliAmdStreamDesc*, BrotliAmdStreamStatus*, uint32_t, uint32_t*, uint8_t*, uint64_t, uint32_t, const uint8_t*);
 
 extern "C" uint32_t brotli_amd_lds_helper_bytes(uint32_t waves);
-extern "C" hipError_t BROTLI_AMD_LAUNCH(const BrotliAmdStreamDesc* descs, BrotliAmdStreamStatus* status, uint32_t n_streams,
-                                        uint32_t* queue, uint8_t* scratch, uint64_t scratch_per_block, uint32_t grid,
-                                        uint32_t lds_arena_bytes, const uint8_t* dict, hipStream_t stream, int helper_waves) {
+namespace {
+template <bool GANG>
+hipError_t launch_decode(const BrotliAmdStreamDesc* descs, BrotliAmdStreamStatus* status, uint32_t n_streams,
+                         uint32_t* queue, uint8_t* scratch, uint64_t scratch_per_block, uint32_t grid,
+                         uint32_t lds_arena_bytes, const uint8_t* dict, hipStream_t stream, int helper_waves) {
+  constexpr auto kernel = brotli_amd_decode_kernel<GANG>;
   if (n_streams == 0) return hipSuccess;
   static const bool no_helpers = getenv("BROTLI_AMD_NO_HELPERS") != nullptr;  // (experiments: one wave per block)
   // (sixteen waves: a block with the command engine; otherwise at most eight)
@@ -4052,16 +4032,27 @@ extern "C" hipError_t BROTLI_AMD_LAUNCH(const BrotliAmdStreamDesc* descs, Brotli
   // and launching is one critical section (the launch itself is asynchronous).
   static std::mutex launch_mutex;
   std::lock_guard<std::mutex> lock(launch_mutex);
-  hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(BROTLI_AMD_KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   if (err != hipSuccess) return err;
   // Blocks of one wave where the caller wants more than four blocks per CU in flight (a CU's registers hold four
   // four-wave blocks): such batches gain more from streams in flight than from helper waves in long literal runs.
-  hipLaunchKernelGGL(BROTLI_AMD_KERNEL, dim3(grid), dim3(64u * waves), smem, stream, descs, status, n_streams, queue, scratch,
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(64u * waves), smem, stream, descs, status, n_streams, queue, scratch,
                      scratch_per_block, lds_arena_bytes, dict);
   return hipGetLastError();
 }
+}  // namespace
+extern "C" hipError_t brotli_amd_launch_decode(const BrotliAmdStreamDesc* descs, BrotliAmdStreamStatus* status, uint32_t n_streams,
+                                               uint32_t* queue, uint8_t* scratch, uint64_t scratch_per_block, uint32_t grid,
+                                               uint32_t lds_arena_bytes, const uint8_t* dict, hipStream_t stream, int helper_waves) {
+  return launch_decode<false>(descs, status, n_streams, queue, scratch, scratch_per_block, grid, lds_arena_bytes, dict, stream, helper_waves);
+}
+// (the launches that give every stream a gang of blocks, or the batch a pool)
+extern "C" hipError_t brotli_amd_launch_decode_gang(const BrotliAmdStreamDesc* descs, BrotliAmdStreamStatus* status, uint32_t n_streams,
+                                                    uint32_t* queue, uint8_t* scratch, uint64_t scratch_per_block, uint32_t grid,
+                                                    uint32_t lds_arena_bytes, const uint8_t* dict, hipStream_t stream, int helper_waves) {
+  return launch_decode<true>(descs, status, n_streams, queue, scratch, scratch_per_block, grid, lds_arena_bytes, dict, stream, helper_waves);
+}
 
-#ifndef BROTLI_AMD_GANG_KERNEL   // (what follows exists once: in the object without the gang kernel)
 // Test hook (BrotliAmdDebugBuildTree, include/brotli/batch.h): the table builder alone.  One wave builds the two-level table of
 // `n_sym` code lengths (src/huffman/mod.rs:273-386) where a metablock's first table would lie and then decodes every fifteen-bit
 // value through it as read_symbol does: decoded[v] = symbol << 4 | code length.  The test compares that -- not the table's layout,
@@ -4097,4 +4088,3 @@ extern "C" uint32_t brotli_amd_lds_helper_bytes(uint32_t waves) {
   if (waves >= SC_WAVES) return SC_BYTES;  // (the rounds' slots lie inside the engine's rings)
   return waves > 1u ? waves * HL_SLOT : 0u;
 }
-#endif

@@ -17,7 +17,7 @@ import sqlite3, sys
 db = sqlite3.connect(sys.argv[1])
 tabs = [r[0] for r in db.execute("select name from sqlite_master where type in ('table','view')")]
 t = [x for x in tabs if x.startswith('counters_collection')]
-for row in db.execute("select counter_name, avg(value), count(*) from %s where kernel_name like 'brotli_amd_decode_kernel%%' group by counter_name" % t[0]):
+for row in db.execute("select counter_name, avg(value), count(*) from %s where kernel_name like '%%brotli_amd_decode_kernel%%' group by counter_name" % t[0]):
     print("  %-28s avg %16.0f  (%d dispatches)" % row)
 PY
 done
