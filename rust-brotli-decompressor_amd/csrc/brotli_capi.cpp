@@ -239,7 +239,7 @@ int probe_streams(BrotliAmdBatch* b, uint32_t n, hipStream_t stream, std::vector
   return 0;
 }
 
-// Several blocks on a stream (csrc/brotli_path_engine.h, PE_CFG_REMOTE): what a launch of sixteen-wave blocks, one a stream, gets on top.
+// Several blocks on a stream (csrc/brotli_path_engine.h, path_engine<false, true>): what a launch of sixteen-wave blocks, one a stream, gets on top.
 // Returns 0 (nothing), 2 / 4 / 8 / 16 (GANGS: that many blocks a stream, dealt at the launch -- its owner and one, three or seven helper blocks that take
 // the path engine's regions in turns with it; eight streams' gangs side by side, a gang's members eight block numbers apart: one XCD; streams beyond a
 // multiple of eight leave their gangs' blocks without work) or 0x108 (a POOL: as many blocks as CUs; a block without a stream of its own -- at once where
@@ -363,7 +363,7 @@ int submit(BrotliAmdBatch* b, uint32_t n, hipStream_t stream) {  // h_descs[0..n
   if (record_blocks) { b->cur_arena = b->lds_arena; b->cur_per_cu = 0; b->grid = std::min(n, b->grid_max); b->waves = 4u; }
   if (can16 && b->grid <= b->cus) { b->cur_arena = arena16; b->waves = 16; }
   // Fewer streams than half the CUs: GANGS of blocks, a CU each, on one stream -- its owner and one, three or seven helper blocks that take
-  // the path engine's regions in turns with it (csrc/brotli_path_engine.h, PE_CFG_REMOTE).  Eight streams' gangs are launched side by side,
+  // the path engine's regions in turns with it (csrc/brotli_path_engine.h, path_engine<false, true>).  Eight streams' gangs are launched side by side,
   // a gang's members eight block numbers apart (one XCD); streams beyond a multiple of eight leave their gangs' blocks without work.
   const int gang_env = getenv("BROTLI_AMD_GANG") ? atoi(getenv("BROTLI_AMD_GANG")) : -1;   // (experiments: 0 or 1 none, 2 / 4 / 8 at most that many)
   const int pool_env = getenv("BROTLI_AMD_POOL") ? atoi(getenv("BROTLI_AMD_POOL")) : -1;   // (experiments, tests: 0 no pool, 2 a pool whatever the sizes)

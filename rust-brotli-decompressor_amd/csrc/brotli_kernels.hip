@@ -1138,7 +1138,7 @@ __device__ __forceinline__ void lds_acquire() { __builtin_amdgcn_fence(__ATOMIC_
 
 // ---- Several CUs on one stream: the gang's control block in memory (one per stream of a gang launch; the host zeroes it) ----
 // A batch of fewer streams than half the CUs is launched as GANGS: the stream's owner -- the block that decodes it, as ever -- and up to
-// seven helper blocks, which do nothing but the path engine's regions in turns with it (brotli_path_engine.h, PE_CFG_REMOTE).  What they
+// seven helper blocks, which do nothing but the path engine's regions in turns with it (brotli_path_engine.h, path_engine<false, true>).  What they
 // tell each other goes through these words, every access an agent-scope atomic (it bypasses the CU's L1; the L2s of the chip's eight XCDs
 // are not coherent for plain accesses):
 //   JOINED   helpers that have started (the owner takes the gang or leaves it: a helper that is not running cannot be waited for)
@@ -1322,9 +1322,10 @@ __device__ __noinline__ void spec_chunk(uint32_t w, uint32_t dw0, uint32_t sh, u
 }
 
 __device__ __noinline__ uint32_t scan_engine(const uint32_t me_);
-namespace pe16 { __device__ __noinline__ uint32_t path_engine(const uint32_t me_); }   // one engine of sixteen waves, the lean form: no words of the static dictionary
-namespace pe16g { __device__ __noinline__ uint32_t path_engine(const uint32_t me_); }  // ... the general form
-namespace pe16r { __device__ __noinline__ uint32_t path_engine(const uint32_t me_); }  // one engine of sixteen a block, the blocks of a gang taking the regions in turns
+namespace pe { template <bool DICT, bool REMOTE> __device__ __noinline__ uint32_t path_engine(const uint32_t me_); }   // one engine of sixteen waves a block (brotli_path_engine.h), in three forms:
+constexpr auto path_engine_lean = pe::path_engine<false, false>;     // no words of the static dictionary: it stops in front of one
+constexpr auto path_engine_general = pe::path_engine<true, false>;   // ... with them
+constexpr auto path_engine_gang = pe::path_engine<false, true>;      // the blocks of a gang taking the stream's regions in turns
 // what the decoding takes (A/B tests, BROTLI_AMD_ENGINE: see brotli_amd_launch_decode); 0 = everything where it applies
 __device__ uint32_t g_engine_mode = 0;
 
@@ -1376,9 +1377,9 @@ __device__ __noinline__ void helper_wave(const uint32_t me /* 1 .. waves - 1 */,
     lds_acquire();
     const uint32_t kind = hc_ld(HC_KIND);
     if (kind == HK_SCAN) { scan_engine(me); continue; }  // every wave of the block runs the command engine
-    if (kind == HK_PATH) { seq = rfl(pe16::path_engine(me)); continue; }   // (back with the last request it answered: see there)
-    if (kind == HK_PATHG) { seq = rfl(pe16g::path_engine(me)); continue; }
-    if constexpr (GANG) { if (kind == HK_PATHR) { seq = rfl(pe16r::path_engine(me)); continue; } }
+    if (kind == HK_PATH) { seq = rfl(path_engine_lean(me)); continue; }   // (back with the last request it answered: see there)
+    if (kind == HK_PATHG) { seq = rfl(path_engine_general(me)); continue; }
+    if constexpr (GANG) { if (kind == HK_PATHR) { seq = rfl(path_engine_gang(me)); continue; } }
     if (kind == HK_RECORDS) {  // a metablock with command records: wave 2 parses them; the others go back to sleep
       if (rfl(me) == 2u && hc_ld(HC_EXT_BASE) != 0u) rec_wave();
       continue;
@@ -1826,26 +1827,12 @@ __device__ __noinline__ void spec_rounds(uint32_t tree_addr) {
 }
 
 #include "brotli_scan_engine.h"
-#define PE_CFG_NS pe16
-#define PE_CFG_DICT 0
-#define PE_CFG_REMOTE 0
 #include "brotli_path_engine.h"
-#undef PE_CFG_NS
-#undef PE_CFG_DICT
-#define PE_CFG_NS pe16g
-#define PE_CFG_DICT 1
-#include "brotli_path_engine.h"
-#undef PE_CFG_NS
-#undef PE_CFG_DICT
-#undef PE_CFG_REMOTE
-#define PE_CFG_NS pe16r
-#define PE_CFG_DICT 0
-#define PE_CFG_REMOTE 1
-#include "brotli_path_engine.h"
-#undef PE_CFG_NS
-#undef PE_CFG_DICT
-#undef PE_CFG_REMOTE
-using pe16::PE_MIN_INPUT;
+// (instantiated here, lean in front of general: where a function lies in the code object is worth half a per cent -- DESIGN 2.  The gang's form
+// comes with the gangs' kernel, behind brotli_amd_decode_kernel<false>.)
+template __device__ uint32_t pe::path_engine<false, false>(const uint32_t);
+template __device__ uint32_t pe::path_engine<true, false>(const uint32_t);
+using pe::PE_MIN_INPUT;
 
 // The pending copy of the lean loop lives in registers the compiler does not know about: v[120:123] (16 bytes per lane)
 // and v124 (one byte per lane), named in inline asm only.  As C++ variables they were shuffled through other registers
@@ -2551,7 +2538,7 @@ struct HotArgs {
   uint64_t spec_scratch;   // global address of the helper waves' literal scratch
   uint64_t num_commands;
   uint32_t engine_commands, reserved_;  // commands a command engine (scan or path) took
-  uint32_t general_engine;  // the stream has words of the static dictionary: the path engine's general form from here on (see PE_CFG_DICT)
+  uint32_t general_engine;  // the stream has words of the static dictionary: the path engine's general form from here on (path_engine<true, false>)
   uint64_t resume_out;     // global address of the status' BrotliAmdResume: command boundaries close to the end of the input are noted there
 };
 
@@ -2833,7 +2820,7 @@ __device__ __noinline__ int process_commands(HotArgs* args) {
         hc_st(HC_KIND, use_remote ? (uint32_t)HK_PATHR : use_general ? (uint32_t)HK_PATHG : use_path ? (uint32_t)HK_PATH : (uint32_t)HK_SCAN);
         lds_release();
         hc_st(HC_SEQ, hc_ld(HC_SEQ) + 1u);  // the other waves of the block join (helper_wave)
-        const uint32_t took = use_remote ? rfl(pe16r::path_engine(0)) : use_general ? rfl(pe16g::path_engine(0)) : use_path ? rfl(pe16::path_engine(0)) : rfl(scan_engine(0));
+        const uint32_t took = use_remote ? rfl(path_engine_gang(0)) : use_general ? rfl(path_engine_general(0)) : use_path ? rfl(path_engine_lean(0)) : rfl(scan_engine(0));
         prefer_one_engine = false;
         engine_commands += took;
         {  // the literal rounds' mailbox words lie in the engine's rings: back to their idle state
@@ -3756,7 +3743,7 @@ __device__ __forceinline__ int decode_stream(Stream& s, bool have_header, uint64
 
 // One decoding wave (+ up to seven helper waves) per stream; persistent blocks pull stream indices from `queue`.
 // Two kernels: brotli_amd_decode_kernel<true> is the kernel of the gang and pool launches, the only one that has the gang's form of the path engine
-// (pe16r) in its call graph; what differs is this body, helper_wave and process_commands<true, true, *> -- everything else is emitted once.
+// (path_engine_gang) in its call graph; what differs is this body, helper_wave and process_commands<true, true, *> -- everything else is emitted once.
 // Launches without gangs run <false>, which has nothing of the gangs in it.  One kernel for both cost the metric 4.5 % (6.39 -> 6.68 ms) while the
 // gang's decision sat in process_commands' registers (a frame of 432 bytes a lane where it is 128: see there).  Since it does not, the gangs'
 // kernel -- 152 bytes of scratch a lane more, a longer prologue -- still costs such launches a third to half a per cent where blocks are many
@@ -3809,7 +3796,7 @@ __global__ __launch_bounds__(1024, 4) void brotli_amd_decode_kernel(const Brotli
     if (queue[6] != 0u) return;   // (tests: helpers that never turn up -- BROTLI_AMD_GANG_NO_HELPERS --, as when the device has no CU for them)
     if constexpr (GANG) {
       if (threadIdx.x == 0u) (void)gang_add32(gang_ctl(), GC_JOINED, 1u);
-      (void)pe16r::path_engine(rfl(threadIdx.x >> 6));
+      (void)path_engine_gang(rfl(threadIdx.x >> 6));
     }
     return;
   }
@@ -3991,7 +3978,7 @@ __global__ __launch_bounds__(1024, 4) void brotli_amd_decode_kernel(const Brotli
       hc_st(HC_KIND, (uint32_t)HK_PATHR);
       lds_release();
       hc_st(HC_SEQ, hc_ld(HC_SEQ) + 1u);   // the other waves of the block join (helper_wave)
-      (void)pe16r::path_engine(0);          // ... and stay until the stream is done
+      (void)path_engine_gang(0);         // ... and stay until the stream is done
     }
   }
   // no more streams: the helper waves may go

@@ -32,17 +32,52 @@
 //
 // Nothing depends on a guess: a record is the exact parse of its state or a marker (END: the parse leaves the region;
 // BYHAND: a cap was hit), and the walk starts at the stream's real position.
-// (no include guard: brotli_kernels.hip includes this file once per configuration -- PE_CFG_NS the namespace, PE_CFG_DICT the
-// form (see PE_DICT below), PE_CFG_REMOTE (round 5) whether the blocks of a gang -- up to sixteen, a CU each, on one stream (see
-// "several CUs on one stream" below) -- take the stream's regions in turns; what they tell each other goes through memory.)
-#if !defined(PE_CFG_NS) || !defined(PE_CFG_DICT) || !defined(PE_CFG_REMOTE)
-#error "brotli_path_engine.h: configuration macros missing"
+// Everything here is defined once, in namespace pe; the engine itself is path_engine<DICT, REMOTE> (see there): DICT the form that
+// takes the static dictionary's words, REMOTE (round 5) whether the blocks of a gang -- up to sixteen, a CU each, on one stream (see
+// "several CUs on one stream" below) -- take the stream's regions in turns; what they tell each other goes through memory.
+#pragma once
+
+// ---- build-time tunables (-D..., e.g. through tools/build_variant.sh) ----
+#ifndef BROTLI_AMD_PE_JUMP_LOG
+#define BROTLI_AMD_PE_JUMP_LOG 3          // commands a hop of the walk, log2 (3 or 4): one block on a stream
 #endif
-namespace PE_CFG_NS {
+#ifndef BROTLI_AMD_PE_REMOTE_JUMP_LOG
+#define BROTLI_AMD_PE_REMOTE_JUMP_LOG 4   // ... a gang of blocks on a stream
+#endif
+#ifndef BROTLI_AMD_PE_RUN_MIN
+#define BROTLI_AMD_PE_RUN_MIN 6000        // literal runs from this many literals on get regions of their own
+#endif
+#ifndef BROTLI_AMD_PE_RUN_SB
+#define BROTLI_AMD_PE_RUN_SB 256          // ... stream bits of such a region a lane decodes one code word after the other (128 or 256)
+#endif
+#ifndef BROTLI_AMD_PE_BULK_NS
+#define BROTLI_AMD_PE_BULK_NS 2           // states a lane evaluates side by side in the bulk of the records
+#endif
+#ifndef BROTLI_AMD_PE_POLL_SLEEP
+#define BROTLI_AMD_PE_POLL_SLEEP 2        // x 64 clocks between two looks at what the walk has published
+#endif
+#ifndef BROTLI_AMD_PE_TAIL_WAVES
+#define BROTLI_AMD_PE_TAIL_WAVES 16       // waves that see the thin end of the records through (all of an engine's, whatever their number)
+#endif
+#ifndef BROTLI_AMD_PE_TAIL_AT
+#define BROTLI_AMD_PE_TAIL_AT 80          // busy slots (of 128) below which a wave hands over what it holds
+#endif
+#ifndef BROTLI_AMD_PE_DEPTH2_MIN
+#define BROTLI_AMD_PE_DEPTH2_MIN 16       // a gang of this many blocks and more may have three executes under way
+#endif
+#ifndef BROTLI_AMD_PE_REMOTE_MARGIN
+#define BROTLI_AMD_PE_REMOTE_MARGIN 1024  // a gang: stream bits between the windows of its plan
+#endif
+#ifndef BROTLI_AMD_PE_SEEDS
+#define BROTLI_AMD_PE_SEEDS 384           // a gang: entry seeds of a window built ahead of the stream, bit positions
+#endif
+#ifndef BROTLI_AMD_PE_SEED_BACK
+#define BROTLI_AMD_PE_SEED_BACK 448       // ... from this many bits in front of where the stream would enter
+#endif
+
+namespace pe {
 constexpr uint32_t GW = 16;                       // waves of the engine: the whole block
 static_assert(GW == SC_WAVES, "one engine a block");
-constexpr bool REMOTE = PE_CFG_REMOTE != 0;       // the blocks of a gang take the stream's regions in turns (a region's tables are built
-                                                  // before the stream's entry into it is known)
 
 constexpr uint32_t PE_RBL = 32768;                // stream bits per region (local bit 0 = the first bit of the region's first dword)
 constexpr uint32_t PE_CHUNKS = PE_RBL / 32;       // one lane per chunk of 32 bits: the whole block
@@ -53,38 +88,20 @@ constexpr uint32_t PE_GROW_BELOW = PE_WCAP / 4u;  // closure states below which 
 constexpr uint32_t PE_HOPCAP = 8;                 // hops through J1 one evaluation takes; a run that needs more goes on in the lane's next evaluation
 constexpr uint32_t PE_SYNC_ROUNDS = GW + 1;  // rounds between waves the chunk entries get to settle: enough for any code
 constexpr uint32_t PE_CMDS = PE_RBL / 32u;          // commands one region's walk lists at most
-#ifndef BROTLI_AMD_PE_DEPTH2_MIN
-#define BROTLI_AMD_PE_DEPTH2_MIN 16
-#endif
 constexpr uint32_t PE_DEPTH2_MIN = BROTLI_AMD_PE_DEPTH2_MIN;   // a gang of this many blocks and more may have three executes under way (see the execute's waits)
 constexpr uint32_t PE_DEP_ROUNDS = 6;             // levels of copies that build on each other which go side by side (execute); deeper ones in order
 constexpr uint32_t PE_LANE_LITS = 64;             // literal runs up to this long are stored by their command's lane, four bytes a step
 constexpr uint32_t PE_LANE_COPY = 16;             // copies up to this long from in front of the region are done by their command's lane: a region
                                                   // that is put together in LDS takes them out of ONE sixteen-byte load
-#ifndef BROTLI_AMD_PE_RUN_MIN
-#define BROTLI_AMD_PE_RUN_MIN 6000
-#endif
 constexpr uint32_t PE_RUN_MIN = BROTLI_AMD_PE_RUN_MIN;             // literal runs from here on (about what a region's path holds) get regions of their own (2048 was tried: slower, C3 6.56 -> 6.75 ms:
                                                   // every run ends the invocation)
-#ifndef BROTLI_AMD_PE_RUN_SB
-#define BROTLI_AMD_PE_RUN_SB 256
-#endif
 constexpr uint32_t PE_RUN_SB = BROTLI_AMD_PE_RUN_SB;   // a long literal run's regions: stream bits a lane decodes one code word after the other (128 or 256: the longer the part,
                                                   // the likelier the lane's last word ends where it does whatever bit the lane entered at, and the fewer rounds the entries take)
 constexpr uint32_t PE_RUN_RBL = 64u * GW * PE_RUN_SB;   // ... and the bits of such a region (no tables per bit: its input lies in the input's and J1's room)
 constexpr uint32_t PE_MIN_INPUT = 4096;           // stream bits that must be left for a region to be worth its set-up
-#ifndef BROTLI_AMD_PE_REMOTE_MARGIN
-#define BROTLI_AMD_PE_REMOTE_MARGIN 1024
-#endif
-#ifndef BROTLI_AMD_PE_SEEDS
-#define BROTLI_AMD_PE_SEEDS 384
-#endif
-#ifndef BROTLI_AMD_PE_SEED_BACK
-#define BROTLI_AMD_PE_SEED_BACK 448
-#endif
 constexpr uint32_t PE_SEEDS = BROTLI_AMD_PE_SEEDS;          // a gang: entry seeds of a window built ahead of the stream (PEC_SEEDLO): this many bit positions ...
 constexpr uint32_t PE_SEED_BACK = BROTLI_AMD_PE_SEED_BACK;  // ... from this far in front of where a stream that ran the region before to its end would enter
-static_assert(!PE_CFG_REMOTE || PE_SEEDS <= 64u * GW, "a thread a seed");
+static_assert(PE_SEEDS <= 64u * GW, "a thread a seed");
 constexpr uint32_t PE_REMOTE_MARGIN = BROTLI_AMD_PE_REMOTE_MARGIN;   // a gang of blocks: the margin between the windows of its plan (a region's walk ends short of its window's end)
 constexpr uint32_t PE_PIPE_USEFUL = 4096;          // ... a window's tables are used if the stream enters them with at least this many bits to go
 constexpr uint32_t PE_PIPE_HAND = 48;              // ... and the walk evaluates this many states itself before the stream is on the path (commands without literals, one after the other)
@@ -95,15 +112,10 @@ constexpr uint32_t PE_CTL = 0;                                    // 1024: contr
 constexpr uint32_t PE_IN = 1024;                                   // the region's input: PE_RBL / 32 + 6 dwords
 constexpr uint32_t PE_J1F = PE_IN + (PE_RBL / 32 + 8) * 4;        // code length at every bit, bit 7: on the path; later NEXT8
 constexpr uint32_t PE_N8 = PE_J1F;                                // u16 per state: the state PE_JUMP commands on
-#ifndef BROTLI_AMD_PE_JUMP_LOG
-#define BROTLI_AMD_PE_JUMP_LOG 3
-#endif
-#ifndef BROTLI_AMD_PE_REMOTE_JUMP_LOG
-#define BROTLI_AMD_PE_REMOTE_JUMP_LOG 4
-#endif
-// commands a hop of the walk (8 or 16; a gang of blocks: 16 -- there the walk is what the stream waits for, and one more doubling of the table is built ahead by somebody else)
-constexpr uint32_t PE_JUMP_LOG = PE_CFG_REMOTE ? BROTLI_AMD_PE_REMOTE_JUMP_LOG : BROTLI_AMD_PE_JUMP_LOG, PE_JUMP = 1u << PE_JUMP_LOG;
-static_assert(PE_JUMP_LOG == 3 || PE_JUMP_LOG == 4, "the walk's hop");
+// commands a hop of the walk, log2 (8 or 16 commands; a gang of blocks: 16 -- there the walk is what the stream waits for, and one more doubling of the table is
+// built ahead by somebody else): the one constant next to the layout that depends on the engine's form -- path_engine's own PE_JUMP_LOG / PE_JUMP
+constexpr uint32_t pe_jump_log(const bool remote) { return remote ? BROTLI_AMD_PE_REMOTE_JUMP_LOG : BROTLI_AMD_PE_JUMP_LOG; }
+static_assert((pe_jump_log(false) == 3 || pe_jump_log(false) == 4) && (pe_jump_log(true) == 3 || pe_jump_log(true) == 4), "the walk's hop");
 constexpr uint32_t PE_STG = PE_J1F;                               // the region's output while it is put together (execute), where it fits: see PE_STG_CAP
 constexpr uint32_t PE_STG_CAP = PE_RBL;            // output bytes of a region that is put together in LDS and written out in one piece (0: never)
 static_assert(PE_STG_CAP <= PE_RBL, "the stage lives in J1's room");
@@ -128,15 +140,6 @@ constexpr uint32_t PE_LIST = PE_WST + PE_WSTB;                    // u16 per lis
 constexpr uint32_t PE_ANCH = PE_LIST + (PE_CMDS + 8) * 2;         // u32 per anchor of the walk: list index | state id << 16
 constexpr uint32_t PE_TAILQ = PE_LIST;                              // u16 per state the bulk of the records left for the thin end (list and anchors are not in use then)
 constexpr uint32_t PE_TAILCAP = PE_CMDS;
-#ifndef BROTLI_AMD_PE_POLL_SLEEP
-#define BROTLI_AMD_PE_POLL_SLEEP 2   // (x 64 clocks between two looks at what the walk has published)
-#endif
-#ifndef BROTLI_AMD_PE_TAIL_WAVES
-#define BROTLI_AMD_PE_TAIL_WAVES 16   /* (all of an engine's, whatever their number) */
-#endif
-#ifndef BROTLI_AMD_PE_TAIL_AT
-#define BROTLI_AMD_PE_TAIL_AT 80
-#endif
 constexpr uint32_t PE_TAIL_WAVES = BROTLI_AMD_PE_TAIL_WAVES;  // waves that see the thin end of the records through
 constexpr uint32_t PE_TAIL_AT = BROTLI_AMD_PE_TAIL_AT;        // busy slots (of 128) below which a wave hands over what it holds
 constexpr uint32_t PE_RUN_LIT = PE_POR;                            // a long literal run's region: its literals (the room of the ranks, literals, records and closure states)
@@ -188,15 +191,11 @@ static_assert(PEC_DEPCHG == PEC_TAKE, "a deliberate share (see above)");
 // the region's tables, the walk's list and the details in the waves' registers hold for every pass.  A word that is not a plain
 // one (unknown transform, an empty word, one that does not fit the limits) ends the invocation behind the command's distance:
 // the checked loop says what it is.
-// The engine compiles twice for that (round 5): PE_CFG_DICT 0 is the LEAN form -- it stops in front of a dictionary reference, as round 3's
-// did, and tells the caller, who takes the general form (PE_CFG_DICT 1) for the rest of the stream.  A stream without such words -- the
+// The engine has two forms for that (round 5): path_engine<false, false> is the LEAN form -- it stops in front of a dictionary reference, as round 3's
+// did, and tells the caller, who takes the general form (path_engine<true, false>) for the rest of the stream.  A stream without such words -- the
 // metric's -- never runs the general form: what that form carries had cost it 4 % through the allocation of one very large function's
 // registers (128 a wave, and the function spills).
-#if PE_CFG_DICT && !PE_CFG_REMOTE
-#define PE_DICT 1
-#else
-#define PE_DICT 0
-#endif
+// (PE_DICT, inside path_engine: the form takes the words -- a gang's never does.)
 
 
 
@@ -640,18 +639,13 @@ __device__ __forceinline__ PeParse pe_eval(const PeCtx& c, uint32_t pos, uint32_
     } } while (0)
 
 // The barrier of the engine's waves: the hardware's.
-#if PE_CFG_REMOTE
 // (a gang's waits inside an invocation are for another block's work on one region -- whose output may be hundreds of megabytes of overlapping
-// copies: a minute or more of looking, not seconds, before the kernel is stopped rather than the machine)
+// copies: a minute or more of looking, not seconds, before the kernel is stopped rather than the machine.  The one-block forms' waits are
+// for their own waves: not counted)
 __device__ __forceinline__ void pe_spin_check(uint32_t& spins) { if (++spins > (1u << 26)) __builtin_trap(); }
-#define PE_SPIN_CHECK(s_) pe_spin_check(s_)
-#else
-#define PE_SPIN_CHECK(s_) do { } while (0)
-#endif
 
 // One invocation: every wave of the block calls it (wave 0 from process_commands, the others from helper_wave).
 // Returns (wave 0) the number of commands it took; exit form and state in LDS_LEAN as the scan engine leaves them.
-#if PE_DICT
 // (PE_DICT) Wave 0, behind a pass that ended with the literals of a command whose copy is a word of the static dictionary: the
 // word goes out behind them (decode.rs:2593-2640, as lean_rec_commands takes them) and the stream's state moves on; PEC_AGAIN
 // says whether the commands behind it get a pass.  A function of its own: it is rare, and the engine's loops stay as they were.
@@ -686,7 +680,6 @@ __device__ __noinline__ void pe_dict_word(const uint32_t pb, gu8* const out, gcu
   pe_ctl_st(pb, PEC_AGAIN, again);
 }
 
-#endif
 // A wave other than the decoding wave stays in here until the block is asked for something else than this engine: a call
 // saves and restores the registers the caller may count on (38 vector registers a lane: 155 KB of scratch a block and
 // invocation, more than a metablock's output is long; the lines are long out of L2 when the epilogue asks for them).  That, not
@@ -694,7 +687,13 @@ __device__ __noinline__ void pe_dict_word(const uint32_t pb, gu8* const out, gcu
 // output: 1.15 and 1.29 with the waves staying (tools/ubench/write_calib.hip: the counter is exact for every store pattern of
 // this kernel).  The loop around the function's body costs the metric 1 % (the compiler's register allocation of the whole
 // kernel shifts).  Such a wave returns the number of the last request it has answered.
+// DICT: the general form, which takes the static dictionary's words (false: the lean form); REMOTE: a gang's form.
+template <bool DICT, bool REMOTE>
 __device__ __noinline__ uint32_t path_engine(const uint32_t me_) {
+  // (static: as automatic objects in front of pe_again these constants gave the function another clean-up structure, which the gang's form's scalar code showed)
+  static constexpr bool PE_DICT = DICT && !REMOTE;   // (a gang's engine stops in front of a dictionary reference, as the lean form does)
+  static constexpr uint32_t PE_JUMP_LOG = pe_jump_log(REMOTE), PE_JUMP = 1u << PE_JUMP_LOG;   // commands a hop of the walk
+  static constexpr uint32_t HK_MINE = REMOTE ? (uint32_t)HK_PATHR : PE_DICT ? (uint32_t)HK_PATHG : (uint32_t)HK_PATH;   // the mailbox's word for this form
 pe_again:
   const uint32_t lane = lane_id();
   const uint32_t me = rfl(me_);
@@ -702,7 +701,7 @@ pe_again:
   const uint32_t pb = hc_ld(HC_SCAN_BASE);                        // the engine's tables
   if (T == 0u) { lds_st32(pb + PE_CTL + 4u * PEC_NXOK, 0u); lds_st32(pb + PE_CTL + 4u * PEC_PDX, 0u); lds_st32(pb + PE_CTL + 4u * PEC_OVF, 0u); lds_st32(pb + PE_CTL + 4u * PEC_DSEEN, 0u); }
   if (REMOTE && T < 7u) lds_st32(pb + PE_CTL + 4u * (PEC_EXECUTED + T), 0u);   // what the blocks of a gang tell each other starts from nothing (EXECUTED .. DECLINE)
-  // ---- several CUs on one stream (PE_CFG_REMOTE; the control block's words: GC_* in brotli_kernels.hip) ----
+  // ---- several CUs on one stream (REMOTE; the control block's words: GC_* in brotli_kernels.hip) ----
   // The blocks of a gang take the stream's regions in turns -- region k is block k mod gang's --, each with
   // the whole of its CU: the tables of a region (70 K clocks of the 130 K a region costs one CU) are built ahead by as many CUs as it takes,
   // and the stream itself only waits for the walk, the details and the resolve of the region before (and the execute for the output of the
@@ -748,7 +747,7 @@ pe_again:
       if (threadIdx.x == 0u) {   // the helpers have all left the invocation before (they read the image below when they enter one)
         uint32_t spins = 0; (void)spins;
         const uint32_t expected = *reinterpret_cast<lds_vu32*>(&g_smem[LDS_HCTL + 4u * HC_GANG_READY]);   // (the helpers of every invocation so far, summed)
-        while (gang_ld32(gc, GC_READY) != expected) { __builtin_amdgcn_s_sleep(8); PE_SPIN_CHECK(spins); }
+        while (gang_ld32(gc, GC_READY) != expected) { __builtin_amdgcn_s_sleep(8); if constexpr (REMOTE) pe_spin_check(spins); }
       }
       __syncthreads();
       const uint32_t ab = (pb - LDS_FIXED + 15u) & ~15u;   // (the table arena lies between the fixed part and the engine's)
@@ -1152,10 +1151,10 @@ pe_again:
       }
       pe_st_store(pb, st);
     }
-#if !PE_CFG_REMOTE
-    __syncthreads();   // (the first region's mode is wave 0's word)
-    if (pe_ctl_ld(pb, PEC_MODE) != 0u) { c.L = pe_ctl_ld(pb, PEC_L); return run_region(); }
-#endif
+    if constexpr (!REMOTE) {
+      __syncthreads();   // (the first region's mode is wave 0's word)
+      if (pe_ctl_ld(pb, PEC_MODE) != 0u) { c.L = pe_ctl_ld(pb, PEC_L); return run_region(); }
+    }
     // ---- J1: the length of the literal code word at every bit, eight bits per lane and pass ----
     for (uint32_t g = T; g < PE_RBL / 8u; g += 64u * GW) {
       const uint32_t pos0 = g << 3;
@@ -1441,9 +1440,6 @@ pe_again:
         }
       }
     };
-#ifndef BROTLI_AMD_PE_BULK_NS
-#define BROTLI_AMD_PE_BULK_NS 2
-#endif
     records_loop(std::integral_constant<uint32_t, BROTLI_AMD_PE_BULK_NS>{}, 0u, c.Rn + seed_n);
     __syncthreads();
     {
@@ -1522,7 +1518,7 @@ pe_again:
       arrived = __ballot(lane < GC_STATE_WORDS && (uint32_t)(v >> 32) == want) == ((1ull << GC_STATE_WORDS) - 1ull);
       stopped = rdlane((uint32_t)(v >> 32), 32) == epoch && rdlane((uint32_t)v, 32) <= kseq;
       if (arrived || stopped) break;
-      __builtin_amdgcn_s_sleep(1); PE_SPIN_CHECK(spins);
+      __builtin_amdgcn_s_sleep(1); if constexpr (REMOTE) pe_spin_check(spins);
     }
     uint32_t ok_ = 0u;
     if (arrived && (rdlane((uint32_t)v, 25) & 1u) != 0u) {   // (the region before's resolve said that the stream goes on)
@@ -2053,7 +2049,7 @@ pe_pass:
       for (;;) {
         const uint64_t ew = gang_ld64(gc, GC_EXEC);
         if ((uint32_t)(ew >> 32) == epoch && (uint32_t)ew >= upto) break;
-        __builtin_amdgcn_s_sleep(1); PE_SPIN_CHECK(spins);
+        __builtin_amdgcn_s_sleep(1); if constexpr (REMOTE) pe_spin_check(spins);
       }
       const uint32_t waited = (uint32_t)(__builtin_amdgcn_s_memtime() - t0_);
       gang_acquire();
@@ -2075,7 +2071,7 @@ pe_pass:
     if (REMOTE) {
       // the region before's output is in memory before this one's copies read it (its engine says so)
       uint32_t spins = 0; (void)spins;
-      while (pe_ctl_ld(pb, PEC_EXECUTED) < kseq) { __builtin_amdgcn_s_sleep(2); PE_SPIN_CHECK(spins); }
+      while (pe_ctl_ld(pb, PEC_EXECUTED) < kseq) { __builtin_amdgcn_s_sleep(2); if constexpr (REMOTE) pe_spin_check(spins); }
     }
     // ---- execute ----
     {
@@ -2241,8 +2237,7 @@ pe_pass:
           big_store(t0, d0, n0); big_store(t1, d1, n1); big_store(t2, d2, n2);
         }
       }
-#if PE_DICT
-      {
+      if constexpr (PE_DICT) {
         // (b') the pass's words of the static dictionary (decode.rs:2593-2640, transform.rs:737-795), a wave each: lane = byte of the word
         const uint32_t nword = pe_ctl_ld(pb, PEC_NWORD);
         if (nword != 0u) for (;;) {
@@ -2256,7 +2251,6 @@ pe_pass:
           if (lane < w.total) { if (staged) lds_st8(sg + at + lane, ob); else o[at + lane] = (uint8_t)ob; }
         }
       }
-#endif
       // (a gang whose executes wait twice) The second wait -- for the region before's output -- stands in front of the word that says this region's is
       // there, and in front of the copies that read that output (`lagging` ones: their source begins in front of the region) and of those that build on them.
       auto second_wait = [&]() {
@@ -2412,8 +2406,7 @@ pe_pass:
         write_out(sg, o, tot);
       }
     }
-#if PE_DICT
-    if (pe_ctl_ld(pb, PEC_DICTK) != 0xFFFFFFFFu) {
+    if constexpr (PE_DICT) if (pe_ctl_ld(pb, PEC_DICTK) != 0xFFFFFFFFu) {
       // the pass ended behind the literals of a command whose copy is a word of the static dictionary (decode.rs:2593-2640, as
       // lean_rec_commands takes them): wave 0 puts it behind them, and the commands behind it get a pass of their own
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -2427,15 +2420,13 @@ pe_pass:
         goto pe_pass;
       }
     }
-#endif
     if (REMOTE) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
       if (REMOTE && T == 0u) { gang_release(); gang_st64(gc, GC_EXEC, ((uint64_t)epoch << 32) | (uint64_t)(kseq + 1u)); }
     }
   };
-#if !PE_CFG_REMOTE
-  for (;;) {
+  if constexpr (!REMOTE) for (;;) {
     if (me == 0) {
       const PeStream st = pe_st_load(pb);
       const uint32_t lbdw_ = st.b >> 5;
@@ -2465,8 +2456,7 @@ pe_pass:
     if (how == 2u) break;
     consume();
     if (pe_ctl_ld(pb, PEC_CONT) == 0u) break;
-  }
-#else
+  } else
   // ---- a gang of blocks: the stream's regions in turns, as many regions ahead as the gang has blocks.  Where
   // the windows lie is a PLAN everybody follows without asking: region k's starts (k - first) strides behind the plan's first bit (a stride is a
   // region less a margin: a region's walk ends a command or two short of its window's end wherever it entered it).  The engine whose turn it
@@ -2514,7 +2504,7 @@ pe_pass:
             stopped = rdlane((uint32_t)(v >> 32), 32) == epoch && rdlane((uint32_t)v, 32) <= kseq;
             replanned = (rdlane((uint32_t)(v >> 32), 33) >> 16) != mygen;
             if (arrived || stopped || replanned) break;
-            __builtin_amdgcn_s_sleep(1); PE_SPIN_CHECK(spins);
+            __builtin_amdgcn_s_sleep(1); if constexpr (REMOTE) pe_spin_check(spins);
           }
 
           plan = 2u;   // 0: the tables are the ones, 1: once more where the stream is, 2: the invocation is over, 3: once more by the new plan, then wait again
@@ -2601,7 +2591,6 @@ pe_pass:
       if (pe_ctl_ld(pb, PEC_CONT) == 0u) break;
     }
   }
-#endif
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   const uint32_t seq_ = hc_ld(HC_SEQ);   // (the request this invocation answers: the decoding wave posts the next one behind the barrier)
   __syncthreads();  // every store of the engine is in memory before the decoding wave goes on alone
@@ -2615,25 +2604,25 @@ pe_pass:
       if (idle < 256u) __builtin_amdgcn_s_sleep(4); else __builtin_amdgcn_s_sleep(127);
     }
     lds_acquire();
-    if (hc_ld(HC_SEQ) == seq_ + 1u && hc_ld(HC_KIND) == (REMOTE ? (uint32_t)HK_PATHR : PE_DICT ? (uint32_t)HK_PATHG : (uint32_t)HK_PATH)) goto pe_again;   // (this form of the engine again: the lean one and the general one are two functions)
+    if (hc_ld(HC_SEQ) == seq_ + 1u && hc_ld(HC_KIND) == HK_MINE) goto pe_again;   // (this form of the engine again: the lean one and the general one are two functions)
     return seq_;
   }
   if (REMOTE && pe_ctl_ld(pb, PEC_PLAN) != 6u) {   // (6: the owner kept the invocation to itself)
     // (the owner of a gang) the invocation's end as the gang left it: the regions resolved in all, the stream's state behind the last of them
     // -- whoever's it was --, and the last one's output in memory
     uint32_t spins = 0; uint64_t sw_, v; (void)spins;
-    for (;;) { sw_ = gang_ld64(gc, GC_STOP); if ((uint32_t)(sw_ >> 32) == epoch) break; __builtin_amdgcn_s_sleep(1); PE_SPIN_CHECK(spins); }
+    for (;;) { sw_ = gang_ld64(gc, GC_STOP); if ((uint32_t)(sw_ >> 32) == epoch) break; __builtin_amdgcn_s_sleep(1); if constexpr (REMOTE) pe_spin_check(spins); }
     const uint32_t Kr = (uint32_t)sw_, want = (epoch << 12) | Kr;
     for (;;) {
       v = gang_ld64(gc, GC_STATE + 8u * (lane < GC_STATE_WORDS ? lane : 0u));
       if (__ballot(lane < GC_STATE_WORDS && (uint32_t)(v >> 32) == want) == ((1ull << GC_STATE_WORDS) - 1ull)) break;
-      __builtin_amdgcn_s_sleep(1); PE_SPIN_CHECK(spins);
+      __builtin_amdgcn_s_sleep(1); if constexpr (REMOTE) pe_spin_check(spins);
     }
     if (lane < 25u) lds_st32(pb + PE_CTL + 4u * (PEC_STATE + lane), (uint32_t)v);
     pe_ctl_st(pb, PEC_DECLINE, (rdlane((uint32_t)v, 25) >> 1) & 3u);
     pe_ctl_st(pb, PEC_DSEEN, Kr != 0u ? (rdlane((uint32_t)v, 25) >> 3) & 1u : 0u);   // (the engine's part ended in front of a dictionary reference: the general form's stream, as the lean form says it)
     if (Kr != 0u) {
-      for (;;) { const uint64_t ew = gang_ld64(gc, GC_EXEC); if ((uint32_t)(ew >> 32) == epoch && (uint32_t)ew >= Kr) break; __builtin_amdgcn_s_sleep(1); PE_SPIN_CHECK(spins); }
+      for (;;) { const uint64_t ew = gang_ld64(gc, GC_EXEC); if ((uint32_t)(ew >> 32) == epoch && (uint32_t)ew >= Kr) break; __builtin_amdgcn_s_sleep(1); if constexpr (REMOTE) pe_spin_check(spins); }
       gang_acquire();
     }
     lds_sync();
@@ -2667,9 +2656,7 @@ pe_pass:
   lds_sync();
   return st.ncmd;
 }
-}  // namespace PE_CFG_NS
+}  // namespace pe
 #undef PE_TRY_RUN
 #undef PE_TRY_RUN_FROM
 #undef PE_HOPS_REC
-#undef PE_DICT
-#undef PE_SPIN_CHECK

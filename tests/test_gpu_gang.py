@@ -1,6 +1,6 @@
 """Several CUs on one stream (needs a real MI355X): batches of fewer streams than half the device's CUs give every stream a GANG of
 blocks -- its owner and one, three or seven helper blocks that take the path engine's regions in turns with it
-(csrc/brotli_path_engine.h, PE_CFG_REMOTE; the words they exchange: GC_* in csrc/brotli_kernels.hip).
+(csrc/brotli_path_engine.h, path_engine<false, true>; the words they exchange: GC_* in csrc/brotli_kernels.hip).
 
 What the reference does for one stream is one serial loop (src/decode.rs:2330-2744, ProcessCommandsInternal); whatever the number of
 blocks on a stream, its bytes and status words must be the oracle's."""

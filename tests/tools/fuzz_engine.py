@@ -54,7 +54,7 @@ for seed in range(first, first + nseeds):
             a = rnd.randrange(0, len(d)); b_ = min(len(d), a + rnd.randrange(1, 64)); del d[a:b_]
         if k >= 0.15 and rnd.random() < 0.3: cap = rnd.randrange(1, n + 4096)  # (damage and a buffer that may be too small: the reference's verdict, batch.h)
         datas.append(bytes(d)); caps.append(cap)
-    # (FUZZ_BATCH: streams a launch -- up to 128 the host gives every stream a gang of blocks, csrc/brotli_path_engine.h PE_CFG_REMOTE; a seed's
+    # (FUZZ_BATCH: streams a launch -- up to 128 the host gives every stream a gang of blocks, csrc/brotli_path_engine.h path_engine<false, true>; a seed's
     # 200 streams then go through several launches of one batch object)
     per = int(os.environ.get("FUZZ_BATCH", "200"))
     b = pkg.Batch(min(per, len(datas))); res, outs, gangs = [], [], set()
