@@ -78,6 +78,29 @@ BROTLI_DEC_API int BrotliAmdBatchWait(BrotliAmdBatch* batch, BrotliAmdResult* re
 BROTLI_DEC_API int BrotliAmdBatchDecodeHost(BrotliAmdBatch* batch, uint32_t n, const uint8_t* const* in, const size_t* in_sizes,
                                            uint8_t* const* out, const size_t* out_caps, uint32_t flags, BrotliAmdResult* results);
 
+/* Custom (LZ77 prefix) dictionaries -- the batch form of the reference's BrotliDecompressCustomDict (src/lib.rs:101, 202) and
+ * BrotliState::new_with_custom_dictionary (src/state.rs:400-411).  BrotliAmdBatchDecodeDevice plus, per stream, a DEVICE pointer to its
+ * dictionary and its size: d_dicts == NULL, dict_sizes == NULL, d_dicts[i] == NULL or dict_sizes[i] == 0 mean no dictionary for that
+ * stream, and a call without any is BrotliAmdBatchDecodeDevice exactly.  Streams of one call may name the same dictionary (the rule: thousands
+ * of small documents against one shared dictionary, which the device then reads out of its caches), different ones or none; the
+ * dictionaries are only read and must stay where they are until BrotliAmdBatchWait has returned (and through every BrotliAmdBatchRelaunch,
+ * which keeps them).  A dictionary's bytes lie in front of output position 0 for back-references alone; one longer than the stream's window
+ * counts with its last (1 << window_bits) - 16 bytes (decode.rs:1831-1839).  Result, error code, decoded_size and every output byte are the
+ * reference's with that dictionary.  Same asynchrony and the same probe rule; the probe's memory of a batch includes the dictionaries.
+ * Launch shapes are PLANNED as for the same batch without dictionaries -- gangs and pools included (BrotliAmdBatchLastGang, BrotliAmdBatchLastPool say
+ * what they say without).  A command whose copy starts in the dictionary is always decoded by the block that owns its stream: a gang stops in
+ * front of it and is invoked again behind it, so while a stream's window still reaches its dictionary the helper blocks have work only between
+ * such commands. */
+BROTLI_DEC_API int BrotliAmdBatchDecodeDeviceDict(BrotliAmdBatch* batch, uint32_t n, const void* const* d_in, const size_t* in_sizes,
+                                                 void* const* d_out, const size_t* out_caps, const void* const* d_dicts,
+                                                 const size_t* dict_sizes, uint32_t flags, void* hip_stream);
+
+/* The same for host buffers: BrotliAmdBatchDecodeHost plus per-stream HOST pointers to the dictionaries.  Each distinct (pointer, size)
+ * pair is uploaded once per call, not once per stream. */
+BROTLI_DEC_API int BrotliAmdBatchDecodeHostDict(BrotliAmdBatch* batch, uint32_t n, const uint8_t* const* in, const size_t* in_sizes,
+                                               uint8_t* const* out, const size_t* out_caps, const uint8_t* const* dicts,
+                                               const size_t* dict_sizes, uint32_t flags, BrotliAmdResult* results);
+
 /* Milliseconds the last launch spent in the decode kernel (HIP events on the launch stream). */
 BROTLI_DEC_API float BrotliAmdBatchLastKernelMs(BrotliAmdBatch* batch);
 
@@ -106,6 +129,14 @@ BROTLI_DEC_API uint32_t BrotliAmdDebugPlanGangs(uint32_t n, uint32_t cus, const 
  * number of commands however the input is cut up; a test asserts that instead of timing calls. */
 struct BrotliDecoderStateStruct;
 BROTLI_DEC_API uint64_t BrotliAmdDecoderDeviceCommands(const struct BrotliDecoderStateStruct* state);
+
+/* Streaming with a custom dictionary (reference: BrotliState::new_with_custom_dictionary, src/state.rs:400-411; the adapters'
+ * new_with_custom_dict, src/reader.rs:103-162, src/writer.rs:115-171): attaches ONE dictionary to an instance made by
+ * BrotliDecoderCreateInstance, before it has decoded anything.  The bytes are copied (the caller's buffer may go); at most the last
+ * (1 << 30) - 16 of them are kept, which is all any window reaches.  Every launch of BrotliDecoderDecompressStream then decodes with it.
+ * Returns 1 on a fresh instance; size == 0 is a no-op that returns 1.  Returns 0 for a NULL state, NULL data with size != 0, a second
+ * dictionary, and once BrotliDecoderIsUsed is true.  The one-shot functions of decode.h have no dictionary, as in src/ffi/mod.rs:120. */
+BROTLI_DEC_API int BrotliAmdDecoderAttachDictionary(struct BrotliDecoderStateStruct* state, const uint8_t* data, size_t size);
 
 /* Text of the last HIP/runtime failure on this thread ("" if none). */
 BROTLI_DEC_API const char* BrotliAmdLastError(void);

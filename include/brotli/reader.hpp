@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "brotli/batch.h"
 #include "brotli/decode.h"
 
 namespace brotli_amd {
@@ -36,6 +37,15 @@ class Decompressor {
     // native constructors of the reference accept large-window streams (src/state.rs:394)
     if (large_window) BrotliDecoderSetParameter(state_, BROTLI_DECODER_PARAM_LARGE_WINDOW, 1);
   }
+  // Decompressor::new_with_custom_dict (src/reader.rs:103-162): the stream was made for a custom (LZ77 prefix) dictionary; its bytes
+  // are copied (BrotliAmdDecoderAttachDictionary, batch.h).  An empty dictionary is none.
+  Decompressor(R source, size_t buffer_size, const uint8_t* dict, size_t dict_size, bool large_window = true)
+      : Decompressor(std::move(source), buffer_size, large_window) {
+    // (a delegating constructor that throws: the object is complete, its destructor runs and destroys the state)
+    if (dict_size != 0 && !BrotliAmdDecoderAttachDictionary(state_, dict, dict_size)) throw std::invalid_argument("custom dictionary refused");
+  }
+  Decompressor(R source, size_t buffer_size, const std::vector<uint8_t>& dict, bool large_window = true)
+      : Decompressor(std::move(source), buffer_size, dict.data(), dict.size(), large_window) {}
   Decompressor(const Decompressor&) = delete;
   Decompressor& operator=(const Decompressor&) = delete;
   ~Decompressor() { BrotliDecoderDestroyInstance(state_); }

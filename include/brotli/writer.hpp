@@ -30,6 +30,13 @@ class DecompressorWriter {
     if (!state_) throw std::bad_alloc();
     if (large_window) BrotliDecoderSetParameter(state_, BROTLI_DECODER_PARAM_LARGE_WINDOW, 1);
   }
+  // DecompressorWriter::new_with_custom_dictionary (src/writer.rs:115-171): as Decompressor's constructor with a dictionary
+  DecompressorWriter(W sink, size_t buffer_size, const uint8_t* dict, size_t dict_size, bool large_window = true)
+      : DecompressorWriter(std::move(sink), buffer_size, large_window) {
+    if (dict_size != 0 && !BrotliAmdDecoderAttachDictionary(state_, dict, dict_size)) throw std::invalid_argument("custom dictionary refused");
+  }
+  DecompressorWriter(W sink, size_t buffer_size, const std::vector<uint8_t>& dict, bool large_window = true)
+      : DecompressorWriter(std::move(sink), buffer_size, dict.data(), dict.size(), large_window) {}
   DecompressorWriter(const DecompressorWriter&) = delete;
   DecompressorWriter& operator=(const DecompressorWriter&) = delete;
   ~DecompressorWriter() { BrotliDecoderDestroyInstance(state_); }

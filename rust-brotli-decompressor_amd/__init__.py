@@ -31,6 +31,7 @@ DECODE_H_SYMBOLS = [
 BATCH_H_SYMBOLS = [
     "BrotliAmdBatchCreate", "BrotliAmdBatchDestroy", "BrotliAmdBatchDecodeDevice", "BrotliAmdBatchRelaunch", "BrotliAmdBatchWait",
     "BrotliAmdBatchDecodeHost", "BrotliAmdBatchLastKernelMs", "BrotliAmdBatchLastSecondPassCount", "BrotliAmdBatchLastGang", "BrotliAmdBatchLastPool", "BrotliAmdBatchLastProbeMs", "BrotliAmdDebugPlanGangs", "BrotliAmdLastError", "BrotliAmdLastNote", "BrotliAmdDebugBuildTree", "BrotliAmdDecoderDeviceCommands",
+    "BrotliAmdBatchDecodeDeviceDict", "BrotliAmdBatchDecodeHostDict", "BrotliAmdDecoderAttachDictionary",
 ]
 
 
@@ -99,6 +100,11 @@ def load_library():
     L.BrotliAmdBatchRelaunch.argtypes = [vp, vp]
     L.BrotliAmdBatchWait.argtypes = [vp, vp]
     L.BrotliAmdBatchDecodeHost.argtypes = [vp, u32, vp, vp, vp, vp, u32, vp]
+    if hasattr(L, "BrotliAmdBatchDecodeDeviceDict"):   # (custom dictionaries: an older build of the library, loaded for an A/B, has none)
+        L.BrotliAmdBatchDecodeDeviceDict.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, u32, vp]
+        L.BrotliAmdBatchDecodeHostDict.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, u32, vp]
+        L.BrotliAmdDecoderAttachDictionary.argtypes = [vp, vp, sz]
+        L.BrotliAmdDecoderAttachDictionary.restype = ctypes.c_int
     L.BrotliAmdBatchLastKernelMs.restype = ctypes.c_float
     L.BrotliAmdBatchLastKernelMs.argtypes = [vp]
     L.BrotliAmdBatchLastSecondPassCount.restype = ctypes.c_uint32
@@ -156,14 +162,23 @@ class Batch:
         except Exception:
             pass
 
-    def decode_device(self, in_ptrs, in_sizes, out_ptrs, out_caps, flags=FLAG_LARGE_WINDOW, stream=None):
-        """Device pointers in, asynchronous launch on `stream` (a hipStream_t handle as int, None = default)."""
+    def decode_device(self, in_ptrs, in_sizes, out_ptrs, out_caps, flags=FLAG_LARGE_WINDOW, stream=None, dict_ptrs=None, dict_sizes=None):
+        """Device pointers in, asynchronous launch on `stream` (a hipStream_t handle as int, None = default).
+        dict_ptrs / dict_sizes: per stream the device address and size of its custom dictionary (None or 0: none) --
+        BrotliAmdBatchDecodeDeviceDict; the dictionaries stay where they are until wait() has returned."""
         n = len(in_ptrs)
         a_in = (ctypes.c_void_p * n)(*in_ptrs)
         a_is = (ctypes.c_size_t * n)(*in_sizes)
         a_out = (ctypes.c_void_p * n)(*out_ptrs)
         a_oc = (ctypes.c_size_t * n)(*out_caps)
-        if self._L.BrotliAmdBatchDecodeDevice(self._h, n, a_in, a_is, a_out, a_oc, flags, stream) != 0:
+        if dict_ptrs is not None or dict_sizes is not None:
+            if dict_ptrs is None or dict_sizes is None or len(dict_ptrs) != n or len(dict_sizes) != n:
+                raise ValueError("dict_ptrs and dict_sizes: one entry per stream each")
+            a_dp = (ctypes.c_void_p * n)(*[p or None for p in dict_ptrs])
+            a_ds = (ctypes.c_size_t * n)(*[int(v or 0) for v in dict_sizes])
+            if self._L.BrotliAmdBatchDecodeDeviceDict(self._h, n, a_in, a_is, a_out, a_oc, a_dp, a_ds, flags, stream) != 0:
+                raise RuntimeError("BrotliAmdBatchDecodeDeviceDict failed: " + last_error())
+        elif self._L.BrotliAmdBatchDecodeDevice(self._h, n, a_in, a_is, a_out, a_oc, flags, stream) != 0:
             raise RuntimeError("BrotliAmdBatchDecodeDevice failed: " + last_error())
         self.n = n
 
@@ -195,8 +210,10 @@ class Batch:
         """whether the last launch was a pool: blocks without a stream of their own help the largest stream still being decoded"""
         return bool(self._L.BrotliAmdBatchLastPool(self._h)) if hasattr(self._L, "BrotliAmdBatchLastPool") else False
 
-    def decode_host(self, datas, out_caps, flags=FLAG_LARGE_WINDOW):
-        """Host bytes in, (results, outputs) out: upload, decode, download."""
+    def decode_host(self, datas, out_caps, flags=FLAG_LARGE_WINDOW, dicts=None):
+        """Host bytes in, (results, outputs) out: upload, decode, download.
+        dicts: per stream its custom dictionary (bytes; None or b"": none) -- BrotliAmdBatchDecodeHostDict.  Streams that are
+        given the same bytes object share one upload."""
         n = len(datas)
         ins = [ctypes.create_string_buffer(bytes(d), max(1, len(d))) for d in datas]
         outs = [ctypes.create_string_buffer(max(1, c)) for c in out_caps]
@@ -205,7 +222,18 @@ class Batch:
         a_out = (ctypes.c_void_p * n)(*[ctypes.addressof(b) for b in outs])
         a_oc = (ctypes.c_size_t * n)(*out_caps)
         res = (BatchResult * max(1, n))()
-        if self._L.BrotliAmdBatchDecodeHost(self._h, n, a_in, a_is, a_out, a_oc, flags, res) != 0:
+        if dicts is not None:
+            if len(dicts) != n:
+                raise ValueError("dicts: one entry per stream")
+            held = {}  # id of the caller's object -> its buffer: one (pointer, size) pair per distinct dictionary
+            for d in dicts:
+                if d and id(d) not in held:
+                    held[id(d)] = ctypes.create_string_buffer(bytes(d), len(d))
+            a_dp = (ctypes.c_void_p * n)(*[ctypes.addressof(held[id(d)]) if d else None for d in dicts])
+            a_ds = (ctypes.c_size_t * n)(*[len(d) if d else 0 for d in dicts])
+            if self._L.BrotliAmdBatchDecodeHostDict(self._h, n, a_in, a_is, a_out, a_oc, a_dp, a_ds, flags, res) != 0:
+                raise RuntimeError("BrotliAmdBatchDecodeHostDict failed: " + last_error())
+        elif self._L.BrotliAmdBatchDecodeHost(self._h, n, a_in, a_is, a_out, a_oc, flags, res) != 0:
             raise RuntimeError("BrotliAmdBatchDecodeHost failed: " + last_error())
         self.n = n
         results = list(res)[:n]
@@ -229,13 +257,21 @@ class Batch:
 class DecoderState:
     """BrotliDecoderState through the C ABI."""
 
-    def __init__(self, large_window=False):
+    def __init__(self, large_window=False, dictionary=None):
         self._L = load_library()
         self._h = self._L.BrotliDecoderCreateInstance(None, None, None)
         if not self._h:
             raise MemoryError("BrotliDecoderCreateInstance")
         if large_window:
             self._L.BrotliDecoderSetParameter(self._h, PARAM_LARGE_WINDOW, 1)
+        if dictionary and not self.attach_dictionary(dictionary):  # BrotliState::new_with_custom_dictionary (state.rs:400-411)
+            raise RuntimeError("BrotliAmdDecoderAttachDictionary refused the dictionary")
+
+    def attach_dictionary(self, data):
+        """BrotliAmdDecoderAttachDictionary (batch.h): one custom dictionary, before anything is decoded; the bytes are copied."""
+        data = bytes(data)
+        buf = ctypes.create_string_buffer(data, max(1, len(data)))
+        return bool(self._L.BrotliAmdDecoderAttachDictionary(self._h, ctypes.addressof(buf), len(data)))
 
     def close(self):
         if self._h:
@@ -288,10 +324,11 @@ class Decompressor:
     decoder, or input that ends before the stream does, raises ValueError (io::ErrorKind::InvalidData /
     UnexpectedEof in the reference, reader.rs:335-346)."""
 
-    def __init__(self, reader, buffer_size=4096, large_window=True):
+    def __init__(self, reader, buffer_size=4096, large_window=True, dictionary=None):
         self._r = reader
         self._bufsize = max(1, buffer_size)
-        self._st = DecoderState(large_window=large_window)  # native constructors default to large_window (state.rs:394)
+        # native constructors default to large_window (state.rs:394); dictionary: Decompressor::new_with_custom_dict (reader.rs:103-162)
+        self._st = DecoderState(large_window=large_window, dictionary=dictionary)
         self._pending = b""
         self._done = False
         self._eof = False
@@ -329,10 +366,10 @@ class DecompressorWriter:
     bytes and forwards decompressed bytes to the wrapped writer; close() drains and fails if the stream is
     incomplete (writer.rs:257-289)."""
 
-    def __init__(self, writer, buffer_size=4096, large_window=True):
+    def __init__(self, writer, buffer_size=4096, large_window=True, dictionary=None):
         self._w = writer
         self._bufsize = max(1, buffer_size)
-        self._st = DecoderState(large_window=large_window)
+        self._st = DecoderState(large_window=large_window, dictionary=dictionary)  # DecompressorWriter::new_with_custom_dictionary (writer.rs:115-171)
         self._done = False
 
     def write(self, data: bytes):

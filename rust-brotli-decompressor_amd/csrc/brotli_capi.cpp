@@ -135,6 +135,7 @@ struct BrotliAmdBatch {
   // staging for BrotliAmdBatchDecodeHost
   uint8_t* d_stage_in = nullptr; size_t stage_in_cap = 0;
   uint8_t* d_stage_out = nullptr; size_t stage_out_cap = 0;
+  uint8_t* d_stage_dict = nullptr; size_t stage_dict_cap = 0;   // ... and of BrotliAmdBatchDecodeHostDict's custom dictionaries, each distinct one once
   // ... and its pinned host side: the caller's buffers are pageable as a rule, a copy engine wants pinned memory (one transfer per
   // direction in pieces, the host's own copies on several threads side by side with the transfers)
   uint8_t* h_pin_in = nullptr; size_t pin_in_cap = 0;
@@ -332,7 +333,8 @@ int submit(BrotliAmdBatch* b, uint32_t n, hipStream_t stream) {  // h_descs[0..n
     uint64_t in_total = 0, in_engine = 0, key = 0xcbf29ce484222325ull ^ n;
     for (uint32_t i = 0; i < n; i++) {
       in_total += b->h_descs[i].in_size;
-      for (uint64_t v : {(uint64_t)(uintptr_t)b->h_descs[i].in, (uint64_t)b->h_descs[i].in_size, (uint64_t)b->h_descs[i].flags}) key = (key ^ v) * 0x100000001b3ull;
+      for (uint64_t v : {(uint64_t)(uintptr_t)b->h_descs[i].in, (uint64_t)b->h_descs[i].in_size, (uint64_t)b->h_descs[i].flags,
+                         (uint64_t)(uintptr_t)b->h_descs[i].dict, (uint64_t)b->h_descs[i].dict_size}) key = (key ^ v) * 0x100000001b3ull;
     }
     if (in_total >= (uint64_t)n * kProbeMinMeanBytes) {
       if (b->probe_kind.size() == n && b->probe_key == key) kind = b->probe_kind;
@@ -608,6 +610,7 @@ extern "C" void BrotliAmdBatchDestroy(BrotliAmdBatch* b) {
   if (b->h_retry_status) (void)hipHostFree(b->h_retry_status);
   if (b->d_stage_in) (void)hipFree(b->d_stage_in);
   if (b->d_stage_out) (void)hipFree(b->d_stage_out);
+  if (b->d_stage_dict) (void)hipFree(b->d_stage_dict);
   if (b->h_pin_in) (void)hipHostFree(b->h_pin_in);
   if (b->h_pin_out) (void)hipHostFree(b->h_pin_out);
   if (b->copy_stream) (void)hipStreamDestroy(b->copy_stream);
@@ -622,8 +625,20 @@ extern "C" void BrotliAmdBatchDestroy(BrotliAmdBatch* b) {
   delete b;
 }
 
-extern "C" int BrotliAmdBatchDecodeDevice(BrotliAmdBatch* b, uint32_t n, const void* const* d_in, const size_t* in_sizes, void* const* d_out,
-                                          const size_t* out_caps, uint32_t flags, void* hip_stream) {
+namespace {
+// A custom dictionary as the kernel is told of it: no window reaches further back than (1 << 30) - 16 bytes (decode.rs:1831-1839), so
+// of a longer one the tail is named -- the same bytes at the same distances.
+constexpr size_t kMaxCustomDict = ((size_t)1 << 30) - 16;
+void name_dictionary(BrotliAmdStreamDesc& d, const uint8_t* dict, size_t size) {
+  if (dict == nullptr || size == 0) return;
+  const size_t tail = std::min(size, kMaxCustomDict);
+  d.dict = dict + (size - tail); d.dict_size = tail;
+}
+}  // namespace
+
+extern "C" int BrotliAmdBatchDecodeDeviceDict(BrotliAmdBatch* b, uint32_t n, const void* const* d_in, const size_t* in_sizes, void* const* d_out,
+                                              const size_t* out_caps, const void* const* d_dicts, const size_t* dict_sizes, uint32_t flags,
+                                              void* hip_stream) {
   if (!b || n > b->max_streams || (n && (!d_in || !in_sizes || !d_out || !out_caps))) { g_last_error = "invalid batch arguments"; return -1; }
   DeviceGuard guard;
   for (uint32_t i = 0; i < n; i++) {
@@ -632,9 +647,15 @@ extern "C" int BrotliAmdBatchDecodeDevice(BrotliAmdBatch* b, uint32_t n, const v
     d.in = static_cast<const uint8_t*>(d_in[i]); d.in_size = in_sizes[i];
     d.out = static_cast<uint8_t*>(d_out[i]); d.out_cap = out_caps[i];
     d.flags = flags & (BROTLI_AMD_FLAG_LARGE_WINDOW | BROTLI_AMD_FLAG_NO_CANNY | BROTLI_AMD_BATCH_SPILL_IN_PLACE);
+    if (d_dicts && dict_sizes) name_dictionary(d, static_cast<const uint8_t*>(d_dicts[i]), dict_sizes[i]);
   }
   b->exact_limit = !(flags & BROTLI_AMD_BATCH_EAGER_OUTPUT_LIMIT);
   return submit(b, n, static_cast<hipStream_t>(hip_stream));
+}
+
+extern "C" int BrotliAmdBatchDecodeDevice(BrotliAmdBatch* b, uint32_t n, const void* const* d_in, const size_t* in_sizes, void* const* d_out,
+                                          const size_t* out_caps, uint32_t flags, void* hip_stream) {
+  return BrotliAmdBatchDecodeDeviceDict(b, n, d_in, in_sizes, d_out, out_caps, nullptr, nullptr, flags, hip_stream);
 }
 
 extern "C" int BrotliAmdBatchRelaunch(BrotliAmdBatch* b, void* hip_stream) {
@@ -684,12 +705,37 @@ extern "C" float BrotliAmdBatchLastKernelMs(BrotliAmdBatch* b) {
   return ms + b->retry_ms;
 }
 
-extern "C" int BrotliAmdBatchDecodeHost(BrotliAmdBatch* b, uint32_t n, const uint8_t* const* in, const size_t* in_sizes, uint8_t* const* out,
-                                        const size_t* out_caps, uint32_t flags, BrotliAmdResult* results) {
+extern "C" int BrotliAmdBatchDecodeHostDict(BrotliAmdBatch* b, uint32_t n, const uint8_t* const* in, const size_t* in_sizes, uint8_t* const* out,
+                                            const size_t* out_caps, const uint8_t* const* dicts, const size_t* dict_sizes, uint32_t flags,
+                                            BrotliAmdResult* results) {
   if (!b || n > b->max_streams || (n && (!in || !in_sizes || !out || !out_caps))) { g_last_error = "invalid batch arguments"; return -1; }
   if (n == 0) return 0;
   DeviceGuard guard;
   if (!hip_ok(hipSetDevice(b->device), "hipSetDevice")) return -1;
+  // custom dictionaries: every distinct (pointer, size) pair is uploaded once -- a batch of documents against one shared dictionary
+  // reads one copy of it, which stays in the device's caches
+  std::vector<std::pair<const uint8_t*, size_t>> dict_of;   // distinct pairs (what name_dictionary would keep of them), in order of appearance
+  std::vector<size_t> dict_off;
+  std::vector<int> dict_ix(n, -1);
+  size_t dict_total = 0;
+  if (dicts && dict_sizes) {
+    for (uint32_t i = 0; i < n; i++) {
+      if (dicts[i] == nullptr || dict_sizes[i] == 0) continue;
+      const size_t tail = std::min(dict_sizes[i], kMaxCustomDict);
+      const std::pair<const uint8_t*, size_t> key(dicts[i] + (dict_sizes[i] - tail), tail);
+      size_t k = 0;
+      if (i != 0 && dict_ix[i - 1] >= 0 && dict_of[(size_t)dict_ix[i - 1]] == key) k = (size_t)dict_ix[i - 1];   // (the rule: the stream before's)
+      else k = (size_t)(std::find(dict_of.begin(), dict_of.end(), key) - dict_of.begin());
+      if (k == dict_of.size()) { dict_of.push_back(key); dict_off.push_back(dict_total); dict_total += (tail + 63) & ~(size_t)63; dict_total += 64; }
+      dict_ix[i] = (int)k;
+    }
+  }
+  if (dict_total > b->stage_dict_cap) {
+    if (b->d_stage_dict) (void)hipFree(b->d_stage_dict);
+    b->d_stage_dict = nullptr; b->stage_dict_cap = 0;
+    if (!hip_ok(hipMalloc(&b->d_stage_dict, dict_total), "hipMalloc(dictionary arena)")) return -1;
+    b->stage_dict_cap = dict_total;
+  }
   // one input arena and one output arena, 64-byte aligned slots
   std::vector<size_t> in_off(n), out_off(n);
   size_t in_total = 0, out_total = 0;
@@ -725,6 +771,8 @@ extern "C" int BrotliAmdBatchDecodeHost(BrotliAmdBatch* b, uint32_t n, const uin
     else { (void)hipGetLastError(); b->h_pin_out = nullptr; pinned = false; }
   }
   if (!b->copy_stream && !hip_ok(hipStreamCreateWithFlags(&b->copy_stream, hipStreamNonBlocking), "hipStreamCreate")) return -1;
+  for (size_t k = 0; k < dict_of.size(); k++)
+    if (!hip_ok(hipMemcpyAsync(b->d_stage_dict + dict_off[k], dict_of[k].first, dict_of[k].second, hipMemcpyHostToDevice, b->copy_stream), "hipMemcpyAsync(dictionary)")) return -1;
   const unsigned hw = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
   // streams [lo, hi) copied by up to `hw` threads, split by bytes
   auto parallel_copy = [&](uint32_t lo, uint32_t hi, auto&& one) {
@@ -762,6 +810,7 @@ extern "C" int BrotliAmdBatchDecodeHost(BrotliAmdBatch* b, uint32_t n, const uin
     d.in = b->d_stage_in + in_off[i]; d.in_size = in_sizes[i];
     d.out = b->d_stage_out + out_off[i]; d.out_cap = out_caps[i];
     d.flags = flags & (BROTLI_AMD_FLAG_LARGE_WINDOW | BROTLI_AMD_FLAG_NO_CANNY | BROTLI_AMD_BATCH_SPILL_IN_PLACE);
+    if (dict_ix[i] >= 0) { d.dict = b->d_stage_dict + dict_off[(size_t)dict_ix[i]]; d.dict_size = dict_of[(size_t)dict_ix[i]].second; }
   }
   b->exact_limit = !(flags & BROTLI_AMD_BATCH_EAGER_OUTPUT_LIMIT);
   if (!hip_ok(hipStreamSynchronize(b->copy_stream), "hipStreamSynchronize(upload)")) return -1;
@@ -811,6 +860,11 @@ extern "C" int BrotliAmdBatchDecodeHost(BrotliAmdBatch* b, uint32_t n, const uin
     if (!ok) return -1;
   }
   return 0;
+}
+
+extern "C" int BrotliAmdBatchDecodeHost(BrotliAmdBatch* b, uint32_t n, const uint8_t* const* in, const size_t* in_sizes, uint8_t* const* out,
+                                        const size_t* out_caps, uint32_t flags, BrotliAmdResult* results) {
+  return BrotliAmdBatchDecodeHostDict(b, n, in, in_sizes, out, out_caps, nullptr, nullptr, flags, results);
 }
 
 extern "C" const char* BrotliAmdLastError(void) { return g_last_error.c_str(); }
@@ -1071,6 +1125,9 @@ struct BrotliDecoderStateStruct {
   uint64_t total_out;      // output bytes handed to the caller (partial_pos_out)
   uint8_t* outq; size_t outq_len, outq_off, outq_cap;  // fetched but not yet handed over
   uint64_t device_commands; // commands the device has decoded for this stream in all its launches together (BrotliAmdDecoderDeviceCommands)
+  // the custom dictionary (BrotliAmdDecoderAttachDictionary): the state's own copy on the host until the instance is bound to a
+  // device, then on the device -- a buffer of its own, which no trim or re-base of the output touches: every launch names it
+  uint8_t* h_dict; uint8_t* d_dict; size_t dict_len;
 };
 
 namespace {
@@ -1161,6 +1218,7 @@ int decode_pass(BrotliDecoderState* s, BrotliAmdStreamStatus* st) {
     d.out = reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(s->d_out) - (uintptr_t)s->out_base); d.out_cap = s->out_base + s->d_out_cap;
     d.flags = (s->large_window ? BROTLI_AMD_FLAG_LARGE_WINDOW : 0u) | (s->canny ? 0u : BROTLI_AMD_FLAG_NO_CANNY);
     if (s->have_resume) { d.flags |= BROTLI_AMD_FLAG_RESUME; d.resume = s->resume; }
+    if (s->d_dict) { d.dict = s->d_dict; d.dict_size = s->dict_len; }
     if (submit(s->batch, 1, nullptr) != 0) return 1;
     if (BrotliAmdBatchWait(s->batch, nullptr) != 0) return 1;
     *st = s->batch->h_status[0];
@@ -1205,6 +1263,12 @@ extern "C" void BrotliDecoderDestroyInstance(BrotliDecoderState* s) {
     if (s->d_in) (void)hipFree(s->d_in);
     if (s->d_out) (void)hipFree(s->d_out);
   }
+  if (s->d_dict) {
+    DeviceGuard guard;
+    if (s->device >= 0) (void)hipSetDevice(s->device);
+    (void)hipFree(s->d_dict);
+  }
+  st_free(s, s->h_dict);
   st_free(s, s->outq);
   brotli_free_func f = s->free_func; void* opaque = s->opaque;
   if (f) f(opaque, s); else std::free(s);
@@ -1265,6 +1329,15 @@ extern "C" BrotliDecoderResult BrotliDecoderDecompressStream(BrotliDecoderState*
       s->device = dev;
     }
     if (!hip_ok(hipSetDevice(s->device), "hipSetDevice")) { set_runtime_error(s, "HIP runtime failure"); return BROTLI_DECODER_RESULT_ERROR; }
+    if (s->h_dict) {   // the attached dictionary moves to the device the instance is bound to
+      if (!hip_ok(hipMalloc(&s->d_dict, s->dict_len + 64), "hipMalloc(custom dictionary)") ||
+          !hip_ok(hipMemcpy(s->d_dict, s->h_dict, s->dict_len, hipMemcpyHostToDevice), "hipMemcpy(custom dictionary)")) {
+        if (s->d_dict) { (void)hipFree(s->d_dict); s->d_dict = nullptr; }
+        set_runtime_error(s, "HIP runtime failure");
+        return BROTLI_DECODER_RESULT_ERROR;
+      }
+      st_free(s, s->h_dict); s->h_dict = nullptr;
+    }
     const size_t fill = (size_t)(s->d_in_len - s->in_base);
     if (!dev_rebase(&s->d_in, &s->d_in_cap, 0, fill, fill + given) ||
         !hip_ok(hipMemcpy(s->d_in + fill, *next_in, given, hipMemcpyHostToDevice), "hipMemcpy(input)")) {
@@ -1322,6 +1395,19 @@ extern "C" const uint8_t* BrotliDecoderTakeOutput(BrotliDecoderState* s, size_t*
   s->outq_off += n; s->total_out += n;
   *size = n;
   return p;  // valid until the next call on this instance
+}
+
+// BrotliState::new_with_custom_dictionary (state.rs:400-411) for an instance of the C ABI: one dictionary, before the first byte is decoded.
+extern "C" BROTLI_BOOL BrotliAmdDecoderAttachDictionary(BrotliDecoderState* s, const uint8_t* data, size_t size) {
+  if (!s || s->used) return BROTLI_FALSE;
+  if (size == 0) return BROTLI_TRUE;
+  if (!data || s->h_dict || s->d_dict) return BROTLI_FALSE;
+  const size_t tail = std::min(size, kMaxCustomDict);   // (no window reaches further back: decode.rs:1831-1839)
+  uint8_t* copy = static_cast<uint8_t*>(st_alloc(s, tail));
+  if (!copy) return BROTLI_FALSE;
+  std::memcpy(copy, data + (size - tail), tail);
+  s->h_dict = copy; s->dict_len = tail;
+  return BROTLI_TRUE;
 }
 
 extern "C" uint64_t BrotliAmdDecoderDeviceCommands(const BrotliDecoderState* s) { return s ? s->device_commands : 0; }

@@ -73,6 +73,12 @@ typedef struct BrotliAmdStreamDesc {
   uint32_t flags;
   uint32_t reserved;
   BrotliAmdResume resume; // only read when BROTLI_AMD_FLAG_RESUME is set
+  // Custom (LZ77 prefix) dictionary (state.rs:400-411): device pointer and size, 0 = none.  Its bytes lie in front of output
+  // position 0 for back-references only -- the kernel reads position v < 0 at dict + dict_size + v; nothing else sees them
+  // (the first two literals' context is (0, 0): decode.rs:2466-2476).  Streams of one launch may name the same dictionary,
+  // different ones or none; every launch of a stream (resumed, larger arena, second decode into scratch) names it again.
+  const uint8_t* dict;
+  uint64_t dict_size;
 } BrotliAmdStreamDesc;
 
 typedef struct BrotliAmdStreamStatus {

@@ -112,6 +112,8 @@ constexpr uint32_t LDS_MTF = LDS_WORD + 128;                // 256: inverse move
 constexpr uint32_t LDS_INWIN = LDS_MTF + 256;               // 1024: compressed-input ring, four 256-byte halves filled by LDS-DMA
 constexpr uint32_t LDS_BR = LDS_INWIN + 1024;               // 32: what the bit reader needs only when it moves its window (BitReader)
 constexpr uint32_t LDS_HOT = LDS_BR + 32;                   // 96: what the command loop needs only at block switches (process_commands)
+constexpr uint32_t LDS_HOT_CDICT_END = 22;                  // (words of LDS_HOT: the address behind the custom dictionary's last byte, two words)
+constexpr uint32_t LDS_HOT_CDICT_SIZE = 21;                 // (word of LDS_HOT: the custom dictionary's size, see run_commands -- the record loop and the path engine's word tests read it)
 constexpr uint32_t LDS_LEAN = LDS_HOT + 96;                 // 192: state handed between process_commands and lean_commands
 constexpr uint32_t LDS_LEANWIN = LDS_LEAN + 192;            // 256: the reader's register window, handed over with the state
 constexpr uint32_t LDS_HCTL = LDS_LEANWIN + 256;            // 80: mailbox between the decoding wave and its helper waves (round-wide words)
@@ -447,6 +449,8 @@ struct Stream {
   uint64_t rb_size;
   gcu8* dict;
   gcu8* in_bytes;
+  gcu8* cdict_end;         // custom (LZ77 prefix) dictionary: the byte behind its last one (output position v < 0 is cdict_end[v]); state.rs:400-411
+  uint32_t cdict_size;     // ... its bytes within a back-reference's reach: the whole of it or, from the stream header on, its last (1 << window_bits) - 16 (decode.rs:1831-1839); 0 = none
   uint32_t flags;
   uint32_t window_bits, large_window;
   int32_t max_backward;
@@ -2061,7 +2065,36 @@ __device__ __noinline__ __attribute__((aligned(256))) uint32_t lean_commands(uin
     {
       const uint32_t n = (uint32_t)copy_len, dist = (uint32_t)distance_code;
       const int32_t max_distance = (P < (uint64_t)(uint32_t)max_backward) ? (int32_t)P : max_backward;
-      if (distance_code > max_distance || distance_code <= 0 || n > quota) { stage = LS_POST_DISTANCE; break; }
+      if (distance_code > max_distance || distance_code <= 0 || n > quota) {
+        // Not a copy inside the stream's own output.  One whose source starts in the custom dictionary (state.rs:400-411: output position
+        // v < 0 is cdict_end[v]) and that does not repeat itself is copied here, split at v = 0: 16 bytes a lane out of the dictionary,
+        // then the rest from the output's first bytes.  All of it on this side of the test: streams without a dictionary run what they ran.
+        const uint32_t cdict_size = rfl(lds_ld32(LDS_HOT + 4u * LDS_HOT_CDICT_SIZE));
+        const uint64_t reach = P + (uint64_t)cdict_size;
+        if (cdict_size == 0u || distance_code <= 0 || n > quota || dist < n || (uint64_t)dist <= P ||
+            (uint64_t)dist > reach || dist > (uint32_t)max_backward) { stage = LS_POST_DISTANCE; break; }
+        gcu8* const cdict_end = (gcu8*)(uintptr_t)((uint64_t)rfl(lds_ld32(LDS_HOT + 4u * LDS_HOT_CDICT_END)) | ((uint64_t)rfl(lds_ld32(LDS_HOT + 4u * LDS_HOT_CDICT_END + 4u)) << 32));
+        if (distance_context == 0) { d3 = d2; d2 = d1; d1 = d0; d0 = distance_code; }
+        mlen -= copy_len;
+        LEAN_FLUSH();
+        const uint32_t before = dist - (uint32_t)P;             // bytes of the source in front of position 0
+        const uint32_t k = before < n ? before : n;             // ... that the copy takes
+        gcu8* s = cdict_end - before; gu8* dst = out + P;
+        for (uint32_t part = 0; part < 2u; part++) {
+          const uint32_t len = part == 0u ? k : n - k;
+          const uint32_t whole = len & ~15u;
+          for (uint32_t c = lane16; c < whole; c += 1024u) {
+            const u32x4 t = *reinterpret_cast<const gu32x4*>(s + c);
+            *reinterpret_cast<gu32x4*>(dst + c) = t;
+          }
+          if (whole + lane < len) dst[whole + lane] = s[whole + lane];
+          s = (gcu8*)out; dst += k;                              // (dist >= n: the rest's source, out[0 .. n - k), lies in front of P)
+        }
+        if (!CTX_NEVER) { ctx_regs = false; ctx_pend = false; }
+        P += n; quota -= n;
+        if (quota == 0) { stage = LS_COMMAND_DONE; break; }
+        continue;
+      }
       // (one path through here for every kind of copy: two that each updated P and the quota and went back to the top
       // of the loop made the compiler shuffle a dozen scalars at the back edge)
       const bool tiny = !CTX_NEVER && n <= 64u;  // short copy where literal context matters: one byte per lane
@@ -2219,6 +2252,10 @@ __device__ __noinline__ __attribute__((aligned(256))) uint32_t lean_rec_commands
   const uint32_t cmd_tree = LEAN_LD(L_CMD_TREE), lit_tree = LEAN_LD(L_LIT_TREE);
   const uint32_t dt0 = LEAN_LD(L_DT0), dt1 = LEAN_LD(L_DT1), dt2 = LEAN_LD(L_DT2), dt3 = LEAN_LD(L_DT3);
   const uint32_t max_backward = LEAN_LD(L_MAX_BACKWARD);
+  // A custom dictionary (0: none) moves the static dictionary's word numbers while the window is not full (decode.rs:2583-2589): the
+  // word tests -- the one below and the hand-written run's, which reads the size from lane 10 of its parameters -- count it.  A short
+  // copy whose source starts in that dictionary is made below; the run leaves it to the loop below as it leaves any command it does not take.
+  const uint32_t cdict_size = rfl(lds_ld32(LDS_HOT + 4u * LDS_HOT_CDICT_SIZE));
   const uint32_t postfix_bits = LEAN_LD(L_POSTFIX), num_direct = LEAN_LD(L_NUM_DIRECT);
   const bool dlut_ok = postfix_bits == 0u && num_direct == 16u;
   uint32_t dlut;
@@ -2308,9 +2345,9 @@ __device__ __noinline__ __attribute__((aligned(256))) uint32_t lean_rec_commands
   bool long_cmd = false;     // (... because of a command longer than the run takes: that is one)
   static const bool no_run_asm = false;
   const uint32_t ctx_tree_abs = ctx_tree_v + LDS_FIXED;   // (the run's literals: a context's tree as an address)
-  // what the run reads once a command at most, a lane each: the four distance contexts' tables (lanes 0 .. 3), XW_POS (lane 5), the static dictionary's address (lanes 6, 7), XW_FRONT and the codes' epoch (lanes 8, 9)
+  // what the run reads once a command at most, a lane each: the four distance contexts' tables (lanes 0 .. 3), XW_POS (lane 5), the static dictionary's address (lanes 6, 7), XW_FRONT and the codes' epoch (lanes 8, 9), the custom dictionary's size (lane 10)
   const uint32_t run_params = lane == 0u ? LDS_FIXED + dt0 : lane == 1u ? LDS_FIXED + dt1 : lane == 2u ? LDS_FIXED + dt2 : lane == 3u ? LDS_FIXED + dt3 :
-                              lane == 6u ? sp_ld(xb, XW_DICT_LO) : lane == 7u ? sp_ld(xb, XW_DICT_HI) : lane == 8u ? xb + 4u * (uint32_t)XW_FRONT : lane == 9u ? my_epoch :
+                              lane == 6u ? sp_ld(xb, XW_DICT_LO) : lane == 7u ? sp_ld(xb, XW_DICT_HI) : lane == 8u ? xb + 4u * (uint32_t)XW_FRONT : lane == 9u ? my_epoch : lane == 10u ? cdict_size :
                               xb + 4u * (uint32_t)XW_POS;
   // ... and of a word of the static dictionary as it stands (transform 0), by its length: where the words of that length begin | the bits of their index << 24
   const uint32_t run_wtab = lane >= 4u && lane <= 24u ? kDictOffsetsByLength[lane] | ((uint32_t)kDictSizeBitsByLength[lane] << 24) : 0u;
@@ -2449,13 +2486,17 @@ __device__ __noinline__ __attribute__((aligned(256))) uint32_t lean_rec_commands
     // finish it from the distance on (the ring and the copy's counts are untouched) ----
     const uint32_t max_distance = P < (uint64_t)max_backward ? (uint32_t)P : max_backward;
     const bool plain = dist > 0 && (uint32_t)dist <= max_distance && n <= 63u && (uint32_t)dist >= n && n < quota;   // (63: the hand-written run makes a copy's lanes with s_bfm_b64)
-    bool word = false;
+    bool word = false, from_cdict = false;
     WordShape w = {};
     uint32_t word_offset = 0;
     if (!plain) {
-      if ((uint32_t)dist > max_distance && dist > 0 && dist <= 0x7FFFFFFC && n >= 4u && n <= 24u) {
+      const uint64_t cdict_reach = P + (uint64_t)cdict_size;
+      const uint32_t word_from = cdict_reach < (uint64_t)max_backward ? (uint32_t)cdict_reach : max_backward;   // (the max distance: max_distance where there is no custom dictionary)
+      // (a plain copy but for its source, which starts in the custom dictionary: made below, a byte a lane from either side of position 0)
+      from_cdict = dist > 0 && (uint32_t)dist > max_distance && (uint32_t)dist <= word_from && n <= 63u && (uint32_t)dist >= n && n < quota;
+      if (!from_cdict && (uint32_t)dist > word_from && dist > 0 && dist <= 0x7FFFFFFC && n >= 4u && n <= 24u) {
         const uint32_t shift = kDictSizeBitsByLength[n];
-        const uint32_t word_id = (uint32_t)dist - max_distance - 1u;
+        const uint32_t word_id = (uint32_t)dist - word_from - 1u;
         const uint32_t transform_idx = word_id >> shift;
         if (transform_idx < (uint32_t)BROTLI_NUM_TRANSFORMS) {
           word_offset = kDictOffsetsByLength[n] + (word_id & mask_bits(shift)) * n;
@@ -2463,7 +2504,7 @@ __device__ __noinline__ __attribute__((aligned(256))) uint32_t lean_rec_commands
           word = w.total != 0u && w.total < quota && (int32_t)w.total <= mlen;
         }
       }
-      if (!word) { if (n > 63u) long_cmd = true; if (committed) stage = LS_POST_DISTANCE; break; }
+      if (!word && !from_cdict) { if (n > 63u) long_cmd = true; if (committed) stage = LS_POST_DISTANCE; break; }
     }
     if (!committed) {
       if (!(rec_lo & XR_IMPLICIT)) bl2--;
@@ -2479,6 +2520,14 @@ __device__ __noinline__ __attribute__((aligned(256))) uint32_t lean_rec_commands
       else if (ctx_regs) { p2 = p1; p1 = rdlane(ob, 0); }  // (else: both come out of memory when a literal asks for them)
       mlen -= (int32_t)w.total;
       P += w.total; quota -= w.total;
+    } else if (from_cdict) {  // (nothing is in flight here: flush() above.  Output position v < 0 is cdict_end[v]; the two bytes before P come out of memory when a literal asks)
+      if (push) { d3 = d2; d2 = d1; d1 = d0; d0 = dist; }
+      mlen -= (int32_t)n;
+      gcu8* const cdict_end = (gcu8*)(uintptr_t)((uint64_t)rfl(lds_ld32(LDS_HOT + 4u * LDS_HOT_CDICT_END)) | ((uint64_t)rfl(lds_ld32(LDS_HOT + 4u * LDS_HOT_CDICT_END + 4u)) << 32));
+      const int64_t v = (int64_t)P + (int64_t)lane - (int64_t)(uint32_t)dist;
+      if (lane < n) out[P + lane] = v < 0 ? cdict_end[v] : out[v];
+      ctx_regs = false;
+      P += n; quota -= n;
     } else {  // its load is issued now, its store when the next command gets here (its source may be what this one writes)
       if (push) { d3 = d2; d2 = d1; d1 = d0; d0 = dist; }
       mlen -= (int32_t)n;
@@ -2556,6 +2605,44 @@ __device__ __noinline__ void gang_took(HotArgs* args, const uint32_t took, const
   args->general_engine = (counts & 0xFFu) | (pen << 8) | (hold << 16);
 }
 
+// A copy whose source starts in the custom dictionary (state.rs:400-411; decode.rs:1861-1864 puts the dictionary in front of the
+// ring's position 0): byte i comes from output position v = P + i - distance, which is the dictionary's byte cdict_end[v] while
+// v < 0 and the stream's own output from there on -- bytes this copy has just written included, where the distance is shorter
+// than the copy.  A step takes at most `distance` bytes, so that what a step reads of the copy's own output an earlier step wrote:
+// 16 bytes a lane and up to 1 KiB a step where the distance allows (a piece that lies across position 0, and the copy's last one, byte
+// by byte), else a byte a lane.  The caller has every earlier byte in memory, has checked distance <= P + the dictionary's size and
+// n <= room in `out`.  A function of its own: the command loop's registers stay as they were.  (The one-wave loops make the copies
+// that do not repeat themselves in place; this is the checked stages' -- what they hand over, and the engines.)
+__device__ __noinline__ void cdict_copy(gu8* const out, gcu8* const cdict_end, const uint64_t P, const uint32_t distance, const uint32_t n) {
+  const uint32_t lane = lane_id();
+  gu8* const dst = out + P;
+  const int64_t v0 = (int64_t)P - (int64_t)distance;
+  if (distance >= 16u) {
+    const uint32_t step = (distance & ~15u) < 1024u ? (distance & ~15u) : 1024u;
+    for (uint32_t k = 0; k < n; k += step) {
+      const uint32_t i = k + (lane << 4);
+      if ((lane << 4) < step && i < n) {
+        const int64_t v = v0 + (int64_t)i;
+        if (i + 16u <= n && (v >= 0 || v + 16 <= 0)) {
+          const u32x4 t = *reinterpret_cast<const gu32x4*>(v < 0 ? cdict_end + v : (gcu8*)out + v);
+          *reinterpret_cast<gu32x4*>(dst + i) = t;
+        } else {
+          for (uint32_t b = 0; b < 16u && i + b < n; b++) dst[i + b] = v + (int64_t)b < 0 ? cdict_end[v + (int64_t)b] : out[v + (int64_t)b];
+        }
+      }
+    }
+    return;
+  }
+  const uint32_t step = distance;
+  for (uint32_t k = 0; k < n; k += step) {
+    const uint32_t i = k + lane;
+    if (lane < step && i < n) {
+      const int64_t v = v0 + (int64_t)i;
+      dst[i] = v < 0 ? cdict_end[v] : out[v];
+    }
+  }
+}
+
 // src/decode.rs:2330-2744 with a flat output buffer.
 //  * literals are collected one per lane (v_writelane) and stored 64 at a time;
 //  * a copy of <= 64 bytes is split in two: its load is issued when the command is decoded, its store when the
@@ -2586,7 +2673,8 @@ __device__ __noinline__ int process_commands(HotArgs* args) {
   // What only block switches need (block-type and block-length trees, number of block types, the block-type rings
   // of state.rs:429-435, where the tree groups and maps are) stays in LDS, put there by run_commands():
   enum { H_BT_TREE = 0, H_BL_TREE = 3, H_NBT = 6, H_CTX_MODES = 9, H_CTX_MAP = 10, H_DIST_CTX_MAP = 11, H_LIT_TREES = 12, H_CMD_TREES = 13,
-         H_DIST_TREES = 14, H_RING = 15 /* + 2 * category: second last, last block type */ };
+         H_DIST_TREES = 14, H_RING = 15 /* + 2 * category: second last, last block type */,
+         H_CDICT_SIZE = LDS_HOT_CDICT_SIZE /* the custom dictionary: its bytes in reach (0: none) */, H_CDICT_END = LDS_HOT_CDICT_END /* ... the address behind its last byte, two words */ };
 #define HOTC(k) rfl(lds_ld32(LDS_HOT + 4u * (uint32_t)(k)))
 #define BLOCK_SWITCH(cat, bl, res) do { \
     uint32_t t0_ = HOTC(H_RING + 2 * (cat)), t1_ = HOTC(H_RING + 2 * (cat) + 1); \
@@ -2829,7 +2917,6 @@ __device__ __noinline__ int process_commands(HotArgs* args) {
         }
         const uint32_t form_raw = LEAN_LD(L_SC_POS_HI), form = form_raw & 0xFFu;
         const bool declined = ((form_raw >> 8) & 1u) != 0u;
-        if (((form_raw >> 10) & 1u) != 0u) prefer_general = true;   // (the lean form stopped in front of a dictionary reference)
         if (use_remote) gang_took(args, took, form_raw);
         if (((form_raw >> 9) & 1u) != 0u) prefer_scan = true;   // (the path engine's regions were bound by their closure: a stream of few literals -- the scan engine's from here on)
         const uint64_t pos = origin + LEAN_LD(L_SC_POS_LO) - BitReader::skip_bits();
@@ -2837,6 +2924,9 @@ __device__ __noinline__ int process_commands(HotArgs* args) {
         br.seek(pos);
         const uint64_t P_before = P;
         P = (uint64_t)LEAN_LD(L_P_LO) | ((uint64_t)LEAN_LD(L_P_HI) << 32);
+        // (the lean form stopped in front of a dictionary reference: the general form's stream from here on -- unless that reference may be a copy out of a
+        // custom dictionary, which the window still reaches: the checked stages make that one copy, and the stream keeps the lean form and its gang)
+        if (((form_raw >> 10) & 1u) != 0u && (HOTC(H_CDICT_SIZE) == 0u || P >= (uint64_t)(uint32_t)max_backward)) prefer_general = true;
         quota = LEAN_LD(L_QUOTA); mlen = (int32_t)LEAN_LD(L_MLEN);
         bl0 = LEAN_LD(L_BL0); bl1 = LEAN_LD(L_BL1); bl2 = LEAN_LD(L_BL2);
         d0 = (int32_t)LEAN_LD(L_D0); d1 = (int32_t)LEAN_LD(L_D1); d2 = (int32_t)LEAN_LD(L_D2); d3 = (int32_t)LEAN_LD(L_D3);
@@ -3208,6 +3298,31 @@ general_distance:
 general_post_distance:
     max_distance = (P < (uint64_t)(uint32_t)max_backward) ? (int32_t)P : max_backward;
     if (distance_code > max_distance) {
+      // Beyond the stream's own output.  With a custom dictionary attached the max distance counts its bytes too (decode.rs:2583-2589:
+      // min(P + size, max_backward)), which moves the static dictionary's word numbers, and a distance within it is a copy whose
+      // source starts in that dictionary.  Every fast loop and engine hands such a command over to here (they test against P alone).
+      const uint32_t cdict_size = HOTC(H_CDICT_SIZE);
+      if (cdict_size != 0u) {
+        const uint64_t reach = P + (uint64_t)cdict_size;
+        max_distance = reach < (uint64_t)(uint32_t)max_backward ? (int32_t)reach : max_backward;
+        if (distance_code <= max_distance) {
+          if (distance_context == 0) { d3 = d2; d2 = d1; d1 = d0; d0 = distance_code; }
+          mlen -= copy_len;
+          if (mlen < 0) STOP(P + (uint32_t)copy_len >= next_boundary ? E_BLOCK_LENGTH_1 : E_BLOCK_LENGTH_2);
+          const uint64_t room = out_cap - P;
+          uint32_t n = (uint32_t)copy_len;
+          const bool clipped = (uint64_t)n > room;
+          if (clipped) n = (uint32_t)room;
+          FLUSH_LITERALS();
+          FLUSH_PENDING();
+          gcu8* const cdict_end = (gcu8*)(uintptr_t)((uint64_t)HOTC(H_CDICT_END) | ((uint64_t)HOTC(H_CDICT_END + 1) << 32));
+          cdict_copy(out, cdict_end, P, (uint32_t)distance_code, n);
+          ctx_src = CTX_MEMORY;
+          P += n;
+          if (clipped) STOP(E_NEEDS_MORE_OUTPUT);
+          goto command_done;
+        }
+      }
       if (distance_code > 0x7FFFFFFC) STOP(E_DISTANCE);
       if (copy_len < 4 || copy_len > 24) STOP(E_DICTIONARY);
       uint32_t shift = kDictSizeBitsByLength[copy_len];
@@ -3386,9 +3501,11 @@ __device__ __forceinline__ int run_commands(Stream& s, const BrotliAmdResume* mi
   h.postfix_bits = s.postfix_bits; h.num_direct = s.num_direct;
   lds_sync();
   if (lane_id() == 0) {  // the cold part of the loop's state (see HOTC in process_commands)
-    const uint32_t cold[21] = {s.bt_tree0, s.bt_tree1, s.bt_tree2, s.bl_tree0, s.bl_tree1, s.bl_tree2, s.nbt0, s.nbt1, s.nbt2,
-                               s.ctx_modes, s.ctx_map, s.dist_ctx_map, s.lit_trees, s.cmd_trees, s.dist_trees, 1, 0, 1, 0, 1, 0};
-    for (int k = 0; k < 21; k++) lds_st32(LDS_HOT + 4u * (uint32_t)k, cold[k]);
+    // (the last three: the custom dictionary -- its size, H_CDICT_SIZE, and the address of its end; only a distance beyond the stream's own output asks for them)
+    const uint32_t cold[24] = {s.bt_tree0, s.bt_tree1, s.bt_tree2, s.bl_tree0, s.bl_tree1, s.bl_tree2, s.nbt0, s.nbt1, s.nbt2,
+                               s.ctx_modes, s.ctx_map, s.dist_ctx_map, s.lit_trees, s.cmd_trees, s.dist_trees, 1, 0, 1, 0, 1, 0,
+                               s.cdict_size, (uint32_t)(uintptr_t)s.cdict_end, (uint32_t)((uint64_t)(uintptr_t)s.cdict_end >> 32)};
+    for (int k = 0; k < 24; k++) lds_st32(LDS_HOT + 4u * (uint32_t)k, cold[k]);
   }
   lds_sync();
   h.resume_out = (uint64_t)(uintptr_t)&st->resume;
@@ -3512,8 +3629,8 @@ __device__ __forceinline__ void allocate_ring(Stream& s, const BitReader& br) {
       if ((b & 3u) == 3u) is_last = 1;
     }
   }
-  if (is_last && !(s.flags & BROTLI_AMD_FLAG_NO_CANNY)) {
-    while ((int64_t)rb >= ((int64_t)s.mlen + 16) * 2 && rb > 32) rb >>= 1;
+  if (is_last && !(s.flags & BROTLI_AMD_FLAG_NO_CANNY)) {   // (a custom dictionary -- what the window holds of it -- takes its room in the ring: decode.rs:1844)
+    while ((int64_t)rb >= ((int64_t)s.cdict_size + (int64_t)s.mlen + 16) * 2 && rb > 32) rb >>= 1;
   }
   s.rb_size = rb;
   s.next_boundary = (s.P / rb + 1) * rb;
@@ -3564,6 +3681,10 @@ __device__ __forceinline__ int decode_stream(Stream& s, bool have_header, uint64
     store_resume(s, br, &st->resume);
   }
   s.max_backward = (int32_t)((1u << s.window_bits) - 16u);
+  // A custom dictionary longer than the window keeps its tail (decode.rs:1831-1839).  The reference takes max_backward - size from
+  // the size before that (decode.rs:2954-2955): negative then, and every position's max distance is max_backward -- which
+  // min(P + size, max_backward) with the tail's size says as well (decode.rs:2583-2589).
+  if (s.cdict_size > (uint32_t)s.max_backward) s.cdict_size = (uint32_t)s.max_backward;
 
   for (;;) {
     // METABLOCK_BEGIN (state.rs:422-450)
@@ -3878,6 +3999,9 @@ __global__ __launch_bounds__(1024, 4) void brotli_amd_decode_kernel(const Brotli
     s.out = as_global<gu8>(d.out); s.out_cap = d.out_cap;
     s.dict = as_global<gcu8>(dict);
     s.in_bytes = as_global<gcu8>(d.in);
+    // (no window is longer than 1 << 30: more than that of a dictionary is never in reach)
+    s.cdict_end = as_global<gcu8>(d.dict != nullptr && d.dict_size != 0 ? d.dict + d.dict_size : nullptr);
+    s.cdict_size = s.cdict_end == nullptr ? 0u : d.dict_size > (1ull << 30) ? (1u << 30) : (uint32_t)d.dict_size;
     s.flags = d.flags;
     s.lut_vgpr = lut; s.bl_vgpr = bl;
     s.num_metablocks = 0; s.num_spilled = 0; s.num_commands = 0; s.engine_commands = 0; s.general_engine = 0;

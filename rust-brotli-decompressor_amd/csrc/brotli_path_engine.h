@@ -653,7 +653,9 @@ __device__ __noinline__ void pe_dict_word(const uint32_t pb, gu8* const out, gcu
   const uint32_t lane = lane_id();
   PeStream sw = pe_st_load(pb);
   const uint32_t dd = pe_ctl_ld(pb, PEC_DICTD), wn_ = pe_ctl_ld(pb, PEC_DICTN), kd = pe_ctl_ld(pb, PEC_DICTK);
-  const uint32_t maxd = sw.P < (uint64_t)(uint32_t)sw.max_backward ? (uint32_t)sw.P : (uint32_t)sw.max_backward;
+  // (the max distance with a custom dictionary's bytes counted -- decode.rs:2583-2589, see process_commands: a distance into that dictionary is no word, it goes to the checked loop below)
+  const uint64_t reach = sw.P + (uint64_t)rfl(lds_ld32(LDS_HOT + 4u * LDS_HOT_CDICT_SIZE));
+  const uint32_t maxd = reach < (uint64_t)(uint32_t)sw.max_backward ? (uint32_t)reach : (uint32_t)sw.max_backward;
   bool word = false; WordShape w = {}; uint32_t word_offset = 0;
   if (dd > maxd && wn_ >= 4u && wn_ <= 24u) {
     const uint32_t shift = kDictSizeBitsByLength[wn_];
@@ -1843,13 +1845,18 @@ pe_pass:
       bool isw = false, plainw = false;   // the copy is a dictionary reference; ... one that goes out inside this pass
       uint32_t wdesc = 0, wdelta = 0, dex = 0;   // the word (offset | transform << 17 | length << 24); its length less the copy's; that, summed over the commands in front of this one
       if (PE_DICT && pe_ctl_ld(pb, PEC_DCAND) != 0u) {
+        // (a custom dictionary's bytes count for the max distance, and so for the words' numbers: decode.rs:2583-2589 -- `wmax`.  A distance INTO that dictionary
+        // is beyond the stream's own output like a word's, and treated like a word that is not a plain one: its command's literals go out, the pass ends behind
+        // them, pe_dict_word finds no word and the checked loop takes the command from its distance on -- it pushes the distance, the resolve does not)
+        const uint32_t cdict_size = lds_ld32(LDS_HOT + 4u * LDS_HOT_CDICT_SIZE);
         auto classify = [&](const bool plain_ok) {
           const uint64_t pk = st.P + (uint64_t)(c_out + out_excl + ins + dex);
           const uint32_t maxd = pk < (uint64_t)(uint32_t)st.max_backward ? (uint32_t)pk : (uint32_t)st.max_backward;
+          const uint32_t wmax = pk + cdict_size < (uint64_t)(uint32_t)st.max_backward ? (uint32_t)pk + cdict_size : (uint32_t)st.max_backward;
           isw = (bool)((uint32_t)active & (uint32_t)!odd & (uint32_t)!big & (uint32_t)(kind == SCK_EXPLICIT) & (uint32_t)(val > maxd));
           plainw = false; wdesc = 0; wdelta = 0;
-          if (plain_ok && isw && copy >= 4u && copy <= 24u) {
-            const uint32_t shift = kDictSizeBitsByLength[copy], id = val - maxd - 1u, tix = id >> shift;
+          if (plain_ok && isw && val > wmax && copy >= 4u && copy <= 24u) {
+            const uint32_t shift = kDictSizeBitsByLength[copy], id = val - wmax - 1u, tix = id >> shift;
             if (tix < (uint32_t)BROTLI_NUM_TRANSFORMS) {
               const WordShape w = word_shape(copy, tix);
               if (w.total != 0u) { plainw = true; wdelta = w.total - copy; wdesc = (kDictOffsetsByLength[copy] + (id & mask_bits(shift)) * copy) | (tix << 17) | (copy << 24); }

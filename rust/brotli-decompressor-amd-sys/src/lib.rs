@@ -6,8 +6,12 @@
 //! reference crate knows: [`Decompressor`] (`src/reader.rs:91-182`) and [`DecompressorWriter`]
 //! (`src/writer.rs:104-199`), with the reference's constructor signatures and error kinds.
 //!
-//! What does not exist on this path: custom (LZ77 prefix) dictionaries (`new_with_custom_dict`), custom
-//! allocators for the decoder's tables (they live in the GPU's LDS), `no_std`.
+//! Custom (LZ77 prefix) dictionaries exist on this path: `Decompressor::new_with_custom_dict` and
+//! `DecompressorWriter::new_with_custom_dictionary` over `BrotliAmdDecoderAttachDictionary`, and the batch
+//! forms `BrotliAmdBatchDecodeDeviceDict` / `BrotliAmdBatchDecodeHostDict` (`include/brotli/batch.h`) -- like
+//! the rest of this crate as source only, never compiled here.
+//! What does not exist on this path: custom allocators for the decoder's tables (they live in the GPU's
+//! LDS), `no_std`.
 #![allow(non_camel_case_types, non_snake_case)]
 
 use libc::{c_char, c_int, c_void, size_t};
@@ -157,6 +161,18 @@ extern "C" {
         batch: *mut BrotliAmdBatch, n: u32, input: *const *const u8, in_sizes: *const size_t, output: *const *mut u8,
         out_caps: *const size_t, flags: u32, results: *mut BrotliAmdResult,
     ) -> c_int;
+    /// `BrotliAmdBatchDecodeDevice` plus per-stream device pointers to custom dictionaries and their sizes (null / 0: none)
+    pub fn BrotliAmdBatchDecodeDeviceDict(
+        batch: *mut BrotliAmdBatch, n: u32, d_in: *const *const c_void, in_sizes: *const size_t, d_out: *const *mut c_void,
+        out_caps: *const size_t, d_dicts: *const *const c_void, dict_sizes: *const size_t, flags: u32, hip_stream: *mut c_void,
+    ) -> c_int;
+    /// `BrotliAmdBatchDecodeHost` plus per-stream host pointers to custom dictionaries; each distinct one is uploaded once
+    pub fn BrotliAmdBatchDecodeHostDict(
+        batch: *mut BrotliAmdBatch, n: u32, input: *const *const u8, in_sizes: *const size_t, output: *const *mut u8,
+        out_caps: *const size_t, dicts: *const *const u8, dict_sizes: *const size_t, flags: u32, results: *mut BrotliAmdResult,
+    ) -> c_int;
+    /// one custom dictionary for a streaming instance that has not decoded yet (the bytes are copied); 1 = attached
+    pub fn BrotliAmdDecoderAttachDictionary(state: *mut BrotliDecoderState, data: *const u8, size: size_t) -> c_int;
     pub fn BrotliAmdBatchLastKernelMs(batch: *mut BrotliAmdBatch) -> f32;
     pub fn BrotliAmdBatchLastSecondPassCount(batch: *mut BrotliAmdBatch) -> u32;
     pub fn BrotliAmdBatchLastGang(batch: *mut BrotliAmdBatch) -> u32;
@@ -254,6 +270,15 @@ impl<R: Read> Decompressor<R> {
             done: false,
         }
     }
+    /// the stream was made for a custom (LZ77 prefix) dictionary (reader.rs:103-162); an empty one is none
+    pub fn new_with_custom_dict(r: R, buffer_size: usize, dict: Vec<u8>) -> Self {
+        let d = Self::new(r, buffer_size);
+        if !dict.is_empty() {
+            let ok = unsafe { BrotliAmdDecoderAttachDictionary(d.state.0, dict.as_ptr(), dict.len()) };
+            assert!(ok != 0, "BrotliAmdDecoderAttachDictionary refused the dictionary");
+        }
+        d
+    }
     pub fn get_ref(&self) -> &R {
         &self.input
     }
@@ -335,6 +360,15 @@ impl<W: Write> DecompressorWriter<W> {
             state: State::new().expect("no HIP device: this decode path has no CPU fallback"),
             finished: false,
         }
+    }
+    /// the stream was made for a custom (LZ77 prefix) dictionary (writer.rs:115-171); an empty one is none
+    pub fn new_with_custom_dictionary(w: W, buffer_size: usize, dict: Vec<u8>) -> Self {
+        let d = Self::new(w, buffer_size);
+        if !dict.is_empty() {
+            let ok = unsafe { BrotliAmdDecoderAttachDictionary(d.state.0, dict.as_ptr(), dict.len()) };
+            assert!(ok != 0, "BrotliAmdDecoderAttachDictionary refused the dictionary");
+        }
+        d
     }
     pub fn get_ref(&self) -> &W {
         self.output.as_ref().unwrap()

@@ -332,16 +332,19 @@ def greedy_commands(data, min_match=4, max_dist=1 << 16, start=0, history=b""):
     return cmds
 
 
-def emit_compressed(w, commands, plan, is_last, prev=b""):
+def emit_compressed(w, commands, plan, is_last, prev=b"", dictionary=b""):
     """commands: [(insert bytes, copy_len, distance)]; distance 0 with copy_len 0 only as the final literals-only command
     (it is written with copy length 2 and an implicit distance that the decoder never executes: the metablock is complete
     after its literals).  `prev` = the stream's output so far (copies may reach into it; its last two bytes are the literal
-    context of the first literal).  Returns the metablock's own output bytes."""
+    context of the first literal).  `dictionary` = a custom (LZ77 prefix) dictionary the stream is decoded with: its bytes lie in front
+    of the stream's first output byte for copies alone -- a copy may start in it and run on into the output -- while the first two
+    literals of the stream have context (0, 0) whatever its last bytes are.  Returns the metablock's own output bytes."""
     npf, ndir = plan.npostfix, plan.ndirect
     # --- the data and symbol sequences
     out = bytearray()
     lits, cmd_syms, dist_syms = [], [], []
-    history = bytearray(2 - min(2, len(prev))) + bytearray(prev)
+    pad = 2 - min(2, len(prev))  # (zero bytes that stand for the context in front of the stream's first byte: not output)
+    history = bytearray(pad) + bytearray(prev)
     start = len(history)
     for ins, clen, dist in commands:
         for b in ins:
@@ -358,7 +361,8 @@ def emit_compressed(w, commands, plan, is_last, prev=b""):
         cmd_syms.append((command_symbol(ic, cc, False), iv, ib, cv, cb))
         dist_syms.append((distance_symbol(dist, npf, ndir), min(3, cc) if cc <= 2 else 3))
         for _ in range(clen):
-            history.append(history[-dist])
+            at = len(history) - dist
+            history.append(dictionary[at - pad] if dictionary and at < pad else history[-dist])  # (at - pad < 0: counted from the dictionary's end)
     mlen = len(history) - start
     # --- block splits
     def expand(blocks, n):

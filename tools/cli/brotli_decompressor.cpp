@@ -1,6 +1,6 @@
-// brotli-decompressor [in [out]] -- the reference's command-line tool (src/bin/brotli-decompressor.rs:325-359) on top
+// brotli-decompressor [-dict=FILE] [--] [in [out]] -- the reference's command-line tool (src/bin/brotli-decompressor.rs:325-359) on top
 // of include/brotli/reader.hpp: stdin/stdout by default, 64 KiB buffers, "Invalid Data"/"Unexpected EOF" on stderr.
-// (The reference's -dict= option is a custom dictionary: not part of the C ABI, not supported.)
+// -dict=FILE: the stream was made for a custom (LZ77 prefix) dictionary, the file's bytes (at most 50331660 of them, as in the reference).
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -17,11 +17,27 @@ struct FileSource {
 int main(int argc, char** argv) {
   FILE* in = stdin;
   FILE* out = stdout;
-  if (argc > 1 && std::strncmp(argv[1], "-dict=", 6) == 0) { std::fprintf(stderr, "custom dictionaries are not supported\n"); return 2; }
-  if (argc > 1 && !(in = std::fopen(argv[1], "rb"))) { std::perror(argv[1]); return 1; }
-  if (argc > 2 && !(out = std::fopen(argv[2], "wb"))) { std::perror(argv[2]); return 1; }
+  std::vector<uint8_t> dictionary;
+  bool double_dash = false;
+  int files = 0;
+  for (int a = 1; a < argc; a++) {
+    if (!double_dash && std::strcmp(argv[a], "--") == 0) { double_dash = true; continue; }
+    if (!double_dash && std::strncmp(argv[a], "-dict=", 6) == 0) {
+      FILE* df = std::fopen(argv[a] + 6, "rb");
+      if (!df) { std::perror(argv[a] + 6); return 1; }
+      uint8_t piece[65536];
+      for (size_t n; (n = std::fread(piece, 1, sizeof piece, df)) != 0;) dictionary.insert(dictionary.end(), piece, piece + n);
+      std::fclose(df);
+      if (dictionary.size() > 50331660u) { std::fprintf(stderr, "Dictionary larger than 50331660\n"); return 1; }
+      continue;
+    }
+    if (files == 0) { if (!(in = std::fopen(argv[a], "rb"))) { std::perror(argv[a]); return 1; } }
+    else if (files == 1) { if (!(out = std::fopen(argv[a], "wb"))) { std::perror(argv[a]); return 1; } }
+    else { std::fprintf(stderr, "Cannot specify more than 2 filename args (input, output)\n"); return 1; }
+    files++;
+  }
   try {
-    brotli_amd::Decompressor<FileSource> r(FileSource{in}, 65536);
+    brotli_amd::Decompressor<FileSource> r(FileSource{in}, 65536, dictionary);
     std::vector<uint8_t> buf(65536);
     for (;;) {
       size_t n = r.read(buf.data(), buf.size());

@@ -95,13 +95,20 @@ s_add_i32 s93, s93, s97
 
 def word_test(p, q, fail, src_lo, src_hi, within):
     """The command is not a plain copy.  A word of the static dictionary as it stands (decode.rs:2593-2640 with transform 0: every word of the
-    reference's alice29 is one)?  distance s93 beyond min(P, max_backward), 4 <= length s92 <= 24, (distance - max_distance - 1) >> bits[length] == 0,
+    reference's alice29 is one)?  distance s93 beyond the max distance s95 = min(P + the custom dictionary's size, max_backward) (decode.rs:2583-2589; the size: lane 10 of the
+    parameters, 0 = none; a distance into that dictionary: {fail}, the compiled loop copies it), 4 <= length s92 <= 24, (distance - max_distance - 1) >> bits[length] == 0,
     length < quota, the distance block's count s94 there -> its address in {src_lo}:{src_hi}; a distance within the window: {within} (see overlap_test); anything else: {fail}.  (p, q as plain_test; lane n of
     %[wtab]: kDictOffsetsByLength[n] | kDictSizeBitsByLength[n] << 24; lanes 6 / 7 of the parameters: the dictionary's address)"""
     return f"""
 s_min_u32 s95, {p}, %[maxb]
 s_cmp_le_u32 s93, s95
 s_cbranch_scc1 {within}f
+v_readlane_b32 s96, %[params], 10
+s_add_u32 s95, {p}, s96
+s_cselect_b32 s95, -1, s95
+s_min_u32 s95, s95, %[maxb]
+s_cmp_le_u32 s93, s95
+s_cbranch_scc1 {fail}f
 s_cmp_gt_u32 s93, 0x7ffffffc
 s_cbranch_scc1 {fail}f
 s_sub_u32 s96, s92, 4
