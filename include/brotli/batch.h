@@ -14,6 +14,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "decode.h" /* BrotliDecoderResult, the states of a stream set */
+
 #if defined(__cplusplus)
 extern "C" {
 #endif
@@ -137,6 +139,67 @@ BROTLI_DEC_API uint64_t BrotliAmdDecoderDeviceCommands(const struct BrotliDecode
  * Returns 1 on a fresh instance; size == 0 is a no-op that returns 1.  Returns 0 for a NULL state, NULL data with size != 0, a second
  * dictionary, and once BrotliDecoderIsUsed is true.  The one-shot functions of decode.h have no dictionary, as in src/ffi/mod.rs:120. */
 BROTLI_DEC_API int BrotliAmdDecoderAttachDictionary(struct BrotliDecoderStateStruct* state, const uint8_t* data, size_t size);
+
+/* ---- Stream sets: many streaming decoders advanced by one launch ----
+ *
+ * BrotliDecoderDecompressStream (decode.h) gives every state a batch object of one stream: a call is one blocking copy of its chunk to the
+ * device, one launch of one stream, one wait and one blocking copy back.  A server with hundreds of open streams, each handed a few KiB at a
+ * time, pays that per stream per round.  A stream set steps n states in ONE call:
+ *
+ *   BrotliAmdStreamSetDecompress(set, n, states, available_in, next_in, available_out, next_out, total_out, results)
+ *
+ * THE CONTRACT: for every i, states[i], the i-th entries of the five arrays and results[i] end up exactly as ONE
+ *   results[i] = BrotliDecoderDecompressStream(states[i], &available_in[i], &next_in[i], &available_out[i], &next_out[i],
+ *                                              total_out ? &total_out[i] : NULL)
+ * would have left them: the result and the bytes consumed; the bytes written, and which; the latched error code and the error string;
+ * BrotliDecoderIsFinished / IsUsed / HasMoreOutput / TakeOutput afterwards; trailing input handed back behind the end of a stream; an attached
+ * custom dictionary; the state's own allocator callbacks for its host memory.  A state may be stepped through a set in one call and alone in
+ * the next: the sequence behaves as one sequence of solo calls.  The states of a call are independent: an error in one changes nothing for
+ * the others.
+ *
+ * How a call runs:
+ *  1. per state, on the host: the argument and slice checks, the latched-error return and the owed-output rule of the solo function.  States
+ *     that end there never reach the device: finished ones, ones with a latched error, ones given no input, ones whose owed output did not fit.
+ *  2. the chunks of all remaining states are packed into one pinned staging buffer and go to the device in ONE transfer; one ragged-copy launch
+ *     (csrc/brotli_copy_kernels.hip) appends each chunk to its state's input buffer.
+ *  3. ONE launch over the set's own batch object of max_states streams decodes all of them -- fresh and resumed states, with and without a
+ *     dictionary, mixed; block shapes, gangs and pools are the batch planner's for that many streams.
+ *  4. states whose device output buffer was full go through the solo function's trim-and-grow rule and are launched again -- they alone.
+ *  5. one ragged-copy launch gathers every state's new output into staging, ONE transfer brings it back, the host appends each part to its
+ *     state's queue, and the solo function's tail (what fits is handed over, the result follows) runs per state.
+ * If no state needs the device, nothing is launched or copied.  Staging is bounded (64 MiB in each direction): a chunk or an output part larger
+ * than that travels by a copy of its own, and parts that add up to more go in several transfers.
+ *
+ * Everything runs on the null stream, as the solo path does.  The set binds to the HIP device that is current at its first call that needs
+ * one, as a state does; a state first used through a set is bound to the set's device and gets no batch object of its own until it is first
+ * stepped alone.  One thread at a time per set, and per state.
+ *
+ * The call as a whole fails -- a negative value, and nothing is touched -- for a NULL set, NULL states, NULL results or a NULL one among the four
+ * in/out arrays, a NULL entry in states, n > max_states, the same state twice, and a state already bound to another device than the set's.
+ * n == 0 returns 0.  Otherwise it returns 0, whatever the states' results: without a usable device the states that needed one end as the solo
+ * call ends them -- BROTLI_DECODER_RESULT_ERROR, BROTLI_DECODER_ERROR_UNREACHABLE and the same error text. */
+typedef struct BrotliAmdStreamSet BrotliAmdStreamSet;
+/* needs no device; NULL only when out of memory (max_states == 0 counts as 1) */
+BROTLI_DEC_API BrotliAmdStreamSet* BrotliAmdStreamSetCreate(uint32_t max_states);
+/* the states stay the caller's: they are not destroyed, and may be stepped alone or through another set of the same device afterwards */
+BROTLI_DEC_API void BrotliAmdStreamSetDestroy(BrotliAmdStreamSet* set);
+BROTLI_DEC_API int BrotliAmdStreamSetDecompress(BrotliAmdStreamSet* set, uint32_t n, struct BrotliDecoderStateStruct* const* states,
+                                               size_t* available_in, const uint8_t** next_in, size_t* available_out, uint8_t** next_out,
+                                               size_t* total_out /* n entries or NULL */, BrotliDecoderResult* results /* n entries */);
+/* decode launches of the last BrotliAmdStreamSetDecompress: 0 where no state needed the device, 1 as a rule, more where states had to grow
+ * their device output buffer (step 4) */
+BROTLI_DEC_API uint32_t BrotliAmdStreamSetLastLaunches(BrotliAmdStreamSet* set);
+/* host <-> device copies of payload bytes (chunks in, output back) in it: at most 2 where one launch did and everything fitted the staging;
+ * a dictionary's upload at a state's first step is not counted */
+BROTLI_DEC_API uint32_t BrotliAmdStreamSetLastTransfers(BrotliAmdStreamSet* set);
+
+/* Test hook: the ragged copy kernel alone (csrc/brotli_copy_kernels.hip).  Host arrays of n DEVICE pointers and n lengths: segment i is
+ * lens[i] bytes from d_src[i] to d_dst[i], any alignment, any length, 0 included; the segments do not overlap each other.  One launch on the
+ * null stream, and a wait.  No byte outside [d_dst[i], d_dst[i] + lens[i]) is written; nothing outside the 16-byte-aligned span around
+ * [d_src[i], d_src[i] + lens[i]) is read.  Returns 0 on success. */
+BROTLI_DEC_API int BrotliAmdDebugRaggedCopy(uint32_t n, const void* const* d_src, void* const* d_dst, const size_t* lens);
+/* ... and the bytes of destination in one of its tiles (the unit in which the blocks of a launch share the work) */
+BROTLI_DEC_API uint32_t BrotliAmdDebugRaggedCopyTile(void);
 
 /* Text of the last HIP/runtime failure on this thread ("" if none). */
 BROTLI_DEC_API const char* BrotliAmdLastError(void);

@@ -32,6 +32,8 @@ BATCH_H_SYMBOLS = [
     "BrotliAmdBatchCreate", "BrotliAmdBatchDestroy", "BrotliAmdBatchDecodeDevice", "BrotliAmdBatchRelaunch", "BrotliAmdBatchWait",
     "BrotliAmdBatchDecodeHost", "BrotliAmdBatchLastKernelMs", "BrotliAmdBatchLastSecondPassCount", "BrotliAmdBatchLastGang", "BrotliAmdBatchLastPool", "BrotliAmdBatchLastProbeMs", "BrotliAmdDebugPlanGangs", "BrotliAmdLastError", "BrotliAmdLastNote", "BrotliAmdDebugBuildTree", "BrotliAmdDecoderDeviceCommands",
     "BrotliAmdBatchDecodeDeviceDict", "BrotliAmdBatchDecodeHostDict", "BrotliAmdDecoderAttachDictionary",
+    "BrotliAmdStreamSetCreate", "BrotliAmdStreamSetDestroy", "BrotliAmdStreamSetDecompress", "BrotliAmdStreamSetLastLaunches",
+    "BrotliAmdStreamSetLastTransfers", "BrotliAmdDebugRaggedCopy", "BrotliAmdDebugRaggedCopyTile",
 ]
 
 
@@ -105,6 +107,16 @@ def load_library():
         L.BrotliAmdBatchDecodeHostDict.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, u32, vp]
         L.BrotliAmdDecoderAttachDictionary.argtypes = [vp, vp, sz]
         L.BrotliAmdDecoderAttachDictionary.restype = ctypes.c_int
+    if hasattr(L, "BrotliAmdStreamSetCreate"):   # (stream sets and the ragged copy: an older build of the library, loaded for an A/B, has none)
+        L.BrotliAmdStreamSetCreate.restype = vp
+        L.BrotliAmdStreamSetCreate.argtypes = [u32]
+        L.BrotliAmdStreamSetDestroy.argtypes = [vp]
+        L.BrotliAmdStreamSetDecompress.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp]
+        for name in ("BrotliAmdStreamSetLastLaunches", "BrotliAmdStreamSetLastTransfers"):
+            getattr(L, name).restype = u32
+            getattr(L, name).argtypes = [vp]
+        L.BrotliAmdDebugRaggedCopy.argtypes = [u32, vp, vp, vp]
+        L.BrotliAmdDebugRaggedCopyTile.restype = u32
     L.BrotliAmdBatchLastKernelMs.restype = ctypes.c_float
     L.BrotliAmdBatchLastKernelMs.argtypes = [vp]
     L.BrotliAmdBatchLastSecondPassCount.restype = ctypes.c_uint32
@@ -316,6 +328,55 @@ class DecoderState:
 
     def has_more_output(self):
         return bool(self._L.BrotliDecoderHasMoreOutput(self._h))
+
+
+class StreamSet:
+    """BrotliAmdStreamSet (batch.h): steps many DecoderStates in one call -- one transfer in, one launch, one transfer back."""
+
+    def __init__(self, max_states):
+        self._L = load_library()
+        self._h = self._L.BrotliAmdStreamSetCreate(max_states)
+        if not self._h:
+            raise MemoryError("BrotliAmdStreamSetCreate")
+        self.max_states = max_states
+
+    def close(self):
+        if self._h:
+            self._L.BrotliAmdStreamSetDestroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def decompress(self, states, datas, out_caps):
+        """One BrotliAmdStreamSetDecompress call: states[i] (a DecoderState) is given datas[i] and room for out_caps[i] bytes.
+        -> [(result, bytes consumed, output bytes), ...], each what states[i].decompress_stream(datas[i], out_caps[i]) returns."""
+        n = len(states)
+        if len(datas) != n or len(out_caps) != n:
+            raise ValueError("datas and out_caps: one entry per state")
+        srcs = [ctypes.create_string_buffer(bytes(d), max(1, len(d))) for d in datas]
+        outs = [ctypes.create_string_buffer(max(1, c)) for c in out_caps]
+        a_st = (ctypes.c_void_p * max(1, n))(*[s._h for s in states])
+        a_ai = (ctypes.c_size_t * max(1, n))(*[len(d) for d in datas])
+        a_ni = (ctypes.c_void_p * max(1, n))(*[ctypes.addressof(b) for b in srcs])
+        a_ao = (ctypes.c_size_t * max(1, n))(*out_caps)
+        a_no = (ctypes.c_void_p * max(1, n))(*[ctypes.addressof(b) for b in outs])
+        a_tot = (ctypes.c_size_t * max(1, n))()
+        a_res = (ctypes.c_int * max(1, n))()
+        if self._L.BrotliAmdStreamSetDecompress(self._h, n, a_st, a_ai, a_ni, a_ao, a_no, a_tot, a_res) != 0:
+            raise RuntimeError("BrotliAmdStreamSetDecompress failed: " + last_error())
+        return [(a_res[i], len(datas[i]) - a_ai[i], outs[i].raw[:out_caps[i] - a_ao[i]]) for i in range(n)]
+
+    def last_launches(self):
+        """decode launches of the last decompress(): 0 where no state needed the device, 1 as a rule"""
+        return int(self._L.BrotliAmdStreamSetLastLaunches(self._h))
+
+    def last_transfers(self):
+        """host <-> device copies of payload bytes in the last decompress()"""
+        return int(self._L.BrotliAmdStreamSetLastTransfers(self._h))
 
 
 class Decompressor:

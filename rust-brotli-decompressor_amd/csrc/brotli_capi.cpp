@@ -35,6 +35,10 @@ extern "C" hipError_t brotli_amd_launch_decode(const BrotliAmdStreamDesc* descs,
 extern "C" hipError_t brotli_amd_launch_decode_gang(const BrotliAmdStreamDesc* descs, BrotliAmdStreamStatus* status, uint32_t n_streams,
                                                     uint32_t* queue, uint8_t* scratch, uint64_t scratch_per_block, uint32_t grid,
                                                     uint32_t lds_arena_bytes, const uint8_t* dict, hipStream_t stream, int waves_per_block);
+// (csrc/brotli_copy_kernels.hip: n segments of any alignment and length in one launch; max_bytes: what their lengths add up to at most, 0 unknown)
+extern "C" hipError_t brotli_amd_launch_ragged_copy(const BrotliAmdCopySeg* d_segs, uint32_t n, hipStream_t stream);
+extern "C" hipError_t brotli_amd_launch_ragged_copy_sized(const BrotliAmdCopySeg* d_segs, uint32_t n, uint64_t max_bytes, hipStream_t stream);
+extern "C" uint32_t brotli_amd_copy_tile_bytes(void);
 extern "C" uint32_t brotli_amd_lds_fixed_bytes(void);
 extern "C" uint32_t brotli_amd_lds_helper_bytes(uint32_t waves);
 extern "C" const uint8_t brotli_amd_dictionary[];  // dict_blob.c: data/dictionary.bin, 122784 bytes
@@ -438,7 +442,9 @@ int retry_with_larger_arenas(BrotliAmdBatch* b) {
     for (uint32_t j = 0; j < m; j++) {
       BrotliAmdStreamDesc d = b->h_descs[idx[j]];
       d.flags = ((last ? d.flags & ~BROTLI_AMD_FLAG_NO_SPILL : d.flags) & ~(BROTLI_AMD_FLAG_ENGINE_ONLY | BROTLI_AMD_FLAG_DEFER)) | BROTLI_AMD_FLAG_RESUME;
-      d.resume = b->h_status[idx[j]].resume;
+      // (a stream sent back unread -- BROTLI_AMD_FLAG_DEFER -- reports no boundary at all: one that came RESUMED, a streaming state in a stream set's launch,
+      // goes on from the boundary it came with, not from byte 0, which its buffers may no longer hold)
+      if (b->h_status[idx[j]].resume.window_bits != 0u || !(b->h_descs[idx[j]].flags & BROTLI_AMD_FLAG_RESUME)) d.resume = b->h_status[idx[j]].resume;
       b->h_retry_descs[j] = d;
     }
     if (run_retry_descs(b, m, arena, grid_max, waves) != 0) return -1;
@@ -1187,55 +1193,176 @@ bool trim_buffers(BrotliDecoderState* s, bool eager = false) {
   return true;
 }
 
+// Room for n more bytes behind what the caller has not taken yet (the state's own allocator).
+bool reserve_outq(BrotliDecoderState* s, size_t n) {
+  if (s->outq_len + n <= s->outq_cap) return true;
+  size_t ncap = std::max(s->outq_cap * 2, s->outq_len + n);
+  uint8_t* nq = static_cast<uint8_t*>(st_alloc(s, ncap));
+  if (!nq) return false;
+  if (s->outq_len) std::memcpy(nq, s->outq, s->outq_len);
+  st_free(s, s->outq);
+  s->outq = nq; s->outq_cap = ncap;
+  return true;
+}
+
 // Copies what the reference would have flushed by now off the device, behind what the caller has not taken yet.
 // 0 = ok, 1 = HIP failure, 2 = allocation failure
 int fetch_output(BrotliDecoderState* s, uint64_t deliverable) {
   if (deliverable <= s->fetched) return 0;
   size_t n = (size_t)(deliverable - s->fetched);
-  if (s->outq_len + n > s->outq_cap) {
-    size_t ncap = std::max(s->outq_cap * 2, s->outq_len + n);
-    uint8_t* nq = static_cast<uint8_t*>(st_alloc(s, ncap));
-    if (!nq) return 2;
-    if (s->outq_len) std::memcpy(nq, s->outq, s->outq_len);
-    st_free(s, s->outq);
-    s->outq = nq; s->outq_cap = ncap;
-  }
+  if (!reserve_outq(s, n)) return 2;
   if (!hip_ok(hipMemcpy(s->outq + s->outq_len, s->d_out + (s->fetched - s->out_base), n, hipMemcpyDeviceToHost), "hipMemcpy(output)")) return 1;
   s->outq_len += n;
   s->fetched = deliverable;
   return 0;
 }
 
+// ---- The phases of one BrotliDecoderDecompressStream call.  The solo entry point runs them for its one state, with its own batch object and
+// synchronous copies; BrotliAmdStreamSetDecompress runs them for many states around ONE launch and ragged copies (below). ----
+
+// The device's output buffer of the state before a launch: room for six times the compressed bytes not yet behind a metablock boundary.
+bool stream_ensure_out(BrotliDecoderState* s) {
+  const size_t pending_in = (size_t)(s->d_in_len - s->in_base);
+  return dev_rebase(&s->d_out, &s->d_out_cap, 0, s->d_out_cap, std::max<size_t>(s->d_out_cap, std::max<size_t>(1 << 16, 6 * pending_in)));
+}
+
+// The state's descriptor of a launch: everything received so far, from the last completed metablock boundary.
+void stream_fill_desc(const BrotliDecoderState* s, BrotliAmdStreamDesc& d) {
+  std::memset(&d, 0, sizeof d);
+  d.in = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(s->d_in) - (uintptr_t)s->in_base); d.in_size = s->d_in_len;
+  d.out = reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(s->d_out) - (uintptr_t)s->out_base); d.out_cap = s->out_base + s->d_out_cap;
+  d.flags = (s->large_window ? BROTLI_AMD_FLAG_LARGE_WINDOW : 0u) | (s->canny ? 0u : BROTLI_AMD_FLAG_NO_CANNY);
+  if (s->have_resume) { d.flags |= BROTLI_AMD_FLAG_RESUME; d.resume = s->resume; }
+  if (s->d_dict) { d.dict = s->d_dict; d.dict_size = s->dict_len; }
+}
+
+void stream_note_status(BrotliDecoderState* s, const BrotliAmdStreamStatus& st) {
+  s->device_commands += st.num_commands;
+  if (st.resume.window_bits != 0) { s->resume = st.resume; s->have_resume = true; }
+}
+
+// A launch came back NEEDS_MORE_OUTPUT -- the device output buffer is exhausted: everything below the resume point is final.  What is dead is
+// dropped; where that does not leave half the buffer free, the buffer doubles.
+bool stream_grow_out(BrotliDecoderState* s) {
+  const uint64_t before = s->out_base;
+  if (!trim_buffers(s, true)) return false;
+  const uint64_t live = (s->have_resume ? s->resume.out_pos : 0) > s->out_base ? (s->have_resume ? s->resume.out_pos : 0) - s->out_base : 0;
+  if (s->out_base == before || live > s->d_out_cap / 2)
+    if (!dev_rebase(&s->d_out, &s->d_out_cap, 0, s->d_out_cap, s->d_out_cap * 2)) return false;
+  return true;
+}
+
 // One decode pass over everything received so far, from the last completed metablock boundary.
 // 0 = ok, 1 = HIP failure, 2 = allocation failure
 int decode_pass(BrotliDecoderState* s, BrotliAmdStreamStatus* st) {
   for (;;) {
-    const size_t pending_in = (size_t)(s->d_in_len - s->in_base);
-    if (!dev_rebase(&s->d_out, &s->d_out_cap, 0, s->d_out_cap, std::max<size_t>(s->d_out_cap, std::max<size_t>(1 << 16, 6 * pending_in)))) return 1;
-    BrotliAmdStreamDesc& d = s->batch->h_descs[0];
-    std::memset(&d, 0, sizeof d);
-    d.in = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(s->d_in) - (uintptr_t)s->in_base); d.in_size = s->d_in_len;
-    d.out = reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(s->d_out) - (uintptr_t)s->out_base); d.out_cap = s->out_base + s->d_out_cap;
-    d.flags = (s->large_window ? BROTLI_AMD_FLAG_LARGE_WINDOW : 0u) | (s->canny ? 0u : BROTLI_AMD_FLAG_NO_CANNY);
-    if (s->have_resume) { d.flags |= BROTLI_AMD_FLAG_RESUME; d.resume = s->resume; }
-    if (s->d_dict) { d.dict = s->d_dict; d.dict_size = s->dict_len; }
+    if (!stream_ensure_out(s)) return 1;
+    stream_fill_desc(s, s->batch->h_descs[0]);
     if (submit(s->batch, 1, nullptr) != 0) return 1;
     if (BrotliAmdBatchWait(s->batch, nullptr) != 0) return 1;
     *st = s->batch->h_status[0];
-    s->device_commands += st->num_commands;
-    if (st->resume.window_bits != 0) { s->resume = st->resume; s->have_resume = true; }
+    stream_note_status(s, *st);
     // bytes the reference would have flushed by now: all of them on success / needs-more-input, the part
     // below the last ring-buffer boundary on a fatal error (decode.rs:2835-2846, 2899-2913)
     if (int e = fetch_output(s, st->decoded_size)) return e;
     if (st->result != BROTLI_DECODER_RESULT_NEEDS_MORE_OUTPUT) return 0;
-    // device output buffer exhausted: everything below the resume point is final.  What is dead is dropped; where that
-    // does not leave half the buffer free, the buffer doubles.
-    const uint64_t before = s->out_base;
-    if (!trim_buffers(s, true)) return 1;
-    const uint64_t live = (s->have_resume ? s->resume.out_pos : 0) > s->out_base ? (s->have_resume ? s->resume.out_pos : 0) - s->out_base : 0;
-    if (s->out_base == before || live > s->d_out_cap / 2)
-      if (!dev_rebase(&s->d_out, &s->d_out_cap, 0, s->d_out_cap, s->d_out_cap * 2)) return 1;
+    if (!stream_grow_out(s)) return 1;
   }
+}
+
+// The head of a call, on the host: argument and slice checks, the latched error, the output the decoder owes.  True: the call is over (*result).
+bool stream_begin(BrotliDecoderState* s, size_t* available_in, const uint8_t** next_in, size_t* available_out, uint8_t** next_out, size_t* total_out,
+                  BrotliDecoderResult* result) {
+  *result = BROTLI_DECODER_RESULT_ERROR;
+  if (!s || !available_in || !next_in || !available_out || !next_out) {  // ffi/mod.rs:397-407
+    if (s) s->error_code = BROTLI_DECODER_ERROR_INVALID_ARGUMENTS;
+    return true;
+  }
+  if (!valid_slice(*next_in, *available_in) || !valid_slice(*next_out, *available_out)) {
+    s->error_code = BROTLI_DECODER_ERROR_INVALID_ARGUMENTS;
+    return true;
+  }
+  if (fatal(s->error_code)) return true;  // decode.rs:2796-2798
+  if ((uint64_t)*available_in >= (1ull << 32)) {                 // decode.rs:2799-2801
+    s->error_code = BROTLI_DECODER_ERROR_INVALID_ARGUMENTS;
+    return true;
+  }
+  // Output the decoder OWES comes first, and while it does not fit no input is consumed (a caller that sees
+  // NEEDS_MORE_OUTPUT finds its input where it left it: bit_reader/mod.rs:295-306).  Owed is what the reference has to write
+  // before it decodes on: the end of the stream (decode.rs:3382-3397), the bytes in front of a fatal error, and a full ring
+  // buffer (decode.rs:1693-1738) -- this decoder keeps no ring, so "a window's worth not yet taken" stands for that.  What a
+  // call that ended in NEEDS_MORE_INPUT had no room for is NOT owed: the reference wrote what fitted, took the call's input
+  // and kept the rest for later calls (decode.rs:2835-2846), and so does this.
+  if (s->outq_len != s->outq_off) {
+    const uint64_t ring = (s->have_resume && s->resume.window_bits) ? (1ull << s->resume.window_bits) : ~0ull;
+    if (s->finished || s->pending_error || (uint64_t)(s->outq_len - s->outq_off) >= ring) {
+      size_t n0 = hand_over(s, *next_out, *available_out);
+      *next_out += n0; *available_out -= n0;
+      if (s->outq_len != s->outq_off) {
+        if (total_out) *total_out = (size_t)s->total_out;
+        s->error_code = BROTLI_DECODER_NEEDS_MORE_OUTPUT;
+        *result = BROTLI_DECODER_RESULT_NEEDS_MORE_OUTPUT;
+        return true;
+      }
+    }
+  }
+  return false;
+}
+
+// Whether a call that got past its head has anything to decode: the others go straight to stream_end.
+bool stream_wants_device(const BrotliDecoderState* s, size_t given) { return !s->finished && !s->pending_error && given != 0; }
+
+BrotliDecoderResult stream_fail(BrotliDecoderState* s, const char* what) { set_runtime_error(s, what); return BROTLI_DECODER_RESULT_ERROR; }
+BrotliDecoderResult stream_fail(BrotliDecoderState* s, int e) {  // (decode_pass's codes)
+  if (e == 2) { s->error_code = BROTLI_DECODER_ERROR_ALLOC_RING_BUFFER_2; return BROTLI_DECODER_RESULT_ERROR; }
+  return stream_fail(s, "HIP runtime failure");
+}
+
+// The attached dictionary moves to the device the instance is bound to (the current one).
+bool stream_upload_dictionary(BrotliDecoderState* s) {
+  if (!s->h_dict) return true;
+  if (!hip_ok(hipMalloc(&s->d_dict, s->dict_len + 64), "hipMalloc(custom dictionary)") ||
+      !hip_ok(hipMemcpy(s->d_dict, s->h_dict, s->dict_len, hipMemcpyHostToDevice), "hipMemcpy(custom dictionary)")) {
+    if (s->d_dict) { (void)hipFree(s->d_dict); s->d_dict = nullptr; }
+    return false;
+  }
+  st_free(s, s->h_dict); s->h_dict = nullptr;
+  return true;
+}
+
+// The call's input is on the device (or on its way there): it counts as consumed.
+void stream_took_input(BrotliDecoderState* s, size_t* available_in, const uint8_t** next_in, size_t given) {
+  s->d_in_len += given;
+  *next_in += given; *available_in = 0;
+  s->used = true;
+}
+
+// What the last launch of the call said.  False: a HIP failure while trimming.
+bool stream_decoded(BrotliDecoderState* s, const BrotliAmdStreamStatus& st, size_t* available_in, const uint8_t** next_in, size_t given) {
+  if (st.result == BROTLI_DECODER_RESULT_SUCCESS) {
+    s->finished = true;
+    // give back what lies beyond the end of the stream (decode.rs:3374-3378); it is part of this call's input
+    size_t unused = (size_t)(s->d_in_len - st.consumed);
+    if (unused > given) unused = given;
+    *next_in -= unused; *available_in += unused;
+  } else if (st.result == BROTLI_DECODER_RESULT_ERROR) {
+    s->pending_error = st.error_code;
+  } else if (!trim_buffers(s)) {
+    return false;
+  }
+  return true;
+}
+
+// The tail of a call: what there is goes out as far as there is room, and the result follows from what is left.
+BrotliDecoderResult stream_end(BrotliDecoderState* s, size_t* available_out, uint8_t** next_out, size_t* total_out) {
+  size_t n = hand_over(s, *next_out, *available_out);
+  *next_out += n; *available_out -= n;
+  if (total_out) *total_out = (size_t)s->total_out;
+  if (s->outq_len != s->outq_off && (s->finished || s->pending_error)) { s->error_code = BROTLI_DECODER_NEEDS_MORE_OUTPUT; return BROTLI_DECODER_RESULT_NEEDS_MORE_OUTPUT; }
+  if (s->pending_error) { s->error_code = s->pending_error; return BROTLI_DECODER_RESULT_ERROR; }
+  if (s->finished) { s->error_code = BROTLI_DECODER_SUCCESS; return BROTLI_DECODER_RESULT_SUCCESS; }
+  s->error_code = BROTLI_DECODER_NEEDS_MORE_INPUT;
+  return BROTLI_DECODER_RESULT_NEEDS_MORE_INPUT;
 }
 
 }  // namespace
@@ -1286,94 +1413,32 @@ extern "C" BROTLI_BOOL BrotliDecoderSetParameter(BrotliDecoderState* s, BrotliDe
 
 extern "C" BrotliDecoderResult BrotliDecoderDecompressStream(BrotliDecoderState* s, size_t* available_in, const uint8_t** next_in,
                                                              size_t* available_out, uint8_t** next_out, size_t* total_out) {
-  if (!s || !available_in || !next_in || !available_out || !next_out) {  // ffi/mod.rs:397-407
-    if (s) s->error_code = BROTLI_DECODER_ERROR_INVALID_ARGUMENTS;
-    return BROTLI_DECODER_RESULT_ERROR;
-  }
-  if (!valid_slice(*next_in, *available_in) || !valid_slice(*next_out, *available_out)) {
-    s->error_code = BROTLI_DECODER_ERROR_INVALID_ARGUMENTS;
-    return BROTLI_DECODER_RESULT_ERROR;
-  }
-  if (fatal(s->error_code)) return BROTLI_DECODER_RESULT_ERROR;  // decode.rs:2796-2798
-  if ((uint64_t)*available_in >= (1ull << 32)) {                 // decode.rs:2799-2801
-    s->error_code = BROTLI_DECODER_ERROR_INVALID_ARGUMENTS;
-    return BROTLI_DECODER_RESULT_ERROR;
-  }
-  // Output the decoder OWES comes first, and while it does not fit no input is consumed (a caller that sees
-  // NEEDS_MORE_OUTPUT finds its input where it left it: bit_reader/mod.rs:295-306).  Owed is what the reference has to write
-  // before it decodes on: the end of the stream (decode.rs:3382-3397), the bytes in front of a fatal error, and a full ring
-  // buffer (decode.rs:1693-1738) -- this decoder keeps no ring, so "a window's worth not yet taken" stands for that.  What a
-  // call that ended in NEEDS_MORE_INPUT had no room for is NOT owed: the reference wrote what fitted, took the call's input
-  // and kept the rest for later calls (decode.rs:2835-2846), and so does this.
-  if (s->outq_len != s->outq_off) {
-    const uint64_t ring = (s->have_resume && s->resume.window_bits) ? (1ull << s->resume.window_bits) : ~0ull;
-    if (s->finished || s->pending_error || (uint64_t)(s->outq_len - s->outq_off) >= ring) {
-      size_t n0 = hand_over(s, *next_out, *available_out);
-      *next_out += n0; *available_out -= n0;
-      if (s->outq_len != s->outq_off) {
-        if (total_out) *total_out = (size_t)s->total_out;
-        s->error_code = BROTLI_DECODER_NEEDS_MORE_OUTPUT;
-        return BROTLI_DECODER_RESULT_NEEDS_MORE_OUTPUT;
-      }
-    }
-  }
+  BrotliDecoderResult early;
+  if (stream_begin(s, available_in, next_in, available_out, next_out, total_out, &early)) return early;
   const size_t given = *available_in;
-  if (!s->finished && !s->pending_error && given) {
+  if (stream_wants_device(s, given)) {
     DeviceGuard guard;
-    // lazily bind to the current device
+    // lazily bind to the current device (a state first stepped through a stream set is bound to the set's already, and has no batch object yet)
     if (!s->batch) {
-      int dev = 0;
-      if (!current_device(&dev)) { set_runtime_error(s, "HIP device unavailable"); return BROTLI_DECODER_RESULT_ERROR; }
+      int dev = s->device;
+      if (dev < 0 && !current_device(&dev)) return stream_fail(s, "HIP device unavailable");
+      if (s->device >= 0 && !hip_ok(hipSetDevice(dev), "hipSetDevice")) return stream_fail(s, "HIP runtime failure");
       s->batch = BrotliAmdBatchCreate(1, 0, 0);
-      if (!s->batch) { set_runtime_error(s, "HIP device unavailable"); return BROTLI_DECODER_RESULT_ERROR; }
+      if (!s->batch) return stream_fail(s, "HIP device unavailable");
       s->device = dev;
     }
-    if (!hip_ok(hipSetDevice(s->device), "hipSetDevice")) { set_runtime_error(s, "HIP runtime failure"); return BROTLI_DECODER_RESULT_ERROR; }
-    if (s->h_dict) {   // the attached dictionary moves to the device the instance is bound to
-      if (!hip_ok(hipMalloc(&s->d_dict, s->dict_len + 64), "hipMalloc(custom dictionary)") ||
-          !hip_ok(hipMemcpy(s->d_dict, s->h_dict, s->dict_len, hipMemcpyHostToDevice), "hipMemcpy(custom dictionary)")) {
-        if (s->d_dict) { (void)hipFree(s->d_dict); s->d_dict = nullptr; }
-        set_runtime_error(s, "HIP runtime failure");
-        return BROTLI_DECODER_RESULT_ERROR;
-      }
-      st_free(s, s->h_dict); s->h_dict = nullptr;
-    }
+    if (!hip_ok(hipSetDevice(s->device), "hipSetDevice")) return stream_fail(s, "HIP runtime failure");
+    if (!stream_upload_dictionary(s)) return stream_fail(s, "HIP runtime failure");
     const size_t fill = (size_t)(s->d_in_len - s->in_base);
     if (!dev_rebase(&s->d_in, &s->d_in_cap, 0, fill, fill + given) ||
-        !hip_ok(hipMemcpy(s->d_in + fill, *next_in, given, hipMemcpyHostToDevice), "hipMemcpy(input)")) {
-      set_runtime_error(s, "HIP runtime failure");
-      return BROTLI_DECODER_RESULT_ERROR;
-    }
-    s->d_in_len += given;
-    *next_in += given; *available_in = 0;
-    s->used = true;
+        !hip_ok(hipMemcpy(s->d_in + fill, *next_in, given, hipMemcpyHostToDevice), "hipMemcpy(input)"))
+      return stream_fail(s, "HIP runtime failure");
+    stream_took_input(s, available_in, next_in, given);
     BrotliAmdStreamStatus st;
-    if (int e = decode_pass(s, &st)) {
-      if (e == 2) { s->error_code = BROTLI_DECODER_ERROR_ALLOC_RING_BUFFER_2; return BROTLI_DECODER_RESULT_ERROR; }
-      set_runtime_error(s, "HIP runtime failure");
-      return BROTLI_DECODER_RESULT_ERROR;
-    }
-    if (st.result == BROTLI_DECODER_RESULT_SUCCESS) {
-      s->finished = true;
-      // give back what lies beyond the end of the stream (decode.rs:3374-3378); it is part of this call's input
-      size_t unused = (size_t)(s->d_in_len - st.consumed);
-      if (unused > given) unused = given;
-      *next_in -= unused; *available_in += unused;
-    } else if (st.result == BROTLI_DECODER_RESULT_ERROR) {
-      s->pending_error = st.error_code;
-    } else if (!trim_buffers(s)) {
-      set_runtime_error(s, "HIP runtime failure");
-      return BROTLI_DECODER_RESULT_ERROR;
-    }
+    if (int e = decode_pass(s, &st)) return stream_fail(s, e);
+    if (!stream_decoded(s, st, available_in, next_in, given)) return stream_fail(s, "HIP runtime failure");
   }
-  size_t n = hand_over(s, *next_out, *available_out);
-  *next_out += n; *available_out -= n;
-  if (total_out) *total_out = (size_t)s->total_out;
-  if (s->outq_len != s->outq_off && (s->finished || s->pending_error)) { s->error_code = BROTLI_DECODER_NEEDS_MORE_OUTPUT; return BROTLI_DECODER_RESULT_NEEDS_MORE_OUTPUT; }
-  if (s->pending_error) { s->error_code = s->pending_error; return BROTLI_DECODER_RESULT_ERROR; }
-  if (s->finished) { s->error_code = BROTLI_DECODER_SUCCESS; return BROTLI_DECODER_RESULT_SUCCESS; }
-  s->error_code = BROTLI_DECODER_NEEDS_MORE_INPUT;
-  return BROTLI_DECODER_RESULT_NEEDS_MORE_INPUT;
+  return stream_end(s, available_out, next_out, total_out);
 }
 
 extern "C" BrotliDecoderResult BrotliDecoderDecompressStreaming(BrotliDecoderState* s, size_t* available_in, const uint8_t* next_in,
@@ -1435,3 +1500,247 @@ extern "C" void BrotliDecoderFreeUsize(BrotliDecoderState* s, size_t* data, size
 extern "C" __attribute__((visibility("default"))) size_t brotli_amd_debug_stream_device_bytes(const BrotliDecoderState* s) {
   return s ? s->d_in_cap + s->d_out_cap : 0;
 }
+
+// ============================================== stream sets ==============================================
+// Many streaming states advanced by ONE launch (include/brotli/batch.h).  Per state the call is BrotliDecoderDecompressStream's, phase by phase
+// (stream_begin ... stream_end above); what differs is how the bytes travel and how many states a launch holds: the chunks of all states go to the
+// device packed in one pinned staging buffer and a ragged copy (csrc/brotli_copy_kernels.hip) appends each to its state's input, one submit()
+// over the set's own batch object decodes them all, a ragged copy gathers every state's new output into staging and one transfer brings it back.
+struct BrotliAmdStreamSet {
+  uint32_t max_states = 0;
+  int device = -1;                       // bound at the first call that needs a device
+  BrotliAmdBatch* batch = nullptr;
+  BrotliAmdCopySeg* h_segs = nullptr;    // pinned, max_states entries
+  BrotliAmdCopySeg* d_segs = nullptr;
+  uint8_t* h_in = nullptr; uint8_t* d_in = nullptr; size_t in_cap = 0;      // staging, host (pinned) and device side
+  uint8_t* h_out = nullptr; uint8_t* d_out = nullptr; size_t out_cap = 0;
+  uint32_t last_launches = 0, last_transfers = 0;
+};
+
+namespace {
+
+constexpr size_t kSetStageMax = (size_t)64 << 20;   // staging in each direction at most; a larger chunk or output part travels alone
+
+bool set_bind(BrotliAmdStreamSet* set) {
+  if (set->batch) return true;
+  int dev = set->device;
+  if (dev < 0 && !current_device(&dev)) return false;
+  if (!hip_ok(hipSetDevice(dev), "hipSetDevice")) return false;
+  BrotliAmdBatch* b = BrotliAmdBatchCreate(set->max_states, 0, 0);
+  if (!b) return false;
+  bool ok = hip_ok(hipHostMalloc(&set->h_segs, sizeof(BrotliAmdCopySeg) * set->max_states), "hipHostMalloc(copy segments)");
+  ok = ok && hip_ok(hipMalloc(&set->d_segs, sizeof(BrotliAmdCopySeg) * set->max_states), "hipMalloc(copy segments)");
+  if (!ok) {
+    if (set->h_segs) (void)hipHostFree(set->h_segs);
+    if (set->d_segs) (void)hipFree(set->d_segs);
+    set->h_segs = nullptr; set->d_segs = nullptr;
+    BrotliAmdBatchDestroy(b);
+    return false;
+  }
+  set->batch = b; set->device = dev;
+  return true;
+}
+
+bool set_stage(uint8_t** h, uint8_t** d, size_t* cap, size_t need) {
+  if (need <= *cap) return true;
+  size_t want = (size_t)1 << 20;
+  while (want < need) want <<= 1;
+  want = std::min(want, kSetStageMax);
+  if (!hip_ok(hipStreamSynchronize(nullptr), "hipStreamSynchronize")) return false;
+  if (*h) (void)hipHostFree(*h);
+  if (*d) (void)hipFree(*d);
+  *h = nullptr; *d = nullptr; *cap = 0;
+  if (!hip_ok(hipHostMalloc(h, want), "hipHostMalloc(staging)") || !hip_ok(hipMalloc(d, want + 256), "hipMalloc(staging)")) {
+    if (*h) (void)hipHostFree(*h);
+    if (*d) (void)hipFree(*d);
+    *h = nullptr; *d = nullptr;
+    return false;
+  }
+  *cap = want;
+  return true;
+}
+
+// One part of a staged move: `len` bytes between a state's device buffer at `dev` and host memory at `host`.
+struct SetPart { uint8_t* dev; uint8_t* host; size_t len; };
+
+// Moves the parts between host and device: those that fit the staging buffer together in one transfer and one ragged copy (several rounds of
+// both where they add up to more than the buffer holds), a part larger than the buffer by a copy of its own.  Synchronous: done on return.
+bool set_move(BrotliAmdStreamSet* set, const std::vector<SetPart>& parts, bool to_device) {
+  uint8_t** h = to_device ? &set->h_in : &set->h_out; uint8_t** d = to_device ? &set->d_in : &set->d_out;
+  size_t* cap = to_device ? &set->in_cap : &set->out_cap;
+  size_t staged = 0;
+  for (const SetPart& p : parts) if (p.len <= kSetStageMax) staged += p.len;
+  if (staged && !set_stage(h, d, cap, std::min(staged, kSetStageMax))) return false;
+  size_t at = 0;
+  while (at < parts.size()) {
+    uint32_t m = 0; size_t bytes = 0, first = at;
+    for (; at < parts.size() && m < set->max_states; at++) {
+      const SetPart& p = parts[at];
+      if (p.len == 0) continue;
+      if (p.len > kSetStageMax) {
+        if (!hip_ok(to_device ? hipMemcpy(p.dev, p.host, p.len, hipMemcpyHostToDevice) : hipMemcpy(p.host, p.dev, p.len, hipMemcpyDeviceToHost), "hipMemcpy(large part)")) return false;
+        set->last_transfers++;
+        continue;
+      }
+      if (bytes + p.len > *cap) break;
+      if (to_device) { std::memcpy(*h + bytes, p.host, p.len); set->h_segs[m] = BrotliAmdCopySeg{*d + bytes, p.dev, p.len}; }
+      else set->h_segs[m] = BrotliAmdCopySeg{p.dev, *d + bytes, p.len};
+      m++; bytes += p.len;
+    }
+    if (m == 0) continue;
+    bool ok = hip_ok(hipMemcpyAsync(set->d_segs, set->h_segs, sizeof(BrotliAmdCopySeg) * m, hipMemcpyHostToDevice, nullptr), "hipMemcpyAsync(copy segments)");
+    if (to_device) ok = ok && hip_ok(hipMemcpyAsync(*d, *h, bytes, hipMemcpyHostToDevice, nullptr), "hipMemcpyAsync(staged input)");
+    ok = ok && hip_ok(brotli_amd_launch_ragged_copy_sized(set->d_segs, m, bytes, nullptr), "brotli_amd_ragged_copy_kernel launch");
+    if (!to_device) ok = ok && hip_ok(hipMemcpyAsync(*h, *d, bytes, hipMemcpyDeviceToHost, nullptr), "hipMemcpyAsync(staged output)");
+    // (output is wanted on the host now; input only has to be out of the pinned buffer before it is filled again -- the launch that follows is
+    // on the same stream, and so are dev_rebase's copies and frees, and the wait for the launch is the wait for this)
+    if (!to_device || at < parts.size()) ok = ok && hip_ok(hipStreamSynchronize(nullptr), "hipStreamSynchronize(staging)");
+    if (!ok) return false;
+    set->last_transfers++;
+    if (!to_device) {
+      size_t off = 0;
+      for (size_t k = first; k < at; k++) {
+        const SetPart& p = parts[k];
+        if (p.len == 0 || p.len > kSetStageMax) continue;
+        std::memcpy(p.host, *h + off, p.len); off += p.len;
+      }
+    }
+  }
+  return true;
+}
+
+}  // namespace
+
+extern "C" BrotliAmdStreamSet* BrotliAmdStreamSetCreate(uint32_t max_states) {
+  BrotliAmdStreamSet* set = new (std::nothrow) BrotliAmdStreamSet();
+  if (!set) return nullptr;
+  set->max_states = max_states ? max_states : 1u;
+  return set;
+}
+
+extern "C" void BrotliAmdStreamSetDestroy(BrotliAmdStreamSet* set) {
+  if (!set) return;
+  if (set->batch) BrotliAmdBatchDestroy(set->batch);   // (waits for the device)
+  if (set->device >= 0) {
+    DeviceGuard guard;
+    (void)hipSetDevice(set->device);
+    if (set->h_segs) (void)hipHostFree(set->h_segs);
+    if (set->d_segs) (void)hipFree(set->d_segs);
+    if (set->h_in) (void)hipHostFree(set->h_in);
+    if (set->d_in) (void)hipFree(set->d_in);
+    if (set->h_out) (void)hipHostFree(set->h_out);
+    if (set->d_out) (void)hipFree(set->d_out);
+  }
+  delete set;
+}
+
+extern "C" uint32_t BrotliAmdStreamSetLastLaunches(BrotliAmdStreamSet* set) { return set ? set->last_launches : 0; }
+extern "C" uint32_t BrotliAmdStreamSetLastTransfers(BrotliAmdStreamSet* set) { return set ? set->last_transfers : 0; }
+
+extern "C" int BrotliAmdStreamSetDecompress(BrotliAmdStreamSet* set, uint32_t n, BrotliDecoderState* const* states, size_t* available_in,
+                                            const uint8_t** next_in, size_t* available_out, uint8_t** next_out, size_t* total_out,
+                                            BrotliDecoderResult* results) {
+  // failures of the call as a whole: nothing is touched
+  if (!set) { g_last_error = "invalid stream set arguments"; return -1; }
+  if (n == 0) { set->last_launches = set->last_transfers = 0; return 0; }
+  if (!states || !results || !available_in || !next_in || !available_out || !next_out || n > set->max_states) { g_last_error = "invalid stream set arguments"; return -1; }
+  {
+    std::vector<const BrotliDecoderState*> seen(states, states + n);
+    std::sort(seen.begin(), seen.end());
+    if (seen[0] == nullptr || std::adjacent_find(seen.begin(), seen.end()) != seen.end()) { g_last_error = "invalid stream set arguments"; return -1; }
+    int dev = set->device;
+    for (uint32_t i = 0; i < n; i++) {
+      if (states[i]->device < 0) continue;
+      if (dev < 0 && hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = -1; break; }   // (the device the set would bind to)
+      if (states[i]->device != dev) { g_last_error = "a state of the set is bound to another device"; return -1; }
+    }
+  }
+  set->last_launches = set->last_transfers = 0;
+  // the head of every state's call, on the host; what is left needs the device
+  std::vector<uint32_t> act; std::vector<size_t> given(n, 0);
+  for (uint32_t i = 0; i < n; i++) {
+    BrotliDecoderState* s = states[i];
+    size_t* tot = total_out ? &total_out[i] : nullptr;
+    if (stream_begin(s, &available_in[i], &next_in[i], &available_out[i], &next_out[i], tot, &results[i])) continue;
+    given[i] = available_in[i];
+    if (stream_wants_device(s, given[i])) act.push_back(i);
+    else results[i] = stream_end(s, &available_out[i], &next_out[i], tot);
+  }
+  if (act.empty()) return 0;
+  DeviceGuard guard;
+  const auto fail_all = [&](const std::vector<uint32_t>& which, const char* what) { for (uint32_t i : which) results[i] = stream_fail(states[i], what); };
+  if (!set_bind(set)) { fail_all(act, "HIP device unavailable"); return 0; }
+  if (!hip_ok(hipSetDevice(set->device), "hipSetDevice")) { fail_all(act, "HIP runtime failure"); return 0; }
+  // input: every state's chunk behind what its device buffer holds
+  {
+    std::vector<uint32_t> ready; std::vector<SetPart> parts;
+    for (uint32_t i : act) {
+      BrotliDecoderState* s = states[i];
+      if (s->device < 0) s->device = set->device;   // (no batch object of its own until it is first stepped alone)
+      const size_t fill = (size_t)(s->d_in_len - s->in_base);
+      if (!stream_upload_dictionary(s) || !dev_rebase(&s->d_in, &s->d_in_cap, 0, fill, fill + given[i])) { results[i] = stream_fail(s, "HIP runtime failure"); continue; }
+      parts.push_back(SetPart{s->d_in + fill, const_cast<uint8_t*>(next_in[i]), given[i]});
+      ready.push_back(i);
+    }
+    act.swap(ready);
+    if (act.empty()) return 0;
+    if (!set_move(set, parts, true)) { fail_all(act, "HIP runtime failure"); return 0; }
+    for (uint32_t i : act) stream_took_input(states[i], &available_in[i], &next_in[i], given[i]);
+  }
+  // decode: one launch over all of them; the states whose device output buffer was full grow it and are launched again, they alone
+  std::vector<uint32_t> cur = act;
+  while (!cur.empty()) {
+    {
+      std::vector<uint32_t> ready;
+      for (uint32_t i : cur) { if (stream_ensure_out(states[i])) ready.push_back(i); else results[i] = stream_fail(states[i], 1); }
+      cur.swap(ready);
+      if (cur.empty()) break;
+    }
+    const uint32_t m = (uint32_t)cur.size();
+    for (uint32_t j = 0; j < m; j++) stream_fill_desc(states[cur[j]], set->batch->h_descs[j]);
+    if (submit(set->batch, m, nullptr) != 0 || BrotliAmdBatchWait(set->batch, nullptr) != 0) { for (uint32_t i : cur) results[i] = stream_fail(states[i], 1); break; }
+    set->last_launches++;
+    std::vector<BrotliAmdStreamStatus> sts(set->batch->h_status, set->batch->h_status + m);
+    // output: what the reference would have flushed by now (fetch_output's rule), off the device behind what each caller has not taken yet
+    std::vector<uint32_t> got; std::vector<SetPart> parts;   // got: positions in cur
+    for (uint32_t j = 0; j < m; j++) {
+      BrotliDecoderState* s = states[cur[j]];
+      stream_note_status(s, sts[j]);
+      const size_t len = sts[j].decoded_size > s->fetched ? (size_t)(sts[j].decoded_size - s->fetched) : 0;
+      if (!reserve_outq(s, len)) { results[cur[j]] = stream_fail(s, 2); continue; }
+      parts.push_back(SetPart{s->d_out + (s->fetched - s->out_base), s->outq + s->outq_len, len});
+      got.push_back(j);
+    }
+    if (!set_move(set, parts, false)) { for (uint32_t j : got) results[cur[j]] = stream_fail(states[cur[j]], 1); break; }
+    std::vector<uint32_t> again;
+    for (size_t k = 0; k < got.size(); k++) {
+      const uint32_t j = got[k], i = cur[j];
+      BrotliDecoderState* s = states[i];
+      s->outq_len += parts[k].len; s->fetched += parts[k].len;
+      if (sts[j].result == BROTLI_DECODER_RESULT_NEEDS_MORE_OUTPUT) {
+        if (stream_grow_out(s)) again.push_back(i); else results[i] = stream_fail(s, 1);
+        continue;
+      }
+      if (!stream_decoded(s, sts[j], &available_in[i], &next_in[i], given[i])) { results[i] = stream_fail(s, "HIP runtime failure"); continue; }
+      results[i] = stream_end(s, &available_out[i], &next_out[i], total_out ? &total_out[i] : nullptr);
+    }
+    cur.swap(again);
+  }
+  return 0;
+}
+
+// Test hook: the ragged copy alone (host arrays of device pointers; launches, waits).
+extern "C" int BrotliAmdDebugRaggedCopy(uint32_t n, const void* const* d_src, void* const* d_dst, const size_t* lens) {
+  if (n == 0) return hip_ok(brotli_amd_launch_ragged_copy(nullptr, 0, nullptr), "brotli_amd_ragged_copy_kernel launch") ? 0 : -1;
+  if (!d_src || !d_dst || !lens) { g_last_error = "invalid ragged copy arguments"; return -1; }
+  std::vector<BrotliAmdCopySeg> segs(n);
+  for (uint32_t i = 0; i < n; i++) segs[i] = BrotliAmdCopySeg{static_cast<const uint8_t*>(d_src[i]), static_cast<uint8_t*>(d_dst[i]), lens[i]};
+  BrotliAmdCopySeg* d = nullptr;
+  bool ok = hip_ok(hipMalloc(&d, sizeof(BrotliAmdCopySeg) * n), "hipMalloc(copy segments)");
+  ok = ok && hip_ok(hipMemcpy(d, segs.data(), sizeof(BrotliAmdCopySeg) * n, hipMemcpyHostToDevice), "hipMemcpy(copy segments)");
+  ok = ok && hip_ok(brotli_amd_launch_ragged_copy(d, n, nullptr), "brotli_amd_ragged_copy_kernel launch");
+  ok = ok && hip_ok(hipStreamSynchronize(nullptr), "hipStreamSynchronize(ragged copy)");
+  if (d) (void)hipFree(d);
+  return ok ? 0 : -1;
+}
+extern "C" uint32_t BrotliAmdDebugRaggedCopyTile(void) { return brotli_amd_copy_tile_bytes(); }

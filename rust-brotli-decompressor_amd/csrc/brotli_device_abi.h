@@ -101,6 +101,16 @@ typedef struct BrotliAmdStreamStatus {
   uint64_t ring_bytes;
 } BrotliAmdStreamStatus;
 
+// One segment of a ragged copy (csrc/brotli_copy_kernels.hip): len bytes from src to dst, device addresses of any alignment, len 0 included.
+// The segments of one launch do not overlap each other.  Nothing outside [dst, dst + len) is written; nothing outside the 16-byte-aligned
+// span around [src, src + len) is read.
+typedef struct BrotliAmdCopySeg {
+  const uint8_t* src;
+  uint8_t* dst;
+  uint64_t len;
+} BrotliAmdCopySeg;
+#define BROTLI_AMD_COPY_TILE_BYTES 16384u  // destination bytes of one tile: the blocks of a launch take the segments' bytes tile by tile
+
 #ifdef __cplusplus
 }
 #endif
