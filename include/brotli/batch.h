@@ -103,6 +103,90 @@ BROTLI_DEC_API int BrotliAmdBatchDecodeHostDict(BrotliAmdBatch* batch, uint32_t 
                                                uint8_t* const* out, const size_t* out_caps, const uint8_t* const* dicts,
                                                const size_t* dict_sizes, uint32_t flags, BrotliAmdResult* results);
 
+/* ---- Batches whose decoded sizes are NOT known: size hints and the packed decode ----
+ *
+ * Every entry point above takes out_caps[]: the caller has to know how large each stream decodes, and Brotli has no size field.  The two
+ * calls below lift that.
+ *
+ * THE SIZE WALK.  A stream's headers say more than one would guess (csrc/brotli_size_walk.h): metadata and stored metablocks carry their own
+ * byte lengths, so they can be stepped over, and the first compressed metablock states its MLEN and ISLAST in front of its prefix codes.
+ * The walk reads the stream header (every WBITS encoding; the 14-bit large-window form with BROTLI_AMD_BATCH_LARGE_WINDOW), then metablock
+ * headers, and stops at the first compressed metablock, at an empty last metablock, at the end of the input or at a header the decoder
+ * rejects (a reserved bit, an exuberant nibble or meta nibble, non-zero padding, invalid window bits).  No prefix code is decoded.
+ *
+ * The contract of a hint is weak on purpose -- the packed decode's correctness never depends on it:
+ *   - `bytes` is a LOWER BOUND on the decoded size of every stream that decodes successfully;
+ *   - it is the exact size where exact == 1 && status == 0 (of such a stream);
+ *   - status == 2 only where the decoder reports an error;
+ *   - the walk need not find every error. */
+typedef struct BrotliAmdSizeHint {
+  uint64_t bytes;      /* sum of MLEN over every stored metablock walked, plus MLEN of the first compressed one reached */
+  uint64_t walked_in;  /* input bytes in front of the point where the walk stopped: the header of the compressed metablock reached or of the
+                          metablock the walk could not finish; behind the last metablock where the walk reached the stream's end */
+  uint32_t exact;      /* 1: the walk reached the stream's last metablock, so nothing can follow `bytes` */
+  uint32_t status;     /* 0 ok, 1 the input ended inside the walk, 2 a header the decoder rejects */
+} BrotliAmdSizeHint;
+
+/* The hints of n streams in DEVICE memory (d_in[i]: any alignment) by one launch of one lane a stream (csrc/brotli_size_kernels.hip) on
+ * hip_stream; the call waits on that stream and copies the hints to `hints` (host, n entries).  n is not bound by the batch object's
+ * max_streams.  flags: BROTLI_AMD_BATCH_LARGE_WINDOW.  n == 0 returns 0; in_sizes[i] == 0 gives {0, 0, 0, 1}.  Negative on failure. */
+BROTLI_DEC_API int BrotliAmdBatchSizeHints(BrotliAmdBatch* batch, uint32_t n, const void* const* d_in, const size_t* in_sizes,
+                                          uint32_t flags, BrotliAmdSizeHint* hints, void* hip_stream);
+
+/* Test hook (no device needed): the same function on the host, over n bytes at `in`.  Returns 0; negative for NULL arguments. */
+BROTLI_DEC_API int BrotliAmdDebugSizeWalk(const uint8_t* in, size_t n, uint32_t flags, BrotliAmdSizeHint* hint);
+
+/* THE PACKED DECODE: n streams in DEVICE memory, no output buffers and no sizes from the caller.  The library sizes, allocates, decodes --
+ * growing what it guessed too small -- and leaves all outputs back to back in ONE device buffer of its own.
+ *
+ * The contract:
+ *   - the call is synchronous: everything is decoded when it returns;
+ *   - result, error_code, decoded_size, consumed and produced of results[i] are what BrotliAmdBatchDecodeDevice(Dict) reports for the same
+ *     stream with out_caps[i] = max_out_bytes and flags | BROTLI_AMD_BATCH_EAGER_OUTPUT_LIMIT -- with max_out_bytes == 0: with a buffer large
+ *     enough that no stream ends NEEDS_MORE_OUTPUT.  (The counters -- num_metablocks, num_commands, engine_commands, spilled_metablocks -- are
+ *     sums over the launches a stream took: a stream that had to grow decodes the metablock it stopped in a second time.)
+ *   - stream i's delivered bytes are [offsets[i], offsets[i + 1]) of BrotliAmdBatchPackedOutput's buffer; the packing is tight:
+ *     offsets[i + 1] - offsets[i] == results[i].decoded_size, and no alignment padding sits between streams;
+ *   - the buffer and the offsets stay valid until the next decode call on the batch object or BrotliAmdBatchDestroy;
+ *   - where a hipMalloc fails the call as a whole fails: a negative value, BrotliAmdLastError says why, and there are no partial results
+ *     (BrotliAmdBatchPackedOutput then returns NULL).  n > max_streams and NULL arrays fail the same way; n == 0 returns 0.
+ * d_dicts / dict_sizes: custom dictionaries as in BrotliAmdBatchDecodeDeviceDict (NULL: none).  max_out_bytes: per stream, 0 = no limit.
+ * WITHOUT A LIMIT NOTHING BOUNDS THE GROWTH: a few hundred compressed bytes can state gigabytes of output, and a stream's slot is doubled until
+ * it decodes or a hipMalloc fails (which fails the call).  Give input that is not trusted a max_out_bytes.
+ * "The next decode call" is any of BrotliAmdBatchDecodeDevice(Dict), BrotliAmdBatchDecodeHost(Dict) and the packed calls on the same object, whatever it
+ * returns: from its entry on BrotliAmdBatchPackedOutput returns NULL (offsets NULL), BrotliAmdBatchPackedFetch fails, and the two counters and
+ * BrotliAmdBatchLastKernelMs no longer speak of the packed call.  After a packed call BrotliAmdBatchLastKernelMs is the time of all its decode launches
+ * together; BrotliAmdBatchWait and BrotliAmdBatchRelaunch have nothing to come back to (0, and a failure).
+ *
+ * How a call runs:
+ *  1. the size hints of all streams (above);
+ *  2. each stream's first capacity: `bytes` where the hint is exact, else max(64 KiB, bytes + 6 x (in_size - walked_in)) -- the streaming
+ *     decoder's first guess for input it has not seen decoded --, clamped to max_out_bytes;
+ *  3. the slots lie back to back in one allocation, and ONE launch decodes the batch -- through the path of BrotliAmdBatchDecodeDeviceDict and
+ *     BrotliAmdBatchWait: dictionaries, probe, gangs and pools (planned from the same in_sizes), the second pass with a larger LDS arena;
+ *  4. streams that came back NEEDS_MORE_OUTPUT below their limit get a new slot of max(2 x cap, out_pos x in_size / consumed) -- the output and input positions of the resume point --, rounded up to
+ *     64 KiB and clamped; the new slots are one allocation a round, one ragged-copy launch (csrc/brotli_copy_kernels.hip) moves what each of
+ *     these streams has decoded up to its last metablock boundary, and they ALONE are launched again, resumed from that boundary; and so on
+ *     until no stream is in that state;
+ *  5. where every stream filled its slot exactly -- the rule for single-metablock documents, whose hints are exact -- the first allocation
+ *     IS the packed output: one decode launch, no copy.  Otherwise one ragged-copy launch gathers the delivered bytes into a tight buffer. */
+BROTLI_DEC_API int BrotliAmdBatchDecodeDevicePacked(BrotliAmdBatch* batch, uint32_t n, const void* const* d_in, const size_t* in_sizes,
+                                                   const void* const* d_dicts, const size_t* dict_sizes, uint64_t max_out_bytes,
+                                                   uint32_t flags, void* hip_stream, BrotliAmdResult* results);
+/* The packed output of the last packed call (a DEVICE pointer; NULL where there is none) and its n + 1 offsets (host memory of the batch object). */
+BROTLI_DEC_API const void* BrotliAmdBatchPackedOutput(BrotliAmdBatch* batch, const uint64_t** offsets);
+/* Copies the whole packed output (offsets[n] bytes) to host memory.  Returns 0 on success. */
+BROTLI_DEC_API int BrotliAmdBatchPackedFetch(BrotliAmdBatch* batch, uint8_t* host_dst);
+/* The same for HOST buffers: the streams (and each distinct dictionary once) are uploaded through the staging of BrotliAmdBatchDecodeHostDict,
+ * then the device form runs.  The caller reads the offsets, allocates, and calls BrotliAmdBatchPackedFetch. */
+BROTLI_DEC_API int BrotliAmdBatchDecodeHostPacked(BrotliAmdBatch* batch, uint32_t n, const uint8_t* const* in, const size_t* in_sizes,
+                                                 const uint8_t* const* dicts, const size_t* dict_sizes, uint64_t max_out_bytes,
+                                                 uint32_t flags, BrotliAmdResult* results);
+/* Decode launches of the last packed call (1 where no stream had to grow; the size walk is not counted) and ragged-copy launches in it
+ * (0 where the first allocation was the packed output). */
+BROTLI_DEC_API uint32_t BrotliAmdBatchLastPackedLaunches(BrotliAmdBatch* batch);
+BROTLI_DEC_API uint32_t BrotliAmdBatchLastPackedCopies(BrotliAmdBatch* batch);
+
 /* Milliseconds the last launch spent in the decode kernel (HIP events on the launch stream). */
 BROTLI_DEC_API float BrotliAmdBatchLastKernelMs(BrotliAmdBatch* batch);
 

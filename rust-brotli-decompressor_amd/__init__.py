@@ -34,6 +34,8 @@ BATCH_H_SYMBOLS = [
     "BrotliAmdBatchDecodeDeviceDict", "BrotliAmdBatchDecodeHostDict", "BrotliAmdDecoderAttachDictionary",
     "BrotliAmdStreamSetCreate", "BrotliAmdStreamSetDestroy", "BrotliAmdStreamSetDecompress", "BrotliAmdStreamSetLastLaunches",
     "BrotliAmdStreamSetLastTransfers", "BrotliAmdDebugRaggedCopy", "BrotliAmdDebugRaggedCopyTile",
+    "BrotliAmdBatchSizeHints", "BrotliAmdDebugSizeWalk", "BrotliAmdBatchDecodeDevicePacked", "BrotliAmdBatchPackedOutput",
+    "BrotliAmdBatchPackedFetch", "BrotliAmdBatchDecodeHostPacked", "BrotliAmdBatchLastPackedLaunches", "BrotliAmdBatchLastPackedCopies",
 ]
 
 
@@ -46,6 +48,16 @@ class BatchResult(ctypes.Structure):  # BrotliAmdResult
                 ("consumed", ctypes.c_uint64), ("produced", ctypes.c_uint64), ("num_metablocks", ctypes.c_uint32),
                 ("spilled_metablocks", ctypes.c_uint32), ("num_commands", ctypes.c_uint64),
                 ("engine_commands", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class SizeHint(ctypes.Structure):  # BrotliAmdSizeHint: what a stream's headers say of its decoded size (batch.h)
+    _fields_ = [("bytes", ctypes.c_uint64), ("walked_in", ctypes.c_uint64), ("exact", ctypes.c_uint32), ("status", ctypes.c_uint32)]
+
+    def astuple(self):
+        return (self.bytes, self.walked_in, self.exact, self.status)
+
+
+SIZE_OK, SIZE_TRUNCATED, SIZE_REJECTED = 0, 1, 2  # SizeHint.status
 
 
 def build(force=False):
@@ -117,6 +129,17 @@ def load_library():
             getattr(L, name).argtypes = [vp]
         L.BrotliAmdDebugRaggedCopy.argtypes = [u32, vp, vp, vp]
         L.BrotliAmdDebugRaggedCopyTile.restype = u32
+    if hasattr(L, "BrotliAmdBatchSizeHints"):   # (size hints and the packed decode: an older build of the library, loaded for an A/B, has none)
+        L.BrotliAmdBatchSizeHints.argtypes = [vp, u32, vp, vp, u32, vp, vp]
+        L.BrotliAmdDebugSizeWalk.argtypes = [vp, sz, u32, vp]
+        L.BrotliAmdBatchDecodeDevicePacked.argtypes = [vp, u32, vp, vp, vp, vp, ctypes.c_uint64, u32, vp, vp]
+        L.BrotliAmdBatchDecodeHostPacked.argtypes = [vp, u32, vp, vp, vp, vp, ctypes.c_uint64, u32, vp]
+        L.BrotliAmdBatchPackedOutput.restype = vp
+        L.BrotliAmdBatchPackedOutput.argtypes = [vp, ctypes.POINTER(ctypes.POINTER(ctypes.c_uint64))]
+        L.BrotliAmdBatchPackedFetch.argtypes = [vp, vp]
+        for name in ("BrotliAmdBatchLastPackedLaunches", "BrotliAmdBatchLastPackedCopies"):
+            getattr(L, name).restype = u32
+            getattr(L, name).argtypes = [vp]
     L.BrotliAmdBatchLastKernelMs.restype = ctypes.c_float
     L.BrotliAmdBatchLastKernelMs.argtypes = [vp]
     L.BrotliAmdBatchLastSecondPassCount.restype = ctypes.c_uint32
@@ -149,6 +172,17 @@ def brotli_decode(data: bytes, out_cap: int):
     src = ctypes.create_string_buffer(bytes(data), max(1, len(data)))
     info = L.BrotliDecoderDecompressWithReturnInfo(len(data), ctypes.addressof(src), out_cap, ctypes.addressof(out))
     return info, out.raw[:info.decoded_size]
+
+
+def size_walk(data: bytes, flags=FLAG_LARGE_WINDOW):
+    """BrotliAmdDebugSizeWalk: the size walk on the host (no device needed) -> SizeHint"""
+    L = load_library()
+    data = bytes(data)
+    buf = ctypes.create_string_buffer(data, max(1, len(data)))
+    hint = SizeHint()
+    if L.BrotliAmdDebugSizeWalk(ctypes.addressof(buf), len(data), flags, ctypes.byref(hint)) != 0:
+        raise RuntimeError("BrotliAmdDebugSizeWalk failed")
+    return hint
 
 
 # ------------------------------------------------------------------ batch (include/brotli/batch.h)
@@ -250,6 +284,83 @@ class Batch:
         self.n = n
         results = list(res)[:n]
         return results, [outs[i].raw[:min(results[i].decoded_size, out_caps[i])] for i in range(n)]
+
+    def size_hints(self, in_ptrs, in_sizes, flags=FLAG_LARGE_WINDOW, stream=None):
+        """BrotliAmdBatchSizeHints: device pointers in -> [SizeHint], one launch of one lane a stream and a wait on `stream`"""
+        n = len(in_ptrs)
+        a_in = (ctypes.c_void_p * max(1, n))(*in_ptrs)
+        a_is = (ctypes.c_size_t * max(1, n))(*in_sizes)
+        hints = (SizeHint * max(1, n))()
+        if self._L.BrotliAmdBatchSizeHints(self._h, n, a_in, a_is, flags, hints, stream) != 0:
+            raise RuntimeError("BrotliAmdBatchSizeHints failed: " + last_error())
+        return list(hints)[:n]
+
+    def _packed_view(self, n):
+        offs = ctypes.POINTER(ctypes.c_uint64)()
+        ptr = self._L.BrotliAmdBatchPackedOutput(self._h, ctypes.byref(offs))
+        if not offs:
+            raise RuntimeError("no packed output: the last decode call on this object was not a packed call that succeeded")
+        return ptr or 0, [int(offs[i]) for i in range(n + 1)]
+
+    def decode_device_packed(self, in_ptrs, in_sizes, dict_ptrs=None, dict_sizes=None, max_out=0, flags=FLAG_LARGE_WINDOW, stream=None):
+        """BrotliAmdBatchDecodeDevicePacked: device pointers in, NO output buffers and no sizes -> (results, device pointer, offsets).
+        Synchronous.  Stream i's bytes are [offsets[i], offsets[i + 1]) of the library's buffer at the device pointer (0 where the
+        batch delivered nothing), valid until the next decode call on this object; packed_fetch() copies them to the host."""
+        n = len(in_ptrs)
+        a_in = (ctypes.c_void_p * max(1, n))(*in_ptrs)
+        a_is = (ctypes.c_size_t * max(1, n))(*in_sizes)
+        a_dp = a_ds = None
+        if dict_ptrs is not None or dict_sizes is not None:
+            if dict_ptrs is None or dict_sizes is None or len(dict_ptrs) != n or len(dict_sizes) != n:
+                raise ValueError("dict_ptrs and dict_sizes: one entry per stream each")
+            a_dp = (ctypes.c_void_p * max(1, n))(*[p or None for p in dict_ptrs])
+            a_ds = (ctypes.c_size_t * max(1, n))(*[int(v or 0) for v in dict_sizes])
+        res = (BatchResult * max(1, n))()
+        if self._L.BrotliAmdBatchDecodeDevicePacked(self._h, n, a_in, a_is, a_dp, a_ds, max_out, flags, stream, res) != 0:
+            raise RuntimeError("BrotliAmdBatchDecodeDevicePacked failed: " + last_error())
+        self.n = 0
+        ptr, offsets = self._packed_view(n)
+        return list(res)[:n], ptr, offsets
+
+    def packed_fetch(self, total):
+        """BrotliAmdBatchPackedFetch: the whole packed output of the last packed call (total = offsets[-1] bytes) as bytes"""
+        buf = ctypes.create_string_buffer(max(1, total))
+        if self._L.BrotliAmdBatchPackedFetch(self._h, ctypes.addressof(buf)) != 0:
+            raise RuntimeError("BrotliAmdBatchPackedFetch failed: " + last_error())
+        return buf.raw[:total]
+
+    def decode_packed(self, datas, dicts=None, max_out=0, flags=FLAG_LARGE_WINDOW):
+        """Host bytes in, (results, [bytes]) out without any sizes from the caller: BrotliAmdBatchDecodeHostPacked, then a fetch.
+        dicts: as in decode_host."""
+        n = len(datas)
+        ins = [ctypes.create_string_buffer(bytes(d), max(1, len(d))) for d in datas]
+        a_in = (ctypes.c_void_p * max(1, n))(*[ctypes.addressof(b) for b in ins])
+        a_is = (ctypes.c_size_t * max(1, n))(*[len(d) for d in datas])
+        a_dp = a_ds = None
+        if dicts is not None:
+            if len(dicts) != n:
+                raise ValueError("dicts: one entry per stream")
+            held = {}
+            for d in dicts:
+                if d and id(d) not in held:
+                    held[id(d)] = ctypes.create_string_buffer(bytes(d), len(d))
+            a_dp = (ctypes.c_void_p * max(1, n))(*[ctypes.addressof(held[id(d)]) if d else None for d in dicts])
+            a_ds = (ctypes.c_size_t * max(1, n))(*[len(d) if d else 0 for d in dicts])
+        res = (BatchResult * max(1, n))()
+        if self._L.BrotliAmdBatchDecodeHostPacked(self._h, n, a_in, a_is, a_dp, a_ds, max_out, flags, res) != 0:
+            raise RuntimeError("BrotliAmdBatchDecodeHostPacked failed: " + last_error())
+        self.n = 0
+        _, offsets = self._packed_view(n)
+        blob = self.packed_fetch(offsets[n])
+        return list(res)[:n], [blob[offsets[i]:offsets[i + 1]] for i in range(n)]
+
+    def last_packed_launches(self):
+        """decode launches of the last packed call: 1 where no stream had to grow"""
+        return int(self._L.BrotliAmdBatchLastPackedLaunches(self._h))
+
+    def last_packed_copies(self):
+        """ragged-copy launches of the last packed call: 0 where its first allocation was the packed output"""
+        return int(self._L.BrotliAmdBatchLastPackedCopies(self._h))
 
     def decode_host_raw(self, in_ptrs, in_sizes, out_ptrs, out_caps, flags=FLAG_LARGE_WINDOW):
         """BrotliAmdBatchDecodeHost on buffers the caller owns (host addresses as integers): nothing is copied on the Python side"""

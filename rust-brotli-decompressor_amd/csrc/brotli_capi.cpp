@@ -27,6 +27,7 @@
 #include "brotli/batch.h"
 #include "brotli/decode.h"
 #include "brotli_device_abi.h"
+#include "brotli_size_walk.h"
 
 extern "C" hipError_t brotli_amd_launch_decode(const BrotliAmdStreamDesc* descs, BrotliAmdStreamStatus* status, uint32_t n_streams,
                                                uint32_t* queue, uint8_t* scratch, uint64_t scratch_per_block, uint32_t grid,
@@ -39,6 +40,8 @@ extern "C" hipError_t brotli_amd_launch_decode_gang(const BrotliAmdStreamDesc* d
 extern "C" hipError_t brotli_amd_launch_ragged_copy(const BrotliAmdCopySeg* d_segs, uint32_t n, hipStream_t stream);
 extern "C" hipError_t brotli_amd_launch_ragged_copy_sized(const BrotliAmdCopySeg* d_segs, uint32_t n, uint64_t max_bytes, hipStream_t stream);
 extern "C" uint32_t brotli_amd_copy_tile_bytes(void);
+// (csrc/brotli_size_kernels.hip: the size walk of n streams, one lane a stream)
+extern "C" hipError_t brotli_amd_launch_size_walk(const BrotliAmdSizeDesc* d_descs, uint32_t n, uint32_t flags, BrotliAmdSizeHint* d_hints, hipStream_t stream);
 extern "C" uint32_t brotli_amd_lds_fixed_bytes(void);
 extern "C" uint32_t brotli_amd_lds_helper_bytes(uint32_t waves);
 extern "C" const uint8_t brotli_amd_dictionary[];  // dict_blob.c: data/dictionary.bin, 122784 bytes
@@ -64,6 +67,9 @@ constexpr uint64_t kProbeMinMeanBytes = 8192;     // mean compressed size of a b
 constexpr uint32_t kEngineQueueMaxPerCu = 4;      // streams per CU up to which blocks of sixteen waves, one a CU, take a batch's streams one after the other -- where the
                                                   // DEVICE says they are a command engine's kind (probe_streams); beyond, streams in flight beat the engine (2048 x 1 MiB of the
                                                   // metric's make-up: 220 GB/s eight to a CU in one-wave blocks, 151 through engine blocks)
+// Output room for compressed bytes nobody has seen decoded: six times their number, 64 KiB at least -- the streaming decoder's device buffer
+// (stream_ensure_out) and the packed decode's first capacity for what the size walk did not reach (packed_decode)
+constexpr size_t kGuessOutFactor = 6, kGuessOutFloor = (size_t)1 << 16;
 constexpr uint32_t kScanArena = 40960;  // table arena of such a block (with the engine's rings: about 108 KiB of LDS)
 
 bool hip_ok(hipError_t e, const char* what) {
@@ -155,6 +161,18 @@ struct BrotliAmdBatch {
   uint8_t* d_gang = nullptr; size_t gang_cap = 0;
   // the probe's answers for the batch it was asked about (probe_streams): the same descriptors again are not probed again
   std::vector<uint8_t> probe_kind; uint64_t probe_key = 0; float last_probe_ms = 0.0f;
+  // the size walk's descriptors and hints on the device (BrotliAmdBatchSizeHints), and the segment table of the packed decode's ragged copies
+  uint8_t* d_size = nullptr; size_t size_cap = 0;
+  uint8_t* d_pack_segs = nullptr; size_t pack_segs_cap = 0;
+  // packed decode (BrotliAmdBatchDecodeDevicePacked): the slots of its first launch and the tight buffer a gather fills are kept with the object;
+  // packed_out names the one that holds the last call's output (nullptr: there is none)
+  uint8_t* d_pack_slots = nullptr; size_t pack_slots_cap = 0;
+  uint8_t* d_pack_tight = nullptr; size_t pack_tight_cap = 0;
+  const uint8_t* packed_out = nullptr;
+  bool packed_valid = false;   // the last decode call on the object was a packed call that succeeded
+  std::vector<uint64_t> packed_offsets;
+  uint32_t last_packed_launches = 0, last_packed_copies = 0;
+  float packed_ms = 0.0f;   // decode kernel time of all its launches together
 };
 
 namespace {
@@ -621,6 +639,10 @@ extern "C" void BrotliAmdBatchDestroy(BrotliAmdBatch* b) {
   if (b->h_pin_out) (void)hipHostFree(b->h_pin_out);
   if (b->copy_stream) (void)hipStreamDestroy(b->copy_stream);
   if (b->d_settle) (void)hipFree(b->d_settle);
+  if (b->d_size) (void)hipFree(b->d_size);
+  if (b->d_pack_segs) (void)hipFree(b->d_pack_segs);
+  if (b->d_pack_slots) (void)hipFree(b->d_pack_slots);
+  if (b->d_pack_tight) (void)hipFree(b->d_pack_tight);
   if (b->h_descs) (void)hipHostFree(b->h_descs);
   if (b->h_status) (void)hipHostFree(b->h_status);
   if (b->h_order) (void)hipHostFree(b->h_order);
@@ -632,6 +654,12 @@ extern "C" void BrotliAmdBatchDestroy(BrotliAmdBatch* b) {
 }
 
 namespace {
+// A decode call ends the validity of the last packed call's output (batch.h): BrotliAmdBatchPackedOutput / PackedFetch / LastKernelMs no longer
+// speak of it.  (The buffers themselves stay with the object for the next packed call.)
+void drop_packed(BrotliAmdBatch* b) {
+  b->packed_out = nullptr; b->packed_valid = false; b->packed_offsets.clear();
+  b->last_packed_launches = b->last_packed_copies = 0; b->packed_ms = 0.0f;
+}
 // A custom dictionary as the kernel is told of it: no window reaches further back than (1 << 30) - 16 bytes (decode.rs:1831-1839), so
 // of a longer one the tail is named -- the same bytes at the same distances.
 constexpr size_t kMaxCustomDict = ((size_t)1 << 30) - 16;
@@ -646,6 +674,7 @@ extern "C" int BrotliAmdBatchDecodeDeviceDict(BrotliAmdBatch* b, uint32_t n, con
                                               const size_t* out_caps, const void* const* d_dicts, const size_t* dict_sizes, uint32_t flags,
                                               void* hip_stream) {
   if (!b || n > b->max_streams || (n && (!d_in || !in_sizes || !d_out || !out_caps))) { g_last_error = "invalid batch arguments"; return -1; }
+  drop_packed(b);
   DeviceGuard guard;
   for (uint32_t i = 0; i < n; i++) {
     BrotliAmdStreamDesc& d = b->h_descs[i];
@@ -704,6 +733,7 @@ extern "C" float BrotliAmdBatchLastProbeMs(BrotliAmdBatch* b) { return b ? b->la
 extern "C" uint32_t BrotliAmdBatchLastPool(BrotliAmdBatch* b) { return b && (b->last_gang & BROTLI_AMD_GANG_POOL_FLAG) != 0u ? 1u : 0u; }
 
 extern "C" float BrotliAmdBatchLastKernelMs(BrotliAmdBatch* b) {
+  if (b && b->packed_valid) return b->packed_ms;   // (a packed call: all its decode launches)
   if (!b || !b->launched) return 0.0f;
   float ms = 0.0f;
   if (!hip_ok(hipEventSynchronize(b->ev1), "hipEventSynchronize")) return -1.0f;
@@ -711,64 +741,124 @@ extern "C" float BrotliAmdBatchLastKernelMs(BrotliAmdBatch* b) {
   return ms + b->retry_ms;
 }
 
-extern "C" int BrotliAmdBatchDecodeHostDict(BrotliAmdBatch* b, uint32_t n, const uint8_t* const* in, const size_t* in_sizes, uint8_t* const* out,
-                                            const size_t* out_caps, const uint8_t* const* dicts, const size_t* dict_sizes, uint32_t flags,
-                                            BrotliAmdResult* results) {
-  if (!b || n > b->max_streams || (n && (!in || !in_sizes || !out || !out_caps))) { g_last_error = "invalid batch arguments"; return -1; }
-  if (n == 0) return 0;
-  DeviceGuard guard;
-  if (!hip_ok(hipSetDevice(b->device), "hipSetDevice")) return -1;
+namespace {
+
+// streams [lo, hi) copied by up to sixteen threads, split by bytes: one(i, false) says stream i's bytes, one(i, true) copies them
+template <class One>
+void parallel_copy(uint32_t lo, uint32_t hi, One&& one) {
+  const unsigned hw = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+  size_t bytes = 0; for (uint32_t i = lo; i < hi; i++) bytes += one(i, false);
+  const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>(hw, bytes >> 20));
+  if (nt <= 1) { for (uint32_t i = lo; i < hi; i++) (void)one(i, true); return; }
+  std::vector<std::thread> ts; const size_t per = (bytes + nt - 1) / nt; uint32_t i0 = lo;
+  for (unsigned t = 0; t < nt && i0 < hi; t++) {
+    uint32_t i1 = i0; size_t acc = 0;
+    while (i1 < hi && (acc < per || t + 1 == nt)) acc += one(i1++, false);
+    try { ts.emplace_back([=, &one]() { for (uint32_t i = i0; i < i1; i++) (void)one(i, true); }); }
+    catch (const std::system_error&) { for (uint32_t i = i0; i < i1; i++) (void)one(i, true); }   // (no thread to be had: this one does the part)
+    i0 = i1;
+  }
+  for (auto& t : ts) t.join();
+}
+
+// The host entry points' way to the device (BrotliAmdBatchDecodeHostDict, BrotliAmdBatchDecodeHostPacked): where each stream and each distinct
+// dictionary lies in the batch object's staging arenas.
+struct StagedInputs {
+  std::vector<std::pair<const uint8_t*, size_t>> dict_of;   // distinct (pointer, size) pairs (what name_dictionary would keep of them), in order of appearance
+  std::vector<size_t> dict_off, in_off;
+  std::vector<int> dict_ix;                                 // per stream: its pair, -1 none
+  size_t dict_total = 0, in_total = 0;
+  const uint8_t* dict_ptr(const BrotliAmdBatch* b, uint32_t i) const { return dict_ix[i] >= 0 ? b->d_stage_dict + dict_off[(size_t)dict_ix[i]] : nullptr; }
+  size_t dict_size(uint32_t i) const { return dict_ix[i] >= 0 ? dict_of[(size_t)dict_ix[i]].second : 0; }
+};
+
+// Lays the inputs out and makes the device arenas, the pinned host side and the copy stream.  *pinned: whether the host gave pinned memory for the
+// inputs (where it has none to give, the transfers go stream by stream from the caller's own, pageable, buffers).
+bool stage_prepare(BrotliAmdBatch* b, uint32_t n, const size_t* in_sizes, const uint8_t* const* dicts, const size_t* dict_sizes, StagedInputs& s, bool* pinned) {
   // custom dictionaries: every distinct (pointer, size) pair is uploaded once -- a batch of documents against one shared dictionary
   // reads one copy of it, which stays in the device's caches
-  std::vector<std::pair<const uint8_t*, size_t>> dict_of;   // distinct pairs (what name_dictionary would keep of them), in order of appearance
-  std::vector<size_t> dict_off;
-  std::vector<int> dict_ix(n, -1);
-  size_t dict_total = 0;
+  s.dict_ix.assign(n, -1); s.in_off.resize(n);
   if (dicts && dict_sizes) {
     for (uint32_t i = 0; i < n; i++) {
       if (dicts[i] == nullptr || dict_sizes[i] == 0) continue;
       const size_t tail = std::min(dict_sizes[i], kMaxCustomDict);
       const std::pair<const uint8_t*, size_t> key(dicts[i] + (dict_sizes[i] - tail), tail);
       size_t k = 0;
-      if (i != 0 && dict_ix[i - 1] >= 0 && dict_of[(size_t)dict_ix[i - 1]] == key) k = (size_t)dict_ix[i - 1];   // (the rule: the stream before's)
-      else k = (size_t)(std::find(dict_of.begin(), dict_of.end(), key) - dict_of.begin());
-      if (k == dict_of.size()) { dict_of.push_back(key); dict_off.push_back(dict_total); dict_total += (tail + 63) & ~(size_t)63; dict_total += 64; }
-      dict_ix[i] = (int)k;
+      if (i != 0 && s.dict_ix[i - 1] >= 0 && s.dict_of[(size_t)s.dict_ix[i - 1]] == key) k = (size_t)s.dict_ix[i - 1];   // (the rule: the stream before's)
+      else k = (size_t)(std::find(s.dict_of.begin(), s.dict_of.end(), key) - s.dict_of.begin());
+      if (k == s.dict_of.size()) { s.dict_of.push_back(key); s.dict_off.push_back(s.dict_total); s.dict_total += (tail + 63) & ~(size_t)63; s.dict_total += 64; }
+      s.dict_ix[i] = (int)k;
     }
   }
-  if (dict_total > b->stage_dict_cap) {
+  if (s.dict_total > b->stage_dict_cap) {
     if (b->d_stage_dict) (void)hipFree(b->d_stage_dict);
     b->d_stage_dict = nullptr; b->stage_dict_cap = 0;
-    if (!hip_ok(hipMalloc(&b->d_stage_dict, dict_total), "hipMalloc(dictionary arena)")) return -1;
-    b->stage_dict_cap = dict_total;
+    if (!hip_ok(hipMalloc(&b->d_stage_dict, s.dict_total), "hipMalloc(dictionary arena)")) return false;
+    b->stage_dict_cap = s.dict_total;
   }
-  // one input arena and one output arena, 64-byte aligned slots
-  std::vector<size_t> in_off(n), out_off(n);
-  size_t in_total = 0, out_total = 0;
-  for (uint32_t i = 0; i < n; i++) {
-    in_off[i] = in_total; in_total += (in_sizes[i] + 63) & ~(size_t)63; in_total += 64;
-    out_off[i] = out_total; out_total += (out_caps[i] + 63) & ~(size_t)63; out_total += 64;
-  }
-  if (in_total > b->stage_in_cap) {
+  // one input arena, 64-byte aligned slots
+  for (uint32_t i = 0; i < n; i++) { s.in_off[i] = s.in_total; s.in_total += (in_sizes[i] + 63) & ~(size_t)63; s.in_total += 64; }
+  if (s.in_total > b->stage_in_cap) {
     if (b->d_stage_in) (void)hipFree(b->d_stage_in);
     b->d_stage_in = nullptr; b->stage_in_cap = 0;
-    if (!hip_ok(hipMalloc(&b->d_stage_in, in_total), "hipMalloc(input arena)")) return -1;
-    b->stage_in_cap = in_total;
+    if (!hip_ok(hipMalloc(&b->d_stage_in, s.in_total), "hipMalloc(input arena)")) return false;
+    b->stage_in_cap = s.in_total;
   }
+  *pinned = true;
+  if (s.in_total > b->pin_in_cap) {
+    if (b->h_pin_in) (void)hipHostFree(b->h_pin_in);
+    b->h_pin_in = nullptr; b->pin_in_cap = 0;
+    if (hipHostMalloc(&b->h_pin_in, s.in_total, hipHostMallocDefault) == hipSuccess) b->pin_in_cap = s.in_total;
+    else { (void)hipGetLastError(); b->h_pin_in = nullptr; *pinned = false; }
+  }
+  return b->copy_stream || hip_ok(hipStreamCreateWithFlags(&b->copy_stream, hipStreamNonBlocking), "hipStreamCreate");
+}
+
+// The dictionaries and the inputs on their way (copy_stream; the caller waits on it): with pinned memory the inputs are packed into it by several
+// threads, piece by piece, each piece's transfer behind it.
+bool stage_upload(BrotliAmdBatch* b, uint32_t n, const uint8_t* const* in, const size_t* in_sizes, const StagedInputs& s, bool pinned) {
+  for (size_t k = 0; k < s.dict_of.size(); k++)
+    if (!hip_ok(hipMemcpyAsync(b->d_stage_dict + s.dict_off[k], s.dict_of[k].first, s.dict_of[k].second, hipMemcpyHostToDevice, b->copy_stream), "hipMemcpyAsync(dictionary)")) return false;
+  if (!pinned) {
+    for (uint32_t i = 0; i < n; i++)
+      if (in_sizes[i] && !hip_ok(hipMemcpyAsync(b->d_stage_in + s.in_off[i], in[i], in_sizes[i], hipMemcpyHostToDevice, b->copy_stream), "hipMemcpyAsync(input)")) return false;
+    return true;
+  }
+  uint32_t lo = 0;
+  while (lo < n) {
+    uint32_t hi = lo; size_t acc = 0;
+    while (hi < n && acc < ((size_t)32 << 20)) acc += in_sizes[hi++];
+    parallel_copy(lo, hi, [&](uint32_t i, bool go) -> size_t { if (go && in_sizes[i]) std::memcpy(b->h_pin_in + s.in_off[i], in[i], in_sizes[i]); return in_sizes[i]; });
+    const size_t o0 = s.in_off[lo], o1 = hi < n ? s.in_off[hi] : s.in_total;
+    if (!hip_ok(hipMemcpyAsync(b->d_stage_in + o0, b->h_pin_in + o0, o1 - o0, hipMemcpyHostToDevice, b->copy_stream), "hipMemcpyAsync(input)")) return false;
+    lo = hi;
+  }
+  return true;
+}
+
+}  // namespace
+
+extern "C" int BrotliAmdBatchDecodeHostDict(BrotliAmdBatch* b, uint32_t n, const uint8_t* const* in, const size_t* in_sizes, uint8_t* const* out,
+                                            const size_t* out_caps, const uint8_t* const* dicts, const size_t* dict_sizes, uint32_t flags,
+                                            BrotliAmdResult* results) {
+  if (!b || n > b->max_streams || (n && (!in || !in_sizes || !out || !out_caps))) { g_last_error = "invalid batch arguments"; return -1; }
+  drop_packed(b);
+  if (n == 0) return 0;
+  DeviceGuard guard;
+  if (!hip_ok(hipSetDevice(b->device), "hipSetDevice")) return -1;
+  StagedInputs staged;
+  bool pinned = true;
+  if (!stage_prepare(b, n, in_sizes, dicts, dict_sizes, staged, &pinned)) return -1;
+  const std::vector<size_t>& in_off = staged.in_off;
+  // one output arena, 64-byte aligned slots, and its pinned host side
+  std::vector<size_t> out_off(n);
+  size_t out_total = 0;
+  for (uint32_t i = 0; i < n; i++) { out_off[i] = out_total; out_total += (out_caps[i] + 63) & ~(size_t)63; out_total += 64; }
   if (out_total > b->stage_out_cap) {
     if (b->d_stage_out) (void)hipFree(b->d_stage_out);
     b->d_stage_out = nullptr; b->stage_out_cap = 0;
     if (!hip_ok(hipMalloc(&b->d_stage_out, out_total), "hipMalloc(output arena)")) return -1;
     b->stage_out_cap = out_total;
-  }
-  // pinned staging on the host (kept with the batch object) and a stream for the transfers; where the host has no pinned memory to give,
-  // the transfers go stream by stream from and to the caller's own (pageable) buffers
-  bool pinned = true;
-  if (in_total > b->pin_in_cap) {
-    if (b->h_pin_in) (void)hipHostFree(b->h_pin_in);
-    b->h_pin_in = nullptr; b->pin_in_cap = 0;
-    if (hipHostMalloc(&b->h_pin_in, in_total, hipHostMallocDefault) == hipSuccess) b->pin_in_cap = in_total;
-    else { (void)hipGetLastError(); b->h_pin_in = nullptr; pinned = false; }
   }
   if (pinned && out_total > b->pin_out_cap) {
     if (b->h_pin_out) (void)hipHostFree(b->h_pin_out);
@@ -776,47 +866,14 @@ extern "C" int BrotliAmdBatchDecodeHostDict(BrotliAmdBatch* b, uint32_t n, const
     if (hipHostMalloc(&b->h_pin_out, out_total, hipHostMallocDefault) == hipSuccess) b->pin_out_cap = out_total;
     else { (void)hipGetLastError(); b->h_pin_out = nullptr; pinned = false; }
   }
-  if (!b->copy_stream && !hip_ok(hipStreamCreateWithFlags(&b->copy_stream, hipStreamNonBlocking), "hipStreamCreate")) return -1;
-  for (size_t k = 0; k < dict_of.size(); k++)
-    if (!hip_ok(hipMemcpyAsync(b->d_stage_dict + dict_off[k], dict_of[k].first, dict_of[k].second, hipMemcpyHostToDevice, b->copy_stream), "hipMemcpyAsync(dictionary)")) return -1;
-  const unsigned hw = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-  // streams [lo, hi) copied by up to `hw` threads, split by bytes
-  auto parallel_copy = [&](uint32_t lo, uint32_t hi, auto&& one) {
-    size_t bytes = 0; for (uint32_t i = lo; i < hi; i++) bytes += one(i, false);
-    const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>(hw, bytes >> 20));
-    if (nt <= 1) { for (uint32_t i = lo; i < hi; i++) (void)one(i, true); return; }
-    std::vector<std::thread> ts; const size_t per = (bytes + nt - 1) / nt; uint32_t i0 = lo;
-    for (unsigned t = 0; t < nt && i0 < hi; t++) {
-      uint32_t i1 = i0; size_t acc = 0;
-      while (i1 < hi && (acc < per || t + 1 == nt)) acc += one(i1++, false);
-      try { ts.emplace_back([=, &one]() { for (uint32_t i = i0; i < i1; i++) (void)one(i, true); }); }
-      catch (const std::system_error&) { for (uint32_t i = i0; i < i1; i++) (void)one(i, true); }   // (no thread to be had: this one does the part)
-      i0 = i1;
-    }
-    for (auto& t : ts) t.join();
-  };
-  // upload: the inputs packed into pinned memory by several threads, piece by piece, each piece's transfer behind it
-  if (!pinned) {
-    for (uint32_t i = 0; i < n; i++)
-      if (in_sizes[i] && !hip_ok(hipMemcpyAsync(b->d_stage_in + in_off[i], in[i], in_sizes[i], hipMemcpyHostToDevice, b->copy_stream), "hipMemcpyAsync(input)")) return -1;
-  } else {
-    uint32_t lo = 0;
-    while (lo < n) {
-      uint32_t hi = lo; size_t acc = 0;
-      while (hi < n && acc < ((size_t)32 << 20)) acc += in_sizes[hi++];
-      parallel_copy(lo, hi, [&](uint32_t i, bool go) -> size_t { if (go && in_sizes[i]) std::memcpy(b->h_pin_in + in_off[i], in[i], in_sizes[i]); return in_sizes[i]; });
-      const size_t o0 = in_off[lo], o1 = hi < n ? in_off[hi] : in_total;
-      if (!hip_ok(hipMemcpyAsync(b->d_stage_in + o0, b->h_pin_in + o0, o1 - o0, hipMemcpyHostToDevice, b->copy_stream), "hipMemcpyAsync(input)")) return -1;
-      lo = hi;
-    }
-  }
+  if (!stage_upload(b, n, in, in_sizes, staged, pinned)) return -1;
   for (uint32_t i = 0; i < n; i++) {
     BrotliAmdStreamDesc& d = b->h_descs[i];
     std::memset(&d, 0, sizeof d);
     d.in = b->d_stage_in + in_off[i]; d.in_size = in_sizes[i];
     d.out = b->d_stage_out + out_off[i]; d.out_cap = out_caps[i];
     d.flags = flags & (BROTLI_AMD_FLAG_LARGE_WINDOW | BROTLI_AMD_FLAG_NO_CANNY | BROTLI_AMD_BATCH_SPILL_IN_PLACE);
-    if (dict_ix[i] >= 0) { d.dict = b->d_stage_dict + dict_off[(size_t)dict_ix[i]]; d.dict_size = dict_of[(size_t)dict_ix[i]].second; }
+    if (staged.dict_ix[i] >= 0) { d.dict = staged.dict_ptr(b, i); d.dict_size = staged.dict_size(i); }
   }
   b->exact_limit = !(flags & BROTLI_AMD_BATCH_EAGER_OUTPUT_LIMIT);
   if (!hip_ok(hipStreamSynchronize(b->copy_stream), "hipStreamSynchronize(upload)")) return -1;
@@ -871,6 +928,249 @@ extern "C" int BrotliAmdBatchDecodeHostDict(BrotliAmdBatch* b, uint32_t n, const
 extern "C" int BrotliAmdBatchDecodeHost(BrotliAmdBatch* b, uint32_t n, const uint8_t* const* in, const size_t* in_sizes, uint8_t* const* out,
                                         const size_t* out_caps, uint32_t flags, BrotliAmdResult* results) {
   return BrotliAmdBatchDecodeHostDict(b, n, in, in_sizes, out, out_caps, nullptr, nullptr, flags, results);
+}
+
+// ================================== size hints and the packed decode (batch.h) ==================================
+namespace {
+
+// a device buffer of the batch object, at least `need` bytes (its contents are not kept)
+bool ensure_dev(uint8_t** p, size_t* cap, size_t need, const char* what) {
+  if (*p && need <= *cap) return true;
+  if (*p) (void)hipFree(*p);
+  *p = nullptr; *cap = 0;
+  if (!hip_ok(hipMalloc(p, need), what)) { *p = nullptr; return false; }
+  *cap = need;
+  return true;
+}
+
+// the size walk of n streams on `stream`, waited for: hints[0..n) on the host
+int size_hints_device(BrotliAmdBatch* b, uint32_t n, const void* const* d_in, const size_t* in_sizes, uint32_t flags, BrotliAmdSizeHint* hints,
+                      hipStream_t stream) {
+  const size_t descs_bytes = sizeof(BrotliAmdSizeDesc) * (size_t)n;
+  if (!ensure_dev(&b->d_size, &b->size_cap, descs_bytes + sizeof(BrotliAmdSizeHint) * (size_t)n, "hipMalloc(size hints)")) return -1;
+  BrotliAmdSizeDesc* d_descs = reinterpret_cast<BrotliAmdSizeDesc*>(b->d_size);
+  BrotliAmdSizeHint* d_hints = reinterpret_cast<BrotliAmdSizeHint*>(b->d_size + descs_bytes);
+  std::vector<BrotliAmdSizeDesc> descs(n);
+  for (uint32_t i = 0; i < n; i++) descs[i] = BrotliAmdSizeDesc{static_cast<const uint8_t*>(d_in[i]), in_sizes[i]};
+  bool ok = hip_ok(hipMemcpyAsync(d_descs, descs.data(), descs_bytes, hipMemcpyHostToDevice, stream), "hipMemcpyAsync(size descs)");
+  ok = ok && hip_ok(brotli_amd_launch_size_walk(d_descs, n, flags & BROTLI_AMD_BATCH_LARGE_WINDOW, d_hints, stream), "brotli_amd_size_walk_kernel launch");
+  ok = ok && hip_ok(hipMemcpyAsync(hints, d_hints, sizeof(BrotliAmdSizeHint) * (size_t)n, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(size hints)");
+  // (waited for in any case: the copies read and write the caller's and this function's pageable memory)
+  return hip_ok(hipStreamSynchronize(stream), "hipStreamSynchronize(size hints)") && ok ? 0 : -1;
+}
+
+// one ragged-copy launch of m segments on `stream` (the table is uploaded from pageable memory: the caller waits on the stream before `segs` goes)
+bool packed_copy(BrotliAmdBatch* b, const std::vector<BrotliAmdCopySeg>& segs, uint64_t bytes, hipStream_t stream) {
+  const uint32_t m = (uint32_t)segs.size();
+  if (!ensure_dev(&b->d_pack_segs, &b->pack_segs_cap, sizeof(BrotliAmdCopySeg) * (size_t)m, "hipMalloc(copy segments)")) return false;
+  BrotliAmdCopySeg* d_segs = reinterpret_cast<BrotliAmdCopySeg*>(b->d_pack_segs);
+  return hip_ok(hipMemcpyAsync(d_segs, segs.data(), sizeof(BrotliAmdCopySeg) * (size_t)m, hipMemcpyHostToDevice, stream), "hipMemcpyAsync(copy segments)") &&
+         hip_ok(brotli_amd_launch_ragged_copy_sized(d_segs, m, bytes, stream), "brotli_amd_ragged_copy_kernel launch");
+}
+
+constexpr uint64_t kPackGrowRound = 65536;   // a grown slot is a multiple of this
+
+// h_descs[0..m) filled: one launch through submit() and BrotliAmdBatchWait (larger-arena passes included), no second look at full buffers
+bool packed_launch(BrotliAmdBatch* b, uint32_t m, hipStream_t stream) {
+  b->exact_limit = false;
+  if (submit(b, m, stream) != 0 || BrotliAmdBatchWait(b, nullptr) != 0) return false;
+  b->last_packed_launches++;
+  const float ms = BrotliAmdBatchLastKernelMs(b);
+  if (ms > 0.0f) b->packed_ms += ms;
+  return true;
+}
+
+// BrotliAmdBatchDecodeDevicePacked behind its argument checks (the steps: batch.h)
+int packed_decode(BrotliAmdBatch* b, uint32_t n, const void* const* d_in, const size_t* in_sizes, const void* const* d_dicts,
+                  const size_t* dict_sizes, uint64_t max_out_bytes, uint32_t flags, hipStream_t stream, BrotliAmdResult* results) {
+  drop_packed(b);
+  if (n == 0) { b->packed_offsets.assign(1, 0); b->packed_valid = true; b->n = 0; b->launched = false; return 0; }
+  if (!hip_ok(hipSetDevice(b->device), "hipSetDevice")) return -1;
+  // 1. the hints; 2. first capacities; the slots back to back
+  std::vector<BrotliAmdSizeHint> hints(n);
+  if (size_hints_device(b, n, d_in, in_sizes, flags, hints.data(), stream) != 0) return -1;
+  const uint64_t limit = max_out_bytes ? max_out_bytes : ~(uint64_t)0;
+  std::vector<uint64_t> cap(n);
+  std::vector<uint8_t*> out(n);
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const BrotliAmdSizeHint& h = hints[i];
+    const uint64_t c = h.exact && h.status == BROTLI_AMD_SIZE_OK ? h.bytes
+                                                                 : std::max<uint64_t>(kGuessOutFloor, h.bytes + kGuessOutFactor * ((uint64_t)in_sizes[i] - h.walked_in));
+    cap[i] = std::min(c, limit);
+    total += cap[i];
+  }
+  if (!ensure_dev(&b->d_pack_slots, &b->pack_slots_cap, (size_t)total + 256, "hipMalloc(packed slots)")) return -1;   // (+: a slot of no bytes at the end has an address as well)
+  { uint64_t at = 0; for (uint32_t i = 0; i < n; i++) { out[i] = b->d_pack_slots + at; at += cap[i]; } }
+  const uint32_t desc_flags = flags & (BROTLI_AMD_FLAG_LARGE_WINDOW | BROTLI_AMD_FLAG_NO_CANNY | BROTLI_AMD_BATCH_SPILL_IN_PLACE);
+  const auto fill_desc = [&](BrotliAmdStreamDesc& d, uint32_t i) {
+    std::memset(&d, 0, sizeof d);
+    d.in = static_cast<const uint8_t*>(d_in[i]); d.in_size = in_sizes[i];
+    d.out = out[i]; d.out_cap = cap[i];
+    d.flags = desc_flags;
+    if (d_dicts && dict_sizes) name_dictionary(d, static_cast<const uint8_t*>(d_dicts[i]), dict_sizes[i]);
+  };
+  std::vector<void*> rounds;   // the growth rounds' allocations: freed when the call is over
+  const auto done = [&](int rc) {
+    for (void* p : rounds) (void)hipFree(p);
+    b->n = 0; b->launched = false;   // (nothing for BrotliAmdBatchWait or BrotliAmdBatchRelaunch to come back to)
+    if (rc != 0) drop_packed(b);
+    else b->packed_valid = true;
+    return rc;
+  };
+  // 3. one launch over all of them
+  for (uint32_t i = 0; i < n; i++) fill_desc(b->h_descs[i], i);
+  if (!packed_launch(b, n, stream)) return done(-1);
+  std::vector<BrotliAmdStreamStatus> st(b->h_status, b->h_status + n);
+  // 4. the streams whose slot was too small, and they alone: a larger slot, what they have decoded moved there, resumed
+  bool moved = false;
+  for (;;) {
+    std::vector<uint32_t> idx;
+    for (uint32_t i = 0; i < n; i++) if (st[i].result == BROTLI_DECODER_RESULT_NEEDS_MORE_OUTPUT && cap[i] < limit) idx.push_back(i);
+    if (idx.empty()) break;
+    const uint32_t m = (uint32_t)idx.size();
+    std::vector<uint64_t> ncap(m);
+    uint64_t rtotal = 0;
+    for (uint32_t j = 0; j < m; j++) {
+      const uint32_t i = idx[j];
+      uint64_t want = std::max<uint64_t>(2u * cap[i], 1u);
+      const uint64_t at_in = st[i].resume.window_bits != 0u ? st[i].resume.bit_pos >> 3 : 0u;
+      if (at_in != 0u) {   // what the stream's ratio up to its resume point says of the whole
+        const unsigned __int128 est = (unsigned __int128)st[i].resume.out_pos * in_sizes[i] / at_in;
+        want = std::max<uint64_t>(want, est > (unsigned __int128)limit ? limit : (uint64_t)est);
+      }
+      want = want > limit - (kPackGrowRound - 1u) ? limit : (want + kPackGrowRound - 1u) / kPackGrowRound * kPackGrowRound;
+      ncap[j] = std::min(want, limit);
+      rtotal += ncap[j];
+    }
+    uint8_t* fresh = nullptr;
+    if (!hip_ok(hipMalloc(&fresh, (size_t)rtotal + 256), "hipMalloc(grown packed slots)")) return done(-1);
+    rounds.push_back(fresh);
+    // everything below the resume point is final: the last metablock boundary, or the command boundary noted inside the metablock behind it
+    std::vector<BrotliAmdCopySeg> segs(m);
+    uint64_t at = 0, copy_bytes = 0;
+    for (uint32_t j = 0; j < m; j++) {
+      const uint32_t i = idx[j];
+      const BrotliAmdResume& r = st[i].resume;
+      uint64_t keep = r.window_bits == 0u ? 0u : std::max<uint64_t>(r.out_pos, r.mid_valid ? r.mid_out_pos : 0u);
+      keep = std::min(keep, cap[i]);
+      segs[j] = BrotliAmdCopySeg{out[i], fresh + at, keep};
+      copy_bytes += keep;
+      out[i] = fresh + at; cap[i] = ncap[j]; at += ncap[j];
+    }
+    if (!packed_copy(b, segs, copy_bytes, stream)) { (void)hipStreamSynchronize(stream); return done(-1); }
+    b->last_packed_copies++;
+    for (uint32_t j = 0; j < m; j++) {
+      const uint32_t i = idx[j];
+      BrotliAmdStreamDesc& d = b->h_descs[j];
+      fill_desc(d, i);
+      if (st[i].resume.window_bits != 0u) { d.flags |= BROTLI_AMD_FLAG_RESUME; d.resume = st[i].resume; }   // (else: no boundary yet, from byte 0 again)
+    }
+    if (!packed_launch(b, m, stream)) return done(-1);
+    for (uint32_t j = 0; j < m; j++) {
+      BrotliAmdStreamStatus& first = st[idx[j]];
+      BrotliAmdStreamStatus next = b->h_status[j];
+      if (first.resume.window_bits != 0u) {   // the counters are sums over a stream's launches
+        next.num_metablocks += first.num_metablocks; next.spilled_metablocks += first.spilled_metablocks;
+        next.num_commands += first.num_commands; next.engine_commands += first.engine_commands;
+      }
+      first = next;
+    }
+    moved = true;
+  }
+  // 5. pack
+  b->packed_offsets.resize((size_t)n + 1);
+  b->packed_offsets[0] = 0;
+  bool in_place = !moved;
+  for (uint32_t i = 0; i < n; i++) {
+    const uint64_t got = std::min(st[i].decoded_size, cap[i]);
+    st[i].decoded_size = got;
+    in_place = in_place && got == cap[i];
+    b->packed_offsets[i + 1] = b->packed_offsets[i] + got;
+  }
+  if (in_place) b->packed_out = b->d_pack_slots;
+  else {
+    const uint64_t bytes = b->packed_offsets[n];
+    if (!ensure_dev(&b->d_pack_tight, &b->pack_tight_cap, (size_t)bytes + 256, "hipMalloc(packed output)")) return done(-1);
+    std::vector<BrotliAmdCopySeg> segs(n);
+    for (uint32_t i = 0; i < n; i++) segs[i] = BrotliAmdCopySeg{out[i], b->d_pack_tight + b->packed_offsets[i], b->packed_offsets[i + 1] - b->packed_offsets[i]};
+    const bool ok = packed_copy(b, segs, bytes, stream);
+    if (!hip_ok(hipStreamSynchronize(stream), "hipStreamSynchronize(packed gather)") || !ok) return done(-1);
+    b->last_packed_copies++;
+    b->packed_out = b->d_pack_tight;
+  }
+  if (results) {
+    for (uint32_t i = 0; i < n; i++) {
+      const BrotliAmdStreamStatus& s = st[i];
+      BrotliAmdResult& r = results[i];
+      r.result = s.result; r.error_code = s.error_code; r.decoded_size = s.decoded_size; r.consumed = s.consumed;
+      r.produced = s.produced; r.num_metablocks = s.num_metablocks; r.spilled_metablocks = s.spilled_metablocks; r.num_commands = s.num_commands;
+      r.engine_commands = s.engine_commands; r.reserved = 0;
+    }
+  }
+  return done(0);
+}
+
+}  // namespace
+
+extern "C" int BrotliAmdDebugSizeWalk(const uint8_t* in, size_t n, uint32_t flags, BrotliAmdSizeHint* hint) {
+  if (!hint || (n && !in)) return -1;
+  *hint = brotli_amd_size_walk(BrotliAmdWalkBytes{in}, n, flags);
+  return 0;
+}
+
+extern "C" int BrotliAmdBatchSizeHints(BrotliAmdBatch* b, uint32_t n, const void* const* d_in, const size_t* in_sizes, uint32_t flags,
+                                       BrotliAmdSizeHint* hints, void* hip_stream) {
+  if (!b || (n && (!d_in || !in_sizes || !hints))) { g_last_error = "invalid batch arguments"; return -1; }
+  if (n == 0) return 0;
+  DeviceGuard guard;
+  if (!hip_ok(hipSetDevice(b->device), "hipSetDevice")) return -1;
+  return size_hints_device(b, n, d_in, in_sizes, flags, hints, static_cast<hipStream_t>(hip_stream));
+}
+
+extern "C" int BrotliAmdBatchDecodeDevicePacked(BrotliAmdBatch* b, uint32_t n, const void* const* d_in, const size_t* in_sizes,
+                                                const void* const* d_dicts, const size_t* dict_sizes, uint64_t max_out_bytes, uint32_t flags,
+                                                void* hip_stream, BrotliAmdResult* results) {
+  if (!b || n > b->max_streams || (n && (!d_in || !in_sizes))) { g_last_error = "invalid batch arguments"; return -1; }
+  DeviceGuard guard;
+  return packed_decode(b, n, d_in, in_sizes, d_dicts, dict_sizes, max_out_bytes, flags, static_cast<hipStream_t>(hip_stream), results);
+}
+
+extern "C" const void* BrotliAmdBatchPackedOutput(BrotliAmdBatch* b, const uint64_t** offsets) {
+  if (offsets) *offsets = b && !b->packed_offsets.empty() ? b->packed_offsets.data() : nullptr;
+  return b ? b->packed_out : nullptr;
+}
+
+extern "C" int BrotliAmdBatchPackedFetch(BrotliAmdBatch* b, uint8_t* host_dst) {
+  if (!b || b->packed_offsets.empty()) { g_last_error = "no packed output"; return -1; }
+  const uint64_t bytes = b->packed_offsets.back();
+  if (bytes == 0) return 0;
+  if (!b->packed_out || !host_dst) { g_last_error = "no packed output"; return -1; }
+  DeviceGuard guard;
+  if (!hip_ok(hipSetDevice(b->device), "hipSetDevice")) return -1;
+  return hip_ok(hipMemcpy(host_dst, b->packed_out, (size_t)bytes, hipMemcpyDeviceToHost), "hipMemcpy(packed output)") ? 0 : -1;
+}
+
+extern "C" uint32_t BrotliAmdBatchLastPackedLaunches(BrotliAmdBatch* b) { return b ? b->last_packed_launches : 0; }
+extern "C" uint32_t BrotliAmdBatchLastPackedCopies(BrotliAmdBatch* b) { return b ? b->last_packed_copies : 0; }
+
+extern "C" int BrotliAmdBatchDecodeHostPacked(BrotliAmdBatch* b, uint32_t n, const uint8_t* const* in, const size_t* in_sizes,
+                                              const uint8_t* const* dicts, const size_t* dict_sizes, uint64_t max_out_bytes, uint32_t flags,
+                                              BrotliAmdResult* results) {
+  if (!b || n > b->max_streams || (n && (!in || !in_sizes))) { g_last_error = "invalid batch arguments"; return -1; }
+  DeviceGuard guard;
+  if (n == 0) return packed_decode(b, 0, nullptr, nullptr, nullptr, nullptr, max_out_bytes, flags, nullptr, results);
+  if (!hip_ok(hipSetDevice(b->device), "hipSetDevice")) return -1;
+  // the staging of BrotliAmdBatchDecodeHostDict: every distinct dictionary once into its arena, the streams into the input arena
+  StagedInputs staged;
+  bool pinned = true;
+  if (!stage_prepare(b, n, in_sizes, dicts, dict_sizes, staged, &pinned)) return -1;
+  const bool ok = stage_upload(b, n, in, in_sizes, staged, pinned);
+  if (!hip_ok(hipStreamSynchronize(b->copy_stream), "hipStreamSynchronize(upload)") || !ok) return -1;
+  std::vector<const void*> d_in(n), d_dict(n, nullptr);
+  std::vector<size_t> d_dict_size(n, 0);
+  for (uint32_t i = 0; i < n; i++) { d_in[i] = b->d_stage_in + staged.in_off[i]; d_dict[i] = staged.dict_ptr(b, i); d_dict_size[i] = staged.dict_size(i); }
+  return packed_decode(b, n, d_in.data(), in_sizes, d_dict.data(), d_dict_size.data(), max_out_bytes, flags, nullptr, results);
 }
 
 extern "C" const char* BrotliAmdLastError(void) { return g_last_error.c_str(); }
@@ -1223,7 +1523,7 @@ int fetch_output(BrotliDecoderState* s, uint64_t deliverable) {
 // The device's output buffer of the state before a launch: room for six times the compressed bytes not yet behind a metablock boundary.
 bool stream_ensure_out(BrotliDecoderState* s) {
   const size_t pending_in = (size_t)(s->d_in_len - s->in_base);
-  return dev_rebase(&s->d_out, &s->d_out_cap, 0, s->d_out_cap, std::max<size_t>(s->d_out_cap, std::max<size_t>(1 << 16, 6 * pending_in)));
+  return dev_rebase(&s->d_out, &s->d_out_cap, 0, s->d_out_cap, std::max<size_t>(s->d_out_cap, std::max<size_t>(kGuessOutFloor, kGuessOutFactor * pending_in)));
 }
 
 // The state's descriptor of a launch: everything received so far, from the last completed metablock boundary.
