@@ -6,11 +6,23 @@ points, chosen literal context modes (MSB6 included) and context maps, chosen NP
 compressed, stored, metadata and empty metablocks.  It is not a compressor: the caller supplies the commands (or lets
 `greedy_commands` find some) and the plan; the emitter builds the prefix codes from the resulting histograms and
 serialises everything.  Its output is validated against Google's libbrotlidec where that library exists
-(tools/make_emitter_vectors.py) and pinned by the committed vectors in tests/golden/emitter/.
+(tools/make_emitter_vectors.py, tools/make_word_vectors.py) and pinned by the committed vectors in tests/golden/emitter/
+and tests/golden/emitter_words/.
 
     w = BitWriter(); write_stream_header(w, 22)
-    emit_compressed(w, data, commands, plan, is_last=False); emit_stored(w, raw); emit_metadata(w, b"..."); emit_last_empty(w)
+    emit_compressed(w, commands, plan, is_last=False); emit_stored(w, raw); emit_metadata(w, b"..."); emit_last_empty(w)
     stream = w.finish()
+
+A command is (insert bytes, copy_len, what), `what` being
+    an int                         an explicit distance (one beyond the maximum distance names a dictionary word, as in any decoder),
+    ("word", word_idx, transform)  a word of the static dictionary: the emitter computes the distance at the command's position,
+    ("ring", k)                    short distance code k (0 .. 15) against the ring of the last four distances, (4, 11, 15, 16) at first,
+    ("implicit",)                  a command symbol below 128: the last distance, no distance symbol,
+    ("raw", distance)              an explicit distance written as given (`unchecked=True`: streams that are invalid on purpose).
+Words need `wbits` (the maximum distance is min(P + len(dictionary), (1 << wbits) - 16)).  The words and their 121
+transforms are restated here in plain Python from RFC 7932 Appendix A / B (`dictionary_word`, `transform_word`), over
+the tables of csrc/brotli_tables_gen.h and data/dictionary.bin; no decoder is called, so that the bytes the emitter
+expects are an opinion of their own beside the oracle's and libbrotlidec's.  `log=[]` receives one record per command.
 """
 import heapq
 
@@ -293,6 +305,78 @@ def literal_context(mode, p1, p2):
     return _CTX_LUT[mode * 512 + p1] | _CTX_LUT[mode * 512 + 256 + p2]
 
 
+# ------------------------------------------------------------------ the static dictionary (RFC 7932 section 8, appendices A and B)
+_TABLES = None
+RING_INIT = (4, 11, 15, 16)  # last, second last, third last, fourth last distance at the start of a stream (section 4)
+NUM_TRANSFORMS = 121
+
+
+def tables():
+    """{"size_bits": [25], "offsets": [25], "transforms": [(prefix, type, suffix)] * 121, "words": the 122784 bytes} out of
+    csrc/brotli_tables_gen.h (pinned against the reference by tests/test_tables_vs_reference.py) and data/dictionary.bin"""
+    global _TABLES
+    if _TABLES is None:
+        import os
+        import re
+        pkg = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "rust-brotli-decompressor_amd")
+        h = open(os.path.join(pkg, "csrc", "brotli_tables_gen.h")).read()
+
+        def array(name):
+            m = re.search(name + r"\[[^\]]*\]\s*=\s*\{(.*?)\};", h, re.S)
+            return [int(x) for x in re.findall(r"\d+", m.group(1))]
+        pool, tr = bytes(array("kAffixPool")), array("kTransforms")
+        assert len(tr) == 3 * NUM_TRANSFORMS
+        affix = lambda off: pool[off:pool.index(0, off)]  # (NUL-terminated strings)
+        _TABLES = {"size_bits": array("kDictSizeBitsByLength"), "offsets": array("kDictOffsetsByLength"),
+                   "transforms": [(affix(tr[3 * t]), tr[3 * t + 1], affix(tr[3 * t + 2])) for t in range(NUM_TRANSFORMS)],
+                   "words": open(os.path.join(pkg, "data", "dictionary.bin"), "rb").read()}
+        assert len(_TABLES["size_bits"]) == 25 and len(_TABLES["offsets"]) == 25 and len(_TABLES["words"]) == 122784
+    return _TABLES
+
+
+def dictionary_word(length, idx):
+    t = tables()
+    assert 4 <= length <= 24 and 0 <= idx < (1 << t["size_bits"][length]), (length, idx)
+    at = t["offsets"][length] + idx * length
+    return t["words"][at:at + length]
+
+
+def _uppercase_one(b, i):
+    """appendix B: the "UTF-8 uppercase" of the character at b[i]; -> its length in bytes (a character that sticks out of
+    the word is changed as far as the word reaches)"""
+    c = b[i]
+    if c < 0xC0:
+        if 97 <= c <= 122:
+            b[i] = c ^ 32
+        return 1
+    if c < 0xE0:
+        if i + 1 < len(b):
+            b[i + 1] ^= 32
+        return 2
+    if i + 2 < len(b):
+        b[i + 2] ^= 5
+    return 3
+
+
+def transform_word(word, transform):
+    """appendix B: prefix + elementary transform of the word + suffix.  Types as csrc/brotli_tables_gen.h numbers them:
+    0 identity, 1 .. 9 omit last N, 10 uppercase first, 11 uppercase all, 12 .. 20 omit first N - 11."""
+    prefix, kind, suffix = tables()["transforms"][transform]
+    b = bytearray(word)
+    if 1 <= kind <= 9:
+        b = b[:max(0, len(b) - kind)]
+    elif kind >= 12:
+        b = b[kind - 11:]
+    elif kind == 10:
+        if b:
+            _uppercase_one(b, 0)
+    elif kind == 11:
+        i = 0
+        while i < len(b):
+            i += _uppercase_one(b, i)
+    return bytes(prefix) + bytes(b) + bytes(suffix)
+
+
 # ------------------------------------------------------------------ the compressed metablock
 class Plan:
     """what the caller chooses: block splits per category as [(type, count), ...] covering every symbol of the category
@@ -332,38 +416,131 @@ def greedy_commands(data, min_match=4, max_dist=1 << 16, start=0, history=b""):
     return cmds
 
 
-def emit_compressed(w, commands, plan, is_last, prev=b"", dictionary=b""):
+def emit_compressed(w, commands, plan, is_last, prev=b"", dictionary=b"", wbits=None, log=None, unchecked=False, mlen=None, literals=None, realised=None):
     """commands: [(insert bytes, copy_len, distance)]; distance 0 with copy_len 0 only as the final literals-only command
     (it is written with copy length 2 and an implicit distance that the decoder never executes: the metablock is complete
     after its literals).  `prev` = the stream's output so far (copies may reach into it; its last two bytes are the literal
     context of the first literal).  `dictionary` = a custom (LZ77 prefix) dictionary the stream is decoded with: its bytes lie in front
     of the stream's first output byte for copies alone -- a copy may start in it and run on into the output -- while the first two
-    literals of the stream have context (0, 0) whatever its last bytes are.  Returns the metablock's own output bytes."""
+    literals of the stream have context (0, 0) whatever its last bytes are.  Returns the metablock's own output bytes.
+
+    In place of the distance a command may carry ("word", word_idx, transform), ("ring", k), ("implicit",) or ("raw", distance)
+    (the module's docstring).  `wbits` = the stream's window: with it a distance beyond min(P + len(dictionary), (1 << wbits) - 16)
+    is a word of the static dictionary, whichever way the distance was written, and the ring of the last four distances is kept
+    as section 4 says (code 0, the implicit distance and words do not push).  Without it every distance is a copy, as before.
+    `log`: a list that receives one dict per command -- "coding" (explicit / ring / implicit / tail), "code" (the short code or
+    None), "insert" (the number of literals), "word" (bool), "copy_len", "word_idx", "transform", "total" (bytes the copy part put out), "pos" (stream position of
+    the copy part), "distance", "max_distance".  `unchecked`: the last command may be invalid (a distance below 1, a word with a
+    copy length outside 4 .. 24 or a transform beyond 120): it is written as it stands, its log record says "invalid", and the
+    bytes returned end in front of its copy part -- what a decoder makes of the stream is not the emitter's to say.  `mlen`
+    declares another MLEN than the commands add up to (unchecked streams again).
+
+    For generators that cannot know the stream's state ahead of time: the insert part may be a count, and `literals(p1, p2, k)`
+    then supplies each byte from the two bytes in front of it and the literal's number in the metablock; `what` may be a function of (pos, ring, max_distance) that returns
+    one of the forms above.  `realised` receives the command list with both resolved: emitting it again, under any plan,
+    gives the same output."""
     npf, ndir = plan.npostfix, plan.ndirect
+    max_backward = (1 << wbits) - 16 if wbits else None
+    ring = list(RING_INIT)
     # --- the data and symbol sequences
     out = bytearray()
     lits, cmd_syms, dist_syms = [], [], []
+    has_dist = []  # per command: does a distance symbol follow its literals?
+    inserts = []   # per command: its literals
     pad = 2 - min(2, len(prev))  # (zero bytes that stand for the context in front of the stream's first byte: not output)
     history = bytearray(pad) + bytearray(prev)
     start = len(history)
-    for ins, clen, dist in commands:
-        for b in ins:
-            lits.append((b, history[-1], history[-2]))
-            history.append(b)
+    invalid_at = None
+    for ci, (ins, clen, what) in enumerate(commands):
+        assert invalid_at is None, "an invalid command must be the last one"
+        if isinstance(ins, int):
+            made = bytearray()
+            for _ in range(ins):
+                b = literals(history[-1], history[-2], len(lits))
+                lits.append((b, history[-1], history[-2]))
+                history.append(b); made.append(b)
+            ins = bytes(made)
+        else:
+            for b in ins:
+                lits.append((b, history[-1], history[-2]))
+                history.append(b)
+        inserts.append(ins)
         if clen == 0:
             # (copy length 2 that is never executed: the metablock is complete after the literals, and the decoder looks
             # at neither the distance nor the copy then -- decode.rs:2552-2556)
             ic, iv, ib = _code_of(len(ins), _INS_BASE, _INS_EXTRA)
             cmd_syms.append((command_symbol(ic, 0, ic < 8), iv, ib, 0, 0))
+            has_dist.append(False)
+            if realised is not None:
+                realised.append((ins, 0, 0))
+            if log is not None:
+                log.append({"coding": "tail", "code": None, "insert": len(ins), "word": False, "copy_len": 0, "word_idx": None, "transform": None, "total": 0,
+                            "pos": len(history) - pad, "distance": 0, "max_distance": None})
             continue
+        pos = len(history) - pad
+        max_distance = min(pos + len(dictionary), max_backward) if max_backward is not None else None
+        coding, code = "explicit", None
+        if callable(what):
+            what = what(pos, tuple(ring), max_distance)
+        if realised is not None:
+            realised.append((ins, clen, what))
+        if isinstance(what, tuple):
+            assert max_backward is not None, "words, ring codes and implicit distances need wbits"
+            if what[0] == "word":
+                _, word_idx, transform = what
+                assert 4 <= clen <= 24 and 0 <= word_idx < (1 << tables()["size_bits"][clen]) and 0 <= transform < NUM_TRANSFORMS, what
+                dist = max_distance + 1 + (transform << tables()["size_bits"][clen]) + word_idx
+            elif what[0] == "ring":
+                coding, code = "ring", what[1]
+                assert 0 <= code <= 15
+                if code < 4:
+                    dist = ring[code]
+                else:
+                    dist = ring[(code - 4) // 6] + (1, 2, 3)[((code - 4) % 6) // 2] * (1 if code & 1 else -1)
+            elif what[0] == "implicit":
+                coding, dist = "implicit", ring[0]
+            else:
+                assert what[0] == "raw" and unchecked, what
+                dist = what[1]
+        else:
+            dist = what
         ic, iv, ib = _code_of(len(ins), _INS_BASE, _INS_EXTRA)
         cc, cv, cb = _code_of(clen, _COPY_BASE, _COPY_EXTRA)
-        cmd_syms.append((command_symbol(ic, cc, False), iv, ib, cv, cb))
-        dist_syms.append((distance_symbol(dist, npf, ndir), min(3, cc) if cc <= 2 else 3))
+        cmd_syms.append((command_symbol(ic, cc, coding == "implicit"), iv, ib, cv, cb))
+        has_dist.append(coding != "implicit")
+        if coding == "explicit":
+            dist_syms.append((distance_symbol(dist, npf, ndir), min(3, cc) if cc <= 2 else 3))
+        elif coding == "ring":
+            dist_syms.append(((code, 0, 0), min(3, cc) if cc <= 2 else 3))
+        rec = {"coding": coding, "code": code, "insert": len(ins), "word": False, "copy_len": clen, "word_idx": None, "transform": None, "total": 0, "pos": pos,
+               "distance": dist, "max_distance": max_distance}
+        if log is not None:
+            log.append(rec)
+        if max_distance is not None and (dist > max_distance or dist <= 0):
+            # a word of the static dictionary (decode.rs:2593-2640); it leaves the ring alone
+            rec["word"] = True
+            word_id = dist - max_distance - 1
+            bits = tables()["size_bits"][clen] if 4 <= clen <= 24 else 0
+            word_idx, transform = word_id & ((1 << bits) - 1), word_id >> bits
+            if dist <= 0 or not 4 <= clen <= 24 or transform >= NUM_TRANSFORMS:
+                assert unchecked, (ci, clen, dist, max_distance)
+                rec["invalid"] = True
+                invalid_at = ci
+                continue
+            bytes_ = transform_word(dictionary_word(clen, word_idx), transform)
+            rec["word_idx"], rec["transform"], rec["total"] = word_idx, transform, len(bytes_)
+            history += bytes_
+            continue
+        rec["total"] = clen
+        if not (coding == "implicit" or code == 0):
+            ring = [dist] + ring[:3]
         for _ in range(clen):
             at = len(history) - dist
             history.append(dictionary[at - pad] if dictionary and at < pad else history[-dist])  # (at - pad < 0: counted from the dictionary's end)
-    mlen = len(history) - start
+    if mlen is None:
+        mlen = len(history) - start
+    else:
+        assert unchecked
     # --- block splits
     def expand(blocks, n):
         if not blocks:
@@ -478,7 +655,7 @@ def emit_compressed(w, commands, plan, is_last, prev=b"", dictionary=b""):
             st["next"] = k + 1
         st["left"] -= 1
     li = di = 0
-    for ci, (ins, clen, dist) in enumerate(commands):
+    for ci, ins in enumerate(inserts):
         consume(1)
         sym, iv, ib, cv, cb = cmd_syms[ci]
         cmd_codes[cmd_types[ci]].put(w, sym)
@@ -487,7 +664,7 @@ def emit_compressed(w, commands, plan, is_last, prev=b"", dictionary=b""):
             consume(0)
             lit_codes[lit_tree_of[li]].put(w, b)
             li += 1
-        if clen:
+        if has_dist[ci]:
             consume(2)
             (dsym, dv, dn), _ = dist_syms[di]
             dist_codes[dist_tree_of[di]].put(w, dsym)
