@@ -6,8 +6,8 @@ points, chosen literal context modes (MSB6 included) and context maps, chosen NP
 compressed, stored, metadata and empty metablocks.  It is not a compressor: the caller supplies the commands (or lets
 `greedy_commands` find some) and the plan; the emitter builds the prefix codes from the resulting histograms and
 serialises everything.  Its output is validated against Google's libbrotlidec where that library exists
-(tools/make_emitter_vectors.py, tools/make_word_vectors.py) and pinned by the committed vectors in tests/golden/emitter/
-and tests/golden/emitter_words/.
+(tools/make_emitter_vectors.py, tools/make_word_vectors.py, tools/make_copy_vectors.py) and pinned by the committed vectors in
+tests/golden/emitter/, tests/golden/emitter_words/ and tests/golden/emitter_copies/.
 
     w = BitWriter(); write_stream_header(w, 22)
     emit_compressed(w, commands, plan, is_last=False); emit_stored(w, raw); emit_metadata(w, b"..."); emit_last_empty(w)
@@ -416,7 +416,7 @@ def greedy_commands(data, min_match=4, max_dist=1 << 16, start=0, history=b""):
     return cmds
 
 
-def emit_compressed(w, commands, plan, is_last, prev=b"", dictionary=b"", wbits=None, log=None, unchecked=False, mlen=None, literals=None, realised=None):
+def emit_compressed(w, commands, plan, is_last, prev=b"", dictionary=b"", wbits=None, log=None, unchecked=False, mlen=None, literals=None, realised=None, ring_io=None):
     """commands: [(insert bytes, copy_len, distance)]; distance 0 with copy_len 0 only as the final literals-only command
     (it is written with copy length 2 and an implicit distance that the decoder never executes: the metablock is complete
     after its literals).  `prev` = the stream's output so far (copies may reach into it; its last two bytes are the literal
@@ -438,10 +438,13 @@ def emit_compressed(w, commands, plan, is_last, prev=b"", dictionary=b"", wbits=
     For generators that cannot know the stream's state ahead of time: the insert part may be a count, and `literals(p1, p2, k)`
     then supplies each byte from the two bytes in front of it and the literal's number in the metablock; `what` may be a function of (pos, ring, max_distance) that returns
     one of the forms above.  `realised` receives the command list with both resolved: emitting it again, under any plan,
-    gives the same output."""
+    gives the same output.
+
+    `ring_io`: the ring of the last four distances as a list that is read at the start and written back at the end -- a stream of
+    several metablocks (`prev=`) keeps its ring from one to the next, as a decoder does; without it every metablock starts from RING_INIT."""
     npf, ndir = plan.npostfix, plan.ndirect
     max_backward = (1 << wbits) - 16 if wbits else None
-    ring = list(RING_INIT)
+    ring = list(RING_INIT) if ring_io is None else list(ring_io)
     # --- the data and symbol sequences
     out = bytearray()
     lits, cmd_syms, dist_syms = [], [], []
@@ -534,9 +537,15 @@ def emit_compressed(w, commands, plan, is_last, prev=b"", dictionary=b"", wbits=
         rec["total"] = clen
         if not (coding == "implicit" or code == 0):
             ring = [dist] + ring[:3]
-        for _ in range(clen):
+        left = clen
+        while left and dictionary and len(history) - dist < pad:
+            history.append(dictionary[len(history) - dist - pad]); left -= 1  # (at - pad < 0: counted from the dictionary's end)
+        while left:  # (a self-overlapping copy repeats its first `dist` bytes)
             at = len(history) - dist
-            history.append(dictionary[at - pad] if dictionary and at < pad else history[-dist])  # (at - pad < 0: counted from the dictionary's end)
+            n = min(left, dist)
+            history += history[at:at + n]; left -= n
+    if ring_io is not None:
+        ring_io[:] = ring
     if mlen is None:
         mlen = len(history) - start
     else:
