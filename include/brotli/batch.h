@@ -210,6 +210,20 @@ BROTLI_DEC_API uint32_t BrotliAmdBatchLastPool(BrotliAmdBatch* batch);
  * BROTLI_AMD_GANG / BROTLI_AMD_POOL, -1 where unset. */
 BROTLI_DEC_API uint32_t BrotliAmdDebugPlanGangs(uint32_t n, uint32_t cus, const size_t* in_sizes, int gang_env, int pool_env, uint32_t* grid);
 
+/* Test hooks (no device needed): the launch planner (csrc/brotli_launch_plan.h, which defines the four structs: plain words, for tests) -- the
+ * shape it gives the first launch of n streams of these compressed sizes on the device and with the knobs described, kinds being what the
+ * probe said of every stream or NULL where the device has not been asked (a plan with want_probe set is the probe launch's own); and the
+ * shape of the pass after one of `level` blocks per CU and arena `cur_arena`, for m streams that came back.  Both return 0, or -1 for a NULL
+ * among dev, knobs, in_sizes and the result, n == 0 or a device without compute units. */
+struct BrotliAmdPlanDevice;
+struct BrotliAmdPlanKnobs;
+struct BrotliAmdLaunchPlan;
+struct BrotliAmdLaterPass;
+BROTLI_DEC_API int BrotliAmdDebugPlanLaunch(const struct BrotliAmdPlanDevice* dev, const struct BrotliAmdPlanKnobs* knobs, uint32_t per_cu_cap,
+                                           uint32_t n, const size_t* in_sizes, const uint8_t* kinds, struct BrotliAmdLaunchPlan* plan);
+BROTLI_DEC_API int BrotliAmdDebugPlanLaterPass(const struct BrotliAmdPlanDevice* dev, const struct BrotliAmdPlanKnobs* knobs, uint32_t per_cu_cap,
+                                              uint32_t level, uint32_t cur_arena, uint32_t m, int deferred, struct BrotliAmdLaterPass* pass);
+
 /* Streaming (BrotliDecoderDecompressStream, decode.h): the commands the device has decoded for this stream in all the launches
  * of its calls together.  A call is a launch from the last command boundary reached, so this stays close to the stream's own
  * number of commands however the input is cut up; a test asserts that instead of timing calls. */

@@ -30,7 +30,7 @@ DECODE_H_SYMBOLS = [
 ]
 BATCH_H_SYMBOLS = [
     "BrotliAmdBatchCreate", "BrotliAmdBatchDestroy", "BrotliAmdBatchDecodeDevice", "BrotliAmdBatchRelaunch", "BrotliAmdBatchWait",
-    "BrotliAmdBatchDecodeHost", "BrotliAmdBatchLastKernelMs", "BrotliAmdBatchLastSecondPassCount", "BrotliAmdBatchLastGang", "BrotliAmdBatchLastPool", "BrotliAmdBatchLastProbeMs", "BrotliAmdDebugPlanGangs", "BrotliAmdLastError", "BrotliAmdLastNote", "BrotliAmdDebugBuildTree", "BrotliAmdDecoderDeviceCommands",
+    "BrotliAmdBatchDecodeHost", "BrotliAmdBatchLastKernelMs", "BrotliAmdBatchLastSecondPassCount", "BrotliAmdBatchLastGang", "BrotliAmdBatchLastPool", "BrotliAmdBatchLastProbeMs", "BrotliAmdDebugPlanGangs", "BrotliAmdDebugPlanLaunch", "BrotliAmdDebugPlanLaterPass", "BrotliAmdLastError", "BrotliAmdLastNote", "BrotliAmdDebugBuildTree", "BrotliAmdDecoderDeviceCommands",
     "BrotliAmdBatchDecodeDeviceDict", "BrotliAmdBatchDecodeHostDict", "BrotliAmdDecoderAttachDictionary",
     "BrotliAmdStreamSetCreate", "BrotliAmdStreamSetDestroy", "BrotliAmdStreamSetDecompress", "BrotliAmdStreamSetLastLaunches",
     "BrotliAmdStreamSetLastTransfers", "BrotliAmdDebugRaggedCopy", "BrotliAmdDebugRaggedCopyTile",
