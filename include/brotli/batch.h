@@ -187,6 +187,48 @@ BROTLI_DEC_API int BrotliAmdBatchDecodeHostPacked(BrotliAmdBatch* batch, uint32_
 BROTLI_DEC_API uint32_t BrotliAmdBatchLastPackedLaunches(BrotliAmdBatch* batch);
 BROTLI_DEC_API uint32_t BrotliAmdBatchLastPackedCopies(BrotliAmdBatch* batch);
 
+/* ---- Digests on the device: CRC-32 and CRC-32C of segments of device memory and of a decode call's outputs ----
+ *
+ * Decoded bytes stay in device memory, and so may compressed payloads; a caller who has to know that they are the right bytes -- a store's
+ * recorded checksum, a framing format's CRC over a payload -- asks for their digests instead of copying them to the host.  Both kinds are
+ * the reflected 32-bit CRCs with init and final XOR 0xFFFFFFFF: CRC32 is 0xEDB88320 (zlib, gzip, PNG, the `crc` of a Parquet page), CRC32C
+ * is 0x82F63B78 (Castagnoli).  "123456789" gives 0xCBF43926 and 0xE3069283; a segment of no bytes gives 0.  A CRC is linear, so one long
+ * segment is spread over the whole device like a thousand short ones (csrc/brotli_crc.h, csrc/brotli_crc_kernels.hip), and a digest does not
+ * depend on how the work was shared out. */
+#define BROTLI_AMD_DIGEST_CRC32 1u
+#define BROTLI_AMD_DIGEST_CRC32C 2u
+
+/* The digests of n segments in DEVICE memory -- lens[i] bytes at d_ptrs[i], any alignment, any length, 0 included; n is not bound by the batch
+ * object's max_streams; segments may overlap or repeat --: one launch on hip_stream, the call waits on that stream and copies the n digests to
+ * `digests` (host).  Nothing outside the 16-byte-aligned span around [d_ptrs[i], d_ptrs[i] + lens[i]) is read.  n == 0 returns 0.  A negative
+ * value, and a BrotliAmdLastError text, for a NULL batch, a NULL array with n != 0, and a kind that is neither of the two. */
+BROTLI_DEC_API int BrotliAmdBatchDigestSegments(BrotliAmdBatch* batch, uint32_t kind, uint32_t n, const void* const* d_ptrs, const size_t* lens,
+                                               uint32_t* digests, void* hip_stream);
+
+/* The digests of the DELIVERED bytes -- [out, out + decoded_size) -- of every stream of the last decode call on the object, into digests[0..n) of
+ * that call's n:
+ *   - after BrotliAmdBatchDecodeDevice(Dict) or BrotliAmdBatchRelaunch, once BrotliAmdBatchWait has returned: the caller's d_out[i];
+ *   - after BrotliAmdBatchDecodeHost(Dict): the streams' slots in the object's device staging, which it keeps -- the bytes the call copied out;
+ *   - after BrotliAmdBatchDecodeDevicePacked / HostPacked: [offsets[i], offsets[i + 1]) of the packed output.
+ * A stream that ended in an error or NEEDS_MORE_OUTPUT is digested over its decoded_size bytes too (not over `produced`).  The launch runs on
+ * the stream of that decode call and the call waits for it.  It is not a decode call itself: BrotliAmdBatchPackedOutput stays valid, and
+ * BrotliAmdBatchRelaunch and the Last* accessors say what they said before.  A negative value, and a BrotliAmdLastError text, for a NULL batch or
+ * NULL digests, a kind that is neither of the two, an object without a decode call, a last decode call that failed behind its argument checks (it has no
+ * outputs; one of no streams returns 0), and a launch that BrotliAmdBatchWait has not been called for. */
+BROTLI_DEC_API int BrotliAmdBatchDigestOutputs(BrotliAmdBatch* batch, uint32_t kind, uint32_t* digests);
+
+/* Milliseconds the digest kernel took in the last of the two calls above (HIP events around its launch). */
+BROTLI_DEC_API float BrotliAmdBatchLastDigestMs(BrotliAmdBatch* batch);
+
+/* Test hooks (no device needed).  The bytes of source memory in one tile of a digest launch (the unit in which its blocks share the work); */
+BROTLI_DEC_API uint32_t BrotliAmdDebugDigestTile(void);
+/* the digest of data[0, n) by the device's functions on the host, cut the way the kernel cuts: the bytes placed at `skew` (0..15) past a
+ * 16-byte boundary among bytes that are not theirs, 16-byte units, a piece for every run of run_units units (0: the kernel's own number), the
+ * pieces combined by a multiplication each and XOR; 0, and a BrotliAmdLastError text, for an unknown kind or skew > 15; */
+BROTLI_DEC_API uint32_t BrotliAmdDebugDigestHost(uint32_t kind, const uint8_t* data, size_t n, uint32_t skew, uint32_t run_units);
+/* crc x^(8 nbytes) mod the kind's polynomial, for any 64-bit nbytes: crc(A B) == BrotliAmdDebugDigestShift(kind, crc(A), |B|) ^ crc(B). */
+BROTLI_DEC_API uint32_t BrotliAmdDebugDigestShift(uint32_t kind, uint32_t crc, uint64_t nbytes);
+
 /* Milliseconds the last launch spent in the decode kernel (HIP events on the launch stream). */
 BROTLI_DEC_API float BrotliAmdBatchLastKernelMs(BrotliAmdBatch* batch);
 

@@ -36,6 +36,8 @@ BATCH_H_SYMBOLS = [
     "BrotliAmdStreamSetLastTransfers", "BrotliAmdDebugRaggedCopy", "BrotliAmdDebugRaggedCopyTile",
     "BrotliAmdBatchSizeHints", "BrotliAmdDebugSizeWalk", "BrotliAmdBatchDecodeDevicePacked", "BrotliAmdBatchPackedOutput",
     "BrotliAmdBatchPackedFetch", "BrotliAmdBatchDecodeHostPacked", "BrotliAmdBatchLastPackedLaunches", "BrotliAmdBatchLastPackedCopies",
+    "BrotliAmdBatchDigestSegments", "BrotliAmdBatchDigestOutputs", "BrotliAmdBatchLastDigestMs", "BrotliAmdDebugDigestTile",
+    "BrotliAmdDebugDigestHost", "BrotliAmdDebugDigestShift",
 ]
 
 
@@ -58,6 +60,7 @@ class SizeHint(ctypes.Structure):  # BrotliAmdSizeHint: what a stream's headers 
 
 
 SIZE_OK, SIZE_TRUNCATED, SIZE_REJECTED = 0, 1, 2  # SizeHint.status
+DIGEST_CRC32, DIGEST_CRC32C = 1, 2  # BROTLI_AMD_DIGEST_*: zlib's polynomial, Castagnoli's
 
 
 def build(force=False):
@@ -140,6 +143,16 @@ def load_library():
         for name in ("BrotliAmdBatchLastPackedLaunches", "BrotliAmdBatchLastPackedCopies"):
             getattr(L, name).restype = u32
             getattr(L, name).argtypes = [vp]
+    if hasattr(L, "BrotliAmdBatchDigestSegments"):   # (digests: an older build of the library, loaded for an A/B, has none)
+        L.BrotliAmdBatchDigestSegments.argtypes = [vp, u32, u32, vp, vp, vp, vp]
+        L.BrotliAmdBatchDigestOutputs.argtypes = [vp, u32, vp]
+        L.BrotliAmdBatchLastDigestMs.restype = ctypes.c_float
+        L.BrotliAmdBatchLastDigestMs.argtypes = [vp]
+        L.BrotliAmdDebugDigestTile.restype = u32
+        L.BrotliAmdDebugDigestHost.restype = u32
+        L.BrotliAmdDebugDigestHost.argtypes = [u32, vp, sz, u32, u32]
+        L.BrotliAmdDebugDigestShift.restype = u32
+        L.BrotliAmdDebugDigestShift.argtypes = [u32, u32, ctypes.c_uint64]
     L.BrotliAmdBatchLastKernelMs.restype = ctypes.c_float
     L.BrotliAmdBatchLastKernelMs.argtypes = [vp]
     L.BrotliAmdBatchLastSecondPassCount.restype = ctypes.c_uint32
@@ -185,6 +198,20 @@ def size_walk(data: bytes, flags=FLAG_LARGE_WINDOW):
     return hint
 
 
+def digest_host(data: bytes, kind=DIGEST_CRC32, skew=0, run_units=0):
+    """BrotliAmdDebugDigestHost: the digest of `data` by the device's functions on the host (no device needed), the bytes placed `skew` past a
+    16-byte boundary and cut into pieces of run_units 16-byte units (0: the kernel's own number)"""
+    L = load_library()
+    data = bytes(data)
+    buf = ctypes.create_string_buffer(data, max(1, len(data)))
+    return int(L.BrotliAmdDebugDigestHost(kind, ctypes.addressof(buf), len(data), skew, run_units))
+
+
+def digest_shift(crc, nbytes, kind=DIGEST_CRC32):
+    """BrotliAmdDebugDigestShift: crc x^(8 nbytes) mod the kind's polynomial -- crc(A + B) == digest_shift(crc(A), len(B)) ^ crc(B)"""
+    return int(load_library().BrotliAmdDebugDigestShift(kind, crc, nbytes))
+
+
 # ------------------------------------------------------------------ batch (include/brotli/batch.h)
 class Batch:
     """Owns one BrotliAmdBatch on the current HIP device."""
@@ -196,6 +223,7 @@ class Batch:
             raise RuntimeError("BrotliAmdBatchCreate failed: " + last_error())
         self.max_streams = max_streams
         self.n = 0
+        self.out_n = 0   # streams of the last decode call, a packed one included (digest_outputs)
 
     def close(self):
         if self._h:
@@ -226,7 +254,7 @@ class Batch:
                 raise RuntimeError("BrotliAmdBatchDecodeDeviceDict failed: " + last_error())
         elif self._L.BrotliAmdBatchDecodeDevice(self._h, n, a_in, a_is, a_out, a_oc, flags, stream) != 0:
             raise RuntimeError("BrotliAmdBatchDecodeDevice failed: " + last_error())
-        self.n = n
+        self.n = self.out_n = n
 
     def relaunch(self, stream=None):
         if self._L.BrotliAmdBatchRelaunch(self._h, stream) != 0:
@@ -281,7 +309,7 @@ class Batch:
                 raise RuntimeError("BrotliAmdBatchDecodeHostDict failed: " + last_error())
         elif self._L.BrotliAmdBatchDecodeHost(self._h, n, a_in, a_is, a_out, a_oc, flags, res) != 0:
             raise RuntimeError("BrotliAmdBatchDecodeHost failed: " + last_error())
-        self.n = n
+        self.n = self.out_n = n
         results = list(res)[:n]
         return results, [outs[i].raw[:min(results[i].decoded_size, out_caps[i])] for i in range(n)]
 
@@ -318,7 +346,7 @@ class Batch:
         res = (BatchResult * max(1, n))()
         if self._L.BrotliAmdBatchDecodeDevicePacked(self._h, n, a_in, a_is, a_dp, a_ds, max_out, flags, stream, res) != 0:
             raise RuntimeError("BrotliAmdBatchDecodeDevicePacked failed: " + last_error())
-        self.n = 0
+        self.n, self.out_n = 0, n
         ptr, offsets = self._packed_view(n)
         return list(res)[:n], ptr, offsets
 
@@ -349,7 +377,7 @@ class Batch:
         res = (BatchResult * max(1, n))()
         if self._L.BrotliAmdBatchDecodeHostPacked(self._h, n, a_in, a_is, a_dp, a_ds, max_out, flags, res) != 0:
             raise RuntimeError("BrotliAmdBatchDecodeHostPacked failed: " + last_error())
-        self.n = 0
+        self.n, self.out_n = 0, n
         _, offsets = self._packed_view(n)
         blob = self.packed_fetch(offsets[n])
         return list(res)[:n], [blob[offsets[i]:offsets[i + 1]] for i in range(n)]
@@ -362,6 +390,32 @@ class Batch:
         """ragged-copy launches of the last packed call: 0 where its first allocation was the packed output"""
         return int(self._L.BrotliAmdBatchLastPackedCopies(self._h))
 
+    def digest_segments(self, ptrs, lens, kind=DIGEST_CRC32, stream=None):
+        """BrotliAmdBatchDigestSegments: the CRC-32 / CRC-32C of lens[i] bytes at the device address ptrs[i] (any alignment, any length) ->
+        [int], one launch and a wait on `stream`"""
+        n = len(ptrs)
+        if len(lens) != n:
+            raise ValueError("ptrs and lens: one entry per segment each")
+        a_p = (ctypes.c_void_p * max(1, n))(*ptrs)
+        a_l = (ctypes.c_size_t * max(1, n))(*lens)
+        out = (ctypes.c_uint32 * max(1, n))()
+        if self._L.BrotliAmdBatchDigestSegments(self._h, kind, n, a_p, a_l, out, stream) != 0:
+            raise RuntimeError("BrotliAmdBatchDigestSegments failed: " + last_error())
+        return list(out)[:n]
+
+    def digest_outputs(self, kind=DIGEST_CRC32):
+        """BrotliAmdBatchDigestOutputs: the digests of the delivered bytes of every stream of the last decode call on this object (after
+        decode_device: once wait() has returned) -> [int]"""
+        n = self.out_n
+        out = (ctypes.c_uint32 * max(1, n))()
+        if self._L.BrotliAmdBatchDigestOutputs(self._h, kind, out) != 0:
+            raise RuntimeError("BrotliAmdBatchDigestOutputs failed: " + last_error())
+        return list(out)[:n]
+
+    def last_digest_ms(self):
+        """milliseconds the digest kernel took in the last digest_segments / digest_outputs"""
+        return float(self._L.BrotliAmdBatchLastDigestMs(self._h))
+
     def decode_host_raw(self, in_ptrs, in_sizes, out_ptrs, out_caps, flags=FLAG_LARGE_WINDOW):
         """BrotliAmdBatchDecodeHost on buffers the caller owns (host addresses as integers): nothing is copied on the Python side"""
         n = len(in_ptrs)
@@ -372,7 +426,7 @@ class Batch:
         res = (BatchResult * max(1, n))()
         if self._L.BrotliAmdBatchDecodeHost(self._h, n, a_in, a_is, a_out, a_oc, flags, res) != 0:
             raise RuntimeError("BrotliAmdBatchDecodeHost failed: " + last_error())
-        self.n = n
+        self.n = self.out_n = n
         return list(res)[:n]
 
 

@@ -134,6 +134,7 @@ int launch(BrotliAmdBatch* b, hipStream_t stream) {
   if (!hip_ok(hipEventRecord(b->ev1, stream), "hipEventRecord")) return -1;
   b->last_stream = stream;
   b->launched = true;
+  b->outputs = BrotliAmdBatch::Outputs::InFlight;
   return 0;
 }
 
@@ -187,7 +188,7 @@ void apply_shape(BrotliAmdBatch* b, const BrotliAmdLaunchPlan& plan) {
 // the same descriptors have not been asked about before, the device is asked in a launch of the shape the planner gave (probe_streams), and the
 // planner is asked again with the answer.  Then the plan is applied: flags, order, scratch, upload, launch.
 int brotli_amd_host::submit(BrotliAmdBatch* b, uint32_t n, hipStream_t stream) {  // h_descs[0..n) filled
-  if (n == 0) { b->n = 0; b->launched = false; return 0; }
+  if (n == 0) { b->n = 0; b->launched = false; b->outputs = BrotliAmdBatch::Outputs::None; return 0; }
   if (!hip_ok(hipSetDevice(b->device), "hipSetDevice")) return -1;
   const BrotliAmdPlanKnobs knobs = launch_knobs();
   const auto size_at = [b](uint32_t i) { return (uint64_t)b->h_descs[i].in_size; };
@@ -238,6 +239,7 @@ bool brotli_amd_host::decode_descs(BrotliAmdBatch* b, uint32_t n, hipStream_t st
 void brotli_amd_host::drop_packed(BrotliAmdBatch* b) {
   b->packed_out = nullptr; b->packed_valid = false; b->packed_offsets.clear();
   b->last_packed_launches = b->last_packed_copies = 0; b->packed_ms = 0.0f;
+  b->outputs = BrotliAmdBatch::Outputs::Failed;   // (until the call gets as far as a launch, or turns out to have no streams)
 }
 
 namespace {
@@ -422,7 +424,7 @@ extern "C" void BrotliAmdBatchDestroy(BrotliAmdBatch* b) {
   if (b->launched && b->last_stream != nullptr) (void)hipStreamSynchronize(b->last_stream);
   else (void)hipDeviceSynchronize();
   if (b->copy_stream) (void)hipStreamDestroy(b->copy_stream);
-  for (hipEvent_t ev : {b->ev0, b->ev1, b->ev2, b->ev3}) if (ev) (void)hipEventDestroy(ev);
+  for (hipEvent_t ev : {b->ev0, b->ev1, b->ev2, b->ev3, b->ev_digest0, b->ev_digest1}) if (ev) (void)hipEventDestroy(ev);
   delete b;
 }
 
@@ -459,6 +461,7 @@ extern "C" int BrotliAmdBatchWait(BrotliAmdBatch* b, BrotliAmdResult* results) {
   if (!hip_ok(hipStreamSynchronize(b->last_stream), "hipStreamSynchronize")) return -1;
   if (retry_with_larger_arenas(b) != 0) return -1;
   if (b->exact_limit && settle_output_limits(b) != 0) return -1;
+  b->outputs = BrotliAmdBatch::Outputs::Waited;
   if (results) for (uint32_t i = 0; i < b->n; i++) results[i] = to_result(b->h_status[i]);
   return 0;
 }

@@ -3,6 +3,7 @@
 //   brotli_staging.cpp  host buffers through staging arenas, size hints, the packed decode
 //   brotli_capi.cpp     the reference's C ABI (include/brotli/decode.h): error strings, one-shot, Prealloc, the streaming state
 //   brotli_stream_set.cpp  many streaming states in one launch, the ragged copy's debug hook
+//   brotli_digest.cpp   CRC-32 / CRC-32C of segments of device memory and of the last decode call's outputs
 #ifndef BROTLI_AMD_HOST_H_
 #define BROTLI_AMD_HOST_H_
 #include <hip/hip_runtime.h>
@@ -156,6 +157,13 @@ struct BrotliAmdBatch {
   std::vector<uint64_t> packed_offsets;
   uint32_t last_packed_launches = 0, last_packed_copies = 0;
   float packed_ms = 0.0f;   // decode kernel time of all its launches together
+  // digests (brotli_digest.cpp).  What BrotliAmdBatchDigestOutputs finds where the last decode call was not a packed one: no decode call yet; a call
+  // that has begun and launched nothing -- where it stays so, it failed --; a call of no streams; a launch nobody has waited for; h_descs and
+  // h_status of the launch waited for
+  enum class Outputs : uint8_t { NoCall, Failed, None, InFlight, Waited } outputs = Outputs::NoCall;
+  brotli_amd_host::DevBuf<> d_digest;   // the segment table and the digests of one launch
+  hipEvent_t ev_digest0 = nullptr, ev_digest1 = nullptr;   // around the digest launch (made at the first)
+  float digest_ms = 0.0f;
 };
 
 namespace brotli_amd_host {

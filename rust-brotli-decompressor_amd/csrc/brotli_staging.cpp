@@ -101,7 +101,7 @@ extern "C" int BrotliAmdBatchDecodeHostDict(BrotliAmdBatch* b, uint32_t n, const
                                             BrotliAmdResult* results) {
   if (!b || n > b->max_streams || (n && (!in || !in_sizes || !out || !out_caps))) { g_last_error = "invalid batch arguments"; return -1; }
   drop_packed(b);
-  if (n == 0) return 0;
+  if (n == 0) { b->outputs = BrotliAmdBatch::Outputs::None; return 0; }
   DeviceGuard guard;
   if (!hip_ok(hipSetDevice(b->device), "hipSetDevice")) return -1;
   StagedInputs staged;

@@ -145,6 +145,9 @@ pub const BROTLI_AMD_BATCH_LARGE_WINDOW: u32 = 1;
 pub const BROTLI_AMD_BATCH_NO_CANNY: u32 = 2;
 pub const BROTLI_AMD_BATCH_SPILL_IN_PLACE: u32 = 16;
 pub const BROTLI_AMD_BATCH_EAGER_OUTPUT_LIMIT: u32 = 64;
+/// batch.h: the digest kinds -- CRC-32 (0xEDB88320: zlib, gzip, PNG, Parquet pages) and CRC-32C (0x82F63B78, Castagnoli)
+pub const BROTLI_AMD_DIGEST_CRC32: u32 = 1;
+pub const BROTLI_AMD_DIGEST_CRC32C: u32 = 2;
 
 extern "C" {
     pub fn BrotliAmdBatchCreate(max_streams: u32, lds_arena_bytes: u32, grid_blocks: u32) -> *mut BrotliAmdBatch;
@@ -178,6 +181,17 @@ extern "C" {
     pub fn BrotliAmdBatchLastGang(batch: *mut BrotliAmdBatch) -> u32;
     pub fn BrotliAmdBatchLastPool(batch: *mut BrotliAmdBatch) -> u32;
     pub fn BrotliAmdBatchLastProbeMs(batch: *mut BrotliAmdBatch) -> f32;
+    /// the digests of `n` segments of DEVICE memory (any alignment, any length) in one launch on `hip_stream`; waits, `digests` is host memory
+    pub fn BrotliAmdBatchDigestSegments(
+        batch: *mut BrotliAmdBatch, kind: u32, n: u32, d_ptrs: *const *const c_void, lens: *const size_t, digests: *mut u32, hip_stream: *mut c_void,
+    ) -> c_int;
+    /// the digests of the delivered bytes of every stream of the last decode call on the object (after `BrotliAmdBatchWait` for a device call)
+    pub fn BrotliAmdBatchDigestOutputs(batch: *mut BrotliAmdBatch, kind: u32, digests: *mut u32) -> c_int;
+    pub fn BrotliAmdBatchLastDigestMs(batch: *mut BrotliAmdBatch) -> f32;
+    /// test hooks, no device needed
+    pub fn BrotliAmdDebugDigestTile() -> u32;
+    pub fn BrotliAmdDebugDigestHost(kind: u32, data: *const u8, n: size_t, skew: u32, run_units: u32) -> u32;
+    pub fn BrotliAmdDebugDigestShift(kind: u32, crc: u32, nbytes: u64) -> u32;
     pub fn BrotliAmdLastError() -> *const c_char;
     pub fn BrotliAmdLastNote() -> *const c_char;
 }
