@@ -23,6 +23,14 @@ Words need `wbits` (the maximum distance is min(P + len(dictionary), (1 << wbits
 transforms are restated here in plain Python from RFC 7932 Appendix A / B (`dictionary_word`, `transform_word`), over
 the tables of csrc/brotli_tables_gen.h and data/dictionary.bin; no decoder is called, so that the bytes the emitter
 expects are an opinion of their own beside the oracle's and libbrotlidec's.  `log=[]` receives one record per command.
+
+The header can be chosen as well (tools/make_header_vectors.py, tests/golden/emitter_headers/): `Plan(codes=...)` puts a WireCode
+-- a prefix code from explicit lengths or words, with its HSKIP, its code-length code, its sixteens and seventeens, its
+trailing zeros, or the simple form in any order -- in the place of any code of the metablock; `Plan(map_forms=...)` gives a
+context map its RLEMAX, its split into zero runs and its IMTF (the forward move-to-front is done here); write_mlen,
+emit_metadata and emit_stored take MNIBBLES, MSKIPBYTES, the reserved bit and padding as given.  `unchecked` writes what no
+decoder accepts.  `hlog=[]` receives one record per such code, per context map and per category's block switches, with the
+bit positions of every word, the runs the repeat words resolved to and the 64-bit steps a wide reader takes over them.
 """
 import heapq
 
@@ -39,6 +47,10 @@ class BitWriter:
             self.out.append(self.acc & 0xFF)
             self.acc >>= 8
             self.n -= 8
+
+    def bits(self):
+        """the number of bits written so far"""
+        return 8 * len(self.out) + self.n
 
     def align(self):
         if self.n:
@@ -188,10 +200,228 @@ class PrefixCode:
         w.put(c, n)
 
 
+class Resolved:
+    """what resolve_words found: `lengths`; per word read `runs` (None, or the number of symbols its repeat added), `depth` (its place in
+    its chain of repeat words, 1 = the first) and `values` (the length it gave its symbols); `used` = the number of words read
+    before the code was complete or the alphabet full; `symbol` = the symbols passed; `space` = the code space left (None: a
+    repeat passed the alphabet's end, which ends the reading with the decoders' verdict)"""
+
+
+def resolve_words(words, max_symbol):
+    """the code-length words of section 3.5 as a decoder reads them: a word is a length 0 .. 15, (16, extra 0 .. 3) or
+    (17, extra 0 .. 7) -> Resolved"""
+    symbol, space, prev, repeat, repeat_len = 0, 32768, 8, 0, 0
+    r = Resolved()
+    r.lengths, r.runs, r.depth, r.values, r.used, d = [0] * max_symbol, [], [], [], 0, 0
+    for word in words:
+        if symbol >= max_symbol or space == 0:   # (an over-used space is not zero: the decoders read on to the alphabet's end)
+            break
+        r.used += 1
+        if isinstance(word, int):
+            assert 0 <= word <= 15
+            repeat, d = 0, 0
+            if word:
+                r.lengths[symbol] = word; prev = word; space -= 32768 >> word
+            symbol += 1
+            r.runs.append(None); r.depth.append(0); r.values.append(word)
+            continue
+        code, extra = word
+        nbits = code - 14
+        assert code in (16, 17) and 0 <= extra < (1 << nbits), word
+        new_len = prev if code == 16 else 0
+        if repeat_len != new_len:
+            repeat, repeat_len, d = 0, new_len, 0
+        old = repeat
+        if repeat > 0:
+            repeat = (repeat - 2) << nbits
+        repeat += extra + 3
+        d = d + 1 if old else 1
+        delta = repeat - old
+        r.runs.append(delta); r.depth.append(d); r.values.append(repeat_len)
+        if symbol + delta > max_symbol:
+            symbol, space = max_symbol, None
+            break
+        if repeat_len:
+            for _ in range(delta):
+                r.lengths[symbol] = repeat_len; symbol += 1
+            space -= delta << (15 - repeat_len)
+        else:
+            symbol += delta
+    r.symbol, r.space = symbol, space
+    return r
+
+
+def words_of(lengths, repeats=False, trailing_zeros=False):
+    """plain words for `lengths` (up to the last non-zero one, or all of them); with `repeats` every run that a chain of
+    sixteens or seventeens can express exactly is written as one (greedily, the decoder's arithmetic run backwards)"""
+    last = max((i for i, l in enumerate(lengths) if l), default=-1)
+    lens = list(lengths) if trailing_zeros else list(lengths[:last + 1])
+    if not repeats:
+        return lens
+    out, i, prev = [], 0, 8
+    while i < len(lens):
+        l = lens[i]
+        j = i
+        while j < len(lens) and lens[j] == l:
+            j += 1
+        n = j - i
+        if l and l != prev:
+            out.append(l); prev = l; i += 1
+            continue
+        code, nbits = (16, 2) if l else (17, 3)
+        chain = _chain_for(n, nbits)
+        if chain is None:
+            out.append(l); i += 1   # (a literal word: it also ends any chain in front of it)
+            continue
+        # a chain continues a repeat word of the same kind directly in front of it: break it with nothing, the total is what counts
+        if out and not isinstance(out[-1], int) and out[-1][0] == code:
+            out.append(l); i += 1
+            continue
+        out += [(code, e) for e in chain]; i += n
+    return out
+
+
+def _chain_for(n, nbits):
+    """extra values of a chain of repeat words whose total is exactly n, or None (n < 3)"""
+    if n < 3:
+        return None
+    chain = []
+    while True:
+        if n - 3 < (1 << nbits):
+            chain.append(n - 3)
+            return chain[::-1]
+        e = (n - 3) & ((1 << nbits) - 1)
+        chain.append(e)
+        n = ((n - 3 - e) >> nbits) + 2
+        if n < 3:
+            return None
+
+
+class WireCode:
+    """a prefix code with its wire form chosen by the caller (PrefixCode chooses its own): write_code / put / codes as there.
+
+    complex form: `words` (see resolve_words) or `lengths` (then one word per length up to the last non-zero one, `trailing_zeros`
+    for all of them; `repeats` for words_of's repeat words); `cl_lengths` = the code-length code's own 18 lengths (default: from the words'
+    histogram; one non-zero entry = the one-symbol code whose words take no bits); `hskip` 0, 2 or 3 (default: the largest the
+    zeros allow).  simple form: `simple` = the symbols in wire order, `tree_select` for four of them.
+    `max_symbol` below the alphabet for the large-window distance codes.  `unchecked`: written as given even where no decoder
+    accepts it; symbols of an incomplete code are then written as nothing."""
+
+    def __init__(self, alphabet, lengths=None, words=None, cl_lengths=None, hskip=None, trailing_zeros=False, repeats=False, simple=None, tree_select=None,
+                 max_symbol=None, unchecked=False):
+        self.alphabet, self.unchecked = alphabet, unchecked
+        self.max_symbol = alphabet if max_symbol is None else max_symbol
+        self.simple = simple is not None
+        self.codes = {}
+        if self.simple:
+            self.syms, self.tree_select = list(simple), tree_select
+            n = len(self.syms)
+            assert 1 <= n <= 4 and (n == 4) == (tree_select is not None)
+            ok = len(set(self.syms)) == n and all(s < self.max_symbol for s in self.syms)
+            assert ok or unchecked
+            shape = {1: [0], 2: [1, 1], 3: [1, 2, 2], 4: [1, 2, 3, 3] if tree_select else [2, 2, 2, 2]}[n]
+            self.full = [0] * alphabet
+            if ok:
+                for s, l in zip(self.syms, shape):
+                    self.full[s] = l
+                self.codes = canonical_codes(self.full) if n > 1 else {self.syms[0]: (0, 0)}
+            return
+        if words is None:
+            words = words_of(lengths, repeats, trailing_zeros)
+        self.words = list(words)
+        r = self.resolved = resolve_words(self.words, self.max_symbol)
+        self.full, self.runs, self.depth, self.consumed, self.space = r.lengths, r.runs, r.depth, r.used, r.space
+        assert lengths is None or list(lengths[:self.max_symbol]) + [0] * (self.max_symbol - len(lengths)) == self.full or unchecked, "the words do not give the lengths"
+        if cl_lengths is None:
+            h = [0] * 18
+            for wd in self.words:
+                h[wd if isinstance(wd, int) else wd[0]] += 1
+            if sum(1 for c in h if c) == 1:
+                h[0 if h[0] == 0 else 1] += 1
+            cl_lengths = limited_lengths(h, 5)
+        self.cl_lengths = list(cl_lengths)
+        assert len(self.cl_lengths) == 18 and all(0 <= v <= 5 for v in self.cl_lengths)
+        seq = [self.cl_lengths[s] for s in _CL_ORDER]
+        most = 3 if seq[0] == seq[1] == seq[2] == 0 else 2 if seq[0] == seq[1] == 0 else 0
+        self.hskip = most if hskip is None else hskip
+        assert self.hskip in (0, 2, 3) and (self.hskip <= most or unchecked)
+        nz = [v for v in self.cl_lengths if v]
+        self.cl_single = len(nz) == 1
+        self.cl_space = 32 - sum(32 >> v for v in nz)
+        if self.cl_single:
+            self.cl_codes = {s: (0, 0) for s, v in enumerate(self.cl_lengths) if v}
+        elif self.cl_space == 0:
+            self.cl_codes = canonical_codes(self.cl_lengths)
+        else:
+            assert unchecked, "the code-length code is not complete"
+            self.cl_codes = None
+        if self.space == 0 and self.cl_codes is not None:
+            self.codes = canonical_codes(self.full)
+        else:
+            assert unchecked, ("the code is not complete", self.space)
+
+    def write_code(self, w, log=None, kind=None):
+        rec = {"kind": kind, "form": "simple" if self.simple else "complex", "alphabet": self.alphabet, "max_symbol": self.max_symbol, "start": w.bits(),
+               "unchecked": self.unchecked}
+        if log is not None:
+            log.append(rec)
+        if self.simple:
+            abits = max(1, (self.alphabet - 1).bit_length())
+            w.put(1, 2); w.put(len(self.syms) - 1, 2)
+            for s in self.syms:
+                w.put(s, abits)
+            if len(self.syms) == 4:
+                w.put(self.tree_select, 1)
+            rec.update(nsym=len(self.syms), symbols=list(self.syms), tree_select=self.tree_select, end=w.bits())
+            return
+        w.put(self.hskip, 2)
+        seq = [self.cl_lengths[s] for s in _CL_ORDER]
+        space = 32
+        for i in range(self.hskip, 18):  # (a decoder reads until the space is used up, or over-used)
+            bits, n = _CL_VLC[seq[i]]
+            w.put(bits, n)
+            if seq[i]:
+                space -= 32 >> seq[i]
+                if space <= 0:
+                    break
+        rec.update(hskip=self.hskip, cl_lengths=list(self.cl_lengths), cl_symbols=sum(1 for v in self.cl_lengths if v), cl_space=self.cl_space,
+                   words_start=w.bits(), words=[], consumed=self.consumed, space=self.space, symbols=sum(1 for l in self.full if l), reached=self.resolved.symbol,
+                   depth=max(self.full) if any(self.full) else 0)
+        if self.cl_codes is None:
+            rec["end"] = w.bits()
+            return
+        for k, wd in enumerate(self.words):
+            code, extra = (wd, None) if isinstance(wd, int) else wd
+            at = w.bits()
+            c, n = self.cl_codes[code]
+            w.put(c, n)
+            if extra is not None:
+                w.put(extra, code - 14)
+            read = k < self.consumed
+            rec["words"].append({"word": code, "extra": extra, "start": at, "mid": at + n, "end": w.bits(), "read": read,
+                                 "run": self.runs[k] if read else None, "chain": self.depth[k] if read else None, "value": self.resolved.values[k] if read else None})
+        # a reader that takes 64 stream bits a step takes every word that starts inside them: the next step starts where the last of them ends
+        base, step = rec["words_start"], 0
+        for wd in rec["words"]:
+            if wd["start"] - base >= 64:
+                base, step = wd["start"], step + 1
+            wd["step"], wd["at"] = step, wd["start"] - base
+        rec["end"] = w.bits()
+
+    def put(self, w, sym):
+        if sym not in self.codes:
+            assert self.unchecked, sym
+            return
+        c, n = self.codes[sym]
+        w.put(c, n)
+
+
 # ------------------------------------------------------------------ small encodings
-def write_stream_header(w, wbits):
-    """section 9.1, standard windows (10 .. 24)"""
-    if wbits == 16:
+def write_stream_header(w, wbits, large=False):
+    """section 9.1, standard windows (10 .. 24); `large`: the large-window form (any six-bit value, as given)"""
+    if large:
+        w.put(1, 1); w.put(0, 3); w.put(1, 3); w.put(0, 1); w.put(wbits, 6)
+    elif wbits == 16:
         w.put(0, 1)
     elif wbits == 17:
         w.put(1, 1); w.put(0, 3); w.put(0, 3)
@@ -210,35 +440,48 @@ def write_varlen8(w, v):  # 0..255 in 1 + 3 + n bits (section 9.2: NBLTYPES - 1,
     w.put(1, 1); w.put(n, 3); w.put(v - (1 << n), n)
 
 
-def write_mlen(w, is_last, mlen, is_uncompressed=False):
+def write_mlen(w, is_last, mlen, is_uncompressed=False, nibbles=None):
+    """`nibbles`: MNIBBLES as given (4, 5 or 6), more than MLEN - 1 needs included -- which no decoder accepts"""
     w.put(1 if is_last else 0, 1)
     if is_last:
         w.put(0, 1)  # ISLASTEMPTY = 0
     nib = max(4, ((mlen - 1).bit_length() + 3) // 4)
     assert nib <= 6
+    if nibbles is not None:
+        assert nib <= nibbles <= 6
+        nib = nibbles
     w.put(nib - 4, 2)
     w.put(mlen - 1, nib * 4)
     if not is_last:
         w.put(1 if is_uncompressed else 0, 1)
 
 
-def emit_stored(w, raw):
+def pad_to_byte(w, pad=0):
+    """the bits up to the next byte boundary: zeros, or the low bits of `pad` (no decoder accepts others than zeros)"""
+    if w.n:
+        k = 8 - w.n
+        w.put(pad & ((1 << k) - 1), k)
+
+
+def emit_stored(w, raw, pad=0):
     assert 0 < len(raw) <= 1 << 24
     write_mlen(w, False, len(raw), True)
-    w.align()
+    pad_to_byte(w, pad)
     w.out += raw
 
 
-def emit_metadata(w, payload):
-    w.put(0, 1); w.put(3, 2); w.put(0, 1)  # ISLAST = 0, MNIBBLES = 0 (code 3), reserved
+def emit_metadata(w, payload, nbytes=None, reserved=0, pad=0):
+    """`nbytes`: MSKIPBYTES as given (more than the length needs: no decoder accepts that); `reserved`: the reserved bit; `pad`: pad_to_byte"""
+    w.put(0, 1); w.put(3, 2); w.put(reserved, 1)  # ISLAST = 0, MNIBBLES = 0 (code 3), reserved
     n = len(payload)
-    nbytes = 0 if n == 0 else (n - 1).bit_length() // 8 + 1 if n > 1 else 1
-    if n == 0:
-        w.put(0, 2)
-    else:
-        nbytes = max(1, ((n - 1).bit_length() + 7) // 8)
-        w.put(nbytes, 2); w.put(n - 1, 8 * nbytes)
-    w.align()
+    least = 0 if n == 0 else max(1, ((n - 1).bit_length() + 7) // 8)
+    if nbytes is None:
+        nbytes = least
+    assert least <= nbytes <= 3
+    w.put(nbytes, 2)
+    if nbytes:
+        w.put(max(0, n - 1), 8 * nbytes)
+    pad_to_byte(w, pad)
     w.out += payload
 
 
@@ -382,10 +625,104 @@ class Plan:
     """what the caller chooses: block splits per category as [(type, count), ...] covering every symbol of the category
     (literals, commands, explicit distances), literal context modes per literal block type, the context maps."""
 
-    def __init__(self, lit_blocks=None, cmd_blocks=None, dist_blocks=None, modes=None, lit_map=None, dist_map=None, npostfix=0, ndirect=0, type_codes="direct"):
+    def __init__(self, lit_blocks=None, cmd_blocks=None, dist_blocks=None, modes=None, lit_map=None, dist_map=None, npostfix=0, ndirect=0, type_codes="direct",
+                 codes=None, map_forms=None, large_window=False):
+        """`codes`: {(slot, index): function of (histogram, alphabet) -> a WireCode} for the prefix codes whose wire form the caller
+        chooses -- slots "lit", "cmd", "dist" (index = the tree), "btype", "blen" (index = the category), "lmap", "dmap" (index 0: the
+        context map's own code); every other code is a PrefixCode of its histogram.  `map_forms`: {"lit" / "dist": a form for
+        write_context_map}.  `large_window`: the distance alphabet of a large-window stream."""
         self.lit_blocks, self.cmd_blocks, self.dist_blocks = lit_blocks, cmd_blocks, dist_blocks
         self.modes, self.lit_map, self.dist_map = modes, lit_map, dist_map
         self.npostfix, self.ndirect, self.type_codes = npostfix, ndirect, type_codes
+        self.codes, self.map_forms, self.large_window = codes or {}, map_forms or {}, large_window
+
+
+def max_distance_symbol(ndirect, npostfix):
+    """the number of distance symbols a large-window stream may use (distances up to 2^31 - 4), as the decoders compute it"""
+    bound, diff, postfix = (0, 4, 12, 28)[npostfix], (73, 126, 228, 424)[npostfix], 1 << npostfix
+    if ndirect < bound:
+        return ndirect + diff + postfix
+    if ndirect > bound + postfix:
+        return ndirect + diff
+    return bound + diff + postfix
+
+
+def forward_mtf(values):
+    """section 7.3 backwards: values -> move-to-front indices"""
+    mtf, out = list(range(256)), []
+    for v in values:
+        i = mtf.index(v)
+        out.append(i)
+        mtf.insert(0, mtf.pop(i))
+    return out
+
+
+def zero_run_pieces(n, rlemax):
+    """a run of n zeros as the longest pieces RLEMAX allows: [(code, extra)], code 0 = a single zero"""
+    out = []
+    while n:
+        c = min(rlemax, n.bit_length() - 1)
+        if c == 0:
+            out.append((0, 0)); n -= 1
+        else:
+            take = min(n, (2 << c) - 1)
+            out.append((c, take - (1 << c))); n -= take
+    return out
+
+
+def write_context_map(w, cmap, ntrees, form=None, code_for=None, log=None, kind=None, unchecked=False):
+    """section 7.3.  `form`: {"rlemax": 0 .. 16, "imtf": 0 / 1, "runs": function of (length of a run of zeros, RLEMAX) ->
+    [(code, extra)] (code 0 = one zero; default zero_run_pieces), "items": the symbols as they go on the wire, [("v", index)] and
+    [("run", code, extra)] -- unchecked: they need not add up to the map; "ntrees": NTREES where the map does not name them all}.  With IMTF = 1 the forward move-to-front is done here.
+    `code_for(histogram, alphabet)` -> the map's own prefix code (default PrefixCode)."""
+    form = form or {}
+    rlemax, imtf = form.get("rlemax", 0), form.get("imtf", 0)
+    write_varlen8(w, ntrees - 1)
+    rec = {"kind": kind, "form": "map", "ntrees": ntrees, "size": len(cmap), "start": w.bits()}
+    if log is not None:
+        log.append(rec)
+    if ntrees < 2:
+        return
+    if rlemax:
+        w.put(1, 1); w.put(rlemax - 1, 4)
+    else:
+        w.put(0, 1)
+    values = forward_mtf(cmap) if imtf else list(cmap)
+    items = form.get("items")
+    if items is None:
+        items, pieces, i = [], form.get("runs", zero_run_pieces), 0
+        while i < len(values):
+            if values[i]:
+                items.append(("v", values[i])); i += 1
+                continue
+            j = i
+            while j < len(values) and values[j] == 0:
+                j += 1
+            got = pieces(j - i, rlemax)
+            assert sum((1 << c) + e if c else 1 for c, e in got) == j - i and all(c <= rlemax and 0 <= e < (1 << c) for c, e in got), (j - i, got)
+            items += [("run", c, e) if c else ("v", 0) for c, e in got]
+            i = j
+    alphabet = ntrees + rlemax
+    h = [0] * alphabet
+    for it in items:
+        h[it[1] if it[0] == "run" else it[1] + rlemax if it[1] else 0] += 1
+    code = (code_for or PrefixCode)(h, alphabet)
+    if isinstance(code, WireCode):
+        code.write_code(w, log, kind + "_code")
+    else:
+        code.write_code(w)
+    rec.update(rlemax=rlemax, imtf=imtf, runs=[], indices=sorted({it[1] for it in items if it[0] == "v"}), mtf_max=max([it[1] for it in items if it[0] == "v"], default=0),
+               items_start=w.bits(), filled=0, items=list(items), map=list(cmap))
+    for it in items:
+        if it[0] == "run":
+            code.put(w, it[1]); w.put(it[2], it[1])
+            rec["runs"].append((it[1], it[2], rec["filled"]))
+            rec["filled"] += (1 << it[1]) + it[2]
+        else:
+            code.put(w, it[1] + rlemax if it[1] else 0)
+            rec["filled"] += 1
+    w.put(imtf, 1)
+    rec["end"] = w.bits()
 
 
 def greedy_commands(data, min_match=4, max_dist=1 << 16, start=0, history=b""):
@@ -416,7 +753,7 @@ def greedy_commands(data, min_match=4, max_dist=1 << 16, start=0, history=b""):
     return cmds
 
 
-def emit_compressed(w, commands, plan, is_last, prev=b"", dictionary=b"", wbits=None, log=None, unchecked=False, mlen=None, literals=None, realised=None, ring_io=None):
+def emit_compressed(w, commands, plan, is_last, prev=b"", dictionary=b"", wbits=None, log=None, unchecked=False, mlen=None, literals=None, realised=None, ring_io=None, hlog=None, nibbles=None):
     """commands: [(insert bytes, copy_len, distance)]; distance 0 with copy_len 0 only as the final literals-only command
     (it is written with copy length 2 and an implicit distance that the decoder never executes: the metablock is complete
     after its literals).  `prev` = the stream's output so far (copies may reach into it; its last two bytes are the literal
@@ -441,7 +778,11 @@ def emit_compressed(w, commands, plan, is_last, prev=b"", dictionary=b"", wbits=
     gives the same output.
 
     `ring_io`: the ring of the last four distances as a list that is read at the start and written back at the end -- a stream of
-    several metablocks (`prev=`) keeps its ring from one to the next, as a decoder does; without it every metablock starts from RING_INIT."""
+    several metablocks (`prev=`) keeps its ring from one to the next, as a decoder does; without it every metablock starts from RING_INIT.
+
+    `hlog`: a list that receives one record per prefix code whose wire form the plan chooses (WireCode.write_code) and per context
+    map (write_context_map), each with its bit positions in the stream, {"kind": "metablock", "start"} in front of them and
+    {"kind": "commands", "start"} where the first command begins."""
     npf, ndir = plan.npostfix, plan.ndirect
     max_backward = (1 << wbits) - 16 if wbits else None
     ring = list(RING_INIT) if ring_io is None else list(ring_io)
@@ -563,7 +904,8 @@ def emit_compressed(w, commands, plan, is_last, prev=b"", dictionary=b"", wbits=
     modes = plan.modes or [0] * nbt[0]
     lit_map = plan.lit_map or [t for t in range(nbt[0]) for _ in range(64)]
     dist_map = plan.dist_map or [t for t in range(nbt[2]) for _ in range(4)]
-    ntrees_l, ntrees_d = max(lit_map) + 1, max(dist_map) + 1
+    ntrees_l = max(max(lit_map) + 1, plan.map_forms.get("lit", {}).get("ntrees", 1))   # (a form may declare trees that the map does not name)
+    ntrees_d = max(max(dist_map) + 1, plan.map_forms.get("dist", {}).get("ntrees", 1))
 
     def assign(blocks, n):
         types = []
@@ -574,7 +916,18 @@ def emit_compressed(w, commands, plan, is_last, prev=b"", dictionary=b"", wbits=
         return types
     lit_types, cmd_types, dist_types = assign(lit_blocks, len(lits)), assign(cmd_blocks, len(cmd_syms)), assign(dist_blocks, len(dist_syms))
     # --- histograms
-    dist_alpha = 16 + ndir + (48 << npf)
+    dist_alpha = 16 + ndir + ((124 if plan.large_window else 48) << npf)
+    dist_max = max_distance_symbol(ndir, npf) if plan.large_window else dist_alpha
+
+    def make_code(slot, index, hist, alphabet):
+        chosen = plan.codes.get((slot, index))
+        return chosen(hist, alphabet) if chosen else PrefixCode(hist, alphabet)
+
+    def write_code(code, slot, index):
+        if isinstance(code, WireCode):
+            code.write_code(w, hlog, "%s%d" % (slot, index))
+        else:
+            code.write_code(w)
     h_lit = [[0] * 256 for _ in range(ntrees_l)]
     lit_tree_of = []
     for (b, p1, p2), t in zip(lits, lit_types):
@@ -591,7 +944,9 @@ def emit_compressed(w, commands, plan, is_last, prev=b"", dictionary=b"", wbits=
         dist_tree_of.append(tree)
         h_dist[tree][sym] += 1
     # --- header
-    write_mlen(w, is_last, mlen)
+    if hlog is not None:
+        hlog.append({"kind": "metablock", "start": w.bits()})
+    write_mlen(w, is_last, mlen, nibbles=nibbles)
     switch_codes = []
     for cat, blocks in enumerate((lit_blocks, cmd_blocks, dist_blocks)):
         write_varlen8(w, nbt[cat] - 1)
@@ -618,35 +973,28 @@ def emit_compressed(w, commands, plan, is_last, prev=b"", dictionary=b"", wbits=
         lsyms = [_code_of(c, _BL_BASE, _BL_EXTRA) for _, c in blocks]
         for c, _, _ in lsyms:
             h_l[c] += 1
-        tcode, lcode = PrefixCode(h_t, nbt[cat] + 2), PrefixCode(h_l, 26)
-        tcode.write_code(w); lcode.write_code(w)
+        tcode, lcode = make_code("btype", cat, h_t, nbt[cat] + 2), make_code("blen", cat, h_l, 26)
+        write_code(tcode, "btype", cat); write_code(lcode, "blen", cat)
         c, v, nb = lsyms[0]
         lcode.put(w, c); w.put(v, nb)
         switch_codes.append((tcode, lcode, tsyms, lsyms))
+        if hlog is not None:
+            hlog.append({"kind": "switches", "cat": cat, "nbt": nbt[cat], "type_codes": tsyms, "lengths": lsyms, "counts": [c for _, c in blocks],
+                         "symbols": (len(lits), len(cmd_syms), len(dist_syms))[cat], "simple": (tcode.simple, lcode.simple)})
     w.put(npf, 2); w.put(ndir >> npf, 4)
     for t in range(nbt[0]):
         w.put(modes[t], 2)
 
-    def write_context_map(cmap, ntrees):
-        write_varlen8(w, ntrees - 1)
-        if ntrees < 2:
-            return
-        w.put(0, 1)  # no run-length coding of zeros
-        h = [0] * ntrees
-        for v in cmap:
-            h[v] += 1
-        code = PrefixCode(h, ntrees)
-        code.write_code(w)
-        for v in cmap:
-            code.put(w, v)
-        w.put(0, 1)  # IMTF = 0
-    write_context_map(lit_map[:nbt[0] * 64], ntrees_l)
-    write_context_map(dist_map[:nbt[2] * 4], ntrees_d)
-    lit_codes = [PrefixCode(h, 256) for h in h_lit]
-    cmd_codes = [PrefixCode(h, 704) for h in h_cmd]
-    dist_codes = [PrefixCode(h, dist_alpha) for h in h_dist]
-    for c in lit_codes + cmd_codes + dist_codes:
-        c.write_code(w)
+    write_context_map(w, lit_map[:nbt[0] * 64], ntrees_l, plan.map_forms.get("lit"), plan.codes.get(("lmap", 0)), hlog, "lit_map", unchecked)
+    write_context_map(w, dist_map[:nbt[2] * 4], ntrees_d, plan.map_forms.get("dist"), plan.codes.get(("dmap", 0)), hlog, "dist_map", unchecked)
+    lit_codes = [make_code("lit", i, h, 256) for i, h in enumerate(h_lit)]
+    cmd_codes = [make_code("cmd", i, h, 704) for i, h in enumerate(h_cmd)]
+    dist_codes = [make_code("dist", i, h, dist_alpha) for i, h in enumerate(h_dist)]
+    for slot, group in (("lit", lit_codes), ("cmd", cmd_codes), ("dist", dist_codes)):
+        for i, c in enumerate(group):
+            write_code(c, slot, i)
+    if hlog is not None:
+        hlog.append({"kind": "commands", "start": w.bits()})
     # --- the commands, with block switches where a block's count runs out
     state = []
     for cat, blocks in enumerate((lit_blocks, cmd_blocks, dist_blocks)):
