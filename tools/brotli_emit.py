@@ -31,6 +31,9 @@ context map its RLEMAX, its split into zero runs and its IMTF (the forward move-
 emit_metadata and emit_stored take MNIBBLES, MSKIPBYTES, the reserved bit and padding as given.  `unchecked` writes what no
 decoder accepts.  `hlog=[]` receives one record per such code, per context map and per category's block switches, with the
 bit positions of every word, the runs the repeat words resolved to and the 64-bit steps a wide reader takes over them.
+
+`llog=[]` receives one record per literal: where its code word lies in the stream, the two bytes in front of it, its block type,
+mode, context and tree (tools/make_literal_vectors.py, tests/golden/emitter_literals/).
 """
 import heapq
 
@@ -753,7 +756,7 @@ def greedy_commands(data, min_match=4, max_dist=1 << 16, start=0, history=b""):
     return cmds
 
 
-def emit_compressed(w, commands, plan, is_last, prev=b"", dictionary=b"", wbits=None, log=None, unchecked=False, mlen=None, literals=None, realised=None, ring_io=None, hlog=None, nibbles=None):
+def emit_compressed(w, commands, plan, is_last, prev=b"", dictionary=b"", wbits=None, log=None, unchecked=False, mlen=None, literals=None, realised=None, ring_io=None, hlog=None, nibbles=None, llog=None):
     """commands: [(insert bytes, copy_len, distance)]; distance 0 with copy_len 0 only as the final literals-only command
     (it is written with copy length 2 and an implicit distance that the decoder never executes: the metablock is complete
     after its literals).  `prev` = the stream's output so far (copies may reach into it; its last two bytes are the literal
@@ -782,13 +785,20 @@ def emit_compressed(w, commands, plan, is_last, prev=b"", dictionary=b"", wbits=
 
     `hlog`: a list that receives one record per prefix code whose wire form the plan chooses (WireCode.write_code) and per context
     map (write_context_map), each with its bit positions in the stream, {"kind": "metablock", "start"} in front of them and
-    {"kind": "commands", "start"} where the first command begins."""
+    {"kind": "commands", "start"} where the first command begins.
+
+    `llog`: a list that receives one record per literal -- "k" (its number in the metablock), "cmd" (the command it belongs to), "pos"
+    (its output position in the stream), "bit" (the stream bit its code word starts at, behind a block switch if one stands in front of
+    it), "nbits", "byte", "p1", "p2" (the two bytes in front of it as the decoder has them: zeros in front of the stream's start and,
+    with a custom dictionary, in place of the dictionary's last bytes), "type" (the literal block type), "mode", "context", "tree" and "first_of_block" (a
+    block switch was written in front of it)."""
     npf, ndir = plan.npostfix, plan.ndirect
     max_backward = (1 << wbits) - 16 if wbits else None
     ring = list(RING_INIT) if ring_io is None else list(ring_io)
     # --- the data and symbol sequences
     out = bytearray()
     lits, cmd_syms, dist_syms = [], [], []
+    lit_at = []    # per literal: its offset in the metablock's output
     has_dist = []  # per command: does a distance symbol follow its literals?
     inserts = []   # per command: its literals
     pad = 2 - min(2, len(prev))  # (zero bytes that stand for the context in front of the stream's first byte: not output)
@@ -801,12 +811,12 @@ def emit_compressed(w, commands, plan, is_last, prev=b"", dictionary=b"", wbits=
             made = bytearray()
             for _ in range(ins):
                 b = literals(history[-1], history[-2], len(lits))
-                lits.append((b, history[-1], history[-2]))
+                lits.append((b, history[-1], history[-2])); lit_at.append(len(history) - start)
                 history.append(b); made.append(b)
             ins = bytes(made)
         else:
             for b in ins:
-                lits.append((b, history[-1], history[-2]))
+                lits.append((b, history[-1], history[-2])); lit_at.append(len(history) - start)
                 history.append(b)
         inserts.append(ins)
         if clen == 0:
@@ -1002,7 +1012,8 @@ def emit_compressed(w, commands, plan, is_last, prev=b"", dictionary=b"", wbits=
 
     def consume(cat):
         st = state[cat]
-        if st["left"] == 0:
+        switched = st["left"] == 0
+        if switched:
             tcode, lcode, tsyms, lsyms = switch_codes[cat]
             k = st["next"]
             tcode.put(w, tsyms[k])
@@ -1011,6 +1022,7 @@ def emit_compressed(w, commands, plan, is_last, prev=b"", dictionary=b"", wbits=
             st["left"] = (lit_blocks, cmd_blocks, dist_blocks)[cat][k + 1][1]
             st["next"] = k + 1
         st["left"] -= 1
+        return switched
     li = di = 0
     for ci, ins in enumerate(inserts):
         consume(1)
@@ -1018,8 +1030,14 @@ def emit_compressed(w, commands, plan, is_last, prev=b"", dictionary=b"", wbits=
         cmd_codes[cmd_types[ci]].put(w, sym)
         w.put(iv, ib); w.put(cv, cb)
         for b in ins:
-            consume(0)
+            switched = consume(0)
+            at = w.bits()
             lit_codes[lit_tree_of[li]].put(w, b)
+            if llog is not None:
+                _, p1, p2 = lits[li]
+                t = lit_types[li]
+                llog.append({"k": li, "cmd": ci, "pos": len(prev) + lit_at[li], "bit": at, "nbits": w.bits() - at, "byte": b, "p1": p1, "p2": p2, "type": t,
+                             "mode": modes[t], "context": literal_context(modes[t], p1, p2), "tree": lit_tree_of[li], "first_of_block": switched})
             li += 1
         if has_dist[ci]:
             consume(2)

@@ -3,7 +3,9 @@
  -- up to 256 literal block types, every literal context mode (MSB6 included) with chosen context
 maps, block-type codes 0 / 1, NPOSTFIX / NDIRECT != 0, sequences of compressed, stored, metadata and empty metablocks.
 Every stream is checked with Google's libbrotlidec (and the oracle) before it is written; the manifest carries size and
-SHA-256 of the raw data."""
+SHA-256 of the raw data.  The families built on the same emitter, each with a generator of its own: make_word_vectors.py
+(tests/golden/emitter_words/), make_copy_vectors.py (emitter_copies/), make_header_vectors.py (emitter_headers/) and
+make_literal_vectors.py (emitter_literals/)."""
 import hashlib
 import json
 import os
