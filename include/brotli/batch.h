@@ -229,6 +229,57 @@ BROTLI_DEC_API uint32_t BrotliAmdDebugDigestHost(uint32_t kind, const uint8_t* d
 /* crc x^(8 nbytes) mod the kind's polynomial, for any 64-bit nbytes: crc(A B) == BrotliAmdDebugDigestShift(kind, crc(A), |B|) ^ crc(B). */
 BROTLI_DEC_API uint32_t BrotliAmdDebugDigestShift(uint32_t kind, uint32_t crc, uint64_t nbytes);
 
+/* ---- Unshuffle on the device: byte planes of outputs back into elements ----
+ *
+ * Numeric data that is compressed with Brotli is, as a rule, not stored as the bytes of the array but SHUFFLED into byte planes first -- plane
+ * 0 holds byte 0 of every element, plane 1 byte 1, and so on --, which puts the exponent bytes of floats next to each other: Parquet's
+ * BYTE_STREAM_SPLIT encoding under its BROTLI codec, the shuffle filter of Blosc and HDF5, the byte grouping of checkpoint compressors.  The
+ * decoded bytes are then one step away from the tensor, and these calls take it where the bytes lie.
+ *
+ * THE TRANSFORM.  A segment of len bytes and a width w: m = len / w elements and r = len % w bytes left over.  For p < w m
+ *     dst[p] = src[(p % w) m + p / w],
+ * and for w m <= p < len, dst[p] = src[p]: the r left-over bytes stay in place at the end (Blosc's rule; Parquet never has r != 0).  The widths
+ * are 1, 2, 4 and 8; width 1 is a copy.  The width is PER SEGMENT: a checkpoint mixes int8 with wider types.  Only this direction -- planes to
+ * elements -- exists.
+ *
+ * OUT OF PLACE: no destination range may overlap any source range or any other destination range of the call.
+ *
+ * One launch does all segments, the work split by bytes as the ragged copy's is (csrc/brotli_unshuffle.h, csrc/brotli_unshuffle_kernels.hip): one
+ * tensor of a gigabyte is spread over the whole device like a hundred thousand pages of a hundred bytes. */
+
+/* n segments in DEVICE memory -- lens[i] bytes of planes at d_src[i] become lens[i] bytes of elements of width widths[i] at d_dst[i]; any
+ * alignment, any length, 0 included; n is not bound by the batch object's max_streams --: one launch on hip_stream, and the call waits on that
+ * stream.  No byte outside [d_dst[i], d_dst[i] + lens[i]) is written; nothing outside the 16-byte-aligned span around
+ * [d_src[i], d_src[i] + lens[i]) is read.  n == 0 returns 0.  A negative value, and a BrotliAmdLastError text, for a NULL batch, a NULL array with
+ * n != 0 and any width that is not 1, 2, 4 or 8: the widths are checked on the host in front of everything else, so nothing is launched and no
+ * byte is written. */
+BROTLI_DEC_API int BrotliAmdBatchUnshuffleSegments(BrotliAmdBatch* batch, uint32_t n, const void* const* d_src, void* const* d_dst,
+                                                  const size_t* lens, const uint8_t* widths, void* hip_stream);
+
+/* The same for the DELIVERED bytes -- [out, out + decoded_size) -- of every stream of the last decode call on the object: stream i's go to
+ * d_dst[i] (device memory of decoded_size bytes, any alignment) by widths[i]; d_dst[i] == NULL skips stream i (its width is not looked at).
+ * Where the sources are, and when they are valid, is BrotliAmdBatchDigestOutputs' rule exactly:
+ *   - after BrotliAmdBatchDecodeDevice(Dict) or BrotliAmdBatchRelaunch, once BrotliAmdBatchWait has returned: the caller's d_out[i];
+ *   - after BrotliAmdBatchDecodeHost(Dict): the streams' slots in the object's device staging, which it keeps;
+ *   - after BrotliAmdBatchDecodeDevicePacked / HostPacked: [offsets[i], offsets[i + 1]) of the packed output.
+ * A stream that ended in an error or NEEDS_MORE_OUTPUT is transformed over its decoded_size bytes by the rule above (m = decoded_size / w).
+ * The launch runs on the stream of that decode call and the call waits for it.  It is not a decode call itself: BrotliAmdBatchPackedOutput stays
+ * valid, and BrotliAmdBatchRelaunch and the Last* accessors say what they said before.  A negative value, and a BrotliAmdLastError text, for a NULL
+ * batch or a NULL array, a width that is not 1, 2, 4 or 8 (nothing is launched), an object without a decode call, a last decode call that
+ * failed behind its argument checks (one of no streams returns 0), and a launch that BrotliAmdBatchWait has not been called for. */
+BROTLI_DEC_API int BrotliAmdBatchUnshuffleOutputs(BrotliAmdBatch* batch, void* const* d_dst, const uint8_t* widths);
+
+/* Milliseconds the unshuffle kernel took in the last of the two calls above (HIP events around its launch). */
+BROTLI_DEC_API float BrotliAmdBatchLastUnshuffleMs(BrotliAmdBatch* batch);
+
+/* Test hooks (no device needed).  The bytes of destination memory in one tile of an unshuffle launch (the unit in which its blocks share the
+ * work); */
+BROTLI_DEC_API uint32_t BrotliAmdDebugUnshuffleTile(void);
+/* the transform of src[0, len) into dst[0, len) by the device's unit function on the host, over every 16-byte unit of the segment: source and
+ * destination are placed at src_skew and dst_skew (0..15) past a 16-byte boundary among bytes that are not theirs.  0; negative, a
+ * BrotliAmdLastError text and an untouched dst for a width that is not 1, 2, 4 or 8, a skew > 15, or a byte written outside the destination. */
+BROTLI_DEC_API int BrotliAmdDebugUnshuffleHost(uint32_t width, const uint8_t* src, size_t len, uint8_t* dst, uint32_t src_skew, uint32_t dst_skew);
+
 /* Milliseconds the last launch spent in the decode kernel (HIP events on the launch stream). */
 BROTLI_DEC_API float BrotliAmdBatchLastKernelMs(BrotliAmdBatch* batch);
 

@@ -38,6 +38,8 @@ BATCH_H_SYMBOLS = [
     "BrotliAmdBatchPackedFetch", "BrotliAmdBatchDecodeHostPacked", "BrotliAmdBatchLastPackedLaunches", "BrotliAmdBatchLastPackedCopies",
     "BrotliAmdBatchDigestSegments", "BrotliAmdBatchDigestOutputs", "BrotliAmdBatchLastDigestMs", "BrotliAmdDebugDigestTile",
     "BrotliAmdDebugDigestHost", "BrotliAmdDebugDigestShift",
+    "BrotliAmdBatchUnshuffleSegments", "BrotliAmdBatchUnshuffleOutputs", "BrotliAmdBatchLastUnshuffleMs", "BrotliAmdDebugUnshuffleTile",
+    "BrotliAmdDebugUnshuffleHost",
 ]
 
 
@@ -153,6 +155,13 @@ def load_library():
         L.BrotliAmdDebugDigestHost.argtypes = [u32, vp, sz, u32, u32]
         L.BrotliAmdDebugDigestShift.restype = u32
         L.BrotliAmdDebugDigestShift.argtypes = [u32, u32, ctypes.c_uint64]
+    if hasattr(L, "BrotliAmdBatchUnshuffleSegments"):   # (unshuffle: an older build of the library, loaded for an A/B, has none)
+        L.BrotliAmdBatchUnshuffleSegments.argtypes = [vp, u32, vp, vp, vp, vp, vp]
+        L.BrotliAmdBatchUnshuffleOutputs.argtypes = [vp, vp, vp]
+        L.BrotliAmdBatchLastUnshuffleMs.restype = ctypes.c_float
+        L.BrotliAmdBatchLastUnshuffleMs.argtypes = [vp]
+        L.BrotliAmdDebugUnshuffleTile.restype = u32
+        L.BrotliAmdDebugUnshuffleHost.argtypes = [u32, vp, sz, vp, u32, u32]
     L.BrotliAmdBatchLastKernelMs.restype = ctypes.c_float
     L.BrotliAmdBatchLastKernelMs.argtypes = [vp]
     L.BrotliAmdBatchLastSecondPassCount.restype = ctypes.c_uint32
@@ -212,6 +221,23 @@ def digest_shift(crc, nbytes, kind=DIGEST_CRC32):
     return int(load_library().BrotliAmdDebugDigestShift(kind, crc, nbytes))
 
 
+def unshuffle_host(data: bytes, width, src_skew=0, dst_skew=0):
+    """BrotliAmdDebugUnshuffleHost: the byte planes in `data` back into elements of `width` bytes by the device's unit function on the host (no
+    device needed), source and destination placed at their skews past a 16-byte boundary -> bytes"""
+    L = load_library()
+    data = bytes(data)
+    src = ctypes.create_string_buffer(data, max(1, len(data)))
+    dst = ctypes.create_string_buffer(max(1, len(data)))
+    if L.BrotliAmdDebugUnshuffleHost(width, ctypes.addressof(src), len(data), ctypes.addressof(dst), src_skew, dst_skew) != 0:
+        raise RuntimeError("BrotliAmdDebugUnshuffleHost failed: " + last_error())
+    return dst.raw[:len(data)]
+
+
+def unshuffle_tile():
+    """BrotliAmdDebugUnshuffleTile: the bytes of destination in one tile of an unshuffle launch"""
+    return int(load_library().BrotliAmdDebugUnshuffleTile())
+
+
 # ------------------------------------------------------------------ batch (include/brotli/batch.h)
 class Batch:
     """Owns one BrotliAmdBatch on the current HIP device."""
@@ -224,6 +250,8 @@ class Batch:
         self.max_streams = max_streams
         self.n = 0
         self.out_n = 0   # streams of the last decode call, a packed one included (digest_outputs)
+        self.out_sizes = None   # their delivered bytes (None: no call yet, or a launch nobody has waited for): tensors.outputs_as_tensors
+        self._caps = []
 
     def close(self):
         if self._h:
@@ -255,6 +283,7 @@ class Batch:
         elif self._L.BrotliAmdBatchDecodeDevice(self._h, n, a_in, a_is, a_out, a_oc, flags, stream) != 0:
             raise RuntimeError("BrotliAmdBatchDecodeDevice failed: " + last_error())
         self.n = self.out_n = n
+        self.out_sizes, self._caps = None, list(out_caps)
 
     def relaunch(self, stream=None):
         if self._L.BrotliAmdBatchRelaunch(self._h, stream) != 0:
@@ -264,6 +293,8 @@ class Batch:
         res = (BatchResult * max(1, self.n))()
         if self._L.BrotliAmdBatchWait(self._h, res) != 0:
             raise RuntimeError("BrotliAmdBatchWait failed: " + last_error())
+        if self.n and self.out_n == self.n:
+            self.out_sizes = [min(res[i].decoded_size, self._caps[i]) for i in range(self.n)]
         return list(res)[:self.n]
 
     def last_kernel_ms(self):
@@ -311,6 +342,7 @@ class Batch:
             raise RuntimeError("BrotliAmdBatchDecodeHost failed: " + last_error())
         self.n = self.out_n = n
         results = list(res)[:n]
+        self.out_sizes = [min(results[i].decoded_size, out_caps[i]) for i in range(n)]
         return results, [outs[i].raw[:min(results[i].decoded_size, out_caps[i])] for i in range(n)]
 
     def size_hints(self, in_ptrs, in_sizes, flags=FLAG_LARGE_WINDOW, stream=None):
@@ -348,6 +380,7 @@ class Batch:
             raise RuntimeError("BrotliAmdBatchDecodeDevicePacked failed: " + last_error())
         self.n, self.out_n = 0, n
         ptr, offsets = self._packed_view(n)
+        self.out_sizes = [offsets[i + 1] - offsets[i] for i in range(n)]
         return list(res)[:n], ptr, offsets
 
     def packed_fetch(self, total):
@@ -379,6 +412,7 @@ class Batch:
             raise RuntimeError("BrotliAmdBatchDecodeHostPacked failed: " + last_error())
         self.n, self.out_n = 0, n
         _, offsets = self._packed_view(n)
+        self.out_sizes = [offsets[i + 1] - offsets[i] for i in range(n)]
         blob = self.packed_fetch(offsets[n])
         return list(res)[:n], [blob[offsets[i]:offsets[i + 1]] for i in range(n)]
 
@@ -416,6 +450,35 @@ class Batch:
         """milliseconds the digest kernel took in the last digest_segments / digest_outputs"""
         return float(self._L.BrotliAmdBatchLastDigestMs(self._h))
 
+    def unshuffle_segments(self, src_ptrs, dst_ptrs, lens, widths, stream=None):
+        """BrotliAmdBatchUnshuffleSegments: lens[i] bytes of byte planes at the device address src_ptrs[i] become elements of widths[i] bytes
+        (1, 2, 4, 8) at dst_ptrs[i]; any alignment, any length; out of place.  One launch and a wait on `stream`."""
+        n = len(src_ptrs)
+        if len(dst_ptrs) != n or len(lens) != n or len(widths) != n:
+            raise ValueError("src_ptrs, dst_ptrs, lens and widths: one entry per segment each")
+        a_s = (ctypes.c_void_p * max(1, n))(*src_ptrs)
+        a_d = (ctypes.c_void_p * max(1, n))(*dst_ptrs)
+        a_l = (ctypes.c_size_t * max(1, n))(*lens)
+        a_w = (ctypes.c_uint8 * max(1, n))(*[w if 0 <= w <= 255 else 0 for w in widths])
+        if self._L.BrotliAmdBatchUnshuffleSegments(self._h, n, a_s, a_d, a_l, a_w, stream) != 0:
+            raise RuntimeError("BrotliAmdBatchUnshuffleSegments failed: " + last_error())
+
+    def unshuffle_outputs(self, dst_ptrs, widths):
+        """BrotliAmdBatchUnshuffleOutputs: the delivered bytes of every stream of the last decode call on this object (after decode_device:
+        once wait() has returned), taken as byte planes of widths[i], become elements at the device address dst_ptrs[i] (None or 0: the stream
+        is skipped).  One launch on that call's stream, and a wait."""
+        n = self.out_n
+        if len(dst_ptrs) != n or len(widths) != n:
+            raise ValueError("dst_ptrs and widths: one entry per stream of the last decode call each")
+        a_d = (ctypes.c_void_p * max(1, n))(*[p or None for p in dst_ptrs])
+        a_w = (ctypes.c_uint8 * max(1, n))(*[w if 0 <= w <= 255 else 0 for w in widths])
+        if self._L.BrotliAmdBatchUnshuffleOutputs(self._h, a_d, a_w) != 0:
+            raise RuntimeError("BrotliAmdBatchUnshuffleOutputs failed: " + last_error())
+
+    def last_unshuffle_ms(self):
+        """milliseconds the unshuffle kernel took in the last unshuffle_segments / unshuffle_outputs"""
+        return float(self._L.BrotliAmdBatchLastUnshuffleMs(self._h))
+
     def decode_host_raw(self, in_ptrs, in_sizes, out_ptrs, out_caps, flags=FLAG_LARGE_WINDOW):
         """BrotliAmdBatchDecodeHost on buffers the caller owns (host addresses as integers): nothing is copied on the Python side"""
         n = len(in_ptrs)
@@ -427,6 +490,7 @@ class Batch:
         if self._L.BrotliAmdBatchDecodeHost(self._h, n, a_in, a_is, a_out, a_oc, flags, res) != 0:
             raise RuntimeError("BrotliAmdBatchDecodeHost failed: " + last_error())
         self.n = self.out_n = n
+        self.out_sizes = [min(res[i].decoded_size, out_caps[i]) for i in range(n)]
         return list(res)[:n]
 
 

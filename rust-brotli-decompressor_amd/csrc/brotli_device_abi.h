@@ -111,6 +111,19 @@ typedef struct BrotliAmdCopySeg {
 } BrotliAmdCopySeg;
 #define BROTLI_AMD_COPY_TILE_BYTES 16384u  // destination bytes of one tile: the blocks of a launch take the segments' bytes tile by tile
 
+// One segment of an unshuffle launch (csrc/brotli_unshuffle_kernels.hip, csrc/brotli_unshuffle.h): the len bytes at src are `width` byte planes
+// (and len % width left-over bytes), the len bytes at dst become the elements; device addresses of any alignment, len 0 included, width 1, 2, 4
+// or 8.  No destination range overlaps a source range or another destination range.  Nothing outside [dst, dst + len) is written; nothing
+// outside the 16-byte-aligned span around [src, src + len) is read.
+typedef struct BrotliAmdUnshuffleSeg {
+  const uint8_t* src;
+  uint8_t* dst;
+  uint64_t len;
+  uint32_t width;
+  uint32_t reserved;
+} BrotliAmdUnshuffleSeg;
+#define BROTLI_AMD_UNSHUFFLE_TILE_BYTES 16384u  // destination bytes of one tile
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,6 +44,24 @@ int digest_device(BrotliAmdBatch* b, uint32_t kind, const std::vector<BrotliAmdC
 
 }  // namespace
 
+// The delivered bytes of every stream of the last decode call (brotli_host.h)
+bool brotli_amd_host::delivered_outputs(BrotliAmdBatch* b, std::vector<DeliveredBytes>* outs) {
+  outs->clear();
+  if (b->packed_valid) {   // a packed call: its buffer and offsets
+    for (size_t i = 0; i + 1 < b->packed_offsets.size(); i++)
+      outs->push_back(DeliveredBytes{b->packed_out + b->packed_offsets[i], b->packed_offsets[i + 1] - b->packed_offsets[i]});
+    return true;
+  }
+  if (b->outputs == BrotliAmdBatch::Outputs::NoCall) { g_last_error = "no decode call on this batch object yet"; return false; }
+  if (b->outputs == BrotliAmdBatch::Outputs::Failed) { g_last_error = "the last decode call on this batch object failed: it has no outputs"; return false; }
+  if (b->outputs == BrotliAmdBatch::Outputs::InFlight) { g_last_error = "the last launch has not been waited for (BrotliAmdBatchWait)"; return false; }
+  // the streams' own buffers (the staging arena's slots after a host call), as far as each was delivered
+  if (b->outputs == BrotliAmdBatch::Outputs::Waited)
+    for (uint32_t i = 0; i < b->n; i++)
+      outs->push_back(DeliveredBytes{b->h_descs[i].out, std::min<uint64_t>(b->h_status[i].decoded_size, b->h_descs[i].out_cap)});
+  return true;
+}
+
 extern "C" int BrotliAmdBatchDigestSegments(BrotliAmdBatch* b, uint32_t kind, uint32_t n, const void* const* d_ptrs, const size_t* lens,
                                             uint32_t* digests, void* hip_stream) {
   if (!known_kind(kind)) return -1;
@@ -61,19 +79,10 @@ extern "C" int BrotliAmdBatchDigestOutputs(BrotliAmdBatch* b, uint32_t kind, uin
   if (!known_kind(kind)) return -1;
   if (!b || !digests) { g_last_error = "invalid digest arguments"; return -1; }
   b->digest_ms = 0.0f;
+  std::vector<DeliveredBytes> outs;
+  if (!delivered_outputs(b, &outs)) return -1;
   std::vector<BrotliAmdCrcSeg> segs;
-  if (b->packed_valid) {   // a packed call: its buffer and offsets
-    for (size_t i = 0; i + 1 < b->packed_offsets.size(); i++)
-      segs.push_back(BrotliAmdCrcSeg{b->packed_out + b->packed_offsets[i], b->packed_offsets[i + 1] - b->packed_offsets[i]});
-  } else {
-    if (b->outputs == BrotliAmdBatch::Outputs::NoCall) { g_last_error = "no decode call on this batch object yet"; return -1; }
-    if (b->outputs == BrotliAmdBatch::Outputs::Failed) { g_last_error = "the last decode call on this batch object failed: it has no outputs"; return -1; }
-    if (b->outputs == BrotliAmdBatch::Outputs::InFlight) { g_last_error = "the last launch has not been waited for (BrotliAmdBatchWait)"; return -1; }
-    // the streams' own buffers (the staging arena's slots after a host call), as far as each was delivered
-    if (b->outputs == BrotliAmdBatch::Outputs::Waited)
-      for (uint32_t i = 0; i < b->n; i++)
-        segs.push_back(BrotliAmdCrcSeg{b->h_descs[i].out, std::min<uint64_t>(b->h_status[i].decoded_size, b->h_descs[i].out_cap)});
-  }
+  for (const DeliveredBytes& o : outs) segs.push_back(BrotliAmdCrcSeg{o.ptr, o.len});
   if (segs.empty()) return 0;
   DeviceGuard guard;
   if (!hip_ok(hipSetDevice(b->device), "hipSetDevice")) return -1;

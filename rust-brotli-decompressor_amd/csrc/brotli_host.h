@@ -4,6 +4,7 @@
 //   brotli_capi.cpp     the reference's C ABI (include/brotli/decode.h): error strings, one-shot, Prealloc, the streaming state
 //   brotli_stream_set.cpp  many streaming states in one launch, the ragged copy's debug hook
 //   brotli_digest.cpp   CRC-32 / CRC-32C of segments of device memory and of the last decode call's outputs
+//   brotli_unshuffle.cpp  byte planes of segments of device memory, and of the last decode call's outputs, back into elements
 #ifndef BROTLI_AMD_HOST_H_
 #define BROTLI_AMD_HOST_H_
 #include <hip/hip_runtime.h>
@@ -164,6 +165,10 @@ struct BrotliAmdBatch {
   brotli_amd_host::DevBuf<> d_digest;   // the segment table and the digests of one launch
   hipEvent_t ev_digest0 = nullptr, ev_digest1 = nullptr;   // around the digest launch (made at the first)
   float digest_ms = 0.0f;
+  // unshuffle (brotli_unshuffle.cpp)
+  brotli_amd_host::DevBuf<> d_unshuffle;   // the segment table of one launch
+  hipEvent_t ev_unshuffle0 = nullptr, ev_unshuffle1 = nullptr;   // around the unshuffle launch (made at the first)
+  float unshuffle_ms = 0.0f;
 };
 
 namespace brotli_amd_host {
@@ -212,6 +217,11 @@ int submit(BrotliAmdBatch* b, uint32_t n, hipStream_t stream);
 // (settle_output_limits).  False: a HIP failure.
 bool decode_descs(BrotliAmdBatch* b, uint32_t n, hipStream_t stream, bool exact_limit);
 constexpr bool kExactLimitDefault = false;   // what a batch object's exact_limit is until a batch entry point says otherwise: the one-shot and streaming paths' value
+// The DELIVERED bytes -- [out, out + decoded_size) -- of every stream of the last decode call on the object, where BrotliAmdBatchDigestOutputs and
+// BrotliAmdBatchUnshuffleOutputs find them (batch.h says where; brotli_digest.cpp).  False, and g_last_error: no decode call yet, one that failed, a
+// launch nobody has waited for.  A call of no streams: true and none.
+struct DeliveredBytes { const uint8_t* ptr; uint64_t len; };
+bool delivered_outputs(BrotliAmdBatch* b, std::vector<DeliveredBytes>* outs);
 void drop_packed(BrotliAmdBatch* b);   // a decode call ends the validity of the last packed call's output
 
 }  // namespace brotli_amd_host

@@ -192,6 +192,19 @@ extern "C" {
     pub fn BrotliAmdDebugDigestTile() -> u32;
     pub fn BrotliAmdDebugDigestHost(kind: u32, data: *const u8, n: size_t, skew: u32, run_units: u32) -> u32;
     pub fn BrotliAmdDebugDigestShift(kind: u32, crc: u32, nbytes: u64) -> u32;
+    /// byte planes back into elements: `n` segments of DEVICE memory (any alignment, any length), `widths[i]` of 1, 2, 4 or 8, out of place, in one
+    /// launch on `hip_stream`; waits
+    pub fn BrotliAmdBatchUnshuffleSegments(
+        batch: *mut BrotliAmdBatch, n: u32, d_src: *const *const c_void, d_dst: *const *mut c_void, lens: *const size_t, widths: *const u8,
+        hip_stream: *mut c_void,
+    ) -> c_int;
+    /// the same for the delivered bytes of every stream of the last decode call on the object (after `BrotliAmdBatchWait` for a device call);
+    /// a NULL `d_dst[i]` skips stream i
+    pub fn BrotliAmdBatchUnshuffleOutputs(batch: *mut BrotliAmdBatch, d_dst: *const *mut c_void, widths: *const u8) -> c_int;
+    pub fn BrotliAmdBatchLastUnshuffleMs(batch: *mut BrotliAmdBatch) -> f32;
+    /// test hooks (no device needed)
+    pub fn BrotliAmdDebugUnshuffleTile() -> u32;
+    pub fn BrotliAmdDebugUnshuffleHost(width: u32, src: *const u8, len: size_t, dst: *mut u8, src_skew: u32, dst_skew: u32) -> c_int;
     pub fn BrotliAmdLastError() -> *const c_char;
     pub fn BrotliAmdLastNote() -> *const c_char;
 }

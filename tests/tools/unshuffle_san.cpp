@@ -1,0 +1,75 @@
+// unshuffle_san.cpp -- the unshuffle unit function (csrc/brotli_unshuffle.h) under AddressSanitizer and UBSan, as a program of its own:
+//   g++ -std=c++17 -fsanitize=address,undefined -I rust-brotli-decompressor_amd/csrc tests/tools/unshuffle_san.cpp
+// Every width; every length 0..160 at every pair of skews for lengths up to 48 and at 32 pairs beyond, the lengths 16 w k + d, 1023 .. 1025 and
+// the tile's edges at 8 pairs, against a bytewise loop of its own.  Every source and every destination lies in a heap block of EXACTLY the
+// sixteen-byte words its span touches: a load or a store one word too far would be reported; the destination's bytes beside the segment must
+// keep their pattern.  Exits 0 when everything agreed.
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+#include "brotli_device_abi.h"
+#include "brotli_unshuffle.h"
+
+static uint32_t g_seed = 2026u;
+static uint32_t rnd() { g_seed = g_seed * 1664525u + 1013904223u; return g_seed >> 8; }
+
+static int one(uint32_t w, size_t len, uint32_t ss, uint32_t ds) {
+  const size_t sspan = len ? (ss + len + 15u) & ~(size_t)15 : 0, dspan = len ? (ds + len + 15u) & ~(size_t)15 : 0;
+  uint8_t* sb = static_cast<uint8_t*>(sspan ? std::aligned_alloc(16, sspan) : std::malloc(1));
+  uint8_t* db = static_cast<uint8_t*>(dspan ? std::aligned_alloc(16, dspan) : std::malloc(1));
+  if (!sb || !db) return 2;
+  for (size_t i = 0; i < sspan; i++) sb[i] = (uint8_t)rnd();
+  for (size_t i = 0; i < dspan; i++) db[i] = (uint8_t)(0xA5u ^ i);
+  const uint64_t src = (uint64_t)(uintptr_t)sb + ss, dst = (uint64_t)(uintptr_t)db + ds;
+  const uint64_t units = brotli_amd_unshuffle_seg_units(dst, len);
+  if (units != dspan / 16u) { std::fprintf(stderr, "units %llu of a span of %zu\n", (unsigned long long)units, dspan); return 1; }
+  // as a lane takes them in a tile inside one segment: two units a step (width 8 has a path of its own for two whole words), pairs that begin at
+  // an even or an odd unit; otherwise unit by unit, the last first (the units do not depend on their order)
+  if (rnd() & 1u) {
+    const uint64_t odd = (ss ^ ds) & 1u;
+    for (uint64_t k = odd; k < units; k += 2u) brotli_amd_unshuffle_two_units(src, dst, len, w, k, units);
+    if (odd && units) brotli_amd_unshuffle_unit(src, dst, len, w, 0);
+  } else {
+    for (uint64_t k = units; k-- > 0;) brotli_amd_unshuffle_unit(src, dst, len, w, k);
+  }
+  const size_t m = len / w;
+  for (size_t i = 0; i < dspan; i++) {
+    uint8_t want = (uint8_t)(0xA5u ^ i);
+    if (i >= ds && i < ds + len) { const size_t p = i - ds; want = p < w * m ? sb[ss + (p % w) * m + p / w] : sb[ss + p]; }
+    if (db[i] != want) { std::fprintf(stderr, "width %u length %zu skews %u %u: byte %zu is %02x, not %02x\n", w, len, ss, ds, i, db[i], want); return 1; }
+  }
+  std::free(sb); std::free(db);
+  return 0;
+}
+
+int main() {
+  unsigned long long segments = 0;
+  for (uint32_t w : {1u, 2u, 4u, 8u}) {
+    for (size_t len = 0; len <= 160; len++) {
+      if (len <= 48) {
+        for (uint32_t ss = 0; ss < 16u; ss++)
+          for (uint32_t ds = 0; ds < 16u; ds++) { if (int e = one(w, len, ss, ds)) return e; segments++; }
+      } else {
+        for (uint32_t k = 0; k < 16u; k++) {
+          if (int e = one(w, len, k, k)) return e;
+          if (int e = one(w, len, rnd() & 15u, rnd() & 15u)) return e;
+          segments += 2;
+        }
+      }
+    }
+    std::vector<size_t> lens = {1023, 1024, 1025, BROTLI_AMD_UNSHUFFLE_TILE_BYTES - 1u, BROTLI_AMD_UNSHUFFLE_TILE_BYTES, BROTLI_AMD_UNSHUFFLE_TILE_BYTES + w + 1u};
+    for (size_t k = 1; k <= 5; k++)
+      for (int d = -1; d <= (int)w; d++) lens.push_back(16u * w * k + d);
+    for (size_t len : lens)
+      for (uint32_t k = 0; k < 8u; k++) { if (int e = one(w, len, k < 2u ? 15u * k : rnd() & 15u, k < 2u ? 15u - 15u * k : rnd() & 15u)) return e; segments++; }
+    // a width that is none: nothing is read or written
+    if (int e = one(1u, 0, 3, 5)) return e;
+  }
+  uint8_t guard[32];
+  for (int i = 0; i < 32; i++) guard[i] = (uint8_t)i;
+  brotli_amd_unshuffle_unit((uint64_t)(uintptr_t)guard, (uint64_t)(uintptr_t)guard + 16u, 16, 3u, 0);
+  for (int i = 0; i < 32; i++) if (guard[i] != (uint8_t)i) return 1;
+  std::printf("%llu segments\n", segments);
+  return 0;
+}
