@@ -280,6 +280,70 @@ BROTLI_DEC_API uint32_t BrotliAmdDebugUnshuffleTile(void);
  * BrotliAmdLastError text and an untouched dst for a width that is not 1, 2, 4 or 8, a skew > 15, or a byte written outside the destination. */
 BROTLI_DEC_API int BrotliAmdDebugUnshuffleHost(uint32_t width, const uint8_t* src, size_t len, uint8_t* dst, uint32_t src_skew, uint32_t dst_skew);
 
+/* ---- Undelta on the device: running sums of deltas back into values ----
+ *
+ * The filter that stands beside shuffle in front of a general-purpose codec is DELTA: sorted timestamps, offsets and index arrays are stored as
+ * differences, TIFF's horizontal predictor and PNG's Sub filter store a sample minus its neighbour, and array containers put a delta or a
+ * byte-delta stage next to their shuffle stage (byte-delta is a width-1 delta per byte plane, undone in front of the unshuffle).  Undoing it is a
+ * running sum, and these calls take it where the decoded bytes lie.
+ *
+ * THE TRANSFORM.  A segment of len bytes and a width w: m = len / w elements, read as little-endian unsigned integers of w bytes, and r = len % w
+ * bytes left over.  For k < m
+ *     dst_elem[k] = (src_elem[0] + src_elem[1] + ... + src_elem[k]) mod 2^(8 w),
+ * and the r left-over bytes behind the last whole element are copied unchanged: unshuffle's rule, so a pipeline of the two agrees on them.  The
+ * widths are 1, 2, 4 and 8; width 1 is a running sum of bytes, not a copy.  The width is PER SEGMENT.  Only this direction -- deltas to values --
+ * exists.  Out of scope: signed or zigzag forms, deltas of order 2, strided or multi-sample deltas (PNG's Sub at 3 bytes a pixel) and XOR
+ * deltas.
+ *
+ * OUT OF PLACE: no destination range overlaps any source range or any other destination range of the call.  IN PLACE: d_dst[i] == d_src[i]
+ * exactly is allowed where that address is a multiple of widths[i].  In place at an address that is no multiple of the width is REJECTED on the
+ * host.  Any other overlap is UNDEFINED.
+ *
+ * A running sum is not local: a segment of a gigabyte is spread over the whole device and still comes out as one sum.  A call is three launches
+ * in stream order over tiles of destination bytes, the work split by bytes as the ragged copy's is -- the tiles' sums, one small launch that
+ * turns them into every tile's carry-in, and the running sums themselves --, and no block ever waits for another block's result
+ * (csrc/brotli_undelta.h, csrc/brotli_undelta_kernels.hip). */
+
+/* n segments in DEVICE memory -- lens[i] bytes of deltas at d_src[i] become lens[i] bytes of values of width widths[i] at d_dst[i]; any
+ * alignment, any length, 0 included; n is not bound by the batch object's max_streams --: the launches run on hip_stream, and the call waits on
+ * that stream.  No byte outside [d_dst[i], d_dst[i] + lens[i]) is written; nothing outside the 16-byte-aligned span around
+ * [d_src[i], d_src[i] + lens[i]) is read.  n == 0 returns 0.  A negative value, and a BrotliAmdLastError text, for a NULL batch, a NULL array with
+ * n != 0, any width that is not 1, 2, 4 or 8, and an in-place segment at an address that is not a multiple of its width: all of these are
+ * checked on the host in front of everything else, so nothing is launched and no byte is written. */
+BROTLI_DEC_API int BrotliAmdBatchUndeltaSegments(BrotliAmdBatch* batch, uint32_t n, const void* const* d_src, void* const* d_dst,
+                                                const size_t* lens, const uint8_t* widths, void* hip_stream);
+
+/* The same for the DELIVERED bytes -- [out, out + decoded_size) -- of every stream of the last decode call on the object: stream i's go to
+ * d_dst[i] (device memory of decoded_size bytes, any alignment) by widths[i]; d_dst[i] == NULL skips stream i (its width is not looked at).
+ * Where the sources are, and when they are valid, is BrotliAmdBatchUnshuffleOutputs' rule exactly, for the three kinds of decode call.  A stream
+ * that ended in an error or NEEDS_MORE_OUTPUT is transformed over its decoded_size bytes by the rule above (m = decoded_size / w).  The launches
+ * run on the stream of that decode call and the call waits for it.  It is not a decode call itself: BrotliAmdBatchPackedOutput stays valid, and
+ * BrotliAmdBatchRelaunch and the Last* accessors say what they said before.  A negative value, and a BrotliAmdLastError text, for a NULL batch or
+ * a NULL array, a width that is not 1, 2, 4 or 8 or a misaligned in-place destination (nothing is launched), an object without a decode call, a
+ * last decode call that failed behind its argument checks (one of no streams returns 0), and a launch that BrotliAmdBatchWait has not been
+ * called for. */
+BROTLI_DEC_API int BrotliAmdBatchUndeltaOutputs(BrotliAmdBatch* batch, void* const* d_dst, const uint8_t* widths);
+
+/* Milliseconds the undelta kernels took in the last of the two calls above (HIP events around all its launches together), */
+BROTLI_DEC_API float BrotliAmdBatchLastUndeltaMs(BrotliAmdBatch* batch);
+/* and those of phase 1 (the tiles' sums), 2 (the carries) or 3 (the running sums) alone; another phase: 0. */
+BROTLI_DEC_API float BrotliAmdBatchLastUndeltaPhaseMs(BrotliAmdBatch* batch, uint32_t phase);
+
+/* Test hooks (no device needed).  The bytes of destination memory in one tile of an undelta call; */
+BROTLI_DEC_API uint32_t BrotliAmdDebugUndeltaTile(void);
+/* the tiles whose carries the one block of the carry launch takes in one pass of its loop; */
+BROTLI_DEC_API uint32_t BrotliAmdDebugUndeltaCarrySpan(void);
+/* all three phases by the device's unit and tile functions on the host, over n segments given as offsets into one source buffer src[0, src_size)
+ * and one destination buffer dst[0, dst_size): the buffers are placed at src_skew and dst_skew (0..15) past a 16-byte boundary among bytes that
+ * are not theirs.  tile_units: the 16-byte units of a tile, 0 for the kernel's own.  order_seed != 0: phases 1 and 3 take the tiles in an order
+ * shuffled by it (the result may not depend on it).  in_place != 0: src_size == dst_size, one room is filled from src and every segment's source
+ * is its destination (src_offs is not looked at).  0, and the segments' bytes of dst written (no other byte of dst is); negative, a
+ * BrotliAmdLastError text and an untouched dst for a width that is not 1, 2, 4 or 8, a skew > 15, a segment outside its buffer, in place at an
+ * address that is not a multiple of the width, or a byte changed outside every segment's destination. */
+BROTLI_DEC_API int BrotliAmdDebugUndeltaHost(uint32_t n, const uint8_t* src, size_t src_size, uint8_t* dst, size_t dst_size,
+                                            const uint64_t* src_offs, const uint64_t* dst_offs, const uint64_t* lens, const uint8_t* widths,
+                                            uint32_t src_skew, uint32_t dst_skew, uint32_t tile_units, uint32_t order_seed, int in_place);
+
 /* Milliseconds the last launch spent in the decode kernel (HIP events on the launch stream). */
 BROTLI_DEC_API float BrotliAmdBatchLastKernelMs(BrotliAmdBatch* batch);
 

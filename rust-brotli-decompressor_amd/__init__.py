@@ -40,6 +40,8 @@ BATCH_H_SYMBOLS = [
     "BrotliAmdDebugDigestHost", "BrotliAmdDebugDigestShift",
     "BrotliAmdBatchUnshuffleSegments", "BrotliAmdBatchUnshuffleOutputs", "BrotliAmdBatchLastUnshuffleMs", "BrotliAmdDebugUnshuffleTile",
     "BrotliAmdDebugUnshuffleHost",
+    "BrotliAmdBatchUndeltaSegments", "BrotliAmdBatchUndeltaOutputs", "BrotliAmdBatchLastUndeltaMs", "BrotliAmdBatchLastUndeltaPhaseMs",
+    "BrotliAmdDebugUndeltaTile", "BrotliAmdDebugUndeltaCarrySpan", "BrotliAmdDebugUndeltaHost",
 ]
 
 
@@ -162,6 +164,16 @@ def load_library():
         L.BrotliAmdBatchLastUnshuffleMs.argtypes = [vp]
         L.BrotliAmdDebugUnshuffleTile.restype = u32
         L.BrotliAmdDebugUnshuffleHost.argtypes = [u32, vp, sz, vp, u32, u32]
+    if hasattr(L, "BrotliAmdBatchUndeltaSegments"):   # (undelta: an older build of the library, loaded for an A/B, has none)
+        L.BrotliAmdBatchUndeltaSegments.argtypes = [vp, u32, vp, vp, vp, vp, vp]
+        L.BrotliAmdBatchUndeltaOutputs.argtypes = [vp, vp, vp]
+        L.BrotliAmdBatchLastUndeltaMs.restype = ctypes.c_float
+        L.BrotliAmdBatchLastUndeltaMs.argtypes = [vp]
+        L.BrotliAmdBatchLastUndeltaPhaseMs.restype = ctypes.c_float
+        L.BrotliAmdBatchLastUndeltaPhaseMs.argtypes = [vp, u32]
+        L.BrotliAmdDebugUndeltaTile.restype = u32
+        L.BrotliAmdDebugUndeltaCarrySpan.restype = u32
+        L.BrotliAmdDebugUndeltaHost.argtypes = [u32, vp, sz, vp, sz, vp, vp, vp, vp, u32, u32, u32, u32, ctypes.c_int]
     L.BrotliAmdBatchLastKernelMs.restype = ctypes.c_float
     L.BrotliAmdBatchLastKernelMs.argtypes = [vp]
     L.BrotliAmdBatchLastSecondPassCount.restype = ctypes.c_uint32
@@ -236,6 +248,38 @@ def unshuffle_host(data: bytes, width, src_skew=0, dst_skew=0):
 def unshuffle_tile():
     """BrotliAmdDebugUnshuffleTile: the bytes of destination in one tile of an unshuffle launch"""
     return int(load_library().BrotliAmdDebugUnshuffleTile())
+
+
+def undelta_host(src: bytes, segs, dst_size=None, src_skew=0, dst_skew=0, tile_units=0, order_seed=0, in_place=False, fill=0):
+    """BrotliAmdDebugUndeltaHost: the deltas in `src` back into values by the device's unit and tile functions on the host (no device needed).
+    segs: [(source offset, destination offset, length, width)]; the destination has dst_size bytes (default: as many as the source), all
+    `fill` in front of the call; the buffers are placed at their skews past a 16-byte boundary; tile_units: the 16-byte units of a tile (0: the
+    kernel's); order_seed != 0 shuffles the order in which the tiles are taken; in_place: the segments' sources are their destinations, in one
+    buffer that starts as `src`.  -> the destination's bytes (in place: what no segment covers is `fill`)"""
+    L = load_library()
+    src = bytes(src)
+    dst_size = len(src) if dst_size is None else dst_size
+    n = len(segs)
+    s_buf = ctypes.create_string_buffer(src, max(1, len(src)))
+    d_buf = ctypes.create_string_buffer(bytes([fill]) * dst_size, max(1, dst_size))
+    a_s = (ctypes.c_uint64 * max(1, n))(*[s[0] for s in segs])
+    a_d = (ctypes.c_uint64 * max(1, n))(*[s[1] for s in segs])
+    a_l = (ctypes.c_uint64 * max(1, n))(*[s[2] for s in segs])
+    a_w = (ctypes.c_uint8 * max(1, n))(*[s[3] if 0 <= s[3] <= 255 else 0 for s in segs])
+    if L.BrotliAmdDebugUndeltaHost(n, ctypes.addressof(s_buf), len(src), ctypes.addressof(d_buf), dst_size, a_s, a_d, a_l, a_w, src_skew, dst_skew,
+                                   tile_units, order_seed, 1 if in_place else 0) != 0:
+        raise RuntimeError("BrotliAmdDebugUndeltaHost failed: " + last_error())
+    return d_buf.raw[:dst_size]
+
+
+def undelta_tile():
+    """BrotliAmdDebugUndeltaTile: the bytes of destination in one tile of an undelta call"""
+    return int(load_library().BrotliAmdDebugUndeltaTile())
+
+
+def undelta_carry_span():
+    """BrotliAmdDebugUndeltaCarrySpan: the tiles the carry launch's one block takes in one pass of its loop"""
+    return int(load_library().BrotliAmdDebugUndeltaCarrySpan())
 
 
 # ------------------------------------------------------------------ batch (include/brotli/batch.h)
@@ -478,6 +522,38 @@ class Batch:
     def last_unshuffle_ms(self):
         """milliseconds the unshuffle kernel took in the last unshuffle_segments / unshuffle_outputs"""
         return float(self._L.BrotliAmdBatchLastUnshuffleMs(self._h))
+
+    def undelta_segments(self, src_ptrs, dst_ptrs, lens, widths, stream=None):
+        """BrotliAmdBatchUndeltaSegments: lens[i] bytes of deltas at the device address src_ptrs[i] become the running sums of their elements of
+        widths[i] bytes (1, 2, 4, 8; little-endian, wrapping) at dst_ptrs[i]; any alignment, any length; out of place, or in place
+        (dst_ptrs[i] == src_ptrs[i]) at a multiple of the width.  Three launches and a wait on `stream`."""
+        n = len(src_ptrs)
+        if len(dst_ptrs) != n or len(lens) != n or len(widths) != n:
+            raise ValueError("src_ptrs, dst_ptrs, lens and widths: one entry per segment each")
+        a_s = (ctypes.c_void_p * max(1, n))(*src_ptrs)
+        a_d = (ctypes.c_void_p * max(1, n))(*dst_ptrs)
+        a_l = (ctypes.c_size_t * max(1, n))(*lens)
+        a_w = (ctypes.c_uint8 * max(1, n))(*[w if 0 <= w <= 255 else 0 for w in widths])
+        if self._L.BrotliAmdBatchUndeltaSegments(self._h, n, a_s, a_d, a_l, a_w, stream) != 0:
+            raise RuntimeError("BrotliAmdBatchUndeltaSegments failed: " + last_error())
+
+    def undelta_outputs(self, dst_ptrs, widths):
+        """BrotliAmdBatchUndeltaOutputs: the delivered bytes of every stream of the last decode call on this object (after decode_device: once
+        wait() has returned), taken as deltas of widths[i], become values at the device address dst_ptrs[i] (None or 0: the stream is skipped).
+        Three launches on that call's stream, and a wait."""
+        n = self.out_n
+        if len(dst_ptrs) != n or len(widths) != n:
+            raise ValueError("dst_ptrs and widths: one entry per stream of the last decode call each")
+        a_d = (ctypes.c_void_p * max(1, n))(*[p or None for p in dst_ptrs])
+        a_w = (ctypes.c_uint8 * max(1, n))(*[w if 0 <= w <= 255 else 0 for w in widths])
+        if self._L.BrotliAmdBatchUndeltaOutputs(self._h, a_d, a_w) != 0:
+            raise RuntimeError("BrotliAmdBatchUndeltaOutputs failed: " + last_error())
+
+    def last_undelta_ms(self, phase=None):
+        """milliseconds the undelta kernels took in the last undelta_segments / undelta_outputs: all launches together, or phase 1, 2 or 3"""
+        if phase is None:
+            return float(self._L.BrotliAmdBatchLastUndeltaMs(self._h))
+        return float(self._L.BrotliAmdBatchLastUndeltaPhaseMs(self._h, phase))
 
     def decode_host_raw(self, in_ptrs, in_sizes, out_ptrs, out_caps, flags=FLAG_LARGE_WINDOW):
         """BrotliAmdBatchDecodeHost on buffers the caller owns (host addresses as integers): nothing is copied on the Python side"""

@@ -124,6 +124,10 @@ typedef struct BrotliAmdUnshuffleSeg {
 } BrotliAmdUnshuffleSeg;
 #define BROTLI_AMD_UNSHUFFLE_TILE_BYTES 16384u  // destination bytes of one tile
 
+// An undelta call (csrc/brotli_undelta_kernels.hip, csrc/brotli_undelta.h) takes the segments of an unshuffle launch -- here len bytes of deltas
+// at src become len bytes of values at dst; dst == src is allowed at a multiple of width -- and cuts their destination into tiles of
+#define BROTLI_AMD_UNDELTA_TILE_BYTES 16384u  // destination bytes: a tile's carry-in comes from the tiles in front of it
+
 #ifdef __cplusplus
 }
 #endif

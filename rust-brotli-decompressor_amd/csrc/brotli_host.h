@@ -5,6 +5,7 @@
 //   brotli_stream_set.cpp  many streaming states in one launch, the ragged copy's debug hook
 //   brotli_digest.cpp   CRC-32 / CRC-32C of segments of device memory and of the last decode call's outputs
 //   brotli_unshuffle.cpp  byte planes of segments of device memory, and of the last decode call's outputs, back into elements
+//   brotli_undelta.cpp  deltas of segments of device memory, and of the last decode call's outputs, back into values
 #ifndef BROTLI_AMD_HOST_H_
 #define BROTLI_AMD_HOST_H_
 #include <hip/hip_runtime.h>
@@ -169,6 +170,10 @@ struct BrotliAmdBatch {
   brotli_amd_host::DevBuf<> d_unshuffle;   // the segment table of one launch
   hipEvent_t ev_unshuffle0 = nullptr, ev_unshuffle1 = nullptr;   // around the unshuffle launch (made at the first)
   float unshuffle_ms = 0.0f;
+  // undelta (brotli_undelta.cpp)
+  brotli_amd_host::DevBuf<> d_undelta;   // the segment table of one call, and the summaries and carries of its tiles
+  hipEvent_t ev_undelta[4] = {nullptr, nullptr, nullptr, nullptr};   // around and between the three launches (made at the first call)
+  float undelta_ms = 0.0f, undelta_phase_ms[3] = {0.0f, 0.0f, 0.0f};
 };
 
 namespace brotli_amd_host {

@@ -205,6 +205,24 @@ extern "C" {
     /// test hooks (no device needed)
     pub fn BrotliAmdDebugUnshuffleTile() -> u32;
     pub fn BrotliAmdDebugUnshuffleHost(width: u32, src: *const u8, len: size_t, dst: *mut u8, src_skew: u32, dst_skew: u32) -> c_int;
+    /// deltas back into values, a wrapping running sum of little-endian elements per segment: `n` segments of DEVICE memory (any alignment, any
+    /// length), `widths[i]` of 1, 2, 4 or 8, out of place or in place at a multiple of the width, in three launches on `hip_stream`; waits
+    pub fn BrotliAmdBatchUndeltaSegments(
+        batch: *mut BrotliAmdBatch, n: u32, d_src: *const *const c_void, d_dst: *const *mut c_void, lens: *const size_t, widths: *const u8,
+        hip_stream: *mut c_void,
+    ) -> c_int;
+    /// the same for the delivered bytes of every stream of the last decode call on the object (after `BrotliAmdBatchWait` for a device call);
+    /// a NULL `d_dst[i]` skips stream i
+    pub fn BrotliAmdBatchUndeltaOutputs(batch: *mut BrotliAmdBatch, d_dst: *const *mut c_void, widths: *const u8) -> c_int;
+    pub fn BrotliAmdBatchLastUndeltaMs(batch: *mut BrotliAmdBatch) -> f32;
+    pub fn BrotliAmdBatchLastUndeltaPhaseMs(batch: *mut BrotliAmdBatch, phase: u32) -> f32;
+    /// test hooks (no device needed)
+    pub fn BrotliAmdDebugUndeltaTile() -> u32;
+    pub fn BrotliAmdDebugUndeltaCarrySpan() -> u32;
+    pub fn BrotliAmdDebugUndeltaHost(
+        n: u32, src: *const u8, src_size: size_t, dst: *mut u8, dst_size: size_t, src_offs: *const u64, dst_offs: *const u64, lens: *const u64,
+        widths: *const u8, src_skew: u32, dst_skew: u32, tile_units: u32, order_seed: u32, in_place: c_int,
+    ) -> c_int;
     pub fn BrotliAmdLastError() -> *const c_char;
     pub fn BrotliAmdLastNote() -> *const c_char;
 }
