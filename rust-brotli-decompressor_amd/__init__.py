@@ -174,6 +174,9 @@ def load_library():
         L.BrotliAmdDebugUndeltaTile.restype = u32
         L.BrotliAmdDebugUndeltaCarrySpan.restype = u32
         L.BrotliAmdDebugUndeltaHost.argtypes = [u32, vp, sz, vp, sz, vp, vp, vp, vp, u32, u32, u32, u32, ctypes.c_int]
+    if hasattr(L, "BrotliAmdDebugSegWalkParts"):   # (the segment walk's host model: an older build of the library, loaded for an A/B, has none)
+        L.BrotliAmdDebugSegWalkParts.restype = ctypes.c_uint64
+        L.BrotliAmdDebugSegWalkParts.argtypes = [u32, vp, u32, u32, vp, ctypes.c_uint64]
     L.BrotliAmdBatchLastKernelMs.restype = ctypes.c_float
     L.BrotliAmdBatchLastKernelMs.argtypes = [vp]
     L.BrotliAmdBatchLastSecondPassCount.restype = ctypes.c_uint32
@@ -280,6 +283,19 @@ def undelta_tile():
 def undelta_carry_span():
     """BrotliAmdDebugUndeltaCarrySpan: the tiles the carry launch's one block takes in one pass of its loop"""
     return int(load_library().BrotliAmdDebugUndeltaCarrySpan())
+
+
+def seg_walk_parts(units, tile_units, grid):
+    """BrotliAmdDebugSegWalkParts: the segment walk of csrc/brotli_seg_walk.h on the host (no device needed) over segments of units[i] 16-byte
+    units each, with tiles of tile_units and `grid` blocks -> [(block, tile, lo, hi)], every part of every block's tiles, block by block"""
+    L = load_library()
+    n = len(units)
+    a_u = (ctypes.c_uint64 * max(1, n))(*units)
+    count = int(L.BrotliAmdDebugSegWalkParts(n, a_u, tile_units, grid, None, 0))
+    out = (ctypes.c_uint64 * max(1, 4 * count))()
+    if int(L.BrotliAmdDebugSegWalkParts(n, a_u, tile_units, grid, out, count)) != count:
+        raise RuntimeError("BrotliAmdDebugSegWalkParts: two runs disagree")
+    return [tuple(out[4 * k:4 * k + 4]) for k in range(count)]
 
 
 # ------------------------------------------------------------------ batch (include/brotli/batch.h)
@@ -494,9 +510,8 @@ class Batch:
         """milliseconds the digest kernel took in the last digest_segments / digest_outputs"""
         return float(self._L.BrotliAmdBatchLastDigestMs(self._h))
 
-    def unshuffle_segments(self, src_ptrs, dst_ptrs, lens, widths, stream=None):
-        """BrotliAmdBatchUnshuffleSegments: lens[i] bytes of byte planes at the device address src_ptrs[i] become elements of widths[i] bytes
-        (1, 2, 4, 8) at dst_ptrs[i]; any alignment, any length; out of place.  One launch and a wait on `stream`."""
+    def _width_segments(self, name, src_ptrs, dst_ptrs, lens, widths, stream):
+        """BrotliAmdBatch<name>Segments over the caller's segments"""
         n = len(src_ptrs)
         if len(dst_ptrs) != n or len(lens) != n or len(widths) != n:
             raise ValueError("src_ptrs, dst_ptrs, lens and widths: one entry per segment each")
@@ -504,20 +519,29 @@ class Batch:
         a_d = (ctypes.c_void_p * max(1, n))(*dst_ptrs)
         a_l = (ctypes.c_size_t * max(1, n))(*lens)
         a_w = (ctypes.c_uint8 * max(1, n))(*[w if 0 <= w <= 255 else 0 for w in widths])
-        if self._L.BrotliAmdBatchUnshuffleSegments(self._h, n, a_s, a_d, a_l, a_w, stream) != 0:
-            raise RuntimeError("BrotliAmdBatchUnshuffleSegments failed: " + last_error())
+        if getattr(self._L, name)(self._h, n, a_s, a_d, a_l, a_w, stream) != 0:
+            raise RuntimeError(name + " failed: " + last_error())
 
-    def unshuffle_outputs(self, dst_ptrs, widths):
-        """BrotliAmdBatchUnshuffleOutputs: the delivered bytes of every stream of the last decode call on this object (after decode_device:
-        once wait() has returned), taken as byte planes of widths[i], become elements at the device address dst_ptrs[i] (None or 0: the stream
-        is skipped).  One launch on that call's stream, and a wait."""
+    def _width_outputs(self, name, dst_ptrs, widths):
+        """BrotliAmdBatch<name>Outputs over the streams of the last decode call"""
         n = self.out_n
         if len(dst_ptrs) != n or len(widths) != n:
             raise ValueError("dst_ptrs and widths: one entry per stream of the last decode call each")
         a_d = (ctypes.c_void_p * max(1, n))(*[p or None for p in dst_ptrs])
         a_w = (ctypes.c_uint8 * max(1, n))(*[w if 0 <= w <= 255 else 0 for w in widths])
-        if self._L.BrotliAmdBatchUnshuffleOutputs(self._h, a_d, a_w) != 0:
-            raise RuntimeError("BrotliAmdBatchUnshuffleOutputs failed: " + last_error())
+        if getattr(self._L, name)(self._h, a_d, a_w) != 0:
+            raise RuntimeError(name + " failed: " + last_error())
+
+    def unshuffle_segments(self, src_ptrs, dst_ptrs, lens, widths, stream=None):
+        """BrotliAmdBatchUnshuffleSegments: lens[i] bytes of byte planes at the device address src_ptrs[i] become elements of widths[i] bytes
+        (1, 2, 4, 8) at dst_ptrs[i]; any alignment, any length; out of place.  One launch and a wait on `stream`."""
+        self._width_segments("BrotliAmdBatchUnshuffleSegments", src_ptrs, dst_ptrs, lens, widths, stream)
+
+    def unshuffle_outputs(self, dst_ptrs, widths):
+        """BrotliAmdBatchUnshuffleOutputs: the delivered bytes of every stream of the last decode call on this object (after decode_device:
+        once wait() has returned), taken as byte planes of widths[i], become elements at the device address dst_ptrs[i] (None or 0: the stream
+        is skipped).  One launch on that call's stream, and a wait."""
+        self._width_outputs("BrotliAmdBatchUnshuffleOutputs", dst_ptrs, widths)
 
     def last_unshuffle_ms(self):
         """milliseconds the unshuffle kernel took in the last unshuffle_segments / unshuffle_outputs"""
@@ -527,27 +551,13 @@ class Batch:
         """BrotliAmdBatchUndeltaSegments: lens[i] bytes of deltas at the device address src_ptrs[i] become the running sums of their elements of
         widths[i] bytes (1, 2, 4, 8; little-endian, wrapping) at dst_ptrs[i]; any alignment, any length; out of place, or in place
         (dst_ptrs[i] == src_ptrs[i]) at a multiple of the width.  Three launches and a wait on `stream`."""
-        n = len(src_ptrs)
-        if len(dst_ptrs) != n or len(lens) != n or len(widths) != n:
-            raise ValueError("src_ptrs, dst_ptrs, lens and widths: one entry per segment each")
-        a_s = (ctypes.c_void_p * max(1, n))(*src_ptrs)
-        a_d = (ctypes.c_void_p * max(1, n))(*dst_ptrs)
-        a_l = (ctypes.c_size_t * max(1, n))(*lens)
-        a_w = (ctypes.c_uint8 * max(1, n))(*[w if 0 <= w <= 255 else 0 for w in widths])
-        if self._L.BrotliAmdBatchUndeltaSegments(self._h, n, a_s, a_d, a_l, a_w, stream) != 0:
-            raise RuntimeError("BrotliAmdBatchUndeltaSegments failed: " + last_error())
+        self._width_segments("BrotliAmdBatchUndeltaSegments", src_ptrs, dst_ptrs, lens, widths, stream)
 
     def undelta_outputs(self, dst_ptrs, widths):
         """BrotliAmdBatchUndeltaOutputs: the delivered bytes of every stream of the last decode call on this object (after decode_device: once
         wait() has returned), taken as deltas of widths[i], become values at the device address dst_ptrs[i] (None or 0: the stream is skipped).
         Three launches on that call's stream, and a wait."""
-        n = self.out_n
-        if len(dst_ptrs) != n or len(widths) != n:
-            raise ValueError("dst_ptrs and widths: one entry per stream of the last decode call each")
-        a_d = (ctypes.c_void_p * max(1, n))(*[p or None for p in dst_ptrs])
-        a_w = (ctypes.c_uint8 * max(1, n))(*[w if 0 <= w <= 255 else 0 for w in widths])
-        if self._L.BrotliAmdBatchUndeltaOutputs(self._h, a_d, a_w) != 0:
-            raise RuntimeError("BrotliAmdBatchUndeltaOutputs failed: " + last_error())
+        self._width_outputs("BrotliAmdBatchUndeltaOutputs", dst_ptrs, widths)
 
     def last_undelta_ms(self, phase=None):
         """milliseconds the undelta kernels took in the last undelta_segments / undelta_outputs: all launches together, or phase 1, 2 or 3"""

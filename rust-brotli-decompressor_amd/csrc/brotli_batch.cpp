@@ -424,8 +424,9 @@ extern "C" void BrotliAmdBatchDestroy(BrotliAmdBatch* b) {
   if (b->launched && b->last_stream != nullptr) (void)hipStreamSynchronize(b->last_stream);
   else (void)hipDeviceSynchronize();
   if (b->copy_stream) (void)hipStreamDestroy(b->copy_stream);
-  for (hipEvent_t ev : {b->ev0, b->ev1, b->ev2, b->ev3, b->ev_digest0, b->ev_digest1, b->ev_unshuffle0, b->ev_unshuffle1, b->ev_undelta[0], b->ev_undelta[1], b->ev_undelta[2],
-                        b->ev_undelta[3]}) if (ev) (void)hipEventDestroy(ev);
+  for (hipEvent_t ev : {b->ev0, b->ev1, b->ev2, b->ev3}) if (ev) (void)hipEventDestroy(ev);
+  for (SegCall* c : {&b->digest, &b->unshuffle, &b->undelta})
+    for (hipEvent_t ev : c->ev) if (ev) (void)hipEventDestroy(ev);
   delete b;
 }
 

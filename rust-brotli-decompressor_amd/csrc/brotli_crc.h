@@ -20,6 +20,8 @@
 
 #include <stdint.h>
 
+#include "brotli_seg_walk.h"   // a segment's units
+
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define BROTLI_AMD_CRC_HD __host__ __device__ inline __attribute__((always_inline))
 #else
@@ -105,10 +107,8 @@ BROTLI_AMD_CRC_HD uint32_t brotli_amd_crc_unit(const uint32_t* t, uint32_t reg, 
   return reg;
 }
 
-// A segment's UNITS are the 16-byte-aligned words of memory that [src, src + len) touches (addresses as integers); unit k is the word at
+// A segment's UNITS (csrc/brotli_seg_walk.h) are the 16-byte-aligned words of memory that [src, src + len) touches; unit k is the word at
 // (src & ~15) + 16 k.
-BROTLI_AMD_CRC_HD uint64_t brotli_amd_crc_seg_units(uint64_t src, uint64_t len) { return len ? ((src + len + 15u) >> 4) - (src >> 4) : 0u; }
-
 // One PIECE: units [u0, u1) of the segment (u0 < u1 <= its units), each fetched as ONE aligned 16-byte word by load(address, w) -> w[0..4).
 // -> the piece's raw register (started with the init value where the piece holds the segment's first byte), and in *behind the segment's bytes
 // behind the piece.

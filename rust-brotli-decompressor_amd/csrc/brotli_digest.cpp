@@ -22,45 +22,21 @@ bool known_kind(uint32_t kind) {
 
 // the digests of segs[0..n) on `stream`, waited for: digests[0..n) on the host (the object's device is current)
 int digest_device(BrotliAmdBatch* b, uint32_t kind, const std::vector<BrotliAmdCrcSeg>& segs, uint32_t* digests, hipStream_t stream) {
-  const size_t n = segs.size(), table_bytes = sizeof(BrotliAmdCrcSeg) * n, out_bytes = sizeof(uint32_t) * n;
-  b->digest_ms = 0.0f;
-  if (!b->d_digest.reserve(table_bytes + out_bytes, "hipMalloc(digests)")) return -1;
-  if (!b->ev_digest0 && !(hip_ok(hipEventCreate(&b->ev_digest0), "hipEventCreate") && hip_ok(hipEventCreate(&b->ev_digest1), "hipEventCreate"))) return -1;
-  BrotliAmdCrcSeg* d_segs = reinterpret_cast<BrotliAmdCrcSeg*>(b->d_digest.get());
-  uint32_t* d_out = reinterpret_cast<uint32_t*>(b->d_digest + table_bytes);
+  const uint32_t n = (uint32_t)segs.size();
+  const size_t out_bytes = sizeof(uint32_t) * n;
   uint64_t units = 0;
-  for (const BrotliAmdCrcSeg& s : segs) units += brotli_amd_crc_seg_units((uint64_t)(uintptr_t)s.ptr, s.len);
-  bool ok = hip_ok(hipMemcpyAsync(d_segs, segs.data(), table_bytes, hipMemcpyHostToDevice, stream), "hipMemcpyAsync(digest segments)");
-  ok = ok && hip_ok(hipMemsetAsync(d_out, 0, out_bytes, stream), "hipMemsetAsync(digests)");
-  ok = ok && hip_ok(hipEventRecord(b->ev_digest0, stream), "hipEventRecord");
-  ok = ok && hip_ok(brotli_amd_launch_crc(d_segs, (uint32_t)n, kind, units, d_out, stream), "brotli_amd_crc_kernel launch");
-  ok = ok && hip_ok(hipEventRecord(b->ev_digest1, stream), "hipEventRecord");
-  ok = ok && hip_ok(hipMemcpyAsync(digests, d_out, out_bytes, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(digests)");
-  // (waited for in any case: the copies read and write the caller's and this function's pageable memory)
-  if (!hip_ok(hipStreamSynchronize(stream), "hipStreamSynchronize(digests)") || !ok) return -1;
-  (void)hipEventElapsedTime(&b->digest_ms, b->ev_digest0, b->ev_digest1);
-  return 0;
+  for (const BrotliAmdCrcSeg& s : segs) units += brotli_amd_seg_units((uint64_t)(uintptr_t)s.ptr, s.len);
+  // behind the table: the n digests, zeroed in front of the launch and brought back behind it
+  return run_seg_call(&b->digest, {"hipMalloc(digests)", "hipMemcpyAsync(digest segments)", "hipStreamSynchronize(digests)"}, segs.data(),
+                      sizeof(BrotliAmdCrcSeg) * n, out_bytes, 2u, stream, [&](uint8_t* d_segs, uint8_t* d_out, const hipEvent_t* ev) {
+    return hip_ok(hipMemsetAsync(d_out, 0, out_bytes, stream), "hipMemsetAsync(digests)") && hip_ok(hipEventRecord(ev[0], stream), "hipEventRecord") &&
+           hip_ok(brotli_amd_launch_crc(reinterpret_cast<BrotliAmdCrcSeg*>(d_segs), n, kind, units, reinterpret_cast<uint32_t*>(d_out), stream), "brotli_amd_crc_kernel launch") &&
+           hip_ok(hipEventRecord(ev[1], stream), "hipEventRecord") &&
+           hip_ok(hipMemcpyAsync(digests, d_out, out_bytes, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(digests)");
+  }, &b->digest_ms);
 }
 
 }  // namespace
-
-// The delivered bytes of every stream of the last decode call (brotli_host.h)
-bool brotli_amd_host::delivered_outputs(BrotliAmdBatch* b, std::vector<DeliveredBytes>* outs) {
-  outs->clear();
-  if (b->packed_valid) {   // a packed call: its buffer and offsets
-    for (size_t i = 0; i + 1 < b->packed_offsets.size(); i++)
-      outs->push_back(DeliveredBytes{b->packed_out + b->packed_offsets[i], b->packed_offsets[i + 1] - b->packed_offsets[i]});
-    return true;
-  }
-  if (b->outputs == BrotliAmdBatch::Outputs::NoCall) { g_last_error = "no decode call on this batch object yet"; return false; }
-  if (b->outputs == BrotliAmdBatch::Outputs::Failed) { g_last_error = "the last decode call on this batch object failed: it has no outputs"; return false; }
-  if (b->outputs == BrotliAmdBatch::Outputs::InFlight) { g_last_error = "the last launch has not been waited for (BrotliAmdBatchWait)"; return false; }
-  // the streams' own buffers (the staging arena's slots after a host call), as far as each was delivered
-  if (b->outputs == BrotliAmdBatch::Outputs::Waited)
-    for (uint32_t i = 0; i < b->n; i++)
-      outs->push_back(DeliveredBytes{b->h_descs[i].out, std::min<uint64_t>(b->h_status[i].decoded_size, b->h_descs[i].out_cap)});
-  return true;
-}
 
 extern "C" int BrotliAmdBatchDigestSegments(BrotliAmdBatch* b, uint32_t kind, uint32_t n, const void* const* d_ptrs, const size_t* lens,
                                             uint32_t* digests, void* hip_stream) {
@@ -109,7 +85,7 @@ extern "C" uint32_t BrotliAmdDebugDigestHost(uint32_t kind, const uint8_t* data,
   const uint32_t poly = brotli_amd_crc_poly(kind);
   const BrotliAmdCrcConsts& c = kConsts[kind - 1u];
   const auto load = [](uint64_t W, uint32_t* w) { std::memcpy(w, reinterpret_cast<const void*>((uintptr_t)W), 16); };
-  const uint64_t units = brotli_amd_crc_seg_units(at, n);
+  const uint64_t units = brotli_amd_seg_units(at, n);
   uint32_t digest = 0;
   for (uint64_t u0 = 0; u0 < units; u0 += run_units) {
     uint64_t behind = 0;

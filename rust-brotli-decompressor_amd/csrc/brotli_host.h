@@ -3,6 +3,7 @@
 //   brotli_staging.cpp  host buffers through staging arenas, size hints, the packed decode
 //   brotli_capi.cpp     the reference's C ABI (include/brotli/decode.h): error strings, one-shot, Prealloc, the streaming state
 //   brotli_stream_set.cpp  many streaming states in one launch, the ragged copy's debug hook
+//   brotli_seg_call.cpp  what the three calls below share: a call over a table of segments, the last decode call's outputs as segments
 //   brotli_digest.cpp   CRC-32 / CRC-32C of segments of device memory and of the last decode call's outputs
 //   brotli_unshuffle.cpp  byte planes of segments of device memory, and of the last decode call's outputs, back into elements
 //   brotli_undelta.cpp  deltas of segments of device memory, and of the last decode call's outputs, back into values
@@ -104,6 +105,12 @@ class Buffer {
 template <class T = uint8_t> using DevBuf = Buffer<T, Mem::Device>;
 template <class T = uint8_t> using PinBuf = Buffer<T, Mem::Pinned>;
 
+// What a call over a table of segments (run_seg_call) keeps with its batch object
+struct SegCall {
+  DevBuf<> d;                                                // the segment table of one call and what the call wants behind it
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // around and between its launches (made at the first call, as many as it needs)
+};
+
 constexpr size_t kReaderSlack = 256;   // behind every buffer the kernel reads a stream's bytes from, or writes them to, up to the buffer's end
 
 }  // namespace brotli_amd_host
@@ -163,16 +170,13 @@ struct BrotliAmdBatch {
   // that has begun and launched nothing -- where it stays so, it failed --; a call of no streams; a launch nobody has waited for; h_descs and
   // h_status of the launch waited for
   enum class Outputs : uint8_t { NoCall, Failed, None, InFlight, Waited } outputs = Outputs::NoCall;
-  brotli_amd_host::DevBuf<> d_digest;   // the segment table and the digests of one launch
-  hipEvent_t ev_digest0 = nullptr, ev_digest1 = nullptr;   // around the digest launch (made at the first)
+  brotli_amd_host::SegCall digest;   // behind the table: the digests of one launch
   float digest_ms = 0.0f;
   // unshuffle (brotli_unshuffle.cpp)
-  brotli_amd_host::DevBuf<> d_unshuffle;   // the segment table of one launch
-  hipEvent_t ev_unshuffle0 = nullptr, ev_unshuffle1 = nullptr;   // around the unshuffle launch (made at the first)
+  brotli_amd_host::SegCall unshuffle;
   float unshuffle_ms = 0.0f;
   // undelta (brotli_undelta.cpp)
-  brotli_amd_host::DevBuf<> d_undelta;   // the segment table of one call, and the summaries and carries of its tiles
-  hipEvent_t ev_undelta[4] = {nullptr, nullptr, nullptr, nullptr};   // around and between the three launches (made at the first call)
+  brotli_amd_host::SegCall undelta;   // behind the table: the summaries and carries of its tiles
   float undelta_ms = 0.0f, undelta_phase_ms[3] = {0.0f, 0.0f, 0.0f};
 };
 
@@ -223,11 +227,41 @@ int submit(BrotliAmdBatch* b, uint32_t n, hipStream_t stream);
 bool decode_descs(BrotliAmdBatch* b, uint32_t n, hipStream_t stream, bool exact_limit);
 constexpr bool kExactLimitDefault = false;   // what a batch object's exact_limit is until a batch entry point says otherwise: the one-shot and streaming paths' value
 // The DELIVERED bytes -- [out, out + decoded_size) -- of every stream of the last decode call on the object, where BrotliAmdBatchDigestOutputs and
-// BrotliAmdBatchUnshuffleOutputs find them (batch.h says where; brotli_digest.cpp).  False, and g_last_error: no decode call yet, one that failed, a
+// BrotliAmdBatchUnshuffleOutputs find them (batch.h says where; brotli_seg_call.cpp).  False, and g_last_error: no decode call yet, one that failed, a
 // launch nobody has waited for.  A call of no streams: true and none.
 struct DeliveredBytes { const uint8_t* ptr; uint64_t len; };
 bool delivered_outputs(BrotliAmdBatch* b, std::vector<DeliveredBytes>* outs);
 void drop_packed(BrotliAmdBatch* b);   // a decode call ends the validity of the last packed call's output
+
+// ---- calls over a table of segments (brotli_seg_call.cpp): digests, unshuffle, undelta ----
+struct SegCallWhat { const char* alloc; const char* upload; const char* wait; };   // what hip_ok says of a failed step
+// One call on `stream` (the object's device is current): room in c->d for the table, rounded up to 16 bytes, and `extra` bytes behind it; its
+// first nev events; the table's upload; then launch(uint8_t* table, uint8_t* what lies behind it, const hipEvent_t* events) -> all of it was queued.  The stream is waited
+// for IN ANY CASE: the upload reads pageable memory.  On success *total_ms is the time from the first event to the last and, where gap_ms is
+// given, gap_ms[i] that from event i to event i + 1.  -> 0, or -1 and g_last_error.
+template <class Launch>
+int run_seg_call(SegCall* c, const SegCallWhat& what, const void* table, size_t table_bytes, size_t extra, uint32_t nev, hipStream_t stream,
+                 Launch launch, float* total_ms, float* gap_ms = nullptr) {
+  const size_t room = (table_bytes + 15u) & ~(size_t)15;
+  if (!c->d.reserve(room + extra, what.alloc)) return -1;
+  for (uint32_t i = 0; i < nev; i++)
+    if (!c->ev[i] && !hip_ok(hipEventCreate(&c->ev[i]), "hipEventCreate")) return -1;
+  bool ok = hip_ok(hipMemcpyAsync(c->d.get(), table, table_bytes, hipMemcpyHostToDevice, stream), what.upload);
+  ok = ok && launch(c->d.get(), c->d.get() + room, c->ev);
+  // (waited for in any case: the copies read and write the caller's pageable memory)
+  if (!hip_ok(hipStreamSynchronize(stream), what.wait) || !ok) return -1;
+  (void)hipEventElapsedTime(total_ms, c->ev[0], c->ev[nev - 1u]);
+  for (uint32_t i = 0; gap_ms && i + 1u < nev; i++) (void)hipEventElapsedTime(&gap_ms[i], c->ev[i], c->ev[i + 1u]);
+  return 0;
+}
+// The segments of an unshuffle or an undelta call, each checked by ok(source, destination, width) -- false: g_last_error says why -- in front of
+// everything that touches the device: from the caller's arrays, and from the delivered bytes of the last decode call's streams, where a NULL
+// destination skips the stream and its width is not looked at.
+typedef bool (*SegCheck)(const void* src, const void* dst, uint32_t width);
+bool width_segments(uint32_t n, const void* const* d_src, void* const* d_dst, const size_t* lens, const uint8_t* widths, SegCheck ok,
+                    std::vector<BrotliAmdUnshuffleSeg>* segs);
+bool width_segments_of_outputs(BrotliAmdBatch* b, void* const* d_dst, const uint8_t* widths, SegCheck ok, std::vector<BrotliAmdUnshuffleSeg>* segs);
+uint64_t width_segments_units(const std::vector<BrotliAmdUnshuffleSeg>& segs);   // the units of their destinations together (brotli_seg_walk.h)
 
 }  // namespace brotli_amd_host
 #endif  // BROTLI_AMD_HOST_H_

@@ -30,27 +30,23 @@ bool placed_ok(uint64_t src, uint64_t dst, uint32_t width) {
   return false;
 }
 
+bool seg_ok(const void* src, const void* dst, uint32_t width) { return known_width(width) && placed_ok((uint64_t)(uintptr_t)src, (uint64_t)(uintptr_t)dst, width); }
+
 void no_times(BrotliAmdBatch* b) { b->undelta_ms = 0.0f; for (float& ms : b->undelta_phase_ms) ms = 0.0f; }
 
-// segs[0..n) on `stream`, waited for (the object's device is current; the widths and the placement were checked)
+// segs on `stream`, waited for (the widths and the placement were checked)
 int undelta_device(BrotliAmdBatch* b, const std::vector<BrotliAmdUnshuffleSeg>& segs, hipStream_t stream) {
-  const size_t table_bytes = (sizeof(BrotliAmdUnshuffleSeg) * segs.size() + 15u) & ~(size_t)15;
-  uint64_t units = 0;
-  for (const BrotliAmdUnshuffleSeg& s : segs) units += brotli_amd_unshuffle_seg_units((uint64_t)(uintptr_t)s.dst, s.len);
+  if (segs.empty()) return 0;
+  DeviceGuard guard;
+  if (!hip_ok(hipSetDevice(b->device), "hipSetDevice")) return -1;
+  const uint32_t n = (uint32_t)segs.size();
+  const uint64_t units = width_segments_units(segs);
   if (units == 0u) return 0;   // (segments without bytes: nothing to launch)
-  // the segment table, and behind it the tiles' summaries and carries: it grows with the launch
-  if (!b->d_undelta.reserve(table_bytes + brotli_amd_undelta_scratch_bytes(units), "hipMalloc(undelta segments and tiles)")) return -1;
-  for (hipEvent_t& ev : b->ev_undelta)
-    if (!ev && !hip_ok(hipEventCreate(&ev), "hipEventCreate")) return -1;
-  uint8_t* d = reinterpret_cast<uint8_t*>(b->d_undelta.get());
-  BrotliAmdUnshuffleSeg* d_segs = reinterpret_cast<BrotliAmdUnshuffleSeg*>(d);
-  bool ok = hip_ok(hipMemcpyAsync(d_segs, segs.data(), sizeof(BrotliAmdUnshuffleSeg) * segs.size(), hipMemcpyHostToDevice, stream), "hipMemcpyAsync(undelta segments)");
-  ok = ok && hip_ok(brotli_amd_launch_undelta(d_segs, (uint32_t)segs.size(), units, d + table_bytes, stream, b->ev_undelta), "brotli_amd_undelta kernels launch");
-  // (waited for in any case: the copy reads this function's pageable memory)
-  if (!hip_ok(hipStreamSynchronize(stream), "hipStreamSynchronize(undelta)") || !ok) return -1;
-  (void)hipEventElapsedTime(&b->undelta_ms, b->ev_undelta[0], b->ev_undelta[3]);
-  for (int p = 0; p < 3; p++) (void)hipEventElapsedTime(&b->undelta_phase_ms[p], b->ev_undelta[p], b->ev_undelta[p + 1]);
-  return 0;
+  // behind the table: the tiles' summaries and carries -- it grows with the launch
+  return run_seg_call(&b->undelta, {"hipMalloc(undelta segments and tiles)", "hipMemcpyAsync(undelta segments)", "hipStreamSynchronize(undelta)"}, segs.data(),
+                      sizeof(BrotliAmdUnshuffleSeg) * n, brotli_amd_undelta_scratch_bytes(units), 4u, stream, [&](uint8_t* d_segs, uint8_t* d_scratch, const hipEvent_t* ev) {
+    return hip_ok(brotli_amd_launch_undelta(reinterpret_cast<BrotliAmdUnshuffleSeg*>(d_segs), n, units, d_scratch, stream, ev), "brotli_amd_undelta kernels launch");
+  }, &b->undelta_ms, b->undelta_phase_ms);
 }
 
 }  // namespace
@@ -59,31 +55,16 @@ extern "C" int BrotliAmdBatchUndeltaSegments(BrotliAmdBatch* b, uint32_t n, cons
                                              const uint8_t* widths, void* hip_stream) {
   if (!b || (n && (!d_src || !d_dst || !lens || !widths))) { g_last_error = "invalid undelta arguments"; return -1; }
   no_times(b);
-  if (n == 0) return 0;
-  for (uint32_t i = 0; i < n; i++)   // (in front of everything that touches the device)
-    if (!known_width(widths[i]) || !placed_ok((uint64_t)(uintptr_t)d_src[i], (uint64_t)(uintptr_t)d_dst[i], widths[i])) return -1;
-  std::vector<BrotliAmdUnshuffleSeg> segs(n);
-  for (uint32_t i = 0; i < n; i++)
-    segs[i] = BrotliAmdUnshuffleSeg{static_cast<const uint8_t*>(d_src[i]), static_cast<uint8_t*>(d_dst[i]), lens[i], widths[i], 0u};
-  DeviceGuard guard;
-  if (!hip_ok(hipSetDevice(b->device), "hipSetDevice")) return -1;
+  std::vector<BrotliAmdUnshuffleSeg> segs;
+  if (!width_segments(n, d_src, d_dst, lens, widths, seg_ok, &segs)) return -1;
   return undelta_device(b, segs, static_cast<hipStream_t>(hip_stream));
 }
 
 extern "C" int BrotliAmdBatchUndeltaOutputs(BrotliAmdBatch* b, void* const* d_dst, const uint8_t* widths) {
   if (!b || !d_dst || !widths) { g_last_error = "invalid undelta arguments"; return -1; }
   no_times(b);
-  std::vector<DeliveredBytes> outs;
-  if (!delivered_outputs(b, &outs)) return -1;
   std::vector<BrotliAmdUnshuffleSeg> segs;
-  for (size_t i = 0; i < outs.size(); i++) {
-    if (d_dst[i] == nullptr) continue;   // (a stream the caller does not want: its width is not looked at)
-    if (!known_width(widths[i]) || !placed_ok((uint64_t)(uintptr_t)outs[i].ptr, (uint64_t)(uintptr_t)d_dst[i], widths[i])) return -1;
-    segs.push_back(BrotliAmdUnshuffleSeg{outs[i].ptr, static_cast<uint8_t*>(d_dst[i]), outs[i].len, widths[i], 0u});
-  }
-  if (segs.empty()) return 0;
-  DeviceGuard guard;
-  if (!hip_ok(hipSetDevice(b->device), "hipSetDevice")) return -1;
+  if (!width_segments_of_outputs(b, d_dst, widths, seg_ok, &segs)) return -1;
   return undelta_device(b, segs, b->last_stream);
 }
 
@@ -121,7 +102,7 @@ extern "C" int BrotliAmdDebugUndeltaHost(uint32_t n, const uint8_t* src, size_t 
     const uint64_t s = s_at + (in_place ? dst_offs[i] : src_offs[i]), d = d_at + dst_offs[i];
     if (!placed_ok(s, d, widths[i])) return -1;
     segs[i] = BrotliAmdUnshuffleSeg{reinterpret_cast<const uint8_t*>((uintptr_t)s), reinterpret_cast<uint8_t*>((uintptr_t)d), lens[i], widths[i], 0u};
-    pre[i + 1u] = pre[i] + brotli_amd_unshuffle_seg_units(d, lens[i]);
+    pre[i + 1u] = pre[i] + brotli_amd_seg_units(d, lens[i]);
   }
   const std::vector<uint8_t> before = droom;
   const uint64_t units = pre[n], ntiles = (units + tile_units - 1u) / tile_units;

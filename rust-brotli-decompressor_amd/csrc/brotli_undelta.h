@@ -39,7 +39,8 @@
 #define BROTLI_AMD_UNDELTA_H_
 
 #include "brotli_device_abi.h"  // the segment of a launch: BrotliAmdUnshuffleSeg (src, dst, len, width)
-#include "brotli_unshuffle.h"   // the memory and register helpers, the unit count, the search for a unit's segment
+#include "brotli_seg_walk.h"    // the unit count, the search for a unit's segment
+#include "brotli_unshuffle.h"   // the memory and register helpers
 
 #define BROTLI_AMD_UNDELTA_HD BROTLI_AMD_UNSHUFFLE_HD
 
@@ -63,13 +64,13 @@ BROTLI_AMD_UNDELTA_HD uint64_t brotli_amd_undelta_carry_in(uint64_t carry_out_be
 // ---- a tile's part [lo, hi) among the segments whose prefix sum is pre[0..count] (the whole tile, or what one chunk of segments holds of it) ----
 // the first unit of the part's last piece, and that piece's segment
 BROTLI_AMD_UNDELTA_HD uint64_t brotli_amd_undelta_last_piece(const uint64_t* pre, uint32_t count, uint64_t lo, uint64_t hi, uint32_t* seg) {
-  const uint32_t j = brotli_amd_unshuffle_find_seg(pre, count, hi - 1u);
+  const uint32_t j = brotli_amd_seg_find(pre, count, hi - 1u);
   *seg = j;
   return pre[j] > lo ? pre[j] : lo;
 }
 // cont of the tile whose first unit t0 is the part's first
 BROTLI_AMD_UNDELTA_HD uint32_t brotli_amd_undelta_cont(const uint64_t* pre, uint32_t count, uint64_t t0) {
-  return pre[brotli_amd_unshuffle_find_seg(pre, count, t0)] < t0 ? 1u : 0u;
+  return pre[brotli_amd_seg_find(pre, count, t0)] < t0 ? 1u : 0u;
 }
 // nohead of the tile at t0 whose last unit belongs to the segment that begins at unit `first`
 BROTLI_AMD_UNDELTA_HD uint32_t brotli_amd_undelta_nohead(uint64_t first, uint64_t t0) { return first < t0 ? 1u : 0u; }
@@ -201,7 +202,7 @@ BROTLI_AMD_UNDELTA_HD void brotli_amd_undelta_finish_w(uint64_t src, uint64_t ds
     }
   }
   if (lo == Wd && hi == Wd + 16u) brotli_amd_unshuffle_st128(Wd, o);
-  else brotli_amd_unshuffle_store_edge(Wd, lo, hi, o);
+  else brotli_amd_seg_store_edge(Wd, lo, hi, o);
 }
 
 // ... of any allowed width (another width: nothing is read or written)
@@ -247,7 +248,7 @@ inline BrotliAmdUndeltaTile brotli_amd_undelta_host_summary(const BrotliAmdUnshu
 inline void brotli_amd_undelta_host_apply(const BrotliAmdUnshuffleSeg* segs, const uint64_t* pre, uint32_t n, uint64_t t0, uint64_t t1, uint64_t carry_in) {
   BrotliAmdUndeltaPair run = {carry_in, 0u};
   for (uint64_t g = t0; g < t1; g++) {
-    const uint32_t j = brotli_amd_unshuffle_find_seg(pre, n, g);
+    const uint32_t j = brotli_amd_seg_find(pre, n, g);
     const uint64_t src = (uint64_t)(uintptr_t)segs[j].src, dst = (uint64_t)(uintptr_t)segs[j].dst, k = g - pre[j];
     const BrotliAmdU4 v = brotli_amd_undelta_fetch(src, dst, segs[j].len, segs[j].width, k);
     if (k == 0u) run = BrotliAmdUndeltaPair{0u, 1u};

@@ -2,9 +2,8 @@
 // (1, 2, 4, 8), back into values: a wrapping running sum per segment (gfx950, wave64).  The transform, what one unit of work reads and writes,
 // and the bookkeeping of a tile are csrc/brotli_undelta.h.
 //
-// Work is split by BYTES as csrc/brotli_unshuffle_kernels.hip splits it (the chunk loop, the prefix sum of unit counts in LDS, the binary search
-// for a unit's segment and the tile walk are that file's): the units of all segments, one after the other, are cut into tiles of kTileUnits
-// (BROTLI_AMD_UNDELTA_TILE_BYTES of destination), and the blocks take the tiles in turns.  A running sum is not local, so a long segment's
+// Work is split by BYTES, not by segments: the segment walk of csrc/brotli_seg_walk.h over the words of DESTINATION memory, in tiles of
+// BROTLI_AMD_UNDELTA_TILE_BYTES, in phases 1 and 3.  A running sum is not local, so a long segment's
 // tiles need the sums of the tiles in front of them.  No block ever waits for another block's result -- no look-back, no flags, no spins, no
 // grid barrier: blocks take tiles in turns, so the owner of a tile in front need not even be resident.  Instead:
 //   1. brotli_amd_undelta_sum_kernel    every tile's summary: the sum of its last piece (striped over the threads: a sum has no order) and the
@@ -16,18 +15,16 @@
 //                                       its carry; the tile's first piece starts from carry_in.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
 #include "brotli_device_abi.h"
+#include "brotli_seg_walk.h"
 #include "brotli_undelta.h"
 
 namespace {
 
-constexpr uint32_t kThreads = 256;
+constexpr uint32_t kThreads = BROTLI_AMD_SEG_THREADS, kChunkSegs = BROTLI_AMD_SEG_CHUNK_SEGS;
 constexpr uint32_t kWaves = kThreads / 64u;
 constexpr uint32_t kUnitsPerThread = 4;
 constexpr uint32_t kTileUnits = kThreads * kUnitsPerThread;
-constexpr uint32_t kChunkSegs = kThreads * 4;   // segments whose prefix sum lies in LDS at a time: four a thread
 constexpr uint32_t kCarryThreads = 1024;        // phase 2: kCarryPerThread neighbouring tiles a thread and pass
 constexpr uint32_t kCarryPerThread = 4;
 constexpr uint32_t kCarrySpan = kCarryThreads * kCarryPerThread;
@@ -50,47 +47,8 @@ __device__ __forceinline__ Pair wave_scan(Pair p, uint32_t lane) {
   return p;
 }
 
-// The chunk loop and the tile walk of the unshuffle kernel: part(pre, the chunk's segments, lo, hi, t0, tile) for every part [lo, hi) -- the
-// units of the tile at t0 among one chunk's segments -- of every tile of this block; every thread makes the same walk.
-template <class Part>
-__device__ __forceinline__ void walk_tiles(const Seg* __restrict__ segs, uint32_t n, uint64_t* pre, uint64_t* scan, Part part) {
-  const uint32_t tid = threadIdx.x;
-  uint64_t base = 0;              // units of the segments in front of the chunk
-  uint64_t tile = blockIdx.x;     // this block's next tile
-  for (uint32_t c0 = 0; c0 < n; c0 += kChunkSegs) {
-    const uint32_t cnt = n - c0 < kChunkSegs ? n - c0 : kChunkSegs;
-    uint64_t u[4], sum = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < 4u; k++) {
-      const uint32_t j = 4u * tid + k;
-      u[k] = j < cnt ? brotli_amd_unshuffle_seg_units((uint64_t)(uintptr_t)segs[c0 + j].dst, segs[c0 + j].len) : 0u;
-      sum += u[k];
-    }
-    __syncthreads();   // (the chunk before is done with pre[])
-    scan[tid] = sum;
-    __syncthreads();
-    for (uint32_t off = 1; off < kThreads; off <<= 1) {
-      const uint64_t v = tid >= off ? scan[tid - off] : 0u;
-      __syncthreads();
-      scan[tid] += v;
-      __syncthreads();
-    }
-    uint64_t at = base + scan[tid] - sum;
-#pragma unroll
-    for (uint32_t k = 0; k < 4u; k++) { pre[4u * tid + k] = at; at += u[k]; }
-    const uint64_t end = base + scan[kThreads - 1u];
-    if (tid == 0u) pre[kChunkSegs] = end;
-    __syncthreads();
-    while (tile * kTileUnits < end) {
-      const uint64_t t0 = tile * kTileUnits, t1 = t0 + kTileUnits;
-      const uint64_t lo = t0 > base ? t0 : base, hi = t1 < end ? t1 : end;   // the tile's units among this chunk's segments
-      if (lo < hi) part(pre, segs + c0, lo, hi, t0, tile);   // (not: a tile that began in the chunk before, and this chunk has no units)
-      if (t1 > end) break;   // (the tile goes on in the next chunk's segments)
-      tile += gridDim.x;
-    }
-    base = end;
-  }
-}
+// the address whose words are a segment's units
+struct DstOf { __device__ __forceinline__ const uint8_t* operator()(const Seg& sg) const { return sg.dst; } };
 
 // ---- phase 1 ----
 // the sum of the contributions of the units [from, hi) of one segment of width W whose first unit is `first`: this thread's share (at most
@@ -117,7 +75,7 @@ __global__ __launch_bounds__(kThreads) void brotli_amd_undelta_sum_kernel(const 
   __shared__ uint64_t scan[kThreads];
   __shared__ uint64_t wsum[kWaves];
   const uint32_t tid = threadIdx.x;
-  walk_tiles(segs, n, pre, scan, [&](const uint64_t* pre, const Seg* segs, uint64_t lo, uint64_t hi, uint64_t t0, uint64_t tile) {
+  brotli_amd_seg_walk<kTileUnits>(segs, n, pre, scan, DstOf(), [&](const uint64_t* pre, const Seg* segs, uint32_t, uint64_t lo, uint64_t hi, uint64_t t0, uint64_t tile) {
     if (lo == t0 && tid == 0u) tiles[tile].cont = brotli_amd_undelta_cont(pre, kChunkSegs, t0);
     const uint64_t tile_end = t0 + kTileUnits < units ? t0 + kTileUnits : units;
     if (hi != tile_end) return;   // (the tile's end lies in a later chunk's segments)
@@ -196,10 +154,10 @@ __global__ __launch_bounds__(kThreads) void brotli_amd_undelta_apply_kernel(cons
   __shared__ uint64_t wsum[kWaves];
   __shared__ uint32_t whead[kWaves];
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  walk_tiles(segs, n, pre, scan, [&](const uint64_t* pre, const Seg* segs, uint64_t lo, uint64_t hi, uint64_t t0, uint64_t tile) {
+  brotli_amd_seg_walk<kTileUnits>(segs, n, pre, scan, DstOf(), [&](const uint64_t* pre, const Seg* segs, uint32_t, uint64_t lo, uint64_t hi, uint64_t t0, uint64_t tile) {
     // (a part that does not begin the tile begins a chunk of segments: its first unit is a segment's first)
     const uint64_t carry_in = lo == t0 ? carries[tile] : 0u;
-    const uint32_t ja = brotli_amd_unshuffle_find_seg(pre, kChunkSegs, lo), jb = brotli_amd_unshuffle_find_seg(pre, kChunkSegs, hi - 1u);
+    const uint32_t ja = brotli_amd_seg_find(pre, kChunkSegs, lo), jb = brotli_amd_seg_find(pre, kChunkSegs, hi - 1u);
     BrotliAmdU4 v[kUnitsPerThread];
     uint64_t c[kUnitsPerThread], k[kUnitsPerThread];
     uint32_t seg[kUnitsPerThread];
@@ -209,7 +167,7 @@ __global__ __launch_bounds__(kThreads) void brotli_amd_undelta_apply_kernel(cons
       const uint64_t g = t0 + kUnitsPerThread * tid + i;
       v[i] = BrotliAmdU4{0u, 0u, 0u, 0u}; c[i] = 0u; k[i] = ~(uint64_t)0; seg[i] = ja;
       if (g >= lo && g < hi) {
-        if (ja != jb) seg[i] = brotli_amd_unshuffle_find_seg(pre, kChunkSegs, g);   // (one segment's tile -- the rule for a long one -- is searched for once)
+        if (ja != jb) seg[i] = brotli_amd_seg_find(pre, kChunkSegs, g);   // (one segment's tile -- the rule for a long one -- is searched for once)
         const Seg sg = segs[seg[i]];
         k[i] = g - pre[seg[i]];
         v[i] = brotli_amd_undelta_fetch((uint64_t)(uintptr_t)sg.src, (uint64_t)(uintptr_t)sg.dst, sg.len, sg.width, k[i]);
@@ -248,18 +206,15 @@ extern "C" uint64_t brotli_amd_undelta_scratch_bytes(uint64_t units) {
   return ((units + kTileUnits - 1u) / kTileUnits) * (sizeof(BrotliAmdUndeltaTile) + sizeof(uint64_t));
 }
 
-// units: the units of all segments together (brotli_amd_unshuffle_seg_units: the host has the table); d_scratch: brotli_amd_undelta_scratch_bytes
+// units: the units of all segments together (brotli_amd_seg_units: the host has the table); d_scratch: brotli_amd_undelta_scratch_bytes
 // of device memory, 16-byte aligned; ev[0..3], where not NULL, are recorded in front of, between and behind the three launches
 extern "C" hipError_t brotli_amd_launch_undelta(const BrotliAmdUnshuffleSeg* d_segs, uint32_t n, uint64_t units, void* d_scratch, hipStream_t stream,
                                                 const hipEvent_t* ev) {
   if (n == 0u || units == 0u) return hipSuccess;
-  int dev = 0, cus = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (e != hipSuccess) return e;
   const uint64_t ntiles = (units + kTileUnits - 1u) / kTileUnits;
-  // four blocks of four waves a CU, and no more blocks than there are tiles
-  const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)(cus > 0 ? cus : 1) * 4u, ntiles);
+  uint32_t grid = 0;
+  hipError_t e = brotli_amd_seg_grid(units, kTileUnits, &grid);
+  if (e != hipSuccess) return e;
   BrotliAmdUndeltaTile* tiles = static_cast<BrotliAmdUndeltaTile*>(d_scratch);
   uint64_t* carries = reinterpret_cast<uint64_t*>(tiles + ntiles);
   if (ev && (e = hipEventRecord(ev[0], stream)) != hipSuccess) return e;

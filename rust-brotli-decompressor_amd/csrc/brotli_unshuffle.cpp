@@ -17,25 +17,22 @@ bool known_width(uint32_t width) {
   g_last_error = "unshuffle width is not 1, 2, 4 or 8";
   return false;
 }
+bool seg_ok(const void*, const void*, uint32_t width) { return known_width(width); }
 
-// segs[0..n) on `stream`, waited for (the object's device is current; the widths were checked)
+// segs on `stream`, waited for (the widths were checked)
 int unshuffle_device(BrotliAmdBatch* b, const std::vector<BrotliAmdUnshuffleSeg>& segs, hipStream_t stream) {
-  const size_t table_bytes = sizeof(BrotliAmdUnshuffleSeg) * segs.size();
-  b->unshuffle_ms = 0.0f;
-  uint64_t units = 0;
-  for (const BrotliAmdUnshuffleSeg& s : segs) units += brotli_amd_unshuffle_seg_units((uint64_t)(uintptr_t)s.dst, s.len);
+  if (segs.empty()) return 0;
+  DeviceGuard guard;
+  if (!hip_ok(hipSetDevice(b->device), "hipSetDevice")) return -1;
+  const uint32_t n = (uint32_t)segs.size();
+  const uint64_t units = width_segments_units(segs);
   if (units == 0u) return 0;   // (segments without bytes: nothing to launch)
-  if (!b->d_unshuffle.reserve(table_bytes, "hipMalloc(unshuffle segments)")) return -1;
-  if (!b->ev_unshuffle0 && !(hip_ok(hipEventCreate(&b->ev_unshuffle0), "hipEventCreate") && hip_ok(hipEventCreate(&b->ev_unshuffle1), "hipEventCreate"))) return -1;
-  BrotliAmdUnshuffleSeg* d_segs = reinterpret_cast<BrotliAmdUnshuffleSeg*>(b->d_unshuffle.get());
-  bool ok = hip_ok(hipMemcpyAsync(d_segs, segs.data(), table_bytes, hipMemcpyHostToDevice, stream), "hipMemcpyAsync(unshuffle segments)");
-  ok = ok && hip_ok(hipEventRecord(b->ev_unshuffle0, stream), "hipEventRecord");
-  ok = ok && hip_ok(brotli_amd_launch_unshuffle(d_segs, (uint32_t)segs.size(), units, stream), "brotli_amd_unshuffle_kernel launch");
-  ok = ok && hip_ok(hipEventRecord(b->ev_unshuffle1, stream), "hipEventRecord");
-  // (waited for in any case: the copy reads this function's pageable memory)
-  if (!hip_ok(hipStreamSynchronize(stream), "hipStreamSynchronize(unshuffle)") || !ok) return -1;
-  (void)hipEventElapsedTime(&b->unshuffle_ms, b->ev_unshuffle0, b->ev_unshuffle1);
-  return 0;
+  return run_seg_call(&b->unshuffle, {"hipMalloc(unshuffle segments)", "hipMemcpyAsync(unshuffle segments)", "hipStreamSynchronize(unshuffle)"}, segs.data(),
+                      sizeof(BrotliAmdUnshuffleSeg) * n, 0u, 2u, stream, [&](uint8_t* d_segs, uint8_t*, const hipEvent_t* ev) {
+    return hip_ok(hipEventRecord(ev[0], stream), "hipEventRecord") &&
+           hip_ok(brotli_amd_launch_unshuffle(reinterpret_cast<BrotliAmdUnshuffleSeg*>(d_segs), n, units, stream), "brotli_amd_unshuffle_kernel launch") &&
+           hip_ok(hipEventRecord(ev[1], stream), "hipEventRecord");
+  }, &b->unshuffle_ms);
 }
 
 }  // namespace
@@ -44,30 +41,16 @@ extern "C" int BrotliAmdBatchUnshuffleSegments(BrotliAmdBatch* b, uint32_t n, co
                                                const uint8_t* widths, void* hip_stream) {
   if (!b || (n && (!d_src || !d_dst || !lens || !widths))) { g_last_error = "invalid unshuffle arguments"; return -1; }
   b->unshuffle_ms = 0.0f;
-  if (n == 0) return 0;
-  for (uint32_t i = 0; i < n; i++) if (!known_width(widths[i])) return -1;   // (in front of everything that touches the device)
-  std::vector<BrotliAmdUnshuffleSeg> segs(n);
-  for (uint32_t i = 0; i < n; i++)
-    segs[i] = BrotliAmdUnshuffleSeg{static_cast<const uint8_t*>(d_src[i]), static_cast<uint8_t*>(d_dst[i]), lens[i], widths[i], 0u};
-  DeviceGuard guard;
-  if (!hip_ok(hipSetDevice(b->device), "hipSetDevice")) return -1;
+  std::vector<BrotliAmdUnshuffleSeg> segs;
+  if (!width_segments(n, d_src, d_dst, lens, widths, seg_ok, &segs)) return -1;
   return unshuffle_device(b, segs, static_cast<hipStream_t>(hip_stream));
 }
 
 extern "C" int BrotliAmdBatchUnshuffleOutputs(BrotliAmdBatch* b, void* const* d_dst, const uint8_t* widths) {
   if (!b || !d_dst || !widths) { g_last_error = "invalid unshuffle arguments"; return -1; }
   b->unshuffle_ms = 0.0f;
-  std::vector<DeliveredBytes> outs;
-  if (!delivered_outputs(b, &outs)) return -1;
   std::vector<BrotliAmdUnshuffleSeg> segs;
-  for (size_t i = 0; i < outs.size(); i++) {
-    if (d_dst[i] == nullptr) continue;   // (a stream the caller does not want: its width is not looked at)
-    if (!known_width(widths[i])) return -1;
-    segs.push_back(BrotliAmdUnshuffleSeg{outs[i].ptr, static_cast<uint8_t*>(d_dst[i]), outs[i].len, widths[i], 0u});
-  }
-  if (segs.empty()) return 0;
-  DeviceGuard guard;
-  if (!hip_ok(hipSetDevice(b->device), "hipSetDevice")) return -1;
+  if (!width_segments_of_outputs(b, d_dst, widths, seg_ok, &segs)) return -1;
   return unshuffle_device(b, segs, b->last_stream);
 }
 
@@ -84,7 +67,7 @@ extern "C" int BrotliAmdDebugUnshuffleHost(uint32_t width, const uint8_t* src, s
   const uint64_t d_at = (((uint64_t)(uintptr_t)droom.data() + 15u) & ~(uint64_t)15) + 16u + dst_skew;
   if (len) std::memcpy(reinterpret_cast<void*>((uintptr_t)s_at), src, len);
   const std::vector<uint8_t> before = droom;
-  const uint64_t units = brotli_amd_unshuffle_seg_units(d_at, len);
+  const uint64_t units = brotli_amd_seg_units(d_at, len);
   // (two units a step, as a lane takes them in a tile inside one segment; odd `len`s of units end in a single one)
   for (uint64_t k = 0; k < units; k += 2u) brotli_amd_unshuffle_two_units(s_at, d_at, len, width, k, units);
   // no byte beside the destination may have changed

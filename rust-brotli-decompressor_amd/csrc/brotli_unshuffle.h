@@ -6,7 +6,7 @@
 // and for w m <= p < len: dst[p] = src[p] (Blosc's rule; Parquet's BYTE_STREAM_SPLIT never has r != 0).  Width 1 is a copy.  Out of place: no
 // destination range overlaps a source range or another destination range.
 //
-// A UNIT is one aligned 16-byte word of DESTINATION memory that [dst, dst + len) touches; unit k is the word at (dst & ~15) + 16 k.  The word
+// A UNIT (csrc/brotli_seg_walk.h) is one aligned 16-byte word of DESTINATION memory that [dst, dst + len) touches; unit k is the word at (dst & ~15) + 16 k.  The word
 // starts at position p0 = W - dst of the segment (negative in a first unit that starts inside its word).  Its bytes belong to the elements
 // e0 = floor(p0 / w) .. e0 + 16 / w (the last one only where p0 is no multiple of w), so the unit needs of every plane j one RUN of 16 / w
 // (+ 1) bytes at src + j m + e0.  A run is fetched as the ALIGNED DWORDS around it, shifted together in registers; the w runs are interleaved by
@@ -28,60 +28,40 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "brotli_seg_walk.h"   // a segment's units, the search for a unit's segment, the edge store, BrotliAmdU4, BROTLI_AMD_GLOBAL
+
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define BROTLI_AMD_UNSHUFFLE_HD __host__ __device__ inline __attribute__((always_inline))
 #else
 #define BROTLI_AMD_UNSHUFFLE_HD inline
 #endif
-// (global-memory instructions, not flat ones: the address space is said where an address is used)
-#if defined(__HIP_DEVICE_COMPILE__)
-#define BROTLI_AMD_UNSHUFFLE_GLOBAL __attribute__((address_space(1)))
-#endif
 
-struct BrotliAmdU4 { uint32_t x, y, z, w; };   // sixteen bytes a lane
-
-// ---- memory: aligned dwords, aligned 16-byte words, single bytes ----
+// ---- memory: aligned dwords, aligned 16-byte words, single bytes (the edge store: csrc/brotli_seg_walk.h) ----
 BROTLI_AMD_UNSHUFFLE_HD uint32_t brotli_amd_unshuffle_ld32(uint64_t a) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  return *(const BROTLI_AMD_UNSHUFFLE_GLOBAL uint32_t*)a;
+  return *(const BROTLI_AMD_GLOBAL uint32_t*)a;
 #else
   uint32_t v; memcpy(&v, reinterpret_cast<const void*>((uintptr_t)a), 4); return v;
 #endif
 }
 BROTLI_AMD_UNSHUFFLE_HD uint32_t brotli_amd_unshuffle_ld8(uint64_t a) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  return *(const BROTLI_AMD_UNSHUFFLE_GLOBAL uint8_t*)a;
+  return *(const BROTLI_AMD_GLOBAL uint8_t*)a;
 #else
   return *reinterpret_cast<const uint8_t*>((uintptr_t)a);
 #endif
 }
 BROTLI_AMD_UNSHUFFLE_HD BrotliAmdU4 brotli_amd_unshuffle_ld128(uint64_t a) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-  const v4u v = *(const BROTLI_AMD_UNSHUFFLE_GLOBAL v4u*)a;
+  const BrotliAmdV4 v = *(const BROTLI_AMD_GLOBAL BrotliAmdV4*)a;
   return BrotliAmdU4{v.x, v.y, v.z, v.w};
 #else
   BrotliAmdU4 v; memcpy(&v, reinterpret_cast<const void*>((uintptr_t)a), 16); return v;
 #endif
 }
-BROTLI_AMD_UNSHUFFLE_HD void brotli_amd_unshuffle_st32(uint64_t a, uint32_t v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  *(BROTLI_AMD_UNSHUFFLE_GLOBAL uint32_t*)a = v;
-#else
-  memcpy(reinterpret_cast<void*>((uintptr_t)a), &v, 4);
-#endif
-}
-BROTLI_AMD_UNSHUFFLE_HD void brotli_amd_unshuffle_st8(uint64_t a, uint32_t v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  *(BROTLI_AMD_UNSHUFFLE_GLOBAL uint8_t*)a = (uint8_t)v;
-#else
-  *reinterpret_cast<uint8_t*>((uintptr_t)a) = (uint8_t)v;
-#endif
-}
 BROTLI_AMD_UNSHUFFLE_HD void brotli_amd_unshuffle_st128(uint64_t a, BrotliAmdU4 v) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-  *(BROTLI_AMD_UNSHUFFLE_GLOBAL v4u*)a = v4u{v.x, v.y, v.z, v.w};
+  *(BROTLI_AMD_GLOBAL BrotliAmdV4*)a = BrotliAmdV4{v.x, v.y, v.z, v.w};
 #else
   memcpy(reinterpret_cast<void*>((uintptr_t)a), &v, 16);
 #endif
@@ -140,33 +120,8 @@ BROTLI_AMD_UNSHUFFLE_HD BrotliAmdU4 brotli_amd_unshuffle_shift_bytes(const uint3
   return v;
 }
 
-// bytes [lo, hi) of the word at W (lo, hi inside [W, W + 16], not the whole word): aligned dwords where the segment has all four bytes, single bytes elsewhere
-BROTLI_AMD_UNSHUFFLE_HD void brotli_amd_unshuffle_store_edge(uint64_t W, uint64_t lo, uint64_t hi, BrotliAmdU4 v) {
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-  for (uint32_t i = 0; i < 4u; i++) {
-    const uint64_t A = W + 4u * i;
-    if (A >= lo && A + 4u <= hi) { brotli_amd_unshuffle_st32(A, w[i]); continue; }
-    for (uint32_t j = 0; j < 4u; j++)
-      if (A + j >= lo && A + j < hi) brotli_amd_unshuffle_st8(A + j, w[i] >> (8u * j));
-  }
-}
-
 // ---- the work ----
 BROTLI_AMD_UNSHUFFLE_HD constexpr bool brotli_amd_unshuffle_width_ok(uint32_t w) { return w == 1u || w == 2u || w == 4u || w == 8u; }
-
-// A segment's UNITS are the 16-byte-aligned words of memory that [dst, dst + len) touches.
-BROTLI_AMD_UNSHUFFLE_HD uint64_t brotli_amd_unshuffle_seg_units(uint64_t dst, uint64_t len) { return len ? ((dst + len + 15u) >> 4) - (dst >> 4) : 0u; }
-
-// the segment of unit g in the prefix sum pre[0..count] of unit counts: pre[j] <= g < pre[j + 1] (pre[0] <= g < pre[count]; a segment without
-// units is never the answer)
-BROTLI_AMD_UNSHUFFLE_HD uint32_t brotli_amd_unshuffle_find_seg(const uint64_t* pre, uint32_t count, uint64_t g) {
-  uint32_t a = 0, b = count;
-  while (b - a > 1u) { const uint32_t m = (a + b) >> 1; if (pre[m] <= g) a = m; else b = m; }
-  return a;
-}
 
 // The run of plane bytes at address A (any alignment) of which the bytes in [need_lo, need_hi) are wanted: ND aligned dwords around it,
 // each loaded only where it holds a wanted byte, shifted together -- r[i] = bytes [4 i, 4 i + 4) of the run (what was not loaded reads as 0).
@@ -299,7 +254,7 @@ BROTLI_AMD_UNSHUFFLE_HD void brotli_amd_unshuffle_unit_w(uint64_t src, uint64_t 
     }
   }
   if (lo == Wd && hi == Wd + 16u) brotli_amd_unshuffle_st128(Wd, v);
-  else brotli_amd_unshuffle_store_edge(Wd, lo, hi, v);
+  else brotli_amd_seg_store_edge(Wd, lo, hi, v);
 }
 
 // Units k and k + 1 of a segment of `units` units (k + 1 only where it is one): what one lane takes in a tile that lies inside one segment.

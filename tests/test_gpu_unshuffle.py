@@ -144,6 +144,25 @@ def test_one_long_segment_among_five_thousand_short_ones(pkg, batch, dev, source
     _unshuffle(batch, dev, source, sentinel, segs, d_at + 64)
 
 
+def test_a_tile_that_spans_a_stretch_of_empty_segments(pkg, batch, dev, source, sentinel):
+    """the kernel takes the segment table a chunk at a time (csrc/brotli_seg_walk.h: a prefix sum of 1024 segments): two segments that share a
+    tile with 2500 empty ones between them -- the tile begins in one chunk, finds nothing in the next and ends in the one after; mixed widths,
+    odd alignments, gaps of sentinel bytes between some neighbours"""
+    rnd = random.Random(5)
+    tile = pkg.unshuffle_tile()
+    lens = [tile // 2 + 7] + [0] * 2500 + [tile + 9, 5, 0, 1] + [0] * 1100 + [3 * tile]
+    widths = iter([2, 8, 4, 1, 8])   # of the five segments that have bytes
+    segs, s_at, d_at = [], 3, 9
+    for l in lens:
+        if rnd.random() < 0.1:
+            s_at += rnd.randrange(1, 3); d_at += rnd.randrange(1, 3)
+        segs.append((s_at, d_at, l, next(widths) if l else rnd.choice(WIDTHS)))
+        s_at += l; d_at += l
+    units0 = (segs[0][1] + segs[0][2] + 15) // 16 - segs[0][1] // 16
+    assert 0 < units0 < tile // 16 and all(l == 0 for _, _, l, _ in segs[1:2501]) and segs[2501][2] > tile   # the first tile goes on 2501 segments later
+    _unshuffle(batch, dev, source, sentinel, segs, d_at + 64)
+
+
 def test_no_segment_empty_segments_and_the_last_byte(pkg, batch, dev, source, sentinel):
     _unshuffle(batch, dev, source, sentinel, [], 256)
     assert pkg.load_library().BrotliAmdBatchUnshuffleSegments(batch._h, 0, None, None, None, None, None) == 0

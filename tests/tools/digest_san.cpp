@@ -40,7 +40,7 @@ int main() {
         const uint64_t at = (uint64_t)(uintptr_t)block + skew;
         const uint32_t want = n ? ~raw_bitwise(poly, 0xFFFFFFFFu, block + skew, n) : 0u;
         const auto load = [](uint64_t W, uint32_t* w) { std::memcpy(w, reinterpret_cast<const void*>((uintptr_t)W), 16); };
-        const uint64_t units = brotli_amd_crc_seg_units(at, n);
+        const uint64_t units = brotli_amd_seg_units(at, n);
         if (units != span / 16u) { std::fprintf(stderr, "units %llu of a span of %zu\n", (unsigned long long)units, span); return 1; }
         for (uint32_t run : {1u, 2u, 3u, 4u, 7u, (uint32_t)BROTLI_AMD_CRC_RUN_UNITS}) {
           uint32_t got = 0;

@@ -45,7 +45,7 @@ static void expect(const uint8_t* s, size_t len, uint32_t w, uint8_t* want) {
 static void run(const std::vector<BrotliAmdUnshuffleSeg>& segs, uint64_t tile_units, bool backwards) {
   const uint32_t n = (uint32_t)segs.size();
   std::vector<uint64_t> pre(n + 1u, 0u);
-  for (uint32_t i = 0; i < n; i++) pre[i + 1u] = pre[i] + brotli_amd_unshuffle_seg_units((uint64_t)(uintptr_t)segs[i].dst, segs[i].len);
+  for (uint32_t i = 0; i < n; i++) pre[i + 1u] = pre[i] + brotli_amd_seg_units((uint64_t)(uintptr_t)segs[i].dst, segs[i].len);
   const uint64_t units = pre[n], ntiles = (units + tile_units - 1u) / tile_units;
   std::vector<BrotliAmdUndeltaTile> tiles(ntiles);
   std::vector<uint64_t> carries(ntiles);
@@ -79,7 +79,7 @@ static int one(uint32_t w, size_t len, uint32_t ss, uint32_t ds, uint64_t tile_u
   Block s(len, ss), d(len, ds);
   for (size_t i = 0; i < s.span; i++) s.base[i] = (uint8_t)rnd();
   for (size_t i = 0; i < d.span; i++) d.base[i] = (uint8_t)(0xA5u ^ i);
-  if (brotli_amd_unshuffle_seg_units((uint64_t)(uintptr_t)d.at(), len) != d.span / 16u) { std::fprintf(stderr, "units of a span of %zu\n", d.span); return 1; }
+  if (brotli_amd_seg_units((uint64_t)(uintptr_t)d.at(), len) != d.span / 16u) { std::fprintf(stderr, "units of a span of %zu\n", d.span); return 1; }
   run({BrotliAmdUnshuffleSeg{s.at(), d.at(), len, w, 0u}}, tile_units, (rnd() & 1u) != 0u);
   return check(s, d, w, "out of place");
 }

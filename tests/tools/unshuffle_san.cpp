@@ -22,7 +22,7 @@ static int one(uint32_t w, size_t len, uint32_t ss, uint32_t ds) {
   for (size_t i = 0; i < sspan; i++) sb[i] = (uint8_t)rnd();
   for (size_t i = 0; i < dspan; i++) db[i] = (uint8_t)(0xA5u ^ i);
   const uint64_t src = (uint64_t)(uintptr_t)sb + ss, dst = (uint64_t)(uintptr_t)db + ds;
-  const uint64_t units = brotli_amd_unshuffle_seg_units(dst, len);
+  const uint64_t units = brotli_amd_seg_units(dst, len);
   if (units != dspan / 16u) { std::fprintf(stderr, "units %llu of a span of %zu\n", (unsigned long long)units, dspan); return 1; }
   // as a lane takes them in a tile inside one segment: two units a step (width 8 has a path of its own for two whole words), pairs that begin at
   // an even or an odd unit; otherwise unit by unit, the last first (the units do not depend on their order)
