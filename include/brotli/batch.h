@@ -344,6 +344,73 @@ BROTLI_DEC_API int BrotliAmdDebugUndeltaHost(uint32_t n, const uint8_t* src, siz
                                             const uint64_t* src_offs, const uint64_t* dst_offs, const uint64_t* lens, const uint8_t* widths,
                                             uint32_t src_skew, uint32_t dst_skew, uint32_t tile_units, uint32_t order_seed, int in_place);
 
+/* ---- Bit-unshuffle on the device: bit planes of outputs back into elements ----
+ *
+ * The third filter that array containers put in front of a general-purpose codec is BITSHUFFLE: the bit transpose of the bitshuffle library and
+ * HDF5 filter 32008, the bit-shuffle mode of Blosc-style containers, the Bitshuffle stage of codec chains in zarr-like stores.  It is what
+ * quantised integers, sensor counts, masks and the low mantissa bits of floats go through where the byte shuffle does not compress well
+ * enough.  Undoing it is an 8 x 8 bit transpose per byte column on top of the unshuffle's byte interleave, and these calls take it where the
+ * decoded bytes lie.
+ *
+ * THE SEGMENT AND ITS PARAMETERS.  A segment has len bytes and a width w in {1, 2, 4, 8}.  It also has a block size B in elements: B == 0
+ * means the whole segment is one block; otherwise B is a multiple of 8, and any other value is rejected on the host.  m = len / w is the
+ * number of elements.
+ *
+ * BLOCKS.  The elements are cut into blocks of B, at the same byte offsets in source and destination: block b starts at element b B and byte
+ * offset o = b B w.  A full block transposes c = B elements.  The last, shorter block transposes c = (m - b B) rounded down to a multiple of
+ * 8; that can be 0.  So the last m % 8 elements and the len % w bytes behind them are always copied unchanged: dst[p] = src[p] for
+ * p >= 8 (m / 8) w.  (The blocked rule of the bitshuffle library; with B == 0 it is Blosc's rule: one block, left-over elements copied.)
+ *
+ * THE FORMULA.  Inside a block, for element i < c, byte j < w and bit k < 8 (bit 0 is the least significant):
+ *     bit k of dst[o + i w + j]  =  bit (i % 8) of src[o + (8 j + k) (c / 8) + i / 8]
+ * The source of a block is 8 w bit rows of c / 8 bytes each; row 8 j + k holds bit k of byte j of every element; element i sits in bit i % 8
+ * of byte i / 8 of its row.
+ *
+ * Width 1 is a real transform: 8 x 8 bit transposes of rows of c / 8 bytes.  The width and B are PER SEGMENT.  Only this direction -- planes
+ * to elements -- exists on the device.  B == 0 means "one block", NOT the library's "default block size": a caller with HDF5 data passes the
+ * file's block size, which is 8192 / w by default.
+ *
+ * OUT OF PLACE: no destination range overlaps any source range or any other destination range of the call.  This is stated, not checked.
+ *
+ * One launch does all segments, the work split by bytes as the unshuffle's is (csrc/brotli_bitunshuffle.h, csrc/brotli_bitunshuffle_kernels.hip).
+ * Blocks whose destination begins at a multiple of 16 bytes and that hold 32 elements or more go 32 elements a lane; every other word of
+ * destination is gathered bit by bit. */
+
+/* n segments in DEVICE memory -- lens[i] bytes of bit planes at d_src[i] become lens[i] bytes of elements of width widths[i], in blocks of
+ * block_elems[i] elements (block_elems == NULL: all 0), at d_dst[i]; any alignment, any length, 0 included; n is not bound by the batch object's
+ * max_streams --: one launch on hip_stream, and the call waits on that stream.  No byte outside [d_dst[i], d_dst[i] + lens[i]) is written;
+ * nothing outside the 16-byte-aligned span around [d_src[i], d_src[i] + lens[i]) is read.  n == 0 returns 0.  A negative value, and a
+ * BrotliAmdLastError text that names what was wrong, for a NULL batch, a NULL array (but block_elems) with n != 0, any width that is not 1, 2, 4 or
+ * 8 and any block_elems that is neither 0 nor a multiple of 8: all of these are checked on the host in front of everything else, so nothing is
+ * launched and no byte is written. */
+BROTLI_DEC_API int BrotliAmdBatchBitUnshuffleSegments(BrotliAmdBatch* batch, uint32_t n, const void* const* d_src, void* const* d_dst,
+                                                     const size_t* lens, const uint8_t* widths, const uint32_t* block_elems /* n entries, or NULL: all 0 */,
+                                                     void* hip_stream);
+
+/* The same for the DELIVERED bytes -- [out, out + decoded_size) -- of every stream of the last decode call on the object: stream i's go to
+ * d_dst[i] (device memory of decoded_size bytes, any alignment) by widths[i] and block_elems[i] (one entry per stream, or NULL: all 0);
+ * d_dst[i] == NULL skips stream i (its width and block are not looked at).  Where the sources are, and when they are valid, is
+ * BrotliAmdBatchUnshuffleOutputs' rule exactly, for the three kinds of decode call.  A stream that ended in an error or NEEDS_MORE_OUTPUT is
+ * transformed over its decoded_size bytes by the rule above (m = decoded_size / w).  The launch runs on the stream of that decode call and the
+ * call waits for it.  It is not a decode call itself: BrotliAmdBatchPackedOutput stays valid, and BrotliAmdBatchRelaunch and the Last* accessors say
+ * what they said before.  A negative value, and a BrotliAmdLastError text, for a NULL batch, a NULL d_dst or widths, a bad width or block (nothing
+ * is launched), an object without a decode call, a last decode call that failed behind its argument checks (one of no streams returns 0), and a
+ * launch that BrotliAmdBatchWait has not been called for. */
+BROTLI_DEC_API int BrotliAmdBatchBitUnshuffleOutputs(BrotliAmdBatch* batch, void* const* d_dst, const uint8_t* widths, const uint32_t* block_elems /* or NULL */);
+
+/* Milliseconds the bit-unshuffle kernel took in the last of the two calls above (HIP events around its launch). */
+BROTLI_DEC_API float BrotliAmdBatchLastBitUnshuffleMs(BrotliAmdBatch* batch);
+
+/* Test hooks (no device needed).  The bytes of destination memory in one tile of a bit-unshuffle launch; */
+BROTLI_DEC_API uint32_t BrotliAmdDebugBitUnshuffleTile(void);
+/* the transform of src[0, len) into dst[0, len) by the device's functions on the host, the segment's words taken in the order and by the items
+ * the kernel's lanes would take them: source and destination are placed at src_skew and dst_skew (0..15) past a 16-byte boundary among bytes
+ * that are not theirs.  *fast_items (may be NULL): the runs of 32 elements that went the fast way.  0; negative, a BrotliAmdLastError text and an
+ * untouched dst for a width that is not 1, 2, 4 or 8, a block_elems that is neither 0 nor a multiple of 8, a skew > 15, or a byte written outside
+ * the destination. */
+BROTLI_DEC_API int BrotliAmdDebugBitUnshuffleHost(uint32_t width, uint32_t block_elems, const uint8_t* src, size_t len, uint8_t* dst,
+                                                 uint32_t src_skew, uint32_t dst_skew, uint64_t* fast_items /* may be NULL */);
+
 /* Milliseconds the last launch spent in the decode kernel (HIP events on the launch stream). */
 BROTLI_DEC_API float BrotliAmdBatchLastKernelMs(BrotliAmdBatch* batch);
 

@@ -42,6 +42,8 @@ BATCH_H_SYMBOLS = [
     "BrotliAmdDebugUnshuffleHost",
     "BrotliAmdBatchUndeltaSegments", "BrotliAmdBatchUndeltaOutputs", "BrotliAmdBatchLastUndeltaMs", "BrotliAmdBatchLastUndeltaPhaseMs",
     "BrotliAmdDebugUndeltaTile", "BrotliAmdDebugUndeltaCarrySpan", "BrotliAmdDebugUndeltaHost",
+    "BrotliAmdBatchBitUnshuffleSegments", "BrotliAmdBatchBitUnshuffleOutputs", "BrotliAmdBatchLastBitUnshuffleMs", "BrotliAmdDebugBitUnshuffleTile",
+    "BrotliAmdDebugBitUnshuffleHost",
 ]
 
 
@@ -174,6 +176,13 @@ def load_library():
         L.BrotliAmdDebugUndeltaTile.restype = u32
         L.BrotliAmdDebugUndeltaCarrySpan.restype = u32
         L.BrotliAmdDebugUndeltaHost.argtypes = [u32, vp, sz, vp, sz, vp, vp, vp, vp, u32, u32, u32, u32, ctypes.c_int]
+    if hasattr(L, "BrotliAmdBatchBitUnshuffleSegments"):   # (bit-unshuffle: an older build of the library, loaded for an A/B, has none)
+        L.BrotliAmdBatchBitUnshuffleSegments.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp]
+        L.BrotliAmdBatchBitUnshuffleOutputs.argtypes = [vp, vp, vp, vp]
+        L.BrotliAmdBatchLastBitUnshuffleMs.restype = ctypes.c_float
+        L.BrotliAmdBatchLastBitUnshuffleMs.argtypes = [vp]
+        L.BrotliAmdDebugBitUnshuffleTile.restype = u32
+        L.BrotliAmdDebugBitUnshuffleHost.argtypes = [u32, u32, vp, sz, vp, u32, u32, vp]
     if hasattr(L, "BrotliAmdDebugSegWalkParts"):   # (the segment walk's host model: an older build of the library, loaded for an A/B, has none)
         L.BrotliAmdDebugSegWalkParts.restype = ctypes.c_uint64
         L.BrotliAmdDebugSegWalkParts.argtypes = [u32, vp, u32, u32, vp, ctypes.c_uint64]
@@ -251,6 +260,25 @@ def unshuffle_host(data: bytes, width, src_skew=0, dst_skew=0):
 def unshuffle_tile():
     """BrotliAmdDebugUnshuffleTile: the bytes of destination in one tile of an unshuffle launch"""
     return int(load_library().BrotliAmdDebugUnshuffleTile())
+
+
+def bitunshuffle_host(data: bytes, width, block=0, src_skew=0, dst_skew=0):
+    """BrotliAmdDebugBitUnshuffleHost: the bit planes in `data` back into elements of `width` bytes, in blocks of `block` elements (0: one block),
+    by the device's functions on the host (no device needed), source and destination placed at their skews past a 16-byte boundary
+    -> (bytes, the runs of 32 elements that went the fast way)"""
+    L = load_library()
+    data = bytes(data)
+    src = ctypes.create_string_buffer(data, max(1, len(data)))
+    dst = ctypes.create_string_buffer(max(1, len(data)))
+    fast = ctypes.c_uint64(0)
+    if L.BrotliAmdDebugBitUnshuffleHost(width, block, ctypes.addressof(src), len(data), ctypes.addressof(dst), src_skew, dst_skew, ctypes.byref(fast)) != 0:
+        raise RuntimeError("BrotliAmdDebugBitUnshuffleHost failed: " + last_error())
+    return dst.raw[:len(data)], int(fast.value)
+
+
+def bitunshuffle_tile():
+    """BrotliAmdDebugBitUnshuffleTile: the bytes of destination in one tile of a bit-unshuffle launch"""
+    return int(load_library().BrotliAmdDebugBitUnshuffleTile())
 
 
 def undelta_host(src: bytes, segs, dst_size=None, src_skew=0, dst_skew=0, tile_units=0, order_seed=0, in_place=False, fill=0):
@@ -564,6 +592,45 @@ class Batch:
         if phase is None:
             return float(self._L.BrotliAmdBatchLastUndeltaMs(self._h))
         return float(self._L.BrotliAmdBatchLastUndeltaPhaseMs(self._h, phase))
+
+    @staticmethod
+    def _block_array(blocks, n):
+        """block sizes as the C calls take them: None (all 0), or n of them"""
+        if blocks is None:
+            return None
+        if len(blocks) != n:
+            raise ValueError("blocks: one entry per segment or stream, or None")
+        return (ctypes.c_uint32 * max(1, n))(*[b if 0 <= b < (1 << 32) else 1 for b in blocks])   # (1: no multiple of 8, so it is refused)
+
+    def bitunshuffle_segments(self, src_ptrs, dst_ptrs, lens, widths, blocks=None, stream=None):
+        """BrotliAmdBatchBitUnshuffleSegments: lens[i] bytes of bit planes at the device address src_ptrs[i] become elements of widths[i] bytes
+        (1, 2, 4, 8), in blocks of blocks[i] elements (0: one block; None: all 0), at dst_ptrs[i]; any alignment, any length; out of place.
+        One launch and a wait on `stream`."""
+        n = len(src_ptrs)
+        if len(dst_ptrs) != n or len(lens) != n or len(widths) != n:
+            raise ValueError("src_ptrs, dst_ptrs, lens and widths: one entry per segment each")
+        a_s = (ctypes.c_void_p * max(1, n))(*src_ptrs)
+        a_d = (ctypes.c_void_p * max(1, n))(*dst_ptrs)
+        a_l = (ctypes.c_size_t * max(1, n))(*lens)
+        a_w = (ctypes.c_uint8 * max(1, n))(*[w if 0 <= w <= 255 else 0 for w in widths])
+        if self._L.BrotliAmdBatchBitUnshuffleSegments(self._h, n, a_s, a_d, a_l, a_w, self._block_array(blocks, n), stream) != 0:
+            raise RuntimeError("BrotliAmdBatchBitUnshuffleSegments failed: " + last_error())
+
+    def bitunshuffle_outputs(self, dst_ptrs, widths, blocks=None):
+        """BrotliAmdBatchBitUnshuffleOutputs: the delivered bytes of every stream of the last decode call on this object (after decode_device:
+        once wait() has returned), taken as bit planes of widths[i] in blocks of blocks[i] elements, become elements at the device address
+        dst_ptrs[i] (None or 0: the stream is skipped).  One launch on that call's stream, and a wait."""
+        n = self.out_n
+        if len(dst_ptrs) != n or len(widths) != n:
+            raise ValueError("dst_ptrs and widths: one entry per stream of the last decode call each")
+        a_d = (ctypes.c_void_p * max(1, n))(*[p or None for p in dst_ptrs])
+        a_w = (ctypes.c_uint8 * max(1, n))(*[w if 0 <= w <= 255 else 0 for w in widths])
+        if self._L.BrotliAmdBatchBitUnshuffleOutputs(self._h, a_d, a_w, self._block_array(blocks, n)) != 0:
+            raise RuntimeError("BrotliAmdBatchBitUnshuffleOutputs failed: " + last_error())
+
+    def last_bitunshuffle_ms(self):
+        """milliseconds the bit-unshuffle kernel took in the last bitunshuffle_segments / bitunshuffle_outputs"""
+        return float(self._L.BrotliAmdBatchLastBitUnshuffleMs(self._h))
 
     def decode_host_raw(self, in_ptrs, in_sizes, out_ptrs, out_caps, flags=FLAG_LARGE_WINDOW):
         """BrotliAmdBatchDecodeHost on buffers the caller owns (host addresses as integers): nothing is copied on the Python side"""

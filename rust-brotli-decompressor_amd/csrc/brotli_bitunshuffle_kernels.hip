@@ -1,0 +1,77 @@
+// brotli_bitunshuffle_kernels.hip -- one launch that turns the bit planes of n independent segments, of any alignment, length, width (1, 2, 4, 8)
+// and block size, back into elements (gfx950, wave64).  The transform, the kinds of a word and what a unit and an item read and write is
+// csrc/brotli_bitunshuffle.h.
+//
+// Work is split by BYTES, not by segments: the segment walk of csrc/brotli_seg_walk.h over the words of DESTINATION memory, in tiles of
+// BROTLI_AMD_BITUNSHUFFLE_TILE_BYTES.  A tile that lies inside one segment -- every tile of a long one -- is searched for once, and its width is
+// then the same for every lane, so the code is chosen once per tile; its lanes take SLOTS of 2 w words, neighbouring lanes neighbouring slots.
+// Where the segment's blocks are aligned a slot is one fast item: eight loads a byte column, each of which reads, over the wave, 256 contiguous
+// bytes of one bit row.  A fast item is 2 w words, so the tile is four times the unshuffle's: at width 8 it still has a slot for every thread.
+// A tile of several segments takes its words one by one, after a search each.
+#include <hip/hip_runtime.h>
+
+#include "brotli_bitunshuffle.h"
+#include "brotli_device_abi.h"
+#include "brotli_seg_walk.h"
+
+namespace {
+
+constexpr uint32_t kThreads = BROTLI_AMD_SEG_THREADS, kChunkSegs = BROTLI_AMD_SEG_CHUNK_SEGS;
+constexpr uint32_t kUnitsPerThread = 16;
+constexpr uint32_t kTileUnits = kThreads * kUnitsPerThread;
+
+static_assert(kTileUnits * 16u == BROTLI_AMD_BITUNSHUFFLE_TILE_BYTES, "the tile the header names");
+static_assert(kUnitsPerThread % 16u == 0u, "a whole number of slots a thread at every width");
+
+// the units [lo, hi) of a tile, all of one segment of width W whose first unit is `first`: the segment's slots that hold them, in turns
+template <uint32_t W>
+__device__ __forceinline__ void tile_of_one(const BrotliAmdUnshuffleSeg& sg, uint64_t first, uint64_t lo, uint64_t hi, uint32_t tid) {
+  const uint64_t src = (uint64_t)(uintptr_t)sg.src, dst = (uint64_t)(uintptr_t)sg.dst;
+  const uint64_t ka = lo - first, kb = hi - first;
+  for (uint64_t s = ka / (2u * W) + tid; 2u * W * s < kb; s += kThreads) (void)brotli_amd_bitunshuffle_slot_w<W>(src, dst, sg.len, sg.reserved, s, ka, kb);
+}
+
+__global__ __launch_bounds__(kThreads) void brotli_amd_bitunshuffle_kernel(const BrotliAmdUnshuffleSeg* __restrict__ segs, uint32_t n) {
+  __shared__ uint64_t pre[kChunkSegs + 1];   // units in front of each segment of the chunk (in front of the chunk included); [kChunkSegs]: behind its last
+  __shared__ uint64_t scan[kThreads];
+  const uint32_t tid = threadIdx.x;
+  brotli_amd_seg_walk<kTileUnits>(segs, n, pre, scan, [](const BrotliAmdUnshuffleSeg& sg) { return sg.dst; },
+                                  [&](const uint64_t* pre, const BrotliAmdUnshuffleSeg* segs, uint32_t, uint64_t lo, uint64_t hi, uint64_t t0, uint64_t) {
+    const uint32_t ja = brotli_amd_seg_find(pre, kChunkSegs, lo), jb = brotli_amd_seg_find(pre, kChunkSegs, hi - 1u);
+    if (ja == jb) {   // one segment's: the rule for a long one
+      const BrotliAmdUnshuffleSeg sg = segs[ja];
+      const uint64_t first = pre[ja];
+      switch (sg.width) {
+        case 1u: tile_of_one<1u>(sg, first, lo, hi, tid); break;
+        case 2u: tile_of_one<2u>(sg, first, lo, hi, tid); break;
+        case 4u: tile_of_one<4u>(sg, first, lo, hi, tid); break;
+        case 8u: tile_of_one<8u>(sg, first, lo, hi, tid); break;
+        default: break;   // (the host lets no other width through)
+      }
+    } else {
+      for (uint32_t it = 0; it < kUnitsPerThread; it++) {
+        const uint64_t g = t0 + it * kThreads + tid;
+        if (g >= lo && g < hi) {
+          const uint32_t j = brotli_amd_seg_find(pre, kChunkSegs, g);
+          const BrotliAmdUnshuffleSeg sg = segs[j];
+          const uint64_t k = g - pre[j];
+          (void)brotli_amd_bitunshuffle_range((uint64_t)(uintptr_t)sg.src, (uint64_t)(uintptr_t)sg.dst, sg.len, sg.width, sg.reserved, k, k + 1u);
+        }
+      }
+    }
+  });
+}
+
+}  // namespace
+
+extern "C" uint32_t brotli_amd_bitunshuffle_tile_bytes(void) { return BROTLI_AMD_BITUNSHUFFLE_TILE_BYTES; }
+
+// units: the units of all segments together (brotli_amd_seg_units: the host has the table)
+extern "C" hipError_t brotli_amd_launch_bitunshuffle(const BrotliAmdUnshuffleSeg* d_segs, uint32_t n, uint64_t units, hipStream_t stream) {
+  if (n == 0u || units == 0u) return hipSuccess;
+  uint32_t grid = 0;
+  const hipError_t e = brotli_amd_seg_grid(units, kTileUnits, &grid);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(brotli_amd_bitunshuffle_kernel, dim3(grid), dim3(kThreads), 0, stream, d_segs, n);
+  return hipGetLastError();
+}

@@ -128,6 +128,11 @@ typedef struct BrotliAmdUnshuffleSeg {
 // at src become len bytes of values at dst; dst == src is allowed at a multiple of width -- and cuts their destination into tiles of
 #define BROTLI_AMD_UNDELTA_TILE_BYTES 16384u  // destination bytes: a tile's carry-in comes from the tiles in front of it
 
+// A bit-unshuffle launch (csrc/brotli_bitunshuffle_kernels.hip, csrc/brotli_bitunshuffle.h) takes the segments of an unshuffle launch too -- here
+// the len bytes at src are blocks of 8 `width` bit rows -- with the block size in elements in `reserved` (0: one block; otherwise a multiple of
+// 8).  A fast item of that kernel is 2 `width` words, so its tile is larger: sixteen words a thread.
+#define BROTLI_AMD_BITUNSHUFFLE_TILE_BYTES 65536u  // destination bytes of one tile
+
 #ifdef __cplusplus
 }
 #endif

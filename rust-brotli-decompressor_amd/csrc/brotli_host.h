@@ -178,6 +178,9 @@ struct BrotliAmdBatch {
   // undelta (brotli_undelta.cpp)
   brotli_amd_host::SegCall undelta;   // behind the table: the summaries and carries of its tiles
   float undelta_ms = 0.0f, undelta_phase_ms[3] = {0.0f, 0.0f, 0.0f};
+  // bit-unshuffle (brotli_bitunshuffle.cpp)
+  brotli_amd_host::SegCall bitunshuffle;
+  float bitunshuffle_ms = 0.0f;
 };
 
 namespace brotli_amd_host {

@@ -6,7 +6,9 @@
 Two launches in all: the decode and the unshuffle (Batch.unshuffle_outputs).  The streams hold arrays SHUFFLED into byte planes (Parquet's
 BYTE_STREAM_SPLIT, the shuffle filter of Blosc and HDF5, the byte grouping of checkpoint compressors); the element width is the dtype's.
 A stream whose array was stored as DELTAS (sorted timestamps, offsets, index arrays), with or without the shuffle, says so in its spec and
-is summed up again by one more call (Batch.undelta_segments / Batch.undelta_outputs)."""
+is summed up again by one more call (Batch.undelta_segments / Batch.undelta_outputs).  A stream whose array went through BITSHUFFLE (the bit
+transpose of the bitshuffle library and HDF5 filter 32008, the bit-shuffle mode of Blosc-style containers) says so in its spec too, with the
+block size where there is one, and its bit planes are turned back by one call for all such streams (Batch.bitunshuffle_outputs)."""
 import torch
 
 SLOT_ALIGN = 64   # every returned tensor starts at a multiple of this many bytes of one buffer
@@ -19,7 +21,7 @@ def _numel(shape):
     return n
 
 
-FILTERS = ("shuffle", "delta")
+FILTERS = ("shuffle", "delta", "bitshuffle")
 
 
 def outputs_as_tensors(batch, specs):
@@ -33,6 +35,12 @@ def outputs_as_tensors(batch, specs):
         (dtype, shape, ("shuffle", "delta"))  byte planes of deltas: unshuffled as above, then Batch.undelta_segments in place over the slots
         (dtype, shape, ("delta",))            deltas: Batch.undelta_outputs straight into the slot
         (dtype, shape, ())                    the array's bytes as they are: a copy
+        (dtype, shape, ("bitshuffle",))       bit planes, one block over the whole array (Blosc's rule): ONE Batch.bitunshuffle_outputs call
+                                              for all such streams, into the slots
+        (dtype, shape, (("bitshuffle", 2048),))  bit planes in blocks of 2048 elements -- an item of the tuple may be the pair
+                                              ("bitshuffle", block_elems), a multiple of 8; HDF5's default is 8192 // itemsize
+        (dtype, shape, ("bitshuffle", "delta"))  bit planes of deltas: that call, then Batch.undelta_segments in place over the slots
+    "shuffle" together with "bitshuffle" in one spec raises ValueError, naming the stream.
     Delta is a wrapping running sum over the flattened array, on the dtype's BIT PATTERN taken as a little-endian unsigned integer of its
     width: meant for integer dtypes, allowed for any.  An unknown filter name raises ValueError, naming the stream."""
     sizes = batch.out_sizes
@@ -40,16 +48,24 @@ def outputs_as_tensors(batch, specs):
         raise RuntimeError("no outputs: no decode call on this batch object yet, or its launch has not been waited for")
     if len(specs) != len(sizes):
         raise ValueError("specs: %d entries for the %d streams of the last decode call" % (len(specs), len(sizes)))
-    slots, widths, filters, total = [], [], [], 0
+    slots, widths, filters, blocks, total = [], [], [], [], 0
     for i, spec in enumerate(specs):
         if spec is None:
-            slots.append(None); widths.append(1); filters.append(())
+            slots.append(None); widths.append(1); filters.append(()); blocks.append(0)
             continue
         dtype, shape = spec[0], spec[1]
-        flt = tuple(spec[2]) if len(spec) > 2 else ("shuffle",)
-        for name in flt:
+        flt, block = [], 0
+        for name in (tuple(spec[2]) if len(spec) > 2 else ("shuffle",)):
+            if isinstance(name, (tuple, list)) and len(name) == 2 and name[0] == "bitshuffle":   # ("bitshuffle", block_elems)
+                name, block = name[0], int(name[1])
+                if block < 0 or block % 8 != 0:
+                    raise ValueError("stream %d: a bitshuffle block of %d elements is neither 0 nor a multiple of 8" % (i, block))
             if name not in FILTERS:
                 raise ValueError("stream %d: unknown filter %r (known: %s)" % (i, name, ", ".join(FILTERS)))
+            flt.append(name)
+        flt = tuple(flt)
+        if "shuffle" in flt and "bitshuffle" in flt:
+            raise ValueError("stream %d: \"shuffle\" and \"bitshuffle\" in one spec: an array goes through one of them" % i)
         shape = tuple(int(d) for d in (shape if isinstance(shape, (tuple, list, torch.Size)) else (shape,)))
         item = torch.empty(0, dtype=dtype).element_size()
         if item not in (1, 2, 4, 8):
@@ -57,7 +73,7 @@ def outputs_as_tensors(batch, specs):
         want = _numel(shape) * item
         if sizes[i] != want:
             raise ValueError("stream %d: %d delivered bytes, but %s of shape %s is %d" % (i, sizes[i], dtype, shape, want))
-        slots.append((total, want, dtype, shape)); widths.append(item); filters.append(flt)
+        slots.append((total, want, dtype, shape)); widths.append(item); filters.append(flt); blocks.append(block)
         total = (total + want + SLOT_ALIGN - 1) // SLOT_ALIGN * SLOT_ALIGN
     buf = torch.empty(total + SLOT_ALIGN, dtype=torch.uint8, device="cuda")
     skip = -buf.data_ptr() % SLOT_ALIGN   # (the allocator's blocks are aligned far beyond this; nothing here depends on it)
@@ -65,12 +81,15 @@ def outputs_as_tensors(batch, specs):
     base = buf.data_ptr()
     # (a slot of no bytes has a pointer too: a NULL one would mean "skip", which is the same here)
     at = [None if s is None else base + s[0] for s in slots]
-    # the unshuffle call: every wanted stream but those that are deltas only; without "shuffle" it is a copy -- width 1
-    plain = [i for i, s in enumerate(slots) if s is not None and "shuffle" not in filters[i] and "delta" in filters[i]]
-    batch.unshuffle_outputs([None if i in plain else p for i, p in enumerate(at)], [w if "shuffle" in f else 1 for w, f in zip(widths, filters)])
+    # the unshuffle call: every wanted stream but those that are deltas only and those of bit planes; without "shuffle" it is a copy -- width 1
+    bits = [i for i, s in enumerate(slots) if s is not None and "bitshuffle" in filters[i]]
+    plain = [i for i, s in enumerate(slots) if s is not None and i not in bits and "shuffle" not in filters[i] and "delta" in filters[i]]
+    batch.unshuffle_outputs([None if i in plain or i in bits else p for i, p in enumerate(at)], [w if "shuffle" in f else 1 for w, f in zip(widths, filters)])
+    if bits:    # bit planes: from the outputs straight into the slots
+        batch.bitunshuffle_outputs([p if i in bits else None for i, p in enumerate(at)], widths, blocks)
     if plain:   # deltas only: from the outputs straight into the slots
         batch.undelta_outputs([p if i in plain else None for i, p in enumerate(at)], widths)
-    both = [i for i, s in enumerate(slots) if s is not None and "shuffle" in filters[i] and "delta" in filters[i]]
+    both = [i for i, s in enumerate(slots) if s is not None and ("shuffle" in filters[i] or "bitshuffle" in filters[i]) and "delta" in filters[i]]
     if both:    # in place over the slots, which are 64-byte aligned
         batch.undelta_segments([at[i] for i in both], [at[i] for i in both], [slots[i][1] for i in both], [widths[i] for i in both])
     return [None if s is None else buf[s[0]:s[0] + s[1]].view(s[2]).reshape(s[3]) for s in slots]

@@ -223,6 +223,22 @@ extern "C" {
         n: u32, src: *const u8, src_size: size_t, dst: *mut u8, dst_size: size_t, src_offs: *const u64, dst_offs: *const u64, lens: *const u64,
         widths: *const u8, src_skew: u32, dst_skew: u32, tile_units: u32, order_seed: u32, in_place: c_int,
     ) -> c_int;
+    /// bit planes back into elements (the inverse of bitshuffle): `n` segments of DEVICE memory (any alignment, any length), `widths[i]` of 1, 2, 4
+    /// or 8, `block_elems[i]` elements a block (0: one block; otherwise a multiple of 8; a NULL array: all 0), out of place, in one launch on
+    /// `hip_stream`; waits
+    pub fn BrotliAmdBatchBitUnshuffleSegments(
+        batch: *mut BrotliAmdBatch, n: u32, d_src: *const *const c_void, d_dst: *const *mut c_void, lens: *const size_t, widths: *const u8,
+        block_elems: *const u32, hip_stream: *mut c_void,
+    ) -> c_int;
+    /// the same for the delivered bytes of every stream of the last decode call on the object (after `BrotliAmdBatchWait` for a device call);
+    /// a NULL `d_dst[i]` skips stream i
+    pub fn BrotliAmdBatchBitUnshuffleOutputs(batch: *mut BrotliAmdBatch, d_dst: *const *mut c_void, widths: *const u8, block_elems: *const u32) -> c_int;
+    pub fn BrotliAmdBatchLastBitUnshuffleMs(batch: *mut BrotliAmdBatch) -> f32;
+    /// test hooks (no device needed)
+    pub fn BrotliAmdDebugBitUnshuffleTile() -> u32;
+    pub fn BrotliAmdDebugBitUnshuffleHost(
+        width: u32, block_elems: u32, src: *const u8, len: size_t, dst: *mut u8, src_skew: u32, dst_skew: u32, fast_items: *mut u64,
+    ) -> c_int;
     pub fn BrotliAmdLastError() -> *const c_char;
     pub fn BrotliAmdLastNote() -> *const c_char;
 }
