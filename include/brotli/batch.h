@@ -411,6 +411,79 @@ BROTLI_DEC_API uint32_t BrotliAmdDebugBitUnshuffleTile(void);
 BROTLI_DEC_API int BrotliAmdDebugBitUnshuffleHost(uint32_t width, uint32_t block_elems, const uint8_t* src, size_t len, uint8_t* dst,
                                                  uint32_t src_skew, uint32_t dst_skew, uint64_t* fast_items /* may be NULL */);
 
+/* ---- Bit-unpack on the device: k-bit fields of outputs back into elements ----
+ *
+ * The fourth layout that the same users put in front of the codec is FIXED-WIDTH BIT PACKING: values of k bits stored back to back, k no
+ * multiple of 8.  Parquet writes it for dictionary indices, levels and the miniblocks of DELTA_BINARY_PACKED, Arrow for validity bitmaps
+ * (k = 1); quantised checkpoints store 4-, 3- and 2-bit weights this way; numpy.packbits, numcodecs' PackBits and the sub-byte samples of PNG
+ * and TIFF are the MSB-first variant; frame-of-reference columns are packed deltas, which the undelta calls above then sum up.  It is the one
+ * filter here whose destination is LARGER than its source.
+ *
+ * THE SEGMENT AND ITS PARAMETERS.  A segment has source bytes src[0, src_len), a count m of elements, a field width k with 1 <= k <= 64, an
+ * element width w in {1, 2, 4, 8} with k <= 8 w, and flags.  The destination is exactly m w bytes: element i is a little-endian unsigned
+ * integer of w bytes at dst + i w.
+ *
+ * THE FORMULA.  Read the source as a string of bits.  Element i is the field of bits i k .. i k + k - 1.
+ *   LSB-first (flags bit 0 clear: Parquet RLE/bit-packed, Arrow, int4 weight packing): stream bit b is bit b % 8 of src[b / 8], bit 0 being
+ *     the least significant, and the first bit of a field is the value's bit 0.
+ *   MSB-first (BROTLI_AMD_BITUNPACK_MSB_FIRST: numpy.packbits' default, PackBits, PNG/TIFF, Parquet's deprecated BIT_PACKED): stream bit b is
+ *     bit 7 - b % 8 of src[b / 8], and the first bit of a field is the value's bit k - 1.
+ *   BROTLI_AMD_BITUNPACK_SIGNED: the value is sign-extended from bit k - 1 to 8 w bits.  Otherwise it is zero-extended.
+ * k == 8 w is a copy with LSB-first, and a byte reversal per element with MSB-first; both are allowed.  Example (the two of the Parquet format
+ * text): the values 0 .. 7 at k = 3 are 88 c6 fa LSB-first and 05 39 77 MSB-first.
+ *
+ * The transform reads ceil(m k / 8) source bytes.  Pad bits in the last one are ignored, and so are source bytes behind it.  k, w and the flags
+ * are PER SEGMENT.  Only this direction -- fields to elements -- exists on the device.
+ *
+ * OUT OF PLACE ONLY: no destination range overlaps any source range or any other destination range of the call.  This is stated, not checked.
+ *
+ * REFUSED ON THE HOST, in front of everything that touches the device: k == 0, k > 8 w, a width outside {1, 2, 4, 8}; unknown flag bits;
+ * ceil(m k / 8) > src_len; m > 2^56 (so that neither m k nor m w can overflow).
+ *
+ * One launch does all segments, the work split by the destination's bytes as the unshuffle's is (csrc/brotli_bitunpack.h,
+ * csrc/brotli_bitunpack_kernels.hip).  Where a destination begins at a multiple of 16 bytes, every whole group of 32 elements goes 32 elements
+ * a lane; every other word of destination is put together byte by byte. */
+#define BROTLI_AMD_BITUNPACK_MSB_FIRST 1u
+#define BROTLI_AMD_BITUNPACK_SIGNED 2u
+
+/* n segments in DEVICE memory -- the first counts[i] fields of bits[i] bits of the src_lens[i] bytes at d_src[i] become counts[i] elements of
+ * widths[i] bytes at d_dst[i], by flags[i] (flags == NULL: all 0); any alignment, any count, 0 included; n is not bound by the batch object's
+ * max_streams --: one launch on hip_stream, and the call waits on that stream.  No byte outside [d_dst[i], d_dst[i] + counts[i] widths[i]) is
+ * written; nothing outside the 16-byte-aligned span around the ceil(counts[i] bits[i] / 8) source bytes is read.  n == 0 and segments of no
+ * elements launch nothing and return 0.  A negative value, and a BrotliAmdLastError text that names the segment and what was wrong, for a NULL
+ * batch, a NULL array (but flags) with n != 0, and everything in the list above: all of these are checked on the host in front of everything
+ * else, so nothing is launched and no byte is written. */
+BROTLI_DEC_API int BrotliAmdBatchBitUnpackSegments(BrotliAmdBatch* batch, uint32_t n, const void* const* d_src, const size_t* src_lens, void* const* d_dst,
+                                                  const uint64_t* counts, const uint8_t* bits, const uint8_t* widths,
+                                                  const uint8_t* flags /* n entries, or NULL: all 0 */, void* hip_stream);
+
+/* The same for the DELIVERED bytes -- [out, out + decoded_size) -- of every stream of the last decode call on the object: stream i's source is
+ * its decoded_size delivered bytes, and its elements go to d_dst[i] (device memory of counts[i] widths[i] bytes, any alignment) by bits[i],
+ * widths[i] and flags[i] (one entry per stream each; flags may be NULL: all 0).  counts == NULL: stream i's count is floor(8 decoded_size /
+ * bits[i]), the whole fields that were delivered.  A given counts[i] that needs more bytes than were delivered fails the whole call: nothing is
+ * launched, and the error text names the stream.  d_dst[i] == NULL skips stream i (none of its parameters are looked at).  Where the sources
+ * are, and when they are valid, is BrotliAmdBatchUnshuffleOutputs' rule exactly, for the three kinds of decode call.  A stream that ended in an
+ * error or NEEDS_MORE_OUTPUT is transformed over its decoded_size bytes by the rule above.  The launch runs on the stream of that decode call
+ * and the call waits for it.  It is not a decode call itself: BrotliAmdBatchPackedOutput stays valid, and BrotliAmdBatchRelaunch and the Last*
+ * accessors say what they said before.  A negative value, and a BrotliAmdLastError text, for a NULL batch, a NULL d_dst, bits or widths, a
+ * refused shape or count (nothing is launched), an object without a decode call, a last decode call that failed behind its argument checks (one
+ * of no streams returns 0), and a launch that BrotliAmdBatchWait has not been called for. */
+BROTLI_DEC_API int BrotliAmdBatchBitUnpackOutputs(BrotliAmdBatch* batch, void* const* d_dst, const uint64_t* counts /* or NULL */, const uint8_t* bits,
+                                                 const uint8_t* widths, const uint8_t* flags /* or NULL */);
+
+/* Milliseconds the bit-unpack kernel took in the last of the two calls above (HIP events around its launch). */
+BROTLI_DEC_API float BrotliAmdBatchLastBitUnpackMs(BrotliAmdBatch* batch);
+
+/* Test hooks (no device needed).  The bytes of destination memory in one tile of a bit-unpack launch; */
+BROTLI_DEC_API uint32_t BrotliAmdDebugBitUnpackTile(void);
+/* the transform of the first `count` fields of src[0, src_len) into dst[0, count width) by the device's functions on the host, the segment's
+ * words taken in the order and by the items the kernel's lanes would take them: source and destination are placed at src_skew and dst_skew
+ * (0..15) past a 16-byte boundary among bytes that are not theirs.  *fast_items (may be NULL): the runs of 32 elements that went the fast way.
+ * 0; negative, a BrotliAmdLastError text and an untouched dst for a refused shape or count (the list above), a skew > 15, or a byte written
+ * outside the destination. */
+BROTLI_DEC_API int BrotliAmdDebugBitUnpackHost(uint32_t bits, uint32_t width, uint32_t flags, const uint8_t* src, size_t src_len, uint64_t count,
+                                              uint8_t* dst, uint32_t src_skew, uint32_t dst_skew, uint64_t* fast_items /* may be NULL */);
+
 /* Milliseconds the last launch spent in the decode kernel (HIP events on the launch stream). */
 BROTLI_DEC_API float BrotliAmdBatchLastKernelMs(BrotliAmdBatch* batch);
 

@@ -44,6 +44,8 @@ BATCH_H_SYMBOLS = [
     "BrotliAmdDebugUndeltaTile", "BrotliAmdDebugUndeltaCarrySpan", "BrotliAmdDebugUndeltaHost",
     "BrotliAmdBatchBitUnshuffleSegments", "BrotliAmdBatchBitUnshuffleOutputs", "BrotliAmdBatchLastBitUnshuffleMs", "BrotliAmdDebugBitUnshuffleTile",
     "BrotliAmdDebugBitUnshuffleHost",
+    "BrotliAmdBatchBitUnpackSegments", "BrotliAmdBatchBitUnpackOutputs", "BrotliAmdBatchLastBitUnpackMs", "BrotliAmdDebugBitUnpackTile",
+    "BrotliAmdDebugBitUnpackHost",
 ]
 
 
@@ -67,6 +69,7 @@ class SizeHint(ctypes.Structure):  # BrotliAmdSizeHint: what a stream's headers 
 
 SIZE_OK, SIZE_TRUNCATED, SIZE_REJECTED = 0, 1, 2  # SizeHint.status
 DIGEST_CRC32, DIGEST_CRC32C = 1, 2  # BROTLI_AMD_DIGEST_*: zlib's polynomial, Castagnoli's
+BITUNPACK_MSB_FIRST, BITUNPACK_SIGNED = 1, 2  # BROTLI_AMD_BITUNPACK_*: the first bit of a field is the value's highest; sign-extended
 
 
 def build(force=False):
@@ -183,6 +186,13 @@ def load_library():
         L.BrotliAmdBatchLastBitUnshuffleMs.argtypes = [vp]
         L.BrotliAmdDebugBitUnshuffleTile.restype = u32
         L.BrotliAmdDebugBitUnshuffleHost.argtypes = [u32, u32, vp, sz, vp, u32, u32, vp]
+    if hasattr(L, "BrotliAmdBatchBitUnpackSegments"):   # (bit-unpack: an older build of the library, loaded for an A/B, has none)
+        L.BrotliAmdBatchBitUnpackSegments.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.BrotliAmdBatchBitUnpackOutputs.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.BrotliAmdBatchLastBitUnpackMs.restype = ctypes.c_float
+        L.BrotliAmdBatchLastBitUnpackMs.argtypes = [vp]
+        L.BrotliAmdDebugBitUnpackTile.restype = u32
+        L.BrotliAmdDebugBitUnpackHost.argtypes = [u32, u32, u32, vp, sz, ctypes.c_uint64, vp, u32, u32, vp]
     if hasattr(L, "BrotliAmdDebugSegWalkParts"):   # (the segment walk's host model: an older build of the library, loaded for an A/B, has none)
         L.BrotliAmdDebugSegWalkParts.restype = ctypes.c_uint64
         L.BrotliAmdDebugSegWalkParts.argtypes = [u32, vp, u32, u32, vp, ctypes.c_uint64]
@@ -274,6 +284,29 @@ def bitunshuffle_host(data: bytes, width, block=0, src_skew=0, dst_skew=0):
     if L.BrotliAmdDebugBitUnshuffleHost(width, block, ctypes.addressof(src), len(data), ctypes.addressof(dst), src_skew, dst_skew, ctypes.byref(fast)) != 0:
         raise RuntimeError("BrotliAmdDebugBitUnshuffleHost failed: " + last_error())
     return dst.raw[:len(data)], int(fast.value)
+
+
+def bitunpack_host(data: bytes, count, bits, width, flags=0, src_skew=0, dst_skew=0):
+    """BrotliAmdDebugBitUnpackHost: the first `count` fields of `bits` bits in `data` back into elements of `width` bytes (flags: BITUNPACK_*),
+    by the device's functions on the host (no device needed), source and destination placed at their skews past a 16-byte boundary
+    -> (bytes, the runs of 32 elements that went the fast way)"""
+    L = load_library()
+    data = bytes(data)
+    room = count * width if 0 <= count <= (1 << 40) and 0 < width <= 8 else 0   # (what is refused writes nothing)
+    src = ctypes.create_string_buffer(data, max(1, len(data)))
+    dst = ctypes.create_string_buffer(max(1, room))
+    fast = ctypes.c_uint64(0)
+    clip = lambda v, top: v if 0 <= v <= top else top   # (what no C type of the call holds is refused as its largest value is)
+    if L.BrotliAmdDebugBitUnpackHost(clip(bits, 0xFFFFFFFF), clip(width, 0xFFFFFFFF), clip(flags, 0xFFFFFFFF), ctypes.addressof(src), len(data),
+                                     clip(count, (1 << 64) - 1), ctypes.addressof(dst), clip(src_skew, 0xFFFFFFFF), clip(dst_skew, 0xFFFFFFFF),
+                                     ctypes.byref(fast)) != 0:
+        raise RuntimeError("BrotliAmdDebugBitUnpackHost failed: " + last_error())
+    return dst.raw[:room], int(fast.value)
+
+
+def bitunpack_tile():
+    """BrotliAmdDebugBitUnpackTile: the bytes of destination in one tile of a bit-unpack launch"""
+    return int(load_library().BrotliAmdDebugBitUnpackTile())
 
 
 def bitunshuffle_tile():
@@ -627,6 +660,46 @@ class Batch:
         a_w = (ctypes.c_uint8 * max(1, n))(*[w if 0 <= w <= 255 else 0 for w in widths])
         if self._L.BrotliAmdBatchBitUnshuffleOutputs(self._h, a_d, a_w, self._block_array(blocks, n)) != 0:
             raise RuntimeError("BrotliAmdBatchBitUnshuffleOutputs failed: " + last_error())
+
+    @staticmethod
+    def _byte_array(values, n, what, bad=255):
+        """small parameters as the C calls take them: n bytes; what no byte holds becomes `bad`, which the call refuses"""
+        if len(values) != n:
+            raise ValueError(what + ": one entry per segment or stream")
+        return (ctypes.c_uint8 * max(1, n))(*[v if 0 <= v <= 255 else bad for v in values])
+
+    def bitunpack_segments(self, src_ptrs, src_lens, dst_ptrs, counts, bits, widths, flags=None, stream=None):
+        """BrotliAmdBatchBitUnpackSegments: the first counts[i] fields of bits[i] bits (1 .. 8 widths[i]) of the src_lens[i] bytes at the device
+        address src_ptrs[i] become counts[i] elements of widths[i] bytes (1, 2, 4, 8) at dst_ptrs[i], by flags[i] (BITUNPACK_MSB_FIRST,
+        BITUNPACK_SIGNED; None: all 0); any alignment, any count; out of place.  One launch and a wait on `stream`."""
+        n = len(src_ptrs)
+        if len(src_lens) != n or len(dst_ptrs) != n or len(counts) != n:
+            raise ValueError("src_ptrs, src_lens, dst_ptrs and counts: one entry per segment each")
+        a_s = (ctypes.c_void_p * max(1, n))(*src_ptrs)
+        a_l = (ctypes.c_size_t * max(1, n))(*src_lens)
+        a_d = (ctypes.c_void_p * max(1, n))(*dst_ptrs)
+        a_c = (ctypes.c_uint64 * max(1, n))(*[c if 0 <= c < (1 << 64) else (1 << 64) - 1 for c in counts])
+        a_f = None if flags is None else self._byte_array(flags, n, "flags")
+        if self._L.BrotliAmdBatchBitUnpackSegments(self._h, n, a_s, a_l, a_d, a_c, self._byte_array(bits, n, "bits"), self._byte_array(widths, n, "widths", 0),
+                                                   a_f, stream) != 0:
+            raise RuntimeError("BrotliAmdBatchBitUnpackSegments failed: " + last_error())
+
+    def bitunpack_outputs(self, dst_ptrs, bits, widths, counts=None, flags=None):
+        """BrotliAmdBatchBitUnpackOutputs: the delivered bytes of every stream of the last decode call on this object (after decode_device: once
+        wait() has returned), taken as fields of bits[i] bits, become counts[i] elements of widths[i] bytes at the device address dst_ptrs[i]
+        (None or 0: the stream is skipped); counts=None: as many whole fields as were delivered.  One launch on that call's stream, and a wait."""
+        n = self.out_n
+        if len(dst_ptrs) != n or (counts is not None and len(counts) != n):
+            raise ValueError("dst_ptrs and counts: one entry per stream of the last decode call each")
+        a_d = (ctypes.c_void_p * max(1, n))(*[p or None for p in dst_ptrs])
+        a_c = None if counts is None else (ctypes.c_uint64 * max(1, n))(*[c if 0 <= c < (1 << 64) else (1 << 64) - 1 for c in counts])
+        a_f = None if flags is None else self._byte_array(flags, n, "flags")
+        if self._L.BrotliAmdBatchBitUnpackOutputs(self._h, a_d, a_c, self._byte_array(bits, n, "bits"), self._byte_array(widths, n, "widths", 0), a_f) != 0:
+            raise RuntimeError("BrotliAmdBatchBitUnpackOutputs failed: " + last_error())
+
+    def last_bitunpack_ms(self):
+        """milliseconds the bit-unpack kernel took in the last bitunpack_segments / bitunpack_outputs"""
+        return float(self._L.BrotliAmdBatchLastBitUnpackMs(self._h))
 
     def last_bitunshuffle_ms(self):
         """milliseconds the bit-unshuffle kernel took in the last bitunshuffle_segments / bitunshuffle_outputs"""

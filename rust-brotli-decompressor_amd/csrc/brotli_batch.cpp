@@ -425,7 +425,7 @@ extern "C" void BrotliAmdBatchDestroy(BrotliAmdBatch* b) {
   else (void)hipDeviceSynchronize();
   if (b->copy_stream) (void)hipStreamDestroy(b->copy_stream);
   for (hipEvent_t ev : {b->ev0, b->ev1, b->ev2, b->ev3}) if (ev) (void)hipEventDestroy(ev);
-  for (SegCall* c : {&b->digest, &b->unshuffle, &b->undelta, &b->bitunshuffle})
+  for (SegCall* c : {&b->digest, &b->unshuffle, &b->undelta, &b->bitunshuffle, &b->bitunpack})
     for (hipEvent_t ev : c->ev) if (ev) (void)hipEventDestroy(ev);
   delete b;
 }

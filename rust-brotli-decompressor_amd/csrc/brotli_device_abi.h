@@ -133,6 +133,12 @@ typedef struct BrotliAmdUnshuffleSeg {
 // 8).  A fast item of that kernel is 2 `width` words, so its tile is larger: sixteen words a thread.
 #define BROTLI_AMD_BITUNSHUFFLE_TILE_BYTES 65536u  // destination bytes of one tile
 
+// A bit-unpack launch (csrc/brotli_bitunpack_kernels.hip, csrc/brotli_bitunpack.h) takes the segments of an unshuffle launch as well, with one
+// difference: `len` is the DESTINATION's bytes -- m elements of `width` bytes, m `width` --, and the units are the destination's; the source is
+// the ceil(m k / 8) bytes at src that hold m fields of k bits.  `reserved` is k | flags << 8 (k: 1 .. 8 `width`; flags: bit 0 MSB-first, bit 1
+// sign-extended).  A fast item of that kernel is 2 `width` words too, so it has the bit-unshuffle's tile: sixteen words a thread.
+#define BROTLI_AMD_BITUNPACK_TILE_BYTES 65536u  // destination bytes of one tile
+
 #ifdef __cplusplus
 }
 #endif

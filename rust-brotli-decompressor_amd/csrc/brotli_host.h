@@ -181,6 +181,9 @@ struct BrotliAmdBatch {
   // bit-unshuffle (brotli_bitunshuffle.cpp)
   brotli_amd_host::SegCall bitunshuffle;
   float bitunshuffle_ms = 0.0f;
+  // bit-unpack (brotli_bitunpack.cpp)
+  brotli_amd_host::SegCall bitunpack;
+  float bitunpack_ms = 0.0f;
 };
 
 namespace brotli_amd_host {

@@ -8,7 +8,10 @@ BYTE_STREAM_SPLIT, the shuffle filter of Blosc and HDF5, the byte grouping of ch
 A stream whose array was stored as DELTAS (sorted timestamps, offsets, index arrays), with or without the shuffle, says so in its spec and
 is summed up again by one more call (Batch.undelta_segments / Batch.undelta_outputs).  A stream whose array went through BITSHUFFLE (the bit
 transpose of the bitshuffle library and HDF5 filter 32008, the bit-shuffle mode of Blosc-style containers) says so in its spec too, with the
-block size where there is one, and its bit planes are turned back by one call for all such streams (Batch.bitunshuffle_outputs)."""
+block size where there is one, and its bit planes are turned back by one call for all such streams (Batch.bitunshuffle_outputs).  A stream
+whose array was BIT-PACKED -- fields of k bits back to back: Parquet's bit-packed runs, Arrow's validity bitmaps, 4-bit weights,
+numpy.packbits -- names k in its spec; it is the one stream whose slot is larger than its delivered bytes, and one call unpacks all such
+streams into their slots (Batch.bitunpack_outputs)."""
 import torch
 
 SLOT_ALIGN = 64   # every returned tensor starts at a multiple of this many bytes of one buffer
@@ -21,7 +24,8 @@ def _numel(shape):
     return n
 
 
-FILTERS = ("shuffle", "delta", "bitshuffle")
+FILTERS = ("shuffle", "delta", "bitshuffle", "bitpack")
+BITPACK_OPTIONS = {"big": 1, "signed": 2}   # BITUNPACK_MSB_FIRST, BITUNPACK_SIGNED
 
 
 def outputs_as_tensors(batch, specs):
@@ -40,7 +44,13 @@ def outputs_as_tensors(batch, specs):
         (dtype, shape, (("bitshuffle", 2048),))  bit planes in blocks of 2048 elements -- an item of the tuple may be the pair
                                               ("bitshuffle", block_elems), a multiple of 8; HDF5's default is 8192 // itemsize
         (dtype, shape, ("bitshuffle", "delta"))  bit planes of deltas: that call, then Batch.undelta_segments in place over the slots
-    "shuffle" together with "bitshuffle" in one spec raises ValueError, naming the stream.
+        (dtype, shape, (("bitpack", 12),))    numel fields of 12 bits, LSB-first, zero-extended into the dtype's elements (k = 1 ..
+                                              8 x itemsize): ONE Batch.bitunpack_outputs call for all such streams, into the slots.  Such a
+                                              stream must have delivered exactly ceil(numel k / 8) bytes; its slot is numel x itemsize
+        (dtype, shape, (("bitpack", 4, "signed"),))  ... sign-extended from bit k - 1; "big" behind k: MSB-first (numpy.packbits, PNG); both may stand
+        (dtype, shape, (("bitpack", 20), "delta"))  packed deltas (frame of reference): that call, then Batch.undelta_segments in place
+    "shuffle" together with "bitshuffle", and "bitpack" together with either, in one spec raises ValueError, naming the stream; so does a k outside
+    1 .. 8 x itemsize and an unknown option.
     Delta is a wrapping running sum over the flattened array, on the dtype's BIT PATTERN taken as a little-endian unsigned integer of its
     width: meant for integer dtypes, allowed for any.  An unknown filter name raises ValueError, naming the stream."""
     sizes = batch.out_sizes
@@ -48,32 +58,49 @@ def outputs_as_tensors(batch, specs):
         raise RuntimeError("no outputs: no decode call on this batch object yet, or its launch has not been waited for")
     if len(specs) != len(sizes):
         raise ValueError("specs: %d entries for the %d streams of the last decode call" % (len(specs), len(sizes)))
-    slots, widths, filters, blocks, total = [], [], [], [], 0
+    slots, widths, filters, blocks, packs, total = [], [], [], [], [], 0
     for i, spec in enumerate(specs):
         if spec is None:
-            slots.append(None); widths.append(1); filters.append(()); blocks.append(0)
+            slots.append(None); widths.append(1); filters.append(()); blocks.append(0); packs.append((1, 0))
             continue
         dtype, shape = spec[0], spec[1]
-        flt, block = [], 0
+        flt, block, pack = [], 0, None
         for name in (tuple(spec[2]) if len(spec) > 2 else ("shuffle",)):
             if isinstance(name, (tuple, list)) and len(name) == 2 and name[0] == "bitshuffle":   # ("bitshuffle", block_elems)
                 name, block = name[0], int(name[1])
                 if block < 0 or block % 8 != 0:
                     raise ValueError("stream %d: a bitshuffle block of %d elements is neither 0 nor a multiple of 8" % (i, block))
+            if isinstance(name, (tuple, list)) and len(name) >= 1 and name[0] == "bitpack":   # ("bitpack", k, options...)
+                if len(name) < 2:
+                    raise ValueError("stream %d: \"bitpack\" without its field width: (\"bitpack\", k)" % i)
+                for opt in name[2:]:
+                    if opt not in BITPACK_OPTIONS:
+                        raise ValueError("stream %d: unknown bitpack option %r (known: %s)" % (i, opt, ", ".join(BITPACK_OPTIONS)))
+                name, pack = name[0], (int(name[1]), sum({BITPACK_OPTIONS[opt] for opt in name[2:]}))
+            elif name == "bitpack":
+                raise ValueError("stream %d: \"bitpack\" without its field width: (\"bitpack\", k)" % i)
             if name not in FILTERS:
                 raise ValueError("stream %d: unknown filter %r (known: %s)" % (i, name, ", ".join(FILTERS)))
             flt.append(name)
         flt = tuple(flt)
         if "shuffle" in flt and "bitshuffle" in flt:
             raise ValueError("stream %d: \"shuffle\" and \"bitshuffle\" in one spec: an array goes through one of them" % i)
+        if pack is not None and ("shuffle" in flt or "bitshuffle" in flt):
+            raise ValueError("stream %d: \"bitpack\" with \"shuffle\" or \"bitshuffle\" in one spec: packed fields have no byte or bit planes" % i)
         shape = tuple(int(d) for d in (shape if isinstance(shape, (tuple, list, torch.Size)) else (shape,)))
         item = torch.empty(0, dtype=dtype).element_size()
         if item not in (1, 2, 4, 8):
             raise ValueError("stream %d: elements of %d bytes (%s) cannot be unshuffled" % (i, item, dtype))
         want = _numel(shape) * item
-        if sizes[i] != want:
+        if pack is not None:
+            if not 1 <= pack[0] <= 8 * item:
+                raise ValueError("stream %d: bitpack fields of %d bits, but %s takes 1 .. %d" % (i, pack[0], dtype, 8 * item))
+            stored = (_numel(shape) * pack[0] + 7) // 8
+            if sizes[i] != stored:
+                raise ValueError("stream %d: %d delivered bytes, but %d fields of %d bits (shape %s) are %d" % (i, sizes[i], _numel(shape), pack[0], shape, stored))
+        elif sizes[i] != want:
             raise ValueError("stream %d: %d delivered bytes, but %s of shape %s is %d" % (i, sizes[i], dtype, shape, want))
-        slots.append((total, want, dtype, shape)); widths.append(item); filters.append(flt); blocks.append(block)
+        slots.append((total, want, dtype, shape)); widths.append(item); filters.append(flt); blocks.append(block); packs.append(pack or (1, 0))
         total = (total + want + SLOT_ALIGN - 1) // SLOT_ALIGN * SLOT_ALIGN
     buf = torch.empty(total + SLOT_ALIGN, dtype=torch.uint8, device="cuda")
     skip = -buf.data_ptr() % SLOT_ALIGN   # (the allocator's blocks are aligned far beyond this; nothing here depends on it)
@@ -81,15 +108,21 @@ def outputs_as_tensors(batch, specs):
     base = buf.data_ptr()
     # (a slot of no bytes has a pointer too: a NULL one would mean "skip", which is the same here)
     at = [None if s is None else base + s[0] for s in slots]
-    # the unshuffle call: every wanted stream but those that are deltas only and those of bit planes; without "shuffle" it is a copy -- width 1
+    # the unshuffle call: every wanted stream but those that are deltas only, those of bit planes and those of packed fields; without "shuffle"
+    # it is a copy -- width 1
     bits = [i for i, s in enumerate(slots) if s is not None and "bitshuffle" in filters[i]]
-    plain = [i for i, s in enumerate(slots) if s is not None and i not in bits and "shuffle" not in filters[i] and "delta" in filters[i]]
-    batch.unshuffle_outputs([None if i in plain or i in bits else p for i, p in enumerate(at)], [w if "shuffle" in f else 1 for w, f in zip(widths, filters)])
+    packed = [i for i, s in enumerate(slots) if s is not None and "bitpack" in filters[i]]
+    plain = [i for i, s in enumerate(slots) if s is not None and i not in bits and i not in packed and "shuffle" not in filters[i] and "delta" in filters[i]]
+    batch.unshuffle_outputs([None if i in plain or i in bits or i in packed else p for i, p in enumerate(at)],
+                            [w if "shuffle" in f else 1 for w, f in zip(widths, filters)])
     if bits:    # bit planes: from the outputs straight into the slots
         batch.bitunshuffle_outputs([p if i in bits else None for i, p in enumerate(at)], widths, blocks)
+    if packed:  # packed fields: from the outputs straight into the slots, which are larger than the outputs
+        batch.bitunpack_outputs([p if i in packed else None for i, p in enumerate(at)], [k for k, _ in packs], widths,
+                                [_numel(s[3]) if s is not None else 0 for s in slots], [f for _, f in packs])
     if plain:   # deltas only: from the outputs straight into the slots
         batch.undelta_outputs([p if i in plain else None for i, p in enumerate(at)], widths)
-    both = [i for i, s in enumerate(slots) if s is not None and ("shuffle" in filters[i] or "bitshuffle" in filters[i]) and "delta" in filters[i]]
+    both = [i for i, s in enumerate(slots) if s is not None and ("shuffle" in filters[i] or "bitshuffle" in filters[i] or "bitpack" in filters[i]) and "delta" in filters[i]]
     if both:    # in place over the slots, which are 64-byte aligned
         batch.undelta_segments([at[i] for i in both], [at[i] for i in both], [slots[i][1] for i in both], [widths[i] for i in both])
     return [None if s is None else buf[s[0]:s[0] + s[1]].view(s[2]).reshape(s[3]) for s in slots]

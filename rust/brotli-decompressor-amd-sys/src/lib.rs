@@ -148,6 +148,9 @@ pub const BROTLI_AMD_BATCH_EAGER_OUTPUT_LIMIT: u32 = 64;
 /// batch.h: the digest kinds -- CRC-32 (0xEDB88320: zlib, gzip, PNG, Parquet pages) and CRC-32C (0x82F63B78, Castagnoli)
 pub const BROTLI_AMD_DIGEST_CRC32: u32 = 1;
 pub const BROTLI_AMD_DIGEST_CRC32C: u32 = 2;
+/// flags of a bit-unpack segment: the first bit of a field is the value's highest; the value is sign-extended
+pub const BROTLI_AMD_BITUNPACK_MSB_FIRST: u8 = 1;
+pub const BROTLI_AMD_BITUNPACK_SIGNED: u8 = 2;
 
 extern "C" {
     pub fn BrotliAmdBatchCreate(max_streams: u32, lds_arena_bytes: u32, grid_blocks: u32) -> *mut BrotliAmdBatch;
@@ -238,6 +241,26 @@ extern "C" {
     pub fn BrotliAmdDebugBitUnshuffleTile() -> u32;
     pub fn BrotliAmdDebugBitUnshuffleHost(
         width: u32, block_elems: u32, src: *const u8, len: size_t, dst: *mut u8, src_skew: u32, dst_skew: u32, fast_items: *mut u64,
+    ) -> c_int;
+    /// fixed-width bit packing undone (this file stays uncompiled source: no Rust toolchain was at hand): `n` segments of DEVICE memory (any
+    /// alignment, any count), the first `counts[i]` fields of `bits[i]` bits (1 ..= 8 * `widths[i]`) of the `src_lens[i]` bytes at `d_src[i]` into
+    /// elements of `widths[i]` bytes (1, 2, 4, 8) at `d_dst[i]`, by `flags[i]` (`BROTLI_AMD_BITUNPACK_*`; a NULL array: all 0), out of place, in one
+    /// launch on `hip_stream`; waits
+    pub fn BrotliAmdBatchBitUnpackSegments(
+        batch: *mut BrotliAmdBatch, n: u32, d_src: *const *const c_void, src_lens: *const size_t, d_dst: *const *mut c_void, counts: *const u64,
+        bits: *const u8, widths: *const u8, flags: *const u8, hip_stream: *mut c_void,
+    ) -> c_int;
+    /// the same for the delivered bytes of every stream of the last decode call on the object (after `BrotliAmdBatchWait` for a device call);
+    /// a NULL `d_dst[i]` skips stream i; a NULL `counts`: as many whole fields as each stream delivered
+    pub fn BrotliAmdBatchBitUnpackOutputs(
+        batch: *mut BrotliAmdBatch, d_dst: *const *mut c_void, counts: *const u64, bits: *const u8, widths: *const u8, flags: *const u8,
+    ) -> c_int;
+    pub fn BrotliAmdBatchLastBitUnpackMs(batch: *mut BrotliAmdBatch) -> f32;
+    /// test hooks (no device needed)
+    pub fn BrotliAmdDebugBitUnpackTile() -> u32;
+    pub fn BrotliAmdDebugBitUnpackHost(
+        bits: u32, width: u32, flags: u32, src: *const u8, src_len: size_t, count: u64, dst: *mut u8, src_skew: u32, dst_skew: u32,
+        fast_items: *mut u64,
     ) -> c_int;
     pub fn BrotliAmdLastError() -> *const c_char;
     pub fn BrotliAmdLastNote() -> *const c_char;
