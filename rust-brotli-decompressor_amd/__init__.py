@@ -162,37 +162,29 @@ def load_library():
         L.BrotliAmdDebugDigestHost.argtypes = [u32, vp, sz, u32, u32]
         L.BrotliAmdDebugDigestShift.restype = u32
         L.BrotliAmdDebugDigestShift.argtypes = [u32, u32, ctypes.c_uint64]
-    if hasattr(L, "BrotliAmdBatchUnshuffleSegments"):   # (unshuffle: an older build of the library, loaded for an A/B, has none)
-        L.BrotliAmdBatchUnshuffleSegments.argtypes = [vp, u32, vp, vp, vp, vp, vp]
-        L.BrotliAmdBatchUnshuffleOutputs.argtypes = [vp, vp, vp]
-        L.BrotliAmdBatchLastUnshuffleMs.restype = ctypes.c_float
-        L.BrotliAmdBatchLastUnshuffleMs.argtypes = [vp]
-        L.BrotliAmdDebugUnshuffleTile.restype = u32
-        L.BrotliAmdDebugUnshuffleHost.argtypes = [u32, vp, sz, vp, u32, u32]
-    if hasattr(L, "BrotliAmdBatchUndeltaSegments"):   # (undelta: an older build of the library, loaded for an A/B, has none)
-        L.BrotliAmdBatchUndeltaSegments.argtypes = [vp, u32, vp, vp, vp, vp, vp]
-        L.BrotliAmdBatchUndeltaOutputs.argtypes = [vp, vp, vp]
-        L.BrotliAmdBatchLastUndeltaMs.restype = ctypes.c_float
-        L.BrotliAmdBatchLastUndeltaMs.argtypes = [vp]
-        L.BrotliAmdBatchLastUndeltaPhaseMs.restype = ctypes.c_float
-        L.BrotliAmdBatchLastUndeltaPhaseMs.argtypes = [vp, u32]
-        L.BrotliAmdDebugUndeltaTile.restype = u32
-        L.BrotliAmdDebugUndeltaCarrySpan.restype = u32
-        L.BrotliAmdDebugUndeltaHost.argtypes = [u32, vp, sz, vp, sz, vp, vp, vp, vp, u32, u32, u32, u32, ctypes.c_int]
-    if hasattr(L, "BrotliAmdBatchBitUnshuffleSegments"):   # (bit-unshuffle: an older build of the library, loaded for an A/B, has none)
-        L.BrotliAmdBatchBitUnshuffleSegments.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp]
-        L.BrotliAmdBatchBitUnshuffleOutputs.argtypes = [vp, vp, vp, vp]
-        L.BrotliAmdBatchLastBitUnshuffleMs.restype = ctypes.c_float
-        L.BrotliAmdBatchLastBitUnshuffleMs.argtypes = [vp]
-        L.BrotliAmdDebugBitUnshuffleTile.restype = u32
-        L.BrotliAmdDebugBitUnshuffleHost.argtypes = [u32, u32, vp, sz, vp, u32, u32, vp]
-    if hasattr(L, "BrotliAmdBatchBitUnpackSegments"):   # (bit-unpack: an older build of the library, loaded for an A/B, has none)
-        L.BrotliAmdBatchBitUnpackSegments.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.BrotliAmdBatchBitUnpackOutputs.argtypes = [vp, vp, vp, vp, vp, vp]
-        L.BrotliAmdBatchLastBitUnpackMs.restype = ctypes.c_float
-        L.BrotliAmdBatchLastBitUnpackMs.argtypes = [vp]
-        L.BrotliAmdDebugBitUnpackTile.restype = u32
-        L.BrotliAmdDebugBitUnpackHost.argtypes = [u32, u32, u32, vp, sz, ctypes.c_uint64, vp, u32, u32, vp]
+    # the element filters, name -> (restype, argtypes), None where ctypes' default stands.  A filter is there or not as a whole: an older build of
+    # the library, loaded for an A/B, has those of its time
+    f32, u64 = ctypes.c_float, ctypes.c_uint64
+    for protos in (
+            {"BrotliAmdBatchUnshuffleSegments": (None, [vp, u32, vp, vp, vp, vp, vp]), "BrotliAmdBatchUnshuffleOutputs": (None, [vp, vp, vp]),
+             "BrotliAmdBatchLastUnshuffleMs": (f32, [vp]), "BrotliAmdDebugUnshuffleTile": (u32, None),
+             "BrotliAmdDebugUnshuffleHost": (None, [u32, vp, sz, vp, u32, u32])},
+            {"BrotliAmdBatchUndeltaSegments": (None, [vp, u32, vp, vp, vp, vp, vp]), "BrotliAmdBatchUndeltaOutputs": (None, [vp, vp, vp]),
+             "BrotliAmdBatchLastUndeltaMs": (f32, [vp]), "BrotliAmdBatchLastUndeltaPhaseMs": (f32, [vp, u32]), "BrotliAmdDebugUndeltaTile": (u32, None),
+             "BrotliAmdDebugUndeltaCarrySpan": (u32, None),
+             "BrotliAmdDebugUndeltaHost": (None, [u32, vp, sz, vp, sz, vp, vp, vp, vp, u32, u32, u32, u32, ctypes.c_int])},
+            {"BrotliAmdBatchBitUnshuffleSegments": (None, [vp, u32, vp, vp, vp, vp, vp, vp]), "BrotliAmdBatchBitUnshuffleOutputs": (None, [vp, vp, vp, vp]),
+             "BrotliAmdBatchLastBitUnshuffleMs": (f32, [vp]), "BrotliAmdDebugBitUnshuffleTile": (u32, None),
+             "BrotliAmdDebugBitUnshuffleHost": (None, [u32, u32, vp, sz, vp, u32, u32, vp])},
+            {"BrotliAmdBatchBitUnpackSegments": (None, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]), "BrotliAmdBatchBitUnpackOutputs": (None, [vp, vp, vp, vp, vp, vp]),
+             "BrotliAmdBatchLastBitUnpackMs": (f32, [vp]), "BrotliAmdDebugBitUnpackTile": (u32, None),
+             "BrotliAmdDebugBitUnpackHost": (None, [u32, u32, u32, vp, sz, u64, vp, u32, u32, vp])}):
+        if hasattr(L, next(iter(protos))):
+            for name, (restype, argtypes) in protos.items():
+                if restype is not None:
+                    getattr(L, name).restype = restype
+                if argtypes is not None:
+                    getattr(L, name).argtypes = argtypes
     if hasattr(L, "BrotliAmdDebugSegWalkParts"):   # (the segment walk's host model: an older build of the library, loaded for an A/B, has none)
         L.BrotliAmdDebugSegWalkParts.restype = ctypes.c_uint64
         L.BrotliAmdDebugSegWalkParts.argtypes = [u32, vp, u32, u32, vp, ctypes.c_uint64]
@@ -571,27 +563,39 @@ class Batch:
         """milliseconds the digest kernel took in the last digest_segments / digest_outputs"""
         return float(self._L.BrotliAmdBatchLastDigestMs(self._h))
 
-    def _width_segments(self, name, src_ptrs, dst_ptrs, lens, widths, stream):
-        """BrotliAmdBatch<name>Segments over the caller's segments"""
-        n = len(src_ptrs)
-        if len(dst_ptrs) != n or len(lens) != n or len(widths) != n:
-            raise ValueError("src_ptrs, dst_ptrs, lens and widths: one entry per segment each")
-        a_s = (ctypes.c_void_p * max(1, n))(*src_ptrs)
-        a_d = (ctypes.c_void_p * max(1, n))(*dst_ptrs)
-        a_l = (ctypes.c_size_t * max(1, n))(*lens)
-        a_w = (ctypes.c_uint8 * max(1, n))(*[w if 0 <= w <= 255 else 0 for w in widths])
-        if getattr(self._L, name)(self._h, n, a_s, a_d, a_l, a_w, stream) != 0:
+    @staticmethod
+    def _column(ctype, values, n, bad=None, what=None):
+        """one of a filter call's parallel arrays: n values of a ctypes type, or None where the call takes NULL for "all 0".  what: the ValueError
+        text for a column that has not n entries.  bad: what stands in for a value the C type cannot hold -- a value the call refuses, or,
+        where there is none, the type's largest, so that it is refused as that is"""
+        if values is None:
+            return None
+        if what is not None and len(values) != n:
+            raise ValueError(what)
+        if bad is not None:
+            top = (1 << 8 * ctypes.sizeof(ctype)) - 1
+            values = [v if 0 <= v <= top else bad for v in values]
+        return (ctype * max(1, n))(*values)
+
+    def _filter_call(self, name, *args):
+        if getattr(self._L, name)(self._h, *args) != 0:
             raise RuntimeError(name + " failed: " + last_error())
 
-    def _width_outputs(self, name, dst_ptrs, widths):
+    def _width_segments(self, name, src_ptrs, dst_ptrs, lens, widths, stream, *blocks):
+        """BrotliAmdBatch<name>Segments over the caller's segments (blocks: bit-unshuffle's one more column)"""
+        n, col = len(src_ptrs), self._column
+        if len(dst_ptrs) != n or len(lens) != n or len(widths) != n:
+            raise ValueError("src_ptrs, dst_ptrs, lens and widths: one entry per segment each")
+        self._filter_call(name, n, col(ctypes.c_void_p, src_ptrs, n), col(ctypes.c_void_p, dst_ptrs, n), col(ctypes.c_size_t, lens, n),
+                          col(ctypes.c_uint8, widths, n, 0), *[self._block_column(b, n) for b in blocks], stream)
+
+    def _width_outputs(self, name, dst_ptrs, widths, *blocks):
         """BrotliAmdBatch<name>Outputs over the streams of the last decode call"""
-        n = self.out_n
+        n, col = self.out_n, self._column
         if len(dst_ptrs) != n or len(widths) != n:
             raise ValueError("dst_ptrs and widths: one entry per stream of the last decode call each")
-        a_d = (ctypes.c_void_p * max(1, n))(*[p or None for p in dst_ptrs])
-        a_w = (ctypes.c_uint8 * max(1, n))(*[w if 0 <= w <= 255 else 0 for w in widths])
-        if getattr(self._L, name)(self._h, a_d, a_w) != 0:
-            raise RuntimeError(name + " failed: " + last_error())
+        self._filter_call(name, col(ctypes.c_void_p, [p or None for p in dst_ptrs], n), col(ctypes.c_uint8, widths, n, 0),
+                          *[self._block_column(b, n) for b in blocks])
 
     def unshuffle_segments(self, src_ptrs, dst_ptrs, lens, widths, stream=None):
         """BrotliAmdBatchUnshuffleSegments: lens[i] bytes of byte planes at the device address src_ptrs[i] become elements of widths[i] bytes
@@ -626,76 +630,48 @@ class Batch:
             return float(self._L.BrotliAmdBatchLastUndeltaMs(self._h))
         return float(self._L.BrotliAmdBatchLastUndeltaPhaseMs(self._h, phase))
 
-    @staticmethod
-    def _block_array(blocks, n):
+    def _block_column(self, blocks, n):
         """block sizes as the C calls take them: None (all 0), or n of them"""
-        if blocks is None:
-            return None
-        if len(blocks) != n:
-            raise ValueError("blocks: one entry per segment or stream, or None")
-        return (ctypes.c_uint32 * max(1, n))(*[b if 0 <= b < (1 << 32) else 1 for b in blocks])   # (1: no multiple of 8, so it is refused)
+        return self._column(ctypes.c_uint32, blocks, n, 1, "blocks: one entry per segment or stream, or None")   # (1: no multiple of 8, so it is refused)
 
     def bitunshuffle_segments(self, src_ptrs, dst_ptrs, lens, widths, blocks=None, stream=None):
         """BrotliAmdBatchBitUnshuffleSegments: lens[i] bytes of bit planes at the device address src_ptrs[i] become elements of widths[i] bytes
         (1, 2, 4, 8), in blocks of blocks[i] elements (0: one block; None: all 0), at dst_ptrs[i]; any alignment, any length; out of place.
         One launch and a wait on `stream`."""
-        n = len(src_ptrs)
-        if len(dst_ptrs) != n or len(lens) != n or len(widths) != n:
-            raise ValueError("src_ptrs, dst_ptrs, lens and widths: one entry per segment each")
-        a_s = (ctypes.c_void_p * max(1, n))(*src_ptrs)
-        a_d = (ctypes.c_void_p * max(1, n))(*dst_ptrs)
-        a_l = (ctypes.c_size_t * max(1, n))(*lens)
-        a_w = (ctypes.c_uint8 * max(1, n))(*[w if 0 <= w <= 255 else 0 for w in widths])
-        if self._L.BrotliAmdBatchBitUnshuffleSegments(self._h, n, a_s, a_d, a_l, a_w, self._block_array(blocks, n), stream) != 0:
-            raise RuntimeError("BrotliAmdBatchBitUnshuffleSegments failed: " + last_error())
+        self._width_segments("BrotliAmdBatchBitUnshuffleSegments", src_ptrs, dst_ptrs, lens, widths, stream, blocks)
 
     def bitunshuffle_outputs(self, dst_ptrs, widths, blocks=None):
         """BrotliAmdBatchBitUnshuffleOutputs: the delivered bytes of every stream of the last decode call on this object (after decode_device:
         once wait() has returned), taken as bit planes of widths[i] in blocks of blocks[i] elements, become elements at the device address
         dst_ptrs[i] (None or 0: the stream is skipped).  One launch on that call's stream, and a wait."""
-        n = self.out_n
-        if len(dst_ptrs) != n or len(widths) != n:
-            raise ValueError("dst_ptrs and widths: one entry per stream of the last decode call each")
-        a_d = (ctypes.c_void_p * max(1, n))(*[p or None for p in dst_ptrs])
-        a_w = (ctypes.c_uint8 * max(1, n))(*[w if 0 <= w <= 255 else 0 for w in widths])
-        if self._L.BrotliAmdBatchBitUnshuffleOutputs(self._h, a_d, a_w, self._block_array(blocks, n)) != 0:
-            raise RuntimeError("BrotliAmdBatchBitUnshuffleOutputs failed: " + last_error())
+        self._width_outputs("BrotliAmdBatchBitUnshuffleOutputs", dst_ptrs, widths, blocks)
 
-    @staticmethod
-    def _byte_array(values, n, what, bad=255):
+    def _byte_column(self, values, n, what, bad=255):
         """small parameters as the C calls take them: n bytes; what no byte holds becomes `bad`, which the call refuses"""
-        if len(values) != n:
-            raise ValueError(what + ": one entry per segment or stream")
-        return (ctypes.c_uint8 * max(1, n))(*[v if 0 <= v <= 255 else bad for v in values])
+        return self._column(ctypes.c_uint8, values, n, bad, what + ": one entry per segment or stream")
 
     def bitunpack_segments(self, src_ptrs, src_lens, dst_ptrs, counts, bits, widths, flags=None, stream=None):
         """BrotliAmdBatchBitUnpackSegments: the first counts[i] fields of bits[i] bits (1 .. 8 widths[i]) of the src_lens[i] bytes at the device
         address src_ptrs[i] become counts[i] elements of widths[i] bytes (1, 2, 4, 8) at dst_ptrs[i], by flags[i] (BITUNPACK_MSB_FIRST,
         BITUNPACK_SIGNED; None: all 0); any alignment, any count; out of place.  One launch and a wait on `stream`."""
-        n = len(src_ptrs)
+        n, col = len(src_ptrs), self._column
         if len(src_lens) != n or len(dst_ptrs) != n or len(counts) != n:
             raise ValueError("src_ptrs, src_lens, dst_ptrs and counts: one entry per segment each")
-        a_s = (ctypes.c_void_p * max(1, n))(*src_ptrs)
-        a_l = (ctypes.c_size_t * max(1, n))(*src_lens)
-        a_d = (ctypes.c_void_p * max(1, n))(*dst_ptrs)
-        a_c = (ctypes.c_uint64 * max(1, n))(*[c if 0 <= c < (1 << 64) else (1 << 64) - 1 for c in counts])
-        a_f = None if flags is None else self._byte_array(flags, n, "flags")
-        if self._L.BrotliAmdBatchBitUnpackSegments(self._h, n, a_s, a_l, a_d, a_c, self._byte_array(bits, n, "bits"), self._byte_array(widths, n, "widths", 0),
-                                                   a_f, stream) != 0:
-            raise RuntimeError("BrotliAmdBatchBitUnpackSegments failed: " + last_error())
+        a_s, a_l, a_d = col(ctypes.c_void_p, src_ptrs, n), col(ctypes.c_size_t, src_lens, n), col(ctypes.c_void_p, dst_ptrs, n)
+        a_c, a_f = col(ctypes.c_uint64, counts, n, (1 << 64) - 1), self._byte_column(flags, n, "flags")
+        self._filter_call("BrotliAmdBatchBitUnpackSegments", n, a_s, a_l, a_d, a_c, self._byte_column(bits, n, "bits"), self._byte_column(widths, n, "widths", 0),
+                          a_f, stream)
 
     def bitunpack_outputs(self, dst_ptrs, bits, widths, counts=None, flags=None):
         """BrotliAmdBatchBitUnpackOutputs: the delivered bytes of every stream of the last decode call on this object (after decode_device: once
         wait() has returned), taken as fields of bits[i] bits, become counts[i] elements of widths[i] bytes at the device address dst_ptrs[i]
         (None or 0: the stream is skipped); counts=None: as many whole fields as were delivered.  One launch on that call's stream, and a wait."""
-        n = self.out_n
+        n, col = self.out_n, self._column
         if len(dst_ptrs) != n or (counts is not None and len(counts) != n):
             raise ValueError("dst_ptrs and counts: one entry per stream of the last decode call each")
-        a_d = (ctypes.c_void_p * max(1, n))(*[p or None for p in dst_ptrs])
-        a_c = None if counts is None else (ctypes.c_uint64 * max(1, n))(*[c if 0 <= c < (1 << 64) else (1 << 64) - 1 for c in counts])
-        a_f = None if flags is None else self._byte_array(flags, n, "flags")
-        if self._L.BrotliAmdBatchBitUnpackOutputs(self._h, a_d, a_c, self._byte_array(bits, n, "bits"), self._byte_array(widths, n, "widths", 0), a_f) != 0:
-            raise RuntimeError("BrotliAmdBatchBitUnpackOutputs failed: " + last_error())
+        a_d, a_c = col(ctypes.c_void_p, [p or None for p in dst_ptrs], n), col(ctypes.c_uint64, counts, n, (1 << 64) - 1)
+        a_f = self._byte_column(flags, n, "flags")
+        self._filter_call("BrotliAmdBatchBitUnpackOutputs", a_d, a_c, self._byte_column(bits, n, "bits"), self._byte_column(widths, n, "widths", 0), a_f)
 
     def last_bitunpack_ms(self):
         """milliseconds the bit-unpack kernel took in the last bitunpack_segments / bitunpack_outputs"""

@@ -425,8 +425,9 @@ extern "C" void BrotliAmdBatchDestroy(BrotliAmdBatch* b) {
   else (void)hipDeviceSynchronize();
   if (b->copy_stream) (void)hipStreamDestroy(b->copy_stream);
   for (hipEvent_t ev : {b->ev0, b->ev1, b->ev2, b->ev3}) if (ev) (void)hipEventDestroy(ev);
-  for (SegCall* c : {&b->digest, &b->unshuffle, &b->undelta, &b->bitunshuffle, &b->bitunpack})
-    for (hipEvent_t ev : c->ev) if (ev) (void)hipEventDestroy(ev);
+  for (hipEvent_t ev : b->digest.ev) if (ev) (void)hipEventDestroy(ev);
+  for (BrotliAmdBatch::FilterCall& f : b->filter)
+    for (hipEvent_t ev : f.call.ev) if (ev) (void)hipEventDestroy(ev);
   delete b;
 }
 

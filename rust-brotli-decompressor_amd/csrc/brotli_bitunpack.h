@@ -32,7 +32,7 @@
 // LOADS.  Single bytes of [src, src + ceil(m k / 8)), and aligned dwords that hold one of them.  STORES.  One aligned 16-byte store where the
 // segment covers the word; at the segment's first and last word the edge store of csrc/brotli_seg_walk.h -- never a read-modify-write.
 //
-// One set of functions for the host (csrc/brotli_bitunpack.cpp: BrotliAmdDebugBitUnpackHost; tests/tools/bitunpack_san.cpp) and the device
+// One set of functions for the host (csrc/brotli_filters.cpp: BrotliAmdDebugBitUnpackHost; tests/tools/bitunpack_san.cpp) and the device
 // (csrc/brotli_bitunpack_kernels.hip).  Addresses are integers.
 #ifndef BROTLI_AMD_BITUNPACK_H_
 #define BROTLI_AMD_BITUNPACK_H_
@@ -64,7 +64,7 @@ BROTLI_AMD_BITUNPACK_HD constexpr bool brotli_amd_bitunpack_shape_ok(uint32_t k,
 }
 // the source bytes that m fields of k bits are read from (m <= BROTLI_AMD_BITUNPACK_MAX_COUNT)
 BROTLI_AMD_BITUNPACK_HD constexpr uint64_t brotli_amd_bitunpack_src_bytes(uint64_t m, uint32_t k) { return (m * k + 7u) >> 3; }
-// what a segment table's `reserved` holds: k | flags << 8
+// what a segment table's `param` holds: k | flags << 8
 BROTLI_AMD_BITUNPACK_HD constexpr uint32_t brotli_amd_bitunpack_param(uint32_t k, uint32_t flags) { return k | flags << 8; }
 
 // THE DECISION: the kind of unit u of a segment of m elements of width w at dst.  FIRST: *i0 is the item's first element.

@@ -18,7 +18,7 @@
 
 namespace {
 
-constexpr uint32_t kThreads = BROTLI_AMD_SEG_THREADS, kChunkSegs = BROTLI_AMD_SEG_CHUNK_SEGS;
+constexpr uint32_t kThreads = BROTLI_AMD_SEG_THREADS;
 constexpr uint32_t kUnitsPerThread = 16;
 constexpr uint32_t kTileUnits = kThreads * kUnitsPerThread;
 
@@ -33,39 +33,24 @@ struct TileItems {
   }
 };
 
+// (both callables always_inline, as the shell's part is: the 120 items make them too large for the inliner's liking, and a call would need a stack)
 __global__ __launch_bounds__(kThreads) void brotli_amd_bitunpack_kernel(const BrotliAmdUnshuffleSeg* __restrict__ segs, uint32_t n) {
-  __shared__ uint64_t pre[kChunkSegs + 1];   // units in front of each segment of the chunk (in front of the chunk included); [kChunkSegs]: behind its last
-  __shared__ uint64_t scan[kThreads];
-  const uint32_t tid = threadIdx.x;
-  brotli_amd_seg_walk<kTileUnits>(segs, n, pre, scan, [](const BrotliAmdUnshuffleSeg& sg) { return sg.dst; },
-                                  [&](const uint64_t* pre, const BrotliAmdUnshuffleSeg* segs, uint32_t, uint64_t lo, uint64_t hi, uint64_t t0, uint64_t)
-                                      __attribute__((always_inline)) {   // (the 120 items make it too large for the inliner's liking: a call would need a stack)
-    const uint32_t ja = brotli_amd_seg_find(pre, kChunkSegs, lo), jb = brotli_amd_seg_find(pre, kChunkSegs, hi - 1u);
-    if (ja == jb) {   // one segment's: the rule for a long one
-      const BrotliAmdUnshuffleSeg sg = segs[ja];
-      const uint64_t src = (uint64_t)(uintptr_t)sg.src, dst = (uint64_t)(uintptr_t)sg.dst;
-      const uint32_t w = sg.width, k = sg.reserved & 0xFFu, flags = sg.reserved >> 8;
-      if (!brotli_amd_bitunpack_shape_ok(k, w, flags)) return;   // (the host lets no other shape through)
-      const uint32_t LOG = brotli_amd_bitunpack_log(w);
-      const uint64_t m = sg.len >> LOG, ka = lo - pre[ja], kb = hi - pre[ja];
-      // the words that are no item's first: all of them where the destination is not aligned, those behind the whole groups of 32 elsewhere
-      const bool items = (dst & 15u) == 0u;
-      const uint64_t tail = ((m & ~(uint64_t)(BROTLI_AMD_BITUNPACK_ITEM_ELEMS - 1u)) << LOG) >> 4;
-      for (uint64_t u = (items && tail > ka ? tail : ka) + tid; u < kb; u += kThreads) brotli_amd_bitunpack_slow_words(src, dst, m, w, k, flags, u, u + 1u);
-      if (items) brotli_amd_bitunpack_for_wk(w, k, TileItems{src, dst, m, flags, ka, kb < tail ? kb : tail, tid});
-    } else {
-      for (uint32_t it = 0; it < kUnitsPerThread; it++) {
-        const uint64_t g = t0 + it * kThreads + tid;
-        if (g >= lo && g < hi) {
-          const uint32_t j = brotli_amd_seg_find(pre, kChunkSegs, g);
-          const BrotliAmdUnshuffleSeg sg = segs[j];
-          const uint32_t w = sg.width;
-          const uint64_t first = pre[j], end = pre[j + 1u];
-          brotli_amd_bitunpack_word_alone((uint64_t)(uintptr_t)sg.src, (uint64_t)(uintptr_t)sg.dst, sg.len >> brotli_amd_bitunpack_log(w), w, sg.reserved & 0xFFu,
-                                          sg.reserved >> 8, g - first, (lo > first ? lo : first) - first, (hi < end ? hi : end) - first);
-        }
-      }
-    }
+  brotli_amd_seg_dst_kernel<kUnitsPerThread>(segs, n, [](const BrotliAmdUnshuffleSeg& sg, uint64_t first, uint64_t lo, uint64_t hi, uint64_t, uint32_t tid)
+                                                          __attribute__((always_inline)) {
+    const uint64_t src = (uint64_t)(uintptr_t)sg.src, dst = (uint64_t)(uintptr_t)sg.dst;
+    const uint32_t w = sg.width, k = sg.param & 0xFFu, flags = sg.param >> 8;
+    if (!brotli_amd_bitunpack_shape_ok(k, w, flags)) return;   // (the host lets no other shape through)
+    const uint32_t LOG = brotli_amd_bitunpack_log(w);
+    const uint64_t m = sg.len >> LOG, ka = lo - first, kb = hi - first;
+    // the words that are no item's first: all of them where the destination is not aligned, those behind the whole groups of 32 elsewhere
+    const bool items = (dst & 15u) == 0u;
+    const uint64_t tail = ((m & ~(uint64_t)(BROTLI_AMD_BITUNPACK_ITEM_ELEMS - 1u)) << LOG) >> 4;
+    for (uint64_t u = (items && tail > ka ? tail : ka) + tid; u < kb; u += kThreads) brotli_amd_bitunpack_slow_words(src, dst, m, w, k, flags, u, u + 1u);
+    if (items) brotli_amd_bitunpack_for_wk(w, k, TileItems{src, dst, m, flags, ka, kb < tail ? kb : tail, tid});
+  }, [](const BrotliAmdUnshuffleSeg& sg, uint64_t first, uint64_t end, uint64_t g, uint64_t lo, uint64_t hi) __attribute__((always_inline)) {
+    const uint32_t w = sg.width;
+    brotli_amd_bitunpack_word_alone((uint64_t)(uintptr_t)sg.src, (uint64_t)(uintptr_t)sg.dst, sg.len >> brotli_amd_bitunpack_log(w), w, sg.param & 0xFFu,
+                                    sg.param >> 8, g - first, (lo > first ? lo : first) - first, (hi < end ? hi : end) - first);
   });
 }
 
@@ -73,12 +58,6 @@ __global__ __launch_bounds__(kThreads) void brotli_amd_bitunpack_kernel(const Br
 
 extern "C" uint32_t brotli_amd_bitunpack_tile_bytes(void) { return BROTLI_AMD_BITUNPACK_TILE_BYTES; }
 
-// units: the units of all segments together (brotli_amd_seg_units: the host has the table)
 extern "C" hipError_t brotli_amd_launch_bitunpack(const BrotliAmdUnshuffleSeg* d_segs, uint32_t n, uint64_t units, hipStream_t stream) {
-  if (n == 0u || units == 0u) return hipSuccess;
-  uint32_t grid = 0;
-  const hipError_t e = brotli_amd_seg_grid(units, kTileUnits, &grid);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(brotli_amd_bitunpack_kernel, dim3(grid), dim3(kThreads), 0, stream, d_segs, n);
-  return hipGetLastError();
+  return brotli_amd_seg_launch(brotli_amd_bitunpack_kernel, kTileUnits, d_segs, n, units, stream);
 }

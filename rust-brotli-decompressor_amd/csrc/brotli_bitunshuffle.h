@@ -29,7 +29,7 @@
 // LOADS.  Single bytes of [src, src + len), and aligned dwords that hold one.  STORES.  One aligned 16-byte store where the segment covers the
 // word; at the segment's first and last word the edge store of csrc/brotli_seg_walk.h -- never a read-modify-write.
 //
-// One set of functions for the host (csrc/brotli_bitunshuffle.cpp: BrotliAmdDebugBitUnshuffleHost; tests/tools/bitunshuffle_san.cpp) and the
+// One set of functions for the host (csrc/brotli_filters.cpp: BrotliAmdDebugBitUnshuffleHost; tests/tools/bitunshuffle_san.cpp) and the
 // device (csrc/brotli_bitunshuffle_kernels.hip).  Addresses are integers.
 #ifndef BROTLI_AMD_BITUNSHUFFLE_H_
 #define BROTLI_AMD_BITUNSHUFFLE_H_

@@ -16,7 +16,7 @@
 
 namespace {
 
-constexpr uint32_t kThreads = BROTLI_AMD_SEG_THREADS, kChunkSegs = BROTLI_AMD_SEG_CHUNK_SEGS;
+constexpr uint32_t kThreads = BROTLI_AMD_SEG_THREADS;
 constexpr uint32_t kUnitsPerThread = 16;
 constexpr uint32_t kTileUnits = kThreads * kUnitsPerThread;
 
@@ -28,37 +28,21 @@ template <uint32_t W>
 __device__ __forceinline__ void tile_of_one(const BrotliAmdUnshuffleSeg& sg, uint64_t first, uint64_t lo, uint64_t hi, uint32_t tid) {
   const uint64_t src = (uint64_t)(uintptr_t)sg.src, dst = (uint64_t)(uintptr_t)sg.dst;
   const uint64_t ka = lo - first, kb = hi - first;
-  for (uint64_t s = ka / (2u * W) + tid; 2u * W * s < kb; s += kThreads) (void)brotli_amd_bitunshuffle_slot_w<W>(src, dst, sg.len, sg.reserved, s, ka, kb);
+  for (uint64_t s = ka / (2u * W) + tid; 2u * W * s < kb; s += kThreads) (void)brotli_amd_bitunshuffle_slot_w<W>(src, dst, sg.len, sg.param, s, ka, kb);
 }
 
 __global__ __launch_bounds__(kThreads) void brotli_amd_bitunshuffle_kernel(const BrotliAmdUnshuffleSeg* __restrict__ segs, uint32_t n) {
-  __shared__ uint64_t pre[kChunkSegs + 1];   // units in front of each segment of the chunk (in front of the chunk included); [kChunkSegs]: behind its last
-  __shared__ uint64_t scan[kThreads];
-  const uint32_t tid = threadIdx.x;
-  brotli_amd_seg_walk<kTileUnits>(segs, n, pre, scan, [](const BrotliAmdUnshuffleSeg& sg) { return sg.dst; },
-                                  [&](const uint64_t* pre, const BrotliAmdUnshuffleSeg* segs, uint32_t, uint64_t lo, uint64_t hi, uint64_t t0, uint64_t) {
-    const uint32_t ja = brotli_amd_seg_find(pre, kChunkSegs, lo), jb = brotli_amd_seg_find(pre, kChunkSegs, hi - 1u);
-    if (ja == jb) {   // one segment's: the rule for a long one
-      const BrotliAmdUnshuffleSeg sg = segs[ja];
-      const uint64_t first = pre[ja];
-      switch (sg.width) {
-        case 1u: tile_of_one<1u>(sg, first, lo, hi, tid); break;
-        case 2u: tile_of_one<2u>(sg, first, lo, hi, tid); break;
-        case 4u: tile_of_one<4u>(sg, first, lo, hi, tid); break;
-        case 8u: tile_of_one<8u>(sg, first, lo, hi, tid); break;
-        default: break;   // (the host lets no other width through)
-      }
-    } else {
-      for (uint32_t it = 0; it < kUnitsPerThread; it++) {
-        const uint64_t g = t0 + it * kThreads + tid;
-        if (g >= lo && g < hi) {
-          const uint32_t j = brotli_amd_seg_find(pre, kChunkSegs, g);
-          const BrotliAmdUnshuffleSeg sg = segs[j];
-          const uint64_t k = g - pre[j];
-          (void)brotli_amd_bitunshuffle_range((uint64_t)(uintptr_t)sg.src, (uint64_t)(uintptr_t)sg.dst, sg.len, sg.width, sg.reserved, k, k + 1u);
-        }
-      }
+  brotli_amd_seg_dst_kernel<kUnitsPerThread>(segs, n, [](const BrotliAmdUnshuffleSeg& sg, uint64_t first, uint64_t lo, uint64_t hi, uint64_t, uint32_t tid) {
+    switch (sg.width) {
+      case 1u: tile_of_one<1u>(sg, first, lo, hi, tid); break;
+      case 2u: tile_of_one<2u>(sg, first, lo, hi, tid); break;
+      case 4u: tile_of_one<4u>(sg, first, lo, hi, tid); break;
+      case 8u: tile_of_one<8u>(sg, first, lo, hi, tid); break;
+      default: break;   // (the host lets no other width through)
     }
+  }, [](const BrotliAmdUnshuffleSeg& sg, uint64_t first, uint64_t, uint64_t g, uint64_t, uint64_t) {
+    const uint64_t k = g - first;
+    (void)brotli_amd_bitunshuffle_range((uint64_t)(uintptr_t)sg.src, (uint64_t)(uintptr_t)sg.dst, sg.len, sg.width, sg.param, k, k + 1u);
   });
 }
 
@@ -66,12 +50,6 @@ __global__ __launch_bounds__(kThreads) void brotli_amd_bitunshuffle_kernel(const
 
 extern "C" uint32_t brotli_amd_bitunshuffle_tile_bytes(void) { return BROTLI_AMD_BITUNSHUFFLE_TILE_BYTES; }
 
-// units: the units of all segments together (brotli_amd_seg_units: the host has the table)
 extern "C" hipError_t brotli_amd_launch_bitunshuffle(const BrotliAmdUnshuffleSeg* d_segs, uint32_t n, uint64_t units, hipStream_t stream) {
-  if (n == 0u || units == 0u) return hipSuccess;
-  uint32_t grid = 0;
-  const hipError_t e = brotli_amd_seg_grid(units, kTileUnits, &grid);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(brotli_amd_bitunshuffle_kernel, dim3(grid), dim3(kThreads), 0, stream, d_segs, n);
-  return hipGetLastError();
+  return brotli_amd_seg_launch(brotli_amd_bitunshuffle_kernel, kTileUnits, d_segs, n, units, stream);
 }

@@ -114,13 +114,14 @@ typedef struct BrotliAmdCopySeg {
 // One segment of an unshuffle launch (csrc/brotli_unshuffle_kernels.hip, csrc/brotli_unshuffle.h): the len bytes at src are `width` byte planes
 // (and len % width left-over bytes), the len bytes at dst become the elements; device addresses of any alignment, len 0 included, width 1, 2, 4
 // or 8.  No destination range overlaps a source range or another destination range.  Nothing outside [dst, dst + len) is written; nothing
-// outside the 16-byte-aligned span around [src, src + len) is read.
+// outside the 16-byte-aligned span around [src, src + len) is read.  `param` is the one parameter a filter has beside the width: 0 for unshuffle
+// and undelta, bit-unshuffle's block size, bit-unpack's field width and flags (below).
 typedef struct BrotliAmdUnshuffleSeg {
   const uint8_t* src;
   uint8_t* dst;
   uint64_t len;
   uint32_t width;
-  uint32_t reserved;
+  uint32_t param;
 } BrotliAmdUnshuffleSeg;
 #define BROTLI_AMD_UNSHUFFLE_TILE_BYTES 16384u  // destination bytes of one tile
 
@@ -129,13 +130,13 @@ typedef struct BrotliAmdUnshuffleSeg {
 #define BROTLI_AMD_UNDELTA_TILE_BYTES 16384u  // destination bytes: a tile's carry-in comes from the tiles in front of it
 
 // A bit-unshuffle launch (csrc/brotli_bitunshuffle_kernels.hip, csrc/brotli_bitunshuffle.h) takes the segments of an unshuffle launch too -- here
-// the len bytes at src are blocks of 8 `width` bit rows -- with the block size in elements in `reserved` (0: one block; otherwise a multiple of
+// the len bytes at src are blocks of 8 `width` bit rows -- with the block size in elements in `param` (0: one block; otherwise a multiple of
 // 8).  A fast item of that kernel is 2 `width` words, so its tile is larger: sixteen words a thread.
 #define BROTLI_AMD_BITUNSHUFFLE_TILE_BYTES 65536u  // destination bytes of one tile
 
 // A bit-unpack launch (csrc/brotli_bitunpack_kernels.hip, csrc/brotli_bitunpack.h) takes the segments of an unshuffle launch as well, with one
 // difference: `len` is the DESTINATION's bytes -- m elements of `width` bytes, m `width` --, and the units are the destination's; the source is
-// the ceil(m k / 8) bytes at src that hold m fields of k bits.  `reserved` is k | flags << 8 (k: 1 .. 8 `width`; flags: bit 0 MSB-first, bit 1
+// the ceil(m k / 8) bytes at src that hold m fields of k bits.  `param` is k | flags << 8 (k: 1 .. 8 `width`; flags: bit 0 MSB-first, bit 1
 // sign-extended).  A fast item of that kernel is 2 `width` words too, so it has the bit-unshuffle's tile: sixteen words a thread.
 #define BROTLI_AMD_BITUNPACK_TILE_BYTES 65536u  // destination bytes of one tile
 

@@ -79,9 +79,9 @@ extern "C" uint32_t BrotliAmdDebugDigestHost(uint32_t kind, const uint8_t* data,
   if (!known_kind(kind)) return 0;
   if ((n && !data) || skew > 15u) { g_last_error = "invalid digest arguments"; return 0; }
   if (run_units == 0u) run_units = BROTLI_AMD_CRC_RUN_UNITS;
-  std::vector<uint8_t> room(n + 64u, 0xA5);
-  const uint64_t at = (((uint64_t)(uintptr_t)room.data() + 15u) & ~(uint64_t)15) + 16u + skew;   // (a whole foreign word in front as well)
-  if (n) std::memcpy(reinterpret_cast<void*>((uintptr_t)at), data, n);
+  SkewedRoom room(n, skew, 0xA5);
+  room.put(data, n);
+  const uint64_t at = room.at();
   const uint32_t poly = brotli_amd_crc_poly(kind);
   const BrotliAmdCrcConsts& c = kConsts[kind - 1u];
   const auto load = [](uint64_t W, uint32_t* w) { std::memcpy(w, reinterpret_cast<const void*>((uintptr_t)W), 16); };

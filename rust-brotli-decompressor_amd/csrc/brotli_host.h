@@ -3,10 +3,10 @@
 //   brotli_staging.cpp  host buffers through staging arenas, size hints, the packed decode
 //   brotli_capi.cpp     the reference's C ABI (include/brotli/decode.h): error strings, one-shot, Prealloc, the streaming state
 //   brotli_stream_set.cpp  many streaming states in one launch, the ragged copy's debug hook
-//   brotli_seg_call.cpp  what the three calls below share: a call over a table of segments, the last decode call's outputs as segments
+//   brotli_seg_call.cpp  what the calls below share: the last decode call's outputs as segments, the segment walk's host model
 //   brotli_digest.cpp   CRC-32 / CRC-32C of segments of device memory and of the last decode call's outputs
-//   brotli_unshuffle.cpp  byte planes of segments of device memory, and of the last decode call's outputs, back into elements
-//   brotli_undelta.cpp  deltas of segments of device memory, and of the last decode call's outputs, back into values
+//   brotli_filters.cpp  the element filters -- unshuffle, undelta, bit-unshuffle, bit-unpack -- of segments of device memory and of the last
+//                       decode call's outputs: one descriptor a filter, one call, one pair of segment builders, the host hooks
 #ifndef BROTLI_AMD_HOST_H_
 #define BROTLI_AMD_HOST_H_
 #include <hip/hip_runtime.h>
@@ -111,6 +111,8 @@ struct SegCall {
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // around and between its launches (made at the first call, as many as it needs)
 };
 
+enum Filter : uint32_t { kUnshuffle, kUndelta, kBitUnshuffle, kBitUnpack, kFilters };   // the element filters (brotli_filters.cpp)
+
 constexpr size_t kReaderSlack = 256;   // behind every buffer the kernel reads a stream's bytes from, or writes them to, up to the buffer's end
 
 }  // namespace brotli_amd_host
@@ -172,18 +174,10 @@ struct BrotliAmdBatch {
   enum class Outputs : uint8_t { NoCall, Failed, None, InFlight, Waited } outputs = Outputs::NoCall;
   brotli_amd_host::SegCall digest;   // behind the table: the digests of one launch
   float digest_ms = 0.0f;
-  // unshuffle (brotli_unshuffle.cpp)
-  brotli_amd_host::SegCall unshuffle;
-  float unshuffle_ms = 0.0f;
-  // undelta (brotli_undelta.cpp)
-  brotli_amd_host::SegCall undelta;   // behind the table: the summaries and carries of its tiles
-  float undelta_ms = 0.0f, undelta_phase_ms[3] = {0.0f, 0.0f, 0.0f};
-  // bit-unshuffle (brotli_bitunshuffle.cpp)
-  brotli_amd_host::SegCall bitunshuffle;
-  float bitunshuffle_ms = 0.0f;
-  // bit-unpack (brotli_bitunpack.cpp)
-  brotli_amd_host::SegCall bitunpack;
-  float bitunpack_ms = 0.0f;
+  // the element filters (brotli_filters.cpp), by brotli_amd_host::Filter: each one's call -- behind undelta's table the summaries and carries of
+  // its tiles -- and the kernel time of its last call; undelta's three launches one by one
+  struct FilterCall { brotli_amd_host::SegCall call; float ms = 0.0f; } filter[brotli_amd_host::kFilters];
+  float undelta_phase_ms[3] = {0.0f, 0.0f, 0.0f};
 };
 
 namespace brotli_amd_host {
@@ -239,7 +233,7 @@ struct DeliveredBytes { const uint8_t* ptr; uint64_t len; };
 bool delivered_outputs(BrotliAmdBatch* b, std::vector<DeliveredBytes>* outs);
 void drop_packed(BrotliAmdBatch* b);   // a decode call ends the validity of the last packed call's output
 
-// ---- calls over a table of segments (brotli_seg_call.cpp): digests, unshuffle, undelta ----
+// ---- calls over a table of segments: the digests (brotli_digest.cpp) and the element filters (brotli_filters.cpp) ----
 struct SegCallWhat { const char* alloc; const char* upload; const char* wait; };   // what hip_ok says of a failed step
 // One call on `stream` (the object's device is current): room in c->d for the table, rounded up to 16 bytes, and `extra` bytes behind it; its
 // first nev events; the table's upload; then launch(uint8_t* table, uint8_t* what lies behind it, const hipEvent_t* events) -> all of it was queued.  The stream is waited
@@ -260,14 +254,32 @@ int run_seg_call(SegCall* c, const SegCallWhat& what, const void* table, size_t 
   for (uint32_t i = 0; gap_ms && i + 1u < nev; i++) (void)hipEventElapsedTime(&gap_ms[i], c->ev[i], c->ev[i + 1u]);
   return 0;
 }
-// The segments of an unshuffle or an undelta call, each checked by ok(source, destination, width) -- false: g_last_error says why -- in front of
-// everything that touches the device: from the caller's arrays, and from the delivered bytes of the last decode call's streams, where a NULL
-// destination skips the stream and its width is not looked at.
-typedef bool (*SegCheck)(const void* src, const void* dst, uint32_t width);
-bool width_segments(uint32_t n, const void* const* d_src, void* const* d_dst, const size_t* lens, const uint8_t* widths, SegCheck ok,
-                    std::vector<BrotliAmdUnshuffleSeg>* segs);
-bool width_segments_of_outputs(BrotliAmdBatch* b, void* const* d_dst, const uint8_t* widths, SegCheck ok, std::vector<BrotliAmdUnshuffleSeg>* segs);
-uint64_t width_segments_units(const std::vector<BrotliAmdUnshuffleSeg>& segs);   // the units of their destinations together (brotli_seg_walk.h)
+
+// `size` bytes placed `skew` past a 16-byte boundary in a room of this object's own, among bytes that are not theirs (whole foreign words in
+// front and behind as well): where the BrotliAmdDebug*Host hooks keep what the device's functions read and write on the host.
+class SkewedRoom {
+ public:
+  SkewedRoom(size_t size, uint32_t skew, uint8_t fill)
+      : room_(size + 64u, fill), at_((((uint64_t)(uintptr_t)room_.data() + 15u) & ~(uint64_t)15) + 16u + skew) {}
+  SkewedRoom(const SkewedRoom&) = delete;
+  SkewedRoom& operator=(const SkewedRoom&) = delete;
+  uint64_t at() const { return at_; }   // the address of the bytes
+  void put(const uint8_t* from, size_t n) { if (n) std::memcpy(reinterpret_cast<void*>((uintptr_t)at_), from, n); }
+  void get(uint8_t* to, size_t off, size_t n) const { if (n) std::memcpy(to, reinterpret_cast<const void*>((uintptr_t)(at_ + off)), n); }
+  void snapshot() { before_ = room_; }
+  // whether, since the snapshot, no byte of the room changed but bytes at offsets i past at() with inside(i)
+  template <class Inside>
+  bool changed_inside_only(Inside inside) const {
+    const size_t off = (size_t)(at_ - (uint64_t)(uintptr_t)room_.data());
+    for (size_t i = 0; i < room_.size(); i++)
+      if (room_[i] != before_[i] && (i < off || !inside(i - off))) return false;
+    return true;
+  }
+
+ private:
+  std::vector<uint8_t> room_, before_;
+  uint64_t at_;
+};
 
 }  // namespace brotli_amd_host
 #endif  // BROTLI_AMD_HOST_H_

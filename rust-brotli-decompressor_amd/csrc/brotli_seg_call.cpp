@@ -1,4 +1,4 @@
-// brotli_seg_call.cpp -- what the calls over a table of segments share on the host (brotli_digest.cpp, brotli_unshuffle.cpp, brotli_undelta.cpp):
+// brotli_seg_call.cpp -- what the calls over a table of segments share on the host (brotli_digest.cpp, brotli_filters.cpp):
 // the last decode call's outputs as segments (the call itself is run_seg_call in brotli_host.h), and the segment walk of csrc/brotli_seg_walk.h on the host, for tests without a device.
 #include "brotli_host.h"
 #include "brotli_seg_walk.h"
@@ -21,34 +21,6 @@ bool delivered_outputs(BrotliAmdBatch* b, std::vector<DeliveredBytes>* outs) {
     for (uint32_t i = 0; i < b->n; i++)
       outs->push_back(DeliveredBytes{b->h_descs[i].out, std::min<uint64_t>(b->h_status[i].decoded_size, b->h_descs[i].out_cap)});
   return true;
-}
-
-bool width_segments(uint32_t n, const void* const* d_src, void* const* d_dst, const size_t* lens, const uint8_t* widths, SegCheck ok,
-                    std::vector<BrotliAmdUnshuffleSeg>* segs) {
-  segs->clear();
-  for (uint32_t i = 0; i < n; i++) {
-    if (!ok(d_src[i], d_dst[i], widths[i])) return false;
-    segs->push_back(BrotliAmdUnshuffleSeg{static_cast<const uint8_t*>(d_src[i]), static_cast<uint8_t*>(d_dst[i]), lens[i], widths[i], 0u});
-  }
-  return true;
-}
-
-bool width_segments_of_outputs(BrotliAmdBatch* b, void* const* d_dst, const uint8_t* widths, SegCheck ok, std::vector<BrotliAmdUnshuffleSeg>* segs) {
-  segs->clear();
-  std::vector<DeliveredBytes> outs;
-  if (!delivered_outputs(b, &outs)) return false;
-  for (size_t i = 0; i < outs.size(); i++) {
-    if (d_dst[i] == nullptr) continue;   // (a stream the caller does not want: its width is not looked at)
-    if (!ok(outs[i].ptr, d_dst[i], widths[i])) return false;
-    segs->push_back(BrotliAmdUnshuffleSeg{outs[i].ptr, static_cast<uint8_t*>(d_dst[i]), outs[i].len, widths[i], 0u});
-  }
-  return true;
-}
-
-uint64_t width_segments_units(const std::vector<BrotliAmdUnshuffleSeg>& segs) {
-  uint64_t units = 0;
-  for (const BrotliAmdUnshuffleSeg& s : segs) units += brotli_amd_seg_units((uint64_t)(uintptr_t)s.dst, s.len);
-  return units;
 }
 
 }  // namespace brotli_amd_host

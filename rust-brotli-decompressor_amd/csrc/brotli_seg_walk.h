@@ -166,6 +166,51 @@ inline hipError_t brotli_amd_seg_grid(uint64_t units, uint32_t tile_units, uint3
   *grid = (uint32_t)g;
   return hipSuccess;
 }
+
+// ---- the shell of a kernel of ONE launch whose units are the words of DESTINATION memory (unshuffle, bit-unshuffle, bit-unpack) ----
+// The body of such a kernel of BROTLI_AMD_SEG_THREADS threads with tiles of kUnitsPerThread units a thread: the LDS of the walk, the walk over the
+// segments' dst, and each part split.  A part that lies inside one segment -- every tile of a long one -- is searched for once:
+// one_segment(sg, first, lo, hi, t0, tid), `first` being the segment's first unit.  Elsewhere a lane takes a word after a search each:
+// word_alone(sg, first, end, g, lo, hi) for unit g of the segment whose units are [first, end).  The part is always_inline, and so should a
+// callable be that is too large for the inliner's liking (bit-unpack's): a call would put a stack into scratch memory.
+template <uint32_t kUnitsPerThread, class Seg, class One, class Alone>
+__device__ __forceinline__ void brotli_amd_seg_dst_kernel(const Seg* __restrict__ segs, uint32_t n, One one_segment, Alone word_alone) {
+  constexpr uint32_t kThreads = BROTLI_AMD_SEG_THREADS, kChunkSegs = BROTLI_AMD_SEG_CHUNK_SEGS;
+  __shared__ uint64_t pre[kChunkSegs + 1];   // units in front of each segment of the chunk (in front of the chunk included); [kChunkSegs]: behind its last
+  __shared__ uint64_t scan[kThreads];
+  const uint32_t tid = threadIdx.x;
+  brotli_amd_seg_walk<kThreads * kUnitsPerThread>(segs, n, pre, scan, [](const Seg& sg) { return sg.dst; },
+                                                  [&](const uint64_t* pre, const Seg* segs, uint32_t, uint64_t lo, uint64_t hi, uint64_t t0, uint64_t)
+                                                      __attribute__((always_inline)) {
+    const uint32_t ja = brotli_amd_seg_find(pre, kChunkSegs, lo), jb = brotli_amd_seg_find(pre, kChunkSegs, hi - 1u);
+    if (ja == jb) {   // one segment's: the rule for a long one
+      const Seg sg = segs[ja];
+      one_segment(sg, pre[ja], lo, hi, t0, tid);
+    } else {
+      for (uint32_t it = 0; it < kUnitsPerThread; it++) {
+        const uint64_t g = t0 + it * kThreads + tid;
+        if (g >= lo && g < hi) {
+          const uint32_t j = brotli_amd_seg_find(pre, kChunkSegs, g);
+          const Seg sg = segs[j];
+          word_alone(sg, pre[j], pre[j + 1u], g, lo, hi);
+        }
+      }
+    }
+  });
+}
+
+// ... and its launch over `units` units (the units of all segments together: the host has the table -- a launch of a few short segments has a
+// few blocks, not a device full of blocks that find nothing to do)
+template <class Seg>
+inline hipError_t brotli_amd_seg_launch(void (*kernel)(const Seg*, uint32_t), uint32_t tile_units, const Seg* d_segs, uint32_t n, uint64_t units,
+                                        hipStream_t stream) {
+  if (n == 0u || units == 0u) return hipSuccess;
+  uint32_t grid = 0;
+  const hipError_t e = brotli_amd_seg_grid(units, tile_units, &grid);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(BROTLI_AMD_SEG_THREADS), 0, stream, d_segs, n);
+  return hipGetLastError();
+}
 #endif  // __HIPCC__
 
 #endif  // BROTLI_AMD_SEG_WALK_H_

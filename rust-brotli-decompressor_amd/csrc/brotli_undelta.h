@@ -33,7 +33,7 @@
 //      starts from carry_in) gives every unit its carry; finish.
 // Sums are kept in 64 bits and truncated to w bytes where they are used.
 //
-// One set of functions for the host (csrc/brotli_undelta.cpp: BrotliAmdDebugUndeltaHost; tests/tools/undelta_san.cpp) and the device
+// One set of functions for the host (csrc/brotli_filters.cpp: BrotliAmdDebugUndeltaHost; tests/tools/undelta_san.cpp) and the device
 // (csrc/brotli_undelta_kernels.hip); only the cross-lane running sum is the device's own.  Addresses are integers.
 #ifndef BROTLI_AMD_UNDELTA_H_
 #define BROTLI_AMD_UNDELTA_H_

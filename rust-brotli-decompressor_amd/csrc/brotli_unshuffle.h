@@ -20,7 +20,7 @@
 // of [dst, dst + len) only -- never a read-modify-write: what lies next to them is not this segment's.  A unit may hold the last element
 // bytes AND the first left-over bytes, and may be the first and the last unit of a short segment at once.
 //
-// One set of functions for the host (csrc/brotli_unshuffle.cpp: BrotliAmdDebugUnshuffleHost; tests/tools/unshuffle_san.cpp) and the device
+// One set of functions for the host (csrc/brotli_filters.cpp: BrotliAmdDebugUnshuffleHost; tests/tools/unshuffle_san.cpp) and the device
 // (csrc/brotli_unshuffle_kernels.hip).  Addresses are integers.
 #ifndef BROTLI_AMD_UNSHUFFLE_H_
 #define BROTLI_AMD_UNSHUFFLE_H_

@@ -12,6 +12,8 @@ block size where there is one, and its bit planes are turned back by one call fo
 whose array was BIT-PACKED -- fields of k bits back to back: Parquet's bit-packed runs, Arrow's validity bitmaps, 4-bit weights,
 numpy.packbits -- names k in its spec; it is the one stream whose slot is larger than its delivered bytes, and one call unpacks all such
 streams into their slots (Batch.bitunpack_outputs)."""
+import collections
+
 import torch
 
 SLOT_ALIGN = 64   # every returned tensor starts at a multiple of this many bytes of one buffer
@@ -26,6 +28,53 @@ def _numel(shape):
 
 FILTERS = ("shuffle", "delta", "bitshuffle", "bitpack")
 BITPACK_OPTIONS = {"big": 1, "signed": 2}   # BITUNPACK_MSB_FIRST, BITUNPACK_SIGNED
+
+
+# What a wanted stream's spec says: the slot's bytes, the tensor's dtype and shape, the element width, the names of its filters, bitshuffle's block
+# and bitpack's (k, flags) -- (1, 0) where the stream is not packed, as for a stream that is not wanted
+_Stream = collections.namedtuple("_Stream", "want dtype shape item filters block pack")
+
+
+def _parse_spec(i, spec, size):
+    """spec of stream i, which delivered `size` bytes -> _Stream; ValueError, naming the stream, for what outputs_as_tensors refuses"""
+    dtype, shape = spec[0], spec[1]
+    flt, block, pack = [], 0, None
+    for name in (tuple(spec[2]) if len(spec) > 2 else ("shuffle",)):
+        if isinstance(name, (tuple, list)) and len(name) == 2 and name[0] == "bitshuffle":   # ("bitshuffle", block_elems)
+            name, block = name[0], int(name[1])
+            if block < 0 or block % 8 != 0:
+                raise ValueError("stream %d: a bitshuffle block of %d elements is neither 0 nor a multiple of 8" % (i, block))
+        if isinstance(name, (tuple, list)) and len(name) >= 1 and name[0] == "bitpack":   # ("bitpack", k, options...)
+            if len(name) < 2:
+                raise ValueError("stream %d: \"bitpack\" without its field width: (\"bitpack\", k)" % i)
+            for opt in name[2:]:
+                if opt not in BITPACK_OPTIONS:
+                    raise ValueError("stream %d: unknown bitpack option %r (known: %s)" % (i, opt, ", ".join(BITPACK_OPTIONS)))
+            name, pack = name[0], (int(name[1]), sum({BITPACK_OPTIONS[opt] for opt in name[2:]}))
+        elif name == "bitpack":
+            raise ValueError("stream %d: \"bitpack\" without its field width: (\"bitpack\", k)" % i)
+        if name not in FILTERS:
+            raise ValueError("stream %d: unknown filter %r (known: %s)" % (i, name, ", ".join(FILTERS)))
+        flt.append(name)
+    flt = tuple(flt)
+    if "shuffle" in flt and "bitshuffle" in flt:
+        raise ValueError("stream %d: \"shuffle\" and \"bitshuffle\" in one spec: an array goes through one of them" % i)
+    if pack is not None and ("shuffle" in flt or "bitshuffle" in flt):
+        raise ValueError("stream %d: \"bitpack\" with \"shuffle\" or \"bitshuffle\" in one spec: packed fields have no byte or bit planes" % i)
+    shape = tuple(int(d) for d in (shape if isinstance(shape, (tuple, list, torch.Size)) else (shape,)))
+    item = torch.empty(0, dtype=dtype).element_size()
+    if item not in (1, 2, 4, 8):
+        raise ValueError("stream %d: elements of %d bytes (%s) cannot be unshuffled" % (i, item, dtype))
+    want = _numel(shape) * item
+    if pack is not None:
+        if not 1 <= pack[0] <= 8 * item:
+            raise ValueError("stream %d: bitpack fields of %d bits, but %s takes 1 .. %d" % (i, pack[0], dtype, 8 * item))
+        stored = (_numel(shape) * pack[0] + 7) // 8
+        if size != stored:
+            raise ValueError("stream %d: %d delivered bytes, but %d fields of %d bits (shape %s) are %d" % (i, size, _numel(shape), pack[0], shape, stored))
+    elif size != want:
+        raise ValueError("stream %d: %d delivered bytes, but %s of shape %s is %d" % (i, size, dtype, shape, want))
+    return _Stream(want, dtype, shape, item, flt, block, pack or (1, 0))
 
 
 def outputs_as_tensors(batch, specs):
@@ -58,71 +107,40 @@ def outputs_as_tensors(batch, specs):
         raise RuntimeError("no outputs: no decode call on this batch object yet, or its launch has not been waited for")
     if len(specs) != len(sizes):
         raise ValueError("specs: %d entries for the %d streams of the last decode call" % (len(specs), len(sizes)))
-    slots, widths, filters, blocks, packs, total = [], [], [], [], [], 0
-    for i, spec in enumerate(specs):
-        if spec is None:
-            slots.append(None); widths.append(1); filters.append(()); blocks.append(0); packs.append((1, 0))
-            continue
-        dtype, shape = spec[0], spec[1]
-        flt, block, pack = [], 0, None
-        for name in (tuple(spec[2]) if len(spec) > 2 else ("shuffle",)):
-            if isinstance(name, (tuple, list)) and len(name) == 2 and name[0] == "bitshuffle":   # ("bitshuffle", block_elems)
-                name, block = name[0], int(name[1])
-                if block < 0 or block % 8 != 0:
-                    raise ValueError("stream %d: a bitshuffle block of %d elements is neither 0 nor a multiple of 8" % (i, block))
-            if isinstance(name, (tuple, list)) and len(name) >= 1 and name[0] == "bitpack":   # ("bitpack", k, options...)
-                if len(name) < 2:
-                    raise ValueError("stream %d: \"bitpack\" without its field width: (\"bitpack\", k)" % i)
-                for opt in name[2:]:
-                    if opt not in BITPACK_OPTIONS:
-                        raise ValueError("stream %d: unknown bitpack option %r (known: %s)" % (i, opt, ", ".join(BITPACK_OPTIONS)))
-                name, pack = name[0], (int(name[1]), sum({BITPACK_OPTIONS[opt] for opt in name[2:]}))
-            elif name == "bitpack":
-                raise ValueError("stream %d: \"bitpack\" without its field width: (\"bitpack\", k)" % i)
-            if name not in FILTERS:
-                raise ValueError("stream %d: unknown filter %r (known: %s)" % (i, name, ", ".join(FILTERS)))
-            flt.append(name)
-        flt = tuple(flt)
-        if "shuffle" in flt and "bitshuffle" in flt:
-            raise ValueError("stream %d: \"shuffle\" and \"bitshuffle\" in one spec: an array goes through one of them" % i)
-        if pack is not None and ("shuffle" in flt or "bitshuffle" in flt):
-            raise ValueError("stream %d: \"bitpack\" with \"shuffle\" or \"bitshuffle\" in one spec: packed fields have no byte or bit planes" % i)
-        shape = tuple(int(d) for d in (shape if isinstance(shape, (tuple, list, torch.Size)) else (shape,)))
-        item = torch.empty(0, dtype=dtype).element_size()
-        if item not in (1, 2, 4, 8):
-            raise ValueError("stream %d: elements of %d bytes (%s) cannot be unshuffled" % (i, item, dtype))
-        want = _numel(shape) * item
-        if pack is not None:
-            if not 1 <= pack[0] <= 8 * item:
-                raise ValueError("stream %d: bitpack fields of %d bits, but %s takes 1 .. %d" % (i, pack[0], dtype, 8 * item))
-            stored = (_numel(shape) * pack[0] + 7) // 8
-            if sizes[i] != stored:
-                raise ValueError("stream %d: %d delivered bytes, but %d fields of %d bits (shape %s) are %d" % (i, sizes[i], _numel(shape), pack[0], shape, stored))
-        elif sizes[i] != want:
-            raise ValueError("stream %d: %d delivered bytes, but %s of shape %s is %d" % (i, sizes[i], dtype, shape, want))
-        slots.append((total, want, dtype, shape)); widths.append(item); filters.append(flt); blocks.append(block); packs.append(pack or (1, 0))
-        total = (total + want + SLOT_ALIGN - 1) // SLOT_ALIGN * SLOT_ALIGN
+    streams = [None if spec is None else _parse_spec(i, spec, sizes[i]) for i, spec in enumerate(specs)]
+    offs, total = [], 0   # every stream's slot in the buffer
+    for st in streams:
+        offs.append(total)
+        if st is not None:
+            total = (total + st.want + SLOT_ALIGN - 1) // SLOT_ALIGN * SLOT_ALIGN
     buf = torch.empty(total + SLOT_ALIGN, dtype=torch.uint8, device="cuda")
     skip = -buf.data_ptr() % SLOT_ALIGN   # (the allocator's blocks are aligned far beyond this; nothing here depends on it)
     buf = buf[skip:skip + total]
     base = buf.data_ptr()
     # (a slot of no bytes has a pointer too: a NULL one would mean "skip", which is the same here)
-    at = [None if s is None else base + s[0] for s in slots]
-    # the unshuffle call: every wanted stream but those that are deltas only, those of bit planes and those of packed fields; without "shuffle"
-    # it is a copy -- width 1
-    bits = [i for i, s in enumerate(slots) if s is not None and "bitshuffle" in filters[i]]
-    packed = [i for i, s in enumerate(slots) if s is not None and "bitpack" in filters[i]]
-    plain = [i for i, s in enumerate(slots) if s is not None and i not in bits and i not in packed and "shuffle" not in filters[i] and "delta" in filters[i]]
-    batch.unshuffle_outputs([None if i in plain or i in bits or i in packed else p for i, p in enumerate(at)],
-                            [w if "shuffle" in f else 1 for w, f in zip(widths, filters)])
+    at = [None if st is None else base + off for st, off in zip(streams, offs)]
+    widths = [1 if st is None else st.item for st in streams]
+
+    def only(which):
+        """the slots of the streams in `which`, None for the others"""
+        return [p if i in which else None for i, p in enumerate(at)]
+
+    wanted = [i for i, st in enumerate(streams) if st is not None]
+    bits = [i for i in wanted if "bitshuffle" in streams[i].filters]
+    packed = [i for i in wanted if "bitpack" in streams[i].filters]
+    # deltas only: every other wanted stream that is neither of bit planes nor of packed fields is the unshuffle call's; without "shuffle" it is
+    # a copy -- width 1
+    plain = [i for i in wanted if i not in bits and i not in packed and "shuffle" not in streams[i].filters and "delta" in streams[i].filters]
+    batch.unshuffle_outputs(only([i for i in wanted if i not in plain and i not in bits and i not in packed]),
+                            [st.item if st is not None and "shuffle" in st.filters else 1 for st in streams])
     if bits:    # bit planes: from the outputs straight into the slots
-        batch.bitunshuffle_outputs([p if i in bits else None for i, p in enumerate(at)], widths, blocks)
+        batch.bitunshuffle_outputs(only(bits), widths, [0 if st is None else st.block for st in streams])
     if packed:  # packed fields: from the outputs straight into the slots, which are larger than the outputs
-        batch.bitunpack_outputs([p if i in packed else None for i, p in enumerate(at)], [k for k, _ in packs], widths,
-                                [_numel(s[3]) if s is not None else 0 for s in slots], [f for _, f in packs])
+        batch.bitunpack_outputs(only(packed), [1 if st is None else st.pack[0] for st in streams], widths,
+                                [0 if st is None else _numel(st.shape) for st in streams], [0 if st is None else st.pack[1] for st in streams])
     if plain:   # deltas only: from the outputs straight into the slots
-        batch.undelta_outputs([p if i in plain else None for i, p in enumerate(at)], widths)
-    both = [i for i, s in enumerate(slots) if s is not None and ("shuffle" in filters[i] or "bitshuffle" in filters[i] or "bitpack" in filters[i]) and "delta" in filters[i]]
+        batch.undelta_outputs(only(plain), widths)
+    both = [i for i in wanted if i not in plain and "delta" in streams[i].filters]
     if both:    # in place over the slots, which are 64-byte aligned
-        batch.undelta_segments([at[i] for i in both], [at[i] for i in both], [slots[i][1] for i in both], [widths[i] for i in both])
-    return [None if s is None else buf[s[0]:s[0] + s[1]].view(s[2]).reshape(s[3]) for s in slots]
+        batch.undelta_segments([at[i] for i in both], [at[i] for i in both], [streams[i].want for i in both], [widths[i] for i in both])
+    return [None if st is None else buf[off:off + st.want].view(st.dtype).reshape(st.shape) for st, off in zip(streams, offs)]

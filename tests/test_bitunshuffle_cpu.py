@@ -5,12 +5,12 @@ import ctypes
 import os
 import random
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import bitshuffle_ref as ref
+import san_program
 from conftest import ROOT
 
 WIDTHS = [1, 2, 4, 8]
@@ -203,10 +203,5 @@ def test_the_tile_hook_is_the_headers_constant(pkg):
 def test_functions_under_sanitizers(tmp_path):
     """tests/tools/bitunshuffle_san.cpp: csrc/brotli_bitunshuffle.h against a bit-by-bit loop, every source and destination in a heap block of
     exactly the sixteen-byte words its span touches, under ASan and UBSan, as a program of its own"""
-    exe = str(tmp_path / "bitunshuffle_san")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "rust-brotli-decompressor_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "tools", "bitunshuffle_san.cpp"), "-o", exe])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    r = san_program.run("bitunshuffle_san", tmp_path)
     assert "segments" in r.stdout and "fast items" in r.stdout

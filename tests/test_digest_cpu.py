@@ -5,12 +5,12 @@ import ctypes
 import os
 import random
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import digest_ref as ref
+import san_program
 from conftest import ROOT
 
 KINDS = [ref.CRC32, ref.CRC32C]
@@ -112,10 +112,5 @@ def test_argument_failures_without_a_device(pkg):
 def test_arithmetic_under_sanitizers(tmp_path):
     """tests/tools/digest_san.cpp: csrc/brotli_crc.h against a bitwise loop, every segment in a heap block of exactly the sixteen-byte words
     it touches, under ASan and UBSan, as a program of its own"""
-    exe = str(tmp_path / "digest_san")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "rust-brotli-decompressor_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "tools", "digest_san.cpp"), "-o", exe])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    r = san_program.run("digest_san", tmp_path)
     assert "digests" in r.stdout

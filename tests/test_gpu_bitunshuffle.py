@@ -5,17 +5,15 @@ compared with the expectation: a byte written outside a segment fails the test."
 import ctypes
 import os
 import random
-import sys
 
 import numpy as np
 import pytest
 
 import bitshuffle_ref as ref
 import shuffle_ref
+import seg_filter_harness as H
 from conftest import ROOT
-
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import brotli_emit as E  # noqa: E402
+from seg_filter_harness import fresh_dst as _fresh_dst, next_at as _next_at, stream as _stream
 
 pytestmark = pytest.mark.gpu
 WIDTHS = [1, 2, 4, 8]
@@ -28,28 +26,17 @@ DST_BYTES = (12 << 20) + 64
 @pytest.fixture(scope="module")
 def source():
     """16 MiB + 64 of seeded bytes: computed once, never changed"""
-    a = np.random.default_rng(20271).integers(0, 256, size=SRC_BYTES, dtype=np.uint8)
-    a.setflags(write=False)
-    return a
+    return H.source(20271, SRC_BYTES)
 
 
 @pytest.fixture(scope="module")
 def sentinel():
-    """what a destination buffer holds in front of a call: a pattern of period 251, so that no shifted copy of it is itself"""
-    a = (np.arange(DST_BYTES, dtype=np.uint64) % 251 + 3).astype(np.uint8)
-    a.setflags(write=False)
-    return a
+    return H.sentinel(DST_BYTES)
 
 
 @pytest.fixture(scope="module")
 def dev(source, sentinel):
-    """the source and the sentinel on the device, and the one destination buffer"""
-    import torch
-    d = {"src": torch.from_numpy(source.copy()).cuda(), "sentinel": torch.from_numpy(sentinel.copy()).cuda(),
-         "dst": torch.empty(DST_BYTES, dtype=torch.uint8, device="cuda")}
-    torch.cuda.synchronize()
-    assert d["src"].data_ptr() % 16 == 0 and d["dst"].data_ptr() % 16 == 0
-    return d
+    return H.device_buffers(source, sentinel)
 
 
 @pytest.fixture(scope="module")
@@ -59,21 +46,8 @@ def batch(pkg):
     b.close()
 
 
-def _fresh_dst(dev, size):
-    import torch
-    assert size <= DST_BYTES
-    dev["dst"][:size].copy_(dev["sentinel"][:size])
-    torch.cuda.synchronize()
-
-
 def _compare(dev, want, segs=None):
-    """the whole destination buffer against the expectation"""
-    got = dev["dst"][:len(want)].cpu().numpy()
-    if not np.array_equal(got, want):
-        at = int(np.flatnonzero(got != want)[0])
-        inside = [s for s in (segs or []) if s[1] <= at < s[1] + s[2]]
-        raise AssertionError("byte %d of the destination is %#x, not %#x; segment (src, dst, len, w, block): %r" %
-                             (at, got[at], want[at], inside[:1] or "none: outside every segment"))
+    H.compare(dev, want, segs, names="(src, dst, len, w, block)")
 
 
 def _bitunshuffle(batch, dev, source, sentinel, segs, size, blocks_none=False):
@@ -87,12 +61,6 @@ def _bitunshuffle(batch, dev, source, sentinel, segs, size, blocks_none=False):
     batch.bitunshuffle_segments([sp + s[0] for s in segs], [dp + s[1] for s in segs], [s[2] for s in segs], [s[3] for s in segs],
                                 None if blocks_none else [s[4] for s in segs])
     _compare(dev, want, segs)
-
-
-def _next_at(at, align, mod=16):
-    while at % mod != align:
-        at += 1
-    return at
 
 
 def test_every_alignment_and_short_length(pkg, batch, dev, source, sentinel):
@@ -191,22 +159,6 @@ def test_bad_arguments_launch_nothing(pkg, batch, dev, source, sentinel):
 
 
 # ------------------------------------------------------------------ the outputs of a decode call
-def _stream(raw):
-    """a stream of stored metablocks and, where there are enough bytes, a compressed last one (tools/brotli_emit.py, as tests/test_gpu_unshuffle.py)"""
-    w = E.BitWriter(); E.write_stream_header(w, 22)
-    if len(raw) < 64:
-        if raw:
-            E.emit_stored(w, raw)
-        E.emit_last_empty(w)
-        return w.finish()
-    cut = len(raw) - min(1500, len(raw) // 2)
-    head, tail = raw[:cut], raw[cut:]
-    E.emit_stored(w, head[:len(head) // 2]); E.emit_stored(w, head[len(head) // 2:])
-    got = E.emit_compressed(w, E.greedy_commands(tail, max_dist=1000, history=b""), E.Plan(), True, prev=head)
-    assert got == tail
-    return w.finish()
-
-
 @pytest.fixture(scope="module")
 def arrays():
     """seeded int8, int16, float32 and float64 arrays of 0, 1, 7, 4096, 4100 and 100 003 bytes -- left-over bytes behind the last whole element
@@ -233,12 +185,7 @@ def arrays():
 
 
 def _slots(sizes, skip=()):
-    """destinations back to back from offset 16 on -> ([offset or None], bytes in all)"""
-    offs, at = [], 16
-    for i, n in enumerate(sizes):
-        offs.append(None if i in skip else at)
-        at += n
-    return offs, at + 64
+    return H.slots(sizes, skip, start=16)
 
 
 def _check_outputs(b, dev, sentinel, arrays, skip):
@@ -348,16 +295,8 @@ def test_truncated_delivery(pkg, dev, sentinel, arrays):
 
 
 def test_outputs_as_tensors(pkg, dev):
-    import importlib.util
     import torch
-    name = "rust_brotli_decompressor_amd.tensors"
-    if name in sys.modules:
-        tensors = sys.modules[name]
-    else:
-        spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "rust-brotli-decompressor_amd", "tensors.py"))
-        tensors = importlib.util.module_from_spec(spec)
-        sys.modules[name] = tensors
-        spec.loader.exec_module(tensors)
+    tensors = H.tensors_module()
     assert "bitshuffle" in tensors.FILTERS
     g = torch.Generator().manual_seed(20273)
     originals = [torch.randint(-500, 500, (33, 7), generator=g, dtype=torch.int16), torch.randn((1031, 5), generator=g),

@@ -6,16 +6,14 @@ missing or doubled carry shows in every byte behind it.  All comparisons are exa
 import ctypes
 import os
 import random
-import sys
 
 import numpy as np
 import pytest
 
 import delta_ref as ref
+import seg_filter_harness as H
 from conftest import ROOT
-
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import brotli_emit as E  # noqa: E402
+from seg_filter_harness import fresh_dst as _fresh_dst, next_at as _next_at, stream as _stream, slots as _slots
 
 pytestmark = pytest.mark.gpu
 WIDTHS = [1, 2, 4, 8]
@@ -35,28 +33,17 @@ def sizes(pkg):
 @pytest.fixture(scope="module")
 def source(sizes):
     """seeded bytes: computed once, never changed"""
-    a = np.random.default_rng(20268).integers(0, 256, size=sizes["bytes"], dtype=np.uint8)
-    a.setflags(write=False)
-    return a
+    return H.source(20268, sizes["bytes"])
 
 
 @pytest.fixture(scope="module")
 def sentinel(sizes):
-    """what a destination buffer holds in front of a call: a pattern of period 251, so that no shifted copy of it is itself"""
-    a = np.resize((np.arange(251) + 3).astype(np.uint8), sizes["bytes"])   # byte i is i % 251 + 3
-    a.setflags(write=False)
-    return a
+    return H.sentinel(sizes["bytes"])
 
 
 @pytest.fixture(scope="module")
 def dev(source, sentinel):
-    """the source and the sentinel on the device, and the one destination buffer"""
-    import torch
-    d = {"src": torch.from_numpy(source.copy()).cuda(), "sentinel": torch.from_numpy(sentinel.copy()).cuda(),
-         "dst": torch.empty(len(sentinel), dtype=torch.uint8, device="cuda")}
-    torch.cuda.synchronize()
-    assert d["src"].data_ptr() % 16 == 0 and d["dst"].data_ptr() % 16 == 0
-    return d
+    return H.device_buffers(source, sentinel)
 
 
 @pytest.fixture(scope="module")
@@ -66,20 +53,8 @@ def batch(pkg):
     b.close()
 
 
-def _fresh_dst(dev, size):
-    import torch
-    assert size <= len(dev["dst"])
-    dev["dst"][:size].copy_(dev["sentinel"][:size])
-    torch.cuda.synchronize()
-
-
 def _compare(dev, want, segs=None):
-    """the whole destination buffer against the expectation"""
-    got = dev["dst"][:len(want)].cpu().numpy()
-    if not np.array_equal(got, want):
-        at = int(np.flatnonzero(got != want)[0])
-        inside = [s for s in (segs or []) if s[1] <= at < s[1] + s[2]]
-        raise AssertionError("byte %d of the destination is %#x, not %#x; segment (src, dst, len, w): %r" % (at, got[at], want[at], inside[:1] or "none: outside every segment"))
+    H.compare(dev, want, segs, names="(src, dst, len, w)")
 
 
 def _undelta(batch, dev, source, sentinel, segs, size, in_place=()):
@@ -99,12 +74,6 @@ def _undelta(batch, dev, source, sentinel, segs, size, in_place=()):
     batch.undelta_segments([dp + d if i in in_place else sp + s for i, (s, d, _, _) in enumerate(segs)], [dp + d for _, d, _, _ in segs],
                            [l for _, _, l, _ in segs], [w for _, _, _, w in segs])
     _compare(dev, want, segs)
-
-
-def _next_at(at, align, mod=16):
-    while at % mod != align:
-        at += 1
-    return at
 
 
 def test_every_alignment_and_short_length(pkg, batch, dev, source, sentinel):
@@ -240,22 +209,6 @@ def test_bad_arguments_launch_nothing(pkg, batch, dev, source, sentinel):
 
 
 # ------------------------------------------------------------------ the outputs of a decode call
-def _stream(raw):
-    """a stream of stored metablocks and, where there are enough bytes, a compressed last one (tools/brotli_emit.py, as tests/size_streams.py)"""
-    w = E.BitWriter(); E.write_stream_header(w, 22)
-    if len(raw) < 64:
-        if raw:
-            E.emit_stored(w, raw)
-        E.emit_last_empty(w)
-        return w.finish()
-    cut = len(raw) - min(1500, len(raw) // 2)
-    head, tail = raw[:cut], raw[cut:]
-    E.emit_stored(w, head[:len(head) // 2]); E.emit_stored(w, head[len(head) // 2:])
-    got = E.emit_compressed(w, E.greedy_commands(tail, max_dist=1000, history=b""), E.Plan(), True, prev=head)
-    assert got == tail
-    return w.finish()
-
-
 @pytest.fixture(scope="module")
 def arrays():
     """seeded sorted int64 timestamps, int32 offsets, int16 and uint8 samples, of 0, 1, 7, 4096 and 100 003 bytes (left-over bytes behind the
@@ -276,15 +229,6 @@ def arrays():
         assert len(x) == nbytes
         out.append((x, w, _stream(ref.delta(x, w))))
     return out
-
-
-def _slots(sizes, skip=()):
-    """destinations back to back from offset 5 on -> ([offset or None], bytes in all)"""
-    offs, at = [], 5
-    for i, n in enumerate(sizes):
-        offs.append(None if i in skip else at)
-        at += n
-    return offs, at + 64
 
 
 def _check_outputs(b, dev, sentinel, arrays, skip):
@@ -391,17 +335,9 @@ def test_truncated_delivery(pkg, dev, sentinel, arrays):
 
 
 def test_outputs_as_tensors(pkg, dev):
-    import importlib.util
     import torch
     import shuffle_ref
-    name = "rust_brotli_decompressor_amd.tensors"
-    if name in sys.modules:
-        tensors = sys.modules[name]
-    else:
-        spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "rust-brotli-decompressor_amd", "tensors.py"))
-        tensors = importlib.util.module_from_spec(spec)
-        sys.modules[name] = tensors
-        spec.loader.exec_module(tensors)
+    tensors = H.tensors_module()
     g = torch.Generator().manual_seed(20270)
     stamps = 1700000000000000000 + torch.cumsum(torch.randint(0, 10 ** 9, (1000,), generator=g, dtype=torch.int64), 0)
     originals = [(stamps, ("shuffle", "delta")),

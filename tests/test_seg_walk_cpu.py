@@ -3,10 +3,10 @@ host hook -- BrotliAmdDebugSegWalkParts runs the very function the device walk r
 segments -- and as a program of its own under sanitizers.  A part is (block, tile, lo, hi): the units [lo, hi) that one chunk of segments holds
 of one tile.  All comparisons are exact."""
 import os
-import subprocess
 
 import pytest
 
+import san_program
 from conftest import ROOT
 
 CHUNK = 1024   # segments whose prefix sum the device holds at a time (BROTLI_AMD_SEG_CHUNK_SEGS)
@@ -98,10 +98,5 @@ def test_a_tile_in_three_chunks_has_a_part_for_each_chunk_with_units(pkg):
 
 def test_the_walk_under_sanitizers(tmp_path):
     """tests/tools/seg_walk_san.cpp: the same enumeration over the same tables under ASan and UBSan, as a program of its own"""
-    exe = str(tmp_path / "seg_walk_san")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "rust-brotli-decompressor_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "tools", "seg_walk_san.cpp"), "-o", exe])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    r = san_program.run("seg_walk_san", tmp_path)
     assert r.stdout.count("parts") == len(CASES) * 4

@@ -3,12 +3,12 @@ oracle, and the new names of batch.h.  A hint's contract (batch.h): `bytes` is a
 size where exact == 1 and status == 0, and status == 2 only where the decoder reports an error."""
 import os
 import re
-import subprocess
 
 import pytest
 
 import oracle_lib as oracle
 import size_streams as ss
+import san_program
 from conftest import ROOT
 
 E = ss.E
@@ -124,14 +124,9 @@ def test_every_wbits_encoding(pkg):
 
 def test_walk_under_sanitizers(pkg, tmp_path):
     """tests/tools/size_walk_san.cpp: every prefix of the streams from an exactly-sized heap block, under ASan and UBSan, as a program of its own"""
-    exe = str(tmp_path / "size_walk_san")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "rust-brotli-decompressor_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "tools", "size_walk_san.cpp"), "-o", exe])
     files = []
     for k, stream in enumerate([ss.long_walk_stream()[0]] + [ss.golden(n) for n in ss.SHORT_GOLDEN] + [ss.golden("empty.compressed.17")[:3000]]):
         files.append(str(tmp_path / ("s%d.br" % k)))
         open(files[-1], "wb").write(stream)
-    r = subprocess.run([exe] + files, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    r = san_program.run("size_walk_san", tmp_path, files)
     assert "walks" in r.stdout

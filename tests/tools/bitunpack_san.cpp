@@ -14,6 +14,7 @@
 
 #include "brotli_bitunpack.h"
 #include "brotli_device_abi.h"
+#include "san_block.h"
 
 static uint32_t g_seed = 2028u;
 static uint32_t rnd() { g_seed = g_seed * 1664525u + 1013904223u; return g_seed >> 8; }
@@ -35,15 +36,12 @@ static uint8_t want_byte(const uint8_t* s, uint32_t k, uint32_t w, uint32_t flag
 
 static int one(uint32_t w, uint32_t k, uint32_t flags, size_t m, uint32_t ss, uint32_t ds) {
   const size_t slen = (m * k + 7u) / 8u, len = m * w;
-  const size_t sspan = slen ? (ss + slen + 15u) & ~(size_t)15 : 0, dspan = len ? (ds + len + 15u) & ~(size_t)15 : 0;
-  uint8_t* sb = static_cast<uint8_t*>(sspan ? std::aligned_alloc(16, sspan) : std::malloc(1));
-  uint8_t* db = static_cast<uint8_t*>(dspan ? std::aligned_alloc(16, dspan) : std::malloc(1));
-  if (!sb || !db) return 2;
-  for (size_t i = 0; i < sspan; i++) sb[i] = (uint8_t)rnd();
-  for (size_t i = 0; i < dspan; i++) db[i] = (uint8_t)(0xA5u ^ i);
-  const uint64_t src = (uint64_t)(uintptr_t)sb + ss, dst = (uint64_t)(uintptr_t)db + ds;
+  SanBlock sb(slen, ss), db(len, ds);
+  sb.fill_random(rnd);
+  db.fill_pattern();
+  const uint64_t src = sb.addr(), dst = db.addr();
   const uint64_t units = brotli_amd_seg_units(dst, len);
-  if (units != dspan / 16u) { std::fprintf(stderr, "units %llu of a span of %zu\n", (unsigned long long)units, dspan); return 1; }
+  if (units != db.span / 16u) { std::fprintf(stderr, "units %llu of a span of %zu\n", (unsigned long long)units, db.span); return 1; }
   const uint64_t tile = BROTLI_AMD_BITUNPACK_TILE_BYTES / 16u, slot = 2u * w;
   if (rnd() & 1u) {
     for (uint64_t t0 = 0; t0 < units; t0 += tile) {
@@ -58,15 +56,12 @@ static int one(uint32_t w, uint32_t k, uint32_t flags, size_t m, uint32_t ss, ui
       t1 = t0;
     }
   }
-  for (size_t i = 0; i < dspan; i++) {
-    uint8_t want = (uint8_t)(0xA5u ^ i);
-    if (i >= ds && i < ds + len) want = want_byte(sb + ss, k, w, flags, i - ds);
-    if (db[i] != want) {
-      std::fprintf(stderr, "width %u bits %u flags %u count %zu skews %u %u: byte %zu is %02x, not %02x\n", w, k, flags, m, ss, ds, i, db[i], want);
-      return 1;
-    }
+  size_t i = 0;
+  uint8_t is = 0, must = 0;
+  if (!db.holds([&](size_t p) { return want_byte(sb.at(), k, w, flags, p); }, &i, &is, &must)) {
+    std::fprintf(stderr, "width %u bits %u flags %u count %zu skews %u %u: byte %zu is %02x, not %02x\n", w, k, flags, m, ss, ds, i, is, must);
+    return 1;
   }
-  std::free(sb); std::free(db);
   return 0;
 }
 

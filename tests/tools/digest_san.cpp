@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "brotli_crc.h"
+#include "san_block.h"
 
 static constexpr BrotliAmdCrcConsts kConsts[2] = {brotli_amd_crc_make_consts(BROTLI_AMD_CRC32_POLY), brotli_amd_crc_make_consts(BROTLI_AMD_CRC32C_POLY)};
 
@@ -33,12 +34,11 @@ int main() {
     for (size_t n : {4079, 4080, 4081, 4095, 4096, 4097, 12293}) lens.push_back(n);
     for (size_t n : lens)
       for (uint32_t skew = 0; skew < 16u; skew++) {
-        const size_t span = n ? (skew + n + 15u) & ~(size_t)15 : 0;
-        uint8_t* block = static_cast<uint8_t*>(span ? std::aligned_alloc(16, span) : std::malloc(1));
-        if (!block) return 2;
-        for (size_t i = 0; i < span; i++) { seed = seed * 1664525u + 1013904223u; block[i] = (uint8_t)(seed >> 24); }
-        const uint64_t at = (uint64_t)(uintptr_t)block + skew;
-        const uint32_t want = n ? ~raw_bitwise(poly, 0xFFFFFFFFu, block + skew, n) : 0u;
+        SanBlock block(n, skew);
+        block.fill_random([&seed] { seed = seed * 1664525u + 1013904223u; return seed >> 24; });
+        const size_t span = block.span;
+        const uint64_t at = block.addr();
+        const uint32_t want = n ? ~raw_bitwise(poly, 0xFFFFFFFFu, block.at(), n) : 0u;
         const auto load = [](uint64_t W, uint32_t* w) { std::memcpy(w, reinterpret_cast<const void*>((uintptr_t)W), 16); };
         const uint64_t units = brotli_amd_seg_units(at, n);
         if (units != span / 16u) { std::fprintf(stderr, "units %llu of a span of %zu\n", (unsigned long long)units, span); return 1; }
@@ -52,7 +52,6 @@ int main() {
           digests++;
           if (got != want) { std::fprintf(stderr, "kind %u length %zu skew %u run %u: %08x, not %08x\n", kind, n, skew, run, got, want); return 1; }
         }
-        std::free(block);
       }
     // the shift: n zero bytes behind a raw register, bit by bit
     const std::vector<uint8_t> zeros(5000, 0);

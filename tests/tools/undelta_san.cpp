@@ -12,21 +12,12 @@
 
 #include "brotli_device_abi.h"
 #include "brotli_undelta.h"
+#include "san_block.h"
 
 static uint32_t g_seed = 2027u;
 static uint32_t rnd() { g_seed = g_seed * 1664525u + 1013904223u; return g_seed >> 8; }
 
-struct Block {   // a segment's bytes at a skew, in a heap block of exactly the words they touch
-  uint8_t* base = nullptr; size_t span = 0; uint32_t skew = 0; size_t len = 0;
-  Block(size_t len_, uint32_t skew_) : skew(skew_), len(len_) {
-    span = len ? (skew + len + 15u) & ~(size_t)15 : 0;
-    base = static_cast<uint8_t*>(span ? std::aligned_alloc(16, span) : std::malloc(1));
-    if (!base) std::abort();
-  }
-  Block(const Block&) = delete;
-  ~Block() { std::free(base); }
-  uint8_t* at() const { return base + skew; }
-};
+typedef SanBlock Block;
 
 // want[0, len): the transform of s[0, len), element by element
 static void expect(const uint8_t* s, size_t len, uint32_t w, uint8_t* want) {
@@ -68,17 +59,17 @@ static void run(const std::vector<BrotliAmdUnshuffleSeg>& segs, uint64_t tile_un
 static int check(const Block& s0, const Block& d, uint32_t w, const char* what) {
   std::vector<uint8_t> want(d.len ? d.len : 1u);
   expect(s0.at(), d.len, w, want.data());
-  for (size_t i = 0; i < d.span; i++) {
-    const uint8_t x = i >= d.skew && i < d.skew + d.len ? want[i - d.skew] : (uint8_t)(0xA5u ^ i);
-    if (d.base[i] != x) { std::fprintf(stderr, "%s: width %u length %zu skews %u %u: byte %zu is %02x, not %02x\n", what, w, d.len, s0.skew, d.skew, i, d.base[i], x); return 1; }
-  }
-  return 0;
+  size_t i = 0;
+  uint8_t is = 0, must = 0;
+  if (d.holds([&](size_t p) { return want[p]; }, &i, &is, &must)) return 0;
+  std::fprintf(stderr, "%s: width %u length %zu skews %u %u: byte %zu is %02x, not %02x\n", what, w, d.len, s0.skew, d.skew, i, is, must);
+  return 1;
 }
 
 static int one(uint32_t w, size_t len, uint32_t ss, uint32_t ds, uint64_t tile_units) {
   Block s(len, ss), d(len, ds);
-  for (size_t i = 0; i < s.span; i++) s.base[i] = (uint8_t)rnd();
-  for (size_t i = 0; i < d.span; i++) d.base[i] = (uint8_t)(0xA5u ^ i);
+  s.fill_random(rnd);
+  d.fill_pattern();
   if (brotli_amd_seg_units((uint64_t)(uintptr_t)d.at(), len) != d.span / 16u) { std::fprintf(stderr, "units of a span of %zu\n", d.span); return 1; }
   run({BrotliAmdUnshuffleSeg{s.at(), d.at(), len, w, 0u}}, tile_units, (rnd() & 1u) != 0u);
   return check(s, d, w, "out of place");
@@ -87,7 +78,7 @@ static int one(uint32_t w, size_t len, uint32_t ss, uint32_t ds, uint64_t tile_u
 // in place: the block holds the deltas, then the values; what lies beside the segment in its words keeps its pattern
 static int one_in_place(uint32_t w, size_t len, uint32_t ds, uint64_t tile_units) {
   Block d(len, ds), copy(len, ds);
-  for (size_t i = 0; i < d.span; i++) d.base[i] = (uint8_t)(0xA5u ^ i);
+  d.fill_pattern();
   for (size_t i = 0; i < len; i++) d.at()[i] = copy.at()[i] = (uint8_t)rnd();
   run({BrotliAmdUnshuffleSeg{d.at(), d.at(), len, w, 0u}}, tile_units, (rnd() & 1u) != 0u);
   return check(copy, d, w, "in place");
@@ -102,8 +93,8 @@ static int table(uint32_t count, uint64_t tile_units) {
     const uint32_t pick = rnd() % 10u;
     const size_t len = pick == 0u ? 0u : pick == 1u ? 700u + rnd() % 50u : rnd() % 70u;
     src.push_back(new Block(len, rnd() & 15u)); dst.push_back(new Block(len, rnd() & 15u));
-    for (size_t k = 0; k < src.back()->span; k++) src.back()->base[k] = (uint8_t)rnd();
-    for (size_t k = 0; k < dst.back()->span; k++) dst.back()->base[k] = (uint8_t)(0xA5u ^ k);
+    src.back()->fill_random(rnd);
+    dst.back()->fill_pattern();
     segs.push_back(BrotliAmdUnshuffleSeg{src.back()->at(), dst.back()->at(), len, w, 0u});
   }
   run(segs, tile_units, (rnd() & 1u) != 0u);

@@ -10,20 +10,18 @@
 
 #include "brotli_device_abi.h"
 #include "brotli_unshuffle.h"
+#include "san_block.h"
 
 static uint32_t g_seed = 2026u;
 static uint32_t rnd() { g_seed = g_seed * 1664525u + 1013904223u; return g_seed >> 8; }
 
 static int one(uint32_t w, size_t len, uint32_t ss, uint32_t ds) {
-  const size_t sspan = len ? (ss + len + 15u) & ~(size_t)15 : 0, dspan = len ? (ds + len + 15u) & ~(size_t)15 : 0;
-  uint8_t* sb = static_cast<uint8_t*>(sspan ? std::aligned_alloc(16, sspan) : std::malloc(1));
-  uint8_t* db = static_cast<uint8_t*>(dspan ? std::aligned_alloc(16, dspan) : std::malloc(1));
-  if (!sb || !db) return 2;
-  for (size_t i = 0; i < sspan; i++) sb[i] = (uint8_t)rnd();
-  for (size_t i = 0; i < dspan; i++) db[i] = (uint8_t)(0xA5u ^ i);
-  const uint64_t src = (uint64_t)(uintptr_t)sb + ss, dst = (uint64_t)(uintptr_t)db + ds;
+  SanBlock sb(len, ss), db(len, ds);
+  sb.fill_random(rnd);
+  db.fill_pattern();
+  const uint64_t src = sb.addr(), dst = db.addr();
   const uint64_t units = brotli_amd_seg_units(dst, len);
-  if (units != dspan / 16u) { std::fprintf(stderr, "units %llu of a span of %zu\n", (unsigned long long)units, dspan); return 1; }
+  if (units != db.span / 16u) { std::fprintf(stderr, "units %llu of a span of %zu\n", (unsigned long long)units, db.span); return 1; }
   // as a lane takes them in a tile inside one segment: two units a step (width 8 has a path of its own for two whole words), pairs that begin at
   // an even or an odd unit; otherwise unit by unit, the last first (the units do not depend on their order)
   if (rnd() & 1u) {
@@ -34,12 +32,13 @@ static int one(uint32_t w, size_t len, uint32_t ss, uint32_t ds) {
     for (uint64_t k = units; k-- > 0;) brotli_amd_unshuffle_unit(src, dst, len, w, k);
   }
   const size_t m = len / w;
-  for (size_t i = 0; i < dspan; i++) {
-    uint8_t want = (uint8_t)(0xA5u ^ i);
-    if (i >= ds && i < ds + len) { const size_t p = i - ds; want = p < w * m ? sb[ss + (p % w) * m + p / w] : sb[ss + p]; }
-    if (db[i] != want) { std::fprintf(stderr, "width %u length %zu skews %u %u: byte %zu is %02x, not %02x\n", w, len, ss, ds, i, db[i], want); return 1; }
+  const uint8_t* s = sb.at();
+  size_t i = 0;
+  uint8_t is = 0, must = 0;
+  if (!db.holds([&](size_t p) { return p < w * m ? s[(p % w) * m + p / w] : s[p]; }, &i, &is, &must)) {
+    std::fprintf(stderr, "width %u length %zu skews %u %u: byte %zu is %02x, not %02x\n", w, len, ss, ds, i, is, must);
+    return 1;
   }
-  std::free(sb); std::free(db);
   return 0;
 }
 
