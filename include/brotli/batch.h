@@ -484,6 +484,96 @@ BROTLI_DEC_API uint32_t BrotliAmdDebugBitUnpackTile(void);
 BROTLI_DEC_API int BrotliAmdDebugBitUnpackHost(uint32_t bits, uint32_t width, uint32_t flags, const uint8_t* src, size_t src_len, uint64_t count,
                                               uint8_t* dst, uint32_t src_skew, uint32_t dst_skew, uint64_t* fast_items /* may be NULL */);
 
+/* ---- Unvarint on the device: LEB128 varints of outputs back into elements ----
+ *
+ * The fifth layout in front of the codec is the VARIABLE-LENGTH INTEGER -- LEB128, protobuf's base-128 varint, plain or zigzag: protobuf packed
+ * repeated fields, the block and miniblock headers and first values of Parquet's DELTA_BINARY_PACKED and DELTA_LENGTH_BYTE_ARRAY, the run headers
+ * of its RLE / bit-packed hybrid, ORC's integer runs, Avro's zigzag longs, the postings lists and offset tables of search indexes, sorted ids
+ * stored as varint deltas (which the undelta calls above then sum up).  It is the one filter here whose output size DEPENDS ON THE DATA: every
+ * segment has a capacity and gets a result.
+ *
+ * THE SEGMENT AND ITS PARAMETERS.  A segment is the bytes src[0, len), with a width w in {1, 2, 4, 8}, flags, and a capacity cap in elements.
+ *
+ * END.  A byte with bit 7 clear ENDS a varint.  Call the positions of such bytes in the segment e_0 < e_1 < ... < e_{m-1}.  Varint i is the bytes
+ * (e_{i-1}, e_i], from the segment's start for i = 0; its length L_i is the number of those bytes.  A varint never reaches back across the
+ * segment's first byte, whatever lies in memory in front of it.
+ *
+ * VALUE.  Byte j of the varint contributes its low 7 bits at bit 7 j of a 64-bit value (little-endian groups).  For L_i <= 10, bits at and above
+ * bit 64 are dropped: only bit 0 of the tenth byte counts, and nothing is reported.  For L_i > 10 the varint is OVERLONG: its element is 0 and
+ * it is counted in `overlong`.  So an end byte needs at most the ten bytes in front of it; no look-back is unbounded.
+ *
+ * BROTLI_AMD_UNVARINT_ZIGZAG: v = (v >> 1) ^ (0 - (v & 1)) on the 64-bit value, in front of the truncation.  An overlong element stays 0.
+ *
+ * ELEMENT.  Element i is the value truncated to 8 w bits and stored little-endian at dst + i w, for i < min(m, cap).  dst has any alignment and
+ * need not be a multiple of w.  No byte outside [dst, dst + min(m, cap) w) is written; nothing outside the 16-byte-aligned span around
+ * [src, src + len) is read.
+ *
+ * RESULT.  Every segment gets a BrotliAmdUnvarintResult in host memory: count is m, also where cap < m (the way to size a second call);
+ * consumed is e_{m-1} + 1, or 0 where m == 0 (len - consumed unfinished bytes trail the last end); overlong is the number of overlong varints
+ * among all m.  All three are independent of cap, and of how the work was shared out.
+ *
+ * Examples: 96 01 ac 02 e5 8e 26 is 150, 300, 624485 (consumed 7); ff x 9 then 01, and ff x 9 then 7f, are both 2^64 - 1 at w = 8; 01 02 03 04
+ * fe ff ff ff 0f with zigzag at w = 4 is -1, 1, -2, 2, 2147483647; 80 x 10 then 01 05 80 80 is 0 and 5 with count 2, consumed 12, overlong 1.
+ *
+ * OUT OF PLACE ONLY: no destination range overlaps any source range or any other destination range of the call.  This is stated, not checked.
+ *
+ * REFUSED ON THE HOST, in front of everything that touches the device: a width outside {1, 2, 4, 8}; unknown flag bits; cap > 2^56; a NULL
+ * d_dst[i] with caps[i] != 0.
+ *
+ * A call is three launches in stream order over tiles of SOURCE bytes, the work split by bytes as the ragged copy's is: the number of ends in
+ * every tile, undelta's carry launch over those numbers, and the elements themselves -- no block ever waits for another block's result
+ * (csrc/brotli_unvarint.h, csrc/brotli_unvarint_kernels.hip). */
+#define BROTLI_AMD_UNVARINT_ZIGZAG 1u
+
+typedef struct BrotliAmdUnvarintResult {
+  uint64_t count;     /* the varints that end in the segment, whatever cap was */
+  uint64_t consumed;  /* the bytes up to and including the last end */
+  uint64_t overlong;  /* the varints of more than ten bytes among them (their elements are 0) */
+} BrotliAmdUnvarintResult;
+
+/* n segments in DEVICE memory -- the varints in the src_lens[i] bytes at d_src[i] become elements of widths[i] bytes at d_dst[i], the first
+ * caps[i] of them, by flags[i] (flags == NULL: all 0); results[i] says what segment i held; any alignment, any length, 0 included; n is not
+ * bound by the batch object's max_streams --: the launches run on hip_stream, and the call waits on that stream.  caps[i] == 0 needs no
+ * destination (d_dst[i] is not looked at, and d_dst itself may be NULL where every capacity is 0): a call of such segments only counts.  n == 0
+ * returns 0.  A negative value, and a BrotliAmdLastError text that names the segment and what was wrong, for a NULL batch, a NULL array (but flags
+ * and d_dst) with n != 0, and everything in the list above: all
+ * of these are checked on the host in front of everything else, so nothing is launched and no byte is written. */
+BROTLI_DEC_API int BrotliAmdBatchUnvarintSegments(BrotliAmdBatch* batch, uint32_t n, const void* const* d_src, const size_t* src_lens, void* const* d_dst,
+                                                 const uint64_t* caps, const uint8_t* widths, const uint8_t* flags /* n entries, or NULL: all 0 */,
+                                                 BrotliAmdUnvarintResult* results, void* hip_stream);
+
+/* The same for the DELIVERED bytes -- [out, out + decoded_size) -- of every stream of the last decode call on the object: stream i's varints go
+ * to d_dst[i] (device memory of caps[i] widths[i] bytes, any alignment) by widths[i] and flags[i] (one entry per stream each; flags may be NULL:
+ * all 0), and results[i] (one entry per stream) says what it held.  d_dst[i] == NULL skips stream i: none of its parameters are looked at and
+ * its result is zeros.  d_dst == NULL or caps == NULL: every stream is counted and nothing is written.  Where the sources are, and when they are
+ * valid, is BrotliAmdBatchUnshuffleOutputs' rule exactly, for the three kinds of decode call.  A stream that ended in an error or
+ * NEEDS_MORE_OUTPUT is taken over its decoded_size bytes.  The launches run on the stream of that decode call and the call waits for it.  It is
+ * not a decode call itself: BrotliAmdBatchPackedOutput stays valid, and BrotliAmdBatchRelaunch and the Last* accessors say what they said before.
+ * A negative value, and a BrotliAmdLastError text, for a NULL batch, widths or results, a refused width, flag or cap (nothing is launched), an
+ * object without a decode call, a last decode call that failed behind its argument checks (one of no streams returns 0), and a launch that
+ * BrotliAmdBatchWait has not been called for. */
+BROTLI_DEC_API int BrotliAmdBatchUnvarintOutputs(BrotliAmdBatch* batch, void* const* d_dst /* or NULL */, const uint64_t* caps /* or NULL */,
+                                                const uint8_t* widths, const uint8_t* flags /* or NULL */, BrotliAmdUnvarintResult* results);
+
+/* Milliseconds the unvarint kernels took in the last of the two calls above (HIP events around all its launches together), */
+BROTLI_DEC_API float BrotliAmdBatchLastUnvarintMs(BrotliAmdBatch* batch);
+/* and those of phase 1 (the tiles' counts), 2 (the carries) or 3 (the elements) alone; another phase: 0. */
+BROTLI_DEC_API float BrotliAmdBatchLastUnvarintPhaseMs(BrotliAmdBatch* batch, uint32_t phase);
+
+/* Test hooks (no device needed).  The bytes of SOURCE memory in one tile of an unvarint call; */
+BROTLI_DEC_API uint32_t BrotliAmdDebugUnvarintTile(void);
+/* all three phases by the device's unit and tile functions on the host, over n segments given as offsets into one source buffer src[0, src_size)
+ * and one destination buffer dst[0, dst_size): the buffers are placed at src_skew and dst_skew (0..15) past a 16-byte boundary among bytes that
+ * are not theirs.  Segment i is src_lens[i] bytes at src_offs[i]; its elements go to dst_offs[i], where there must be room for
+ * min(caps[i], src_lens[i]) of them.  tile_units: the 16-byte units of a tile, 0 for the kernel's own.  order_seed != 0: phases 1 and 3 take
+ * the tiles in an order shuffled by it (the result may not depend on it).  0, results[0..n) filled and the elements' bytes of dst written (no
+ * other byte of dst is); -1, a BrotliAmdLastError text and an untouched dst for a refused width, flag or cap, a skew > 15 or a segment outside
+ * its buffer; -2 where a byte outside the elements' destinations changed. */
+BROTLI_DEC_API int BrotliAmdDebugUnvarintHost(uint32_t n, const uint8_t* src, size_t src_size, uint8_t* dst, size_t dst_size, const uint64_t* src_offs,
+                                             const uint64_t* src_lens, const uint64_t* dst_offs, const uint64_t* caps, const uint8_t* widths,
+                                             const uint8_t* flags /* or NULL */, uint32_t src_skew, uint32_t dst_skew, uint32_t tile_units,
+                                             uint32_t order_seed, BrotliAmdUnvarintResult* results);
+
 /* Milliseconds the last launch spent in the decode kernel (HIP events on the launch stream). */
 BROTLI_DEC_API float BrotliAmdBatchLastKernelMs(BrotliAmdBatch* batch);
 

@@ -46,6 +46,8 @@ BATCH_H_SYMBOLS = [
     "BrotliAmdDebugBitUnshuffleHost",
     "BrotliAmdBatchBitUnpackSegments", "BrotliAmdBatchBitUnpackOutputs", "BrotliAmdBatchLastBitUnpackMs", "BrotliAmdDebugBitUnpackTile",
     "BrotliAmdDebugBitUnpackHost",
+    "BrotliAmdBatchUnvarintSegments", "BrotliAmdBatchUnvarintOutputs", "BrotliAmdBatchLastUnvarintMs", "BrotliAmdBatchLastUnvarintPhaseMs",
+    "BrotliAmdDebugUnvarintTile", "BrotliAmdDebugUnvarintHost",
 ]
 
 
@@ -70,6 +72,14 @@ class SizeHint(ctypes.Structure):  # BrotliAmdSizeHint: what a stream's headers 
 SIZE_OK, SIZE_TRUNCATED, SIZE_REJECTED = 0, 1, 2  # SizeHint.status
 DIGEST_CRC32, DIGEST_CRC32C = 1, 2  # BROTLI_AMD_DIGEST_*: zlib's polynomial, Castagnoli's
 BITUNPACK_MSB_FIRST, BITUNPACK_SIGNED = 1, 2  # BROTLI_AMD_BITUNPACK_*: the first bit of a field is the value's highest; sign-extended
+UNVARINT_ZIGZAG = 1  # BROTLI_AMD_UNVARINT_ZIGZAG: (v >> 1) ^ -(v & 1)
+
+
+class UnvarintResult(ctypes.Structure):  # BrotliAmdUnvarintResult: what a segment of varints held (batch.h)
+    _fields_ = [("count", ctypes.c_uint64), ("consumed", ctypes.c_uint64), ("overlong", ctypes.c_uint64)]
+
+    def astuple(self):
+        return (self.count, self.consumed, self.overlong)
 
 
 def build(force=False):
@@ -178,7 +188,10 @@ def load_library():
              "BrotliAmdDebugBitUnshuffleHost": (None, [u32, u32, vp, sz, vp, u32, u32, vp])},
             {"BrotliAmdBatchBitUnpackSegments": (None, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]), "BrotliAmdBatchBitUnpackOutputs": (None, [vp, vp, vp, vp, vp, vp]),
              "BrotliAmdBatchLastBitUnpackMs": (f32, [vp]), "BrotliAmdDebugBitUnpackTile": (u32, None),
-             "BrotliAmdDebugBitUnpackHost": (None, [u32, u32, u32, vp, sz, u64, vp, u32, u32, vp])}):
+             "BrotliAmdDebugBitUnpackHost": (None, [u32, u32, u32, vp, sz, u64, vp, u32, u32, vp])},
+            {"BrotliAmdBatchUnvarintSegments": (None, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]), "BrotliAmdBatchUnvarintOutputs": (None, [vp, vp, vp, vp, vp, vp]),
+             "BrotliAmdBatchLastUnvarintMs": (f32, [vp]), "BrotliAmdBatchLastUnvarintPhaseMs": (f32, [vp, u32]), "BrotliAmdDebugUnvarintTile": (u32, None),
+             "BrotliAmdDebugUnvarintHost": (None, [u32, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, vp])}):
         if hasattr(L, next(iter(protos))):
             for name, (restype, argtypes) in protos.items():
                 if restype is not None:
@@ -326,6 +339,35 @@ def undelta_host(src: bytes, segs, dst_size=None, src_skew=0, dst_skew=0, tile_u
                                    tile_units, order_seed, 1 if in_place else 0) != 0:
         raise RuntimeError("BrotliAmdDebugUndeltaHost failed: " + last_error())
     return d_buf.raw[:dst_size]
+
+
+def unvarint_host(src: bytes, segs, dst_size, src_skew=0, dst_skew=0, tile_units=0, order_seed=0, fill=0):
+    """BrotliAmdDebugUnvarintHost: the LEB128 varints in `src` back into elements by the device's unit and tile functions on the host (no device
+    needed).  segs: [(source offset, source length, destination offset, capacity in elements, width, flags)]; the destination has dst_size bytes,
+    all `fill` in front of the call (or, where `fill` is bytes of that size, those); the buffers are placed at their skews past a 16-byte
+    boundary; tile_units: the 16-byte units of SOURCE in a tile (0: the kernel's); order_seed != 0 shuffles the order in which the tiles are
+    taken.  -> (the destination's bytes, [(count, consumed, overlong)])"""
+    L = load_library()
+    src = bytes(src)
+    n = len(segs)
+    before = bytes(fill) if isinstance(fill, (bytes, bytearray)) else bytes([fill]) * dst_size
+    if len(before) != dst_size:
+        raise ValueError("fill: %d bytes for a destination of %d" % (len(before), dst_size))
+    s_buf = ctypes.create_string_buffer(src, max(1, len(src)))
+    d_buf = ctypes.create_string_buffer(before, max(1, dst_size))
+    u64s = lambda k: (ctypes.c_uint64 * max(1, n))(*[s[k] if 0 <= s[k] < (1 << 64) else (1 << 64) - 1 for s in segs])
+    a_w = (ctypes.c_uint8 * max(1, n))(*[s[4] if 0 <= s[4] <= 255 else 0 for s in segs])
+    a_f = (ctypes.c_uint8 * max(1, n))(*[s[5] if 0 <= s[5] <= 255 else 255 for s in segs])
+    res = (UnvarintResult * max(1, n))()
+    if L.BrotliAmdDebugUnvarintHost(n, ctypes.addressof(s_buf), len(src), ctypes.addressof(d_buf), dst_size, u64s(0), u64s(1), u64s(2), u64s(3), a_w, a_f,
+                                    src_skew, dst_skew, tile_units, order_seed, res) != 0:
+        raise RuntimeError("BrotliAmdDebugUnvarintHost failed: " + last_error())
+    return d_buf.raw[:dst_size], [res[i].astuple() for i in range(n)]
+
+
+def unvarint_tile():
+    """BrotliAmdDebugUnvarintTile: the bytes of SOURCE in one tile of an unvarint call"""
+    return int(load_library().BrotliAmdDebugUnvarintTile())
 
 
 def undelta_tile():
@@ -672,6 +714,45 @@ class Batch:
         a_d, a_c = col(ctypes.c_void_p, [p or None for p in dst_ptrs], n), col(ctypes.c_uint64, counts, n, (1 << 64) - 1)
         a_f = self._byte_column(flags, n, "flags")
         self._filter_call("BrotliAmdBatchBitUnpackOutputs", a_d, a_c, self._byte_column(bits, n, "bits"), self._byte_column(widths, n, "widths", 0), a_f)
+
+    def unvarint_segments(self, src_ptrs, src_lens, dst_ptrs, caps, widths, flags=None, stream=None):
+        """BrotliAmdBatchUnvarintSegments: the LEB128 varints in the src_lens[i] bytes at the device address src_ptrs[i] become elements of
+        widths[i] bytes (1, 2, 4, 8) at dst_ptrs[i], the first caps[i] of them, by flags[i] (UNVARINT_ZIGZAG; None: all 0); any alignment, any
+        length; out of place; caps[i] == 0 needs no destination (dst_ptrs[i] may be None; dst_ptrs=None: none has one).  Three launches and a
+        wait on `stream`.  -> [(count, consumed, overlong)]: what each segment held, whatever its capacity was"""
+        n, col = len(src_ptrs), self._column
+        if len(src_lens) != n or (dst_ptrs is not None and len(dst_ptrs) != n) or len(caps) != n:
+            raise ValueError("src_ptrs, src_lens, dst_ptrs and caps: one entry per segment each")
+        a_d = None if dst_ptrs is None else col(ctypes.c_void_p, [p or None for p in dst_ptrs], n)
+        res = (UnvarintResult * max(1, n))()
+        self._filter_call("BrotliAmdBatchUnvarintSegments", n, col(ctypes.c_void_p, src_ptrs, n), col(ctypes.c_size_t, src_lens, n), a_d,
+                          col(ctypes.c_uint64, caps, n, (1 << 64) - 1), self._byte_column(widths, n, "widths", 0), self._byte_column(flags, n, "flags"), res, stream)
+        return [res[i].astuple() for i in range(n)]
+
+    def unvarint_outputs(self, dst_ptrs, caps, widths, flags=None):
+        """BrotliAmdBatchUnvarintOutputs: the delivered bytes of every stream of the last decode call on this object (after decode_device: once
+        wait() has returned), taken as LEB128 varints, become elements of widths[i] bytes at the device address dst_ptrs[i], the first caps[i]
+        of them (None or 0: the stream is skipped, and its result is zeros).  dst_ptrs=None or caps=None: every stream is counted and nothing is
+        written.  Three launches on that call's stream, and a wait.  -> [(count, consumed, overlong)], one per stream"""
+        n, col = self.out_n, self._column
+        if (dst_ptrs is not None and len(dst_ptrs) != n) or (caps is not None and len(caps) != n):
+            raise ValueError("dst_ptrs and caps: one entry per stream of the last decode call each")
+        a_d = None if dst_ptrs is None else col(ctypes.c_void_p, [p or None for p in dst_ptrs], n)
+        res = (UnvarintResult * max(1, n))()
+        self._filter_call("BrotliAmdBatchUnvarintOutputs", a_d, col(ctypes.c_uint64, caps, n, (1 << 64) - 1), self._byte_column(widths, n, "widths", 0),
+                          self._byte_column(flags, n, "flags"), res)
+        return [res[i].astuple() for i in range(n)]
+
+    def count_varints_outputs(self):
+        """unvarint_outputs without destinations: how many varints every stream of the last decode call holds, the bytes they take and the
+        overlong ones among them -> [(count, consumed, overlong)]; the way to size the destinations of the call that writes"""
+        return self.unvarint_outputs(None, None, [1] * self.out_n)
+
+    def last_unvarint_ms(self, phase=None):
+        """milliseconds the unvarint kernels took in the last unvarint_segments / unvarint_outputs: all launches together, or phase 1, 2 or 3"""
+        if phase is None:
+            return float(self._L.BrotliAmdBatchLastUnvarintMs(self._h))
+        return float(self._L.BrotliAmdBatchLastUnvarintPhaseMs(self._h, phase))
 
     def last_bitunpack_ms(self):
         """milliseconds the bit-unpack kernel took in the last bitunpack_segments / bitunpack_outputs"""

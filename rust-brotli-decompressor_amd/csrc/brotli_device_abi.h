@@ -140,6 +140,22 @@ typedef struct BrotliAmdUnshuffleSeg {
 // sign-extended).  A fast item of that kernel is 2 `width` words too, so it has the bit-unshuffle's tile: sixteen words a thread.
 #define BROTLI_AMD_BITUNPACK_TILE_BYTES 65536u  // destination bytes of one tile
 
+// One segment of an unvarint call (csrc/brotli_unvarint_kernels.hip, csrc/brotli_unvarint.h): the len bytes at src are LEB128 varints, and the
+// first `cap` of them become elements of `width` bytes (1, 2, 4 or 8) at dst, by `flags` (bit 0: zigzag); device addresses of any alignment,
+// len 0 and cap 0 included (cap 0: dst is not looked at).  The number of elements depends on the bytes, so the units are the words of SOURCE
+// memory, and every segment has a result (BrotliAmdUnvarintResult, include/brotli/batch.h) behind the table.  No destination range overlaps a
+// source range or another destination range.  Nothing outside [dst, dst + min(count, cap) width) is written; nothing outside the
+// 16-byte-aligned span around [src, src + len) is read.
+typedef struct BrotliAmdUnvarintSeg {
+  const uint8_t* src;
+  uint8_t* dst;
+  uint64_t len;
+  uint64_t cap;
+  uint32_t width;
+  uint32_t flags;
+} BrotliAmdUnvarintSeg;
+#define BROTLI_AMD_UNVARINT_TILE_BYTES 16384u  // source bytes of one tile: a tile's carry-in is the number of varints that end in front of it
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,14 +1,17 @@
 // brotli_filters.cpp -- the element filters on the device (include/brotli/batch.h): unshuffle (byte planes back into elements), undelta (deltas
-// back into values, a wrapping running sum per segment), bit-unshuffle (bit planes back into elements) and bit-unpack (k-bit fields back into
-// elements).  Each takes n segments of device memory (BrotliAmdBatch*Segments) or the delivered bytes of every stream of the last decode call
-// (BrotliAmdBatch*Outputs), in one launch -- undelta in three --, and each has a hook that runs the device's functions of its header
-// (csrc/brotli_unshuffle.h, brotli_undelta.h, brotli_bitunshuffle.h, brotli_bitunpack.h) on the host as the kernel's lanes take them, for tests
-// without a device.  What differs between the filters is a descriptor (kFilter), a check of a segment's shape, and the hook's loop.
+// back into values, a wrapping running sum per segment), bit-unshuffle (bit planes back into elements), bit-unpack (k-bit fields back into
+// elements) and unvarint (LEB128 varints back into elements, with a result per segment).  Each takes n segments of device memory
+// (BrotliAmdBatch*Segments) or the delivered bytes of every stream of the last decode call (BrotliAmdBatch*Outputs), in one launch -- undelta and
+// unvarint in three --, and each has a hook that runs the device's functions of its header (csrc/brotli_unshuffle.h, brotli_undelta.h,
+// brotli_bitunshuffle.h, brotli_bitunpack.h, brotli_unvarint.h) on the host as the kernel's lanes take them, for tests without a device.  What
+// differs between the filters is a descriptor (kFilter), a check of a segment's shape, and the hook's loop; unvarint has a segment of its own
+// (BrotliAmdUnvarintSeg: a source length and a capacity), whose units are its source's.
 #include "brotli_bitunpack.h"
 #include "brotli_bitunshuffle.h"
 #include "brotli_host.h"
 #include "brotli_undelta.h"
 #include "brotli_unshuffle.h"
+#include "brotli_unvarint.h"
 
 #include <numeric>
 
@@ -18,7 +21,12 @@ extern "C" hipError_t brotli_amd_launch_bitunshuffle(const BrotliAmdUnshuffleSeg
 extern "C" hipError_t brotli_amd_launch_bitunpack(const BrotliAmdUnshuffleSeg* d_segs, uint32_t n, uint64_t units, hipStream_t stream);
 extern "C" hipError_t brotli_amd_launch_undelta(const BrotliAmdUnshuffleSeg* d_segs, uint32_t n, uint64_t units, void* d_scratch, hipStream_t stream,
                                                 const hipEvent_t* ev);
+extern "C" hipError_t brotli_amd_launch_unvarint(const BrotliAmdUnvarintSeg* d_segs, uint32_t n, uint64_t units, void* d_scratch, hipStream_t stream,
+                                                 const hipEvent_t* ev);
 extern "C" uint64_t brotli_amd_undelta_scratch_bytes(uint64_t units);
+extern "C" uint64_t brotli_amd_unvarint_scratch_bytes(uint64_t units, uint32_t n);
+extern "C" uint64_t brotli_amd_unvarint_results_at(uint64_t units);
+extern "C" uint32_t brotli_amd_unvarint_tile_bytes(void);
 extern "C" uint32_t brotli_amd_unshuffle_tile_bytes(void);
 extern "C" uint32_t brotli_amd_undelta_tile_bytes(void);
 extern "C" uint32_t brotli_amd_undelta_carry_span(void);
@@ -29,29 +37,48 @@ using namespace brotli_amd_host;
 
 namespace {
 
-// What the host needs to know of a filter.  A filter of one launch (`launch`) has two events, recorded around it here; undelta (`launch_timed`)
-// has four, which its launcher records around and between its launches, and room behind the table that grows with the units.
+// What the host needs to know of a filter.  A filter of one launch (`launch`) has two events, recorded around it here; undelta and unvarint
+// (`launch_timed`, `launch_counted`: unvarint's table has its own segments) have four, which their launchers record around and between their
+// launches, and room behind the table that grows with the units -- unvarint's with the segments too, for their results.
 struct FilterDesc {
   const char* name;   // in the texts of g_last_error
   SegCallWhat what;
   const char* launch_what;
   hipError_t (*launch)(const BrotliAmdUnshuffleSeg*, uint32_t, uint64_t, hipStream_t);
   hipError_t (*launch_timed)(const BrotliAmdUnshuffleSeg*, uint32_t, uint64_t, void*, hipStream_t, const hipEvent_t*);
-  uint64_t (*scratch_bytes)(uint64_t units);   // behind the table (nullptr: nothing)
+  hipError_t (*launch_counted)(const BrotliAmdUnvarintSeg*, uint32_t, uint64_t, void*, hipStream_t, const hipEvent_t*);
+  uint64_t (*scratch_bytes)(uint64_t units, uint32_t n);   // behind the table (nullptr: nothing)
   uint32_t events;
 };
 const FilterDesc kFilter[kFilters] = {
     {"unshuffle", {"hipMalloc(unshuffle segments)", "hipMemcpyAsync(unshuffle segments)", "hipStreamSynchronize(unshuffle)"},
-     "brotli_amd_unshuffle_kernel launch", brotli_amd_launch_unshuffle, nullptr, nullptr, 2u},
+     "brotli_amd_unshuffle_kernel launch", brotli_amd_launch_unshuffle, nullptr, nullptr, nullptr, 2u},
     {"undelta", {"hipMalloc(undelta segments and tiles)", "hipMemcpyAsync(undelta segments)", "hipStreamSynchronize(undelta)"},
-     "brotli_amd_undelta kernels launch", nullptr, brotli_amd_launch_undelta, brotli_amd_undelta_scratch_bytes, 4u},
+     "brotli_amd_undelta kernels launch", nullptr, brotli_amd_launch_undelta, nullptr, [](uint64_t units, uint32_t) { return brotli_amd_undelta_scratch_bytes(units); }, 4u},
     {"bit-unshuffle", {"hipMalloc(bit-unshuffle segments)", "hipMemcpyAsync(bit-unshuffle segments)", "hipStreamSynchronize(bit-unshuffle)"},
-     "brotli_amd_bitunshuffle_kernel launch", brotli_amd_launch_bitunshuffle, nullptr, nullptr, 2u},
+     "brotli_amd_bitunshuffle_kernel launch", brotli_amd_launch_bitunshuffle, nullptr, nullptr, nullptr, 2u},
     {"bit-unpack", {"hipMalloc(bit-unpack segments)", "hipMemcpyAsync(bit-unpack segments)", "hipStreamSynchronize(bit-unpack)"},
-     "brotli_amd_bitunpack_kernel launch", brotli_amd_launch_bitunpack, nullptr, nullptr, 2u},
+     "brotli_amd_bitunpack_kernel launch", brotli_amd_launch_bitunpack, nullptr, nullptr, nullptr, 2u},
+    {"unvarint", {"hipMalloc(unvarint segments, tiles and results)", "hipMemcpyAsync(unvarint segments)", "hipStreamSynchronize(unvarint)"},
+     "brotli_amd_unvarint kernels launch", nullptr, nullptr, brotli_amd_launch_unvarint, brotli_amd_unvarint_scratch_bytes, 4u},
 };
 
 typedef std::vector<BrotliAmdUnshuffleSeg> Segs;
+typedef std::vector<BrotliAmdUnvarintSeg> VarintSegs;
+
+// a segment's units: its destination's words, unvarint's its source's (brotli_seg_walk.h)
+inline uint64_t units_of(const BrotliAmdUnshuffleSeg& s) { return brotli_amd_seg_units((uint64_t)(uintptr_t)s.dst, s.len); }
+inline uint64_t units_of(const BrotliAmdUnvarintSeg& s) { return brotli_amd_seg_units((uint64_t)(uintptr_t)s.src, s.len); }
+// a filter's launches over its table
+inline hipError_t launch_of(const FilterDesc& d, const BrotliAmdUnshuffleSeg* d_segs, uint32_t n, uint64_t units, void* d_scratch, hipStream_t stream, const hipEvent_t* ev) {
+  return d.launch_timed(d_segs, n, units, d_scratch, stream, ev);
+}
+inline hipError_t launch_of(const FilterDesc& d, const BrotliAmdUnvarintSeg* d_segs, uint32_t n, uint64_t units, void* d_scratch, hipStream_t stream, const hipEvent_t* ev) {
+  return d.launch_counted(d_segs, n, units, d_scratch, stream, ev);
+}
+// ... of one launch (unvarint has none of these)
+inline hipError_t launch_of(const FilterDesc& d, const BrotliAmdUnshuffleSeg* d_segs, uint32_t n, uint64_t units, hipStream_t stream) { return d.launch(d_segs, n, units, stream); }
+inline hipError_t launch_of(const FilterDesc&, const BrotliAmdUnvarintSeg*, uint32_t, uint64_t, hipStream_t) { return hipErrorInvalidValue; }
 
 int invalid_arguments(Filter f) { g_last_error = std::string("invalid ") + kFilter[f].name + " arguments"; return -1; }
 
@@ -59,25 +86,32 @@ int invalid_arguments(Filter f) { g_last_error = std::string("invalid ") + kFilt
 void no_times(BrotliAmdBatch* b, Filter f) {
   b->filter[f].ms = 0.0f;
   if (f == kUndelta) for (float& ms : b->undelta_phase_ms) ms = 0.0f;
+  if (f == kUnvarint) for (float& ms : b->unvarint_phase_ms) ms = 0.0f;
 }
 
-// segs on `stream`, waited for (their shapes were checked)
-int filter_device(BrotliAmdBatch* b, Filter f, const Segs& segs, hipStream_t stream) {
+// segs on `stream`, waited for (their shapes were checked).  units_out: their units together; scratch_out: the device memory behind the table,
+// where unvarint's results lie until the next call (nullptr: nothing was launched)
+template <class Seg>
+int filter_device(BrotliAmdBatch* b, Filter f, const std::vector<Seg>& segs, hipStream_t stream, uint64_t* units_out = nullptr,
+                  const uint8_t** scratch_out = nullptr) {
+  if (scratch_out) *scratch_out = nullptr;
   if (segs.empty()) return 0;
   DeviceGuard guard;
   if (!hip_ok(hipSetDevice(b->device), "hipSetDevice")) return -1;
   const FilterDesc& d = kFilter[f];
   const uint32_t n = (uint32_t)segs.size();
-  uint64_t units = 0;   // of their destinations together (brotli_seg_walk.h)
-  for (const BrotliAmdUnshuffleSeg& s : segs) units += brotli_amd_seg_units((uint64_t)(uintptr_t)s.dst, s.len);
+  uint64_t units = 0;   // of all segments together (brotli_seg_walk.h)
+  for (const Seg& s : segs) units += units_of(s);
+  if (units_out) *units_out = units;
   if (units == 0u) return 0;   // (segments without bytes: nothing to launch)
-  return run_seg_call(&b->filter[f].call, d.what, segs.data(), sizeof(BrotliAmdUnshuffleSeg) * n, d.scratch_bytes ? d.scratch_bytes(units) : 0u, d.events, stream,
+  return run_seg_call(&b->filter[f].call, d.what, segs.data(), sizeof(Seg) * n, d.scratch_bytes ? d.scratch_bytes(units, n) : 0u, d.events, stream,
                       [&](uint8_t* d_table, uint8_t* d_scratch, const hipEvent_t* ev) {
-    const BrotliAmdUnshuffleSeg* d_segs = reinterpret_cast<BrotliAmdUnshuffleSeg*>(d_table);
-    if (d.launch_timed) return hip_ok(d.launch_timed(d_segs, n, units, d_scratch, stream, ev), d.launch_what);
-    return hip_ok(hipEventRecord(ev[0], stream), "hipEventRecord") && hip_ok(d.launch(d_segs, n, units, stream), d.launch_what) &&
+    const Seg* d_segs = reinterpret_cast<Seg*>(d_table);
+    if (scratch_out) *scratch_out = d_scratch;
+    if (!d.launch) return hip_ok(launch_of(d, d_segs, n, units, d_scratch, stream, ev), d.launch_what);
+    return hip_ok(hipEventRecord(ev[0], stream), "hipEventRecord") && hip_ok(launch_of(d, d_segs, n, units, stream), d.launch_what) &&
            hip_ok(hipEventRecord(ev[1], stream), "hipEventRecord");
-  }, &b->filter[f].ms, f == kUndelta ? b->undelta_phase_ms : nullptr);
+  }, &b->filter[f].ms, f == kUndelta ? b->undelta_phase_ms : f == kUnvarint ? b->unvarint_phase_ms : nullptr);
 }
 
 // ---- a call's segments, each checked in front of everything that touches the device ----
@@ -180,6 +214,38 @@ void packed_shape(BrotliAmdUnshuffleSeg* s, uint64_t count, uint32_t bits, uint3
   s->len = count * width; s->width = width; s->param = brotli_amd_bitunpack_param(bits, flags);
 }
 
+// ---- unvarint: a width, flags and a capacity; a result per segment ----
+// `who` names the segment or stream in the text
+bool known_varint(uint32_t width, uint32_t flags, uint64_t cap, bool has_dst, const char* who, size_t i) {
+  const char* what = nullptr;
+  if (!brotli_amd_unshuffle_width_ok(width)) what = "width is not 1, 2, 4 or 8";
+  else if ((flags & ~BROTLI_AMD_UNVARINT_FLAGS) != 0u) what = "unknown flag bits";
+  else if (cap > BROTLI_AMD_UNVARINT_MAX_CAP) what = "a capacity above 2^56 elements";
+  else if (cap != 0u && !has_dst) what = "no destination for a capacity that is not 0";
+  if (!what) return true;
+  g_last_error = std::string("unvarint ") + who + " " + std::to_string(i) + ": " + what + " (width " + std::to_string(width) + ", flags " + std::to_string(flags) +
+                 ", capacity " + std::to_string(cap) + ")";
+  return false;
+}
+
+// segs on `stream`, waited for, and their results: segment j's to results[where[j]] of the n_results, the others zeros
+int varint_device(BrotliAmdBatch* b, const VarintSegs& segs, const std::vector<size_t>& where, BrotliAmdUnvarintResult* results, size_t n_results,
+                  hipStream_t stream) {
+  std::fill(results, results + n_results, BrotliAmdUnvarintResult{0u, 0u, 0u});
+  uint64_t units = 0;
+  const uint8_t* d_scratch = nullptr;
+  if (filter_device(b, kUnvarint, segs, stream, &units, &d_scratch) != 0) return -1;
+  if (!d_scratch) return 0;   // (segments without bytes: their results are zeros)
+  std::vector<BrotliAmdUnvarintResult> got(segs.size());
+  DeviceGuard guard;
+  if (!hip_ok(hipSetDevice(b->device), "hipSetDevice") ||
+      !hip_ok(hipMemcpy(got.data(), d_scratch + brotli_amd_unvarint_results_at(units), sizeof(BrotliAmdUnvarintResult) * got.size(), hipMemcpyDeviceToHost),
+              "hipMemcpy(unvarint results)"))
+    return -1;
+  for (size_t j = 0; j < got.size(); j++) results[where[j]] = got[j];
+  return 0;
+}
+
 // ---- the hooks ----
 // what a hook of one segment ends with: no byte beside the len bytes of the destination may have changed; they go to dst
 int hook_result(Filter f, const SkewedRoom& droom, uint8_t* dst, size_t len) {
@@ -243,11 +309,52 @@ extern "C" int BrotliAmdBatchBitUnpackOutputs(BrotliAmdBatch* b, void* const* d_
   return filter_device(b, kBitUnpack, segs, b->last_stream);
 }
 
+extern "C" int BrotliAmdBatchUnvarintSegments(BrotliAmdBatch* b, uint32_t n, const void* const* d_src, const size_t* src_lens, void* const* d_dst,
+                                              const uint64_t* caps, const uint8_t* widths, const uint8_t* flags, BrotliAmdUnvarintResult* results, void* hip_stream) {
+  if (!b || (n && (!d_src || !src_lens || !caps || !widths || !results))) return invalid_arguments(kUnvarint);
+  no_times(b, kUnvarint);
+  VarintSegs segs;
+  std::vector<size_t> where(n);
+  segs.reserve(n);
+  for (uint32_t i = 0; i < n; i++) {
+    void* dst = d_dst ? d_dst[i] : nullptr;   // (no array of destinations: a call that counts, where every capacity is 0)
+    const uint32_t f = flags ? flags[i] : 0u;
+    if (!known_varint(widths[i], f, caps[i], dst != nullptr, "segment", i)) return -1;
+    segs.push_back(BrotliAmdUnvarintSeg{static_cast<const uint8_t*>(d_src[i]), static_cast<uint8_t*>(dst), src_lens[i], caps[i], widths[i], f});
+    where[i] = i;
+  }
+  return varint_device(b, segs, where, results, n, static_cast<hipStream_t>(hip_stream));
+}
+
+extern "C" int BrotliAmdBatchUnvarintOutputs(BrotliAmdBatch* b, void* const* d_dst, const uint64_t* caps, const uint8_t* widths, const uint8_t* flags,
+                                             BrotliAmdUnvarintResult* results) {
+  if (!b || !widths || !results) return invalid_arguments(kUnvarint);
+  no_times(b, kUnvarint);
+  std::vector<DeliveredBytes> outs;
+  if (!delivered_outputs(b, &outs)) return -1;
+  const bool count_only = !d_dst || !caps;   // every stream is counted and nothing is written
+  VarintSegs segs;
+  std::vector<size_t> where;
+  segs.reserve(outs.size());
+  for (size_t i = 0; i < outs.size(); i++) {
+    if (!count_only && d_dst[i] == nullptr) continue;   // skipped: none of its parameters are looked at
+    const uint32_t f = flags ? flags[i] : 0u;
+    const uint64_t cap = count_only ? 0u : caps[i];
+    if (!known_varint(widths[i], f, cap, !count_only, "stream", i)) return -1;
+    segs.push_back(BrotliAmdUnvarintSeg{outs[i].ptr, count_only ? nullptr : static_cast<uint8_t*>(d_dst[i]), outs[i].len, cap, widths[i], f});
+    where.push_back(i);
+  }
+  return varint_device(b, segs, where, results, outs.size(), b->last_stream);
+}
+
 extern "C" float BrotliAmdBatchLastUnshuffleMs(BrotliAmdBatch* b) { return b ? b->filter[kUnshuffle].ms : 0.0f; }
 extern "C" float BrotliAmdBatchLastUndeltaMs(BrotliAmdBatch* b) { return b ? b->filter[kUndelta].ms : 0.0f; }
 extern "C" float BrotliAmdBatchLastUndeltaPhaseMs(BrotliAmdBatch* b, uint32_t phase) { return b && phase >= 1u && phase <= 3u ? b->undelta_phase_ms[phase - 1u] : 0.0f; }
 extern "C" float BrotliAmdBatchLastBitUnshuffleMs(BrotliAmdBatch* b) { return b ? b->filter[kBitUnshuffle].ms : 0.0f; }
 extern "C" float BrotliAmdBatchLastBitUnpackMs(BrotliAmdBatch* b) { return b ? b->filter[kBitUnpack].ms : 0.0f; }
+extern "C" float BrotliAmdBatchLastUnvarintMs(BrotliAmdBatch* b) { return b ? b->filter[kUnvarint].ms : 0.0f; }
+extern "C" float BrotliAmdBatchLastUnvarintPhaseMs(BrotliAmdBatch* b, uint32_t phase) { return b && phase >= 1u && phase <= 3u ? b->unvarint_phase_ms[phase - 1u] : 0.0f; }
+extern "C" uint32_t BrotliAmdDebugUnvarintTile(void) { return brotli_amd_unvarint_tile_bytes(); }
 extern "C" uint32_t BrotliAmdDebugUnshuffleTile(void) { return brotli_amd_unshuffle_tile_bytes(); }
 extern "C" uint32_t BrotliAmdDebugUndeltaTile(void) { return brotli_amd_undelta_tile_bytes(); }
 extern "C" uint32_t BrotliAmdDebugUndeltaCarrySpan(void) { return brotli_amd_undelta_carry_span(); }
@@ -363,5 +470,67 @@ extern "C" int BrotliAmdDebugUndeltaHost(uint32_t n, const uint8_t* src, size_t 
   for (uint32_t i = 0; i < n; i++) std::fill(inside.begin() + dst_offs[i], inside.begin() + dst_offs[i] + lens[i], 1);
   if (!droom.changed_inside_only([&](size_t i) { return i < dst_size && inside[i]; })) { g_last_error = "undelta wrote outside its destination"; return -2; }
   for (uint32_t i = 0; i < n; i++) droom.get(dst + dst_offs[i], dst_offs[i], lens[i]);
+  return 0;
+}
+
+// Unvarint's three phases, tile by tile, over n segments given as offsets into one source and one destination buffer, each buffer in its room.
+extern "C" int BrotliAmdDebugUnvarintHost(uint32_t n, const uint8_t* src, size_t src_size, uint8_t* dst, size_t dst_size, const uint64_t* src_offs,
+                                          const uint64_t* src_lens, const uint64_t* dst_offs, const uint64_t* caps, const uint8_t* widths, const uint8_t* flags,
+                                          uint32_t src_skew, uint32_t dst_skew, uint32_t tile_units, uint32_t order_seed, BrotliAmdUnvarintResult* results) {
+  if ((n && (!src_offs || !src_lens || !dst_offs || !caps || !widths || !results)) || (src_size && !src) || (dst_size && !dst) || src_skew > 15u || dst_skew > 15u)
+    return invalid_arguments(kUnvarint);
+  for (uint32_t i = 0; i < n; i++) {
+    if (!known_varint(widths[i], flags ? flags[i] : 0u, caps[i], true, "segment", i)) return -1;
+    const uint64_t room = std::min<uint64_t>(caps[i], src_lens[i]) * widths[i];   // (a segment of len bytes holds len varints at the most)
+    if (src_lens[i] > src_size || src_offs[i] > src_size - src_lens[i] || room > dst_size || dst_offs[i] > dst_size - room) {
+      g_last_error = "invalid unvarint arguments: a segment outside its buffer";
+      return -1;
+    }
+  }
+  if (tile_units == 0u) tile_units = brotli_amd_unvarint_tile_bytes() / 16u;
+  SkewedRoom sroom(src_size, src_skew, 0xA5), droom(dst_size, dst_skew, 0x5A);
+  sroom.put(src, src_size);
+  droom.put(dst, dst_size);
+  VarintSegs segs(n);
+  std::vector<uint64_t> pre(n + 1u, 0u);
+  for (uint32_t i = 0; i < n; i++) {
+    const uint64_t s = sroom.at() + src_offs[i], d = droom.at() + dst_offs[i];
+    segs[i] = BrotliAmdUnvarintSeg{reinterpret_cast<const uint8_t*>((uintptr_t)s), reinterpret_cast<uint8_t*>((uintptr_t)d), src_lens[i], caps[i], widths[i],
+                                   flags ? flags[i] : 0u};
+    pre[i + 1u] = pre[i] + brotli_amd_seg_units(s, src_lens[i]);
+  }
+  droom.snapshot();
+  const uint64_t units = pre[n], ntiles = (units + tile_units - 1u) / tile_units;
+  // phases 1 and 3 take the tiles in an order shuffled by the seed: the result may not depend on it
+  std::vector<uint64_t> order(ntiles);
+  std::iota(order.begin(), order.end(), (uint64_t)0);
+  uint32_t rnd = order_seed * 2654435761u + 1u;
+  auto shuffle = [&]() {
+    if (order_seed == 0u) return;
+    for (uint64_t i = ntiles; i > 1u; i--) { rnd = rnd * 1664525u + 1013904223u; std::swap(order[i - 1u], order[(rnd >> 8) % i]); }
+  };
+  auto tile_end = [&](uint64_t t) { return std::min<uint64_t>((t + 1u) * tile_units, units); };
+  std::vector<BrotliAmdUndeltaTile> tiles(ntiles);
+  std::vector<uint64_t> carries(ntiles);
+  std::vector<BrotliAmdUnvarintResult> got(n, BrotliAmdUnvarintResult{0u, 0u, 0u});
+  shuffle();
+  for (uint64_t t : order) tiles[t] = brotli_amd_unvarint_host_summary(segs.data(), pre.data(), n, t * tile_units, tile_end(t));
+  BrotliAmdUndeltaPair out = {0u, 0u};
+  for (uint64_t t = 0; t < ntiles; t++) {
+    carries[t] = brotli_amd_undelta_carry_in(out.sum, tiles[t]);
+    out = brotli_amd_undelta_combine(out, brotli_amd_undelta_tile_pair(tiles[t]));
+  }
+  shuffle();
+  for (uint64_t t : order) brotli_amd_unvarint_host_emit(segs.data(), pre.data(), n, t * tile_units, tile_end(t), carries[t], got.data());
+  // no byte outside every segment's elements may have changed
+  std::vector<uint8_t> inside(dst_size, 0);
+  for (uint32_t i = 0; i < n; i++) {
+    const uint64_t bytes = std::min(got[i].count, caps[i]) * widths[i];
+    if (bytes > dst_size - dst_offs[i]) { g_last_error = "unvarint counted more varints than the segment has bytes"; return -2; }
+    std::fill(inside.begin() + dst_offs[i], inside.begin() + dst_offs[i] + bytes, 1);
+  }
+  if (!droom.changed_inside_only([&](size_t i) { return i < dst_size && inside[i]; })) { g_last_error = "unvarint wrote outside its destination"; return -2; }
+  droom.get(dst, 0u, dst_size);
+  std::copy(got.begin(), got.end(), results);
   return 0;
 }

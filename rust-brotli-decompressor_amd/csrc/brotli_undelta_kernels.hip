@@ -206,6 +206,13 @@ extern "C" uint64_t brotli_amd_undelta_scratch_bytes(uint64_t units) {
   return ((units + kTileUnits - 1u) / kTileUnits) * (sizeof(BrotliAmdUndeltaTile) + sizeof(uint64_t));
 }
 
+// The carry launch alone, for every call whose tiles leave BrotliAmdUndeltaTile records (undelta's sums, unvarint's counts of ends): ONE block turns
+// tiles[0..ntiles) into carries[0..ntiles) on `stream`.
+extern "C" hipError_t brotli_amd_launch_tile_carries(const BrotliAmdUndeltaTile* tiles, uint64_t* carries, uint64_t ntiles, hipStream_t stream) {
+  hipLaunchKernelGGL(brotli_amd_undelta_carry_kernel, dim3(1), dim3(kCarryThreads), 0, stream, tiles, carries, ntiles);
+  return hipGetLastError();
+}
+
 // units: the units of all segments together (brotli_amd_seg_units: the host has the table); d_scratch: brotli_amd_undelta_scratch_bytes
 // of device memory, 16-byte aligned; ev[0..3], where not NULL, are recorded in front of, between and behind the three launches
 extern "C" hipError_t brotli_amd_launch_undelta(const BrotliAmdUnshuffleSeg* d_segs, uint32_t n, uint64_t units, void* d_scratch, hipStream_t stream,
@@ -221,8 +228,7 @@ extern "C" hipError_t brotli_amd_launch_undelta(const BrotliAmdUnshuffleSeg* d_s
   hipLaunchKernelGGL(brotli_amd_undelta_sum_kernel, dim3(grid), dim3(kThreads), 0, stream, d_segs, n, units, tiles);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if (ev && (e = hipEventRecord(ev[1], stream)) != hipSuccess) return e;
-  hipLaunchKernelGGL(brotli_amd_undelta_carry_kernel, dim3(1), dim3(kCarryThreads), 0, stream, tiles, carries, ntiles);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if ((e = brotli_amd_launch_tile_carries(tiles, carries, ntiles, stream)) != hipSuccess) return e;
   if (ev && (e = hipEventRecord(ev[2], stream)) != hipSuccess) return e;
   hipLaunchKernelGGL(brotli_amd_undelta_apply_kernel, dim3(grid), dim3(kThreads), 0, stream, d_segs, n, carries);
   if ((e = hipGetLastError()) != hipSuccess) return e;

@@ -11,7 +11,10 @@ transpose of the bitshuffle library and HDF5 filter 32008, the bit-shuffle mode 
 block size where there is one, and its bit planes are turned back by one call for all such streams (Batch.bitunshuffle_outputs).  A stream
 whose array was BIT-PACKED -- fields of k bits back to back: Parquet's bit-packed runs, Arrow's validity bitmaps, 4-bit weights,
 numpy.packbits -- names k in its spec; it is the one stream whose slot is larger than its delivered bytes, and one call unpacks all such
-streams into their slots (Batch.bitunpack_outputs)."""
+streams into their slots (Batch.bitunpack_outputs).  A stream whose array was stored as VARINTS -- LEB128, protobuf's base-128 integers, plain or
+zigzag: packed repeated fields, postings lists, offset tables -- says so in its spec; its size depends on its values, so one call decodes all such
+streams into their slots and says how many integers each held (Batch.unvarint_outputs), and a stream that held another number than its shape
+says, unfinished bytes or an integer of more than ten bytes is refused."""
 import collections
 
 import torch
@@ -26,19 +29,20 @@ def _numel(shape):
     return n
 
 
-FILTERS = ("shuffle", "delta", "bitshuffle", "bitpack")
+FILTERS = ("shuffle", "delta", "bitshuffle", "bitpack", "varint")
 BITPACK_OPTIONS = {"big": 1, "signed": 2}   # BITUNPACK_MSB_FIRST, BITUNPACK_SIGNED
+VARINT_OPTIONS = {"zigzag": 1}              # UNVARINT_ZIGZAG
 
 
 # What a wanted stream's spec says: the slot's bytes, the tensor's dtype and shape, the element width, the names of its filters, bitshuffle's block
-# and bitpack's (k, flags) -- (1, 0) where the stream is not packed, as for a stream that is not wanted
-_Stream = collections.namedtuple("_Stream", "want dtype shape item filters block pack")
+# and bitpack's (k, flags) -- (1, 0) where the stream is not packed, as for a stream that is not wanted --, varint's flags
+_Stream = collections.namedtuple("_Stream", "want dtype shape item filters block pack varint")
 
 
 def _parse_spec(i, spec, size):
     """spec of stream i, which delivered `size` bytes -> _Stream; ValueError, naming the stream, for what outputs_as_tensors refuses"""
     dtype, shape = spec[0], spec[1]
-    flt, block, pack = [], 0, None
+    flt, block, pack, varint = [], 0, None, 0
     for name in (tuple(spec[2]) if len(spec) > 2 else ("shuffle",)):
         if isinstance(name, (tuple, list)) and len(name) == 2 and name[0] == "bitshuffle":   # ("bitshuffle", block_elems)
             name, block = name[0], int(name[1])
@@ -53,6 +57,14 @@ def _parse_spec(i, spec, size):
             name, pack = name[0], (int(name[1]), sum({BITPACK_OPTIONS[opt] for opt in name[2:]}))
         elif name == "bitpack":
             raise ValueError("stream %d: \"bitpack\" without its field width: (\"bitpack\", k)" % i)
+        if isinstance(name, (tuple, list)) and len(name) >= 1 and name[0] == "varint":   # ("varint", options...)
+            for opt in name[1:]:
+                if opt not in VARINT_OPTIONS:
+                    raise ValueError("stream %d: unknown varint option %r (known: %s)" % (i, opt, ", ".join(VARINT_OPTIONS)))
+            name, varint = name[0], sum({VARINT_OPTIONS[opt] for opt in name[1:]})
+        if name in VARINT_OPTIONS and flt and flt[-1] == "varint":   # ("varint", "zigzag") as the spec's filters: the option right behind its filter
+            varint |= VARINT_OPTIONS[name]
+            continue
         if name not in FILTERS:
             raise ValueError("stream %d: unknown filter %r (known: %s)" % (i, name, ", ".join(FILTERS)))
         flt.append(name)
@@ -61,6 +73,8 @@ def _parse_spec(i, spec, size):
         raise ValueError("stream %d: \"shuffle\" and \"bitshuffle\" in one spec: an array goes through one of them" % i)
     if pack is not None and ("shuffle" in flt or "bitshuffle" in flt):
         raise ValueError("stream %d: \"bitpack\" with \"shuffle\" or \"bitshuffle\" in one spec: packed fields have no byte or bit planes" % i)
+    if "varint" in flt and ("shuffle" in flt or "bitshuffle" in flt or pack is not None):
+        raise ValueError("stream %d: \"varint\" with \"shuffle\", \"bitshuffle\" or \"bitpack\" in one spec: integers of variable length have no planes and no fields" % i)
     shape = tuple(int(d) for d in (shape if isinstance(shape, (tuple, list, torch.Size)) else (shape,)))
     item = torch.empty(0, dtype=dtype).element_size()
     if item not in (1, 2, 4, 8):
@@ -72,9 +86,11 @@ def _parse_spec(i, spec, size):
         stored = (_numel(shape) * pack[0] + 7) // 8
         if size != stored:
             raise ValueError("stream %d: %d delivered bytes, but %d fields of %d bits (shape %s) are %d" % (i, size, _numel(shape), pack[0], shape, stored))
+    elif "varint" in flt:
+        pass   # (how many integers the delivered bytes hold is the call's to say: outputs_as_tensors checks its result)
     elif size != want:
         raise ValueError("stream %d: %d delivered bytes, but %s of shape %s is %d" % (i, size, dtype, shape, want))
-    return _Stream(want, dtype, shape, item, flt, block, pack or (1, 0))
+    return _Stream(want, dtype, shape, item, flt, block, pack or (1, 0), varint)
 
 
 def outputs_as_tensors(batch, specs):
@@ -98,6 +114,13 @@ def outputs_as_tensors(batch, specs):
                                               stream must have delivered exactly ceil(numel k / 8) bytes; its slot is numel x itemsize
         (dtype, shape, (("bitpack", 4, "signed"),))  ... sign-extended from bit k - 1; "big" behind k: MSB-first (numpy.packbits, PNG); both may stand
         (dtype, shape, (("bitpack", 20), "delta"))  packed deltas (frame of reference): that call, then Batch.undelta_segments in place
+        (dtype, shape, ("varint",))           numel LEB128 varints, each truncated to the dtype's elements: ONE Batch.unvarint_outputs call for
+                                              all such streams, into the slots.  ValueError, naming the stream, where the delivered bytes hold
+                                              another number of varints than numel, end in an unfinished one, or hold one of more than ten bytes
+        (dtype, shape, (("varint", "zigzag"),))  ... zigzag: (v >> 1) ^ -(v & 1), the signed integers of protobuf's sint64 and Avro's long;
+                                              ("varint", "zigzag") as the filters, the option right behind its filter, says the same
+        (dtype, shape, ("varint", "delta"))   varints of deltas (sorted ids, postings): that call, then Batch.undelta_segments in place
+    "varint" together with "shuffle", "bitshuffle" or "bitpack" in one spec raises ValueError, naming the stream.
     "shuffle" together with "bitshuffle", and "bitpack" together with either, in one spec raises ValueError, naming the stream; so does a k outside
     1 .. 8 x itemsize and an unknown option.
     Delta is a wrapping running sum over the flattened array, on the dtype's BIT PATTERN taken as a little-endian unsigned integer of its
@@ -128,16 +151,28 @@ def outputs_as_tensors(batch, specs):
     wanted = [i for i, st in enumerate(streams) if st is not None]
     bits = [i for i in wanted if "bitshuffle" in streams[i].filters]
     packed = [i for i in wanted if "bitpack" in streams[i].filters]
+    varints = [i for i in wanted if "varint" in streams[i].filters]
     # deltas only: every other wanted stream that is neither of bit planes nor of packed fields is the unshuffle call's; without "shuffle" it is
     # a copy -- width 1
-    plain = [i for i in wanted if i not in bits and i not in packed and "shuffle" not in streams[i].filters and "delta" in streams[i].filters]
-    batch.unshuffle_outputs(only([i for i in wanted if i not in plain and i not in bits and i not in packed]),
+    plain = [i for i in wanted if i not in bits and i not in packed and i not in varints and "shuffle" not in streams[i].filters and "delta" in streams[i].filters]
+    batch.unshuffle_outputs(only([i for i in wanted if i not in plain and i not in bits and i not in packed and i not in varints]),
                             [st.item if st is not None and "shuffle" in st.filters else 1 for st in streams])
     if bits:    # bit planes: from the outputs straight into the slots
         batch.bitunshuffle_outputs(only(bits), widths, [0 if st is None else st.block for st in streams])
     if packed:  # packed fields: from the outputs straight into the slots, which are larger than the outputs
         batch.bitunpack_outputs(only(packed), [1 if st is None else st.pack[0] for st in streams], widths,
                                 [0 if st is None else _numel(st.shape) for st in streams], [0 if st is None else st.pack[1] for st in streams])
+    if varints:  # varints: from the outputs straight into the slots, numel elements each; what a stream held must be exactly that
+        res = batch.unvarint_outputs(only(varints), [0 if st is None else _numel(st.shape) for st in streams], widths,
+                                     [0 if st is None else st.varint for st in streams])
+        for i in varints:
+            count, consumed, overlong = res[i]
+            if count != _numel(streams[i].shape):
+                raise ValueError("stream %d: %d varints, but shape %s is %d elements" % (i, count, streams[i].shape, _numel(streams[i].shape)))
+            if consumed != sizes[i]:
+                raise ValueError("stream %d: %d delivered bytes, but its varints end after %d: an unfinished one trails them" % (i, sizes[i], consumed))
+            if overlong != 0:
+                raise ValueError("stream %d: %d varints of more than ten bytes" % (i, overlong))
     if plain:   # deltas only: from the outputs straight into the slots
         batch.undelta_outputs(only(plain), widths)
     both = [i for i in wanted if i not in plain and "delta" in streams[i].filters]
