@@ -488,7 +488,7 @@ BROTLI_DEC_API int BrotliAmdDebugBitUnpackHost(uint32_t bits, uint32_t width, ui
  *
  * The fifth layout in front of the codec is the VARIABLE-LENGTH INTEGER -- LEB128, protobuf's base-128 varint, plain or zigzag: protobuf packed
  * repeated fields, the block and miniblock headers and first values of Parquet's DELTA_BINARY_PACKED and DELTA_LENGTH_BYTE_ARRAY, the run headers
- * of its RLE / bit-packed hybrid, ORC's integer runs, Avro's zigzag longs, the postings lists and offset tables of search indexes, sorted ids
+ * of its RLE / bit-packed hybrid (a whole stream of which is the unrle calls' below), ORC's integer runs, Avro's zigzag longs, the postings lists and offset tables of search indexes, sorted ids
  * stored as varint deltas (which the undelta calls above then sum up).  It is the one filter here whose output size DEPENDS ON THE DATA: every
  * segment has a capacity and gets a result.
  *
@@ -573,6 +573,124 @@ BROTLI_DEC_API int BrotliAmdDebugUnvarintHost(uint32_t n, const uint8_t* src, si
                                              const uint64_t* src_lens, const uint64_t* dst_offs, const uint64_t* caps, const uint8_t* widths,
                                              const uint8_t* flags /* or NULL */, uint32_t src_skew, uint32_t dst_skew, uint32_t tile_units,
                                              uint32_t order_seed, BrotliAmdUnvarintResult* results);
+
+/* ---- Unrle on the device: RLE / bit-packed hybrid runs of outputs back into elements ----
+ *
+ * The sixth layout in front of the codec is the RUN: Parquet's RLE / bit-packed hybrid, which holds the dictionary indices of every
+ * dictionary-encoded column, the definition and repetition levels, and the booleans of v2 pages.  It is a varint header and then either
+ * bit-unpack's packed fields or one repeated value; where a header lies depends on every header in front of it, so neither of the two calls
+ * above can take it.  Like unvarint, its output size DEPENDS ON THE DATA: every segment has a capacity and gets a result.
+ *
+ * THE SEGMENT AND ITS PARAMETERS.  A segment is the bytes src[0, len), with a field width k in bits (0 .. 32), an element width w in
+ * {1, 2, 4, 8} with k <= 8 w, flags, and a capacity cap in elements.  It is a sequence of RUNS, decoded from offset 0 (offset 1 with
+ * BROTLI_AMD_UNRLE_WIDTH_BYTE) until the segment's end or the first STOP.
+ *
+ * HEADER.  h is a LEB128 varint of 1 .. 5 bytes, low group first.  Its up to 35 bits are taken as they are: nothing is dropped.
+ * BIT-PACKED RUN, h & 1 == 1: g = h >> 1 groups, 8 g values.  The payload is g k bytes: fields of k bits, LSB-first, zero-extended --
+ *   bit-unpack's default form.
+ * RLE RUN, h & 1 == 0: c = h >> 1 values.  The payload is ceil(k / 8) bytes: a little-endian value, repeated c times.  The value is NOT
+ *   masked to k bits; it is zero-extended to w bytes.
+ * k == 0: both payloads are empty and every value is 0 (a dictionary of one entry).
+ * BROTLI_AMD_UNRLE_WIDTH_BYTE: the segment's first byte is k (Parquet's dictionary-index page body); the `bits` argument is not looked at.  A
+ *   k above 32 or above 8 w stops the decode, and so does an empty segment.
+ *
+ * STORES.  Element i of the concatenated runs, truncated to w bytes, goes to dst + i w, little-endian, for i < min(count, cap).  dst has any
+ * alignment.  No byte outside [dst, dst + min(count, cap) w) is written; nothing outside the 16-byte-aligned span around [src, src + len)
+ * is read.
+ *
+ * STOPS.  The decode ends at the first stop; everything in front of it is delivered.
+ *   status                        when                                       values counted                              consumed
+ *   BROTLI_AMD_UNRLE_OK           the runs end exactly at len                all                                         len
+ *   BROTLI_AMD_UNRLE_BAD_HEADER   a header's fifth byte has bit 7 set        the runs in front                           that header's offset
+ *   BROTLI_AMD_UNRLE_ZERO_RUN     h >> 1 == 0                                the runs in front                           that header's offset
+ *   BROTLI_AMD_UNRLE_TRUNCATED    a header's continuation reaches len        the runs in front                           that header's offset
+ *   BROTLI_AMD_UNRLE_TRUNCATED    an RLE value reaches len                   the runs in front                           that header's offset
+ *   BROTLI_AMD_UNRLE_TRUNCATED    a bit-packed payload reaches len           the runs in front, and floor(8 r / k) values len
+ *                                                                            of the r payload bytes that are there
+ *   BROTLI_AMD_UNRLE_BAD_WIDTH    only with WIDTH_BYTE, see above            0                                           0
+ * (The bit-packed TRUNCATED row exists because some writers cut the last group's padding: those values are counted and delivered.)
+ *
+ * RESULT.  Every segment gets a BrotliAmdUnrleResult in host memory.  count, consumed, runs, status and bits are independent of cap, and of how
+ * the work was shared out.
+ *
+ * Examples (k, bytes, values): 3, 03 88 C6 FA: 0 .. 7;  3, 10 05: 8 x 5;  9, 06 2C 01: 3 x 300;  3, 90 03 07: 200 x 7;  0, 07: 24 x 0.
+ *
+ * OUT OF PLACE ONLY: no destination range overlaps any source range or any other destination range of the call.  This is stated, not checked.
+ *
+ * REFUSED ON THE HOST, in front of everything that touches the device: a width outside {1, 2, 4, 8}; unknown flag bits; k > 32 or k > 8 w
+ * without WIDTH_BYTE; cap > 2^56; a NULL d_dst[i] with caps[i] != 0.
+ *
+ * A call is two launches in stream order, and no block ever waits for another.  1. THE WALK, one wave a segment: the wave stages the source
+ * through LDS in aligned chunks and takes the headers one after the other -- it never reads a packed payload --, writes the segment's result,
+ * and for every ITEM of the destination (BrotliAmdDebugUnrleItemElems() elements) a checkpoint: the header offset and first element of the
+ * run that holds the item's first element.  2. THE EXPANSION, one wave an item, over the items of all segments in one list: the wave starts at
+ * its checkpoint, collects the runs that cover the item and stores its elements, a lane's elements neighbours.  So one segment with a gigabyte
+ * of destination is expanded by every CU; its walk is one wave's.  A call that only counts is the first launch alone
+ * (csrc/brotli_unrle.h, csrc/brotli_unrle_kernels.hip).
+ *
+ * OUT OF SCOPE: a speculative parallel walk of one long segment; page framing -- thrift headers, and the 4-byte length in front of v1 levels,
+ * where the caller passes src + 4 --; DELTA_BINARY_PACKED; the dictionary gather; ORC's and PackBits' run formats; MSB-first fields; sign
+ * extension. */
+#define BROTLI_AMD_UNRLE_WIDTH_BYTE 1u
+
+#define BROTLI_AMD_UNRLE_OK 0u
+#define BROTLI_AMD_UNRLE_BAD_HEADER 1u
+#define BROTLI_AMD_UNRLE_ZERO_RUN 2u
+#define BROTLI_AMD_UNRLE_TRUNCATED 3u
+#define BROTLI_AMD_UNRLE_BAD_WIDTH 4u
+
+typedef struct BrotliAmdUnrleResult {
+  uint64_t count;     /* values in all runs, whatever cap was */
+  uint64_t consumed;  /* the table above */
+  uint64_t runs;      /* runs that gave at least one value */
+  uint32_t status;    /* BROTLI_AMD_UNRLE_* */
+  uint32_t bits;      /* the k that was used */
+} BrotliAmdUnrleResult;
+
+/* n segments in DEVICE memory -- the runs in the src_lens[i] bytes at d_src[i], of fields of bits[i] bits, become elements of widths[i] bytes
+ * at d_dst[i], the first caps[i] of them, by flags[i] (flags == NULL: all 0); results[i] says what segment i held; any alignment, any length,
+ * 0 included; n is not bound by the batch object's max_streams --: the launches run on hip_stream, and the call waits on that stream.
+ * caps[i] == 0 needs no destination (d_dst[i] is not looked at, and d_dst itself may be NULL where every capacity is 0): a call of such
+ * segments only counts.  n == 0 returns 0.  A negative value, and a BrotliAmdLastError text that names the segment and what was wrong, for a
+ * NULL batch, a NULL array (but flags and d_dst) with n != 0, and everything in the list above: all of these are checked on the host in front
+ * of everything else, so nothing is launched and no byte is written. */
+BROTLI_DEC_API int BrotliAmdBatchUnrleSegments(BrotliAmdBatch* batch, uint32_t n, const void* const* d_src, const size_t* src_lens, void* const* d_dst,
+                                              const uint64_t* caps, const uint8_t* bits, const uint8_t* widths,
+                                              const uint8_t* flags /* n entries, or NULL: all 0 */, BrotliAmdUnrleResult* results, void* hip_stream);
+
+/* The same for the DELIVERED bytes -- [out, out + decoded_size) -- of every stream of the last decode call on the object: stream i's values go
+ * to d_dst[i] (device memory of caps[i] widths[i] bytes, any alignment) by bits[i], widths[i] and flags[i] (one entry per stream each; flags
+ * may be NULL: all 0), and results[i] (one entry per stream) says what it held.  d_dst[i] == NULL skips stream i: none of its parameters are
+ * looked at and its result is zeros.  d_dst == NULL or caps == NULL: every stream is counted and nothing is written.  Where the sources are,
+ * and when they are valid, is BrotliAmdBatchUnshuffleOutputs' rule exactly, for the three kinds of decode call.  A stream that ended in an
+ * error or NEEDS_MORE_OUTPUT is taken over its decoded_size bytes.  The launches run on the stream of that decode call and the call waits for
+ * it.  It is not a decode call itself: BrotliAmdBatchPackedOutput stays valid, and BrotliAmdBatchRelaunch and the Last* accessors say what they
+ * said before.  A negative value, and a BrotliAmdLastError text, for a NULL batch, bits, widths or results, a refused shape, flag or cap
+ * (nothing is launched), an object without a decode call, a last decode call that failed behind its argument checks (one of no streams
+ * returns 0), and a launch that BrotliAmdBatchWait has not been called for. */
+BROTLI_DEC_API int BrotliAmdBatchUnrleOutputs(BrotliAmdBatch* batch, void* const* d_dst /* or NULL */, const uint64_t* caps /* or NULL */,
+                                             const uint8_t* bits, const uint8_t* widths, const uint8_t* flags /* or NULL */,
+                                             BrotliAmdUnrleResult* results);
+
+/* Milliseconds the unrle kernels took in the last of the two calls above (HIP events around its launches together), */
+BROTLI_DEC_API float BrotliAmdBatchLastUnrleMs(BrotliAmdBatch* batch);
+/* and those of phase 1 (the walk) or 2 (the expansion) alone; another phase: 0. */
+BROTLI_DEC_API float BrotliAmdBatchLastUnrlePhaseMs(BrotliAmdBatch* batch, uint32_t phase);
+
+/* Test hooks (no device needed).  The elements of one item of the expansion, and the source bytes that the walk stages at a time; */
+BROTLI_DEC_API uint32_t BrotliAmdDebugUnrleItemElems(void);
+BROTLI_DEC_API uint32_t BrotliAmdDebugUnrleWalkChunk(void);
+/* both phases by the functions of csrc/brotli_unrle.h on the host, over n segments given as offsets into one source buffer src[0, src_size)
+ * and one destination buffer dst[0, dst_size): the buffers are placed at src_skew and dst_skew (0..15) past a 16-byte boundary among bytes that
+ * are not theirs.  Segment i is src_lens[i] bytes at src_offs[i]; its elements go to dst_offs[i], where there must be room for
+ * min(caps[i], count) of them.  item_elems: the elements of an item, 0 for the device's own.  order_seed != 0: the items are taken in an order
+ * shuffled by it (the result may not depend on it).  0, results[0..n) filled and the elements' bytes of dst written (no other byte of dst
+ * is); -1, a BrotliAmdLastError text and an untouched dst for a refused shape, flag or cap, a skew > 15 or a segment outside its buffer; -2
+ * where a byte outside the elements' destinations changed. */
+BROTLI_DEC_API int BrotliAmdDebugUnrleHost(uint32_t n, const uint8_t* src, size_t src_size, uint8_t* dst, size_t dst_size, const uint64_t* src_offs,
+                                          const uint64_t* src_lens, const uint64_t* dst_offs, const uint64_t* caps, const uint8_t* bits,
+                                          const uint8_t* widths, const uint8_t* flags /* or NULL */, uint32_t src_skew, uint32_t dst_skew,
+                                          uint32_t item_elems, uint32_t order_seed, BrotliAmdUnrleResult* results);
 
 /* Milliseconds the last launch spent in the decode kernel (HIP events on the launch stream). */
 BROTLI_DEC_API float BrotliAmdBatchLastKernelMs(BrotliAmdBatch* batch);

@@ -48,6 +48,8 @@ BATCH_H_SYMBOLS = [
     "BrotliAmdDebugBitUnpackHost",
     "BrotliAmdBatchUnvarintSegments", "BrotliAmdBatchUnvarintOutputs", "BrotliAmdBatchLastUnvarintMs", "BrotliAmdBatchLastUnvarintPhaseMs",
     "BrotliAmdDebugUnvarintTile", "BrotliAmdDebugUnvarintHost",
+    "BrotliAmdBatchUnrleSegments", "BrotliAmdBatchUnrleOutputs", "BrotliAmdBatchLastUnrleMs", "BrotliAmdBatchLastUnrlePhaseMs",
+    "BrotliAmdDebugUnrleItemElems", "BrotliAmdDebugUnrleWalkChunk", "BrotliAmdDebugUnrleHost",
 ]
 
 
@@ -80,6 +82,17 @@ class UnvarintResult(ctypes.Structure):  # BrotliAmdUnvarintResult: what a segme
 
     def astuple(self):
         return (self.count, self.consumed, self.overlong)
+
+
+UNRLE_WIDTH_BYTE = 1  # BROTLI_AMD_UNRLE_WIDTH_BYTE: the segment's first byte is the field width
+UNRLE_OK, UNRLE_BAD_HEADER, UNRLE_ZERO_RUN, UNRLE_TRUNCATED, UNRLE_BAD_WIDTH = 0, 1, 2, 3, 4  # UnrleResult.status
+
+
+class UnrleResult(ctypes.Structure):  # BrotliAmdUnrleResult: what a segment of RLE / bit-packed hybrid runs held (batch.h)
+    _fields_ = [("count", ctypes.c_uint64), ("consumed", ctypes.c_uint64), ("runs", ctypes.c_uint64), ("status", ctypes.c_uint32), ("bits", ctypes.c_uint32)]
+
+    def astuple(self):
+        return (self.count, self.consumed, self.runs, self.status, self.bits)
 
 
 def build(force=False):
@@ -191,7 +204,11 @@ def load_library():
              "BrotliAmdDebugBitUnpackHost": (None, [u32, u32, u32, vp, sz, u64, vp, u32, u32, vp])},
             {"BrotliAmdBatchUnvarintSegments": (None, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]), "BrotliAmdBatchUnvarintOutputs": (None, [vp, vp, vp, vp, vp, vp]),
              "BrotliAmdBatchLastUnvarintMs": (f32, [vp]), "BrotliAmdBatchLastUnvarintPhaseMs": (f32, [vp, u32]), "BrotliAmdDebugUnvarintTile": (u32, None),
-             "BrotliAmdDebugUnvarintHost": (None, [u32, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, vp])}):
+             "BrotliAmdDebugUnvarintHost": (None, [u32, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, vp])},
+            {"BrotliAmdBatchUnrleSegments": (None, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]), "BrotliAmdBatchUnrleOutputs": (None, [vp, vp, vp, vp, vp, vp, vp]),
+             "BrotliAmdBatchLastUnrleMs": (f32, [vp]), "BrotliAmdBatchLastUnrlePhaseMs": (f32, [vp, u32]), "BrotliAmdDebugUnrleItemElems": (u32, None),
+             "BrotliAmdDebugUnrleWalkChunk": (u32, None),
+             "BrotliAmdDebugUnrleHost": (None, [u32, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, vp])}):
         if hasattr(L, next(iter(protos))):
             for name, (restype, argtypes) in protos.items():
                 if restype is not None:
@@ -363,6 +380,39 @@ def unvarint_host(src: bytes, segs, dst_size, src_skew=0, dst_skew=0, tile_units
                                     src_skew, dst_skew, tile_units, order_seed, res) != 0:
         raise RuntimeError("BrotliAmdDebugUnvarintHost failed: " + last_error())
     return d_buf.raw[:dst_size], [res[i].astuple() for i in range(n)]
+
+
+def unrle_host(src: bytes, segs, dst_size, src_skew=0, dst_skew=0, item_elems=0, order_seed=0, fill=0):
+    """BrotliAmdDebugUnrleHost: the RLE / bit-packed hybrid runs in `src` back into elements by the device's walk and item functions on the host
+    (no device needed).  segs: [(source offset, source length, destination offset, capacity in elements, bits, width, flags)]; the destination
+    has dst_size bytes, all `fill` in front of the call (or, where `fill` is bytes of that size, those); the buffers are placed at their skews
+    past a 16-byte boundary; item_elems: the elements of an item (0: the device's); order_seed != 0 shuffles the order in which the items are
+    taken.  -> (the destination's bytes, [(count, consumed, runs, status, bits)])"""
+    L = load_library()
+    src = bytes(src)
+    n = len(segs)
+    before = bytes(fill) if isinstance(fill, (bytes, bytearray)) else bytes([fill]) * dst_size
+    if len(before) != dst_size:
+        raise ValueError("fill: %d bytes for a destination of %d" % (len(before), dst_size))
+    s_buf = ctypes.create_string_buffer(src, max(1, len(src)))
+    d_buf = ctypes.create_string_buffer(before, max(1, dst_size))
+    u64s = lambda k: (ctypes.c_uint64 * max(1, n))(*[s[k] if 0 <= s[k] < (1 << 64) else (1 << 64) - 1 for s in segs])
+    u8s = lambda k, bad: (ctypes.c_uint8 * max(1, n))(*[s[k] if 0 <= s[k] <= 255 else bad for s in segs])
+    res = (UnrleResult * max(1, n))()
+    if L.BrotliAmdDebugUnrleHost(n, ctypes.addressof(s_buf), len(src), ctypes.addressof(d_buf), dst_size, u64s(0), u64s(1), u64s(2), u64s(3), u8s(4, 255),
+                                 u8s(5, 0), u8s(6, 255), src_skew, dst_skew, item_elems, order_seed, res) != 0:
+        raise RuntimeError("BrotliAmdDebugUnrleHost failed: " + last_error())
+    return d_buf.raw[:dst_size], [res[i].astuple() for i in range(n)]
+
+
+def unrle_item_elems():
+    """BrotliAmdDebugUnrleItemElems: the elements of one item of an unrle call's expansion"""
+    return int(load_library().BrotliAmdDebugUnrleItemElems())
+
+
+def unrle_walk_chunk():
+    """BrotliAmdDebugUnrleWalkChunk: the source bytes that the walk of an unrle call stages at a time"""
+    return int(load_library().BrotliAmdDebugUnrleWalkChunk())
 
 
 def unvarint_tile():
@@ -753,6 +803,53 @@ class Batch:
         if phase is None:
             return float(self._L.BrotliAmdBatchLastUnvarintMs(self._h))
         return float(self._L.BrotliAmdBatchLastUnvarintPhaseMs(self._h, phase))
+
+    def unrle_segments(self, src_ptrs, src_lens, dst_ptrs, caps, bits, widths, flags=None, stream=None):
+        """BrotliAmdBatchUnrleSegments: the RLE / bit-packed hybrid runs in the src_lens[i] bytes at the device address src_ptrs[i], of fields of
+        bits[i] bits (0 .. 32), become elements of widths[i] bytes (1, 2, 4, 8) at dst_ptrs[i], the first caps[i] of them, by flags[i]
+        (UNRLE_WIDTH_BYTE; None: all 0); any alignment, any length; out of place; caps[i] == 0 needs no destination (dst_ptrs[i] may be None;
+        dst_ptrs=None: none has one).  Two launches and a wait on `stream`.  -> [(count, consumed, runs, status, bits)]: what each segment
+        held, whatever its capacity was"""
+        n, col = len(src_ptrs), self._column
+        if len(src_lens) != n or (dst_ptrs is not None and len(dst_ptrs) != n) or len(caps) != n:
+            raise ValueError("src_ptrs, src_lens, dst_ptrs and caps: one entry per segment each")
+        a_d = None if dst_ptrs is None else col(ctypes.c_void_p, [p or None for p in dst_ptrs], n)
+        res = (UnrleResult * max(1, n))()
+        self._filter_call("BrotliAmdBatchUnrleSegments", n, col(ctypes.c_void_p, src_ptrs, n), col(ctypes.c_size_t, src_lens, n), a_d,
+                          col(ctypes.c_uint64, caps, n, (1 << 64) - 1), self._byte_column(bits, n, "bits"), self._byte_column(widths, n, "widths", 0),
+                          self._byte_column(flags, n, "flags"), res, stream)
+        return [res[i].astuple() for i in range(n)]
+
+    def unrle_outputs(self, dst_ptrs, caps, bits, widths, flags=None):
+        """BrotliAmdBatchUnrleOutputs: the delivered bytes of every stream of the last decode call on this object (after decode_device: once
+        wait() has returned), taken as RLE / bit-packed hybrid runs of fields of bits[i] bits, become elements of widths[i] bytes at the device
+        address dst_ptrs[i], the first caps[i] of them (None or 0: the stream is skipped, and its result is zeros).  dst_ptrs=None or caps=None:
+        every stream is counted and nothing is written.  Two launches on that call's stream, and a wait.
+        -> [(count, consumed, runs, status, bits)], one per stream"""
+        n, col = self.out_n, self._column
+        if (dst_ptrs is not None and len(dst_ptrs) != n) or (caps is not None and len(caps) != n):
+            raise ValueError("dst_ptrs and caps: one entry per stream of the last decode call each")
+        a_d = None if dst_ptrs is None else col(ctypes.c_void_p, [p or None for p in dst_ptrs], n)
+        res = (UnrleResult * max(1, n))()
+        self._filter_call("BrotliAmdBatchUnrleOutputs", a_d, col(ctypes.c_uint64, caps, n, (1 << 64) - 1), self._byte_column(bits, n, "bits"),
+                          self._byte_column(widths, n, "widths", 0), self._byte_column(flags, n, "flags"), res)
+        return [res[i].astuple() for i in range(n)]
+
+    def count_rle_outputs(self, bits=None):
+        """unrle_outputs without destinations: how many values the runs of every stream of the last decode call hold -> [(count, consumed, runs,
+        status, bits)]; bits: every stream's field width, or None: every stream's first byte says it (UNRLE_WIDTH_BYTE).  The way to size the
+        destinations of the call that writes"""
+        n = self.out_n
+        if bits is None:
+            return self.unrle_outputs(None, None, [0] * n, [4] * n, [UNRLE_WIDTH_BYTE] * n)
+        return self.unrle_outputs(None, None, bits, [4] * n)
+
+    def last_unrle_ms(self, phase=None):
+        """milliseconds the unrle kernels took in the last unrle_segments / unrle_outputs: both launches together, or phase 1 (the walk) or 2
+        (the expansion)"""
+        if phase is None:
+            return float(self._L.BrotliAmdBatchLastUnrleMs(self._h))
+        return float(self._L.BrotliAmdBatchLastUnrlePhaseMs(self._h, phase))
 
     def last_bitunpack_ms(self):
         """milliseconds the bit-unpack kernel took in the last bitunpack_segments / bitunpack_outputs"""

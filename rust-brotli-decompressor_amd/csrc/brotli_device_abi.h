@@ -156,6 +156,27 @@ typedef struct BrotliAmdUnvarintSeg {
 } BrotliAmdUnvarintSeg;
 #define BROTLI_AMD_UNVARINT_TILE_BYTES 16384u  // source bytes of one tile: a tile's carry-in is the number of varints that end in front of it
 
+// One segment of an unrle call (csrc/brotli_unrle_kernels.hip, csrc/brotli_unrle.h): the len bytes at src are runs of the RLE / bit-packed
+// hybrid with fields of `bits` bits (0 .. 32), and the first `cap` of their values become elements of `width` bytes (1, 2, 4 or 8) at dst, by
+// `flags` (bit 0: the segment's first byte is the field width); device addresses of any alignment, len 0 and cap 0 included (cap 0: dst is not
+// looked at).  The destination is cut into ITEMS of BROTLI_AMD_UNRLE_ITEM_ELEMS elements; first_item is the number of items of the segments in
+// front of this one, so a call's units are one a segment -- its walk -- and one an item.  Every segment has a result (BrotliAmdUnrleResult,
+// include/brotli/batch.h) and every item a checkpoint behind the table.  No destination range overlaps a source range or another destination
+// range.  Nothing outside [dst, dst + min(count, cap) width) is written; nothing outside the 16-byte-aligned span around [src, src + len) is read.
+typedef struct BrotliAmdUnrleSeg {
+  const uint8_t* src;
+  uint8_t* dst;
+  uint64_t len;
+  uint64_t cap;
+  uint64_t first_item;
+  uint32_t width;
+  uint32_t bits;
+  uint32_t flags;
+  uint32_t reserved;
+} BrotliAmdUnrleSeg;
+#define BROTLI_AMD_UNRLE_ITEM_ELEMS 1024u  // elements of one item of the expansion: a wave's share of a destination
+#define BROTLI_AMD_UNRLE_WALK_CHUNK 1024u  // source bytes that a wave stages in LDS at a time: one 16-byte load a lane
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,7 @@
 //   brotli_stream_set.cpp  many streaming states in one launch, the ragged copy's debug hook
 //   brotli_seg_call.cpp  what the calls below share: the last decode call's outputs as segments, the segment walk's host model
 //   brotli_digest.cpp   CRC-32 / CRC-32C of segments of device memory and of the last decode call's outputs
-//   brotli_filters.cpp  the element filters -- unshuffle, undelta, bit-unshuffle, bit-unpack, unvarint -- of segments of device memory and of the last
+//   brotli_filters.cpp  the element filters -- unshuffle, undelta, bit-unshuffle, bit-unpack, unvarint, unrle -- of segments of device memory and of the last
 //                       decode call's outputs: one descriptor a filter, one call, one pair of segment builders, the host hooks
 #ifndef BROTLI_AMD_HOST_H_
 #define BROTLI_AMD_HOST_H_
@@ -111,7 +111,7 @@ struct SegCall {
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // around and between its launches (made at the first call, as many as it needs)
 };
 
-enum Filter : uint32_t { kUnshuffle, kUndelta, kBitUnshuffle, kBitUnpack, kUnvarint, kFilters };   // the element filters (brotli_filters.cpp)
+enum Filter : uint32_t { kUnshuffle, kUndelta, kBitUnshuffle, kBitUnpack, kUnvarint, kUnrle, kFilters };   // the element filters (brotli_filters.cpp)
 
 constexpr size_t kReaderSlack = 256;   // behind every buffer the kernel reads a stream's bytes from, or writes them to, up to the buffer's end
 
@@ -179,6 +179,7 @@ struct BrotliAmdBatch {
   struct FilterCall { brotli_amd_host::SegCall call; float ms = 0.0f; } filter[brotli_amd_host::kFilters];
   float undelta_phase_ms[3] = {0.0f, 0.0f, 0.0f};
   float unvarint_phase_ms[3] = {0.0f, 0.0f, 0.0f};   // unvarint's three launches as well; behind its table the summaries, the carries and the segments' results
+  float unrle_phase_ms[2] = {0.0f, 0.0f};            // unrle's two launches; behind its table the segments' results, the items' prefix array and their checkpoints
 };
 
 namespace brotli_amd_host {

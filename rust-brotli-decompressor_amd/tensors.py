@@ -14,7 +14,10 @@ numpy.packbits -- names k in its spec; it is the one stream whose slot is larger
 streams into their slots (Batch.bitunpack_outputs).  A stream whose array was stored as VARINTS -- LEB128, protobuf's base-128 integers, plain or
 zigzag: packed repeated fields, postings lists, offset tables -- says so in its spec; its size depends on its values, so one call decodes all such
 streams into their slots and says how many integers each held (Batch.unvarint_outputs), and a stream that held another number than its shape
-says, unfinished bytes or an integer of more than ten bytes is refused."""
+says, unfinished bytes or an integer of more than ten bytes is refused.  A stream whose array was stored as RUNS -- Parquet's RLE / bit-packed
+hybrid: dictionary indices, definition and repetition levels, booleans -- says so in its spec, with its field width k or, where the stream's
+first byte holds k, without; one call decodes all such streams into their slots (Batch.unrle_outputs), and a stream whose runs did not end
+well or held fewer values than its shape says is refused."""
 import collections
 
 import torch
@@ -29,20 +32,23 @@ def _numel(shape):
     return n
 
 
-FILTERS = ("shuffle", "delta", "bitshuffle", "bitpack", "varint")
+FILTERS = ("shuffle", "delta", "bitshuffle", "bitpack", "varint", "rle")
 BITPACK_OPTIONS = {"big": 1, "signed": 2}   # BITUNPACK_MSB_FIRST, BITUNPACK_SIGNED
 VARINT_OPTIONS = {"zigzag": 1}              # UNVARINT_ZIGZAG
+RLE_WIDTH_BYTE = 1                          # UNRLE_WIDTH_BYTE
+RLE_STATUS = ("ok", "a header of more than five bytes", "a run of no values", "runs that the stream's end cuts", "a width byte that is none")
 
 
 # What a wanted stream's spec says: the slot's bytes, the tensor's dtype and shape, the element width, the names of its filters, bitshuffle's block
-# and bitpack's (k, flags) -- (1, 0) where the stream is not packed, as for a stream that is not wanted --, varint's flags
-_Stream = collections.namedtuple("_Stream", "want dtype shape item filters block pack varint")
+# and bitpack's (k, flags) -- (1, 0) where the stream is not packed, as for a stream that is not wanted --, varint's flags, rle's (k, flags) --
+# (0, 0) where the stream has no runs
+_Stream = collections.namedtuple("_Stream", "want dtype shape item filters block pack varint rle")
 
 
 def _parse_spec(i, spec, size):
     """spec of stream i, which delivered `size` bytes -> _Stream; ValueError, naming the stream, for what outputs_as_tensors refuses"""
     dtype, shape = spec[0], spec[1]
-    flt, block, pack, varint = [], 0, None, 0
+    flt, block, pack, varint, rle = [], 0, None, 0, None
     for name in (tuple(spec[2]) if len(spec) > 2 else ("shuffle",)):
         if isinstance(name, (tuple, list)) and len(name) == 2 and name[0] == "bitshuffle":   # ("bitshuffle", block_elems)
             name, block = name[0], int(name[1])
@@ -62,6 +68,12 @@ def _parse_spec(i, spec, size):
                 if opt not in VARINT_OPTIONS:
                     raise ValueError("stream %d: unknown varint option %r (known: %s)" % (i, opt, ", ".join(VARINT_OPTIONS)))
             name, varint = name[0], sum({VARINT_OPTIONS[opt] for opt in name[1:]})
+        if isinstance(name, (tuple, list)) and len(name) >= 1 and name[0] == "rle":   # ("rle", k)
+            if len(name) != 2:
+                raise ValueError("stream %d: (\"rle\", k) names the field width and nothing else; \"rle\" alone: the stream's first byte holds it" % i)
+            name, rle = name[0], (int(name[1]), 0)
+        elif name == "rle":
+            rle = (0, RLE_WIDTH_BYTE)
         if name in VARINT_OPTIONS and flt and flt[-1] == "varint":   # ("varint", "zigzag") as the spec's filters: the option right behind its filter
             varint |= VARINT_OPTIONS[name]
             continue
@@ -75,6 +87,8 @@ def _parse_spec(i, spec, size):
         raise ValueError("stream %d: \"bitpack\" with \"shuffle\" or \"bitshuffle\" in one spec: packed fields have no byte or bit planes" % i)
     if "varint" in flt and ("shuffle" in flt or "bitshuffle" in flt or pack is not None):
         raise ValueError("stream %d: \"varint\" with \"shuffle\", \"bitshuffle\" or \"bitpack\" in one spec: integers of variable length have no planes and no fields" % i)
+    if "rle" in flt and ("shuffle" in flt or "bitshuffle" in flt or pack is not None or "varint" in flt):
+        raise ValueError("stream %d: \"rle\" with \"shuffle\", \"bitshuffle\", \"bitpack\" or \"varint\" in one spec: runs have no planes, and their fields and headers are their own" % i)
     shape = tuple(int(d) for d in (shape if isinstance(shape, (tuple, list, torch.Size)) else (shape,)))
     item = torch.empty(0, dtype=dtype).element_size()
     if item not in (1, 2, 4, 8):
@@ -86,11 +100,13 @@ def _parse_spec(i, spec, size):
         stored = (_numel(shape) * pack[0] + 7) // 8
         if size != stored:
             raise ValueError("stream %d: %d delivered bytes, but %d fields of %d bits (shape %s) are %d" % (i, size, _numel(shape), pack[0], shape, stored))
-    elif "varint" in flt:
+    elif "varint" in flt or "rle" in flt:
         pass   # (how many integers the delivered bytes hold is the call's to say: outputs_as_tensors checks its result)
     elif size != want:
         raise ValueError("stream %d: %d delivered bytes, but %s of shape %s is %d" % (i, size, dtype, shape, want))
-    return _Stream(want, dtype, shape, item, flt, block, pack or (1, 0), varint)
+    if rle is not None and not rle[1] and not 0 <= rle[0] <= min(32, 8 * item):
+        raise ValueError("stream %d: rle fields of %d bits, but %s takes 0 .. %d" % (i, rle[0], dtype, min(32, 8 * item)))
+    return _Stream(want, dtype, shape, item, flt, block, pack or (1, 0), varint, rle or (0, 0))
 
 
 def outputs_as_tensors(batch, specs):
@@ -120,7 +136,15 @@ def outputs_as_tensors(batch, specs):
         (dtype, shape, (("varint", "zigzag"),))  ... zigzag: (v >> 1) ^ -(v & 1), the signed integers of protobuf's sint64 and Avro's long;
                                               ("varint", "zigzag") as the filters, the option right behind its filter, says the same
         (dtype, shape, ("varint", "delta"))   varints of deltas (sorted ids, postings): that call, then Batch.undelta_segments in place
-    "varint" together with "shuffle", "bitshuffle" or "bitpack" in one spec raises ValueError, naming the stream.
+        (dtype, shape, (("rle", 12),))        runs of Parquet's RLE / bit-packed hybrid with fields of 12 bits (k = 0 .. 32 and at most
+                                              8 x itemsize), zero-extended into the dtype's elements: ONE Batch.unrle_outputs call for all such
+                                              streams, into the slots, which are numel x itemsize.  ValueError, naming the stream and what was
+                                              found, where the runs do not end well (a status that is not OK) or hold fewer values than numel;
+                                              more values than numel are the last group's padding and are not judged
+        (dtype, shape, ("rle",))              ... the stream's first byte holds k: a dictionary-index page body
+        (dtype, shape, (("rle", 20), "delta"))  runs of deltas: that call, then Batch.undelta_segments in place
+    "varint" together with "shuffle", "bitshuffle" or "bitpack" in one spec raises ValueError, naming the stream; so does "rle" together with
+    any of those four.
     "shuffle" together with "bitshuffle", and "bitpack" together with either, in one spec raises ValueError, naming the stream; so does a k outside
     1 .. 8 x itemsize and an unknown option.
     Delta is a wrapping running sum over the flattened array, on the dtype's BIT PATTERN taken as a little-endian unsigned integer of its
@@ -152,10 +176,11 @@ def outputs_as_tensors(batch, specs):
     bits = [i for i in wanted if "bitshuffle" in streams[i].filters]
     packed = [i for i in wanted if "bitpack" in streams[i].filters]
     varints = [i for i in wanted if "varint" in streams[i].filters]
+    runs = [i for i in wanted if "rle" in streams[i].filters]
     # deltas only: every other wanted stream that is neither of bit planes nor of packed fields is the unshuffle call's; without "shuffle" it is
     # a copy -- width 1
-    plain = [i for i in wanted if i not in bits and i not in packed and i not in varints and "shuffle" not in streams[i].filters and "delta" in streams[i].filters]
-    batch.unshuffle_outputs(only([i for i in wanted if i not in plain and i not in bits and i not in packed and i not in varints]),
+    plain = [i for i in wanted if i not in bits and i not in packed and i not in varints and i not in runs and "shuffle" not in streams[i].filters and "delta" in streams[i].filters]
+    batch.unshuffle_outputs(only([i for i in wanted if i not in plain and i not in bits and i not in packed and i not in varints and i not in runs]),
                             [st.item if st is not None and "shuffle" in st.filters else 1 for st in streams])
     if bits:    # bit planes: from the outputs straight into the slots
         batch.bitunshuffle_outputs(only(bits), widths, [0 if st is None else st.block for st in streams])
@@ -173,6 +198,16 @@ def outputs_as_tensors(batch, specs):
                 raise ValueError("stream %d: %d delivered bytes, but its varints end after %d: an unfinished one trails them" % (i, sizes[i], consumed))
             if overlong != 0:
                 raise ValueError("stream %d: %d varints of more than ten bytes" % (i, overlong))
+    if runs:    # runs: from the outputs straight into the slots, numel elements each; a stream must have ended well and held at least that
+        res = batch.unrle_outputs(only(runs), [0 if st is None else _numel(st.shape) for st in streams], [0 if st is None else st.rle[0] for st in streams], widths,
+                                  [0 if st is None else st.rle[1] for st in streams])
+        for i in runs:
+            count, consumed, _, status, k = res[i]
+            if status != 0:
+                raise ValueError("stream %d: %s (status %d) after %d values in %d of its %d delivered bytes, fields of %d bits" %
+                                 (i, RLE_STATUS[status] if status < len(RLE_STATUS) else "an unknown status", status, count, consumed, sizes[i], k))
+            if count < _numel(streams[i].shape):
+                raise ValueError("stream %d: %d values in its runs, but shape %s is %d elements" % (i, count, streams[i].shape, _numel(streams[i].shape)))
     if plain:   # deltas only: from the outputs straight into the slots
         batch.undelta_outputs(only(plain), widths)
     both = [i for i in wanted if i not in plain and "delta" in streams[i].filters]
