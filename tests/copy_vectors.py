@@ -1,41 +1,19 @@
 """tests/golden/emitter_copies/ (tools/make_copy_vectors.py): the committed streams and the oracle's answers for them.
 Shared by test_emitter_copies_cpu.py and test_gpu_copies.py."""
-import json
-import random
 import os
+import random
 
-import oracle_lib as oracle
+import path_harness as H
 from conftest import ROOT
+from path_harness import expected  # noqa: F401  ((stream, capacity, flags=0) -> the oracle's answer, computed once -- answers of more than 4 MiB are not kept)
 
 DIR = os.path.join(ROOT, "tests", "golden", "emitter_copies")
-MAX_FILE, MAX_PARTS = 64466, 4
+MAX_FILE, MAX_PARTS = H.store.MAX_FILE, H.store.MAX_PARTS
 
 
 def load():
     """[(manifest entry, stream)] in the manifest's order"""
-    out = []
-    for e in json.load(open(os.path.join(DIR, "manifest.json"))):
-        if "hex" in e:
-            comp = bytes.fromhex(e["hex"])
-        else:  # (a stream of more than 64 466 bytes lies in parts)
-            comp = b"".join(open(os.path.join(DIR, name), "rb").read() for name in e.get("files", [e.get("file")]))
-        assert len(comp) == e["csize"], e["label"]
-        out.append((e, comp))
-    return out
-
-
-_expected = {}
-
-
-def expected(data, cap, flags=0):
-    """the oracle's answer, computed once per (stream, capacity, flags) -- answers of more than 4 MiB are not kept"""
-    key = (data, cap, flags)
-    if key in _expected:
-        return _expected[key]
-    got = oracle.decode(data, cap, flags)
-    if len(got[1]) <= 1 << 22:
-        _expected[key] = got
-    return got
+    return H.store.load(DIR)
 
 
 SPLIT = 26  # (leg_set: the second batch starts here)
@@ -43,31 +21,19 @@ SPLIT = 26  # (leg_set: the second batch starts here)
 
 def wide_set():
     """the streams of window 24 -- S2 and D under (0, 0) and (3, 120), 17 to 22 MB of output each -- which go through three of the
-    paths in a test of their own -> [(label, stream, capacity)]"""
+    paths in a test of their own -> [(label, stream, capacity, 0, None)]"""
     by = {e["label"]: (e, c) for e, c in load()}
-    out = [(label, by[label][1], by[label][0]["size"]) for label in ("S2-wide-fields-cf", "S2-wide-fields-ctx", "D-p0-d0-cf", "D-p0-d0-ctx", "D-p3-d120-cf", "D-p3-d120-ctx")]
-    return out + [("S2-wide-fields-cf/half", by["S2-wide-fields-cf"][1], by["S2-wide-fields-cf"][0]["size"] // 2)]
+    out = [(label, by[label][1], by[label][0]["size"], 0, None) for label in ("S2-wide-fields-cf", "S2-wide-fields-ctx", "D-p0-d0-cf", "D-p0-d0-ctx", "D-p3-d120-cf", "D-p3-d120-ctx")]
+    return out + [("S2-wide-fields-cf/half", by["S2-wide-fields-cf"][1], by["S2-wide-fields-cf"][0]["size"] // 2, 0, None)]
 
 
 def leg_set():
     """the streams that go through every command path of the device (test_gpu_copies.py): S1, M in both orders, T under its
     three plans, H and W whole, D for the seven parameter pairs of window 18, and short / half / cut / flipped copies of a few
-    (wide_set has S2 and the other two pairs) -> [(label, stream, capacity)].  Positions 0 and SPLIT hold T's long form, so that each part of the set, decoded as a batch of its own, is one
-    that gets gangs of blocks."""
-    rnd = random.Random(61)
-    by = {e["label"]: (e, c) for e, c in load()}
+    (wide_set has S2 and the other two pairs) -> [(label, stream, capacity, 0, None)].  Positions 0 and SPLIT hold T's long form, so that
+    each part of the set, decoded as a batch of its own, is one that gets gangs of blocks."""
     out = []
-
-    def take(label, cap=None, damage=None):
-        e, c = by[label]
-        n = e["size"]
-        if damage == "cut":
-            c = c[:rnd.randrange(len(c) // 2, len(c))]
-        elif damage == "flip":
-            d = bytearray(c); d[rnd.randrange(len(d) // 3, len(d))] ^= 1 << rnd.randrange(8); c = bytes(d)
-        cap = {None: n if not damage else n + 64, "short": n - 1, "half": n // 2}.get(cap, cap)
-        out.append((label + ("" if cap == n and not damage else "/%s/%s" % (cap, damage)), c, cap))
-
+    take = H.take({e["label"]: (e, c) for e, c in load()}, random.Random(61), out)
     take("T2-text-long-cf")
     for label in ("S1a-symbols", "S1b-symbols", "M-rows-w22", "M-mixed-w22", "T-text", "H-chains", "W-edge-w10", "W-edge-w11", "W-edge-w16"):
         take(label + "-cf"); take(label + "-ctx")

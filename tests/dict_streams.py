@@ -67,17 +67,29 @@ def variants(rnd, c, n, damaged=6):
 _expected = {}
 
 
-def expected(data, cap, flags, dictionary):
-    """the oracle's answer, computed once per (stream, capacity, flags, dictionary)"""
+def expected(data, cap, flags=0, dictionary=None):
+    """the oracle's answer, computed once per (stream, capacity, the oracle's two flags, dictionary) -- answers of more than 4 MiB are
+    not kept.  The one cache of the suites: brotli_oracle_decode is brotli_oracle_decode_dict without a dictionary."""
+    flags &= oracle.FLAG_LARGE_WINDOW | oracle.FLAG_NO_CANNY   # (what else a batch's flags hold is the device's)
     key = (bytes(data), cap, flags, bytes(dictionary) if dictionary else b"")
-    if key not in _expected:
-        _expected[key] = oracle_decode_dict(data, cap, flags, dictionary)
-    return _expected[key]
+    if key in _expected:
+        return _expected[key]
+    got = oracle_decode_dict(data, cap, flags, dictionary)
+    if len(got[1]) <= 1 << 22:
+        _expected[key] = got
+    return got
 
 
-def compare(results, outs, datas, caps, dicts, flags, what=""):
+def first_difference(out, exp):
+    """the first byte at which two outputs differ; None: one is the other's beginning"""
+    n = min(len(out), len(exp))
+    return None if out[:n] == exp[:n] else next(k for k in range(n) if out[k] != exp[k])
+
+
+def compare(results, outs, datas, caps, dicts, flags, what="", entries=None, where=None):
     """result, error code, decoded_size and every output byte against the oracle; on success consumed, num_commands and
-    num_metablocks too (test_gpu_engine._check_against_oracle with dictionaries) -> the mismatches"""
+    num_metablocks too (test_gpu_engine._check_against_oracle with dictionaries) -> the mismatches, each with its first differing
+    byte; `entries`: the manifest entry of each stream, which names it, and where(entry, byte) what the byte belongs to"""
     bad = []
     for i, (d, cap) in enumerate(zip(datas, caps)):
         info, exp = expected(d, cap, flags, dicts[i] if dicts else None)
@@ -86,20 +98,23 @@ def compare(results, outs, datas, caps, dicts, flags, what=""):
         if ok and info.result == 1:
             ok = r.consumed == info.consumed and r.num_commands == info.num_commands and r.num_metablocks == info.num_metablocks
         if not ok:
-            first = next((k for k in range(min(len(outs[i]), len(exp))) if outs[i][k] != exp[k]), None)
-            bad.append((i, what, (r.result, r.error_code, r.decoded_size), (info.result, info.error_code, info.decoded_size),
-                        r.consumed, info.consumed, r.num_commands, info.num_commands, len(d), cap, len(dicts[i]) if dicts and dicts[i] else 0, first))
+            first = first_difference(outs[i], exp)
+            e = entries[i] if entries else None
+            bad.append((i, what, e and e["label"], (r.result, r.error_code, r.decoded_size), (info.result, info.error_code, info.decoded_size),
+                        r.consumed, info.consumed, r.num_commands, info.num_commands, len(d), cap, len(dicts[i]) if dicts and dicts[i] else 0, first,
+                        e and where and where(e, first)))
     return bad
 
 
-def check(pkg, datas, caps, dicts, flags=1, what="", batch=None):
-    """decodes the streams in one batch with their dictionaries and compares with the oracle; -> the results"""
+def check(pkg, datas, caps, dicts, flags=1, what="", batch=None, entries=None, where=None):
+    """decodes the streams in one batch (the caller's, or one of its own) with their dictionaries and compares with the oracle;
+    -> the results"""
     b = batch or pkg.Batch(len(datas))
     try:
         results, outs = b.decode_host(datas, caps, flags, dicts=dicts)
     finally:
         if batch is None:
             b.close()
-    bad = compare(results, outs, datas, caps, dicts, flags, what)
+    bad = compare(results, outs, datas, caps, dicts, flags, what, entries, where)
     assert not bad, (len(bad), bad[:8])
     return results

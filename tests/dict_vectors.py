@@ -1,19 +1,16 @@
 """tests/golden/emitter_dict/ (tools/make_dict_vectors.py): the committed streams, their dictionaries -- made again from the seed the
 manifest holds -- and the oracle's answers for them.  Shared by test_emitter_dict_cpu.py and test_gpu_dict_paths.py."""
 import hashlib
-import json
 import os
 import random
-import sys
 
-import dict_streams
+import path_harness as H
 from conftest import ROOT
 
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import dict_gen  # noqa: E402
+import dict_gen  # noqa: I100  (tools/, which path_harness has put on the path)
 
 DIR = os.path.join(ROOT, "tests", "golden", "emitter_dict")
-MAX_FILE, MAX_PARTS = 64466, 4
+MAX_FILE, MAX_PARTS = H.store.MAX_FILE, H.store.MAX_PARTS
 ALPHABET = "etaoinshrdlucmfwypvbgkqjxz ,.0123456789"   # (tools/make_dict_vectors.py ALPHABET)
 
 _dicts = {}
@@ -32,14 +29,8 @@ _loaded = []
 def load():
     """[(manifest entry, stream, dictionary)] in the manifest's order"""
     if not _loaded:
-        manifest = json.load(open(os.path.join(DIR, "manifest.json")))
-        shas = {(x["seed"], x["size"]): x["sha256"] for x in manifest["dictionaries"]}
-        for e in manifest["streams"]:
-            if "hex" in e:
-                comp = bytes.fromhex(e["hex"])
-            else:
-                comp = b"".join(open(os.path.join(DIR, name), "rb").read() for name in e.get("files", [e.get("file")]))
-            assert len(comp) == e["csize"], e["label"]
+        shas = {(x["seed"], x["size"]): x["sha256"] for x in H.store.manifest(DIR)["dictionaries"]}
+        for e, comp in H.store.load(DIR):
             d = dictionary(*e["dict"])
             assert len(d) == e["dict"][1] and hashlib.sha256(d).hexdigest() == shas[tuple(e["dict"])], e["label"]
             _loaded.append((e, comp, d))
@@ -47,8 +38,8 @@ def load():
 
 
 def expected(data, cap, dictionary, flags=0):
-    """the oracle's answer with the dictionary, computed once (dict_streams.expected)"""
-    return dict_streams.expected(data, cap, flags, dictionary)
+    """the oracle's answer with the dictionary, computed once (path_harness.expected)"""
+    return H.expected(data, cap, flags, dictionary)
 
 
 SPLIT = 32  # (leg_set: the second batch starts here; 32 streams a batch: more, and a launch's gangs are of four blocks)
@@ -58,23 +49,10 @@ CARRIERS = ("F-T-cf", "F-T-ctx", "F-T-cf4", "F-C-cf", "F-C-ctx", "F-T2-long-cf",
 def leg_set():
     """the streams that go through every command path of the device (test_gpu_dict_paths.py): the carriers F, the matrices of A for
     eight dictionary sizes, B, C, D, E and G in samples, invalid ones, and short / half / cut / flipped copies of a few
-    -> [(label, stream, capacity, dictionary)].  Positions 0 and SPLIT hold F's long form, so that each part of the set, decoded as
+    -> [(label, stream, capacity, 0, dictionary)].  Positions 0 and SPLIT hold F's long form, so that each part of the set, decoded as
     a batch of its own, is one that gets gangs of blocks."""
-    rnd = random.Random(62)
-    by = {e["label"]: (e, c, d) for e, c, d in load()}
     out = []
-
-    def take(label, cap=None, damage=None):
-        e, c, d = by[label]
-        n = e["size"]
-        if damage == "cut":
-            c = c[:rnd.randrange(len(c) // 2, len(c))]
-        elif damage == "flip":
-            x = bytearray(c); x[rnd.randrange(len(x) // 3, len(x))] ^= 1 << rnd.randrange(8); c = bytes(x)
-        tag = "/%s/%s" % (cap, damage) if cap or damage else ""
-        cap = {None: n if not damage and e["valid"] else n + 64, "short": n - 1, "half": n // 2}[cap]
-        out.append((label + tag, c, cap, d))
-
+    take = H.take({e["label"]: (e, c, d) for e, c, d in load()}, random.Random(62), out, named_tag=True)
     take("F-T2-long-cf")
     for label in CARRIERS[:5]:
         take(label)

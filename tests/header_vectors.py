@@ -1,35 +1,27 @@
 """tests/golden/emitter_headers/ (tools/make_header_vectors.py): the committed streams and the oracle's answers for them.
 Shared by test_emitter_headers_cpu.py and test_gpu_headers.py."""
-import json
 import os
 import random
 
 import oracle_lib as oracle
+import path_harness as H
 from conftest import ROOT
-from copy_vectors import MAX_FILE, MAX_PARTS  # noqa: F401  (the same limits)
+from path_harness import expected  # noqa: F401  ((stream, capacity, flags=0) -> the oracle's answer, computed once -- answers of more than 4 MiB are not kept)
 
 DIR = os.path.join(ROOT, "tests", "golden", "emitter_headers")
+MAX_FILE, MAX_PARTS = H.store.MAX_FILE, H.store.MAX_PARTS
 FLAG_LARGE_WINDOW = oracle.FLAG_LARGE_WINDOW
 
 
-_loaded = None
+_loaded = []
 
 
 def load():
     """[(manifest entry, stream)] in the manifest's order.  An entry as the manifest has it names what cannot be derived; here it
     gets "family" (the label's first letter), "window" (22 unless named), "large", "valid" (no "oracle" triple: the answer is
     (1, 1, size)) and "oracle" filled in.  Streams of less than 256 bytes lie end to end in small.N.bin, at offset "at"."""
-    global _loaded
-    if _loaded is None:
-        names = sorted((n for n in os.listdir(DIR) if n.startswith("small.")), key=lambda n: int(n.split(".")[1]))
-        pack = b"".join(open(os.path.join(DIR, n), "rb").read() for n in names)
-        _loaded = []
-        for e in json.load(open(os.path.join(DIR, "manifest.json"))):
-            if "at" in e:
-                comp = pack[e["at"]:e["at"] + e["csize"]]
-            else:
-                comp = b"".join(open(os.path.join(DIR, name), "rb").read() for name in e.get("files", [e.get("file")]))
-            assert len(comp) == e["csize"], e["label"]
+    if not _loaded:
+        for e, comp in H.store.load(DIR):
             e = dict(e, family=e["label"][0], window=e.get("window", 22), large=e.get("large", False), valid="oracle" not in e)
             e.setdefault("oracle", [1, 1, e["size"]])
             _loaded.append((e, comp))
@@ -46,20 +38,6 @@ def big(e):
     return e["size"] > 1 << 22
 
 
-_expected = {}
-
-
-def expected(data, cap, flags=0):
-    """the oracle's answer, computed once per (stream, capacity, flags) -- answers of more than 4 MiB are not kept"""
-    key = (data, cap, flags)
-    if key in _expected:
-        return _expected[key]
-    got = oracle.decode(data, cap, flags)
-    if len(got[1]) <= 1 << 22:
-        _expected[key] = got
-    return got
-
-
 def cap_of(e):
     """room for everything a vector puts out (an invalid one delivers at most what lies in front of its fault)"""
     return e["size"] if e["valid"] else e["size"] + 64
@@ -71,22 +49,10 @@ SPLIT = 30  # (leg_set: the second batch starts here)
 def leg_set():
     """the streams that go through every command path of the device (test_gpu_headers.py): B's long form and its every-length-code
     streams, the mixed trivial / non-trivial maps, the 256-type vectors, P and C vectors of every kind, valid and not, and short /
-    cut / flipped copies of a few -> [(label, stream, capacity, flags)].  Positions 0 and SPLIT hold a stream of more than 64 KiB
+    cut / flipped copies of a few -> [(label, stream, capacity, flags, None)].  Positions 0 and SPLIT hold a stream of more than 64 KiB
     (M's metadata block of 65 537 bytes: the size from which a launch forms gangs)."""
-    rnd = random.Random(62)
-    by = {e["label"]: (e, c) for e, c in load()}
     out = []
-
-    def take(label, cap=None, damage=None):
-        e, c = by[label]
-        n = e["size"]
-        if damage == "cut":
-            c = c[:rnd.randrange(len(c) // 2, len(c))]
-        elif damage == "flip":
-            d = bytearray(c); d[rnd.randrange(len(d) // 3, len(d))] ^= 1 << rnd.randrange(8); c = bytes(d)
-        cap = {None: cap_of(e) if not damage else n + 64, "short": n - 1, "half": n // 2}.get(cap, cap)
-        out.append((label + ("" if cap == n and not damage else "/%s/%s" % (cap, damage)), c, cap, flags_of(e)))
-
+    take = H.take({e["label"]: (e, c) for e, c in load()}, random.Random(62), out, flags_of)
     take("M-metadata-65537")
     for label in ("B-long", "B-lit-every-length-code", "B-cmd-every-length-code", "B-dist-every-length-code", "C-some-types-trivial", "C-all-trivial-and-different",
                   "B-lit-n256-ring", "B-cmd-n256-ring", "B-dist-n256-direct", "B-lit-n255-direct", "B-ones-all", "C-lit-n256-r16", "C-dist-n256-r16", "C-runs-1-8",

@@ -1,55 +1,33 @@
 """tests/golden/emitter_literals/ (tools/make_literal_vectors.py): the committed streams and the oracle's answers for them.
 Shared by test_emitter_literals_cpu.py and test_gpu_literals.py."""
-import json
 import os
 import random
-import sys
 
 import oracle_lib as oracle
+import path_harness as H
 from conftest import ROOT
-from copy_vectors import MAX_FILE, MAX_PARTS  # noqa: F401  (the same limits)
+from path_harness import expected  # noqa: F401  ((stream, capacity, flags=0) -> the oracle's answer, computed once)
 
-sys.path.insert(0, os.path.join(ROOT, "tools"))
 DIR = os.path.join(ROOT, "tests", "golden", "emitter_literals")
+MAX_FILE, MAX_PARTS = H.store.MAX_FILE, H.store.MAX_PARTS
 FLAG_LARGE_WINDOW = oracle.FLAG_LARGE_WINDOW
 
 
-_loaded = None
+_loaded = []
 
 
 def load():
     """[(manifest entry, stream)] in the manifest's order.  An entry as the manifest has it names what cannot be derived; here it
     gets "family" (the label's first letter), "window" (22 unless named), "valid" (every vector of this family is) and "oracle"
     filled in.  Streams of less than 256 bytes lie end to end in small.N.bin, at offset "at"."""
-    global _loaded
-    if _loaded is None:
-        names = sorted((n for n in os.listdir(DIR) if n.startswith("small.")), key=lambda n: int(n.split(".")[1]))
-        pack = b"".join(open(os.path.join(DIR, n), "rb").read() for n in names)
-        _loaded = []
-        for e in json.load(open(os.path.join(DIR, "manifest.json"))):
-            if "at" in e:
-                comp = pack[e["at"]:e["at"] + e["csize"]]
-            else:
-                comp = b"".join(open(os.path.join(DIR, name), "rb").read() for name in e.get("files", [e.get("file")]))
-            assert len(comp) == e["csize"], e["label"]
-            e = dict(e, family=e["label"][0], window=e.get("window", 22), large=False, valid=True, oracle=[1, 1, e["size"]])
-            _loaded.append((e, comp))
+    if not _loaded:
+        for e, comp in H.store.load(DIR):
+            _loaded.append((dict(e, family=e["label"][0], window=e.get("window", 22), large=False, valid=True, oracle=[1, 1, e["size"]]), comp))
     return list(_loaded)
 
 
 def by_label():
     return {e["label"]: (e, c) for e, c in load()}
-
-
-_expected = {}
-
-
-def expected(data, cap, flags=0):
-    """the oracle's answer, computed once per (stream, capacity, flags)"""
-    key = (data, cap, flags)
-    if key not in _expected:
-        _expected[key] = oracle.decode(data, cap, flags)
-    return _expected[key]
 
 
 def cap_of(e):
@@ -79,24 +57,13 @@ SPLIT = 31  # (leg_set: the second batch starts here)
 def leg_set():
     """the streams that go through every command path of the device (test_gpu_literals.py): every shape of S with the sweep in front
     and at the end -- the end vectors' first command is a run of PE_RUN_MIN literals, which a gang declines --, every X vector, E's
-    long runs, and short / half / cut / flipped copies of a few -> [(label, stream, capacity, flags)].  Positions 0 and SPLIT hold
+    long runs, and short / half / cut / flipped copies of a few -> [(label, stream, capacity, 0, None)].  Positions 0 and SPLIT hold
     streams of more than 64 KiB (the size from which a launch forms gangs), most of it the runs of 40 000 and 2 x PE_RUN_MIN + 1
     literals: the staircase's front vector, and the staircase's long runs behind a first command of PE_RUN_MIN literals (built here by
     the generator, not committed)."""
-    rnd = random.Random(63)
     by = by_label()
     out = []
-
-    def take(label, cap=None, damage=None):
-        e, c = by[label]
-        n = e["size"]
-        if damage == "cut":
-            c = c[:rnd.randrange(len(c) // 2, len(c))]
-        elif damage == "flip":
-            d = bytearray(c); d[rnd.randrange(len(d) // 3, len(d))] ^= 1 << rnd.randrange(8); c = bytes(d)
-        cap = {None: n if not damage else n + 64, "short": n - 1, "half": n // 2}.get(cap, cap)
-        out.append((label + ("" if cap == n and not damage else "/%s/%s" % (cap, damage)), c, cap, 0))
-
+    take = H.take(by, random.Random(63), out)
     shapes = ["simple1", "simple2", "simple3", "simple4a", "simple4b", "flat8", "stair", "deep9", "deep10", "deep11", "deep12", "grid"]
     take("S-stair-front")
     for s in shapes:
@@ -109,7 +76,7 @@ def leg_set():
     assert len(out) == SPLIT and len(out[0][1]) > 65536, (len(out), len(out[0][1]))
     import make_literal_vectors   # (tools/: the one stream of the set that is not committed, 0.3 s to build)
     b = make_literal_vectors.s_vector("stair", "first", 1099)
-    by["S-stair-first"] = ({"label": "S-stair-first", "size": len(b.out), "runs": b.runs}, b.w.finish())
+    by["S-stair-first"] = ({"label": "S-stair-first", "size": len(b.out), "runs": b.runs, "valid": True}, b.w.finish())
     assert [r["insert"] for r in b.clog][0] >= make_literal_vectors.PE_RUN_MIN
     take("S-stair-first")
     assert len(out[SPLIT][1]) > 65536

@@ -8,129 +8,36 @@ tests/golden/emitter_copies/ (tools/make_copy_vectors.py, pinned on the CPU by t
 construction; here they go through each path, against the oracle: result, error code, decoded size, every byte, and for
 successes consumed, num_commands, num_metablocks."""
 import hashlib
-import json
-import os
 import random
-import subprocess
-import sys
 import time
 
 import pytest
 
 import copy_vectors
-import dict_streams
+import path_harness as H
 import stream_model as sm
-from conftest import ROOT
-from test_gpu_stream_set import Run
-from test_gpu_words import _LEGS, _product_seq, _variants
+
+import make_copy_vectors as C  # noqa: I100  (tools/, which path_harness has put on the path)
 
 pytestmark = pytest.mark.gpu
 
 
-def _gen():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import make_copy_vectors
-    return make_copy_vectors
-
-
-def _check(pkg, datas, caps, what, flags=0):
-    """test_gpu_words._check against copy_vectors.expected"""
-    batch = pkg.Batch(len(datas))
-    results, outs = batch.decode_host(datas, caps, flags)
-    batch.close()
-    bad = []
-    for i, (d, cap) in enumerate(zip(datas, caps)):
-        info, exp = copy_vectors.expected(d, cap, flags)
-        r = results[i]
-        ok = (r.result, r.error_code, r.decoded_size, outs[i]) == (info.result, info.error_code, info.decoded_size, exp)
-        if ok and info.result == 1:
-            ok = r.consumed == info.consumed and r.num_commands == info.num_commands and r.num_metablocks == info.num_metablocks
-        if not ok:
-            first = next((k for k in range(min(len(outs[i]), len(exp))) if outs[i][k] != exp[k]), None)
-            bad.append((i, what, (r.result, r.error_code, r.decoded_size), (info.result, info.error_code, info.decoded_size), r.consumed, info.consumed, len(d), cap, first))
-    assert not bad, (len(bad), bad[:10])
-    return results
-
-
 def test_every_vector_whole_short_truncated_and_damaged(pkg):
     """every stream of tests/golden/emitter_copies/ with exact, short, half, random and roomy output buffers and four truncated or
-    bit-flipped copies each (test_gpu_words._variants); those of more than 4 MiB of output -- S2 and the two window-24 forms of D --
+    bit-flipped copies each (path_harness.variants); those of more than 4 MiB of output -- S2 and the two window-24 forms of D --
     exact, one short, truncated and with one bit flipped; batches of at most 240 streams"""
     t0 = time.time()
     rnd = random.Random(2018)
     datas, caps = [], []
     for e, comp in copy_vectors.load():
         if e["size"] <= 1 << 22:
-            d, c = _variants(rnd, comp, e["size"])
+            d, c = H.variants(rnd, comp, e["size"])
         else:
             flipped = bytearray(comp); flipped[rnd.randrange(len(comp) // 2, len(comp))] ^= 1 << rnd.randrange(8)
             d, c = [comp, comp, comp[:rnd.randrange(len(comp) // 2, len(comp))], bytes(flipped)], [e["size"], e["size"] - 1, e["size"] + 64, e["size"] + 64]
         datas += d; caps += c
-    for at in range(0, len(datas), 240):
-        _check(pkg, datas[at:at + 240], caps[at:at + 240], "vectors %d.." % at)
+    H.in_batches(pkg, datas, caps, what="vectors")
     print("wall time %.1f s, %d streams" % (time.time() - t0, len(datas)))
-
-
-_LEG_SCRIPT = r"""
-import importlib.util, json, os, sys, hashlib
-ROOT = sys.argv[1]
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import copy_vectors
-spec = importlib.util.spec_from_file_location("rust_brotli_decompressor_amd", os.path.join(ROOT, "rust-brotli-decompressor_amd", "__init__.py"))
-pkg = importlib.util.module_from_spec(spec); sys.modules["rust_brotli_decompressor_amd"] = pkg; spec.loader.exec_module(pkg)
-streams = copy_vectors.wide_set() if sys.argv[2] == "wide" else copy_vectors.leg_set()
-rows, gangs = [], []
-for part in ([streams] if sys.argv[2] == "wide" else [streams[:copy_vectors.SPLIT], streams[copy_vectors.SPLIT:]]):
-    b = pkg.Batch(len(part))
-    res, outs = b.decode_host([c for _, c, _ in part], [cap for _, _, cap in part], 0)
-    gangs.append(b.last_gang())
-    b.close()
-    rows += [[r.result, r.error_code, r.decoded_size, r.consumed, r.num_commands, r.num_metablocks, r.engine_commands, hashlib.sha256(o).hexdigest()] for r, o in zip(res, outs)]
-print(json.dumps({"rows": rows, "gangs": gangs}))
-"""
-
-
-def _child_env(env):
-    e = dict(os.environ)
-    for k in ("BROTLI_AMD_GANG", "BROTLI_AMD_ENGINE", "BROTLI_AMD_NO_SCAN", "BROTLI_AMD_POOL"):
-        e.pop(k, None)
-    e.update(env)
-    return e
-
-
-def _legs(streams, which, legs):
-    """the streams in a fresh process per leg, the legs side by side -> {leg: {"rows": [status words, engine_commands, SHA-256],
-    "gangs"}}; all legs return the same status words and SHA-256s, and those are the oracle's"""
-    labels = [l for l, _, _ in streams]
-    got = {}
-    running = [(name, subprocess.Popen([sys.executable, "-c", _LEG_SCRIPT, ROOT, which], env=_child_env(env), stdin=subprocess.DEVNULL,
-                                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)) for name, env in legs]
-    try:
-        for name, p in running:
-            out, err = p.communicate(timeout=600)
-            assert p.returncode == 0, (name, err[-2000:])
-            got[name] = json.loads(out.strip().splitlines()[-1])
-    finally:
-        for _, p in running:
-            if p.poll() is None:
-                p.kill(); p.wait()
-    for name, g in got.items():
-        print("engine_commands of num_commands,", name, {l: (r[6], r[4]) for l, r in zip(labels, g["rows"]) if "/" not in l}, "gangs:", g["gangs"])
-    for name, g in got.items():
-        bad = []
-        for (label, comp, cap), r in zip(streams, g["rows"]):
-            info, exp = copy_vectors.expected(comp, cap, 0)
-            ok = r[:3] == [info.result, info.error_code, info.decoded_size] and r[7] == hashlib.sha256(exp).hexdigest()
-            if ok and info.result == 1:
-                ok = r[3:6] == [info.consumed, info.num_commands, info.num_metablocks]
-            if not ok:
-                bad.append((label, r[:6], (info.result, info.error_code, info.decoded_size, info.consumed, info.num_commands)))
-        assert not bad, (name, len(bad), bad[:8])
-    strip = lambda rs: [r[:6] + r[7:] for r in rs]   # (everything but engine_commands)
-    first = next(iter(got))
-    for name, g in got.items():
-        assert strip(g["rows"]) == strip(got[first]["rows"]), name
-    return got
 
 
 def test_the_streams_of_window_24_on_three_paths(pkg):
@@ -138,26 +45,23 @@ def test_the_streams_of_window_24_on_three_paths(pkg):
     (0, 0) and (3, 120) (every distance symbol up to 2^24 - 16): the general, records and checked legs.  They are kept out of the
     seven-leg test, which they made more than twice as slow as that of test_gpu_words.py."""
     t0 = time.time()
-    got = _legs(copy_vectors.wide_set(), "wide", [l for l in _LEGS if l[0] in ("general", "records", "checked")])
+    got = H.run_legs(copy_vectors, "wide_set", [l for l in H.LEGS if l[0] in ("general", "records", "checked")])
     assert set(got) == {"general", "records", "checked"}
     print("wall time %.1f s" % (time.time() - t0))
 
 
 def test_every_command_path_agrees_with_the_oracle_and_the_others(pkg):
     """copy_vectors.leg_set (two batches, each led by T's long form of more than 64 KiB, the size from which a launch forms gangs)
-    in a fresh process per leg of test_gpu_words._LEGS: the path engine's one-block form, whatever the launch picks, gangs of
+    in a fresh process per leg of path_harness.LEGS: the path engine's one-block form, whatever the launch picks, gangs of
     eight, the scan engine, the command records, the checked loop alone, and no records at all.  All legs return the same status
     words and SHA-256s, and those are the oracle's.  `engine_commands` says which path ran: T goes through the engine it is made
     for, under the bar test_gpu_words.py sets for its text-like vector; for the others the share is printed, and the general
     leg's must be above 0 for M and H."""
     t0 = time.time()
-    streams = copy_vectors.leg_set()
-    labels = [l for l, _, _ in streams]
-    got = _legs(streams, "all", _LEGS)
+    got = H.run_legs(copy_vectors)
     # which path ran
-    at = {l: i for i, l in enumerate(labels)}
-    eng = lambda name, label: got[name]["rows"][at[label]][6]
-    cmds = lambda label: got["general"]["rows"][at[label]][4]
+    eng = lambda name, label: got[name]["rows"][label][H.ENGINE]
+    cmds = lambda label: got["general"]["rows"][label][H.COMMANDS]
     for label in ("T-text-cf", "T2-text-long-cf"):
         assert eng("general", label) >= 0.9 * cmds(label), (label, eng("general", label), cmds(label))
         assert eng("default", label) > 0 and eng("gang8", label) > 0 and eng("scan", label) > 0, label
@@ -168,21 +72,8 @@ def test_every_command_path_agrees_with_the_oracle_and_the_others(pkg):
         assert eng("general", label) > 0, label
     assert got["gang8"]["gangs"] == [8, 8], got["gang8"]["gangs"]
     assert all(g <= 1 for g in got["general"]["gangs"]), got["general"]["gangs"]   # (no gangs)
-    assert all(r[6] == 0 for r in got["norec"]["rows"])
+    assert all(r[H.ENGINE] == 0 for r in got["norec"]["rows"].values())
     print("wall time %.1f s" % (time.time() - t0))
-
-
-def _limit_caps(size, n):
-    """out_cap at every byte from 3 in front of the final copy of n bytes to 1 behind it; for a copy of more than 64 bytes every
-    16-byte boundary of the output inside the copy, and the bytes on both sides of it"""
-    start = size - n
-    caps = set(range(start - 3, start + 1)) | set(range(size - 3, size + 2))
-    if n <= 64:
-        caps |= set(range(start, size))
-    else:
-        for p in range((start + 16) // 16 * 16, size, 16):
-            caps |= {p - 1, p, p + 1}
-    return sorted(caps)
 
 
 def _output_limits(pkg):
@@ -190,11 +81,9 @@ def _output_limits(pkg):
     for e, comp in copy_vectors.load():
         if e["label"].startswith("L-"):
             copy_len = int(e["label"].split("-")[1][1:])
-            caps = _limit_caps(e["size"], copy_len)
+            caps = H.limit_caps(e["size"], copy_len)
             assert caps[-1] == e["size"] + 1 and caps[0] == e["size"] - copy_len - 3
-            results = []
-            for at in range(0, len(caps), 240):
-                results += _check(pkg, [comp] * len(caps[at:at + 240]), caps[at:at + 240], e["label"])
+            results = H.in_batches(pkg, [comp] * len(caps), caps, what=e["label"])
             assert [r.result for r in results][-3:] == [3, 1, 1], e["label"]
             n += 1
     assert n == 24
@@ -207,16 +96,13 @@ def test_output_limits_at_a_copy(pkg):
     short ones in registers across the exit).  Once as the launch picks, once in a fresh process with BROTLI_AMD_NO_SCAN=1."""
     t0 = time.time()
     _output_limits(pkg)
-    script = "import sys; sys.path.insert(0, sys.argv[1]); import conftest, test_gpu_copies as t; print('limits', t._output_limits(conftest.load_pkg()))"
-    out = subprocess.run([sys.executable, "-c", script, os.path.join(ROOT, "tests")], env=_child_env({"BROTLI_AMD_NO_SCAN": "1"}), capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0 and "limits 24" in out.stdout, (out.stdout[-500:], out.stderr[-2000:])
+    assert H.in_a_child("test_gpu_copies", "_output_limits", {"BROTLI_AMD_NO_SCAN": "1"})[0] == 24
     print("wall time %.1f s" % (time.time() - t0))
 
 
 def _small_streams():
     """the cut-down matrix, W at window 10 -- in less than the 1024 bytes of its ring buffer, and in 2000, which wrap it -- and one
     chain of depth 8, at most 2000 bytes of output each, CF and CTX -> [(label, stream, output)]"""
-    C = _gen()
     out = []
     for label, cmds, wbits in (("M-small", C.m_small_commands(), 22), ("W-small", C.w_small_commands(False), 10), ("H-small", C.h_small_commands(), 22),
                                ("W-wraps", C.w_small_commands(True), 10)):
@@ -237,15 +123,13 @@ def test_small_streams_byte_by_byte(pkg, chunks):
     and stops for output only where the caller's buffer is full."""
     ic, oc = chunks
     for label, comp, raw in _small_streams():
-        got, out = _product_seq(pkg, comp, ic, oc)
         if label.startswith("W-wraps"):
+            got, out = H.product_seq(pkg, comp, ic, oc)
             info = copy_vectors.expected(comp, len(raw), 0)[0]
             assert got[-1][0] == sm.RESULT_SUCCESS and out == raw, (label, chunks, got[-1])
             assert sum(g[2] for g in got) == info.decoded_size and sum(g[1] for g in got) == info.consumed and all(g[2] <= oc for g in got), (label, chunks)
             continue
-        m = sm.ReferenceStream(comp)
-        want = sm.run_schedule(lambda pending, cap: m.call(len(pending), cap), comp, ic, oc, drain=True)
-        assert got == want, (label, chunks, next((i, g, w) for i, (g, w) in enumerate(zip(got + [None], want + [None])) if g != w))
+        out = H.streamed_like_the_model(pkg, comp, ic, oc, label)
         assert out == copy_vectors.expected(comp, len(raw), 0)[1] == raw, label
 
 
@@ -255,21 +139,15 @@ def test_the_windows_edge_and_the_matrix_in_a_stream_set(pkg):
     by = {e["label"]: (e, c) for e, c in copy_vectors.load()}
     names = ["W-edge-w10-cf", "W-edge-w10-ctx", "M-rows-w16-cf", "M-mixed-w16-ctx"]
     jobs = [dict(data=by[n][1], ic=4096, oc=517, lw=False) for n in names]
-    run, twin = Run(pkg, jobs).run(), Run(pkg, jobs).run(how=lambda k: "solo")
-    try:
-        for i, n in enumerate(names):
-            assert run.seq[i] == twin.seq[i] and run.seq[i][-1][0] == 1, n
-            exp = copy_vectors.expected(by[n][1], by[n][0]["size"], 0)[1]
-            assert run.bytes_of(i) == twin.bytes_of(i) == exp and hashlib.sha256(exp).hexdigest() == by[n][0]["sha256"], n
-    finally:
-        run.close(); twin.close()
+    want = [copy_vectors.expected(by[n][1], by[n][0]["size"], 0)[1] for n in names]
+    assert [hashlib.sha256(exp).hexdigest() for exp in want] == [by[n][0]["sha256"] for n in names]
+    H.stream_set_like_solo(pkg, jobs, names, want)
 
 
 def test_the_matrix_with_custom_dictionaries(pkg):
     """the cut-down matrix emitted for custom dictionaries of 1, 15, 16, 17, 300 and 70000 bytes: every copy starts 1 .. 20 bytes
     inside the dictionary's end and runs over into the output, the first ones overlap themselves as well (cdict_copy splits at a
-    distance of 16).  Against brotli_oracle_decode_dict through dict_streams.check, CF and CTX, whole, short and cut."""
-    C = _gen()
+    distance of 16).  Against brotli_oracle_decode_dict through path_harness.check, CF and CTX, whole, short and cut."""
     rnd = random.Random(301)
     datas, caps, dicts = [], [], []
     for size in (1, 15, 16, 17, 300, 70000):
@@ -284,30 +162,22 @@ def test_the_matrix_with_custom_dictionaries(pkg):
             assert all(1 <= r["distance"] - r["pos"] <= min(20, size) and r["max_distance"] == r["pos"] + size for r in copies)
             assert {r["distance"] - r["pos"] for r in copies} == set(range(1, min(20, size) + 1))
             assert any(r["copy_len"] > r["distance"] for r in copies) and (size < 16 or any(r["copy_len"] > r["distance"] - r["pos"] >= 16 for r in copies))
-            info, out = dict_streams.expected(comp, len(raw), 0, dictionary)
+            info, out = H.expected(comp, len(raw), 0, dictionary)
             assert info.result == 1 and out == raw
             for cap in (len(raw), len(raw) - 1, len(raw) // 2, len(raw) + 1000):
                 datas.append(comp); caps.append(cap); dicts.append(dictionary)
             datas.append(comp[:len(comp) * 2 // 3]); caps.append(len(raw)); dicts.append(dictionary)
-    dict_streams.check(pkg, datas, caps, dicts, flags=0, what="M with custom dictionaries")
+    H.check(pkg, datas, caps, dicts, flags=0, what="M with custom dictionaries")
 
 
 def test_the_matrix_and_the_symbols_in_one_wave_blocks(pkg):
     """M and S1 replicated to 4 * CUs + 1 streams in one batch: more than four blocks a CU, which are blocks of one wave whatever
-    the streams are; status words and one SHA-256 per stream"""
-    import torch
-    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    the streams are; status words and every byte against the oracle, whose bytes have the manifest's SHA-256"""
     by = {e["label"]: (e, c) for e, c in copy_vectors.load()}
     four = [by["M-rows-w22-cf"], by["M-mixed-w22-ctx"], by["S1a-symbols-ctx"], by["S1b-symbols-cf"]]
-    n = 4 * cus + 1
-    datas = [four[i % 4][1] for i in range(n)]
-    caps = [four[i % 4][0]["size"] for i in range(n)]
-    batch = pkg.Batch(n)
-    results, outs = batch.decode_host(datas, caps, 0)
-    batch.close()
-    for i, (r, out) in enumerate(zip(results, outs)):
-        e = four[i % 4][0]
-        assert (r.result, r.error_code, r.decoded_size, r.consumed, r.num_commands, r.num_metablocks) == (1, 1, e["size"], e["csize"], e["commands"], e["metablocks"]), i
-        assert hashlib.sha256(out).hexdigest() == e["sha256"], i
     for e, c in four:
         assert hashlib.sha256(copy_vectors.expected(c, e["size"], 0)[1]).hexdigest() == e["sha256"]
+    results, _ = H.blocks_a_cu(pkg, four)
+    for i, r in enumerate(results):
+        e = four[i % 4][0]
+        assert (r.result, r.error_code, r.decoded_size, r.consumed, r.num_commands, r.num_metablocks) == (1, 1, e["size"], e["csize"], e["commands"], e["metablocks"]), i

@@ -6,47 +6,20 @@ cdict_copy for every other shape, the path engine ends a pass at a distance into
 the dictionary's size (pe_dict_word, classify), the gangs' form decides from the dictionary's size whether a reference beyond P
 ends it, and the setup clamps what is in reach of a dictionary longer than the window.  The streams of tests/golden/emitter_dict/
 (tools/make_dict_vectors.py, pinned on the CPU by test_emitter_dict_cpu.py) hold every shape by construction; here they go through
-each path with their dictionaries.  Every comparison is dict_streams.compare: result, error code, decoded size, every delivered
+each path with their dictionaries.  Every comparison is path_harness.compare: result, error code, decoded size, every delivered
 byte, and for successes consumed, num_commands, num_metablocks -- against brotli_oracle_decode_dict."""
-import hashlib
-import json
-import os
 import random
-import subprocess
-import sys
 import time
 
 import pytest
 
-import dict_streams
 import dict_vectors
+import path_harness as H
 import stream_model as sm
-from conftest import ROOT
-from test_gpu_copies import _child_env, _limit_caps
-from test_gpu_stream_set import Run
-from test_gpu_words import _LEGS
+
+import make_dict_vectors as M  # noqa: I100  (tools/, which path_harness has put on the path)
 
 pytestmark = pytest.mark.gpu
-
-
-def _gen():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import make_dict_vectors
-    return make_dict_vectors
-
-
-def _variants(rnd, c, n):
-    """exact, one short, half, roomy; two truncated and two bit-flipped copies -> (datas, caps)"""
-    datas, caps = [c] * 4, [n, max(0, n - 1), n // 2, n + 1000]
-    for k in range(4):
-        d = bytearray(c)
-        if k < 2:
-            d = d[:rnd.randrange(1, max(2, len(d)))]
-        else:
-            for _ in range(rnd.choice([1, 1, 2])):
-                d[rnd.randrange(0, len(d))] ^= 1 << rnd.randrange(8)
-        datas.append(bytes(d)); caps.append(n + 4096)
-    return datas, caps
 
 
 def test_every_vector_whole_short_truncated_and_damaged(pkg):
@@ -58,87 +31,38 @@ def test_every_vector_whole_short_truncated_and_damaged(pkg):
     datas, caps, dicts = [], [], []
     for e, comp, d in dict_vectors.load():
         if e["valid"]:
-            a, b = _variants(rnd, comp, e["size"])
+            a, b = H.variants(rnd, comp, e["size"], "dict")
         else:
             a, b = [comp, comp], [e["size"] + 64, max(0, e["oracle"][2] - 1)]
         datas += a; caps += b; dicts += [d] * len(a)
-    for at in range(0, len(datas), 240):
-        dict_streams.check(pkg, datas[at:at + 240], caps[at:at + 240], dicts[at:at + 240], flags=0, what="vectors %d.." % at)
+    H.in_batches(pkg, datas, caps, dicts, what="vectors")
     print("wall time %.1f s, %d streams" % (time.time() - t0, len(datas)))
-
-
-_LEG_SCRIPT = r"""
-import importlib.util, json, os, sys, hashlib
-ROOT = sys.argv[1]
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import dict_vectors
-spec = importlib.util.spec_from_file_location("rust_brotli_decompressor_amd", os.path.join(ROOT, "rust-brotli-decompressor_amd", "__init__.py"))
-pkg = importlib.util.module_from_spec(spec); sys.modules["rust_brotli_decompressor_amd"] = pkg; spec.loader.exec_module(pkg)
-streams = dict_vectors.leg_set()
-rows, gangs = [], []
-for part in (streams[:dict_vectors.SPLIT], streams[dict_vectors.SPLIT:]):
-    b = pkg.Batch(len(part))
-    res, outs = b.decode_host([c for _, c, _, _ in part], [cap for _, _, cap, _ in part], 0, dicts=[d for _, _, _, d in part])
-    gangs.append(b.last_gang())
-    b.close()
-    rows += [[r.result, r.error_code, r.decoded_size, r.consumed, r.num_commands, r.num_metablocks, r.engine_commands, hashlib.sha256(o).hexdigest()] for r, o in zip(res, outs)]
-print(json.dumps({"rows": rows, "gangs": gangs}))
-"""
 
 
 def test_every_command_path_agrees_with_the_oracle_and_the_others(pkg):
     """dict_vectors.leg_set (two batches, each led by F's long form of more than 64 KiB, the size from which a launch forms gangs) with
-    its dictionaries in a fresh process per leg of test_gpu_words._LEGS, the seven side by side: the path engine's one-block form,
+    its dictionaries in a fresh process per leg of path_harness.LEGS, the seven side by side: the path engine's one-block form,
     whatever the launch picks, gangs of eight, the scan engine, the command records, the checked loop alone, and no records at all.
     All legs return the same status words and SHA-256s, and those are the oracle's.  `engine_commands` says which path ran: on the
     carriers it is above 0 in the general, records, scan and gang8 legs; the share is printed, not judged -- nobody has measured
     what the engines take of a stream made for its dictionary (test_gpu_custom_dict.test_engines_with_a_dictionary_attached)."""
     t0 = time.time()
-    streams = dict_vectors.leg_set()
-    labels = [s[0] for s in streams]
-    running = [(name, subprocess.Popen([sys.executable, "-c", _LEG_SCRIPT, ROOT], env=_child_env(env), stdin=subprocess.DEVNULL, stdout=subprocess.PIPE,
-                                       stderr=subprocess.PIPE, text=True)) for name, env in _LEGS]
-    got = {}
-    try:
-        for name, p in running:
-            out, err = p.communicate(timeout=600)
-            assert p.returncode == 0, (name, err[-2000:])
-            got[name] = json.loads(out.strip().splitlines()[-1])
-    finally:
-        for _, p in running:
-            if p.poll() is None:
-                p.kill(); p.wait()
-    at = {l: i for i, l in enumerate(labels)}
-    for name, g in got.items():
-        print("engine_commands of num_commands,", name, {l: (g["rows"][at[l]][6], g["rows"][at[l]][4]) for l in dict_vectors.CARRIERS}, "gangs:", g["gangs"])
-    bad = {}
-    for name, g in got.items():
-        for (label, comp, cap, d), r in zip(streams, g["rows"]):
-            info, exp = dict_vectors.expected(comp, cap, d)
-            ok = r[:3] == [info.result, info.error_code, info.decoded_size] and r[7] == hashlib.sha256(exp).hexdigest()
-            if ok and info.result == 1:
-                ok = r[3:6] == [info.consumed, info.num_commands, info.num_metablocks]
-            if not ok:
-                bad.setdefault(name, []).append((label, r[:6], (info.result, info.error_code, info.decoded_size, info.consumed, info.num_commands)))
-    assert not bad, {name: (len(b), b[:4]) for name, b in bad.items()}   # (per leg: how many streams, the first ones)
-    strip = lambda rs: [r[:6] + r[7:] for r in rs]   # (everything but engine_commands)
-    for name, g in got.items():
-        assert strip(g["rows"]) == strip(got["general"]["rows"]), name
+    got = H.run_legs(dict_vectors, show=lambda label, row: label in dict_vectors.CARRIERS)
     for name in ("general", "records", "scan", "gang8"):
         for label in dict_vectors.CARRIERS:
-            assert got[name]["rows"][at[label]][6] > 0, (name, label)
+            assert got[name]["rows"][label][H.ENGINE] > 0, (name, label)
     assert got["gang8"]["gangs"] == [8, 8], got["gang8"]["gangs"]
     assert all(g <= 1 for g in got["general"]["gangs"]), got["general"]["gangs"]   # (no gangs)
-    assert all(r[6] == 0 for r in got["norec"]["rows"])
+    assert all(r[H.ENGINE] == 0 for r in got["norec"]["rows"].values())
     print("wall time %.1f s" % (time.time() - t0))
 
 
 def _g_caps(e):
-    """test_gpu_copies._limit_caps for the final copy, and the bytes round position 0's image: where the copy's source passes from the
+    """path_harness.limit_caps for the final copy, and the bytes round position 0's image: where the copy's source passes from the
     dictionary into the output"""
     n, before = (int(x[1:]) for x in e["label"].split("-")[1:3])
     start = e["size"] - n
-    return sorted(set(_limit_caps(e["size"], n)) | {start + before - 1, start + before, start + before + 1})
+    return sorted(set(H.limit_caps(e["size"], n)) | {start + before - 1, start + before, start + before + 1})
 
 
 def _output_limits(pkg):
@@ -147,10 +71,7 @@ def _output_limits(pkg):
         if e["label"].startswith("G-"):
             caps = _g_caps(e)
             assert caps[-1] == e["size"] + 1 and caps[0] == e["size"] - int(e["label"].split("-")[1][1:]) - 3
-            results = []
-            for at in range(0, len(caps), 240):
-                part = caps[at:at + 240]
-                results += dict_streams.check(pkg, [comp] * len(part), part, [d] * len(part), flags=0, what=e["label"])
+            results = H.in_batches(pkg, [comp] * len(caps), caps, [d] * len(caps), what=e["label"])
             assert [r.result for r in results][-3:] == [3, 1, 1], e["label"]
             n += 1
     assert n == 8
@@ -163,9 +84,7 @@ def test_output_limits_at_a_dictionary_copy(pkg):
     Once as the launch picks, once in a fresh process with BROTLI_AMD_NO_SCAN=1."""
     t0 = time.time()
     _output_limits(pkg)
-    script = "import sys; sys.path.insert(0, sys.argv[1]); import conftest, test_gpu_dict_paths as t; print('limits', t._output_limits(conftest.load_pkg()))"
-    out = subprocess.run([sys.executable, "-c", script, os.path.join(ROOT, "tests")], env=_child_env({"BROTLI_AMD_NO_SCAN": "1"}), capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0 and "limits 8" in out.stdout, (out.stdout[-500:], out.stderr[-2000:])
+    assert H.in_a_child("test_gpu_dict_paths", "_output_limits", {"BROTLI_AMD_NO_SCAN": "1"})[0] == 8
     print("wall time %.1f s" % (time.time() - t0))
 
 
@@ -173,15 +92,11 @@ def test_dictionary_streams_in_one_wave_blocks(pkg):
     """two of A's streams and two of C's replicated to 4 * CUs + 1 streams in one batch with their dictionaries, each dictionary the
     same object for all its streams (one upload each): more than four blocks a CU, which are blocks of one wave whatever the streams
     are"""
-    import torch
     t0 = time.time()
-    cus = torch.cuda.get_device_properties(0).multi_processor_count
     by = {e["label"]: (e, c, d) for e, c, d in dict_vectors.load()}
     four = [by["A-matrix-D300-cf"], by["A-matrix-D17-ctx"], by["C-regimes-ctx"], by["C-edge-w10-D2500-cf"]]
-    n = 4 * cus + 1
-    datas, caps, dicts = [four[i % 4][1] for i in range(n)], [four[i % 4][0]["size"] for i in range(n)], [four[i % 4][2] for i in range(n)]
-    assert len({id(d) for d in dicts}) == 4
-    results = dict_streams.check(pkg, datas, caps, dicts, flags=0, what="one-wave blocks")
+    assert len({id(v[2]) for v in four}) == 4
+    results, _ = H.blocks_a_cu(pkg, four)
     for i, r in enumerate(results):
         e = four[i % 4][0]
         assert [r.result, r.error_code, r.decoded_size] == e["oracle"] and [r.consumed, r.num_commands, r.num_metablocks] == e["success"], i
@@ -196,7 +111,6 @@ def _small_streams():
     copies of more than 25 bytes, B's commands round the regimes' borders without the stretch that fills three windows, D's ring streams
     -> [(label, stream, output, dictionary)]"""
     if not _small:
-        M = _gen()
         by = {e["label"]: (e, c, d) for e, c, d in dict_vectors.load()}
         for label in ("A-first-p0-d1-n65-mbend-cf", "A-first-p0-d16-n1040-mbend-cf", "A-first-p2-d17-n1040-last-cf", "A-first-p17-d33-n65-lits-ctx",
                       "D-w22-code5-zero+1", "D-w22-implicit-inside", "D-w10-code9-reach+1", "D-w10-code0-reach", "C-run-ctx"):
@@ -218,19 +132,6 @@ def _small_streams():
     return list(_small)
 
 
-def _product_seq(pkg, data, dictionary, ic, oc):
-    st = pkg.DecoderState(large_window=True, dictionary=dictionary)
-    outs = []
-
-    def step(pending, cap):
-        r = st.decompress_stream(pending, cap)
-        outs.append(r[2])
-        return r[0], r[1], len(r[2])
-    seq = sm.run_schedule(step, data, ic, oc, drain=True)
-    st.close()
-    return seq, b"".join(outs)
-
-
 @pytest.mark.parametrize("chunks", [(1, 1), (3, 3), (65536, 1)])
 def test_small_streams_byte_by_byte(pkg, chunks):
     """cut-down forms of A, B and D through a DecoderState with the dictionary attached: every byte, the final result, the totals of
@@ -242,7 +143,7 @@ def test_small_streams_byte_by_byte(pkg, chunks):
     t0 = time.time()
     for label, comp, raw, d in _small_streams():
         info = dict_vectors.expected(comp, len(raw), d)[0]
-        got, out = _product_seq(pkg, comp, d, ic, oc)
+        got, out = H.product_seq(pkg, comp, ic, oc, d)
         assert got[-1][0] == sm.RESULT_SUCCESS and out == raw, (label, chunks, got[-1], len(out), len(raw))
         assert sum(g[1] for g in got) == info.consumed and sum(g[2] for g in got) == info.decoded_size == len(raw) and all(g[2] <= oc for g in got), (label, chunks)
     print("wall time %.1f s" % (time.time() - t0))
@@ -254,10 +155,4 @@ def test_four_dictionary_streams_in_a_stream_set(pkg):
     small = {s[0]: s for s in _small_streams()}
     names = ["A-matrix-D17-cut-ctx", "B-D600-p408-copy-cut-cf", "B-D2500-p1-copy-cut-ctx", "D-w10-code9-reach+1-cf"]
     jobs = [dict(data=small[n][1], ic=64, oc=37, lw=False, dict=small[n][3]) for n in names]
-    run, twin = Run(pkg, jobs).run(), Run(pkg, jobs).run(how=lambda k: "solo")
-    try:
-        for i, n in enumerate(names):
-            assert run.seq[i] == twin.seq[i] and run.seq[i][-1][0] == 1, n
-            assert run.bytes_of(i) == twin.bytes_of(i) == small[n][2], n
-    finally:
-        run.close(); twin.close()
+    H.stream_set_like_solo(pkg, jobs, names, [small[n][2] for n in names])

@@ -200,7 +200,7 @@ OUTPUT_LABELS = ["T-text-cf", "W-edge-w10-ctx", "W-edge-w16-cf", "L-n64-d64-cf",
 
 @pytest.fixture(scope="module")
 def streams():
-    by = {label: (c, cap) for label, c, cap in cv.leg_set()}
+    by = {label: (c, cap) for label, c, cap, _, _ in cv.leg_set()}
     return [by[label] for label in OUTPUT_LABELS]
 
 

@@ -9,56 +9,18 @@ header in code of its own.  An encoder library writes a sliver of these forms.  
 through each path, against the oracle: result, error code, decoded size, every byte, and for successes consumed, num_commands,
 num_metablocks."""
 import hashlib
-import json
-import os
 import random
-import subprocess
-import sys
 import time
 
 import pytest
 
 import header_vectors
-import stream_model as sm
-from conftest import ROOT
-from test_gpu_copies import _child_env
-from test_gpu_stream_set import Run
-from test_gpu_words import _LEGS, _product_seq, _variants
+import path_harness as H
+
+import make_header_vectors  # noqa: I100  (tools/, which path_harness has put on the path)
 
 pytestmark = pytest.mark.gpu
 LW = header_vectors.FLAG_LARGE_WINDOW
-
-
-def _gen():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import make_header_vectors
-    return make_header_vectors
-
-
-def _check(pkg, datas, caps, what, flags=0, batch=None):
-    """test_gpu_words._check against header_vectors.expected"""
-    own = batch is None
-    batch = batch or pkg.Batch(len(datas))
-    results, outs = batch.decode_host(datas, caps, flags)
-    if own:
-        batch.close()
-    bad = []
-    for i, (d, cap) in enumerate(zip(datas, caps)):
-        info, exp = header_vectors.expected(d, cap, flags & LW)
-        r = results[i]
-        ok = (r.result, r.error_code, r.decoded_size, outs[i]) == (info.result, info.error_code, info.decoded_size, exp)
-        if ok and info.result == 1:
-            ok = r.consumed == info.consumed and r.num_commands == info.num_commands and r.num_metablocks == info.num_metablocks
-        if not ok:
-            first = next((k for k in range(min(len(outs[i]), len(exp))) if outs[i][k] != exp[k]), None)
-            bad.append((i, what, (r.result, r.error_code, r.decoded_size), (info.result, info.error_code, info.decoded_size), r.consumed, info.consumed, len(d), cap, first))
-    assert not bad, (len(bad), bad[:10])
-    return results
-
-
-def _in_batches(pkg, datas, caps, what, flags=0, size=240):
-    for at in range(0, len(datas), size):
-        _check(pkg, datas[at:at + size], caps[at:at + size], "%s %d.." % (what, at), flags)
 
 
 def _family(family):
@@ -68,7 +30,7 @@ def _family(family):
 @pytest.mark.parametrize("family", ["P", "C", "B", "M"])
 def test_every_vector_whole_short_truncated_and_damaged(pkg, family):
     """every stream of tests/golden/emitter_headers/ with exact, one-short, half and roomy output buffers (a random one too:
-    test_gpu_words._variants) and two truncated and two bit-flipped copies each; the one of 16 MiB of output exact and one short;
+    path_harness.variants) and two truncated and two bit-flipped copies each; the one of 16 MiB of output exact and one short;
     without FLAG_LARGE_WINDOW and with it (the large-window streams: with it); batches of at most 240 streams"""
     t0 = time.time()
     rnd = random.Random(2019)
@@ -78,19 +40,13 @@ def test_every_vector_whole_short_truncated_and_damaged(pkg, family):
         if header_vectors.big(e):
             datas += [comp, comp]; caps += [e["size"], e["size"] - 1]
             continue
-        d, c = _variants(rnd, comp, e["size"])
-        d, c = d[:5], c[:5]
-        for k in range(2):
-            d.append(comp[:rnd.randrange(1, len(comp))]); c.append(e["size"] + 4096)
-        for k in range(2):
-            f = bytearray(comp); f[rnd.randrange(len(f))] ^= 1 << rnd.randrange(8)
-            d.append(bytes(f)); c.append(e["size"] + 4096)
+        d, c = H.variants(rnd, comp, e["size"], "tails")
         datas += d; caps += c
         if not e["large"]:
             by_flags[LW][0].extend(d); by_flags[LW][1].extend(c)
     n = 0
     for flags, (datas, caps) in by_flags.items():
-        _in_batches(pkg, datas, caps, family, flags)
+        H.in_batches(pkg, datas, caps, None, flags, family)
         n += len(datas)
     print("wall time %.1f s, %d vectors, %d streams" % (time.time() - t0, len(_family(family)), n))
 
@@ -115,7 +71,7 @@ def test_every_header_cut_at_every_byte(pkg, family, slot):
                 datas.append(comp[:cut]); caps.append(min(e["size"], 1 << 16) + 64)
         n += 1
     for flags, (datas, caps) in by_flags.items():
-        _in_batches(pkg, datas, caps, "%s%s cuts" % (family, slot), flags)
+        H.in_batches(pkg, datas, caps, None, flags, "%s%s cuts" % (family, slot))
     assert n >= 40
     print("wall time %.1f s, %d vectors, %d streams" % (time.time() - t0, n, sum(len(d) for d, _ in by_flags.values())))
 
@@ -125,80 +81,27 @@ def test_the_other_setting_of_the_large_window_flag(pkg):
     the distance codes whose max_symbol lies below their alphabet among them -- without it (E_WINDOW_BITS)"""
     t0 = time.time()
     vectors = [(e, c) for e, c in header_vectors.load() if not header_vectors.big(e)]
-    _in_batches(pkg, [c for e, c in vectors], [header_vectors.cap_of(e) for e, c in vectors], "with the flag", LW)
+    H.in_batches(pkg, [c for e, c in vectors], [header_vectors.cap_of(e) for e, c in vectors], None, LW, "with the flag")
     large = [(e, c) for e, c in vectors if e["large"]]
     assert len(large) >= 80
-    results = _check(pkg, [c for e, c in large], [header_vectors.cap_of(e) for e, c in large], "without the flag", 0)
+    results = H.check(pkg, [c for e, c in large], [header_vectors.cap_of(e) for e, c in large], None, 0, "without the flag")
     assert all((r.result, r.error_code) == (0, -13) for r in results)
     print("wall time %.1f s, %d + %d streams" % (time.time() - t0, len(vectors), len(large)))
 
 
-_LEG_SCRIPT = r"""
-import importlib.util, json, os, sys, hashlib
-ROOT = sys.argv[1]
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import header_vectors
-spec = importlib.util.spec_from_file_location("rust_brotli_decompressor_amd", os.path.join(ROOT, "rust-brotli-decompressor_amd", "__init__.py"))
-pkg = importlib.util.module_from_spec(spec); sys.modules["rust_brotli_decompressor_amd"] = pkg; spec.loader.exec_module(pkg)
-streams = header_vectors.leg_set()
-rows, gangs = [], []
-for part in (streams[:header_vectors.SPLIT], streams[header_vectors.SPLIT:]):
-    for flags in sorted({f for _, _, _, f in part}):
-        sel = [s for s in part if s[3] == flags]
-        b = pkg.Batch(len(sel))
-        res, outs = b.decode_host([c for _, c, _, _ in sel], [cap for _, _, cap, _ in sel], flags)
-        if flags == 0:
-            gangs.append(b.last_gang())
-        b.close()
-        rows += [[l, r.result, r.error_code, r.decoded_size, r.consumed, r.num_commands, r.num_metablocks, r.engine_commands, hashlib.sha256(o).hexdigest()]
-                 for (l, _, _, _), r, o in zip(sel, res, outs)]
-print(json.dumps({"rows": rows, "gangs": gangs}))
-"""
-
-
 def test_every_command_path_agrees_with_the_oracle_and_the_others(pkg):
     """header_vectors.leg_set (two batches, each led by a stream of more than 64 KiB, the size from which a launch forms gangs) in
-    a fresh process per leg of test_gpu_words._LEGS.  All legs return the oracle's status words and SHA-256s, and one another's.
+    a fresh process per leg of path_harness.LEGS.  All legs return the oracle's status words and SHA-256s, and one another's.
     `engine_commands` says which path ran and is printed per leg; what the code guarantees is asserted: none without records, some
     for B's long form (a switch every 1 .. 40 symbols in each category, no context modelling) under the record loop, and gangs in
     the gang leg."""
     t0 = time.time()
-    streams = header_vectors.leg_set()
-    by = {l: (c, cap, f) for l, c, cap, f in streams}
-    got = {}
-    running = [(name, subprocess.Popen([sys.executable, "-c", _LEG_SCRIPT, ROOT], env=_child_env(env), stdin=subprocess.DEVNULL, stdout=subprocess.PIPE,
-                                       stderr=subprocess.PIPE, text=True)) for name, env in _LEGS]
-    try:
-        for name, p in running:
-            out, err = p.communicate(timeout=600)
-            assert p.returncode == 0, (name, err[-2000:])
-            got[name] = json.loads(out.strip().splitlines()[-1])
-    finally:
-        for _, p in running:
-            if p.poll() is None:
-                p.kill(); p.wait()
-    for name, g in got.items():
-        print("engine_commands of num_commands,", name, {r[0]: (r[7], r[5]) for r in g["rows"] if "/" not in r[0] and r[5] >= 40}, "gangs:", g["gangs"])
-    for name, g in got.items():
-        bad = []
-        assert len(g["rows"]) == len(streams)
-        for r in g["rows"]:
-            comp, cap, flags = by[r[0]]
-            info, exp = header_vectors.expected(comp, cap, flags)
-            ok = r[1:4] == [info.result, info.error_code, info.decoded_size] and r[8] == hashlib.sha256(exp).hexdigest()
-            if ok and info.result == 1:
-                ok = r[4:7] == [info.consumed, info.num_commands, info.num_metablocks]
-            if not ok:
-                bad.append((r[:7], (info.result, info.error_code, info.decoded_size, info.consumed, info.num_commands)))
-        assert not bad, (name, len(bad), bad[:8])
-    strip = lambda rs: [r[:7] + r[8:] for r in rs]   # (everything but engine_commands)
-    for name, g in got.items():
-        assert strip(g["rows"]) == strip(got["general"]["rows"]), name
-    eng = lambda name, label: next(r[7] for r in got[name]["rows"] if r[0] == label)
-    assert all(r[7] == 0 for r in got["norec"]["rows"])
+    got = H.run_legs(header_vectors, show=lambda label, row: "/" not in label and row[H.COMMANDS] >= 40)
+    eng = lambda name, label: got[name]["rows"][label][H.ENGINE]
+    assert all(r[H.ENGINE] == 0 for r in got["norec"]["rows"].values())
     assert eng("records", "B-long") > 0, eng("records", "B-long")
     assert all(g >= 2 for g in got["gang8"]["gangs"]) and len(got["gang8"]["gangs"]) == 2, got["gang8"]["gangs"]
-    print("wall time %.1f s, %d streams a leg" % (time.time() - t0, len(streams)))
+    print("wall time %.1f s, %d streams a leg" % (time.time() - t0, len(got["general"]["rows"])))
 
 
 def _arena_set():
@@ -223,7 +126,7 @@ def test_small_lds_arenas(pkg, arena):
             datas += [c, c, c[:rnd.randrange(len(c) // 2, len(c))]]; caps += [header_vectors.cap_of(e), e["size"] // 2, e["size"] + 64]
         for spill in (pkg.FLAG_SPILL_IN_PLACE, 0):
             batch = pkg.Batch(len(datas), lds_arena_bytes=arena)
-            results = _check(pkg, datas, caps, "arena %d spill %d" % (arena, spill), flags | spill, batch)
+            results = H.check(pkg, datas, caps, None, flags | spill, "arena %d spill %d" % (arena, spill), batch)
             batch.close()
             if spill and flags == 0 and arena == 256:
                 assert sum(r.spilled_metablocks for r in results) > 0
@@ -233,23 +136,12 @@ def test_small_lds_arenas(pkg, arena):
 def test_one_wave_blocks(pkg):
     """4 * CUs + 1 streams cycling over eight vectors: more than four blocks a CU, which are blocks of one wave and the small
     automatic arena whatever the streams are"""
-    import torch
     t0 = time.time()
-    cus = torch.cuda.get_device_properties(0).multi_processor_count
     by = {e["label"]: (e, c) for e, c in header_vectors.load()}
     eight = [by[n] for n in ("B-long", "B-lit-n256-ring", "C-imtf-every-tree-r9", "C-some-types-trivial", "P-cmd-depth-sixteens", "P-lit-one-16", "P-cmd-16chain-k5-e3",
                              "P-lit-V-seventeens-21")]
-    n = 4 * cus + 1
-    _check(pkg, [eight[i % 8][1] for i in range(n)], [header_vectors.cap_of(eight[i % 8][0]) for i in range(n)], "one-wave blocks")
+    _, n = H.blocks_a_cu(pkg, eight, cap_of=header_vectors.cap_of)
     print("wall time %.1f s, %d streams" % (time.time() - t0, n))
-
-
-_PROBE_SCRIPT = r"""
-import sys, os, json, hashlib
-sys.path.insert(0, sys.argv[1])
-import conftest, test_gpu_headers as t
-print(json.dumps(t._probe_batch(conftest.load_pkg())))
-"""
 
 
 def _probe_streams(cus):
@@ -258,7 +150,7 @@ def _probe_streams(cus):
     by = {e["label"]: (e, c) for e, c in header_vectors.load()}
     pool = [(c, header_vectors.cap_of(e)) for e, c in (by[n] for n in ("B-long", "B-lit-n256-ring", "B-lit-every-length-code", "B-lit-n255-direct",
                                                                           "B-cmd-every-length-code", "B-long", "B-dist-every-length-code", "B-lit-n256-direct"))]
-    pool += [(c, len(raw) + 64) for _, c, raw in _gen().behind_stored()]
+    pool += [(c, len(raw) + 64) for _, c, raw in make_header_vectors.behind_stored()]
     n = cus + 1
     streams = [pool[i % len(pool)] for i in range(n)]
     assert sum(len(c) for c, _ in streams) >= 8192 * n, sum(len(c) for c, _ in streams) / n
@@ -268,7 +160,7 @@ def _probe_streams(cus):
 def _probe_batch(pkg):
     import torch
     streams = _probe_streams(torch.cuda.get_device_properties(0).multi_processor_count)
-    results = _check(pkg, [c for c, _ in streams], [cap for _, cap in streams], "probe")
+    results = H.check(pkg, [c for c, _ in streams], [cap for _, cap in streams], None, 0, "probe")
     return [len(streams), sum(1 for r in results if r.result == 1)]
 
 
@@ -277,13 +169,10 @@ def test_the_launch_that_asks_first(pkg):
     launch decodes the distance context map and both tree groups in code of its own.  In a child with BROTLI_AMD_DEBUG_PROBE=1:
     stderr shows that it ran, and every result is the oracle's."""
     t0 = time.time()
-    out = subprocess.run([sys.executable, "-c", _PROBE_SCRIPT, os.path.join(ROOT, "tests")], env=_child_env({"BROTLI_AMD_DEBUG_PROBE": "1"}),
-                         capture_output=True, text=True, timeout=600, stdin=subprocess.DEVNULL)
-    assert out.returncode == 0, (out.stdout[-1000:], out.stderr[-3000:])
-    n, good = json.loads(out.stdout.strip().splitlines()[-1])
-    assert "probe: %d streams" % n in out.stderr, out.stderr[-2000:]
+    (n, good), stderr = H.in_a_child("test_gpu_headers", "_probe_batch", {"BROTLI_AMD_DEBUG_PROBE": "1"})
+    assert "probe: %d streams" % n in stderr, stderr[-2000:]
     assert 0 < good < n
-    print(out.stderr.strip().splitlines()[-1])
+    print(stderr.strip().splitlines()[-1])
     print("wall time %.1f s, %d streams" % (time.time() - t0, n))
 
 
@@ -314,10 +203,7 @@ def test_small_streams_byte_by_byte(pkg, family, slot, part, parts, chunks):
     assert len(streams) >= {"P": 60, "C": 40, "B": 30, "M": 30}[family], len(streams)
     streams = sorted(streams, key=lambda x: -x[0]["csize"] - x[0]["size"])[part::parts]
     for e, comp in streams:
-        got, out = _product_seq(pkg, comp, ic, oc)
-        m = sm.ReferenceStream(comp)
-        want = sm.run_schedule(lambda pending, cap: m.call(len(pending), cap), comp, ic, oc, drain=True)
-        assert got == want, (e["label"], chunks, next((i, g, w) for i, (g, w) in enumerate(zip(got + [None], want + [None])) if g != w))
+        out = H.streamed_like_the_model(pkg, comp, ic, oc, e["label"])
         assert out == header_vectors.expected(comp, e["size"], header_vectors.flags_of(e))[1] and hashlib.sha256(out).hexdigest()[:16] == e["sha"], e["label"]
     print("wall time %.1f s, %d streams" % (time.time() - t0, len(streams)))
 
@@ -329,12 +215,7 @@ def test_four_vectors_in_a_stream_set(pkg):
     t0 = time.time()
     names = ["P-cmd-depth-sixteens", "C-imtf-every-tree-r9", "B-ones-all", "M-metadata-run-200x1"]
     jobs = [dict(data=by[n][1], ic=64, oc=37, lw=False) for n in names]
-    run, twin = Run(pkg, jobs).run(), Run(pkg, jobs).run(how=lambda k: "solo")
-    try:
-        for i, n in enumerate(names):
-            assert run.seq[i] == twin.seq[i] and run.seq[i][-1][0] == 1, n
-            exp = header_vectors.expected(by[n][1], by[n][0]["size"], 0)[1]
-            assert run.bytes_of(i) == twin.bytes_of(i) == exp and hashlib.sha256(exp).hexdigest()[:16] == by[n][0]["sha"], n
-    finally:
-        run.close(); twin.close()
+    want = [header_vectors.expected(by[n][1], by[n][0]["size"], 0)[1] for n in names]
+    assert [hashlib.sha256(exp).hexdigest()[:16] for exp in want] == [by[n][0]["sha"] for n in names]
+    H.stream_set_like_solo(pkg, jobs, names, want)
     print("wall time %.1f s" % (time.time() - t0))

@@ -8,57 +8,16 @@ zero or one byte, no ring code that names a word and no invalid reference.  The 
 (tools/make_word_vectors.py, pinned on the CPU by test_emitter_words_cpu.py) do; here they go through each of those paths,
 against the oracle: result, error code, decoded size, every byte, and for successes consumed, num_commands, num_metablocks."""
 import hashlib
-import json
-import os
 import random
-import subprocess
-import sys
 import time
 
 import pytest
 
-import dict_streams
 import oracle_lib as oracle
-import stream_model as sm
+import path_harness as H
 import word_vectors
-from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
-
-
-def _check(pkg, datas, caps, what, flags=0):
-    """test_gpu_engine._check_against_oracle, with the oracle's answers shared between the tests"""
-    batch = pkg.Batch(len(datas))
-    results, outs = batch.decode_host(datas, caps, flags)
-    batch.close()
-    bad = []
-    for i, (d, cap) in enumerate(zip(datas, caps)):
-        info, exp = word_vectors.expected(d, cap, flags)
-        r = results[i]
-        ok = (r.result, r.error_code, r.decoded_size, outs[i]) == (info.result, info.error_code, info.decoded_size, exp)
-        if ok and info.result == 1:
-            ok = r.consumed == info.consumed and r.num_commands == info.num_commands and r.num_metablocks == info.num_metablocks
-        if not ok:
-            first = next((k for k in range(min(len(outs[i]), len(exp))) if outs[i][k] != exp[k]), None)
-            bad.append((i, what, (r.result, r.error_code, r.decoded_size), (info.result, info.error_code, info.decoded_size), r.consumed, info.consumed, len(d), cap, first))
-    assert not bad, (len(bad), bad[:10])
-    return results
-
-
-def _variants(rnd, c, n):
-    """test_gpu_engine._variants: exact, one short, half, random, roomy; four truncated or bit-flipped copies"""
-    datas, caps = [], []
-    for cap in (n, n - 1, n // 2, rnd.randrange(1, max(2, n)), n + 1000):
-        datas.append(c); caps.append(max(0, cap))
-    for _ in range(4):
-        d = bytearray(c)
-        if rnd.random() < 0.4:
-            d = d[:rnd.randrange(1, len(d))]
-        else:
-            for _ in range(rnd.choice([1, 1, 2])):
-                d[rnd.randrange(0, len(d))] ^= 1 << rnd.randrange(8)
-        datas.append(bytes(d)); caps.append(n + 4096)
-    return datas, caps
 
 
 def test_every_vector_whole_short_truncated_and_damaged(pkg):
@@ -69,80 +28,28 @@ def test_every_vector_whole_short_truncated_and_damaged(pkg):
     datas, caps = [], []
     for e, comp in word_vectors.load():
         if e["valid"]:
-            d, c = _variants(rnd, comp, e["size"])
+            d, c = H.variants(rnd, comp, e["size"])
             datas += d; caps += c
         else:
             datas += [comp, comp]; caps += [e["size"] + 64, max(0, e["size"] - 1)]
-    for at in range(0, len(datas), 240):
-        _check(pkg, datas[at:at + 240], caps[at:at + 240], "vectors %d.." % at)
+    H.in_batches(pkg, datas, caps, what="vectors")
     print("wall time %.1f s, %d streams" % (time.time() - t0, len(datas)))
-
-
-_LEG_SCRIPT = r"""
-import importlib.util, json, os, sys, hashlib
-ROOT = sys.argv[1]
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import word_vectors
-spec = importlib.util.spec_from_file_location("rust_brotli_decompressor_amd", os.path.join(ROOT, "rust-brotli-decompressor_amd", "__init__.py"))
-pkg = importlib.util.module_from_spec(spec); sys.modules["rust_brotli_decompressor_amd"] = pkg; spec.loader.exec_module(pkg)
-streams = word_vectors.leg_set()
-rows, gangs = [], []
-for at in (0, 30):
-    part = streams[at:at + 30] if at == 0 else streams[at:]
-    b = pkg.Batch(len(part))
-    res, outs = b.decode_host([c for _, c, _ in part], [cap for _, _, cap in part], 0)
-    gangs.append(b.last_gang())
-    b.close()
-    rows += [[r.result, r.error_code, r.decoded_size, r.consumed, r.num_commands, r.num_metablocks, r.engine_commands, hashlib.sha256(o).hexdigest()] for r, o in zip(res, outs)]
-print(json.dumps({"rows": rows, "gangs": gangs}))
-"""
-
-_LEGS = (("general", {"BROTLI_AMD_GANG": "0"}), ("default", {}), ("gang8", {"BROTLI_AMD_GANG": "8"}), ("scan", {"BROTLI_AMD_ENGINE": "scan"}),
-         ("records", {"BROTLI_AMD_NO_SCAN": "1"}), ("checked", {"BROTLI_AMD_NO_SCAN": "1", "BROTLI_AMD_ENGINE": "norecall"}),
-         ("norec", {"BROTLI_AMD_NO_SCAN": "1", "BROTLI_AMD_ENGINE": "norec"}))
 
 
 def test_every_command_path_agrees_with_the_oracle_and_the_others(pkg):
     """The same 61 streams (word_vectors.leg_set: two batches of about 30, each with one stream of more than 64 KiB, the size
-    from which a launch forms gangs) in a fresh process per leg: the path engine's one-block form with the words inside its passes
-    (BROTLI_AMD_GANG=0), whatever the launch picks, gangs of eight, the scan engine, the command records (BROTLI_AMD_NO_SCAN=1),
-    and the checked loop alone (plus BROTLI_AMD_ENGINE=norecall: no records for metablocks without context; =norec: none at all).
-    All legs return the same status words and SHA-256s, and those are the oracle's.  `engine_commands` says which path ran
-    (csrc/brotli_device_abi.h: commands a command engine took; the record loop's commands count as well, brotli_kernels.hip,
-    `engine_commands += took_` behind lean_rec_commands): the text-like vector C goes through the engine it is meant for."""
+    from which a launch forms gangs) in a fresh process per leg (path_harness.LEGS): the path engine's one-block form with the words
+    inside its passes (BROTLI_AMD_GANG=0), whatever the launch picks, gangs of eight, the scan engine, the command records
+    (BROTLI_AMD_NO_SCAN=1), and the checked loop alone (plus BROTLI_AMD_ENGINE=norecall: no records for metablocks without context;
+    =norec: none at all).  All legs return the same status words and SHA-256s, and those are the oracle's.  `engine_commands` says
+    which path ran (csrc/brotli_device_abi.h: commands a command engine took; the record loop's commands count as well,
+    brotli_kernels.hip, `engine_commands += took_` behind lean_rec_commands): the text-like vector C goes through the engine it is
+    meant for."""
     t0 = time.time()
-    streams = word_vectors.leg_set()
-    labels = [l for l, _, _ in streams]
-    got = {}
-    for name, env in _LEGS:
-        e = dict(os.environ)
-        for k in ("BROTLI_AMD_GANG", "BROTLI_AMD_ENGINE", "BROTLI_AMD_NO_SCAN", "BROTLI_AMD_POOL"):
-            e.pop(k, None)
-        e.update(env)
-        out = subprocess.run([sys.executable, "-c", _LEG_SCRIPT, ROOT], env=e, capture_output=True, text=True, timeout=600)
-        assert out.returncode == 0, (name, out.stderr[-2000:])
-        got[name] = json.loads(out.stdout.strip().splitlines()[-1])
-    share = {name: {l: (r[6], r[4]) for l, r in zip(labels, g["rows"]) if l in ("C-text-cf", "C-text-ctx", "C-text-cf4", "C2-text-long-cf")} for name, g in got.items()}
-    print("engine_commands of num_commands:", share, "gangs:", {name: g["gangs"] for name, g in got.items()})
-    # against the oracle
-    for name, g in got.items():
-        bad = []
-        for (label, comp, cap), r in zip(streams, g["rows"]):
-            info, exp = word_vectors.expected(comp, cap, 0)
-            ok = r[:3] == [info.result, info.error_code, info.decoded_size] and r[7] == hashlib.sha256(exp).hexdigest()
-            if ok and info.result == 1:
-                ok = r[3:6] == [info.consumed, info.num_commands, info.num_metablocks]
-            if not ok:
-                bad.append((label, r[:6], (info.result, info.error_code, info.decoded_size, info.consumed, info.num_commands)))
-        assert not bad, (name, len(bad), bad[:8])
-    # against each other: everything but engine_commands
-    strip = lambda rs: [r[:6] + r[7:] for r in rs]
-    for name, g in got.items():
-        assert strip(g["rows"]) == strip(got["general"]["rows"]), name
+    got = H.run_legs(word_vectors, show=lambda label, row: label in ("C-text-cf", "C-text-ctx", "C-text-cf4", "C2-text-long-cf"))
     # which path ran
-    at = {l: i for i, l in enumerate(labels)}
-    eng = lambda name, label: got[name]["rows"][at[label]][6]
-    cmds = lambda label: got["general"]["rows"][at[label]][4]
+    eng = lambda name, label: got[name]["rows"][label][H.ENGINE]
+    cmds = lambda label: got["general"]["rows"][label][H.COMMANDS]
     for label in ("C-text-cf", "C2-text-long-cf"):
         assert eng("general", label) >= 0.9 * cmds(label), (label, eng("general", label), cmds(label))   # (the words went out inside passes)
         assert eng("default", label) > 0 and eng("gang8", label) > 0 and eng("scan", label) > 0, label
@@ -151,8 +58,8 @@ def test_every_command_path_agrees_with_the_oracle_and_the_others(pkg):
     assert eng("records", "C-text-ctx") >= 0.9 * cmds("C-text-ctx"), (eng("records", "C-text-ctx"), cmds("C-text-ctx"))
     assert got["gang8"]["gangs"] == [8, 8], got["gang8"]["gangs"]
     assert all(g <= 1 for g in got["general"]["gangs"]), got["general"]["gangs"]   # (no gangs)
-    assert all(r[6] == 0 for r in got["norec"]["rows"])
-    assert all(r[6] == 0 for l, r in zip(labels, got["checked"]["rows"]) if "-ctx" not in l)   # (norecall leaves the context-modelled metablocks their records)
+    assert all(r[H.ENGINE] == 0 for r in got["norec"]["rows"].values())
+    assert all(r[H.ENGINE] == 0 for l, r in got["checked"]["rows"].items() if "-ctx" not in l)   # (norecall leaves the context-modelled metablocks their records)
     print("wall time %.1f s" % (time.time() - t0))
 
 
@@ -168,8 +75,7 @@ def test_ring_codes_that_name_words(pkg):
                 for cut in range(4, len(comp)):
                     datas.append(comp[:cut]); caps.append(e["size"] + 64)
     assert len(datas) >= 180
-    for at in range(0, len(datas), 240):
-        _check(pkg, datas[at:at + 240], caps[at:at + 240], "ring codes that name words")
+    H.in_batches(pkg, datas, caps, what="ring codes that name words")
 
 
 def test_output_limits_at_a_final_word(pkg):
@@ -185,37 +91,20 @@ def test_output_limits_at_a_final_word(pkg):
         total = e["size"] - base
         assert total == {"total1": 1, "total2": 2}.get(e["label"].split("-")[1], total) and 1 <= total <= 40
         caps = list(range(e["size"] - total - 3, e["size"] + 2))
-        results = _check(pkg, [comp] * len(caps), caps, e["label"])
+        results = H.check(pkg, [comp] * len(caps), caps, None, 0, e["label"])
         assert [r.result for r in results][-2:] == [1, 1] and results[-3].result == 3
         n += 1
     assert n == 6
-
-
-def _product_seq(pkg, data, ic, oc):
-    st = pkg.DecoderState(large_window=True)
-    outs = []
-
-    def step(pending, cap):
-        r = st.decompress_stream(pending, cap)
-        outs.append(r[2])
-        return r[0], r[1], len(r[2])
-    seq = sm.run_schedule(step, data, ic, oc, drain=True)
-    st.close()
-    return seq, b"".join(outs)
 
 
 @pytest.mark.parametrize("chunks", [(1, 1), (3, 3), (65536, 1)])
 def test_small_streams_byte_by_byte(pkg, chunks):
     """H (at most 600 bytes of output, 30 words) through BrotliDecoderDecompressStream: call for call what the model of the
     reference's driver returns (tests/stream_model.py), as test_stream_contract.py does for the fixtures"""
-    ic, oc = chunks
     n = 0
     for e, comp in word_vectors.load():
         if e["label"].startswith("H-"):
-            got, out = _product_seq(pkg, comp, ic, oc)
-            m = sm.ReferenceStream(comp)
-            want = sm.run_schedule(lambda pending, cap: m.call(len(pending), cap), comp, ic, oc, drain=True)
-            assert got == want, (e["label"], chunks, next((i, g, w) for i, (g, w) in enumerate(zip(got + [None], want + [None])) if g != w))
+            out = H.streamed_like_the_model(pkg, comp, *chunks, e["label"])
             assert out == word_vectors.expected(comp, e["size"], 0)[1] and hashlib.sha256(out).hexdigest() == e["sha256"]
             n += 1
     assert n == 2
@@ -224,8 +113,7 @@ def test_small_streams_byte_by_byte(pkg, chunks):
 def test_small_streams_with_custom_dictionaries(pkg):
     """H's command list emitted again for custom dictionaries of 1, 300 and 70000 bytes: the maximum distance grows by the
     dictionary's size and every word's number with it.  Against brotli_oracle_decode_dict, through the batch call of the
-    custom-dictionary tests (dict_streams.check); without its dictionary such a stream does not decode to the same bytes."""
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    custom-dictionary tests (path_harness.check); without its dictionary such a stream does not decode to the same bytes."""
     import make_word_vectors as M
     rnd = random.Random(300)
     cmds = M.h_commands()
@@ -236,30 +124,23 @@ def test_small_streams_with_custom_dictionaries(pkg):
         for kind in ("cf", "ctx"):
             comp, raw, log, _ = M.emit(cmds, kind, 22, dictionary=dictionary)
             assert raw == plain and sum(1 for r in log if r["word"]) >= 30 and all(r["max_distance"] == r["pos"] + size for r in log if r["word"])
-            info, out = dict_streams.expected(comp, len(raw), 0, dictionary)
+            info, out = H.expected(comp, len(raw), 0, dictionary)
             assert info.result == 1 and out == raw
             assert oracle.decode(comp, len(raw), 0)[1] != raw
             for cap in (len(raw), len(raw) - 1, len(raw) // 2, len(raw) + 1000):
                 datas.append(comp); caps.append(cap); dicts.append(dictionary)
             datas.append(comp[:len(comp) * 2 // 3]); caps.append(len(raw)); dicts.append(dictionary)
-    dict_streams.check(pkg, datas, caps, dicts, flags=0, what="H with custom dictionaries")
+    H.check(pkg, datas, caps, dicts, flags=0, what="H with custom dictionaries")
 
 
 def test_the_matrix_in_one_wave_blocks(pkg):
     """A/CF and A/CTX replicated to 4 * CUs + 1 streams in one batch: more than four blocks a CU, which are blocks of one wave
-    whatever the streams are; status words and one SHA-256 per stream"""
-    import torch
-    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    whatever the streams are; status words and every byte against the oracle, whose bytes have the manifest's SHA-256"""
     by = {e["label"]: (e, c) for e, c in word_vectors.load()}
-    pair = [by["A1-matrix-cf"], by["A1-matrix-ctx"], by["A2-multibyte-cf"], by["A2-multibyte-ctx"]]
-    n = 4 * cus + 1
-    datas = [pair[i % 4][1] for i in range(n)]
-    caps = [pair[i % 4][0]["size"] for i in range(n)]
-    batch = pkg.Batch(n)
-    results, outs = batch.decode_host(datas, caps, 0)
-    batch.close()
-    for i, (r, out) in enumerate(zip(results, outs)):
-        e = pair[i % 4][0]
-        info, exp = word_vectors.expected(datas[i], caps[i], 0)
+    four = [by["A1-matrix-cf"], by["A1-matrix-ctx"], by["A2-multibyte-cf"], by["A2-multibyte-ctx"]]
+    for e, c in four:
+        assert hashlib.sha256(word_vectors.expected(c, e["size"], 0)[1]).hexdigest() == e["sha256"]
+    results, _ = H.blocks_a_cu(pkg, four)
+    for i, r in enumerate(results):
+        e = four[i % 4][0]
         assert (r.result, r.error_code, r.decoded_size, r.consumed, r.num_commands, r.num_metablocks) == (1, 1, e["size"], e["csize"], e["commands"], e["metablocks"]), i
-        assert hashlib.sha256(out).hexdigest() == e["sha256"] == hashlib.sha256(exp).hexdigest(), i

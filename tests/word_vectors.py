@@ -1,58 +1,30 @@
 """tests/golden/emitter_words/ (tools/make_word_vectors.py): the committed streams and the oracle's answers for them.
 Shared by test_emitter_words_cpu.py and test_gpu_words.py."""
-import json
-import random
 import os
+import random
 
-import oracle_lib as oracle
+import path_harness as H
 from conftest import ROOT
+from path_harness import expected  # noqa: F401  ((stream, capacity, flags=0) -> the oracle's answer, computed once)
 
 DIR = os.path.join(ROOT, "tests", "golden", "emitter_words")
 
 
 def load():
     """[(manifest entry, stream)] in the manifest's order"""
-    out = []
-    for e in json.load(open(os.path.join(DIR, "manifest.json"))):
-        if "hex" in e:
-            comp = bytes.fromhex(e["hex"])
-        else:  # (a stream of more than 64 KiB lies in parts)
-            comp = b"".join(open(os.path.join(DIR, name), "rb").read() for name in e.get("files", [e.get("file")]))
-        assert len(comp) == e["csize"], e["label"]
-        out.append((e, comp))
-    return out
+    return H.store.load(DIR)
 
 
-_expected = {}
-
-
-def expected(data, cap, flags=0):
-    """the oracle's answer, computed once per (stream, capacity, flags)"""
-    key = (data, cap, flags)
-    if key not in _expected:
-        _expected[key] = oracle.decode(data, cap, flags)
-    return _expected[key]
+SPLIT = 30  # (leg_set: the second batch starts here)
 
 
 def leg_set():
     """the streams that go through every command path of the device (test_gpu_words.py): every valid vector whole, every
     stream that is invalid on purpose, some of the tiny ones, and short / truncated / damaged copies of a few -> [(label, stream,
-    capacity)].  Positions 0 and 30 hold the long stream, so that each half of the set, decoded as a batch of its own, is one
-    that gets gangs of blocks."""
-    rnd = random.Random(60)
-    by = {e["label"]: (e, c) for e, c in load()}
+    capacity, 0, None)].  Positions 0 and SPLIT hold the long stream, so that each half of the set, decoded as a batch of its own, is
+    one that gets gangs of blocks."""
     out = []
-
-    def take(label, cap=None, damage=None):
-        e, c = by[label]
-        n = e["size"]
-        if damage == "cut":
-            c = c[:rnd.randrange(len(c) // 2, len(c))]
-        elif damage == "flip":
-            d = bytearray(c); d[rnd.randrange(len(d) // 3, len(d))] ^= 1 << rnd.randrange(8); c = bytes(d)
-        cap = {None: n if e["valid"] and not damage else n + 64, "short": n - 1, "half": n // 2, "random": rnd.randrange(1, max(2, n)), "roomy": n + 1000}.get(cap, cap)
-        out.append((label + ("" if cap == n and not damage else "/%s/%s" % (cap, damage)), c, cap))
-
+    take = H.take({e["label"]: (e, c) for e, c in load()}, random.Random(60), out, random_cap=True)
     take("C2-text-long-cf")
     for label in ("A1-matrix", "A2-multibyte", "B-matrix-w10", "B-matrix-w16", "C-text", "D-chains", "F-boundary", "G-utf8-upper", "H-small"):
         take(label + "-cf"); take(label + "-ctx")
@@ -60,7 +32,7 @@ def leg_set():
     for label in ("E-p0-code0", "E-p3-code1", "E-p12-code3", "E-code8-beyond1", "E-code15-beyond1", "E-p0-code0-len2", "E-p4-code9-len25"):
         take(label + ("-cf" if len(out) & 1 else "-ctx"))
     take("F-t121-cf"); take("F-t121-ctx"); take("F-tmax-cf")
-    assert len(out) == 30, len(out)
+    assert len(out) == SPLIT, len(out)
     take("C2-text-long-cf", "short")
     take("F-tmax-ctx")
     for label in ("F-len3", "F-len25", "F-ring-zero", "F-ring-minus2", "F-mlen-plus1", "F-mlen-plus1-ring-end"):

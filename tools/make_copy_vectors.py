@@ -17,7 +17,6 @@ A vector is a list of metablocks (command lists); the ring of the last four dist
 less than 256 bytes live in the manifest ("hex"), the others in files of at most 64 466 bytes ("file" / "files"); a stream that
 would need more than four files is refused (none does)."""
 import hashlib
-import json
 import os
 import random
 import sys
@@ -25,12 +24,12 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "tools"))
 import brotli_emit as E  # noqa: E402
+import vector_store  # noqa: E402
 import make_word_vectors as WV  # noqa: E402
 from make_word_vectors import Literals, plan, ring_or  # noqa: E402,F401
 
 OUT = os.path.join(ROOT, "tests", "golden", "emitter_copies")
-MAX_FILE = WV.MAX_FILE
-MAX_PARTS = 4
+from vector_store import MAX_FILE, MAX_PARTS  # noqa: E402
 PAIRS = ((0, 0), (0, 15), (1, 0), (1, 2), (1, 30), (2, 4), (2, 60), (3, 8), (3, 120))  # D's (NPOSTFIX, NDIRECT)
 M_DIST = list(range(1, 70)) + [95, 96, 97, 127, 128, 129, 255, 256, 257, 511, 512, 1022, 1023, 1024, 1025, 2047, 2048, 4095, 4096, 4097, 65535, 65536, 65537]
 M_LEN = list(range(2, 10)) + [15, 16, 17, 31, 32, 33, 47, 48, 49, 62, 63, 64, 65, 66, 79, 80, 81, 127, 128, 129, 255, 256, 257,
@@ -431,13 +430,10 @@ def vectors():
     return out
 
 
-def main():
+def entries():
+    """(manifest entry, stream) of every vector, checked with the oracle and libbrotlidec"""
     import libbrotli_ref as ref
     import oracle_lib as oracle
-    os.makedirs(OUT, exist_ok=True)
-    for f in os.listdir(OUT):
-        os.remove(os.path.join(OUT, f))
-    manifest = []
     for label, wbits, comp, raw, log, meta in vectors():
         info, got = oracle.decode(comp, len(raw) + 64, 0)
         assert info.result == 1 and got == raw and info.consumed == len(comp), (label, info.result, info.error_code, info.decoded_size, len(raw))
@@ -447,19 +443,12 @@ def main():
             assert r[0] == 1 and r[2] == raw, (label, r[0], r[1])
         e = {"label": label, "window": wbits, "valid": True, "csize": len(comp), "size": len(raw), "sha256": hashlib.sha256(raw).hexdigest(),
              "npostfix": meta["npostfix"], "ndirect": meta["ndirect"], "metablocks": info.num_metablocks, "commands": info.num_commands}
-        if len(comp) < 256:
-            e["hex"] = comp.hex()
-        elif len(comp) <= MAX_FILE:
-            e["file"] = "%s.br" % label
-            open(os.path.join(OUT, e["file"]), "wb").write(comp)
-        else:
-            e["files"] = ["%s.%d.br" % (label, k) for k in range((len(comp) + MAX_FILE - 1) // MAX_FILE)]
-            assert len(e["files"]) <= MAX_PARTS
-            for k, name in enumerate(e["files"]):
-                open(os.path.join(OUT, name), "wb").write(comp[k * MAX_FILE:(k + 1) * MAX_FILE])
-        manifest.append(e)
-        print({k: v for k, v in e.items() if k != "hex"})
-    json.dump(manifest, open(os.path.join(OUT, "manifest.json"), "w"), indent=1)
+        yield e, comp
+        print({k: v for k, v in e.items() if k != "hex"})   # (placed by now)
+
+
+def main():
+    vector_store.write(OUT, entries())
 
 
 if __name__ == "__main__":

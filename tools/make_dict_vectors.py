@@ -27,7 +27,6 @@ a stream's entry its (seed, size).
 `vectors()` is deterministic.  `main()` asks the oracle (brotli_oracle_decode_dict) about every stream before it writes.  Streams
 of less than 256 bytes live in the manifest ("hex"), the others in files of at most 64 466 bytes ("file" / "files")."""
 import hashlib
-import json
 import os
 import random
 import sys
@@ -39,10 +38,11 @@ import dict_gen as DG  # noqa: E402
 import make_copy_vectors as CV  # noqa: E402
 import make_literal_vectors as LV  # noqa: E402
 import make_word_vectors as WV  # noqa: E402
+import vector_store  # noqa: E402
 from make_word_vectors import ring_or  # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden", "emitter_dict")
-MAX_FILE, MAX_PARTS = CV.MAX_FILE, CV.MAX_PARTS
+from vector_store import MAX_FILE, MAX_PARTS  # noqa: E402
 ALPHABET = "etaoinshrdlucmfwypvbgkqjxz ,.0123456789"
 
 A_BEFORE = [1, 2, 3, 4, 7, 8, 15, 16, 17, 31, 32, 33, 63, 64, 65, 1023, 1024, 1025]   # (and D - 1, D)
@@ -528,29 +528,11 @@ def entry(v, oracle_decode_dict):
 
 def main():
     import dict_streams
-    os.makedirs(OUT, exist_ok=True)
-    for f in os.listdir(OUT):
-        os.remove(os.path.join(OUT, f))
-    manifest, dicts = [], {}
-    for v in vectors():
-        dicts[(v["dseed"], v["dsize"])] = hashlib.sha256(dictionary(v["dseed"], v["dsize"])).hexdigest()
-        e = entry(v, dict_streams.oracle_decode_dict)
-        comp = v["comp"]
-        if len(comp) < 256:
-            e["hex"] = comp.hex()
-        elif len(comp) <= MAX_FILE:
-            e["file"] = "%s.br" % v["label"]
-            open(os.path.join(OUT, e["file"]), "wb").write(comp)
-        else:
-            e["files"] = ["%s.%d.br" % (v["label"], k) for k in range((len(comp) + MAX_FILE - 1) // MAX_FILE)]
-            assert len(e["files"]) <= MAX_PARTS
-            for k, name in enumerate(e["files"]):
-                open(os.path.join(OUT, name), "wb").write(comp[k * MAX_FILE:(k + 1) * MAX_FILE])
-        manifest.append(e)
+    made = vectors()
+    dicts = dict.fromkeys((v["dseed"], v["dsize"]) for v in made)   # (in the order of their first use)
+    rows = [{"seed": seed, "size": size, "sha256": hashlib.sha256(dictionary(seed, size)).hexdigest()} for seed, size in dicts]
+    for e in vector_store.write(OUT, ((entry(v, dict_streams.oracle_decode_dict), v["comp"]) for v in made), dictionaries=rows):
         print({k: x for k, x in e.items() if k != "hex"})
-    with open(os.path.join(OUT, "manifest.json"), "w") as f:   # (a line per dictionary and per stream)
-        rows = [json.dumps({"seed": k[0], "size": k[1], "sha256": sha}) for k, sha in dicts.items()]
-        f.write('{"dictionaries": [\n' + ",\n".join(rows) + '\n], "streams": [\n' + ",\n".join(json.dumps(e) for e in manifest) + "\n]}\n")
 
 
 if __name__ == "__main__":

@@ -7,7 +7,6 @@ SHA-256 of the raw data.  The families built on the same emitter, each with a ge
 (tests/golden/emitter_words/), make_copy_vectors.py (emitter_copies/), make_header_vectors.py (emitter_headers/) and
 make_literal_vectors.py (emitter_literals/)."""
 import hashlib
-import json
 import os
 import random
 import sys
@@ -17,6 +16,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join
 import brotli_emit as E  # noqa: E402
 import libbrotli_ref as ref  # noqa: E402
 import oracle_lib as oracle  # noqa: E402
+import vector_store  # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden", "emitter")
 
@@ -101,24 +101,23 @@ def vectors():
     return out
 
 
-def main():
-    os.makedirs(OUT, exist_ok=True)
-    for f in os.listdir(OUT):
-        os.remove(os.path.join(OUT, f))
-    manifest = []
+def entries():
+    """(manifest entry, stream) of every vector, checked with libbrotlidec and the oracle; each in a numbered file of its own"""
     for i, (label, comp, raw) in enumerate(vectors()):
         if ref.available():
             r = ref.decode(comp, len(raw) + 16, False)
             assert r[0] == 1 and r[2] == raw, (label, r[0], r[1])
         info, out = oracle.decode(comp, len(raw) + 16, 0)
         assert info.result == 1 and out == raw, (label, info.result, info.error_code)
-        name = "%02d-%s.br" % (i, label)
-        open(os.path.join(OUT, name), "wb").write(comp)
-        manifest.append({"label": label, "file": name, "csize": len(comp), "size": len(raw), "sha256": hashlib.sha256(raw).hexdigest(),
+        e = {"label": label, "file": "%02d-%s.br" % (i, label), "csize": len(comp), "size": len(raw), "sha256": hashlib.sha256(raw).hexdigest(),
                          "metablocks": info.num_metablocks, "commands": info.num_commands, "max_block_types": info.max_block_types,
-                         "max_literal_trees": info.max_literal_trees})
-        print(manifest[-1])
-    json.dump(manifest, open(os.path.join(OUT, "manifest.json"), "w"), indent=1)
+                         "max_literal_trees": info.max_literal_trees}
+        yield e, comp
+        print(e)
+
+
+def main():
+    vector_store.write(OUT, entries())
 
 
 if __name__ == "__main__":

@@ -23,7 +23,6 @@ which has an entry a line and only what cannot be derived (tests/header_vectors.
 byte in which the first command of the last metablock begins."""
 import hashlib
 import itertools
-import json
 import os
 import random
 import sys
@@ -31,7 +30,9 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "tools"))
 import brotli_emit as E  # noqa: E402
-from make_copy_vectors import MAX_FILE, MAX_PARTS, _dist_range, t_commands  # noqa: E402
+import vector_store  # noqa: E402
+from make_copy_vectors import _dist_range, t_commands  # noqa: E402
+from vector_store import MAX_FILE, MAX_PARTS  # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden", "emitter_headers")
 FRONT = [(b"a valid metablock in front; ", 9, 7), (b"then the header.", 0, 0)]
@@ -705,13 +706,10 @@ def vectors(families="PCBM"):
     return out
 
 
-def main():
+def entries():
+    """(manifest entry, stream) of every vector, checked with the oracle and libbrotlidec"""
     import libbrotli_ref as ref
     import oracle_lib as oracle
-    os.makedirs(OUT, exist_ok=True)
-    for f in os.listdir(OUT):
-        os.remove(os.path.join(OUT, f))
-    manifest, pack = [], bytearray()
     for v in vectors():
         comp, raw, label = v["stream"], v["output"], v["label"]
         flags = 1 if v["large"] else 0
@@ -732,23 +730,12 @@ def main():
         else:
             e["oracle"] = [info.result, info.error_code, info.decoded_size]
         e["csize"] = len(comp)
-        if len(comp) < 256:
-            e["at"] = len(pack)
-            pack += comp
-        elif len(comp) <= MAX_FILE:
-            e["file"] = "%s.br" % label
-            open(os.path.join(OUT, e["file"]), "wb").write(comp)
-        else:
-            e["files"] = ["%s.%d.br" % (label, k) for k in range((len(comp) + MAX_FILE - 1) // MAX_FILE)]
-            assert len(e["files"]) <= MAX_PARTS
-            for k, name in enumerate(e["files"]):
-                open(os.path.join(OUT, name), "wb").write(comp[k * MAX_FILE:(k + 1) * MAX_FILE])
-        manifest.append(e)
-        print(e)
-    for k in range(0, len(pack), MAX_FILE):
-        open(os.path.join(OUT, "small.%d.bin" % (k // MAX_FILE)), "wb").write(pack[k:k + MAX_FILE])
-    with open(os.path.join(OUT, "manifest.json"), "w") as f:   # (an entry a line)
-        f.write("[\n" + ",\n".join(json.dumps(e, separators=(",", ":")) for e in manifest) + "\n]\n")
+        yield e, comp
+        print(e)   # (placed by now)
+
+
+def main():
+    vector_store.write(OUT, entries(), small="pack", style="lines")
 
 
 if __name__ == "__main__":

@@ -31,7 +31,6 @@ fails with "regenerate" if one has moved):
 The files and the manifest are those of tools/make_header_vectors.py; an entry's "runs" is [position, length, ...] of its literal
 runs of 16 literals or more, "probes" [position, cell number, ...] with "cells" the cells' names."""
 import hashlib
-import json
 import os
 import random
 import sys
@@ -39,7 +38,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "tools"))
 import brotli_emit as E  # noqa: E402
-from make_copy_vectors import MAX_FILE, MAX_PARTS  # noqa: E402
+import vector_store  # noqa: E402
+from vector_store import MAX_FILE, MAX_PARTS  # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden", "emitter_literals")
 SPEC_ROUND_MIN, SP_MIN_MLEN, ROOT_BITS, PE_RUN_MIN, PE_RUN_SB, REC_INS_RUN, REC_INS_LONG, LIT_FLUSH, SPEC_WINDOWS = 768, 4096, 8, 6000, 256, 16, 63, 64, 64
@@ -891,13 +891,10 @@ def vectors(families="SEX"):
 NOTES = ("shape", "place", "run", "run2", "ends", "held")
 
 
-def main():
+def entries():
+    """(manifest entry, stream) of every vector, checked with the oracle and libbrotlidec"""
     import libbrotli_ref as ref
     import oracle_lib as oracle
-    os.makedirs(OUT, exist_ok=True)
-    for f in os.listdir(OUT):
-        os.remove(os.path.join(OUT, f))
-    manifest, pack = [], bytearray()
     for v in vectors():
         comp, raw, label = v["stream"], v["output"], v["label"]
         info, got = oracle.decode(comp, len(raw) + 64, 0)
@@ -917,23 +914,12 @@ def main():
         if v["probes"]:
             e["cells"], e["probes"] = v["cells"], v["probes"]
         e["csize"] = len(comp)
-        if len(comp) < 256:
-            e["at"] = len(pack)
-            pack += comp
-        elif len(comp) <= MAX_FILE:
-            e["file"] = "%s.br" % label
-            open(os.path.join(OUT, e["file"]), "wb").write(comp)
-        else:
-            e["files"] = ["%s.%d.br" % (label, k) for k in range((len(comp) + MAX_FILE - 1) // MAX_FILE)]
-            assert len(e["files"]) <= MAX_PARTS
-            for k, name in enumerate(e["files"]):
-                open(os.path.join(OUT, name), "wb").write(comp[k * MAX_FILE:(k + 1) * MAX_FILE])
-        manifest.append(e)
         print(label, len(comp), len(raw))
-    for k in range(0, len(pack), MAX_FILE):
-        open(os.path.join(OUT, "small.%d.bin" % (k // MAX_FILE)), "wb").write(pack[k:k + MAX_FILE])
-    with open(os.path.join(OUT, "manifest.json"), "w") as f:   # (an entry a line)
-        f.write("[\n" + ",\n".join(json.dumps(e, separators=(",", ":")) for e in manifest) + "\n]\n")
+        yield e, comp
+
+
+def main():
+    vector_store.write(OUT, entries(), small="pack", style="lines")
 
 
 if __name__ == "__main__":

@@ -12,7 +12,6 @@ records the oracle's (result, error_code, decoded_size) for the invalid ones.  S
 manifest itself ("hex"); the others are files, one stream of more than 64 KiB -- the size from which a batch's launch gives a
 stream a gang of blocks -- a file per part ("files")."""
 import hashlib
-import json
 import os
 import random
 import sys
@@ -20,9 +19,10 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "tools"))
 import brotli_emit as E  # noqa: E402
+import vector_store  # noqa: E402
+from vector_store import MAX_FILE  # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden", "emitter_words")
-MAX_FILE = 64466  # (the largest file under tests/golden/emitter/; a longer stream is written in parts)
 
 # ------------------------------------------------------------------ plans
 _ALPHABET = b" etaoinshrdlucmfw,.0123456789ETAOINSH\n\"'()-;:\xc3\xa9\xe4\xb8\xad"
@@ -323,14 +323,11 @@ def h_commands():
     return realise(small_commands(random.Random(8)), 22, 11)
 
 
-def main():
+def entries():
+    """(manifest entry, stream) of every vector, checked with the oracle and libbrotlidec"""
     import libbrotli_ref as ref
     import oracle_lib as oracle
-    os.makedirs(OUT, exist_ok=True)
-    for f in os.listdir(OUT):
-        os.remove(os.path.join(OUT, f))
-    manifest = []
-    for i, (label, wbits, comp, raw, log, valid) in enumerate(vectors()):
+    for label, wbits, comp, raw, log, valid in vectors():
         info, got = oracle.decode(comp, len(raw) + 64, 0)
         e = {"label": label, "window": wbits, "valid": valid, "csize": len(comp), "size": len(raw), "sha256": hashlib.sha256(raw).hexdigest()}
         if valid:
@@ -343,18 +340,12 @@ def main():
         else:
             assert info.result == 0 and got[:len(raw)] == raw[:len(got)], (label, info.result, info.error_code)
             e.update({"oracle": [info.result, info.error_code, info.decoded_size]})
-        if len(comp) < 256:
-            e["hex"] = comp.hex()
-        elif len(comp) <= MAX_FILE:
-            e["file"] = "%s.br" % label
-            open(os.path.join(OUT, e["file"]), "wb").write(comp)
-        else:
-            e["files"] = ["%s.%d.br" % (label, k) for k in range((len(comp) + MAX_FILE - 1) // MAX_FILE)]
-            for k, name in enumerate(e["files"]):
-                open(os.path.join(OUT, name), "wb").write(comp[k * MAX_FILE:(k + 1) * MAX_FILE])
-        manifest.append(e)
-        print({k: v for k, v in e.items() if k != "hex"})
-    json.dump(manifest, open(os.path.join(OUT, "manifest.json"), "w"), indent=1)
+        yield e, comp
+        print({k: v for k, v in e.items() if k != "hex"})   # (placed by now)
+
+
+def main():
+    vector_store.write(OUT, entries())
 
 
 if __name__ == "__main__":
