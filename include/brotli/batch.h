@@ -487,7 +487,7 @@ BROTLI_DEC_API int BrotliAmdDebugBitUnpackHost(uint32_t bits, uint32_t width, ui
 /* ---- Unvarint on the device: LEB128 varints of outputs back into elements ----
  *
  * The fifth layout in front of the codec is the VARIABLE-LENGTH INTEGER -- LEB128, protobuf's base-128 varint, plain or zigzag: protobuf packed
- * repeated fields, the block and miniblock headers and first values of Parquet's DELTA_BINARY_PACKED and DELTA_LENGTH_BYTE_ARRAY, the run headers
+ * repeated fields, the block and miniblock headers and first values of Parquet's DELTA_BINARY_PACKED and DELTA_LENGTH_BYTE_ARRAY (a whole stream of which is the undbp calls' below), the run headers
  * of its RLE / bit-packed hybrid (a whole stream of which is the unrle calls' below), ORC's integer runs, Avro's zigzag longs, the postings lists and offset tables of search indexes, sorted ids
  * stored as varint deltas (which the undelta calls above then sum up).  It is the one filter here whose output size DEPENDS ON THE DATA: every
  * segment has a capacity and gets a result.
@@ -629,7 +629,7 @@ BROTLI_DEC_API int BrotliAmdDebugUnvarintHost(uint32_t n, const uint8_t* src, si
  * (csrc/brotli_unrle.h, csrc/brotli_unrle_kernels.hip).
  *
  * OUT OF SCOPE: a speculative parallel walk of one long segment; page framing -- thrift headers, and the 4-byte length in front of v1 levels,
- * where the caller passes src + 4 --; DELTA_BINARY_PACKED; the dictionary gather; ORC's and PackBits' run formats; MSB-first fields; sign
+ * where the caller passes src + 4 --; the dictionary gather; ORC's and PackBits' run formats; MSB-first fields; sign
  * extension. */
 #define BROTLI_AMD_UNRLE_WIDTH_BYTE 1u
 
@@ -691,6 +691,134 @@ BROTLI_DEC_API int BrotliAmdDebugUnrleHost(uint32_t n, const uint8_t* src, size_
                                           const uint64_t* src_lens, const uint64_t* dst_offs, const uint64_t* caps, const uint8_t* bits,
                                           const uint8_t* widths, const uint8_t* flags /* or NULL */, uint32_t src_skew, uint32_t dst_skew,
                                           uint32_t item_elems, uint32_t order_seed, BrotliAmdUnrleResult* results);
+
+/* ---- Undbp on the device: DELTA_BINARY_PACKED blocks of outputs back into elements ----
+ *
+ * The seventh layout in front of the codec is the DELTA BLOCK: Parquet's DELTA_BINARY_PACKED, which v2 writers use for INT32 and INT64 columns
+ * -- timestamps, ids, offsets --, for the lengths of DELTA_LENGTH_BYTE_ARRAY and for the prefix and suffix lengths of DELTA_BYTE_ARRAY.  It is
+ * unvarint's varints, bit-unpack's fields and undelta's running sum in one stream; where a block lies depends on every block header in front of
+ * it, and the values are a running sum across all blocks, so none of those three calls can take it.  Its output size DEPENDS ON THE DATA: every
+ * segment has a capacity and gets a result.
+ *
+ * THE SEGMENT AND ITS PARAMETERS.  A segment is the bytes src[0, len), with an element width w in {1, 2, 4, 8} and a capacity cap in elements.
+ * There are no flags yet: every bit of a flags array is refused.
+ *
+ * HEADER.  Four LEB128 varints by unvarint's value rule, each of at most ten bytes, padded forms such as 80 00 included: B, the values per
+ * block; M, the miniblocks per block; N, the total values; first, zigzag.  The header is BAD_HEADER where a varint is longer than ten bytes,
+ * B == 0, B % 128 != 0, B > 65536, M == 0, B % M != 0 or (B / M) % 32 != 0; the varints are judged first, in their order, then their values.
+ * V = B / M is the values per miniblock.  (Writers use B = 128 or 256 and M = 4; 65536 is this contract's limit.)
+ *
+ * BLOCKS.  Value 0 is `first`.  The N - 1 deltas lie in ceil((N - 1) / B) blocks; N == 0 and N == 1 have none, and N == 0 gives count 0.  A block
+ * is min_delta, a zigzag varint of at most ten bytes; M width bytes; and the payloads of its miniblocks, miniblock j being V fields of width[j]
+ * bits, LSB-first and zero-extended -- bit-unpack's default form -- in V width[j] / 8 bytes.  In the last block only the ceil(remaining / V)
+ * NEEDED miniblocks have payloads; the width bytes of the others are present and are not looked at, whatever they hold; the last needed
+ * miniblock is padded to V fields.
+ *
+ * VALUE.  v_i = v_(i-1) + min_delta(block) + field, wrapping at 64 bits.  Element i is the low 8 w bits of v_i, little-endian at dst + i w, for
+ * i < min(count, cap); with w = 4 this is Parquet's INT32 arithmetic, which wraps at 32 bits.  dst has any alignment.  No byte outside
+ * [dst, dst + min(count, cap) w) is written; nothing outside the 16-byte-aligned span around [src, src + len) is read.
+ *
+ * STOPS.  The decode ends at the first stop; everything in front of it is delivered.
+ *   status                        when                                              count                                     consumed
+ *   BROTLI_AMD_UNDBP_OK           all N values decoded                              N                                         the end of the last needed miniblock
+ *                                                                                                                             (N <= 1: of the header)
+ *   BROTLI_AMD_UNDBP_BAD_HEADER   the list above; a min_delta of more than          0; the values in front of that block      0; that block's offset
+ *                                 ten bytes
+ *   BROTLI_AMD_UNDBP_BAD_WIDTH    a NEEDED miniblock's width byte is above 64       the values in front of that block         that block's offset
+ *   BROTLI_AMD_UNDBP_TRUNCATED    the header, a block's min_delta or its width      0; the values in front of that block      0; that block's offset
+ *                                 bytes reach len
+ *   BROTLI_AMD_UNDBP_TRUNCATED    a needed miniblock's payload reaches len          the values in front, the block's whole    len
+ *                                                                                   miniblocks in front of it, and
+ *                                                                                   floor(8 r / k) values (never more than
+ *                                                                                   are still needed) of the r payload
+ *                                                                                   bytes that are there
+ * (With a header that was read and N != 0, `first` is a value in front of every block.  A width above 64 stops its block whatever payload in
+ * front of it is cut: the width bytes come first.)  OK with consumed < len is no error: the byte data of DELTA_LENGTH_BYTE_ARRAY follows the
+ * lengths, and `consumed` is how the caller finds it.
+ *
+ * RESULT.  Every segment gets a BrotliAmdUndbpResult in host memory.  All of its fields are independent of cap, and of how the work was shared
+ * out.  declared, block_values and miniblocks are as read where the header's four varints were read (a value above 2^32 - 1 as 2^32 - 1), 0
+ * elsewhere.
+ *
+ * Examples (bytes: values; consumed):
+ *   80 01 04 05 0e 02 00 00 00 00: 7, 8, 9, 10, 11; 10
+ *   80 01 04 08 0e 03 02 00 00 00 c0 3f 00 00 00 00 00 00: 7, 5, 3, 1, 2, 3, 4, 5; 18 (the format text's second example)
+ *   80 01 04 01 01: -1; 5
+ *   80 01 04 02 00 ff ff ff ff ff ff ff ff ff 01 00 ee ee ee: 0, -2^63; 19 (a ten-byte min_delta, junk in the unneeded width bytes)
+ *
+ * OUT OF PLACE ONLY: no destination range overlaps any source range or any other destination range of the call.  This is stated, not checked.
+ *
+ * REFUSED ON THE HOST, in front of everything that touches the device: a width outside {1, 2, 4, 8}; any flag bit; cap > 2^56; a NULL d_dst[i]
+ * with caps[i] != 0.
+ *
+ * A call is four launches in stream order, and no block ever waits for another.  1. THE WALK, one wave a segment, on unrle's walk: it reads the
+ * header and every block's min_delta and width bytes -- never a payload --, writes the segment's result, and for every ITEM of the deltas
+ * (BrotliAmdDebugUndbpItemDeltas() deltas) a checkpoint: the offset and first delta of the block that holds the item's first delta.  2. THE
+ * ITEMS' SUMS, one wave an item over the items of all segments: from its checkpoint the wave reads the few block headers that cover the item and
+ * gives each lane a group of 32 fields; the item's sum is an undelta tile record, the first item of a segment a head that carries `first`.
+ * 3. UNDELTA'S CARRY LAUNCH over those records.  4. THE EXPANSION, the same item function, a running sum inside the wave on top of the carry-in,
+ * and the stores.  So one long segment is expanded by every CU; its walk is one wave's.  A call that only counts is the first launch alone
+ * (csrc/brotli_undbp.h, csrc/brotli_undbp_kernels.hip).
+ *
+ * OUT OF SCOPE: the byte part of DELTA_LENGTH_BYTE_ARRAY (`consumed` says where it begins); DELTA_BYTE_ARRAY's prefix copies; page framing --
+ * thrift headers, v2's level sections --; a speculative parallel walk of one long segment; sign extension of elements narrower than 8 bytes. */
+#define BROTLI_AMD_UNDBP_OK 0u
+#define BROTLI_AMD_UNDBP_BAD_HEADER 1u
+#define BROTLI_AMD_UNDBP_BAD_WIDTH 2u
+#define BROTLI_AMD_UNDBP_TRUNCATED 3u
+
+typedef struct BrotliAmdUndbpResult {
+  uint64_t count;         /* values decoded, whatever cap was */
+  uint64_t consumed;      /* the table above */
+  uint64_t declared;      /* N */
+  uint64_t blocks;        /* blocks that gave at least one value */
+  uint32_t status;        /* BROTLI_AMD_UNDBP_* */
+  uint32_t block_values;  /* B */
+  uint32_t miniblocks;    /* M */
+} BrotliAmdUndbpResult;
+
+/* n segments in DEVICE memory -- the stream in the src_lens[i] bytes at d_src[i] becomes elements of widths[i] bytes at d_dst[i], the first
+ * caps[i] of them; flags == NULL or all 0; results[i] says what segment i held; any alignment, any length, 0 included; n is not bound by the
+ * batch object's max_streams --: the launches run on hip_stream, and the call waits on that stream.  caps[i] == 0 needs no destination
+ * (d_dst[i] is not looked at, and d_dst itself may be NULL where every capacity is 0): a call of such segments only counts.  n == 0 returns 0.
+ * A negative value, and a BrotliAmdLastError text that names the segment and what was wrong, for a NULL batch, a NULL array (but flags and
+ * d_dst) with n != 0, and everything in the list above: all of these are checked on the host in front of everything else, so nothing is
+ * launched and no byte is written. */
+BROTLI_DEC_API int BrotliAmdBatchUndbpSegments(BrotliAmdBatch* batch, uint32_t n, const void* const* d_src, const size_t* src_lens, void* const* d_dst,
+                                              const uint64_t* caps, const uint8_t* widths, const uint8_t* flags /* n entries, or NULL: all 0 */,
+                                              BrotliAmdUndbpResult* results, void* hip_stream);
+
+/* The same for the DELIVERED bytes -- [out, out + decoded_size) -- of every stream of the last decode call on the object: stream i's values go
+ * to d_dst[i] (device memory of caps[i] widths[i] bytes, any alignment), and results[i] (one entry per stream) says what it held.
+ * d_dst[i] == NULL skips stream i: none of its parameters are looked at and its result is zeros.  d_dst == NULL or caps == NULL: every stream is
+ * counted and nothing is written.  Where the sources are, and when they are valid, is BrotliAmdBatchUnshuffleOutputs' rule exactly, for the
+ * three kinds of decode call.  A stream that ended in an error or NEEDS_MORE_OUTPUT is taken over its decoded_size bytes.  The launches run on
+ * the stream of that decode call and the call waits for it.  It is not a decode call itself: BrotliAmdBatchPackedOutput stays valid, and
+ * BrotliAmdBatchRelaunch and the Last* accessors say what they said before.  A negative value, and a BrotliAmdLastError text, for a NULL batch,
+ * widths or results, a refused width, flag or cap (nothing is launched), an object without a decode call, a last decode call that failed behind
+ * its argument checks (one of no streams returns 0), and a launch that BrotliAmdBatchWait has not been called for. */
+BROTLI_DEC_API int BrotliAmdBatchUndbpOutputs(BrotliAmdBatch* batch, void* const* d_dst /* or NULL */, const uint64_t* caps /* or NULL */,
+                                             const uint8_t* widths, const uint8_t* flags /* or NULL */, BrotliAmdUndbpResult* results);
+
+/* Milliseconds the undbp kernels took in the last of the two calls above (HIP events around its launches together), */
+BROTLI_DEC_API float BrotliAmdBatchLastUndbpMs(BrotliAmdBatch* batch);
+/* and those of phase 1 (the walk), 2 (the items' sums), 3 (the carries) or 4 (the expansion) alone; another phase: 0. */
+BROTLI_DEC_API float BrotliAmdBatchLastUndbpPhaseMs(BrotliAmdBatch* batch, uint32_t phase);
+
+/* Test hooks (no device needed).  The deltas of one item, and the source bytes that the walk stages at a time; */
+BROTLI_DEC_API uint32_t BrotliAmdDebugUndbpItemDeltas(void);
+BROTLI_DEC_API uint32_t BrotliAmdDebugUndbpWalkChunk(void);
+/* all phases by the functions of csrc/brotli_undbp.h on the host, over n segments given as offsets into one source buffer src[0, src_size) and
+ * one destination buffer dst[0, dst_size): the buffers are placed at src_skew and dst_skew (0..15) past a 16-byte boundary among bytes that are
+ * not theirs.  Segment i is src_lens[i] bytes at src_offs[i]; its elements go to dst_offs[i], where there must be room for min(caps[i], count)
+ * of them.  item_deltas: the deltas of an item, a multiple of 32, 0 for the device's own.  order_seed != 0: the items are taken in an order
+ * shuffled by it, in the sums and in the expansion (the result may not depend on it).  0, results[0..n) filled and the elements' bytes of dst
+ * written (no other byte of dst is); -1, a BrotliAmdLastError text and an untouched dst for a refused width, flag, cap or item size, a skew > 15
+ * or a segment outside its buffer; -2 where a byte outside the elements' destinations changed. */
+BROTLI_DEC_API int BrotliAmdDebugUndbpHost(uint32_t n, const uint8_t* src, size_t src_size, uint8_t* dst, size_t dst_size, const uint64_t* src_offs,
+                                          const uint64_t* src_lens, const uint64_t* dst_offs, const uint64_t* caps, const uint8_t* widths,
+                                          const uint8_t* flags /* or NULL */, uint32_t src_skew, uint32_t dst_skew, uint32_t item_deltas,
+                                          uint32_t order_seed, BrotliAmdUndbpResult* results);
 
 /* Milliseconds the last launch spent in the decode kernel (HIP events on the launch stream). */
 BROTLI_DEC_API float BrotliAmdBatchLastKernelMs(BrotliAmdBatch* batch);

@@ -50,6 +50,8 @@ BATCH_H_SYMBOLS = [
     "BrotliAmdDebugUnvarintTile", "BrotliAmdDebugUnvarintHost",
     "BrotliAmdBatchUnrleSegments", "BrotliAmdBatchUnrleOutputs", "BrotliAmdBatchLastUnrleMs", "BrotliAmdBatchLastUnrlePhaseMs",
     "BrotliAmdDebugUnrleItemElems", "BrotliAmdDebugUnrleWalkChunk", "BrotliAmdDebugUnrleHost",
+    "BrotliAmdBatchUndbpSegments", "BrotliAmdBatchUndbpOutputs", "BrotliAmdBatchLastUndbpMs", "BrotliAmdBatchLastUndbpPhaseMs",
+    "BrotliAmdDebugUndbpItemDeltas", "BrotliAmdDebugUndbpWalkChunk", "BrotliAmdDebugUndbpHost",
 ]
 
 
@@ -93,6 +95,17 @@ class UnrleResult(ctypes.Structure):  # BrotliAmdUnrleResult: what a segment of 
 
     def astuple(self):
         return (self.count, self.consumed, self.runs, self.status, self.bits)
+
+
+UNDBP_OK, UNDBP_BAD_HEADER, UNDBP_BAD_WIDTH, UNDBP_TRUNCATED = 0, 1, 2, 3  # UndbpResult.status
+
+
+class UndbpResult(ctypes.Structure):  # BrotliAmdUndbpResult: what a segment of DELTA_BINARY_PACKED blocks held (batch.h)
+    _fields_ = [("count", ctypes.c_uint64), ("consumed", ctypes.c_uint64), ("declared", ctypes.c_uint64), ("blocks", ctypes.c_uint64),
+                ("status", ctypes.c_uint32), ("block_values", ctypes.c_uint32), ("miniblocks", ctypes.c_uint32)]
+
+    def astuple(self):
+        return (self.count, self.consumed, self.declared, self.blocks, self.status, self.block_values, self.miniblocks)
 
 
 def build(force=False):
@@ -208,7 +221,11 @@ def load_library():
             {"BrotliAmdBatchUnrleSegments": (None, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]), "BrotliAmdBatchUnrleOutputs": (None, [vp, vp, vp, vp, vp, vp, vp]),
              "BrotliAmdBatchLastUnrleMs": (f32, [vp]), "BrotliAmdBatchLastUnrlePhaseMs": (f32, [vp, u32]), "BrotliAmdDebugUnrleItemElems": (u32, None),
              "BrotliAmdDebugUnrleWalkChunk": (u32, None),
-             "BrotliAmdDebugUnrleHost": (None, [u32, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, vp])}):
+             "BrotliAmdDebugUnrleHost": (None, [u32, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, vp])},
+            {"BrotliAmdBatchUndbpSegments": (None, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]), "BrotliAmdBatchUndbpOutputs": (None, [vp, vp, vp, vp, vp, vp]),
+             "BrotliAmdBatchLastUndbpMs": (f32, [vp]), "BrotliAmdBatchLastUndbpPhaseMs": (f32, [vp, u32]), "BrotliAmdDebugUndbpItemDeltas": (u32, None),
+             "BrotliAmdDebugUndbpWalkChunk": (u32, None),
+             "BrotliAmdDebugUndbpHost": (None, [u32, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, vp])}):
         if hasattr(L, next(iter(protos))):
             for name, (restype, argtypes) in protos.items():
                 if restype is not None:
@@ -403,6 +420,41 @@ def unrle_host(src: bytes, segs, dst_size, src_skew=0, dst_skew=0, item_elems=0,
                                  u8s(5, 0), u8s(6, 255), src_skew, dst_skew, item_elems, order_seed, res) != 0:
         raise RuntimeError("BrotliAmdDebugUnrleHost failed: " + last_error())
     return d_buf.raw[:dst_size], [res[i].astuple() for i in range(n)]
+
+
+def undbp_host(src: bytes, segs, dst_size, src_skew=0, dst_skew=0, item_deltas=0, order_seed=0, fill=0):
+    """BrotliAmdDebugUndbpHost: the DELTA_BINARY_PACKED streams in `src` back into elements by the device's walk, block, group and item functions on
+    the host (no device needed).  segs: [(source offset, source length, destination offset, capacity in elements, width)] -- a sixth entry is the
+    segment's flags, which are all refused --; the destination has dst_size bytes, all `fill` in front of the call (or, where `fill` is bytes of
+    that size, those); the buffers are placed at their skews past a 16-byte boundary; item_deltas: the deltas of an item, a multiple of 32 (0: the
+    device's); order_seed != 0 shuffles the order in which the items are taken.
+    -> (the destination's bytes, [(count, consumed, declared, blocks, status, block_values, miniblocks)])"""
+    L = load_library()
+    src = bytes(src)
+    n = len(segs)
+    before = bytes(fill) if isinstance(fill, (bytes, bytearray)) else bytes([fill]) * dst_size
+    if len(before) != dst_size:
+        raise ValueError("fill: %d bytes for a destination of %d" % (len(before), dst_size))
+    s_buf = ctypes.create_string_buffer(src, max(1, len(src)))
+    d_buf = ctypes.create_string_buffer(before, max(1, dst_size))
+    u64s = lambda k: (ctypes.c_uint64 * max(1, n))(*[s[k] if 0 <= s[k] < (1 << 64) else (1 << 64) - 1 for s in segs])
+    widths = (ctypes.c_uint8 * max(1, n))(*[s[4] if 0 <= s[4] <= 255 else 0 for s in segs])
+    flags = (ctypes.c_uint8 * max(1, n))(*[(s[5] if 0 <= s[5] <= 255 else 255) if len(s) > 5 else 0 for s in segs])
+    res = (UndbpResult * max(1, n))()
+    if L.BrotliAmdDebugUndbpHost(n, ctypes.addressof(s_buf), len(src), ctypes.addressof(d_buf), dst_size, u64s(0), u64s(1), u64s(2), u64s(3), widths, flags,
+                                 src_skew, dst_skew, item_deltas, order_seed, res) != 0:
+        raise RuntimeError("BrotliAmdDebugUndbpHost failed: " + last_error())
+    return d_buf.raw[:dst_size], [res[i].astuple() for i in range(n)]
+
+
+def undbp_item_deltas():
+    """BrotliAmdDebugUndbpItemDeltas: the deltas of one item of an undbp call"""
+    return int(load_library().BrotliAmdDebugUndbpItemDeltas())
+
+
+def undbp_walk_chunk():
+    """BrotliAmdDebugUndbpWalkChunk: the source bytes that the walk of an undbp call stages at a time"""
+    return int(load_library().BrotliAmdDebugUndbpWalkChunk())
 
 
 def unrle_item_elems():
@@ -850,6 +902,48 @@ class Batch:
         if phase is None:
             return float(self._L.BrotliAmdBatchLastUnrleMs(self._h))
         return float(self._L.BrotliAmdBatchLastUnrlePhaseMs(self._h, phase))
+
+    def undbp_segments(self, src_ptrs, src_lens, dst_ptrs, caps, widths, flags=None, stream=None):
+        """BrotliAmdBatchUndbpSegments: the DELTA_BINARY_PACKED stream in the src_lens[i] bytes at the device address src_ptrs[i] becomes elements
+        of widths[i] bytes (1, 2, 4, 8) at dst_ptrs[i], the first caps[i] of them; flags: None or all 0; any alignment, any length; out of place;
+        caps[i] == 0 needs no destination (dst_ptrs[i] may be None; dst_ptrs=None: none has one).  Four launches and a wait on `stream`.
+        -> [(count, consumed, declared, blocks, status, block_values, miniblocks)]: what each segment held, whatever its capacity was"""
+        n, col = len(src_ptrs), self._column
+        if len(src_lens) != n or (dst_ptrs is not None and len(dst_ptrs) != n) or len(caps) != n:
+            raise ValueError("src_ptrs, src_lens, dst_ptrs and caps: one entry per segment each")
+        a_d = None if dst_ptrs is None else col(ctypes.c_void_p, [p or None for p in dst_ptrs], n)
+        res = (UndbpResult * max(1, n))()
+        self._filter_call("BrotliAmdBatchUndbpSegments", n, col(ctypes.c_void_p, src_ptrs, n), col(ctypes.c_size_t, src_lens, n), a_d,
+                          col(ctypes.c_uint64, caps, n, (1 << 64) - 1), self._byte_column(widths, n, "widths", 0), self._byte_column(flags, n, "flags"), res, stream)
+        return [res[i].astuple() for i in range(n)]
+
+    def undbp_outputs(self, dst_ptrs, caps, widths, flags=None):
+        """BrotliAmdBatchUndbpOutputs: the delivered bytes of every stream of the last decode call on this object (after decode_device: once
+        wait() has returned), taken as DELTA_BINARY_PACKED streams, become elements of widths[i] bytes at the device address dst_ptrs[i], the
+        first caps[i] of them (None or 0: the stream is skipped, and its result is zeros).  dst_ptrs=None or caps=None: every stream is counted
+        and nothing is written.  Four launches on that call's stream, and a wait.
+        -> [(count, consumed, declared, blocks, status, block_values, miniblocks)], one per stream"""
+        n, col = self.out_n, self._column
+        if (dst_ptrs is not None and len(dst_ptrs) != n) or (caps is not None and len(caps) != n):
+            raise ValueError("dst_ptrs and caps: one entry per stream of the last decode call each")
+        a_d = None if dst_ptrs is None else col(ctypes.c_void_p, [p or None for p in dst_ptrs], n)
+        res = (UndbpResult * max(1, n))()
+        self._filter_call("BrotliAmdBatchUndbpOutputs", a_d, col(ctypes.c_uint64, caps, n, (1 << 64) - 1), self._byte_column(widths, n, "widths", 0),
+                          self._byte_column(flags, n, "flags"), res)
+        return [res[i].astuple() for i in range(n)]
+
+    def count_dbp_outputs(self):
+        """undbp_outputs without destinations: how many values the DELTA_BINARY_PACKED stream of every stream of the last decode call holds, and
+        where it ends -> [(count, consumed, declared, blocks, status, block_values, miniblocks)].  The way to size the destinations of the call
+        that writes"""
+        return self.undbp_outputs(None, None, [8] * self.out_n)
+
+    def last_undbp_ms(self, phase=None):
+        """milliseconds the undbp kernels took in the last undbp_segments / undbp_outputs: all launches together, or phase 1 (the walk), 2 (the
+        items' sums), 3 (the carries) or 4 (the expansion)"""
+        if phase is None:
+            return float(self._L.BrotliAmdBatchLastUndbpMs(self._h))
+        return float(self._L.BrotliAmdBatchLastUndbpPhaseMs(self._h, phase))
 
     def last_bitunpack_ms(self):
         """milliseconds the bit-unpack kernel took in the last bitunpack_segments / bitunpack_outputs"""

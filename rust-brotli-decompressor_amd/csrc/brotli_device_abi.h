@@ -177,6 +177,24 @@ typedef struct BrotliAmdUnrleSeg {
 #define BROTLI_AMD_UNRLE_ITEM_ELEMS 1024u  // elements of one item of the expansion: a wave's share of a destination
 #define BROTLI_AMD_UNRLE_WALK_CHUNK 1024u  // source bytes that a wave stages in LDS at a time: one 16-byte load a lane
 
+// One segment of an undbp call (csrc/brotli_undbp_kernels.hip, csrc/brotli_undbp.h): the len bytes at src are a DELTA_BINARY_PACKED stream, and
+// the first `cap` of its values become elements of `width` bytes (1, 2, 4 or 8) at dst; device addresses of any alignment, len 0 and cap 0
+// included (cap 0: dst is not looked at).  The deltas are cut into ITEMS of BROTLI_AMD_UNDBP_ITEM_DELTAS deltas; first_item is the number of
+// items of the segments in front of this one, so a call's units are one a segment -- its walk -- and one an item.  Every segment has a result
+// (BrotliAmdUndbpResult, include/brotli/batch.h) and its first value behind the table, and every item a checkpoint, a tile record and a carry.
+// No destination range overlaps a source range or another destination range.  Nothing outside [dst, dst + min(count, cap) width) is written;
+// nothing outside the 16-byte-aligned span around [src, src + len) is read.
+typedef struct BrotliAmdUndbpSeg {
+  const uint8_t* src;
+  uint8_t* dst;
+  uint64_t len;
+  uint64_t cap;
+  uint64_t first_item;
+  uint32_t width;
+  uint32_t reserved;
+} BrotliAmdUndbpSeg;
+#define BROTLI_AMD_UNDBP_ITEM_DELTAS 2048u  // deltas of one item: 64 groups of 32 fields, a group a lane
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,16 +1,17 @@
 // brotli_filters.cpp -- the element filters on the device (include/brotli/batch.h): unshuffle (byte planes back into elements), undelta (deltas
 // back into values, a wrapping running sum per segment), bit-unshuffle (bit planes back into elements), bit-unpack (k-bit fields back into
-// elements), unvarint (LEB128 varints back into elements, with a result per segment) and unrle (runs of the RLE / bit-packed hybrid back into
-// elements, with a result per segment as well).  Each takes n segments of device memory
+// elements), unvarint (LEB128 varints back into elements, with a result per segment), unrle (runs of the RLE / bit-packed hybrid back into
+// elements, with a result per segment as well) and undbp (DELTA_BINARY_PACKED blocks back into elements, with a result per segment too).  Each takes n segments of device memory
 // (BrotliAmdBatch*Segments) or the delivered bytes of every stream of the last decode call (BrotliAmdBatch*Outputs), in one launch -- undelta and
 // unvarint in three --, and each has a hook that runs the device's functions of its header (csrc/brotli_unshuffle.h, brotli_undelta.h,
 // brotli_bitunshuffle.h, brotli_bitunpack.h, brotli_unvarint.h) on the host as the kernel's lanes take them, for tests without a device.  What
 // differs between the filters is a descriptor (kFilter), a check of a segment's shape, and the hook's loop; unvarint has a segment of its own
 // (BrotliAmdUnvarintSeg: a source length and a capacity), whose units are its source's, and so has unrle (BrotliAmdUnrleSeg), whose units are
-// one a segment and one an item of its destination.
+// one a segment and one an item of its destination; undbp (BrotliAmdUndbpSeg) is unrle's shape with items of deltas, four launches and five events.
 #include "brotli_bitunpack.h"
 #include "brotli_bitunshuffle.h"
 #include "brotli_host.h"
+#include "brotli_undbp.h"
 #include "brotli_undelta.h"
 #include "brotli_unrle.h"
 #include "brotli_unshuffle.h"
@@ -28,6 +29,11 @@ extern "C" hipError_t brotli_amd_launch_unvarint(const BrotliAmdUnvarintSeg* d_s
                                                  const hipEvent_t* ev);
 extern "C" hipError_t brotli_amd_launch_unrle(const BrotliAmdUnrleSeg* d_segs, uint32_t n, uint64_t units, void* d_scratch, hipStream_t stream,
                                               const hipEvent_t* ev);
+extern "C" hipError_t brotli_amd_launch_undbp(const BrotliAmdUndbpSeg* d_segs, uint32_t n, uint64_t units, void* d_scratch, hipStream_t stream,
+                                              const hipEvent_t* ev);
+extern "C" uint64_t brotli_amd_undbp_scratch_bytes(uint64_t units, uint32_t n);
+extern "C" uint32_t brotli_amd_undbp_item_deltas(void);
+extern "C" uint32_t brotli_amd_undbp_walk_chunk(void);
 extern "C" uint64_t brotli_amd_unrle_scratch_bytes(uint64_t units, uint32_t n);
 extern "C" uint32_t brotli_amd_unrle_item_elems(void);
 extern "C" uint32_t brotli_amd_unrle_walk_chunk(void);
@@ -48,7 +54,7 @@ namespace {
 // What the host needs to know of a filter.  A filter of one launch (`launch`) has two events, recorded around it here; undelta and unvarint
 // (`launch_timed`, `launch_counted`: unvarint's table has its own segments) have four, which their launchers record around and between their
 // launches, and room behind the table that grows with the units -- unvarint's with the segments too, for their results.  Unrle (`launch_runs`)
-// has three around and between its two launches.
+// has three around and between its two launches, undbp (`launch_blocks`) five around and between its four.
 struct FilterDesc {
   const char* name;   // in the texts of g_last_error
   SegCallWhat what;
@@ -57,32 +63,37 @@ struct FilterDesc {
   hipError_t (*launch_timed)(const BrotliAmdUnshuffleSeg*, uint32_t, uint64_t, void*, hipStream_t, const hipEvent_t*);
   hipError_t (*launch_counted)(const BrotliAmdUnvarintSeg*, uint32_t, uint64_t, void*, hipStream_t, const hipEvent_t*);
   hipError_t (*launch_runs)(const BrotliAmdUnrleSeg*, uint32_t, uint64_t, void*, hipStream_t, const hipEvent_t*);
+  hipError_t (*launch_blocks)(const BrotliAmdUndbpSeg*, uint32_t, uint64_t, void*, hipStream_t, const hipEvent_t*);
   uint64_t (*scratch_bytes)(uint64_t units, uint32_t n);   // behind the table (nullptr: nothing)
   uint32_t events;
 };
 const FilterDesc kFilter[kFilters] = {
     {"unshuffle", {"hipMalloc(unshuffle segments)", "hipMemcpyAsync(unshuffle segments)", "hipStreamSynchronize(unshuffle)"},
-     "brotli_amd_unshuffle_kernel launch", brotli_amd_launch_unshuffle, nullptr, nullptr, nullptr, nullptr, 2u},
+     "brotli_amd_unshuffle_kernel launch", brotli_amd_launch_unshuffle, nullptr, nullptr, nullptr, nullptr, nullptr, 2u},
     {"undelta", {"hipMalloc(undelta segments and tiles)", "hipMemcpyAsync(undelta segments)", "hipStreamSynchronize(undelta)"},
-     "brotli_amd_undelta kernels launch", nullptr, brotli_amd_launch_undelta, nullptr, nullptr, [](uint64_t units, uint32_t) { return brotli_amd_undelta_scratch_bytes(units); }, 4u},
+     "brotli_amd_undelta kernels launch", nullptr, brotli_amd_launch_undelta, nullptr, nullptr, nullptr, [](uint64_t units, uint32_t) { return brotli_amd_undelta_scratch_bytes(units); }, 4u},
     {"bit-unshuffle", {"hipMalloc(bit-unshuffle segments)", "hipMemcpyAsync(bit-unshuffle segments)", "hipStreamSynchronize(bit-unshuffle)"},
-     "brotli_amd_bitunshuffle_kernel launch", brotli_amd_launch_bitunshuffle, nullptr, nullptr, nullptr, nullptr, 2u},
+     "brotli_amd_bitunshuffle_kernel launch", brotli_amd_launch_bitunshuffle, nullptr, nullptr, nullptr, nullptr, nullptr, 2u},
     {"bit-unpack", {"hipMalloc(bit-unpack segments)", "hipMemcpyAsync(bit-unpack segments)", "hipStreamSynchronize(bit-unpack)"},
-     "brotli_amd_bitunpack_kernel launch", brotli_amd_launch_bitunpack, nullptr, nullptr, nullptr, nullptr, 2u},
+     "brotli_amd_bitunpack_kernel launch", brotli_amd_launch_bitunpack, nullptr, nullptr, nullptr, nullptr, nullptr, 2u},
     {"unvarint", {"hipMalloc(unvarint segments, tiles and results)", "hipMemcpyAsync(unvarint segments)", "hipStreamSynchronize(unvarint)"},
-     "brotli_amd_unvarint kernels launch", nullptr, nullptr, brotli_amd_launch_unvarint, nullptr, brotli_amd_unvarint_scratch_bytes, 4u},
+     "brotli_amd_unvarint kernels launch", nullptr, nullptr, brotli_amd_launch_unvarint, nullptr, nullptr, brotli_amd_unvarint_scratch_bytes, 4u},
     {"unrle", {"hipMalloc(unrle segments, results and checkpoints)", "hipMemcpyAsync(unrle segments)", "hipStreamSynchronize(unrle)"},
-     "brotli_amd_unrle kernels launch", nullptr, nullptr, nullptr, brotli_amd_launch_unrle, brotli_amd_unrle_scratch_bytes, 3u},
+     "brotli_amd_unrle kernels launch", nullptr, nullptr, nullptr, brotli_amd_launch_unrle, nullptr, brotli_amd_unrle_scratch_bytes, 3u},
+    {"undbp", {"hipMalloc(undbp segments, results, checkpoints and tiles)", "hipMemcpyAsync(undbp segments)", "hipStreamSynchronize(undbp)"},
+     "brotli_amd_undbp kernels launch", nullptr, nullptr, nullptr, nullptr, brotli_amd_launch_undbp, brotli_amd_undbp_scratch_bytes, 5u},
 };
 
 typedef std::vector<BrotliAmdUnshuffleSeg> Segs;
 typedef std::vector<BrotliAmdUnvarintSeg> VarintSegs;
 typedef std::vector<BrotliAmdUnrleSeg> RleSegs;
+typedef std::vector<BrotliAmdUndbpSeg> DbpSegs;
 
 // a segment's units: its destination's words, unvarint's its source's (brotli_seg_walk.h), unrle's one for its walk and one for every item
 inline uint64_t units_of(const BrotliAmdUnshuffleSeg& s) { return brotli_amd_seg_units((uint64_t)(uintptr_t)s.dst, s.len); }
 inline uint64_t units_of(const BrotliAmdUnvarintSeg& s) { return brotli_amd_seg_units((uint64_t)(uintptr_t)s.src, s.len); }
 inline uint64_t units_of(const BrotliAmdUnrleSeg& s) { return 1u + brotli_amd_unrle_items(s.cap, brotli_amd_unrle_item_elems()); }
+inline uint64_t units_of(const BrotliAmdUndbpSeg& s) { return 1u + brotli_amd_undbp_items(s.cap, brotli_amd_undbp_item_deltas()); }
 // a filter's launches over its table
 inline hipError_t launch_of(const FilterDesc& d, const BrotliAmdUnshuffleSeg* d_segs, uint32_t n, uint64_t units, void* d_scratch, hipStream_t stream, const hipEvent_t* ev) {
   return d.launch_timed(d_segs, n, units, d_scratch, stream, ev);
@@ -93,10 +104,14 @@ inline hipError_t launch_of(const FilterDesc& d, const BrotliAmdUnvarintSeg* d_s
 inline hipError_t launch_of(const FilterDesc& d, const BrotliAmdUnrleSeg* d_segs, uint32_t n, uint64_t units, void* d_scratch, hipStream_t stream, const hipEvent_t* ev) {
   return d.launch_runs(d_segs, n, units, d_scratch, stream, ev);
 }
-// ... of one launch (unvarint and unrle have none of these)
+inline hipError_t launch_of(const FilterDesc& d, const BrotliAmdUndbpSeg* d_segs, uint32_t n, uint64_t units, void* d_scratch, hipStream_t stream, const hipEvent_t* ev) {
+  return d.launch_blocks(d_segs, n, units, d_scratch, stream, ev);
+}
+// ... of one launch (unvarint, unrle and undbp have none of these)
 inline hipError_t launch_of(const FilterDesc& d, const BrotliAmdUnshuffleSeg* d_segs, uint32_t n, uint64_t units, hipStream_t stream) { return d.launch(d_segs, n, units, stream); }
 inline hipError_t launch_of(const FilterDesc&, const BrotliAmdUnvarintSeg*, uint32_t, uint64_t, hipStream_t) { return hipErrorInvalidValue; }
 inline hipError_t launch_of(const FilterDesc&, const BrotliAmdUnrleSeg*, uint32_t, uint64_t, hipStream_t) { return hipErrorInvalidValue; }
+inline hipError_t launch_of(const FilterDesc&, const BrotliAmdUndbpSeg*, uint32_t, uint64_t, hipStream_t) { return hipErrorInvalidValue; }
 
 int invalid_arguments(Filter f) { g_last_error = std::string("invalid ") + kFilter[f].name + " arguments"; return -1; }
 
@@ -106,6 +121,7 @@ void no_times(BrotliAmdBatch* b, Filter f) {
   if (f == kUndelta) for (float& ms : b->undelta_phase_ms) ms = 0.0f;
   if (f == kUnvarint) for (float& ms : b->unvarint_phase_ms) ms = 0.0f;
   if (f == kUnrle) for (float& ms : b->unrle_phase_ms) ms = 0.0f;
+  if (f == kUndbp) for (float& ms : b->undbp_phase_ms) ms = 0.0f;
 }
 
 // segs on `stream`, waited for (their shapes were checked).  units_out: their units together; scratch_out: the device memory behind the table,
@@ -130,7 +146,7 @@ int filter_device(BrotliAmdBatch* b, Filter f, const std::vector<Seg>& segs, hip
     if (!d.launch) return hip_ok(launch_of(d, d_segs, n, units, d_scratch, stream, ev), d.launch_what);
     return hip_ok(hipEventRecord(ev[0], stream), "hipEventRecord") && hip_ok(launch_of(d, d_segs, n, units, stream), d.launch_what) &&
            hip_ok(hipEventRecord(ev[1], stream), "hipEventRecord");
-  }, &b->filter[f].ms, f == kUndelta ? b->undelta_phase_ms : f == kUnvarint ? b->unvarint_phase_ms : f == kUnrle ? b->unrle_phase_ms : nullptr);
+  }, &b->filter[f].ms, f == kUndelta ? b->undelta_phase_ms : f == kUnvarint ? b->unvarint_phase_ms : f == kUnrle ? b->unrle_phase_ms : f == kUndbp ? b->undbp_phase_ms : nullptr);
 }
 
 // ---- a call's segments, each checked in front of everything that touches the device ----
@@ -306,6 +322,45 @@ int runs_device(BrotliAmdBatch* b, const RleSegs& segs, const std::vector<size_t
   return 0;
 }
 
+// ---- undbp: a width, no flags and a capacity; a result per segment ----
+// `who` names the segment or stream in the text
+bool known_blocks(uint32_t width, uint32_t flags, uint64_t cap, bool has_dst, const char* who, size_t i) {
+  const char* what = nullptr;
+  if (!brotli_amd_unshuffle_width_ok(width)) what = "width is not 1, 2, 4 or 8";
+  else if (flags != 0u) what = "unknown flag bits";
+  else if (cap > BROTLI_AMD_UNDBP_MAX_CAP) what = "a capacity above 2^56 elements";
+  else if (cap != 0u && !has_dst) what = "no destination for a capacity that is not 0";
+  if (!what) return true;
+  g_last_error = std::string("undbp ") + who + " " + std::to_string(i) + ": " + what + " (width " + std::to_string(width) + ", flags " + std::to_string(flags) +
+                 ", capacity " + std::to_string(cap) + ")";
+  return false;
+}
+// a table's next entry: its first item is the number of items of the entries in front of it
+void push_blocks(DbpSegs* segs, const void* src, void* dst, uint64_t len, uint64_t cap, uint32_t width) {
+  const uint64_t first = segs->empty() ? 0u : segs->back().first_item + brotli_amd_undbp_items(segs->back().cap, brotli_amd_undbp_item_deltas());
+  segs->push_back(BrotliAmdUndbpSeg{static_cast<const uint8_t*>(src), static_cast<uint8_t*>(dst), len, cap, first, width, 0u});
+}
+
+// segs on `stream`, waited for, and their results: segment j's to results[where[j]] of the n_results, the others zeros
+int blocks_device(BrotliAmdBatch* b, const DbpSegs& segs, const std::vector<size_t>& where, BrotliAmdUndbpResult* results, size_t n_results, hipStream_t stream) {
+  std::fill(results, results + n_results, BrotliAmdUndbpResult{0u, 0u, 0u, 0u, 0u, 0u, 0u});
+  const uint8_t* d_scratch = nullptr;
+  if (filter_device(b, kUndbp, segs, stream, nullptr, &d_scratch) != 0) return -1;
+  if (!d_scratch) return 0;   // (no segments)
+  // (a call without items is the walk alone: what lies between the events behind it is no launch's time)
+  if (segs.back().first_item + brotli_amd_undbp_items(segs.back().cap, brotli_amd_undbp_item_deltas()) == 0u) {
+    b->undbp_phase_ms[1] = b->undbp_phase_ms[2] = b->undbp_phase_ms[3] = 0.0f;
+    b->filter[kUndbp].ms = b->undbp_phase_ms[0];
+  }
+  std::vector<BrotliAmdUndbpResult> got(segs.size());
+  DeviceGuard guard;
+  if (!hip_ok(hipSetDevice(b->device), "hipSetDevice") ||
+      !hip_ok(hipMemcpy(got.data(), d_scratch, sizeof(BrotliAmdUndbpResult) * got.size(), hipMemcpyDeviceToHost), "hipMemcpy(undbp results)"))
+    return -1;
+  for (size_t j = 0; j < got.size(); j++) results[where[j]] = got[j];
+  return 0;
+}
+
 // ---- the hooks ----
 // what a hook of one segment ends with: no byte beside the len bytes of the destination may have changed; they go to dst
 int hook_result(Filter f, const SkewedRoom& droom, uint8_t* dst, size_t len) {
@@ -446,6 +501,42 @@ extern "C" int BrotliAmdBatchUnrleOutputs(BrotliAmdBatch* b, void* const* d_dst,
   return runs_device(b, segs, where, results, outs.size(), b->last_stream);
 }
 
+extern "C" int BrotliAmdBatchUndbpSegments(BrotliAmdBatch* b, uint32_t n, const void* const* d_src, const size_t* src_lens, void* const* d_dst,
+                                           const uint64_t* caps, const uint8_t* widths, const uint8_t* flags, BrotliAmdUndbpResult* results, void* hip_stream) {
+  if (!b || (n && (!d_src || !src_lens || !caps || !widths || !results))) return invalid_arguments(kUndbp);
+  no_times(b, kUndbp);
+  DbpSegs segs;
+  std::vector<size_t> where(n);
+  segs.reserve(n);
+  for (uint32_t i = 0; i < n; i++) {
+    void* dst = d_dst ? d_dst[i] : nullptr;   // (no array of destinations: a call that counts, where every capacity is 0)
+    if (!known_blocks(widths[i], flags ? flags[i] : 0u, caps[i], dst != nullptr, "segment", i)) return -1;
+    push_blocks(&segs, d_src[i], dst, src_lens[i], caps[i], widths[i]);
+    where[i] = i;
+  }
+  return blocks_device(b, segs, where, results, n, static_cast<hipStream_t>(hip_stream));
+}
+
+extern "C" int BrotliAmdBatchUndbpOutputs(BrotliAmdBatch* b, void* const* d_dst, const uint64_t* caps, const uint8_t* widths, const uint8_t* flags,
+                                          BrotliAmdUndbpResult* results) {
+  if (!b || !widths || !results) return invalid_arguments(kUndbp);
+  no_times(b, kUndbp);
+  std::vector<DeliveredBytes> outs;
+  if (!delivered_outputs(b, &outs)) return -1;
+  const bool count_only = !d_dst || !caps;   // every stream is counted and nothing is written
+  DbpSegs segs;
+  std::vector<size_t> where;
+  segs.reserve(outs.size());
+  for (size_t i = 0; i < outs.size(); i++) {
+    if (!count_only && d_dst[i] == nullptr) continue;   // skipped: none of its parameters are looked at
+    const uint64_t cap = count_only ? 0u : caps[i];
+    if (!known_blocks(widths[i], flags ? flags[i] : 0u, cap, !count_only, "stream", i)) return -1;
+    push_blocks(&segs, outs[i].ptr, count_only ? nullptr : d_dst[i], outs[i].len, cap, widths[i]);
+    where.push_back(i);
+  }
+  return blocks_device(b, segs, where, results, outs.size(), b->last_stream);
+}
+
 extern "C" float BrotliAmdBatchLastUnshuffleMs(BrotliAmdBatch* b) { return b ? b->filter[kUnshuffle].ms : 0.0f; }
 extern "C" float BrotliAmdBatchLastUndeltaMs(BrotliAmdBatch* b) { return b ? b->filter[kUndelta].ms : 0.0f; }
 extern "C" float BrotliAmdBatchLastUndeltaPhaseMs(BrotliAmdBatch* b, uint32_t phase) { return b && phase >= 1u && phase <= 3u ? b->undelta_phase_ms[phase - 1u] : 0.0f; }
@@ -455,6 +546,10 @@ extern "C" float BrotliAmdBatchLastUnvarintMs(BrotliAmdBatch* b) { return b ? b-
 extern "C" float BrotliAmdBatchLastUnvarintPhaseMs(BrotliAmdBatch* b, uint32_t phase) { return b && phase >= 1u && phase <= 3u ? b->unvarint_phase_ms[phase - 1u] : 0.0f; }
 extern "C" float BrotliAmdBatchLastUnrleMs(BrotliAmdBatch* b) { return b ? b->filter[kUnrle].ms : 0.0f; }
 extern "C" float BrotliAmdBatchLastUnrlePhaseMs(BrotliAmdBatch* b, uint32_t phase) { return b && phase >= 1u && phase <= 2u ? b->unrle_phase_ms[phase - 1u] : 0.0f; }
+extern "C" float BrotliAmdBatchLastUndbpMs(BrotliAmdBatch* b) { return b ? b->filter[kUndbp].ms : 0.0f; }
+extern "C" float BrotliAmdBatchLastUndbpPhaseMs(BrotliAmdBatch* b, uint32_t phase) { return b && phase >= 1u && phase <= 4u ? b->undbp_phase_ms[phase - 1u] : 0.0f; }
+extern "C" uint32_t BrotliAmdDebugUndbpItemDeltas(void) { return brotli_amd_undbp_item_deltas(); }
+extern "C" uint32_t BrotliAmdDebugUndbpWalkChunk(void) { return brotli_amd_undbp_walk_chunk(); }
 extern "C" uint32_t BrotliAmdDebugUnrleItemElems(void) { return brotli_amd_unrle_item_elems(); }
 extern "C" uint32_t BrotliAmdDebugUnrleWalkChunk(void) { return brotli_amd_unrle_walk_chunk(); }
 extern "C" uint32_t BrotliAmdDebugUnvarintTile(void) { return brotli_amd_unvarint_tile_bytes(); }
@@ -688,6 +783,81 @@ extern "C" int BrotliAmdDebugUnrleHost(uint32_t n, const uint8_t* src, size_t sr
     std::fill(inside.begin() + dst_offs[i], inside.begin() + dst_offs[i] + bytes, 1);
   }
   if (!droom.changed_inside_only([&](size_t i) { return i < dst_size && inside[i]; })) { g_last_error = "unrle wrote outside its destination"; return -2; }
+  droom.get(dst, 0u, dst_size);
+  std::copy(got.begin(), got.end(), results);
+  return 0;
+}
+
+// Undbp's phases over n segments given as offsets into one source and one destination buffer, each buffer in its room: every segment's walk, the
+// items' sums in an order shuffled by the seed, the carries as undelta's hook takes them, and the items' stores in another shuffled order.
+extern "C" int BrotliAmdDebugUndbpHost(uint32_t n, const uint8_t* src, size_t src_size, uint8_t* dst, size_t dst_size, const uint64_t* src_offs,
+                                       const uint64_t* src_lens, const uint64_t* dst_offs, const uint64_t* caps, const uint8_t* widths, const uint8_t* flags,
+                                       uint32_t src_skew, uint32_t dst_skew, uint32_t item_deltas, uint32_t order_seed, BrotliAmdUndbpResult* results) {
+  if ((n && (!src_offs || !src_lens || !dst_offs || !caps || !widths || !results)) || (src_size && !src) || (dst_size && !dst) || src_skew > 15u || dst_skew > 15u)
+    return invalid_arguments(kUndbp);
+  if (item_deltas == 0u) item_deltas = brotli_amd_undbp_item_deltas();
+  if (!brotli_amd_undbp_item_ok(item_deltas)) { g_last_error = "invalid undbp arguments: an item that is no multiple of 32 deltas"; return -1; }
+  for (uint32_t i = 0; i < n; i++) {
+    if (!known_blocks(widths[i], flags ? flags[i] : 0u, caps[i], true, "segment", i)) return -1;
+    if (src_lens[i] > src_size || src_offs[i] > src_size - src_lens[i] || dst_offs[i] > dst_size) {
+      g_last_error = "invalid undbp arguments: a segment outside its buffer";
+      return -1;
+    }
+  }
+  SkewedRoom sroom(src_size, src_skew, 0xA5), droom(dst_size, dst_skew, 0x5A);
+  sroom.put(src, src_size);
+  droom.put(dst, dst_size);
+  // the walks: they write nothing, and say how much room every segment needs
+  DbpSegs segs;
+  std::vector<BrotliAmdUndbpResult> got(n);
+  std::vector<uint64_t> firsts(n, 0u), pre(n + 1u, 0u);
+  std::vector<BrotliAmdUndbpCheckpoint> ckpts;
+  for (uint32_t i = 0; i < n; i++) {
+    // (the items of the elements there is room for: the walk marks no others, and a capacity of 2^56 needs no table of its own)
+    const uint64_t room = (dst_size - dst_offs[i]) / widths[i], cap = std::min<uint64_t>(caps[i], room + 1u);
+    segs.push_back(BrotliAmdUndbpSeg{reinterpret_cast<const uint8_t*>((uintptr_t)(sroom.at() + src_offs[i])), reinterpret_cast<uint8_t*>((uintptr_t)(droom.at() + dst_offs[i])),
+                                     src_lens[i], cap, pre[i], widths[i], 0u});
+    pre[i + 1u] = pre[i] + brotli_amd_undbp_items(cap, item_deltas);
+    ckpts.resize(pre[i + 1u], BrotliAmdUndbpCheckpoint{BROTLI_AMD_UNDBP_NONE, BROTLI_AMD_UNDBP_NONE});
+    got[i] = brotli_amd_undbp_host_walk(segs[i], item_deltas, ckpts.data() + pre[i], &firsts[i]);
+    if (std::min(got[i].count, caps[i]) > room) {
+      g_last_error = "invalid undbp arguments: a segment outside its buffer";
+      return -1;
+    }
+  }
+  droom.snapshot();
+  const uint64_t items = pre[n];
+  std::vector<uint64_t> order(items);
+  std::iota(order.begin(), order.end(), (uint64_t)0);
+  uint32_t rnd = order_seed * 2654435761u + 1u;
+  auto shuffle = [&]() {
+    if (order_seed == 0u) return;
+    for (uint64_t i = items; i > 1u; i--) { rnd = rnd * 1664525u + 1013904223u; std::swap(order[i - 1u], order[(rnd >> 8) % i]); }
+  };
+  std::vector<BrotliAmdUndeltaTile> tiles(items);
+  std::vector<uint64_t> carries(items);
+  shuffle();
+  for (uint64_t g : order) {
+    const uint32_t i = brotli_amd_seg_find(pre.data(), n, g);
+    tiles[g] = brotli_amd_undbp_host_sum(segs[i], got[i], ckpts[g], firsts[i], g - pre[i], item_deltas);
+  }
+  BrotliAmdUndeltaPair out = {0u, 0u};
+  for (uint64_t g = 0; g < items; g++) {
+    carries[g] = brotli_amd_undelta_carry_in(out.sum, tiles[g]);
+    out = brotli_amd_undelta_combine(out, brotli_amd_undelta_tile_pair(tiles[g]));
+  }
+  shuffle();
+  for (uint64_t g : order) {
+    const uint32_t i = brotli_amd_seg_find(pre.data(), n, g);
+    brotli_amd_undbp_host_store(segs[i], got[i], ckpts[g], firsts[i], g - pre[i], item_deltas, carries[g]);
+  }
+  // no byte outside every segment's elements may have changed
+  std::vector<uint8_t> inside(dst_size, 0);
+  for (uint32_t i = 0; i < n; i++) {
+    const uint64_t bytes = std::min(got[i].count, caps[i]) * widths[i];
+    std::fill(inside.begin() + dst_offs[i], inside.begin() + dst_offs[i] + bytes, 1);
+  }
+  if (!droom.changed_inside_only([&](size_t i) { return i < dst_size && inside[i]; })) { g_last_error = "undbp wrote outside its destination"; return -2; }
   droom.get(dst, 0u, dst_size);
   std::copy(got.begin(), got.end(), results);
   return 0;

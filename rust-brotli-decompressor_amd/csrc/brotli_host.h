@@ -108,10 +108,10 @@ template <class T = uint8_t> using PinBuf = Buffer<T, Mem::Pinned>;
 // What a call over a table of segments (run_seg_call) keeps with its batch object
 struct SegCall {
   DevBuf<> d;                                                // the segment table of one call and what the call wants behind it
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // around and between its launches (made at the first call, as many as it needs)
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // around and between its launches (made at the first call, as many as it needs)
 };
 
-enum Filter : uint32_t { kUnshuffle, kUndelta, kBitUnshuffle, kBitUnpack, kUnvarint, kUnrle, kFilters };   // the element filters (brotli_filters.cpp)
+enum Filter : uint32_t { kUnshuffle, kUndelta, kBitUnshuffle, kBitUnpack, kUnvarint, kUnrle, kUndbp, kFilters };   // the element filters (brotli_filters.cpp)
 
 constexpr size_t kReaderSlack = 256;   // behind every buffer the kernel reads a stream's bytes from, or writes them to, up to the buffer's end
 
@@ -180,6 +180,7 @@ struct BrotliAmdBatch {
   float undelta_phase_ms[3] = {0.0f, 0.0f, 0.0f};
   float unvarint_phase_ms[3] = {0.0f, 0.0f, 0.0f};   // unvarint's three launches as well; behind its table the summaries, the carries and the segments' results
   float unrle_phase_ms[2] = {0.0f, 0.0f};            // unrle's two launches; behind its table the segments' results, the items' prefix array and their checkpoints
+  float undbp_phase_ms[4] = {0.0f, 0.0f, 0.0f, 0.0f};   // undbp's four launches; behind its table the results, first values, prefix array, checkpoints, tile records and carries
 };
 
 namespace brotli_amd_host {

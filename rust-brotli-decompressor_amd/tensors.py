@@ -17,7 +17,9 @@ streams into their slots and says how many integers each held (Batch.unvarint_ou
 says, unfinished bytes or an integer of more than ten bytes is refused.  A stream whose array was stored as RUNS -- Parquet's RLE / bit-packed
 hybrid: dictionary indices, definition and repetition levels, booleans -- says so in its spec, with its field width k or, where the stream's
 first byte holds k, without; one call decodes all such streams into their slots (Batch.unrle_outputs), and a stream whose runs did not end
-well or held fewer values than its shape says is refused."""
+well or held fewer values than its shape says is refused.  A stream whose array was stored as DELTA BLOCKS -- Parquet's DELTA_BINARY_PACKED:
+INT32 and INT64 pages, the lengths of byte arrays -- says "dbp"; one call decodes all such streams into their slots (Batch.undbp_outputs), and
+a stream that did not end well or held another number of values than its shape says is refused; bytes behind its last block are not judged."""
 import collections
 
 import torch
@@ -32,10 +34,11 @@ def _numel(shape):
     return n
 
 
-FILTERS = ("shuffle", "delta", "bitshuffle", "bitpack", "varint", "rle")
+FILTERS = ("shuffle", "delta", "bitshuffle", "bitpack", "varint", "rle", "dbp")
 BITPACK_OPTIONS = {"big": 1, "signed": 2}   # BITUNPACK_MSB_FIRST, BITUNPACK_SIGNED
 VARINT_OPTIONS = {"zigzag": 1}              # UNVARINT_ZIGZAG
 RLE_WIDTH_BYTE = 1                          # UNRLE_WIDTH_BYTE
+DBP_STATUS = ("ok", "a header that is none", "a miniblock of more than 64 bits", "blocks that the stream's end cuts")
 RLE_STATUS = ("ok", "a header of more than five bytes", "a run of no values", "runs that the stream's end cuts", "a width byte that is none")
 
 
@@ -89,6 +92,8 @@ def _parse_spec(i, spec, size):
         raise ValueError("stream %d: \"varint\" with \"shuffle\", \"bitshuffle\" or \"bitpack\" in one spec: integers of variable length have no planes and no fields" % i)
     if "rle" in flt and ("shuffle" in flt or "bitshuffle" in flt or pack is not None or "varint" in flt):
         raise ValueError("stream %d: \"rle\" with \"shuffle\", \"bitshuffle\", \"bitpack\" or \"varint\" in one spec: runs have no planes, and their fields and headers are their own" % i)
+    if "dbp" in flt and len(flt) != 1 and flt != ("dbp", "delta"):
+        raise ValueError("stream %d: \"dbp\" stands alone or in front of \"delta\": its blocks have no planes, and their fields and varints are their own" % i)
     shape = tuple(int(d) for d in (shape if isinstance(shape, (tuple, list, torch.Size)) else (shape,)))
     item = torch.empty(0, dtype=dtype).element_size()
     if item not in (1, 2, 4, 8):
@@ -100,7 +105,7 @@ def _parse_spec(i, spec, size):
         stored = (_numel(shape) * pack[0] + 7) // 8
         if size != stored:
             raise ValueError("stream %d: %d delivered bytes, but %d fields of %d bits (shape %s) are %d" % (i, size, _numel(shape), pack[0], shape, stored))
-    elif "varint" in flt or "rle" in flt:
+    elif "varint" in flt or "rle" in flt or "dbp" in flt:
         pass   # (how many integers the delivered bytes hold is the call's to say: outputs_as_tensors checks its result)
     elif size != want:
         raise ValueError("stream %d: %d delivered bytes, but %s of shape %s is %d" % (i, size, dtype, shape, want))
@@ -143,6 +148,13 @@ def outputs_as_tensors(batch, specs):
                                               more values than numel are the last group's padding and are not judged
         (dtype, shape, ("rle",))              ... the stream's first byte holds k: a dictionary-index page body
         (dtype, shape, (("rle", 20), "delta"))  runs of deltas: that call, then Batch.undelta_segments in place
+        (dtype, shape, ("dbp",))              a DELTA_BINARY_PACKED stream (Parquet's INT32 and INT64 pages, the lengths of its byte arrays), its
+                                              values truncated to the dtype's elements: ONE Batch.undbp_outputs call for all such streams, into
+                                              the slots.  ValueError, naming the stream and what was found, where the stream does not end well
+                                              (a status that is not OK) or holds another number of values than numel; bytes behind its last
+                                              block are not judged
+        (dtype, shape, ("dbp", "delta"))      such a stream of deltas: that call, then Batch.undelta_segments in place; "dbp" with any other
+                                              filter raises ValueError
     "varint" together with "shuffle", "bitshuffle" or "bitpack" in one spec raises ValueError, naming the stream; so does "rle" together with
     any of those four.
     "shuffle" together with "bitshuffle", and "bitpack" together with either, in one spec raises ValueError, naming the stream; so does a k outside
@@ -177,10 +189,11 @@ def outputs_as_tensors(batch, specs):
     packed = [i for i in wanted if "bitpack" in streams[i].filters]
     varints = [i for i in wanted if "varint" in streams[i].filters]
     runs = [i for i in wanted if "rle" in streams[i].filters]
+    blocks = [i for i in wanted if "dbp" in streams[i].filters]
     # deltas only: every other wanted stream that is neither of bit planes nor of packed fields is the unshuffle call's; without "shuffle" it is
     # a copy -- width 1
-    plain = [i for i in wanted if i not in bits and i not in packed and i not in varints and i not in runs and "shuffle" not in streams[i].filters and "delta" in streams[i].filters]
-    batch.unshuffle_outputs(only([i for i in wanted if i not in plain and i not in bits and i not in packed and i not in varints and i not in runs]),
+    plain = [i for i in wanted if i not in bits and i not in packed and i not in varints and i not in runs and i not in blocks and "shuffle" not in streams[i].filters and "delta" in streams[i].filters]
+    batch.unshuffle_outputs(only([i for i in wanted if i not in plain and i not in bits and i not in packed and i not in varints and i not in runs and i not in blocks]),
                             [st.item if st is not None and "shuffle" in st.filters else 1 for st in streams])
     if bits:    # bit planes: from the outputs straight into the slots
         batch.bitunshuffle_outputs(only(bits), widths, [0 if st is None else st.block for st in streams])
@@ -208,6 +221,15 @@ def outputs_as_tensors(batch, specs):
                                  (i, RLE_STATUS[status] if status < len(RLE_STATUS) else "an unknown status", status, count, consumed, sizes[i], k))
             if count < _numel(streams[i].shape):
                 raise ValueError("stream %d: %d values in its runs, but shape %s is %d elements" % (i, count, streams[i].shape, _numel(streams[i].shape)))
+    if blocks:  # delta blocks: from the outputs straight into the slots; a stream must have ended well and held exactly numel values
+        res = batch.undbp_outputs(only(blocks), [0 if st is None else _numel(st.shape) for st in streams], widths)
+        for i in blocks:
+            count, consumed, declared, _, status, _, _ = res[i]
+            if status != 0:
+                raise ValueError("stream %d: %s (status %d) after %d of %d declared values in %d of its %d delivered bytes" %
+                                 (i, DBP_STATUS[status] if status < len(DBP_STATUS) else "an unknown status", status, count, declared, consumed, sizes[i]))
+            if count != _numel(streams[i].shape):
+                raise ValueError("stream %d: %d values in its blocks, but shape %s is %d elements" % (i, count, streams[i].shape, _numel(streams[i].shape)))
     if plain:   # deltas only: from the outputs straight into the slots
         batch.undelta_outputs(only(plain), widths)
     both = [i for i in wanted if i not in plain and "delta" in streams[i].filters]
