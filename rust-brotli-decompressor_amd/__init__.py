@@ -375,12 +375,10 @@ def undelta_host(src: bytes, segs, dst_size=None, src_skew=0, dst_skew=0, tile_u
     return d_buf.raw[:dst_size]
 
 
-def unvarint_host(src: bytes, segs, dst_size, src_skew=0, dst_skew=0, tile_units=0, order_seed=0, fill=0):
-    """BrotliAmdDebugUnvarintHost: the LEB128 varints in `src` back into elements by the device's unit and tile functions on the host (no device
-    needed).  segs: [(source offset, source length, destination offset, capacity in elements, width, flags)]; the destination has dst_size bytes,
-    all `fill` in front of the call (or, where `fill` is bytes of that size, those); the buffers are placed at their skews past a 16-byte
-    boundary; tile_units: the 16-byte units of SOURCE in a tile (0: the kernel's); order_seed != 0 shuffles the order in which the tiles are
-    taken.  -> (the destination's bytes, [(count, consumed, overlong)])"""
+def _counted_host(fn_name, Result, src, segs, dst_size, columns, src_skew, dst_skew, knob, order_seed, fill):
+    """what the hooks of the filters with a result per segment share.  segs: [(source offset, source length, destination offset, capacity, ...)];
+    columns: [(index in a segment's tuple, what stands in for a value no byte holds)], the byte columns in the call's order; knob: the tile or item
+    size.  -> (the destination's bytes, [a result's tuple per segment])"""
     L = load_library()
     src = bytes(src)
     n = len(segs)
@@ -389,14 +387,21 @@ def unvarint_host(src: bytes, segs, dst_size, src_skew=0, dst_skew=0, tile_units
         raise ValueError("fill: %d bytes for a destination of %d" % (len(before), dst_size))
     s_buf = ctypes.create_string_buffer(src, max(1, len(src)))
     d_buf = ctypes.create_string_buffer(before, max(1, dst_size))
-    u64s = lambda k: (ctypes.c_uint64 * max(1, n))(*[s[k] if 0 <= s[k] < (1 << 64) else (1 << 64) - 1 for s in segs])
-    a_w = (ctypes.c_uint8 * max(1, n))(*[s[4] if 0 <= s[4] <= 255 else 0 for s in segs])
-    a_f = (ctypes.c_uint8 * max(1, n))(*[s[5] if 0 <= s[5] <= 255 else 255 for s in segs])
-    res = (UnvarintResult * max(1, n))()
-    if L.BrotliAmdDebugUnvarintHost(n, ctypes.addressof(s_buf), len(src), ctypes.addressof(d_buf), dst_size, u64s(0), u64s(1), u64s(2), u64s(3), a_w, a_f,
-                                    src_skew, dst_skew, tile_units, order_seed, res) != 0:
-        raise RuntimeError("BrotliAmdDebugUnvarintHost failed: " + last_error())
+    u64s = [(ctypes.c_uint64 * max(1, n))(*[s[k] if 0 <= s[k] < (1 << 64) else (1 << 64) - 1 for s in segs]) for k in range(4)]
+    u8s = [(ctypes.c_uint8 * max(1, n))(*[s[k] if 0 <= s[k] <= 255 else bad for s in segs]) for k, bad in columns]
+    res = (Result * max(1, n))()
+    if getattr(L, fn_name)(n, ctypes.addressof(s_buf), len(src), ctypes.addressof(d_buf), dst_size, *u64s, *u8s, src_skew, dst_skew, knob, order_seed, res) != 0:
+        raise RuntimeError(fn_name + " failed: " + last_error())
     return d_buf.raw[:dst_size], [res[i].astuple() for i in range(n)]
+
+
+def unvarint_host(src: bytes, segs, dst_size, src_skew=0, dst_skew=0, tile_units=0, order_seed=0, fill=0):
+    """BrotliAmdDebugUnvarintHost: the LEB128 varints in `src` back into elements by the device's unit and tile functions on the host (no device
+    needed).  segs: [(source offset, source length, destination offset, capacity in elements, width, flags)]; the destination has dst_size bytes,
+    all `fill` in front of the call (or, where `fill` is bytes of that size, those); the buffers are placed at their skews past a 16-byte
+    boundary; tile_units: the 16-byte units of SOURCE in a tile (0: the kernel's); order_seed != 0 shuffles the order in which the tiles are
+    taken.  -> (the destination's bytes, [(count, consumed, overlong)])"""
+    return _counted_host("BrotliAmdDebugUnvarintHost", UnvarintResult, src, segs, dst_size, [(4, 0), (5, 255)], src_skew, dst_skew, tile_units, order_seed, fill)
 
 
 def unrle_host(src: bytes, segs, dst_size, src_skew=0, dst_skew=0, item_elems=0, order_seed=0, fill=0):
@@ -405,21 +410,7 @@ def unrle_host(src: bytes, segs, dst_size, src_skew=0, dst_skew=0, item_elems=0,
     has dst_size bytes, all `fill` in front of the call (or, where `fill` is bytes of that size, those); the buffers are placed at their skews
     past a 16-byte boundary; item_elems: the elements of an item (0: the device's); order_seed != 0 shuffles the order in which the items are
     taken.  -> (the destination's bytes, [(count, consumed, runs, status, bits)])"""
-    L = load_library()
-    src = bytes(src)
-    n = len(segs)
-    before = bytes(fill) if isinstance(fill, (bytes, bytearray)) else bytes([fill]) * dst_size
-    if len(before) != dst_size:
-        raise ValueError("fill: %d bytes for a destination of %d" % (len(before), dst_size))
-    s_buf = ctypes.create_string_buffer(src, max(1, len(src)))
-    d_buf = ctypes.create_string_buffer(before, max(1, dst_size))
-    u64s = lambda k: (ctypes.c_uint64 * max(1, n))(*[s[k] if 0 <= s[k] < (1 << 64) else (1 << 64) - 1 for s in segs])
-    u8s = lambda k, bad: (ctypes.c_uint8 * max(1, n))(*[s[k] if 0 <= s[k] <= 255 else bad for s in segs])
-    res = (UnrleResult * max(1, n))()
-    if L.BrotliAmdDebugUnrleHost(n, ctypes.addressof(s_buf), len(src), ctypes.addressof(d_buf), dst_size, u64s(0), u64s(1), u64s(2), u64s(3), u8s(4, 255),
-                                 u8s(5, 0), u8s(6, 255), src_skew, dst_skew, item_elems, order_seed, res) != 0:
-        raise RuntimeError("BrotliAmdDebugUnrleHost failed: " + last_error())
-    return d_buf.raw[:dst_size], [res[i].astuple() for i in range(n)]
+    return _counted_host("BrotliAmdDebugUnrleHost", UnrleResult, src, segs, dst_size, [(4, 255), (5, 0), (6, 255)], src_skew, dst_skew, item_elems, order_seed, fill)
 
 
 def undbp_host(src: bytes, segs, dst_size, src_skew=0, dst_skew=0, item_deltas=0, order_seed=0, fill=0):
@@ -429,22 +420,8 @@ def undbp_host(src: bytes, segs, dst_size, src_skew=0, dst_skew=0, item_deltas=0
     that size, those); the buffers are placed at their skews past a 16-byte boundary; item_deltas: the deltas of an item, a multiple of 32 (0: the
     device's); order_seed != 0 shuffles the order in which the items are taken.
     -> (the destination's bytes, [(count, consumed, declared, blocks, status, block_values, miniblocks)])"""
-    L = load_library()
-    src = bytes(src)
-    n = len(segs)
-    before = bytes(fill) if isinstance(fill, (bytes, bytearray)) else bytes([fill]) * dst_size
-    if len(before) != dst_size:
-        raise ValueError("fill: %d bytes for a destination of %d" % (len(before), dst_size))
-    s_buf = ctypes.create_string_buffer(src, max(1, len(src)))
-    d_buf = ctypes.create_string_buffer(before, max(1, dst_size))
-    u64s = lambda k: (ctypes.c_uint64 * max(1, n))(*[s[k] if 0 <= s[k] < (1 << 64) else (1 << 64) - 1 for s in segs])
-    widths = (ctypes.c_uint8 * max(1, n))(*[s[4] if 0 <= s[4] <= 255 else 0 for s in segs])
-    flags = (ctypes.c_uint8 * max(1, n))(*[(s[5] if 0 <= s[5] <= 255 else 255) if len(s) > 5 else 0 for s in segs])
-    res = (UndbpResult * max(1, n))()
-    if L.BrotliAmdDebugUndbpHost(n, ctypes.addressof(s_buf), len(src), ctypes.addressof(d_buf), dst_size, u64s(0), u64s(1), u64s(2), u64s(3), widths, flags,
-                                 src_skew, dst_skew, item_deltas, order_seed, res) != 0:
-        raise RuntimeError("BrotliAmdDebugUndbpHost failed: " + last_error())
-    return d_buf.raw[:dst_size], [res[i].astuple() for i in range(n)]
+    segs = [tuple(s) if len(s) > 5 else tuple(s) + (0,) for s in segs]
+    return _counted_host("BrotliAmdDebugUndbpHost", UndbpResult, src, segs, dst_size, [(4, 0), (5, 255)], src_skew, dst_skew, item_deltas, order_seed, fill)
 
 
 def undbp_item_deltas():
@@ -741,6 +718,34 @@ class Batch:
         self._filter_call(name, col(ctypes.c_void_p, [p or None for p in dst_ptrs], n), col(ctypes.c_uint8, widths, n, 0),
                           *[self._block_column(b, n) for b in blocks])
 
+    def _counted_segments(self, name, Result, src_ptrs, src_lens, dst_ptrs, caps, columns, stream):
+        """BrotliAmdBatch<name>Segments of a filter with a capacity and a result per segment.  columns: its byte columns in the call's order, each
+        (values, its name, what stands in for a value no byte holds).  -> [a result's tuple per segment]"""
+        n, col = len(src_ptrs), self._column
+        if len(src_lens) != n or (dst_ptrs is not None and len(dst_ptrs) != n) or len(caps) != n:
+            raise ValueError("src_ptrs, src_lens, dst_ptrs and caps: one entry per segment each")
+        a_d = None if dst_ptrs is None else col(ctypes.c_void_p, [p or None for p in dst_ptrs], n)
+        res = (Result * max(1, n))()
+        self._filter_call(name, n, col(ctypes.c_void_p, src_ptrs, n), col(ctypes.c_size_t, src_lens, n), a_d, col(ctypes.c_uint64, caps, n, (1 << 64) - 1),
+                          *[self._byte_column(v, n, what, bad) for v, what, bad in columns], res, stream)
+        return [res[i].astuple() for i in range(n)]
+
+    def _counted_outputs(self, name, Result, dst_ptrs, caps, columns):
+        """BrotliAmdBatch<name>Outputs of such a filter over the streams of the last decode call -> [a result's tuple per stream]"""
+        n, col = self.out_n, self._column
+        if (dst_ptrs is not None and len(dst_ptrs) != n) or (caps is not None and len(caps) != n):
+            raise ValueError("dst_ptrs and caps: one entry per stream of the last decode call each")
+        a_d = None if dst_ptrs is None else col(ctypes.c_void_p, [p or None for p in dst_ptrs], n)
+        res = (Result * max(1, n))()
+        self._filter_call(name, a_d, col(ctypes.c_uint64, caps, n, (1 << 64) - 1), *[self._byte_column(v, n, what, bad) for v, what, bad in columns], res)
+        return [res[i].astuple() for i in range(n)]
+
+    def _last_ms(self, stem, phase):
+        """BrotliAmdBatchLast<stem>Ms, or BrotliAmdBatchLast<stem>PhaseMs of one launch"""
+        if phase is None:
+            return float(getattr(self._L, "BrotliAmdBatchLast%sMs" % stem)(self._h))
+        return float(getattr(self._L, "BrotliAmdBatchLast%sPhaseMs" % stem)(self._h, phase))
+
     def unshuffle_segments(self, src_ptrs, dst_ptrs, lens, widths, stream=None):
         """BrotliAmdBatchUnshuffleSegments: lens[i] bytes of byte planes at the device address src_ptrs[i] become elements of widths[i] bytes
         (1, 2, 4, 8) at dst_ptrs[i]; any alignment, any length; out of place.  One launch and a wait on `stream`."""
@@ -770,9 +775,7 @@ class Batch:
 
     def last_undelta_ms(self, phase=None):
         """milliseconds the undelta kernels took in the last undelta_segments / undelta_outputs: all launches together, or phase 1, 2 or 3"""
-        if phase is None:
-            return float(self._L.BrotliAmdBatchLastUndeltaMs(self._h))
-        return float(self._L.BrotliAmdBatchLastUndeltaPhaseMs(self._h, phase))
+        return self._last_ms("Undelta", phase)
 
     def _block_column(self, blocks, n):
         """block sizes as the C calls take them: None (all 0), or n of them"""
@@ -822,28 +825,14 @@ class Batch:
         widths[i] bytes (1, 2, 4, 8) at dst_ptrs[i], the first caps[i] of them, by flags[i] (UNVARINT_ZIGZAG; None: all 0); any alignment, any
         length; out of place; caps[i] == 0 needs no destination (dst_ptrs[i] may be None; dst_ptrs=None: none has one).  Three launches and a
         wait on `stream`.  -> [(count, consumed, overlong)]: what each segment held, whatever its capacity was"""
-        n, col = len(src_ptrs), self._column
-        if len(src_lens) != n or (dst_ptrs is not None and len(dst_ptrs) != n) or len(caps) != n:
-            raise ValueError("src_ptrs, src_lens, dst_ptrs and caps: one entry per segment each")
-        a_d = None if dst_ptrs is None else col(ctypes.c_void_p, [p or None for p in dst_ptrs], n)
-        res = (UnvarintResult * max(1, n))()
-        self._filter_call("BrotliAmdBatchUnvarintSegments", n, col(ctypes.c_void_p, src_ptrs, n), col(ctypes.c_size_t, src_lens, n), a_d,
-                          col(ctypes.c_uint64, caps, n, (1 << 64) - 1), self._byte_column(widths, n, "widths", 0), self._byte_column(flags, n, "flags"), res, stream)
-        return [res[i].astuple() for i in range(n)]
+        return self._counted_segments("BrotliAmdBatchUnvarintSegments", UnvarintResult, src_ptrs, src_lens, dst_ptrs, caps, [(widths, "widths", 0), (flags, "flags", 255)], stream)
 
     def unvarint_outputs(self, dst_ptrs, caps, widths, flags=None):
         """BrotliAmdBatchUnvarintOutputs: the delivered bytes of every stream of the last decode call on this object (after decode_device: once
         wait() has returned), taken as LEB128 varints, become elements of widths[i] bytes at the device address dst_ptrs[i], the first caps[i]
         of them (None or 0: the stream is skipped, and its result is zeros).  dst_ptrs=None or caps=None: every stream is counted and nothing is
         written.  Three launches on that call's stream, and a wait.  -> [(count, consumed, overlong)], one per stream"""
-        n, col = self.out_n, self._column
-        if (dst_ptrs is not None and len(dst_ptrs) != n) or (caps is not None and len(caps) != n):
-            raise ValueError("dst_ptrs and caps: one entry per stream of the last decode call each")
-        a_d = None if dst_ptrs is None else col(ctypes.c_void_p, [p or None for p in dst_ptrs], n)
-        res = (UnvarintResult * max(1, n))()
-        self._filter_call("BrotliAmdBatchUnvarintOutputs", a_d, col(ctypes.c_uint64, caps, n, (1 << 64) - 1), self._byte_column(widths, n, "widths", 0),
-                          self._byte_column(flags, n, "flags"), res)
-        return [res[i].astuple() for i in range(n)]
+        return self._counted_outputs("BrotliAmdBatchUnvarintOutputs", UnvarintResult, dst_ptrs, caps, [(widths, "widths", 0), (flags, "flags", 255)])
 
     def count_varints_outputs(self):
         """unvarint_outputs without destinations: how many varints every stream of the last decode call holds, the bytes they take and the
@@ -852,9 +841,7 @@ class Batch:
 
     def last_unvarint_ms(self, phase=None):
         """milliseconds the unvarint kernels took in the last unvarint_segments / unvarint_outputs: all launches together, or phase 1, 2 or 3"""
-        if phase is None:
-            return float(self._L.BrotliAmdBatchLastUnvarintMs(self._h))
-        return float(self._L.BrotliAmdBatchLastUnvarintPhaseMs(self._h, phase))
+        return self._last_ms("Unvarint", phase)
 
     def unrle_segments(self, src_ptrs, src_lens, dst_ptrs, caps, bits, widths, flags=None, stream=None):
         """BrotliAmdBatchUnrleSegments: the RLE / bit-packed hybrid runs in the src_lens[i] bytes at the device address src_ptrs[i], of fields of
@@ -862,15 +849,7 @@ class Batch:
         (UNRLE_WIDTH_BYTE; None: all 0); any alignment, any length; out of place; caps[i] == 0 needs no destination (dst_ptrs[i] may be None;
         dst_ptrs=None: none has one).  Two launches and a wait on `stream`.  -> [(count, consumed, runs, status, bits)]: what each segment
         held, whatever its capacity was"""
-        n, col = len(src_ptrs), self._column
-        if len(src_lens) != n or (dst_ptrs is not None and len(dst_ptrs) != n) or len(caps) != n:
-            raise ValueError("src_ptrs, src_lens, dst_ptrs and caps: one entry per segment each")
-        a_d = None if dst_ptrs is None else col(ctypes.c_void_p, [p or None for p in dst_ptrs], n)
-        res = (UnrleResult * max(1, n))()
-        self._filter_call("BrotliAmdBatchUnrleSegments", n, col(ctypes.c_void_p, src_ptrs, n), col(ctypes.c_size_t, src_lens, n), a_d,
-                          col(ctypes.c_uint64, caps, n, (1 << 64) - 1), self._byte_column(bits, n, "bits"), self._byte_column(widths, n, "widths", 0),
-                          self._byte_column(flags, n, "flags"), res, stream)
-        return [res[i].astuple() for i in range(n)]
+        return self._counted_segments("BrotliAmdBatchUnrleSegments", UnrleResult, src_ptrs, src_lens, dst_ptrs, caps, [(bits, "bits", 255), (widths, "widths", 0), (flags, "flags", 255)], stream)
 
     def unrle_outputs(self, dst_ptrs, caps, bits, widths, flags=None):
         """BrotliAmdBatchUnrleOutputs: the delivered bytes of every stream of the last decode call on this object (after decode_device: once
@@ -878,14 +857,7 @@ class Batch:
         address dst_ptrs[i], the first caps[i] of them (None or 0: the stream is skipped, and its result is zeros).  dst_ptrs=None or caps=None:
         every stream is counted and nothing is written.  Two launches on that call's stream, and a wait.
         -> [(count, consumed, runs, status, bits)], one per stream"""
-        n, col = self.out_n, self._column
-        if (dst_ptrs is not None and len(dst_ptrs) != n) or (caps is not None and len(caps) != n):
-            raise ValueError("dst_ptrs and caps: one entry per stream of the last decode call each")
-        a_d = None if dst_ptrs is None else col(ctypes.c_void_p, [p or None for p in dst_ptrs], n)
-        res = (UnrleResult * max(1, n))()
-        self._filter_call("BrotliAmdBatchUnrleOutputs", a_d, col(ctypes.c_uint64, caps, n, (1 << 64) - 1), self._byte_column(bits, n, "bits"),
-                          self._byte_column(widths, n, "widths", 0), self._byte_column(flags, n, "flags"), res)
-        return [res[i].astuple() for i in range(n)]
+        return self._counted_outputs("BrotliAmdBatchUnrleOutputs", UnrleResult, dst_ptrs, caps, [(bits, "bits", 255), (widths, "widths", 0), (flags, "flags", 255)])
 
     def count_rle_outputs(self, bits=None):
         """unrle_outputs without destinations: how many values the runs of every stream of the last decode call hold -> [(count, consumed, runs,
@@ -899,23 +871,14 @@ class Batch:
     def last_unrle_ms(self, phase=None):
         """milliseconds the unrle kernels took in the last unrle_segments / unrle_outputs: both launches together, or phase 1 (the walk) or 2
         (the expansion)"""
-        if phase is None:
-            return float(self._L.BrotliAmdBatchLastUnrleMs(self._h))
-        return float(self._L.BrotliAmdBatchLastUnrlePhaseMs(self._h, phase))
+        return self._last_ms("Unrle", phase)
 
     def undbp_segments(self, src_ptrs, src_lens, dst_ptrs, caps, widths, flags=None, stream=None):
         """BrotliAmdBatchUndbpSegments: the DELTA_BINARY_PACKED stream in the src_lens[i] bytes at the device address src_ptrs[i] becomes elements
         of widths[i] bytes (1, 2, 4, 8) at dst_ptrs[i], the first caps[i] of them; flags: None or all 0; any alignment, any length; out of place;
         caps[i] == 0 needs no destination (dst_ptrs[i] may be None; dst_ptrs=None: none has one).  Four launches and a wait on `stream`.
         -> [(count, consumed, declared, blocks, status, block_values, miniblocks)]: what each segment held, whatever its capacity was"""
-        n, col = len(src_ptrs), self._column
-        if len(src_lens) != n or (dst_ptrs is not None and len(dst_ptrs) != n) or len(caps) != n:
-            raise ValueError("src_ptrs, src_lens, dst_ptrs and caps: one entry per segment each")
-        a_d = None if dst_ptrs is None else col(ctypes.c_void_p, [p or None for p in dst_ptrs], n)
-        res = (UndbpResult * max(1, n))()
-        self._filter_call("BrotliAmdBatchUndbpSegments", n, col(ctypes.c_void_p, src_ptrs, n), col(ctypes.c_size_t, src_lens, n), a_d,
-                          col(ctypes.c_uint64, caps, n, (1 << 64) - 1), self._byte_column(widths, n, "widths", 0), self._byte_column(flags, n, "flags"), res, stream)
-        return [res[i].astuple() for i in range(n)]
+        return self._counted_segments("BrotliAmdBatchUndbpSegments", UndbpResult, src_ptrs, src_lens, dst_ptrs, caps, [(widths, "widths", 0), (flags, "flags", 255)], stream)
 
     def undbp_outputs(self, dst_ptrs, caps, widths, flags=None):
         """BrotliAmdBatchUndbpOutputs: the delivered bytes of every stream of the last decode call on this object (after decode_device: once
@@ -923,14 +886,7 @@ class Batch:
         first caps[i] of them (None or 0: the stream is skipped, and its result is zeros).  dst_ptrs=None or caps=None: every stream is counted
         and nothing is written.  Four launches on that call's stream, and a wait.
         -> [(count, consumed, declared, blocks, status, block_values, miniblocks)], one per stream"""
-        n, col = self.out_n, self._column
-        if (dst_ptrs is not None and len(dst_ptrs) != n) or (caps is not None and len(caps) != n):
-            raise ValueError("dst_ptrs and caps: one entry per stream of the last decode call each")
-        a_d = None if dst_ptrs is None else col(ctypes.c_void_p, [p or None for p in dst_ptrs], n)
-        res = (UndbpResult * max(1, n))()
-        self._filter_call("BrotliAmdBatchUndbpOutputs", a_d, col(ctypes.c_uint64, caps, n, (1 << 64) - 1), self._byte_column(widths, n, "widths", 0),
-                          self._byte_column(flags, n, "flags"), res)
-        return [res[i].astuple() for i in range(n)]
+        return self._counted_outputs("BrotliAmdBatchUndbpOutputs", UndbpResult, dst_ptrs, caps, [(widths, "widths", 0), (flags, "flags", 255)])
 
     def count_dbp_outputs(self):
         """undbp_outputs without destinations: how many values the DELTA_BINARY_PACKED stream of every stream of the last decode call holds, and
@@ -941,9 +897,7 @@ class Batch:
     def last_undbp_ms(self, phase=None):
         """milliseconds the undbp kernels took in the last undbp_segments / undbp_outputs: all launches together, or phase 1 (the walk), 2 (the
         items' sums), 3 (the carries) or 4 (the expansion)"""
-        if phase is None:
-            return float(self._L.BrotliAmdBatchLastUndbpMs(self._h))
-        return float(self._L.BrotliAmdBatchLastUndbpPhaseMs(self._h, phase))
+        return self._last_ms("Undbp", phase)
 
     def last_bitunpack_ms(self):
         """milliseconds the bit-unpack kernel took in the last bitunpack_segments / bitunpack_outputs"""

@@ -58,6 +58,6 @@ __global__ __launch_bounds__(kThreads) void brotli_amd_bitunpack_kernel(const Br
 
 extern "C" uint32_t brotli_amd_bitunpack_tile_bytes(void) { return BROTLI_AMD_BITUNPACK_TILE_BYTES; }
 
-extern "C" hipError_t brotli_amd_launch_bitunpack(const BrotliAmdUnshuffleSeg* d_segs, uint32_t n, uint64_t units, hipStream_t stream) {
-  return brotli_amd_seg_launch(brotli_amd_bitunpack_kernel, kTileUnits, d_segs, n, units, stream);
+extern "C" hipError_t brotli_amd_launch_bitunpack(const void* d_segs, uint32_t n, uint64_t units, void*, hipStream_t stream, const hipEvent_t* ev) {
+  return brotli_amd_seg_launch(brotli_amd_bitunpack_kernel, kTileUnits, d_segs, n, units, stream, ev);
 }

@@ -50,6 +50,6 @@ __global__ __launch_bounds__(kThreads) void brotli_amd_bitunshuffle_kernel(const
 
 extern "C" uint32_t brotli_amd_bitunshuffle_tile_bytes(void) { return BROTLI_AMD_BITUNSHUFFLE_TILE_BYTES; }
 
-extern "C" hipError_t brotli_amd_launch_bitunshuffle(const BrotliAmdUnshuffleSeg* d_segs, uint32_t n, uint64_t units, hipStream_t stream) {
-  return brotli_amd_seg_launch(brotli_amd_bitunshuffle_kernel, kTileUnits, d_segs, n, units, stream);
+extern "C" hipError_t brotli_amd_launch_bitunshuffle(const void* d_segs, uint32_t n, uint64_t units, void*, hipStream_t stream, const hipEvent_t* ev) {
+  return brotli_amd_seg_launch(brotli_amd_bitunshuffle_kernel, kTileUnits, d_segs, n, units, stream, ev);
 }

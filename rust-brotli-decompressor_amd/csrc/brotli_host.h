@@ -5,8 +5,9 @@
 //   brotli_stream_set.cpp  many streaming states in one launch, the ragged copy's debug hook
 //   brotli_seg_call.cpp  what the calls below share: the last decode call's outputs as segments, the segment walk's host model
 //   brotli_digest.cpp   CRC-32 / CRC-32C of segments of device memory and of the last decode call's outputs
-//   brotli_filters.cpp  the element filters -- unshuffle, undelta, bit-unshuffle, bit-unpack, unvarint, unrle -- of segments of device memory and of the last
-//                       decode call's outputs: one descriptor a filter, one call, one pair of segment builders, the host hooks
+//   brotli_filters.cpp  the element filters of segments of device memory and of the last decode call's outputs: one descriptor a filter and one call;
+//                       the plain path (unshuffle, undelta, bit-unshuffle, bit-unpack), the counted path with a result per segment (unvarint,
+//                       unrle, undbp), the host hooks
 #ifndef BROTLI_AMD_HOST_H_
 #define BROTLI_AMD_HOST_H_
 #include <hip/hip_runtime.h>
@@ -106,9 +107,10 @@ template <class T = uint8_t> using DevBuf = Buffer<T, Mem::Device>;
 template <class T = uint8_t> using PinBuf = Buffer<T, Mem::Pinned>;
 
 // What a call over a table of segments (run_seg_call) keeps with its batch object
+constexpr uint32_t kMaxSegEvents = 5;
 struct SegCall {
-  DevBuf<> d;                                                // the segment table of one call and what the call wants behind it
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // around and between its launches (made at the first call, as many as it needs)
+  DevBuf<> d;                         // the segment table of one call and what the call wants behind it
+  hipEvent_t ev[kMaxSegEvents] = {};   // around and between its launches (made at the first call, as many as it needs)
 };
 
 enum Filter : uint32_t { kUnshuffle, kUndelta, kBitUnshuffle, kBitUnpack, kUnvarint, kUnrle, kUndbp, kFilters };   // the element filters (brotli_filters.cpp)
@@ -174,13 +176,9 @@ struct BrotliAmdBatch {
   enum class Outputs : uint8_t { NoCall, Failed, None, InFlight, Waited } outputs = Outputs::NoCall;
   brotli_amd_host::SegCall digest;   // behind the table: the digests of one launch
   float digest_ms = 0.0f;
-  // the element filters (brotli_filters.cpp), by brotli_amd_host::Filter: each one's call -- behind undelta's table the summaries and carries of
-  // its tiles -- and the kernel time of its last call; undelta's three launches one by one
-  struct FilterCall { brotli_amd_host::SegCall call; float ms = 0.0f; } filter[brotli_amd_host::kFilters];
-  float undelta_phase_ms[3] = {0.0f, 0.0f, 0.0f};
-  float unvarint_phase_ms[3] = {0.0f, 0.0f, 0.0f};   // unvarint's three launches as well; behind its table the summaries, the carries and the segments' results
-  float unrle_phase_ms[2] = {0.0f, 0.0f};            // unrle's two launches; behind its table the segments' results, the items' prefix array and their checkpoints
-  float undbp_phase_ms[4] = {0.0f, 0.0f, 0.0f, 0.0f};   // undbp's four launches; behind its table the results, first values, prefix array, checkpoints, tile records and carries
+  // the element filters (brotli_filters.cpp), by brotli_amd_host::Filter: each one's call, the kernel time of its last call and, of a filter of
+  // several launches, that of each launch (phase_ms[i]: from event i to event i + 1).  What lies behind each table is its launcher's to say.
+  struct FilterCall { brotli_amd_host::SegCall call; float ms = 0.0f; float phase_ms[brotli_amd_host::kMaxSegEvents - 1u] = {}; } filter[brotli_amd_host::kFilters];
 };
 
 namespace brotli_amd_host {

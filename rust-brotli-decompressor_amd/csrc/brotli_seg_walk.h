@@ -200,16 +200,19 @@ __device__ __forceinline__ void brotli_amd_seg_dst_kernel(const Seg* __restrict_
 }
 
 // ... and its launch over `units` units (the units of all segments together: the host has the table -- a launch of a few short segments has a
-// few blocks, not a device full of blocks that find nothing to do)
+// few blocks, not a device full of blocks that find nothing to do).  The signature is every filter's launcher's: no scratch is used here, and
+// ev[0..1], where not NULL, are recorded in front of and behind the launch.
 template <class Seg>
-inline hipError_t brotli_amd_seg_launch(void (*kernel)(const Seg*, uint32_t), uint32_t tile_units, const Seg* d_segs, uint32_t n, uint64_t units,
-                                        hipStream_t stream) {
+inline hipError_t brotli_amd_seg_launch(void (*kernel)(const Seg*, uint32_t), uint32_t tile_units, const void* d_segs, uint32_t n, uint64_t units,
+                                        hipStream_t stream, const hipEvent_t* ev) {
   if (n == 0u || units == 0u) return hipSuccess;
   uint32_t grid = 0;
-  const hipError_t e = brotli_amd_seg_grid(units, tile_units, &grid);
+  hipError_t e = brotli_amd_seg_grid(units, tile_units, &grid);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(BROTLI_AMD_SEG_THREADS), 0, stream, d_segs, n);
-  return hipGetLastError();
+  if (ev && (e = hipEventRecord(ev[0], stream)) != hipSuccess) return e;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(BROTLI_AMD_SEG_THREADS), 0, stream, static_cast<const Seg*>(d_segs), n);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  return ev ? hipEventRecord(ev[1], stream) : hipSuccess;
 }
 #endif  // __HIPCC__
 

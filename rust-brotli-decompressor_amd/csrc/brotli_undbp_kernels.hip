@@ -182,9 +182,9 @@ extern "C" uint64_t brotli_amd_undbp_scratch_bytes(uint64_t units, uint32_t n) {
 
 // units: n + the items of all segments (the host has the table); d_scratch: brotli_amd_undbp_scratch_bytes of device memory, 16-byte aligned;
 // ev[0..4], where not NULL, are recorded in front of, between and behind the four launches
-extern "C" hipError_t brotli_amd_launch_undbp(const BrotliAmdUndbpSeg* d_segs, uint32_t n, uint64_t units, void* d_scratch, hipStream_t stream,
-                                              const hipEvent_t* ev) {
+extern "C" hipError_t brotli_amd_launch_undbp(const void* d_table, uint32_t n, uint64_t units, void* d_scratch, hipStream_t stream, const hipEvent_t* ev) {
   if (n == 0u) return hipSuccess;
+  const BrotliAmdUndbpSeg* d_segs = static_cast<const BrotliAmdUndbpSeg*>(d_table);
   const uint64_t items = units - n;
   uint8_t* at = static_cast<uint8_t*>(d_scratch);
   Result* results = reinterpret_cast<Result*>(at); at += pad16((uint64_t)n * sizeof(Result));

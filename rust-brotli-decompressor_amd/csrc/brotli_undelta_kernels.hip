@@ -215,9 +215,9 @@ extern "C" hipError_t brotli_amd_launch_tile_carries(const BrotliAmdUndeltaTile*
 
 // units: the units of all segments together (brotli_amd_seg_units: the host has the table); d_scratch: brotli_amd_undelta_scratch_bytes
 // of device memory, 16-byte aligned; ev[0..3], where not NULL, are recorded in front of, between and behind the three launches
-extern "C" hipError_t brotli_amd_launch_undelta(const BrotliAmdUnshuffleSeg* d_segs, uint32_t n, uint64_t units, void* d_scratch, hipStream_t stream,
-                                                const hipEvent_t* ev) {
+extern "C" hipError_t brotli_amd_launch_undelta(const void* d_table, uint32_t n, uint64_t units, void* d_scratch, hipStream_t stream, const hipEvent_t* ev) {
   if (n == 0u || units == 0u) return hipSuccess;
+  const BrotliAmdUnshuffleSeg* d_segs = static_cast<const BrotliAmdUnshuffleSeg*>(d_table);
   const uint64_t ntiles = (units + kTileUnits - 1u) / kTileUnits;
   uint32_t grid = 0;
   hipError_t e = brotli_amd_seg_grid(units, kTileUnits, &grid);

@@ -151,9 +151,9 @@ extern "C" uint64_t brotli_amd_unrle_scratch_bytes(uint64_t units, uint32_t n) {
 
 // units: n + the items of all segments (the host has the table); d_scratch: brotli_amd_unrle_scratch_bytes of device memory, 16-byte aligned;
 // ev[0..2], where not NULL, are recorded in front of, between and behind the two launches
-extern "C" hipError_t brotli_amd_launch_unrle(const BrotliAmdUnrleSeg* d_segs, uint32_t n, uint64_t units, void* d_scratch, hipStream_t stream,
-                                              const hipEvent_t* ev) {
+extern "C" hipError_t brotli_amd_launch_unrle(const void* d_table, uint32_t n, uint64_t units, void* d_scratch, hipStream_t stream, const hipEvent_t* ev) {
   if (n == 0u) return hipSuccess;
+  const BrotliAmdUnrleSeg* d_segs = static_cast<const BrotliAmdUnrleSeg*>(d_table);
   const uint64_t items = units - n;
   Result* results = static_cast<Result*>(d_scratch);
   uint64_t* pre = reinterpret_cast<uint64_t*>(results + n);

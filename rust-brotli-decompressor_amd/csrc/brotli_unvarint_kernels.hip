@@ -199,25 +199,23 @@ __global__ __launch_bounds__(kThreads) void brotli_amd_unvarint_emit_kernel(cons
 }  // namespace
 
 extern "C" uint32_t brotli_amd_unvarint_tile_bytes(void) { return BROTLI_AMD_UNVARINT_TILE_BYTES; }
-// the scratch of a launch over `units` units of n segments: the tiles' summaries, their carries, the segments' results
+// the scratch of a launch over `units` units of n segments: the segments' results first, then the tiles' summaries and their carries, which
+// start at a multiple of 16 bytes as they do where nothing lies in front of them
+static constexpr uint64_t results_bytes(uint32_t n) { return ((uint64_t)n * sizeof(BrotliAmdUnvarintResult) + 15u) & ~(uint64_t)15; }
 extern "C" uint64_t brotli_amd_unvarint_scratch_bytes(uint64_t units, uint32_t n) {
-  return ((units + kTileUnits - 1u) / kTileUnits) * (sizeof(BrotliAmdUndeltaTile) + sizeof(uint64_t)) + (uint64_t)n * sizeof(BrotliAmdUnvarintResult);
-}
-// where the results lie in it
-extern "C" uint64_t brotli_amd_unvarint_results_at(uint64_t units) {
-  return ((units + kTileUnits - 1u) / kTileUnits) * (sizeof(BrotliAmdUndeltaTile) + sizeof(uint64_t));
+  return results_bytes(n) + ((units + kTileUnits - 1u) / kTileUnits) * (sizeof(BrotliAmdUndeltaTile) + sizeof(uint64_t));
 }
 
 // units: the units of all segments' SOURCES together (brotli_amd_seg_units: the host has the table); d_scratch: brotli_amd_unvarint_scratch_bytes
 // of device memory, 16-byte aligned -- the results in it are zeroed here, on `stream`; ev[0..3], where not NULL, are recorded in front of, between
 // and behind the three launches
-extern "C" hipError_t brotli_amd_launch_unvarint(const BrotliAmdUnvarintSeg* d_segs, uint32_t n, uint64_t units, void* d_scratch, hipStream_t stream,
-                                                 const hipEvent_t* ev) {
+extern "C" hipError_t brotli_amd_launch_unvarint(const void* d_table, uint32_t n, uint64_t units, void* d_scratch, hipStream_t stream, const hipEvent_t* ev) {
   if (n == 0u) return hipSuccess;
+  const BrotliAmdUnvarintSeg* d_segs = static_cast<const BrotliAmdUnvarintSeg*>(d_table);
   const uint64_t ntiles = (units + kTileUnits - 1u) / kTileUnits;
-  BrotliAmdUndeltaTile* tiles = static_cast<BrotliAmdUndeltaTile*>(d_scratch);
+  BrotliAmdUnvarintResult* results = static_cast<BrotliAmdUnvarintResult*>(d_scratch);
+  BrotliAmdUndeltaTile* tiles = reinterpret_cast<BrotliAmdUndeltaTile*>(static_cast<uint8_t*>(d_scratch) + results_bytes(n));
   uint64_t* carries = reinterpret_cast<uint64_t*>(tiles + ntiles);
-  BrotliAmdUnvarintResult* results = reinterpret_cast<BrotliAmdUnvarintResult*>(carries + ntiles);
   hipError_t e = hipMemsetAsync(results, 0, (size_t)n * sizeof(BrotliAmdUnvarintResult), stream);
   if (e != hipSuccess || units == 0u) return e;
   uint32_t grid = 0;

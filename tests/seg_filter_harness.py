@@ -1,6 +1,8 @@
-"""What the GPU tests of the element filters (test_gpu_unshuffle.py, test_gpu_undelta.py, test_gpu_bitunshuffle.py, test_gpu_bitunpack.py) share:
-sources from one seeded read-only buffer, destinations from one buffer prefilled with a sentinel pattern, the WHOLE destination buffer compared
-with the expectation, and streams that carry an array to a decode call.  Each test file has its own fixtures: seeds and sizes differ."""
+"""What the GPU tests of the element filters (test_gpu_unshuffle.py, test_gpu_undelta.py, test_gpu_bitunshuffle.py, test_gpu_bitunpack.py,
+test_gpu_unvarint.py, test_gpu_unrle.py, test_gpu_undbp.py) share: sources from one seeded read-only buffer, destinations from one buffer prefilled
+with a sentinel pattern, the WHOLE destination buffer compared with the expectation, and streams that carry an array to a decode call; for the
+three filters with a capacity and a result per segment, the call that is compared with its reference as well (counted_call).  Each test file has
+its own fixtures: seeds and sizes differ."""
 import importlib.util
 import os
 import sys
@@ -52,6 +54,46 @@ def compare(dev, want, segs=None, names="(src, dst, len, w)", dst_len=lambda s: 
         inside = [s for s in (segs or []) if s[1] <= at < s[1] + dst_len(s)]
         raise AssertionError("byte %d of the destination is %#x, not %#x; segment %s: %r" %
                              (at, got[at], want[at], names, inside[:1] or "none: outside every segment"))
+
+
+def upload(src):
+    """bytes on the device, with 16 bytes of room behind them"""
+    import torch
+    t = torch.frombuffer(bytearray(src) + bytearray(16), dtype=torch.uint8).cuda()
+    torch.cuda.synchronize()
+    assert t.data_ptr() % 16 == 0
+    return t
+
+
+def pack(datas, start=3, gap=lambda i: i % 3):
+    """segments' bytes one after the other in one source -> (source, [source offset])"""
+    src, offs = bytearray(b"\xee" * start), []
+    for i, d in enumerate(datas):
+        src += b"\xee" * gap(i)
+        offs.append(len(src))
+        src += d
+    return bytes(src), offs
+
+
+def counted_call(call, elements_bytes, layout, dev, src, d_src, sentinel, segs, size):
+    """One call of a filter with a capacity and a result per segment into a fresh destination of `size` bytes, the results compared item by item
+    and the whole destination compared.  segs: [(source offset, source length, destination offset, cap, *columns)], the columns being what
+    call(src_ptrs, src_lens, dst_ptrs, caps, *columns) -- a Batch's *_segments -- takes behind the capacities, and what the reference's
+    elements_bytes(bytes, *columns, cap) -> (the elements' bytes, the result) takes between the bytes and the capacity.  layout: the names of
+    what a segment's tuple holds, the width's being "w"; d_src: src on the device.  -> the results"""
+    want, results = sentinel[:size].copy(), []
+    for s, l, d, cap, *columns in segs:
+        elems, res = elements_bytes(src[s:s + l], *columns, cap)
+        assert d + len(elems) <= size
+        want[d:d + len(elems)] = np.frombuffer(elems, dtype=np.uint8)
+        results.append(res)
+    fresh_dst(dev, size)
+    sp, dp = d_src.data_ptr(), dev["dst"].data_ptr()
+    got = call([sp + s[0] for s in segs], [s[1] for s in segs], [dp + s[2] for s in segs], [s[3] for s in segs],
+               *[[s[k] for s in segs] for k in range(4, len(layout))])
+    assert got == results, [(i, a, b) for i, (a, b) in enumerate(zip(got, results)) if a != b][:3]
+    compare(dev, want, segs, names="(%s)" % ", ".join(layout), dst_len=lambda s: s[3] * s[layout.index("w")])
+    return got
 
 
 def next_at(at, align, mod=16):

@@ -11,7 +11,7 @@ import pytest
 import dbp_ref as ref
 import seg_filter_harness as H
 from conftest import ROOT
-from seg_filter_harness import fresh_dst as _fresh_dst, stream as _stream, slots as _slots
+from seg_filter_harness import fresh_dst as _fresh_dst, pack as _pack, stream as _stream, slots as _slots, upload as _upload
 
 pytestmark = pytest.mark.gpu
 FLAGS = 1        # BROTLI_AMD_BATCH_LARGE_WINDOW
@@ -42,51 +42,12 @@ def batch(pkg):
     b.close()
 
 
-def _compare(dev, want, segs=None):
-    H.compare(dev, want, segs, names="(src, len, dst, cap, w)", dst_len=lambda s: s[3] * s[4])
-
-
-def _expect(src, sentinel, segs, size):
-    """-> (the destination's bytes behind the call, the results)"""
-    want, results = sentinel[:size].copy(), []
-    for s, l, d, cap, w in segs:
-        elems, res = ref.elements_bytes(src[s:s + l], w, cap)
-        assert d + len(elems) <= size
-        want[d:d + len(elems)] = np.frombuffer(elems, dtype=np.uint8)
-        results.append(res)
-    return want, results
-
-
-def _upload(src):
-    import torch
-    t = torch.frombuffer(bytearray(src) + bytearray(16), dtype=torch.uint8).cuda()
-    torch.cuda.synchronize()
-    assert t.data_ptr() % 16 == 0
-    return t
-
-
 def _undbp(batch, dev, src, sentinel, segs, size, d_src=None):
     """segs: [(source offset, source length, destination offset, cap, width)] -> one call into a fresh destination of `size` bytes, the whole
     destination and all results compared; d_src: the device's copy of src where it is not the module's source"""
     src = bytes(src)
-    want, results = _expect(src, sentinel, segs, size)
-    _fresh_dst(dev, size)
-    d_src = _upload(src) if d_src is None else d_src
-    sp, dp = d_src.data_ptr(), dev["dst"].data_ptr()
-    got = batch.undbp_segments([sp + s[0] for s in segs], [s[1] for s in segs], [dp + s[2] for s in segs], [s[3] for s in segs], [s[4] for s in segs])
-    assert got == results, [(i, a, b) for i, (a, b) in enumerate(zip(got, results)) if a != b][:3]
-    _compare(dev, want, segs)
-    return got
-
-
-def _pack(datas, start=3, gap=lambda i: i % 3):
-    """segments' bytes one after the other in one source -> (source, [source offset])"""
-    src, offs = bytearray(b"\xee" * start), []
-    for i, d in enumerate(datas):
-        src += b"\xee" * gap(i)
-        offs.append(len(src))
-        src += d
-    return bytes(src), offs
+    return H.counted_call(batch.undbp_segments, ref.elements_bytes, ("src", "len", "dst", "cap", "w"), dev, src,
+                          _upload(src) if d_src is None else d_src, sentinel, segs, size)
 
 
 def _lay(datas, offs, widths, start=2, caps=None):

@@ -52,32 +52,11 @@ def batch(pkg):
     b.close()
 
 
-def _compare(dev, want, segs=None):
-    H.compare(dev, want, segs, names="(src, len, dst, cap, w, flags)", dst_len=lambda s: s[3] * s[4])
-
-
-def _expect(src, sentinel, segs, size):
-    """-> (the destination's bytes behind the call, the results)"""
-    want, results = sentinel[:size].copy(), []
-    for s, l, d, cap, w, f in segs:
-        elems, res = ref.elements_bytes(src[s:s + l], w, f, cap)
-        assert d + len(elems) <= size
-        want[d:d + len(elems)] = np.frombuffer(elems, dtype=np.uint8)
-        results.append(res)
-    return want, results
-
-
 def _unvarint(batch, dev, src, sentinel, segs, size, d_src=None):
     """segs: [(source offset, source length, destination offset, cap, width, flags)] -> one call into a fresh destination of `size` bytes, the
     whole destination and all results compared; d_src: the device's copy of src where it is not the module's source"""
-    want, results = _expect(src, sentinel, segs, size)
-    _fresh_dst(dev, size)
-    sp, dp = (dev["src"] if d_src is None else d_src).data_ptr(), dev["dst"].data_ptr()
-    got = batch.unvarint_segments([sp + s[0] for s in segs], [s[1] for s in segs], [dp + s[2] for s in segs], [s[3] for s in segs], [s[4] for s in segs],
-                                  [s[5] for s in segs])
-    assert got == results, [(i, a, b) for i, (a, b) in enumerate(zip(got, results)) if a != b][:3]
-    _compare(dev, want, segs)
-    return got
+    return H.counted_call(batch.unvarint_segments, ref.elements_bytes, ("src", "len", "dst", "cap", "w", "flags"), dev, src,
+                          dev["src"] if d_src is None else d_src, sentinel, segs, size)
 
 
 def test_three_thousand_short_segments_and_the_host_hook(pkg, batch, dev, source, sentinel):
