@@ -629,8 +629,8 @@ BROTLI_DEC_API int BrotliAmdDebugUnvarintHost(uint32_t n, const uint8_t* src, si
  * (csrc/brotli_unrle.h, csrc/brotli_unrle_kernels.hip).
  *
  * OUT OF SCOPE: a speculative parallel walk of one long segment; page framing -- thrift headers, and the 4-byte length in front of v1 levels,
- * where the caller passes src + 4 --; the dictionary gather; ORC's and PackBits' run formats; MSB-first fields; sign
- * extension. */
+ * where the caller passes src + 4 --; ORC's and PackBits' run formats; MSB-first fields; sign extension.  The dictionary gather is the
+ * undict calls' below: runs in, values out. */
 #define BROTLI_AMD_UNRLE_WIDTH_BYTE 1u
 
 #define BROTLI_AMD_UNRLE_OK 0u
@@ -819,6 +819,106 @@ BROTLI_DEC_API int BrotliAmdDebugUndbpHost(uint32_t n, const uint8_t* src, size_
                                           const uint64_t* src_lens, const uint64_t* dst_offs, const uint64_t* caps, const uint8_t* widths,
                                           const uint8_t* flags /* or NULL */, uint32_t src_skew, uint32_t dst_skew, uint32_t item_deltas,
                                           uint32_t order_seed, BrotliAmdUndbpResult* results);
+
+/* ---- Undict on the device: dictionary-index runs of outputs back into VALUES ----
+ *
+ * Writers dictionary-encode almost every column by default (Parquet's RLE_DICTIONARY): a column chunk is one dictionary page -- the distinct
+ * values, PLAIN, D entries of w bytes -- and data pages whose body is a width byte k and then the RLE / bit-packed hybrid of k-bit INDICES
+ * into that dictionary.  The unrle calls above turn such a body into indices; these calls turn it into the values themselves, in one pass:
+ * the indices never reach memory, every one of them is checked against D before it is used as an address, and every segment's result says
+ * how many were out of range and where the first one was.
+ *
+ * THE SEGMENT AND ITS PARAMETERS.  A segment is the bytes src[0, len), read by unrle's grammar EXACTLY: headers, the two payload kinds,
+ * k == 0, the stops, and count, consumed, runs, status and bits of the result.  It has a field width `bits` of 0 .. 32 (or
+ * BROTLI_AMD_UNDICT_WIDTH_BYTE: the segment's first byte is k, unrle's meaning), an element width w in {1, 2, 4, 8}, a capacity cap in
+ * elements, a destination dst, and a DICTIONARY: dict, device memory of any alignment, and dict_entries = D.  The index width is NOT bound by
+ * w: the only bound is k <= 32, for the argument and for the width byte alike -- a uint8 dictionary addressed by 12-bit fields is legal.
+ *
+ * VALUE.  Element i, i < min(count, cap), is the w bytes at dict + idx_i w, copied as they are, where idx_i < D.  Where idx_i >= D the element
+ * is 0, nothing is read through that index, and the element is counted as bad.  An RLE run's value is not masked to k bits (unrle's rule), so
+ * it may be out of range like any other index.  With D == 0 every element is bad and dict is not looked at.
+ *
+ * RESULT.  BrotliAmdUndictResult, 48 bytes: unrle's five fields in unrle's order and meaning -- independent of cap and of how the work was
+ * shared out --, then bad, the DELIVERED elements whose index was >= D, and first_bad, the smallest such element index (UINT64_MAX: none).
+ * bad and first_bad are about delivered elements only: they depend on cap, and a call that only counts gives 0 and UINT64_MAX; they do not
+ * depend on how the work was shared out.  A skipped stream's result is zeros, with first_bad UINT64_MAX.
+ *
+ * LOADS AND STORES.  No byte outside [dst, dst + min(count, cap) w) is written.  Nothing outside the 16-byte-aligned span around
+ * [src, src + len) is read, and nothing outside the 16-byte-aligned span around [dict, dict + D w): an entry is one load of w bytes where
+ * dict is a multiple of w, and single bytes elsewhere.  OUT OF PLACE: no destination overlaps a source, a dictionary or another destination.
+ * This is stated, not checked.
+ *
+ * Examples (k, bytes, dictionary): 3, 03 88 C6 FA over eight uint16 entries: the eight entries in order;  3, 10 05 with D = 5: 8 zeros,
+ * bad 8, first_bad 0;  the same with D = 6: 8 x entry 5, bad 0;  0, 07: 24 x entry 0.
+ *
+ * REFUSED ON THE HOST, in front of everything that touches the device, with a text that names the segment: a width outside {1, 2, 4, 8};
+ * unknown flag bits; bits > 32 without the width-byte flag; cap > 2^56; a NULL destination with cap != 0; a NULL dict with dict_entries != 0
+ * and cap != 0; dict_entries > 2^56.
+ *
+ * A call is two launches in stream order, and no block ever waits for another.  1. THE WALK: unrle's, as it is.  2. THE EXPANSION WITH THE
+ * LOOKUP, one wave an item over the items of all segments: a lane forms the indices of a group of its 16 neighbouring elements, issues their dictionary
+ * loads together -- inside an RLE run one lookup serves every element of the run that the lane holds --, and puts the aligned 16-byte words
+ * together.  The dictionary is read through the caches.  Bad indices are summed up inside the wave; an item that has some adds them to its
+ * segment's result with one atomic add and one atomic minimum (csrc/brotli_undict.h, csrc/brotli_undict_kernels.hip).
+ *
+ * OUT OF SCOPE: BYTE_ARRAY, FIXED_LEN_BYTE_ARRAY and INT96 dictionaries (entries of 12, 16 or variable bytes); definition levels and the
+ * spreading of values over nulls; page framing; plain index arrays (a framework's gather does those); a parallel walk of one long segment. */
+#define BROTLI_AMD_UNDICT_WIDTH_BYTE 1u          /* BROTLI_AMD_UNRLE_WIDTH_BYTE's meaning */
+#define BROTLI_AMD_UNDICT_NO_STREAM 0xFFFFFFFFu  /* dict_streams[i]: the dictionary is d_dicts[i], not a stream of the decode call */
+
+typedef struct BrotliAmdUndictResult {
+  uint64_t count;      /* values in all runs, whatever cap was */
+  uint64_t consumed;   /* unrle's table */
+  uint64_t runs;       /* runs that gave at least one value */
+  uint32_t status;     /* BROTLI_AMD_UNRLE_* */
+  uint32_t bits;       /* the k that was used */
+  uint64_t bad;        /* delivered elements whose index was >= D */
+  uint64_t first_bad;  /* the smallest such element index; UINT64_MAX: none */
+} BrotliAmdUndictResult;
+
+/* n segments in DEVICE memory -- the runs in the src_lens[i] bytes at d_src[i], of fields of bits[i] bits, index the dict_entries[i] entries of
+ * widths[i] bytes at d_dicts[i], and the first caps[i] values go to d_dst[i], by flags[i] (flags == NULL: all 0); results[i] says what
+ * segment i held; any alignment, any length, 0 included; n is not bound by the batch object's max_streams --: the launches run on hip_stream,
+ * and the call waits on that stream.  caps[i] == 0 only counts: d_dst[i], d_dicts[i] and dict_entries[i] are not looked at but for the
+ * refusals above, and d_dst, d_dicts and dict_entries themselves may be NULL where every capacity is 0.  n == 0 returns 0.  A negative value,
+ * and a BrotliAmdLastError text that names the segment and what was wrong, for a NULL batch, a NULL array (but flags, and the three just
+ * named) with n != 0, and everything in the list above: all of these are checked on the host in front of everything else, so nothing is
+ * launched and no byte is written. */
+BROTLI_DEC_API int BrotliAmdBatchUndictSegments(BrotliAmdBatch* batch, uint32_t n, const void* const* d_src, const size_t* src_lens, void* const* d_dst,
+                                               const uint64_t* caps, const uint8_t* bits, const uint8_t* widths,
+                                               const uint8_t* flags /* n entries, or NULL: all 0 */, const void* const* d_dicts,
+                                               const uint64_t* dict_entries, BrotliAmdUndictResult* results, void* hip_stream);
+
+/* The same for the DELIVERED bytes of every stream of the last decode call on the object, by BrotliAmdBatchUnrleOutputs' rules for the three
+ * kinds of decode call, for skipped streams (d_dst[i] == NULL: none of the stream's parameters are looked at) and for counting (d_dst == NULL
+ * or caps == NULL).  dict_streams[i] below the call's stream count names the stream OF THE SAME DECODE CALL whose delivered bytes are stream
+ * i's dictionary -- the Brotli-compressed dictionary page in the same batch --, with D = floor(decoded_size / widths[i]); such a stream is
+ * normally skipped as a data stream itself.  BROTLI_AMD_UNDICT_NO_STREAM, or dict_streams == NULL, takes d_dicts[i] and dict_entries[i]: a
+ * dictionary that an earlier call decoded (d_dicts and dict_entries may be NULL where no stream that writes takes them).  A stream that names
+ * itself, and an index at or above the stream count that is not BROTLI_AMD_UNDICT_NO_STREAM, are refused.  A negative value, and a
+ * BrotliAmdLastError text, for a NULL batch, bits, widths or results, a refusal (nothing is launched), an object without a decode call, a last
+ * decode call that failed behind its argument checks (one of no streams returns 0), and a launch that BrotliAmdBatchWait has not been called
+ * for. */
+BROTLI_DEC_API int BrotliAmdBatchUndictOutputs(BrotliAmdBatch* batch, void* const* d_dst /* or NULL */, const uint64_t* caps /* or NULL */,
+                                              const uint8_t* bits, const uint8_t* widths, const uint8_t* flags /* or NULL */,
+                                              const uint32_t* dict_streams /* or NULL */, const void* const* d_dicts /* or NULL */,
+                                              const uint64_t* dict_entries /* or NULL */, BrotliAmdUndictResult* results);
+
+/* Milliseconds the undict kernels took in the last of the two calls above (HIP events around its launches together), */
+BROTLI_DEC_API float BrotliAmdBatchLastUndictMs(BrotliAmdBatch* batch);
+/* and those of phase 1 (the walk) or 2 (the expansion with the lookup) alone; another phase: 0. */
+BROTLI_DEC_API float BrotliAmdBatchLastUndictPhaseMs(BrotliAmdBatch* batch, uint32_t phase);
+
+/* Test hook (no device needed): both phases by the functions of csrc/brotli_unrle.h and csrc/brotli_undict.h on the host.  It has
+ * BrotliAmdDebugUnrleHost's shape -- and its item size, BrotliAmdDebugUnrleItemElems() -- plus one dictionary buffer dict[0, dict_size), placed
+ * at dict_skew (0..15) past a 16-byte boundary in a room of its own: segment i's dictionary is dict_entries[i] entries of widths[i] bytes at
+ * dict_offs[i].  The items are taken in an order shuffled by order_seed (bad and first_bad may not depend on it).  0, -1 and -2 as there; -1
+ * also for a dictionary outside its buffer. */
+BROTLI_DEC_API int BrotliAmdDebugUndictHost(uint32_t n, const uint8_t* src, size_t src_size, uint8_t* dst, size_t dst_size, const uint8_t* dict,
+                                           size_t dict_size, const uint64_t* src_offs, const uint64_t* src_lens, const uint64_t* dst_offs,
+                                           const uint64_t* caps, const uint64_t* dict_offs, const uint64_t* dict_entries, const uint8_t* bits,
+                                           const uint8_t* widths, const uint8_t* flags /* or NULL */, uint32_t src_skew, uint32_t dst_skew,
+                                           uint32_t dict_skew, uint32_t item_elems, uint32_t order_seed, BrotliAmdUndictResult* results);
 
 /* Milliseconds the last launch spent in the decode kernel (HIP events on the launch stream). */
 BROTLI_DEC_API float BrotliAmdBatchLastKernelMs(BrotliAmdBatch* batch);

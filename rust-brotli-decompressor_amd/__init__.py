@@ -52,6 +52,8 @@ BATCH_H_SYMBOLS = [
     "BrotliAmdDebugUnrleItemElems", "BrotliAmdDebugUnrleWalkChunk", "BrotliAmdDebugUnrleHost",
     "BrotliAmdBatchUndbpSegments", "BrotliAmdBatchUndbpOutputs", "BrotliAmdBatchLastUndbpMs", "BrotliAmdBatchLastUndbpPhaseMs",
     "BrotliAmdDebugUndbpItemDeltas", "BrotliAmdDebugUndbpWalkChunk", "BrotliAmdDebugUndbpHost",
+    "BrotliAmdBatchUndictSegments", "BrotliAmdBatchUndictOutputs", "BrotliAmdBatchLastUndictMs", "BrotliAmdBatchLastUndictPhaseMs",
+    "BrotliAmdDebugUndictHost",
 ]
 
 
@@ -106,6 +108,19 @@ class UndbpResult(ctypes.Structure):  # BrotliAmdUndbpResult: what a segment of 
 
     def astuple(self):
         return (self.count, self.consumed, self.declared, self.blocks, self.status, self.block_values, self.miniblocks)
+
+
+UNDICT_WIDTH_BYTE = 1  # BROTLI_AMD_UNDICT_WIDTH_BYTE: the segment's first byte is the field width (UNRLE_WIDTH_BYTE's meaning)
+UNDICT_NO_STREAM = 0xFFFFFFFF  # BROTLI_AMD_UNDICT_NO_STREAM: a stream's dictionary is a pointer of the caller's, not a stream of the decode call
+UNDICT_NONE = (1 << 64) - 1  # UndictResult.first_bad where no element was bad
+
+
+class UndictResult(ctypes.Structure):  # BrotliAmdUndictResult: what a segment of dictionary-index runs held, and its indices outside the dictionary (batch.h)
+    _fields_ = [("count", ctypes.c_uint64), ("consumed", ctypes.c_uint64), ("runs", ctypes.c_uint64), ("status", ctypes.c_uint32), ("bits", ctypes.c_uint32),
+                ("bad", ctypes.c_uint64), ("first_bad", ctypes.c_uint64)]
+
+    def astuple(self):
+        return (self.count, self.consumed, self.runs, self.status, self.bits, self.bad, self.first_bad)
 
 
 def build(force=False):
@@ -225,7 +240,11 @@ def load_library():
             {"BrotliAmdBatchUndbpSegments": (None, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]), "BrotliAmdBatchUndbpOutputs": (None, [vp, vp, vp, vp, vp, vp]),
              "BrotliAmdBatchLastUndbpMs": (f32, [vp]), "BrotliAmdBatchLastUndbpPhaseMs": (f32, [vp, u32]), "BrotliAmdDebugUndbpItemDeltas": (u32, None),
              "BrotliAmdDebugUndbpWalkChunk": (u32, None),
-             "BrotliAmdDebugUndbpHost": (None, [u32, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, vp])}):
+             "BrotliAmdDebugUndbpHost": (None, [u32, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, vp])},
+            {"BrotliAmdBatchUndictSegments": (None, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+             "BrotliAmdBatchUndictOutputs": (None, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+             "BrotliAmdBatchLastUndictMs": (f32, [vp]), "BrotliAmdBatchLastUndictPhaseMs": (f32, [vp, u32]),
+             "BrotliAmdDebugUndictHost": (None, [u32, vp, sz, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, vp])}):
         if hasattr(L, next(iter(protos))):
             for name, (restype, argtypes) in protos.items():
                 if restype is not None:
@@ -422,6 +441,30 @@ def undbp_host(src: bytes, segs, dst_size, src_skew=0, dst_skew=0, item_deltas=0
     -> (the destination's bytes, [(count, consumed, declared, blocks, status, block_values, miniblocks)])"""
     segs = [tuple(s) if len(s) > 5 else tuple(s) + (0,) for s in segs]
     return _counted_host("BrotliAmdDebugUndbpHost", UndbpResult, src, segs, dst_size, [(4, 0), (5, 255)], src_skew, dst_skew, item_deltas, order_seed, fill)
+
+
+def undict_host(src: bytes, dictionary: bytes, segs, dst_size, src_skew=0, dst_skew=0, dict_skew=0, item_elems=0, order_seed=0, fill=0):
+    """BrotliAmdDebugUndictHost: the dictionary-index runs in `src` back into the values they name in `dictionary`, by unrle's walk and the item
+    and lookup functions of csrc/brotli_undict.h on the host (no device needed).  segs: [(source offset, source length, destination offset,
+    capacity in elements, bits, width, flags, dictionary offset, dictionary entries)]; the destination has dst_size bytes, all `fill` in front
+    of the call (or, where `fill` is bytes of that size, those); the three buffers are placed at their skews past a 16-byte boundary;
+    item_elems: the elements of an item (0: the device's, unrle_item_elems()); order_seed != 0 shuffles the order in which the items are taken.
+    -> (the destination's bytes, [(count, consumed, runs, status, bits, bad, first_bad)])"""
+    L = load_library()
+    src, dictionary, n = bytes(src), bytes(dictionary), len(segs)
+    before = bytes(fill) if isinstance(fill, (bytes, bytearray)) else bytes([fill]) * dst_size
+    if len(before) != dst_size:
+        raise ValueError("fill: %d bytes for a destination of %d" % (len(before), dst_size))
+    s_buf = ctypes.create_string_buffer(src, max(1, len(src)))
+    d_buf = ctypes.create_string_buffer(before, max(1, dst_size))
+    t_buf = ctypes.create_string_buffer(dictionary, max(1, len(dictionary)))
+    u64s = [(ctypes.c_uint64 * max(1, n))(*[s[k] if 0 <= s[k] < (1 << 64) else (1 << 64) - 1 for s in segs]) for k in (0, 1, 2, 3, 7, 8)]
+    u8s = [(ctypes.c_uint8 * max(1, n))(*[s[k] if 0 <= s[k] <= 255 else bad for s in segs]) for k, bad in [(4, 255), (5, 0), (6, 255)]]
+    res = (UndictResult * max(1, n))()
+    if L.BrotliAmdDebugUndictHost(n, ctypes.addressof(s_buf), len(src), ctypes.addressof(d_buf), dst_size, ctypes.addressof(t_buf), len(dictionary),
+                                  *u64s, *u8s, src_skew, dst_skew, dict_skew, item_elems, order_seed, res) != 0:
+        raise RuntimeError("BrotliAmdDebugUndictHost failed: " + last_error())
+    return d_buf.raw[:dst_size], [res[i].astuple() for i in range(n)]
 
 
 def undbp_item_deltas():
@@ -718,26 +761,40 @@ class Batch:
         self._filter_call(name, col(ctypes.c_void_p, [p or None for p in dst_ptrs], n), col(ctypes.c_uint8, widths, n, 0),
                           *[self._block_column(b, n) for b in blocks])
 
-    def _counted_segments(self, name, Result, src_ptrs, src_lens, dst_ptrs, caps, columns, stream):
+    def _counted_segments(self, name, Result, src_ptrs, src_lens, dst_ptrs, caps, columns, stream, more=()):
         """BrotliAmdBatch<name>Segments of a filter with a capacity and a result per segment.  columns: its byte columns in the call's order, each
-        (values, its name, what stands in for a value no byte holds).  -> [a result's tuple per segment]"""
+        (values, its name, what stands in for a value no byte holds); more: the arrays it has behind them (undict's dictionaries), each
+        (C type, values or None, its name).  -> [a result's tuple per segment]"""
         n, col = len(src_ptrs), self._column
         if len(src_lens) != n or (dst_ptrs is not None and len(dst_ptrs) != n) or len(caps) != n:
             raise ValueError("src_ptrs, src_lens, dst_ptrs and caps: one entry per segment each")
         a_d = None if dst_ptrs is None else col(ctypes.c_void_p, [p or None for p in dst_ptrs], n)
         res = (Result * max(1, n))()
         self._filter_call(name, n, col(ctypes.c_void_p, src_ptrs, n), col(ctypes.c_size_t, src_lens, n), a_d, col(ctypes.c_uint64, caps, n, (1 << 64) - 1),
-                          *[self._byte_column(v, n, what, bad) for v, what, bad in columns], res, stream)
+                          *[self._byte_column(v, n, what, bad) for v, what, bad in columns], *self._more_columns(more, n), res, stream)
         return [res[i].astuple() for i in range(n)]
 
-    def _counted_outputs(self, name, Result, dst_ptrs, caps, columns):
+    def _more_columns(self, more, n):
+        """the arrays of a counted call behind its byte columns: None stays NULL, a pointer that is None or 0 is NULL, a number its type cannot hold
+        becomes the type's largest -- which the call refuses or takes for what it is"""
+        out = []
+        for ctype, values, what in more:
+            if values is not None and len(values) != n:
+                raise ValueError("%s: one entry per segment or stream" % what)
+            if values is not None and ctype is ctypes.c_void_p:
+                values = [p or None for p in values]
+            out.append(self._column(ctype, values, n, None if ctype is ctypes.c_void_p else (1 << 8 * ctypes.sizeof(ctype)) - 1))
+        return out
+
+    def _counted_outputs(self, name, Result, dst_ptrs, caps, columns, more=()):
         """BrotliAmdBatch<name>Outputs of such a filter over the streams of the last decode call -> [a result's tuple per stream]"""
         n, col = self.out_n, self._column
         if (dst_ptrs is not None and len(dst_ptrs) != n) or (caps is not None and len(caps) != n):
             raise ValueError("dst_ptrs and caps: one entry per stream of the last decode call each")
         a_d = None if dst_ptrs is None else col(ctypes.c_void_p, [p or None for p in dst_ptrs], n)
         res = (Result * max(1, n))()
-        self._filter_call(name, a_d, col(ctypes.c_uint64, caps, n, (1 << 64) - 1), *[self._byte_column(v, n, what, bad) for v, what, bad in columns], res)
+        self._filter_call(name, a_d, col(ctypes.c_uint64, caps, n, (1 << 64) - 1), *[self._byte_column(v, n, what, bad) for v, what, bad in columns],
+                          *self._more_columns(more, n), res)
         return [res[i].astuple() for i in range(n)]
 
     def _last_ms(self, stem, phase):
@@ -872,6 +929,31 @@ class Batch:
         """milliseconds the unrle kernels took in the last unrle_segments / unrle_outputs: both launches together, or phase 1 (the walk) or 2
         (the expansion)"""
         return self._last_ms("Unrle", phase)
+
+    def undict_segments(self, src_ptrs, src_lens, dst_ptrs, caps, bits, widths, flags, dict_ptrs, dict_entries, stream=None):
+        """BrotliAmdBatchUndictSegments: the RLE / bit-packed hybrid runs in the src_lens[i] bytes at the device address src_ptrs[i], of fields of
+        bits[i] bits (0 .. 32, whatever the width), are INDICES into the dict_entries[i] entries of widths[i] bytes at the device address
+        dict_ptrs[i]; the first caps[i] of the entries they name go to dst_ptrs[i], by flags[i] (UNDICT_WIDTH_BYTE; None: all 0); any alignment,
+        any length; out of place.  An index at or above dict_entries[i] gives 0 and is counted.  caps[i] == 0 only counts (dst_ptrs, dict_ptrs
+        and dict_entries may then be None).  Two launches and a wait on `stream`.  -> [(count, consumed, runs, status, bits, bad, first_bad)]"""
+        return self._counted_segments("BrotliAmdBatchUndictSegments", UndictResult, src_ptrs, src_lens, dst_ptrs, caps,
+                                      [(bits, "bits", 255), (widths, "widths", 0), (flags, "flags", 255)], stream,
+                                      [(ctypes.c_void_p, dict_ptrs, "dict_ptrs"), (ctypes.c_uint64, dict_entries, "dict_entries")])
+
+    def undict_outputs(self, dst_ptrs, caps, bits, widths, flags=None, dict_streams=None, dict_ptrs=None, dict_entries=None):
+        """BrotliAmdBatchUndictOutputs: the delivered bytes of every stream of the last decode call on this object (after decode_device: once
+        wait() has returned), taken as dictionary-index runs, become the values they name at dst_ptrs[i] (None or 0: the stream is skipped).
+        dict_streams[i]: the stream of the same decode call whose delivered bytes are stream i's dictionary, or UNDICT_NO_STREAM (and
+        dict_streams None) for the dictionary at the device address dict_ptrs[i] with dict_entries[i] entries.  dst_ptrs None or caps None:
+        every stream is counted and nothing is written.  -> [(count, consumed, runs, status, bits, bad, first_bad)]"""
+        return self._counted_outputs("BrotliAmdBatchUndictOutputs", UndictResult, dst_ptrs, caps, [(bits, "bits", 255), (widths, "widths", 0), (flags, "flags", 255)],
+                                     [(ctypes.c_uint32, dict_streams, "dict_streams"), (ctypes.c_void_p, dict_ptrs, "dict_ptrs"),
+                                      (ctypes.c_uint64, dict_entries, "dict_entries")])
+
+    def last_undict_ms(self, phase=None):
+        """milliseconds the undict kernels took in the last undict_segments / undict_outputs: both launches together, or phase 1 (the walk) or 2
+        (the expansion with the lookup)"""
+        return self._last_ms("Undict", phase)
 
     def undbp_segments(self, src_ptrs, src_lens, dst_ptrs, caps, widths, flags=None, stream=None):
         """BrotliAmdBatchUndbpSegments: the DELTA_BINARY_PACKED stream in the src_lens[i] bytes at the device address src_ptrs[i] becomes elements

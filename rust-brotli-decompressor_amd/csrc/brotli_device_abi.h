@@ -195,6 +195,27 @@ typedef struct BrotliAmdUndbpSeg {
 } BrotliAmdUndbpSeg;
 #define BROTLI_AMD_UNDBP_ITEM_DELTAS 2048u  // deltas of one item: 64 groups of 32 fields, a group a lane
 
+// One segment of an undict call (csrc/brotli_undict_kernels.hip, csrc/brotli_undict.h): an unrle segment whose values are INDICES into the
+// dict_entries entries of `width` bytes at dict, device memory of any alignment; the first `cap` of the entries they name become the elements
+// at dst, and an index at or above dict_entries gives 0 and is counted.  `bits` is bound by 32 alone.  Items, first_item and the checkpoints
+// are unrle's; every segment has a result (BrotliAmdUndictResult, include/brotli/batch.h) behind the table, whose bad and first_bad the items
+// add to.  No destination range overlaps a source range, a dictionary or another destination range.  Nothing outside
+// [dst, dst + min(count, cap) width) is written; nothing outside the 16-byte-aligned spans around [src, src + len) and
+// [dict, dict + dict_entries width) is read.
+typedef struct BrotliAmdUndictSeg {
+  const uint8_t* src;
+  uint8_t* dst;
+  uint64_t len;
+  uint64_t cap;
+  uint64_t first_item;
+  uint32_t width;
+  uint32_t bits;
+  uint32_t flags;
+  uint32_t reserved;
+  const uint8_t* dict;
+  uint64_t dict_entries;
+} BrotliAmdUndictSeg;
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,9 +4,9 @@
 //                   filter_device runs any table through it and keeps the call's times with the batch object.
 //   the plain path  unshuffle, undelta, bit-unshuffle, bit-unpack: a table of BrotliAmdUnshuffleSeg built from the caller's arrays or from the
 //                   outputs by a shape check per filter; nothing comes back but the destination's bytes.
-//   the counted path  unvarint, unrle, undbp: a capacity per segment and a result per segment.  A traits struct a filter (its segment, its result,
-//                   its shape check, how an entry is made, how many items a capacity gives) under three templates: counted_device,
-//                   counted_segments, counted_outputs.
+//   the counted path  unvarint, unrle, undbp, undict: a capacity per segment and a result per segment.  A traits struct a filter (its segment, its
+//                   result, its shape check, how an entry is made, how many items a capacity gives, whether it has a dictionary) under three
+//                   templates: counted_device, counted_segments, counted_outputs.
 //   the hooks       BrotliAmdDebug*Host run the device's functions of a filter's header (csrc/brotli_<filter>.h) on the host as the kernel's lanes
 //                   take them, for tests without a device.  They share the seeded orders, the serial carries, the argument checks and the
 //                   counted filters' closing block; each keeps its own phase loops.
@@ -14,6 +14,7 @@
 #include "brotli_bitunshuffle.h"
 #include "brotli_host.h"
 #include "brotli_undbp.h"
+#include "brotli_undict.h"
 #include "brotli_undelta.h"
 #include "brotli_unrle.h"
 #include "brotli_unshuffle.h"
@@ -25,11 +26,12 @@
 // ev: the filter's events, recorded around and between its launches)
 typedef hipError_t FilterLaunch(const void* d_segs, uint32_t n, uint64_t units, void* d_scratch, hipStream_t stream, const hipEvent_t* ev);
 extern "C" FilterLaunch brotli_amd_launch_unshuffle, brotli_amd_launch_undelta, brotli_amd_launch_bitunshuffle, brotli_amd_launch_bitunpack,
-    brotli_amd_launch_unvarint, brotli_amd_launch_unrle, brotli_amd_launch_undbp;
+    brotli_amd_launch_unvarint, brotli_amd_launch_unrle, brotli_amd_launch_undbp, brotli_amd_launch_undict;
 extern "C" uint64_t brotli_amd_undelta_scratch_bytes(uint64_t units);
 extern "C" uint64_t brotli_amd_unvarint_scratch_bytes(uint64_t units, uint32_t n);
 extern "C" uint64_t brotli_amd_unrle_scratch_bytes(uint64_t units, uint32_t n);
 extern "C" uint64_t brotli_amd_undbp_scratch_bytes(uint64_t units, uint32_t n);
+extern "C" uint64_t brotli_amd_undict_scratch_bytes(uint64_t units, uint32_t n);
 extern "C" uint32_t brotli_amd_undbp_item_deltas(void);
 extern "C" uint32_t brotli_amd_undbp_walk_chunk(void);
 extern "C" uint32_t brotli_amd_unrle_item_elems(void);
@@ -47,7 +49,7 @@ namespace {
 
 // ---- the descriptor ----
 // What the host needs to know of a filter.  A filter of one launch has two events; undelta and unvarint have four around and between their three
-// launches, unrle three, undbp five.  The counted filters' results lie first behind the table.
+// launches, unrle and undict three, undbp five.  The counted filters' results lie first behind the table.
 struct FilterDesc {
   const char* name;   // in the texts of g_last_error
   SegCallWhat what;
@@ -71,6 +73,8 @@ const FilterDesc kFilter[kFilters] = {
      "brotli_amd_unrle kernels launch", brotli_amd_launch_unrle, brotli_amd_unrle_scratch_bytes, 3u},
     {"undbp", {"hipMalloc(undbp segments, results, checkpoints and tiles)", "hipMemcpyAsync(undbp segments)", "hipStreamSynchronize(undbp)"},
      "brotli_amd_undbp kernels launch", brotli_amd_launch_undbp, brotli_amd_undbp_scratch_bytes, 5u},
+    {"undict", {"hipMalloc(undict segments, results and checkpoints)", "hipMemcpyAsync(undict segments)", "hipStreamSynchronize(undict)"},
+     "brotli_amd_undict kernels launch", brotli_amd_launch_undict, brotli_amd_undict_scratch_bytes, 3u},
 };
 
 typedef std::vector<BrotliAmdUnshuffleSeg> Segs;
@@ -80,6 +84,7 @@ inline uint64_t units_of(const BrotliAmdUnshuffleSeg& s) { return brotli_amd_seg
 inline uint64_t units_of(const BrotliAmdUnvarintSeg& s) { return brotli_amd_seg_units((uint64_t)(uintptr_t)s.src, s.len); }
 inline uint64_t units_of(const BrotliAmdUnrleSeg& s) { return 1u + brotli_amd_unrle_items(s.cap, brotli_amd_unrle_item_elems()); }
 inline uint64_t units_of(const BrotliAmdUndbpSeg& s) { return 1u + brotli_amd_undbp_items(s.cap, brotli_amd_undbp_item_deltas()); }
+inline uint64_t units_of(const BrotliAmdUndictSeg& s) { return 1u + brotli_amd_unrle_items(s.cap, brotli_amd_unrle_item_elems()); }
 
 int invalid_arguments(Filter f) { g_last_error = std::string("invalid ") + kFilter[f].name + " arguments"; return -1; }
 
@@ -214,17 +219,19 @@ void packed_shape(BrotliAmdUnshuffleSeg* s, uint64_t count, uint32_t bits, uint3
 // ---- the counted path: a width, flags and a capacity (unrle: a field width too); a result per segment ----
 // What differs between the counted filters.  kFlags: the flag bits it knows; kMaxCap: the largest capacity; kBits: it has a column of field widths
 // and names it in its texts; kItems: its units are items of its destination; field_fault: what is wrong with a field width (nullptr: nothing); items: the items a capacity gives (unvarint: none, its
-// units are its source's); make: a table entry, first_item being the items of the entries in front of it.
+// units are its source's); make: a table entry, first_item being the items of the entries in front of it; kDict: it has the two dictionary
+// columns, and make takes what they say; empty: the result of a segment that was not looked at.
+struct Dict { const void* ptr; uint64_t entries; };   // a segment's dictionary (undict's; nothing elsewhere)
 struct Unvarint {
   typedef BrotliAmdUnvarintSeg Seg;
   typedef BrotliAmdUnvarintResult Result;
   static constexpr Filter kId = kUnvarint;
   static constexpr uint32_t kFlags = BROTLI_AMD_UNVARINT_FLAGS;
   static constexpr uint64_t kMaxCap = BROTLI_AMD_UNVARINT_MAX_CAP;
-  static constexpr bool kBits = false, kItems = false;
+  static constexpr bool kBits = false, kItems = false, kDict = false;
   static const char* field_fault(uint32_t, uint32_t, uint32_t) { return nullptr; }
   static uint64_t items(uint64_t) { return 0u; }
-  static Seg make(const uint8_t* src, uint8_t* dst, uint64_t len, uint64_t cap, uint32_t width, uint32_t, uint32_t flags, uint64_t) {
+  static Seg make(const uint8_t* src, uint8_t* dst, uint64_t len, uint64_t cap, uint32_t width, uint32_t, uint32_t flags, uint64_t, Dict) {
     return Seg{src, dst, len, cap, width, flags};
   }
 };
@@ -234,13 +241,13 @@ struct Unrle {
   static constexpr Filter kId = kUnrle;
   static constexpr uint32_t kFlags = BROTLI_AMD_UNRLE_FLAGS;
   static constexpr uint64_t kMaxCap = BROTLI_AMD_UNRLE_MAX_CAP;
-  static constexpr bool kBits = true, kItems = true;
+  static constexpr bool kBits = true, kItems = true, kDict = false;
   static const char* field_fault(uint32_t bits, uint32_t width, uint32_t flags) {
     if ((flags & BROTLI_AMD_UNRLE_WIDTH_BYTE) != 0u) return nullptr;   // (the field width is in the source, and bits is not looked at)
     return bits > BROTLI_AMD_UNRLE_MAX_BITS ? "field of more than 32 bits" : bits > 8u * width ? "field is wider than the element" : nullptr;
   }
   static uint64_t items(uint64_t cap) { return brotli_amd_unrle_items(cap, brotli_amd_unrle_item_elems()); }
-  static Seg make(const uint8_t* src, uint8_t* dst, uint64_t len, uint64_t cap, uint32_t width, uint32_t bits, uint32_t flags, uint64_t first_item) {
+  static Seg make(const uint8_t* src, uint8_t* dst, uint64_t len, uint64_t cap, uint32_t width, uint32_t bits, uint32_t flags, uint64_t first_item, Dict) {
     return Seg{src, dst, len, cap, first_item, width, bits, flags, 0u};
   }
 };
@@ -250,35 +257,61 @@ struct Undbp {
   static constexpr Filter kId = kUndbp;
   static constexpr uint32_t kFlags = 0u;
   static constexpr uint64_t kMaxCap = BROTLI_AMD_UNDBP_MAX_CAP;
-  static constexpr bool kBits = false, kItems = true;
+  static constexpr bool kBits = false, kItems = true, kDict = false;
   static const char* field_fault(uint32_t, uint32_t, uint32_t) { return nullptr; }
   static uint64_t items(uint64_t cap) { return brotli_amd_undbp_items(cap, brotli_amd_undbp_item_deltas()); }
-  static Seg make(const uint8_t* src, uint8_t* dst, uint64_t len, uint64_t cap, uint32_t width, uint32_t, uint32_t, uint64_t first_item) {
+  static Seg make(const uint8_t* src, uint8_t* dst, uint64_t len, uint64_t cap, uint32_t width, uint32_t, uint32_t, uint64_t first_item, Dict) {
     return Seg{src, dst, len, cap, first_item, width, 0u};
   }
 };
+struct Undict {
+  typedef BrotliAmdUndictSeg Seg;
+  typedef BrotliAmdUndictResult Result;
+  static constexpr Filter kId = kUndict;
+  static constexpr uint32_t kFlags = BROTLI_AMD_UNDICT_FLAGS;
+  static constexpr uint64_t kMaxCap = BROTLI_AMD_UNDICT_MAX_CAP;
+  static constexpr bool kBits = true, kItems = true, kDict = true;
+  static const char* field_fault(uint32_t bits, uint32_t, uint32_t flags) {   // (an index is not bound by the element's width)
+    return (flags & BROTLI_AMD_UNDICT_WIDTH_BYTE) == 0u && bits > BROTLI_AMD_UNRLE_MAX_BITS ? "field of more than 32 bits" : nullptr;
+  }
+  static uint64_t items(uint64_t cap) { return brotli_amd_unrle_items(cap, brotli_amd_unrle_item_elems()); }
+  static Seg make(const uint8_t* src, uint8_t* dst, uint64_t len, uint64_t cap, uint32_t width, uint32_t bits, uint32_t flags, uint64_t first_item, Dict d) {
+    return Seg{src, dst, len, cap, first_item, width, bits, flags, 0u, static_cast<const uint8_t*>(d.ptr), d.entries};
+  }
+};
+// the result of a segment that was not looked at: zeros, and of undict no first bad element
+template <class T> typename T::Result empty_result() { return typename T::Result{}; }
+template <> BrotliAmdUndictResult empty_result<Undict>() { return BrotliAmdUndictResult{0u, 0u, 0u, 0u, 0u, 0u, BROTLI_AMD_UNDICT_NONE}; }
 
 // the shape check.  (A table has a hundred thousand segments: what passes costs a few comparisons in the caller's loop, and the text -- it names
 // the first clause that fails, and `who` names the segment or stream -- is built out of line.)
 template <class T>
-__attribute__((noinline)) bool refuse_counted(const char* what, uint32_t bits, uint32_t width, uint32_t flags, uint64_t cap, const char* who, size_t i) {
+__attribute__((noinline)) bool refuse_counted(const char* what, uint32_t bits, uint32_t width, uint32_t flags, uint64_t cap, Dict d, const char* who, size_t i) {
   g_last_error = std::string(kFilter[T::kId].name) + " " + who + " " + std::to_string(i) + ": " + what + " (" + (T::kBits ? "bits " + std::to_string(bits) + ", " : "") +
-                 "width " + std::to_string(width) + ", flags " + std::to_string(flags) + ", capacity " + std::to_string(cap) + ")";
+                 "width " + std::to_string(width) + ", flags " + std::to_string(flags) + ", capacity " + std::to_string(cap) +
+                 (T::kDict ? ", dictionary entries " + std::to_string(d.entries) : "") + ")";
   return false;
 }
 template <class T>
-inline bool known_counted(uint32_t bits, uint32_t width, uint32_t flags, uint64_t cap, bool has_dst, const char* who, size_t i) {
+inline bool known_counted(uint32_t bits, uint32_t width, uint32_t flags, uint64_t cap, bool has_dst, const char* who, size_t i, Dict d = Dict{nullptr, 0u}) {
   const char* what = nullptr;
   if (!brotli_amd_unshuffle_width_ok(width)) what = "width is not 1, 2, 4 or 8";
   else if ((flags & ~T::kFlags) != 0u) what = "unknown flag bits";
   else if ((what = T::field_fault(bits, width, flags)) != nullptr) {}
   else if (cap > T::kMaxCap) what = "a capacity above 2^56 elements";
   else if (cap != 0u && !has_dst) what = "no destination for a capacity that is not 0";
-  return !what || refuse_counted<T>(what, bits, width, flags, cap, who, i);
+  else if (T::kDict && d.entries > BROTLI_AMD_UNDICT_MAX_ENTRIES) what = "a dictionary of more than 2^56 entries";
+  else if (T::kDict && cap != 0u && d.entries != 0u && !d.ptr) what = "no dictionary for entries and a capacity that are not 0";
+  return !what || refuse_counted<T>(what, bits, width, flags, cap, d, who, i);
 }
 
-// a call's columns, by segment or stream: flags may be NULL (zeros), and bits is looked at where the filter has field widths
-struct Columns { const uint64_t* caps; const uint8_t* bits; const uint8_t* widths; const uint8_t* flags; };
+// a call's columns, by segment or stream: flags may be NULL (zeros), bits is looked at where the filter has field widths, and dicts and
+// dict_entries where it has dictionaries (NULL: none, and no entries)
+struct Columns {
+  const uint64_t* caps; const uint8_t* bits; const uint8_t* widths; const uint8_t* flags;
+  const void* const* dicts = nullptr; const uint64_t* dict_entries = nullptr;
+  Dict dict(size_t i) const { return Dict{dicts ? dicts[i] : nullptr, dict_entries ? dict_entries[i] : 0u}; }
+};
 
 // A counted call's table, entry by entry: each checked, then made where it stays.  `where`: the index of every entry's result.
 template <class T>
@@ -289,10 +322,10 @@ struct CountedTable {
   void reserve(size_t n) { segs.reserve(n); where.reserve(n); }
   // entry i of the call, with a capacity and a destination that its caller has settled -- false: g_last_error says why.  (In the caller's loop:
   // as a function of its own it cost a call with nine arguments a segment, 0.25 ms in a table of a hundred thousand -- profiles/filter_host_paths.txt.)
-  __attribute__((always_inline)) bool push(const Columns& c, size_t i, const void* src, void* dst, uint64_t len, uint64_t cap, bool has_dst, const char* who) {
+  __attribute__((always_inline)) bool push(const Columns& c, size_t i, const void* src, void* dst, uint64_t len, uint64_t cap, bool has_dst, const char* who, Dict d = Dict{nullptr, 0u}) {
     const uint32_t bits = T::kBits ? c.bits[i] : 0u, flags = c.flags ? c.flags[i] : 0u;
-    if (!known_counted<T>(bits, c.widths[i], flags, cap, has_dst, who, i)) return false;
-    segs.push_back(T::make(static_cast<const uint8_t*>(src), static_cast<uint8_t*>(dst), len, cap, c.widths[i], bits, flags, items));
+    if (!known_counted<T>(bits, c.widths[i], flags, cap, has_dst, who, i, d)) return false;
+    segs.push_back(T::make(static_cast<const uint8_t*>(src), static_cast<uint8_t*>(dst), len, cap, c.widths[i], bits, flags, items, d));
     where.push_back(i);
     items += T::items(cap);
     return true;
@@ -302,7 +335,7 @@ struct CountedTable {
 // the table on `stream`, waited for, and its results: entry j's to results[where[j]] of the n_results, the others zeros
 template <class T>
 int counted_device(BrotliAmdBatch* b, const CountedTable<T>& t, typename T::Result* results, size_t n_results, hipStream_t stream) {
-  std::fill(results, results + n_results, typename T::Result{});
+  std::fill(results, results + n_results, empty_result<T>());
   const uint8_t* d_scratch = nullptr;
   if (filter_device(b, T::kId, t.segs, stream, &d_scratch) != 0) return -1;
   if (!d_scratch) return 0;   // (no segments, or segments without bytes: their results are zeros)
@@ -331,13 +364,30 @@ int counted_segments(BrotliAmdBatch* b, uint32_t n, const void* const* d_src, co
   t.reserve(n);
   for (uint32_t i = 0; i < n; i++) {
     void* dst = d_dst ? d_dst[i] : nullptr;   // (no array of destinations: a call that counts, where every capacity is 0)
-    if (!t.push(c, i, d_src[i], dst, src_lens[i], c.caps[i], dst != nullptr, "segment")) return -1;
+    if (T::kDict && c.caps[i] != 0u && (!c.dicts || !c.dict_entries)) return invalid_arguments(T::kId);   // (no arrays of dictionaries: the same)
+    if (!t.push(c, i, d_src[i], dst, src_lens[i], c.caps[i], dst != nullptr, "segment", T::kDict ? c.dict(i) : Dict{nullptr, 0u})) return -1;
   }
   return counted_device(b, t, results, n, static_cast<hipStream_t>(hip_stream));
 }
 
+// the dictionary of stream i of the outputs: what stream dict_streams[i] of the same call delivered, as entries of stream i's width, or -- for
+// BROTLI_AMD_UNDICT_NO_STREAM and without dict_streams -- the columns' own.  False: g_last_error says why.
+__attribute__((noinline)) bool refuse_dict_stream(size_t i, uint32_t j, size_t n) {
+  g_last_error = "undict stream " + std::to_string(i) + ": its dictionary stream " + std::to_string(j) +
+                 (j == i ? " is the stream itself" : " is none of the " + std::to_string(n) + " streams of the last decode call");
+  return false;
+}
+inline bool dict_of_outputs(const std::vector<DeliveredBytes>& outs, const Columns& c, const uint32_t* dict_streams, size_t i, Dict* d) {
+  const uint32_t j = dict_streams ? dict_streams[i] : BROTLI_AMD_UNDICT_NO_STREAM;
+  if (j == BROTLI_AMD_UNDICT_NO_STREAM) { *d = c.dict(i); return true; }
+  if (j == i || j >= outs.size()) return refuse_dict_stream(i, j, outs.size());
+  const uint32_t w = c.widths[i];
+  *d = Dict{outs[j].ptr, brotli_amd_unshuffle_width_ok(w) ? outs[j].len / w : 0u};   // (a width that is none is refused by the shape check)
+  return true;
+}
+
 template <class T>
-int counted_outputs(BrotliAmdBatch* b, void* const* d_dst, const Columns& c, typename T::Result* results) {
+int counted_outputs(BrotliAmdBatch* b, void* const* d_dst, const Columns& c, typename T::Result* results, const uint32_t* dict_streams = nullptr) {
   if (!b || (T::kBits && !c.bits) || !c.widths || !results) return invalid_arguments(T::kId);
   no_times(b, T::kId);
   std::vector<DeliveredBytes> outs;
@@ -347,7 +397,9 @@ int counted_outputs(BrotliAmdBatch* b, void* const* d_dst, const Columns& c, typ
   t.reserve(outs.size());
   for (size_t i = 0; i < outs.size(); i++) {
     if (!count_only && d_dst[i] == nullptr) continue;   // skipped: none of its parameters are looked at
-    if (!t.push(c, i, outs[i].ptr, count_only ? nullptr : d_dst[i], outs[i].len, count_only ? 0u : c.caps[i], !count_only, "stream")) return -1;
+    Dict d = {nullptr, 0u};
+    if (T::kDict && !count_only && !dict_of_outputs(outs, c, dict_streams, i, &d)) return -1;
+    if (!t.push(c, i, outs[i].ptr, count_only ? nullptr : d_dst[i], outs[i].len, count_only ? 0u : c.caps[i], !count_only, "stream", d)) return -1;
   }
   return counted_device(b, t, results, outs.size(), b->last_stream);
 }
@@ -493,6 +545,17 @@ extern "C" int BrotliAmdBatchUndbpOutputs(BrotliAmdBatch* b, void* const* d_dst,
   return counted_outputs<Undbp>(b, d_dst, Columns{caps, nullptr, widths, flags}, results);
 }
 
+extern "C" int BrotliAmdBatchUndictSegments(BrotliAmdBatch* b, uint32_t n, const void* const* d_src, const size_t* src_lens, void* const* d_dst,
+                                            const uint64_t* caps, const uint8_t* bits, const uint8_t* widths, const uint8_t* flags, const void* const* d_dicts,
+                                            const uint64_t* dict_entries, BrotliAmdUndictResult* results, void* hip_stream) {
+  return counted_segments<Undict>(b, n, d_src, src_lens, d_dst, Columns{caps, bits, widths, flags, d_dicts, dict_entries}, results, hip_stream);
+}
+extern "C" int BrotliAmdBatchUndictOutputs(BrotliAmdBatch* b, void* const* d_dst, const uint64_t* caps, const uint8_t* bits, const uint8_t* widths,
+                                           const uint8_t* flags, const uint32_t* dict_streams, const void* const* d_dicts, const uint64_t* dict_entries,
+                                           BrotliAmdUndictResult* results) {
+  return counted_outputs<Undict>(b, d_dst, Columns{caps, bits, widths, flags, d_dicts, dict_entries}, results, dict_streams);
+}
+
 extern "C" float BrotliAmdBatchLastUnshuffleMs(BrotliAmdBatch* b) { return b ? b->filter[kUnshuffle].ms : 0.0f; }
 extern "C" float BrotliAmdBatchLastUndeltaMs(BrotliAmdBatch* b) { return b ? b->filter[kUndelta].ms : 0.0f; }
 extern "C" float BrotliAmdBatchLastUndeltaPhaseMs(BrotliAmdBatch* b, uint32_t phase) { return phase_ms(b, kUndelta, phase); }
@@ -504,6 +567,8 @@ extern "C" float BrotliAmdBatchLastUnrleMs(BrotliAmdBatch* b) { return b ? b->fi
 extern "C" float BrotliAmdBatchLastUnrlePhaseMs(BrotliAmdBatch* b, uint32_t phase) { return phase_ms(b, kUnrle, phase); }
 extern "C" float BrotliAmdBatchLastUndbpMs(BrotliAmdBatch* b) { return b ? b->filter[kUndbp].ms : 0.0f; }
 extern "C" float BrotliAmdBatchLastUndbpPhaseMs(BrotliAmdBatch* b, uint32_t phase) { return phase_ms(b, kUndbp, phase); }
+extern "C" float BrotliAmdBatchLastUndictMs(BrotliAmdBatch* b) { return b ? b->filter[kUndict].ms : 0.0f; }
+extern "C" float BrotliAmdBatchLastUndictPhaseMs(BrotliAmdBatch* b, uint32_t phase) { return phase_ms(b, kUndict, phase); }
 extern "C" uint32_t BrotliAmdDebugUndbpItemDeltas(void) { return brotli_amd_undbp_item_deltas(); }
 extern "C" uint32_t BrotliAmdDebugUndbpWalkChunk(void) { return brotli_amd_undbp_walk_chunk(); }
 extern "C" uint32_t BrotliAmdDebugUnrleItemElems(void) { return brotli_amd_unrle_item_elems(); }
@@ -739,4 +804,49 @@ extern "C" int BrotliAmdDebugUndbpHost(uint32_t n, const uint8_t* src, size_t sr
     brotli_amd_undbp_host_store(segs[i], got[i], ckpts[g], firsts[i], g - pre[i], item_deltas, carries[g]);
   }
   return counted_hook_result(kUndbp, droom, n, dst, dst_size, dst_offs, caps, widths, got, results);
+}
+
+// Undict's two phases over n segments given as offsets into one source, one destination and one dictionary buffer, each buffer in its room:
+// every segment's walk -- unrle's --, then the items of all segments in an order shuffled by the seed, each adding its bad elements to its
+// segment's result.
+extern "C" int BrotliAmdDebugUndictHost(uint32_t n, const uint8_t* src, size_t src_size, uint8_t* dst, size_t dst_size, const uint8_t* dict, size_t dict_size,
+                                        const uint64_t* src_offs, const uint64_t* src_lens, const uint64_t* dst_offs, const uint64_t* caps, const uint64_t* dict_offs,
+                                        const uint64_t* dict_entries, const uint8_t* bits, const uint8_t* widths, const uint8_t* flags, uint32_t src_skew,
+                                        uint32_t dst_skew, uint32_t dict_skew, uint32_t item_elems, uint32_t order_seed, BrotliAmdUndictResult* results) {
+  if ((n && (!src_offs || !src_lens || !dst_offs || !caps || !dict_offs || !dict_entries || !bits || !widths || !results)) ||
+      !rooms_ok(src, src_size, dst, dst_size, src_skew, dst_skew) || (dict_size && !dict) || dict_skew > 15u)
+    return invalid_arguments(kUndict);
+  if (item_elems == 0u) item_elems = brotli_amd_unrle_item_elems();
+  for (uint32_t i = 0; i < n; i++) {
+    if (!known_counted<Undict>(bits[i], widths[i], flags ? flags[i] : 0u, caps[i], true, "segment", i, Dict{dict ? dict : src, dict_entries[i]})) return -1;
+    if (!lies_in(src_offs[i], src_lens[i], src_size) || dst_offs[i] > dst_size) return outside_buffer(kUndict);
+    if (dict_entries[i] != 0u && !lies_in(dict_offs[i], dict_entries[i] * widths[i], dict_size)) {
+      g_last_error = "invalid undict arguments: a dictionary outside its buffer";
+      return -1;
+    }
+  }
+  SkewedRoom sroom(src_size, src_skew, 0xA5), droom(dst_size, dst_skew, 0x5A), troom(dict_size, dict_skew, 0x3C);
+  sroom.put(src, src_size);
+  droom.put(dst, dst_size);
+  troom.put(dict, dict_size);
+  // the walks: they write nothing, and say how much room every segment needs
+  std::vector<BrotliAmdUndictSeg> segs;
+  std::vector<BrotliAmdUndictResult> got(n);
+  std::vector<std::vector<BrotliAmdUnrleCheckpoint>> ckpts(n);
+  std::vector<std::pair<uint32_t, uint64_t>> order;   // (segment, item)
+  for (uint32_t i = 0; i < n; i++) {
+    // (the items of the elements there is room for: the walk marks no others, and a capacity of 2^56 needs no table of its own)
+    const uint64_t room = (dst_size - dst_offs[i]) / widths[i], cap = std::min<uint64_t>(caps[i], room + 1u);
+    segs.push_back(BrotliAmdUndictSeg{reinterpret_cast<const uint8_t*>((uintptr_t)(sroom.at() + src_offs[i])), reinterpret_cast<uint8_t*>((uintptr_t)(droom.at() + dst_offs[i])),
+                                      src_lens[i], cap, 0u, widths[i], bits[i], flags ? flags[i] : 0u, 0u,
+                                      reinterpret_cast<const uint8_t*>((uintptr_t)(troom.at() + dict_offs[i])), dict_entries[i]});
+    ckpts[i].assign(brotli_amd_unrle_items(cap, item_elems), BrotliAmdUnrleCheckpoint{BROTLI_AMD_UNRLE_NONE, BROTLI_AMD_UNRLE_NONE});
+    got[i] = brotli_amd_undict_host_walk(segs[i], item_elems, ckpts[i].data());
+    if (std::min(got[i].count, caps[i]) > room) return outside_buffer(kUndict);
+    for (uint64_t j = 0; j < ckpts[i].size(); j++) order.push_back({i, j});
+  }
+  droom.snapshot();
+  SeededOrder(order_seed).shuffle(&order);
+  for (const auto& it : order) brotli_amd_undict_host_item(segs[it.first], &got[it.first], ckpts[it.first][it.second], it.second, item_elems);
+  return counted_hook_result(kUndict, droom, n, dst, dst_size, dst_offs, caps, widths, got, results);
 }

@@ -159,23 +159,30 @@ inline BrotliAmdUnrleResult brotli_amd_unrle_host_walk(const BrotliAmdUnrleSeg& 
     for (uint64_t j = j0; j < j1; j++) ckpts[j] = BrotliAmdUnrleCheckpoint{off, first};
   });
 }
-// item j of the segment, res being the walk's result and cp the item's checkpoint
-inline void brotli_amd_unrle_host_item(const BrotliAmdUnrleSeg& sg, const BrotliAmdUnrleResult& res, BrotliAmdUnrleCheckpoint cp, uint64_t j, uint32_t item_elems) {
-  const uint64_t src = (uint64_t)(uintptr_t)sg.src, dst = (uint64_t)(uintptr_t)sg.dst;
-  const uint64_t end = res.count < sg.cap ? res.count : sg.cap, e0 = j * item_elems;
+// Item j of a segment of len bytes at src with capacity cap, count and k being its walk's and cp the item's checkpoint: each(e, v) for every
+// element e of the item, v being the value of its run (brotli_amd_undict.h takes v as an index)
+template <class Each>
+inline void brotli_amd_unrle_host_item_each(uint64_t src, uint64_t len, uint64_t cap, uint64_t count, uint32_t k, BrotliAmdUnrleCheckpoint cp, uint64_t j,
+                                            uint32_t item_elems, Each each) {
+  const uint64_t end = count < cap ? count : cap, e0 = j * item_elems;
   if (cp.off == BROTLI_AMD_UNRLE_NONE || e0 >= end) return;
   const uint64_t e1 = e0 + item_elems < end ? e0 + item_elems : end;
   BrotliAmdUnrleDirect rd = {src};
   BrotliAmdUnrleWalk st = {cp.off, cp.first};
   for (uint64_t e = e0; e < e1;) {
-    const BrotliAmdUnrleRun run = brotli_amd_unrle_run(rd, sg.len, res.bits, st);
+    const BrotliAmdUnrleRun run = brotli_amd_unrle_run(rd, len, k, st);
     if (run.kind == BROTLI_AMD_UNRLE_STOP) return;   // (not below count)
     const uint64_t run_end = st.elems + run.count, payload = run.kind == BROTLI_AMD_UNRLE_RLE ? BROTLI_AMD_UNRLE_NONE : run.payload;
-    for (; e < run_end && e < e1; e++)
-      brotli_amd_unvarint_store(dst + e * sg.width, sg.width, brotli_amd_unrle_element(src, payload, run.value, res.bits, e - st.elems));
+    for (; e < run_end && e < e1; e++) each(e, brotli_amd_unrle_element(src, payload, run.value, k, e - st.elems));
     st.off = run.next; st.elems = run_end;
     if (run.status != BROTLI_AMD_UNRLE_OK) return;
   }
+}
+// item j of the segment, res being the walk's result and cp the item's checkpoint
+inline void brotli_amd_unrle_host_item(const BrotliAmdUnrleSeg& sg, const BrotliAmdUnrleResult& res, BrotliAmdUnrleCheckpoint cp, uint64_t j, uint32_t item_elems) {
+  const uint64_t dst = (uint64_t)(uintptr_t)sg.dst;
+  brotli_amd_unrle_host_item_each((uint64_t)(uintptr_t)sg.src, sg.len, sg.cap, res.count, res.bits, cp, j, item_elems,
+                                  [&](uint64_t e, uint64_t v) { brotli_amd_unvarint_store(dst + e * sg.width, sg.width, v); });
 }
 
 #endif  // BROTLI_AMD_UNRLE_H_

@@ -19,7 +19,10 @@ hybrid: dictionary indices, definition and repetition levels, booleans -- says s
 first byte holds k, without; one call decodes all such streams into their slots (Batch.unrle_outputs), and a stream whose runs did not end
 well or held fewer values than its shape says is refused.  A stream whose array was stored as DELTA BLOCKS -- Parquet's DELTA_BINARY_PACKED:
 INT32 and INT64 pages, the lengths of byte arrays -- says "dbp"; one call decodes all such streams into their slots (Batch.undbp_outputs), and
-a stream that did not end well or held another number of values than its shape says is refused; bytes behind its last block are not judged."""
+a stream that did not end well or held another number of values than its shape says is refused; bytes behind its last block are not judged.
+A stream that is a DICTIONARY-INDEX PAGE BODY -- Parquet's RLE_DICTIONARY: a width byte and then runs of indices -- names its dictionary, another
+stream of the same call or a tensor, and one call turns all such streams into their VALUES (Batch.undict_outputs): the indices never reach
+memory, and a stream with an index outside its dictionary is refused."""
 import collections
 
 import torch
@@ -34,24 +37,25 @@ def _numel(shape):
     return n
 
 
-FILTERS = ("shuffle", "delta", "bitshuffle", "bitpack", "varint", "rle", "dbp")
+FILTERS = ("shuffle", "delta", "bitshuffle", "bitpack", "varint", "rle", "dbp", "dict")
 BITPACK_OPTIONS = {"big": 1, "signed": 2}   # BITUNPACK_MSB_FIRST, BITUNPACK_SIGNED
 VARINT_OPTIONS = {"zigzag": 1}              # UNVARINT_ZIGZAG
-RLE_WIDTH_BYTE = 1                          # UNRLE_WIDTH_BYTE
+RLE_WIDTH_BYTE = 1                          # UNRLE_WIDTH_BYTE, UNDICT_WIDTH_BYTE
+DICT_NO_STREAM = 0xFFFFFFFF                 # UNDICT_NO_STREAM
 DBP_STATUS = ("ok", "a header that is none", "a miniblock of more than 64 bits", "blocks that the stream's end cuts")
 RLE_STATUS = ("ok", "a header of more than five bytes", "a run of no values", "runs that the stream's end cuts", "a width byte that is none")
 
 
 # What a wanted stream's spec says: the slot's bytes, the tensor's dtype and shape, the element width, the names of its filters, bitshuffle's block
 # and bitpack's (k, flags) -- (1, 0) where the stream is not packed, as for a stream that is not wanted --, varint's flags, rle's (k, flags) --
-# (0, 0) where the stream has no runs
-_Stream = collections.namedtuple("_Stream", "want dtype shape item filters block pack varint rle")
+# (0, 0) where the stream has no runs --, dict's dictionary: a stream's number or a tensor (None where the stream has none)
+_Stream = collections.namedtuple("_Stream", "want dtype shape item filters block pack varint rle dict")
 
 
 def _parse_spec(i, spec, size):
     """spec of stream i, which delivered `size` bytes -> _Stream; ValueError, naming the stream, for what outputs_as_tensors refuses"""
     dtype, shape = spec[0], spec[1]
-    flt, block, pack, varint, rle = [], 0, None, 0, None
+    flt, block, pack, varint, rle, dictionary = [], 0, None, 0, None, None
     for name in (tuple(spec[2]) if len(spec) > 2 else ("shuffle",)):
         if isinstance(name, (tuple, list)) and len(name) == 2 and name[0] == "bitshuffle":   # ("bitshuffle", block_elems)
             name, block = name[0], int(name[1])
@@ -77,6 +81,12 @@ def _parse_spec(i, spec, size):
             name, rle = name[0], (int(name[1]), 0)
         elif name == "rle":
             rle = (0, RLE_WIDTH_BYTE)
+        if isinstance(name, (tuple, list)) and len(name) >= 1 and name[0] == "dict":   # ("dict", j) or ("dict", tensor)
+            if len(name) != 2 or isinstance(name[1], bool) or not isinstance(name[1], (int, torch.Tensor)):
+                raise ValueError("stream %d: (\"dict\", j) names the stream that holds the dictionary, (\"dict\", tensor) the dictionary itself, and nothing else" % i)
+            name, dictionary = name[0], name[1]
+        elif name == "dict":
+            raise ValueError("stream %d: \"dict\" without its dictionary: (\"dict\", j) or (\"dict\", tensor)" % i)
         if name in VARINT_OPTIONS and flt and flt[-1] == "varint":   # ("varint", "zigzag") as the spec's filters: the option right behind its filter
             varint |= VARINT_OPTIONS[name]
             continue
@@ -84,6 +94,8 @@ def _parse_spec(i, spec, size):
             raise ValueError("stream %d: unknown filter %r (known: %s)" % (i, name, ", ".join(FILTERS)))
         flt.append(name)
     flt = tuple(flt)
+    if "dict" in flt and len(flt) != 1:
+        raise ValueError("stream %d: \"dict\" stands alone in a spec: the values come out of the dictionary as they are" % i)
     if "shuffle" in flt and "bitshuffle" in flt:
         raise ValueError("stream %d: \"shuffle\" and \"bitshuffle\" in one spec: an array goes through one of them" % i)
     if pack is not None and ("shuffle" in flt or "bitshuffle" in flt):
@@ -105,13 +117,16 @@ def _parse_spec(i, spec, size):
         stored = (_numel(shape) * pack[0] + 7) // 8
         if size != stored:
             raise ValueError("stream %d: %d delivered bytes, but %d fields of %d bits (shape %s) are %d" % (i, size, _numel(shape), pack[0], shape, stored))
-    elif "varint" in flt or "rle" in flt or "dbp" in flt:
+    elif "varint" in flt or "rle" in flt or "dbp" in flt or "dict" in flt:
         pass   # (how many integers the delivered bytes hold is the call's to say: outputs_as_tensors checks its result)
     elif size != want:
         raise ValueError("stream %d: %d delivered bytes, but %s of shape %s is %d" % (i, size, dtype, shape, want))
     if rle is not None and not rle[1] and not 0 <= rle[0] <= min(32, 8 * item):
         raise ValueError("stream %d: rle fields of %d bits, but %s takes 0 .. %d" % (i, rle[0], dtype, min(32, 8 * item)))
-    return _Stream(want, dtype, shape, item, flt, block, pack or (1, 0), varint, rle or (0, 0))
+    if isinstance(dictionary, torch.Tensor) and (dictionary.dtype != dtype or dictionary.dim() != 1 or not dictionary.is_contiguous() or not dictionary.is_cuda):
+        raise ValueError("stream %d: its dictionary is a %s tensor of shape %s%s, not a contiguous 1-D device tensor of %s" %
+                         (i, dictionary.dtype, tuple(dictionary.shape), "" if dictionary.is_cuda else " on the host", dtype))
+    return _Stream(want, dtype, shape, item, flt, block, pack or (1, 0), varint, rle or (0, 0), dictionary)
 
 
 def outputs_as_tensors(batch, specs):
@@ -155,6 +170,15 @@ def outputs_as_tensors(batch, specs):
                                               block are not judged
         (dtype, shape, ("dbp", "delta"))      such a stream of deltas: that call, then Batch.undelta_segments in place; "dbp" with any other
                                               filter raises ValueError
+        (dtype, shape, (("dict", j),))        a dictionary-index page body -- a width byte k, then runs of k-bit indices --, whose dictionary is
+                                              what stream j of the same call delivered, taken as elements of the dtype (D = its bytes //
+                                              itemsize; stream j's own spec may be None or one of its own): ONE Batch.undict_outputs call for
+                                              all such streams, into the slots; the indices never reach memory.  ValueError, naming the stream
+                                              and what was found, where the runs do not end well (a status that is not OK), hold fewer values
+                                              than numel, or hold an index outside the dictionary (the text names the first one and D); more
+                                              values than numel are the last group's padding and are not judged
+        (dtype, shape, (("dict", tensor),))   ... whose dictionary is a 1-D contiguous device tensor of the dtype; "dict" with any other
+                                              filter raises ValueError, and so does a j that is the stream itself or no stream of the call
     "varint" together with "shuffle", "bitshuffle" or "bitpack" in one spec raises ValueError, naming the stream; so does "rle" together with
     any of those four.
     "shuffle" together with "bitshuffle", and "bitpack" together with either, in one spec raises ValueError, naming the stream; so does a k outside
@@ -190,10 +214,15 @@ def outputs_as_tensors(batch, specs):
     varints = [i for i in wanted if "varint" in streams[i].filters]
     runs = [i for i in wanted if "rle" in streams[i].filters]
     blocks = [i for i in wanted if "dbp" in streams[i].filters]
+    dicts = [i for i in wanted if "dict" in streams[i].filters]
+    for i in dicts:
+        j = streams[i].dict
+        if not isinstance(j, torch.Tensor) and (j == i or not 0 <= j < len(sizes)):
+            raise ValueError("stream %d: its dictionary stream %d is %s" % (i, j, "the stream itself" if j == i else "none of the %d streams of the last decode call" % len(sizes)))
     # deltas only: every other wanted stream that is neither of bit planes nor of packed fields is the unshuffle call's; without "shuffle" it is
     # a copy -- width 1
-    plain = [i for i in wanted if i not in bits and i not in packed and i not in varints and i not in runs and i not in blocks and "shuffle" not in streams[i].filters and "delta" in streams[i].filters]
-    batch.unshuffle_outputs(only([i for i in wanted if i not in plain and i not in bits and i not in packed and i not in varints and i not in runs and i not in blocks]),
+    plain = [i for i in wanted if i not in bits and i not in packed and i not in varints and i not in runs and i not in blocks and i not in dicts and "shuffle" not in streams[i].filters and "delta" in streams[i].filters]
+    batch.unshuffle_outputs(only([i for i in wanted if i not in plain and i not in bits and i not in packed and i not in varints and i not in runs and i not in blocks and i not in dicts]),
                             [st.item if st is not None and "shuffle" in st.filters else 1 for st in streams])
     if bits:    # bit planes: from the outputs straight into the slots
         batch.bitunshuffle_outputs(only(bits), widths, [0 if st is None else st.block for st in streams])
@@ -230,6 +259,24 @@ def outputs_as_tensors(batch, specs):
                                  (i, DBP_STATUS[status] if status < len(DBP_STATUS) else "an unknown status", status, count, declared, consumed, sizes[i]))
             if count != _numel(streams[i].shape):
                 raise ValueError("stream %d: %d values in its blocks, but shape %s is %d elements" % (i, count, streams[i].shape, _numel(streams[i].shape)))
+    if dicts:   # dictionary indices: the values from the outputs and the dictionaries straight into the slots; every index must lie inside
+        by_tensor = {i: isinstance(streams[i].dict, torch.Tensor) for i in dicts}
+        entries = {i: streams[i].dict.numel() if by_tensor[i] else sizes[streams[i].dict] // streams[i].item for i in dicts}
+        res = batch.undict_outputs(only(dicts), [0 if st is None else _numel(st.shape) for st in streams], [0] * len(streams), widths,
+                                   [RLE_WIDTH_BYTE if i in by_tensor else 0 for i in range(len(streams))],
+                                   [streams[i].dict if i in by_tensor and not by_tensor[i] else DICT_NO_STREAM for i in range(len(streams))],
+                                   [streams[i].dict.data_ptr() if by_tensor.get(i) else None for i in range(len(streams))],
+                                   [entries[i] if by_tensor.get(i) else 0 for i in range(len(streams))])
+        for i in dicts:
+            count, consumed, _, status, k, bad, first_bad = res[i]
+            if status != 0:
+                raise ValueError("stream %d: %s (status %d) after %d values in %d of its %d delivered bytes, indices of %d bits" %
+                                 (i, RLE_STATUS[status] if status < len(RLE_STATUS) else "an unknown status", status, count, consumed, sizes[i], k))
+            if count < _numel(streams[i].shape):
+                raise ValueError("stream %d: %d values in its runs, but shape %s is %d elements" % (i, count, streams[i].shape, _numel(streams[i].shape)))
+            if bad != 0:
+                raise ValueError("stream %d: %d of its %d values have an index outside its dictionary of %d entries, the first of them value %d" %
+                                 (i, bad, _numel(streams[i].shape), entries[i], first_bad))
     if plain:   # deltas only: from the outputs straight into the slots
         batch.undelta_outputs(only(plain), widths)
     both = [i for i in wanted if i not in plain and "delta" in streams[i].filters]
