@@ -861,8 +861,9 @@ BROTLI_DEC_API int BrotliAmdDebugUndbpHost(uint32_t n, const uint8_t* src, size_
  * together.  The dictionary is read through the caches.  Bad indices are summed up inside the wave; an item that has some adds them to its
  * segment's result with one atomic add and one atomic minimum (csrc/brotli_undict.h, csrc/brotli_undict_kernels.hip).
  *
- * OUT OF SCOPE: BYTE_ARRAY, FIXED_LEN_BYTE_ARRAY and INT96 dictionaries (entries of 12, 16 or variable bytes); definition levels and the
- * spreading of values over nulls; page framing; plain index arrays (a framework's gather does those); a parallel walk of one long segment. */
+ * OUT OF SCOPE: BYTE_ARRAY, FIXED_LEN_BYTE_ARRAY and INT96 dictionaries (entries of 12, 16 or variable bytes); page framing; plain index arrays
+ * (a framework's gather does those); a parallel walk of one long segment.  Definition levels and the spreading of values over nulls are the
+ * unnull calls' below. */
 #define BROTLI_AMD_UNDICT_WIDTH_BYTE 1u          /* BROTLI_AMD_UNRLE_WIDTH_BYTE's meaning */
 #define BROTLI_AMD_UNDICT_NO_STREAM 0xFFFFFFFFu  /* dict_streams[i]: the dictionary is d_dicts[i], not a stream of the decode call */
 
@@ -919,6 +920,135 @@ BROTLI_DEC_API int BrotliAmdDebugUndictHost(uint32_t n, const uint8_t* src, size
                                            const uint64_t* caps, const uint64_t* dict_offs, const uint64_t* dict_entries, const uint8_t* bits,
                                            const uint8_t* widths, const uint8_t* flags /* or NULL */, uint32_t src_skew, uint32_t dst_skew,
                                            uint32_t dict_skew, uint32_t item_elems, uint32_t order_seed, BrotliAmdUndictResult* results);
+
+/* ---- Unnull on the device: dense values spread over nulls by definition levels ----
+ *
+ * Every decoder above writes a DENSE array of the values that are there, and almost every real column is nullable: a Parquet writer puts
+ * DEFINITION LEVELS -- unrle's runs of k-bit fields -- in front of the values of every nullable field, even where no value is null, and only
+ * the slots whose level is the maximum have a value.  These calls take the levels and the dense values and write what a framework wants: one
+ * slot a row, 0 where the row is null, and Arrow's validity bitmap.  The levels never reach memory as an array.
+ *
+ * THE SEGMENT AND ITS PARAMETERS.
+ *   levels   the bytes src[0, len), read by unrle's grammar EXACTLY: headers, the two payload kinds, k == 0, an RLE run's value not masked,
+ *            every stop, and count, consumed, runs, status and bits of the result.  The field width `bits` = k is 0 .. 32; there is no width
+ *            byte.
+ *   level    a uint32: slot i is PRESENT iff level_i == level, compared unmasked; it is NULL otherwise, for levels below and above alike.
+ *   values   values_count = V dense elements of w bytes (w in {1, 2, 4, 8}) at `values`, any alignment.
+ *   cap      the capacity in slots; dst, any alignment; valid, a byte pointer of any alignment, or NULL for no bitmap.
+ *
+ * SLOTS.  With m = min(count, cap), slot i < m gets the value of RANK r_i, the number of present slots in front of i, where it is present and
+ * r_i < V, and 0 otherwise.  A present slot with r_i >= V is MISSING: its value is 0, nothing is read through that rank, and it is counted --
+ * the rank goes through undict's bounds-checked entry load as the index.  VALIDITY follows the levels alone, so a missing slot's bit is still
+ * 1.  It is Arrow's layout: bit i & 7 of byte i >> 3, LSB-first; exactly ceil(m / 8) bytes are written, and the bits at and above m in the
+ * last byte are 0.
+ *
+ * LOADS AND STORES.  No byte outside [dst, dst + m w) and [valid, valid + ceil(m / 8)) is written, and all of the first range is.  Reads stay
+ * inside the 16-byte-aligned spans around the levels and around [values, values + V w).  OUT OF PLACE ONLY: no destination or bitmap overlaps
+ * a source, the values or another destination or bitmap.  This is stated, not checked.
+ *
+ * FLAGS.  BROTLI_AMD_UNNULL_LENGTH_PREFIX: the segment is the front of a v1 data page -- its first four bytes are the little-endian length L,
+ * and the runs are src[4, 4 + L), judged as unrle judges a segment of that length.  consumed counts from the segment's first byte, so OK gives
+ * 4 + L.  len < 4 or L > len - 4 is the status BROTLI_AMD_UNNULL_BAD_LENGTH: count 0, consumed 0.
+ * BROTLI_AMD_UNNULL_VALUES_FOLLOW (refused without LENGTH_PREFIX): the values are what lies behind the runs in the same segment --
+ * values = src + consumed and V = floor((len - consumed) / w) where the status is OK, V = 0 elsewhere.  The values and values_count arguments
+ * are not looked at.
+ *
+ * RESULT.  BrotliAmdUnnullResult, 56 bytes: unrle's five fields with unrle's meaning, independent of cap and of how the work was shared
+ * out; then present, the delivered slots whose level is `level`; missing, the delivered present slots of rank >= V; and values, the V that
+ * was used.  present and missing depend on cap, like undict's bad: a call that only counts gives 0 for both.  A skipped stream's result is
+ * zeros.
+ *
+ * Examples (k, level, levels; values; slots; validity; present, missing):
+ *   1, 1, 03 A5; {10, 20, 30, 40} as uint16; 10 0 20 0 0 30 0 40; A5; 4, 0.
+ *   3, 5, 10 05 (8 x 5); {1 .. 8} as uint8; 1 2 3 4 5 6 7 8; FF; 8, 0.
+ *   3, 5, 10 05; {1 .. 6}: a MISSING value; 1 2 3 4 5 6 0 0; FF; 8, 2.
+ *   3, 2, 03 88 C6 FA (0 .. 7); {9} as uint32; 0 0 9 0 0 0 0 0; 04; 1, 0.
+ *   9, 300, 06 2C 01 (3 x 300, not masked); {7, 8, 9} as uint8; 7 8 9; 07; 3, 0.  With level 44: 0 0 0; 00; 0, 0.
+ *   0, 0, 07 (24 x 0), cap 10; {1 .. 10} as uint8; 1 .. 10; FF 03; count 24, 10, 0.
+ *   LENGTH_PREFIX | VALUES_FOLLOW, 1, 1, w = 2: the segment 02 00 00 00 03 A5 0A 00 14 00 1E 00 28 00 -- L = 2, consumed 6, V = 4 --;
+ *     10 0 20 0 0 30 0 40; A5; 4, 0.  The same segment cut to 3 bytes, or with a first byte of 0B: BAD_LENGTH.
+ *
+ * REFUSED ON THE HOST, in front of everything that touches the device, with a text that names the segment: a width outside {1, 2, 4, 8};
+ * unknown flag bits; VALUES_FOLLOW without LENGTH_PREFIX; bits > 32; cap > 2^56; values_count > 2^56; a NULL dst with cap != 0; a NULL
+ * values with V != 0, cap != 0 and no VALUES_FOLLOW.
+ *
+ * A call is four launches in stream order, on undbp's shape, and no block ever waits for another -- no look-back, no flags, no spins, no
+ * grid barrier, no atomics on the bitmap.  1. THE WALK, one wave a segment: the four bytes of the prefix where there is one, then unrle's
+ * walk: the result, the checkpoints of unrle's items, the prefix entry.  2. THE COUNTS, one wave an item over the items of all segments: the
+ * runs that cover the item, a lane's present mask of its 16 neighbouring slots -- inside an RLE run one compare --, and the wave's popcount
+ * as an undelta tile record.  3. undelta's CARRY launch as it is: every item's present slots in front of it.  4. THE EXPANSION, the same item
+ * function: a scan of the lanes' popcounts on top of the carry gives a lane its first rank; its present slots have consecutive ranks, so
+ * neighbouring lanes read neighbouring values; slots go out as aligned 16-byte stores with single ones at the edges, and the lanes' two
+ * validity bytes are gathered into aligned 16-byte stores.  The item that holds a segment's last delivered slot writes present and missing:
+ * its carry-in and its own popcount are all of them, and the ranks at or above V are the missing ones.  A call that only counts is the first
+ * launch alone (csrc/brotli_unnull.h, csrc/brotli_unnull_kernels.hip).
+ *
+ * OUT OF SCOPE: repetition levels and nested columns; a bit offset into the bitmap; a fill value other than 0; byte-array values; thrift
+ * framing; a fused undict + unnull -- a nullable dictionary column is two calls, and a counting call with LENGTH_PREFIX tells the caller where
+ * a v1 dictionary-index body begins --; a parallel walk of one long segment. */
+#define BROTLI_AMD_UNNULL_LENGTH_PREFIX 1u
+#define BROTLI_AMD_UNNULL_VALUES_FOLLOW 2u
+#define BROTLI_AMD_UNNULL_BAD_LENGTH 5u   /* a status behind BROTLI_AMD_UNRLE_*: the length prefix is cut, or says more than there is */
+
+typedef struct BrotliAmdUnnullResult {
+  uint64_t count;     /* levels in all runs, whatever cap was */
+  uint64_t consumed;  /* unrle's table, from the segment's first byte */
+  uint64_t runs;      /* runs that gave at least one level */
+  uint32_t status;    /* BROTLI_AMD_UNRLE_*, or BROTLI_AMD_UNNULL_BAD_LENGTH */
+  uint32_t bits;      /* the k that was used */
+  uint64_t present;   /* delivered slots whose level is `level` */
+  uint64_t missing;   /* delivered present slots of rank >= values */
+  uint64_t values;    /* the V that was used */
+} BrotliAmdUnnullResult;
+
+/* n segments in DEVICE memory -- the level_lens[i] bytes at d_levels[i] are the levels, of fields of bits[i] bits, compared with levels[i];
+ * the value_counts[i] dense values of widths[i] bytes at d_values[i] go to the first caps[i] slots at d_dst[i], and their validity bits to
+ * d_valid[i] (NULL, or d_valid == NULL: no bitmap), by flags[i] (flags == NULL: all 0); results[i] says what segment i held; any alignment,
+ * any length, 0 included; n is not bound by the batch object's max_streams --: the launches run on hip_stream, and the call waits on that
+ * stream.  caps[i] == 0 only counts -- the walk alone --: d_dst[i], d_values[i] and value_counts[i] are not looked at but for the refusals
+ * above, and d_dst, d_values and value_counts themselves may be NULL where every capacity is 0.  n == 0 returns 0.  A negative value, and a
+ * BrotliAmdLastError text that names the segment and what was wrong, for a NULL batch, a NULL array (but flags, d_valid and the three just
+ * named) with n != 0, and everything in the list above: all of these are checked on the host in front of everything else, so nothing is
+ * launched and no byte is written. */
+BROTLI_DEC_API int BrotliAmdBatchUnnullSegments(BrotliAmdBatch* batch, uint32_t n, const void* const* d_levels, const size_t* level_lens,
+                                               const void* const* d_values, const uint64_t* value_counts, void* const* d_dst,
+                                               void* const* d_valid /* or NULL */, const uint64_t* caps, const uint8_t* bits, const uint32_t* levels,
+                                               const uint8_t* widths, const uint8_t* flags /* n entries, or NULL: all 0 */,
+                                               BrotliAmdUnnullResult* results, void* hip_stream);
+
+/* The same for the DELIVERED bytes of every stream of the last decode call on the object, by BrotliAmdBatchUnrleOutputs' rules for the three
+ * kinds of decode call, for skipped streams (d_dst[i] == NULL: none of the stream's parameters are looked at, its result is zeros) and for
+ * counting (d_dst == NULL or caps == NULL).  In two forms, stream by stream.  Where d_levels is NULL or d_levels[i] is NULL, stream i is a V1
+ * BODY -- prefix, levels, values --, with both flags implied.  Where d_levels[i] is set, this is the V2 case: the levels are the caller's
+ * uncompressed device bytes d_levels[i] of level_lens[i], with no flags, and the values are the whole of stream i's delivered bytes,
+ * V = floor(decoded_size / widths[i]).  A negative value, and a BrotliAmdLastError text, for a NULL batch, bits, levels, widths or results, a
+ * d_levels without level_lens, a refusal (nothing is launched), an object without a decode call, a last decode call that failed behind its
+ * argument checks (one of no streams returns 0), and a launch that BrotliAmdBatchWait has not been called for. */
+BROTLI_DEC_API int BrotliAmdBatchUnnullOutputs(BrotliAmdBatch* batch, void* const* d_dst /* or NULL */, void* const* d_valid /* or NULL */,
+                                              const uint64_t* caps /* or NULL */, const uint8_t* bits, const uint32_t* levels, const uint8_t* widths,
+                                              const void* const* d_levels /* or NULL */, const size_t* level_lens /* or NULL */,
+                                              BrotliAmdUnnullResult* results);
+
+/* Milliseconds the unnull kernels took in the last of the two calls above (HIP events around its launches together), */
+BROTLI_DEC_API float BrotliAmdBatchLastUnnullMs(BrotliAmdBatch* batch);
+/* and those of phase 1 (the walk), 2 (the counts), 3 (the carries) or 4 (the expansion) alone; another phase: 0. */
+BROTLI_DEC_API float BrotliAmdBatchLastUnnullPhaseMs(BrotliAmdBatch* batch, uint32_t phase);
+
+/* Test hook (no device needed): the four phases by the functions of csrc/brotli_unrle.h and csrc/brotli_unnull.h on the host.  It has
+ * BrotliAmdDebugUndictHost's shape, with a values buffer values[0, values_size) and a validity buffer valid[0, valid_size), each placed at
+ * its skew (0..15) past a 16-byte boundary in a room of its own: segment i's values are value_counts[i] elements of widths[i] bytes at
+ * value_offs[i] (not looked at with VALUES_FOLLOW), and its bitmap lies at valid_offs[i] (UINT64_MAX: it has none).  item_elems: the slots of
+ * an item, a multiple of 8, so that items own whole validity bytes (0: the device's, BrotliAmdDebugUnrleItemElems()); any other value is
+ * refused.  The items are taken in an order shuffled by order_seed, in the counting phase and again in the expansion (no result may depend on
+ * it).  0, results[0..n) filled, the slots' bytes of dst and the bitmaps' bytes of valid written; -1, a BrotliAmdLastError text and untouched
+ * buffers for a refusal, a skew > 15 or a segment, values or bitmap outside its buffer; -2 where a byte outside the slots and the bitmap
+ * bytes changed. */
+BROTLI_DEC_API int BrotliAmdDebugUnnullHost(uint32_t n, const uint8_t* src, size_t src_size, uint8_t* dst, size_t dst_size, const uint8_t* values,
+                                           size_t values_size, uint8_t* valid, size_t valid_size, const uint64_t* src_offs, const uint64_t* src_lens,
+                                           const uint64_t* dst_offs, const uint64_t* caps, const uint64_t* value_offs, const uint64_t* value_counts,
+                                           const uint64_t* valid_offs, const uint32_t* levels, const uint8_t* bits, const uint8_t* widths,
+                                           const uint8_t* flags /* or NULL */, uint32_t src_skew, uint32_t dst_skew, uint32_t values_skew,
+                                           uint32_t valid_skew, uint32_t item_elems, uint32_t order_seed, BrotliAmdUnnullResult* results);
 
 /* Milliseconds the last launch spent in the decode kernel (HIP events on the launch stream). */
 BROTLI_DEC_API float BrotliAmdBatchLastKernelMs(BrotliAmdBatch* batch);

@@ -54,6 +54,8 @@ BATCH_H_SYMBOLS = [
     "BrotliAmdDebugUndbpItemDeltas", "BrotliAmdDebugUndbpWalkChunk", "BrotliAmdDebugUndbpHost",
     "BrotliAmdBatchUndictSegments", "BrotliAmdBatchUndictOutputs", "BrotliAmdBatchLastUndictMs", "BrotliAmdBatchLastUndictPhaseMs",
     "BrotliAmdDebugUndictHost",
+    "BrotliAmdBatchUnnullSegments", "BrotliAmdBatchUnnullOutputs", "BrotliAmdBatchLastUnnullMs", "BrotliAmdBatchLastUnnullPhaseMs",
+    "BrotliAmdDebugUnnullHost",
 ]
 
 
@@ -121,6 +123,19 @@ class UndictResult(ctypes.Structure):  # BrotliAmdUndictResult: what a segment o
 
     def astuple(self):
         return (self.count, self.consumed, self.runs, self.status, self.bits, self.bad, self.first_bad)
+
+
+UNNULL_LENGTH_PREFIX, UNNULL_VALUES_FOLLOW = 1, 2  # BROTLI_AMD_UNNULL_*: a v1 data page's 4-byte length in front of the levels; the values lie behind them
+UNNULL_BAD_LENGTH = 5  # UnnullResult.status behind UNRLE_*: the length prefix is cut, or says more than there is
+UNNULL_NO_BITMAP = (1 << 64) - 1  # unnull_host: a segment's validity offset where it has no bitmap
+
+
+class UnnullResult(ctypes.Structure):  # BrotliAmdUnnullResult: what a segment of definition levels held, its present and missing slots and the values used (batch.h)
+    _fields_ = [("count", ctypes.c_uint64), ("consumed", ctypes.c_uint64), ("runs", ctypes.c_uint64), ("status", ctypes.c_uint32), ("bits", ctypes.c_uint32),
+                ("present", ctypes.c_uint64), ("missing", ctypes.c_uint64), ("values", ctypes.c_uint64)]
+
+    def astuple(self):
+        return (self.count, self.consumed, self.runs, self.status, self.bits, self.present, self.missing, self.values)
 
 
 def build(force=False):
@@ -244,7 +259,11 @@ def load_library():
             {"BrotliAmdBatchUndictSegments": (None, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
              "BrotliAmdBatchUndictOutputs": (None, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
              "BrotliAmdBatchLastUndictMs": (f32, [vp]), "BrotliAmdBatchLastUndictPhaseMs": (f32, [vp, u32]),
-             "BrotliAmdDebugUndictHost": (None, [u32, vp, sz, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, vp])}):
+             "BrotliAmdDebugUndictHost": (None, [u32, vp, sz, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, vp])},
+            {"BrotliAmdBatchUnnullSegments": (None, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+             "BrotliAmdBatchUnnullOutputs": (None, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+             "BrotliAmdBatchLastUnnullMs": (f32, [vp]), "BrotliAmdBatchLastUnnullPhaseMs": (f32, [vp, u32]),
+             "BrotliAmdDebugUnnullHost": (None, [u32, vp, sz, vp, sz, vp, sz, vp, sz] + [vp] * 11 + [u32] * 6 + [vp])}):
         if hasattr(L, next(iter(protos))):
             for name, (restype, argtypes) in protos.items():
                 if restype is not None:
@@ -465,6 +484,37 @@ def undict_host(src: bytes, dictionary: bytes, segs, dst_size, src_skew=0, dst_s
                                   *u64s, *u8s, src_skew, dst_skew, dict_skew, item_elems, order_seed, res) != 0:
         raise RuntimeError("BrotliAmdDebugUndictHost failed: " + last_error())
     return d_buf.raw[:dst_size], [res[i].astuple() for i in range(n)]
+
+
+def unnull_host(src: bytes, values: bytes, segs, dst_size, valid_size, src_skew=0, dst_skew=0, values_skew=0, valid_skew=0, item_elems=0, order_seed=0, fill=0,
+                valid_fill=0):
+    """BrotliAmdDebugUnnullHost: the dense `values` spread over nulls by the definition levels in `src`, by unrle's walk and the prefix, mask,
+    rank and validity functions of csrc/brotli_unnull.h on the host (no device needed).  segs: [(source offset, source length, destination
+    offset, capacity in slots, bits, width, flags, level, values offset, values count, validity offset or UNNULL_NO_BITMAP)]; the destination
+    has dst_size bytes and the bitmaps' buffer valid_size, all `fill` and `valid_fill` in front of the call (or, where those are bytes of that
+    size, those); the four buffers are placed at their skews past a 16-byte boundary; item_elems: the slots of an item, a multiple of 8 (0:
+    the device's, unrle_item_elems()); order_seed != 0 shuffles the order in which the items are taken, in both phases.
+    -> (the destination's bytes, the bitmaps' bytes, [(count, consumed, runs, status, bits, present, missing, values)])"""
+    L = load_library()
+    src, values, n = bytes(src), bytes(values), len(segs)
+
+    def before(f, size):
+        b = bytes(f) if isinstance(f, (bytes, bytearray)) else bytes([f]) * size
+        if len(b) != size:
+            raise ValueError("fill: %d bytes for a buffer of %d" % (len(b), size))
+        return b
+    s_buf = ctypes.create_string_buffer(src, max(1, len(src)))
+    d_buf = ctypes.create_string_buffer(before(fill, dst_size), max(1, dst_size))
+    v_buf = ctypes.create_string_buffer(values, max(1, len(values)))
+    b_buf = ctypes.create_string_buffer(before(valid_fill, valid_size), max(1, valid_size))
+    u64s = [(ctypes.c_uint64 * max(1, n))(*[s[k] if 0 <= s[k] < (1 << 64) else (1 << 64) - 1 for s in segs]) for k in (0, 1, 2, 3, 8, 9, 10)]
+    lv = (ctypes.c_uint32 * max(1, n))(*[s[7] for s in segs])
+    u8s = [(ctypes.c_uint8 * max(1, n))(*[s[k] if 0 <= s[k] <= 255 else bad for s in segs]) for k, bad in [(4, 255), (5, 0), (6, 255)]]
+    res = (UnnullResult * max(1, n))()
+    if L.BrotliAmdDebugUnnullHost(n, ctypes.addressof(s_buf), len(src), ctypes.addressof(d_buf), dst_size, ctypes.addressof(v_buf), len(values),
+                                  ctypes.addressof(b_buf), valid_size, *u64s, lv, *u8s, src_skew, dst_skew, values_skew, valid_skew, item_elems, order_seed, res) != 0:
+        raise RuntimeError("BrotliAmdDebugUnnullHost failed: " + last_error())
+    return d_buf.raw[:dst_size], b_buf.raw[:valid_size], [res[i].astuple() for i in range(n)]
 
 
 def undbp_item_deltas():
@@ -954,6 +1004,58 @@ class Batch:
         """milliseconds the undict kernels took in the last undict_segments / undict_outputs: both launches together, or phase 1 (the walk) or 2
         (the expansion with the lookup)"""
         return self._last_ms("Undict", phase)
+
+    def _ptr_column(self, ptrs, n, what):
+        """device addresses as the C calls take them: None stays NULL, and so does an entry that is None or 0"""
+        return self._column(ctypes.c_void_p, None if ptrs is None else [p or None for p in ptrs], n, None, what + ": one entry per segment or stream")
+
+    def unnull_segments(self, level_ptrs, level_lens, value_ptrs, value_counts, dst_ptrs, valid_ptrs, caps, bits, levels, widths, flags=None, stream=None):
+        """BrotliAmdBatchUnnullSegments: the level_lens[i] bytes at the device address level_ptrs[i] are DEFINITION LEVELS, unrle runs of fields of
+        bits[i] bits (0 .. 32); slot j of the first caps[i] is present where its level equals levels[i], and the present slots get the
+        value_counts[i] dense values of widths[i] bytes at value_ptrs[i] in order, every other slot 0, at dst_ptrs[i]; bit j & 7 of byte j >> 3
+        at valid_ptrs[i] (None: no bitmap; valid_ptrs=None: none has one) says whether slot j is present.  flags[i]: UNNULL_LENGTH_PREFIX,
+        UNNULL_VALUES_FOLLOW (None: all 0).  Any alignment, any length; out of place.  caps[i] == 0 only counts (dst_ptrs, value_ptrs and
+        value_counts may then be None).  Four launches and a wait on `stream`.
+        -> [(count, consumed, runs, status, bits, present, missing, values)]"""
+        n, col = len(level_ptrs), self._column
+        if len(level_lens) != n or len(caps) != n or len(levels) != n:
+            raise ValueError("level_ptrs, level_lens, caps and levels: one entry per segment each")
+        res = (UnnullResult * max(1, n))()
+        self._filter_call("BrotliAmdBatchUnnullSegments", n, col(ctypes.c_void_p, level_ptrs, n), col(ctypes.c_size_t, level_lens, n),
+                          self._ptr_column(value_ptrs, n, "value_ptrs"), col(ctypes.c_uint64, value_counts, n, (1 << 64) - 1, "value_counts: one entry per segment"),
+                          self._ptr_column(dst_ptrs, n, "dst_ptrs"), self._ptr_column(valid_ptrs, n, "valid_ptrs"), col(ctypes.c_uint64, caps, n, (1 << 64) - 1),
+                          self._byte_column(bits, n, "bits"), col(ctypes.c_uint32, levels, n, (1 << 32) - 1), self._byte_column(widths, n, "widths", 0),
+                          self._byte_column(flags, n, "flags"), res, stream)
+        return [res[i].astuple() for i in range(n)]
+
+    def unnull_outputs(self, dst_ptrs, valid_ptrs, caps, bits, levels, widths, level_ptrs=None, level_lens=None):
+        """BrotliAmdBatchUnnullOutputs: the delivered bytes of every stream of the last decode call on this object (after decode_device: once
+        wait() has returned), spread over nulls into the slots at dst_ptrs[i] (None or 0: the stream is skipped) and the bitmap at
+        valid_ptrs[i] (None: no bitmap).  Without level_ptrs, or where level_ptrs[i] is None, stream i is a V1 BODY: a 4-byte length, the
+        levels, the values.  Where level_ptrs[i] is set -- the V2 case -- the levels are the level_lens[i] uncompressed bytes at that device
+        address, and the stream's delivered bytes are the values.  dst_ptrs None or caps None: every stream is counted and nothing is written.
+        -> [(count, consumed, runs, status, bits, present, missing, values)], one per stream"""
+        n, col = self.out_n, self._column
+        if len(levels) != n or (caps is not None and len(caps) != n):
+            raise ValueError("caps and levels: one entry per stream of the last decode call each")
+        res = (UnnullResult * max(1, n))()
+        self._filter_call("BrotliAmdBatchUnnullOutputs", self._ptr_column(dst_ptrs, n, "dst_ptrs"), self._ptr_column(valid_ptrs, n, "valid_ptrs"),
+                          col(ctypes.c_uint64, caps, n, (1 << 64) - 1), self._byte_column(bits, n, "bits"), col(ctypes.c_uint32, levels, n, (1 << 32) - 1),
+                          self._byte_column(widths, n, "widths", 0), self._ptr_column(level_ptrs, n, "level_ptrs"),
+                          col(ctypes.c_size_t, level_lens, n, None, "level_lens: one entry per stream"), res)
+        return [res[i].astuple() for i in range(n)]
+
+    def count_levels_outputs(self, bits, level_ptrs=None, level_lens=None):
+        """unnull_outputs without destinations: how many levels every stream of the last decode call holds -- a v1 body behind its 4-byte
+        length, or the levels at level_ptrs[i] -- and where they end -> [(count, consumed, runs, status, bits, 0, 0, values)].  The way to size the
+        destinations of the call that writes; `consumed` of a v1 body is where its values -- or its dictionary-index body -- begin"""
+        n = self.out_n
+        return self.unnull_outputs(None, None, None, bits, [0] * n, [1] * n, level_ptrs, level_lens)
+
+    def last_unnull_ms(self, phase=None):
+        """milliseconds the unnull kernels took in the last unnull_segments / unnull_outputs: all launches together, or phase 1 (the walk), 2
+        (the counts), 3 (the carries) or 4 (the expansion)"""
+        return self._last_ms("Unnull", phase)
 
     def undbp_segments(self, src_ptrs, src_lens, dst_ptrs, caps, widths, flags=None, stream=None):
         """BrotliAmdBatchUndbpSegments: the DELTA_BINARY_PACKED stream in the src_lens[i] bytes at the device address src_ptrs[i] becomes elements

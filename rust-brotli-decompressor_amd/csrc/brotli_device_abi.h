@@ -216,6 +216,29 @@ typedef struct BrotliAmdUndictSeg {
   uint64_t dict_entries;
 } BrotliAmdUndictSeg;
 
+// One segment of an unnull call (csrc/brotli_unnull_kernels.hip, csrc/brotli_unnull.h): the len bytes at src are unrle runs of DEFINITION
+// LEVELS of `bits` bits -- behind a 4-byte length with flag bit 0 --, and the first `cap` of them become slots of `width` bytes at dst and
+// validity bits at valid (NULL: no bitmap): a slot whose level is `level` gets the next of the values_count dense values at `values` -- with
+// flag bit 1 what lies behind the runs in the segment itself --, every other slot 0.  Device addresses of any alignment.  Items, first_item and
+// the checkpoints are unrle's; every segment has a result (BrotliAmdUnnullResult, include/brotli/batch.h) and its runs' length behind the
+// table, and every item a checkpoint, a tile record and a carry.  No destination or bitmap range overlaps a source range, a values range or
+// another destination or bitmap range.  Nothing outside [dst, dst + min(count, cap) width) and [valid, valid + ceil(min(count, cap) / 8)) is
+// written; nothing outside the 16-byte-aligned spans around [src, src + len) and [values, values + values_count width) is read.
+typedef struct BrotliAmdUnnullSeg {
+  const uint8_t* src;
+  uint8_t* dst;
+  uint64_t len;
+  uint64_t cap;
+  uint64_t first_item;
+  uint32_t width;
+  uint32_t bits;
+  uint32_t flags;
+  uint32_t level;
+  const uint8_t* values;
+  uint64_t values_count;
+  uint8_t* valid;
+} BrotliAmdUnnullSeg;
+
 #ifdef __cplusplus
 }
 #endif

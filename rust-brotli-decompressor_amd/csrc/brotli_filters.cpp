@@ -7,6 +7,8 @@
 //   the counted path  unvarint, unrle, undbp, undict: a capacity per segment and a result per segment.  A traits struct a filter (its segment, its
 //                   result, its shape check, how an entry is made, how many items a capacity gives, whether it has a dictionary) under three
 //                   templates: counted_device, counted_segments, counted_outputs.
+//   unnull          beside the counted path: two sources, two destinations and a level a segment are columns of its own; it shares the counted
+//                   table's members and counted_device, and the four counted filters' templates do not know of it.
 //   the hooks       BrotliAmdDebug*Host run the device's functions of a filter's header (csrc/brotli_<filter>.h) on the host as the kernel's lanes
 //                   take them, for tests without a device.  They share the seeded orders, the serial carries, the argument checks and the
 //                   counted filters' closing block; each keeps its own phase loops.
@@ -16,6 +18,7 @@
 #include "brotli_undbp.h"
 #include "brotli_undict.h"
 #include "brotli_undelta.h"
+#include "brotli_unnull.h"
 #include "brotli_unrle.h"
 #include "brotli_unshuffle.h"
 #include "brotli_unvarint.h"
@@ -26,7 +29,8 @@
 // ev: the filter's events, recorded around and between its launches)
 typedef hipError_t FilterLaunch(const void* d_segs, uint32_t n, uint64_t units, void* d_scratch, hipStream_t stream, const hipEvent_t* ev);
 extern "C" FilterLaunch brotli_amd_launch_unshuffle, brotli_amd_launch_undelta, brotli_amd_launch_bitunshuffle, brotli_amd_launch_bitunpack,
-    brotli_amd_launch_unvarint, brotli_amd_launch_unrle, brotli_amd_launch_undbp, brotli_amd_launch_undict;
+    brotli_amd_launch_unvarint, brotli_amd_launch_unrle, brotli_amd_launch_undbp, brotli_amd_launch_undict, brotli_amd_launch_unnull;
+extern "C" uint64_t brotli_amd_unnull_scratch_bytes(uint64_t units, uint32_t n);
 extern "C" uint64_t brotli_amd_undelta_scratch_bytes(uint64_t units);
 extern "C" uint64_t brotli_amd_unvarint_scratch_bytes(uint64_t units, uint32_t n);
 extern "C" uint64_t brotli_amd_unrle_scratch_bytes(uint64_t units, uint32_t n);
@@ -75,6 +79,8 @@ const FilterDesc kFilter[kFilters] = {
      "brotli_amd_undbp kernels launch", brotli_amd_launch_undbp, brotli_amd_undbp_scratch_bytes, 5u},
     {"undict", {"hipMalloc(undict segments, results and checkpoints)", "hipMemcpyAsync(undict segments)", "hipStreamSynchronize(undict)"},
      "brotli_amd_undict kernels launch", brotli_amd_launch_undict, brotli_amd_undict_scratch_bytes, 3u},
+    {"unnull", {"hipMalloc(unnull segments, results, checkpoints and tiles)", "hipMemcpyAsync(unnull segments)", "hipStreamSynchronize(unnull)"},
+     "brotli_amd_unnull kernels launch", brotli_amd_launch_unnull, brotli_amd_unnull_scratch_bytes, 5u},
 };
 
 typedef std::vector<BrotliAmdUnshuffleSeg> Segs;
@@ -85,6 +91,7 @@ inline uint64_t units_of(const BrotliAmdUnvarintSeg& s) { return brotli_amd_seg_
 inline uint64_t units_of(const BrotliAmdUnrleSeg& s) { return 1u + brotli_amd_unrle_items(s.cap, brotli_amd_unrle_item_elems()); }
 inline uint64_t units_of(const BrotliAmdUndbpSeg& s) { return 1u + brotli_amd_undbp_items(s.cap, brotli_amd_undbp_item_deltas()); }
 inline uint64_t units_of(const BrotliAmdUndictSeg& s) { return 1u + brotli_amd_unrle_items(s.cap, brotli_amd_unrle_item_elems()); }
+inline uint64_t units_of(const BrotliAmdUnnullSeg& s) { return 1u + brotli_amd_unrle_items(s.cap, brotli_amd_unrle_item_elems()); }
 
 int invalid_arguments(Filter f) { g_last_error = std::string("invalid ") + kFilter[f].name + " arguments"; return -1; }
 
@@ -404,6 +411,44 @@ int counted_outputs(BrotliAmdBatch* b, void* const* d_dst, const Columns& c, typ
   return counted_device(b, t, results, outs.size(), b->last_stream);
 }
 
+// ---- unnull: a path of its own beside the counted one ----
+// It has two sources a segment -- levels and values --, two destinations -- slots and a bitmap -- and a level, so its columns are its own; what
+// it shares with the counted filters is the table (entries, where, items) and counted_device.  The four counted filters pay nothing for it.
+struct Unnull {
+  typedef BrotliAmdUnnullSeg Seg;
+  typedef BrotliAmdUnnullResult Result;
+  static constexpr Filter kId = kUnnull;
+  static constexpr bool kItems = true;
+};
+__attribute__((noinline)) bool refuse_unnull(const char* what, const BrotliAmdUnnullSeg& s, const char* who, size_t i) {
+  g_last_error = std::string("unnull ") + who + " " + std::to_string(i) + ": " + what + " (bits " + std::to_string(s.bits) + ", level " + std::to_string(s.level) + ", width " +
+                 std::to_string(s.width) + ", flags " + std::to_string(s.flags) + ", capacity " + std::to_string(s.cap) + ", values " + std::to_string(s.values_count) + ")";
+  return false;
+}
+// the shape check of one entry, in the order of batch.h's list (has_dst: the call has a destination for it)
+inline bool known_unnull(const BrotliAmdUnnullSeg& s, bool has_dst, const char* who, size_t i) {
+  const char* what = nullptr;
+  const bool follow = (s.flags & BROTLI_AMD_UNNULL_VALUES_FOLLOW) != 0u;
+  if (!brotli_amd_unshuffle_width_ok(s.width)) what = "width is not 1, 2, 4 or 8";
+  else if ((s.flags & ~BROTLI_AMD_UNNULL_FLAGS) != 0u) what = "unknown flag bits";
+  else if (follow && (s.flags & BROTLI_AMD_UNNULL_LENGTH_PREFIX) == 0u) what = "values that follow the levels without a length prefix";
+  else if (s.bits > BROTLI_AMD_UNRLE_MAX_BITS) what = "field of more than 32 bits";
+  else if (s.cap > BROTLI_AMD_UNNULL_MAX_CAP) what = "a capacity above 2^56 elements";
+  else if (s.values_count > BROTLI_AMD_UNNULL_MAX_VALUES) what = "more than 2^56 values";
+  else if (s.cap != 0u && !has_dst) what = "no destination for a capacity that is not 0";
+  else if (!follow && s.cap != 0u && s.values_count != 0u && !s.values) what = "no values for a count and a capacity that are not 0";
+  return !what || refuse_unnull(what, s, who, i);
+}
+// entry i of a call into its table: checked, then given its place among the items
+inline bool push_unnull(CountedTable<Unnull>* t, BrotliAmdUnnullSeg s, size_t i, bool has_dst, const char* who) {
+  if (!known_unnull(s, has_dst, who, i)) return false;
+  s.first_item = t->items;
+  t->segs.push_back(s);
+  t->where.push_back(i);
+  t->items += brotli_amd_unrle_items(s.cap, brotli_amd_unrle_item_elems());
+  return true;
+}
+
 // ---- what the hooks share ----
 // The hooks run the device's functions on the host over every unit of a segment, source and destination each in a SkewedRoom (brotli_host.h).
 // a hook's buffers and skews
@@ -556,6 +601,54 @@ extern "C" int BrotliAmdBatchUndictOutputs(BrotliAmdBatch* b, void* const* d_dst
   return counted_outputs<Undict>(b, d_dst, Columns{caps, bits, widths, flags, d_dicts, dict_entries}, results, dict_streams);
 }
 
+extern "C" int BrotliAmdBatchUnnullSegments(BrotliAmdBatch* b, uint32_t n, const void* const* d_levels, const size_t* level_lens, const void* const* d_values,
+                                            const uint64_t* value_counts, void* const* d_dst, void* const* d_valid, const uint64_t* caps, const uint8_t* bits,
+                                            const uint32_t* levels, const uint8_t* widths, const uint8_t* flags, BrotliAmdUnnullResult* results, void* hip_stream) {
+  if (!b || (n && (!d_levels || !level_lens || !caps || !bits || !levels || !widths || !results))) return invalid_arguments(kUnnull);
+  no_times(b, kUnnull);
+  CountedTable<Unnull> t;
+  t.reserve(n);
+  for (uint32_t i = 0; i < n; i++) {
+    void* dst = d_dst ? d_dst[i] : nullptr;   // (no array of destinations: a call that counts, where every capacity is 0)
+    const uint32_t f = flags ? flags[i] : 0u;
+    // (no arrays of values: the same, but for segments whose values follow their levels)
+    if (caps[i] != 0u && (f & BROTLI_AMD_UNNULL_VALUES_FOLLOW) == 0u && (!d_values || !value_counts)) return invalid_arguments(kUnnull);
+    const BrotliAmdUnnullSeg s = {static_cast<const uint8_t*>(d_levels[i]), static_cast<uint8_t*>(dst), level_lens[i], caps[i], 0u, widths[i], bits[i], f, levels[i],
+                                  static_cast<const uint8_t*>(d_values ? d_values[i] : nullptr), value_counts ? value_counts[i] : 0u,
+                                  static_cast<uint8_t*>(d_valid ? d_valid[i] : nullptr)};
+    if (!push_unnull(&t, s, i, dst != nullptr, "segment")) return -1;
+  }
+  return counted_device(b, t, results, n, static_cast<hipStream_t>(hip_stream));
+}
+extern "C" int BrotliAmdBatchUnnullOutputs(BrotliAmdBatch* b, void* const* d_dst, void* const* d_valid, const uint64_t* caps, const uint8_t* bits, const uint32_t* levels,
+                                           const uint8_t* widths, const void* const* d_levels, const size_t* level_lens, BrotliAmdUnnullResult* results) {
+  if (!b || !bits || !levels || !widths || !results || (d_levels && !level_lens)) return invalid_arguments(kUnnull);
+  no_times(b, kUnnull);
+  std::vector<DeliveredBytes> outs;
+  if (!delivered_outputs(b, &outs)) return -1;
+  const bool count_only = !d_dst || !caps;   // every stream is counted and nothing is written
+  CountedTable<Unnull> t;
+  t.reserve(outs.size());
+  for (size_t i = 0; i < outs.size(); i++) {
+    if (!count_only && d_dst[i] == nullptr) continue;   // skipped: none of its parameters are looked at
+    uint8_t* dst = count_only ? nullptr : static_cast<uint8_t*>(d_dst[i]);
+    uint8_t* valid = count_only || !d_valid ? nullptr : static_cast<uint8_t*>(d_valid[i]);
+    const uint64_t cap = count_only ? 0u : caps[i];
+    const uint32_t w = widths[i];
+    BrotliAmdUnnullSeg s;
+    if (d_levels && d_levels[i]) {   // v2: the caller's levels, and the stream's bytes as the values (a width that is none is refused by the shape check)
+      s = BrotliAmdUnnullSeg{static_cast<const uint8_t*>(d_levels[i]), dst, level_lens[i], cap, 0u, w, bits[i], 0u, levels[i], outs[i].ptr,
+                             brotli_amd_unshuffle_width_ok(w) ? outs[i].len / w : 0u, valid};
+    } else {   // a v1 body: prefix, levels, values
+      s = BrotliAmdUnnullSeg{outs[i].ptr, dst, outs[i].len, cap, 0u, w, bits[i], BROTLI_AMD_UNNULL_FLAGS, levels[i], nullptr, 0u, valid};
+    }
+    if (!push_unnull(&t, s, i, !count_only, "stream")) return -1;
+  }
+  return counted_device(b, t, results, outs.size(), b->last_stream);
+}
+
+extern "C" float BrotliAmdBatchLastUnnullMs(BrotliAmdBatch* b) { return b ? b->filter[kUnnull].ms : 0.0f; }
+extern "C" float BrotliAmdBatchLastUnnullPhaseMs(BrotliAmdBatch* b, uint32_t phase) { return phase_ms(b, kUnnull, phase); }
 extern "C" float BrotliAmdBatchLastUnshuffleMs(BrotliAmdBatch* b) { return b ? b->filter[kUnshuffle].ms : 0.0f; }
 extern "C" float BrotliAmdBatchLastUndeltaMs(BrotliAmdBatch* b) { return b ? b->filter[kUndelta].ms : 0.0f; }
 extern "C" float BrotliAmdBatchLastUndeltaPhaseMs(BrotliAmdBatch* b, uint32_t phase) { return phase_ms(b, kUndelta, phase); }
@@ -849,4 +942,83 @@ extern "C" int BrotliAmdDebugUndictHost(uint32_t n, const uint8_t* src, size_t s
   SeededOrder(order_seed).shuffle(&order);
   for (const auto& it : order) brotli_amd_undict_host_item(segs[it.first], &got[it.first], ckpts[it.first][it.second], it.second, item_elems);
   return counted_hook_result(kUndict, droom, n, dst, dst_size, dst_offs, caps, widths, got, results);
+}
+
+// Unnull's four phases over n segments given as offsets into one source, one destination, one values and one validity buffer, each buffer in its
+// room: every segment's walk behind its prefix, the items' counts in an order shuffled by the seed, the carries as undelta's hook takes them,
+// and the items' slots and validity bytes in another shuffled order, each adding its present and missing slots to its segment's result.
+extern "C" int BrotliAmdDebugUnnullHost(uint32_t n, const uint8_t* src, size_t src_size, uint8_t* dst, size_t dst_size, const uint8_t* values, size_t values_size,
+                                        uint8_t* valid, size_t valid_size, const uint64_t* src_offs, const uint64_t* src_lens, const uint64_t* dst_offs,
+                                        const uint64_t* caps, const uint64_t* value_offs, const uint64_t* value_counts, const uint64_t* valid_offs, const uint32_t* levels,
+                                        const uint8_t* bits, const uint8_t* widths, const uint8_t* flags, uint32_t src_skew, uint32_t dst_skew, uint32_t values_skew,
+                                        uint32_t valid_skew, uint32_t item_elems, uint32_t order_seed, BrotliAmdUnnullResult* results) {
+  if ((n && (!src_offs || !src_lens || !dst_offs || !caps || !value_offs || !value_counts || !valid_offs || !levels || !bits || !widths || !results)) ||
+      !rooms_ok(src, src_size, dst, dst_size, src_skew, dst_skew) || !rooms_ok(values, values_size, valid, valid_size, values_skew, valid_skew))
+    return invalid_arguments(kUnnull);
+  if (item_elems == 0u) item_elems = brotli_amd_unrle_item_elems();
+  if (!brotli_amd_unnull_item_ok(item_elems)) { g_last_error = "invalid unnull arguments: an item that is no multiple of 8 slots"; return -1; }
+  SkewedRoom sroom(src_size, src_skew, 0xA5), droom(dst_size, dst_skew, 0x5A), vroom(values_size, values_skew, 0x3C), broom(valid_size, valid_skew, 0xC3);
+  std::vector<BrotliAmdUnnullSeg> segs;
+  for (uint32_t i = 0; i < n; i++) {
+    const bool has_valid = valid_offs[i] != ~(uint64_t)0;
+    const BrotliAmdUnnullSeg s = {reinterpret_cast<const uint8_t*>((uintptr_t)(sroom.at() + src_offs[i])), reinterpret_cast<uint8_t*>((uintptr_t)(droom.at() + dst_offs[i])),
+                                  src_lens[i], caps[i], 0u, widths[i], bits[i], flags ? flags[i] : 0u, levels[i],
+                                  reinterpret_cast<const uint8_t*>((uintptr_t)(vroom.at() + value_offs[i])), value_counts[i],
+                                  has_valid ? reinterpret_cast<uint8_t*>((uintptr_t)(broom.at() + valid_offs[i])) : nullptr};
+    if (!known_unnull(s, true, "segment", i)) return -1;
+    if (!lies_in(src_offs[i], src_lens[i], src_size) || dst_offs[i] > dst_size || (has_valid && valid_offs[i] > valid_size)) return outside_buffer(kUnnull);
+    if ((s.flags & BROTLI_AMD_UNNULL_VALUES_FOLLOW) == 0u && value_counts[i] != 0u && !lies_in(value_offs[i], value_counts[i] * widths[i], values_size)) {
+      g_last_error = "invalid unnull arguments: values outside their buffer";
+      return -1;
+    }
+    segs.push_back(s);
+  }
+  sroom.put(src, src_size);
+  droom.put(dst, dst_size);
+  vroom.put(values, values_size);
+  broom.put(valid, valid_size);
+  // the walks: they write nothing, and say how much room every segment needs
+  std::vector<BrotliAmdUnnullResult> got(n);
+  std::vector<BrotliAmdUnnullRuns> runs(n);
+  std::vector<uint64_t> pre(n + 1u, 0u);
+  std::vector<BrotliAmdUnrleCheckpoint> ckpts;
+  for (uint32_t i = 0; i < n; i++) {
+    // (the items of the slots there is room for: the walk marks no others, and a capacity of 2^56 needs no table of its own)
+    const uint64_t room = (dst_size - dst_offs[i]) / widths[i];
+    segs[i].cap = std::min<uint64_t>(caps[i], room + 1u);
+    segs[i].first_item = pre[i];
+    pre[i + 1u] = pre[i] + brotli_amd_unrle_items(segs[i].cap, item_elems);
+    ckpts.resize(pre[i + 1u], BrotliAmdUnrleCheckpoint{BROTLI_AMD_UNRLE_NONE, BROTLI_AMD_UNRLE_NONE});
+    got[i] = brotli_amd_unnull_host_walk(segs[i], item_elems, ckpts.data() + pre[i], &runs[i]);
+    const uint64_t m = std::min(got[i].count, caps[i]);
+    if (m > room || (segs[i].valid && (m + 7u) / 8u > valid_size - valid_offs[i])) return outside_buffer(kUnnull);
+  }
+  droom.snapshot();
+  broom.snapshot();
+  const uint64_t items = pre[n];
+  std::vector<uint64_t> order = first_numbers(items);
+  SeededOrder seeded(order_seed);
+  std::vector<BrotliAmdUndeltaTile> tiles(items);
+  std::vector<uint32_t> masks((item_elems + BROTLI_AMD_UNNULL_LANE_SLOTS - 1u) / BROTLI_AMD_UNNULL_LANE_SLOTS);
+  seeded.shuffle(&order);
+  for (uint64_t g : order) {
+    const uint32_t i = brotli_amd_seg_find(pre.data(), n, g);
+    std::fill(masks.begin(), masks.end(), 0u);
+    tiles[g] = brotli_amd_unnull_host_count(segs[i], runs[i], got[i], ckpts[g], g - pre[i], item_elems, masks.data());
+  }
+  const std::vector<uint64_t> carries = carries_of(tiles);
+  seeded.shuffle(&order);
+  for (uint64_t g : order) {
+    const uint32_t i = brotli_amd_seg_find(pre.data(), n, g);
+    std::fill(masks.begin(), masks.end(), 0u);
+    brotli_amd_unnull_host_expand(segs[i], runs[i], &got[i], ckpts[g], g - pre[i], item_elems, carries[g], masks.data());
+  }
+  // no byte outside every segment's validity bytes may have changed; the slots' room is judged by the counted hooks' closing block
+  std::vector<uint8_t> inside(valid_size, 0);
+  for (uint32_t i = 0; i < n; i++)
+    if (segs[i].valid) std::fill(inside.begin() + valid_offs[i], inside.begin() + valid_offs[i] + (std::min(got[i].count, caps[i]) + 7u) / 8u, 1);
+  if (!broom.changed_inside_only([&](size_t i) { return i < valid_size && inside[i]; })) { g_last_error = "unnull wrote outside its bitmap"; return -2; }
+  const int r = counted_hook_result(kUnnull, droom, n, dst, dst_size, dst_offs, caps, widths, got, results);
+  if (r == 0) broom.get(valid, 0u, valid_size);
+  return r;
 }

@@ -22,7 +22,9 @@ INT32 and INT64 pages, the lengths of byte arrays -- says "dbp"; one call decode
 a stream that did not end well or held another number of values than its shape says is refused; bytes behind its last block are not judged.
 A stream that is a DICTIONARY-INDEX PAGE BODY -- Parquet's RLE_DICTIONARY: a width byte and then runs of indices -- names its dictionary, another
 stream of the same call or a tensor, and one call turns all such streams into their VALUES (Batch.undict_outputs): the indices never reach
-memory, and a stream with an index outside its dictionary is refused."""
+memory, and a stream with an index outside its dictionary is refused.  A stream that is the body of a NULLABLE column's data page -- definition
+levels and the dense values that are there -- says ("nulls", level): one call spreads the values of all such streams over their nulls
+(Batch.unnull_outputs), and the stream's entry is the pair (tensor, validity bitmap)."""
 import collections
 
 import torch
@@ -37,25 +39,27 @@ def _numel(shape):
     return n
 
 
-FILTERS = ("shuffle", "delta", "bitshuffle", "bitpack", "varint", "rle", "dbp", "dict")
+FILTERS = ("shuffle", "delta", "bitshuffle", "bitpack", "varint", "rle", "dbp", "dict", "nulls")
 BITPACK_OPTIONS = {"big": 1, "signed": 2}   # BITUNPACK_MSB_FIRST, BITUNPACK_SIGNED
 VARINT_OPTIONS = {"zigzag": 1}              # UNVARINT_ZIGZAG
 RLE_WIDTH_BYTE = 1                          # UNRLE_WIDTH_BYTE, UNDICT_WIDTH_BYTE
 DICT_NO_STREAM = 0xFFFFFFFF                 # UNDICT_NO_STREAM
 DBP_STATUS = ("ok", "a header that is none", "a miniblock of more than 64 bits", "blocks that the stream's end cuts")
-RLE_STATUS = ("ok", "a header of more than five bytes", "a run of no values", "runs that the stream's end cuts", "a width byte that is none")
+RLE_STATUS = ("ok", "a header of more than five bytes", "a run of no values", "runs that the stream's end cuts", "a width byte that is none",
+              "a length in front of the levels that is cut or says more than there is")
 
 
 # What a wanted stream's spec says: the slot's bytes, the tensor's dtype and shape, the element width, the names of its filters, bitshuffle's block
 # and bitpack's (k, flags) -- (1, 0) where the stream is not packed, as for a stream that is not wanted --, varint's flags, rle's (k, flags) --
-# (0, 0) where the stream has no runs --, dict's dictionary: a stream's number or a tensor (None where the stream has none)
-_Stream = collections.namedtuple("_Stream", "want dtype shape item filters block pack varint rle dict")
+# (0, 0) where the stream has no runs --, dict's dictionary: a stream's number or a tensor (None where the stream has none), nulls' (level, the
+# levels' tensor or None: they lie in the stream) (None where the stream has no levels)
+_Stream = collections.namedtuple("_Stream", "want dtype shape item filters block pack varint rle dict nulls")
 
 
 def _parse_spec(i, spec, size):
     """spec of stream i, which delivered `size` bytes -> _Stream; ValueError, naming the stream, for what outputs_as_tensors refuses"""
     dtype, shape = spec[0], spec[1]
-    flt, block, pack, varint, rle, dictionary = [], 0, None, 0, None, None
+    flt, block, pack, varint, rle, dictionary, nulls = [], 0, None, 0, None, None, None
     for name in (tuple(spec[2]) if len(spec) > 2 else ("shuffle",)):
         if isinstance(name, (tuple, list)) and len(name) == 2 and name[0] == "bitshuffle":   # ("bitshuffle", block_elems)
             name, block = name[0], int(name[1])
@@ -87,6 +91,14 @@ def _parse_spec(i, spec, size):
             name, dictionary = name[0], name[1]
         elif name == "dict":
             raise ValueError("stream %d: \"dict\" without its dictionary: (\"dict\", j) or (\"dict\", tensor)" % i)
+        if isinstance(name, (tuple, list)) and len(name) >= 1 and name[0] == "nulls":   # ("nulls", level) or ("nulls", level, levels_tensor)
+            if len(name) not in (2, 3) or isinstance(name[1], bool) or not isinstance(name[1], int) or not 0 <= name[1] < (1 << 32) or \
+                    (len(name) == 3 and not isinstance(name[2], torch.Tensor)):
+                raise ValueError("stream %d: (\"nulls\", level) names the definition level of a value that is there, 0 .. 2^32 - 1, "
+                                 "(\"nulls\", level, tensor) the levels' bytes as well, and nothing else" % i)
+            name, nulls = name[0], (int(name[1]), name[2] if len(name) == 3 else None)
+        elif name == "nulls":
+            raise ValueError("stream %d: \"nulls\" without its level: (\"nulls\", level) or (\"nulls\", level, tensor)" % i)
         if name in VARINT_OPTIONS and flt and flt[-1] == "varint":   # ("varint", "zigzag") as the spec's filters: the option right behind its filter
             varint |= VARINT_OPTIONS[name]
             continue
@@ -96,6 +108,8 @@ def _parse_spec(i, spec, size):
     flt = tuple(flt)
     if "dict" in flt and len(flt) != 1:
         raise ValueError("stream %d: \"dict\" stands alone in a spec: the values come out of the dictionary as they are" % i)
+    if "nulls" in flt and len(flt) != 1:
+        raise ValueError("stream %d: \"nulls\" stands alone in a spec: the values go to their slots as they are" % i)
     if "shuffle" in flt and "bitshuffle" in flt:
         raise ValueError("stream %d: \"shuffle\" and \"bitshuffle\" in one spec: an array goes through one of them" % i)
     if pack is not None and ("shuffle" in flt or "bitshuffle" in flt):
@@ -117,7 +131,7 @@ def _parse_spec(i, spec, size):
         stored = (_numel(shape) * pack[0] + 7) // 8
         if size != stored:
             raise ValueError("stream %d: %d delivered bytes, but %d fields of %d bits (shape %s) are %d" % (i, size, _numel(shape), pack[0], shape, stored))
-    elif "varint" in flt or "rle" in flt or "dbp" in flt or "dict" in flt:
+    elif "varint" in flt or "rle" in flt or "dbp" in flt or "dict" in flt or "nulls" in flt:
         pass   # (how many integers the delivered bytes hold is the call's to say: outputs_as_tensors checks its result)
     elif size != want:
         raise ValueError("stream %d: %d delivered bytes, but %s of shape %s is %d" % (i, size, dtype, shape, want))
@@ -126,7 +140,10 @@ def _parse_spec(i, spec, size):
     if isinstance(dictionary, torch.Tensor) and (dictionary.dtype != dtype or dictionary.dim() != 1 or not dictionary.is_contiguous() or not dictionary.is_cuda):
         raise ValueError("stream %d: its dictionary is a %s tensor of shape %s%s, not a contiguous 1-D device tensor of %s" %
                          (i, dictionary.dtype, tuple(dictionary.shape), "" if dictionary.is_cuda else " on the host", dtype))
-    return _Stream(want, dtype, shape, item, flt, block, pack or (1, 0), varint, rle or (0, 0), dictionary)
+    if nulls is not None and nulls[1] is not None and (nulls[1].dtype != torch.uint8 or nulls[1].dim() != 1 or not nulls[1].is_contiguous() or not nulls[1].is_cuda):
+        raise ValueError("stream %d: its levels are a %s tensor of shape %s%s, not a contiguous 1-D device tensor of torch.uint8" %
+                         (i, nulls[1].dtype, tuple(nulls[1].shape), "" if nulls[1].is_cuda else " on the host"))
+    return _Stream(want, dtype, shape, item, flt, block, pack or (1, 0), varint, rle or (0, 0), dictionary, nulls)
 
 
 def outputs_as_tensors(batch, specs):
@@ -179,6 +196,17 @@ def outputs_as_tensors(batch, specs):
                                               values than numel are the last group's padding and are not judged
         (dtype, shape, (("dict", tensor),))   ... whose dictionary is a 1-D contiguous device tensor of the dtype; "dict" with any other
                                               filter raises ValueError, and so does a j that is the stream itself or no stream of the call
+        (dtype, shape, (("nulls", level),))   the body of a NULLABLE column's v1 data page: a 4-byte length, the definition levels -- runs of
+                                              fields of level.bit_length() bits --, and behind them the dense values of the rows that are
+                                              there, PLAIN.  ONE Batch.unnull_outputs call for all such streams spreads the values over the
+                                              rows: a row whose level is `level` gets the next value, every other row 0.  The stream's entry
+                                              in the result is the PAIR (tensor, valid), valid being a uint8 tensor of ceil(numel / 8) bytes,
+                                              Arrow's validity bitmap (bit i & 7 of byte i >> 3).  ValueError, naming the stream and what was
+                                              found, where the levels do not end well (a status that is not OK), hold another number of rows
+                                              than numel, a row that is there has no value, or values are left over
+        (dtype, shape, (("nulls", level, levels),))  ... of a v2 data page: the levels are the caller's, a contiguous 1-D uint8 device tensor
+                                              (a v2 page keeps them outside the compressed body), and the stream holds the dense values
+                                              alone; "nulls" with any other filter raises ValueError
     "varint" together with "shuffle", "bitshuffle" or "bitpack" in one spec raises ValueError, naming the stream; so does "rle" together with
     any of those four.
     "shuffle" together with "bitshuffle", and "bitpack" together with either, in one spec raises ValueError, naming the stream; so does a k outside
@@ -196,6 +224,8 @@ def outputs_as_tensors(batch, specs):
         offs.append(total)
         if st is not None:
             total = (total + st.want + SLOT_ALIGN - 1) // SLOT_ALIGN * SLOT_ALIGN
+            if st.nulls is not None:   # the bitmap has a slot of its own behind the rows'
+                total = (total + (_numel(st.shape) + 7) // 8 + SLOT_ALIGN - 1) // SLOT_ALIGN * SLOT_ALIGN
     buf = torch.empty(total + SLOT_ALIGN, dtype=torch.uint8, device="cuda")
     skip = -buf.data_ptr() % SLOT_ALIGN   # (the allocator's blocks are aligned far beyond this; nothing here depends on it)
     buf = buf[skip:skip + total]
@@ -215,14 +245,15 @@ def outputs_as_tensors(batch, specs):
     runs = [i for i in wanted if "rle" in streams[i].filters]
     blocks = [i for i in wanted if "dbp" in streams[i].filters]
     dicts = [i for i in wanted if "dict" in streams[i].filters]
+    nullable = [i for i in wanted if "nulls" in streams[i].filters]
     for i in dicts:
         j = streams[i].dict
         if not isinstance(j, torch.Tensor) and (j == i or not 0 <= j < len(sizes)):
             raise ValueError("stream %d: its dictionary stream %d is %s" % (i, j, "the stream itself" if j == i else "none of the %d streams of the last decode call" % len(sizes)))
     # deltas only: every other wanted stream that is neither of bit planes nor of packed fields is the unshuffle call's; without "shuffle" it is
     # a copy -- width 1
-    plain = [i for i in wanted if i not in bits and i not in packed and i not in varints and i not in runs and i not in blocks and i not in dicts and "shuffle" not in streams[i].filters and "delta" in streams[i].filters]
-    batch.unshuffle_outputs(only([i for i in wanted if i not in plain and i not in bits and i not in packed and i not in varints and i not in runs and i not in blocks and i not in dicts]),
+    plain = [i for i in wanted if i not in bits and i not in packed and i not in varints and i not in runs and i not in blocks and i not in dicts and i not in nullable and "shuffle" not in streams[i].filters and "delta" in streams[i].filters]
+    batch.unshuffle_outputs(only([i for i in wanted if i not in plain and i not in bits and i not in packed and i not in varints and i not in runs and i not in blocks and i not in dicts and i not in nullable]),
                             [st.item if st is not None and "shuffle" in st.filters else 1 for st in streams])
     if bits:    # bit planes: from the outputs straight into the slots
         batch.bitunshuffle_outputs(only(bits), widths, [0 if st is None else st.block for st in streams])
@@ -277,9 +308,33 @@ def outputs_as_tensors(batch, specs):
             if bad != 0:
                 raise ValueError("stream %d: %d of its %d values have an index outside its dictionary of %d entries, the first of them value %d" %
                                  (i, bad, _numel(streams[i].shape), entries[i], first_bad))
+    valid_at = {i: offs[i] + (streams[i].want + SLOT_ALIGN - 1) // SLOT_ALIGN * SLOT_ALIGN for i in nullable}   # the bitmaps' slots
+    if nullable:   # levels and dense values: the rows and their bitmaps from the outputs straight into the slots; every row that is there has a value
+        n = len(streams)
+        level_of = [streams[i].nulls[0] if i in valid_at else 0 for i in range(n)]
+        lv = [streams[i].nulls[1] if i in valid_at else None for i in range(n)]
+        res = batch.unnull_outputs(only(nullable), [base + valid_at[i] if i in valid_at else None for i in range(n)], [0 if st is None else _numel(st.shape) for st in streams],
+                                   [v.bit_length() for v in level_of], level_of, widths,
+                                   [None if t is None else t.data_ptr() or 1 for t in lv] if any(t is not None for t in lv) else None,
+                                   [0 if t is None else t.numel() for t in lv] if any(t is not None for t in lv) else None)
+        for i in nullable:
+            count, consumed, _, status, k, present, missing, values = res[i]
+            numel = _numel(streams[i].shape)
+            if status != 0:
+                raise ValueError("stream %d: %s (status %d) after %d levels in %d of their bytes, levels of %d bits" %
+                                 (i, RLE_STATUS[status] if status < len(RLE_STATUS) else "an unknown status", status, count, consumed, k))
+            if count != numel:
+                raise ValueError("stream %d: %d levels, but shape %s is %d elements" % (i, count, streams[i].shape, numel))
+            if missing != 0:
+                raise ValueError("stream %d: %d of its %d rows that are there have no value: the stream holds %d values" % (i, missing, present, values))
+            if present != values:
+                raise ValueError("stream %d: %d values for the %d rows that are there: values are left over" % (i, values, present))
     if plain:   # deltas only: from the outputs straight into the slots
         batch.undelta_outputs(only(plain), widths)
     both = [i for i in wanted if i not in plain and "delta" in streams[i].filters]
     if both:    # in place over the slots, which are 64-byte aligned
         batch.undelta_segments([at[i] for i in both], [at[i] for i in both], [streams[i].want for i in both], [widths[i] for i in both])
-    return [None if st is None else buf[off:off + st.want].view(st.dtype).reshape(st.shape) for st, off in zip(streams, offs)]
+    out = [None if st is None else buf[off:off + st.want].view(st.dtype).reshape(st.shape) for st, off in zip(streams, offs)]
+    for i in nullable:
+        out[i] = (out[i], buf[valid_at[i]:valid_at[i] + (_numel(streams[i].shape) + 7) // 8])
+    return out
