@@ -509,6 +509,78 @@ int counted_hook_result(Filter f, const SkewedRoom& droom, uint32_t n, uint8_t* 
   return 0;
 }
 
+// The destination's side of the arguments of a hook whose segments are walked and then taken item by item.
+struct ItemHookDst { uint8_t* dst; size_t dst_size; const uint64_t* dst_offs; const uint64_t* caps; const uint8_t* widths; };
+
+// What such a hook's walks leave -- the items' prefix array, and every item's checkpoint --, and the order its items are taken in.
+template <class Checkpoint>
+struct HookItems {
+  std::vector<uint64_t> pre;
+  std::vector<Checkpoint> ckpts;
+  // Every segment's walk: walk(i, ckpts) -> got[i].  It writes nothing, and says how much room the segment needs; fits(i, m): the segment's other
+  // rooms hold its m elements.  A segment's capacity becomes the elements there is room for and one more: the walk marks the items of no
+  // others, and a capacity of 2^56 needs no table of its own.  items_of(cap): the items of a capacity.
+  template <class Seg, class Result, class Items, class Walk, class Fits>
+  int walks(Filter f, std::vector<Seg>& segs, std::vector<Result>& got, const ItemHookDst& d, Items items_of, Walk walk, Fits fits) {
+    static_assert(BROTLI_AMD_UNDBP_NONE == BROTLI_AMD_UNRLE_NONE, "one checkpoint of an item beyond count");
+    pre.assign(segs.size() + 1u, 0u);
+    for (uint32_t i = 0; i < segs.size(); i++) {
+      const uint64_t room = (d.dst_size - d.dst_offs[i]) / d.widths[i];
+      segs[i].cap = std::min<uint64_t>(d.caps[i], room + 1u);
+      segs[i].first_item = pre[i];
+      pre[i + 1u] = pre[i] + items_of(segs[i].cap);
+      ckpts.resize(pre[i + 1u], Checkpoint{BROTLI_AMD_UNRLE_NONE, BROTLI_AMD_UNRLE_NONE});
+      got[i] = walk(i, ckpts.data() + pre[i]);
+      const uint64_t m = std::min(got[i].count, d.caps[i]);
+      if (m > room || !fits(i, m)) return outside_buffer(f);
+    }
+    return 0;
+  }
+  // each(i, checkpoint, j, g) for item j of segment i, the g-th of all, in the order that `seeded` shuffles next
+  template <class Each>
+  void shuffled(SeededOrder* seeded, Each each) const {
+    std::vector<uint64_t> order = first_numbers(pre.back());
+    seeded->shuffle(&order);
+    for (uint64_t g : order) {
+      const uint32_t i = brotli_amd_seg_find(pre.data(), (uint32_t)pre.size() - 1u, g);
+      each(i, ckpts[g], g - pre[i], g);
+    }
+  }
+};
+
+// A hook of two phases (unrle, undict) over segs, whose capacities are the caller's: the walks, then the items of all segments in an order
+// shuffled by the seed: item(i, &result, checkpoint, j).
+template <class Seg, class Result, class Walk, class Item>
+int walk_items_hook(Filter f, std::vector<Seg>& segs, SkewedRoom& droom, const ItemHookDst& d, uint32_t item_elems, uint32_t order_seed, Walk walk, Item item,
+                    Result* results) {
+  std::vector<Result> got(segs.size());
+  HookItems<BrotliAmdUnrleCheckpoint> items;
+  const int walked = items.walks(f, segs, got, d, [&](uint64_t cap) { return brotli_amd_unrle_items(cap, item_elems); }, walk, [](uint32_t, uint64_t) { return true; });
+  if (walked != 0) return walked;
+  droom.snapshot();
+  SeededOrder seeded(order_seed);
+  items.shuffled(&seeded, [&](uint32_t i, BrotliAmdUnrleCheckpoint cp, uint64_t j, uint64_t) { item(i, &got[i], cp, j); });
+  return counted_hook_result(f, droom, (uint32_t)segs.size(), d.dst, d.dst_size, d.dst_offs, d.caps, d.widths, got, results);
+}
+
+// The phases of a hook of four (undbp, unnull) up to its stores: the walks, the items' records in an order shuffled by the seed --
+// count(i, checkpoint, j) --, the carries as undelta's hook takes them, and the items' stores in another shuffled order:
+// store(i, checkpoint, j, carry_in).  The caller ends with counted_hook_result.
+template <class Checkpoint, class Seg, class Result, class Items, class Walk, class Fits, class Count, class Store>
+int walk_count_store_hook(Filter f, std::vector<Seg>& segs, std::vector<Result>& got, SkewedRoom& droom, const ItemHookDst& d, uint32_t order_seed, Items items_of,
+                          Walk walk, Fits fits, Count count, Store store) {
+  HookItems<Checkpoint> items;
+  const int walked = items.walks(f, segs, got, d, items_of, walk, fits);
+  if (walked != 0) return walked;
+  droom.snapshot();
+  SeededOrder seeded(order_seed);
+  std::vector<BrotliAmdUndeltaTile> tiles(items.pre.back());
+  items.shuffled(&seeded, [&](uint32_t i, Checkpoint cp, uint64_t j, uint64_t g) { tiles[g] = count(i, cp, j); });
+  const std::vector<uint64_t> carries = carries_of(tiles);
+  items.shuffled(&seeded, [&](uint32_t i, Checkpoint cp, uint64_t j, uint64_t g) { store(i, cp, j, carries[g]); });
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int BrotliAmdBatchUnshuffleSegments(BrotliAmdBatch* b, uint32_t n, const void* const* d_src, void* const* d_dst, const size_t* lens,
@@ -828,25 +900,14 @@ extern "C" int BrotliAmdDebugUnrleHost(uint32_t n, const uint8_t* src, size_t sr
   SkewedRoom sroom(src_size, src_skew, 0xA5), droom(dst_size, dst_skew, 0x5A);
   sroom.put(src, src_size);
   droom.put(dst, dst_size);
-  // the walks: they write nothing, and say how much room every segment needs
   std::vector<BrotliAmdUnrleSeg> segs;
-  std::vector<BrotliAmdUnrleResult> got(n);
-  std::vector<std::vector<BrotliAmdUnrleCheckpoint>> ckpts(n);
-  std::vector<std::pair<uint32_t, uint64_t>> order;   // (segment, item)
-  for (uint32_t i = 0; i < n; i++) {
-    // (the items of the elements there is room for: the walk marks no others, and a capacity of 2^56 needs no table of its own)
-    const uint64_t room = (dst_size - dst_offs[i]) / widths[i], cap = std::min<uint64_t>(caps[i], room + 1u);
+  for (uint32_t i = 0; i < n; i++)
     segs.push_back(BrotliAmdUnrleSeg{reinterpret_cast<const uint8_t*>((uintptr_t)(sroom.at() + src_offs[i])), reinterpret_cast<uint8_t*>((uintptr_t)(droom.at() + dst_offs[i])),
-                                     src_lens[i], cap, 0u, widths[i], bits[i], flags ? flags[i] : 0u, 0u});
-    ckpts[i].assign(brotli_amd_unrle_items(cap, item_elems), BrotliAmdUnrleCheckpoint{BROTLI_AMD_UNRLE_NONE, BROTLI_AMD_UNRLE_NONE});
-    got[i] = brotli_amd_unrle_host_walk(segs[i], item_elems, ckpts[i].data());
-    if (std::min(got[i].count, caps[i]) > room) return outside_buffer(kUnrle);
-    for (uint64_t j = 0; j < ckpts[i].size(); j++) order.push_back({i, j});
-  }
-  droom.snapshot();
-  SeededOrder(order_seed).shuffle(&order);
-  for (const auto& it : order) brotli_amd_unrle_host_item(segs[it.first], got[it.first], ckpts[it.first][it.second], it.second, item_elems);
-  return counted_hook_result(kUnrle, droom, n, dst, dst_size, dst_offs, caps, widths, got, results);
+                                     src_lens[i], caps[i], 0u, widths[i], bits[i], flags ? flags[i] : 0u, 0u});
+  return walk_items_hook(
+      kUnrle, segs, droom, ItemHookDst{dst, dst_size, dst_offs, caps, widths}, item_elems, order_seed,
+      [&](uint32_t i, BrotliAmdUnrleCheckpoint* ckpts) { return brotli_amd_unrle_host_walk(segs[i], item_elems, ckpts); },
+      [&](uint32_t i, BrotliAmdUnrleResult* res, BrotliAmdUnrleCheckpoint cp, uint64_t j) { brotli_amd_unrle_host_item(segs[i], *res, cp, j, item_elems); }, results);
 }
 
 // Undbp's phases over n segments given as offsets into one source and one destination buffer, each buffer in its room: every segment's walk, the
@@ -865,38 +926,18 @@ extern "C" int BrotliAmdDebugUndbpHost(uint32_t n, const uint8_t* src, size_t sr
   SkewedRoom sroom(src_size, src_skew, 0xA5), droom(dst_size, dst_skew, 0x5A);
   sroom.put(src, src_size);
   droom.put(dst, dst_size);
-  // the walks: they write nothing, and say how much room every segment needs
   std::vector<BrotliAmdUndbpSeg> segs;
-  std::vector<BrotliAmdUndbpResult> got(n);
-  std::vector<uint64_t> firsts(n, 0u), pre(n + 1u, 0u);
-  std::vector<BrotliAmdUndbpCheckpoint> ckpts;
-  for (uint32_t i = 0; i < n; i++) {
-    // (the items of the elements there is room for: the walk marks no others, and a capacity of 2^56 needs no table of its own)
-    const uint64_t room = (dst_size - dst_offs[i]) / widths[i], cap = std::min<uint64_t>(caps[i], room + 1u);
+  for (uint32_t i = 0; i < n; i++)
     segs.push_back(BrotliAmdUndbpSeg{reinterpret_cast<const uint8_t*>((uintptr_t)(sroom.at() + src_offs[i])), reinterpret_cast<uint8_t*>((uintptr_t)(droom.at() + dst_offs[i])),
-                                     src_lens[i], cap, pre[i], widths[i], 0u});
-    pre[i + 1u] = pre[i] + brotli_amd_undbp_items(cap, item_deltas);
-    ckpts.resize(pre[i + 1u], BrotliAmdUndbpCheckpoint{BROTLI_AMD_UNDBP_NONE, BROTLI_AMD_UNDBP_NONE});
-    got[i] = brotli_amd_undbp_host_walk(segs[i], item_deltas, ckpts.data() + pre[i], &firsts[i]);
-    if (std::min(got[i].count, caps[i]) > room) return outside_buffer(kUndbp);
-  }
-  droom.snapshot();
-  const uint64_t items = pre[n];
-  std::vector<uint64_t> order = first_numbers(items);
-  SeededOrder seeded(order_seed);
-  std::vector<BrotliAmdUndeltaTile> tiles(items);
-  seeded.shuffle(&order);
-  for (uint64_t g : order) {
-    const uint32_t i = brotli_amd_seg_find(pre.data(), n, g);
-    tiles[g] = brotli_amd_undbp_host_sum(segs[i], got[i], ckpts[g], firsts[i], g - pre[i], item_deltas);
-  }
-  const std::vector<uint64_t> carries = carries_of(tiles);
-  seeded.shuffle(&order);
-  for (uint64_t g : order) {
-    const uint32_t i = brotli_amd_seg_find(pre.data(), n, g);
-    brotli_amd_undbp_host_store(segs[i], got[i], ckpts[g], firsts[i], g - pre[i], item_deltas, carries[g]);
-  }
-  return counted_hook_result(kUndbp, droom, n, dst, dst_size, dst_offs, caps, widths, got, results);
+                                     src_lens[i], caps[i], 0u, widths[i], 0u});
+  std::vector<BrotliAmdUndbpResult> got(n);
+  std::vector<uint64_t> firsts(n, 0u);
+  const int r = walk_count_store_hook<BrotliAmdUndbpCheckpoint>(
+      kUndbp, segs, got, droom, ItemHookDst{dst, dst_size, dst_offs, caps, widths}, order_seed, [&](uint64_t cap) { return brotli_amd_undbp_items(cap, item_deltas); },
+      [&](uint32_t i, BrotliAmdUndbpCheckpoint* ckpts) { return brotli_amd_undbp_host_walk(segs[i], item_deltas, ckpts, &firsts[i]); }, [](uint32_t, uint64_t) { return true; },
+      [&](uint32_t i, BrotliAmdUndbpCheckpoint cp, uint64_t j) { return brotli_amd_undbp_host_sum(segs[i], got[i], cp, firsts[i], j, item_deltas); },
+      [&](uint32_t i, BrotliAmdUndbpCheckpoint cp, uint64_t j, uint64_t carry) { brotli_amd_undbp_host_store(segs[i], got[i], cp, firsts[i], j, item_deltas, carry); });
+  return r != 0 ? r : counted_hook_result(kUndbp, droom, n, dst, dst_size, dst_offs, caps, widths, got, results);
 }
 
 // Undict's two phases over n segments given as offsets into one source, one destination and one dictionary buffer, each buffer in its room:
@@ -922,26 +963,15 @@ extern "C" int BrotliAmdDebugUndictHost(uint32_t n, const uint8_t* src, size_t s
   sroom.put(src, src_size);
   droom.put(dst, dst_size);
   troom.put(dict, dict_size);
-  // the walks: they write nothing, and say how much room every segment needs
   std::vector<BrotliAmdUndictSeg> segs;
-  std::vector<BrotliAmdUndictResult> got(n);
-  std::vector<std::vector<BrotliAmdUnrleCheckpoint>> ckpts(n);
-  std::vector<std::pair<uint32_t, uint64_t>> order;   // (segment, item)
-  for (uint32_t i = 0; i < n; i++) {
-    // (the items of the elements there is room for: the walk marks no others, and a capacity of 2^56 needs no table of its own)
-    const uint64_t room = (dst_size - dst_offs[i]) / widths[i], cap = std::min<uint64_t>(caps[i], room + 1u);
+  for (uint32_t i = 0; i < n; i++)
     segs.push_back(BrotliAmdUndictSeg{reinterpret_cast<const uint8_t*>((uintptr_t)(sroom.at() + src_offs[i])), reinterpret_cast<uint8_t*>((uintptr_t)(droom.at() + dst_offs[i])),
-                                      src_lens[i], cap, 0u, widths[i], bits[i], flags ? flags[i] : 0u, 0u,
+                                      src_lens[i], caps[i], 0u, widths[i], bits[i], flags ? flags[i] : 0u, 0u,
                                       reinterpret_cast<const uint8_t*>((uintptr_t)(troom.at() + dict_offs[i])), dict_entries[i]});
-    ckpts[i].assign(brotli_amd_unrle_items(cap, item_elems), BrotliAmdUnrleCheckpoint{BROTLI_AMD_UNRLE_NONE, BROTLI_AMD_UNRLE_NONE});
-    got[i] = brotli_amd_undict_host_walk(segs[i], item_elems, ckpts[i].data());
-    if (std::min(got[i].count, caps[i]) > room) return outside_buffer(kUndict);
-    for (uint64_t j = 0; j < ckpts[i].size(); j++) order.push_back({i, j});
-  }
-  droom.snapshot();
-  SeededOrder(order_seed).shuffle(&order);
-  for (const auto& it : order) brotli_amd_undict_host_item(segs[it.first], &got[it.first], ckpts[it.first][it.second], it.second, item_elems);
-  return counted_hook_result(kUndict, droom, n, dst, dst_size, dst_offs, caps, widths, got, results);
+  return walk_items_hook(
+      kUndict, segs, droom, ItemHookDst{dst, dst_size, dst_offs, caps, widths}, item_elems, order_seed,
+      [&](uint32_t i, BrotliAmdUnrleCheckpoint* ckpts) { return brotli_amd_undict_host_walk(segs[i], item_elems, ckpts); },
+      [&](uint32_t i, BrotliAmdUndictResult* res, BrotliAmdUnrleCheckpoint cp, uint64_t j) { brotli_amd_undict_host_item(segs[i], res, cp, j, item_elems); }, results);
 }
 
 // Unnull's four phases over n segments given as offsets into one source, one destination, one values and one validity buffer, each buffer in its
@@ -977,42 +1007,23 @@ extern "C" int BrotliAmdDebugUnnullHost(uint32_t n, const uint8_t* src, size_t s
   droom.put(dst, dst_size);
   vroom.put(values, values_size);
   broom.put(valid, valid_size);
-  // the walks: they write nothing, and say how much room every segment needs
+  broom.snapshot();   // (the walks write nothing)
   std::vector<BrotliAmdUnnullResult> got(n);
   std::vector<BrotliAmdUnnullRuns> runs(n);
-  std::vector<uint64_t> pre(n + 1u, 0u);
-  std::vector<BrotliAmdUnrleCheckpoint> ckpts;
-  for (uint32_t i = 0; i < n; i++) {
-    // (the items of the slots there is room for: the walk marks no others, and a capacity of 2^56 needs no table of its own)
-    const uint64_t room = (dst_size - dst_offs[i]) / widths[i];
-    segs[i].cap = std::min<uint64_t>(caps[i], room + 1u);
-    segs[i].first_item = pre[i];
-    pre[i + 1u] = pre[i] + brotli_amd_unrle_items(segs[i].cap, item_elems);
-    ckpts.resize(pre[i + 1u], BrotliAmdUnrleCheckpoint{BROTLI_AMD_UNRLE_NONE, BROTLI_AMD_UNRLE_NONE});
-    got[i] = brotli_amd_unnull_host_walk(segs[i], item_elems, ckpts.data() + pre[i], &runs[i]);
-    const uint64_t m = std::min(got[i].count, caps[i]);
-    if (m > room || (segs[i].valid && (m + 7u) / 8u > valid_size - valid_offs[i])) return outside_buffer(kUnnull);
-  }
-  droom.snapshot();
-  broom.snapshot();
-  const uint64_t items = pre[n];
-  std::vector<uint64_t> order = first_numbers(items);
-  SeededOrder seeded(order_seed);
-  std::vector<BrotliAmdUndeltaTile> tiles(items);
   std::vector<uint32_t> masks((item_elems + BROTLI_AMD_UNNULL_LANE_SLOTS - 1u) / BROTLI_AMD_UNNULL_LANE_SLOTS);
-  seeded.shuffle(&order);
-  for (uint64_t g : order) {
-    const uint32_t i = brotli_amd_seg_find(pre.data(), n, g);
-    std::fill(masks.begin(), masks.end(), 0u);
-    tiles[g] = brotli_amd_unnull_host_count(segs[i], runs[i], got[i], ckpts[g], g - pre[i], item_elems, masks.data());
-  }
-  const std::vector<uint64_t> carries = carries_of(tiles);
-  seeded.shuffle(&order);
-  for (uint64_t g : order) {
-    const uint32_t i = brotli_amd_seg_find(pre.data(), n, g);
-    std::fill(masks.begin(), masks.end(), 0u);
-    brotli_amd_unnull_host_expand(segs[i], runs[i], &got[i], ckpts[g], g - pre[i], item_elems, carries[g], masks.data());
-  }
+  const int walked = walk_count_store_hook<BrotliAmdUnrleCheckpoint>(
+      kUnnull, segs, got, droom, ItemHookDst{dst, dst_size, dst_offs, caps, widths}, order_seed, [&](uint64_t cap) { return brotli_amd_unrle_items(cap, item_elems); },
+      [&](uint32_t i, BrotliAmdUnrleCheckpoint* ckpts) { return brotli_amd_unnull_host_walk(segs[i], item_elems, ckpts, &runs[i]); },
+      [&](uint32_t i, uint64_t m) { return !segs[i].valid || (m + 7u) / 8u <= valid_size - valid_offs[i]; },
+      [&](uint32_t i, BrotliAmdUnrleCheckpoint cp, uint64_t j) {
+        std::fill(masks.begin(), masks.end(), 0u);
+        return brotli_amd_unnull_host_count(segs[i], runs[i], got[i], cp, j, item_elems, masks.data());
+      },
+      [&](uint32_t i, BrotliAmdUnrleCheckpoint cp, uint64_t j, uint64_t carry) {
+        std::fill(masks.begin(), masks.end(), 0u);
+        brotli_amd_unnull_host_expand(segs[i], runs[i], &got[i], cp, j, item_elems, carry, masks.data());
+      });
+  if (walked != 0) return walked;
   // no byte outside every segment's validity bytes may have changed; the slots' room is judged by the counted hooks' closing block
   std::vector<uint8_t> inside(valid_size, 0);
   for (uint32_t i = 0; i < n; i++)

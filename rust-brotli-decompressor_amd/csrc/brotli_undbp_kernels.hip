@@ -26,16 +26,14 @@
 #include <hip/hip_runtime.h>
 
 #include "brotli_device_abi.h"
+#include "brotli_run_items.h"    // the walk's frame, the scratch and the launcher
 #include "brotli_seg_walk.h"
 #include "brotli_undbp.h"
 #include "brotli_wave_stage.h"
 
-// (csrc/brotli_undelta_kernels.hip)
-extern "C" hipError_t brotli_amd_launch_tile_carries(const BrotliAmdUndeltaTile* tiles, uint64_t* carries, uint64_t ntiles, hipStream_t stream);
-
 namespace {
 
-constexpr uint32_t kThreads = BROTLI_AMD_SEG_THREADS, kWaves = kThreads / 64u;
+constexpr uint32_t kThreads = brotli_amd_wave::kSegThreads, kWaves = brotli_amd_wave::kSegWaves;
 constexpr uint32_t kChunk = brotli_amd_wave::kStageChunk, kItem = BROTLI_AMD_UNDBP_ITEM_DELTAS, kGroup = BROTLI_AMD_UNDBP_GROUP;
 
 static_assert(kItem == 64u * kGroup, "a group a lane");
@@ -53,22 +51,18 @@ typedef BrotliAmdUndeltaTile Tile;
 __global__ __launch_bounds__(kThreads) void brotli_amd_undbp_walk_kernel(const Seg* __restrict__ segs, uint32_t n, uint64_t items, Result* __restrict__ results,
                                                                          uint64_t* __restrict__ firsts, uint64_t* __restrict__ pre, Checkpoint* __restrict__ ckpts) {
   __shared__ __attribute__((aligned(16))) uint8_t stage[kWaves][2u * kChunk];
-  const uint32_t lane = threadIdx.x & 63u, wave = same(threadIdx.x >> 6);
-  for (uint64_t i = (uint64_t)blockIdx.x * kWaves + wave; i < n; i += (uint64_t)gridDim.x * kWaves) {
-    const Seg sg = segs[i];
-    Stage rd(stage[wave], (uint64_t)(uintptr_t)sg.src, sg.len, lane);
-    Checkpoint* mine = ckpts + sg.first_item;
-    uint64_t first = 0;
-    const Result res = brotli_amd_undbp_walk(rd, sg.len, sg.cap, kItem, &first, [&](uint64_t j0, uint64_t j1, uint64_t off, uint64_t d0) {
-      for (uint64_t j = j0 + lane; j < j1; j += 64u) mine[j] = Checkpoint{off, d0};
-    });
-    if (lane == 0u) {
-      results[i] = res;
-      firsts[i] = first;
-      pre[i] = sg.first_item;
-      if (i + 1u == n) pre[n] = items;
-    }
-  }
+  struct Walked { Result res; uint64_t first; };
+  brotli_amd_wave::walk_segments(
+      stage, segs, n, items, pre, ckpts,
+      [](const Seg& sg, Stage& rd, auto mark) {
+        Walked got = {{}, 0u};
+        got.res = brotli_amd_undbp_walk(rd, sg.len, sg.cap, kItem, &got.first, mark);
+        return got;
+      },
+      [&](uint64_t i, const Seg&, const Walked& got) {
+        results[i] = got.res;
+        firsts[i] = got.first;
+      });
 }
 
 // ---- launches 2 and 4 ----
@@ -166,9 +160,6 @@ __global__ __launch_bounds__(kThreads) void brotli_amd_undbp_expand_kernel(const
   }
 }
 
-constexpr uint64_t pad16(uint64_t bytes) { return (bytes + 15u) & ~(uint64_t)15; }
-constexpr uint64_t pre_bytes(uint32_t n) { return pad16(((uint64_t)n + 1u) * sizeof(uint64_t)); }
-
 }  // namespace
 
 extern "C" uint32_t brotli_amd_undbp_item_deltas(void) { return kItem; }
@@ -176,43 +167,12 @@ extern "C" uint32_t brotli_amd_undbp_walk_chunk(void) { return kChunk; }
 // the scratch of a launch over `units` units of n segments -- a unit a segment and a unit an item --: the results first, then the first values,
 // the items' prefix array, the checkpoints, the tile records and the carries
 extern "C" uint64_t brotli_amd_undbp_scratch_bytes(uint64_t units, uint32_t n) {
-  return pad16((uint64_t)n * sizeof(Result)) + pad16((uint64_t)n * sizeof(uint64_t)) + pre_bytes(n) +
-         (units - n) * (sizeof(Checkpoint) + sizeof(Tile) + sizeof(uint64_t));
+  return brotli_amd_wave::ItemScratch<Result, Checkpoint, true, true>::bytes(units - n, n);
 }
 
 // units: n + the items of all segments (the host has the table); d_scratch: brotli_amd_undbp_scratch_bytes of device memory, 16-byte aligned;
 // ev[0..4], where not NULL, are recorded in front of, between and behind the four launches
 extern "C" hipError_t brotli_amd_launch_undbp(const void* d_table, uint32_t n, uint64_t units, void* d_scratch, hipStream_t stream, const hipEvent_t* ev) {
-  if (n == 0u) return hipSuccess;
-  const BrotliAmdUndbpSeg* d_segs = static_cast<const BrotliAmdUndbpSeg*>(d_table);
-  const uint64_t items = units - n;
-  uint8_t* at = static_cast<uint8_t*>(d_scratch);
-  Result* results = reinterpret_cast<Result*>(at); at += pad16((uint64_t)n * sizeof(Result));
-  uint64_t* firsts = reinterpret_cast<uint64_t*>(at); at += pad16((uint64_t)n * sizeof(uint64_t));
-  uint64_t* pre = reinterpret_cast<uint64_t*>(at); at += pre_bytes(n);
-  Checkpoint* ckpts = reinterpret_cast<Checkpoint*>(at); at += items * sizeof(Checkpoint);
-  Tile* tiles = reinterpret_cast<Tile*>(at); at += items * sizeof(Tile);
-  uint64_t* carries = reinterpret_cast<uint64_t*>(at);
-  hipError_t e = hipSuccess;
-  uint32_t grid = 0;
-  if (items != 0u && (e = hipMemsetAsync(ckpts, 0xFF, (size_t)items * sizeof(Checkpoint), stream)) != hipSuccess) return e;
-  if ((e = brotli_amd_wave::wave_grid(n, kWaves, &grid)) != hipSuccess) return e;
-  if (ev && (e = hipEventRecord(ev[0], stream)) != hipSuccess) return e;
-  hipLaunchKernelGGL(brotli_amd_undbp_walk_kernel, dim3(grid), dim3(kThreads), 0, stream, d_segs, n, items, results, firsts, pre, ckpts);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  if (ev && (e = hipEventRecord(ev[1], stream)) != hipSuccess) return e;
-  if (items != 0u) {
-    if ((e = brotli_amd_wave::wave_grid(items, kWaves, &grid)) != hipSuccess) return e;
-    hipLaunchKernelGGL(brotli_amd_undbp_sum_kernel, dim3(grid), dim3(kThreads), 0, stream, d_segs, n, items, results, firsts, pre, ckpts, tiles);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
-  if (ev && (e = hipEventRecord(ev[2], stream)) != hipSuccess) return e;
-  if (items != 0u && (e = brotli_amd_launch_tile_carries(tiles, carries, items, stream)) != hipSuccess) return e;
-  if (ev && (e = hipEventRecord(ev[3], stream)) != hipSuccess) return e;
-  if (items != 0u) {
-    hipLaunchKernelGGL(brotli_amd_undbp_expand_kernel, dim3(grid), dim3(kThreads), 0, stream, d_segs, n, items, results, firsts, pre, ckpts, carries);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
-  if (ev && (e = hipEventRecord(ev[4], stream)) != hipSuccess) return e;
-  return hipSuccess;
+  return brotli_amd_wave::launch_walk_count_carry_expand<Seg, Result, Checkpoint>(brotli_amd_undbp_walk_kernel, brotli_amd_undbp_sum_kernel, brotli_amd_undbp_expand_kernel, d_table, n,
+                                                                                  units, d_scratch, stream, ev);
 }

@@ -16,20 +16,21 @@
 //                                       item that has some adds them to its segment's result with one atomicAdd and one atomicMin.
 // THE SCRATCH behind the table: the n results, the items' prefix array (n + 1 entries), the checkpoints -- one an item, set to
 // BROTLI_AMD_UNRLE_NONE in front of the walk.  A call that only counts has no items and is the first launch alone.
-// The collection of an item's runs into LDS and the search of a lane's first run are unrle's lines, repeated here: DESIGN.md says why.
+// The collection of an item's runs into LDS and a lane's way through them are csrc/brotli_run_items.h.
 #include <hip/hip_runtime.h>
 
 #include "brotli_device_abi.h"
+#include "brotli_run_items.h"    // the run batch, the walk's frame, the scratch and the launcher
 #include "brotli_seg_walk.h"
 #include "brotli_undict.h"
 #include "brotli_wave_stage.h"   // the wave's view of its source through LDS, same(), Word16, wave_grid
 
 namespace {
 
-constexpr uint32_t kThreads = BROTLI_AMD_SEG_THREADS, kWaves = kThreads / 64u;
+constexpr uint32_t kThreads = brotli_amd_wave::kSegThreads, kWaves = brotli_amd_wave::kSegWaves;
 constexpr uint32_t kChunk = BROTLI_AMD_UNRLE_WALK_CHUNK, kItem = BROTLI_AMD_UNRLE_ITEM_ELEMS;
 constexpr uint32_t kPerLane = kItem / 64u;   // neighbouring elements of a lane
-constexpr uint32_t kBatch = 64;              // runs collected at a time
+constexpr uint32_t kBatch = brotli_amd_wave::kRunBatch;
 #ifndef BROTLI_AMD_UNDICT_GROUP
 #define BROTLI_AMD_UNDICT_GROUP 4u
 #endif
@@ -38,7 +39,8 @@ constexpr uint32_t kGroup = BROTLI_AMD_UNDICT_GROUP;   // elements of a lane who
 static_assert(kChunk == brotli_amd_wave::kStageChunk, "the chunk the stage has");
 static_assert(kPerLane == 16u && kPerLane % kGroup == 0u, "a lane's elements are whole 16-byte words at every width, in whole groups");
 
-using brotli_amd_wave::lds_sync;
+using brotli_amd_wave::RunBatch;
+using brotli_amd_wave::RunCursor;
 using brotli_amd_wave::same;
 using brotli_amd_wave::Stage;
 using brotli_amd_wave::Word16;
@@ -51,21 +53,12 @@ typedef BrotliAmdUnrleCheckpoint Checkpoint;
 __global__ __launch_bounds__(kThreads) void brotli_amd_undict_walk_kernel(const Seg* __restrict__ segs, uint32_t n, uint64_t items, Result* __restrict__ results,
                                                                           uint64_t* __restrict__ pre, Checkpoint* __restrict__ ckpts) {
   __shared__ __attribute__((aligned(16))) uint8_t stage[kWaves][2u * kChunk];
-  const uint32_t lane = threadIdx.x & 63u, wave = same(threadIdx.x >> 6);
-  for (uint64_t i = (uint64_t)blockIdx.x * kWaves + wave; i < n; i += (uint64_t)gridDim.x * kWaves) {
-    const Seg sg = segs[i];
-    Stage rd(stage[wave], (uint64_t)(uintptr_t)sg.src, sg.len, lane);
-    Checkpoint* mine = ckpts + sg.first_item;
-    const BrotliAmdUnrleResult res = brotli_amd_unrle_walk(rd, sg.len, sg.cap, BROTLI_AMD_UNDICT_WALK_WIDTH, sg.bits, sg.flags, kItem,
-                                                           [&](uint64_t j0, uint64_t j1, uint64_t off, uint64_t first) {
-      for (uint64_t j = j0 + lane; j < j1; j += 64u) mine[j] = Checkpoint{off, first};
-    });
-    if (lane == 0u) {
-      results[i] = Result{res.count, res.consumed, res.runs, res.status, res.bits, 0u, BROTLI_AMD_UNDICT_NONE};   // (what the items add to)
-      pre[i] = sg.first_item;
-      if (i + 1u == n) pre[n] = items;
-    }
-  }
+  brotli_amd_wave::walk_segments(
+      stage, segs, n, items, pre, ckpts,
+      [](const Seg& sg, Stage& rd, auto mark) { return brotli_amd_unrle_walk(rd, sg.len, sg.cap, BROTLI_AMD_UNDICT_WALK_WIDTH, sg.bits, sg.flags, kItem, mark); },
+      [&](uint64_t i, const Seg&, const BrotliAmdUnrleResult& res) {
+        results[i] = Result{res.count, res.consumed, res.runs, res.status, res.bits, 0u, BROTLI_AMD_UNDICT_NONE};   // (what the items add to)
+      });
 }
 
 // ---- launch 2 ----
@@ -73,9 +66,10 @@ __global__ __launch_bounds__(kThreads) void brotli_amd_undict_walk_kernel(const 
 struct LaneCarry { Word16 word; uint64_t val = 0; uint32_t bad = 0; };
 
 // The elements [g0, g0 + kGroup) below m of a lane whose m elements (1 .. 16) begin at address at0, their indices in idx: looked up in the D
-// entries of W bytes at dict, and stored -- single elements in front of `head` and from `tail` on, whole 16-byte words between.  Bit u of
-// `fresh` says that element g0 + u needs a lookup of its own; the others have the value of the element in front of them.  -> the bad
-// elements' bits
+// entries of W bytes at dict, and stored -- single elements in front of `head` and from `tail` on, whole 16-byte words between (unnull has
+// the same rule in lines of its own: through one helper for both, this kernel's 8-byte gathers measured 3 % slower, profiles/run_items.txt).
+// Bit u of `fresh` says that element g0 + u needs a lookup of its own; the others have the value of the element in front of them.  -> the
+// bad elements' bits
 template <uint32_t W>
 __device__ __forceinline__ uint32_t lookup_and_store(uint64_t dict, uint64_t D, uint64_t at0, uint32_t m, uint32_t head, uint32_t tail, uint32_t g0,
                                                      const uint32_t (&idx)[kGroup], uint32_t fresh, LaneCarry* carry) {
@@ -120,9 +114,7 @@ __global__ __launch_bounds__(kThreads) void brotli_amd_undict_expand_kernel(cons
   __shared__ uint64_t run_payload[kWaves][kBatch];      // (BROTLI_AMD_UNRLE_NONE: an RLE run)
   __shared__ uint32_t run_value[kWaves][kBatch];
   const uint32_t lane = threadIdx.x & 63u, wave = same(threadIdx.x >> 6);
-  uint64_t* const first = run_first[wave];
-  uint64_t* const payload = run_payload[wave];
-  uint32_t* const value = run_value[wave];
+  RunBatch batch(run_first[wave], run_payload[wave], run_value[wave]);
   for (uint64_t g = (uint64_t)blockIdx.x * kWaves + wave; g < items; g += (uint64_t)gridDim.x * kWaves) {
     const Checkpoint cp = ckpts[g];
     if (cp.off == BROTLI_AMD_UNRLE_NONE) continue;   // (beyond count; the same in every lane)
@@ -131,9 +123,9 @@ __global__ __launch_bounds__(kThreads) void brotli_amd_undict_expand_kernel(cons
     const uint64_t count = results[i].count;
     const uint32_t k = results[i].bits, w = sg.width;
     const uint64_t src = (uint64_t)(uintptr_t)sg.src, dst = (uint64_t)(uintptr_t)sg.dst, dict = (uint64_t)(uintptr_t)sg.dict, D = sg.dict_entries;
-    const uint64_t end = count < sg.cap ? count : sg.cap, e0 = (g - pre[i]) * kItem;
-    if (e0 >= end) continue;
-    const uint64_t e1 = e0 + kItem < end ? e0 + kItem : end;
+    uint64_t e0, e1;
+    brotli_amd_unrle_item_range(count, sg.cap, g - pre[i], kItem, &e0, &e1);
+    if (e0 >= e1) continue;
     const uint64_t la = e0 + (uint64_t)kPerLane * lane, lb = la + kPerLane < e1 ? la + kPerLane : e1;   // this lane's elements
     Stage rd(stage[wave], src, sg.len, lane);
     BrotliAmdUnrleWalk st = {cp.off, cp.first};
@@ -141,32 +133,11 @@ __global__ __launch_bounds__(kThreads) void brotli_amd_undict_expand_kernel(cons
     uint64_t lane_first = BROTLI_AMD_UNDICT_NONE;   // and the first of them
     bool more = true;
     while (more && st.elems < e1) {
-      // the next runs, up to kBatch of them: every lane walks, lane 0 keeps
-      const uint64_t batch_lo = st.elems;
-      uint32_t nr = 0;
-      lds_sync();   // (the batch before is done with)
-      while (more && nr < kBatch && st.elems < e1) {
-        rd.ensure(st.off);
-        const BrotliAmdUnrleRun run = brotli_amd_unrle_run(rd, sg.len, k, st);
-        if (run.kind == BROTLI_AMD_UNRLE_STOP) { more = false; break; }   // (not below count)
-        if (lane == 0u) {
-          first[nr] = st.elems;
-          payload[nr] = run.kind == BROTLI_AMD_UNRLE_RLE ? BROTLI_AMD_UNRLE_NONE : run.payload;
-          value[nr] = run.value;
-        }
-        nr++;
-        st.off = run.next; st.elems += run.count;
-        more = run.status == BROTLI_AMD_UNRLE_OK;
-      }
-      if (lane == 0u) first[nr] = st.elems;
-      lds_sync();
+      batch.collect(rd, sg.len, k, st, more, e1, lane);
       // this lane's elements among the batch's
-      const uint64_t a = la > batch_lo ? la : batch_lo, b = lb < st.elems ? lb : st.elems;
+      const uint64_t a = la > batch.lo ? la : batch.lo, b = lb < st.elems ? lb : st.elems;
       if (a >= b) continue;
-      uint32_t r = 0;
-      { uint32_t hi = nr; while (hi - r > 1u) { const uint32_t m = (r + hi) >> 1; if (first[m] <= a) r = m; else hi = m; } }
-      uint64_t r_first = first[r], r_end = first[r + 1u], r_payload = payload[r];
-      uint32_t r_value = value[r];
+      RunCursor<true> run(batch, a);
       // group after group of the lane's elements: all of a group's indices first, then its lookups together, then its stores
       const uint32_t m = (uint32_t)(b - a);
       const uint64_t at0 = dst + a * w;
@@ -182,10 +153,9 @@ __global__ __launch_bounds__(kThreads) void brotli_amd_undict_expand_kernel(cons
           idx[u] = 0u;
           if (g0 + u < m) {
             const uint64_t e = a + g0 + u;
-            bool moved = g0 + u == 0u;
-            while (e >= r_end) { r++; r_first = r_end; r_end = first[r + 1u]; r_payload = payload[r]; r_value = value[r]; moved = true; }
-            idx[u] = (uint32_t)brotli_amd_unrle_element(src, r_payload, r_value, k, e - r_first);
-            if (moved || r_payload != BROTLI_AMD_UNRLE_NONE) fresh |= 1u << u;   // (inside an RLE run: the lookup of the element in front)
+            const bool moved = run.seek(e) || g0 + u == 0u;
+            idx[u] = (uint32_t)brotli_amd_unrle_element(src, run.payload, run.value, k, e - run.first);
+            if (moved || run.payload != BROTLI_AMD_UNRLE_NONE) fresh |= 1u << u;   // (inside an RLE run: the lookup of the element in front)
           }
         }
         uint32_t group_bad;
@@ -219,38 +189,16 @@ __global__ __launch_bounds__(kThreads) void brotli_amd_undict_expand_kernel(cons
   }
 }
 
-constexpr uint64_t pre_bytes(uint32_t n) { return (((uint64_t)n + 1u) * sizeof(uint64_t) + 15u) & ~(uint64_t)15; }
-
 }  // namespace
 
 // the scratch of a launch over `units` units of n segments -- a unit a segment and a unit an item --: the results first, then the items' prefix
 // array and the checkpoints
 extern "C" uint64_t brotli_amd_undict_scratch_bytes(uint64_t units, uint32_t n) {
-  return (uint64_t)n * sizeof(Result) + pre_bytes(n) + (units - n) * sizeof(Checkpoint);
+  return brotli_amd_wave::ItemScratch<Result, Checkpoint, false, false>::bytes(units - n, n);
 }
 
 // units: n + the items of all segments (the host has the table); d_scratch: brotli_amd_undict_scratch_bytes of device memory, 16-byte aligned;
 // ev[0..2], where not NULL, are recorded in front of, between and behind the two launches
 extern "C" hipError_t brotli_amd_launch_undict(const void* d_table, uint32_t n, uint64_t units, void* d_scratch, hipStream_t stream, const hipEvent_t* ev) {
-  if (n == 0u) return hipSuccess;
-  const Seg* d_segs = static_cast<const Seg*>(d_table);
-  const uint64_t items = units - n;
-  Result* results = static_cast<Result*>(d_scratch);
-  uint64_t* pre = reinterpret_cast<uint64_t*>(results + n);
-  Checkpoint* ckpts = reinterpret_cast<Checkpoint*>(reinterpret_cast<uint8_t*>(pre) + pre_bytes(n));
-  hipError_t e = hipSuccess;
-  uint32_t grid = 0;
-  if (items != 0u && (e = hipMemsetAsync(ckpts, 0xFF, (size_t)items * sizeof(Checkpoint), stream)) != hipSuccess) return e;
-  if ((e = brotli_amd_wave::wave_grid(n, kWaves, &grid)) != hipSuccess) return e;
-  if (ev && (e = hipEventRecord(ev[0], stream)) != hipSuccess) return e;
-  hipLaunchKernelGGL(brotli_amd_undict_walk_kernel, dim3(grid), dim3(kThreads), 0, stream, d_segs, n, items, results, pre, ckpts);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  if (ev && (e = hipEventRecord(ev[1], stream)) != hipSuccess) return e;
-  if (items != 0u) {
-    if ((e = brotli_amd_wave::wave_grid(items, kWaves, &grid)) != hipSuccess) return e;
-    hipLaunchKernelGGL(brotli_amd_undict_expand_kernel, dim3(grid), dim3(kThreads), 0, stream, d_segs, n, items, results, pre, ckpts);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
-  if (ev && (e = hipEventRecord(ev[2], stream)) != hipSuccess) return e;
-  return hipSuccess;
+  return brotli_amd_wave::launch_walk_expand<Seg, Result, Checkpoint>(brotli_amd_undict_walk_kernel, brotli_amd_undict_expand_kernel, d_table, n, units, d_scratch, stream, ev);
 }

@@ -100,12 +100,7 @@ BROTLI_AMD_UNNULL_HD BrotliAmdUndictValue brotli_amd_unnull_slot(uint64_t values
 BROTLI_AMD_UNNULL_HD uint32_t brotli_amd_unnull_valid_byte(uint32_t mask, uint32_t j) { return (mask >> (8u * j)) & 0xFFu; }
 
 // ---- the items ----
-// the slots [*e0, *e1) of item j of a segment that delivers min(count, cap) slots (*e0 >= *e1: none), and its validity bytes [*e0 / 8, ceil(*e1 / 8))
-BROTLI_AMD_UNNULL_HD void brotli_amd_unnull_item_range(uint64_t count, uint64_t cap, uint64_t j, uint32_t item_elems, uint64_t* e0, uint64_t* e1) {
-  const uint64_t end = count < cap ? count : cap;
-  *e0 = j * item_elems;
-  *e1 = *e0 + item_elems < end ? *e0 + item_elems : end;
-}
+// An item's slots [e0, e1) are unrle's elements (brotli_amd_unrle_item_range); its validity bytes are [e0 / 8, ceil(e1 / 8)).
 
 // ---- the segment's sums ----
 // What the item that holds the segment's last delivered slot knows: the delivered slots that are there are its carry-in and its own, and their
@@ -134,7 +129,7 @@ inline void brotli_amd_unnull_host_masks(const BrotliAmdUnnullSeg& sg, BrotliAmd
                                          uint32_t item_elems, uint32_t* masks) {
   const uint64_t src = (uint64_t)(uintptr_t)sg.src + runs.off;
   uint64_t e0, e1;
-  brotli_amd_unnull_item_range(res.count, sg.cap, j, item_elems, &e0, &e1);
+  brotli_amd_unrle_item_range(res.count, sg.cap, j, item_elems, &e0, &e1);
   if (cp.off == BROTLI_AMD_UNRLE_NONE || e0 >= e1) return;
   BrotliAmdUnrleDirect rd = {src};
   BrotliAmdUnrleWalk st = {cp.off, cp.first};
@@ -165,7 +160,7 @@ inline BrotliAmdUndeltaTile brotli_amd_unnull_host_count(const BrotliAmdUnnullSe
 inline void brotli_amd_unnull_host_expand(const BrotliAmdUnnullSeg& sg, BrotliAmdUnnullRuns runs, BrotliAmdUnnullResult* res, BrotliAmdUnrleCheckpoint cp, uint64_t j,
                                           uint32_t item_elems, uint64_t carry_in, uint32_t* masks) {
   uint64_t e0, e1;
-  brotli_amd_unnull_item_range(res->count, sg.cap, j, item_elems, &e0, &e1);
+  brotli_amd_unrle_item_range(res->count, sg.cap, j, item_elems, &e0, &e1);
   if (cp.off == BROTLI_AMD_UNRLE_NONE || e0 >= e1) return;
   brotli_amd_unnull_host_masks(sg, runs, *res, cp, j, item_elems, masks);
   const uint64_t dst = (uint64_t)(uintptr_t)sg.dst, valid = (uint64_t)(uintptr_t)sg.valid, values = brotli_amd_unnull_values_at(sg, *res);

@@ -24,23 +24,21 @@
 // THE SCRATCH behind the table: the n results, the n lengths of the runs, the items' prefix array (n + 1 entries), and for every item a
 // checkpoint -- set to BROTLI_AMD_UNRLE_NONE in front of the walk --, a tile record and a carry.  A call that only counts has no items and is
 // the first launch alone.
-// The collection of an item's runs into LDS and the search of a lane's first run are unrle's lines, repeated here as undict repeats them.
+// The collection of an item's runs into LDS and a lane's way through them are csrc/brotli_run_items.h.
 #include <hip/hip_runtime.h>
 
 #include "brotli_device_abi.h"
+#include "brotli_run_items.h"    // the run batch, the walk's frame, the scratch and the launcher
 #include "brotli_seg_walk.h"
 #include "brotli_unnull.h"
 #include "brotli_wave_stage.h"   // the wave's view of its source through LDS, same(), Word16, wave_grid
 
-// (csrc/brotli_undelta_kernels.hip)
-extern "C" hipError_t brotli_amd_launch_tile_carries(const BrotliAmdUndeltaTile* tiles, uint64_t* carries, uint64_t ntiles, hipStream_t stream);
-
 namespace {
 
-constexpr uint32_t kThreads = BROTLI_AMD_SEG_THREADS, kWaves = kThreads / 64u;
+constexpr uint32_t kThreads = brotli_amd_wave::kSegThreads, kWaves = brotli_amd_wave::kSegWaves;
 constexpr uint32_t kChunk = BROTLI_AMD_UNRLE_WALK_CHUNK, kItem = BROTLI_AMD_UNRLE_ITEM_ELEMS;
 constexpr uint32_t kPerLane = kItem / 64u;   // neighbouring slots of a lane
-constexpr uint32_t kBatch = 64;              // runs collected at a time
+constexpr uint32_t kBatch = brotli_amd_wave::kRunBatch;
 #ifndef BROTLI_AMD_UNNULL_GROUP
 #define BROTLI_AMD_UNNULL_GROUP 4u
 #endif
@@ -50,7 +48,8 @@ static_assert(kChunk == brotli_amd_wave::kStageChunk, "the chunk the stage has")
 static_assert(kPerLane == BROTLI_AMD_UNNULL_LANE_SLOTS && kPerLane % kGroup == 0u, "a lane's slots are two validity bytes and whole 16-byte words, in whole groups");
 static_assert(kItem / 8u == 128u, "an item's validity bytes: eight 16-byte words, nine where the bitmap is not aligned");
 
-using brotli_amd_wave::lds_sync;
+using brotli_amd_wave::RunBatch;
+using brotli_amd_wave::RunCursor;
 using brotli_amd_wave::same;
 using brotli_amd_wave::Stage;
 using brotli_amd_wave::Word16;
@@ -64,72 +63,43 @@ typedef BrotliAmdUndeltaTile Tile;
 __global__ __launch_bounds__(kThreads) void brotli_amd_unnull_walk_kernel(const Seg* __restrict__ segs, uint32_t n, uint64_t items, Result* __restrict__ results,
                                                                           uint64_t* __restrict__ run_lens, uint64_t* __restrict__ pre, Checkpoint* __restrict__ ckpts) {
   __shared__ __attribute__((aligned(16))) uint8_t stage[kWaves][2u * kChunk];
-  const uint32_t lane = threadIdx.x & 63u, wave = same(threadIdx.x >> 6);
-  for (uint64_t i = (uint64_t)blockIdx.x * kWaves + wave; i < n; i += (uint64_t)gridDim.x * kWaves) {
-    const Seg sg = segs[i];
-    const uint64_t src = (uint64_t)(uintptr_t)sg.src;
-    BrotliAmdUnnullRuns runs;
-    {
-      Stage whole(stage[wave], src, sg.len, lane);
-      runs = brotli_amd_unnull_prefix(whole, sg.len, sg.flags);
-    }
-    BrotliAmdUnrleResult r = {0u, 0u, 0u, BROTLI_AMD_UNRLE_OK, sg.bits};
-    if (runs.status == BROTLI_AMD_UNRLE_OK) {   // (the same in every lane)
-      Stage rd(stage[wave], src + runs.off, runs.len, lane);
-      Checkpoint* mine = ckpts + sg.first_item;
-      r = brotli_amd_unrle_walk(rd, runs.len, sg.cap, BROTLI_AMD_UNNULL_WALK_WIDTH, sg.bits, 0u, kItem, [&](uint64_t j0, uint64_t j1, uint64_t off, uint64_t first) {
-        for (uint64_t j = j0 + lane; j < j1; j += 64u) mine[j] = Checkpoint{off, first};
+  struct Walked { BrotliAmdUnnullRuns runs; BrotliAmdUnrleResult r; };
+  brotli_amd_wave::walk_segments(
+      stage, segs, n, items, pre, ckpts,
+      [](const Seg& sg, Stage& whole, auto mark) {
+        Walked got = {brotli_amd_unnull_prefix(whole, sg.len, sg.flags), {0u, 0u, 0u, BROTLI_AMD_UNRLE_OK, sg.bits}};
+        if (got.runs.status == BROTLI_AMD_UNRLE_OK) {   // (the same in every lane)
+          Stage rd(whole.lds, (uint64_t)(uintptr_t)sg.src + got.runs.off, got.runs.len, whole.lane);
+          got.r = brotli_amd_unrle_walk(rd, got.runs.len, sg.cap, BROTLI_AMD_UNNULL_WALK_WIDTH, sg.bits, 0u, kItem, mark);
+        }
+        return got;
+      },
+      [&](uint64_t i, const Seg& sg, const Walked& got) {
+        results[i] = brotli_amd_unnull_result(sg, got.runs, got.r);   // (what the items add to)
+        run_lens[i] = got.runs.len;
       });
-    }
-    if (lane == 0u) {
-      results[i] = brotli_amd_unnull_result(sg, runs, r);   // (what the items add to)
-      run_lens[i] = runs.len;
-      pre[i] = sg.first_item;
-      if (i + 1u == n) pre[n] = items;
-    }
-  }
 }
 
 // ---- launches 2 and 4 ----
 // The present mask of this lane's slots [la, lb) of an item that ends at slot e1, whose runs -- len bytes at address src, fields of k bits --
-// are walked from the checkpoint cp on: bit t is slot la + t's.  first, payload and value: the wave's room for a batch of runs.
-__device__ __forceinline__ uint32_t item_mask(uint8_t* lds, uint64_t* first, uint64_t* payload, uint32_t* value, uint64_t src, uint64_t len, uint32_t k, uint32_t level,
+// are walked from the checkpoint cp on: bit t is slot la + t's.  batch: the wave's room for a batch of runs.
+__device__ __forceinline__ uint32_t item_mask(uint8_t* lds, RunBatch batch, uint64_t src, uint64_t len, uint32_t k, uint32_t level,
                                               Checkpoint cp, uint64_t e1, uint64_t la, uint64_t lb, uint32_t lane) {
   Stage rd(lds, src, len, lane);
   BrotliAmdUnrleWalk st = {cp.off, cp.first};
   uint32_t mask = 0;
   bool more = true;
   while (more && st.elems < e1) {
-    // the next runs, up to kBatch of them: every lane walks, lane 0 keeps
-    const uint64_t batch_lo = st.elems;
-    uint32_t nr = 0;
-    lds_sync();   // (the batch before is done with)
-    while (more && nr < kBatch && st.elems < e1) {
-      rd.ensure(st.off);
-      const BrotliAmdUnrleRun run = brotli_amd_unrle_run(rd, len, k, st);
-      if (run.kind == BROTLI_AMD_UNRLE_STOP) { more = false; break; }   // (not below count)
-      if (lane == 0u) {
-        first[nr] = st.elems;
-        payload[nr] = run.kind == BROTLI_AMD_UNRLE_RLE ? BROTLI_AMD_UNRLE_NONE : run.payload;
-        value[nr] = run.value;
-      }
-      nr++;
-      st.off = run.next; st.elems += run.count;
-      more = run.status == BROTLI_AMD_UNRLE_OK;
-    }
-    if (lane == 0u) first[nr] = st.elems;
-    lds_sync();
+    batch.collect(rd, len, k, st, more, e1, lane);
     // this lane's slots among the batch's: run after run, each part's bits at once
-    const uint64_t a = la > batch_lo ? la : batch_lo, b = lb < st.elems ? lb : st.elems;
+    const uint64_t a = la > batch.lo ? la : batch.lo, b = lb < st.elems ? lb : st.elems;
     if (a < b) {
-      uint32_t r = 0;
-      { uint32_t hi = nr; while (hi - r > 1u) { const uint32_t m = (r + hi) >> 1; if (first[m] <= a) r = m; else hi = m; } }
-      uint64_t r_first = first[r], r_end = first[r + 1u];
+      RunCursor<false> run(batch, a);
       uint64_t e = a;
       while (e < b) {
-        while (e >= r_end) { r++; r_first = r_end; r_end = first[r + 1u]; }
-        const uint64_t stop = b < r_end ? b : r_end;
-        mask |= brotli_amd_unnull_run_mask(src, payload[r], value[r], k, level, e - r_first, (uint32_t)(stop - e)) << (uint32_t)(e - la);
+        run.seek(e);
+        const uint64_t stop = b < run.end ? b : run.end;
+        mask |= brotli_amd_unnull_run_mask(src, batch.payload[run.r], batch.value[run.r], k, level, e - run.first, (uint32_t)(stop - e)) << (uint32_t)(e - la);
         e = stop;
       }
     }
@@ -153,10 +123,10 @@ __global__ __launch_bounds__(kThreads) void brotli_amd_unnull_count_kernel(const
     if (cp.off != BROTLI_AMD_UNRLE_NONE) {   // (beyond count otherwise; the same in every lane)
       const Seg sg = segs[i];
       uint64_t e0, e1;
-      brotli_amd_unnull_item_range(results[i].count, sg.cap, j, kItem, &e0, &e1);
+      brotli_amd_unrle_item_range(results[i].count, sg.cap, j, kItem, &e0, &e1);
       if (e0 < e1) {
         const uint64_t la = e0 + (uint64_t)kPerLane * lane, lb = la + kPerLane < e1 ? la + kPerLane : e1;   // this lane's slots
-        sum = brotli_amd_unnull_popcount(item_mask(stage[wave], run_first[wave], run_payload[wave], run_value[wave],
+        sum = brotli_amd_unnull_popcount(item_mask(stage[wave], RunBatch(run_first[wave], run_payload[wave], run_value[wave]),
                                                    (uint64_t)(uintptr_t)sg.src + brotli_amd_unnull_runs_off(sg.flags), run_lens[i], results[i].bits, sg.level, cp, e1, la, lb, lane));
 #pragma unroll
         for (uint32_t off = 32; off != 0u; off >>= 1) sum += (uint32_t)__shfl_down((int)sum, off, 64);
@@ -168,7 +138,8 @@ __global__ __launch_bounds__(kThreads) void brotli_amd_unnull_count_kernel(const
 
 // The slots [g0, g0 + kGroup) below m of a lane whose m slots (1 .. 16) begin at address at0 and whose present mask is `mask`, the first
 // present one of rank rank0: their values out of the V dense ones of W bytes at `values`, and stored -- single slots in front of `head` and
-// from `tail` on, whole 16-byte words between.
+// from `tail` on, whole 16-byte words between.  (undict's store rule, in lines of its own as there: one helper for both measured slower in
+// both, profiles/run_items.txt.)
 template <uint32_t W>
 __device__ __forceinline__ void gather_and_store(uint64_t values, uint64_t V, uint64_t rank0, uint32_t mask, uint64_t at0, uint32_t m, uint32_t head, uint32_t tail,
                                                  uint32_t g0, Word16* word) {
@@ -207,11 +178,11 @@ __global__ __launch_bounds__(kThreads) void brotli_amd_unnull_expand_kernel(cons
     const Result res = results[i];   // (what the walk left: present and missing are not looked at)
     const uint32_t w = sg.width;
     uint64_t e0, e1;
-    brotli_amd_unnull_item_range(res.count, sg.cap, g - pre[i], kItem, &e0, &e1);
+    brotli_amd_unrle_item_range(res.count, sg.cap, g - pre[i], kItem, &e0, &e1);
     if (e0 >= e1) continue;
     const uint64_t la = e0 + (uint64_t)kPerLane * lane, lb = la + kPerLane < e1 ? la + kPerLane : e1;   // this lane's slots
     const uint32_t m = la < lb ? (uint32_t)(lb - la) : 0u;
-    const uint32_t mask = item_mask(stage[wave], run_first[wave], run_payload[wave], run_value[wave], (uint64_t)(uintptr_t)sg.src + brotli_amd_unnull_runs_off(sg.flags),
+    const uint32_t mask = item_mask(stage[wave], RunBatch(run_first[wave], run_payload[wave], run_value[wave]), (uint64_t)(uintptr_t)sg.src + brotli_amd_unnull_runs_off(sg.flags),
                                     run_lens[i], res.bits, sg.level, cp, e1, la, lb, lane);
     // this lane's first rank: the item's carry-in and the present slots of the lanes below
     const uint32_t pc = brotli_amd_unnull_popcount(mask);
@@ -270,50 +241,17 @@ __global__ __launch_bounds__(kThreads) void brotli_amd_unnull_expand_kernel(cons
   }
 }
 
-constexpr uint64_t pad16(uint64_t bytes) { return (bytes + 15u) & ~(uint64_t)15; }
-constexpr uint64_t pre_bytes(uint32_t n) { return pad16(((uint64_t)n + 1u) * sizeof(uint64_t)); }
-
 }  // namespace
 
 // the scratch of a launch over `units` units of n segments -- a unit a segment and a unit an item --: the results first, then the runs' lengths,
 // the items' prefix array, the checkpoints, the tile records and the carries
 extern "C" uint64_t brotli_amd_unnull_scratch_bytes(uint64_t units, uint32_t n) {
-  return pad16((uint64_t)n * sizeof(Result)) + pad16((uint64_t)n * sizeof(uint64_t)) + pre_bytes(n) + (units - n) * (sizeof(Checkpoint) + sizeof(Tile) + sizeof(uint64_t));
+  return brotli_amd_wave::ItemScratch<Result, Checkpoint, true, true>::bytes(units - n, n);
 }
 
 // units: n + the items of all segments (the host has the table); d_scratch: brotli_amd_unnull_scratch_bytes of device memory, 16-byte aligned;
 // ev[0..4], where not NULL, are recorded in front of, between and behind the four launches
 extern "C" hipError_t brotli_amd_launch_unnull(const void* d_table, uint32_t n, uint64_t units, void* d_scratch, hipStream_t stream, const hipEvent_t* ev) {
-  if (n == 0u) return hipSuccess;
-  const Seg* d_segs = static_cast<const Seg*>(d_table);
-  const uint64_t items = units - n;
-  uint8_t* at = static_cast<uint8_t*>(d_scratch);
-  Result* results = reinterpret_cast<Result*>(at); at += pad16((uint64_t)n * sizeof(Result));
-  uint64_t* run_lens = reinterpret_cast<uint64_t*>(at); at += pad16((uint64_t)n * sizeof(uint64_t));
-  uint64_t* pre = reinterpret_cast<uint64_t*>(at); at += pre_bytes(n);
-  Checkpoint* ckpts = reinterpret_cast<Checkpoint*>(at); at += items * sizeof(Checkpoint);
-  Tile* tiles = reinterpret_cast<Tile*>(at); at += items * sizeof(Tile);
-  uint64_t* carries = reinterpret_cast<uint64_t*>(at);
-  hipError_t e = hipSuccess;
-  uint32_t grid = 0;
-  if (items != 0u && (e = hipMemsetAsync(ckpts, 0xFF, (size_t)items * sizeof(Checkpoint), stream)) != hipSuccess) return e;
-  if ((e = brotli_amd_wave::wave_grid(n, kWaves, &grid)) != hipSuccess) return e;
-  if (ev && (e = hipEventRecord(ev[0], stream)) != hipSuccess) return e;
-  hipLaunchKernelGGL(brotli_amd_unnull_walk_kernel, dim3(grid), dim3(kThreads), 0, stream, d_segs, n, items, results, run_lens, pre, ckpts);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  if (ev && (e = hipEventRecord(ev[1], stream)) != hipSuccess) return e;
-  if (items != 0u) {
-    if ((e = brotli_amd_wave::wave_grid(items, kWaves, &grid)) != hipSuccess) return e;
-    hipLaunchKernelGGL(brotli_amd_unnull_count_kernel, dim3(grid), dim3(kThreads), 0, stream, d_segs, n, items, results, run_lens, pre, ckpts, tiles);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
-  if (ev && (e = hipEventRecord(ev[2], stream)) != hipSuccess) return e;
-  if (items != 0u && (e = brotli_amd_launch_tile_carries(tiles, carries, items, stream)) != hipSuccess) return e;
-  if (ev && (e = hipEventRecord(ev[3], stream)) != hipSuccess) return e;
-  if (items != 0u) {
-    hipLaunchKernelGGL(brotli_amd_unnull_expand_kernel, dim3(grid), dim3(kThreads), 0, stream, d_segs, n, items, results, run_lens, pre, ckpts, carries);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
-  if (ev && (e = hipEventRecord(ev[4], stream)) != hipSuccess) return e;
-  return hipSuccess;
+  return brotli_amd_wave::launch_walk_count_carry_expand<Seg, Result, Checkpoint>(brotli_amd_unnull_walk_kernel, brotli_amd_unnull_count_kernel, brotli_amd_unnull_expand_kernel, d_table,
+                                                                                  n, units, d_scratch, stream, ev);
 }

@@ -100,6 +100,12 @@ struct BrotliAmdUnrleCheckpoint {
 };
 
 BROTLI_AMD_UNRLE_HD uint64_t brotli_amd_unrle_items(uint64_t cap, uint32_t item_elems) { return (cap + item_elems - 1u) / item_elems; }
+// the elements [*e0, *e1) of item j of a segment that delivers min(count, cap) elements (*e0 >= *e1: none)
+BROTLI_AMD_UNRLE_HD void brotli_amd_unrle_item_range(uint64_t count, uint64_t cap, uint64_t j, uint32_t item_elems, uint64_t* e0, uint64_t* e1) {
+  const uint64_t end = count < cap ? count : cap;
+  *e0 = j * item_elems;
+  *e1 = *e0 + item_elems < end ? *e0 + item_elems : end;
+}
 // The items [*j0, *j1) whose first element lies in the run of `count` values from element `first` on, below cap.
 BROTLI_AMD_UNRLE_HD void brotli_amd_unrle_run_items(uint64_t first, uint64_t count, uint64_t cap, uint32_t item_elems, uint64_t* j0, uint64_t* j1) {
   const uint64_t end = first + count < cap ? first + count : cap;
@@ -164,9 +170,9 @@ inline BrotliAmdUnrleResult brotli_amd_unrle_host_walk(const BrotliAmdUnrleSeg& 
 template <class Each>
 inline void brotli_amd_unrle_host_item_each(uint64_t src, uint64_t len, uint64_t cap, uint64_t count, uint32_t k, BrotliAmdUnrleCheckpoint cp, uint64_t j,
                                             uint32_t item_elems, Each each) {
-  const uint64_t end = count < cap ? count : cap, e0 = j * item_elems;
-  if (cp.off == BROTLI_AMD_UNRLE_NONE || e0 >= end) return;
-  const uint64_t e1 = e0 + item_elems < end ? e0 + item_elems : end;
+  uint64_t e0, e1;
+  brotli_amd_unrle_item_range(count, cap, j, item_elems, &e0, &e1);
+  if (cp.off == BROTLI_AMD_UNRLE_NONE || e0 >= e1) return;
   BrotliAmdUnrleDirect rd = {src};
   BrotliAmdUnrleWalk st = {cp.off, cp.first};
   for (uint64_t e = e0; e < e1;) {

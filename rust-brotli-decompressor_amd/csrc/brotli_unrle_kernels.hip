@@ -21,21 +21,23 @@
 #include <hip/hip_runtime.h>
 
 #include "brotli_device_abi.h"
+#include "brotli_run_items.h"    // the run batch, the walk's frame, the scratch and the launcher
 #include "brotli_seg_walk.h"
 #include "brotli_unrle.h"
 #include "brotli_wave_stage.h"   // the wave's view of its source through LDS, same(), Word16, wave_grid
 
 namespace {
 
-constexpr uint32_t kThreads = BROTLI_AMD_SEG_THREADS, kWaves = kThreads / 64u;
+constexpr uint32_t kThreads = brotli_amd_wave::kSegThreads, kWaves = brotli_amd_wave::kSegWaves;
 constexpr uint32_t kChunk = BROTLI_AMD_UNRLE_WALK_CHUNK, kItem = BROTLI_AMD_UNRLE_ITEM_ELEMS;
 constexpr uint32_t kPerLane = kItem / 64u;   // neighbouring elements of a lane
-constexpr uint32_t kBatch = 64;              // runs collected at a time
+constexpr uint32_t kBatch = brotli_amd_wave::kRunBatch;
 
 static_assert(kChunk == brotli_amd_wave::kStageChunk, "the chunk the stage has");
 static_assert(kPerLane * 64u == kItem && kPerLane % 16u == 0u, "a lane's elements are whole 16-byte words at every width");
 
-using brotli_amd_wave::lds_sync;
+using brotli_amd_wave::RunBatch;
+using brotli_amd_wave::RunCursor;
 using brotli_amd_wave::same;
 using brotli_amd_wave::Stage;
 using brotli_amd_wave::Word16;
@@ -48,20 +50,10 @@ typedef BrotliAmdUnrleCheckpoint Checkpoint;
 __global__ __launch_bounds__(kThreads) void brotli_amd_unrle_walk_kernel(const Seg* __restrict__ segs, uint32_t n, uint64_t items, Result* __restrict__ results,
                                                                          uint64_t* __restrict__ pre, Checkpoint* __restrict__ ckpts) {
   __shared__ __attribute__((aligned(16))) uint8_t stage[kWaves][2u * kChunk];
-  const uint32_t lane = threadIdx.x & 63u, wave = same(threadIdx.x >> 6);
-  for (uint64_t i = (uint64_t)blockIdx.x * kWaves + wave; i < n; i += (uint64_t)gridDim.x * kWaves) {
-    const Seg sg = segs[i];
-    Stage rd(stage[wave], (uint64_t)(uintptr_t)sg.src, sg.len, lane);
-    Checkpoint* mine = ckpts + sg.first_item;
-    const Result res = brotli_amd_unrle_walk(rd, sg.len, sg.cap, sg.width, sg.bits, sg.flags, kItem, [&](uint64_t j0, uint64_t j1, uint64_t off, uint64_t first) {
-      for (uint64_t j = j0 + lane; j < j1; j += 64u) mine[j] = Checkpoint{off, first};
-    });
-    if (lane == 0u) {
-      results[i] = res;
-      pre[i] = sg.first_item;
-      if (i + 1u == n) pre[n] = items;
-    }
-  }
+  brotli_amd_wave::walk_segments(
+      stage, segs, n, items, pre, ckpts,
+      [](const Seg& sg, Stage& rd, auto mark) { return brotli_amd_unrle_walk(rd, sg.len, sg.cap, sg.width, sg.bits, sg.flags, kItem, mark); },
+      [&](uint64_t i, const Seg&, const Result& res) { results[i] = res; });
 }
 
 // ---- launch 2 ----
@@ -72,9 +64,7 @@ __global__ __launch_bounds__(kThreads) void brotli_amd_unrle_expand_kernel(const
   __shared__ uint64_t run_payload[kWaves][kBatch];      // (BROTLI_AMD_UNRLE_NONE: an RLE run)
   __shared__ uint32_t run_value[kWaves][kBatch];
   const uint32_t lane = threadIdx.x & 63u, wave = same(threadIdx.x >> 6);
-  uint64_t* const first = run_first[wave];
-  uint64_t* const payload = run_payload[wave];
-  uint32_t* const value = run_value[wave];
+  RunBatch batch(run_first[wave], run_payload[wave], run_value[wave]);
   for (uint64_t g = (uint64_t)blockIdx.x * kWaves + wave; g < items; g += (uint64_t)gridDim.x * kWaves) {
     const Checkpoint cp = ckpts[g];
     if (cp.off == BROTLI_AMD_UNRLE_NONE) continue;   // (beyond count; the same in every lane)
@@ -83,43 +73,22 @@ __global__ __launch_bounds__(kThreads) void brotli_amd_unrle_expand_kernel(const
     const Result res = results[i];
     const uint64_t src = (uint64_t)(uintptr_t)sg.src, dst = (uint64_t)(uintptr_t)sg.dst;
     const uint32_t k = res.bits, w = sg.width, per_word = 16u / w;
-    const uint64_t end = res.count < sg.cap ? res.count : sg.cap, e0 = (g - pre[i]) * kItem;
-    if (e0 >= end) continue;
-    const uint64_t e1 = e0 + kItem < end ? e0 + kItem : end;
+    uint64_t e0, e1;
+    brotli_amd_unrle_item_range(res.count, sg.cap, g - pre[i], kItem, &e0, &e1);
+    if (e0 >= e1) continue;
     const uint64_t la = e0 + (uint64_t)kPerLane * lane, lb = la + kPerLane < e1 ? la + kPerLane : e1;   // this lane's elements
     Stage rd(stage[wave], src, sg.len, lane);
     BrotliAmdUnrleWalk st = {cp.off, cp.first};
     bool more = true;
     while (more && st.elems < e1) {
-      // the next runs, up to kBatch of them: every lane walks, lane 0 keeps
-      const uint64_t batch_lo = st.elems;
-      uint32_t nr = 0;
-      lds_sync();   // (the batch before is done with)
-      while (more && nr < kBatch && st.elems < e1) {
-        rd.ensure(st.off);
-        const BrotliAmdUnrleRun run = brotli_amd_unrle_run(rd, sg.len, k, st);
-        if (run.kind == BROTLI_AMD_UNRLE_STOP) { more = false; break; }   // (not below count)
-        if (lane == 0u) {
-          first[nr] = st.elems;
-          payload[nr] = run.kind == BROTLI_AMD_UNRLE_RLE ? BROTLI_AMD_UNRLE_NONE : run.payload;
-          value[nr] = run.value;
-        }
-        nr++;
-        st.off = run.next; st.elems += run.count;
-        more = run.status == BROTLI_AMD_UNRLE_OK;
-      }
-      if (lane == 0u) first[nr] = st.elems;
-      lds_sync();
+      batch.collect(rd, sg.len, k, st, more, e1, lane);
       // this lane's elements among the batch's
-      const uint64_t a = la > batch_lo ? la : batch_lo, b = lb < st.elems ? lb : st.elems;
+      const uint64_t a = la > batch.lo ? la : batch.lo, b = lb < st.elems ? lb : st.elems;
       if (a >= b) continue;
-      uint32_t r = 0;
-      { uint32_t hi = nr; while (hi - r > 1u) { const uint32_t m = (r + hi) >> 1; if (first[m] <= a) r = m; else hi = m; } }
-      uint64_t r_first = first[r], r_end = first[r + 1u], r_payload = payload[r];
-      uint32_t r_value = value[r];
+      RunCursor<true> run(batch, a);
       auto element = [&](uint64_t e) {
-        while (e >= r_end) { r++; r_first = r_end; r_end = first[r + 1u]; r_payload = payload[r]; r_value = value[r]; }
-        return brotli_amd_unrle_element(src, r_payload, r_value, k, e - r_first);
+        run.seek(e);
+        return brotli_amd_unrle_element(src, run.payload, run.value, k, e - run.first);
       };
       for (uint64_t e = a; e < b;) {
         const uint64_t at = dst + e * w;
@@ -137,8 +106,6 @@ __global__ __launch_bounds__(kThreads) void brotli_amd_unrle_expand_kernel(const
   }
 }
 
-constexpr uint64_t pre_bytes(uint32_t n) { return (((uint64_t)n + 1u) * sizeof(uint64_t) + 15u) & ~(uint64_t)15; }
-
 }  // namespace
 
 extern "C" uint32_t brotli_amd_unrle_item_elems(void) { return kItem; }
@@ -146,31 +113,11 @@ extern "C" uint32_t brotli_amd_unrle_walk_chunk(void) { return kChunk; }
 // the scratch of a launch over `units` units of n segments -- a unit a segment and a unit an item --: the results first, then the items' prefix
 // array and the checkpoints
 extern "C" uint64_t brotli_amd_unrle_scratch_bytes(uint64_t units, uint32_t n) {
-  return (uint64_t)n * sizeof(Result) + pre_bytes(n) + (units - n) * sizeof(Checkpoint);
+  return brotli_amd_wave::ItemScratch<Result, Checkpoint, false, false>::bytes(units - n, n);
 }
 
 // units: n + the items of all segments (the host has the table); d_scratch: brotli_amd_unrle_scratch_bytes of device memory, 16-byte aligned;
 // ev[0..2], where not NULL, are recorded in front of, between and behind the two launches
 extern "C" hipError_t brotli_amd_launch_unrle(const void* d_table, uint32_t n, uint64_t units, void* d_scratch, hipStream_t stream, const hipEvent_t* ev) {
-  if (n == 0u) return hipSuccess;
-  const BrotliAmdUnrleSeg* d_segs = static_cast<const BrotliAmdUnrleSeg*>(d_table);
-  const uint64_t items = units - n;
-  Result* results = static_cast<Result*>(d_scratch);
-  uint64_t* pre = reinterpret_cast<uint64_t*>(results + n);
-  Checkpoint* ckpts = reinterpret_cast<Checkpoint*>(reinterpret_cast<uint8_t*>(pre) + pre_bytes(n));
-  hipError_t e = hipSuccess;
-  uint32_t grid = 0;
-  if (items != 0u && (e = hipMemsetAsync(ckpts, 0xFF, (size_t)items * sizeof(Checkpoint), stream)) != hipSuccess) return e;
-  if ((e = brotli_amd_wave::wave_grid(n, kWaves, &grid)) != hipSuccess) return e;
-  if (ev && (e = hipEventRecord(ev[0], stream)) != hipSuccess) return e;
-  hipLaunchKernelGGL(brotli_amd_unrle_walk_kernel, dim3(grid), dim3(kThreads), 0, stream, d_segs, n, items, results, pre, ckpts);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  if (ev && (e = hipEventRecord(ev[1], stream)) != hipSuccess) return e;
-  if (items != 0u) {
-    if ((e = brotli_amd_wave::wave_grid(items, kWaves, &grid)) != hipSuccess) return e;
-    hipLaunchKernelGGL(brotli_amd_unrle_expand_kernel, dim3(grid), dim3(kThreads), 0, stream, d_segs, n, items, results, pre, ckpts);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
-  if (ev && (e = hipEventRecord(ev[2], stream)) != hipSuccess) return e;
-  return hipSuccess;
+  return brotli_amd_wave::launch_walk_expand<Seg, Result, Checkpoint>(brotli_amd_unrle_walk_kernel, brotli_amd_unrle_expand_kernel, d_table, n, units, d_scratch, stream, ev);
 }

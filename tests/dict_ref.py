@@ -54,6 +54,27 @@ def random_dictionary(rnd, entries, w):
     return bytes(rnd.getrandbits(8) for _ in range(entries * w))
 
 
+def many_runs_plan(seed, runs=900, k=9):
+    """short runs of k-bit indices, so that an item of 1024 elements holds several batches of 64 runs: every fifth is a packed run of 8 values,
+    the others are repeated runs of 1 + i % 3.  With 900 runs: 2880 elements in three items of 321, 320 and 260 runs, and every batch's first
+    element lies inside a lane's 16 elements, none at a lane's edge"""
+    rnd = random.Random(seed)
+    top = (1 << k) - 1
+    return [("packed", [rnd.randint(0, top) for _ in range(8)]) if i % 5 == 4 else ("rle", 1 + i % 3, rnd.randint(0, top)) for i in range(runs)]
+
+
+def runs_per_item(plan, item):
+    """the runs of a plan that hold an element of each item of `item` elements"""
+    at, out = 0, []
+    for run in plan:
+        m = run[1] if run[0] == "rle" else len(run[1])
+        for j in range(at // item, (at + m - 1) // item + 1):
+            out += [0] * (j + 1 - len(out))
+            out[j] += 1
+        at += m
+    return out
+
+
 def short_table(count=3000, seed=12, max_k=32):
     """`count` short segments of mixed shapes, flags, capacities and endings (rle_ref.short_table's), each with a dictionary of its own size at
     any alignment in one dictionary buffer: larger than its indices, smaller, of one entry, of none.  Fields of up to max_k bits; with max_k <= 10

@@ -95,6 +95,28 @@ def test_one_long_segment_and_a_second_behind_it(pkg, batch, dev, sentinel):
         assert got[0][3] == got[1][3] == ref.OK and got[1][4] == 7 and got[0][5] > 0 and got[1][5] == 0
 
 
+def test_more_than_64_runs_in_one_item(pkg, batch, dev, sentinel):
+    """items of several batches of 64 runs, every batch's edge inside one lane's 16 elements, at every width and at destination skews 0 and 1;
+    a dictionary of 400 entries under 9-bit indices: bad and first_bad come from more than one batch"""
+    C, k, D = pkg.unrle_item_elems(), 9, 400
+    plan = ref.many_runs_plan(61)
+    assert max(ref.runs_per_item(plan, C)) > 64
+    data = rle_ref.encode(plan, k)
+    count = rle_ref.decode(data, k, 8)[1][0]
+    assert count == len(rle_ref.plan_values(plan)) == 2880
+    src, offs = _pack([data])
+    d_src = _upload(src)
+    room = _room(ref.random_dictionary(random.Random(62), D, 8), (1 << k) * 8 + 64, sentinel)
+    segs, d_at = [], 0
+    for skew in (0, 1):
+        for w in ref.WIDTHS:
+            d_at = H.next_at(d_at, skew)
+            segs.append((offs[0], len(data), d_at, count, k, w, 0, 0, D))
+            d_at += count * w
+    got = _undict(batch, dev, src, sentinel, segs, d_at + 64, room, d_src=d_src)
+    assert all(r[:4] == (count, len(data), len(plan), ref.OK) and r[5] > 0 for r in got)
+
+
 def test_a_payload_across_the_walk_chunks(pkg, batch, dev, sentinel):
     """packed payloads that skip more than two of the walk's chunks, between short runs, at several skews of the source"""
     chunk = pkg.unrle_walk_chunk()

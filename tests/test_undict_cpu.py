@@ -163,6 +163,25 @@ def test_bad_indices_across_items_in_any_order(pkg, item):
     assert seen == {(lead + len(values), len(data), 2, ref.OK, k, len(where), lead + where[0])}
 
 
+@pytest.mark.parametrize("item", [64, 0])
+def test_more_than_64_runs_in_one_item(pkg, item):
+    """the plan of the device's test of the same name -- at the default item size, three items of several batches of runs each --, at every width
+    and at destination skews 0 and 1, the items in a shuffled order"""
+    k, D = 9, 400
+    plan = ref.many_runs_plan(61)
+    assert max(ref.runs_per_item(plan, pkg.unrle_item_elems())) > 64
+    data = rle_ref.encode(plan, k)
+    dictionary = ref.random_dictionary(random.Random(62), D, 8)
+    segs, d_at = [], 0
+    for skew in (0, 1):
+        for w in ref.WIDTHS:
+            d_at += (skew - d_at) % 16
+            segs.append((2, len(data), d_at, 2880, k, w, 0, 0, D))
+            d_at += 2880 * w
+    res = check(pkg, b"\x99\x99" + data + b"\x99", dictionary, segs, d_at + 40, item_elems=item, order_seed=7)
+    assert all(r[:4] == (2880, len(data), len(plan), ref.OK) and r[5] > 0 for r in res)
+
+
 def test_capacities(pkg):
     """a capacity that cuts in front of the only bad index (bad 0) and behind it; counting alone: 0 and none"""
     rnd = random.Random(45)
