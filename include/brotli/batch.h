@@ -761,7 +761,8 @@ BROTLI_DEC_API int BrotliAmdDebugUnrleHost(uint32_t n, const uint8_t* src, size_
  * (csrc/brotli_undbp.h, csrc/brotli_undbp_kernels.hip).
  *
  * OUT OF SCOPE: the byte part of DELTA_LENGTH_BYTE_ARRAY (`consumed` says where it begins); DELTA_BYTE_ARRAY's prefix copies; page framing --
- * thrift headers, v2's level sections --; a speculative parallel walk of one long segment; sign extension of elements narrower than 8 bytes. */
+ * thrift headers, v2's level sections --; a speculative parallel walk of one long segment; sign extension of elements narrower than 8 bytes.
+ * Byte arrays behind a DICTIONARY are the undict-bytes calls' below. */
 #define BROTLI_AMD_UNDBP_OK 0u
 #define BROTLI_AMD_UNDBP_BAD_HEADER 1u
 #define BROTLI_AMD_UNDBP_BAD_WIDTH 2u
@@ -861,9 +862,9 @@ BROTLI_DEC_API int BrotliAmdDebugUndbpHost(uint32_t n, const uint8_t* src, size_
  * together.  The dictionary is read through the caches.  Bad indices are summed up inside the wave; an item that has some adds them to its
  * segment's result with one atomic add and one atomic minimum (csrc/brotli_undict.h, csrc/brotli_undict_kernels.hip).
  *
- * OUT OF SCOPE: BYTE_ARRAY, FIXED_LEN_BYTE_ARRAY and INT96 dictionaries (entries of 12, 16 or variable bytes); page framing; plain index arrays
- * (a framework's gather does those); a parallel walk of one long segment.  Definition levels and the spreading of values over nulls are the
- * unnull calls' below. */
+ * OUT OF SCOPE: FIXED_LEN_BYTE_ARRAY and INT96 dictionaries (entries of 12 or 16 bytes); page framing; plain index arrays (a framework's
+ * gather does those); a parallel walk of one long segment.  BYTE_ARRAY dictionaries -- entries of variable bytes -- are the undict-bytes
+ * calls' below.  Definition levels and the spreading of values over nulls are the unnull calls' below. */
 #define BROTLI_AMD_UNDICT_WIDTH_BYTE 1u          /* BROTLI_AMD_UNRLE_WIDTH_BYTE's meaning */
 #define BROTLI_AMD_UNDICT_NO_STREAM 0xFFFFFFFFu  /* dict_streams[i]: the dictionary is d_dicts[i], not a stream of the decode call */
 
@@ -920,6 +921,144 @@ BROTLI_DEC_API int BrotliAmdDebugUndictHost(uint32_t n, const uint8_t* src, size
                                            const uint64_t* caps, const uint64_t* dict_offs, const uint64_t* dict_entries, const uint8_t* bits,
                                            const uint8_t* widths, const uint8_t* flags /* or NULL */, uint32_t src_skew, uint32_t dst_skew,
                                            uint32_t dict_skew, uint32_t item_elems, uint32_t order_seed, BrotliAmdUndictResult* results);
+
+/* ---- Undict for byte arrays on the device: dictionary-index runs of outputs back into OFFSETS AND BYTES ----
+ *
+ * String columns are the columns that writers dictionary-encode most reliably: a column chunk is one dictionary page -- PLAIN BYTE_ARRAY: per
+ * entry a 4-byte little-endian length, then that many bytes -- and data pages whose body is what undict walks: a width byte k, then RLE /
+ * bit-packed runs of k-bit indices.  These calls take the index runs and such a dictionary and write an Arrow string column, (offsets, data),
+ * in one call: the indices never reach memory, and every one of them is checked against D before it becomes an address.
+ *
+ * THE SEGMENT AND ITS PARAMETERS.  A segment is an undict segment: src[0, len) is read by unrle's grammar EXACTLY -- headers, the two payload
+ * kinds, k == 0, the stops, and count, consumed, runs, status and bits of the result --, with `bits` of 0 .. 32 (or
+ * BROTLI_AMD_UNDICT_BYTES_WIDTH_BYTE: the segment's first byte is k) and a capacity cap in ELEMENTS.  Instead of an element width it has:
+ *
+ * THE DICTIONARY.  dict_len bytes at dict, device memory of any alignment, read as PLAIN byte arrays: entry e is a little-endian uint32 length
+ * L_e, then L_e bytes.  dict_entries bounds how many entries are taken -- the page header's num_values --; BROTLI_AMD_UNDICT_BYTES_ALL: as many
+ * as the bytes hold.  The dictionary ends at dict_entries entries, at dict_len exactly (dict_status BROTLI_AMD_UNDICT_BYTES_DICT_OK), or at
+ * the first entry whose 4 length bytes or L_e value bytes the end cuts: BROTLI_AMD_UNDICT_BYTES_DICT_CUT; the entries in front of the cut
+ * count, and D is their number.  Bytes left over behind dict_entries whole entries are no error.  Entry positions are 32-bit: dict_len >= 2^32
+ * is refused, and a length that does not fit is simply a cut.
+ *
+ * THE OUTPUTS.  m = min(count, cap); element i < m has the index idx_i, by unrle's rule (an RLE run's value is not masked to k bits).  Where
+ * idx_i < D the element's bytes are entry idx_i's, L_i of them; where idx_i >= D the element is EMPTY (L_i = 0), nothing is read through the
+ * index, and the element is counted as bad.  bytes = the sum of L_i over i < m, 64 bits, independent of data_cap.
+ *   OFFSETS  offsets[i] = offset_base + the sum of L_j over j < i, for i = 0 .. m, little-endian integers of 4 bytes -- of 8 with
+ *            BROTLI_AMD_UNDICT_BYTES_OFFSETS64 --, truncated to that width, at d_offsets.  With BROTLI_AMD_UNDICT_BYTES_ENDS_ONLY offsets[0] is
+ *            not written, d_offsets points at offsets[1], and m entries are written: the pages of one column chunk append into one Arrow array
+ *            without two segments writing the same word.  d_offsets == NULL: no offsets.
+ *   DATA     d_data[0, min(bytes, data_cap)) is the concatenation of the elements' bytes, cut at data_cap byte-exactly.  d_data == NULL needs
+ *            data_cap == 0.
+ * A call with cap != 0 and neither destination only MEASURES: the caller knows its rows from the page header but not its bytes, and
+ * result.bytes is how it sizes d_data for a second call.  (cap is the page's rows, not a large constant: as in unrle, a call's room on the
+ * device grows with the items that its capacities name.)  cap == 0 only counts, as in unrle: nothing of the dictionary is looked at.
+ *
+ * RESULT.  BrotliAmdUndictBytesResult, 80 bytes: undict's seven fields in undict's order and meaning, then bytes, dict_entries (the D that was
+ * used), dict_consumed (the bytes of the D entries), dict_status and a reserved 0.  Nothing in it depends on how the work was shared out.  A
+ * skipped stream gives zeros with first_bad UINT64_MAX.
+ *
+ * LOADS AND STORES.  No byte outside [d_data, d_data + min(bytes, data_cap)) and outside the offsets named above is written.  Nothing outside
+ * the 16-byte-aligned spans around [src, src + len) and [dict, dict + dict_len) is read.  OUT OF PLACE: no destination overlaps a source, a
+ * dictionary or another destination.  This is stated, not checked.
+ *
+ * Examples (k, bytes, dictionary): 3, 03 88 C6 FA over the eight entries "", "a", "bc", ...: the eight in order;  3, 10 05 with D = 5: eight
+ * empty elements, bad 8, first_bad 0, bytes 0;  the same with D = 6: 8 x entry 5;  0, 07: 24 x entry 0;  a dictionary whose third entry is cut
+ * inside its length bytes: D = 2, DICT_CUT.
+ *
+ * REFUSED ON THE HOST, in front of everything that touches the device, with a text that names the segment: unknown flag bits; bits > 32
+ * without the width-byte flag; cap > 2^56; data_cap != 0 with a NULL d_data; a NULL dict with dict_len != 0 and cap != 0; dict_len >= 2^32.
+ *
+ * A call is five launches in stream order, and no block ever waits for another -- no spins, no flags, no atomics on offsets or data.
+ * 1. THE DICTIONARY WALK: the host makes the table of the call's DISTINCT dictionaries -- segments that name the same (pointer, length, bound)
+ * share one record, the normal case for the pages of a chunk --; one wave a dictionary follows its length chain and writes starts[e], the
+ * position of entry e's first value byte, for e = 0 .. D -- a sentinel behind the last, so that L_e = starts[e + 1] - 4 - starts[e] for every
+ * e < D.  2. THE RLE WALK: unrle's, as it is.  3. THE LENGTHS, one wave an item: the indices, each compared with D in 64 bits by the one function
+ * that turns (starts, D, idx) into (position, length, bad), the lengths summed into the item's tile record; bad elements go to the segment's
+ * result with one atomic add and one atomic minimum.  4. THE CARRIES: undelta's carry launch.  5. THE EXPANSION, one wave an item: the lanes
+ * redo indices and lengths, a scan on top of the item's carry-in gives every element its offset; offsets go out as aligned 16-byte stores, single
+ * elements at the edges; the BYTES are written with the work split by the DESTINATION: the lanes stride over the aligned 16-byte words of the
+ * item's range, each finds its word's first element by a binary search of the item's offsets in LDS, puts the word together from consecutive
+ * elements' bytes and stores it once; the range's head and tail are single bytes (csrc/brotli_undict_bytes.h,
+ * csrc/brotli_undict_bytes_kernels.hip).  A measuring call runs the same launches with every store predicated off.
+ *
+ * One item -- 1024 elements -- is one wave's work whatever its bytes: splitting an item of very long strings over several waves is out of
+ * scope.  ALSO OUT OF SCOPE: PLAIN (non-dictionary) byte-array data pages; DELTA_LENGTH_BYTE_ARRAY and DELTA_BYTE_ARRAY; FIXED_LEN_BYTE_ARRAY
+ * and INT96 dictionaries; nullable string columns in one call -- unnull over byte arrays; a caller uses BrotliAmdBatchUnnullOutputs' counting
+ * call to find where a v1 index body begins --; page framing; keeping a dictionary's starts from one call to the next; a parallel walk of one
+ * long dictionary or segment. */
+#define BROTLI_AMD_UNDICT_BYTES_WIDTH_BYTE 1u   /* BROTLI_AMD_UNRLE_WIDTH_BYTE's meaning */
+#define BROTLI_AMD_UNDICT_BYTES_OFFSETS64 2u    /* offsets of 8 bytes */
+#define BROTLI_AMD_UNDICT_BYTES_ENDS_ONLY 4u    /* offsets[0] is not written, and d_offsets points at offsets[1] */
+#define BROTLI_AMD_UNDICT_BYTES_SKIP 8u         /* BrotliAmdBatchUndictBytesOutputs: the stream is skipped */
+#define BROTLI_AMD_UNDICT_BYTES_ALL 0xFFFFFFFFFFFFFFFFull   /* dict_entries: as many entries as the bytes hold */
+#define BROTLI_AMD_UNDICT_BYTES_DICT_OK 0u
+#define BROTLI_AMD_UNDICT_BYTES_DICT_CUT 1u
+
+typedef struct BrotliAmdUndictBytesResult {
+  uint64_t count;          /* values in all runs, whatever cap was */
+  uint64_t consumed;       /* unrle's table */
+  uint64_t runs;           /* runs that gave at least one value */
+  uint32_t status;         /* BROTLI_AMD_UNRLE_* */
+  uint32_t bits;           /* the k that was used */
+  uint64_t bad;            /* delivered elements whose index was >= D */
+  uint64_t first_bad;      /* the smallest such element index; UINT64_MAX: none */
+  uint64_t bytes;          /* of the delivered elements together, whatever data_cap was */
+  uint64_t dict_entries;   /* the D that was used */
+  uint64_t dict_consumed;  /* the dictionary's bytes that those entries take */
+  uint32_t dict_status;    /* BROTLI_AMD_UNDICT_BYTES_DICT_* */
+  uint32_t reserved;       /* 0 */
+} BrotliAmdUndictBytesResult;
+
+/* n segments in DEVICE memory: the runs in the src_lens[i] bytes at d_src[i], of fields of bits[i] bits, index the byte arrays of the
+ * dict_lens[i] bytes at d_dicts[i], at most dict_entries[i] of them (dict_entries == NULL: all ALL); the first caps[i] elements' offsets go to
+ * d_offsets[i] on top of offset_bases[i] (NULL: all 0) and their bytes to d_data[i], at most data_caps[i] of them, by flags[i] (NULL: all 0);
+ * results[i] says what segment i held.  d_offsets and d_data, or single entries of them, may be NULL (data_caps too, where d_data is): that
+ * destination is not written.  caps[i] == 0 only counts: d_dicts and dict_lens may be NULL where every capacity is 0.  The launches run on
+ * hip_stream, and the call waits on that stream.  n == 0 returns 0.  A negative value, and a BrotliAmdLastError text that names the segment
+ * and what was wrong, for a NULL batch, a NULL array (but those named) with n != 0, BROTLI_AMD_UNDICT_BYTES_SKIP and everything in the list
+ * above: all checked on the host in front of everything else, so nothing is launched and no byte is written. */
+BROTLI_DEC_API int BrotliAmdBatchUndictBytesSegments(BrotliAmdBatch* batch, uint32_t n, const void* const* d_src, const size_t* src_lens,
+                                                    void* const* d_offsets /* or NULL */, void* const* d_data /* or NULL */,
+                                                    const uint64_t* data_caps /* or NULL */, const uint64_t* caps, const uint8_t* bits,
+                                                    const uint8_t* flags /* or NULL */, const uint64_t* offset_bases /* or NULL */,
+                                                    const void* const* d_dicts, const uint64_t* dict_lens, const uint64_t* dict_entries /* or NULL */,
+                                                    BrotliAmdUndictBytesResult* results, void* hip_stream);
+
+/* The same for the DELIVERED bytes of every stream of the last decode call on the object, by BrotliAmdBatchUndictOutputs' rules for the three
+ * kinds of decode call.  A stream with BROTLI_AMD_UNDICT_BYTES_SKIP in flags[i] is skipped: none of its other parameters are looked at and
+ * its result is zeros -- the dictionary pages of the batch.  caps == NULL counts every stream and nothing else.  dict_streams[i] below the
+ * call's stream count names the stream OF THE SAME DECODE CALL whose delivered bytes are stream i's dictionary, dict_len being its delivered
+ * size: a dictionary stream that was delivered truncated is simply a shorter dictionary.  BROTLI_AMD_UNDICT_NO_STREAM, or dict_streams ==
+ * NULL, takes d_dicts[i] and dict_lens[i].  dict_entries[i] bounds either kind.  A stream that names itself, and an index at or above the
+ * stream count that is not BROTLI_AMD_UNDICT_NO_STREAM, are refused.  A negative value, and a BrotliAmdLastError text, as there. */
+BROTLI_DEC_API int BrotliAmdBatchUndictBytesOutputs(BrotliAmdBatch* batch, void* const* d_offsets /* or NULL */, void* const* d_data /* or NULL */,
+                                                   const uint64_t* data_caps /* or NULL */, const uint64_t* caps /* or NULL */, const uint8_t* bits,
+                                                   const uint8_t* flags /* or NULL */, const uint64_t* offset_bases /* or NULL */,
+                                                   const uint32_t* dict_streams /* or NULL */, const void* const* d_dicts /* or NULL */,
+                                                   const uint64_t* dict_lens /* or NULL */, const uint64_t* dict_entries /* or NULL */,
+                                                   BrotliAmdUndictBytesResult* results);
+
+/* Milliseconds the undict-bytes kernels took in the last of the two calls above (HIP events around its launches together), */
+BROTLI_DEC_API float BrotliAmdBatchLastUndictBytesMs(BrotliAmdBatch* batch);
+/* and those of phase 1 (the dictionary walk), 2 (the RLE walk), 3 (the lengths), 4 (the carries) or 5 (the expansion) alone; another: 0. */
+BROTLI_DEC_API float BrotliAmdBatchLastUndictBytesPhaseMs(BrotliAmdBatch* batch, uint32_t phase);
+
+/* Test hook (no device needed): all five phases by the functions of csrc/brotli_unrle.h and csrc/brotli_undict_bytes.h on the host.  It has
+ * BrotliAmdDebugUndictHost's shape with four buffers, each placed at its skew (0..15) past a 16-byte boundary in a room of its own: the source,
+ * the offsets, the data and the dictionaries.  Segment i's runs are src_lens[i] bytes at src_offs[i], its offsets go to offsets_offs[i] and
+ * its bytes to data_offs[i] (UINT64_MAX: that destination is NULL), its dictionary is dict_lens[i] bytes at dict_offs[i].  Segments that name
+ * the same (offset, length, bound) share one dictionary walk, and *dict_walks (where not NULL) is the number of walks.  The items are taken in
+ * orders shuffled by order_seed, and an item's destination words in an order shuffled by word_seed: no result and no byte may depend on
+ * either.  0; -1 and a BrotliAmdLastError text for arguments that are refused or a segment, destination or dictionary outside its buffer; -2
+ * where a byte outside the destinations named above changed. */
+BROTLI_DEC_API int BrotliAmdDebugUndictBytesHost(uint32_t n, const uint8_t* src, size_t src_size, uint8_t* offsets, size_t offsets_size, uint8_t* data,
+                                                size_t data_size, const uint8_t* dict, size_t dict_size, const uint64_t* src_offs,
+                                                const uint64_t* src_lens, const uint64_t* offsets_offs, const uint64_t* data_offs,
+                                                const uint64_t* data_caps, const uint64_t* caps, const uint64_t* offset_bases,
+                                                const uint64_t* dict_offs, const uint64_t* dict_lens, const uint64_t* dict_entries,
+                                                const uint8_t* bits, const uint8_t* flags /* or NULL */, uint32_t src_skew, uint32_t offsets_skew,
+                                                uint32_t data_skew, uint32_t dict_skew, uint32_t item_elems, uint32_t order_seed, uint32_t word_seed,
+                                                BrotliAmdUndictBytesResult* results, uint64_t* dict_walks /* or NULL */);
 
 /* ---- Unnull on the device: dense values spread over nulls by definition levels ----
  *
@@ -983,9 +1122,10 @@ BROTLI_DEC_API int BrotliAmdDebugUndictHost(uint32_t n, const uint8_t* src, size
  * its carry-in and its own popcount are all of them, and the ranks at or above V are the missing ones.  A call that only counts is the first
  * launch alone (csrc/brotli_unnull.h, csrc/brotli_unnull_kernels.hip).
  *
- * OUT OF SCOPE: repetition levels and nested columns; a bit offset into the bitmap; a fill value other than 0; byte-array values; thrift
- * framing; a fused undict + unnull -- a nullable dictionary column is two calls, and a counting call with LENGTH_PREFIX tells the caller where
- * a v1 dictionary-index body begins --; a parallel walk of one long segment. */
+ * OUT OF SCOPE: repetition levels and nested columns; a bit offset into the bitmap; a fill value other than 0; byte-array values (those of a
+ * required dictionary column are the undict-bytes calls' above); thrift framing; a fused undict + unnull -- a nullable dictionary column is
+ * two calls, and a counting call with LENGTH_PREFIX tells the caller where a v1 dictionary-index body begins --; a parallel walk of one long
+ * segment. */
 #define BROTLI_AMD_UNNULL_LENGTH_PREFIX 1u
 #define BROTLI_AMD_UNNULL_VALUES_FOLLOW 2u
 #define BROTLI_AMD_UNNULL_BAD_LENGTH 5u   /* a status behind BROTLI_AMD_UNRLE_*: the length prefix is cut, or says more than there is */

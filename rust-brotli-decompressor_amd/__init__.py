@@ -56,6 +56,8 @@ BATCH_H_SYMBOLS = [
     "BrotliAmdDebugUndictHost",
     "BrotliAmdBatchUnnullSegments", "BrotliAmdBatchUnnullOutputs", "BrotliAmdBatchLastUnnullMs", "BrotliAmdBatchLastUnnullPhaseMs",
     "BrotliAmdDebugUnnullHost",
+    "BrotliAmdBatchUndictBytesSegments", "BrotliAmdBatchUndictBytesOutputs", "BrotliAmdBatchLastUndictBytesMs", "BrotliAmdBatchLastUndictBytesPhaseMs",
+    "BrotliAmdDebugUndictBytesHost",
 ]
 
 
@@ -123,6 +125,22 @@ class UndictResult(ctypes.Structure):  # BrotliAmdUndictResult: what a segment o
 
     def astuple(self):
         return (self.count, self.consumed, self.runs, self.status, self.bits, self.bad, self.first_bad)
+
+
+UNDICT_BYTES_WIDTH_BYTE, UNDICT_BYTES_OFFSETS64, UNDICT_BYTES_ENDS_ONLY, UNDICT_BYTES_SKIP = 1, 2, 4, 8  # BROTLI_AMD_UNDICT_BYTES_*: a segment's flags
+UNDICT_BYTES_ALL = (1 << 64) - 1  # BROTLI_AMD_UNDICT_BYTES_ALL: as many dictionary entries as the bytes hold
+UNDICT_BYTES_DICT_OK, UNDICT_BYTES_DICT_CUT = 0, 1  # UndictBytesResult.dict_status
+UNDICT_BYTES_NO_DESTINATION = (1 << 64) - 1  # undict_bytes_host: a segment's offsets or data offset where it has no such destination
+
+
+class UndictBytesResult(ctypes.Structure):  # BrotliAmdUndictBytesResult: undict's seven fields, the elements' bytes and what the dictionary's walk found (batch.h)
+    _fields_ = [("count", ctypes.c_uint64), ("consumed", ctypes.c_uint64), ("runs", ctypes.c_uint64), ("status", ctypes.c_uint32), ("bits", ctypes.c_uint32),
+                ("bad", ctypes.c_uint64), ("first_bad", ctypes.c_uint64), ("bytes", ctypes.c_uint64), ("dict_entries", ctypes.c_uint64),
+                ("dict_consumed", ctypes.c_uint64), ("dict_status", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+    def astuple(self):
+        return (self.count, self.consumed, self.runs, self.status, self.bits, self.bad, self.first_bad, self.bytes, self.dict_entries, self.dict_consumed,
+                self.dict_status)
 
 
 UNNULL_LENGTH_PREFIX, UNNULL_VALUES_FOLLOW = 1, 2  # BROTLI_AMD_UNNULL_*: a v1 data page's 4-byte length in front of the levels; the values lie behind them
@@ -263,7 +281,10 @@ def load_library():
             {"BrotliAmdBatchUnnullSegments": (None, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
              "BrotliAmdBatchUnnullOutputs": (None, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
              "BrotliAmdBatchLastUnnullMs": (f32, [vp]), "BrotliAmdBatchLastUnnullPhaseMs": (f32, [vp, u32]),
-             "BrotliAmdDebugUnnullHost": (None, [u32, vp, sz, vp, sz, vp, sz, vp, sz] + [vp] * 11 + [u32] * 6 + [vp])}):
+             "BrotliAmdDebugUnnullHost": (None, [u32, vp, sz, vp, sz, vp, sz, vp, sz] + [vp] * 11 + [u32] * 6 + [vp])},
+            {"BrotliAmdBatchUndictBytesSegments": (None, [vp, u32] + [vp] * 14), "BrotliAmdBatchUndictBytesOutputs": (None, [vp] * 13),
+             "BrotliAmdBatchLastUndictBytesMs": (f32, [vp]), "BrotliAmdBatchLastUndictBytesPhaseMs": (f32, [vp, u32]),
+             "BrotliAmdDebugUndictBytesHost": (None, [u32, vp, sz, vp, sz, vp, sz, vp, sz] + [vp] * 12 + [u32] * 7 + [vp, vp])}):
         if hasattr(L, next(iter(protos))):
             for name, (restype, argtypes) in protos.items():
                 if restype is not None:
@@ -484,6 +505,39 @@ def undict_host(src: bytes, dictionary: bytes, segs, dst_size, src_skew=0, dst_s
                                   *u64s, *u8s, src_skew, dst_skew, dict_skew, item_elems, order_seed, res) != 0:
         raise RuntimeError("BrotliAmdDebugUndictHost failed: " + last_error())
     return d_buf.raw[:dst_size], [res[i].astuple() for i in range(n)]
+
+
+def undict_bytes_host(src: bytes, dictionary: bytes, segs, offsets_size, data_size, src_skew=0, offsets_skew=0, data_skew=0, dict_skew=0, item_elems=0, order_seed=0,
+                      word_seed=0, offsets_fill=0, data_fill=0):
+    """BrotliAmdDebugUndictBytesHost: the dictionary-index runs in `src` and the PLAIN byte arrays in `dictionary` back into offsets and bytes, by
+    unrle's walk and the functions of csrc/brotli_undict_bytes.h on the host (no device needed).  segs: [(source offset, source length, offsets
+    offset or UNDICT_BYTES_NO_DESTINATION, data offset or UNDICT_BYTES_NO_DESTINATION, data capacity in bytes, capacity in elements, offset
+    base, dictionary offset, dictionary length, dictionary entries or UNDICT_BYTES_ALL, bits, flags)]; the two destinations have offsets_size
+    and data_size bytes, all `offsets_fill` and `data_fill` in front of the call (or, where those are bytes of that size, those); the four
+    buffers are placed at their skews past a 16-byte boundary; item_elems: the elements of an item (0: the device's, unrle_item_elems());
+    order_seed != 0 shuffles the order in which the items are taken, word_seed != 0 that of an item's destination words.
+    -> (the offsets' bytes, the data's bytes, [(count, consumed, runs, status, bits, bad, first_bad, bytes, dict_entries, dict_consumed,
+    dict_status)], the dictionaries that were walked)"""
+    L = load_library()
+    src, dictionary, n = bytes(src), bytes(dictionary), len(segs)
+    rooms = []
+    for fill, size, what in ((offsets_fill, offsets_size, "offsets_fill"), (data_fill, data_size, "data_fill")):
+        before = bytes(fill) if isinstance(fill, (bytes, bytearray)) else bytes([fill]) * size
+        if len(before) != size:
+            raise ValueError("%s: %d bytes for a destination of %d" % (what, len(before), size))
+        rooms.append(ctypes.create_string_buffer(before, max(1, size)))
+    s_buf = ctypes.create_string_buffer(src, max(1, len(src)))
+    t_buf = ctypes.create_string_buffer(dictionary, max(1, len(dictionary)))
+    # the call's order: source, offsets, data, data capacity, capacity, base, dictionary offset, length, entries
+    u64s = [(ctypes.c_uint64 * max(1, n))(*[s[k] if 0 <= s[k] < (1 << 64) else (1 << 64) - 1 for s in segs]) for k in (0, 1, 2, 3, 4, 5, 6, 7, 8, 9)]
+    u8s = [(ctypes.c_uint8 * max(1, n))(*[s[k] if 0 <= s[k] <= 255 else 255 for s in segs]) for k in (10, 11)]
+    res = (UndictBytesResult * max(1, n))()
+    walks = ctypes.c_uint64(0)
+    if L.BrotliAmdDebugUndictBytesHost(n, ctypes.addressof(s_buf), len(src), ctypes.addressof(rooms[0]), offsets_size, ctypes.addressof(rooms[1]), data_size,
+                                       ctypes.addressof(t_buf), len(dictionary), *u64s, *u8s, src_skew, offsets_skew, data_skew, dict_skew, item_elems, order_seed,
+                                       word_seed, res, ctypes.byref(walks)) != 0:
+        raise RuntimeError("BrotliAmdDebugUndictBytesHost failed: " + last_error())
+    return rooms[0].raw[:offsets_size], rooms[1].raw[:data_size], [res[i].astuple() for i in range(n)], walks.value
 
 
 def unnull_host(src: bytes, values: bytes, segs, dst_size, valid_size, src_skew=0, dst_skew=0, values_skew=0, valid_skew=0, item_elems=0, order_seed=0, fill=0,
@@ -1004,6 +1058,66 @@ class Batch:
         """milliseconds the undict kernels took in the last undict_segments / undict_outputs: both launches together, or phase 1 (the walk) or 2
         (the expansion with the lookup)"""
         return self._last_ms("Undict", phase)
+
+    def undict_bytes_segments(self, src_ptrs, src_lens, offsets_ptrs, data_ptrs, data_caps, caps, bits, flags, offset_bases, dict_ptrs, dict_lens, dict_entries=None,
+                              stream=None):
+        """BrotliAmdBatchUndictBytesSegments: the RLE / bit-packed hybrid runs in the src_lens[i] bytes at the device address src_ptrs[i], of fields
+        of bits[i] bits (0 .. 32), are INDICES into the PLAIN byte arrays -- a 4-byte length, then the bytes -- of the dict_lens[i] bytes at
+        dict_ptrs[i], at most dict_entries[i] of them (None: as many as the bytes hold).  The first caps[i] elements become an Arrow string
+        column: offsets on top of offset_bases[i] (None: 0) at offsets_ptrs[i] -- int32, or int64 with UNDICT_BYTES_OFFSETS64; with
+        UNDICT_BYTES_ENDS_ONLY without offsets[0] --, and the bytes at data_ptrs[i], at most data_caps[i] of them.  A destination that is None
+        is not written: with neither the call MEASURES, and `bytes` of the result sizes the data.  An index at or above the dictionary's
+        entries gives an empty element and is counted.  caps[i] == 0 only counts.  Five launches and a wait on `stream`.
+        -> [(count, consumed, runs, status, bits, bad, first_bad, bytes, dict_entries, dict_consumed, dict_status)]"""
+        n, col = len(src_ptrs), self._column
+        if len(src_lens) != n or len(caps) != n:
+            raise ValueError("src_ptrs, src_lens and caps: one entry per segment each")
+        res = (UndictBytesResult * max(1, n))()
+        big = (1 << 64) - 1
+        self._filter_call("BrotliAmdBatchUndictBytesSegments", n, col(ctypes.c_void_p, src_ptrs, n), col(ctypes.c_size_t, src_lens, n),
+                          self._ptr_column(offsets_ptrs, n, "offsets_ptrs"), self._ptr_column(data_ptrs, n, "data_ptrs"),
+                          col(ctypes.c_uint64, data_caps, n, big, "data_caps: one entry per segment"), col(ctypes.c_uint64, caps, n, big),
+                          self._byte_column(bits, n, "bits"), self._byte_column(flags, n, "flags"), col(ctypes.c_uint64, offset_bases, n, None, "offset_bases: one entry per segment"),
+                          self._ptr_column(dict_ptrs, n, "dict_ptrs"), col(ctypes.c_uint64, dict_lens, n, big, "dict_lens: one entry per segment"),
+                          col(ctypes.c_uint64, dict_entries, n, big, "dict_entries: one entry per segment"), res, stream)
+        return [res[i].astuple() for i in range(n)]
+
+    def undict_bytes_outputs(self, offsets_ptrs, data_ptrs, data_caps, caps, bits, flags=None, offset_bases=None, dict_streams=None, dict_ptrs=None, dict_lens=None,
+                             dict_entries=None):
+        """BrotliAmdBatchUndictBytesOutputs: the delivered bytes of every stream of the last decode call on this object (after decode_device:
+        once wait() has returned), taken as dictionary-index runs, become offsets at offsets_ptrs[i] and bytes at data_ptrs[i] as in
+        undict_bytes_segments.  A stream with UNDICT_BYTES_SKIP in flags[i] is skipped -- the dictionary pages of the batch -- and its result is
+        zeros.  dict_streams[i]: the stream of the same decode call whose delivered bytes are stream i's dictionary, or UNDICT_NO_STREAM (and
+        dict_streams None) for the dict_lens[i] bytes at the device address dict_ptrs[i]; dict_entries[i] bounds either kind (None: all the
+        bytes hold).  caps None: every stream is counted and nothing else.
+        -> [(count, consumed, runs, status, bits, bad, first_bad, bytes, dict_entries, dict_consumed, dict_status)], one per stream"""
+        n, col = self.out_n, self._column
+        if caps is not None and len(caps) != n:
+            raise ValueError("caps: one entry per stream of the last decode call")
+        res = (UndictBytesResult * max(1, n))()
+        big = (1 << 64) - 1
+        self._filter_call("BrotliAmdBatchUndictBytesOutputs", self._ptr_column(offsets_ptrs, n, "offsets_ptrs"), self._ptr_column(data_ptrs, n, "data_ptrs"),
+                          col(ctypes.c_uint64, data_caps, n, big, "data_caps: one entry per stream"), col(ctypes.c_uint64, caps, n, big), self._byte_column(bits, n, "bits"),
+                          self._byte_column(flags, n, "flags"), col(ctypes.c_uint64, offset_bases, n, None, "offset_bases: one entry per stream"),
+                          col(ctypes.c_uint32, dict_streams, n, None, "dict_streams: one entry per stream"), self._ptr_column(dict_ptrs, n, "dict_ptrs"),
+                          col(ctypes.c_uint64, dict_lens, n, big, "dict_lens: one entry per stream"),
+                          col(ctypes.c_uint64, dict_entries, n, big, "dict_entries: one entry per stream"), res)
+        return [res[i].astuple() for i in range(n)]
+
+    def measure_dict_bytes_outputs(self, caps, bits, dict_streams=None, dict_ptrs=None, dict_lens=None, dict_entries=None, flags=None):
+        """undict_bytes_outputs without destinations: what the first caps[i] elements of every stream of the last decode call take -- `bytes`
+        of the result -- and what its dictionary holds; caps[i] None skips the stream (UNDICT_BYTES_SKIP).  The way to size the data of the
+        call that writes: the rows are in the page header, the bytes are not."""
+        n = self.out_n
+        if len(caps) != n:
+            raise ValueError("caps: one entry per stream of the last decode call")
+        flags = [(flags[i] if flags is not None else 0) | (UNDICT_BYTES_SKIP if caps[i] is None else 0) for i in range(n)]
+        return self.undict_bytes_outputs(None, None, None, [c or 0 for c in caps], bits, flags, None, dict_streams, dict_ptrs, dict_lens, dict_entries)
+
+    def last_undict_bytes_ms(self, phase=None):
+        """milliseconds the undict-bytes kernels took in the last undict_bytes_segments / undict_bytes_outputs: all launches together, or phase 1
+        (the dictionary walk), 2 (the RLE walk), 3 (the lengths), 4 (the carries) or 5 (the expansion)"""
+        return self._last_ms("UndictBytes", phase)
 
     def _ptr_column(self, ptrs, n, what):
         """device addresses as the C calls take them: None stays NULL, and so does an entry that is None or 0"""

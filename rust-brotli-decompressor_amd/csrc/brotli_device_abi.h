@@ -239,6 +239,40 @@ typedef struct BrotliAmdUnnullSeg {
   uint8_t* valid;
 } BrotliAmdUnnullSeg;
 
+// One segment of an undict-bytes call (csrc/brotli_undict_bytes_kernels.hip, csrc/brotli_undict_bytes.h): an unrle segment whose values are
+// INDICES into a dictionary of PLAIN byte arrays -- record `dict` of the call's table of distinct dictionaries (BROTLI_AMD_UNDICT_BYTES_NO_DICT:
+// none, cap is 0) --; the first `cap` of the entries they name become an Arrow string column: their running byte offsets on top of offset_base at
+// `offsets` (NULL: none), 4 bytes each or 8 by flags, and their bytes one behind the other at `data`, cut at data_cap.  Items, first_item and the
+// checkpoints are unrle's; every segment has a result (BrotliAmdUndictBytesResult, include/brotli/batch.h) behind the table, and every item a
+// checkpoint, a tile record and a carry.  No destination range overlaps a source range, a dictionary or another destination range.  Nothing
+// outside [data, data + min(bytes, data_cap)) and the offsets that batch.h names is written; nothing outside the 16-byte-aligned spans around
+// [src, src + len) and the dictionary is read.
+typedef struct BrotliAmdUndictBytesSeg {
+  const uint8_t* src;
+  uint8_t* data;
+  uint64_t len;
+  uint64_t cap;
+  uint64_t first_item;
+  uint32_t dict;
+  uint32_t bits;
+  uint32_t flags;
+  uint32_t reserved;
+  uint8_t* offsets;
+  uint64_t data_cap;
+  uint64_t offset_base;
+} BrotliAmdUndictBytesSeg;
+#define BROTLI_AMD_UNDICT_BYTES_NO_DICT 0xFFFFFFFFu
+
+// One DISTINCT dictionary of such a call: `len` bytes (below 2^32) at `dict`, device memory of any alignment, of which at most `bound` entries
+// are taken; first_start is where its entries' positions begin in the call's array of them, min(bound, len / 4) + 1 of them.  The records lie
+// behind the segments in the call's table; every record has a result (BrotliAmdUndictBytesDictResult, csrc/brotli_undict_bytes.h) in the scratch.
+typedef struct BrotliAmdUndictBytesDict {
+  const uint8_t* dict;
+  uint64_t len;
+  uint64_t bound;
+  uint64_t first_start;
+} BrotliAmdUndictBytesDict;
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,8 @@
 //                   templates: counted_device, counted_segments, counted_outputs.
 //   unnull          beside the counted path: two sources, two destinations and a level a segment are columns of its own; it shares the counted
 //                   table's members and counted_device, and the four counted filters' templates do not know of it.
+//   undict-bytes    beside them as well: two destinations a segment, and a second table -- the call's DISTINCT dictionaries -- behind the
+//                   segments, so it has a launcher, a table and a device call of its own.
 //   the hooks       BrotliAmdDebug*Host run the device's functions of a filter's header (csrc/brotli_<filter>.h) on the host as the kernel's lanes
 //                   take them, for tests without a device.  They share the seeded orders, the serial carries, the argument checks and the
 //                   counted filters' closing block; each keeps its own phase loops.
@@ -17,13 +19,16 @@
 #include "brotli_host.h"
 #include "brotli_undbp.h"
 #include "brotli_undict.h"
+#include "brotli_undict_bytes.h"
 #include "brotli_undelta.h"
 #include "brotli_unnull.h"
 #include "brotli_unrle.h"
 #include "brotli_unshuffle.h"
 #include "brotli_unvarint.h"
 
+#include <map>
 #include <numeric>
+#include <tuple>
 
 // (csrc/brotli_*_kernels.hip: d_segs: the filter's table on the device; units: the segments' units together; d_scratch: what lies behind the table;
 // ev: the filter's events, recorded around and between its launches)
@@ -31,6 +36,10 @@ typedef hipError_t FilterLaunch(const void* d_segs, uint32_t n, uint64_t units, 
 extern "C" FilterLaunch brotli_amd_launch_unshuffle, brotli_amd_launch_undelta, brotli_amd_launch_bitunshuffle, brotli_amd_launch_bitunpack,
     brotli_amd_launch_unvarint, brotli_amd_launch_unrle, brotli_amd_launch_undbp, brotli_amd_launch_undict, brotli_amd_launch_unnull;
 extern "C" uint64_t brotli_amd_unnull_scratch_bytes(uint64_t units, uint32_t n);
+// (csrc/brotli_undict_bytes_kernels.hip: d_dicts: the call's nd distinct dictionaries, whose entry positions are `starts` together)
+extern "C" uint64_t brotli_amd_undict_bytes_scratch_bytes(uint64_t units, uint32_t n, uint32_t nd, uint64_t starts);
+extern "C" hipError_t brotli_amd_launch_undict_bytes(const void* d_segs, uint32_t n, uint64_t units, const void* d_dicts, uint32_t nd, void* d_scratch, hipStream_t stream,
+                                                     const hipEvent_t* ev);
 extern "C" uint64_t brotli_amd_undelta_scratch_bytes(uint64_t units);
 extern "C" uint64_t brotli_amd_unvarint_scratch_bytes(uint64_t units, uint32_t n);
 extern "C" uint64_t brotli_amd_unrle_scratch_bytes(uint64_t units, uint32_t n);
@@ -53,7 +62,8 @@ namespace {
 
 // ---- the descriptor ----
 // What the host needs to know of a filter.  A filter of one launch has two events; undelta and unvarint have four around and between their three
-// launches, unrle and undict three, undbp five.  The counted filters' results lie first behind the table.
+// launches, unrle and undict three, undbp and unnull five, undict-bytes six -- and a launcher of its own signature (undict_bytes_device).  The
+// counted filters' results lie first behind the table.
 struct FilterDesc {
   const char* name;   // in the texts of g_last_error
   SegCallWhat what;
@@ -81,6 +91,9 @@ const FilterDesc kFilter[kFilters] = {
      "brotli_amd_undict kernels launch", brotli_amd_launch_undict, brotli_amd_undict_scratch_bytes, 3u},
     {"unnull", {"hipMalloc(unnull segments, results, checkpoints and tiles)", "hipMemcpyAsync(unnull segments)", "hipStreamSynchronize(unnull)"},
      "brotli_amd_unnull kernels launch", brotli_amd_launch_unnull, brotli_amd_unnull_scratch_bytes, 5u},
+    {"undict-bytes", {"hipMalloc(undict-bytes segments, dictionaries, results, checkpoints, tiles and entry positions)", "hipMemcpyAsync(undict-bytes segments)",
+                      "hipStreamSynchronize(undict-bytes)"},
+     "brotli_amd_undict_bytes kernels launch", nullptr, nullptr, 6u},
 };
 
 typedef std::vector<BrotliAmdUnshuffleSeg> Segs;
@@ -92,6 +105,7 @@ inline uint64_t units_of(const BrotliAmdUnrleSeg& s) { return 1u + brotli_amd_un
 inline uint64_t units_of(const BrotliAmdUndbpSeg& s) { return 1u + brotli_amd_undbp_items(s.cap, brotli_amd_undbp_item_deltas()); }
 inline uint64_t units_of(const BrotliAmdUndictSeg& s) { return 1u + brotli_amd_unrle_items(s.cap, brotli_amd_unrle_item_elems()); }
 inline uint64_t units_of(const BrotliAmdUnnullSeg& s) { return 1u + brotli_amd_unrle_items(s.cap, brotli_amd_unrle_item_elems()); }
+inline uint64_t units_of(const BrotliAmdUndictBytesSeg& s) { return 1u + brotli_amd_unrle_items(s.cap, brotli_amd_unrle_item_elems()); }
 
 int invalid_arguments(Filter f) { g_last_error = std::string("invalid ") + kFilter[f].name + " arguments"; return -1; }
 
@@ -449,6 +463,97 @@ inline bool push_unnull(CountedTable<Unnull>* t, BrotliAmdUnnullSeg s, size_t i,
   return true;
 }
 
+// ---- undict for byte arrays: a path of its own beside the counted one ----
+// A segment has two destinations, a data capacity and an offset base, and its dictionary is bytes and a bound, not entries of a width: its
+// columns are its own.  Behind the segments the call's table has a record for every DISTINCT dictionary -- (pointer, length, bound) --, which the
+// device walks once however many segments name it.
+struct BytesDict { const void* ptr; uint64_t len, bound; };
+typedef BrotliAmdUndictBytesResult BytesResult;
+BytesResult empty_bytes_result() { return brotli_amd_undict_bytes_result(BrotliAmdUnrleResult{0u, 0u, 0u, 0u, 0u}, BrotliAmdUndictBytesDictResult{0u, 0u, 0u, 0u}); }
+
+__attribute__((noinline)) bool refuse_bytes(const char* what, const BrotliAmdUndictBytesSeg& s, BytesDict d, const char* who, size_t i) {
+  g_last_error = std::string("undict-bytes ") + who + " " + std::to_string(i) + ": " + what + " (bits " + std::to_string(s.bits) + ", flags " + std::to_string(s.flags) +
+                 ", capacity " + std::to_string(s.cap) + ", data capacity " + std::to_string(s.data_cap) + ", dictionary bytes " + std::to_string(d.len) + ")";
+  return false;
+}
+// the shape check of one entry, in the order of batch.h's list
+inline bool known_bytes(const BrotliAmdUndictBytesSeg& s, BytesDict d, const char* who, size_t i) {
+  const char* what = nullptr;
+  if ((s.flags & ~BROTLI_AMD_UNDICT_BYTES_FLAGS) != 0u) what = "unknown flag bits";
+  else if ((s.flags & BROTLI_AMD_UNDICT_BYTES_WIDTH_BYTE) == 0u && s.bits > BROTLI_AMD_UNRLE_MAX_BITS) what = "field of more than 32 bits";
+  else if (s.cap > BROTLI_AMD_UNDICT_BYTES_MAX_CAP) what = "a capacity above 2^56 elements";
+  else if (s.data_cap != 0u && !s.data) what = "no data destination for a data capacity that is not 0";
+  else if (s.cap != 0u && d.len != 0u && !d.ptr) what = "no dictionary for bytes and a capacity that are not 0";
+  else if (d.len >= BROTLI_AMD_UNDICT_BYTES_MAX_DICT) what = "a dictionary of 2^32 bytes or more";
+  return !what || refuse_bytes(what, s, d, who, i);
+}
+
+// the call's distinct dictionaries, and where each one's entry positions begin
+struct BytesDicts {
+  std::vector<BrotliAmdUndictBytesDict> recs;
+  uint64_t starts = 0;   // of all records together
+  uint32_t index(BytesDict d) {
+    if (!recs.empty() && recs.back().dict == d.ptr && recs.back().len == d.len && recs.back().bound == d.bound) return (uint32_t)recs.size() - 1u;   // (the pages of a chunk)
+    const auto at = known_.emplace(std::make_tuple(d.ptr, d.len, d.bound), (uint32_t)recs.size());
+    if (at.second) {
+      recs.push_back(BrotliAmdUndictBytesDict{static_cast<const uint8_t*>(d.ptr), d.len, d.bound, starts});
+      starts += brotli_amd_undict_bytes_starts(d.len, d.bound);
+    }
+    return at.first->second;
+  }
+ private:
+  std::map<std::tuple<const void*, uint64_t, uint64_t>, uint32_t> known_;
+};
+
+struct BytesTable {
+  std::vector<BrotliAmdUndictBytesSeg> segs;
+  std::vector<size_t> where;
+  uint64_t items = 0;
+  BytesDicts dicts;
+  // entry i of a call: checked, then given its place among the items and its dictionary's record (a segment that only counts has none)
+  bool push(BrotliAmdUndictBytesSeg s, BytesDict d, size_t i, const char* who) {
+    if (!known_bytes(s, d, who, i)) return false;
+    s.first_item = items;
+    s.dict = s.cap != 0u ? dicts.index(d) : BROTLI_AMD_UNDICT_BYTES_NO_DICT;
+    segs.push_back(s);
+    where.push_back(i);
+    items += brotli_amd_unrle_items(s.cap, brotli_amd_unrle_item_elems());
+    return true;
+  }
+};
+
+// the table on `stream`, waited for, and its results: entry j's to results[where[j]] of the n_results, the others zeros
+int undict_bytes_device(BrotliAmdBatch* b, const BytesTable& t, BytesResult* results, size_t n_results, hipStream_t stream) {
+  std::fill(results, results + n_results, empty_bytes_result());
+  if (t.segs.empty()) return 0;
+  DeviceGuard guard;
+  if (!hip_ok(hipSetDevice(b->device), "hipSetDevice")) return -1;
+  const FilterDesc& d = kFilter[kUndictBytes];
+  BrotliAmdBatch::FilterCall& call = b->filter[kUndictBytes];
+  const uint32_t n = (uint32_t)t.segs.size(), nd = (uint32_t)t.dicts.recs.size();
+  const uint64_t units = n + t.items;
+  // the segments, and behind them -- at a multiple of 16 -- the dictionaries' records
+  const size_t seg_bytes = (sizeof(BrotliAmdUndictBytesSeg) * n + 15u) & ~(size_t)15;
+  std::vector<uint8_t> table(seg_bytes + sizeof(BrotliAmdUndictBytesDict) * nd, 0);
+  std::memcpy(table.data(), t.segs.data(), sizeof(BrotliAmdUndictBytesSeg) * n);
+  if (nd) std::memcpy(table.data() + seg_bytes, t.dicts.recs.data(), sizeof(BrotliAmdUndictBytesDict) * nd);
+  const uint8_t* d_results = nullptr;
+  if (run_seg_call(&call.call, d.what, table.data(), table.size(), brotli_amd_undict_bytes_scratch_bytes(units, n, nd, t.dicts.starts), d.events, stream,
+                   [&](uint8_t* d_table, uint8_t* d_scratch, const hipEvent_t* ev) {
+    d_results = d_scratch;
+    return hip_ok(brotli_amd_launch_undict_bytes(d_table, n, units, d_table + seg_bytes, nd, d_scratch, stream, ev), d.launch_what);
+  }, &call.ms, call.phase_ms) != 0) return -1;
+  if (t.items == 0u) {   // (the RLE walk alone: what lies between the other events is no launch's time)
+    const float walk = call.phase_ms[1];
+    std::fill(std::begin(call.phase_ms), std::end(call.phase_ms), 0.0f);
+    call.ms = call.phase_ms[1] = walk;
+  }
+  std::vector<BytesResult> got(n);
+  if (!hip_ok(hipMemcpy(got.data(), d_results, sizeof(BytesResult) * n, hipMemcpyDeviceToHost), "hipMemcpy(undict-bytes results)")) return -1;
+  for (size_t j = 0; j < got.size(); j++) results[t.where[j]] = got[j];
+  return 0;
+}
+
 // ---- what the hooks share ----
 // The hooks run the device's functions on the host over every unit of a segment, source and destination each in a SkewedRoom (brotli_host.h).
 // a hook's buffers and skews
@@ -719,6 +824,57 @@ extern "C" int BrotliAmdBatchUnnullOutputs(BrotliAmdBatch* b, void* const* d_dst
   return counted_device(b, t, results, outs.size(), b->last_stream);
 }
 
+extern "C" int BrotliAmdBatchUndictBytesSegments(BrotliAmdBatch* b, uint32_t n, const void* const* d_src, const size_t* src_lens, void* const* d_offsets, void* const* d_data,
+                                                 const uint64_t* data_caps, const uint64_t* caps, const uint8_t* bits, const uint8_t* flags, const uint64_t* offset_bases,
+                                                 const void* const* d_dicts, const uint64_t* dict_lens, const uint64_t* dict_entries, BrotliAmdUndictBytesResult* results,
+                                                 void* hip_stream) {
+  if (!b || (n && (!d_src || !src_lens || !caps || !bits || !results))) return invalid_arguments(kUndictBytes);
+  no_times(b, kUndictBytes);
+  BytesTable t;
+  t.segs.reserve(n); t.where.reserve(n);
+  for (uint32_t i = 0; i < n; i++) {
+    if (caps[i] != 0u && (!d_dicts || !dict_lens)) return invalid_arguments(kUndictBytes);   // (no arrays of dictionaries: a call that counts, where every capacity is 0)
+    const BytesDict d = {d_dicts ? d_dicts[i] : nullptr, dict_lens ? dict_lens[i] : 0u, dict_entries ? dict_entries[i] : BROTLI_AMD_UNDICT_BYTES_ALL};
+    const BrotliAmdUndictBytesSeg s = {static_cast<const uint8_t*>(d_src[i]), static_cast<uint8_t*>(d_data ? d_data[i] : nullptr), src_lens[i], caps[i], 0u, 0u, bits[i],
+                                       flags ? flags[i] : 0u, 0u, static_cast<uint8_t*>(d_offsets ? d_offsets[i] : nullptr), data_caps ? data_caps[i] : 0u,
+                                       offset_bases ? offset_bases[i] : 0u};
+    if (!t.push(s, d, i, "segment")) return -1;
+  }
+  return undict_bytes_device(b, t, results, n, static_cast<hipStream_t>(hip_stream));
+}
+__attribute__((noinline)) static bool refuse_bytes_dict_stream(size_t i, uint32_t j, size_t n) {
+  g_last_error = "undict-bytes stream " + std::to_string(i) + ": its dictionary stream " + std::to_string(j) +
+                 (j == i ? " is the stream itself" : " is none of the " + std::to_string(n) + " streams of the last decode call");
+  return false;
+}
+extern "C" int BrotliAmdBatchUndictBytesOutputs(BrotliAmdBatch* b, void* const* d_offsets, void* const* d_data, const uint64_t* data_caps, const uint64_t* caps,
+                                                const uint8_t* bits, const uint8_t* flags, const uint64_t* offset_bases, const uint32_t* dict_streams,
+                                                const void* const* d_dicts, const uint64_t* dict_lens, const uint64_t* dict_entries, BrotliAmdUndictBytesResult* results) {
+  if (!b || !bits || !results) return invalid_arguments(kUndictBytes);
+  no_times(b, kUndictBytes);
+  std::vector<DeliveredBytes> outs;
+  if (!delivered_outputs(b, &outs)) return -1;
+  BytesTable t;
+  t.segs.reserve(outs.size()); t.where.reserve(outs.size());
+  for (size_t i = 0; i < outs.size(); i++) {
+    uint32_t f = flags ? flags[i] : 0u;
+    if ((f & BROTLI_AMD_UNDICT_BYTES_SKIP) != 0u) continue;   // skipped: none of its other parameters are looked at
+    const uint64_t cap = caps ? caps[i] : 0u;   // (without capacities every stream is counted, and nothing of a dictionary is looked at)
+    BytesDict d = {nullptr, 0u, dict_entries ? dict_entries[i] : BROTLI_AMD_UNDICT_BYTES_ALL};
+    if (cap != 0u) {
+      const uint32_t j = dict_streams ? dict_streams[i] : BROTLI_AMD_UNDICT_NO_STREAM;
+      if (j == BROTLI_AMD_UNDICT_NO_STREAM) { d.ptr = d_dicts ? d_dicts[i] : nullptr; d.len = dict_lens ? dict_lens[i] : 0u; }
+      else if (j == i || j >= outs.size()) { refuse_bytes_dict_stream(i, j, outs.size()); return -1; }
+      else { d.ptr = outs[j].ptr; d.len = outs[j].len; }
+    }
+    const BrotliAmdUndictBytesSeg s = {outs[i].ptr, static_cast<uint8_t*>(caps && d_data ? d_data[i] : nullptr), outs[i].len, cap, 0u, 0u, bits[i], f, 0u,
+                                       static_cast<uint8_t*>(caps && d_offsets ? d_offsets[i] : nullptr), caps && data_caps ? data_caps[i] : 0u,
+                                       offset_bases ? offset_bases[i] : 0u};
+    if (!t.push(s, d, i, "stream")) return -1;
+  }
+  return undict_bytes_device(b, t, results, outs.size(), b->last_stream);
+}
+
 extern "C" float BrotliAmdBatchLastUnnullMs(BrotliAmdBatch* b) { return b ? b->filter[kUnnull].ms : 0.0f; }
 extern "C" float BrotliAmdBatchLastUnnullPhaseMs(BrotliAmdBatch* b, uint32_t phase) { return phase_ms(b, kUnnull, phase); }
 extern "C" float BrotliAmdBatchLastUnshuffleMs(BrotliAmdBatch* b) { return b ? b->filter[kUnshuffle].ms : 0.0f; }
@@ -734,6 +890,8 @@ extern "C" float BrotliAmdBatchLastUndbpMs(BrotliAmdBatch* b) { return b ? b->fi
 extern "C" float BrotliAmdBatchLastUndbpPhaseMs(BrotliAmdBatch* b, uint32_t phase) { return phase_ms(b, kUndbp, phase); }
 extern "C" float BrotliAmdBatchLastUndictMs(BrotliAmdBatch* b) { return b ? b->filter[kUndict].ms : 0.0f; }
 extern "C" float BrotliAmdBatchLastUndictPhaseMs(BrotliAmdBatch* b, uint32_t phase) { return phase_ms(b, kUndict, phase); }
+extern "C" float BrotliAmdBatchLastUndictBytesMs(BrotliAmdBatch* b) { return b ? b->filter[kUndictBytes].ms : 0.0f; }
+extern "C" float BrotliAmdBatchLastUndictBytesPhaseMs(BrotliAmdBatch* b, uint32_t phase) { return phase_ms(b, kUndictBytes, phase); }
 extern "C" uint32_t BrotliAmdDebugUndbpItemDeltas(void) { return brotli_amd_undbp_item_deltas(); }
 extern "C" uint32_t BrotliAmdDebugUndbpWalkChunk(void) { return brotli_amd_undbp_walk_chunk(); }
 extern "C" uint32_t BrotliAmdDebugUnrleItemElems(void) { return brotli_amd_unrle_item_elems(); }
@@ -1032,4 +1190,111 @@ extern "C" int BrotliAmdDebugUnnullHost(uint32_t n, const uint8_t* src, size_t s
   const int r = counted_hook_result(kUnnull, droom, n, dst, dst_size, dst_offs, caps, widths, got, results);
   if (r == 0) broom.get(valid, 0u, valid_size);
   return r;
+}
+
+// Undict-bytes' five phases over n segments given as offsets into one source, one offsets, one data and one dictionary buffer, each buffer in
+// its room: every distinct dictionary's walk, every segment's walk -- unrle's --, the items' byte counts in an order shuffled by the seed, the
+// carries as undelta's hook takes them, and the items' offsets and bytes in another shuffled order, every item's destination words in an
+// order shuffled by word_seed.
+extern "C" int BrotliAmdDebugUndictBytesHost(uint32_t n, const uint8_t* src, size_t src_size, uint8_t* offsets, size_t offsets_size, uint8_t* data, size_t data_size,
+                                             const uint8_t* dict, size_t dict_size, const uint64_t* src_offs, const uint64_t* src_lens, const uint64_t* offsets_offs,
+                                             const uint64_t* data_offs, const uint64_t* data_caps, const uint64_t* caps, const uint64_t* offset_bases,
+                                             const uint64_t* dict_offs, const uint64_t* dict_lens, const uint64_t* dict_entries, const uint8_t* bits, const uint8_t* flags,
+                                             uint32_t src_skew, uint32_t offsets_skew, uint32_t data_skew, uint32_t dict_skew, uint32_t item_elems, uint32_t order_seed,
+                                             uint32_t word_seed, BrotliAmdUndictBytesResult* results, uint64_t* dict_walks) {
+  const uint64_t none = ~(uint64_t)0;
+  if ((n && (!src_offs || !src_lens || !offsets_offs || !data_offs || !data_caps || !caps || !offset_bases || !dict_offs || !dict_lens || !dict_entries || !bits || !results)) ||
+      !rooms_ok(src, src_size, offsets, offsets_size, src_skew, offsets_skew) || !rooms_ok(dict, dict_size, data, data_size, dict_skew, data_skew))
+    return invalid_arguments(kUndictBytes);
+  if (item_elems == 0u) item_elems = brotli_amd_unrle_item_elems();
+  SkewedRoom sroom(src_size, src_skew, 0xA5), oroom(offsets_size, offsets_skew, 0x5A), droom(data_size, data_skew, 0x69), troom(dict_size, dict_skew, 0x3C);
+  std::vector<BrotliAmdUndictBytesSeg> segs;
+  std::vector<BytesDict> dicts;
+  for (uint32_t i = 0; i < n; i++) {
+    const bool has_offsets = offsets_offs[i] != none, has_data = data_offs[i] != none;
+    const BytesDict d = {dict_lens[i] ? reinterpret_cast<const void*>((uintptr_t)(troom.at() + dict_offs[i])) : nullptr, dict_lens[i], dict_entries[i]};
+    const BrotliAmdUndictBytesSeg s = {reinterpret_cast<const uint8_t*>((uintptr_t)(sroom.at() + src_offs[i])),
+                                       has_data ? reinterpret_cast<uint8_t*>((uintptr_t)(droom.at() + data_offs[i])) : nullptr, src_lens[i], caps[i], 0u,
+                                       BROTLI_AMD_UNDICT_BYTES_NO_DICT, bits[i], flags ? flags[i] : 0u, 0u,
+                                       has_offsets ? reinterpret_cast<uint8_t*>((uintptr_t)(oroom.at() + offsets_offs[i])) : nullptr, data_caps[i], offset_bases[i]};
+    if (!known_bytes(s, d, "segment", i)) return -1;
+    if (!lies_in(src_offs[i], src_lens[i], src_size) || (has_offsets && offsets_offs[i] > offsets_size) || (has_data && data_offs[i] > data_size)) return outside_buffer(kUndictBytes);
+    if (caps[i] != 0u && dict_lens[i] != 0u && !lies_in(dict_offs[i], dict_lens[i], dict_size)) {
+      g_last_error = "invalid undict-bytes arguments: a dictionary outside its buffer";
+      return -1;
+    }
+    segs.push_back(s);
+    dicts.push_back(d);
+  }
+  sroom.put(src, src_size);
+  oroom.put(offsets, offsets_size);
+  droom.put(data, data_size);
+  troom.put(dict, dict_size);
+  // phase 1: every distinct dictionary once
+  BytesDicts table;
+  for (uint32_t i = 0; i < n; i++)
+    if (caps[i] != 0u) segs[i].dict = table.index(dicts[i]);
+  std::vector<uint32_t> starts(table.starts);
+  std::vector<BrotliAmdUndictBytesDictResult> dict_results;
+  for (const BrotliAmdUndictBytesDict& r : table.recs)
+    dict_results.push_back(brotli_amd_undict_bytes_host_dict((uint64_t)(uintptr_t)r.dict, r.len, r.bound, starts.data() + r.first_start));
+  if (dict_walks) *dict_walks = table.recs.size();
+  // phase 2: the walks.  A segment's capacity becomes its count and one more at the most: the walk marks the items of no other elements, and a
+  // capacity of 2^56 needs no table of its own.
+  HookItems<BrotliAmdUnrleCheckpoint> items;
+  std::vector<BytesResult> got(n);
+  items.pre.assign(n + 1u, 0u);
+  for (uint32_t i = 0; i < n; i++) {
+    const BrotliAmdUndictBytesDictResult dr = segs[i].dict != BROTLI_AMD_UNDICT_BYTES_NO_DICT ? dict_results[segs[i].dict] : BrotliAmdUndictBytesDictResult{0u, 0u, 0u, 0u};
+    BrotliAmdUndictBytesSeg counting = segs[i];
+    counting.cap = 0u;
+    segs[i].cap = std::min<uint64_t>(caps[i], brotli_amd_undict_bytes_host_walk(counting, dr, item_elems, nullptr).count + 1u);
+    segs[i].first_item = items.pre[i];
+    items.pre[i + 1u] = items.pre[i] + brotli_amd_unrle_items(segs[i].cap, item_elems);
+    items.ckpts.resize(items.pre[i + 1u], BrotliAmdUnrleCheckpoint{BROTLI_AMD_UNRLE_NONE, BROTLI_AMD_UNRLE_NONE});
+    got[i] = brotli_amd_undict_bytes_host_walk(segs[i], dr, item_elems, items.ckpts.data() + items.pre[i]);
+    const uint64_t slots = std::min(got[i].count, caps[i]) + ((segs[i].flags & BROTLI_AMD_UNDICT_BYTES_ENDS_ONLY) != 0u || caps[i] == 0u ? 0u : 1u);
+    if (segs[i].offsets && slots * brotli_amd_undict_bytes_offset_width(segs[i].flags) > offsets_size - offsets_offs[i]) return outside_buffer(kUndictBytes);
+  }
+  oroom.snapshot();
+  droom.snapshot();
+  // phases 3 and 4
+  SeededOrder seeded(order_seed), word_order(word_seed);
+  std::vector<BrotliAmdUndeltaTile> tiles(items.pre.back());
+  items.shuffled(&seeded, [&](uint32_t i, BrotliAmdUnrleCheckpoint cp, uint64_t j, uint64_t g) {
+    tiles[g] = brotli_amd_undict_bytes_host_count(segs[i], starts.data() + table.recs[segs[i].dict].first_start, &got[i], cp, j, item_elems);
+  });
+  const std::vector<uint64_t> carries = carries_of(tiles);
+  std::vector<uint64_t> kept(n, 0u);   // the bytes of every segment that its data capacity leaves
+  for (uint32_t i = 0; i < n; i++) {
+    uint64_t bytes = 0;
+    for (uint64_t g = items.pre[i]; g < items.pre[i + 1u]; g++) bytes += tiles[g].sum;
+    kept[i] = segs[i].data ? std::min(bytes, segs[i].data_cap) : 0u;
+    if (segs[i].data && kept[i] > data_size - data_offs[i]) return outside_buffer(kUndictBytes);
+  }
+  // phase 5
+  std::vector<uint64_t> ends(item_elems + 1u);
+  std::vector<uint32_t> pos(item_elems);
+  items.shuffled(&seeded, [&](uint32_t i, BrotliAmdUnrleCheckpoint cp, uint64_t j, uint64_t g) {
+    const BrotliAmdUndictBytesDict& r = table.recs[segs[i].dict];
+    brotli_amd_undict_bytes_host_expand(segs[i], (uint64_t)(uintptr_t)r.dict, starts.data() + r.first_start, &got[i], cp, j, item_elems, carries[g], ends.data(), pos.data(),
+                                        [&](uint64_t count, auto each) {
+      std::vector<uint64_t> order = first_numbers(count);
+      word_order.shuffle(&order);
+      for (uint64_t q : order) each(q);
+    });
+  });
+  // no byte outside every segment's offsets and bytes may have changed
+  std::vector<uint8_t> in_offsets(offsets_size, 0), in_data(data_size, 0);
+  for (uint32_t i = 0; i < n; i++) {
+    const uint64_t slots = std::min(got[i].count, caps[i]) + ((segs[i].flags & BROTLI_AMD_UNDICT_BYTES_ENDS_ONLY) != 0u || caps[i] == 0u ? 0u : 1u);
+    if (segs[i].offsets) std::fill(in_offsets.begin() + offsets_offs[i], in_offsets.begin() + offsets_offs[i] + slots * brotli_amd_undict_bytes_offset_width(segs[i].flags), 1);
+    if (segs[i].data) std::fill(in_data.begin() + data_offs[i], in_data.begin() + data_offs[i] + kept[i], 1);
+  }
+  if (!oroom.changed_inside_only([&](size_t i) { return i < offsets_size && in_offsets[i]; })) { g_last_error = "undict-bytes wrote outside its offsets"; return -2; }
+  if (!droom.changed_inside_only([&](size_t i) { return i < data_size && in_data[i]; })) { g_last_error = "undict-bytes wrote outside its data"; return -2; }
+  oroom.get(offsets, 0u, offsets_size);
+  droom.get(data, 0u, data_size);
+  std::copy(got.begin(), got.end(), results);
+  return 0;
 }

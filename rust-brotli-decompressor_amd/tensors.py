@@ -24,7 +24,8 @@ A stream that is a DICTIONARY-INDEX PAGE BODY -- Parquet's RLE_DICTIONARY: a wid
 stream of the same call or a tensor, and one call turns all such streams into their VALUES (Batch.undict_outputs): the indices never reach
 memory, and a stream with an index outside its dictionary is refused.  A stream that is the body of a NULLABLE column's data page -- definition
 levels and the dense values that are there -- says ("nulls", level): one call spreads the values of all such streams over their nulls
-(Batch.unnull_outputs), and the stream's entry is the pair (tensor, validity bitmap)."""
+(Batch.unnull_outputs), and the stream's entry is the pair (tensor, validity bitmap).  A STRING column -- the index page body over a
+dictionary of byte arrays -- has no slot size before it is decoded, so it has a function of its own: outputs_as_strings."""
 import collections
 
 import torch
@@ -337,4 +338,85 @@ def outputs_as_tensors(batch, specs):
     out = [None if st is None else buf[off:off + st.want].view(st.dtype).reshape(st.shape) for st, off in zip(streams, offs)]
     for i in nullable:
         out[i] = (out[i], buf[valid_at[i]:valid_at[i] + (_numel(streams[i].shape) + 7) // 8])
+    return out
+
+
+BYTES_OFFSETS64, BYTES_SKIP, BYTES_ALL = 2, 8, (1 << 64) - 1   # UNDICT_BYTES_OFFSETS64, UNDICT_BYTES_SKIP, UNDICT_BYTES_ALL
+INT32_MAX = (1 << 31) - 1
+
+
+def outputs_as_strings(batch, specs):
+    """The streams of the last decode call on `batch` that are DICTIONARY-INDEX PAGE BODIES of string columns -- a width byte k, then runs of
+    k-bit indices into a dictionary of PLAIN byte arrays (Parquet's RLE_DICTIONARY over BYTE_ARRAY) -- as Arrow string columns.  specs[i]:
+    None for a stream that is not wanted (a dictionary page among them), (rows, j) for a body of `rows` rows whose dictionary is what stream j of
+    the same call delivered, or (rows, tensor) with the dictionary page's bytes as a contiguous 1-D uint8 device tensor; a third item "large"
+    asks for int64 offsets.  -> a list of (offsets, data) pairs (None where the spec was None): offsets has rows + 1 entries, int32 or int64,
+    data is uint8, and both are views of ONE buffer with 64-byte-aligned slots.  One measuring call (Batch.measure_dict_bytes_outputs: the
+    rows are in the page header, the bytes are not), one allocation and one writing call (Batch.undict_bytes_outputs); the indices never
+    reach memory.  ValueError, naming the stream and what was found, where the runs do not end well (a status that is not OK), hold fewer
+    values than rows (more are the last group's padding and are not judged), the dictionary is cut, an index lies outside the dictionary (the
+    text names the first one and D), the bytes are more than 2^31 - 1 without "large", or j is the stream itself or no stream of the call."""
+    sizes = batch.out_sizes
+    if sizes is None:
+        raise RuntimeError("no outputs: no decode call on this batch object yet, or its launch has not been waited for")
+    n = len(sizes)
+    if len(specs) != n:
+        raise ValueError("specs: %d entries for the %d streams of the last decode call" % (len(specs), n))
+    rows, large, dict_streams, dict_ptrs, dict_lens = [None] * n, [False] * n, [DICT_NO_STREAM] * n, [None] * n, [0] * n
+    for i, spec in enumerate(specs):
+        if spec is None:
+            continue
+        if len(spec) not in (2, 3) or (len(spec) == 3 and spec[2] != "large") or isinstance(spec[0], bool) or not isinstance(spec[0], int) or spec[0] < 0:
+            raise ValueError("stream %d: a spec is (rows, j), (rows, tensor) or either with \"large\" behind it" % i)
+        rows[i], large[i], j = int(spec[0]), len(spec) == 3, spec[1]
+        if isinstance(j, torch.Tensor):
+            if j.dtype != torch.uint8 or j.dim() != 1 or not j.is_contiguous() or not j.is_cuda:
+                raise ValueError("stream %d: its dictionary is a %s tensor of shape %s%s, not a contiguous 1-D device tensor of torch.uint8" %
+                                 (i, j.dtype, tuple(j.shape), "" if j.is_cuda else " on the host"))
+            dict_ptrs[i], dict_lens[i] = j.data_ptr(), j.numel()
+        elif isinstance(j, bool) or not isinstance(j, int):
+            raise ValueError("stream %d: (rows, j) names the stream that holds the dictionary, (rows, tensor) the dictionary's bytes, and nothing else" % i)
+        elif j == i or not 0 <= j < n:
+            raise ValueError("stream %d: its dictionary stream %d is %s" % (i, j, "the stream itself" if j == i else "none of the %d streams of the last decode call" % n))
+        else:
+            dict_streams[i] = j
+    wanted = [i for i in range(n) if rows[i] is not None]
+    flags = [1 | (BYTES_OFFSETS64 if large[i] else 0) if rows[i] is not None else BYTES_SKIP for i in range(n)]
+    # a column of no rows is still measured and written: a capacity of 0 would only count, and offsets[0] would stay unwritten
+    caps = [None if r is None else max(r, 1) for r in rows]
+    res = batch.measure_dict_bytes_outputs(caps, [0] * n, dict_streams, dict_ptrs, dict_lens, None, [f & ~BYTES_SKIP for f in flags])
+    kept = {}
+    for i in wanted:
+        count, consumed, _, status, k, bad, first_bad, nbytes, D, dict_consumed, dict_status = res[i]
+        if status != 0:
+            raise ValueError("stream %d: %s (status %d) after %d values in %d of its %d delivered bytes, indices of %d bits" %
+                             (i, RLE_STATUS[status] if status < len(RLE_STATUS) else "an unknown status", status, count, consumed, sizes[i], k))
+        if count < rows[i]:
+            raise ValueError("stream %d: %d values in its runs, but the column has %d rows" % (i, count, rows[i]))
+        if dict_status != 0:
+            raise ValueError("stream %d: its dictionary is cut: %d whole entries in %d of its bytes" % (i, D, dict_consumed))
+        if rows[i] == 0:   # (the one element that was measured is not the column's)
+            bad, nbytes = 0, 0
+        if bad != 0:
+            raise ValueError("stream %d: %d of its %d values have an index outside its dictionary of %d entries, the first of them value %d" % (i, bad, rows[i], D, first_bad))
+        if nbytes > INT32_MAX and not large[i]:
+            raise ValueError("stream %d: %d bytes of strings, more than int32 offsets hold: ask for \"large\"" % (i, nbytes))
+        kept[i] = nbytes
+    up = lambda v: (v + SLOT_ALIGN - 1) // SLOT_ALIGN * SLOT_ALIGN
+    o_at, d_at, total = {}, {}, 0
+    for i in wanted:
+        o_at[i], total = total, up(total + (rows[i] + 1) * (8 if large[i] else 4))
+        d_at[i], total = total, up(total + kept[i])
+    buf = torch.empty(total + SLOT_ALIGN, dtype=torch.uint8, device="cuda")
+    skip = -buf.data_ptr() % SLOT_ALIGN
+    buf = buf[skip:skip + total]
+    base = buf.data_ptr()
+    if wanted:
+        # rows of 0: a capacity of 1 with a data capacity of 0 writes offsets[0] and offsets[1], and offsets[1]'s slot is the padding's
+        batch.undict_bytes_outputs([base + o_at[i] if i in o_at else None for i in range(n)], [base + d_at[i] if i in d_at else None for i in range(n)],
+                                   [kept.get(i, 0) for i in range(n)], [0 if c is None else c for c in caps], [0] * n, flags, None, dict_streams, dict_ptrs, dict_lens)
+    out = [None] * n
+    for i in wanted:
+        offsets = buf[o_at[i]:o_at[i] + (rows[i] + 1) * (8 if large[i] else 4)].view(torch.int64 if large[i] else torch.int32)
+        out[i] = (offsets, buf[d_at[i]:d_at[i] + kept[i]])
     return out
