@@ -760,9 +760,9 @@ BROTLI_DEC_API int BrotliAmdDebugUnrleHost(uint32_t n, const uint8_t* src, size_
  * and the stores.  So one long segment is expanded by every CU; its walk is one wave's.  A call that only counts is the first launch alone
  * (csrc/brotli_undbp.h, csrc/brotli_undbp_kernels.hip).
  *
- * OUT OF SCOPE: the byte part of DELTA_LENGTH_BYTE_ARRAY (`consumed` says where it begins); DELTA_BYTE_ARRAY's prefix copies; page framing --
- * thrift headers, v2's level sections --; a speculative parallel walk of one long segment; sign extension of elements narrower than 8 bytes.
- * Byte arrays behind a DICTIONARY are the undict-bytes calls' below. */
+ * OUT OF SCOPE: DELTA_BYTE_ARRAY's prefix copies; page framing -- thrift headers, v2's level sections --; a speculative parallel walk of one
+ * long segment; sign extension of elements narrower than 8 bytes.  Byte arrays behind a DICTIONARY are the undict-bytes calls' below, and the
+ * lengths AND bytes of DELTA_LENGTH_BYTE_ARRAY the undlba calls'. */
 #define BROTLI_AMD_UNDBP_OK 0u
 #define BROTLI_AMD_UNDBP_BAD_HEADER 1u
 #define BROTLI_AMD_UNDBP_BAD_WIDTH 2u
@@ -982,7 +982,7 @@ BROTLI_DEC_API int BrotliAmdDebugUndictHost(uint32_t n, const uint8_t* src, size
  * csrc/brotli_undict_bytes_kernels.hip).  A measuring call runs the same launches with every store predicated off.
  *
  * One item -- 1024 elements -- is one wave's work whatever its bytes: splitting an item of very long strings over several waves is out of
- * scope.  ALSO OUT OF SCOPE: PLAIN (non-dictionary) byte-array data pages; DELTA_LENGTH_BYTE_ARRAY and DELTA_BYTE_ARRAY; FIXED_LEN_BYTE_ARRAY
+ * scope.  ALSO OUT OF SCOPE: PLAIN (non-dictionary) byte-array data pages; DELTA_BYTE_ARRAY (DELTA_LENGTH_BYTE_ARRAY is the undlba calls' below); FIXED_LEN_BYTE_ARRAY
  * and INT96 dictionaries; nullable string columns in one call -- unnull over byte arrays; a caller uses BrotliAmdBatchUnnullOutputs' counting
  * call to find where a v1 index body begins --; page framing; keeping a dictionary's starts from one call to the next; a parallel walk of one
  * long dictionary or segment. */
@@ -1059,6 +1059,133 @@ BROTLI_DEC_API int BrotliAmdDebugUndictBytesHost(uint32_t n, const uint8_t* src,
                                                 const uint8_t* bits, const uint8_t* flags /* or NULL */, uint32_t src_skew, uint32_t offsets_skew,
                                                 uint32_t data_skew, uint32_t dict_skew, uint32_t item_elems, uint32_t order_seed, uint32_t word_seed,
                                                 BrotliAmdUndictBytesResult* results, uint64_t* dict_walks /* or NULL */);
+
+/* ---- Undlba on the device: DELTA_LENGTH_BYTE_ARRAY of outputs back into OFFSETS AND BYTES ----
+ *
+ * DELTA_LENGTH_BYTE_ARRAY is the one string encoding of Parquet that is parallel by construction: all lengths first, as one DELTA_BINARY_PACKED
+ * stream, then all values' bytes back to back.  A writer uses it for strings that are not dictionary-encoded.  These calls turn such a page
+ * body into an Arrow string column -- (offsets, data) -- in one call: the lengths are never an array in memory, every length is checked, and
+ * the bytes are one contiguous copy that is spread over the whole device.
+ *
+ * THE SEGMENT AND ITS PARAMETERS.  A segment is src[0, len) in device memory, at any alignment: a DELTA_BINARY_PACKED stream of N lengths and,
+ * directly behind it, the values' bytes.  Per segment: a capacity cap in ELEMENTS, flags, offset_base, the destinations d_offsets and d_data,
+ * and data_cap in bytes.
+ *
+ * LENGTHS.  The front part is read by undbp's grammar EXACTLY: the header, the blocks, the stops, the 64-bit wrapping value rule.  The
+ * result's first seven fields -- count, consumed, declared, blocks, status, block_values, miniblocks -- are those of BrotliAmdUndbpResult for
+ * the same bytes and the same cap, with undbp's meaning and undbp's status codes.  m = min(count, cap).  The length of element i < m is L_i,
+ * the low 32 bits of v_i as a signed int32: Parquet's INT32 arithmetic, and what Arrow's decoder computes.  L_i < 0 makes the element BAD: it
+ * is EMPTY (its length counts as 0), it is counted in `bad`, and the smallest such i is first_bad (UINT64_MAX: none).  `bytes` is the sum of
+ * the good L_i over i < m, in 64 bits, whatever data_cap is.
+ *
+ * DATA.  The data begins at src + consumed, whatever the status is, and data_avail = len - consumed.  data_status is
+ * BROTLI_AMD_UNDLBA_DATA_OK where bytes <= data_avail and BROTLI_AMD_UNDLBA_DATA_SHORT otherwise.  Delivered is
+ * d_data[0, min(bytes, data_avail, data_cap)), and it equals src[consumed, ...) byte for byte; the cut is exact to the byte.
+ * data_avail > bytes is no error where cap < count; where cap >= count it is the caller's to judge -- a page of a nullable column is one such
+ * case --, and both numbers are in the result.
+ *
+ * OFFSETS.  offsets[i] = offset_base + the sum of L_j over j < i, for i = 0 .. m: little-endian integers of 4 bytes, or of 8 with
+ * BROTLI_AMD_UNDLBA_OFFSETS64, truncated to that width.  They follow the lengths also where the data is SHORT or cut.  With
+ * BROTLI_AMD_UNDLBA_ENDS_ONLY offsets[0] is not written, d_offsets points at offsets[1] and m entries are written -- as in undict-bytes, so
+ * that the pages of a chunk append into one Arrow array.  With cap != 0, a d_offsets that is not NULL and no ENDS_ONLY, offsets[0] is written
+ * even where m == 0: a page with N == 0 is one such case.
+ *
+ * KINDS OF CALL.  cap == 0 only COUNTS and is the walk alone: the seven undbp fields and data_avail are filled, bytes and bad are 0 and
+ * first_bad is UINT64_MAX.  This is how a caller sizes d_data: a well-formed page has bytes == data_avail.  cap != 0 with neither destination
+ * only MEASURES: the same launches with every store off.  BROTLI_AMD_UNDLBA_SKIP is for BrotliAmdBatchUndlbaOutputs alone: the stream is
+ * skipped, and its result is zeros with first_bad UINT64_MAX.
+ *
+ * RESULT.  BrotliAmdUndlbaResult, 80 bytes.  Nothing in it depends on data_cap or on how the work was shared out; only bad, first_bad and
+ * bytes depend on cap.
+ *
+ * Examples (bytes: elements; offsets; other results):
+ *   80 01 04 04 00 02 00 00 00 00 61 62 62 63 63 63: "", "a", "bb", "ccc"; 0 0 1 3 6; consumed 10, bytes 6, data_avail 6
+ *   80 01 04 01 06 78 79 7a: "xyz"; 0 3; consumed 5
+ *   80 01 04 01 01 61 62: one length of -1; 0 0; bad 1, first_bad 0, bytes 0, data_avail 2, DATA_OK, no data byte written
+ *   80 01 04 01 0a 61 62: one length of 5 over 2 bytes; 0 5; bytes 5, data_avail 2, DATA_SHORT, data "ab"
+ *   80 01 04 00 00: none (N = 0); offset_base alone; count 0, consumed 5
+ *
+ * LOADS AND STORES.  No byte is written outside [d_data, d_data + min(bytes, data_avail, data_cap)) and outside the offsets named above;
+ * nothing is read outside the 16-byte-aligned span around [src, src + len).  OUT OF PLACE ONLY: stated, not checked.
+ *
+ * REFUSED ON THE HOST, in front of everything that touches the device, with a BrotliAmdLastError text that names the segment: unknown flag
+ * bits; BROTLI_AMD_UNDLBA_SKIP in the Segments call; cap > 2^56; data_cap != 0 with a NULL d_data; a NULL array with n != 0, but those named
+ * as optional.
+ *
+ * A call is seven launches in stream order, and no block ever waits for another: no spins, no flags, no atomics on offsets or data.  1. THE
+ * WALK, undbp's as it is, one wave a segment: the result's first seven fields, data_avail, the first value and the items' checkpoints.
+ * 2. THE DELTA SUMS, undbp's item function and group sum, one wave an item of BrotliAmdDebugUndbpItemDeltas() deltas: an undelta tile record
+ * an item.  3. UNDELTA'S CARRY LAUNCH: the value in front of every item's first delta.  4. THE LENGTHS, one wave an item: the lanes redo their
+ * 32 values on top of the carry-in and turn each into (L, bad) by one function; the wave's sum of good lengths is a second tile record, and
+ * the item's bad elements go to the result with one atomic add and one atomic minimum.  5. UNDELTA'S CARRY LAUNCH again, over the byte sums:
+ * the bytes in front of every item.  6. THE OFFSETS, one wave an item: a scan over the lanes' byte sums on top of the carry-in gives a lane
+ * its first offset; it stores its 32 neighbouring entries as aligned 16-byte words wherever it has a whole word, and singly at its two ends.
+ * The item that holds the segment's last delivered element writes bytes, data_status and the segment's entry of a table of copies on the
+ * device: src + consumed, d_data, min(bytes, data_avail, data_cap).  7. THE DATA: the ragged copy kernel itself over that table, the work
+ * split by bytes -- one page of a gigabyte of strings is spread over every CU, and an item of very long strings is nobody's single wave
+ * (csrc/brotli_undlba.h, csrc/brotli_undlba_kernels.hip).
+ *
+ * OUT OF SCOPE: DELTA_BYTE_ARRAY's prefix copies; PLAIN byte-array pages; nullable string columns in one call; repetition levels; page
+ * framing; a parallel walk of one long segment; lengths wider than INT32. */
+#define BROTLI_AMD_UNDLBA_OFFSETS64 2u    /* offsets of 8 bytes */
+#define BROTLI_AMD_UNDLBA_ENDS_ONLY 4u    /* offsets[0] is not written, and d_offsets points at offsets[1] */
+#define BROTLI_AMD_UNDLBA_SKIP 8u         /* BrotliAmdBatchUndlbaOutputs: the stream is skipped */
+#define BROTLI_AMD_UNDLBA_DATA_OK 0u
+#define BROTLI_AMD_UNDLBA_DATA_SHORT 1u
+
+typedef struct BrotliAmdUndlbaResult {
+  uint64_t count;         /* lengths decoded, whatever cap was */
+  uint64_t consumed;      /* undbp's: where the data begins */
+  uint64_t declared;      /* N */
+  uint64_t blocks;        /* blocks that gave at least one length */
+  uint32_t status;        /* BROTLI_AMD_UNDBP_* */
+  uint32_t block_values;  /* B */
+  uint32_t miniblocks;    /* M */
+  uint32_t data_status;   /* BROTLI_AMD_UNDLBA_DATA_* */
+  uint64_t bad;           /* delivered elements whose length was negative */
+  uint64_t first_bad;     /* the smallest such element index; UINT64_MAX: none */
+  uint64_t bytes;         /* of the delivered elements together, whatever data_cap was */
+  uint64_t data_avail;    /* len - consumed */
+} BrotliAmdUndlbaResult;
+
+/* n segments in DEVICE memory: the lengths and bytes in the src_lens[i] bytes at d_src[i]; the first caps[i] elements' offsets go to
+ * d_offsets[i] on top of offset_bases[i] (NULL: all 0) and their bytes to d_data[i], at most data_caps[i] of them, by flags[i] (NULL: all 0);
+ * results[i] says what segment i held.  d_offsets and d_data, or single entries of them, may be NULL (data_caps too, where d_data is): that
+ * destination is not written.  The launches run on hip_stream, and the call waits on that stream.  n == 0 returns 0.  A negative value, and a
+ * BrotliAmdLastError text that names the segment and what was wrong, for a NULL batch, a NULL array (but those named) with n != 0 and
+ * everything in the list above: all checked on the host in front of everything else, so nothing is launched and no byte is written. */
+BROTLI_DEC_API int BrotliAmdBatchUndlbaSegments(BrotliAmdBatch* batch, uint32_t n, const void* const* d_src, const size_t* src_lens,
+                                               void* const* d_offsets /* or NULL */, void* const* d_data /* or NULL */,
+                                               const uint64_t* data_caps /* or NULL */, const uint64_t* caps, const uint8_t* flags /* or NULL */,
+                                               const uint64_t* offset_bases /* or NULL */, BrotliAmdUndlbaResult* results, void* hip_stream);
+
+/* The same for the DELIVERED bytes of every stream of the last decode call on the object, by BrotliAmdBatchUndbpOutputs' rules for the three
+ * kinds of decode call.  A stream with BROTLI_AMD_UNDLBA_SKIP in flags[i] is skipped: none of its other parameters are looked at and its
+ * result is zeros with first_bad UINT64_MAX.  caps == NULL counts every stream and nothing else.  A negative value, and a BrotliAmdLastError
+ * text, as there. */
+BROTLI_DEC_API int BrotliAmdBatchUndlbaOutputs(BrotliAmdBatch* batch, void* const* d_offsets /* or NULL */, void* const* d_data /* or NULL */,
+                                              const uint64_t* data_caps /* or NULL */, const uint64_t* caps /* or NULL */,
+                                              const uint8_t* flags /* or NULL */, const uint64_t* offset_bases /* or NULL */,
+                                              BrotliAmdUndlbaResult* results);
+
+/* Milliseconds the undlba kernels took in the last of the two calls above (HIP events around its launches together), */
+BROTLI_DEC_API float BrotliAmdBatchLastUndlbaMs(BrotliAmdBatch* batch);
+/* and those of phase 1 (the walk), 2 (the delta sums), 3 (their carries), 4 (the lengths), 5 (their carries), 6 (the offsets) or 7 (the
+ * data) alone; another: 0. */
+BROTLI_DEC_API float BrotliAmdBatchLastUndlbaPhaseMs(BrotliAmdBatch* batch, uint32_t phase);
+
+/* Test hook (no device needed): all phases by the functions of csrc/brotli_undbp.h and csrc/brotli_undlba.h on the host.  Three buffers, each
+ * placed at its skew (0..15) past a 16-byte boundary in a room of its own: the source, the offsets and the data.  Segment i is src_lens[i]
+ * bytes at src_offs[i]; its offsets go to offsets_offs[i] and its bytes to data_offs[i] (UINT64_MAX: that destination is NULL).
+ * item_deltas: the deltas of an item, a multiple of 32, 0 for the device's own.  order_seed != 0: the items are taken in orders shuffled by
+ * it, in every phase (no result and no byte may depend on it).  0; -1 and a BrotliAmdLastError text for arguments that are refused or a
+ * segment or destination outside its buffer; -2 where a byte outside the destinations named above changed. */
+BROTLI_DEC_API int BrotliAmdDebugUndlbaHost(uint32_t n, const uint8_t* src, size_t src_size, uint8_t* offsets, size_t offsets_size, uint8_t* data,
+                                           size_t data_size, const uint64_t* src_offs, const uint64_t* src_lens, const uint64_t* offsets_offs,
+                                           const uint64_t* data_offs, const uint64_t* data_caps, const uint64_t* caps,
+                                           const uint64_t* offset_bases, const uint8_t* flags /* or NULL */, uint32_t src_skew,
+                                           uint32_t offsets_skew, uint32_t data_skew, uint32_t item_deltas, uint32_t order_seed,
+                                           BrotliAmdUndlbaResult* results);
 
 /* ---- Unnull on the device: dense values spread over nulls by definition levels ----
  *

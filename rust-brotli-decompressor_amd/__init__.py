@@ -58,6 +58,8 @@ BATCH_H_SYMBOLS = [
     "BrotliAmdDebugUnnullHost",
     "BrotliAmdBatchUndictBytesSegments", "BrotliAmdBatchUndictBytesOutputs", "BrotliAmdBatchLastUndictBytesMs", "BrotliAmdBatchLastUndictBytesPhaseMs",
     "BrotliAmdDebugUndictBytesHost",
+    "BrotliAmdBatchUndlbaSegments", "BrotliAmdBatchUndlbaOutputs", "BrotliAmdBatchLastUndlbaMs", "BrotliAmdBatchLastUndlbaPhaseMs",
+    "BrotliAmdDebugUndlbaHost",
 ]
 
 
@@ -141,6 +143,22 @@ class UndictBytesResult(ctypes.Structure):  # BrotliAmdUndictBytesResult: undict
     def astuple(self):
         return (self.count, self.consumed, self.runs, self.status, self.bits, self.bad, self.first_bad, self.bytes, self.dict_entries, self.dict_consumed,
                 self.dict_status)
+
+
+UNDLBA_OFFSETS64, UNDLBA_ENDS_ONLY, UNDLBA_SKIP = 2, 4, 8  # BROTLI_AMD_UNDLBA_*: a segment's flags
+UNDLBA_DATA_OK, UNDLBA_DATA_SHORT = 0, 1  # UndlbaResult.data_status
+UNDLBA_NONE = (1 << 64) - 1  # UndlbaResult.first_bad where no length was negative
+UNDLBA_NO_DESTINATION = (1 << 64) - 1  # undlba_host: a segment's offsets or data offset where it has no such destination
+
+
+class UndlbaResult(ctypes.Structure):  # BrotliAmdUndlbaResult: undbp's seven fields, what became of the data, the negative lengths and the bytes (batch.h)
+    _fields_ = [("count", ctypes.c_uint64), ("consumed", ctypes.c_uint64), ("declared", ctypes.c_uint64), ("blocks", ctypes.c_uint64),
+                ("status", ctypes.c_uint32), ("block_values", ctypes.c_uint32), ("miniblocks", ctypes.c_uint32), ("data_status", ctypes.c_uint32),
+                ("bad", ctypes.c_uint64), ("first_bad", ctypes.c_uint64), ("bytes", ctypes.c_uint64), ("data_avail", ctypes.c_uint64)]
+
+    def astuple(self):
+        return (self.count, self.consumed, self.declared, self.blocks, self.status, self.block_values, self.miniblocks, self.data_status, self.bad,
+                self.first_bad, self.bytes, self.data_avail)
 
 
 UNNULL_LENGTH_PREFIX, UNNULL_VALUES_FOLLOW = 1, 2  # BROTLI_AMD_UNNULL_*: a v1 data page's 4-byte length in front of the levels; the values lie behind them
@@ -284,7 +302,10 @@ def load_library():
              "BrotliAmdDebugUnnullHost": (None, [u32, vp, sz, vp, sz, vp, sz, vp, sz] + [vp] * 11 + [u32] * 6 + [vp])},
             {"BrotliAmdBatchUndictBytesSegments": (None, [vp, u32] + [vp] * 14), "BrotliAmdBatchUndictBytesOutputs": (None, [vp] * 13),
              "BrotliAmdBatchLastUndictBytesMs": (f32, [vp]), "BrotliAmdBatchLastUndictBytesPhaseMs": (f32, [vp, u32]),
-             "BrotliAmdDebugUndictBytesHost": (None, [u32, vp, sz, vp, sz, vp, sz, vp, sz] + [vp] * 12 + [u32] * 7 + [vp, vp])}):
+             "BrotliAmdDebugUndictBytesHost": (None, [u32, vp, sz, vp, sz, vp, sz, vp, sz] + [vp] * 12 + [u32] * 7 + [vp, vp])},
+            {"BrotliAmdBatchUndlbaSegments": (None, [vp, u32] + [vp] * 10), "BrotliAmdBatchUndlbaOutputs": (None, [vp] * 8),
+             "BrotliAmdBatchLastUndlbaMs": (f32, [vp]), "BrotliAmdBatchLastUndlbaPhaseMs": (f32, [vp, u32]),
+             "BrotliAmdDebugUndlbaHost": (None, [u32, vp, sz, vp, sz, vp, sz] + [vp] * 8 + [u32] * 5 + [vp])}):
         if hasattr(L, next(iter(protos))):
             for name, (restype, argtypes) in protos.items():
                 if restype is not None:
@@ -538,6 +559,34 @@ def undict_bytes_host(src: bytes, dictionary: bytes, segs, offsets_size, data_si
                                        word_seed, res, ctypes.byref(walks)) != 0:
         raise RuntimeError("BrotliAmdDebugUndictBytesHost failed: " + last_error())
     return rooms[0].raw[:offsets_size], rooms[1].raw[:data_size], [res[i].astuple() for i in range(n)], walks.value
+
+
+def undlba_host(src: bytes, segs, offsets_size, data_size, src_skew=0, offsets_skew=0, data_skew=0, item_deltas=0, order_seed=0, offsets_fill=0, data_fill=0):
+    """BrotliAmdDebugUndlbaHost: the DELTA_LENGTH_BYTE_ARRAY bodies in `src` back into offsets and bytes, by undbp's walk and items and the
+    functions of csrc/brotli_undlba.h on the host (no device needed).  segs: [(source offset, source length, offsets offset or
+    UNDLBA_NO_DESTINATION, data offset or UNDLBA_NO_DESTINATION, data capacity in bytes, capacity in elements, offset base, flags)]; the two
+    destinations have offsets_size and data_size bytes, all `offsets_fill` and `data_fill` in front of the call (or, where those are bytes of
+    that size, those); the three buffers are placed at their skews past a 16-byte boundary; item_deltas: the deltas of an item, a multiple of
+    32 (0: the device's, undbp_item_deltas()); order_seed != 0 shuffles the order in which the items are taken, in every phase.
+    -> (the offsets' bytes, the data's bytes, [(count, consumed, declared, blocks, status, block_values, miniblocks, data_status, bad,
+    first_bad, bytes, data_avail)])"""
+    L = load_library()
+    src, n = bytes(src), len(segs)
+    rooms = []
+    for fill, size, what in ((offsets_fill, offsets_size, "offsets_fill"), (data_fill, data_size, "data_fill")):
+        before = bytes(fill) if isinstance(fill, (bytes, bytearray)) else bytes([fill]) * size
+        if len(before) != size:
+            raise ValueError("%s: %d bytes for a destination of %d" % (what, len(before), size))
+        rooms.append(ctypes.create_string_buffer(before, max(1, size)))
+    s_buf = ctypes.create_string_buffer(src, max(1, len(src)))
+    # the call's order: source, length, offsets, data, data capacity, capacity, base
+    u64s = [(ctypes.c_uint64 * max(1, n))(*[s[k] if 0 <= s[k] < (1 << 64) else (1 << 64) - 1 for s in segs]) for k in range(7)]
+    flags = (ctypes.c_uint8 * max(1, n))(*[s[7] if 0 <= s[7] <= 255 else 255 for s in segs])
+    res = (UndlbaResult * max(1, n))()
+    if L.BrotliAmdDebugUndlbaHost(n, ctypes.addressof(s_buf), len(src), ctypes.addressof(rooms[0]), offsets_size, ctypes.addressof(rooms[1]), data_size, *u64s, flags,
+                                  src_skew, offsets_skew, data_skew, item_deltas, order_seed, res) != 0:
+        raise RuntimeError("BrotliAmdDebugUndlbaHost failed: " + last_error())
+    return rooms[0].raw[:offsets_size], rooms[1].raw[:data_size], [res[i].astuple() for i in range(n)]
 
 
 def unnull_host(src: bytes, values: bytes, segs, dst_size, valid_size, src_skew=0, dst_skew=0, values_skew=0, valid_skew=0, item_elems=0, order_seed=0, fill=0,
@@ -1118,6 +1167,61 @@ class Batch:
         """milliseconds the undict-bytes kernels took in the last undict_bytes_segments / undict_bytes_outputs: all launches together, or phase 1
         (the dictionary walk), 2 (the RLE walk), 3 (the lengths), 4 (the carries) or 5 (the expansion)"""
         return self._last_ms("UndictBytes", phase)
+
+    def undlba_segments(self, src_ptrs, src_lens, offsets_ptrs, data_ptrs, data_caps, caps, flags=None, offset_bases=None, stream=None):
+        """BrotliAmdBatchUndlbaSegments: the src_lens[i] bytes at the device address src_ptrs[i] are a DELTA_LENGTH_BYTE_ARRAY body -- a
+        DELTA_BINARY_PACKED stream of lengths and, directly behind it, the values' bytes.  The first caps[i] elements become an Arrow string
+        column: offsets on top of offset_bases[i] (None: 0) at offsets_ptrs[i] -- int32, or int64 with UNDLBA_OFFSETS64; with UNDLBA_ENDS_ONLY
+        without offsets[0] --, and the bytes at data_ptrs[i], at most data_caps[i] of them.  A destination that is None is not written: with
+        neither the call MEASURES.  A negative length gives an empty element and is counted.  caps[i] == 0 only counts: `data_avail` of the
+        result sizes the data.  Seven launches and a wait on `stream`.
+        -> [(count, consumed, declared, blocks, status, block_values, miniblocks, data_status, bad, first_bad, bytes, data_avail)]"""
+        n, col = len(src_ptrs), self._column
+        if len(src_lens) != n or len(caps) != n:
+            raise ValueError("src_ptrs, src_lens and caps: one entry per segment each")
+        res = (UndlbaResult * max(1, n))()
+        big = (1 << 64) - 1
+        self._filter_call("BrotliAmdBatchUndlbaSegments", n, col(ctypes.c_void_p, src_ptrs, n), col(ctypes.c_size_t, src_lens, n),
+                          self._ptr_column(offsets_ptrs, n, "offsets_ptrs"), self._ptr_column(data_ptrs, n, "data_ptrs"),
+                          col(ctypes.c_uint64, data_caps, n, big, "data_caps: one entry per segment"), col(ctypes.c_uint64, caps, n, big),
+                          self._byte_column(flags, n, "flags"), col(ctypes.c_uint64, offset_bases, n, None, "offset_bases: one entry per segment"), res, stream)
+        return [res[i].astuple() for i in range(n)]
+
+    def undlba_outputs(self, offsets_ptrs, data_ptrs, data_caps, caps, flags=None, offset_bases=None):
+        """BrotliAmdBatchUndlbaOutputs: the delivered bytes of every stream of the last decode call on this object (after decode_device: once
+        wait() has returned), taken as DELTA_LENGTH_BYTE_ARRAY bodies, become offsets at offsets_ptrs[i] and bytes at data_ptrs[i] as in
+        undlba_segments.  A stream with UNDLBA_SKIP in flags[i] is skipped, and its result is zeros.  caps None: every stream is counted and
+        nothing else.
+        -> [(count, consumed, declared, blocks, status, block_values, miniblocks, data_status, bad, first_bad, bytes, data_avail)], one per stream"""
+        n, col = self.out_n, self._column
+        if caps is not None and len(caps) != n:
+            raise ValueError("caps: one entry per stream of the last decode call")
+        res = (UndlbaResult * max(1, n))()
+        big = (1 << 64) - 1
+        self._filter_call("BrotliAmdBatchUndlbaOutputs", self._ptr_column(offsets_ptrs, n, "offsets_ptrs"), self._ptr_column(data_ptrs, n, "data_ptrs"),
+                          col(ctypes.c_uint64, data_caps, n, big, "data_caps: one entry per stream"), col(ctypes.c_uint64, caps, n, big),
+                          self._byte_column(flags, n, "flags"), col(ctypes.c_uint64, offset_bases, n, None, "offset_bases: one entry per stream"), res)
+        return [res[i].astuple() for i in range(n)]
+
+    def count_dlba_outputs(self, flags=None):
+        """undlba_outputs without capacities: how many lengths the DELTA_LENGTH_BYTE_ARRAY body of every stream of the last decode call holds,
+        where its bytes begin (`consumed`) and how many there are (`data_avail`); a stream with UNDLBA_SKIP in flags[i] is skipped.  The way to
+        size the destinations of the call that writes: a well-formed page has bytes == data_avail"""
+        return self.undlba_outputs(None, None, None, None, flags)
+
+    def measure_dlba_outputs(self, caps, flags=None):
+        """undlba_outputs without destinations: what the first caps[i] elements of every stream of the last decode call take -- `bytes` of the
+        result -- and which lengths are negative; caps[i] None skips the stream (UNDLBA_SKIP)"""
+        n = self.out_n
+        if len(caps) != n:
+            raise ValueError("caps: one entry per stream of the last decode call")
+        flags = [(flags[i] if flags is not None else 0) | (UNDLBA_SKIP if caps[i] is None else 0) for i in range(n)]
+        return self.undlba_outputs(None, None, None, [c or 0 for c in caps], flags)
+
+    def last_undlba_ms(self, phase=None):
+        """milliseconds the undlba kernels took in the last undlba_segments / undlba_outputs: all launches together, or phase 1 (the walk), 2
+        (the delta sums), 3 (their carries), 4 (the lengths), 5 (their carries), 6 (the offsets) or 7 (the data)"""
+        return self._last_ms("Undlba", phase)
 
     def _ptr_column(self, ptrs, n, what):
         """device addresses as the C calls take them: None stays NULL, and so does an entry that is None or 0"""

@@ -273,6 +273,26 @@ typedef struct BrotliAmdUndictBytesDict {
   uint64_t first_start;
 } BrotliAmdUndictBytesDict;
 
+// One segment of an undlba call (csrc/brotli_undlba_kernels.hip, csrc/brotli_undlba.h): the len bytes at src are a DELTA_BINARY_PACKED stream
+// of lengths and, directly behind it, the values' bytes; the first `cap` lengths become an Arrow string column: their running sums on top of
+// offset_base at `offsets` (NULL: none), 4 bytes each or 8 by flags, and the bytes one behind the other at `data` (NULL: none), cut at
+// data_cap.  Items, first_item and the checkpoints are undbp's; every segment has a result (BrotliAmdUndlbaResult, include/brotli/batch.h), its
+// first value and an entry of the table of copies behind the table, and every item a checkpoint, two tile records and two carries.  No
+// destination range overlaps a source range or another destination range.  Nothing outside [data, data + min(bytes, data_avail, data_cap))
+// and the offsets that batch.h names is written; nothing outside the 16-byte-aligned span around [src, src + len) is read.
+typedef struct BrotliAmdUndlbaSeg {
+  const uint8_t* src;
+  uint8_t* data;
+  uint64_t len;
+  uint64_t cap;
+  uint64_t first_item;
+  uint32_t flags;
+  uint32_t reserved;
+  uint8_t* offsets;
+  uint64_t data_cap;
+  uint64_t offset_base;
+} BrotliAmdUndlbaSeg;
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@
 //                   table's members and counted_device, and the four counted filters' templates do not know of it.
 //   undict-bytes    beside them as well: two destinations a segment, and a second table -- the call's DISTINCT dictionaries -- behind the
 //                   segments, so it has a launcher, a table and a device call of its own.
+//   undlba          beside them too: two destinations a segment and no dictionary; its launcher wants the bound of the bytes its copies move.
 //   the hooks       BrotliAmdDebug*Host run the device's functions of a filter's header (csrc/brotli_<filter>.h) on the host as the kernel's lanes
 //                   take them, for tests without a device.  They share the seeded orders, the serial carries, the argument checks and the
 //                   counted filters' closing block; each keeps its own phase loops.
@@ -21,6 +22,7 @@
 #include "brotli_undict.h"
 #include "brotli_undict_bytes.h"
 #include "brotli_undelta.h"
+#include "brotli_undlba.h"
 #include "brotli_unnull.h"
 #include "brotli_unrle.h"
 #include "brotli_unshuffle.h"
@@ -40,6 +42,9 @@ extern "C" uint64_t brotli_amd_unnull_scratch_bytes(uint64_t units, uint32_t n);
 extern "C" uint64_t brotli_amd_undict_bytes_scratch_bytes(uint64_t units, uint32_t n, uint32_t nd, uint64_t starts);
 extern "C" hipError_t brotli_amd_launch_undict_bytes(const void* d_segs, uint32_t n, uint64_t units, const void* d_dicts, uint32_t nd, void* d_scratch, hipStream_t stream,
                                                      const hipEvent_t* ev);
+// (csrc/brotli_undlba_kernels.hip: max_bytes: what the segments' copies add up to at the most)
+extern "C" uint64_t brotli_amd_undlba_scratch_bytes(uint64_t units, uint32_t n);
+extern "C" hipError_t brotli_amd_launch_undlba(const void* d_segs, uint32_t n, uint64_t units, uint64_t max_bytes, void* d_scratch, hipStream_t stream, const hipEvent_t* ev);
 extern "C" uint64_t brotli_amd_undelta_scratch_bytes(uint64_t units);
 extern "C" uint64_t brotli_amd_unvarint_scratch_bytes(uint64_t units, uint32_t n);
 extern "C" uint64_t brotli_amd_unrle_scratch_bytes(uint64_t units, uint32_t n);
@@ -62,8 +67,8 @@ namespace {
 
 // ---- the descriptor ----
 // What the host needs to know of a filter.  A filter of one launch has two events; undelta and unvarint have four around and between their three
-// launches, unrle and undict three, undbp and unnull five, undict-bytes six -- and a launcher of its own signature (undict_bytes_device).  The
-// counted filters' results lie first behind the table.
+// launches, unrle and undict three, undbp and unnull five, undict-bytes six and undlba eight -- the last two with launchers of their own
+// signatures (undict_bytes_device, undlba_device).  The counted filters' results lie first behind the table.
 struct FilterDesc {
   const char* name;   // in the texts of g_last_error
   SegCallWhat what;
@@ -94,6 +99,8 @@ const FilterDesc kFilter[kFilters] = {
     {"undict-bytes", {"hipMalloc(undict-bytes segments, dictionaries, results, checkpoints, tiles and entry positions)", "hipMemcpyAsync(undict-bytes segments)",
                       "hipStreamSynchronize(undict-bytes)"},
      "brotli_amd_undict_bytes kernels launch", nullptr, nullptr, 6u},
+    {"undlba", {"hipMalloc(undlba segments, results, checkpoints, tiles and copies)", "hipMemcpyAsync(undlba segments)", "hipStreamSynchronize(undlba)"},
+     "brotli_amd_undlba kernels launch", nullptr, nullptr, 8u},
 };
 
 typedef std::vector<BrotliAmdUnshuffleSeg> Segs;
@@ -554,6 +561,70 @@ int undict_bytes_device(BrotliAmdBatch* b, const BytesTable& t, BytesResult* res
   return 0;
 }
 
+// ---- undlba: a path of its own beside the counted one ----
+// A segment has undict-bytes' two destinations, data capacity and offset base, and no dictionary and no field width.  What the host knows of
+// the bytes that the call's copies move is a bound: min(len, data_cap) a segment that has a data destination.
+typedef BrotliAmdUndlbaResult DlbaResult;
+DlbaResult empty_dlba_result() { return brotli_amd_undlba_result(BrotliAmdUndbpResult{0u, 0u, 0u, 0u, 0u, 0u, 0u}, 0u); }
+
+__attribute__((noinline)) bool refuse_dlba(const char* what, const BrotliAmdUndlbaSeg& s, const char* who, size_t i) {
+  g_last_error = std::string("undlba ") + who + " " + std::to_string(i) + ": " + what + " (flags " + std::to_string(s.flags) + ", capacity " + std::to_string(s.cap) +
+                 ", data capacity " + std::to_string(s.data_cap) + ")";
+  return false;
+}
+// the shape check of one entry, in the order of batch.h's list (the outputs call has taken its skipped streams out in front of it)
+inline bool known_dlba(const BrotliAmdUndlbaSeg& s, const char* who, size_t i) {
+  const char* what = nullptr;
+  if ((s.flags & BROTLI_AMD_UNDLBA_SKIP) != 0u) what = "BROTLI_AMD_UNDLBA_SKIP is for the outputs of a decode call";
+  else if ((s.flags & ~BROTLI_AMD_UNDLBA_FLAGS) != 0u) what = "unknown flag bits";
+  else if (s.cap > BROTLI_AMD_UNDLBA_MAX_CAP) what = "a capacity above 2^56 elements";
+  else if (s.data_cap != 0u && !s.data) what = "no data destination for a data capacity that is not 0";
+  return !what || refuse_dlba(what, s, who, i);
+}
+
+struct DlbaTable {
+  std::vector<BrotliAmdUndlbaSeg> segs;
+  std::vector<size_t> where;
+  uint64_t items = 0, max_bytes = 0;
+  void reserve(size_t n) { segs.reserve(n); where.reserve(n); }
+  // entry i of a call: checked, then given its place among the items
+  bool push(BrotliAmdUndlbaSeg s, size_t i, const char* who) {
+    if (!known_dlba(s, who, i)) return false;
+    s.first_item = items;
+    segs.push_back(s);
+    where.push_back(i);
+    items += brotli_amd_undbp_items(s.cap, brotli_amd_undbp_item_deltas());
+    if (s.cap != 0u && s.data) max_bytes += std::min(s.len, s.data_cap);
+    return true;
+  }
+};
+
+// the table on `stream`, waited for, and its results: entry j's to results[where[j]] of the n_results, the others zeros
+int undlba_device(BrotliAmdBatch* b, const DlbaTable& t, DlbaResult* results, size_t n_results, hipStream_t stream) {
+  std::fill(results, results + n_results, empty_dlba_result());
+  if (t.segs.empty()) return 0;
+  DeviceGuard guard;
+  if (!hip_ok(hipSetDevice(b->device), "hipSetDevice")) return -1;
+  const FilterDesc& d = kFilter[kUndlba];
+  BrotliAmdBatch::FilterCall& call = b->filter[kUndlba];
+  const uint32_t n = (uint32_t)t.segs.size();
+  const uint64_t units = n + t.items;
+  const uint8_t* d_results = nullptr;
+  if (run_seg_call(&call.call, d.what, t.segs.data(), sizeof(BrotliAmdUndlbaSeg) * n, brotli_amd_undlba_scratch_bytes(units, n), d.events, stream,
+                   [&](uint8_t* d_table, uint8_t* d_scratch, const hipEvent_t* ev) {
+    d_results = d_scratch;
+    return hip_ok(brotli_amd_launch_undlba(d_table, n, units, t.max_bytes, d_scratch, stream, ev), d.launch_what);
+  }, &call.ms, call.phase_ms) != 0) return -1;
+  if (t.items == 0u) {   // (the walk alone: what lies between the other events is no launch's time)
+    std::fill(call.phase_ms + 1, std::end(call.phase_ms), 0.0f);
+    call.ms = call.phase_ms[0];
+  }
+  std::vector<DlbaResult> got(n);
+  if (!hip_ok(hipMemcpy(got.data(), d_results, sizeof(DlbaResult) * n, hipMemcpyDeviceToHost), "hipMemcpy(undlba results)")) return -1;
+  for (size_t j = 0; j < got.size(); j++) results[t.where[j]] = got[j];
+  return 0;
+}
+
 // ---- what the hooks share ----
 // The hooks run the device's functions on the host over every unit of a segment, source and destination each in a SkewedRoom (brotli_host.h).
 // a hook's buffers and skews
@@ -875,6 +946,40 @@ extern "C" int BrotliAmdBatchUndictBytesOutputs(BrotliAmdBatch* b, void* const* 
   return undict_bytes_device(b, t, results, outs.size(), b->last_stream);
 }
 
+extern "C" int BrotliAmdBatchUndlbaSegments(BrotliAmdBatch* b, uint32_t n, const void* const* d_src, const size_t* src_lens, void* const* d_offsets, void* const* d_data,
+                                            const uint64_t* data_caps, const uint64_t* caps, const uint8_t* flags, const uint64_t* offset_bases, BrotliAmdUndlbaResult* results,
+                                            void* hip_stream) {
+  if (!b || (n && (!d_src || !src_lens || !caps || !results))) return invalid_arguments(kUndlba);
+  no_times(b, kUndlba);
+  DlbaTable t;
+  t.reserve(n);
+  for (uint32_t i = 0; i < n; i++) {
+    const BrotliAmdUndlbaSeg s = {static_cast<const uint8_t*>(d_src[i]), static_cast<uint8_t*>(d_data ? d_data[i] : nullptr), src_lens[i], caps[i], 0u, flags ? flags[i] : 0u, 0u,
+                                  static_cast<uint8_t*>(d_offsets ? d_offsets[i] : nullptr), data_caps ? data_caps[i] : 0u, offset_bases ? offset_bases[i] : 0u};
+    if (!t.push(s, i, "segment")) return -1;
+  }
+  return undlba_device(b, t, results, n, static_cast<hipStream_t>(hip_stream));
+}
+extern "C" int BrotliAmdBatchUndlbaOutputs(BrotliAmdBatch* b, void* const* d_offsets, void* const* d_data, const uint64_t* data_caps, const uint64_t* caps,
+                                           const uint8_t* flags, const uint64_t* offset_bases, BrotliAmdUndlbaResult* results) {
+  if (!b || !results) return invalid_arguments(kUndlba);
+  no_times(b, kUndlba);
+  std::vector<DeliveredBytes> outs;
+  if (!delivered_outputs(b, &outs)) return -1;
+  DlbaTable t;
+  t.reserve(outs.size());
+  for (size_t i = 0; i < outs.size(); i++) {
+    const uint32_t f = flags ? flags[i] : 0u;
+    if ((f & BROTLI_AMD_UNDLBA_SKIP) != 0u) continue;   // skipped: none of its other parameters are looked at
+    // (without capacities every stream is counted, and no destination is looked at)
+    const BrotliAmdUndlbaSeg s = {outs[i].ptr, static_cast<uint8_t*>(caps && d_data ? d_data[i] : nullptr), outs[i].len, caps ? caps[i] : 0u, 0u, f, 0u,
+                                  static_cast<uint8_t*>(caps && d_offsets ? d_offsets[i] : nullptr), caps && data_caps ? data_caps[i] : 0u,
+                                  offset_bases ? offset_bases[i] : 0u};
+    if (!t.push(s, i, "stream")) return -1;
+  }
+  return undlba_device(b, t, results, outs.size(), b->last_stream);
+}
+
 extern "C" float BrotliAmdBatchLastUnnullMs(BrotliAmdBatch* b) { return b ? b->filter[kUnnull].ms : 0.0f; }
 extern "C" float BrotliAmdBatchLastUnnullPhaseMs(BrotliAmdBatch* b, uint32_t phase) { return phase_ms(b, kUnnull, phase); }
 extern "C" float BrotliAmdBatchLastUnshuffleMs(BrotliAmdBatch* b) { return b ? b->filter[kUnshuffle].ms : 0.0f; }
@@ -892,6 +997,8 @@ extern "C" float BrotliAmdBatchLastUndictMs(BrotliAmdBatch* b) { return b ? b->f
 extern "C" float BrotliAmdBatchLastUndictPhaseMs(BrotliAmdBatch* b, uint32_t phase) { return phase_ms(b, kUndict, phase); }
 extern "C" float BrotliAmdBatchLastUndictBytesMs(BrotliAmdBatch* b) { return b ? b->filter[kUndictBytes].ms : 0.0f; }
 extern "C" float BrotliAmdBatchLastUndictBytesPhaseMs(BrotliAmdBatch* b, uint32_t phase) { return phase_ms(b, kUndictBytes, phase); }
+extern "C" float BrotliAmdBatchLastUndlbaMs(BrotliAmdBatch* b) { return b ? b->filter[kUndlba].ms : 0.0f; }
+extern "C" float BrotliAmdBatchLastUndlbaPhaseMs(BrotliAmdBatch* b, uint32_t phase) { return phase_ms(b, kUndlba, phase); }
 extern "C" uint32_t BrotliAmdDebugUndbpItemDeltas(void) { return brotli_amd_undbp_item_deltas(); }
 extern "C" uint32_t BrotliAmdDebugUndbpWalkChunk(void) { return brotli_amd_undbp_walk_chunk(); }
 extern "C" uint32_t BrotliAmdDebugUnrleItemElems(void) { return brotli_amd_unrle_item_elems(); }
@@ -1293,6 +1400,92 @@ extern "C" int BrotliAmdDebugUndictBytesHost(uint32_t n, const uint8_t* src, siz
   }
   if (!oroom.changed_inside_only([&](size_t i) { return i < offsets_size && in_offsets[i]; })) { g_last_error = "undict-bytes wrote outside its offsets"; return -2; }
   if (!droom.changed_inside_only([&](size_t i) { return i < data_size && in_data[i]; })) { g_last_error = "undict-bytes wrote outside its data"; return -2; }
+  oroom.get(offsets, 0u, offsets_size);
+  droom.get(data, 0u, data_size);
+  std::copy(got.begin(), got.end(), results);
+  return 0;
+}
+
+// Undlba's phases over n segments given as offsets into one source, one offsets and one data buffer, each buffer in its room: every segment's
+// walk -- undbp's --, the items' delta sums in an order shuffled by the seed, the carries as undelta's hook takes them, the items' lengths in
+// another shuffled order, the carries of their bytes, the items' offsets in a third, and the segments' copies in a fourth.
+extern "C" int BrotliAmdDebugUndlbaHost(uint32_t n, const uint8_t* src, size_t src_size, uint8_t* offsets, size_t offsets_size, uint8_t* data, size_t data_size,
+                                        const uint64_t* src_offs, const uint64_t* src_lens, const uint64_t* offsets_offs, const uint64_t* data_offs,
+                                        const uint64_t* data_caps, const uint64_t* caps, const uint64_t* offset_bases, const uint8_t* flags, uint32_t src_skew,
+                                        uint32_t offsets_skew, uint32_t data_skew, uint32_t item_deltas, uint32_t order_seed, BrotliAmdUndlbaResult* results) {
+  const uint64_t none = ~(uint64_t)0;
+  if ((n && (!src_offs || !src_lens || !offsets_offs || !data_offs || !data_caps || !caps || !offset_bases || !results)) ||
+      !rooms_ok(src, src_size, offsets, offsets_size, src_skew, offsets_skew) || (data_size && !data) || data_skew > 15u)
+    return invalid_arguments(kUndlba);
+  if (item_deltas == 0u) item_deltas = brotli_amd_undbp_item_deltas();
+  if (!brotli_amd_undbp_item_ok(item_deltas)) { g_last_error = "invalid undlba arguments: an item that is no multiple of 32 deltas"; return -1; }
+  SkewedRoom sroom(src_size, src_skew, 0xA5), oroom(offsets_size, offsets_skew, 0x5A), droom(data_size, data_skew, 0x69);
+  std::vector<BrotliAmdUndlbaSeg> segs;
+  for (uint32_t i = 0; i < n; i++) {
+    const bool has_offsets = offsets_offs[i] != none, has_data = data_offs[i] != none;
+    const BrotliAmdUndlbaSeg s = {reinterpret_cast<const uint8_t*>((uintptr_t)(sroom.at() + src_offs[i])),
+                                  has_data ? reinterpret_cast<uint8_t*>((uintptr_t)(droom.at() + data_offs[i])) : nullptr, src_lens[i], caps[i], 0u, flags ? flags[i] : 0u, 0u,
+                                  has_offsets ? reinterpret_cast<uint8_t*>((uintptr_t)(oroom.at() + offsets_offs[i])) : nullptr, data_caps[i], offset_bases[i]};
+    if (!known_dlba(s, "segment", i)) return -1;
+    if (!lies_in(src_offs[i], src_lens[i], src_size) || (has_offsets && offsets_offs[i] > offsets_size) || (has_data && data_offs[i] > data_size)) return outside_buffer(kUndlba);
+    segs.push_back(s);
+  }
+  sroom.put(src, src_size);
+  oroom.put(offsets, offsets_size);
+  droom.put(data, data_size);
+  // phase 1: the walks.  A segment's capacity becomes its count and one more at the most: the walk marks the items of no other elements, and a
+  // capacity of 2^56 needs no table of its own.
+  HookItems<BrotliAmdUndbpCheckpoint> items;
+  std::vector<DlbaResult> got(n);
+  std::vector<uint64_t> firsts(n, 0u);
+  items.pre.assign(n + 1u, 0u);
+  auto slots_of = [&](uint32_t i) { return std::min(got[i].count, caps[i]) + ((segs[i].flags & BROTLI_AMD_UNDLBA_ENDS_ONLY) != 0u || caps[i] == 0u ? 0u : 1u); };
+  for (uint32_t i = 0; i < n; i++) {
+    BrotliAmdUndlbaSeg counting = segs[i];
+    counting.cap = 0u;
+    segs[i].cap = std::min<uint64_t>(caps[i], brotli_amd_undlba_host_walk(counting, item_deltas, nullptr, &firsts[i]).count + 1u);
+    segs[i].first_item = items.pre[i];
+    items.pre[i + 1u] = items.pre[i] + brotli_amd_undbp_items(segs[i].cap, item_deltas);
+    items.ckpts.resize(items.pre[i + 1u], BrotliAmdUndbpCheckpoint{BROTLI_AMD_UNDBP_NONE, BROTLI_AMD_UNDBP_NONE});
+    got[i] = brotli_amd_undlba_host_walk(segs[i], item_deltas, items.ckpts.data() + items.pre[i], &firsts[i]);
+    if (segs[i].offsets && slots_of(i) * brotli_amd_undlba_offset_width(segs[i].flags) > offsets_size - offsets_offs[i]) return outside_buffer(kUndlba);
+  }
+  oroom.snapshot();
+  droom.snapshot();
+  // phases 2 to 5
+  SeededOrder seeded(order_seed);
+  std::vector<BrotliAmdUndeltaTile> tiles(items.pre.back()), byte_tiles(items.pre.back());
+  items.shuffled(&seeded, [&](uint32_t i, BrotliAmdUndbpCheckpoint cp, uint64_t j, uint64_t g) {
+    tiles[g] = brotli_amd_undlba_host_sum(segs[i], got[i], cp, firsts[i], j, item_deltas);
+  });
+  const std::vector<uint64_t> carries = carries_of(tiles);
+  items.shuffled(&seeded, [&](uint32_t i, BrotliAmdUndbpCheckpoint cp, uint64_t j, uint64_t g) {
+    byte_tiles[g] = brotli_amd_undlba_host_lengths(segs[i], &got[i], cp, firsts[i], j, item_deltas, carries[g]);
+  });
+  const std::vector<uint64_t> byte_carries = carries_of(byte_tiles);
+  std::vector<uint64_t> kept(n, 0u);   // the bytes of every segment that its source and its data capacity leave
+  for (uint32_t i = 0; i < n; i++) {
+    uint64_t bytes = 0;
+    for (uint64_t g = items.pre[i]; g < items.pre[i + 1u]; g++) bytes += byte_tiles[g].sum;
+    kept[i] = segs[i].data && segs[i].cap != 0u ? std::min({bytes, got[i].data_avail, segs[i].data_cap}) : 0u;
+    if (kept[i] > data_size - (segs[i].data ? data_offs[i] : 0u)) return outside_buffer(kUndlba);
+  }
+  // phases 6 and 7: the table of copies starts as zeros
+  std::vector<BrotliAmdCopySeg> copies(n, BrotliAmdCopySeg{nullptr, nullptr, 0u});
+  items.shuffled(&seeded, [&](uint32_t i, BrotliAmdUndbpCheckpoint cp, uint64_t j, uint64_t g) {
+    brotli_amd_undlba_host_expand(segs[i], &got[i], cp, firsts[i], j, item_deltas, carries[g], byte_carries[g], &copies[i]);
+  });
+  std::vector<uint64_t> order = first_numbers(n);
+  seeded.shuffle(&order);
+  for (uint64_t i : order) brotli_amd_undlba_host_copy(copies[i]);
+  // no byte outside every segment's offsets and bytes may have changed
+  std::vector<uint8_t> in_offsets(offsets_size, 0), in_data(data_size, 0);
+  for (uint32_t i = 0; i < n; i++) {
+    if (segs[i].offsets) std::fill(in_offsets.begin() + offsets_offs[i], in_offsets.begin() + offsets_offs[i] + slots_of(i) * brotli_amd_undlba_offset_width(segs[i].flags), 1);
+    if (segs[i].data) std::fill(in_data.begin() + data_offs[i], in_data.begin() + data_offs[i] + kept[i], 1);
+  }
+  if (!oroom.changed_inside_only([&](size_t i) { return i < offsets_size && in_offsets[i]; })) { g_last_error = "undlba wrote outside its offsets"; return -2; }
+  if (!droom.changed_inside_only([&](size_t i) { return i < data_size && in_data[i]; })) { g_last_error = "undlba wrote outside its data"; return -2; }
   oroom.get(offsets, 0u, offsets_size);
   droom.get(data, 0u, data_size);
   std::copy(got.begin(), got.end(), results);

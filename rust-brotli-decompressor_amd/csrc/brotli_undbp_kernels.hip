@@ -29,6 +29,7 @@
 #include "brotli_run_items.h"    // the walk's frame, the scratch and the launcher
 #include "brotli_seg_walk.h"
 #include "brotli_undbp.h"
+#include "brotli_undbp_groups.h"   // an item's groups, a group a lane
 #include "brotli_wave_stage.h"
 
 namespace {
@@ -66,34 +67,9 @@ __global__ __launch_bounds__(kThreads) void brotli_amd_undbp_walk_kernel(const S
 }
 
 // ---- launches 2 and 4 ----
-// a lane's group: nf (0 .. 32) fields of k bits from the address `at` on, under min_delta
-struct Group { uint64_t at, min_delta; uint32_t k, nf; };
-
-// item g of the flat list: its segment i and its place j in it; the groups of its deltas [a, b), this lane's being *mine.  False: the item has
-// no deltas.
-__device__ __forceinline__ bool item_groups(uint8_t* lds, const Seg* __restrict__ segs, uint32_t n, const Result* __restrict__ results, const uint64_t* __restrict__ pre,
-                                            const Checkpoint* __restrict__ ckpts, uint64_t g, uint32_t lane, uint32_t* i_out, uint64_t* j_out, uint64_t* a_out, Group* mine) {
-  const uint32_t i = brotli_amd_seg_find(pre, n, g);
-  const uint64_t j = g - pre[i];
-  *i_out = i; *j_out = j;
-  *mine = Group{0u, 0u, 0u, 0u};
-  const Checkpoint cp = ckpts[g];
-  if (cp.off == BROTLI_AMD_UNDBP_NONE) return false;   // (beyond count; the same in every lane)
-  const Seg sg = segs[i];
-  const Result res = results[i];
-  uint64_t a, b;
-  brotli_amd_undbp_item_range(res.count, sg.cap, j, kItem, &a, &b);
-  *a_out = a;
-  if (a >= b) return false;
-  const uint64_t src = (uint64_t)(uintptr_t)sg.src, gl = a + (uint64_t)kGroup * lane;   // this lane's first delta
-  Stage rd(lds, src, sg.len, lane);
-  Group got = {0u, 0u, 0u, 0u};
-  brotli_amd_undbp_item_blocks(rd, sg.len, res.block_values / res.miniblocks, res.miniblocks, cp, a, b, [&](uint64_t lo, uint64_t hi, uint64_t pos, uint32_t k, uint64_t md, uint64_t m0) {
-    if (gl >= lo && gl < hi) got = Group{src + pos + (gl - m0) / 8u * k, md, k, (uint32_t)(hi - gl < kGroup ? hi - gl : kGroup)};
-  });
-  *mine = got;
-  return true;
-}
+// (a lane's group and the item function: csrc/brotli_undbp_groups.h)
+typedef brotli_amd_wave::DbpGroup Group;
+using brotli_amd_wave::dbp_item_groups;
 
 __global__ __launch_bounds__(kThreads) void brotli_amd_undbp_sum_kernel(const Seg* __restrict__ segs, uint32_t n, uint64_t items, const Result* __restrict__ results,
                                                                         const uint64_t* __restrict__ firsts, const uint64_t* __restrict__ pre,
@@ -103,7 +79,7 @@ __global__ __launch_bounds__(kThreads) void brotli_amd_undbp_sum_kernel(const Se
   for (uint64_t g = (uint64_t)blockIdx.x * kWaves + wave; g < items; g += (uint64_t)gridDim.x * kWaves) {
     uint32_t i; uint64_t j, a; Group grp;
     uint64_t sum = 0;
-    if (item_groups(stage[wave], segs, n, results, pre, ckpts, g, lane, &i, &j, &a, &grp)) {
+    if (dbp_item_groups<kItem>(stage[wave], segs, n, results, pre, ckpts, g, lane, &i, &j, &a, &grp)) {
       sum = brotli_amd_undbp_group_sum(grp.at, grp.k, grp.min_delta, grp.nf);
 #pragma unroll
       for (uint32_t off = 32; off != 0u; off >>= 1) sum += (uint64_t)__shfl_down((unsigned long long)sum, off, 64);
@@ -119,7 +95,7 @@ __global__ __launch_bounds__(kThreads) void brotli_amd_undbp_expand_kernel(const
   const uint32_t lane = threadIdx.x & 63u, wave = same(threadIdx.x >> 6);
   for (uint64_t g = (uint64_t)blockIdx.x * kWaves + wave; g < items; g += (uint64_t)gridDim.x * kWaves) {
     uint32_t i; uint64_t j, a = 0; Group grp;
-    const bool deltas = item_groups(stage[wave], segs, n, results, pre, ckpts, g, lane, &i, &j, &a, &grp);
+    const bool deltas = dbp_item_groups<kItem>(stage[wave], segs, n, results, pre, ckpts, g, lane, &i, &j, &a, &grp);
     if (ckpts[g].off == BROTLI_AMD_UNDBP_NONE) continue;
     const Seg sg = segs[i];
     if (j == 0u && (results[i].count == 0u || sg.cap == 0u)) continue;

@@ -342,6 +342,7 @@ def outputs_as_tensors(batch, specs):
 
 
 BYTES_OFFSETS64, BYTES_SKIP, BYTES_ALL = 2, 8, (1 << 64) - 1   # UNDICT_BYTES_OFFSETS64, UNDICT_BYTES_SKIP, UNDICT_BYTES_ALL
+DLBA_OFFSETS64, DLBA_SKIP = 2, 8   # UNDLBA_OFFSETS64, UNDLBA_SKIP
 INT32_MAX = (1 << 31) - 1
 
 
@@ -355,7 +356,12 @@ def outputs_as_strings(batch, specs):
     rows are in the page header, the bytes are not), one allocation and one writing call (Batch.undict_bytes_outputs); the indices never
     reach memory.  ValueError, naming the stream and what was found, where the runs do not end well (a status that is not OK), hold fewer
     values than rows (more are the last group's padding and are not judged), the dictionary is cut, an index lies outside the dictionary (the
-    text names the first one and D), the bytes are more than 2^31 - 1 without "large", or j is the stream itself or no stream of the call."""
+    text names the first one and D), the bytes are more than 2^31 - 1 without "large", or j is the stream itself or no stream of the call.
+    specs[i] may also be ("dlba", rows) or ("dlba", rows, "large") for a DELTA_LENGTH_BYTE_ARRAY page body of a required column -- the lengths
+    as DELTA_BINARY_PACKED, then the bytes --: one counting call (Batch.count_dlba_outputs gives the bytes there are), the same allocation, one
+    writing call (Batch.undlba_outputs).  ValueError for such a stream where the lengths do not end well, their number is not `rows` exactly
+    (the encoding states it: there is no padding to forgive), a length is negative (the text names the first one), or the lengths' sum is not
+    the bytes that are there (the text says which is larger).  Both kinds may stand in one call: two pairs of library calls into one buffer."""
     sizes = batch.out_sizes
     if sizes is None:
         raise RuntimeError("no outputs: no decode call on this batch object yet, or its launch has not been waited for")
@@ -363,8 +369,14 @@ def outputs_as_strings(batch, specs):
     if len(specs) != n:
         raise ValueError("specs: %d entries for the %d streams of the last decode call" % (len(specs), n))
     rows, large, dict_streams, dict_ptrs, dict_lens = [None] * n, [False] * n, [DICT_NO_STREAM] * n, [None] * n, [0] * n
+    dlba = {}   # the streams that are DELTA_LENGTH_BYTE_ARRAY bodies: their rows
     for i, spec in enumerate(specs):
         if spec is None:
+            continue
+        if len(spec) >= 1 and isinstance(spec[0], str) and spec[0] == "dlba":
+            if len(spec) not in (2, 3) or (len(spec) == 3 and spec[2] != "large") or isinstance(spec[1], bool) or not isinstance(spec[1], int) or spec[1] < 0:
+                raise ValueError("stream %d: a \"dlba\" spec is (\"dlba\", rows) or (\"dlba\", rows, \"large\")" % i)
+            dlba[i], large[i] = int(spec[1]), len(spec) == 3
             continue
         if len(spec) not in (2, 3) or (len(spec) == 3 and spec[2] != "large") or isinstance(spec[0], bool) or not isinstance(spec[0], int) or spec[0] < 0:
             raise ValueError("stream %d: a spec is (rows, j), (rows, tensor) or either with \"large\" behind it" % i)
@@ -402,6 +414,20 @@ def outputs_as_strings(batch, specs):
         if nbytes > INT32_MAX and not large[i]:
             raise ValueError("stream %d: %d bytes of strings, more than int32 offsets hold: ask for \"large\"" % (i, nbytes))
         kept[i] = nbytes
+    dlba_flags = [(DLBA_OFFSETS64 if large[i] else 0) if i in dlba else DLBA_SKIP for i in range(n)]
+    if dlba:   # the lengths state the rows, and the bytes that are there are the data's size
+        counted = batch.count_dlba_outputs(dlba_flags)
+        for i in sorted(dlba):
+            count, consumed, declared, _, status, _, _, _, _, _, _, avail = counted[i]
+            if status != 0:
+                raise ValueError("stream %d: %s (status %d) after %d lengths in %d of its %d delivered bytes, of %d declared" %
+                                 (i, DBP_STATUS[status] if status < len(DBP_STATUS) else "an unknown status", status, count, consumed, sizes[i], declared))
+            if count != dlba[i]:
+                raise ValueError("stream %d: %d lengths in its stream, but the column has %d rows" % (i, count, dlba[i]))
+            if avail > INT32_MAX and not large[i]:
+                raise ValueError("stream %d: %d bytes of strings, more than int32 offsets hold: ask for \"large\"" % (i, avail))
+            rows[i], kept[i] = dlba[i], avail
+        wanted = sorted(wanted + list(dlba))
     up = lambda v: (v + SLOT_ALIGN - 1) // SLOT_ALIGN * SLOT_ALIGN
     o_at, d_at, total = {}, {}, 0
     for i in wanted:
@@ -411,10 +437,22 @@ def outputs_as_strings(batch, specs):
     skip = -buf.data_ptr() % SLOT_ALIGN
     buf = buf[skip:skip + total]
     base = buf.data_ptr()
-    if wanted:
+    if len(wanted) > len(dlba):
         # rows of 0: a capacity of 1 with a data capacity of 0 writes offsets[0] and offsets[1], and offsets[1]'s slot is the padding's
-        batch.undict_bytes_outputs([base + o_at[i] if i in o_at else None for i in range(n)], [base + d_at[i] if i in d_at else None for i in range(n)],
-                                   [kept.get(i, 0) for i in range(n)], [0 if c is None else c for c in caps], [0] * n, flags, None, dict_streams, dict_ptrs, dict_lens)
+        of_dict = lambda at: [base + at[i] if i in at and i not in dlba else None for i in range(n)]
+        batch.undict_bytes_outputs(of_dict(o_at), of_dict(d_at), [0 if i in dlba else kept.get(i, 0) for i in range(n)], [0 if c is None else c for c in caps], [0] * n, flags,
+                                   None, dict_streams, dict_ptrs, dict_lens)
+    if dlba:
+        # (rows of 0: the stream has no lengths, as was counted, so a capacity of 1 writes offsets[0] alone)
+        written = batch.undlba_outputs([base + o_at[i] if i in dlba else None for i in range(n)], [base + d_at[i] if i in dlba else None for i in range(n)],
+                                       [kept[i] if i in dlba else 0 for i in range(n)], [max(dlba[i], 1) if i in dlba else 0 for i in range(n)], dlba_flags)
+        for i in sorted(dlba):
+            bad, first_bad, nbytes, avail = written[i][8:12]
+            if bad != 0:
+                raise ValueError("stream %d: %d of its %d lengths are negative, the first of them value %d" % (i, bad, dlba[i], first_bad))
+            if nbytes != avail:
+                raise ValueError("stream %d: its lengths add up to %d bytes and %d are there: %s" %
+                                 (i, nbytes, avail, "bytes are left over" if avail > nbytes else "the data is short"))
     out = [None] * n
     for i in wanted:
         offsets = buf[o_at[i]:o_at[i] + (rows[i] + 1) * (8 if large[i] else 4)].view(torch.int64 if large[i] else torch.int32)
