@@ -760,9 +760,9 @@ BROTLI_DEC_API int BrotliAmdDebugUnrleHost(uint32_t n, const uint8_t* src, size_
  * and the stores.  So one long segment is expanded by every CU; its walk is one wave's.  A call that only counts is the first launch alone
  * (csrc/brotli_undbp.h, csrc/brotli_undbp_kernels.hip).
  *
- * OUT OF SCOPE: DELTA_BYTE_ARRAY's prefix copies; page framing -- thrift headers, v2's level sections --; a speculative parallel walk of one
+ * OUT OF SCOPE: page framing -- thrift headers, v2's level sections --; a speculative parallel walk of one
  * long segment; sign extension of elements narrower than 8 bytes.  Byte arrays behind a DICTIONARY are the undict-bytes calls' below, and the
- * lengths AND bytes of DELTA_LENGTH_BYTE_ARRAY the undlba calls'. */
+ * lengths AND bytes of DELTA_LENGTH_BYTE_ARRAY the undlba calls', and DELTA_BYTE_ARRAY the undba calls'. */
 #define BROTLI_AMD_UNDBP_OK 0u
 #define BROTLI_AMD_UNDBP_BAD_HEADER 1u
 #define BROTLI_AMD_UNDBP_BAD_WIDTH 2u
@@ -982,7 +982,7 @@ BROTLI_DEC_API int BrotliAmdDebugUndictHost(uint32_t n, const uint8_t* src, size
  * csrc/brotli_undict_bytes_kernels.hip).  A measuring call runs the same launches with every store predicated off.
  *
  * One item -- 1024 elements -- is one wave's work whatever its bytes: splitting an item of very long strings over several waves is out of
- * scope.  ALSO OUT OF SCOPE: PLAIN (non-dictionary) byte-array data pages; DELTA_BYTE_ARRAY (DELTA_LENGTH_BYTE_ARRAY is the undlba calls' below); FIXED_LEN_BYTE_ARRAY
+ * scope.  ALSO OUT OF SCOPE: PLAIN (non-dictionary) byte-array data pages (DELTA_LENGTH_BYTE_ARRAY is the undlba calls' below, DELTA_BYTE_ARRAY the undba calls'); FIXED_LEN_BYTE_ARRAY
  * and INT96 dictionaries; nullable string columns in one call -- unnull over byte arrays; a caller uses BrotliAmdBatchUnnullOutputs' counting
  * call to find where a v1 index body begins --; page framing; keeping a dictionary's starts from one call to the next; a parallel walk of one
  * long dictionary or segment. */
@@ -1125,7 +1125,7 @@ BROTLI_DEC_API int BrotliAmdDebugUndictBytesHost(uint32_t n, const uint8_t* src,
  * split by bytes -- one page of a gigabyte of strings is spread over every CU, and an item of very long strings is nobody's single wave
  * (csrc/brotli_undlba.h, csrc/brotli_undlba_kernels.hip).
  *
- * OUT OF SCOPE: DELTA_BYTE_ARRAY's prefix copies; PLAIN byte-array pages; nullable string columns in one call; repetition levels; page
+ * OUT OF SCOPE: PLAIN byte-array pages (DELTA_BYTE_ARRAY is the undba calls' below); nullable string columns in one call; repetition levels; page
  * framing; a parallel walk of one long segment; lengths wider than INT32. */
 #define BROTLI_AMD_UNDLBA_OFFSETS64 2u    /* offsets of 8 bytes */
 #define BROTLI_AMD_UNDLBA_ENDS_ONLY 4u    /* offsets[0] is not written, and d_offsets points at offsets[1] */
@@ -1186,6 +1186,147 @@ BROTLI_DEC_API int BrotliAmdDebugUndlbaHost(uint32_t n, const uint8_t* src, size
                                            const uint64_t* offset_bases, const uint8_t* flags /* or NULL */, uint32_t src_skew,
                                            uint32_t offsets_skew, uint32_t data_skew, uint32_t item_deltas, uint32_t order_seed,
                                            BrotliAmdUndlbaResult* results);
+
+/* ---- Undba on the device: DELTA_BYTE_ARRAY of outputs back into OFFSETS AND BYTES ----
+ *
+ * DELTA_BYTE_ARRAY is Parquet's front coding: element i is the first p_i bytes of element i - 1 and then s_i bytes of its own.  Writers choose
+ * it for sorted strings and keys -- URLs, paths, ids --, and it is parquet-mr's default for BYTE_ARRAY under the V2 encodings.  These calls
+ * turn such a page body into an Arrow string column -- (offsets, data) -- in one call; the chain of prefix copies through the whole page is
+ * resolved on the device, by a local phase an item, a carry over the items' last elements, and a fill.
+ *
+ * THE SEGMENT AND ITS PARAMETERS.  A segment is src[0, len) in device memory, at any alignment, three parts directly behind one another: a
+ * DELTA_BINARY_PACKED stream P of N prefix lengths; a DELTA_BINARY_PACKED stream S of suffix lengths, from consumed_p on; the suffix bytes,
+ * back to back, from consumed_p + consumed_s on.  S and the bytes together are exactly a DELTA_LENGTH_BYTE_ARRAY body.  Per segment, as in
+ * undlba: a capacity cap in ELEMENTS, flags, offset_base, the destinations d_offsets and d_data, and data_cap in bytes.
+ *
+ * LENGTHS.  Both streams are read by undbp's grammar EXACTLY.  The result carries undbp's seven fields for P (.._p) and for S (.._s), S being
+ * read from src + consumed_p over len - consumed_p bytes -- consumed_s counts from there --, each with the meaning and the status codes of
+ * BrotliAmdUndbpResult for the same bytes and the same cap.  S is read from P's consumed whatever P's status is.  m = min(count_p, count_s,
+ * cap).  p_i and s_i are the low 32 bits of the values as signed int32.
+ *
+ * BAD ELEMENTS.  D_i = p_i + s_i in 64 bits, D_-1 = 0.  Element i < m breaks the rules where p_i < 0 (BROTLI_AMD_UNDBA_BAD_PREFIX_NEGATIVE),
+ * s_i < 0 (.._SUFFIX_NEGATIVE) or p_i > D_(i-1) (.._PREFIX_LONG): the first element's prefix is 0.  first_bad is the smallest such i
+ * (UINT64_MAX: none) and bad_kind the first of the three rules, in that order, that it broke.  Elements i >= first_bad are EMPTY: L_i = 0.
+ * Elements i < first_bad have L_i = D_i.  A bad prefix poisons everything behind it -- Arrow's decoder throws there --, unlike undlba's
+ * "empty and go on".  The upper 32 bits of a value are not looked at.
+ *
+ * OFFSETS.  Exactly undlba's rule over these L_i: offsets[i] = offset_base + the sum of L_j over j < i, i = 0 .. m, of 4 bytes or of 8 with
+ * BROTLI_AMD_UNDBA_OFFSETS64, truncated; with BROTLI_AMD_UNDBA_ENDS_ONLY offsets[0] is not written and d_offsets points at offsets[1]; with
+ * cap != 0, a d_offsets and no ENDS_ONLY, offsets[0] is written even where m == 0.
+ *
+ * DATA.  bytes = the sum of L_i over i < m; suffix_bytes = the sum of s_i over i < min(m, first_bad); data_avail = len - consumed_p -
+ * consumed_s.  Byte k of element i is byte k of element i - 1 where k < p_i, and otherwise suffix byte (the sum of s_j over j < i) + k - p_i.
+ * A suffix byte at or behind src + len reads as 0 and is never loaded.  Delivered is d_data[0, min(bytes, data_cap)), cut exactly to the
+ * byte: every copy's source lies in front of its destination, so a cut output is a prefix of the uncut one.  data_status is a set of bits:
+ * BROTLI_AMD_UNDBA_DATA_SHORT where suffix_bytes > data_avail, .._DATA_BAD where first_bad is set, .._DATA_COUNTS_DIFFER where count_p !=
+ * count_s with both walks OK.  Nothing in the result depends on data_cap or on how the work was shared out.
+ *
+ * KINDS OF CALL.  cap == 0 only COUNTS and is the two walks alone: the fourteen undbp fields and data_avail are filled (and COUNTS_DIFFER);
+ * bytes and suffix_bytes are 0 and first_bad is UINT64_MAX.  cap != 0 with neither destination only MEASURES: the same launches with every
+ * store off.  BROTLI_AMD_UNDBA_SKIP is for BrotliAmdBatchUndbaOutputs alone: the stream's result is zeros with first_bad UINT64_MAX.
+ *
+ * Examples (bytes: elements; offsets; other results):
+ *   80 01 04 01 00 | 80 01 04 01 06 | 78 79 7a: "xyz"; 0 3; consumed_p 5, consumed_s 5, bytes 3, suffix_bytes 3, data_avail 3
+ *   80 01 04 02 00 04 00 00 00 00 | 80 01 04 02 06 03 00 00 00 00 | 61 62 63 64: prefixes 0 2, suffix lengths 3 1: "abc", "abd"; 0 3 6;
+ *     data abcabd, bytes 6, suffix_bytes 4
+ *   the same with prefixes 0 4 (.. 02 00 08 00 ..): first_bad 1, PREFIX_LONG, DATA_BAD; 0 3 3; data abc, bytes 3, suffix_bytes 3
+ *   the second without its last byte: DATA_SHORT; 0 3 6; data abcab\0, data_avail 3
+ *   80 01 04 02 00 01 00 00 00 00 | 80 01 04 02 02 01 00 00 00 00 | 61: prefixes 0 -1: first_bad 1, PREFIX_NEGATIVE; 0 1 1; data a
+ *   80 01 04 01 02 | 80 01 04 01 02 | 61: a first prefix of 1: first_bad 0, PREFIX_LONG; 0 0; no data byte written
+ *   80 01 04 00 00 | 80 01 04 00 00: none (N = 0 in both); offset_base alone
+ *
+ * LOADS AND STORES.  No byte is written outside [d_data, d_data + min(bytes, data_cap)) and outside the offsets named above; nothing is read
+ * outside the 16-byte-aligned span around [src, src + len) and the call's own destinations.  OUT OF PLACE ONLY: stated, not checked.
+ *
+ * REFUSED ON THE HOST, in front of everything that touches the device, with a BrotliAmdLastError text ("undba segment i: ..") that names the
+ * segment: undlba's list -- unknown flag bits; BROTLI_AMD_UNDBA_SKIP in the Segments call; cap > 2^56; data_cap != 0 with a NULL d_data; a
+ * NULL array with n != 0, but those named as optional.
+ *
+ * A call is nine launches in stream order, and no block ever waits for another: no spins, no flags, no atomics on offsets or data.  1. THE
+ * WALKS, undbp's as it is, one wave a segment, P and then S from P's consumed: the result's fourteen fields, data_avail, both first values,
+ * both streams' checkpoints, and -- derived on the device -- both streams as undbp segments for the items.  2. THE DELTA SUMS of both streams,
+ * undbp's item function and group sum, one wave an item.  3. UNDELTA'S CARRY LAUNCH over both streams' records at once.  4. THE LENGTHS, one
+ * wave an item: the lanes redo their 32 values of both streams on top of the carry-ins and test every element against the one in front of
+ * it; the item's sums of L and of s up to ITS first bad element are two more tile records, and that element goes to the result with one
+ * atomic minimum.  5. THE CARRY LAUNCH again, over those.  6. THE OFFSETS as undlba stores them; an item behind first_bad takes the bytes in
+ * front of first_bad for its carry-in; the item of first_bad writes bad_kind, the last item bytes, suffix_bytes and data_status.  7. PHASE A,
+ * one wave an item, items in any order: with r_e = min(p_first .. p_e) inside the item, every element's suffix bytes [p_e, L_e) and its bytes
+ * [r_e, p_e), which element e - 1 of the same item has; the running string is kept in LDS up to BROTLI_AMD_UNDBA_LDS_STRING bytes, and a byte
+ * beyond that is found by walking back through the item's elements to the suffix that holds it.  The item's last element is recorded.
+ * 8. PHASE B, one wave a segment, its items one after the other: the LAST element of item j gets its bytes [0, r_last) from the last element
+ * of item j - 1, complete by then; the carried string is kept in LDS up to BROTLI_AMD_UNDBA_LDS_CARRY bytes, and a byte beyond that is read
+ * from the item whose phase A wrote it.  9. PHASE C, one wave an item, items in any order: every other element of an item j >= 1 gets its bytes
+ * [0, r_e) from the last element of item j - 1, the bytes of 64 elements spread evenly over the lanes (csrc/brotli_undba.h,
+ * csrc/brotli_undba_kernels.hip).
+ *
+ * OUT OF SCOPE: FIXED_LEN_BYTE_ARRAY under this encoding; nullable string columns in one call; page framing; a parallel walk of one long
+ * segment; a parallel carry over one segment's items (phase B is serial in a segment's items); lengths wider than INT32. */
+#define BROTLI_AMD_UNDBA_OFFSETS64 2u    /* offsets of 8 bytes */
+#define BROTLI_AMD_UNDBA_ENDS_ONLY 4u    /* offsets[0] is not written, and d_offsets points at offsets[1] */
+#define BROTLI_AMD_UNDBA_SKIP 8u         /* BrotliAmdBatchUndbaOutputs: the stream is skipped */
+#define BROTLI_AMD_UNDBA_DATA_OK 0u
+#define BROTLI_AMD_UNDBA_DATA_SHORT 1u          /* bits of data_status */
+#define BROTLI_AMD_UNDBA_DATA_BAD 2u
+#define BROTLI_AMD_UNDBA_DATA_COUNTS_DIFFER 4u
+#define BROTLI_AMD_UNDBA_BAD_NONE 0u
+#define BROTLI_AMD_UNDBA_BAD_PREFIX_NEGATIVE 1u
+#define BROTLI_AMD_UNDBA_BAD_SUFFIX_NEGATIVE 2u
+#define BROTLI_AMD_UNDBA_BAD_PREFIX_LONG 3u
+#define BROTLI_AMD_UNDBA_LDS_STRING 4096u  /* phase A's running string in LDS */
+#define BROTLI_AMD_UNDBA_LDS_CARRY 32768u  /* phase B's carried string in LDS */
+
+typedef struct BrotliAmdUndbaResult {
+  uint64_t count_p;         /* prefix lengths decoded, whatever cap was */
+  uint64_t consumed_p;      /* undbp's: where S begins */
+  uint64_t declared_p;      /* N of P */
+  uint64_t blocks_p;
+  uint32_t status_p;        /* BROTLI_AMD_UNDBP_* */
+  uint32_t block_values_p;
+  uint32_t miniblocks_p;
+  uint32_t data_status;     /* BROTLI_AMD_UNDBA_DATA_* bits */
+  uint64_t count_s;         /* suffix lengths decoded, whatever cap was */
+  uint64_t consumed_s;      /* undbp's, counted from src + consumed_p: where the suffix bytes begin */
+  uint64_t declared_s;
+  uint64_t blocks_s;
+  uint32_t status_s;
+  uint32_t block_values_s;
+  uint32_t miniblocks_s;
+  uint32_t bad_kind;        /* BROTLI_AMD_UNDBA_BAD_*: the rule that element first_bad broke */
+  uint64_t first_bad;       /* the smallest element index that broke a rule; UINT64_MAX: none */
+  uint64_t bytes;           /* of the delivered elements together, whatever data_cap was */
+  uint64_t suffix_bytes;    /* of their suffixes together */
+  uint64_t data_avail;      /* len - consumed_p - consumed_s */
+} BrotliAmdUndbaResult;
+
+/* n segments in DEVICE memory, with the arguments of BrotliAmdBatchUndlbaSegments and their rules. */
+BROTLI_DEC_API int BrotliAmdBatchUndbaSegments(BrotliAmdBatch* batch, uint32_t n, const void* const* d_src, const size_t* src_lens,
+                                              void* const* d_offsets /* or NULL */, void* const* d_data /* or NULL */,
+                                              const uint64_t* data_caps /* or NULL */, const uint64_t* caps, const uint8_t* flags /* or NULL */,
+                                              const uint64_t* offset_bases /* or NULL */, BrotliAmdUndbaResult* results, void* hip_stream);
+
+/* The same for the DELIVERED bytes of every stream of the last decode call on the object, by BrotliAmdBatchUndbpOutputs' rules for the three
+ * kinds of decode call.  A stream with BROTLI_AMD_UNDBA_SKIP in flags[i] is skipped: none of its other parameters are looked at and its
+ * result is zeros with first_bad UINT64_MAX.  caps == NULL counts every stream and nothing else. */
+BROTLI_DEC_API int BrotliAmdBatchUndbaOutputs(BrotliAmdBatch* batch, void* const* d_offsets /* or NULL */, void* const* d_data /* or NULL */,
+                                             const uint64_t* data_caps /* or NULL */, const uint64_t* caps /* or NULL */,
+                                             const uint8_t* flags /* or NULL */, const uint64_t* offset_bases /* or NULL */,
+                                             BrotliAmdUndbaResult* results);
+
+/* Milliseconds the undba kernels took in the last of the two calls above (HIP events around its launches together), */
+BROTLI_DEC_API float BrotliAmdBatchLastUndbaMs(BrotliAmdBatch* batch);
+/* and those of phase 1 (the walks), 2 (the delta sums), 3 (their carries), 4 (the lengths), 5 (their carries), 6 (the offsets), 7 (phase A),
+ * 8 (phase B) or 9 (phase C) alone; another: 0. */
+BROTLI_DEC_API float BrotliAmdBatchLastUndbaPhaseMs(BrotliAmdBatch* batch, uint32_t phase);
+
+/* Test hook (no device needed): all phases by the functions of csrc/brotli_undbp.h and csrc/brotli_undba.h on the host, with the arguments of
+ * BrotliAmdDebugUndlbaHost and its return values.  order_seed != 0: the items are taken in shuffled orders in every phase where the order is
+ * free -- all but phase B, which takes a segment's items one after the other and the segments in a shuffled order. */
+BROTLI_DEC_API int BrotliAmdDebugUndbaHost(uint32_t n, const uint8_t* src, size_t src_size, uint8_t* offsets, size_t offsets_size, uint8_t* data,
+                                          size_t data_size, const uint64_t* src_offs, const uint64_t* src_lens, const uint64_t* offsets_offs,
+                                          const uint64_t* data_offs, const uint64_t* data_caps, const uint64_t* caps,
+                                          const uint64_t* offset_bases, const uint8_t* flags /* or NULL */, uint32_t src_skew,
+                                          uint32_t offsets_skew, uint32_t data_skew, uint32_t item_deltas, uint32_t order_seed,
+                                          BrotliAmdUndbaResult* results);
 
 /* ---- Unnull on the device: dense values spread over nulls by definition levels ----
  *

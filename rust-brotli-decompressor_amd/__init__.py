@@ -60,6 +60,8 @@ BATCH_H_SYMBOLS = [
     "BrotliAmdDebugUndictBytesHost",
     "BrotliAmdBatchUndlbaSegments", "BrotliAmdBatchUndlbaOutputs", "BrotliAmdBatchLastUndlbaMs", "BrotliAmdBatchLastUndlbaPhaseMs",
     "BrotliAmdDebugUndlbaHost",
+    "BrotliAmdBatchUndbaSegments", "BrotliAmdBatchUndbaOutputs", "BrotliAmdBatchLastUndbaMs", "BrotliAmdBatchLastUndbaPhaseMs",
+    "BrotliAmdDebugUndbaHost",
 ]
 
 
@@ -159,6 +161,26 @@ class UndlbaResult(ctypes.Structure):  # BrotliAmdUndlbaResult: undbp's seven fi
     def astuple(self):
         return (self.count, self.consumed, self.declared, self.blocks, self.status, self.block_values, self.miniblocks, self.data_status, self.bad,
                 self.first_bad, self.bytes, self.data_avail)
+
+
+UNDBA_OFFSETS64, UNDBA_ENDS_ONLY, UNDBA_SKIP = 2, 4, 8  # BROTLI_AMD_UNDBA_*: a segment's flags
+UNDBA_DATA_OK, UNDBA_DATA_SHORT, UNDBA_DATA_BAD, UNDBA_DATA_COUNTS_DIFFER = 0, 1, 2, 4  # UndbaResult.data_status: bits
+UNDBA_BAD_NONE, UNDBA_BAD_PREFIX_NEGATIVE, UNDBA_BAD_SUFFIX_NEGATIVE, UNDBA_BAD_PREFIX_LONG = 0, 1, 2, 3  # UndbaResult.bad_kind
+UNDBA_BAD_KINDS = ("no rule", "a negative prefix length", "a negative suffix length", "a prefix longer than the element in front of it")
+UNDBA_NONE = (1 << 64) - 1  # UndbaResult.first_bad where no element broke a rule
+UNDBA_NO_DESTINATION = (1 << 64) - 1  # undba_host: a segment's offsets or data offset where it has no such destination
+UNDBA_LDS_STRING, UNDBA_LDS_CARRY = 4096, 32768  # BROTLI_AMD_UNDBA_LDS_*: the bytes of a running string that phases A and B keep in LDS
+
+
+class UndbaResult(ctypes.Structure):  # BrotliAmdUndbaResult: undbp's seven fields of both streams, the first bad element, the bytes (batch.h)
+    _fields_ = [("count_p", ctypes.c_uint64), ("consumed_p", ctypes.c_uint64), ("declared_p", ctypes.c_uint64), ("blocks_p", ctypes.c_uint64),
+                ("status_p", ctypes.c_uint32), ("block_values_p", ctypes.c_uint32), ("miniblocks_p", ctypes.c_uint32), ("data_status", ctypes.c_uint32),
+                ("count_s", ctypes.c_uint64), ("consumed_s", ctypes.c_uint64), ("declared_s", ctypes.c_uint64), ("blocks_s", ctypes.c_uint64),
+                ("status_s", ctypes.c_uint32), ("block_values_s", ctypes.c_uint32), ("miniblocks_s", ctypes.c_uint32), ("bad_kind", ctypes.c_uint32),
+                ("first_bad", ctypes.c_uint64), ("bytes", ctypes.c_uint64), ("suffix_bytes", ctypes.c_uint64), ("data_avail", ctypes.c_uint64)]
+
+    def astuple(self):
+        return tuple(getattr(self, name) for name, _ in self._fields_)
 
 
 UNNULL_LENGTH_PREFIX, UNNULL_VALUES_FOLLOW = 1, 2  # BROTLI_AMD_UNNULL_*: a v1 data page's 4-byte length in front of the levels; the values lie behind them
@@ -305,7 +327,10 @@ def load_library():
              "BrotliAmdDebugUndictBytesHost": (None, [u32, vp, sz, vp, sz, vp, sz, vp, sz] + [vp] * 12 + [u32] * 7 + [vp, vp])},
             {"BrotliAmdBatchUndlbaSegments": (None, [vp, u32] + [vp] * 10), "BrotliAmdBatchUndlbaOutputs": (None, [vp] * 8),
              "BrotliAmdBatchLastUndlbaMs": (f32, [vp]), "BrotliAmdBatchLastUndlbaPhaseMs": (f32, [vp, u32]),
-             "BrotliAmdDebugUndlbaHost": (None, [u32, vp, sz, vp, sz, vp, sz] + [vp] * 8 + [u32] * 5 + [vp])}):
+             "BrotliAmdDebugUndlbaHost": (None, [u32, vp, sz, vp, sz, vp, sz] + [vp] * 8 + [u32] * 5 + [vp])},
+            {"BrotliAmdBatchUndbaSegments": (None, [vp, u32] + [vp] * 10), "BrotliAmdBatchUndbaOutputs": (None, [vp] * 8),
+             "BrotliAmdBatchLastUndbaMs": (f32, [vp]), "BrotliAmdBatchLastUndbaPhaseMs": (f32, [vp, u32]),
+             "BrotliAmdDebugUndbaHost": (None, [u32, vp, sz, vp, sz, vp, sz] + [vp] * 8 + [u32] * 5 + [vp])}):
         if hasattr(L, next(iter(protos))):
             for name, (restype, argtypes) in protos.items():
                 if restype is not None:
@@ -586,6 +611,31 @@ def undlba_host(src: bytes, segs, offsets_size, data_size, src_skew=0, offsets_s
     if L.BrotliAmdDebugUndlbaHost(n, ctypes.addressof(s_buf), len(src), ctypes.addressof(rooms[0]), offsets_size, ctypes.addressof(rooms[1]), data_size, *u64s, flags,
                                   src_skew, offsets_skew, data_skew, item_deltas, order_seed, res) != 0:
         raise RuntimeError("BrotliAmdDebugUndlbaHost failed: " + last_error())
+    return rooms[0].raw[:offsets_size], rooms[1].raw[:data_size], [res[i].astuple() for i in range(n)]
+
+
+def undba_host(src: bytes, segs, offsets_size, data_size, src_skew=0, offsets_skew=0, data_skew=0, item_deltas=0, order_seed=0, offsets_fill=0, data_fill=0):
+    """BrotliAmdDebugUndbaHost: the DELTA_BYTE_ARRAY bodies in `src` back into offsets and bytes, by undbp's walk and items and the functions
+    of csrc/brotli_undba.h on the host (no device needed), with undlba_host's arguments: segs: [(source offset, source length, offsets offset
+    or UNDBA_NO_DESTINATION, data offset or UNDBA_NO_DESTINATION, data capacity in bytes, capacity in elements, offset base, flags)];
+    order_seed != 0 shuffles the order in which the items are taken in every phase where it is free.
+    -> (the offsets' bytes, the data's bytes, [UndbaResult's twenty fields in their order])"""
+    L = load_library()
+    src, n = bytes(src), len(segs)
+    rooms = []
+    for fill, size, what in ((offsets_fill, offsets_size, "offsets_fill"), (data_fill, data_size, "data_fill")):
+        before = bytes(fill) if isinstance(fill, (bytes, bytearray)) else bytes([fill]) * size
+        if len(before) != size:
+            raise ValueError("%s: %d bytes for a destination of %d" % (what, len(before), size))
+        rooms.append(ctypes.create_string_buffer(before, max(1, size)))
+    s_buf = ctypes.create_string_buffer(src, max(1, len(src)))
+    # the call's order: source, length, offsets, data, data capacity, capacity, base
+    u64s = [(ctypes.c_uint64 * max(1, n))(*[s[k] if 0 <= s[k] < (1 << 64) else (1 << 64) - 1 for s in segs]) for k in range(7)]
+    flags = (ctypes.c_uint8 * max(1, n))(*[s[7] if 0 <= s[7] <= 255 else 255 for s in segs])
+    res = (UndbaResult * max(1, n))()
+    if L.BrotliAmdDebugUndbaHost(n, ctypes.addressof(s_buf), len(src), ctypes.addressof(rooms[0]), offsets_size, ctypes.addressof(rooms[1]), data_size, *u64s, flags,
+                                 src_skew, offsets_skew, data_skew, item_deltas, order_seed, res) != 0:
+        raise RuntimeError("BrotliAmdDebugUndbaHost failed: " + last_error())
     return rooms[0].raw[:offsets_size], rooms[1].raw[:data_size], [res[i].astuple() for i in range(n)]
 
 
@@ -1222,6 +1272,58 @@ class Batch:
         """milliseconds the undlba kernels took in the last undlba_segments / undlba_outputs: all launches together, or phase 1 (the walk), 2
         (the delta sums), 3 (their carries), 4 (the lengths), 5 (their carries), 6 (the offsets) or 7 (the data)"""
         return self._last_ms("Undlba", phase)
+
+    def undba_segments(self, src_ptrs, src_lens, offsets_ptrs, data_ptrs, data_caps, caps, flags=None, offset_bases=None, stream=None):
+        """BrotliAmdBatchUndbaSegments: the src_lens[i] bytes at the device address src_ptrs[i] are a DELTA_BYTE_ARRAY body -- a
+        DELTA_BINARY_PACKED stream of prefix lengths, one of suffix lengths and the suffix bytes, directly behind one another.  The first
+        caps[i] elements become an Arrow string column with undlba_segments' arguments and flags (UNDBA_*).  The first element that breaks a
+        rule, and every one behind it, is empty.  caps[i] == 0 only counts; with neither destination the call MEASURES: `bytes` of the
+        result sizes the data.  Nine launches and a wait on `stream`.
+        -> [UndbaResult's twenty fields in their order]"""
+        n, col = len(src_ptrs), self._column
+        if len(src_lens) != n or len(caps) != n:
+            raise ValueError("src_ptrs, src_lens and caps: one entry per segment each")
+        res = (UndbaResult * max(1, n))()
+        big = (1 << 64) - 1
+        self._filter_call("BrotliAmdBatchUndbaSegments", n, col(ctypes.c_void_p, src_ptrs, n), col(ctypes.c_size_t, src_lens, n),
+                          self._ptr_column(offsets_ptrs, n, "offsets_ptrs"), self._ptr_column(data_ptrs, n, "data_ptrs"),
+                          col(ctypes.c_uint64, data_caps, n, big, "data_caps: one entry per segment"), col(ctypes.c_uint64, caps, n, big),
+                          self._byte_column(flags, n, "flags"), col(ctypes.c_uint64, offset_bases, n, None, "offset_bases: one entry per segment"), res, stream)
+        return [res[i].astuple() for i in range(n)]
+
+    def undba_outputs(self, offsets_ptrs, data_ptrs, data_caps, caps, flags=None, offset_bases=None):
+        """BrotliAmdBatchUndbaOutputs: the delivered bytes of every stream of the last decode call on this object (after decode_device: once
+        wait() has returned), taken as DELTA_BYTE_ARRAY bodies, become offsets at offsets_ptrs[i] and bytes at data_ptrs[i] as in
+        undba_segments.  A stream with UNDBA_SKIP in flags[i] is skipped, and its result is zeros.  caps None: every stream is counted and
+        nothing else.  -> [UndbaResult's twenty fields in their order], one per stream"""
+        n, col = self.out_n, self._column
+        if caps is not None and len(caps) != n:
+            raise ValueError("caps: one entry per stream of the last decode call")
+        res = (UndbaResult * max(1, n))()
+        big = (1 << 64) - 1
+        self._filter_call("BrotliAmdBatchUndbaOutputs", self._ptr_column(offsets_ptrs, n, "offsets_ptrs"), self._ptr_column(data_ptrs, n, "data_ptrs"),
+                          col(ctypes.c_uint64, data_caps, n, big, "data_caps: one entry per stream"), col(ctypes.c_uint64, caps, n, big),
+                          self._byte_column(flags, n, "flags"), col(ctypes.c_uint64, offset_bases, n, None, "offset_bases: one entry per stream"), res)
+        return [res[i].astuple() for i in range(n)]
+
+    def count_dba_outputs(self, flags=None):
+        """undba_outputs without capacities: the two walks of every stream of the last decode call alone -- how many prefix and suffix lengths
+        its DELTA_BYTE_ARRAY body holds and how many suffix bytes are there (`data_avail`); a stream with UNDBA_SKIP in flags[i] is skipped"""
+        return self.undba_outputs(None, None, None, None, flags)
+
+    def measure_dba_outputs(self, caps, flags=None):
+        """undba_outputs without destinations: what the first caps[i] elements of every stream of the last decode call take -- `bytes` of the
+        result, which sizes the data --, and the first element that breaks a rule; caps[i] None skips the stream (UNDBA_SKIP)"""
+        n = self.out_n
+        if len(caps) != n:
+            raise ValueError("caps: one entry per stream of the last decode call")
+        flags = [(flags[i] if flags is not None else 0) | (UNDBA_SKIP if caps[i] is None else 0) for i in range(n)]
+        return self.undba_outputs(None, None, None, [c or 0 for c in caps], flags)
+
+    def last_undba_ms(self, phase=None):
+        """milliseconds the undba kernels took in the last undba_segments / undba_outputs: all launches together, or phase 1 (the walks), 2
+        (the delta sums), 3 (their carries), 4 (the lengths), 5 (their carries), 6 (the offsets), 7 (phase A), 8 (phase B) or 9 (phase C)"""
+        return self._last_ms("Undba", phase)
 
     def _ptr_column(self, ptrs, n, what):
         """device addresses as the C calls take them: None stays NULL, and so does an entry that is None or 0"""

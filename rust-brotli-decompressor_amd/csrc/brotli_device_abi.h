@@ -293,6 +293,21 @@ typedef struct BrotliAmdUndlbaSeg {
   uint64_t offset_base;
 } BrotliAmdUndlbaSeg;
 
+// One segment of an undba call (csrc/brotli_undba_kernels.hip, csrc/brotli_undba.h) has undlba's fields with undlba's meanings: the len bytes
+// at src are a DELTA_BINARY_PACKED stream of prefix lengths, one of suffix lengths directly behind it, and the suffix bytes behind that.  Items
+// and first_item are undbp's, for both streams alike; behind the table every segment has a result (BrotliAmdUndbaResult, include/brotli/batch.h),
+// both streams as undbp segments and undbp results, and two first values, and every item two checkpoints, four tile records, four carries and
+// the record of its last element.  No destination range overlaps a source range or another destination range.  Nothing outside
+// [data, data + min(bytes, data_cap)) and the offsets that batch.h names is written; nothing outside the 16-byte-aligned span around
+// [src, src + len) and the call's own destinations is read.
+typedef BrotliAmdUndlbaSeg BrotliAmdUndbaSeg;
+// What phase A leaves of an item for phases B and C: its LAST element's place in the segment's data, its length and r = min(p) over the item.
+typedef struct BrotliAmdUndbaLast {
+  uint64_t at;
+  uint32_t len;
+  uint32_t r;
+} BrotliAmdUndbaLast;
+
 #ifdef __cplusplus
 }
 #endif

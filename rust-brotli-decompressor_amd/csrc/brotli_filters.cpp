@@ -12,6 +12,7 @@
 //   undict-bytes    beside them as well: two destinations a segment, and a second table -- the call's DISTINCT dictionaries -- behind the
 //                   segments, so it has a launcher, a table and a device call of its own.
 //   undlba          beside them too: two destinations a segment and no dictionary; its launcher wants the bound of the bytes its copies move.
+//   undba           beside them too: undlba's segments and checks under its own name, a result of its own.
 //   the hooks       BrotliAmdDebug*Host run the device's functions of a filter's header (csrc/brotli_<filter>.h) on the host as the kernel's lanes
 //                   take them, for tests without a device.  They share the seeded orders, the serial carries, the argument checks and the
 //                   counted filters' closing block; each keeps its own phase loops.
@@ -22,6 +23,7 @@
 #include "brotli_undict.h"
 #include "brotli_undict_bytes.h"
 #include "brotli_undelta.h"
+#include "brotli_undba.h"
 #include "brotli_undlba.h"
 #include "brotli_unnull.h"
 #include "brotli_unrle.h"
@@ -45,6 +47,11 @@ extern "C" hipError_t brotli_amd_launch_undict_bytes(const void* d_segs, uint32_
 // (csrc/brotli_undlba_kernels.hip: max_bytes: what the segments' copies add up to at the most)
 extern "C" uint64_t brotli_amd_undlba_scratch_bytes(uint64_t units, uint32_t n);
 extern "C" hipError_t brotli_amd_launch_undlba(const void* d_segs, uint32_t n, uint64_t units, uint64_t max_bytes, void* d_scratch, hipStream_t stream, const hipEvent_t* ev);
+// (csrc/brotli_undba_kernels.hip)
+extern "C" uint64_t brotli_amd_undba_scratch_bytes(uint64_t units, uint32_t n);
+extern "C" hipError_t brotli_amd_launch_undba(const void* d_segs, uint32_t n, uint64_t units, void* d_scratch, hipStream_t stream, const hipEvent_t* ev);
+extern "C" uint32_t brotli_amd_undba_lds_string(void);
+extern "C" uint32_t brotli_amd_undba_lds_carry(void);
 extern "C" uint64_t brotli_amd_undelta_scratch_bytes(uint64_t units);
 extern "C" uint64_t brotli_amd_unvarint_scratch_bytes(uint64_t units, uint32_t n);
 extern "C" uint64_t brotli_amd_unrle_scratch_bytes(uint64_t units, uint32_t n);
@@ -67,8 +74,8 @@ namespace {
 
 // ---- the descriptor ----
 // What the host needs to know of a filter.  A filter of one launch has two events; undelta and unvarint have four around and between their three
-// launches, unrle and undict three, undbp and unnull five, undict-bytes six and undlba eight -- the last two with launchers of their own
-// signatures (undict_bytes_device, undlba_device).  The counted filters' results lie first behind the table.
+// launches, unrle and undict three, undbp and unnull five, undict-bytes six, undlba eight and undba ten -- the last three with launchers of their own
+// signatures (undict_bytes_device, undlba_device, undba_device).  The counted filters' results lie first behind the table.
 struct FilterDesc {
   const char* name;   // in the texts of g_last_error
   SegCallWhat what;
@@ -101,6 +108,8 @@ const FilterDesc kFilter[kFilters] = {
      "brotli_amd_undict_bytes kernels launch", nullptr, nullptr, 6u},
     {"undlba", {"hipMalloc(undlba segments, results, checkpoints, tiles and copies)", "hipMemcpyAsync(undlba segments)", "hipStreamSynchronize(undlba)"},
      "brotli_amd_undlba kernels launch", nullptr, nullptr, 8u},
+    {"undba", {"hipMalloc(undba segments, results, checkpoints, tiles and last elements)", "hipMemcpyAsync(undba segments)", "hipStreamSynchronize(undba)"},
+     "brotli_amd_undba kernels launch", nullptr, nullptr, 10u},
 };
 
 typedef std::vector<BrotliAmdUnshuffleSeg> Segs;
@@ -625,6 +634,67 @@ int undlba_device(BrotliAmdBatch* b, const DlbaTable& t, DlbaResult* results, si
   return 0;
 }
 
+// ---- undba: undlba's segments and checks under its own name, a result and a launcher of its own ----
+typedef BrotliAmdUndbaResult DbaResult;
+DbaResult empty_dba_result() { const BrotliAmdUndbpResult none = {0u, 0u, 0u, 0u, 0u, 0u, 0u}; return brotli_amd_undba_result(none, none, 0u); }
+
+__attribute__((noinline)) bool refuse_dba(const char* what, const BrotliAmdUndbaSeg& s, const char* who, size_t i) {
+  g_last_error = std::string("undba ") + who + " " + std::to_string(i) + ": " + what + " (flags " + std::to_string(s.flags) + ", capacity " + std::to_string(s.cap) +
+                 ", data capacity " + std::to_string(s.data_cap) + ")";
+  return false;
+}
+// the shape check of one entry, in the order of batch.h's list (the outputs call has taken its skipped streams out in front of it)
+inline bool known_dba(const BrotliAmdUndbaSeg& s, const char* who, size_t i) {
+  const char* what = nullptr;
+  if ((s.flags & BROTLI_AMD_UNDBA_SKIP) != 0u) what = "BROTLI_AMD_UNDBA_SKIP is for the outputs of a decode call";
+  else if ((s.flags & ~BROTLI_AMD_UNDBA_FLAGS) != 0u) what = "unknown flag bits";
+  else if (s.cap > BROTLI_AMD_UNDBA_MAX_CAP) what = "a capacity above 2^56 elements";
+  else if (s.data_cap != 0u && !s.data) what = "no data destination for a data capacity that is not 0";
+  return !what || refuse_dba(what, s, who, i);
+}
+
+struct DbaTable {
+  std::vector<BrotliAmdUndbaSeg> segs;
+  std::vector<size_t> where;
+  uint64_t items = 0;
+  void reserve(size_t n) { segs.reserve(n); where.reserve(n); }
+  // entry i of a call: checked, then given its place among the items
+  bool push(BrotliAmdUndbaSeg s, size_t i, const char* who) {
+    if (!known_dba(s, who, i)) return false;
+    s.first_item = items;
+    segs.push_back(s);
+    where.push_back(i);
+    items += brotli_amd_undbp_items(s.cap, brotli_amd_undbp_item_deltas());
+    return true;
+  }
+};
+
+// the table on `stream`, waited for, and its results: entry j's to results[where[j]] of the n_results, the others zeros
+int undba_device(BrotliAmdBatch* b, const DbaTable& t, DbaResult* results, size_t n_results, hipStream_t stream) {
+  std::fill(results, results + n_results, empty_dba_result());
+  if (t.segs.empty()) return 0;
+  DeviceGuard guard;
+  if (!hip_ok(hipSetDevice(b->device), "hipSetDevice")) return -1;
+  const FilterDesc& d = kFilter[kUndba];
+  BrotliAmdBatch::FilterCall& call = b->filter[kUndba];
+  const uint32_t n = (uint32_t)t.segs.size();
+  const uint64_t units = n + t.items;
+  const uint8_t* d_results = nullptr;
+  if (run_seg_call(&call.call, d.what, t.segs.data(), sizeof(BrotliAmdUndbaSeg) * n, brotli_amd_undba_scratch_bytes(units, n), d.events, stream,
+                   [&](uint8_t* d_table, uint8_t* d_scratch, const hipEvent_t* ev) {
+    d_results = d_scratch;
+    return hip_ok(brotli_amd_launch_undba(d_table, n, units, d_scratch, stream, ev), d.launch_what);
+  }, &call.ms, call.phase_ms) != 0) return -1;
+  if (t.items == 0u) {   // (the walks alone: what lies between the other events is no launch's time)
+    std::fill(call.phase_ms + 1, std::end(call.phase_ms), 0.0f);
+    call.ms = call.phase_ms[0];
+  }
+  std::vector<DbaResult> got(n);
+  if (!hip_ok(hipMemcpy(got.data(), d_results, sizeof(DbaResult) * n, hipMemcpyDeviceToHost), "hipMemcpy(undba results)")) return -1;
+  for (size_t j = 0; j < got.size(); j++) results[t.where[j]] = got[j];
+  return 0;
+}
+
 // ---- what the hooks share ----
 // The hooks run the device's functions on the host over every unit of a segment, source and destination each in a SkewedRoom (brotli_host.h).
 // a hook's buffers and skews
@@ -980,6 +1050,42 @@ extern "C" int BrotliAmdBatchUndlbaOutputs(BrotliAmdBatch* b, void* const* d_off
   return undlba_device(b, t, results, outs.size(), b->last_stream);
 }
 
+extern "C" int BrotliAmdBatchUndbaSegments(BrotliAmdBatch* b, uint32_t n, const void* const* d_src, const size_t* src_lens, void* const* d_offsets, void* const* d_data,
+                                           const uint64_t* data_caps, const uint64_t* caps, const uint8_t* flags, const uint64_t* offset_bases, BrotliAmdUndbaResult* results,
+                                           void* hip_stream) {
+  if (!b || (n && (!d_src || !src_lens || !caps || !results))) return invalid_arguments(kUndba);
+  no_times(b, kUndba);
+  DbaTable t;
+  t.reserve(n);
+  for (uint32_t i = 0; i < n; i++) {
+    const BrotliAmdUndbaSeg s = {static_cast<const uint8_t*>(d_src[i]), static_cast<uint8_t*>(d_data ? d_data[i] : nullptr), src_lens[i], caps[i], 0u, flags ? flags[i] : 0u, 0u,
+                                 static_cast<uint8_t*>(d_offsets ? d_offsets[i] : nullptr), data_caps ? data_caps[i] : 0u, offset_bases ? offset_bases[i] : 0u};
+    if (!t.push(s, i, "segment")) return -1;
+  }
+  return undba_device(b, t, results, n, static_cast<hipStream_t>(hip_stream));
+}
+extern "C" int BrotliAmdBatchUndbaOutputs(BrotliAmdBatch* b, void* const* d_offsets, void* const* d_data, const uint64_t* data_caps, const uint64_t* caps,
+                                          const uint8_t* flags, const uint64_t* offset_bases, BrotliAmdUndbaResult* results) {
+  if (!b || !results) return invalid_arguments(kUndba);
+  no_times(b, kUndba);
+  std::vector<DeliveredBytes> outs;
+  if (!delivered_outputs(b, &outs)) return -1;
+  DbaTable t;
+  t.reserve(outs.size());
+  for (size_t i = 0; i < outs.size(); i++) {
+    const uint32_t f = flags ? flags[i] : 0u;
+    if ((f & BROTLI_AMD_UNDBA_SKIP) != 0u) continue;   // skipped: none of its other parameters are looked at
+    // (without capacities every stream is counted, and no destination is looked at)
+    const BrotliAmdUndbaSeg s = {outs[i].ptr, static_cast<uint8_t*>(caps && d_data ? d_data[i] : nullptr), outs[i].len, caps ? caps[i] : 0u, 0u, f, 0u,
+                                 static_cast<uint8_t*>(caps && d_offsets ? d_offsets[i] : nullptr), caps && data_caps ? data_caps[i] : 0u,
+                                 offset_bases ? offset_bases[i] : 0u};
+    if (!t.push(s, i, "stream")) return -1;
+  }
+  return undba_device(b, t, results, outs.size(), b->last_stream);
+}
+
+extern "C" float BrotliAmdBatchLastUndbaMs(BrotliAmdBatch* b) { return b ? b->filter[kUndba].ms : 0.0f; }
+extern "C" float BrotliAmdBatchLastUndbaPhaseMs(BrotliAmdBatch* b, uint32_t phase) { return phase_ms(b, kUndba, phase); }
 extern "C" float BrotliAmdBatchLastUnnullMs(BrotliAmdBatch* b) { return b ? b->filter[kUnnull].ms : 0.0f; }
 extern "C" float BrotliAmdBatchLastUnnullPhaseMs(BrotliAmdBatch* b, uint32_t phase) { return phase_ms(b, kUnnull, phase); }
 extern "C" float BrotliAmdBatchLastUnshuffleMs(BrotliAmdBatch* b) { return b ? b->filter[kUnshuffle].ms : 0.0f; }
@@ -1486,6 +1592,131 @@ extern "C" int BrotliAmdDebugUndlbaHost(uint32_t n, const uint8_t* src, size_t s
   }
   if (!oroom.changed_inside_only([&](size_t i) { return i < offsets_size && in_offsets[i]; })) { g_last_error = "undlba wrote outside its offsets"; return -2; }
   if (!droom.changed_inside_only([&](size_t i) { return i < data_size && in_data[i]; })) { g_last_error = "undlba wrote outside its data"; return -2; }
+  oroom.get(offsets, 0u, offsets_size);
+  droom.get(data, 0u, data_size);
+  std::copy(got.begin(), got.end(), results);
+  return 0;
+}
+
+// Undba's phases over n segments given as offsets into one source, one offsets and one data buffer, each buffer in its room: every segment's
+// two walks -- undbp's --, the items' delta sums of both streams in an order shuffled by the seed, the carries as undelta's hook takes them, the
+// items' tests and sums in another shuffled order, their carries, the offsets in a third, phase A in a fourth, phase B segment by segment in a
+// shuffled order of the segments, and phase C in a sixth.
+extern "C" int BrotliAmdDebugUndbaHost(uint32_t n, const uint8_t* src, size_t src_size, uint8_t* offsets, size_t offsets_size, uint8_t* data, size_t data_size,
+                                       const uint64_t* src_offs, const uint64_t* src_lens, const uint64_t* offsets_offs, const uint64_t* data_offs,
+                                       const uint64_t* data_caps, const uint64_t* caps, const uint64_t* offset_bases, const uint8_t* flags, uint32_t src_skew,
+                                       uint32_t offsets_skew, uint32_t data_skew, uint32_t item_deltas, uint32_t order_seed, BrotliAmdUndbaResult* results) {
+  const uint64_t none = ~(uint64_t)0;
+  if ((n && (!src_offs || !src_lens || !offsets_offs || !data_offs || !data_caps || !caps || !offset_bases || !results)) ||
+      !rooms_ok(src, src_size, offsets, offsets_size, src_skew, offsets_skew) || (data_size && !data) || data_skew > 15u)
+    return invalid_arguments(kUndba);
+  if (item_deltas == 0u) item_deltas = brotli_amd_undbp_item_deltas();
+  if (!brotli_amd_undbp_item_ok(item_deltas)) { g_last_error = "invalid undba arguments: an item that is no multiple of 32 deltas"; return -1; }
+  SkewedRoom sroom(src_size, src_skew, 0xA5), oroom(offsets_size, offsets_skew, 0x5A), droom(data_size, data_skew, 0x69);
+  std::vector<BrotliAmdUndbaSeg> segs;
+  for (uint32_t i = 0; i < n; i++) {
+    const bool has_offsets = offsets_offs[i] != none, has_data = data_offs[i] != none;
+    const BrotliAmdUndbaSeg s = {reinterpret_cast<const uint8_t*>((uintptr_t)(sroom.at() + src_offs[i])),
+                                 has_data ? reinterpret_cast<uint8_t*>((uintptr_t)(droom.at() + data_offs[i])) : nullptr, src_lens[i], caps[i], 0u, flags ? flags[i] : 0u, 0u,
+                                 has_offsets ? reinterpret_cast<uint8_t*>((uintptr_t)(oroom.at() + offsets_offs[i])) : nullptr, data_caps[i], offset_bases[i]};
+    if (!known_dba(s, "segment", i)) return -1;
+    if (!lies_in(src_offs[i], src_lens[i], src_size) || (has_offsets && offsets_offs[i] > offsets_size) || (has_data && data_offs[i] > data_size)) return outside_buffer(kUndba);
+    segs.push_back(s);
+  }
+  sroom.put(src, src_size);
+  oroom.put(offsets, offsets_size);
+  droom.put(data, data_size);
+  // phase 1: the walks.  A segment's capacity becomes its values and one more at the most: the walks mark the items of no other elements, and
+  // a capacity of 2^56 needs no table of its own.  P's checkpoints, and S's beside them.
+  HookItems<BrotliAmdUndbpCheckpoint> items;
+  std::vector<BrotliAmdUndbpCheckpoint> ckpts_s;
+  std::vector<DbaResult> got(n);
+  std::vector<uint64_t> firsts_p(n, 0u), firsts_s(n, 0u);
+  items.pre.assign(n + 1u, 0u);
+  auto slots_of = [&](uint32_t i) {
+    return brotli_amd_undba_m(got[i].count_p, got[i].count_s, caps[i]) + ((segs[i].flags & BROTLI_AMD_UNDBA_ENDS_ONLY) != 0u || caps[i] == 0u ? 0u : 1u);
+  };
+  for (uint32_t i = 0; i < n; i++) {
+    BrotliAmdUndbaSeg counting = segs[i];
+    counting.cap = 0u;
+    const DbaResult counted = brotli_amd_undba_host_walk(counting, item_deltas, nullptr, nullptr, &firsts_p[i], &firsts_s[i]);
+    segs[i].cap = std::min<uint64_t>(caps[i], std::max(counted.count_p, counted.count_s) + 1u);
+    segs[i].first_item = items.pre[i];
+    items.pre[i + 1u] = items.pre[i] + brotli_amd_undbp_items(segs[i].cap, item_deltas);
+    items.ckpts.resize(items.pre[i + 1u], BrotliAmdUndbpCheckpoint{BROTLI_AMD_UNDBP_NONE, BROTLI_AMD_UNDBP_NONE});
+    ckpts_s.resize(items.pre[i + 1u], BrotliAmdUndbpCheckpoint{BROTLI_AMD_UNDBP_NONE, BROTLI_AMD_UNDBP_NONE});
+    got[i] = brotli_amd_undba_host_walk(segs[i], item_deltas, items.ckpts.data() + items.pre[i], ckpts_s.data() + items.pre[i], &firsts_p[i], &firsts_s[i]);
+    if (segs[i].offsets && slots_of(i) * brotli_amd_undlba_offset_width(segs[i].flags) > offsets_size - offsets_offs[i]) return outside_buffer(kUndba);
+  }
+  oroom.snapshot();
+  droom.snapshot();
+  // phases 2 to 5
+  SeededOrder seeded(order_seed);
+  const uint64_t all = items.pre.back();
+  std::vector<BrotliAmdUndeltaTile> tiles_p(all), tiles_s(all), tiles_l(all), tiles_x(all);
+  items.shuffled(&seeded, [&](uint32_t i, BrotliAmdUndbpCheckpoint cp, uint64_t j, uint64_t g) {
+    brotli_amd_undba_host_sum(segs[i], got[i], cp, ckpts_s[g], firsts_p[i], firsts_s[i], j, item_deltas, &tiles_p[g], &tiles_s[g]);
+  });
+  const std::vector<uint64_t> carries_p = carries_of(tiles_p), carries_s = carries_of(tiles_s);
+  auto item_of = [&](uint32_t i, BrotliAmdUndbpCheckpoint cp, uint64_t j, uint64_t g) {
+    return brotli_amd_undba_host_item(segs[i], got[i], cp, ckpts_s[g], firsts_p[i], firsts_s[i], j, item_deltas, carries_p[g], carries_s[g]);
+  };
+  items.shuffled(&seeded, [&](uint32_t i, BrotliAmdUndbpCheckpoint cp, uint64_t j, uint64_t g) {
+    brotli_amd_undba_host_lengths(item_of(i, cp, j, g), j, &got[i], &tiles_l[g], &tiles_x[g]);
+  });
+  const std::vector<uint64_t> carries_l = carries_of(tiles_l), carries_x = carries_of(tiles_x);
+  // what item g, whose first element is lo, has in front of it of L and of s
+  auto sums_in = [&](uint32_t i, uint64_t g, uint64_t lo, uint64_t* bytes_in, uint64_t* suffix_in) {
+    const uint64_t fb = got[i].first_bad, gb = lo > fb ? items.pre[i] + brotli_amd_undba_item_of(fb, item_deltas) : g;
+    *bytes_in = brotli_amd_undba_sum_in(fb, lo, carries_l[g], carries_l[gb], tiles_l[gb].sum);
+    *suffix_in = brotli_amd_undba_sum_in(fb, lo, carries_x[g], carries_x[gb], tiles_x[gb].sum);
+  };
+  // phase 6
+  items.shuffled(&seeded, [&](uint32_t i, BrotliAmdUndbpCheckpoint cp, uint64_t j, uint64_t g) {
+    const BrotliAmdUndbaHostItem it = item_of(i, cp, j, g);
+    uint64_t bytes_in, suffix_in;
+    sums_in(i, g, it.lo, &bytes_in, &suffix_in);
+    brotli_amd_undba_host_expand(segs[i], &got[i], it, j, item_deltas, bytes_in, suffix_in);
+  });
+  std::vector<uint64_t> kept(n, 0u);   // the bytes of every segment that its data capacity leaves
+  for (uint32_t i = 0; i < n; i++) {
+    kept[i] = segs[i].cap != 0u ? brotli_amd_undba_keep(segs[i], got[i].bytes) : 0u;
+    if (kept[i] > data_size - (segs[i].data ? data_offs[i] : 0u)) return outside_buffer(kUndba);
+  }
+  // phases 7 to 9
+  std::vector<BrotliAmdUndbaLast> lasts(all, BrotliAmdUndbaLast{0u, 0u, 0u});
+  std::vector<uint8_t> string(brotli_amd_undba_lds_string()), carried(brotli_amd_undba_lds_carry());
+  auto lens_of = [&](uint32_t i, BrotliAmdUndbpCheckpoint cp, uint64_t j, uint64_t g, uint64_t* bytes_in, uint64_t* suffix_in) {
+    const BrotliAmdUndbaHostItem it = item_of(i, cp, j, g);
+    sums_in(i, g, it.lo, bytes_in, suffix_in);
+    return brotli_amd_undba_host_lens(it, got[i].first_bad);
+  };
+  items.shuffled(&seeded, [&](uint32_t i, BrotliAmdUndbpCheckpoint cp, uint64_t j, uint64_t g) {
+    if (kept[i] == 0u) return;
+    uint64_t bytes_in, suffix_in;
+    const BrotliAmdUndbaHostLens lens = lens_of(i, cp, j, g, &bytes_in, &suffix_in);
+    lasts[g] = brotli_amd_undba_host_a((uint64_t)(uintptr_t)segs[i].data, kept[i], (uint64_t)(uintptr_t)segs[i].src + got[i].consumed_p + got[i].consumed_s, got[i].data_avail,
+                                       lens.p.data(), lens.s.data(), (uint32_t)lens.p.size(), bytes_in, suffix_in, string.data(), (uint32_t)string.size());
+  });
+  std::vector<uint64_t> order = first_numbers(n);
+  seeded.shuffle(&order);
+  for (uint64_t i : order)
+    if (kept[i] != 0u)
+      brotli_amd_undba_host_b((uint64_t)(uintptr_t)segs[i].data, kept[i], lasts.data() + items.pre[i], items.pre[i + 1u] - items.pre[i], carried.data(), (uint32_t)carried.size());
+  items.shuffled(&seeded, [&](uint32_t i, BrotliAmdUndbpCheckpoint cp, uint64_t j, uint64_t g) {
+    if (kept[i] == 0u || j == 0u) return;
+    uint64_t bytes_in, suffix_in;
+    const BrotliAmdUndbaHostLens lens = lens_of(i, cp, j, g, &bytes_in, &suffix_in);
+    brotli_amd_undba_host_c((uint64_t)(uintptr_t)segs[i].data, kept[i], lasts[g - 1u], lens.p.data(), lens.s.data(), (uint32_t)lens.p.size(), bytes_in);
+  });
+  // no byte outside every segment's offsets and bytes may have changed
+  std::vector<uint8_t> in_offsets(offsets_size, 0), in_data(data_size, 0);
+  for (uint32_t i = 0; i < n; i++) {
+    if (segs[i].offsets) std::fill(in_offsets.begin() + offsets_offs[i], in_offsets.begin() + offsets_offs[i] + slots_of(i) * brotli_amd_undlba_offset_width(segs[i].flags), 1);
+    if (segs[i].data) std::fill(in_data.begin() + data_offs[i], in_data.begin() + data_offs[i] + kept[i], 1);
+  }
+  if (!oroom.changed_inside_only([&](size_t i) { return i < offsets_size && in_offsets[i]; })) { g_last_error = "undba wrote outside its offsets"; return -2; }
+  if (!droom.changed_inside_only([&](size_t i) { return i < data_size && in_data[i]; })) { g_last_error = "undba wrote outside its data"; return -2; }
   oroom.get(offsets, 0u, offsets_size);
   droom.get(data, 0u, data_size);
   std::copy(got.begin(), got.end(), results);

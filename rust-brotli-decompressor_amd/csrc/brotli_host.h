@@ -7,7 +7,7 @@
 //   brotli_digest.cpp   CRC-32 / CRC-32C of segments of device memory and of the last decode call's outputs
 //   brotli_filters.cpp  the element filters of segments of device memory and of the last decode call's outputs: one descriptor a filter and one call;
 //                       the plain path (unshuffle, undelta, bit-unshuffle, bit-unpack), the counted path with a result per segment (unvarint,
-//                       unrle, undbp, undict), unnull's, undict-bytes' and undlba's paths of their own beside it, the host hooks
+//                       unrle, undbp, undict), unnull's, undict-bytes', undlba's and undba's paths of their own beside it, the host hooks
 #ifndef BROTLI_AMD_HOST_H_
 #define BROTLI_AMD_HOST_H_
 #include <hip/hip_runtime.h>
@@ -107,13 +107,13 @@ template <class T = uint8_t> using DevBuf = Buffer<T, Mem::Device>;
 template <class T = uint8_t> using PinBuf = Buffer<T, Mem::Pinned>;
 
 // What a call over a table of segments (run_seg_call) keeps with its batch object
-constexpr uint32_t kMaxSegEvents = 8;
+constexpr uint32_t kMaxSegEvents = 10;
 struct SegCall {
   DevBuf<> d;                         // the segment table of one call and what the call wants behind it
   hipEvent_t ev[kMaxSegEvents] = {};   // around and between its launches (made at the first call, as many as it needs)
 };
 
-enum Filter : uint32_t { kUnshuffle, kUndelta, kBitUnshuffle, kBitUnpack, kUnvarint, kUnrle, kUndbp, kUndict, kUnnull, kUndictBytes, kUndlba, kFilters };   // the element filters (brotli_filters.cpp)
+enum Filter : uint32_t { kUnshuffle, kUndelta, kBitUnshuffle, kBitUnpack, kUnvarint, kUnrle, kUndbp, kUndict, kUnnull, kUndictBytes, kUndlba, kUndba, kFilters };   // the element filters (brotli_filters.cpp)
 
 constexpr size_t kReaderSlack = 256;   // behind every buffer the kernel reads a stream's bytes from, or writes them to, up to the buffer's end
 

@@ -343,6 +343,8 @@ def outputs_as_tensors(batch, specs):
 
 BYTES_OFFSETS64, BYTES_SKIP, BYTES_ALL = 2, 8, (1 << 64) - 1   # UNDICT_BYTES_OFFSETS64, UNDICT_BYTES_SKIP, UNDICT_BYTES_ALL
 DLBA_OFFSETS64, DLBA_SKIP = 2, 8   # UNDLBA_OFFSETS64, UNDLBA_SKIP
+DBA_OFFSETS64, DBA_SKIP = 2, 8   # UNDBA_OFFSETS64, UNDBA_SKIP
+DBA_BAD_KINDS = ("no rule", "a negative prefix length", "a negative suffix length", "a prefix longer than the element in front of it")   # UndbaResult.bad_kind
 INT32_MAX = (1 << 31) - 1
 
 
@@ -361,7 +363,12 @@ def outputs_as_strings(batch, specs):
     as DELTA_BINARY_PACKED, then the bytes --: one counting call (Batch.count_dlba_outputs gives the bytes there are), the same allocation, one
     writing call (Batch.undlba_outputs).  ValueError for such a stream where the lengths do not end well, their number is not `rows` exactly
     (the encoding states it: there is no padding to forgive), a length is negative (the text names the first one), or the lengths' sum is not
-    the bytes that are there (the text says which is larger).  Both kinds may stand in one call: two pairs of library calls into one buffer."""
+    the bytes that are there (the text says which is larger).  Both kinds may stand in one call: two pairs of library calls into one buffer.
+    specs[i] may also be ("dba", rows) or ("dba", rows, "large") for a DELTA_BYTE_ARRAY page body of a required column -- prefix lengths and
+    suffix lengths as DELTA_BINARY_PACKED, then the suffix bytes --: one measuring call (Batch.measure_dba_outputs gives the bytes the strings
+    take), the same allocation, one writing call (Batch.undba_outputs).  ValueError for such a stream where either stream of lengths does not
+    end well, the two hold different numbers of lengths, their number is not `rows` exactly, an element breaks a rule (the text names the first
+    one and the rule), or the suffix lengths' sum is not the bytes that are there (the data is short, or bytes are left over)."""
     sizes = batch.out_sizes
     if sizes is None:
         raise RuntimeError("no outputs: no decode call on this batch object yet, or its launch has not been waited for")
@@ -370,6 +377,7 @@ def outputs_as_strings(batch, specs):
         raise ValueError("specs: %d entries for the %d streams of the last decode call" % (len(specs), n))
     rows, large, dict_streams, dict_ptrs, dict_lens = [None] * n, [False] * n, [DICT_NO_STREAM] * n, [None] * n, [0] * n
     dlba = {}   # the streams that are DELTA_LENGTH_BYTE_ARRAY bodies: their rows
+    dba = {}    # the streams that are DELTA_BYTE_ARRAY bodies: their rows
     for i, spec in enumerate(specs):
         if spec is None:
             continue
@@ -377,6 +385,11 @@ def outputs_as_strings(batch, specs):
             if len(spec) not in (2, 3) or (len(spec) == 3 and spec[2] != "large") or isinstance(spec[1], bool) or not isinstance(spec[1], int) or spec[1] < 0:
                 raise ValueError("stream %d: a \"dlba\" spec is (\"dlba\", rows) or (\"dlba\", rows, \"large\")" % i)
             dlba[i], large[i] = int(spec[1]), len(spec) == 3
+            continue
+        if len(spec) >= 1 and isinstance(spec[0], str) and spec[0] == "dba":
+            if len(spec) not in (2, 3) or (len(spec) == 3 and spec[2] != "large") or isinstance(spec[1], bool) or not isinstance(spec[1], int) or spec[1] < 0:
+                raise ValueError("stream %d: a \"dba\" spec is (\"dba\", rows) or (\"dba\", rows, \"large\")" % i)
+            dba[i], large[i] = int(spec[1]), len(spec) == 3
             continue
         if len(spec) not in (2, 3) or (len(spec) == 3 and spec[2] != "large") or isinstance(spec[0], bool) or not isinstance(spec[0], int) or spec[0] < 0:
             raise ValueError("stream %d: a spec is (rows, j), (rows, tensor) or either with \"large\" behind it" % i)
@@ -428,6 +441,29 @@ def outputs_as_strings(batch, specs):
                 raise ValueError("stream %d: %d bytes of strings, more than int32 offsets hold: ask for \"large\"" % (i, avail))
             rows[i], kept[i] = dlba[i], avail
         wanted = sorted(wanted + list(dlba))
+    dba_flags = [(DBA_OFFSETS64 if large[i] else 0) if i in dba else DBA_SKIP for i in range(n)]
+    if dba:   # everything is judged by the measuring call: nothing in a result depends on the data's capacity
+        measured = batch.measure_dba_outputs([max(dba[i], 1) if i in dba else None for i in range(n)], [f & ~DBA_SKIP for f in dba_flags])
+        for i in sorted(dba):
+            r = measured[i]
+            for what, (count, consumed, declared, _, status) in (("prefix", r[0:5]), ("suffix", r[8:13])):
+                if status != 0:
+                    raise ValueError("stream %d: its %s lengths: %s (status %d) after %d lengths in %d bytes, of %d declared" %
+                                     (i, what, DBP_STATUS[status] if status < len(DBP_STATUS) else "an unknown status", status, count, consumed, declared))
+            count_p, count_s, kind, first_bad, nbytes, suffix_bytes, avail = r[0], r[8], r[15], r[16], r[17], r[18], r[19]
+            if count_p != count_s:
+                raise ValueError("stream %d: %d prefix lengths and %d suffix lengths" % (i, count_p, count_s))
+            if count_p != dba[i]:
+                raise ValueError("stream %d: %d lengths in its streams, but the column has %d rows" % (i, count_p, dba[i]))
+            if dba[i] != 0 and first_bad != (1 << 64) - 1:
+                raise ValueError("stream %d: element %d of its %d has %s" % (i, first_bad, dba[i], DBA_BAD_KINDS[kind] if kind < len(DBA_BAD_KINDS) else "an unknown fault"))
+            if suffix_bytes != avail:
+                raise ValueError("stream %d: its suffix lengths add up to %d bytes and %d are there: %s" %
+                                 (i, suffix_bytes, avail, "bytes are left over" if avail > suffix_bytes else "the data is short"))
+            if nbytes > INT32_MAX and not large[i]:
+                raise ValueError("stream %d: %d bytes of strings, more than int32 offsets hold: ask for \"large\"" % (i, nbytes))
+            rows[i], kept[i] = dba[i], nbytes
+        wanted = sorted(wanted + list(dba))
     up = lambda v: (v + SLOT_ALIGN - 1) // SLOT_ALIGN * SLOT_ALIGN
     o_at, d_at, total = {}, {}, 0
     for i in wanted:
@@ -437,10 +473,10 @@ def outputs_as_strings(batch, specs):
     skip = -buf.data_ptr() % SLOT_ALIGN
     buf = buf[skip:skip + total]
     base = buf.data_ptr()
-    if len(wanted) > len(dlba):
+    if len(wanted) > len(dlba) + len(dba):
         # rows of 0: a capacity of 1 with a data capacity of 0 writes offsets[0] and offsets[1], and offsets[1]'s slot is the padding's
-        of_dict = lambda at: [base + at[i] if i in at and i not in dlba else None for i in range(n)]
-        batch.undict_bytes_outputs(of_dict(o_at), of_dict(d_at), [0 if i in dlba else kept.get(i, 0) for i in range(n)], [0 if c is None else c for c in caps], [0] * n, flags,
+        of_dict = lambda at: [base + at[i] if i in at and i not in dlba and i not in dba else None for i in range(n)]
+        batch.undict_bytes_outputs(of_dict(o_at), of_dict(d_at), [0 if i in dlba or i in dba else kept.get(i, 0) for i in range(n)], [0 if c is None else c for c in caps], [0] * n, flags,
                                    None, dict_streams, dict_ptrs, dict_lens)
     if dlba:
         # (rows of 0: the stream has no lengths, as was counted, so a capacity of 1 writes offsets[0] alone)
@@ -453,6 +489,10 @@ def outputs_as_strings(batch, specs):
             if nbytes != avail:
                 raise ValueError("stream %d: its lengths add up to %d bytes and %d are there: %s" %
                                  (i, nbytes, avail, "bytes are left over" if avail > nbytes else "the data is short"))
+    if dba:
+        # (rows of 0: the streams have no lengths, as was measured, so a capacity of 1 writes offsets[0] alone)
+        batch.undba_outputs([base + o_at[i] if i in dba else None for i in range(n)], [base + d_at[i] if i in dba else None for i in range(n)],
+                            [kept[i] if i in dba else 0 for i in range(n)], [max(dba[i], 1) if i in dba else 0 for i in range(n)], dba_flags)
     out = [None] * n
     for i in wanted:
         offsets = buf[o_at[i]:o_at[i] + (rows[i] + 1) * (8 if large[i] else 4)].view(torch.int64 if large[i] else torch.int32)
