@@ -96,6 +96,32 @@ def test_a_tile_in_three_chunks_has_a_part_for_each_chunk_with_units(pkg):
         assert first == [(0, 0, 0, units[0]), (0, 0, units[0], t)], first
 
 
+def test_a_table_beyond_2_to_the_29_units(pkg):
+    """short segments, one of 2^28 + 3 units -- 4 GiB and 48 bytes --, short segments, and one more of 2^28 + 1 units, so that the units sum
+    beyond 2^29 and the bytes beyond 2^33: the same disjoint cover as above, with tiles of 1024 units and two grids (numpy does the comparing:
+    there are more than half a million parts)"""
+    import numpy as np
+    tile_units = 1024
+    units = [1, 3, 0, 7, 2] * 20 + [(1 << 28) + 3] + [2, 0, 5, 1, 9] * 20 + [(1 << 28) + 1]
+    total = sum(units)
+    tiles = (total + tile_units - 1) // tile_units
+    assert len(units) < CHUNK and sum(units[:101]) > 1 << 28 and total > 1 << 29
+    sets = []
+    for grid in (7, tiles + 3):
+        p = np.array(pkg.seg_walk_parts(units, tile_units, grid), dtype=np.uint64)
+        for b in (0, 3, grid - 1):   # a block takes its tiles in rising order, a tile's parts in rising order
+            mine = p[p[:, 0] == b]
+            assert np.array_equal(mine, mine[np.lexsort((mine[:, 2], mine[:, 1]))]), (grid, b)
+        p = p[np.argsort(p[:, 2], kind="stable")]
+        block, tile, lo, hi = p[:, 0], p[:, 1], p[:, 2], p[:, 3]
+        assert lo[0] == 0 and hi[-1] == total and np.array_equal(lo[1:], hi[:-1]) and (lo < hi).all(), grid   # disjoint, no unit left out
+        assert (tile * tile_units <= lo).all() and (hi <= (tile + 1) * tile_units).all(), grid
+        assert np.array_equal(block, tile % grid), grid
+        assert len(p) >= tiles and int(tile[-1]) == tiles - 1
+        sets.append(p[:, 1:])
+    assert np.array_equal(sets[0], sets[1])
+
+
 def test_the_walk_under_sanitizers(tmp_path):
     """tests/tools/seg_walk_san.cpp: the same enumeration over the same tables under ASan and UBSan, as a program of its own"""
     r = san_program.run("seg_walk_san", tmp_path)
